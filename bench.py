@@ -1,17 +1,23 @@
 """Headline benchmark: training patches/sec of the ResUnet-a multitask path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one rank per
 GPU, what the driver does), or started plainly - then THIS process, which has made no GPU call, starts exactly that
 launcher as a child process (never exec), relays rank 0's JSON line and exits with the child's status
-(/root/reference/train_ISPRS.py:347,432: MirroredStrategy over the node's GPUs).
+(reference train_ISPRS.py:347,432: MirroredStrategy over the node's GPUs).
 
 A step = one full train_on_batch on one resident synthetic batch per GPU: forward (training-mode BN),
 Tanimoto-dual losses on the four heads, backward, gradient all-reduce (N>1), Adam update, bf16 weight
 refresh.  Default workload = BASELINE config 3 (256x256x6, 6 classes, multitask, bs 8/GPU, bf16).
-Prints ONE JSON line (rank 0) with the bench contract fields plus `roofline` (dominant kernel, timed
-live with events on the launch stream) and `cpu_baseline` (the CPU oracle timed on the host cores).
+
+A plain run sets up, warms up (W steps, the first of which records the plan and captures the step), times K steps
+(--blocks B: B blocks of K steps, the median block reported), writes the last timed step's outputs if --dump-outputs is
+given (that step then starts from the initial training state, so every run dumps the same computation), and prints ONE
+JSON line (rank 0) with the bench contract fields.  --full adds everything else the line can carry,
+each measured after the timed steps: `roofline` (per-kernel and per-block HIP-event timing in instrumented steps, the
+d6 ceiling probe, the dispatch count), `dp` (data-parallel diagnostics), `also` (short runs of the other BASELINE
+configurations, N = 1) and `cpu_baseline` (the CPU oracle timed on the host cores, N = 1).
 """
 import argparse
 import ctypes as C
@@ -438,6 +444,52 @@ def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
 
+class TrainState:
+    """Device copies of everything a training step reads and then updates - fp32 parameters, BatchNorm moving statistics,
+    the optimizer's moments and its step counter.  Training on the one resident batch turns the run-to-run noise of the
+    floating-point atomics (statistics, loss sums, weight-gradient reductions) into differences that grow with every step;
+    the step that --dump-outputs writes starts from this state instead, so two runs dump the same computation."""
+
+    def __init__(self, eng):
+        self.tensors = {k: getattr(eng, k).clone() for k in ("P", "S", "M1", "V1")}
+        self.t, self.t_dev, self.lr_base_dev = eng.t, eng._t_dev, eng._lr_base_dev
+
+    def restore(self, eng):
+        torch.cuda.synchronize()
+        for k, v in self.tensors.items():
+            getattr(eng, k).copy_(v)
+        eng.t, eng._t_dev, eng._lr_base_dev = self.t, self.t_dev, self.lr_base_dev    # the next step pushes its counter again
+        eng.params_changed()                                    # both bf16 weight copies are rebuilt from P before the replay
+        torch.cuda.synchronize()
+
+
+DUMP_MAX_ELEMS = 1 << 21             # per array (8 MB as float32): six large arrays at most, so a dump stays under 64 MB
+
+
+def dump_outputs(eng, B, res, out_dir):
+    """What the timed path computed in its last step, as a caller of train_step receives it: the metric list (float64),
+    every head's output (the probabilities the losses were taken on) and the state the step left - the fp32 parameters
+    after the optimizer update and the BatchNorm moving statistics (float32).  An array above DUMP_MAX_ELEMS elements is
+    written as a fixed, seeded sample of its flattened elements (the same indices in every run of the same workload).
+    Inputs and initial weights are the same in every run, and the dumped step starts from the initial training state
+    (TrainState), so two runs differ by the rounding of one step."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrs = {"metrics": np.asarray(res, dtype=np.float64)}
+    for h in eng.graph(B, True).heads:
+        arrs["head_" + h["name"]] = h["p"].t.float().cpu().numpy()
+    arrs["params"] = eng.P.float().cpu().numpy()
+    arrs["bn_state"] = eng.S.float().cpu().numpy()
+    total = 0
+    for i, (name, a) in enumerate(sorted(arrs.items())):
+        if a.size > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng(1000 + i)
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    log(f"outputs of the last timed step: {len(arrs)} arrays, {total / 2**20:.1f} MiB in {out_dir}")
+
+
 def cpu_baseline(sample_steps=6):
     """CPU oracle (PyTorch-CPU fp32 restatement of the Keras graph) on BASELINE config 1:
     256x256x3, 6 classes, single task, bs 4, weighted CE, Adam - full train steps on all host cores.
@@ -557,9 +609,14 @@ def main():
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS))
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the workload's)")
-    ap.add_argument("--blocks", type=int, default=3, help="timed blocks of --steps steps each; the median block is reported (SURVEY 8d)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the short runs of the other BASELINE configurations (N = 1 line)")
+    ap.add_argument("--blocks", type=int, default=1, help="timed blocks of --steps steps each; the median block is reported (SURVEY 8d: 3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (metrics, head outputs, updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure roofline / per-kernel timing, data-parallel diagnostics, the other BASELINE "
+                         "configurations and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the short runs of the other BASELINE configurations (N = 1 line)")
     ap.add_argument("--also-steps", type=int, default=10)
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--bucket-mb", type=float, default=50.0)
@@ -589,6 +646,7 @@ def main():
     eng, x, y, B, depth = build_engine(args.workload, args.dtype, args.batch, rank, world, args)
     if os.environ.get("RUA_LANES"):                             # experiment: ResBlock branches on parallel graph branches
         eng.use_lanes = True
+    snap = TrainState(eng) if args.dump_outputs else None      # the state the first step starts from (the dumped step starts from it too)
     t_build = time.time()
     eng.train_step(x, y, fetch=False)                           # builds the plan, uploads the resident batch
     torch.cuda.synchronize()
@@ -607,21 +665,29 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # SURVEY 8d protocol: 10 warm-up steps, then 3 timed blocks of >= 50 steps, each bracketed by barrier + device
-    # synchronise on both sides and taken as the MAX over ranks; the MEDIAN block is the reported one.
-    if eng.dist is not None:
+    # --steps timed steps, bracketed by barrier + device synchronise on both sides and taken as the MAX over ranks.  SURVEY 8d
+    # protocol: --warmup 10 --blocks 3 --steps 50 (or more) - three such blocks, the MEDIAN block is the reported one.
+    if eng.dist is not None and args.full:
         eng.dist.reducer.measure = True                         # event pairs around the wait for the buckets (dp.allreduce_exposed_ms)
     block_dt = []
     own_dt = []                                                 # this rank's own block times (dp.ms_per_step_per_rank)
     host_issue = 0.0                                            # host time spent INSIDE train_step (issue only: nothing in it waits for the GPU)
-    for _ in range(max(args.blocks, 1)):
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            eng.train_step(None, None, fetch=False)
-        host_issue += time.perf_counter() - t0
-        fence()
-        dt = time.perf_counter() - t0
+    nblocks = max(args.blocks, 1)
+    for bi in range(nblocks):
+        # --dump-outputs: the block's last step is timed on its own, after the training state is put back to the initial one
+        # (outside the clock), so the dumped step is the same computation in every run (TrainState)
+        parts = [args.steps - 1, 1] if (snap is not None and bi == nblocks - 1) else [args.steps]
+        dt = 0.0
+        for pi, n in enumerate(parts):
+            if pi == 1:
+                snap.restore(eng)
+            fence()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                eng.train_step(None, None, fetch=False)
+            host_issue += time.perf_counter() - t0
+            fence()
+            dt += time.perf_counter() - t0
         own_dt.append(dt)
         if world > 1:
             t = torch.tensor([dt], dtype=torch.float64, device="cuda")
@@ -652,6 +718,19 @@ def main():
         "step_path": ("hip-graph (whole step)" if (eng.use_graph and eng.dist is None) else
                       ("hip-graph pieces + eager collectives" if (eng.use_graph and eng.dp_graph) else "eager launches + bucketed all-reduce overlapped with backward")),
     }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, B, res, args.dump_outputs)
+    if not args.full:                                           # a plain run: the headline figure and nothing else
+        finish()
+        return
     if eng.dist is not None:
         # data-parallel diagnostics, so that the first multi-GPU record explains itself: ranks counted BY the communicator, bucket
         # sizes, the all-reduce time the backward did not hide (events around the launch stream's wait), every rank's own step time
@@ -777,11 +856,7 @@ def main():
             out["also"] = also
         if not args.no_cpu_baseline:                            # the CPU oracle is timed at N=1 only (the other ranks would idle)
             out["cpu_baseline"] = cpu_baseline()
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -267,4 +267,8 @@ def test_fullsize_goldens_match_the_live_oracle(name):
     for k in gold.files:
         a, b = np.asarray(gold[k], np.float64), np.asarray(live[k], np.float64)
         scale = max(1.0, float(np.abs(a).max()))
-        assert a.shape == b.shape and np.abs(a - b).max() <= 1e-5 * scale, (k, float(np.abs(a - b).max()), scale)
+        # a checksum's rounding depends on the host's float32 kernels: the tolerance of <head>_sum also admits the float32 unit
+        # roundoff of the summed magnitudes (<head>_sumabs), else a sum that cancels to ~0 (color_logits_sum: -0.037 of 1.9e6)
+        # would be held to 1e-5 absolute
+        slack = 2.0 ** -23 * float(gold[k[:-len("_sum")] + "_sumabs"]) if k.endswith("_sum") else 0.0
+        assert a.shape == b.shape and np.abs(a - b).max() <= 1e-5 * scale + slack, (k, float(np.abs(a - b).max()), scale, slack)

@@ -1,6 +1,6 @@
 #!/bin/bash
 for v in ${1:-1 3 1 3}; do
-  RUA_TUNE_WGRAD_ROWS=$v timeout -k 10 200 python bench.py --no-cpu-baseline --no-also --steps 60 --warmup 15 2>/dev/null > /tmp/l.json
+  RUA_TUNE_WGRAD_ROWS=$v timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-also --steps 60 --warmup 15 2>/dev/null > /tmp/l.json
   python - $v <<'PY'
 import json,sys
 j=json.loads(open('/tmp/l.json').read().strip().splitlines()[-1])
