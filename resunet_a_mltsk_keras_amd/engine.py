@@ -237,80 +237,31 @@ class _Dummy:
 
 
 class Plan:
-    """Recorded launches.  Entries carry a lane: lane 0 is the caller's stream, lanes 1..3 are engine-owned side
-    streams used for the independent branches of a ResBlock (fork / join markers become event dependencies, which a
-    HIP-graph capture turns into parallel graph branches)."""
-    FORK, JOIN = "fork", "join"
+    """Recorded launches, replayed in order on one stream.  calls[i] = (fn, name, args, grads): grads are the offsets of the
+    parameters whose gradient that launch writes (in the flat buffer: Engine._bucket_marks fires an all-reduce bucket after the
+    last launch that names one of its parameters)."""
 
     def __init__(self, dry=False):
         self.calls: List[tuple] = []
         self.keep: List[object] = []
         self.dry = dry
-        self.lane = 0
-        self.open_fork = 0
         self.scope: Optional[str] = None     # composite the next launches belong to (per-block timing in bench.py)
         self.scopes: List[Optional[str]] = []  # scope of calls[i]
 
-    def add(self, name: str, *args):
+    def add(self, name: str, *args, grads=()):
         if not self.dry:
-            self.calls.append((L.lib().raw(name), name, args, self.lane))
+            self.calls.append((L.lib().raw(name), name, args, tuple(grads)))
             self.scopes.append(self.scope)
 
-    def fork(self, n: int):
-        if not self.dry and n > 1:
-            self.calls.append((None, Plan.FORK, n, 0))
-            self.scopes.append(self.scope)
-        self.open_fork = n
-
-    def join(self, n: int):
-        self.lane = 0
-        if not self.dry and n > 1:
-            self.calls.append((None, Plan.JOIN, n, 0))
-            self.scopes.append(self.scope)
-        self.open_fork = 0
-
-    def set_lane(self, lane: int):
-        self.lane = lane
-
-    def safe_hook_index(self, idx: int) -> int:
-        """First call index >= idx after which no side lane is running (where a 'gradients so far are final' hook may fire)."""
-        depth, out = 0, None
-        for i, c in enumerate(self.calls):
-            if c[1] == Plan.FORK:
-                depth += 1
-            elif c[1] == Plan.JOIN:
-                depth -= 1
-            if i >= idx and depth == 0:
-                return i
-        return len(self.calls) - 1
-
-    def run(self, stream_ptr: int, hooks=None, side=None, first=0, last=None):
-        """Replay calls [first, last).  side: torch streams for lanes 1..; None => everything on the caller's stream.
-        hooks: {call index -> python callable run right after that launch} (gradient buckets)."""
+    def run(self, stream_ptr: int, hooks=None, first=0, last=None):
+        """Replay calls [first, last).  hooks: {call index -> python callable run right after that launch} (gradient buckets)."""
         lib = L.lib()
-        ptrs = [C.c_void_p(stream_ptr)]
-        main = None
-        if side is not None:
-            main = torch.cuda.current_stream()
-            ptrs += [C.c_void_p(st.cuda_stream) for st in side]
+        s = C.c_void_p(stream_ptr)
         calls = self.calls if (first == 0 and last is None) else self.calls[first:last]
-        for i, (fn, name, args, lane) in enumerate(calls, start=first):
-            if fn is None:
-                if side is not None:
-                    if name == Plan.FORK:
-                        ev = torch.cuda.Event()
-                        ev.record(main)
-                        for l in range(1, args):
-                            side[l - 1].wait_event(ev)
-                    else:
-                        for l in range(1, args):
-                            ev = torch.cuda.Event()
-                            ev.record(side[l - 1])
-                            main.wait_event(ev)
-            else:
-                rc = fn(*args, ptrs[lane if side is not None else 0])
-                if rc != 0:
-                    lib.check(rc, name)
+        for i, (fn, name, args, _) in enumerate(calls, start=first):
+            rc = fn(*args, s)
+            if rc != 0:
+                lib.check(rc, name)
             if hooks:
                 h = hooks.get(i)
                 if h is not None:
@@ -367,8 +318,6 @@ class Graph:
         self.loss_plan = Plan(dry)
         self.back_steps: List = _BackSteps(self)
         self.cur_tag: Optional[str] = None      # composite being recorded (stem, down, PSP, combine, heads): per-composite timing in bench.py
-        self.grad_touch: Dict[int, int] = {}
-        self.cur_lane = 0
         self.block_tag = ""
         self.pending: List[tuple] = []          # deferred weight-gradient reductions (record, dW offset)
         self.pending_bytes = 0                  # ... and the bytes of partials they will read (Engine.flush_bytes)
@@ -425,11 +374,8 @@ class Graph:
     def P(self, off):   # pointer into the flat fp32 parameter buffer
         return 0 if self.dry else self.e.P.data_ptr() + off * 4
 
-    def G(self, off):
-        if self.dry:
-            return 0
-        self.grad_touch[off] = len(self.bwd.calls)          # index of the launch about to be recorded
-        return self.e.G.data_ptr() + off * 4
+    def G(self, off):   # pointer into the flat fp32 gradient buffer (the launch that writes there names `off`: Plan.add(grads=))
+        return 0 if self.dry else self.e.G.data_ptr() + off * 4
 
     def S(self, off):
         return 0 if self.dry else self.e.S.data_ptr() + off * 4
@@ -489,32 +435,20 @@ class Graph:
         if defer is not None:                                # the caller issues several as one rua_bn_fwd_group
             defer.append(d)
             return outs, coefs
-        plan.keep.append(d)
-        plan.add("rua_bn_fwd", C.byref(d))
+        self.issue(plan, [d], "rua_bn_fwd")
         return outs, coefs
 
-    def issue_bn_fwd(self, plan: Plan, ds: List):
-        """The deferred rua_bn_fwd descriptors `ds` as one rua_bn_fwd_group launch."""
-        if len(ds) == 1:
-            plan.keep.append(ds[0])
-            plan.add("rua_bn_fwd", C.byref(ds[0]))
-        elif ds:
-            arr = (L.BnFwdDesc * len(ds))()
-            for i, d in enumerate(ds):
-                C.memmove(C.byref(arr, i * C.sizeof(L.BnFwdDesc)), C.byref(d), C.sizeof(L.BnFwdDesc))
+    def issue(self, plan: Plan, descs: List, one: str, group: Optional[str] = None):
+        """Descriptors of one type as ONE launch: `one` on the descriptor itself, or `group` over a packed copy of them all.  The launch
+        names the gradients its descriptors write (the `grads` that wgrad_desc / bn_bwd give them)."""
+        grads = [o for d in descs for o in getattr(d, "grads", ())]
+        if len(descs) == 1:
+            plan.keep.append(descs[0])
+            plan.add(one, C.byref(descs[0]), grads=grads)
+        elif descs:
+            arr = (type(descs[0]) * len(descs))(*descs)
             plan.keep.append(arr)
-            plan.add("rua_bn_fwd_group", arr, len(ds))
-
-    def issue_bn_bwd(self, plan: Plan, ds: List):
-        if len(ds) == 1:
-            plan.keep.append(ds[0])
-            plan.add("rua_bn_bwd", C.byref(ds[0]))
-        elif ds:
-            arr = (L.BnBwdDesc * len(ds))()
-            for i, d in enumerate(ds):
-                C.memmove(C.byref(arr, i * C.sizeof(L.BnBwdDesc)), C.byref(d), C.sizeof(L.BnBwdDesc))
-            plan.keep.append(arr)
-            plan.add("rua_bn_bwd_group", arr, len(ds))
+            plan.add(group, arr, len(descs), grads=grads)
 
     def bn_fwd_group(self, plan: Plan, items: List[tuple], relu: bool, count):
         """[relu](BN(x_i)) for several tensors of equal shape, each with its own BatchNorm and statistics, as ONE launch: items = (x, bn, stats);
@@ -523,7 +457,7 @@ class Graph:
         for x, bn, st in items:
             o, c = self.bn_fwd(plan, x, [bn], relu, st, count, defer=ds)
             outs.append(o[0]); coefs.append(c[0])
-        self.issue_bn_fwd(plan, ds)
+        self.issue(plan, ds, "rua_bn_fwd", "rua_bn_fwd_group")
         return outs, coefs
 
     def bn_coefs(self, plan: Plan, like: Ten, bns: List[dict], stats: List[Optional[Stat]], count, bessel=None) -> List[Coef]:
@@ -560,6 +494,7 @@ class Graph:
             b.stats2_out = 1 if (stats2_out and stats2_out[i]) else 0
             b.gamma, b.mean, b.rstd, b.scale, b.shift = self.P(bn["gamma"]), c.mean, c.rstd, c.scale, c.shift
             b.dgamma, b.dbeta = self.G(bn["gamma"]), self.G(bn["beta"])
+        d.grads = [o for bn in bns for o in (bn["gamma"], bn["beta"])]
         st = None
         cg = x.C // self.vec
         if skip_bias and dskip is not None and not (cg <= 256 and 256 % cg == 0):
@@ -589,8 +524,7 @@ class Graph:
             sx = self.stat(x.C, blocks, burst=True)
             d.dx_stats, d.dx_replicas = sx.ptr, sx.R
             x.bias_done = True
-        plan.keep.append(d)
-        plan.add("rua_bn_bwd", C.byref(d))
+        self.issue(plan, [d], "rua_bn_bwd")
         if st is not None:
             self.stats_to_grads(plan, st, x.C, skip_bias)
         if sx is not None:
@@ -602,7 +536,7 @@ class Graph:
         ds: List = []
         for g, c, bn, s2, x, out, cnt in items:
             self.bn_bwd(plan, [g], [c], [bn], [s2], x, out, 0, cnt, defer=ds)
-        self.issue_bn_bwd(plan, ds)
+        self.issue(plan, ds, "rua_bn_bwd", "rua_bn_bwd_group")
 
     def conv(self, plan: Plan, segs, layer_segs, cout, bias_ptr, out: Ten, stride=1, residual: Optional[Ten] = None,
              out_relu=False, stats=None, bias_more=(), in_bn: Optional["Coef"] = None, accumulate: int = 0, in_fold=None):
@@ -664,7 +598,7 @@ class Graph:
         w = L.WgradDesc()
         w.a, w.C, w.Hs, w.Ws, w.dy, w.Cout, w.H, w.W = x.ptr, x.C, x.H, x.W, x.ptr, nf, x.H, x.W
         w.N, w.stride, w.dil, w.taps, w.dtype = x.N, 1, dil, 9, self.dt
-        sc = self.e.scratches[0]
+        sc = self.e.scratch
         w.workspace, w.workspace_bytes = sc.data_ptr(), sc.numel() * 4
         lib = L.lib()
         return lib.raw("rua_conv_fused_input_ok")(C.byref(d)) == 1 and lib.raw("rua_wgrad_kind")(C.byref(w)) == 1
@@ -672,8 +606,7 @@ class Graph:
     def _ws(self, d):
         """Shared split-K scratch (launches are serialised on one stream, so one buffer serves every conv)."""
         if not self.dry and self.e.split_k and d.N * d.H * d.W * d.Cout * 4 <= self.e.workspace.numel() * 4:
-            w = self.e.workspaces[self.cur_lane]
-            d.workspace, d.workspace_bytes = w.data_ptr(), w.numel() * 4
+            d.workspace, d.workspace_bytes = self.e.workspace.data_ptr(), self.e.workspace.numel() * 4
 
     def dgrad(self, plan: Plan, dy: Ten, wd_ptr, cin: int, dil: int, taps: int, out: Ten, accumulate: int,
               mask: Optional[Tuple[Ten, Optional[int], Optional[int]]] = None, stats2: Optional[int] = None,
@@ -685,31 +618,15 @@ class Graph:
 
     def conv_group(self, plan: Plan, descs: List):
         """Independent convolutions (the dilation branches of a ResBlock) in one call: members on the same kernel share ONE grid."""
-        if len(descs) == 1:
-            plan.keep.append(descs[0])
-            plan.add("rua_conv_fwd", C.byref(descs[0]))
-            return
         if len(descs) > L.RUA_MAX_BRANCH:                      # (the five sources of a PSPPooling fuse conv: the library takes RUA_MAX_BRANCH members per call)
             self.conv_group(plan, descs[:L.RUA_MAX_BRANCH])
             self.conv_group(plan, descs[L.RUA_MAX_BRANCH:])
             return
-        arr = (L.ConvDesc * len(descs))()
-        for i, dsc in enumerate(descs):
-            C.memmove(C.byref(arr, i * C.sizeof(L.ConvDesc)), C.byref(dsc), C.sizeof(L.ConvDesc))
-        plan.keep.append(arr)
-        plan.add("rua_conv_fwd_group", arr, len(descs))
+        self.issue(plan, descs, "rua_conv_fwd", "rua_conv_fwd_group")
 
     def conv_sum(self, plan: Plan, descs: List):
         """Convolutions into ONE output, summed (member 0 writes, the others accumulate): rua_conv_fwd_sum."""
-        if len(descs) == 1:
-            plan.keep.append(descs[0])
-            plan.add("rua_conv_fwd", C.byref(descs[0]))
-            return
-        arr = (L.ConvDesc * len(descs))()
-        for i, dsc in enumerate(descs):
-            C.memmove(C.byref(arr, i * C.sizeof(L.ConvDesc)), C.byref(dsc), C.sizeof(L.ConvDesc))
-        plan.keep.append(arr)
-        plan.add("rua_conv_fwd_sum", arr, len(descs))
+        self.issue(plan, descs, "rua_conv_fwd", "rua_conv_fwd_sum")
 
     def dgrad_desc(self, dy: Ten, wd_ptr, cin: int, dil: int, taps: int, out: Ten, accumulate: int, mask=None, stats2=None,
                    stat_aux=None, out_stride: int = 1):
@@ -741,23 +658,20 @@ class Graph:
         if not self.dry and self.e.wgrad_overwrite:
             d.overwrite_dev = self.e.ow_flag.data_ptr()    # whole steps store dW instead of adding to the zeroed arena (Engine._set_overwrite)
         defer = (not self.dry) and self.e.defer_reduce and plan is self.bwd and defer_ok
-        if defer and may_flush:                             # before G(): a flush is a launch of its own and must not count as this one
+        if defer and may_flush:
             bucket = self.e.dist.bucket_of(dw_off) if self.e.dist is not None else 0
             if self.pending and (bucket != self.pending_bucket or self.pending_bytes > self.e.flush_bytes):
                 self.flush_wgrad(plan)
             self.pending_bucket = bucket
-        d.dw = self.G(dw_off)
+        d.dw, d.grads = self.G(dw_off), (dw_off,)
         if not self.dry:
-            sc = self.e.scratches[self.cur_lane]
-            d.workspace, d.workspace_bytes = sc.data_ptr(), sc.numel() * 4
+            d.workspace, d.workspace_bytes = self.e.scratch.data_ptr(), self.e.scratch.numel() * 4
             if defer:
                 self._defer_wgrad(plan, d, dw_off)
         return d
 
     def wgrad(self, plan: Plan, a: Ten, dy: Ten, dw_off: int, stride: int, dil: int, taps: int, in_bn: Optional["Coef"] = None):
-        d = self.wgrad_desc(plan, a, dy, dw_off, stride, dil, taps, in_bn)
-        plan.keep.append(d)
-        plan.add("rua_conv_wgrad", C.byref(d))
+        self.issue(plan, [self.wgrad_desc(plan, a, dy, dw_off, stride, dil, taps, in_bn)], "rua_conv_wgrad")
 
     def wgrad_group(self, plan: Plan, specs: List[tuple]):
         """Independent weight gradients (the dilation branches of a ResBlock) in one call: members on the same kernel share ONE
@@ -772,11 +686,7 @@ class Graph:
             self.wgrad_group(plan, specs[L.RUA_MAX_WGRAD_GROUP:])
             return
         descs = [self.wgrad_desc(plan, *sp, may_flush=(i == 0), group=len(specs)) for i, sp in enumerate(specs)]
-        arr = (L.WgradDesc * len(descs))()
-        for i, dsc in enumerate(descs):
-            C.memmove(C.byref(arr, i * C.sizeof(L.WgradDesc)), C.byref(dsc), C.sizeof(L.WgradDesc))
-        plan.keep.append(arr)
-        plan.add("rua_conv_wgrad_group", arr, len(descs))
+        self.issue(plan, descs, "rua_conv_wgrad", "rua_conv_wgrad_group")
 
     def wgrad_now_or_later(self, plan: Plan, specs: List[tuple]) -> List[tuple]:
         """The weight gradients of a ResBlock's SECOND convolutions: issued here - or returned, to ride in ONE group with the first convolutions' (whose
@@ -803,8 +713,7 @@ class Graph:
         descs = [self.wgrad_desc(plan, *sp, may_flush=(i == 0)) for i, sp in enumerate(specs)]
         if not all(lib.raw("rua_wgrad_kind")(C.byref(d)) == 3 for d in descs):
             for d in descs:                                    # (descriptors are already recorded for the deferred reductions: launch exactly these)
-                plan.keep.append(d)
-                plan.add("rua_conv_wgrad", C.byref(d))
+                self.issue(plan, [d], "rua_conv_wgrad")
             return
         for d in descs:
             if d.defer:                                        # block partials, summed by the next rua_wgrad_reduce_batch: _defer_wgrad gave it a private workspace
@@ -812,11 +721,7 @@ class Graph:
             nbytes = int(lib.raw("rua_wgrad_workspace_bytes")(C.byref(d)))
             ws = self.alloc(((nbytes + 3) // 4,), torch.float32, zero=True)
             d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        arr = (L.WgradDesc * len(descs))()
-        for i, dsc in enumerate(descs):
-            C.memmove(C.byref(arr, i * C.sizeof(L.WgradDesc)), C.byref(dsc), C.sizeof(L.WgradDesc))
-        plan.keep.append(arr)
-        plan.add("rua_conv_wgrad_group", arr, len(descs))
+        self.issue(plan, descs, "rua_conv_wgrad", "rua_conv_wgrad_group")
 
     # -- deferred weight-gradient reductions: the partial sums of many weight gradients (all-taps block partials, K-slice slabs)
     #    are added into dW by ONE batched launch instead of one small launch each (80 of them per cfg3 step).  Under data
@@ -843,16 +748,14 @@ class Graph:
         self.pending_bytes = 0
         if not self.pending:
             return
-        recs = (L.WgradPending * len(self.pending))()
         blocks = 0
-        for i, (r, off) in enumerate(self.pending):
+        for r, _ in self.pending:
             r.block_begin = blocks
             blocks += r.blocks
-            C.memmove(C.byref(recs, i * C.sizeof(L.WgradPending)), C.byref(r), C.sizeof(L.WgradPending))
-            self.grad_touch[off] = len(plan.calls)                     # this launch makes the gradient final
+        recs = (L.WgradPending * len(self.pending))(*[r for r, _ in self.pending])
         table = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(self.dev)
         self.allocs.append(table)
-        plan.add("rua_wgrad_reduce_batch", table.data_ptr(), len(self.pending), blocks)
+        plan.add("rua_wgrad_reduce_batch", table.data_ptr(), len(self.pending), blocks, grads=[off for _, off in self.pending])
         self.pending = []
 
     def bias_grad(self, plan: Plan, dy: Ten, bias_offs: List[int]):
@@ -865,7 +768,7 @@ class Graph:
         if self.dry or not (self.e.defer_reduce and plan is self.bwd):
             dst = L.ptr_array([self.G(o) for o in offs])
             plan.keep.append(dst)
-            plan.add("rua_stats_to_f32", s.ptr, s.R, Cc, dst, len(offs))
+            plan.add("rua_stats_to_f32", s.ptr, s.R, Cc, dst, len(offs), grads=offs)
             return
         for o in offs:
             bucket = self.e.dist.bucket_of(o) if self.e.dist is not None else 0
@@ -878,7 +781,7 @@ class Graph:
 
     def bn_bwd_finalize(self, plan: Plan, stats2, count, bn, coef: Coef):
         plan.add("rua_bn_bwd_finalize", stats2.ptr, stats2.R, float(count), self.P(bn["gamma"]), coef.mean, coef.rstd,
-                 self.G(bn["gamma"]), self.G(bn["beta"]), coef.A, coef.B, coef.Cc, bn["C"])
+                 self.G(bn["gamma"]), self.G(bn["beta"]), coef.A, coef.B, coef.Cc, bn["C"], grads=(bn["gamma"], bn["beta"]))
 
     def bn_bwd_apply(self, plan: Plan, gs: List[Ten], coefs: List[Coef], x: Ten, out: Ten, accumulate: int,
                      dskip: Optional[Ten] = None, masked=False):
@@ -978,7 +881,7 @@ class Graph:
         lib = L.lib()
         arr = (L.ConvDesc * len(dils))()
         dummy = L.BnFold()
-        outs = [self.e.scratches[0].data_ptr() + 4096 * (i + 1) for i in range(len(dils))]       # distinct, never dereferenced
+        outs = [self.e.scratch.data_ptr() + 4096 * (i + 1) for i in range(len(dils))]       # distinct, never dereferenced
         for bi, d in enumerate(dils):
             q = arr[bi]
             q.nseg = 1
@@ -997,7 +900,7 @@ class Graph:
         w = L.WgradDesc()
         w.a, w.C, w.Hs, w.Ws, w.dy, w.Cout, w.H, w.W = x.ptr, x.C, x.H, x.W, x.ptr, nf, x.H, x.W
         w.N, w.stride, w.taps, w.dtype = x.N, 1, 9, self.dt
-        sc = self.e.scratches[0]
+        sc = self.e.scratch
         w.workspace, w.workspace_bytes = sc.data_ptr(), sc.numel() * 4
         for d in dils:
             w.dil = d
@@ -1028,7 +931,7 @@ class Graph:
         w = L.WgradDesc()
         w.a, w.C, w.Hs, w.Ws, w.dy, w.Cout, w.H, w.W = x.ptr, x.C, x.H, x.W, x.ptr, nf, x.H, x.W
         w.N, w.stride, w.taps, w.dtype = x.N, 1, 9, self.dt
-        sc = self.e.scratches[0]
+        sc = self.e.scratch
         w.workspace, w.workspace_bytes = sc.data_ptr(), sc.numel() * 4
         for d in dils:
             w.dil = d
@@ -1252,7 +1155,7 @@ class Graph:
             for k, p, z, lay, bn in zs:
                 zb, node = self.bn_node(z, bn, False, count=z.M, bessel=z.M * k * k, stats=z.stats, defer=bds)
                 br.append((k, p, z, lay, zb, node))
-            self.issue_bn_fwd(F, bds)
+            self.issue(F, bds, "rua_bn_fwd", "rua_bn_fwd_group")
         segs = [(b[4], int(math.log2(b[0]))) for b in br] + [(x, 0)]
         zf, layf = self.conv1x1_multi(segs, nf, (x.H, x.W))
         bnf = self.Lbn(nf)
@@ -1267,7 +1170,7 @@ class Graph:
                 if bbs is not None:                                # every zb.grad is there: the four BatchNorm backwards as one launch
                     for b_ in br:
                         b_[5]["back"](defer=bbs)
-                    self.issue_bn_bwd(Bp, bbs)
+                    self.issue(Bp, bbs, "rua_bn_bwd", "rua_bn_bwd_group")
                 if bbs is not None and pyramid and bdescs is not None:
                     # the branch convolutions' data gradients as one group (independent: own source gradients)
                     self.wgrad_pw_group(Bp, [(p, z.grad, lay["segs"][0]["off"], 1, 1, 1) for (k, p, z, lay, zb, node) in br])
@@ -1569,13 +1472,14 @@ class Graph:
             hx = h["x"]
             gx, acc = self.gacc(hx, masked=hx.relu_out)
             lay = h["lay"]
-            dxsum = None
+            dxsum, grads = None, [lay["segs"][0]["off"], lay["bias"]]
             if hx.bias_offs and hx.relu_out and not acc and not self.dry and self.e.bn_dx_bias:
                 dxsum = self.G(hx.bias_offs[0])            # the head's backward sums the masked gradient it writes: the bias gradient of the conv behind hx
+                grads.append(hx.bias_offs[0])
                 hx.bias_done = True
             Bp.add("rua_head_bwd_sums", hx.ptr, dz.ptr, self.P(lay["segs"][0]["off"]), gx.ptr, acc, self.G(lay["segs"][0]["off"]),
                    self.G(lay["bias"]), dxsum, self.e.scratch.data_ptr(), self.e.scratch.numel() * 4, M, hx.C, Cc, self.dt,
-                   1 if hx.relu_out else 0)
+                   1 if hx.relu_out else 0, grads=grads)
         self.back_steps.append(back)
 
     # -- whole network ---------------------------------------------------------------------------------
@@ -1622,13 +1526,13 @@ class Graph:
                 if pack:
                     tmp = self.alloc((w0 * 16,), torch.float32, zero=True)          # [Cout][16]: zero before every launch (the fold leaves it so)
                     d = self.wgrad_desc(Bp, xpack, c1.grad, stem["segs"][0]["off"], 1, 1, 1, defer_ok=False)      # the fold reads tmp right behind the call: its partials are summed by the call itself
-                    d.dw = tmp.data_ptr()
-                    Bp.keep.append(d)
-                    Bp.add("rua_conv_wgrad", C.byref(d))
-                    Bp.add("rua_stem_bwd_fold", tmp.data_ptr(), self.G(stem["segs"][0]["off"]), self.G(stem["bias"]), Cin, w0)
+                    d.dw, d.grads = tmp.data_ptr(), ()
+                    self.issue(Bp, [d], "rua_conv_wgrad")
+                    Bp.add("rua_stem_bwd_fold", tmp.data_ptr(), self.G(stem["segs"][0]["off"]), self.G(stem["bias"]), Cin, w0,
+                           grads=(stem["segs"][0]["off"], stem["bias"]))
                 else:
                     Bp.add("rua_stem_bwd", self.x_in.ptr, c1.grad.ptr, self.G(stem["segs"][0]["off"]), self.G(stem["bias"]),
-                           c1.M, Cin, w0, self.dt)
+                           c1.M, Cin, w0, self.dt, grads=(stem["segs"][0]["off"], stem["bias"]))
             self.back_steps.append(stem_back)
         self.cur_tag, F.scope = None, None
         x = c1
@@ -1771,12 +1675,10 @@ class Engine:
         self.wprep_map = torch.tensor(bm if bm else [0, 0], dtype=torch.int32, device=self.dev)
         self.wprep_map_n = len(bm) // 2
         self.stats_arena = torch.zeros(1 << 22, dtype=torch.float64, device=self.dev)
-        # one split-K slab workspace and one weight-gradient partial scratch per lane: branches run concurrently
-        self.workspaces = [torch.zeros(8 << 20, dtype=torch.float32, device=self.dev) for _ in range(4)]
-        self.scratches = [torch.zeros((32 if i == 0 else 16) << 20, dtype=torch.float32, device=self.dev) for i in range(4)]   # lane 0: room for the fp32 K-slice slabs of the deterministic weight gradients (128 MB)
-        self.workspace, self.scratch = self.workspaces[0], self.scratches[0]
-        self.side_streams = [torch.cuda.Stream(device=self.dev) for _ in range(3)]
-        self.use_lanes = False      # measured: no gain (13.5 vs 14.0 ms/step), the step is bound by shared memory-side resources
+        # the split-K slab workspace of the convolutions and the weight gradients' partial scratch: launches are serialised on one stream, so
+        # one of each serves every launch (the scratch has room for the fp32 K-slice slabs of the deterministic weight gradients: 128 MB)
+        self.workspace = torch.zeros(8 << 20, dtype=torch.float32, device=self.dev)
+        self.scratch = torch.zeros(32 << 20, dtype=torch.float32, device=self.dev)
         self.lr_dev = torch.zeros(16, dtype=torch.float32, device=self.dev)               # step-dependent optimizer scalars
         self.lr_state = torch.zeros(2, dtype=torch.float64, device=self.dev)              # [steps taken, base learning rate]
         self._t_dev, self._lr_base_dev = -1, None                                         # what lr_state holds (host shadow)
@@ -1961,8 +1863,7 @@ class Engine:
         self._upload(g, x, y)
         self._zero_arena(g, s)
         self._prep_weights(s)
-        side = self.side_streams if self.use_lanes else None
-        g.fwd.run(s, side=side)
+        g.fwd.run(s)
         g.loss_plan.run(s)
         hooks = None
         if self.dist is not None:
@@ -1970,20 +1871,20 @@ class Engine:
             self.dist.reducer.begin()
             if self.dist.overlap:
                 hooks = self._bucket_hooks(g)
-        g.bwd.run(s, hooks, side=side)
+        g.bwd.run(s, hooks)
         return g
 
     def _bucket_marks(self, g: Graph) -> Dict[int, List[int]]:
-        """{backward launch index -> gradient buckets that are complete after that launch}."""
+        """{backward launch index -> gradient buckets that are complete after that launch}: a bucket is complete after the last launch
+        that names one of its parameters' gradients."""
         if getattr(g, "_marks", None) is None:
-            last = [-1] * len(self.dist.buckets)
-            for off, idx in g.grad_touch.items():
-                b = self.dist.bucket_of(off)
-                last[b] = max(last[b], idx)
+            last: Dict[int, int] = {}
+            for idx, (_, _, _, grads) in enumerate(g.bwd.calls):
+                for off in grads:
+                    last[self.dist.bucket_of(off)] = idx
             by_idx: Dict[int, List[int]] = {}
-            for b, idx in enumerate(last):
-                if idx >= 0:
-                    by_idx.setdefault(g.bwd.safe_hook_index(idx), []).append(b)    # never while side lanes are running
+            for b, idx in sorted(last.items()):
+                by_idx.setdefault(idx, []).append(b)
             g._marks = by_idx
         return g._marks
 
@@ -2023,6 +1924,18 @@ class Engine:
         self.weights_dirty = True
         self._g_pending = False                             # the optimizer zeroed the arena as it consumed it
 
+    def _issue_step(self, g: Graph):
+        """The whole training step on the current stream: arena fill, weight refresh (forced), forward, losses, backward, optimizer -
+        what _graph_step runs and captures and count_step_dispatches counts."""
+        s = self._stream()
+        self._zero_arena(g, s)
+        self.weights_dirty = True
+        self._prep_weights(s)
+        g.fwd.run(s)
+        g.loss_plan.run(s)
+        g.bwd.run(s)
+        self._launch_optimizer(1.0, s)
+
     def _graph_step(self, x, y):
         """Single-GPU fast path: the whole step (arena zeroing, weight refresh, forward, losses, backward, optimizer)
         captured once into a HIP graph and replayed; only the input upload and the lr scalar stay outside."""
@@ -2036,18 +1949,11 @@ class Engine:
         cap = self._captured.get(B)
         if cap is None:
             # warm-up run outside capture (sets kernel attributes, pays first-launch costs), then capture
-            s = self._stream()
-            side = self.side_streams if self.use_lanes else None
-            self._zero_arena(g, s); self.weights_dirty = True; self._prep_weights(s)
-            g.fwd.run(s, side=side); g.loss_plan.run(s); g.bwd.run(s, side=side)
-            self._launch_optimizer(1.0, s)
+            self._issue_step(g)
             torch.cuda.synchronize()
             cap = torch.cuda.CUDAGraph()
             with torch.cuda.graph(cap):
-                s = self._stream()
-                self._zero_arena(g, s); self.weights_dirty = True; self._prep_weights(s)
-                g.fwd.run(s, side=side); g.loss_plan.run(s); g.bwd.run(s, side=side)
-                self._launch_optimizer(1.0, s)
+                self._issue_step(g)
             self._captured[B] = cap
             self.weights_dirty = True
             # the warm-up consumed this step's update; the capture itself launched nothing
@@ -2067,10 +1973,7 @@ class Engine:
             cap = torch.cuda.CUDAGraph(keep_graph=True)
             dirty, fresh = self.weights_dirty, self.wf_fresh
             with torch.cuda.graph(cap):
-                s = self._stream()
-                self._zero_arena(g, s); self.weights_dirty = True; self._prep_weights(s)
-                g.fwd.run(s); g.loss_plan.run(s); g.bwd.run(s)
-                self._launch_optimizer(1.0, s)
+                self._issue_step(g)
             self.weights_dirty, self.wf_fresh = dirty, fresh
             k = C.c_int32(0)
             L.lib().call("rua_graph_kernel_nodes", C.c_void_p(cap.raw_cuda_graph()), C.byref(k), None)
@@ -2167,7 +2070,7 @@ class Engine:
         if self.use_graph and self.dist is None:
             g = self._graph_step(x, y)
             return self._results(g) if fetch else None
-        if self.use_graph and self.dp_graph and not self.dist.host_staged and not self.use_lanes:
+        if self.use_graph and self.dp_graph and not self.dist.host_staged:
             g = self._graph_step_dp(x, y)
             return self._results(g) if fetch else None
         g = self.forward_backward(x, y, _whole_step=True)
@@ -2197,9 +2100,9 @@ class Engine:
         self._upload(g, x, None)
         self._prep_weights(s)
         cap = self._captured_eval.get(B) if self.use_graph else None
-        if cap is None or self.use_lanes:
+        if cap is None:
             g.fwd.run(s)
-            if self.use_graph and not self.use_lanes and B in self._eval_seen:
+            if self.use_graph and B in self._eval_seen:
                 try:
                     torch.cuda.synchronize()
                     cap = torch.cuda.CUDAGraph()

@@ -359,6 +359,70 @@ def test_data_parallel_graph_pieces_match_single_process_step():
             dist.destroy_process_group()
 
 
+def _ints(v):
+    """Every integer reachable from a recorded launch argument: plain ints, ctypes structs (passed by reference) and arrays."""
+    import ctypes
+    if isinstance(v, int):
+        yield v
+    elif isinstance(v, (tuple, ctypes.Array)):
+        for e in v:
+            yield from _ints(e)
+    elif isinstance(v, ctypes.Structure):
+        for f in v._fields_:
+            yield from _ints(getattr(v, f[0]))
+    elif hasattr(v, "_obj"):                                     # ctypes.byref(struct)
+        yield from _ints(v._obj)
+
+
+def test_data_parallel_bucket_hooks_follow_the_last_gradient_writer():
+    """Under data parallel a bucket's all-reduce is issued right after the last backward launch that writes into it: not earlier (it would
+    read unwritten gradients), not later (overlap lost).  Which launch writes which gradient is read off the recorded arguments themselves -
+    every pointer into the gradient arena a launch passes, its descriptors and the batched reductions' tables included - not off the
+    recorder's bookkeeping.  Buckets of the default size, and one bucket per parameter entry; the cfg3 layout in bf16 and the cfg4 layout
+    (depth 7, C = 2048) in fp32.  Nothing runs: the plans are only recorded."""
+    import gc
+    import torch.distributed as dist
+    from resunet_a_mltsk_keras_amd import _lib as L
+    from resunet_a_mltsk_keras_amd.dist import DataParallel
+    from resunet_a_mltsk_keras_amd.engine import Engine, LossSpec, ModelConfig
+    created = not dist.is_initialized()
+    if created:
+        dist.init_process_group("nccl", init_method="tcp://127.0.0.1:29543", rank=0, world_size=1)
+    try:
+        for size, depth, dtype, B in ((256, 6, "bf16", 8), (512, 7, "f32", 1)):
+            eng = Engine(ModelConfig(input_shape=(size, size, 6), num_classes=6, multitasking=True, depth=depth), dtype=dtype)
+            eng.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in HEADS}, weight={h: 1.0 for h in HEADS}))
+            g0, g1 = eng.G.data_ptr(), eng.G.data_ptr() + 4 * eng.params.n
+            for kw in ({}, {"bucket_mb": 1e-5}):                   # 1e-5 MB: every parameter entry is a bucket of its own
+                dp = DataParallel(eng, **kw)
+                eng.drop_plans()
+                g = eng.graph(B, True)
+                last = {}
+                for i, (_, name, args, _) in enumerate(g.bwd.calls):
+                    vals = list(_ints(args))
+                    if name == "rua_wgrad_reduce_batch":         # the records of the batched reduction live in a device table
+                        table = next(t for t in g.allocs if t.data_ptr() == args[0])
+                        vals += list(_ints((L.WgradPending * args[1]).from_buffer_copy(table.cpu().numpy().tobytes())))
+                    for v in vals:
+                        if g0 <= v < g1:
+                            last[dp.bucket_of((v - g0) // 4)] = i
+                hook = {b: i for i, bs in eng._bucket_marks(g).items() for b in bs}
+                bad = {b: (hook.get(b), last.get(b)) for b in set(hook) | set(last) if hook.get(b) != last.get(b)}
+                assert not bad, (size, dtype, kw, sorted(bad.items())[:8])
+                # every bucket gets its hook, except one that holds nothing but the bias of a convolution followed by a training-mode
+                # BatchNorm: that gradient is exactly zero and no launch writes it (the arena's zeros are reduced at the end of the step)
+                unwritten = [e["name"] for e in eng.params.entries if dp.bucket_of(e["off"]) not in hook]
+                assert all(n.endswith("/bias") for n in unwritten), (size, dtype, kw, unwritten[:8])
+                if not kw:
+                    assert not unwritten, (size, dtype, unwritten[:8])
+            del eng, g, dp
+            gc.collect()
+            torch.cuda.empty_cache()
+    finally:
+        if created:
+            dist.destroy_process_group()
+
+
 def test_evaluation_script_end_to_end(tmp_path):
     """test_ISPRS.py: tile -> predict -> argmax -> metrics -> mosaic on a synthetic test tile; the numbers must
     equal what the same model gives through predict() directly."""
