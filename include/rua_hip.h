@@ -417,6 +417,19 @@ int rua_adam_step_w(float* theta, float* g, float* m, float* v, int64_t n, float
 int rua_sgd_step_w(float* theta, float* g, float* vel, int64_t n, float lr, const float* lr_dev, float momentum, float grad_scale,
                    int zero_grad, void* wcopy_bf16, void* stream);
 
+/* ---- multitask training targets from uint8 patches (labels.py; the reference's preprocess_save_patches_ISPRS.py:206-228,
+ * multitasking_utils.py:6-35) ------------------------------------------------------------------------------------------------
+ * img [N][H][W][Cin] and cls [N][H][W] are uint8 (4-byte aligned); x [N][H][W][Cin], seg / bound / dist [N][H][W][C] and
+ * color [N][H][W][3] are fp32 (16-byte aligned).  Bit for bit the host definitions:
+ *   x = float(img) / 255 (norm_type 1) or / 126.5 (norm_type 2: `img /= 127.5 - 1.`), seg = onehot(cls) (a class value >= C: all zero),
+ *   bound = get_boundary_label(seg), dist = get_distance_label(seg), color = color_label(img, norm_type).
+ * cls and seg are null together (x only: inference); bound, dist and color are null together (single task: x and seg only), color needs
+ * Cin = 3.  scratch: rua_targets_scratch_bytes(N, C) bytes (only with dist).  Limits: 1 <= H, W <= 512, 1 <= C <= 64, 1 <= Cin <= 16,
+ * N*H*W*max(C, Cin, 4) < 2^31.  Four launches (one without dist); the results do not depend on launch order or timing. */
+int64_t rua_targets_scratch_bytes(int N, int num_classes);
+int rua_multitask_targets(const uint8_t* img, const uint8_t* cls, int N, int H, int W, int Cin, int num_classes, int norm_type,
+                          float* x, float* seg, float* bound, float* dist, float* color, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

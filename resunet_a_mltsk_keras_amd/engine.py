@@ -325,7 +325,18 @@ class Graph:
         self.allocs: List[torch.Tensor] = []
         self.stats_used = 16                 # the first 16 doubles of the arena are the loss / metric scalars
         self.act_bytes = 0
+        self.img_u8 = self.cls_u8 = self.tgt_scratch = None     # compact batches (Engine._upload_compact): allocated on first use
         self._build()
+
+    def compact_buffers(self):
+        """uint8 image [B,H,W,Cin] and class map [B,H,W] the compact batch is uploaded into, and the targets' scratch."""
+        if self.img_u8 is None:
+            H, W, Cin = self.cfg.input_shape
+            self.img_u8 = torch.empty((self.B, H, W, Cin), dtype=torch.uint8, device=self.dev)
+            self.cls_u8 = torch.empty((self.B, H, W), dtype=torch.uint8, device=self.dev)
+            n = int(L.lib().raw("rua_targets_scratch_bytes")(self.B, self.cfg.num_classes))
+            self.tgt_scratch = torch.empty((max(n, 4),), dtype=torch.uint8, device=self.dev)
+        return self.img_u8, self.cls_u8, self.tgt_scratch
 
     # -- allocation -------------------------------------------------------------------------
     def alloc(self, shape, dtype, zero=False):
@@ -1823,6 +1834,41 @@ class Engine:
             else:
                 put(g.heads[0]["y"].t, y)
 
+    def _upload_compact(self, g: Graph, x, y, norm_type: int):
+        """Compact batch: x uint8 [B,H,W,Cin], y uint8 class map [B,H,W] (None: x only).  The bytes go up like _upload's, then
+        rua_multitask_targets writes x (normalised) into g.x_in and seg / bound / dist / color into the heads' label buffers on the
+        compute stream - in front of the recorded plans, outside any captured graph."""
+        img, cls, scratch = g.compact_buffers()
+
+        def put(dst: torch.Tensor, src):
+            if isinstance(src, np.ndarray):
+                if src.dtype != np.uint8:
+                    raise ValueError(f"compact batches are uint8, got {src.dtype}")
+                src = torch.from_numpy(np.ascontiguousarray(src))
+            if src.dtype != torch.uint8:
+                raise ValueError(f"compact batches are uint8, got {src.dtype}")
+            if tuple(src.shape) != tuple(dst.shape):
+                raise ValueError(f"expected shape {tuple(dst.shape)}, got {tuple(src.shape)}")
+            dst.copy_(src, non_blocking=bool(src.is_pinned()))
+        put(img, x)
+        H, W, Cin = self.cfg.input_shape
+        ptr = lambda name: g.outputs[name]["y"].ptr
+        if y is None:
+            labels = (None, None, None, None, None)
+        else:
+            put(cls, y)
+            mt = self.cfg.multitasking
+            labels = (cls.data_ptr(), ptr("seg")) + ((ptr("bound"), ptr("dist"), ptr("color")) if mt else (None, None, None))
+        L.lib().call("rua_multitask_targets", img.data_ptr(), labels[0], g.B, H, W, Cin, self.cfg.num_classes, int(norm_type), g.x_in.ptr,
+                     labels[1], labels[2], labels[3], labels[4], scratch.data_ptr(), scratch.numel(), C.c_void_p(self._stream()))
+
+    def _put_batch(self, g: Graph, x, y, norm_type: Optional[int]):
+        """norm_type None: float batch (_upload); 1 or 2: compact uint8 batch (_upload_compact)."""
+        if norm_type is None:
+            self._upload(g, x, y)
+        elif x is not None:
+            self._upload_compact(g, x, y, norm_type)
+
     def _zero_arena(self, g: Graph, s):
         L.lib().call("rua_fill_zero", self.stats_arena.data_ptr(), g.stats_used * 8, C.c_void_p(s))
 
@@ -1848,9 +1894,10 @@ class Engine:
             self.ow_flag.fill_(v)
             self._ow = v
 
-    def forward_backward(self, x=None, y=None, _whole_step: bool = False):
+    def forward_backward(self, x=None, y=None, _whole_step: bool = False, norm_type: Optional[int] = None):
         """forward + losses + backward on the current stream; gradients are ADDED to self.G (several calls before one optimizer_step accumulate, e.g. the
-        replicas of a data-parallel step played one after the other); _whole_step (train_step): the arena is zero and this is the step's only backward."""
+        replicas of a data-parallel step played one after the other); _whole_step (train_step): the arena is zero and this is the step's only backward.
+        norm_type 1 / 2: x, y are a compact batch (uint8 image, uint8 class map; _upload_compact)."""
         # first-writer overwrite needs a ZERO gradient arena: after a standalone forward_backward() (which accumulates) the arena holds
         # unapplied gradients, and the next whole step must accumulate on top of them too (mixing the two calls keeps its old meaning)
         self._set_overwrite(1 if (_whole_step and self.wgrad_overwrite and not self._g_pending) else 0)
@@ -1860,7 +1907,7 @@ class Engine:
         self._last_B = B
         g = self.graph(B, True)
         s = self._stream()
-        self._upload(g, x, y)
+        self._put_batch(g, x, y, norm_type)
         self._zero_arena(g, s)
         self._prep_weights(s)
         g.fwd.run(s)
@@ -1936,13 +1983,13 @@ class Engine:
         g.bwd.run(s)
         self._launch_optimizer(1.0, s)
 
-    def _graph_step(self, x, y):
+    def _graph_step(self, x, y, norm_type: Optional[int] = None):
         """Single-GPU fast path: the whole step (arena zeroing, weight refresh, forward, losses, backward, optimizer)
         captured once into a HIP graph and replayed; only the input upload and the lr scalar stay outside."""
         B = x.shape[0] if x is not None else self._last_B
         self._last_B = B
         g = self.graph(B, True)
-        self._upload(g, x, y)
+        self._put_batch(g, x, y, norm_type)
         self._set_lr()
         self._set_overwrite(1 if (self.wgrad_overwrite and not self._g_pending) else 0)
         self._g_pending = False                             # the step's optimizer launch zeroes the arena
@@ -1983,14 +2030,14 @@ class Engine:
             torch.cuda.synchronize()
             return None
 
-    def _graph_step_dp(self, x, y):
+    def _graph_step_dp(self, x, y, norm_type: Optional[int] = None):
         """Data-parallel fast path: the step is cut at the launches after which a gradient bucket is complete; every
         piece is its own HIP graph, the bucket all-reduces are issued eagerly between the replays on the reducer's side
         stream (RCCL stays outside the captures), so they overlap the next pieces exactly like in the eager path."""
         B = x.shape[0] if x is not None else self._last_B
         self._last_B = B
         g = self.graph(B, True)
-        self._upload(g, x, y)
+        self._put_batch(g, x, y, norm_type)
         red = self.dist.reducer
         pieces = self._captured_dp.get(B)
         if pieces is None:
@@ -2065,39 +2112,41 @@ class Engine:
         self.weights_dirty = True
         return g
 
-    def train_step(self, x=None, y=None, fetch: bool = True):
-        """One Keras train_on_batch (train_ISPRS.py:131,148): returns the metric list in the reference's order."""
+    def train_step(self, x=None, y=None, fetch: bool = True, norm_type: Optional[int] = None):
+        """One Keras train_on_batch (train_ISPRS.py:131,148): returns the metric list in the reference's order.
+        norm_type 1 / 2: x, y are a compact batch - uint8 image [B,H,W,Cin], uint8 class map [B,H,W] - whose float input and targets
+        are built on the device (_upload_compact) before the step."""
         if self.use_graph and self.dist is None:
-            g = self._graph_step(x, y)
+            g = self._graph_step(x, y, norm_type)
             return self._results(g) if fetch else None
         if self.use_graph and self.dp_graph and not self.dist.host_staged:
-            g = self._graph_step_dp(x, y)
+            g = self._graph_step_dp(x, y, norm_type)
             return self._results(g) if fetch else None
-        g = self.forward_backward(x, y, _whole_step=True)
+        g = self.forward_backward(x, y, _whole_step=True, norm_type=norm_type)
         if self.dist is not None:
             self.dist.reduce_gradients(self)
         self.optimizer_step(1.0 / self.world)
         return self._results(g) if fetch else None
 
-    def test_step(self, x, y):
-        """Keras test_on_batch (train_ISPRS.py:167,186): BN uses moving statistics, nothing is updated."""
+    def test_step(self, x, y, norm_type: Optional[int] = None):
+        """Keras test_on_batch (train_ISPRS.py:167,186): BN uses moving statistics, nothing is updated.  norm_type: as train_step."""
         g = self.graph(x.shape[0], False)
         s = self._stream()
-        self._upload(g, x, y)
+        self._put_batch(g, x, y, norm_type)
         self._zero_arena(g, s)
         self._prep_weights(s)
         g.fwd.run(s)
         g.loss_plan.run(s)
         return self._results(g)
 
-    def predict(self, x):
+    def predict(self, x, norm_type: Optional[int] = None):
         """Inference forward (moving BN statistics).  The forward launch list of a batch size is captured into a HIP graph
         on its second use (the reference's evaluation calls predict(batch_size=1) per patch, test_ISPRS.py:28: ~250
-        launches of host time per patch otherwise)."""
+        launches of host time per patch otherwise).  norm_type 1 / 2: x is uint8 and normalised on the device."""
         B = x.shape[0]
         g = self.graph(B, False)
         s = self._stream()
-        self._upload(g, x, None)
+        self._put_batch(g, x, None, norm_type)
         self._prep_weights(s)
         cap = self._captured_eval.get(B) if self.use_graph else None
         if cap is None:

@@ -7,7 +7,8 @@ Mirrors exactly what the reference's callers touch:
   * `Adam(lr=, beta_1=)`, `SGD(lr=, momentum=)`, `K.get_value/set_value`, `load_model`          utils.py imports, train_ISPRS.py:404-407,474
   * loss factories `Tanimoto_dual_loss()` and `weighted_categorical_crossentropy(weights)`     multitasking_utils.py:71-85, utils.py:466-491
 x / y cross this boundary as host numpy float32 NHWC arrays (dict of arrays for the multitask heads), like in
-the reference.  Everything numerical runs in librua_hip.so; there is no CPU fallback.
+the reference, or as a compact batch - uint8 image [B,H,W,Cin] and integer class map [B,H,W] - whose float input and targets
+are built on the GPU (rua_multitask_targets).  Everything numerical runs in librua_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -185,6 +186,31 @@ def _loss_kind(loss, head):
     return kind, getattr(loss, "weights", None)
 
 
+# ---- compact batches ---------------------------------------------------------------------------------
+def _is_int(a) -> bool:
+    if isinstance(a, torch.Tensor):
+        return not (a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool)
+    return isinstance(a, np.ndarray) and np.issubdtype(a.dtype, np.integer)
+
+
+def compact_batch(x, y):
+    """(x, y) of the compact path - uint8 image [B,H,W,Cin], uint8 class map [B,H,W] - or None when y is not an integer array of
+    shape [B,H,W] (then the batch is the float one).  A class map of a wider integer type must lie in [0, 255]."""
+    if y is None or isinstance(y, dict) or getattr(y, "ndim", None) != 3 or not _is_int(y):
+        return None
+    is_u8 = (y.dtype == torch.uint8) if isinstance(y, torch.Tensor) else (y.dtype == np.uint8)
+    if not is_u8:
+        lo, hi = int(y.min()), int(y.max())
+        if lo < 0 or hi > 255:
+            raise ValueError(f"class map values must lie in [0, 255], got [{lo}, {hi}]")
+        y = y.to(torch.uint8) if isinstance(y, torch.Tensor) else y.astype(np.uint8)
+    x_u8 = (x.dtype == torch.uint8) if isinstance(x, torch.Tensor) else (isinstance(x, np.ndarray) and x.dtype == np.uint8)
+    if not x_u8 or x.ndim != 4 or tuple(x.shape[:3]) != tuple(y.shape):
+        raise ValueError(f"with a class map y {tuple(y.shape)}, x must be uint8 [B,H,W,Cin] of the same B, H, W "
+                         f"(got {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))})")
+    return x, y
+
+
 # ---- the model ---------------------------------------------------------------------------------------
 class Model:
     """Keras-Model duck type over the recorded HIP plan."""
@@ -276,24 +302,45 @@ class Model:
         sl = slice(r * (B // w), (r + 1) * (B // w))
         return x[sl], ({k: v[sl] for k, v in y.items()} if isinstance(y, dict) else (None if y is None else y[sl]))
 
-    def train_on_batch(self, x, y=None, return_dict=False, local_shard=False, **_):
+    def _batch(self, x, y, norm_type, local_shard):
+        """This rank's (x, y, norm_type for the engine): norm_type only for a compact batch (compact_batch), None for the float one."""
+        cb = compact_batch(x, y)
+        if cb is not None:
+            if norm_type not in (1, 2):
+                raise ValueError(f"norm_type {norm_type!r}: compact batches support 1 (/255) and 2 (/126.5)")
+            x, y = cb
+        x, y = self._local_batch(x, y, local_shard)
+        return x, y, (int(norm_type) if cb is not None else None)
+
+    def train_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, **_):
+        """y an integer class map [B,H,W] (x then uint8 [B,H,W,Cin]): the compact path - x / norm_type and the targets seg, bound, dist
+        and color (labels.py) are built on the GPU."""
         assert self._compiled, "compile() first"
         self._sync_lr()
-        x, y = self._local_batch(x, y, local_shard)
-        res = self.engine.train_step(x, y)
+        x, y, nt = self._batch(x, y, norm_type, local_shard)
+        res = self.engine.train_step(x, y, norm_type=nt)
         return dict(zip(self.metrics_names, res)) if return_dict else res
 
-    def test_on_batch(self, x, y=None, return_dict=False, local_shard=False, **_):
+    def test_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, **_):
         assert self._compiled, "compile() first"
-        x, y = self._local_batch(x, y, local_shard)
-        res = self.engine.test_step(x, y)
+        x, y, nt = self._batch(x, y, norm_type, local_shard)
+        res = self.engine.test_step(x, y, norm_type=nt)
         return dict(zip(self.metrics_names, res)) if return_dict else res
 
-    def predict(self, x, batch_size=1, **_):
-        x = np.asarray(x, np.float32)
+    def predict(self, x, batch_size=1, norm_type=None, **_):
+        """norm_type None: x is cast to float32 as it is.  1 / 2: x is uint8 and divided by 255 / 126.5 on the GPU."""
+        if norm_type is None:
+            x = np.asarray(x, np.float32)
+        else:
+            if norm_type not in (1, 2):
+                raise ValueError(f"norm_type {norm_type!r}: 1 (/255), 2 (/126.5) or None (x as given)")
+            if not isinstance(x, torch.Tensor):
+                x = np.asarray(x)
+            if x.dtype != (torch.uint8 if isinstance(x, torch.Tensor) else np.uint8):
+                raise ValueError(f"predict(norm_type={norm_type}) takes uint8 images, got {x.dtype}")
         if self.engine.loss is None:                      # load_model(..., compile=False) then predict (test_ISPRS.py:278,28)
             self.engine.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in HEADS}, weight={h: 1.0 for h in HEADS}))
-        outs = [self.engine.predict(x[i:i + batch_size]) for i in range(0, x.shape[0], batch_size)]
+        outs = [self.engine.predict(x[i:i + batch_size], norm_type=norm_type) for i in range(0, x.shape[0], batch_size)]
         if self.cfg.multitasking:
             return {h: np.concatenate([o[h] for o in outs], axis=0) for h in HEADS}
         return np.concatenate(outs, axis=0)

@@ -5,7 +5,8 @@ The reference reads 5*B `.npy` files serially inside the training loop before ev
 keeps the same semantics - the caller's list of paths, paired BY NAME upstream, `n // batch_size` batches per
 pass, the last partial batch dropped (train_ISPRS.py:102,154) - and moves the file reads to worker threads
 that fill a small ring of preallocated (pinned, when a GPU is present) host buffers ahead of the consumer.
-Buffers are float32 NHWC like the files, so the upload into the engine is a plain async copy.
+Buffers are float32 NHWC like the files, so the upload into the engine is a plain async copy.  keep_dtype=True keeps the
+files' own dtype instead: the compact layout (uint8 images and class maps, compact.py) travels as uint8.
 """
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ class PrefetchLoader:
     depth:   batches read ahead (ring slots = depth + 1: the slot handed to the caller is reused only after the
              caller has asked for the NEXT batch, i.e. after its training step has returned).
     workers: threads reading files (np.load releases the GIL while it reads).
+    keep_dtype: slots in the dtype of the first patch's files (uint8 for the compact layout) instead of float32.
     rank, world: data-parallel shard.  `batch_size` stays the GLOBAL batch (train_ISPRS.py:314 under MirroredStrategy);
              rank r reads and yields only samples [r*B/world, (r+1)*B/world) of every global batch - the contiguous
              split Keras makes - so N ranks read each file once between them instead of N times.
@@ -32,7 +34,7 @@ class PrefetchLoader:
 
     def __init__(self, x_paths: Sequence[str], y_paths: Dict[str, Sequence[str]], batch_size: int,
                  order: Optional[Sequence[int]] = None, depth: int = 2, workers: int = 4, pin: Optional[bool] = None,
-                 rank: int = 0, world: int = 1):
+                 rank: int = 0, world: int = 1, keep_dtype: bool = False):
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")
         if world < 1 or not (0 <= rank < world):
@@ -52,9 +54,12 @@ class PrefetchLoader:
         self._stop = threading.Event()
         if self.x_paths:
             x0 = np.load(self.x_paths[0])
-            shapes = {h: np.load(v[0]).shape for h, v in self.y_paths.items()}
-            mk = lambda shp: torch.empty((self.local_B,) + tuple(shp), dtype=torch.float32, pin_memory=self.pin)
-            self._slots = [(mk(x0.shape), {h: mk(s) for h, s in shapes.items()}) for _ in range(self.depth + 1)]
+            y0 = {h: np.load(v[0]) for h, v in self.y_paths.items()}
+
+            def mk(a: np.ndarray) -> torch.Tensor:
+                dt = torch.from_numpy(np.empty(0, a.dtype)).dtype if keep_dtype else torch.float32
+                return torch.empty((self.local_B,) + a.shape, dtype=dt, pin_memory=self.pin)
+            self._slots = [(mk(x0), {h: mk(a) for h, a in y0.items()}) for _ in range(self.depth + 1)]
 
     def __len__(self) -> int:
         return len(self.order) // self.B
@@ -70,7 +75,7 @@ class PrefetchLoader:
         def one(b: int, i: int) -> None:
             xn[b] = np.load(self.x_paths[i])
             for h, arr in yn.items():
-                arr[b] = np.load(self.y_paths[h][i])          # assignment casts to float32 like .astype(np.float32)
+                arr[b] = np.load(self.y_paths[h][i])          # assignment casts to the slot's dtype (float32: like .astype(np.float32))
 
         for f in [pool.submit(one, b, i) for b, i in enumerate(idx)]:
             f.result()                                        # re-raises a worker's exception here

@@ -12,6 +12,8 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
   * scalars go to `<results_path>/logs/{train,val}/scalars.jsonl` with the reference's TensorBoard tag names
     (tensorboard is not available); the best model is `<results_path>/best_model.h5`: real HDF5 whose `model_weights` group is
     Keras' own weight layout (plus this package's metadata and optimizer state, written without h5py by h5lite).
+  * `--compact_dataset yes --norm_type {1,2}`: read the compact layout (uint8 images/ and labels/classes/, written by
+    `python -m resunet_a_mltsk_keras_amd.compact`); x and the seg / bound / dist / color targets are built on the GPU.
   * `--dtype {bf16,f32}`, `--seed`: engine options.  Launch with torch.distributed.run for multi-GPU data
     parallel (`-bs` is then the GLOBAL batch, as under MirroredStrategy).
 """
@@ -66,6 +68,9 @@ def build_parser():
     p.add_argument("--channels", type=int, default=0, help="input bands (0 = read from the first patch)")
     p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "f32"])
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--compact_dataset", type=str2bool, default=False,
+                   help="dataset in the compact layout: images/<name>.npy (uint8 HxWxC) + labels/classes/<name>.npy (uint8 HxW)")
+    p.add_argument("--norm_type", type=int, default=1, choices=[1, 2], help="compact layout: x = u8 / 255 (1) or u8 / 126.5 (2)")
     return p
 
 
@@ -87,6 +92,16 @@ def list_dataset(root, multitasking):
     xs = [os.path.join(tdir, n) for n in names]
     ys = {h: [os.path.join(root, "labels", h, n) for n in names] for h in heads}
     return xs, ys
+
+
+def list_compact_dataset(root):
+    """Name-paired compact patches: <root>/images/x.npy with <root>/labels/classes/x.npy."""
+    names = sorted(n for n in os.listdir(os.path.join(root, "images")) if n.endswith(".npy"))
+    have = set(os.listdir(os.path.join(root, "labels", "classes")))
+    missing = [n for n in names if n not in have]
+    if missing:
+        raise FileNotFoundError(f"labels/classes lacks {len(missing)} patches, e.g. {missing[0]}")
+    return [os.path.join(root, "images", n) for n in names], {"classes": [os.path.join(root, "labels", "classes", n) for n in names]}
 
 
 def split_dataset(xs, ys):
@@ -138,9 +153,14 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
     # the reference loads 5*B .npy files serially before every step (train_ISPRS.py:115-141); here worker threads read
     # two batches ahead into pinned buffers
     # under data parallel `batch_size` is the global batch and every rank reads only its own shard of it
-    ld_tr = PrefetchLoader(x_tr, y_tr, batch_size, rank=rank, world=world)
-    ld_va = PrefetchLoader(x_va, y_va, batch_size, rank=rank, world=world)
+    # compact layout: uint8 slots, and the targets are built on the GPU from the class map
+    compact = bool(getattr(args, "compact_dataset", False))
+    ld_tr = PrefetchLoader(x_tr, y_tr, batch_size, rank=rank, world=world, keep_dtype=compact)
+    ld_va = PrefetchLoader(x_va, y_va, batch_size, rank=rank, world=world, keep_dtype=compact)
     shard = dict(local_shard=True) if world > 1 else {}
+    if compact:
+        shard["norm_type"] = args.norm_type
+    labels = (lambda yb: yb["classes"]) if compact else (lambda yb: yb if args.multitasking else yb["seg"])
     min_loss, cont = float("inf"), 0
     rng = np.random.default_rng(args.seed)
     say(net.output_names)
@@ -149,10 +169,10 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
         ld_tr.set_order(rng.permutation(len(x_tr)))
         n_tr, n_va = len(ld_tr), len(ld_va)
         for xb, yb in ld_tr:
-            acc_tr += np.asarray(net.train_on_batch(x=xb, y=yb if args.multitasking else yb["seg"], return_dict=False, **shard))
+            acc_tr += np.asarray(net.train_on_batch(x=xb, y=labels(yb), return_dict=False, **shard))
         acc_tr /= max(n_tr, 1)
         for xb, yb in ld_va:
-            acc_va += np.asarray(net.test_on_batch(x=xb, y=yb if args.multitasking else yb["seg"], **shard))
+            acc_va += np.asarray(net.test_on_batch(x=xb, y=labels(yb), **shard))
         acc_va /= max(n_va, 1)
         tm, vm = dict(zip(metrics_names, acc_tr)), dict(zip(metrics_names, acc_va))
         pre = "seg_" if args.multitasking else ""
@@ -209,7 +229,7 @@ def main(argv=None):
     from resunet_a_mltsk_keras_amd.keras_api import (SGD, Adam, BinaryCrossentropy, CategoricalCrossentropy, K, MeanSquaredError,
                                                    load_model, weighted_categorical_crossentropy)
 
-    xs, ys = list_dataset(args.dataset_path, args.multitasking)
+    xs, ys = list_compact_dataset(args.dataset_path) if args.compact_dataset else list_dataset(args.dataset_path, args.multitasking)
     x_tr, y_tr, x_va, y_va = split_dataset(xs, ys)
     rows = cols = args.patch_size
     channels = args.channels or int(np.load(xs[0]).shape[-1])
