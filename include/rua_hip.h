@@ -430,6 +430,20 @@ int64_t rua_targets_scratch_bytes(int N, int num_classes);
 int rua_multitask_targets(const uint8_t* img, const uint8_t* cls, int N, int H, int W, int Cin, int num_classes, int norm_type,
                           float* x, float* seg, float* bound, float* dist, float* color, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ---- training windows cut and augmented from resident scenes (scenes.py; the reference's preprocess_save_patches_ISPRS.py:28-48,
+ * utils.py:69-95 done per step on the device) ------------------------------------------------------------------------------------
+ * All array arguments are HOST arrays.  scene_img[s] / scene_cls[s] are device pointers to a uint8 [scene_h[s]][scene_w[s]][Cin]
+ * image and its uint8 [scene_h[s]][scene_w[s]] class map; windows is int32 [N][4], rows (scene, row, col, code): the window
+ * scene[row : row + PH, col : col + PW] transformed by code - 0 as it is, 1 rot90, 2 rot180, 3 rows flipped, 4 columns flipped,
+ * 5 rot270, 6 transposed, 7 anti-transposed (1, 5, 6, 7 need PH == PW).  img_out [N][PH][PW][Cin] and cls_out [N][PH][PW] are
+ * device memory, 4-byte aligned (what the targets call above reads); scene_cls and cls_out are null together (images only).
+ * Every row is checked on the host before anything is launched (a violation: RUA_ERR_ARG, the message names the row); the
+ * resolved windows travel as kernel arguments, 128 per launch, image and class map in the same launch: no device-side table,
+ * no copy, no synchronisation.  Limits: 1 <= PH, PW <= 512, 1 <= Cin <= 16. */
+int rua_scene_windows(const uint8_t* const* scene_img, const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w,
+                      int nscenes, const int32_t* windows, int N, int PH, int PW, int Cin,
+                      uint8_t* img_out, uint8_t* cls_out, void* stream);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

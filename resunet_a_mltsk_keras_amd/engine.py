@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .scenes import SceneBatch
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -1851,20 +1852,65 @@ class Engine:
                 raise ValueError(f"expected shape {tuple(dst.shape)}, got {tuple(src.shape)}")
             dst.copy_(src, non_blocking=bool(src.is_pinned()))
         put(img, x)
+        if y is not None:
+            put(cls, y)
+        self._compact_targets(g, y is not None, norm_type)
+
+    def _compact_targets(self, g: Graph, with_labels: bool, norm_type: int):
+        """rua_multitask_targets from g.compact_buffers() into g.x_in and (with_labels) the heads' label buffers, on the compute stream."""
+        img, cls, scratch = g.compact_buffers()
         H, W, Cin = self.cfg.input_shape
         ptr = lambda name: g.outputs[name]["y"].ptr
-        if y is None:
+        if not with_labels:
             labels = (None, None, None, None, None)
         else:
-            put(cls, y)
             mt = self.cfg.multitasking
             labels = (cls.data_ptr(), ptr("seg")) + ((ptr("bound"), ptr("dist"), ptr("color")) if mt else (None, None, None))
         L.lib().call("rua_multitask_targets", img.data_ptr(), labels[0], g.B, H, W, Cin, self.cfg.num_classes, int(norm_type), g.x_in.ptr,
                      labels[1], labels[2], labels[3], labels[4], scratch.data_ptr(), scratch.numel(), C.c_void_p(self._stream()))
 
-    def _put_batch(self, g: Graph, x, y, norm_type: Optional[int]):
-        """norm_type None: float batch (_upload); 1 or 2: compact uint8 batch (_upload_compact)."""
-        if norm_type is None:
+    def _check_scene(self, x, y, norm_type, with_labels: bool = True):
+        """The host-side conditions of a scene batch (no-op for any other x): the public entry points call it before they build or
+        launch anything."""
+        if not isinstance(x, SceneBatch):
+            return
+        pool = x.pool
+        H, W, Cin = self.cfg.input_shape
+        if y is not None:
+            raise ValueError("a scene batch carries its own labels: y must be None")
+        if isinstance(norm_type, bool) or not isinstance(norm_type, (int, np.integer)) or norm_type not in (1, 2):
+            raise ValueError(f"norm_type {norm_type!r}: scene batches support 1 (/255) and 2 (/126.5)")
+        if tuple(x.patch) != (H, W) or pool.channels != Cin:
+            raise ValueError(f"scene batch of {x.patch[0]} x {x.patch[1]} x {pool.channels} patches for a model whose input is {H} x {W} x {Cin}")
+        if with_labels and pool.cls_ptrs is None:
+            raise ValueError("this scene pool holds no class maps: it serves predict() only")
+        dev = torch.device(self.dev)
+        if pool.device.type != dev.type or (dev.index is not None and pool.device.index != dev.index):
+            raise ValueError(f"the scene pool lives on {pool.device}, the engine on {self.dev}")
+
+    def _upload_scene(self, g: Graph, batch: SceneBatch, norm_type: int, with_labels: bool = True):
+        """Scene batch (scenes.SceneBatch: resident scenes + a window table): rua_scene_windows cuts and augments the windows into
+        g.compact_buffers(), then the targets call of _upload_compact - both on the compute stream, in front of the recorded plans,
+        outside any captured graph.  The host passes B * 4 integers; nothing is copied.  with_labels False: images only (inference)."""
+        self._check_scene(batch, None, norm_type, with_labels)
+        pool = batch.pool
+        H, W, Cin = self.cfg.input_shape
+        if len(batch) != g.B:
+            raise ValueError(f"scene batch of {len(batch)} windows for a graph of batch {g.B}")
+        img, cls, _ = g.compact_buffers()
+        rows = np.ascontiguousarray(batch.rows, dtype=np.int32)
+        L.lib().call("rua_scene_windows", pool.img_ptrs, pool.cls_ptrs if with_labels else None, pool.heights, pool.widths, len(pool),
+                     rows.ctypes.data, g.B, H, W, Cin, img.data_ptr(), cls.data_ptr() if with_labels else None, C.c_void_p(self._stream()))
+        self._compact_targets(g, with_labels, int(norm_type))
+
+    def _put_batch(self, g: Graph, x, y, norm_type: Optional[int], with_labels: bool = True):
+        """norm_type None: float batch (_upload); 1 or 2: compact uint8 batch (_upload_compact).  x a SceneBatch: _upload_scene
+        (y is None: the labels are the pool's class maps; with_labels False: predict)."""
+        if isinstance(x, SceneBatch):
+            if y is not None:
+                raise ValueError("a scene batch carries its own labels: y must be None")
+            self._upload_scene(g, x, norm_type, with_labels)
+        elif norm_type is None:
             self._upload(g, x, y)
         elif x is not None:
             self._upload_compact(g, x, y, norm_type)
@@ -1898,6 +1944,7 @@ class Engine:
         """forward + losses + backward on the current stream; gradients are ADDED to self.G (several calls before one optimizer_step accumulate, e.g. the
         replicas of a data-parallel step played one after the other); _whole_step (train_step): the arena is zero and this is the step's only backward.
         norm_type 1 / 2: x, y are a compact batch (uint8 image, uint8 class map; _upload_compact)."""
+        self._check_scene(x, y, norm_type)
         # first-writer overwrite needs a ZERO gradient arena: after a standalone forward_backward() (which accumulates) the arena holds
         # unapplied gradients, and the next whole step must accumulate on top of them too (mixing the two calls keeps its old meaning)
         self._set_overwrite(1 if (_whole_step and self.wgrad_overwrite and not self._g_pending) else 0)
@@ -2115,7 +2162,9 @@ class Engine:
     def train_step(self, x=None, y=None, fetch: bool = True, norm_type: Optional[int] = None):
         """One Keras train_on_batch (train_ISPRS.py:131,148): returns the metric list in the reference's order.
         norm_type 1 / 2: x, y are a compact batch - uint8 image [B,H,W,Cin], uint8 class map [B,H,W] - whose float input and targets
-        are built on the device (_upload_compact) before the step."""
+        are built on the device (_upload_compact) before the step.  x a scenes.SceneBatch (y None, norm_type 1 / 2): the patches are cut
+        from the resident scenes on the device (_upload_scene)."""
+        self._check_scene(x, y, norm_type)
         if self.use_graph and self.dist is None:
             g = self._graph_step(x, y, norm_type)
             return self._results(g) if fetch else None
@@ -2130,6 +2179,7 @@ class Engine:
 
     def test_step(self, x, y, norm_type: Optional[int] = None):
         """Keras test_on_batch (train_ISPRS.py:167,186): BN uses moving statistics, nothing is updated.  norm_type: as train_step."""
+        self._check_scene(x, y, norm_type)
         g = self.graph(x.shape[0], False)
         s = self._stream()
         self._put_batch(g, x, y, norm_type)
@@ -2143,10 +2193,11 @@ class Engine:
         """Inference forward (moving BN statistics).  The forward launch list of a batch size is captured into a HIP graph
         on its second use (the reference's evaluation calls predict(batch_size=1) per patch, test_ISPRS.py:28: ~250
         launches of host time per patch otherwise).  norm_type 1 / 2: x is uint8 and normalised on the device."""
+        self._check_scene(x, None, norm_type, with_labels=False)
         B = x.shape[0]
         g = self.graph(B, False)
         s = self._stream()
-        self._put_batch(g, x, None, norm_type)
+        self._put_batch(g, x, None, norm_type, with_labels=False)
         self._prep_weights(s)
         cap = self._captured_eval.get(B) if self.use_graph else None
         if cap is None:

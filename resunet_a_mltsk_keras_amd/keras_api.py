@@ -22,6 +22,7 @@ import torch
 
 from . import _lib as L
 from .engine import HEADS, Engine, LossSpec, ModelConfig
+from .scenes import SceneBatch
 
 
 # ---- optimizers / backend shims -------------------------------------------------------------------
@@ -303,7 +304,14 @@ class Model:
         return x[sl], ({k: v[sl] for k, v in y.items()} if isinstance(y, dict) else (None if y is None else y[sl]))
 
     def _batch(self, x, y, norm_type, local_shard):
-        """This rank's (x, y, norm_type for the engine): norm_type only for a compact batch (compact_batch), None for the float one."""
+        """This rank's (x, y, norm_type for the engine): norm_type only for a compact batch (compact_batch), None for the float one.
+        A scenes.SceneBatch (y None) is checked against the model (Engine._check_scene) and sharded by its rows: every rank holds the pool."""
+        if isinstance(x, SceneBatch):
+            self.engine._check_scene(x, y, norm_type)
+            if self.engine.world > 1 and not local_shard:
+                import torch.distributed as dist
+                x = x.shard(dist.get_rank(), self.engine.world)
+            return x, None, int(norm_type)
         cb = compact_batch(x, y)
         if cb is not None:
             if norm_type not in (1, 2):
@@ -329,7 +337,9 @@ class Model:
 
     def predict(self, x, batch_size=1, norm_type=None, **_):
         """norm_type None: x is cast to float32 as it is.  1 / 2: x is uint8 and divided by 255 / 126.5 on the GPU."""
-        if norm_type is None:
+        if isinstance(x, SceneBatch):                      # windows of resident scenes (images only): cut and normalised on the GPU
+            self.engine._check_scene(x, None, norm_type, with_labels=False)
+        elif norm_type is None:
             x = np.asarray(x, np.float32)
         else:
             if norm_type not in (1, 2):

@@ -1,0 +1,368 @@
+"""Training from whole scenes: the scenes stay resident on the GPU and a step names its patches by index; rua_scene_windows
+(csrc/scene.hip) cuts and augments them straight into the uint8 buffers rua_multitask_targets reads (Engine._upload_scene).
+The reference does this offline (preprocess_save_patches_ISPRS.py): a 256 x 256 window slid at stride 32, every window written
+five times (as it is, rot90 once, rot90 twice, flipped on axis 0, flipped on axis 1) - 64 windows x 5 copies per scene pixel.
+
+    <root>/scenes/<name>.npy          uint8 H x W x C
+    <root>/labels/scenes/<name>.npy   uint8 H x W
+
+A batch is a window table, int32 [N][4] rows (scene, row, col, code): the window scene[row:row+PH, col:col+PW] transformed by
+
+    code  numpy                              out[i, j] =
+    0     w                                  w[i, j]
+    1     np.rot90(w, 1)                     w[j, P-1-i]
+    2     np.rot90(w, 2)                     w[PH-1-i, PW-1-j]
+    3     np.flip(w, 0)                      w[PH-1-i, j]
+    4     np.flip(w, 1)                      w[i, PW-1-j]
+    5     np.rot90(w, 3)                     w[P-1-j, i]
+    6     w.transpose(1, 0, 2)               w[j, i]
+    7     np.rot90(w, 2).transpose(1, 0, 2)  w[P-1-j, P-1-i]
+
+0 - 4 are the reference's five copies in its order, 5 - 7 complete the symmetries of the square; 1, 5, 6 and 7 need PH == PW.
+window_table() enumerates the reference's patch set: patch k of a written-out dataset (`patch_{k}.npy`) is row k.
+
+`python -m resunet_a_mltsk_keras_amd.scenes --image Image_Train.npy --reference Reference_Train.npy --dst DIR` writes a scene
+directory from the reference's two inputs (C x H x W arrays, the reference colour-coded); `--materialize DST` also writes the
+compact patch layout (compact.py) of its window table, for users who want files.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import os
+import sys
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+TRANSPOSING = (1, 5, 6, 7)
+NUM_CODES = 8
+MAX_PATCH, MAX_CHANNELS = 512, 16
+# the five ISPRS label colours and their class values (the reference's label_dict)
+ISPRS_COLOURS = {(255, 255, 255): 0, (0, 255, 0): 1, (0, 255, 255): 2, (0, 0, 255): 3, (255, 255, 0): 4}
+
+
+def _patch2(patch) -> Tuple[int, int]:
+    if isinstance(patch, (int, np.integer)):
+        return int(patch), int(patch)
+    ph, pw = patch
+    return int(ph), int(pw)
+
+
+def transform(w: np.ndarray, code: int) -> np.ndarray:
+    """Window w (H x W or H x W x C) under `code` (the table in the module docstring)."""
+    if code == 0:
+        return w
+    if code == 1:
+        return np.rot90(w, 1)
+    if code == 2:
+        return np.rot90(w, 2)
+    if code == 3:
+        return np.flip(w, 0)
+    if code == 4:
+        return np.flip(w, 1)
+    if code == 5:
+        return np.rot90(w, 3)
+    if code == 6:
+        return np.swapaxes(w, 0, 1)
+    if code == 7:
+        return np.swapaxes(np.rot90(w, 2), 0, 1)
+    raise ValueError(f"code {code} outside 0..7")
+
+
+def window_table(shapes: Sequence[Sequence[int]], patch, stride: int, data_aug: bool) -> np.ndarray:
+    """The reference's patch set as a window table: scene after scene the origins row = 0, stride, ... while row + patch <= H,
+    the same for columns, row-major (the order view_as_windows(..., step=stride) reshapes to); with data_aug patch 5 * i + j is
+    window i under code j, without it patch i is window i under code 0."""
+    ph, pw = _patch2(patch)
+    if stride < 1:
+        raise ValueError(f"stride {stride} must be at least 1")
+    parts = []
+    codes = np.arange(5 if data_aug else 1, dtype=np.int32)
+    for s, shp in enumerate(shapes):
+        H, W = int(shp[0]), int(shp[1])
+        if H < ph or W < pw:
+            raise ValueError(f"scene {s} is {H} x {W}: smaller than the {ph} x {pw} patch")
+        rows, cols = np.arange(0, H - ph + 1, stride, dtype=np.int32), np.arange(0, W - pw + 1, stride, dtype=np.int32)
+        t = np.empty((len(rows), len(cols), len(codes), 4), np.int32)
+        t[..., 0] = s
+        t[..., 1] = rows[:, None, None]
+        t[..., 2] = cols[None, :, None]
+        t[..., 3] = codes[None, None, :]
+        parts.append(t.reshape(-1, 4))
+    return np.concatenate(parts) if parts else np.zeros((0, 4), np.int32)
+
+
+def check_table(shapes: Sequence[Sequence[int]], table: np.ndarray, patch) -> np.ndarray:
+    """The table as a contiguous int32 [N][4] array; ValueError, in rua_scene_windows' own words, for the first bad row."""
+    ph, pw = _patch2(patch)
+    t = np.asarray(table)
+    if t.ndim != 2 or t.shape[1] != 4 or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError(f"a window table is an integer [N][4] array of (scene, row, col, code) rows, got {t.dtype} {t.shape}")
+    n = len(shapes)
+    if n < 1 or t.shape[0] < 1:
+        raise ValueError(f"rua_scene_windows: nscenes {n}, N {t.shape[0]} (both >= 1)")
+    if not (1 <= ph <= MAX_PATCH and 1 <= pw <= MAX_PATCH):
+        raise ValueError(f"rua_scene_windows: PH {ph}, PW {pw} (1 <= PH, PW <= 512)")
+    for k, (s, r, c, code) in enumerate(t.tolist()):
+        if not 0 <= s < n:
+            raise ValueError(f"rua_scene_windows: row {k}: scene {s} outside 0..{n - 1}")
+        H, W = int(shapes[s][0]), int(shapes[s][1])
+        if r < 0 or c < 0 or r + ph > H or c + pw > W:
+            raise ValueError(f"rua_scene_windows: row {k}: window ({r}, {c}) + {ph} x {pw} leaves its {H} x {W} scene")
+        if not 0 <= code < NUM_CODES:
+            raise ValueError(f"rua_scene_windows: row {k}: code {code} outside 0..7")
+        if ph != pw and code in TRANSPOSING:
+            raise ValueError(f"rua_scene_windows: row {k}: code {code} transposes and needs a square patch (got {ph} x {pw})")
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def host_windows(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]], table: np.ndarray, patch):
+    """The numpy definition of what rua_scene_windows writes: (img uint8 [N][PH][PW][C], cls uint8 [N][PH][PW] or None)."""
+    ph, pw = _patch2(patch)
+    t = check_table([im.shape for im in images], table, patch)
+    img = np.empty((len(t), ph, pw, images[0].shape[2]), np.uint8)
+    cls = np.empty((len(t), ph, pw), np.uint8) if class_maps is not None else None
+    for k, (s, r, c, code) in enumerate(t.tolist()):
+        img[k] = transform(images[s][r:r + ph, c:c + pw], code)
+        if cls is not None:
+            cls[k] = transform(class_maps[s][r:r + ph, c:c + pw], code)
+    return img, cls
+
+
+def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]]) -> int:
+    """Scenes are uint8 H x W x C with one C for all, class maps uint8 H x W of their image's size.  Returns C."""
+    if len(images) < 1:
+        raise ValueError("no scenes")
+    if class_maps is not None and len(class_maps) != len(images):
+        raise ValueError(f"{len(images)} scenes but {len(class_maps)} class maps")
+    ch = None
+    for s, im in enumerate(images):
+        if im.dtype != np.uint8 or im.ndim != 3:
+            raise ValueError(f"scene {s}: images are uint8 H x W x C, got {im.dtype} {im.shape}")
+        ch = im.shape[2] if ch is None else ch
+        if im.shape[2] != ch or not 1 <= ch <= MAX_CHANNELS:
+            raise ValueError(f"scene {s}: {im.shape[2]} channels (scene 0 has {ch}; 1..{MAX_CHANNELS} supported)")
+        if class_maps is not None:
+            cm = class_maps[s]
+            if cm.dtype != np.uint8 or cm.shape != im.shape[:2]:
+                raise ValueError(f"scene {s}: its class map is uint8 {im.shape[0]} x {im.shape[1]}, got {cm.dtype} {cm.shape}")
+    return int(ch)
+
+
+class SceneBatch:
+    """A batch named by index: a pool, int32 [B][4] table rows and the patch size.  Takes the place of x in Engine.train_step /
+    test_step / predict and Model.train_on_batch / test_on_batch / predict (y is None: the class maps are the pool's)."""
+
+    def __init__(self, pool: "ScenePool", rows: np.ndarray, patch: Tuple[int, int]):
+        self.pool, self.rows, self.patch = pool, rows, patch
+
+    @property
+    def shape(self):
+        return (self.rows.shape[0], self.patch[0], self.patch[1], self.pool.channels)
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    def __getitem__(self, sl):
+        if not isinstance(sl, slice):
+            raise TypeError("a SceneBatch is sliced, not indexed")
+        return SceneBatch(self.pool, np.ascontiguousarray(self.rows[sl]), self.patch)
+
+    def shard(self, rank: int, world: int) -> "SceneBatch":
+        """This rank's contiguous share of a global batch (the split Model._local_batch makes)."""
+        B = len(self)
+        if B % world:
+            raise ValueError(f"global batch {B} not divisible by {world} replicas")
+        return self[rank * (B // world):(rank + 1) * (B // world)]
+
+    def host(self):
+        """host_windows of this batch."""
+        return host_windows(self.pool.images, self.pool.class_maps, self.rows, self.patch)
+
+
+class ScenePool:
+    """Scenes uploaded once: uint8 H x W x C images (one C for all) and, for training, their uint8 H x W class maps.  Keeps the
+    host arrays of device pointers and sizes rua_scene_windows takes.  patch: checked against every scene, and the default of
+    batch().  device "cpu" keeps the scenes in host memory: table checks and host_windows work, the engine refuses it."""
+
+    def __init__(self, images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]] = None, patch=None, device="cuda"):
+        import torch
+        self.images = [np.ascontiguousarray(im) for im in images]
+        self.class_maps = None if class_maps is None else [np.ascontiguousarray(cm) for cm in class_maps]
+        self.channels = check_scenes(self.images, self.class_maps)
+        self.shapes: List[Tuple[int, int]] = [(im.shape[0], im.shape[1]) for im in self.images]
+        self.patch = None if patch is None else _patch2(patch)
+        if self.patch is not None:
+            for s, (H, W) in enumerate(self.shapes):
+                if H < self.patch[0] or W < self.patch[1]:
+                    raise ValueError(f"scene {s} is {H} x {W}: smaller than the {self.patch[0]} x {self.patch[1]} patch")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.img_dev = [torch.from_numpy(im).to(self.device) for im in self.images]
+        self.cls_dev = None if self.class_maps is None else [torch.from_numpy(cm).to(self.device) for cm in self.class_maps]
+        n = len(self.images)
+        self.img_ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in self.img_dev])
+        self.cls_ptrs = None if self.cls_dev is None else (C.c_void_p * n)(*[t.data_ptr() for t in self.cls_dev])
+        self.heights = (C.c_int32 * n)(*[h for h, _ in self.shapes])
+        self.widths = (C.c_int32 * n)(*[w for _, w in self.shapes])
+
+    def __len__(self):
+        return len(self.images)
+
+    def batch(self, rows, patch=None) -> SceneBatch:
+        """The batch of these table rows; ValueError (rua_scene_windows' wording) for a row the kernel would refuse."""
+        p = self.patch if patch is None else _patch2(patch)
+        if p is None:
+            raise ValueError("no patch size: give ScenePool(patch=) or batch(rows, patch)")
+        return SceneBatch(self, check_table(self.shapes, rows, p), p)
+
+
+class SceneLoader:
+    """loader.PrefetchLoader's iteration over a window table instead of files: `len(order) // batch_size` batches per pass, the
+    last partial batch dropped, `batch_size` the GLOBAL batch of which rank r yields rows [r * B / world, (r + 1) * B / world).
+    Yields (SceneBatch, None); order: indices into `table` (default: all of it, in order)."""
+
+    def __init__(self, pool: ScenePool, table: np.ndarray, batch_size: int, patch=None, order: Optional[Sequence[int]] = None,
+                 rank: int = 0, world: int = 1):
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        if world < 1 or not (0 <= rank < world):
+            raise ValueError(f"rank {rank} outside world {world}")
+        if batch_size % world:
+            raise ValueError(f"global batch {batch_size} not divisible by {world} replicas")
+        self.pool, self.table, self.patch = pool, np.asarray(table), patch
+        self.B, self.rank, self.local_B = int(batch_size), int(rank), int(batch_size) // int(world)
+        self.order = np.arange(len(self.table)) if order is None else np.asarray(order, dtype=np.int64)
+
+    def __len__(self) -> int:
+        return len(self.order) // self.B
+
+    def set_order(self, order: Sequence[int]) -> None:
+        self.order = np.asarray(order, dtype=np.int64)
+
+    def __iter__(self):
+        for k in range(len(self)):
+            first = k * self.B + self.rank * self.local_B
+            yield self.pool.batch(self.table[self.order[first:first + self.local_B]], self.patch), None
+
+
+# ---- scene directories ------------------------------------------------------------------------------------------------------
+def save_scene_dir(root: str, names: Sequence[str], images: Sequence[np.ndarray], class_maps: Sequence[np.ndarray]) -> None:
+    check_scenes(images, class_maps)
+    os.makedirs(os.path.join(root, "scenes"), exist_ok=True)
+    os.makedirs(os.path.join(root, "labels", "scenes"), exist_ok=True)
+    for n, im, cm in zip(names, images, class_maps):
+        np.save(os.path.join(root, "scenes", n + ".npy"), im)
+        np.save(os.path.join(root, "labels", "scenes", n + ".npy"), cm)
+
+
+def load_scene_dir(root: str):
+    """(names, images, class maps) of a scene directory, sorted by name and paired by file name."""
+    files = sorted(n for n in os.listdir(os.path.join(root, "scenes")) if n.endswith(".npy"))
+    if not files:
+        raise FileNotFoundError(f"{os.path.join(root, 'scenes')} holds no .npy scene")
+    have = set(os.listdir(os.path.join(root, "labels", "scenes")))
+    missing = [n for n in files if n not in have]
+    if missing:
+        raise FileNotFoundError(f"labels/scenes lacks {len(missing)} scenes, e.g. {missing[0]}")
+    images = [np.load(os.path.join(root, "scenes", n)) for n in files]
+    class_maps = [np.load(os.path.join(root, "labels", "scenes", n)) for n in files]
+    try:
+        check_scenes(images, class_maps)
+    except ValueError as exc:
+        raise ValueError(f"{root}: {exc} (scenes in name order: {files})") from None
+    return [n[:-4] for n in files], images, class_maps
+
+
+def patch_name(k: int) -> str:
+    return f"patch_{k}.npy"
+
+
+def patch_index(name: str) -> int:
+    """k of `patch_{k}.npy` (a bare name or a path)."""
+    base = os.path.basename(name)
+    if not (base.startswith("patch_") and base.endswith(".npy") and base[6:-4].isdigit()):
+        raise ValueError(f"{name}: not a patch_<k>.npy name")
+    return int(base[6:-4])
+
+
+def materialize(root: str, dst: str, patch, stride: int, data_aug: bool, chunk: int = 256) -> int:
+    """Writes the compact patch layout of a scene directory's window table: <dst>/images/patch_{k}.npy and
+    <dst>/labels/classes/patch_{k}.npy for table row k.  Returns the number of patches."""
+    _, images, class_maps = load_scene_dir(root)
+    table = window_table([im.shape for im in images], patch, stride, data_aug)
+    os.makedirs(os.path.join(dst, "images"), exist_ok=True)
+    os.makedirs(os.path.join(dst, "labels", "classes"), exist_ok=True)
+    for k0 in range(0, len(table), chunk):
+        img, cls = host_windows(images, class_maps, table[k0:k0 + chunk], patch)
+        for k in range(len(img)):
+            np.save(os.path.join(dst, "images", patch_name(k0 + k)), img[k])
+            np.save(os.path.join(dst, "labels", "classes", patch_name(k0 + k)), cls[k])
+    return len(table)
+
+
+# ---- the reference's inputs -------------------------------------------------------------------------------------------------
+def colours_to_classes(ref_hwc: np.ndarray, colours=None) -> np.ndarray:
+    """uint8 class map of a colour-coded H x W x 3 label image; ValueError naming the first (row-major) pixel of an unknown colour."""
+    colours = ISPRS_COLOURS if colours is None else colours
+    a = np.asarray(ref_hwc)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"a colour-coded reference is H x W x 3, got {a.shape}")
+    key = (a[..., 0].astype(np.int64) << 16) | (a[..., 1].astype(np.int64) << 8) | a[..., 2].astype(np.int64)
+    out = np.zeros(a.shape[:2], np.uint8)
+    known = np.zeros(a.shape[:2], bool)
+    for (r, g, b), v in colours.items():
+        m = key == ((r << 16) | (g << 8) | b)
+        out[m] = v
+        known |= m
+    if not known.all():
+        i, j = np.unravel_index(int(np.argmin(known)), known.shape)
+        raise ValueError(f"unknown colour {tuple(int(v) for v in a[i, j])} at row {i}, column {j}: not one of {sorted(colours)}")
+    return out
+
+
+def convert_reference_inputs(image_chw: np.ndarray, reference_chw: np.ndarray):
+    """(uint8 H x W x C image, uint8 H x W class map) from the reference's C x H x W Image_Train / Reference_Train arrays."""
+    if image_chw.ndim != 3 or reference_chw.ndim != 3:
+        raise ValueError(f"C x H x W arrays expected, got {image_chw.shape} and {reference_chw.shape}")
+    if image_chw.dtype != np.uint8:
+        raise ValueError(f"the image must be uint8, got {image_chw.dtype}")
+    if image_chw.shape[1:] != reference_chw.shape[1:]:
+        raise ValueError(f"image is {image_chw.shape[1:]}, reference {reference_chw.shape[1:]}")
+    img = np.ascontiguousarray(image_chw.transpose(1, 2, 0))
+    return img, colours_to_classes(reference_chw.transpose(1, 2, 0))
+
+
+def _yes(v) -> bool:
+    s = str(v).lower()
+    if s in ("yes", "true", "t", "y", "1"):
+        return True
+    if s in ("no", "false", "f", "n", "0"):
+        return False
+    raise argparse.ArgumentTypeError("Boolean value expected.")
+
+
+def main(argv=None) -> int:
+    p = argparse.ArgumentParser(description="write a scene directory from the reference's Image_Train.npy / Reference_Train.npy")
+    p.add_argument("--image", required=True, help="C x H x W uint8 image (.npy)")
+    p.add_argument("--reference", required=True, help="3 x H x W colour-coded labels (.npy)")
+    p.add_argument("--dst", required=True, help="output scene directory: scenes/ and labels/scenes/")
+    p.add_argument("--name", default="scene", help="file name of the scene")
+    p.add_argument("--materialize", default=None, metavar="DST", help="also write the compact patch layout of the window table there")
+    p.add_argument("-ps", "--patch_size", type=int, default=256)
+    p.add_argument("--stride", type=int, default=32)
+    p.add_argument("--data_aug", type=_yes, default=True)
+    a = p.parse_args(argv)
+    img, cls = convert_reference_inputs(np.load(a.image), np.load(a.reference))
+    save_scene_dir(a.dst, [a.name], [img], [cls])
+    print(f"scene {a.name}: {img.shape[0]} x {img.shape[1]} x {img.shape[2]} written to {a.dst}")
+    if a.materialize:
+        n = materialize(a.dst, a.materialize, a.patch_size, a.stride, a.data_aug)
+        print(f"{n} patches written to {a.materialize}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -14,6 +14,10 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
     Keras' own weight layout (plus this package's metadata and optimizer state, written without h5py by h5lite).
   * `--compact_dataset yes --norm_type {1,2}`: read the compact layout (uint8 images/ and labels/classes/, written by
     `python -m resunet_a_mltsk_keras_amd.compact`); x and the seg / bound / dist / color targets are built on the GPU.
+  * `--scene_dataset yes --stride S --data_aug {yes,no}` (with `-ps`, `--norm_type`): `-dp` is a scene directory (scenes/ and
+    labels/scenes/, written by `python -m resunet_a_mltsk_keras_amd.scenes`).  The scenes stay on the GPU and every step cuts and
+    augments its patches there; the patch set, its split and its order are those of a `--compact_dataset yes` run on the
+    directory `scenes.materialize` writes from the same arguments.
   * `--dtype {bf16,f32}`, `--seed`: engine options.  Launch with torch.distributed.run for multi-GPU data
     parallel (`-bs` is then the GLOBAL batch, as under MirroredStrategy).
 """
@@ -71,6 +75,10 @@ def build_parser():
     p.add_argument("--compact_dataset", type=str2bool, default=False,
                    help="dataset in the compact layout: images/<name>.npy (uint8 HxWxC) + labels/classes/<name>.npy (uint8 HxW)")
     p.add_argument("--norm_type", type=int, default=1, choices=[1, 2], help="compact layout: x = u8 / 255 (1) or u8 / 126.5 (2)")
+    p.add_argument("--scene_dataset", type=str2bool, default=False,
+                   help="dataset is a scene directory: scenes/<name>.npy (uint8 HxWxC) + labels/scenes/<name>.npy (uint8 HxW); patches are cut on the GPU")
+    p.add_argument("--stride", type=int, default=32, help="scene directory: window stride")
+    p.add_argument("--data_aug", type=str2bool, default=True, help="scene directory: every window five times (as is, rot90, rot180, flipped rows, flipped columns)")
     return p
 
 
@@ -102,6 +110,14 @@ def list_compact_dataset(root):
     if missing:
         raise FileNotFoundError(f"labels/classes lacks {len(missing)} patches, e.g. {missing[0]}")
     return [os.path.join(root, "images", n) for n in names], {"classes": [os.path.join(root, "labels", "classes", n) for n in names]}
+
+
+def list_scene_dataset(n_patches):
+    """The listing list_compact_dataset would give for the materialised dataset of an n-row window table (scenes.materialize
+    writes row k as patch_{k}.npy): the file names in lexicographic order, as the images and as the labels."""
+    from resunet_a_mltsk_keras_amd.scenes import patch_name
+    names = sorted(patch_name(k) for k in range(n_patches))
+    return names, {"classes": list(names)}
 
 
 def split_dataset(xs, ys):
@@ -143,7 +159,7 @@ def agree_from_rank0(value, world):
 
 
 def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, n_classes, patience=10, delta=0.001,
-                metrics_names=None, rank=0, world=1):
+                metrics_names=None, rank=0, world=1, scenes=None):
     say = print if rank == 0 else (lambda *a, **k: None)
     say("Start training...\n" + "=" * 60)
     say(f"Training on {len(x_tr)} images\nValidating on {len(x_va)} images\n" + "=" * 60 + f"\nTotal Epochs: {epochs}")
@@ -155,12 +171,20 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
     # under data parallel `batch_size` is the global batch and every rank reads only its own shard of it
     # compact layout: uint8 slots, and the targets are built on the GPU from the class map
     compact = bool(getattr(args, "compact_dataset", False))
-    ld_tr = PrefetchLoader(x_tr, y_tr, batch_size, rank=rank, world=world, keep_dtype=compact)
-    ld_va = PrefetchLoader(x_va, y_va, batch_size, rank=rank, world=world, keep_dtype=compact)
+    if scenes is None:
+        ld_tr = PrefetchLoader(x_tr, y_tr, batch_size, rank=rank, world=world, keep_dtype=compact)
+        ld_va = PrefetchLoader(x_va, y_va, batch_size, rank=rank, world=world, keep_dtype=compact)
+    else:
+        # scenes = (ScenePool, window table): x_tr / x_va are patch_{k}.npy names of table rows k; no files, no loader threads - a
+        # batch is its rows of the table, and every rank holds the pool and takes its own rows
+        from resunet_a_mltsk_keras_amd.scenes import SceneLoader, patch_index
+        pool, table = scenes
+        ld_tr = SceneLoader(pool, table[[patch_index(n) for n in x_tr]], batch_size, args.patch_size, rank=rank, world=world)
+        ld_va = SceneLoader(pool, table[[patch_index(n) for n in x_va]], batch_size, args.patch_size, rank=rank, world=world)
     shard = dict(local_shard=True) if world > 1 else {}
-    if compact:
+    if compact or scenes is not None:
         shard["norm_type"] = args.norm_type
-    labels = (lambda yb: yb["classes"]) if compact else (lambda yb: yb if args.multitasking else yb["seg"])
+    labels = (lambda yb: None) if scenes is not None else (lambda yb: yb["classes"]) if compact else (lambda yb: yb if args.multitasking else yb["seg"])
     min_loss, cont = float("inf"), 0
     rng = np.random.default_rng(args.seed)
     say(net.output_names)
@@ -229,10 +253,20 @@ def main(argv=None):
     from resunet_a_mltsk_keras_amd.keras_api import (SGD, Adam, BinaryCrossentropy, CategoricalCrossentropy, K, MeanSquaredError,
                                                    load_model, weighted_categorical_crossentropy)
 
-    xs, ys = list_compact_dataset(args.dataset_path) if args.compact_dataset else list_dataset(args.dataset_path, args.multitasking)
+    scenes = None
+    if args.scene_dataset:
+        if args.compact_dataset:
+            sys.exit("--scene_dataset and --compact_dataset name two different layouts of -dp: give one of them")
+        from resunet_a_mltsk_keras_amd.scenes import ScenePool, load_scene_dir, window_table
+        _, images, class_maps = load_scene_dir(args.dataset_path)
+        table = window_table([im.shape for im in images], args.patch_size, args.stride, args.data_aug)
+        scenes = (ScenePool(images, class_maps, patch=args.patch_size), table)
+        xs, ys = list_scene_dataset(len(table))
+    else:
+        xs, ys = list_compact_dataset(args.dataset_path) if args.compact_dataset else list_dataset(args.dataset_path, args.multitasking)
     x_tr, y_tr, x_va, y_va = split_dataset(xs, ys)
     rows = cols = args.patch_size
-    channels = args.channels or int(np.load(xs[0]).shape[-1])
+    channels = args.channels or (int(images[0].shape[-1]) if scenes is not None else int(np.load(xs[0]).shape[-1]))
     optm = Adam(lr=args.learning_rate, beta_1=0.9) if args.optimizer == "adam" else SGD(lr=args.learning_rate, momentum=0.8)
     say("=" * 60)
     if args.loss == "cross_entropy":
@@ -277,7 +311,7 @@ def main(argv=None):
     x_shape = (args.batch_size, rows, cols, channels)
     t0 = time.time()
     train_model(args, model, x_tr, y_tr, x_va, y_va, args.batch_size, args.epochs, x_shape, args.num_classes,
-                metrics_names=model.metrics_names, rank=rank, world=world)
+                metrics_names=model.metrics_names, rank=rank, world=world, scenes=scenes)
     say(f"\nTraining took: {(time.time() - t0) / 3600} \n")
     if world > 1:
         import torch.distributed as dist
