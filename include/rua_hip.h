@@ -21,6 +21,7 @@ extern "C" {
 #define RUA_BF16 1
 #define RUA_MAX_SEG 6
 #define RUA_MAX_BRANCH 4
+#define RUA_MAX_WGRAD_BATCH 32  /* members of one grid of the batched form of rua_conv_wgrad_group (rua_wgrad_desc.batch): a whole step's small weight gradients */
 #define RUA_MAX_WGRAD_GROUP 8   /* members of one rua_conv_wgrad_group call (both convolutions of every branch of a ResBlock) */
 
 #define RUA_OK 0
@@ -169,7 +170,10 @@ typedef struct rua_wgrad_desc {
    * kernel sizes its persistent grid for a share of the chip - one round of blocks for the whole group, 1 / group_members of the
    * block partials to write and to reduce.  Set it on every member (rua_wgrad_plan must see the same value as the launch). */
   int32_t group_members;
-  int32_t pad_group;
+  /* batch != 0: a member of the BATCHED form of rua_conv_wgrad_group - unequal weight gradients of the generic bf16 tile kernel (rua_wgrad_kind() == 0,
+   * rua_wgrad_img_kind() == 0) in one compact grid that shares ONE block budget: the member's K split depends on the whole call, so its pending record comes
+   * from rua_wgrad_group_plan over the same descriptors, not from rua_wgrad_plan.  Ignored by rua_conv_wgrad and by groups with other members. */
+  int32_t batch;
   /* overwrite_dev (optional): a DEVICE int32 read when the kernel runs.  Non-zero: the caller guarantees that dw holds zeros and that this call is its only
    * writer before it is read (the step's gradient arena: zeroed by the optimizer, every weight has one producer) - kernels that end in a read-modify-write of dw
    * (one K slice per element, the slab / block-partial reductions) then STORE instead: dw = sum, one pass over dw spared.  Zero / NULL: dw += sum (gradient
@@ -196,11 +200,22 @@ int rua_wgrad_plan(const rua_wgrad_desc* d, rua_wgrad_pending* out);
  * block_begin, total_blocks = sum of their `blocks` */
 int rua_wgrad_reduce_batch(const rua_wgrad_pending* items_dev, int n_items, int total_blocks, void* stream);
 int rua_conv_wgrad(const rua_wgrad_desc* d, void* stream);
-/* n (<= RUA_MAX_WGRAD_GROUP) INDEPENDENT weight gradients - the dilation branches of a ResBlock (model2.py:26-31), first and second convolutions - with the results of n
+/* n (<= RUA_MAX_WGRAD_GROUP; the batched form below: more) INDEPENDENT weight gradients - the dilation branches of a ResBlock (model2.py:26-31), first and second convolutions - with the results of n
  * rua_conv_wgrad calls; members on the same kernel run as ONE grid.  Members must not share dw or partial-sum workspace (a group
  * that does runs member by member). */
 int rua_conv_wgrad_group(const rua_wgrad_desc* d, int n, void* stream);
 int rua_wgrad_group_last_grids(void);            /* grids the calling thread's latest rua_conv_wgrad_group issued */
+/* The batched form: when EVERY member has rua_wgrad_desc.batch set, is bf16 and lands on the generic tile kernel, the call takes any number of members (up to
+ * 4 * RUA_MAX_WGRAD_BATCH) and issues ceil(n / RUA_MAX_WGRAD_BATCH) grids (consecutive members, in the caller's order, share a grid).  A grid is exactly the sum
+ * of its members' blocks, the longest blocks first; a block finds its member from prefix sums in the kernel arguments.  The grid has one block budget (tuning
+ * key wgrad_batch_blocks, 0 = 4 per CU) dealt by work: member i asks for budget * stages_i / sum_j(stages_j * tiles_j) K slices (stages: 64-pixel steps of its K
+ * range, tiles: 64 x 64 tiles of its dW), at least 1, at most its stages and the fp32 slabs its workspace holds.  A member left with one slice writes dW itself
+ * (honouring overwrite_dev); the others leave slabs: summed by the call, or - defer - by rua_wgrad_reduce_batch from the records of rua_wgrad_group_plan.
+ * Bit 5 of the tuning key wgrad_group: every member keeps the K split it would take alone - the batch is then bit-identical to n rua_conv_wgrad calls; without
+ * it (the default) the results differ by the order of the fp32 sums only, and stay deterministic.  Members whose slabs overlap run one by one.
+ * rua_wgrad_group_plan: out[i] = the record member i of rua_conv_wgrad_group(d, n) leaves (kind 0: none); for calls that do not take the batched form it is
+ * rua_wgrad_plan per member. */
+int rua_wgrad_group_plan(const rua_wgrad_desc* d, int n, rua_wgrad_pending* out);
 int64_t rua_wgrad_workspace_bytes(const rua_wgrad_desc* d);
 int rua_wgrad_kind(const rua_wgrad_desc* d);   /* 0: generic tiled kernel, 1: all-taps kernel + deterministic partial reduce,
                                                   2: wgrad_dmap (wide levels), 3: wgrad_pw (narrow 1x1) */

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RUA_LIB_PATH") or os.path.join(HERE, "librua_hip.so")   # RUA_LIB_PATH: experiment builds only
 
 RUA_F32, RUA_BF16 = 0, 1
-RUA_MAX_SEG, RUA_MAX_BRANCH, RUA_MAX_WGRAD_GROUP = 6, 4, 8
+RUA_MAX_SEG, RUA_MAX_BRANCH, RUA_MAX_WGRAD_GROUP, RUA_MAX_WGRAD_BATCH = 6, 4, 8, 32
 LOSS_TANIMOTO, LOSS_WCE, LOSS_CE_LOGITS, LOSS_BCE_LOGITS, LOSS_MSE = 0, 1, 2, 3, 4
 ACT_NONE, ACT_SOFTMAX, ACT_SIGMOID = 0, 1, 2
 
@@ -36,7 +36,7 @@ class BnFold(C.Structure):
 class WgradDesc(C.Structure):
     _fields_ = [("a", vp), ("C", i32), ("Hs", i32), ("Ws", i32), ("dy", vp), ("Cout", i32), ("H", i32), ("W", i32),
                 ("N", i32), ("stride", i32), ("dil", i32), ("taps", i32), ("dtype", i32), ("dw", vp), ("workspace", vp), ("workspace_bytes", i64),
-                ("in_scale", vp), ("in_shift", vp), ("in_relu", i32), ("defer", i32), ("group_members", i32), ("pad_group", i32), ("overwrite_dev", vp)]
+                ("in_scale", vp), ("in_shift", vp), ("in_relu", i32), ("defer", i32), ("group_members", i32), ("batch", i32), ("overwrite_dev", vp)]
 
 
 class WgradPending(C.Structure):
@@ -100,6 +100,7 @@ _SIGS = {
     "rua_conv_sum_kernel": ([C.POINTER(ConvDesc), i32], i32),
     "rua_conv_wgrad_group": ([C.POINTER(WgradDesc), i32, vp], i32),
     "rua_wgrad_group_last_grids": ([], i32),
+    "rua_wgrad_group_plan": ([C.POINTER(WgradDesc), i32, C.POINTER(WgradPending)], i32),
     "rua_profile_mid_event": ([vp], None),
     "rua_profile_mid_event_fired": ([], i32),
     "rua_prof_event_create": ([], vp),

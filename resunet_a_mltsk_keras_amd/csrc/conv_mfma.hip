@@ -2419,7 +2419,7 @@ struct WgK {
 };
 
 template <typename T>
-__device__ __forceinline__ void wgrad_kernel_body(const WgK& p) {
+__device__ __forceinline__ void wgrad_kernel_body(const WgK& p, int b) {
   constexpr int VEC = ET<T>::VEC, ES = sizeof(T);
   constexpr int TP = 64;                         // pixels per stage
   constexpr int PPR = 64 / VEC;                  // pieces per 64-channel row
@@ -2428,7 +2428,6 @@ __device__ __forceinline__ void wgrad_kernel_body(const WgK& p) {
   __shared__ __attribute__((aligned(16))) unsigned char sD[TP * ROWB];   // dy tile  [pix][co]
   __shared__ __attribute__((aligned(16))) unsigned char sX[TP * ROWB];   // a  tile  [pix][ci]
 
-  int b = blockIdx.x;
   const int ks = b % p.ksplit; b /= p.ksplit;
   const int ti = b % p.nti; b /= p.nti;
   const int tc = b % p.ntc; b /= p.ntc;
@@ -2546,7 +2545,7 @@ __device__ __forceinline__ void wgrad_kernel_body(const WgK& p) {
     }
   }
 }
-template <typename T> __global__ __launch_bounds__(256) void wgrad_kernel(const WgK p) { wgrad_kernel_body<T>(p); }
+template <typename T> __global__ __launch_bounds__(256) void wgrad_kernel(const WgK p) { wgrad_kernel_body<T>(p, (int)blockIdx.x); }
 // grouped launch (rua_conv_wgrad_group): the weight gradients of the dilation branches of a ResBlock in ONE grid; blockIdx.y picks
 // the member, blocks beyond a member's own grid leave at once
 struct WgKG { WgK k[RUA_MAX_WGRAD_GROUP]; };
@@ -2554,7 +2553,19 @@ static_assert(sizeof(WgKG) <= 4096, "grouped launch: kernel arguments are limite
 __global__ __launch_bounds__(256) void wgrad_kernel_g(const WgKG g) {
   const WgK& p = g.k[blockIdx.y];
   if ((long long)blockIdx.x >= (long long)p.ntc * p.nti * p.taps * p.ksplit) return;
-  wgrad_kernel_body<bf16_t>(p);
+  wgrad_kernel_body<bf16_t>(p, (int)blockIdx.x);
+}
+// batched launch (rua_conv_wgrad_group, members with rua_wgrad_desc.batch set that all land on this kernel): UNEQUAL weight gradients - a step's wide 1x1 convolutions on
+// small maps - in one COMPACT grid: exactly the sum of the members' blocks, longest blocks first.  end[i] = first block behind member i (prefix sums, in the
+// kernel arguments): a block finds its member by scalar compares, no division
+struct WgKB { WgK k[RUA_MAX_WGRAD_BATCH]; unsigned end[RUA_MAX_WGRAD_BATCH]; int n; };
+static_assert(sizeof(WgKB) <= 4096, "batched launch: kernel arguments are limited to 4 KiB");
+__global__ __launch_bounds__(256) void wgrad_kernel_b(const WgKB g) {
+  const unsigned b = blockIdx.x;
+  int m = 0;
+  for (int i = 0; i + 1 < g.n; ++i) m += (b >= g.end[i]) ? 1 : 0;
+  const unsigned first = m ? g.end[m - 1] : 0u;
+  wgrad_kernel_body<bf16_t>(g.k[m], (int)(b - first));
 }
 
 // dw += sum of the K slices' slabs, in a FIXED order (bit-reproducible).  A thread owns one float4 column and walks the slices
@@ -4632,6 +4643,10 @@ static int wgrad_img_pick(const rua_wgrad_desc* d) {
 }
 extern "C" int rua_wgrad_img_kind(const rua_wgrad_desc* d) { return (d && rua_wgrad_kind(d) == 0) ? wgrad_img_pick(d) : 0; }
 
+// a member of a batched launch (wgrad_batch_launch / rua_wgrad_group_plan): rua_conv_wgrad takes the K split from here and hands its kernel arguments back
+struct WgBatchMember { long long want; WgK k; unsigned grid; long long ndw; };
+static thread_local WgBatchMember* g_wg_batch = nullptr;
+
 extern "C" int rua_conv_wgrad(const rua_wgrad_desc* d, void* stream) {
   RUA_CHECK_ARG(d && d->a && d->dy && d->dw, "rua_conv_wgrad: null pointer");
   RUA_CHECK_ARG(d->dtype == RUA_F32 || d->dtype == RUA_BF16, "rua_conv_wgrad: bad dtype");
@@ -4706,6 +4721,7 @@ extern "C" int rua_conv_wgrad(const rua_wgrad_desc* d, void* stream) {
   const int target = (g_tune.wgrad_blocks > 0 ? g_tune.wgrad_blocks : 2 * rua_cu_count()) / wshare;      // 512 on MI355X
   long long want = target / tiles; if (want < 1) want = 1;
   long long stages = (k.M + 63) / 64;
+  if (g_wg_batch && g_wg_batch->want > 0) want = g_wg_batch->want;      // a member of a batched launch: its share of the batch's blocks (wgrad_batch_split)
   if (want > stages) want = stages;
   const long long ndw = (long long)d->taps * d->Cout * d->C;
   const int cap = (g_tune.wgrad_slabs && ndw % 4 == 0) ? slab_capacity(d, ndw) : 0;
@@ -4719,6 +4735,7 @@ extern "C" int rua_conv_wgrad(const rua_wgrad_desc* d, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (k.slabs) note_pending(2, k.ksplit, ndw, k.slabs, d->dw, 0, (int)((ndw / 4 + SLAB_RED_COLS - 1) / SLAB_RED_COLS));
   if (g_wgrad_dry) return RUA_OK;
+  if (g_wg_batch) { g_wg_batch->k = k; g_wg_batch->grid = (unsigned)grid; g_wg_batch->ndw = ndw; return RUA_OK; }      // issued by wgrad_batch_launch
   if (g_wg_group && (g_tune.wgrad_group & 1) && g_wg_group->n < RUA_MAX_WGRAD_GROUP && d->dtype == RUA_BF16) {
     WgGroupCapture& c = *g_wg_group; const int i = c.n++;
     c.kind[i] = 0; c.gx[i] = (unsigned)grid; c.smem[i] = 0; c.g[i] = k;
@@ -4738,9 +4755,115 @@ extern "C" int rua_conv_wgrad(const rua_wgrad_desc* d, void* stream) {
 // such a group runs member by member.
 static thread_local int g_wg_group_last_grids = 0;
 extern "C" int rua_wgrad_group_last_grids(void) { return g_wg_group_last_grids; }
+
+// The batched form: every member lands on the generic bf16 tile kernel (rua_wgrad_kind() == 0, no whole-image kernel) and asks for it
+// (rua_wgrad_desc.batch).  Any number of members; RUA_MAX_WGRAD_BATCH per grid (the kernel arguments), so ceil(n / RUA_MAX_WGRAD_BATCH) grids.
+constexpr int WG_BATCH_MAX_MEMBERS = 4 * RUA_MAX_WGRAD_BATCH;
+static bool wgrad_batch_ok(const rua_wgrad_desc* d, int n) {
+  if (!(g_tune.wgrad_group & 1) || n > WG_BATCH_MAX_MEMBERS) return false;
+  for (int i = 0; i < n; ++i) {
+    if (!d[i].a || !d[i].dy || !d[i].dw || d[i].dtype != RUA_BF16 || !d[i].batch || d[i].in_scale) return false;
+    if (d[i].C <= 0 || d[i].Cout <= 0 || d[i].C % 8 || d[i].Cout % 8 || (d[i].taps != 1 && d[i].taps != 9)) return false;
+    if (rua_wgrad_kind(d + i) != 0 || wgrad_img_pick(d + i) != 0) return false;
+  }
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j) if (d[i].dw == d[j].dw) return false;
+  return true;
+}
+// One block budget for the members [0, n) of ONE grid, dealt by work (a pure function of the descriptors): a member's work is stages x tiles (64-pixel stages of
+// its K range, 64 x 64 tiles of its dW), and it gets that share of the budget as blocks - so every block of the grid runs about work / budget stages, whichever
+// member it belongs to.  want[i] = K slices asked for (rua_conv_wgrad bounds it by the member's stages and slab capacity); 0: the split it would take alone
+// (bit 5 of wgrad_group: the batch is then bit-identical to the single launches).
+static void wgrad_batch_split(const rua_wgrad_desc* d, int n, long long* want) {
+  long long work = 0;
+  for (int i = 0; i < n; ++i)
+    work += (((long long)d[i].N * d[i].H * d[i].W + 63) / 64) * ((d[i].Cout + 63) / 64) * ((d[i].C + 63) / 64) * d[i].taps;
+  const long long budget = g_tune.wgrad_batch_blocks > 0 ? g_tune.wgrad_batch_blocks : 4ll * rua_cu_count();
+  for (int i = 0; i < n; ++i) {
+    const long long stages = ((long long)d[i].N * d[i].H * d[i].W + 63) / 64;
+    long long w = work > 0 ? (budget * stages + work / 2) / work : 1;           // blocks of the member / its tiles
+    want[i] = (g_tune.wgrad_group & 32) ? 0 : (w < 1 ? 1 : w);
+  }
+}
+// geometry of the members of one grid: kernel arguments, grid and (through g_wgrad_pending, one record per member) the partials each leaves
+static int wgrad_batch_members(const rua_wgrad_desc* d, int n, WgBatchMember* mem, rua_wgrad_pending* recs, bool dry) {
+  long long want[RUA_MAX_WGRAD_BATCH];
+  wgrad_batch_split(d, n, want);
+  int rc = RUA_OK;
+  for (int i = 0; i < n && rc == RUA_OK; ++i) {
+    mem[i].want = want[i]; mem[i].grid = 0;
+    if (recs) { memset(recs + i, 0, sizeof(*recs)); g_wgrad_pending = recs + i; }
+    g_wg_batch = mem + i; g_wgrad_dry = dry;
+    rc = rua_conv_wgrad(d + i, nullptr);
+    g_wg_batch = nullptr; g_wgrad_dry = false; g_wgrad_pending = nullptr;
+    if (recs) recs[i].overwrite_dev = d[i].overwrite_dev;
+  }
+  return rc;
+}
+static int wgrad_batch_launch(const rua_wgrad_desc* d, int n, hipStream_t st) {
+  int grids = 0;
+  for (int base = 0; base < n; base += RUA_MAX_WGRAD_BATCH) {
+    const int m = n - base < RUA_MAX_WGRAD_BATCH ? n - base : RUA_MAX_WGRAD_BATCH;
+    WgBatchMember mem[RUA_MAX_WGRAD_BATCH];
+    const int rc = wgrad_batch_members(d + base, m, mem, nullptr, false);
+    if (rc != RUA_OK) return rc;
+    int order[RUA_MAX_WGRAD_BATCH];
+    for (int i = 0; i < m; ++i) order[i] = i;
+    for (int i = 1; i < m; ++i) {                          // longest blocks first (stable: equal members keep the caller's order)
+      const int o = order[i]; int j = i;
+      while (j > 0 && mem[order[j - 1]].k.pix_per_block < mem[o].k.pix_per_block) { order[j] = order[j - 1]; --j; }
+      order[j] = o;
+    }
+    WgKB g;
+    unsigned long long total = 0;
+    for (int i = 0; i < m; ++i) { g.k[i] = mem[order[i]].k; total += mem[order[i]].grid; g.end[i] = (unsigned)total; }
+    for (int i = m; i < RUA_MAX_WGRAD_BATCH; ++i) { g.k[i] = g.k[0]; g.end[i] = (unsigned)total; }
+    g.n = m;
+    RUA_CHECK_ARG(total >= 1 && total < (1ull << 31), "rua_conv_wgrad_group: grid too large");
+    hipLaunchKernelGGL(wgrad_kernel_b, dim3((unsigned)total), dim3(256), 0, st, g);
+    RUA_LAUNCH_CHECK("wgrad_kernel_b");
+    ++grids;
+    for (int i = 0; i < m; ++i)                            // members that did not defer their reduction
+      if (mem[i].k.slabs && !d[base + i].defer) { const int rr = launch_slab_reduce(mem[i].k.slabs, mem[i].k.dw, mem[i].ndw, mem[i].k.ksplit, st); if (rr != RUA_OK) return rr; }
+  }
+  g_wg_group_last_grids = grids;
+  return RUA_OK;
+}
+extern "C" int rua_wgrad_group_plan(const rua_wgrad_desc* d, int n, rua_wgrad_pending* out) {
+  RUA_CHECK_ARG(d && out && n >= 1, "rua_wgrad_group_plan: bad arguments");
+  if (!wgrad_batch_ok(d, n)) {
+    for (int i = 0; i < n; ++i) { const int rc = rua_wgrad_plan(d + i, out + i); if (rc != RUA_OK) return rc; }
+    return RUA_OK;
+  }
+  for (int base = 0; base < n; base += RUA_MAX_WGRAD_BATCH) {
+    const int m = n - base < RUA_MAX_WGRAD_BATCH ? n - base : RUA_MAX_WGRAD_BATCH;
+    WgBatchMember mem[RUA_MAX_WGRAD_BATCH];
+    const int rc = wgrad_batch_members(d + base, m, mem, out + base, true);
+    if (rc != RUA_OK) return rc;
+  }
+  return RUA_OK;
+}
 extern "C" int rua_conv_wgrad_group(const rua_wgrad_desc* d, int n, void* stream) {
-  RUA_CHECK_ARG(d && n >= 1 && n <= RUA_MAX_WGRAD_GROUP, "rua_conv_wgrad_group: 1..%d members", RUA_MAX_WGRAD_GROUP);
+  RUA_CHECK_ARG(d && n >= 1, "rua_conv_wgrad_group: no members");
   hipStream_t st = (hipStream_t)stream;
+  if (wgrad_batch_ok(d, n)) {
+    // members whose slabs overlap (a shared workspace) cannot run at once: member by member, as any group that shares workspace
+    static thread_local rua_wgrad_pending recs[WG_BATCH_MAX_MEMBERS];
+    const int rp = rua_wgrad_group_plan(d, n, recs);
+    if (rp != RUA_OK) return rp;
+    bool overlap = false;
+    for (int i = 0; i < n && !overlap; ++i)
+      for (int j = i + 1; j < n && !overlap; ++j) {
+        if (recs[i].kind != 2 || recs[j].kind != 2) continue;
+        const float* a0 = recs[i].partials; const float* b0 = recs[j].partials;
+        overlap = a0 < b0 + (long long)recs[j].parts * recs[j].n && b0 < a0 + (long long)recs[i].parts * recs[i].n;
+      }
+    if (!overlap) return wgrad_batch_launch(d, n, st);
+    g_wg_group_last_grids = n;
+    for (int i = 0; i < n; ++i) { const int rc = rua_conv_wgrad(d + i, stream); if (rc != RUA_OK) return rc; }
+    return RUA_OK;
+  }
+  RUA_CHECK_ARG(n <= RUA_MAX_WGRAD_GROUP, "rua_conv_wgrad_group: 1..%d members (more only in the batched form)", RUA_MAX_WGRAD_GROUP);
   bool shared = false;
   for (int i = 0; i < n; ++i)
     for (int j = i + 1; j < n; ++j) {

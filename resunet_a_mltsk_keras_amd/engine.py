@@ -323,6 +323,7 @@ class Graph:
         self.pending: List[tuple] = []          # deferred weight-gradient reductions (record, dW offset)
         self.pending_bytes = 0                  # ... and the bytes of partials they will read (Engine.flush_bytes)
         self.pending_bucket = 0
+        self.later: List[tuple] = []            # generic-tile weight gradients held back for ONE batched launch in front of the next flush (descriptor, dW offset)
         self.allocs: List[torch.Tensor] = []
         self.stats_used = 16                 # the first 16 doubles of the arena are the loss / metric scalars
         self.act_bytes = 0
@@ -672,7 +673,7 @@ class Graph:
         defer = (not self.dry) and self.e.defer_reduce and plan is self.bwd and defer_ok
         if defer and may_flush:
             bucket = self.e.dist.bucket_of(dw_off) if self.e.dist is not None else 0
-            if self.pending and (bucket != self.pending_bucket or self.pending_bytes > self.e.flush_bytes):
+            if (self.pending or self.later) and (bucket != self.pending_bucket or self.pending_bytes > self.e.flush_bytes):
                 self.flush_wgrad(plan)
             self.pending_bucket = bucket
         d.dw, d.grads = self.G(dw_off), (dw_off,)
@@ -683,7 +684,60 @@ class Graph:
         return d
 
     def wgrad(self, plan: Plan, a: Ten, dy: Ten, dw_off: int, stride: int, dil: int, taps: int, in_bn: Optional["Coef"] = None):
-        self.issue(plan, [self.wgrad_desc(plan, a, dy, dw_off, stride, dil, taps, in_bn)], "rua_conv_wgrad")
+        if not self.wgrad_later(plan, a, dy, dw_off, stride, dil, taps, in_bn):
+            self.issue(plan, [self.wgrad_desc(plan, a, dy, dw_off, stride, dil, taps, in_bn)], "rua_conv_wgrad")
+
+    # -- batched weight gradients: the generic-tile weight gradients of a step (the wide 1x1 convolutions on small maps: 2 - 13 us apiece, each a launch that
+    #    splits its K range to fill the chip alone) are not launched where they are recorded.  They wait in `later` and go out as ONE rua_conv_wgrad_group call
+    #    (its batched form: one compact grid, one block budget) IMMEDIATELY IN FRONT OF every flush_wgrad - a bucket change, Engine.flush_bytes, the end of
+    #    backward.  The flush invariant: the pending records of a held-back member are created by that call's recording (_issue_later), so they can never be
+    #    reduced before their slabs are written, and under data parallel a bucket's gradients are final at the same flush as with one launch each.
+    def wgrad_later(self, plan: Plan, a: Ten, dy: Ten, dw_off: int, stride: int, dil: int, taps: int, in_bn: Optional["Coef"] = None) -> bool:
+        """Hold this weight gradient back for the batched launch in front of the next flush; False: the caller launches it here.  Candidates: bf16 backward
+        plans with deferred reductions, rua_wgrad_kind() == 0 and no whole-image kernel.  Holding a launch back is sound only while nothing writes its operands
+        between the recorded position and the flush: `a` is a forward activation (or its pooled / normalised copy) and `dy` the finished gradient of the
+        convolution's output; the graph owns every buffer for its lifetime (alloc) and the backward rewrites neither.  The one explicit storage reuse of the
+        backward, the ResBlocks' g1s = g2s, holds gradients of 3x3 branch convolutions: all-taps / wgrad_dmap / whole-image launches, never candidates here."""
+        if self.dry or plan is not self.bwd or in_bn is not None or self.dt != L.RUA_BF16 or not (self.e.batch_wgrad and self.e.defer_reduce):
+            return False
+        d = self.wgrad_desc(plan, a, dy, dw_off, stride, dil, taps, defer_ok=False)          # (no side effects: neither a flush nor a workspace)
+        lib = L.lib()
+        if lib.raw("rua_wgrad_kind")(C.byref(d)) != 0 or lib.raw("rua_wgrad_img_kind")(C.byref(d)) != 0:
+            return False
+        bucket = self.e.dist.bucket_of(dw_off) if self.e.dist is not None else 0
+        if (self.pending or self.later) and (bucket != self.pending_bucket or self.pending_bytes > self.e.flush_bytes):
+            self.flush_wgrad(plan)
+        self.pending_bucket = bucket
+        d.batch, d.defer = 1, 1
+        self.later.append((d, dw_off))
+        return True
+
+    def _issue_later(self, plan: Plan):
+        """The held-back weight gradients as one rua_conv_wgrad_group call, and the pending records of the slabs it leaves."""
+        if not self.later:
+            return
+        lib = L.lib()
+        n = len(self.later)
+        arr = (L.WgradDesc * n)(*[d for d, _ in self.later])
+        recs = (L.WgradPending * n)()
+        lib.call("rua_wgrad_group_plan", arr, n, recs)                   # with the shared scratch: which members leave slabs, and how many
+        for i in range(n):
+            if recs[i].kind != 0:
+                nbytes = recs[i].parts * recs[i].n * 4 + (264 << 10)
+                ws = self.alloc(((nbytes + 3) // 4,), torch.float32, zero=True)   # private until the flush, as in _defer_wgrad
+                arr[i].workspace, arr[i].workspace_bytes = ws.data_ptr(), ws.numel() * 4
+                self.pending_bytes += nbytes
+        first = [(recs[i].kind, recs[i].parts) for i in range(n)]
+        lib.call("rua_wgrad_group_plan", arr, n, recs)                   # the records for the private workspaces
+        assert first == [(recs[i].kind, recs[i].parts) for i in range(n)]
+        for i, (_, off) in enumerate(self.later):
+            if recs[i].kind != 0:
+                self.pending.append((L.WgradPending.from_buffer_copy(recs[i]), off))
+        plan.keep.append(arr)
+        prev, plan.scope = plan.scope, "wgrad_batch"
+        plan.add("rua_conv_wgrad_group", arr, n, grads=[off for _, off in self.later])
+        plan.scope = prev
+        self.later = []
 
     def wgrad_group(self, plan: Plan, specs: List[tuple]):
         """Independent weight gradients (the dilation branches of a ResBlock) in one call: members on the same kernel share ONE
@@ -722,11 +776,11 @@ class Graph:
             for sp in specs:
                 self.wgrad(plan, *sp)
             return
-        descs = [self.wgrad_desc(plan, *sp, may_flush=(i == 0)) for i, sp in enumerate(specs)]
-        if not all(lib.raw("rua_wgrad_kind")(C.byref(d)) == 3 for d in descs):
-            for d in descs:                                    # (descriptors are already recorded for the deferred reductions: launch exactly these)
-                self.issue(plan, [d], "rua_conv_wgrad")
+        if not all(lib.raw("rua_wgrad_kind")(C.byref(self.wgrad_desc(plan, *sp, defer_ok=False))) == 3 for sp in specs):
+            for sp in specs:                                   # one launch each - or, generic tiles, held back for the step's batched launch (wgrad_later)
+                self.wgrad(plan, *sp)
             return
+        descs = [self.wgrad_desc(plan, *sp, may_flush=(i == 0)) for i, sp in enumerate(specs)]
         for d in descs:
             if d.defer:                                        # block partials, summed by the next rua_wgrad_reduce_batch: _defer_wgrad gave it a private workspace
                 continue
@@ -757,6 +811,7 @@ class Graph:
         self.pending_bytes += nbytes
 
     def flush_wgrad(self, plan: Plan):
+        self._issue_later(plan)
         self.pending_bytes = 0
         if not self.pending:
             return
@@ -784,7 +839,7 @@ class Graph:
             return
         for o in offs:
             bucket = self.e.dist.bucket_of(o) if self.e.dist is not None else 0
-            if self.pending and bucket != self.pending_bucket:
+            if (self.pending or self.later) and bucket != self.pending_bucket:
                 self.flush_wgrad(plan)
             self.pending_bucket = bucket
             rec = L.WgradPending()
@@ -1701,6 +1756,7 @@ class Engine:
         self.multi_head = os.environ.get("RUA_MULTI_HEAD", "1") != "0"     # the heads' loss finalisation / d(loss)/d(logits) as one launch each
         self.merge_wgrad = {int(v) for v in os.environ.get("RUA_MERGE_WGRAD", "1,32,64,128,256").split(",") if v}     # channel counts whose ResBlocks issue both weight-gradient groups as one (Graph.wgrad_now_or_later)
         self.group_wgrad_pw = os.environ.get("RUA_GROUP_WGRAD_PW", "1") != "0"   # the narrow 1x1 weight gradients of a composite as one grid (Graph.wgrad_pw_group)
+        self.batch_wgrad = os.environ.get("RUA_BATCH_WGRAD", "1") != "0"         # bf16: a step's generic-tile weight gradients as one batched launch in front of each flush (Graph.wgrad_later)
         self.stem_mfma = os.environ.get("RUA_STEM_MFMA", "1") != "0"       # bf16: the stem's weight gradient through rua_stem_fwd_pack / rua_conv_wgrad / rua_stem_bwd_fold
         self.stem_stats = os.environ.get("RUA_STEM_STATS", "1") != "0"     # rua_stem_fwd_stats instead of a rua_col_stats pass over the stem's output
         self._captured: Dict[int, object] = {}
