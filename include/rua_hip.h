@@ -459,6 +459,26 @@ int rua_scene_windows(const uint8_t* const* scene_img, const uint8_t* const* sce
                       int nscenes, const int32_t* windows, int N, int PH, int PW, int Cin,
                       uint8_t* img_out, uint8_t* cls_out, void* stream);
 
+/* ---- the same outputs under a free affine map: random rotation, zoom and shift with reflect padding (scenes.py,
+ * host_windows_affine / affine_rows) ------------------------------------------------------------------------------------------
+ * Arguments as for rua_scene_windows, but windows is int32 [N][7], rows (scene, y0, x0, a_yy, a_yx, a_xy, a_xx), all but scene
+ * in Q16 fixed point.  Destination pixel (i, j) samples the scene at
+ *   sy = y0 + i * a_yy + j * a_yx      sx = x0 + i * a_xy + j * a_xx      (exact integers; pixel centres on integers).
+ * A scene index t is folded into [0, n) by numpy's 'reflect' rule (no edge repeat, any number of reflections):
+ *   refl(t, n):  m = 2 * (n - 1);  u = t mod m (non-negative);  u < n ? u : m - u.
+ * Image, per channel, bilinear with 8-bit fractions:  iy = sy >> 16 (arithmetic), fy = (sy & 0xFFFF) >> 8, the same in x;
+ *   p00 = img[refl(iy, H)][refl(ix, W)], p01 at ix + 1, p10 at iy + 1, p11 at both;
+ *   out = ((256 - fy) * ((256 - fx) * p00 + fx * p01) + fy * ((256 - fx) * p10 + fx * p11) + 32768) >> 16.
+ * Class map, nearest:  cls[refl((sy + 32768) >> 16, H)][refl((sx + 32768) >> 16, W)].
+ * Integers only, so scenes.host_windows_affine gives the same bytes.  Limits, all checked on the host before anything is launched
+ * (a violation: RUA_ERR_ARG, the message names the scene or the row): 0 <= scene < nscenes, 2 <= H, W <= 16384 for every scene,
+ * |a| <= 4 * 65536 for every coefficient, |y0|, |x0| <= 2^30, 1 <= PH, PW <= 512, 1 <= Cin <= 16 - under them every sum above
+ * fits in 32 bits.  The windows travel as kernel arguments, 80 per launch, image and class map in the same launch: no
+ * device-side table, no copy, no synchronisation. */
+int rua_scene_windows_affine(const uint8_t* const* scene_img, const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w,
+                             int nscenes, const int32_t* windows /* [N][7] */, int N, int PH, int PW, int Cin,
+                             uint8_t* img_out, uint8_t* cls_out, void* stream);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

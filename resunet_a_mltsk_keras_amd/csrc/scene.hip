@@ -159,3 +159,147 @@ extern "C" int rua_scene_windows(const uint8_t* const* scene_img, const uint8_t*
   }
   return RUA_OK;
 }
+
+// ---- rua_scene_windows_affine: the same outputs under a free affine map (rotation, zoom, shift), reflect-padded ------------------
+// Destination pixel (i, j) samples its scene at sy = y0 + i * a_yy + j * a_yx, sx = x0 + i * a_xy + j * a_xx (Q16, pixel centres
+// on integers): the image bilinearly with 8-bit fractions, the class map at the nearest pixel, indices folded into the scene by
+// numpy's 'reflect' rule (include/rua_hip.h spells the arithmetic out; scenes.host_windows_affine is its numpy twin).
+//
+// One form: a direct gather.  A block owns one 32 x 32 destination tile of one plane; a thread resolves a destination pixel once
+// (two reflections per axis, four tap offsets, the weights), reads its taps through L1 / L2 - neighbouring lanes are neighbouring
+// destination columns, so their taps are neighbours along the map's x direction - and puts the result bytes into an LDS image of
+// the DESTINATION tile.  After the barrier the tile leaves along destination rows in 16-byte pieces (4 bytes or single bytes where
+// PW * Cin does not allow more), exactly as sw_write stores.  Staging the SOURCE bounding box in LDS instead was not built: at
+// zoom-out 4 under 45 degrees a tile's box is about 181 x 181 pixels (512 KiB at Cin = 16), so that form needs this gather as its
+// other branch anyway, and the gather alone already runs far below the copy it replaces.
+namespace {
+
+constexpr int SA_CHUNK = 80;                   // windows per launch: 48 bytes each
+constexpr int SA_PITCH = SW_T * SW_MAXPIX + 16;  // LDS row pitch in bytes: a multiple of 16, 132 dwords (rows 4 banks apart)
+constexpr int SA_MAXDIM = 16384, SA_MAXCOEF = 4 << 16, SA_MAXORG = 1 << 30;
+
+struct AffineWin { const uint8_t* img; const uint8_t* cls; int H, W, y0, x0, ayy, ayx, axy, axx; };
+struct AffineArgs {
+  AffineWin w[SA_CHUNK];
+  uint8_t* img_out; uint8_t* cls_out;          // of the chunk's first window
+  int PH, PW, Cin, img_unit, cls_unit, planes;
+};
+static_assert(sizeof(AffineArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+// numpy 'reflect' (no edge repeat, any number of reflections): t mod 2 (n - 1), folded.  m = 2 (n - 1) >= 2.
+__device__ __forceinline__ int sa_mod(int t, int m) { const int u = t % m; return u < 0 ? u + m : u; }
+__device__ __forceinline__ int sa_fold(int u, int n, int m) { return u < n ? u : m - u; }
+
+template <int U>
+__device__ __forceinline__ void sa_write(const uint8_t* T, uint8_t* out, int PW, int cb, int i0, int j0, int th, int tw, int tid) {
+  const int upr = tw * cb / U, total = th * upr;
+  for (int e = tid; e < total; e += 256) {
+    const int ti = e / upr, v = e - ti * upr;
+    const uint8_t* s = T + ti * SA_PITCH + v * U;                       // 16-byte aligned for U = 16, 4-byte for U = 4
+    uint32_t word[U >= 4 ? U / 4 : 1];
+    if (U == 1) word[0] = *s;
+    else {
+#pragma unroll
+      for (int k = 0; k < U / 4; ++k) word[k] = reinterpret_cast<const uint32_t*>(s)[k];
+    }
+    StoreUnit<U>::st(out + ((size_t)(i0 + ti) * PW + j0) * cb + (size_t)v * U, word);
+  }
+}
+
+__global__ __launch_bounds__(256) void scene_windows_affine(AffineArgs a) {
+  __shared__ uint4 Tq[SW_T * SA_PITCH / 16];
+  uint8_t* T = reinterpret_cast<uint8_t*>(Tq);
+  const int tid = threadIdx.x, n = blockIdx.y, plane = blockIdx.z;
+  const int PH = a.PH, PW = a.PW;
+  const int tiles_x = (PW + SW_T - 1) / SW_T;
+  const int i0 = (blockIdx.x / tiles_x) * SW_T, j0 = (blockIdx.x % tiles_x) * SW_T;
+  const int th = min(SW_T, PH - i0), tw = min(SW_T, PW - j0);
+  const AffineWin& w = a.w[n];
+  const int H = w.H, W = w.W, mh = 2 * (H - 1), mw = 2 * (W - 1);
+  const int cb = plane ? 1 : a.Cin, unit = plane ? a.cls_unit : a.img_unit;
+  uint8_t* out = (plane ? a.cls_out : a.img_out) + (size_t)n * PH * PW * cb;
+  for (int e = tid; e < th * SW_T; e += 256) {
+    const int ti = e / SW_T, tj = e % SW_T;
+    if (tj >= tw) continue;
+    const int i = i0 + ti, j = j0 + tj;
+    // 32-bit throughout: |y0|, |x0| <= 2^30, |a| <= 2^18 and i, j <= 511 give |i * a + j * a'| < 2^28, so |sy|, |sx| < 2^30 + 2^28,
+    // and the + 32768 of the nearest rule stays below 2^31 (the host refuses anything beyond these limits)
+    const int sy = w.y0 + i * w.ayy + j * w.ayx, sx = w.x0 + i * w.axy + j * w.axx;
+    uint8_t* d = T + ti * SA_PITCH + tj * cb;
+    if (plane) {
+      const int r = sa_fold(sa_mod((sy + 32768) >> 16, mh), H, mh), c = sa_fold(sa_mod((sx + 32768) >> 16, mw), W, mw);
+      *d = w.cls[(size_t)r * W + c];
+    } else {
+      const int uy = sa_mod(sy >> 16, mh), ux = sa_mod(sx >> 16, mw);   // of iy, ix; iy + 1 and ix + 1 are one step on in the cycle
+      const int r0 = sa_fold(uy, H, mh), r1 = sa_fold(uy + 1 == mh ? 0 : uy + 1, H, mh);
+      const int c0 = sa_fold(ux, W, mw), c1 = sa_fold(ux + 1 == mw ? 0 : ux + 1, W, mw);
+      const uint32_t fy = (uint32_t)(sy & 0xFFFF) >> 8, fx = (uint32_t)(sx & 0xFFFF) >> 8;
+      const uint8_t* p00 = w.img + ((size_t)r0 * W + c0) * cb;
+      const uint8_t* p01 = w.img + ((size_t)r0 * W + c1) * cb;
+      const uint8_t* p10 = w.img + ((size_t)r1 * W + c0) * cb;
+      const uint8_t* p11 = w.img + ((size_t)r1 * W + c1) * cb;
+      for (int ch = 0; ch < cb; ++ch) {
+        // at most 256 * 256 * 255 + 32768 < 2^25
+        const uint32_t top = (256 - fx) * p00[ch] + fx * p01[ch], bot = (256 - fx) * p10[ch] + fx * p11[ch];
+        d[ch] = (uint8_t)(((256 - fy) * top + fy * bot + 32768) >> 16);
+      }
+    }
+  }
+  __syncthreads();
+  if (unit == 16) sa_write<16>(T, out, PW, cb, i0, j0, th, tw, tid);
+  else if (unit == 4) sa_write<4>(T, out, PW, cb, i0, j0, th, tw, tid);
+  else sa_write<1>(T, out, PW, cb, i0, j0, th, tw, tid);
+}
+
+}  // namespace
+
+extern "C" int rua_scene_windows_affine(const uint8_t* const* scene_img, const uint8_t* const* scene_cls, const int32_t* scene_h,
+                                        const int32_t* scene_w, int nscenes, const int32_t* windows, int N, int PH, int PW, int Cin,
+                                        uint8_t* img_out, uint8_t* cls_out, void* stream) {
+  RUA_CHECK_ARG(scene_img && scene_h && scene_w && windows && img_out,
+                "rua_scene_windows_affine: scene_img, scene_h, scene_w, windows and img_out are required");
+  RUA_CHECK_ARG(!scene_cls == !cls_out, "rua_scene_windows_affine: scene_cls and cls_out go together");
+  RUA_CHECK_ARG(nscenes >= 1 && N >= 1, "rua_scene_windows_affine: nscenes %d, N %d (both >= 1)", nscenes, N);
+  RUA_CHECK_ARG(Cin >= 1 && Cin <= SW_MAXPIX, "rua_scene_windows_affine: Cin %d outside 1..16", Cin);
+  RUA_CHECK_ARG(PH >= 1 && PW >= 1 && PH <= SW_MAXP && PW <= SW_MAXP, "rua_scene_windows_affine: PH %d, PW %d (1 <= PH, PW <= 512)", PH, PW);
+  RUA_CHECK_ARG(((uintptr_t)img_out & 3) == 0 && ((uintptr_t)cls_out & 3) == 0, "rua_scene_windows_affine: img_out and cls_out must be 4-byte aligned");
+  for (int s = 0; s < nscenes; ++s) {
+    RUA_CHECK_ARG(scene_img[s] && (!scene_cls || scene_cls[s]), "rua_scene_windows_affine: scene %d: null pointer", s);
+    RUA_CHECK_ARG(scene_h[s] >= 2 && scene_w[s] >= 2 && scene_h[s] <= SA_MAXDIM && scene_w[s] <= SA_MAXDIM,
+                  "rua_scene_windows_affine: scene %d: size %d x %d (2 <= H, W <= 16384)", s, scene_h[s], scene_w[s]);
+  }
+  for (int k = 0; k < N; ++k) {
+    const int32_t* t = windows + 7 * (size_t)k;
+    const int s = t[0];
+    RUA_CHECK_ARG(s >= 0 && s < nscenes, "rua_scene_windows_affine: row %d: scene %d outside 0..%d", k, s, nscenes - 1);
+    RUA_CHECK_ARG(t[1] >= -SA_MAXORG && t[1] <= SA_MAXORG && t[2] >= -SA_MAXORG && t[2] <= SA_MAXORG,
+                  "rua_scene_windows_affine: row %d: origin (%d, %d) outside -2^30..2^30 (Q16)", k, t[1], t[2]);
+    for (int q = 3; q < 7; ++q)
+      RUA_CHECK_ARG(t[q] >= -SA_MAXCOEF && t[q] <= SA_MAXCOEF,
+                    "rua_scene_windows_affine: row %d: coefficient %d outside -262144..262144 (4 in Q16)", k, t[q]);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int tiles = ((PH + SW_T - 1) / SW_T) * ((PW + SW_T - 1) / SW_T);
+  AffineArgs a;
+  memset(&a, 0, sizeof(a));
+  a.PH = PH; a.PW = PW; a.Cin = Cin; a.planes = cls_out ? 2 : 1;
+  a.img_unit = store_unit(img_out, PW * Cin);
+  a.cls_unit = store_unit(cls_out, PW);
+  for (int k0 = 0; k0 < N; k0 += SA_CHUNK) {
+    const int nk = N - k0 < SA_CHUNK ? N - k0 : SA_CHUNK;
+    for (int k = 0; k < nk; ++k) {
+      const int32_t* t = windows + 7 * (size_t)(k0 + k);
+      const int s = t[0];
+      AffineWin& w = a.w[k];
+      w.img = scene_img[s];
+      w.cls = scene_cls ? scene_cls[s] : nullptr;
+      w.H = scene_h[s]; w.W = scene_w[s];
+      w.y0 = t[1]; w.x0 = t[2]; w.ayy = t[3]; w.ayx = t[4]; w.axy = t[5]; w.axx = t[6];
+    }
+    a.img_out = img_out + (size_t)k0 * PH * PW * Cin;          // a window is a whole number of rows, a row a whole number of store units
+    a.cls_out = cls_out ? cls_out + (size_t)k0 * PH * PW : nullptr;
+    hipLaunchKernelGGL(scene_windows_affine, dim3(tiles, nk, a.planes), dim3(256), 0, st, a);
+    RUA_LAUNCH_CHECK("rua_scene_windows_affine");
+  }
+  return RUA_OK;
+}

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .scenes import SceneBatch
+from .scenes import AffineSceneBatch, SceneBatch
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -1947,7 +1947,8 @@ class Engine:
     def _upload_scene(self, g: Graph, batch: SceneBatch, norm_type: int, with_labels: bool = True):
         """Scene batch (scenes.SceneBatch: resident scenes + a window table): rua_scene_windows cuts and augments the windows into
         g.compact_buffers(), then the targets call of _upload_compact - both on the compute stream, in front of the recorded plans,
-        outside any captured graph.  The host passes B * 4 integers; nothing is copied.  with_labels False: images only (inference)."""
+        outside any captured graph.  The host passes B * 4 integers; nothing is copied.  with_labels False: images only (inference).
+        An AffineSceneBatch (B * 7 integers: rotation, zoom and shift) goes through rua_scene_windows_affine in the same place."""
         self._check_scene(batch, None, norm_type, with_labels)
         pool = batch.pool
         H, W, Cin = self.cfg.input_shape
@@ -1955,7 +1956,7 @@ class Engine:
             raise ValueError(f"scene batch of {len(batch)} windows for a graph of batch {g.B}")
         img, cls, _ = g.compact_buffers()
         rows = np.ascontiguousarray(batch.rows, dtype=np.int32)
-        L.lib().call("rua_scene_windows", pool.img_ptrs, pool.cls_ptrs if with_labels else None, pool.heights, pool.widths, len(pool),
+        L.lib().call("rua_scene_windows_affine" if isinstance(batch, AffineSceneBatch) else "rua_scene_windows", pool.img_ptrs, pool.cls_ptrs if with_labels else None, pool.heights, pool.widths, len(pool),
                      rows.ctypes.data, g.B, H, W, Cin, img.data_ptr(), cls.data_ptr() if with_labels else None, C.c_void_p(self._stream()))
         self._compact_targets(g, with_labels, int(norm_type))
 

@@ -21,6 +21,12 @@ A batch is a window table, int32 [N][4] rows (scene, row, col, code): the window
 0 - 4 are the reference's five copies in its order, 5 - 7 complete the symmetries of the square; 1, 5, 6 and 7 need PH == PW.
 window_table() enumerates the reference's patch set: patch k of a written-out dataset (`patch_{k}.npy`) is row k.
 
+Random rotation, zoom and shift (the ResUNet-a paper's augmentation) go through a second table, int32 [N][7] rows
+(scene, y0, x0, a_yy, a_yx, a_xy, a_xx) in Q16 fixed point: destination pixel (i, j) samples the scene at
+sy = y0 + i * a_yy + j * a_yx, sx = x0 + i * a_xy + j * a_xx, the image bilinearly, the class map at the nearest pixel, with
+reflect padding at the scene border (host_windows_affine is the definition, rua_scene_windows_affine its kernel).  affine_rows()
+makes such rows from [N][4] rows and a rotation / zoom / shift, AffineSceneBatch carries them, SceneLoader(jitter=) draws them.
+
 `python -m resunet_a_mltsk_keras_amd.scenes --image Image_Train.npy --reference Reference_Train.npy --dst DIR` writes a scene
 directory from the reference's two inputs (C x H x W arrays, the reference colour-coded); `--materialize DST` also writes the
 compact patch layout (compact.py) of its window table, for users who want files.
@@ -130,6 +136,111 @@ def host_windows(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.
     return img, cls
 
 
+# ---- affine windows: rotation, zoom and shift, reflect-padded -------------------------------------------------------------------
+Q16 = 65536
+MAX_SCENE, MAX_COEF, MAX_ORIGIN = 16384, 4 * Q16, 1 << 30
+# out[i, j] = w[S (i, j) + offset] for the eight codes: the rows (a_yy, a_yx), (a_xy, a_xx) of S
+SYMMETRY = np.array([[[1, 0], [0, 1]], [[0, 1], [-1, 0]], [[-1, 0], [0, -1]], [[-1, 0], [0, 1]],
+                     [[1, 0], [0, -1]], [[0, -1], [1, 0]], [[0, 1], [1, 0]], [[0, -1], [-1, 0]]], np.int64)
+
+
+def check_affine_table(shapes: Sequence[Sequence[int]], table7: np.ndarray, patch, channels: int = 1) -> np.ndarray:
+    """The table as a contiguous int32 [N][7] array; ValueError, in rua_scene_windows_affine's own words, for the first violation."""
+    ph, pw = _patch2(patch)
+    t = np.asarray(table7)
+    if t.ndim != 2 or t.shape[1] != 7 or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError(f"an affine window table is an integer [N][7] array of (scene, y0, x0, a_yy, a_yx, a_xy, a_xx) rows, got {t.dtype} {t.shape}")
+    n = len(shapes)
+    if n < 1 or t.shape[0] < 1:
+        raise ValueError(f"rua_scene_windows_affine: nscenes {n}, N {t.shape[0]} (both >= 1)")
+    if not 1 <= channels <= MAX_CHANNELS:
+        raise ValueError(f"rua_scene_windows_affine: Cin {channels} outside 1..16")
+    if not (1 <= ph <= MAX_PATCH and 1 <= pw <= MAX_PATCH):
+        raise ValueError(f"rua_scene_windows_affine: PH {ph}, PW {pw} (1 <= PH, PW <= 512)")
+    for s, shp in enumerate(shapes):
+        H, W = int(shp[0]), int(shp[1])
+        if not (2 <= H <= MAX_SCENE and 2 <= W <= MAX_SCENE):
+            raise ValueError(f"rua_scene_windows_affine: scene {s}: size {H} x {W} (2 <= H, W <= 16384)")
+    t64 = t.astype(np.int64)
+    bad = (t64[:, 0] < 0) | (t64[:, 0] >= n) | (np.abs(t64[:, 1:3]) > MAX_ORIGIN).any(1) | (np.abs(t64[:, 3:]) > MAX_COEF).any(1)
+    if bad.any():
+        k = int(np.argmax(bad))
+        row = [int(v) for v in t64[k]]
+        if not 0 <= row[0] < n:
+            raise ValueError(f"rua_scene_windows_affine: row {k}: scene {row[0]} outside 0..{n - 1}")
+        if abs(row[1]) > MAX_ORIGIN or abs(row[2]) > MAX_ORIGIN:
+            raise ValueError(f"rua_scene_windows_affine: row {k}: origin ({row[1]}, {row[2]}) outside -2^30..2^30 (Q16)")
+        a = next(v for v in row[3:] if abs(v) > MAX_COEF)
+        raise ValueError(f"rua_scene_windows_affine: row {k}: coefficient {a} outside -262144..262144 (4 in Q16)")
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def _reflect(t: np.ndarray, n: int) -> np.ndarray:
+    """numpy's 'reflect' padding as an index map: no edge repeat, any number of reflections."""
+    m = 2 * (n - 1)
+    u = np.mod(t, m)
+    return np.where(u < n, u, m - u)
+
+
+def host_windows_affine(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]], table7: np.ndarray, patch):
+    """The numpy definition of what rua_scene_windows_affine writes (include/rua_hip.h spells the same arithmetic out), in int64:
+    (img uint8 [N][PH][PW][C], cls uint8 [N][PH][PW] or None)."""
+    ph, pw = _patch2(patch)
+    t = check_affine_table([im.shape for im in images], table7, patch, images[0].shape[2])
+    img = np.empty((len(t), ph, pw, images[0].shape[2]), np.uint8)
+    cls = np.empty((len(t), ph, pw), np.uint8) if class_maps is not None else None
+    i, j = np.arange(ph, dtype=np.int64)[:, None], np.arange(pw, dtype=np.int64)[None, :]
+    for k, (s, y0, x0, ayy, ayx, axy, axx) in enumerate(t.tolist()):
+        im = images[s]
+        H, W = im.shape[:2]
+        sy, sx = y0 + i * ayy + j * ayx, x0 + i * axy + j * axx
+        iy, ix, fy, fx = sy >> 16, sx >> 16, ((sy & 0xFFFF) >> 8)[..., None], ((sx & 0xFFFF) >> 8)[..., None]
+        r0, r1, c0, c1 = _reflect(iy, H), _reflect(iy + 1, H), _reflect(ix, W), _reflect(ix + 1, W)
+        p = lambda r, c: im[r, c].astype(np.int64)
+        top, bot = (256 - fx) * p(r0, c0) + fx * p(r0, c1), (256 - fx) * p(r1, c0) + fx * p(r1, c1)
+        img[k] = ((256 - fy) * top + fy * bot + 32768) >> 16
+        if cls is not None:
+            cls[k] = class_maps[s][_reflect((sy + 32768) >> 16, H), _reflect((sx + 32768) >> 16, W)]
+    return img, cls
+
+
+def affine_rows(rows4: np.ndarray, patch, rotate_deg=0.0, zoom=1.0, shift_q16=(0, 0)) -> np.ndarray:
+    """[N][7] affine rows of [N][4] (scene, row, col, code) rows rotated by rotate_deg about the window centre, zoomed (> 1: in)
+    and shifted by shift_q16 = (y, x) in Q16 pixels; the arguments broadcast per row ([N], [N], [N][2]).  The matrix is
+    M = (1 / zoom) R(theta) S(code), a = rint(65536 M); the origin puts the patch centre on the window centre (+ shift).  With no
+    rotation, zoom 1 and no shift host_windows_affine of the result is host_windows of rows4, bit for bit."""
+    ph, pw = _patch2(patch)
+    r4 = np.asarray(rows4)
+    if r4.ndim != 2 or r4.shape[1] != 4 or not np.issubdtype(r4.dtype, np.integer):
+        raise ValueError(f"a window table is an integer [N][4] array of (scene, row, col, code) rows, got {r4.dtype} {r4.shape}")
+    r4 = r4.astype(np.int64)
+    N, code = len(r4), r4[:, 3]
+    bad = np.flatnonzero((code < 0) | (code >= NUM_CODES))
+    if bad.size:
+        raise ValueError(f"affine_rows: row {int(bad[0])}: code {int(code[bad[0]])} outside 0..7")
+    if ph != pw:
+        bad = np.flatnonzero(np.isin(code, TRANSPOSING))
+        if bad.size:
+            raise ValueError(f"affine_rows: row {int(bad[0])}: code {int(code[bad[0]])} transposes and needs a square patch (got {ph} x {pw})")
+    theta = np.deg2rad(np.broadcast_to(np.asarray(rotate_deg, np.float64), (N,)))
+    z = np.broadcast_to(np.asarray(zoom, np.float64), (N,))
+    if not (z > 0).all():
+        raise ValueError("affine_rows: zoom must be positive")
+    shift = np.broadcast_to(np.asarray(shift_q16, np.int64), (N, 2))
+    R = np.empty((N, 2, 2), np.float64)
+    R[:, 0, 0], R[:, 0, 1], R[:, 1, 0], R[:, 1, 1] = np.cos(theta), -np.sin(theta), np.sin(theta), np.cos(theta)
+    a = np.rint(Q16 * (R @ SYMMETRY[code].astype(np.float64)) / z[:, None, None]).astype(np.int64)
+    out = np.empty((N, 7), np.int64)
+    out[:, 0] = r4[:, 0]
+    out[:, 3:] = a.reshape(N, 4)
+    # window centre in half pixels, minus half the patch's extent under the map
+    out[:, 1] = (2 * r4[:, 1] + ph - 1) * (Q16 // 2) + shift[:, 0] - ((a[:, 0, 0] * (ph - 1) + a[:, 0, 1] * (pw - 1)) >> 1)
+    out[:, 2] = (2 * r4[:, 2] + pw - 1) * (Q16 // 2) + shift[:, 1] - ((a[:, 1, 0] * (ph - 1) + a[:, 1, 1] * (pw - 1)) >> 1)
+    if (np.abs(out) > 2 ** 31 - 1).any():
+        raise ValueError("affine_rows: a row leaves the int32 range")
+    return out.astype(np.int32)
+
+
 def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]]) -> int:
     """Scenes are uint8 H x W x C with one C for all, class maps uint8 H x W of their image's size.  Returns C."""
     if len(images) < 1:
@@ -181,6 +292,39 @@ class SceneBatch:
         return host_windows(self.pool.images, self.pool.class_maps, self.rows, self.patch)
 
 
+class AffineSceneBatch(SceneBatch):
+    """A SceneBatch whose rows are the int32 [B][7] affine table (check_affine_table): rua_scene_windows_affine cuts it."""
+
+    def __getitem__(self, sl):
+        if not isinstance(sl, slice):
+            raise TypeError("a SceneBatch is sliced, not indexed")
+        return AffineSceneBatch(self.pool, np.ascontiguousarray(self.rows[sl]), self.patch)
+
+    def host(self):
+        """host_windows_affine of this batch."""
+        return host_windows_affine(self.pool.images, self.pool.class_maps, self.rows, self.patch)
+
+
+class Jitter:
+    """The random part of SceneLoader's augmentation: the angle uniform in [-rotate_deg, rotate_deg], the zoom log-uniform in
+    zoom = (lo, hi), the shift uniform in whole Q16 units within [-shift, shift] pixels on either axis."""
+
+    def __init__(self, rotate_deg: float = 180.0, zoom: Tuple[float, float] = (0.75, 1.33), shift: float = 16.0):
+        lo, hi = float(zoom[0]), float(zoom[1])
+        if not 0 < lo <= hi:
+            raise ValueError(f"zoom range ({lo}, {hi}): 0 < lo <= hi")
+        if rotate_deg < 0 or shift < 0:
+            raise ValueError(f"rotate_deg {rotate_deg} and shift {shift} are magnitudes (>= 0)")
+        self.rotate_deg, self.zoom, self.shift = float(rotate_deg), (lo, hi), float(shift)
+
+    def draw(self, rng: np.random.Generator, n: int):
+        """(angles in degrees [n], zooms [n], Q16 shifts int64 [n][2]) - in this order from rng."""
+        angle = rng.uniform(-self.rotate_deg, self.rotate_deg, n)
+        zoom = np.exp(rng.uniform(np.log(self.zoom[0]), np.log(self.zoom[1]), n))
+        s = int(round(self.shift * Q16))
+        return angle, zoom, rng.integers(-s, s + 1, (n, 2), dtype=np.int64)
+
+
 class ScenePool:
     """Scenes uploaded once: uint8 H x W x C images (one C for all) and, for training, their uint8 H x W class maps.  Keeps the
     host arrays of device pointers and sizes rua_scene_windows takes.  patch: checked against every scene, and the default of
@@ -218,14 +362,24 @@ class ScenePool:
             raise ValueError("no patch size: give ScenePool(patch=) or batch(rows, patch)")
         return SceneBatch(self, check_table(self.shapes, rows, p), p)
 
+    def affine_batch(self, table7, patch=None) -> AffineSceneBatch:
+        """The batch of these [N][7] affine rows; ValueError (rua_scene_windows_affine's wording) for what the kernel would refuse."""
+        p = self.patch if patch is None else _patch2(patch)
+        if p is None:
+            raise ValueError("no patch size: give ScenePool(patch=) or affine_batch(table7, patch)")
+        return AffineSceneBatch(self, check_affine_table(self.shapes, table7, p, self.channels), p)
+
 
 class SceneLoader:
     """loader.PrefetchLoader's iteration over a window table instead of files: `len(order) // batch_size` batches per pass, the
     last partial batch dropped, `batch_size` the GLOBAL batch of which rank r yields rows [r * B / world, (r + 1) * B / world).
-    Yields (SceneBatch, None); order: indices into `table` (default: all of it, in order)."""
+    Yields (SceneBatch, None); order: indices into `table` (default: all of it, in order).
+    jitter (a Jitter): batch k of pass e (e counts __iter__ calls from 0) draws one rotation, zoom and shift per row of the GLOBAL
+    batch from np.random.default_rng([seed, e, k]), turns its rows into affine rows (affine_rows) and every rank takes its own:
+    a world of 2 sees exactly the windows a world of 1 sees.  Yields (AffineSceneBatch, None) then."""
 
     def __init__(self, pool: ScenePool, table: np.ndarray, batch_size: int, patch=None, order: Optional[Sequence[int]] = None,
-                 rank: int = 0, world: int = 1):
+                 rank: int = 0, world: int = 1, jitter: Optional[Jitter] = None, seed: int = 0):
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")
         if world < 1 or not (0 <= rank < world):
@@ -235,6 +389,7 @@ class SceneLoader:
         self.pool, self.table, self.patch = pool, np.asarray(table), patch
         self.B, self.rank, self.local_B = int(batch_size), int(rank), int(batch_size) // int(world)
         self.order = np.arange(len(self.table)) if order is None else np.asarray(order, dtype=np.int64)
+        self.jitter, self.seed, self.passes = jitter, int(seed), 0
 
     def __len__(self) -> int:
         return len(self.order) // self.B
@@ -243,9 +398,24 @@ class SceneLoader:
         self.order = np.asarray(order, dtype=np.int64)
 
     def __iter__(self):
+        if self.jitter is not None:
+            e, self.passes = self.passes, self.passes + 1
+            return self._jittered(e)
+        return self._plain()
+
+    def _plain(self):
         for k in range(len(self)):
             first = k * self.B + self.rank * self.local_B
             yield self.pool.batch(self.table[self.order[first:first + self.local_B]], self.patch), None
+
+    def _jittered(self, e: int):
+        patch = self.pool.patch if self.patch is None else _patch2(self.patch)
+        if patch is None:
+            raise ValueError("no patch size: give ScenePool(patch=) or SceneLoader(patch=)")
+        for k in range(len(self)):
+            angle, zoom, shift = self.jitter.draw(np.random.default_rng([self.seed, e, k]), self.B)
+            rows = affine_rows(self.table[self.order[k * self.B:(k + 1) * self.B]], patch, angle, zoom, shift)
+            yield self.pool.affine_batch(rows[self.rank * self.local_B:(self.rank + 1) * self.local_B], patch), None
 
 
 # ---- scene directories ------------------------------------------------------------------------------------------------------

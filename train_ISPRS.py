@@ -18,6 +18,10 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
     labels/scenes/, written by `python -m resunet_a_mltsk_keras_amd.scenes`).  The scenes stay on the GPU and every step cuts and
     augments its patches there; the patch set, its split and its order are those of a `--compact_dataset yes` run on the
     directory `scenes.materialize` writes from the same arguments.
+  * `--random_aug yes --aug_rotate DEG --aug_zoom LO HI --aug_shift PX` (with `--scene_dataset yes`): every training window is
+    rotated by a random angle in [-DEG, DEG], zoomed by a log-uniform factor in [LO, HI] and shifted by up to PX pixels (default
+    `--stride` / 2), with reflect padding at the scene border, drawn afresh every epoch from `--seed` (scenes.SceneLoader(jitter=)).
+    The validation windows and the split are untouched, so validation numbers compare between runs with and without the flag.
   * `--dtype {bf16,f32}`, `--seed`: engine options.  Launch with torch.distributed.run for multi-GPU data
     parallel (`-bs` is then the GLOBAL batch, as under MirroredStrategy).
 """
@@ -79,6 +83,11 @@ def build_parser():
                    help="dataset is a scene directory: scenes/<name>.npy (uint8 HxWxC) + labels/scenes/<name>.npy (uint8 HxW); patches are cut on the GPU")
     p.add_argument("--stride", type=int, default=32, help="scene directory: window stride")
     p.add_argument("--data_aug", type=str2bool, default=True, help="scene directory: every window five times (as is, rot90, rot180, flipped rows, flipped columns)")
+    p.add_argument("--random_aug", type=str2bool, default=False,
+                   help="scene directory: random rotation, zoom and shift of every training window, resampled on the GPU")
+    p.add_argument("--aug_rotate", type=float, default=180.0, metavar="DEG", help="random_aug: the angle is uniform in [-DEG, DEG]")
+    p.add_argument("--aug_zoom", type=float, nargs=2, default=[0.75, 1.33], metavar=("LO", "HI"), help="random_aug: the zoom is log-uniform in [LO, HI]")
+    p.add_argument("--aug_shift", type=float, default=None, metavar="PX", help="random_aug: shift of up to PX pixels per axis (default: stride / 2)")
     return p
 
 
@@ -179,7 +188,13 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
         # batch is its rows of the table, and every rank holds the pool and takes its own rows
         from resunet_a_mltsk_keras_amd.scenes import SceneLoader, patch_index
         pool, table = scenes
-        ld_tr = SceneLoader(pool, table[[patch_index(n) for n in x_tr]], batch_size, args.patch_size, rank=rank, world=world)
+        # --random_aug: the training loader alone draws a rotation, zoom and shift per window and pass (the same on every rank)
+        jitter = None
+        if getattr(args, "random_aug", False):
+            from resunet_a_mltsk_keras_amd.scenes import Jitter
+            jitter = Jitter(args.aug_rotate, tuple(args.aug_zoom), args.stride / 2 if args.aug_shift is None else args.aug_shift)
+        ld_tr = SceneLoader(pool, table[[patch_index(n) for n in x_tr]], batch_size, args.patch_size, rank=rank, world=world,
+                            jitter=jitter, seed=args.seed)
         ld_va = SceneLoader(pool, table[[patch_index(n) for n in x_va]], batch_size, args.patch_size, rank=rank, world=world)
     shard = dict(local_shard=True) if world > 1 else {}
     if compact or scenes is not None:
@@ -234,6 +249,8 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.random_aug and not args.scene_dataset:
+        sys.exit("--random_aug yes resamples windows of resident scenes: it needs --scene_dataset yes")
     import torch
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
