@@ -1,0 +1,96 @@
+"""Evaluation of a trained model on whole scenes, on the GPU: what test_ISPRS.py does for the reference's test tile (patches,
+predict, arg-max, metrics, mosaic), for a scene directory (resunet_a_mltsk_keras_amd.scenes: scenes/<name>.npy,
+labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride.
+
+Every scene stays on the GPU, is covered by windows --stride apart (default: the patch; the last window flush with the border, so
+nothing is left unpredicted), every pixel is predicted from the window it is most central in, and Model.predict_scene brings back
+only the uint8 class map and the C x C confusion matrix.  metrics_from_confusion turns the matrix into the accuracy / F1 / recall /
+precision of test_ISPRS.compute_metrics_hw.  Per scene it writes `pred_seg_reconstructed_<name>.npy/.ppm` and
+`confusion_matrix_<name>.npy`; the printed and returned metrics are those of the summed matrix.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+from test_ISPRS import LABEL_DICT, build_parser as _patch_parser, convert_preds2rgb
+
+
+def metrics_from_confusion(cm):
+    """compute_metrics_hw from a C x C confusion matrix [true][pred]: accuracy and per-class F1 / recall / precision in percent,
+    (accuracy, f1score, recall, precision).  A class without support (or never predicted) gives 0, sklearn's default apart from its
+    warning; unlike sklearn, which drops a class that occurs in neither array, the vectors always have C entries."""
+    cm = np.asarray(cm, np.float64)
+    if cm.ndim != 2 or cm.shape[0] != cm.shape[1]:
+        raise ValueError(f"a confusion matrix is C x C, got {cm.shape}")
+    tp, support, predicted, total = np.diag(cm), cm.sum(1), cm.sum(0), cm.sum()
+    ratio = lambda num, den: np.divide(num, den, out=np.zeros_like(num), where=den > 0)
+    accuracy = 100 * float(tp.sum() / total) if total > 0 else 0.0
+    return accuracy, 100 * ratio(2 * tp, support + predicted), 100 * ratio(tp, support), 100 * ratio(tp, predicted)
+
+
+def _yes(v):
+    s = str(v).lower()
+    if s in ("yes", "true", "t", "y", "1"):
+        return True
+    if s in ("no", "false", "f", "n", "0"):
+        return False
+    raise argparse.ArgumentTypeError("Boolean value expected.")
+
+
+def build_parser():
+    parser = _patch_parser()                                   # test_ISPRS.py's flags; --dataset_path is the scene directory
+    parser.add_argument("--scene_dataset", type=_yes, default=True, help="as train_ISPRS.py names the layout; this script reads no other")
+    parser.add_argument("--stride", type=int, default=None, help="distance between windows (default: the patch size)")
+    return parser
+
+
+def write_ppm(path, rgb):
+    h, w = rgb.shape[:2]
+    with open(path, 'wb') as f:                                                               # dependency-free image
+        f.write(f"P6\n{w} {h}\n255\n".encode() + np.ascontiguousarray(rgb, dtype=np.uint8).tobytes())
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    from resunet_a_mltsk_keras_amd import scenes
+    from resunet_a_mltsk_keras_amd.keras_api import load_model
+    if not args.scene_dataset:
+        raise SystemExit("--scene_dataset no: test_ISPRS.py evaluates Image_Test.npy / Reference_Test.npy")
+    if args.norm_type not in (1, 2):
+        raise SystemExit("scenes are normalised on the GPU: --norm_type 1 or 2")
+    names, images, class_maps = scenes.load_scene_dir(args.dataset_path)
+    model = load_model(args.model_path, compile=False)
+    model.summary()
+    if model.cfg.num_classes != args.num_classes:
+        raise SystemExit(f"--num_classes {args.num_classes}, but the model predicts {model.cfg.num_classes} classes")
+    pool = scenes.ScenePool(images, class_maps, patch=args.patch_size)
+    os.makedirs(args.output_path, exist_ok=True)
+    lut = {k: v for k, v in LABEL_DICT.items() if v < args.num_classes}
+    for extra in range(len(lut), args.num_classes):                                              # classes beyond the ISPRS colours: greys
+        lut[str((40 * extra % 256,) * 3)] = extra
+    total = np.zeros((args.num_classes, args.num_classes), np.int64)
+    print('=' * 40)
+    print('[TEST]')
+    for s, name in enumerate(names):
+        pred, cm = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type)
+        total += cm
+        print(f'scene {name}: {pred.shape[0]} x {pred.shape[1]}, accuracy {metrics_from_confusion(cm)[0]:.4f}')
+        np.save(os.path.join(args.output_path, f'pred_seg_reconstructed_{name}.npy'), pred)
+        write_ppm(os.path.join(args.output_path, f'pred_seg_reconstructed_{name}.ppm'), convert_preds2rgb(pred, lut))
+        np.save(os.path.join(args.output_path, f'confusion_matrix_{name}.npy'), cm)
+    metrics = metrics_from_confusion(total)
+    print('Confusion  matrix \n', total)
+    print()
+    print('Accuracy: ', metrics[0])
+    print('F1score: ', metrics[1])
+    print('Recall: ', metrics[2])
+    print('Precision: ', metrics[3])
+    return {"accuracy": metrics[0], "f1": metrics[1], "recall": metrics[2], "precision": metrics[3], "confusion_matrix": total}
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

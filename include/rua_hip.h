@@ -479,6 +479,26 @@ int rua_scene_windows_affine(const uint8_t* const* scene_img, const uint8_t* con
                              int nscenes, const int32_t* windows /* [N][7] */, int N, int PH, int PW, int Cin,
                              uint8_t* img_out, uint8_t* cls_out, void* stream);
 
+/* ---- whole-scene evaluation: window probabilities -> a uint8 class map per scene and a confusion matrix (scenes.py, predict_table /
+ * host_stitch; the reference's test_ISPRS.py:26-87 arg-max, mosaic and confusion_matrix done on the device) ----------------------
+ * p is DEVICE memory, fp32 [N][PH][PW][C], 16-byte aligned: the class probabilities of N windows (the seg head's output).  windows
+ * and own are HOST arrays, int32 [N][4]: rows (scene, row, col, 0) as rua_scene_windows reads them, and (r0, r1, c0, c1), the
+ * rectangle of window coordinates [r0, r1) x [c0, c1) this window is responsible for.  scene_pred / scene_cls / scene_h / scene_w are
+ * HOST arrays of nscenes entries: device pointers to a uint8 [scene_h[s]][scene_w[s]] prediction map and class map, and the sizes.
+ * For every window n and every (i, j) of its rectangle:
+ *   pred = first index of the maximum of p[n][i][j][0..C) (a strict > scan from 0: np.argmax on finite input);
+ *   scene_pred[s][row + i][col + j] = pred;  with class maps and t = scene_cls[s][row + i][col + j] < C:  confusion[t][pred] += 1.
+ * confusion is DEVICE memory, int64 [C][C], and is ACCUMULATED into (zero it first); scene_cls and confusion are null together (maps
+ * only).  Nothing outside the rectangles is written; an empty rectangle (r0 == r1 or c0 == c1) writes nothing - a padded batch.
+ * Rectangles that overlap in a scene are the caller's mistake: the map then holds one of the predictions, the matrix counts both.
+ * Integers only, so scenes.host_stitch gives the same bytes and counts whatever the launch order.  Every row is checked on the host
+ * before anything is launched (a violation: RUA_ERR_ARG, the message names the row): 0 <= scene < nscenes, the window inside its
+ * scene, code == 0, 0 <= r0 <= r1 <= PH, 0 <= c0 <= c1 <= PW.  The resolved windows travel as kernel arguments, 120 per launch: no
+ * device-side table, no copy, no synchronisation.  Limits: 1 <= PH, PW <= 512, 1 <= C <= 64. */
+int rua_scene_stitch(const float* p, int N, int PH, int PW, int C, const int32_t* windows, const int32_t* own,
+                     uint8_t* const* scene_pred, const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w,
+                     int nscenes, int64_t* confusion, void* stream);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

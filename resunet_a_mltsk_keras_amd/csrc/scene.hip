@@ -303,3 +303,145 @@ extern "C" int rua_scene_windows_affine(const uint8_t* const* scene_img, const u
   }
   return RUA_OK;
 }
+
+// ---- rua_scene_stitch: class probabilities of prediction windows -> a uint8 class map per scene and a confusion matrix -----------
+// Window n of p [N][PH][PW][C] (fp32, what the seg head leaves) owns the rectangle [r0, r1) x [c0, c1) of itself (scenes.py,
+// predict_table: every scene pixel belongs to exactly one window); each owned pixel's arg-max (first index of the maximum, a strict
+// > scan from class 0) goes into its scene's map and, with a class map t there, into confusion[t][pred].  Integers out of one
+// probability vector each: no float sum, no dependence on order; scenes.host_stitch gives the same bytes.
+//
+// The kernel is bound by reading p.  A block owns up to SS_BAND rows x tw columns of one window's rectangle (tw * C <= SS_ROWF
+// floats, at most 256 columns) and walks it in passes of as many rows as fit into LDS.  An owned row is one contiguous run of
+// (c1 - c0) * C floats that may start at any dword (C = 5: every pixel 20 bytes), so it comes in as the ALIGNED 16-byte pieces
+// that cover it - whole pieces straight into LDS at the same dword phase, single dwords only where a piece would reach past the end
+// of p - and then one lane takes the arg-max of one pixel out of LDS (stride C dwords: free of conflicts for odd C, two-way for
+// C = 6).  Lanes of a wave are neighbouring pixels of a scene row: the class map is read and the prediction written as contiguous
+// bytes.  Counts collect in an LDS histogram of C * C cells (a block holds at most 8 * 256 pixels: 32 bits are plenty) and every
+// non-zero cell leaves with one 64-bit atomicAdd at the end of the block.
+namespace {
+
+constexpr int SS_CHUNK = 120;                  // windows per launch: 32 bytes each
+constexpr int SS_BAND = 8;                     // rows of a window per block
+constexpr int SS_ROWF = 4096;                  // floats of one staged row run at most (C = 64: 64 pixels)
+constexpr int SS_LDSF = 4608;                  // LDS floats: >= one row's pitch (SS_ROWF + 6) / 4 * 4 = 4100
+constexpr int SS_MAXC = 64;
+
+struct StitchWin { uint8_t* pred; const uint8_t* cls; int W; uint16_t r0, r1, c0, c1; int pad; };   // pred, cls: at the window's origin
+struct StitchArgs {
+  StitchWin w[SS_CHUNK];
+  const float* p; unsigned long long* confusion;
+  long long total;                             // floats in p: nothing beyond is read
+  int first, PH, PW, C, tw;                    // first: table row of w[0]; tw: columns per block
+};
+static_assert(sizeof(StitchWin) == 32 && sizeof(StitchArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+__global__ __launch_bounds__(256) void scene_stitch(StitchArgs a) {
+  __shared__ uint4 Sq[SS_LDSF / 4];
+  extern __shared__ uint32_t hist[];             // C * C cells (dynamic: 144 bytes at C = 6, not the 16 KiB of C = 64)
+  float* S = reinterpret_cast<float*>(Sq);
+  const int tid = threadIdx.x, C = a.C, PW = a.PW;
+  const StitchWin& w = a.w[blockIdx.y];
+  const int chunks = (PW + a.tw - 1) / a.tw;
+  const int band = blockIdx.x / chunks, chunk = blockIdx.x - band * chunks;
+  const int i0 = w.r0 + band * SS_BAND, j0 = w.c0 + chunk * a.tw;
+  if (i0 >= w.r1 || j0 >= w.c1) return;        // the whole block: nothing of the rectangle lies here (an empty rectangle: every block)
+  const int th = min(SS_BAND, w.r1 - i0), tw = min(a.tw, w.c1 - j0);
+  const bool count = w.cls != nullptr;
+  if (count)
+    for (int e = tid; e < C * C; e += 256) hist[e] = 0u;
+  const int ne = tw * C, maxp = (ne + 6) / 4, pitch = maxp * 4;        // pieces that cover a run at any phase; LDS row pitch in floats
+  const int R = min(th, SS_LDSF / pitch);
+  const long long wbase = ((long long)(a.first + blockIdx.y) * a.PH) * PW;   // pixel index of the window in p
+  for (int ib = 0; ib < th; ib += R) {
+    const int nr = min(R, th - ib);
+    __syncthreads();                           // the last pass' reads of S (and the zeroing of hist) are done
+    for (int e = tid; e < nr * maxp; e += 256) {
+      const int rr = e / maxp, q = e - rr * maxp;
+      const long long e0 = (wbase + (long long)(i0 + ib + rr) * PW + j0) * C, a0 = e0 & ~3LL;   // the run is floats [e0, e0 + ne) of p
+      const long long lo = a0 + 4 * q;
+      if (lo >= e0 + ne) continue;
+      if (lo + 4 <= a.total) Sq[rr * maxp + q] = ldg16(a.p + lo);
+      else for (long long k = lo; k < a.total; ++k) S[rr * pitch + (int)(k - a0)] = a.p[k];
+    }
+    __syncthreads();
+    for (int e = tid; e < nr * tw; e += 256) {
+      const int rr = e / tw, tj = e - rr * tw, i = i0 + ib + rr, j = j0 + tj;
+      const int phase = (int)(((wbase + (long long)i * PW + j0) * C) & 3);
+      const float* v = S + rr * pitch + phase + tj * C;
+      float best = v[0];
+      int pred = 0;
+      for (int c = 1; c < C; ++c) {
+        const float x = v[c];
+        if (x > best) { best = x; pred = c; }
+      }
+      const size_t at = (size_t)i * w.W + j;
+      w.pred[at] = (uint8_t)pred;
+      if (count) {
+        const int t = w.cls[at];
+        if (t < C) atomicAdd(&hist[t * C + pred], 1u);
+      }
+    }
+  }
+  if (!count) return;
+  __syncthreads();
+  for (int e = tid; e < C * C; e += 256) {
+    const uint32_t n = hist[e];
+    if (n) atomicAdd(a.confusion + e, (unsigned long long)n);
+  }
+}
+
+}  // namespace
+
+extern "C" int rua_scene_stitch(const float* p, int N, int PH, int PW, int C, const int32_t* windows, const int32_t* own,
+                                uint8_t* const* scene_pred, const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w,
+                                int nscenes, int64_t* confusion, void* stream) {
+  RUA_CHECK_ARG(p && windows && own && scene_pred && scene_h && scene_w, "rua_scene_stitch: p, windows, own, scene_pred, scene_h and scene_w are required");
+  RUA_CHECK_ARG(!scene_cls == !confusion, "rua_scene_stitch: scene_cls and confusion go together");
+  RUA_CHECK_ARG(nscenes >= 1 && N >= 1, "rua_scene_stitch: nscenes %d, N %d (both >= 1)", nscenes, N);
+  RUA_CHECK_ARG(C >= 1 && C <= SS_MAXC, "rua_scene_stitch: C %d outside 1..64", C);
+  RUA_CHECK_ARG(PH >= 1 && PW >= 1 && PH <= SW_MAXP && PW <= SW_MAXP, "rua_scene_stitch: PH %d, PW %d (1 <= PH, PW <= 512)", PH, PW);
+  RUA_CHECK_ARG(((uintptr_t)p & 15) == 0 && ((uintptr_t)confusion & 7) == 0, "rua_scene_stitch: p must be 16-byte, confusion 8-byte aligned");
+  for (int s = 0; s < nscenes; ++s) {
+    RUA_CHECK_ARG(scene_pred[s] && (!scene_cls || scene_cls[s]), "rua_scene_stitch: scene %d: null pointer", s);
+    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] < ((int64_t)1 << 40),
+                  "rua_scene_stitch: scene %d: size %d x %d", s, scene_h[s], scene_w[s]);
+  }
+  for (int k = 0; k < N; ++k) {
+    const int32_t* t = windows + 4 * (size_t)k;
+    const int32_t* o = own + 4 * (size_t)k;
+    const int s = t[0], r = t[1], c = t[2];
+    RUA_CHECK_ARG(s >= 0 && s < nscenes, "rua_scene_stitch: row %d: scene %d outside 0..%d", k, s, nscenes - 1);
+    RUA_CHECK_ARG(r >= 0 && c >= 0 && (int64_t)r + PH <= scene_h[s] && (int64_t)c + PW <= scene_w[s],
+                  "rua_scene_stitch: row %d: window (%d, %d) + %d x %d leaves its %d x %d scene", k, r, c, PH, PW, scene_h[s], scene_w[s]);
+    RUA_CHECK_ARG(t[3] == 0, "rua_scene_stitch: row %d: code %d (a prediction window is cut as it is: code 0)", k, t[3]);
+    RUA_CHECK_ARG(0 <= o[0] && o[0] <= o[1] && o[1] <= PH && 0 <= o[2] && o[2] <= o[3] && o[3] <= PW,
+                  "rua_scene_stitch: row %d: owned rows %d..%d, columns %d..%d outside the %d x %d window", k, o[0], o[1], o[2], o[3], PH, PW);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  StitchArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p = p; a.confusion = reinterpret_cast<unsigned long long*>(confusion);
+  a.total = (long long)N * PH * PW * C;
+  a.PH = PH; a.PW = PW; a.C = C;
+  a.tw = SS_ROWF / C < 256 ? SS_ROWF / C : 256;
+  if (a.tw > PW) a.tw = PW;
+  const int blocks = ((PH + SS_BAND - 1) / SS_BAND) * ((PW + a.tw - 1) / a.tw);
+  for (int k0 = 0; k0 < N; k0 += SS_CHUNK) {
+    const int nk = N - k0 < SS_CHUNK ? N - k0 : SS_CHUNK;
+    for (int k = 0; k < nk; ++k) {
+      const int32_t* t = windows + 4 * (size_t)(k0 + k);
+      const int32_t* o = own + 4 * (size_t)(k0 + k);
+      const int s = t[0];
+      const size_t px = (size_t)t[1] * scene_w[s] + t[2];
+      StitchWin& w = a.w[k];
+      w.pred = scene_pred[s] + px;
+      w.cls = scene_cls ? scene_cls[s] + px : nullptr;
+      w.W = scene_w[s];
+      w.r0 = (uint16_t)o[0]; w.r1 = (uint16_t)o[1]; w.c0 = (uint16_t)o[2]; w.c1 = (uint16_t)o[3];
+    }
+    a.first = k0;
+    hipLaunchKernelGGL(scene_stitch, dim3(blocks, nk), dim3(256), scene_cls ? (size_t)C * C * sizeof(uint32_t) : 0, st, a);
+    RUA_LAUNCH_CHECK("rua_scene_stitch");
+  }
+  return RUA_OK;
+}

@@ -2253,8 +2253,16 @@ class Engine:
         self._check_scene(x, None, norm_type, with_labels=False)
         B = x.shape[0]
         g = self.graph(B, False)
-        s = self._stream()
         self._put_batch(g, x, None, norm_type, with_labels=False)
+        self._forward_eval(g)
+        outs = {h["name"]: h["p"].t.cpu().numpy() for h in g.heads}
+        return outs if self.cfg.multitasking else outs["seg"]
+
+    def _forward_eval(self, g: Graph):
+        """The inference forward of the batch already in g.x_in, on the compute stream: the recorded launch list, or its captured HIP
+        graph from the second use of a batch size on (predict and predict_scene share the captures)."""
+        B = g.B
+        s = self._stream()
         self._prep_weights(s)
         cap = self._captured_eval.get(B) if self.use_graph else None
         if cap is None:
@@ -2276,8 +2284,50 @@ class Engine:
             g.fwd.run(s)
         else:
             cap.replay()
-        outs = {h["name"]: h["p"].t.cpu().numpy() for h in g.heads}
-        return outs if self.cfg.multitasking else outs["seg"]
+
+    def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None):
+        """The class map of a whole resident scene: (uint8 [H][W] prediction, int64 [C][C] confusion matrix indexed [true][pred], None
+        for a pool without class maps).  scenes.predict_table covers the scene with windows `stride` apart (None: the patch) and gives
+        every pixel to the window it is most central in; the windows go through the forward `batch` at a time - rua_scene_windows,
+        the plan or captured graph of predict(), then rua_scene_stitch on the seg head's probabilities, all on the compute stream -
+        and only the map and the matrix come back, once, at the end.  The last batch is padded with repeats of its last window that
+        own nothing, so one batch size (one graph, one capture) serves the scene.  A label >= C is not counted.
+        on_batch(rows, own, p): called after each batch's stitch has been issued with the batch's tables and the seg head's device
+        tensor [batch][H][W][C], which the next batch overwrites (clone it to keep it)."""
+        H, W, _ = self.cfg.input_shape
+        Cn = self.cfg.num_classes
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
+            raise ValueError(f"batch {batch!r} must be a positive integer")
+        if pool.patch is None or tuple(pool.patch) != (H, W):
+            raise ValueError(f"the scene pool's patch is {pool.patch}, the model's input {H} x {W}")
+        rows, own = pool.predict_table(scene, stride)
+        self._check_scene(pool.batch(rows[:1]), None, norm_type, with_labels=False)
+        B, SH, SW = int(batch), *pool.shapes[int(scene)]
+        g = self.graph(B, False)
+        seg = g.outputs["seg"]["p"]
+        pred = torch.empty((SH, SW), dtype=torch.uint8, device=self.dev)
+        counted = pool.cls_ptrs is not None
+        conf = torch.zeros((Cn, Cn), dtype=torch.int64, device=self.dev) if counted else None
+        # rua_scene_stitch addresses scenes through host arrays of device pointers, like the pool's own: here one scene, index 0
+        sc = int(scene)
+        pred_ptr, cls_ptr = (C.c_void_p * 1)(pred.data_ptr()), (C.c_void_p * 1)(pool.cls_dev[sc].data_ptr()) if counted else None
+        sh, sw = (C.c_int32 * 1)(SH), (C.c_int32 * 1)(SW)
+        nothing = np.zeros((1, 4), np.int32)
+        for k0 in range(0, len(rows), B):
+            r, o = rows[k0:k0 + B], own[k0:k0 + B]
+            if len(r) < B:
+                r = np.concatenate([r, np.repeat(r[-1:], B - len(r), 0)])
+                o = np.concatenate([o, np.repeat(nothing, B - len(o), 0)])
+            r, o = np.ascontiguousarray(r, dtype=np.int32), np.ascontiguousarray(o, dtype=np.int32)
+            self._upload_scene(g, pool.batch(r), norm_type, with_labels=False)
+            self._forward_eval(g)
+            r0 = r.copy()
+            r0[:, 0] = 0
+            L.lib().call("rua_scene_stitch", seg.ptr, B, H, W, Cn, r0.ctypes.data, o.ctypes.data, pred_ptr, cls_ptr, sh, sw, 1,
+                         conf.data_ptr() if counted else None, C.c_void_p(self._stream()))
+            if on_batch is not None:
+                on_batch(r, o, seg.t)
+        return pred.cpu().numpy(), (conf.cpu().numpy() if counted else None)
 
     def logits(self, training: bool, batch: int) -> Dict[str, np.ndarray]:
         g = self.graph(batch, training)

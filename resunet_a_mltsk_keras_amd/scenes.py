@@ -27,6 +27,11 @@ sy = y0 + i * a_yy + j * a_yx, sx = x0 + i * a_xy + j * a_xx, the image bilinear
 reflect padding at the scene border (host_windows_affine is the definition, rua_scene_windows_affine its kernel).  affine_rows()
 makes such rows from [N][4] rows and a rotation / zoom / shift, AffineSceneBatch carries them, SceneLoader(jitter=) draws them.
 
+Whole-scene evaluation goes the other way: predict_table() covers a scene with windows (the last one flush with the border) and
+gives every scene pixel to exactly one of them, an int32 [N][4] ownership table of (r0, r1, c0, c1) rectangles in window
+coordinates next to the window rows; rua_scene_stitch writes the arg-max of each owned pixel's class probabilities into a uint8
+scene map and counts (true, predicted) pairs into a confusion matrix (host_stitch is its definition, Engine.predict_scene its user).
+
 `python -m resunet_a_mltsk_keras_amd.scenes --image Image_Train.npy --reference Reference_Train.npy --dst DIR` writes a scene
 directory from the reference's two inputs (C x H x W arrays, the reference colour-coded); `--materialize DST` also writes the
 compact patch layout (compact.py) of its window table, for users who want files.
@@ -241,6 +246,101 @@ def affine_rows(rows4: np.ndarray, patch, rotate_deg=0.0, zoom=1.0, shift_q16=(0
     return out.astype(np.int32)
 
 
+# ---- whole-scene prediction: windows that cover a scene, every pixel owned by one of them -----------------------------------------
+MAX_CLASSES = 64
+
+
+def _axis_cover(L: int, P: int, S: int):
+    """One axis of predict_table: (origins [K], owned intervals [K][2] in scene coordinates)."""
+    K = -(-(L - P) // S) + 1
+    o = np.minimum(np.arange(K, dtype=np.int64) * S, L - P)
+    b = np.empty(K + 1, np.int64)
+    b[0], b[K] = 0, L
+    b[1:K] = (o[:-1] + P + o[1:]) // 2                          # half way through the overlap of windows k and k + 1
+    return o, np.stack([b[:-1], b[1:]], 1)
+
+
+def predict_table(shape_hw: Sequence[int], patch, stride: int):
+    """(rows, own), both int32 [N][4]: windows that cover an H x W scene and the part of each that is predicted from it.
+    Per axis of length L (patch P, stride S, 1 <= S <= P <= L): origins o_k = min(k S, L - P) for k < K = ceil((L - P) / S) + 1 - the
+    last window is flush with the border -, cuts b_-1 = 0, b_k = (o_k + P + o_{k+1}) // 2, b_{K-1} = L; window k owns [b_{k-1}, b_k),
+    which lies inside [o_k, o_k + P) since S <= P.  Every scene pixel is owned exactly once, by the window it is most central in.
+    rows: (0, row, col, 0), row-major over (row index, column index) - what rua_scene_windows reads; own: (r0, r1, c0, c1) in
+    window coordinates.  With S == P and L % P == 0 these are the non-overlapping tiles in row-major order, each owned in full.
+    patch and stride may be (rows, columns) pairs."""
+    ph, pw = _patch2(patch)
+    H, W = int(shape_hw[0]), int(shape_hw[1])
+    pair = stride if isinstance(stride, (tuple, list)) and len(stride) == 2 else (stride, stride)     # (rows, columns), as patch
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in pair):
+        raise ValueError(f"stride {stride!r} must be an integer (or a pair of them: rows, columns)")
+    sh, sw = int(pair[0]), int(pair[1])
+    for L, P, S, what in ((H, ph, sh, "rows"), (W, pw, sw, "columns")):
+        if not 1 <= S <= P <= L:
+            raise ValueError(f"predict_table: {what}: stride {S}, patch {P}, scene {L} (1 <= stride <= patch <= scene)")
+    (orow, brow), (ocol, bcol) = _axis_cover(H, ph, sh), _axis_cover(W, pw, sw)
+    rows = np.zeros((len(orow), len(ocol), 4), np.int32)
+    own = np.empty((len(orow), len(ocol), 4), np.int32)
+    rows[..., 1], rows[..., 2] = orow[:, None], ocol[None, :]
+    own[..., 0:2] = (brow - orow[:, None])[:, None, :]
+    own[..., 2:4] = (bcol - ocol[:, None])[None, :, :]
+    return rows.reshape(-1, 4), own.reshape(-1, 4)
+
+
+def check_own(shapes: Sequence[Sequence[int]], rows: np.ndarray, own: np.ndarray, patch, num_classes: int = 1):
+    """(rows, own) as contiguous int32 [N][4] arrays; ValueError, in rua_scene_stitch's own words, for the first violation."""
+    ph, pw = _patch2(patch)
+    t, o = np.asarray(rows), np.asarray(own)
+    for a, what in ((t, "(scene, row, col, 0)"), (o, "(r0, r1, c0, c1)")):
+        if a.ndim != 2 or a.shape[1] != 4 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"rua_scene_stitch takes integer [N][4] arrays of {what} rows, got {a.dtype} {a.shape}")
+    n = len(shapes)
+    if n < 1 or t.shape[0] < 1 or o.shape[0] != t.shape[0]:
+        raise ValueError(f"rua_scene_stitch: nscenes {n}, N {t.shape[0]} windows, {o.shape[0]} ownership rows (both >= 1, one per window)")
+    if not (1 <= ph <= MAX_PATCH and 1 <= pw <= MAX_PATCH):
+        raise ValueError(f"rua_scene_stitch: PH {ph}, PW {pw} (1 <= PH, PW <= 512)")
+    if not 1 <= num_classes <= MAX_CLASSES:
+        raise ValueError(f"rua_scene_stitch: C {num_classes} outside 1..64")
+    for k, ((s, r, c, code), (r0, r1, c0, c1)) in enumerate(zip(t.tolist(), o.tolist())):
+        if not 0 <= s < n:
+            raise ValueError(f"rua_scene_stitch: row {k}: scene {s} outside 0..{n - 1}")
+        H, W = int(shapes[s][0]), int(shapes[s][1])
+        if r < 0 or c < 0 or r + ph > H or c + pw > W:
+            raise ValueError(f"rua_scene_stitch: row {k}: window ({r}, {c}) + {ph} x {pw} leaves its {H} x {W} scene")
+        if code != 0:
+            raise ValueError(f"rua_scene_stitch: row {k}: code {code} (a prediction window is cut as it is: code 0)")
+        if not (0 <= r0 <= r1 <= ph and 0 <= c0 <= c1 <= pw):
+            raise ValueError(f"rua_scene_stitch: row {k}: owned rows {r0}..{r1}, columns {c0}..{c1} outside the {ph} x {pw} window")
+    return np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(o, dtype=np.int32)
+
+
+def host_stitch(p: np.ndarray, rows: np.ndarray, own: np.ndarray, shapes: Sequence[Sequence[int]],
+                class_maps: Optional[Sequence[np.ndarray]] = None, num_classes: Optional[int] = None, fill: int = 0):
+    """The numpy definition of what rua_scene_stitch writes.  p: [N][PH][PW][C] class probabilities of the windows `rows`; for every
+    (i, j) of window n's owned rectangle pred = np.argmax(p[n, i, j]) (the first index of the maximum) goes to
+    maps[scene][row + i, col + j] and, where class maps are given and the label t there is < C, confusion[t, pred] += 1.
+    Returns (uint8 [H][W] map per scene of `shapes`, unowned pixels holding `fill`; int64 [C][C] confusion matrix indexed
+    [true][pred], None without class maps)."""
+    p = np.asarray(p)
+    if p.ndim != 4 or len(p) != len(np.asarray(rows)):
+        raise ValueError(f"p is [N][PH][PW][C] with one window per table row, got {p.shape} for {len(np.asarray(rows))} rows")
+    C = int(p.shape[3]) if num_classes is None else int(num_classes)
+    if C != p.shape[3]:
+        raise ValueError(f"p holds {p.shape[3]} classes, num_classes is {C}")
+    t, o = check_own(shapes, rows, own, p.shape[1:3], C)
+    maps = [np.full((int(h), int(w)), fill, np.uint8) for h, w in shapes]
+    cm = None if class_maps is None else np.zeros((C, C), np.int64)
+    for k, ((s, r, c, _), (r0, r1, c0, c1)) in enumerate(zip(t.tolist(), o.tolist())):
+        if r0 == r1 or c0 == c1:
+            continue
+        pred = np.argmax(p[k, r0:r1, c0:c1], axis=-1)
+        maps[s][r + r0:r + r1, c + c0:c + c1] = pred
+        if cm is not None:
+            true = np.asarray(class_maps[s])[r + r0:r + r1, c + c0:c + c1].astype(np.int64)
+            keep = true < C
+            cm += np.bincount(true[keep] * C + pred[keep], minlength=C * C).reshape(C, C)
+    return maps, cm
+
+
 def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]]) -> int:
     """Scenes are uint8 H x W x C with one C for all, class maps uint8 H x W of their image's size.  Returns C."""
     if len(images) < 1:
@@ -368,6 +468,18 @@ class ScenePool:
         if p is None:
             raise ValueError("no patch size: give ScenePool(patch=) or affine_batch(table7, patch)")
         return AffineSceneBatch(self, check_affine_table(self.shapes, table7, p, self.channels), p)
+
+    def predict_table(self, scene: int, stride: Optional[int] = None):
+        """predict_table of scene `scene` with the pool's patch (stride None: the patch, non-overlapping windows), rows naming it."""
+        if self.patch is None:
+            raise ValueError("no patch size: give ScenePool(patch=)")
+        if not 0 <= int(scene) < len(self):
+            raise ValueError(f"scene {scene} outside 0..{len(self) - 1}")
+        if stride is None:
+            stride = self.patch
+        rows, own = predict_table(self.shapes[int(scene)], self.patch, stride)
+        rows[:, 0] = int(scene)
+        return rows, own
 
 
 class SceneLoader:
