@@ -1,12 +1,16 @@
 """Evaluation of a trained model on whole scenes, on the GPU: what test_ISPRS.py does for the reference's test tile (patches,
 predict, arg-max, metrics, mosaic), for a scene directory (resunet_a_mltsk_keras_amd.scenes: scenes/<name>.npy,
-labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride.
+labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride and --views.
 
 Every scene stays on the GPU, is covered by windows --stride apart (default: the patch; the last window flush with the border, so
 nothing is left unpredicted), every pixel is predicted from the window it is most central in, and Model.predict_scene brings back
 only the uint8 class map and the C x C confusion matrix.  metrics_from_confusion turns the matrix into the accuracy / F1 / recall /
 precision of test_ISPRS.compute_metrics_hw.  Per scene it writes `pred_seg_reconstructed_<name>.npy/.ppm` and
 `confusion_matrix_<name>.npy`; the printed and returned metrics are those of the summed matrix.
+
+--views is test-time augmentation: every window is predicted under the named symmetries (`none`, `flips`, `aug5` - the five copies
+`--data_aug` trains on -, `all`, or a list of codes 0..7 of scenes.transform) in one forward, and the arg-max is taken of the sum of
+the turned-back probabilities (scenes.host_stitch_views).  The output files are the same.
 """
 from __future__ import annotations
 
@@ -45,7 +49,23 @@ def build_parser():
     parser = _patch_parser()                                   # test_ISPRS.py's flags; --dataset_path is the scene directory
     parser.add_argument("--scene_dataset", type=_yes, default=True, help="as train_ISPRS.py names the layout; this script reads no other")
     parser.add_argument("--stride", type=int, default=None, help="distance between windows (default: the patch size)")
+    parser.add_argument("--views", nargs="+", default=["none"], metavar="SET|CODE",
+                        help="test-time augmentation: none, flips, aug5, all, or symmetry codes 0..7 (e.g. --views 0 3 4)")
     return parser
+
+
+def parse_views(words):
+    """--views' words as a tuple of codes: one set name, or codes separated by blanks or commas."""
+    from resunet_a_mltsk_keras_amd import scenes
+    words = [w for word in words for w in str(word).split(",") if w]
+    if len(words) == 1 and words[0] in scenes.VIEW_SETS:
+        return scenes.check_views(words[0])
+    if not words or not all(w.isdigit() for w in words):
+        raise SystemExit(f"--views {' '.join(words)}: one of {', '.join(scenes.VIEW_SETS)}, or symmetry codes 0..7")
+    try:
+        return scenes.check_views(tuple(int(w) for w in words))
+    except ValueError as exc:
+        raise SystemExit(f"--views: {exc}") from None
 
 
 def write_ppm(path, rgb):
@@ -68,6 +88,7 @@ def main(argv=None):
     if model.cfg.num_classes != args.num_classes:
         raise SystemExit(f"--num_classes {args.num_classes}, but the model predicts {model.cfg.num_classes} classes")
     pool = scenes.ScenePool(images, class_maps, patch=args.patch_size)
+    views = parse_views(args.views)
     os.makedirs(args.output_path, exist_ok=True)
     lut = {k: v for k, v in LABEL_DICT.items() if v < args.num_classes}
     for extra in range(len(lut), args.num_classes):                                              # classes beyond the ISPRS colours: greys
@@ -75,8 +96,9 @@ def main(argv=None):
     total = np.zeros((args.num_classes, args.num_classes), np.int64)
     print('=' * 40)
     print('[TEST]')
+    print(f'views: {" ".join(str(c) for c in views)} ({len(views)} per window)')
     for s, name in enumerate(names):
-        pred, cm = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type)
+        pred, cm = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type, views=views)
         total += cm
         print(f'scene {name}: {pred.shape[0]} x {pred.shape[1]}, accuracy {metrics_from_confusion(cm)[0]:.4f}')
         np.save(os.path.join(args.output_path, f'pred_seg_reconstructed_{name}.npy'), pred)

@@ -499,6 +499,25 @@ int rua_scene_stitch(const float* p, int N, int PH, int PW, int C, const int32_t
                      uint8_t* const* scene_pred, const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w,
                      int nscenes, int64_t* confusion, void* stream);
 
+/* Test-time augmentation: the same map and matrix from K views of every window, summed (scenes.py, view_rows / host_stitch_views).
+ * p is fp32 [G*K][PH][PW][C]: rows g*K .. g*K+K-1 of `windows` (HOST, int32 [G*K][4]) name ONE window - the same scene, row and col -
+ * under K symmetry codes (rua_scene_windows' codes 0..7), and p[g*K+k] is the network's answer to that window cut under code_k.
+ * own is HOST int32 [G][4], one rectangle per group, in the window's own (code 0) coordinates.  For every group g and (i, j) of its
+ * rectangle, with q_k = p[g*K+k] turned back into the window's orientation (the inverse symmetry: codes 1 and 5 undo each other,
+ * every other code itself):
+ *   s[c] = q_0[i][j][c];  s[c] = s[c] + q_k[i][j][c] for k = 1 .. K-1   (fp32 adds, strictly in this order; no division)
+ *   pred = first index of the maximum of s;  map and confusion as rua_scene_stitch.
+ * The order is fixed, so scenes.host_stitch_views gives the same bytes and counts whatever the launch order.  Everything else is
+ * rua_scene_stitch's: confusion is accumulated into, scene_cls and confusion are null together, an empty rectangle writes nothing,
+ * every row is checked on the host before anything is launched (RUA_ERR_ARG, the message names the row or the group): 1 <= K <= 8,
+ * 0 <= scene < nscenes, the window inside its scene, every row of a group at the group's scene, row and col, 0 <= code <= 7, a
+ * transposing code (1, 5, 6, 7) only with PH == PW, the rectangle inside the window.  With K = 1 and code 0 the result is
+ * rua_scene_stitch's.  The resolved groups travel as kernel arguments, 120 per launch (the K codes of a group three bits each in one
+ * word): no device-side table, no copy, no synchronisation.  Limits: 1 <= PH, PW <= 512, 1 <= C <= 64; p 16-byte aligned. */
+int rua_scene_stitch_views(const float* p, int G, int K, int PH, int PW, int C, const int32_t* windows /* [G*K][4] */,
+                           const int32_t* own /* [G][4] */, uint8_t* const* scene_pred, const uint8_t* const* scene_cls,
+                           const int32_t* scene_h, const int32_t* scene_w, int nscenes, int64_t* confusion, void* stream);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

@@ -445,3 +445,195 @@ extern "C" int rua_scene_stitch(const float* p, int N, int PH, int PW, int C, co
   }
   return RUA_OK;
 }
+
+// ---- rua_scene_stitch_views: test-time augmentation - K views of every window summed, then the arg-max, map and matrix --------
+// Group g of p [G*K][PH][PW][C] holds K views of ONE window: view k is the network's answer to the window under symmetry code_k
+// (rua_scene_windows cut it so).  Turned back (scenes.INVERSE), the K probability vectors of a window pixel are summed per class by
+// sequential fp32 adds in view order, s = q_0, s = s + q_k - no tree, no atomics, no wider accumulator - and the arg-max of s goes
+// where rua_scene_stitch puts the arg-max of p.  scenes.host_stitch_views gives the same bytes.
+//
+// A block owns a T x T tile of a group's owned rectangle (clipped to it); T, a multiple of 4 up to 32, is the largest with
+// T * T * C <= SV_ACCF, so a thread holds at most SV_SLOTS = 16 (pixel, class) sums in registers, the same ones under every view:
+// the order of a sum is the order of the view loop.  Under any of the eight symmetries the tile is a (transposed, mirrored)
+// rectangle of the view, so every view is read ALONG ITS OWN ROWS: the run of vb * C floats of a view row comes in as the aligned
+// 16-byte pieces that cover it (single dwords only where a piece would reach past the end of p), into LDS at the same dword
+// phase; the turn back happens in the LDS read, whose row pitch is an odd number of 16-byte pieces so that the rows a transposed
+// read walks start in different banks.  A barrier on either side of the staging separates the views.  At the end the sums go to
+// LDS (over the staging area), one lane takes the arg-max of one pixel - lanes along scene rows, so the class map is read and the
+// prediction written as contiguous bytes - and the counts leave as in scene_stitch: an LDS histogram, one 64-bit atomicAdd per
+// non-zero cell.
+namespace {
+
+constexpr int SV_CHUNK = 120;                  // groups per launch: 32 bytes each
+constexpr int SV_MAXK = 8;
+constexpr int SV_ACCF = 4096;                  // sums of one tile at most: T * T * C
+constexpr int SV_SLOTS = SV_ACCF / 256;        // ... and of one thread
+
+struct ViewGroup { uint8_t* pred; const uint8_t* cls; int W; uint16_t r0, r1, c0, c1; uint32_t codes; };   // codes: 3 bits per view, view 0 lowest
+struct ViewArgs {
+  ViewGroup g[SV_CHUNK];
+  const float* p; unsigned long long* confusion;
+  long long total;                             // floats in p: nothing beyond is read
+  int first, PH, PW, C, K, T, maxp;            // first: group of g[0]; maxp: LDS row pitch in 16-byte pieces (odd)
+};
+static_assert(sizeof(ViewGroup) == 32 && sizeof(ViewArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+__global__ __launch_bounds__(256) void scene_stitch_views(ViewArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint4 Vq[];      // T * maxp pieces of staging, then C * C histogram cells
+  float* S = reinterpret_cast<float*>(Vq);
+  const int tid = threadIdx.x, C = a.C, PH = a.PH, PW = a.PW, T = a.T, maxp = a.maxp, pitch = maxp * 4;
+  uint32_t* hist = reinterpret_cast<uint32_t*>(Vq + T * maxp);
+  const ViewGroup& w = a.g[blockIdx.y];
+  const int tiles_x = (PW + T - 1) / T;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int i0 = w.r0 + ty * T, j0 = w.c0 + tx * T;
+  if (i0 >= w.r1 || j0 >= w.c1) return;        // the whole block: nothing of the rectangle lies here (an empty rectangle: every block)
+  const int th = min(T, w.r1 - i0), tw = min(T, w.c1 - j0), ne_tile = th * tw * C;
+  const bool count = w.cls != nullptr;
+  if (count)
+    for (int e = tid; e < C * C; e += 256) hist[e] = 0u;            // the view loop's barriers come before any use
+  // this thread's sums: element e = (ti * tw + tj) * C + c of the tile for e = tid + 256 m
+  int pk[SV_SLOTS];
+  float acc[SV_SLOTS];
+#pragma unroll
+  for (int m = 0; m < SV_SLOTS; ++m) {
+    const int e = tid + 256 * m;
+    pk[m] = 0;
+    acc[m] = 0.f;
+    if (e < ne_tile) {
+      const int px = e / C, c = e - px * C, ti = px / tw, tj = px - ti * tw;
+      pk[m] = (ti << 16) | (tj << 8) | c;
+    }
+  }
+  const long long group = a.first + (long long)blockIdx.y;
+  for (int k = 0; k < a.K; ++k) {
+    const int code = (int)(w.codes >> (3 * k)) & 7;
+    const bool tr = code == 1 || code == 5 || code == 6 || code == 7;
+    const bool fr = code == 2 || code == 3 || code == 5 || code == 7;
+    const bool fc = code == 1 || code == 2 || code == 4 || code == 7;
+    // window pixel (i, j) sits at view (tr ? (y, x) : (x, y)) with x = fr ? PH-1-i : i, y = fc ? PW-1-j : j (PH == PW when tr)
+    const int x0 = fr ? PH - i0 - th : i0, y0 = fc ? PW - j0 - tw : j0;
+    const int a0 = tr ? y0 : x0, b0 = tr ? x0 : y0, va = tr ? tw : th, vb = tr ? th : tw;   // the tile in the view: va rows of vb pixels at (a0, b0)
+    const int ne = vb * C;
+    const long long vbase = (group * a.K + k) * PH * PW;            // pixel index of the view in p
+    __syncthreads();                           // the last view's reads of S are done
+    for (int e = tid; e < va * maxp; e += 256) {
+      const int rr = e / maxp, q = e - rr * maxp;
+      const long long e0 = (vbase + (long long)(a0 + rr) * PW + b0) * C, al = e0 & ~3LL;   // the run is floats [e0, e0 + ne) of p
+      const long long lo = al + 4 * q;
+      if (lo >= e0 + ne) continue;
+      if (lo + 4 <= a.total) Vq[rr * maxp + q] = ldg16(a.p + lo);
+      else for (long long x = lo; x < a.total; ++x) S[rr * pitch + (int)(x - al)] = a.p[x];
+    }
+    __syncthreads();
+    const unsigned pb = (unsigned)vbase + (unsigned)(a0 * PW + b0);  // low bits of a row's first pixel index: its dword phase
+#pragma unroll
+    for (int m = 0; m < SV_SLOTS; ++m) {
+      if (tid + 256 * m < ne_tile) {
+        const int ti = pk[m] >> 16, tj = (pk[m] >> 8) & 255, c = pk[m] & 255;
+        const int xl = fr ? th - 1 - ti : ti, yl = fc ? tw - 1 - tj : tj;
+        const int ra = tr ? yl : xl, cb = tr ? xl : yl;
+        const int phase = (int)(((pb + (unsigned)(ra * PW)) * (unsigned)C) & 3u);
+        const float v = S[ra * pitch + phase + cb * C + c];
+        acc[m] = k == 0 ? v : acc[m] + v;      // sequential fp32 adds in view order
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < SV_SLOTS; ++m)
+    if (tid + 256 * m < ne_tile) S[tid + 256 * m] = acc[m];
+  __syncthreads();
+  for (int e = tid; e < th * tw; e += 256) {
+    const int ti = e / tw, tj = e - ti * tw;
+    const float* v = S + e * C;
+    float best = v[0];
+    int pred = 0;
+    for (int c = 1; c < C; ++c) {
+      const float x = v[c];
+      if (x > best) { best = x; pred = c; }
+    }
+    const size_t at = (size_t)(i0 + ti) * w.W + (j0 + tj);
+    w.pred[at] = (uint8_t)pred;
+    if (count) {
+      const int t = w.cls[at];
+      if (t < C) atomicAdd(&hist[t * C + pred], 1u);
+    }
+  }
+  if (!count) return;
+  __syncthreads();
+  for (int e = tid; e < C * C; e += 256) {
+    const uint32_t n = hist[e];
+    if (n) atomicAdd(a.confusion + e, (unsigned long long)n);
+  }
+}
+
+}  // namespace
+
+extern "C" int rua_scene_stitch_views(const float* p, int G, int K, int PH, int PW, int C, const int32_t* windows, const int32_t* own,
+                                      uint8_t* const* scene_pred, const uint8_t* const* scene_cls, const int32_t* scene_h,
+                                      const int32_t* scene_w, int nscenes, int64_t* confusion, void* stream) {
+  RUA_CHECK_ARG(p && windows && own && scene_pred && scene_h && scene_w,
+                "rua_scene_stitch_views: p, windows, own, scene_pred, scene_h and scene_w are required");
+  RUA_CHECK_ARG(!scene_cls == !confusion, "rua_scene_stitch_views: scene_cls and confusion go together");
+  RUA_CHECK_ARG(nscenes >= 1 && G >= 1, "rua_scene_stitch_views: nscenes %d, G %d (both >= 1)", nscenes, G);
+  RUA_CHECK_ARG(K >= 1 && K <= SV_MAXK, "rua_scene_stitch_views: K %d outside 1..8", K);
+  RUA_CHECK_ARG(C >= 1 && C <= SS_MAXC, "rua_scene_stitch_views: C %d outside 1..64", C);
+  RUA_CHECK_ARG(PH >= 1 && PW >= 1 && PH <= SW_MAXP && PW <= SW_MAXP, "rua_scene_stitch_views: PH %d, PW %d (1 <= PH, PW <= 512)", PH, PW);
+  RUA_CHECK_ARG(((uintptr_t)p & 15) == 0 && ((uintptr_t)confusion & 7) == 0, "rua_scene_stitch_views: p must be 16-byte, confusion 8-byte aligned");
+  for (int s = 0; s < nscenes; ++s) {
+    RUA_CHECK_ARG(scene_pred[s] && (!scene_cls || scene_cls[s]), "rua_scene_stitch_views: scene %d: null pointer", s);
+    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] < ((int64_t)1 << 40),
+                  "rua_scene_stitch_views: scene %d: size %d x %d", s, scene_h[s], scene_w[s]);
+  }
+  for (int g = 0; g < G; ++g) {
+    const int32_t* t0 = windows + 4 * (size_t)g * K;
+    const int32_t* o = own + 4 * (size_t)g;
+    for (int v = 0; v < K; ++v) {
+      const int32_t* t = t0 + 4 * v;
+      const int k = g * K + v, s = t[0], r = t[1], c = t[2], code = t[3];
+      RUA_CHECK_ARG(s >= 0 && s < nscenes, "rua_scene_stitch_views: row %d: scene %d outside 0..%d", k, s, nscenes - 1);
+      RUA_CHECK_ARG(r >= 0 && c >= 0 && (int64_t)r + PH <= scene_h[s] && (int64_t)c + PW <= scene_w[s],
+                    "rua_scene_stitch_views: row %d: window (%d, %d) + %d x %d leaves its %d x %d scene", k, r, c, PH, PW, scene_h[s], scene_w[s]);
+      RUA_CHECK_ARG(s == t0[0] && r == t0[1] && c == t0[2],
+                    "rua_scene_stitch_views: row %d: scene %d, window (%d, %d), but its group %d is scene %d, window (%d, %d)",
+                    k, s, r, c, g, t0[0], t0[1], t0[2]);
+      RUA_CHECK_ARG(code >= 0 && code <= 7, "rua_scene_stitch_views: row %d: code %d outside 0..7", k, code);
+      RUA_CHECK_ARG(PH == PW || !(code == 1 || code >= 5),
+                    "rua_scene_stitch_views: row %d: code %d transposes and needs a square patch (got %d x %d)", k, code, PH, PW);
+    }
+    RUA_CHECK_ARG(0 <= o[0] && o[0] <= o[1] && o[1] <= PH && 0 <= o[2] && o[2] <= o[3] && o[3] <= PW,
+                  "rua_scene_stitch_views: group %d: owned rows %d..%d, columns %d..%d outside the %d x %d window", g, o[0], o[1], o[2], o[3], PH, PW);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ViewArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p = p; a.confusion = reinterpret_cast<unsigned long long*>(confusion);
+  a.total = (long long)G * K * PH * PW * C;
+  a.PH = PH; a.PW = PW; a.C = C; a.K = K;
+  a.T = 32;
+  while (a.T * a.T * C > SV_ACCF) a.T -= 4;                    // C = 64: 8
+  a.maxp = ((a.T * C + 6) / 4) | 1;                            // pieces that cover a run at any phase, made odd
+  const int blocks = ((PH + a.T - 1) / a.T) * ((PW + a.T - 1) / a.T);
+  const size_t lds = (size_t)a.T * a.maxp * 16 + (scene_cls ? (size_t)C * C * sizeof(uint32_t) : 0);   // 33 KiB at most (C = 64)
+  for (int g0 = 0; g0 < G; g0 += SV_CHUNK) {
+    const int ng = G - g0 < SV_CHUNK ? G - g0 : SV_CHUNK;
+    for (int g = 0; g < ng; ++g) {
+      const int32_t* t = windows + 4 * (size_t)(g0 + g) * K;
+      const int32_t* o = own + 4 * (size_t)(g0 + g);
+      const int s = t[0];
+      const size_t px = (size_t)t[1] * scene_w[s] + t[2];
+      ViewGroup& w = a.g[g];
+      w.pred = scene_pred[s] + px;
+      w.cls = scene_cls ? scene_cls[s] + px : nullptr;
+      w.W = scene_w[s];
+      w.r0 = (uint16_t)o[0]; w.r1 = (uint16_t)o[1]; w.c0 = (uint16_t)o[2]; w.c1 = (uint16_t)o[3];
+      w.codes = 0;
+      for (int v = 0; v < K; ++v) w.codes |= (uint32_t)t[4 * v + 3] << (3 * v);
+    }
+    a.first = g0;
+    hipLaunchKernelGGL(scene_stitch_views, dim3(blocks, ng), dim3(256), lds, st, a);
+    RUA_LAUNCH_CHECK("rua_scene_stitch_views");
+  }
+  return RUA_OK;
+}

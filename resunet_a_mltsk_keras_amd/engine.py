@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .scenes import AffineSceneBatch, SceneBatch
+from .scenes import AffineSceneBatch, SceneBatch, check_views, view_rows
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -2285,7 +2285,7 @@ class Engine:
         else:
             cap.replay()
 
-    def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None):
+    def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None, views=(0,)):
         """The class map of a whole resident scene: (uint8 [H][W] prediction, int64 [C][C] confusion matrix indexed [true][pred], None
         for a pool without class maps).  scenes.predict_table covers the scene with windows `stride` apart (None: the patch) and gives
         every pixel to the window it is most central in; the windows go through the forward `batch` at a time - rua_scene_windows,
@@ -2293,16 +2293,26 @@ class Engine:
         and only the map and the matrix come back, once, at the end.  The last batch is padded with repeats of its last window that
         own nothing, so one batch size (one graph, one capture) serves the scene.  A label >= C is not counted.
         on_batch(rows, own, p): called after each batch's stitch has been issued with the batch's tables and the seg head's device
-        tensor [batch][H][W][C], which the next batch overwrites (clone it to keep it)."""
+        tensor [batch][H][W][C], which the next batch overwrites (clone it to keep it).
+        views: test-time augmentation - a tuple of symmetry codes (scenes.transform) or a scenes.VIEW_SETS name.  (0,) is the path
+        above, call for call.  Otherwise every window is predicted under its K views in ONE forward: G = max(1, batch // K) windows
+        make a forward of G * K patches (scenes.view_rows, cut by rua_scene_windows), and rua_scene_stitch_views turns the views
+        back, sums each pixel's K probability vectors in view order and takes the arg-max of the sum (scenes.host_stitch_views is
+        its definition).  Ownership is unchanged; the last batch is padded with repeats of its last group that own nothing;
+        on_batch sees rows [G * K][4], own [G][4] and p [G * K][H][W][C]."""
         H, W, _ = self.cfg.input_shape
         Cn = self.cfg.num_classes
+        views = check_views(views, (H, W))
         if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
             raise ValueError(f"batch {batch!r} must be a positive integer")
         if pool.patch is None or tuple(pool.patch) != (H, W):
             raise ValueError(f"the scene pool's patch is {pool.patch}, the model's input {H} x {W}")
         rows, own = pool.predict_table(scene, stride)
         self._check_scene(pool.batch(rows[:1]), None, norm_type, with_labels=False)
-        B, SH, SW = int(batch), *pool.shapes[int(scene)]
+        K = len(views)
+        tta = views != (0,)
+        G = max(1, int(batch) // K) if tta else int(batch)          # windows per forward
+        B, SH, SW = G * K, *pool.shapes[int(scene)]
         g = self.graph(B, False)
         seg = g.outputs["seg"]["p"]
         pred = torch.empty((SH, SW), dtype=torch.uint8, device=self.dev)
@@ -2313,18 +2323,24 @@ class Engine:
         pred_ptr, cls_ptr = (C.c_void_p * 1)(pred.data_ptr()), (C.c_void_p * 1)(pool.cls_dev[sc].data_ptr()) if counted else None
         sh, sw = (C.c_int32 * 1)(SH), (C.c_int32 * 1)(SW)
         nothing = np.zeros((1, 4), np.int32)
-        for k0 in range(0, len(rows), B):
-            r, o = rows[k0:k0 + B], own[k0:k0 + B]
-            if len(r) < B:
-                r = np.concatenate([r, np.repeat(r[-1:], B - len(r), 0)])
-                o = np.concatenate([o, np.repeat(nothing, B - len(o), 0)])
+        for k0 in range(0, len(rows), G):
+            r, o = rows[k0:k0 + G], own[k0:k0 + G]
+            if len(r) < G:
+                r = np.concatenate([r, np.repeat(r[-1:], G - len(r), 0)])
+                o = np.concatenate([o, np.repeat(nothing, G - len(o), 0)])
+            if tta:
+                r = view_rows(r, views)
             r, o = np.ascontiguousarray(r, dtype=np.int32), np.ascontiguousarray(o, dtype=np.int32)
             self._upload_scene(g, pool.batch(r), norm_type, with_labels=False)
             self._forward_eval(g)
             r0 = r.copy()
             r0[:, 0] = 0
-            L.lib().call("rua_scene_stitch", seg.ptr, B, H, W, Cn, r0.ctypes.data, o.ctypes.data, pred_ptr, cls_ptr, sh, sw, 1,
-                         conf.data_ptr() if counted else None, C.c_void_p(self._stream()))
+            if tta:
+                L.lib().call("rua_scene_stitch_views", seg.ptr, G, K, H, W, Cn, r0.ctypes.data, o.ctypes.data, pred_ptr, cls_ptr, sh, sw, 1,
+                             conf.data_ptr() if counted else None, C.c_void_p(self._stream()))
+            else:
+                L.lib().call("rua_scene_stitch", seg.ptr, B, H, W, Cn, r0.ctypes.data, o.ctypes.data, pred_ptr, cls_ptr, sh, sw, 1,
+                             conf.data_ptr() if counted else None, C.c_void_p(self._stream()))
             if on_batch is not None:
                 on_batch(r, o, seg.t)
         return pred.cpu().numpy(), (conf.cpu().numpy() if counted else None)

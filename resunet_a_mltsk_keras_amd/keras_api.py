@@ -355,18 +355,19 @@ class Model:
             return {h: np.concatenate([o[h] for o in outs], axis=0) for h in HEADS}
         return np.concatenate(outs, axis=0)
 
-    def predict_scene(self, pool, scene, stride=None, batch=8, norm_type=1, on_batch=None):
+    def predict_scene(self, pool, scene, stride=None, batch=8, norm_type=1, on_batch=None, views=(0,)):
         """Engine.predict_scene: (uint8 [H][W] class map of the pool's scene `scene`, int64 [C][C] confusion matrix [true][pred] or None
-        without class maps), the windows cut, predicted and stitched on the GPU; only these two arrays come back."""
+        without class maps), the windows cut, predicted and stitched on the GPU; only these two arrays come back.  views: test-time
+        augmentation, a tuple of symmetry codes or a scenes.VIEW_SETS name ("none", "flips", "aug5", "all")."""
         if self.engine.loss is None:                      # load_model(..., compile=False), as predict
             self.engine.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in HEADS}, weight={h: 1.0 for h in HEADS}))
-        return self.engine.predict_scene(pool, scene, stride=stride, batch=batch, norm_type=norm_type, on_batch=on_batch)
+        return self.engine.predict_scene(pool, scene, stride=stride, batch=batch, norm_type=norm_type, on_batch=on_batch, views=views)
 
-    def evaluate_scenes(self, pool, stride=None, batch_size=8, norm_type=1):
+    def evaluate_scenes(self, pool, stride=None, batch_size=8, norm_type=1, views=(0,)):
         """predict_scene of every scene of the pool: (list of uint8 class maps, the confusion matrices summed - None without class maps)."""
         maps, total = [], None
         for s in range(len(pool)):
-            m, cm = self.predict_scene(pool, s, stride=stride, batch=batch_size, norm_type=norm_type)
+            m, cm = self.predict_scene(pool, s, stride=stride, batch=batch_size, norm_type=norm_type, views=views)
             maps.append(m)
             if cm is not None:
                 total = cm if total is None else total + cm

@@ -32,6 +32,11 @@ gives every scene pixel to exactly one of them, an int32 [N][4] ownership table 
 coordinates next to the window rows; rua_scene_stitch writes the arg-max of each owned pixel's class probabilities into a uint8
 scene map and counts (true, predicted) pairs into a confusion matrix (host_stitch is its definition, Engine.predict_scene its user).
 
+Test-time augmentation keeps that ownership and predicts every window under K of the eight codes, its views: view_rows() repeats a
+code-0 table K times with the codes of VIEW_SETS (or any distinct codes), the K views of a window sit next to each other in one
+forward batch, and rua_scene_stitch_views turns them back (INVERSE), sums each pixel's K probability vectors in float32 in view
+order and takes the arg-max of the sum (host_stitch_views is its definition, Engine.predict_scene(views=) its user).
+
 `python -m resunet_a_mltsk_keras_amd.scenes --image Image_Train.npy --reference Reference_Train.npy --dst DIR` writes a scene
 directory from the reference's two inputs (C x H x W arrays, the reference colour-coded); `--materialize DST` also writes the
 compact patch layout (compact.py) of its window table, for users who want files.
@@ -336,6 +341,140 @@ def host_stitch(p: np.ndarray, rows: np.ndarray, own: np.ndarray, shapes: Sequen
         maps[s][r + r0:r + r1, c + c0:c + c1] = pred
         if cm is not None:
             true = np.asarray(class_maps[s])[r + r0:r + r1, c + c0:c + c1].astype(np.int64)
+            keep = true < C
+            cm += np.bincount(true[keep] * C + pred[keep], minlength=C * C).reshape(C, C)
+    return maps, cm
+
+
+# ---- test-time augmentation: a window predicted under K symmetries (its views), the probabilities summed ------------------------
+INVERSE = (0, 5, 2, 3, 4, 1, 6, 7)            # transform(transform(w, c), INVERSE[c]) is w
+VIEW_SETS = {"none": (0,), "flips": (0, 3, 4), "aug5": (0, 1, 2, 3, 4), "all": (0, 1, 2, 3, 4, 5, 6, 7)}
+MAX_VIEWS = 8
+
+
+def check_views(views, patch=None) -> Tuple[int, ...]:
+    """The views as a tuple of codes: a VIEW_SETS name or 1 to 8 distinct codes in 0..7, a transposing one only with a square patch
+    (patch None: not checked).  ValueError, in rua_scene_stitch_views' own words where it has any."""
+    if isinstance(views, str):
+        if views not in VIEW_SETS:
+            raise ValueError(f"views {views!r}: not one of {sorted(VIEW_SETS)} (or a list of codes 0..7)")
+        views = VIEW_SETS[views]
+    try:
+        v = tuple(views)
+    except TypeError:
+        raise ValueError(f"views {views!r}: a name of {sorted(VIEW_SETS)} or a sequence of codes 0..7") from None
+    if any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) for c in v):
+        raise ValueError(f"views {views!r}: the codes are integers 0..7")
+    v = tuple(int(c) for c in v)
+    if not 1 <= len(v) <= MAX_VIEWS:
+        raise ValueError(f"rua_scene_stitch_views: K {len(v)} outside 1..8")
+    for k, c in enumerate(v):
+        if not 0 <= c < NUM_CODES:
+            raise ValueError(f"rua_scene_stitch_views: row {k}: code {c} outside 0..7")
+        if c in v[:k]:
+            raise ValueError(f"views {v}: code {c} occurs twice")
+    if patch is not None:
+        ph, pw = _patch2(patch)
+        for k, c in enumerate(v):
+            if ph != pw and c in TRANSPOSING:
+                raise ValueError(f"rua_scene_stitch_views: row {k}: code {c} transposes and needs a square patch (got {ph} x {pw})")
+    return v
+
+
+def view_rows(rows: np.ndarray, views) -> np.ndarray:
+    """int32 [G*K][4]: rows g*K .. g*K+K-1 repeat row g of the code-0 table `rows` [G][4] with the codes of `views`, in that order."""
+    v = check_views(views)
+    r = np.asarray(rows)
+    if r.ndim != 2 or r.shape[1] != 4 or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f"a window table is an integer [N][4] array of (scene, row, col, code) rows, got {r.dtype} {r.shape}")
+    out = np.repeat(r.astype(np.int32), len(v), axis=0)
+    out[:, 3] = np.tile(np.asarray(v, np.int32), len(r))
+    return out
+
+
+def check_view_table(shapes: Sequence[Sequence[int]], rows: np.ndarray, own: np.ndarray, views_or_K, patch, num_classes: int = 1):
+    """(rows [G*K][4], own [G][4], K) as contiguous int32 arrays; ValueError, in rua_scene_stitch_views' own words, for the first
+    violation.  views_or_K: K, or the views every group must carry in order (then check_views applies to them too)."""
+    ph, pw = _patch2(patch)
+    t, o = np.asarray(rows), np.asarray(own)
+    for a, what in ((t, "(scene, row, col, code)"), (o, "(r0, r1, c0, c1)")):
+        if a.ndim != 2 or a.shape[1] != 4 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"rua_scene_stitch_views takes integer [N][4] arrays of {what} rows, got {a.dtype} {a.shape}")
+    views = None
+    if isinstance(views_or_K, (int, np.integer)) and not isinstance(views_or_K, bool):
+        K = int(views_or_K)
+    else:
+        views = check_views(views_or_K, patch)
+        K = len(views)
+    n, G = len(shapes), o.shape[0]
+    if n < 1 or G < 1:
+        raise ValueError(f"rua_scene_stitch_views: nscenes {n}, G {G} (both >= 1)")
+    if not 1 <= K <= MAX_VIEWS:
+        raise ValueError(f"rua_scene_stitch_views: K {K} outside 1..8")
+    if t.shape[0] != G * K:
+        raise ValueError(f"rua_scene_stitch_views: {t.shape[0]} window rows for {G} groups of K {K} views (K rows per ownership row)")
+    if not 1 <= num_classes <= MAX_CLASSES:
+        raise ValueError(f"rua_scene_stitch_views: C {num_classes} outside 1..64")
+    if not (1 <= ph <= MAX_PATCH and 1 <= pw <= MAX_PATCH):
+        raise ValueError(f"rua_scene_stitch_views: PH {ph}, PW {pw} (1 <= PH, PW <= 512)")
+    tl = t.tolist()
+    for g, (r0, r1, c0, c1) in enumerate(o.tolist()):
+        s0, ra, ca, _ = tl[g * K]
+        for v in range(K):
+            k = g * K + v
+            s, r, c, code = tl[k]
+            if not 0 <= s < n:
+                raise ValueError(f"rua_scene_stitch_views: row {k}: scene {s} outside 0..{n - 1}")
+            H, W = int(shapes[s][0]), int(shapes[s][1])
+            if r < 0 or c < 0 or r + ph > H or c + pw > W:
+                raise ValueError(f"rua_scene_stitch_views: row {k}: window ({r}, {c}) + {ph} x {pw} leaves its {H} x {W} scene")
+            if (s, r, c) != (s0, ra, ca):
+                raise ValueError(f"rua_scene_stitch_views: row {k}: scene {s}, window ({r}, {c}), but its group {g} is scene {s0}, window ({ra}, {ca})")
+            if not 0 <= code < NUM_CODES:
+                raise ValueError(f"rua_scene_stitch_views: row {k}: code {code} outside 0..7")
+            if ph != pw and code in TRANSPOSING:
+                raise ValueError(f"rua_scene_stitch_views: row {k}: code {code} transposes and needs a square patch (got {ph} x {pw})")
+            if views is not None and code != views[v]:
+                raise ValueError(f"rua_scene_stitch_views: row {k}: code {code}, but view {v} of {views} is code {views[v]}")
+        if not (0 <= r0 <= r1 <= ph and 0 <= c0 <= c1 <= pw):
+            raise ValueError(f"rua_scene_stitch_views: group {g}: owned rows {r0}..{r1}, columns {c0}..{c1} outside the {ph} x {pw} window")
+    return np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(o, dtype=np.int32), K
+
+
+def host_stitch_views(p: np.ndarray, rows: np.ndarray, own: np.ndarray, shapes: Sequence[Sequence[int]],
+                      class_maps: Optional[Sequence[np.ndarray]] = None, num_classes: Optional[int] = None, fill: int = 0):
+    """The numpy definition of what rua_scene_stitch_views writes.  p: [G*K][PH][PW][C] float32, the class probabilities of the K
+    views of G windows (rows [G*K][4], view_rows' layout; own [G][4]; K = len(rows) // len(own)).  For group g the views are turned
+    back, q_k = transform(p[g*K + k], INVERSE[code_k]), and summed in float32 strictly in view order: s = q_0, then s = s + q_k - no
+    pairwise sum, no wider accumulator, no division.  pred = np.argmax(s[i, j]) for every (i, j) of the owned rectangle; the map and
+    the confusion matrix follow as in host_stitch, whose result this is for K = 1 and code 0."""
+    p = np.asarray(p)
+    r, o = np.asarray(rows), np.asarray(own)
+    if o.ndim != 2 or len(o) < 1 or r.ndim != 2 or len(r) % len(o):
+        raise ValueError(f"rows is [G*K][4] and own [G][4]: {len(r)} rows are no multiple of {len(o)} ownership rows")
+    if p.ndim != 4 or len(p) != len(r):
+        raise ValueError(f"p is [G*K][PH][PW][C] with one view per table row, got {p.shape} for {len(r)} rows")
+    if p.dtype != np.float32:
+        raise ValueError(f"p is float32 (the sums are defined in it), got {p.dtype}")
+    C = int(p.shape[3]) if num_classes is None else int(num_classes)
+    if C != p.shape[3]:
+        raise ValueError(f"p holds {p.shape[3]} classes, num_classes is {C}")
+    t, o, K = check_view_table(shapes, r, o, len(r) // len(o), p.shape[1:3], C)
+    maps = [np.full((int(h), int(w)), fill, np.uint8) for h, w in shapes]
+    cm = None if class_maps is None else np.zeros((C, C), np.int64)
+    for g, (r0, r1, c0, c1) in enumerate(o.tolist()):
+        if r0 == r1 or c0 == c1:
+            continue
+        s, row, col, _ = t[g * K].tolist()
+        acc = None
+        for k in range(K):
+            q = transform(p[g * K + k], INVERSE[int(t[g * K + k, 3])])[r0:r1, c0:c1]
+            acc = q.astype(np.float32, copy=True) if acc is None else acc + q
+        assert acc.dtype == np.float32
+        pred = np.argmax(acc, axis=-1)
+        maps[s][row + r0:row + r1, col + c0:col + c1] = pred
+        if cm is not None:
+            true = np.asarray(class_maps[s])[row + r0:row + r1, col + c0:col + c1].astype(np.int64)
             keep = true < C
             cm += np.bincount(true[keep] * C + pred[keep], minlength=C * C).reshape(C, C)
     return maps, cm
