@@ -518,6 +518,23 @@ int rua_scene_stitch_views(const float* p, int G, int K, int PH, int PW, int C, 
                            const int32_t* own /* [G][4] */, uint8_t* const* scene_pred, const uint8_t* const* scene_cls,
                            const int32_t* scene_h, const int32_t* scene_w, int nscenes, int64_t* confusion, void* stream);
 
+/* ---- class counts of scene windows (scenes.py, host_class_counts / class_weights / balance_rows; what the reference's class weights,
+ * train_ISPRS.py:424, and its balance filter, utils.py:383, are functions of) ------------------------------------------------------
+ * Array arguments other than counts are HOST arrays: scene_cls / scene_h / scene_w and windows, int32 [N][4] rows (scene, row, col,
+ * code), as rua_scene_windows reads them.  counts is DEVICE memory, int32 [N][C + 1], 4-byte aligned.  For window n, the PH x PW
+ * pixels scene_cls[scene][row : row + PH, col : col + PW]:
+ *   counts[n][c] = pixels equal to c, for c < C;   counts[n][C] = pixels with a value >= C (the "no class" pixels that
+ *   rua_multitask_targets turns into an all-zero seg row and rua_scene_stitch leaves out of the matrix).
+ * Every row of counts sums to PH * PW.  A symmetry code permutes pixels: it is checked as rua_scene_windows checks it and does not
+ * change the counts.  counts is OVERWRITTEN, not accumulated into: what it held before does not matter (a window is split into row
+ * bands over blocks that add with integer atomics; the zeroing is part of the call, on the same stream).  Integers only, so
+ * scenes.host_class_counts gives the same numbers whatever the launch or arrival order.  Every row is checked on the host before
+ * anything is launched (a violation: RUA_ERR_ARG, the message names the row, nothing is written): 0 <= scene < nscenes, the window
+ * inside its scene, 0 <= code <= 7, a transposing code only with PH == PW.  The resolved windows travel as kernel arguments, 250
+ * per launch (16 bytes each): no device-side table, no copy, no synchronisation.  Limits: 1 <= PH, PW <= 512, 1 <= C <= 64, N >= 1. */
+int rua_scene_class_counts(const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w, int nscenes,
+                           const int32_t* windows, int N, int PH, int PW, int C, int32_t* counts, void* stream);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

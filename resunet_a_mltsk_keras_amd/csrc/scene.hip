@@ -637,3 +637,145 @@ extern "C" int rua_scene_stitch_views(const float* p, int G, int K, int PH, int 
   }
   return RUA_OK;
 }
+
+// ---- rua_scene_class_counts: how many pixels of each class lie in each window of a table ------------------------------------------
+// counts[n][c] for c < C is the number of pixels equal to c in window n of the class map, counts[n][C] the number of pixels >= C
+// (scenes.host_class_counts is the definition).  A symmetry code permutes pixels, so it is checked and otherwise ignored.
+//
+// A block owns a band of R rows of one window, R the largest with R * np <= 512 where np = (PW + 30) / 16 aligned 16-byte pieces
+// cover a row at any byte phase: a lane holds at most SC_KP = 2 pieces, 32 bytes, in registers.  Piece e = tid + 256 m is piece
+// e % np of band row e / np, so neighbouring lanes read neighbouring pieces of a scene row (a wave crosses a row end every np
+// lanes, never a pitch per lane).  A piece that lies wholly inside the row is one 16-byte load; at the ragged ends a dword that
+// lies wholly inside is a dword load and what remains single bytes - nothing outside the window's rows is touched.  Bytes outside
+// the row are 0xFF in the register, which equals no class below 64.
+//
+// Counting is byte-parallel and independent of the content: for a class c the lane XORs its eight dwords with c in every byte
+// and counts the NON-zero bytes (((x & 0x7F7F7F7F) + 0x7F7F7F7F) | x has bit 7 of a byte set exactly when the byte is non-zero;
+// one popcount per dword), so its matches are 32 minus that.  Two classes share one wave reduction, 16 bits each: a lane has at
+// most 32 matches, a wave 2048, so a half cannot carry into the other.  Lane 0 of each wave puts the wave's count into LDS (a cell
+// of its own: no LDS atomics), and after one barrier wave 0 adds the four waves' cells - lane c class c -, takes the >= C count as
+// the band's pixels minus the sum over the classes, and leaves with at most one 32-bit atomicAdd per (window, class) and block.
+// counts is zeroed by a fill launch on the same stream first; the sums are integers, so the order of arrival does not matter.
+namespace {
+
+constexpr int SC_CHUNK = 250;                  // windows per launch: 16 bytes each
+constexpr int SC_KP = 2;                       // 16-byte pieces per lane
+constexpr int SC_MAXC = 64;
+
+struct CountWin { const uint8_t* cls; int W; int pad; };      // cls: at the window's origin
+struct CountArgs {
+  CountWin w[SC_CHUNK];
+  int32_t* counts;                             // of the chunk's first window
+  int PH, PW, C, R, np;                        // R: rows per block; np: pieces per row
+};
+static_assert(sizeof(CountWin) == 16 && sizeof(CountArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+__device__ __forceinline__ int sc_wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void scene_class_counts(CountArgs a) {
+  __shared__ uint32_t part[4 * SC_MAXC];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int PW = a.PW, C = a.C, np = a.np;
+  const CountWin& w = a.w[blockIdx.y];
+  const int i0 = blockIdx.x * a.R, th = min(a.R, a.PH - i0);
+  uint32_t v[SC_KP][4];
+#pragma unroll
+  for (int m = 0; m < SC_KP; ++m) {
+    v[m][0] = v[m][1] = v[m][2] = v[m][3] = 0xFFFFFFFFu;
+    const int e = tid + 256 * m, rr = e / np, q = e - rr * np;
+    if (rr >= th) continue;
+    const uint8_t* row = w.cls + (size_t)(i0 + rr) * w.W;
+    const int s = (int)((uintptr_t)row & 15), end = s + PW;             // the row's bytes sit at al + [s, end)
+    const uint8_t* al = row - s;
+    const int p0 = 16 * q;
+    if (p0 >= s && p0 + 16 <= end) {
+      const uint4 x = ldg16(al + p0);
+      v[m][0] = x.x; v[m][1] = x.y; v[m][2] = x.z; v[m][3] = x.w;
+    } else if (p0 + 16 > s && p0 < end) {
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const int d0 = p0 + 4 * d, lo = max(d0, s), hi = min(d0 + 4, end);
+        if (hi - lo == 4) v[m][d] = *reinterpret_cast<const uint32_t*>(al + d0);
+        else for (int k = lo; k < hi; ++k) v[m][d] = (v[m][d] & ~(0xFFu << (8 * (k - d0)))) | ((uint32_t)al[k] << (8 * (k - d0)));
+      }
+    }
+  }
+  for (int c = 0; c < C; c += 2) {
+    const uint32_t k0 = (uint32_t)c * 0x01010101u, k1 = k0 + 0x01010101u;
+    int n0 = 0, n1 = 0;                        // non-zero bytes of v ^ k: the bytes that are NOT the class
+#pragma unroll
+    for (int m = 0; m < SC_KP; ++m)
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const uint32_t x0 = v[m][d] ^ k0, x1 = v[m][d] ^ k1;
+        n0 += __popc((((x0 & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x0) & 0x80808080u);
+        n1 += __popc((((x1 & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x1) & 0x80808080u);
+      }
+    const int both = sc_wave_sum((16 * SC_KP - n0) | ((16 * SC_KP - n1) << 16));   // a wave: at most 64 * 32 = 2048 per half
+    if (lane == 0) {
+      part[wv * SC_MAXC + c] = (uint32_t)both & 0xFFFFu;
+      if (c + 1 < C) part[wv * SC_MAXC + c + 1] = (uint32_t)both >> 16;
+    }
+  }
+  __syncthreads();
+  if (wv == 0) {
+    const int t = lane < C ? (int)(part[lane] + part[SC_MAXC + lane] + part[2 * SC_MAXC + lane] + part[3 * SC_MAXC + lane]) : 0;
+    const int rest = th * PW - sc_wave_sum(t);                         // the band's pixels with a value >= C
+    int32_t* out = a.counts + (size_t)blockIdx.y * (C + 1);
+    if (lane < C && t) atomicAdd(out + lane, t);
+    if (lane == 0 && rest) atomicAdd(out + C, rest);
+  }
+}
+
+}  // namespace
+
+extern "C" int rua_scene_class_counts(const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w, int nscenes,
+                                      const int32_t* windows, int N, int PH, int PW, int C, int32_t* counts, void* stream) {
+  RUA_CHECK_ARG(scene_cls && scene_h && scene_w && windows && counts, "rua_scene_class_counts: scene_cls, scene_h, scene_w, windows and counts are required");
+  RUA_CHECK_ARG(nscenes >= 1 && N >= 1, "rua_scene_class_counts: nscenes %d, N %d (both >= 1)", nscenes, N);
+  RUA_CHECK_ARG(C >= 1 && C <= SC_MAXC, "rua_scene_class_counts: C %d outside 1..64", C);
+  RUA_CHECK_ARG(PH >= 1 && PW >= 1 && PH <= SW_MAXP && PW <= SW_MAXP, "rua_scene_class_counts: PH %d, PW %d (1 <= PH, PW <= 512)", PH, PW);
+  RUA_CHECK_ARG(((uintptr_t)counts & 3) == 0, "rua_scene_class_counts: counts must be 4-byte aligned");
+  for (int s = 0; s < nscenes; ++s) {
+    RUA_CHECK_ARG(scene_cls[s], "rua_scene_class_counts: scene %d: null pointer", s);
+    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] < ((int64_t)1 << 40),
+                  "rua_scene_class_counts: scene %d: size %d x %d", s, scene_h[s], scene_w[s]);
+  }
+  for (int k = 0; k < N; ++k) {
+    const int32_t* t = windows + 4 * (size_t)k;
+    const int s = t[0], r = t[1], c = t[2], code = t[3];
+    RUA_CHECK_ARG(s >= 0 && s < nscenes, "rua_scene_class_counts: row %d: scene %d outside 0..%d", k, s, nscenes - 1);
+    RUA_CHECK_ARG(r >= 0 && c >= 0 && (int64_t)r + PH <= scene_h[s] && (int64_t)c + PW <= scene_w[s],
+                  "rua_scene_class_counts: row %d: window (%d, %d) + %d x %d leaves its %d x %d scene", k, r, c, PH, PW, scene_h[s], scene_w[s]);
+    RUA_CHECK_ARG(code >= 0 && code <= 7, "rua_scene_class_counts: row %d: code %d outside 0..7", k, code);
+    RUA_CHECK_ARG(PH == PW || !(code == 1 || code >= 5), "rua_scene_class_counts: row %d: code %d transposes and needs a square patch (got %d x %d)",
+                  k, code, PH, PW);
+  }
+  // the bands add into their window's cells: zeroed here, on the same stream, so the call overwrites
+  const int rc = rua_fill_zero(counts, (int64_t)N * (C + 1) * (int64_t)sizeof(int32_t), stream);
+  if (rc != RUA_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  CountArgs a;
+  memset(&a, 0, sizeof(a));
+  a.PH = PH; a.PW = PW; a.C = C;
+  a.np = (PW + 30) / 16;                                       // pieces that cover a row at any phase: 33 at most
+  a.R = 256 * SC_KP / a.np < PH ? 256 * SC_KP / a.np : PH;     // 15 rows at least
+  const int bands = (PH + a.R - 1) / a.R;
+  for (int k0 = 0; k0 < N; k0 += SC_CHUNK) {
+    const int nk = N - k0 < SC_CHUNK ? N - k0 : SC_CHUNK;
+    for (int k = 0; k < nk; ++k) {
+      const int32_t* t = windows + 4 * (size_t)(k0 + k);
+      const int s = t[0];
+      a.w[k].cls = scene_cls[s] + (size_t)t[1] * scene_w[s] + t[2];
+      a.w[k].W = scene_w[s];
+    }
+    a.counts = counts + (size_t)k0 * (C + 1);
+    hipLaunchKernelGGL(scene_class_counts, dim3(bands, nk), dim3(256), 0, st, a);
+    RUA_LAUNCH_CHECK("rua_scene_class_counts");
+  }
+  return RUA_OK;
+}

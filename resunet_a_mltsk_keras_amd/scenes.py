@@ -37,6 +37,12 @@ code-0 table K times with the codes of VIEW_SETS (or any distinct codes), the K 
 forward batch, and rua_scene_stitch_views turns them back (INVERSE), sums each pixel's K probability vectors in float32 in view
 order and takes the arg-max of the sum (host_stitch_views is its definition, Engine.predict_scene(views=) its user).
 
+Class counts close the loop on the dataset: host_class_counts() says how many pixels of each class (and how many of none, a
+value >= C) lie in each window of a table, rua_scene_class_counts is its kernel on the resident class maps and
+ScenePool.class_counts() its user; class_weights() turns the counts of the training rows into the reference's weighted-CE weights
+(total / pixels of the class - its five hard-coded numbers are exactly that for its own patch set) and balance_rows() is the test
+of the reference's bal_aug_patches (keep a window only if a chosen class covers at least `percent` of it) on a window table.
+
 `python -m resunet_a_mltsk_keras_amd.scenes --image Image_Train.npy --reference Reference_Train.npy --dst DIR` writes a scene
 directory from the reference's two inputs (C x H x W arrays, the reference colour-coded); `--materialize DST` also writes the
 compact patch layout (compact.py) of its window table, for users who want files.
@@ -480,6 +486,59 @@ def host_stitch_views(p: np.ndarray, rows: np.ndarray, own: np.ndarray, shapes: 
     return maps, cm
 
 
+# ---- class counts of windows: what class weights and a balance filter are functions of ------------------------------------------
+def _check_classes(num_classes) -> int:
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 1 <= int(num_classes) <= MAX_CLASSES:
+        raise ValueError(f"rua_scene_class_counts: C {num_classes} outside 1..64")
+    return int(num_classes)
+
+
+def host_class_counts(class_maps: Sequence[np.ndarray], table: np.ndarray, patch, num_classes: int) -> np.ndarray:
+    """The numpy definition of what rua_scene_class_counts writes, as int64 [N][C + 1]: for row n = (scene, row, col, code) and the
+    window cm[row:row+PH, col:col+PW], counts[n][c] is the number of pixels equal to c for c < C and counts[n][C] the number with a
+    value >= C.  Every row sums to PH * PW.  The code is checked as check_table checks it and does not change the counts: a
+    symmetry permutes pixels."""
+    ph, pw = _patch2(patch)
+    C_ = _check_classes(num_classes)
+    t = check_table([cm.shape for cm in class_maps], table, patch)
+    out = np.empty((len(t), C_ + 1), np.int64)
+    for k, (s, r, c, _) in enumerate(t.tolist()):
+        w = np.minimum(np.asarray(class_maps[s])[r:r + ph, c:c + pw], C_)
+        out[k] = np.bincount(w.ravel(), minlength=C_ + 1)
+    return out
+
+
+def class_weights(counts: np.ndarray) -> np.ndarray:
+    """float64 [C] weighted-CE class weights of int [N][C + 1] window counts, the reference's rule: with n_c the column sums over
+    c < C (the >= C column is ignored), w_c = sum(n) / n_c.  A class with n_c = 0 gets the largest weight among the classes that
+    are present - it is rare, not free.  ValueError if no pixel carries a class."""
+    a = np.asarray(counts)
+    if a.ndim != 2 or a.shape[1] < 2 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"class counts are an integer [N][C + 1] array, got {a.dtype} {a.shape}")
+    n = a[:, :-1].astype(np.int64).sum(0)
+    total = int(n.sum())
+    if total == 0:
+        raise ValueError("class_weights: no pixel of the counted windows carries a class below C: there is nothing to weigh")
+    w = np.zeros(len(n), np.float64)
+    w[n > 0] = float(total) / n[n > 0]
+    w[n == 0] = w.max()
+    return w
+
+
+def balance_rows(counts: np.ndarray, cls: int, percent: float, patch) -> np.ndarray:
+    """bool [N]: counts[:, cls] >= int(PH * PW * percent / 100) - the test of the reference's bal_aug_patches (utils.py:383), which
+    keeps a patch when class 1 covers at least `percent` of it, with the class a parameter."""
+    ph, pw = _patch2(patch)
+    a = np.asarray(counts)
+    if a.ndim != 2 or a.shape[1] < 2 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"class counts are an integer [N][C + 1] array, got {a.dtype} {a.shape}")
+    if isinstance(cls, bool) or not isinstance(cls, (int, np.integer)) or not 0 <= int(cls) < a.shape[1] - 1:
+        raise ValueError(f"balance_rows: class {cls} outside 0..{a.shape[1] - 2}")
+    if not 0 <= percent <= 100:
+        raise ValueError(f"balance_rows: percent {percent} outside 0..100")
+    return a[:, int(cls)] >= int(ph * pw * percent / 100)
+
+
 def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]]) -> int:
     """Scenes are uint8 H x W x C with one C for all, class maps uint8 H x W of their image's size.  Returns C."""
     if len(images) < 1:
@@ -607,6 +666,31 @@ class ScenePool:
         if p is None:
             raise ValueError("no patch size: give ScenePool(patch=) or affine_batch(table7, patch)")
         return AffineSceneBatch(self, check_affine_table(self.shapes, table7, p, self.channels), p)
+
+    def class_counts(self, rows, num_classes: int, patch=None) -> np.ndarray:
+        """int64 [N][C + 1] class counts of these table rows (host_class_counts is the definition).  The distinct (scene, row,
+        col) windows - the reference's five copies of a window are one - are counted in one rua_scene_class_counts call on the
+        resident class maps, fetched once and scattered back to the rows; a "cpu" pool returns host_class_counts."""
+        p = self.patch if patch is None else _patch2(patch)
+        if p is None:
+            raise ValueError("no patch size: give ScenePool(patch=) or class_counts(rows, num_classes, patch)")
+        if self.class_maps is None:
+            raise ValueError("class_counts needs the pool's class maps")
+        C_ = _check_classes(num_classes)
+        t = check_table(self.shapes, rows, p)
+        if self.device.type != "cuda":
+            return host_class_counts(self.class_maps, t, p, C_)
+        import torch
+        from . import _lib as L
+        uniq, inverse = np.unique(t[:, :3], axis=0, return_inverse=True)
+        win = np.zeros((len(uniq), 4), np.int32)                            # code 0: a symmetry does not change the counts
+        win[:, :3] = uniq
+        with torch.cuda.device(self.device):
+            out = torch.empty((len(win), C_ + 1), dtype=torch.int32, device=self.device)
+            L.lib().call("rua_scene_class_counts", self.cls_ptrs, self.heights, self.widths, len(self), win.ctypes.data, len(win), p[0], p[1], C_,
+                         out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            got = out.cpu().numpy()
+        return got.astype(np.int64)[np.asarray(inverse).reshape(-1)]
 
     def predict_table(self, scene: int, stride: Optional[int] = None):
         """predict_table of scene `scene` with the pool's patch (stride None: the patch, non-overlapping windows), rows naming it."""

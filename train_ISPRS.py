@@ -22,6 +22,13 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
     rotated by a random angle in [-DEG, DEG], zoomed by a log-uniform factor in [LO, HI] and shifted by up to PX pixels (default
     `--stride` / 2), with reflect padding at the scene border, drawn afresh every epoch from `--seed` (scenes.SceneLoader(jitter=)).
     The validation windows and the split are untouched, so validation numbers compare between runs with and without the flag.
+  * `--class_weights auto` (with `--scene_dataset yes --loss weighted_cross_entropy`): the weighted-CE class weights are total /
+    pixels of the class over the training windows (scenes.class_weights; the reference's five numbers are that rule on its own
+    patch set), counted on the GPU from the resident class maps (ScenePool.class_counts).  `--class_weights w0 ... wC-1` gives
+    them explicitly, for any layout.  Without the flag: the reference's five values at 5 classes, uniform weights otherwise.
+  * `--balance_class K --balance_percent P` (with `--scene_dataset yes`): only the training windows in which class K covers at
+    least P percent of the pixels are trained on (the reference's bal_aug_patches, utils.py:383, with the class a parameter;
+    scenes.balance_rows).  The validation windows and the split are untouched.
   * `--dtype {bf16,f32}`, `--seed`: engine options.  Launch with torch.distributed.run for multi-GPU data
     parallel (`-bs` is then the GLOBAL batch, as under MirroredStrategy).
 """
@@ -88,7 +95,56 @@ def build_parser():
     p.add_argument("--aug_rotate", type=float, default=180.0, metavar="DEG", help="random_aug: the angle is uniform in [-DEG, DEG]")
     p.add_argument("--aug_zoom", type=float, nargs=2, default=[0.75, 1.33], metavar=("LO", "HI"), help="random_aug: the zoom is log-uniform in [LO, HI]")
     p.add_argument("--aug_shift", type=float, default=None, metavar="PX", help="random_aug: shift of up to PX pixels per axis (default: stride / 2)")
+    p.add_argument("--class_weights", type=str, nargs="+", default=None, metavar="W",
+                   help="weighted_cross_entropy: `auto` (scene directory: total / pixels of the class over the training windows) or one weight per class")
+    p.add_argument("--balance_class", type=int, default=None, metavar="K",
+                   help="scene directory: train only on windows in which class K covers at least --balance_percent of the pixels")
+    p.add_argument("--balance_percent", type=float, default=None, metavar="P", help="balance_class: the share of the window, in percent")
     return p
+
+
+def check_class_flags(args):
+    """The --class_weights / --balance_* flags checked against the rest of the command line, before anything is loaded: returns
+    None (no flag: today's weights), "auto" or the explicit weights as a list of floats; SystemExit with a message otherwise."""
+    cw = args.class_weights
+    if (args.balance_class is None) != (args.balance_percent is None):
+        sys.exit("--balance_class K and --balance_percent P go together")
+    if args.balance_class is not None:
+        if not args.scene_dataset:
+            sys.exit("--balance_class filters the windows of resident scenes: it needs --scene_dataset yes")
+        if not 0 <= args.balance_class < args.num_classes:
+            sys.exit(f"--balance_class {args.balance_class} outside 0..{args.num_classes - 1} (--num_classes {args.num_classes})")
+        if not 0 <= args.balance_percent <= 100:
+            sys.exit(f"--balance_percent {args.balance_percent} outside 0..100")
+    if cw is None:
+        return None
+    if args.checkpoint_path is not None:
+        sys.exit("--class_weights: with --checkpoint_path the loss, its class weights included, comes from the checkpoint")
+    if args.loss != "weighted_cross_entropy":
+        sys.exit(f"--class_weights are the weights of --loss weighted_cross_entropy, not of --loss {args.loss}")
+    if len(cw) == 1 and cw[0].lower() == "auto":
+        if not args.scene_dataset:
+            sys.exit("--class_weights auto counts the classes of resident scenes: it needs --scene_dataset yes")
+        return "auto"
+    try:
+        w = [float(v) for v in cw]
+    except ValueError:
+        sys.exit(f"--class_weights {' '.join(cw)}: `auto` or one number per class")
+    if len(w) != args.num_classes:
+        sys.exit(f"--class_weights: {len(w)} weights for --num_classes {args.num_classes}")
+    if not all(math.isfinite(v) and v >= 0 for v in w):
+        sys.exit(f"--class_weights {' '.join(cw)}: the weights are finite and not negative")
+    return w
+
+
+def print_class_histogram(say, counts, num_classes):
+    """Pixels and share per class of int64 [N][C + 1] window counts, and the share of pixels that carry no class (>= C)."""
+    n = counts.sum(0)
+    total = max(int(n.sum()), 1)
+    say(f"Class histogram of the {len(counts)} training windows:")
+    for c in range(num_classes):
+        say(f"  class {c}: {int(n[c])} pixels ({100.0 * int(n[c]) / total:.4f} %)")
+    say(f"  no class (>= {num_classes}): {int(n[num_classes])} pixels ({100.0 * int(n[num_classes]) / total:.4f} %)")
 
 
 def compute_mcc(tp, tn, fp, fn):
@@ -251,6 +307,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.random_aug and not args.scene_dataset:
         sys.exit("--random_aug yes resamples windows of resident scenes: it needs --scene_dataset yes")
+    class_weights = check_class_flags(args)
     import torch
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -282,6 +339,26 @@ def main(argv=None):
     else:
         xs, ys = list_compact_dataset(args.dataset_path) if args.compact_dataset else list_dataset(args.dataset_path, args.multitasking)
     x_tr, y_tr, x_va, y_va = split_dataset(xs, ys)
+    if class_weights == "auto" or args.balance_class is not None:
+        # class counts of the training windows, from the resident class maps: every rank computes the same integers itself
+        from resunet_a_mltsk_keras_amd.scenes import balance_rows, patch_index
+        from resunet_a_mltsk_keras_amd.scenes import class_weights as weights_of_counts
+        pool, table = scenes
+        counts = pool.class_counts(table[[patch_index(n) for n in x_tr]], args.num_classes)
+        if args.balance_class is not None:
+            keep = balance_rows(counts, args.balance_class, args.balance_percent, args.patch_size)
+            if not keep.any():
+                sys.exit(f"--balance_class {args.balance_class} --balance_percent {args.balance_percent:g}: none of the {len(keep)} training windows passes")
+            say(f"Balance filter: class {args.balance_class} >= {args.balance_percent:g} % keeps {int(keep.sum())} of {len(keep)} training windows")
+            x_tr = [n for n, k in zip(x_tr, keep) if k]
+            y_tr = {h: [n for n, k in zip(v, keep) if k] for h, v in y_tr.items()}
+            counts = counts[keep]
+        print_class_histogram(say, counts, args.num_classes)
+        if class_weights == "auto":
+            try:
+                class_weights = [float(w) for w in weights_of_counts(counts)]
+            except ValueError as exc:
+                sys.exit(f"--class_weights auto: {exc}")
     rows = cols = args.patch_size
     channels = args.channels or (int(images[0].shape[-1]) if scenes is not None else int(np.load(xs[0]).shape[-1]))
     optm = Adam(lr=args.learning_rate, beta_1=0.9) if args.optimizer == "adam" else SGD(lr=args.learning_rate, momentum=0.8)
@@ -294,7 +371,7 @@ def main(argv=None):
         loss = loss_bound = loss_reg = Tanimoto_dual_loss()
     else:
         say("Using Weighted cross entropy")
-        weights = REFERENCE_WCE_WEIGHTS if args.num_classes == 5 else [1.0] * args.num_classes
+        weights = class_weights if class_weights is not None else REFERENCE_WCE_WEIGHTS if args.num_classes == 5 else [1.0] * args.num_classes
         say(weights)
         loss, loss_bound, loss_reg = weighted_categorical_crossentropy(weights), BinaryCrossentropy(), MeanSquaredError()
     say("=" * 60)
