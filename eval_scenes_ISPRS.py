@@ -1,6 +1,6 @@
 """Evaluation of a trained model on whole scenes, on the GPU: what test_ISPRS.py does for the reference's test tile (patches,
 predict, arg-max, metrics, mosaic), for a scene directory (resunet_a_mltsk_keras_amd.scenes: scenes/<name>.npy,
-labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride and --views.
+labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views and --erode_boundary.
 
 Every scene stays on the GPU, is covered by windows --stride apart (default: the patch; the last window flush with the border, so
 nothing is left unpredicted), every pixel is predicted from the window it is most central in, and Model.predict_scene brings back
@@ -11,6 +11,11 @@ precision of test_ISPRS.compute_metrics_hw.  Per scene it writes `pred_seg_recon
 --views is test-time augmentation: every window is predicted under the named symmetries (`none`, `flips`, `aug5` - the five copies
 `--data_aug` trains on -, `all`, or a list of codes 0..7 of scenes.transform) in one forward, and the arg-max is taken of the sum of
 the turned-back probabilities (scenes.host_stitch_views).  The output files are the same.
+
+--erode_boundary R also scores on the eroded ground truth, the one the ISPRS benchmark and the ResUNet-a paper publish numbers on
+(R = 3 there): class-map pixels within a disc of radius R of a pixel of another value are left out (scenes.host_erode), on the GPU,
+against the same stitched map.  After the full block a second one follows, `Eroded ground truth (radius R)` and the same five
+entries; per scene `confusion_matrix_eroded_<name>.npy` is written, and the returned dict gains the `*_eroded` keys.
 """
 from __future__ import annotations
 
@@ -51,6 +56,8 @@ def build_parser():
     parser.add_argument("--stride", type=int, default=None, help="distance between windows (default: the patch size)")
     parser.add_argument("--views", nargs="+", default=["none"], metavar="SET|CODE",
                         help="test-time augmentation: none, flips, aug5, all, or symmetry codes 0..7 (e.g. --views 0 3 4)")
+    parser.add_argument("--erode_boundary", type=int, default=0, metavar="R",
+                        help="also score on the ground truth eroded by a disc of radius R (0..16; the ISPRS benchmark uses 3); 0: off")
     return parser
 
 
@@ -89,21 +96,30 @@ def main(argv=None):
         raise SystemExit(f"--num_classes {args.num_classes}, but the model predicts {model.cfg.num_classes} classes")
     pool = scenes.ScenePool(images, class_maps, patch=args.patch_size)
     views = parse_views(args.views)
+    try:
+        erode = scenes.check_radius(args.erode_boundary)
+    except ValueError as exc:
+        raise SystemExit(f"--erode_boundary: {exc}") from None
     os.makedirs(args.output_path, exist_ok=True)
     lut = {k: v for k, v in LABEL_DICT.items() if v < args.num_classes}
     for extra in range(len(lut), args.num_classes):                                              # classes beyond the ISPRS colours: greys
         lut[str((40 * extra % 256,) * 3)] = extra
     total = np.zeros((args.num_classes, args.num_classes), np.int64)
+    total_eroded = np.zeros_like(total)
     print('=' * 40)
     print('[TEST]')
     print(f'views: {" ".join(str(c) for c in views)} ({len(views)} per window)')
     for s, name in enumerate(names):
-        pred, cm = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type, views=views)
+        pred, cm, *more = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type, views=views,
+                                              erode=erode)
         total += cm
         print(f'scene {name}: {pred.shape[0]} x {pred.shape[1]}, accuracy {metrics_from_confusion(cm)[0]:.4f}')
         np.save(os.path.join(args.output_path, f'pred_seg_reconstructed_{name}.npy'), pred)
         write_ppm(os.path.join(args.output_path, f'pred_seg_reconstructed_{name}.ppm'), convert_preds2rgb(pred, lut))
         np.save(os.path.join(args.output_path, f'confusion_matrix_{name}.npy'), cm)
+        if erode:
+            total_eroded += more[0]
+            np.save(os.path.join(args.output_path, f'confusion_matrix_eroded_{name}.npy'), more[0])
     metrics = metrics_from_confusion(total)
     print('Confusion  matrix \n', total)
     print()
@@ -111,7 +127,19 @@ def main(argv=None):
     print('F1score: ', metrics[1])
     print('Recall: ', metrics[2])
     print('Precision: ', metrics[3])
-    return {"accuracy": metrics[0], "f1": metrics[1], "recall": metrics[2], "precision": metrics[3], "confusion_matrix": total}
+    res = {"accuracy": metrics[0], "f1": metrics[1], "recall": metrics[2], "precision": metrics[3], "confusion_matrix": total}
+    if erode:
+        m = metrics_from_confusion(total_eroded)
+        print()
+        print(f'Eroded ground truth (radius {erode})')
+        print('Confusion  matrix \n', total_eroded)
+        print()
+        print('Accuracy: ', m[0])
+        print('F1score: ', m[1])
+        print('Recall: ', m[2])
+        print('Precision: ', m[3])
+        res.update(confusion_matrix_eroded=total_eroded, accuracy_eroded=m[0], f1_eroded=m[1], recall_eroded=m[2], precision_eroded=m[3])
+    return res
 
 
 if __name__ == "__main__":

@@ -535,6 +535,26 @@ int rua_scene_stitch_views(const float* p, int G, int K, int PH, int PW, int C, 
 int rua_scene_class_counts(const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w, int nscenes,
                            const int32_t* windows, int N, int PH, int PW, int C, int32_t* counts, void* stream);
 
+/* ---- the eroded ground truth (scenes.py, host_erode / host_erode_confusion; the ISPRS benchmark scores on reference maps from which
+ * every pixel within a disc of radius 3 of a class boundary is left out) ---------------------------------------------------------
+ * scene_cls / scene_h / scene_w are HOST arrays of nscenes entries, as the calls above read them; scene_out and scene_pred are HOST
+ * arrays of nscenes device pointers to uint8 [scene_h[s]][scene_w[s]] maps.  For every pixel (i, j) of every scene:
+ *   out[i][j] = 255 if some offset (dy, dx) with dy * dy + dx * dx <= radius * radius has (i + dy, j + dx) inside the map and
+ *   cls[i + dy][j + dx] != cls[i][j];  otherwise out[i][j] = cls[i][j].
+ * Bytes are compared raw: a "no class" byte (>= C) beside a class pixel erodes that pixel, and stays no class itself; pixels outside
+ * the map do not exist, so the scene border is no boundary; radius 0 is the identity.  255 is no class for every C <= 64: the eroded
+ * map feeds the t < C rule of rua_scene_stitch and rua_scene_class_counts as it is.  scene_out (nullable) receives these bytes.
+ * With scene_pred and confusion (null together; confusion DEVICE memory, int64 [C][C], 8-byte aligned), every pixel with
+ * t = out[i][j] < C and p = scene_pred[s][i][j] < C adds one to confusion[t][p], which is ACCUMULATED into, as rua_scene_stitch does
+ * (zero it first); C is read only then.  One pass over each scene does both.  Integers only, so scenes.host_erode and
+ * scenes.host_erode_confusion give the same bytes and counts whatever the launch or arrival order.  Everything is checked on the host
+ * before anything is launched (a violation: RUA_ERR_ARG, the message names the offender, nothing is written): 0 <= radius <= 16,
+ * nscenes >= 1, at least one of scene_out and (scene_pred, confusion), 1 <= C <= 64 when counting, no null entry in a pointer
+ * array, 1 <= H, W and H * W < 2^40, scene_out[s] != scene_cls[s] (an erosion in place would read its own output).  The scenes
+ * travel as kernel arguments, 120 per launch (32 bytes each): no device-side table, no copy, no synchronisation. */
+int rua_scene_erode(const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w, int nscenes, int radius,
+                    uint8_t* const* scene_out, const uint8_t* const* scene_pred, int C, int64_t* confusion, void* stream);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

@@ -779,3 +779,201 @@ extern "C" int rua_scene_class_counts(const uint8_t* const* scene_cls, const int
   }
   return RUA_OK;
 }
+
+// ---- rua_scene_erode: the eroded ground truth of whole class maps, and the confusion matrix of a prediction against it -----------
+// out[i][j] = 255 if some (dy, dx) with dy^2 + dx^2 <= radius^2 has (i + dy, j + dx) inside the map and a byte there other than
+// cls[i][j], else cls[i][j] (scenes.host_erode is the definition; bytes are compared raw and the scene border is no boundary).
+// With a prediction map, every pixel whose eroded value t < C and whose pred < C counts into confusion[t][pred].
+//
+// The disc is scanned in its O(radius) form.  hd(i, j) is the distance along row i to the nearest byte other than cls[i][j]
+// (127: none within radius); pixel (i, j) erodes iff for some |dy| <= radius, rows clamped into the map - a clamped row is a row of
+// the disc, so clamping adds nothing -, cls[i + dy][j] != cls[i][j] or hd(i + dy, j) <= isqrt(radius^2 - dy^2).
+//
+// A block owns a tile of SE_TH rows x SE_TW columns of one scene.  It stages the tile's rows plus `radius` rows above and below
+// and `radius` columns left and right, as far as they exist, into LDS as bytes: a staged row run may start at any byte (scene
+// widths are arbitrary), so it comes in as the ALIGNED 16-byte pieces that cover it, at the same byte phase - single bytes only
+// where a piece would reach outside the map.  Columns beyond the scene's left or right border are then filled with the border byte
+// (clamping moves an offset towards the centre, so it stays in the disc): the passes below need no border case.
+// Both passes work on FOUR neighbouring pixels of a row at once, bytes of one dword.  A dword at any byte of LDS is two aligned
+// dwords and a v_alignbyte; "which bytes differ" is an XOR and the carry trick of scene_class_counts; "hd <= limit" is one add
+// that carries into bit 7 of a byte.  Pass A: a lane takes four pixels of a staged row and, for d = radius down to 1, the dwords d
+// bytes to the left and to the right, and leaves the four hd bytes in a second LDS image.  Pass B: a lane takes four pixels of a
+// tile row and walks the 2 radius + 1 rows of its columns through both images; lanes run along a scene row, so pred is read and out
+// written as contiguous dwords (single bytes in the ragged last group of a row).  Counts collect in an LDS histogram (a block holds
+// SE_TH * SE_TW = 8192 pixels: 32 bits are plenty) and leave with one 64-bit atomicAdd per non-zero cell.
+namespace {
+
+constexpr int SE_TH = 32, SE_TW = 256;         // tile: rows x columns
+constexpr int SE_MAXR = 16;
+constexpr int SE_ROWS = SE_TH + 2 * SE_MAXR;   // staged rows at most
+constexpr int SE_LEFT = 16;                    // bytes in front of a row's first piece: room for the left border fill at phase 0
+constexpr int SE_NP = (15 + SE_TW + 2 * SE_MAXR + 15) / 16;   // 16-byte pieces that cover a staged run at any phase: 19
+constexpr int SE_PITCH = SE_LEFT + SE_NP * 16; // LDS row pitch in bytes: 320
+constexpr int SE_NONE = 127;                   // hd of a pixel with no other value within radius
+constexpr int SE_CHUNK = 120;                  // scenes per launch: 32 bytes each
+constexpr int SE_MAXC = 64;
+
+struct ErodeScene { const uint8_t* cls; const uint8_t* pred; uint8_t* out; int H, W; };
+struct ErodeArgs {
+  ErodeScene s[SE_CHUNK];
+  unsigned long long* confusion;
+  int radius, C;
+};
+static_assert(sizeof(ErodeScene) == 32 && sizeof(ErodeArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+typedef uint32_t __attribute__((aligned(1))) se_u32u;           // a dword of four pixels at any byte of a global row
+
+// the four bytes at byte address `at` of an LDS image, `at` of any phase: two aligned dwords, funnelled
+__device__ __forceinline__ uint32_t se_ld4(const uint32_t* Td, int at) {
+  return __builtin_amdgcn_alignbyte(Td[(at >> 2) + 1], Td[at >> 2], (uint32_t)at & 3u);
+}
+// bit 7 of every byte of x that is not zero
+__device__ __forceinline__ uint32_t se_nz(uint32_t x) { return (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; }
+// 0xFF in every byte whose bit 7 is set in m (m has no other bits)
+__device__ __forceinline__ uint32_t se_bytes(uint32_t m) { return (m >> 7) * 255u; }
+
+__global__ __launch_bounds__(256) void scene_erode(ErodeArgs a) {
+  __shared__ uint4 Tq[SE_ROWS * SE_PITCH / 16 + 1];   // the staged bytes: column jlo of row rr at rr * SE_PITCH + SE_LEFT + phase(rr); one piece of slack
+  __shared__ uint32_t Hd[SE_ROWS * SE_TW / 4];        // hd of the staged rows over the tile's columns, four pixels a dword
+  __shared__ uint32_t limk[SE_MAXR + 1];              // (127 - isqrt(r^2 - dy^2)) in every byte: hd + limk carries into bit 7 iff hd > limit
+  extern __shared__ uint32_t ehist[];                 // C * C cells, only when counting
+  uint8_t* Tb = reinterpret_cast<uint8_t*>(Tq);
+  const uint32_t* Td = reinterpret_cast<const uint32_t*>(Tq);
+  const ErodeScene& sc = a.s[blockIdx.y];
+  const int tid = threadIdx.x, r = a.radius, C = a.C, H = sc.H, W = sc.W;
+  const int tiles_x = (W + SE_TW - 1) / SE_TW;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  if (ty * SE_TH >= H) return;                   // the whole block: a smaller scene of the chunk
+  const int i0 = ty * SE_TH, j0 = tx * SE_TW;
+  const int th = min(SE_TH, H - i0), tw = min(SE_TW, W - j0), ng = (tw + 3) >> 2;     // ng: groups of four pixels in a tile row
+  const int ilo = max(i0 - r, 0), ihi = min(i0 + th + r, H), nrows = ihi - ilo;      // staged rows [ilo, ihi): at most SE_ROWS
+  const int jlo = max(j0 - r, 0), jhi = min(j0 + tw + r, W), ncols = jhi - jlo;      // staged columns: at most SE_TW + 2 SE_MAXR
+  const bool count = sc.pred != nullptr;
+  if (count)
+    for (int e = tid; e < C * C; e += 256) ehist[e] = 0u;
+  if (tid <= r) {
+    int l = 0;
+    while ((l + 1) * (l + 1) <= r * r - tid * tid) ++l;
+    limk[tid] = (uint32_t)(SE_NONE - l) * 0x01010101u;
+  }
+  const uint8_t* mend = sc.cls + (size_t)H * W;
+  // byte phase of staged row rr, the low four bits of its run's address: (ph0 + rr * W) mod 16
+  const int ph0 = (int)(((uintptr_t)sc.cls + (size_t)ilo * W + jlo) & 15), wl = W & 15;
+#define SE_COL0(rr) ((rr) * SE_PITCH + SE_LEFT + ((ph0 + (rr) * wl) & 15))     // LDS byte of column jlo of staged row rr
+#pragma unroll 1
+  for (int e = tid; e < nrows * SE_NP; e += 256) {
+    const int rr = e / SE_NP, q = e - rr * SE_NP;
+    const uint8_t* row = sc.cls + (size_t)(ilo + rr) * W + jlo;         // the run is bytes [row, row + ncols)
+    const int s = (ph0 + rr * wl) & 15;
+    if (16 * q >= s + ncols) continue;
+    const uint8_t* p = row - s + 16 * q;
+    if (p >= sc.cls && p + 16 <= mend) Tq[rr * (SE_PITCH / 16) + 1 + q] = ldg16(p);   // what lies beside the run is the map's own: read, never used
+    else for (int k = max(16 * q, s); k < min(16 * q + 16, s + ncols); ++k) Tb[rr * SE_PITCH + SE_LEFT + k] = row[k - s];
+  }
+  __syncthreads();
+  if (jlo == 0 || jhi == W) {                    // the whole block: a tile on the scene's left or right border (r >= 1 inside)
+    for (int e = tid; e < nrows * r; e += 256) {
+      const int rr = e / r, d = e - rr * r + 1, c0 = SE_COL0(rr);
+      if (jlo == 0) Tb[c0 - d] = Tb[c0];
+      if (d <= j0 + tw + r - W) Tb[c0 + ncols - 1 + d] = Tb[c0 + ncols - 1];     // the tile's own halo only: at most byte 318 of the row
+    }
+    __syncthreads();
+  }
+#pragma unroll 1
+  for (int e = tid; e < nrows * ng; e += 256) {
+    const int rr = e / ng, k = e - rr * ng;
+    const int at = SE_COL0(rr) + (j0 - jlo) + 4 * k;                    // columns j0 + 4k .. + 3; beyond tw: staged bytes of no meaning, never used
+    const uint32_t v = se_ld4(Td, at);
+    uint32_t h = SE_NONE * 0x01010101u;
+#pragma unroll 4
+    for (int d = r; d >= 1; --d) {                                      // downwards: the smallest distance is written last
+      const uint32_t m = se_bytes(se_nz((se_ld4(Td, at - d) ^ v) | (se_ld4(Td, at + d) ^ v)));
+      h = (h & ~m) | (((uint32_t)d * 0x01010101u) & m);
+    }
+    Hd[rr * (SE_TW / 4) + k] = h;
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int e = tid; e < th * ng; e += 256) {
+    const int ti = e / ng, k = e - ti * ng, i = i0 + ti, j = j0 + 4 * k;
+    const int off = (j0 - jlo) + 4 * k;
+    const uint32_t v = se_ld4(Td, SE_COL0(i - ilo) + off);
+    uint32_t er = 0u;                            // bit 7 of a byte: that pixel erodes
+#pragma unroll 4
+    for (int dy = -r; dy <= r; ++dy) {
+      const int rr = min(max(i + dy, 0), H - 1) - ilo;
+      const uint32_t u = se_ld4(Td, SE_COL0(rr) + off), h = Hd[rr * (SE_TW / 4) + k];
+      er |= se_nz(u ^ v) | (~(h + limk[dy < 0 ? -dy : dy]) & 0x80808080u);
+    }
+    const uint32_t t4 = v | se_bytes(er);
+    const size_t at = (size_t)i * W + j;
+    const int np = min(4, tw - 4 * k);           // pixels of this group inside the tile
+    uint32_t p4 = 0xFFFFFFFFu;
+    if (np == 4) {
+      if (sc.out) *reinterpret_cast<se_u32u*>(sc.out + at) = t4;
+      if (count) p4 = *reinterpret_cast<const se_u32u*>(sc.pred + at);
+    } else {
+      for (int b = 0; b < np; ++b) {
+        if (sc.out) sc.out[at + b] = (uint8_t)(t4 >> (8 * b));
+        if (count) p4 = (p4 & ~(0xFFu << (8 * b))) | ((uint32_t)sc.pred[at + b] << (8 * b));
+      }
+    }
+    if (count) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int t = (t4 >> (8 * b)) & 255, p = (p4 >> (8 * b)) & 255;             // outside the tile: p = 255, no class
+        if (t < C && p < C) atomicAdd(&ehist[t * C + p], 1u);
+      }
+    }
+  }
+  if (!count) return;
+  __syncthreads();
+  for (int e = tid; e < C * C; e += 256) {
+    const uint32_t n = ehist[e];
+    if (n) atomicAdd(a.confusion + e, (unsigned long long)n);
+  }
+#undef SE_COL0
+}
+
+}  // namespace
+
+extern "C" int rua_scene_erode(const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w, int nscenes, int radius,
+                               uint8_t* const* scene_out, const uint8_t* const* scene_pred, int C, int64_t* confusion, void* stream) {
+  RUA_CHECK_ARG(scene_cls && scene_h && scene_w, "rua_scene_erode: scene_cls, scene_h and scene_w are required");
+  RUA_CHECK_ARG(radius >= 0 && radius <= SE_MAXR, "rua_scene_erode: radius %d outside 0..16", radius);
+  RUA_CHECK_ARG(nscenes >= 1, "rua_scene_erode: nscenes %d (>= 1)", nscenes);
+  RUA_CHECK_ARG(!scene_pred == !confusion, "rua_scene_erode: scene_pred and confusion go together");
+  RUA_CHECK_ARG(scene_out || scene_pred, "rua_scene_erode: nothing to do: give scene_out, or scene_pred and confusion, or both");
+  if (scene_pred) {
+    RUA_CHECK_ARG(C >= 1 && C <= SE_MAXC, "rua_scene_erode: C %d outside 1..64", C);
+    RUA_CHECK_ARG(((uintptr_t)confusion & 7) == 0, "rua_scene_erode: confusion must be 8-byte aligned");
+  }
+  for (int s = 0; s < nscenes; ++s) {
+    RUA_CHECK_ARG(scene_cls[s] && (!scene_out || scene_out[s]) && (!scene_pred || scene_pred[s]), "rua_scene_erode: scene %d: null pointer", s);
+    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] < ((int64_t)1 << 40),
+                  "rua_scene_erode: scene %d: size %d x %d", s, scene_h[s], scene_w[s]);
+    RUA_CHECK_ARG(!scene_out || scene_out[s] != scene_cls[s], "rua_scene_erode: scene %d: scene_out is scene_cls (an erosion in place would read its own output)", s);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ErodeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.confusion = reinterpret_cast<unsigned long long*>(confusion);
+  a.radius = radius; a.C = scene_pred ? C : 0;
+  for (int s0 = 0; s0 < nscenes; s0 += SE_CHUNK) {
+    const int ns = nscenes - s0 < SE_CHUNK ? nscenes - s0 : SE_CHUNK;
+    int most = 0;
+    for (int k = 0; k < ns; ++k) {
+      const int s = s0 + k;
+      ErodeScene& e = a.s[k];
+      e.cls = scene_cls[s];
+      e.pred = scene_pred ? scene_pred[s] : nullptr;
+      e.out = scene_out ? scene_out[s] : nullptr;
+      e.H = scene_h[s]; e.W = scene_w[s];
+      const int tiles = ((e.H + SE_TH - 1) / SE_TH) * ((e.W + SE_TW - 1) / SE_TW);   // below 2^28: H * W < 2^40 and a tile holds 2^13 pixels
+      if (tiles > most) most = tiles;
+    }
+    hipLaunchKernelGGL(scene_erode, dim3(most, ns), dim3(256), scene_pred ? (size_t)C * C * sizeof(uint32_t) : 0, st, a);
+    RUA_LAUNCH_CHECK("rua_scene_erode");
+  }
+  return RUA_OK;
+}

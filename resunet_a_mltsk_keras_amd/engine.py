@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .scenes import AffineSceneBatch, SceneBatch, check_views, view_rows
+from .scenes import AffineSceneBatch, SceneBatch, check_radius, check_views, view_rows
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -2285,7 +2285,8 @@ class Engine:
         else:
             cap.replay()
 
-    def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None, views=(0,)):
+    def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None, views=(0,),
+                      erode: int = 0):
         """The class map of a whole resident scene: (uint8 [H][W] prediction, int64 [C][C] confusion matrix indexed [true][pred], None
         for a pool without class maps).  scenes.predict_table covers the scene with windows `stride` apart (None: the patch) and gives
         every pixel to the window it is most central in; the windows go through the forward `batch` at a time - rua_scene_windows,
@@ -2299,10 +2300,18 @@ class Engine:
         make a forward of G * K patches (scenes.view_rows, cut by rua_scene_windows), and rua_scene_stitch_views turns the views
         back, sums each pixel's K probability vectors in view order and takes the arg-max of the sum (scenes.host_stitch_views is
         its definition).  Ownership is unchanged; the last batch is padded with repeats of its last group that own nothing;
-        on_batch sees rows [G * K][4], own [G][4] and p [G * K][H][W][C]."""
+        on_batch sees rows [G * K][4], own [G][4] and p [G * K][H][W][C].
+        erode: 0 is the path and the return value above.  A radius 1..16 also scores the finished map on the eroded ground truth
+        (scenes.host_erode: class-map pixels within that radius of another value become "no class"; the ISPRS benchmark uses 3):
+        after the window loop one rua_scene_erode call counts the stitched prediction against the eroded class map into a second
+        matrix, on the compute stream, and the return value is (prediction, confusion matrix, confusion matrix on the eroded ground
+        truth).  It scores the stitched map, so it works under any views.  ValueError for a pool without class maps."""
         H, W, _ = self.cfg.input_shape
         Cn = self.cfg.num_classes
         views = check_views(views, (H, W))
+        erode = check_radius(erode)
+        if erode and pool.cls_ptrs is None:
+            raise ValueError(f"predict_scene(erode={erode}) needs the pool's class maps: there is no ground truth to erode")
         if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
             raise ValueError(f"batch {batch!r} must be a positive integer")
         if pool.patch is None or tuple(pool.patch) != (H, W):
@@ -2343,6 +2352,10 @@ class Engine:
                              conf.data_ptr() if counted else None, C.c_void_p(self._stream()))
             if on_batch is not None:
                 on_batch(r, o, seg.t)
+        if erode:
+            conf_e = torch.zeros((Cn, Cn), dtype=torch.int64, device=self.dev)
+            L.lib().call("rua_scene_erode", cls_ptr, sh, sw, 1, erode, None, pred_ptr, Cn, conf_e.data_ptr(), C.c_void_p(self._stream()))
+            return pred.cpu().numpy(), conf.cpu().numpy(), conf_e.cpu().numpy()
         return pred.cpu().numpy(), (conf.cpu().numpy() if counted else None)
 
     def logits(self, training: bool, batch: int) -> Dict[str, np.ndarray]:

@@ -43,6 +43,12 @@ ScenePool.class_counts() its user; class_weights() turns the counts of the train
 (total / pixels of the class - its five hard-coded numbers are exactly that for its own patch set) and balance_rows() is the test
 of the reference's bal_aug_patches (keep a window only if a chosen class covers at least `percent` of it) on a window table.
 
+The eroded ground truth is what the ISPRS benchmark publishes numbers on: host_erode() replaces every pixel that has a pixel of
+another value within a disc of `radius` (3 there) by 255, "no class" for every C, because the reference labels are uncertain at
+class boundaries; the scene border is no boundary.  rua_scene_erode is its kernel on resident maps - one pass writes the eroded
+map, counts a prediction map against it into a confusion matrix (host_erode_confusion), or both -, ScenePool.eroded_maps() and
+Engine.predict_scene(erode=) are its users.
+
 `python -m resunet_a_mltsk_keras_amd.scenes --image Image_Train.npy --reference Reference_Train.npy --dst DIR` writes a scene
 directory from the reference's two inputs (C x H x W arrays, the reference colour-coded); `--materialize DST` also writes the
 compact patch layout (compact.py) of its window table, for users who want files.
@@ -539,6 +545,62 @@ def balance_rows(counts: np.ndarray, cls: int, percent: float, patch) -> np.ndar
     return a[:, int(cls)] >= int(ph * pw * percent / 100)
 
 
+# ---- the eroded ground truth: pixels near a class boundary become "no class" ------------------------------------------------------
+MAX_RADIUS = 16
+
+
+def check_radius(radius) -> int:
+    """The erosion radius as an int; ValueError, in rua_scene_erode's own words, unless it is an integer in 0..16."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)):
+        raise ValueError(f"rua_scene_erode: radius {radius!r} is no integer")
+    if not 0 <= int(radius) <= MAX_RADIUS:
+        raise ValueError(f"rua_scene_erode: radius {int(radius)} outside 0..16")
+    return int(radius)
+
+
+def _check_map(a, what: str) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.size == 0:
+        raise ValueError(f"{what} is a non-empty uint8 H x W array, got {a.dtype} {a.shape}")
+    return a
+
+
+def host_erode(class_map: np.ndarray, radius: int) -> np.ndarray:
+    """The numpy definition of what rua_scene_erode writes, uint8 [H][W]: out[i, j] = 255 if some offset (dy, dx) with
+    dy^2 + dx^2 <= radius^2 has (i + dy, j + dx) inside the map and class_map[i + dy, j + dx] != class_map[i, j], otherwise
+    class_map[i, j].  Bytes are compared raw (a value >= C beside a class pixel erodes it and stays what it is - no class - itself),
+    pixels outside the map do not exist (the border is no boundary), radius 0 is the identity, and no class count is involved: 255
+    is "no class" for every C <= 64."""
+    cm = _check_map(class_map, "a class map")
+    r = check_radius(radius)
+    H, W = cm.shape
+    eroded = np.zeros((H, W), bool)
+    for dy in range(-min(r, H - 1), min(r, H - 1) + 1):
+        lim = min(int(np.sqrt(r * r - dy * dy) + 1e-9), W - 1)               # isqrt: the argument is an integer below 2^9
+        for dx in range(-lim, lim + 1):
+            if dy == 0 and dx == 0:
+                continue
+            i0, i1, j0, j1 = max(0, -dy), min(H, H - dy), max(0, -dx), min(W, W - dx)    # the pixels whose neighbour exists
+            eroded[i0:i1, j0:j1] |= cm[i0 + dy:i1 + dy, j0 + dx:j1 + dx] != cm[i0:i1, j0:j1]
+    out = cm.copy()
+    out[eroded] = 255
+    return out
+
+
+def host_erode_confusion(class_map: np.ndarray, pred: np.ndarray, radius: int, num_classes: int) -> np.ndarray:
+    """int64 [C][C] indexed [true][pred]: the (t, pred) pairs over the pixels with t = host_erode(class_map, radius)[i, j] < C and
+    pred[i, j] < C - what rua_scene_erode adds to its confusion matrix."""
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 1 <= int(num_classes) <= MAX_CLASSES:
+        raise ValueError(f"rua_scene_erode: C {num_classes} outside 1..64")
+    C_ = int(num_classes)
+    t = host_erode(class_map, radius).astype(np.int64)
+    p = _check_map(pred, "a prediction map")
+    if p.shape != t.shape:
+        raise ValueError(f"the prediction map is {p.shape}, the class map {t.shape}")
+    keep = (t < C_) & (p < C_)
+    return np.bincount(t[keep] * C_ + p[keep].astype(np.int64), minlength=C_ * C_).reshape(C_, C_)
+
+
 def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]]) -> int:
     """Scenes are uint8 H x W x C with one C for all, class maps uint8 H x W of their image's size.  Returns C."""
     if len(images) < 1:
@@ -691,6 +753,26 @@ class ScenePool:
                          out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
             got = out.cpu().numpy()
         return got.astype(np.int64)[np.asarray(inverse).reshape(-1)]
+
+    def eroded_maps(self, radius: int) -> List[np.ndarray]:
+        """host_erode of every class map of the pool, a list of uint8 [H][W] arrays: one rua_scene_erode call over all resident
+        class maps into one device buffer, fetched once; a "cpu" pool returns host_erode of each map."""
+        if self.class_maps is None:
+            raise ValueError("eroded_maps needs the pool's class maps")
+        r = check_radius(radius)
+        if self.device.type != "cuda":
+            return [host_erode(cm, r) for cm in self.class_maps]
+        import torch
+        from . import _lib as L
+        sizes = [h * w for h, w in self.shapes]
+        first = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        with torch.cuda.device(self.device):
+            out = torch.empty((int(first[-1]),), dtype=torch.uint8, device=self.device)
+            out_ptrs = (C.c_void_p * len(self))(*[out.data_ptr() + int(o) for o in first[:-1]])
+            L.lib().call("rua_scene_erode", self.cls_ptrs, self.heights, self.widths, len(self), r, out_ptrs, None, 0, None,
+                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            got = out.cpu().numpy()
+        return [got[first[s]:first[s + 1]].reshape(self.shapes[s]).copy() for s in range(len(self))]
 
     def predict_table(self, scene: int, stride: Optional[int] = None):
         """predict_table of scene `scene` with the pool's patch (stride None: the patch, non-overlapping windows), rows naming it."""
