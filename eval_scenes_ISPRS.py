@@ -1,6 +1,6 @@
 """Evaluation of a trained model on whole scenes, on the GPU: what test_ISPRS.py does for the reference's test tile (patches,
 predict, arg-max, metrics, mosaic), for a scene directory (resunet_a_mltsk_keras_amd.scenes: scenes/<name>.npy,
-labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views and --erode_boundary.
+labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views, --erode_boundary and --head_maps.
 
 Every scene stays on the GPU, is covered by windows --stride apart (default: the patch; the last window flush with the border, so
 nothing is left unpredicted), every pixel is predicted from the window it is most central in, and Model.predict_scene brings back
@@ -16,6 +16,12 @@ the turned-back probabilities (scenes.host_stitch_views).  The output files are 
 (R = 3 there): class-map pixels within a disc of radius R of a pixel of another value are left out (scenes.host_erode), on the GPU,
 against the same stitched map.  After the full block a second one follows, `Eroded ground truth (radius R)` and the same five
 entries; per scene `confusion_matrix_eroded_<name>.npy` is written, and the returned dict gains the `*_eroded` keys.
+
+--head_maps HEAD [HEAD ...] also writes whole-scene maps of the named heads (`seg`, `bound`, `dist`, `color`, `color_rgb`; what
+test_ISPRS.py:285-414 displays per patch): `pred_<head>_<name>.npy`, uint8 H x W x Ch - the head's output averaged over the views,
+times 255, rounded (scenes.host_stitch_maps), stitched on the GPU by the same windows and ownership as the class map.  `color_rgb`
+is the colour head's HSV turned into an RGB picture; it is also written as `pred_color_rgb_<name>.ppm`, and its mean absolute
+difference from the scene image is printed.  The returned dict gains `head_maps` (per scene {head: map}) and `color_mae`.
 """
 from __future__ import annotations
 
@@ -58,6 +64,8 @@ def build_parser():
                         help="test-time augmentation: none, flips, aug5, all, or symmetry codes 0..7 (e.g. --views 0 3 4)")
     parser.add_argument("--erode_boundary", type=int, default=0, metavar="R",
                         help="also score on the ground truth eroded by a disc of radius R (0..16; the ISPRS benchmark uses 3); 0: off")
+    parser.add_argument("--head_maps", nargs="+", default=[], metavar="HEAD",
+                        help="also write uint8 whole-scene maps of these heads: seg, bound, dist, color, color_rgb (default: none)")
     return parser
 
 
@@ -89,6 +97,12 @@ def main(argv=None):
         raise SystemExit("--scene_dataset no: test_ISPRS.py evaluates Image_Test.npy / Reference_Test.npy")
     if args.norm_type not in (1, 2):
         raise SystemExit("scenes are normalised on the GPU: --norm_type 1 or 2")
+    heads = tuple(args.head_maps)
+    for k, h in enumerate(heads):
+        if h not in scenes.MAP_HEADS or h in heads[:k]:
+            raise SystemExit(f"--head_maps {' '.join(heads)}: distinct names out of {', '.join(scenes.MAP_HEADS)}")
+    if "color_rgb" in heads and args.norm_type != 1:
+        raise SystemExit("--head_maps color_rgb needs --norm_type 1 (the colour target is HSV / (179, 255, 255) only there)")
     names, images, class_maps = scenes.load_scene_dir(args.dataset_path)
     model = load_model(args.model_path, compile=False)
     model.summary()
@@ -100,18 +114,22 @@ def main(argv=None):
         erode = scenes.check_radius(args.erode_boundary)
     except ValueError as exc:
         raise SystemExit(f"--erode_boundary: {exc}") from None
+    if heads and not (model.cfg.multitasking or heads == ("seg",)):
+        raise SystemExit(f"--head_maps {' '.join(heads)}: a single-task model has only the seg head")
     os.makedirs(args.output_path, exist_ok=True)
     lut = {k: v for k, v in LABEL_DICT.items() if v < args.num_classes}
     for extra in range(len(lut), args.num_classes):                                              # classes beyond the ISPRS colours: greys
         lut[str((40 * extra % 256,) * 3)] = extra
     total = np.zeros((args.num_classes, args.num_classes), np.int64)
     total_eroded = np.zeros_like(total)
+    all_head_maps, mae_sum, mae_n = [], 0.0, 0
     print('=' * 40)
     print('[TEST]')
     print(f'views: {" ".join(str(c) for c in views)} ({len(views)} per window)')
     for s, name in enumerate(names):
         pred, cm, *more = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type, views=views,
-                                              erode=erode)
+                                              erode=erode, heads=heads)
+        head_maps = more.pop() if heads else {}
         total += cm
         print(f'scene {name}: {pred.shape[0]} x {pred.shape[1]}, accuracy {metrics_from_confusion(cm)[0]:.4f}')
         np.save(os.path.join(args.output_path, f'pred_seg_reconstructed_{name}.npy'), pred)
@@ -120,6 +138,16 @@ def main(argv=None):
         if erode:
             total_eroded += more[0]
             np.save(os.path.join(args.output_path, f'confusion_matrix_eroded_{name}.npy'), more[0])
+        for h, m in head_maps.items():
+            np.save(os.path.join(args.output_path, f'pred_{h}_{name}.npy'), m)
+        if "color_rgb" in head_maps:
+            rgb = head_maps["color_rgb"]
+            write_ppm(os.path.join(args.output_path, f'pred_color_rgb_{name}.ppm'), rgb)
+            diff = np.abs(rgb.astype(np.int16) - images[s][..., :3].astype(np.int16))
+            mae_sum, mae_n = mae_sum + float(diff.sum()), mae_n + diff.size
+            print(f'scene {name}: colour reconstruction, mean absolute difference from the image {diff.mean():.4f}')
+        if heads:
+            all_head_maps.append(head_maps)
     metrics = metrics_from_confusion(total)
     print('Confusion  matrix \n', total)
     print()
@@ -139,6 +167,12 @@ def main(argv=None):
         print('Recall: ', m[2])
         print('Precision: ', m[3])
         res.update(confusion_matrix_eroded=total_eroded, accuracy_eroded=m[0], f1_eroded=m[1], recall_eroded=m[2], precision_eroded=m[3])
+    if heads:
+        res["head_maps"] = all_head_maps
+        res["color_mae"] = mae_sum / mae_n if mae_n else None
+        if mae_n:
+            print()
+            print('Colour reconstruction, mean absolute difference: ', res["color_mae"])
     return res
 
 

@@ -518,6 +518,33 @@ int rua_scene_stitch_views(const float* p, int G, int K, int PH, int PW, int C, 
                            const int32_t* own /* [G][4] */, uint8_t* const* scene_pred, const uint8_t* const* scene_cls,
                            const int32_t* scene_h, const int32_t* scene_w, int nscenes, int64_t* confusion, void* stream);
 
+/* Whole-scene maps of any head: fp32 window outputs under K views -> uint8 maps of Ch interleaved channels (scenes.py,
+ * host_stitch_maps; what the reference's test_ISPRS.py:285-414 shows of the boundary, distance and colour heads and of the seg
+ * head's per-class probability).  p, G, K, PH, PW, windows and own are rua_scene_stitch_views': p is DEVICE fp32 [G*K][PH][PW][Ch],
+ * 16-byte aligned, any head's output; windows (HOST int32 [G*K][4]) and own (HOST int32 [G][4]) name the groups, their view codes and
+ * the rectangle each group owns.  scene_out / scene_h / scene_w are HOST arrays of nscenes entries: scene_out[s] is a device pointer
+ * to uint8 [scene_h[s]][scene_w[s]][Ch].  For every group g, every (i, j) of its rectangle and every channel c, with q_k = p[g*K+k]
+ * turned back into the window's orientation and
+ *   a_k = rint(y * 65536), y = q_k[i][j][c] > 0 ? min(q_k[i][j][c], 1) : 0   (fp32, ties to even; NaN and -inf give 0, +inf 65536;
+ *                                                                              the multiply by a power of two is exact)
+ * mode 0 (plain):    A = a_0 + .. + a_{K-1};  out[row + i][col + j][c] = (255 A + K 32768) / (K 65536)   - the rounded mean, 0..255;
+ * mode 1 (hsv_rgb):  Ch = 3.  Per view h = 179 a_k[0] >> 16, s = 255 a_k[1] >> 16, v = 255 a_k[2] >> 16 (truncation), then with
+ *   sec = h / 30, f = h % 30, p = (v (255 - s) + 127) / 255, q = (v (7650 - s f) + 3825) / 7650, t = (v (7650 - s (30 - f)) + 3825) / 7650:
+ *   rgb_k = (v,t,p), (q,v,p), (p,v,t), (p,q,v), (t,p,v), (v,p,q) for sec = 0..5;  out = (2 (rgb_0 + .. + rgb_{K-1}) + K) / (2 K).
+ *   The views are averaged in RGB because hue is circular.
+ * All divisions are integer divisions of non-negative numbers, every intermediate stays below 2^28: integers from the first step
+ * on, so scenes.host_stitch_maps gives the same bytes whatever the order of views, launches or lanes.  Nothing outside the owned
+ * rectangles is written - a tile row leaves as the aligned dwords wholly inside it and single bytes at its ragged ends -, an empty
+ * rectangle writes nothing, rectangles that overlap in a scene are the caller's mistake.  Everything is checked on the host before
+ * anything is launched (a violation: RUA_ERR_ARG, the message names the row, the group or the scene, nothing is written):
+ * 1 <= K <= 8, 1 <= Ch <= 64, mode 0 or 1 and mode 1 only with Ch == 3, 1 <= PH, PW <= 512, p 16-byte aligned, no null entry in
+ * scene_out, 1 <= H, W and H * W * Ch < 2^40, 0 <= scene < nscenes, the window inside its scene, every row of a group at the group's
+ * scene, row and col, 0 <= code <= 7, a transposing code only with PH == PW, the rectangle inside the window.  The resolved groups
+ * travel as kernel arguments, 120 per launch: no device-side table, no copy, no synchronisation. */
+int rua_scene_stitch_maps(const float* p, int G, int K, int PH, int PW, int Ch, const int32_t* windows /* [G*K][4] */,
+                          const int32_t* own /* [G][4] */, uint8_t* const* scene_out, const int32_t* scene_h,
+                          const int32_t* scene_w, int nscenes, int mode /* 0 plain, 1 hsv_rgb */, void* stream);
+
 /* ---- class counts of scene windows (scenes.py, host_class_counts / class_weights / balance_rows; what the reference's class weights,
  * train_ISPRS.py:424, and its balance filter, utils.py:383, are functions of) ------------------------------------------------------
  * Array arguments other than counts are HOST arrays: scene_cls / scene_h / scene_w and windows, int32 [N][4] rows (scene, row, col,

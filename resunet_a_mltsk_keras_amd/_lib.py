@@ -175,6 +175,7 @@ _SIGS = {
     "rua_scene_windows_affine": ([vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp], i32),
     "rua_scene_stitch": ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp], i32),
     "rua_scene_stitch_views": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp], i32),
+    "rua_scene_stitch_maps": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp], i32),
     "rua_scene_class_counts": ([vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp], i32),
     "rua_scene_erode": ([vp, vp, vp, i32, i32, vp, vp, i32, vp, vp], i32),
     "rua_set_tuning": ([C.c_char_p, i64], i32),

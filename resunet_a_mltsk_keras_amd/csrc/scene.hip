@@ -638,6 +638,233 @@ extern "C" int rua_scene_stitch_views(const float* p, int G, int K, int PH, int 
   return RUA_OK;
 }
 
+// ---- rua_scene_stitch_maps: any head's window outputs under K views -> a uint8 scene map of Ch interleaved channels -------------
+// The same groups, ownership and view codes as rua_scene_stitch_views, but the map keeps every channel: a float becomes the integer
+// a = rint(clamp(x, 0, 1) * 65536) the moment it leaves LDS (sm_q16: a multiply by a power of two, so contraction cannot matter), and
+// everything after is integer arithmetic - the order of the views, of the launches and of the lanes cannot change a byte, and
+// scenes.host_stitch_maps gives the same ones.  Mode 0 (plain): A = sum of a_k, out = (255 A + K 32768) / (K 65536), the rounded
+// mean.  Mode 1 (hsv_rgb, Ch = 3): every view's (h, s, v) = (179 a_0 >> 16, 255 a_1 >> 16, 255 a_2 >> 16) goes through sm_hsv_rgb
+// and the views are averaged in RGB, out = (2 sum + K) / (2 K): hue is circular, its mean is not a hue.
+//
+// The read side is scene_stitch_views': a block owns a T x T tile of a group's rectangle, each view comes in along its own rows
+// (sm_stage), the turn back happens in the LDS read and the sums stay in registers over the view loop - in mode 0 a thread holds
+// (pixel, channel) elements tid + 256 m, consecutive lanes consecutive floats of a window row (free of bank conflicts under a
+// code that keeps rows, stride Ch dwords under a transposing one: odd pitch, so 2-way at most for even Ch); in mode 1 it holds
+// whole pixels tid + 256 m (T = 32: four of them), three floats at a stride of 3 dwords between lanes, conflict-free.
+//
+// The write side: a tile row is tw * Ch bytes of a scene row at ANY byte phase (W * Ch is odd as often as not), and its
+// neighbours in the same dword belong to other blocks.  The finished bytes go into an LDS image of the tile, row ti at the byte
+// phase of its scene row, and leave as the aligned dwords that lie wholly inside the row plus single bytes at its two ragged ends,
+// lanes along the row - what scene_windows does on its read side, mirrored.  No lane stores a byte outside its rectangle.
+namespace {
+
+constexpr int SM_CHUNK = 120;                  // groups per launch: 32 bytes each
+constexpr int SM_PIX = 4;                      // pixels of one thread in mode 1: 32 * 32 / 256
+
+struct MapGroup { uint8_t* out; int W; uint16_t r0, r1, c0, c1; uint32_t codes; int pad; };   // out: at the window's origin; codes as ViewGroup's
+struct MapArgs {
+  MapGroup g[SM_CHUNK];
+  const float* p;
+  long long total;                             // floats in p: nothing beyond is read
+  int first, PH, PW, Ch, K, T, maxp;           // as ViewArgs
+};
+static_assert(sizeof(MapGroup) == 32 && sizeof(MapArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+// NaN and everything <= 0 give 0, everything >= 1 (+inf too) 65536; ties to even
+__device__ __forceinline__ uint32_t sm_q16(float x) {
+  const float y = x > 0.f ? fminf(x, 1.f) : 0.f;
+  return (uint32_t)__float2int_rn(y * 65536.f);
+}
+
+// scenes.hsv_to_rgb_u8: the textbook sector formula rounded exactly, h in 0..179 (30 per sector), s and v in 0..255
+__device__ __forceinline__ void sm_hsv_rgb(uint32_t h, uint32_t s, uint32_t v, uint32_t& r, uint32_t& g, uint32_t& b) {
+  const uint32_t sec = h / 30u, f = h - sec * 30u;
+  const uint32_t p = (v * (255u - s) + 127u) / 255u;
+  const uint32_t q = (v * (7650u - s * f) + 3825u) / 7650u;
+  const uint32_t t = (v * (7650u - s * (30u - f)) + 3825u) / 7650u;
+  r = sec == 0 || sec == 5 ? v : sec == 1 ? q : sec == 4 ? t : p;
+  g = sec == 1 || sec == 2 ? v : sec == 0 ? t : sec == 3 ? q : p;
+  b = sec == 3 || sec == 4 ? v : sec == 2 ? t : sec == 5 ? q : p;
+}
+
+// the read side of a view, scene_stitch_views' staging loop as a function: va rows of ne floats, row rr the run that starts at pixel
+// vbase + (a0 + rr) * PW + b0 of p, into LDS rows of maxp 16-byte pieces at the run's own dword phase
+__device__ __forceinline__ void sm_stage(uint4* Vq, const float* p, long long total, long long vbase, int a0, int b0, int va, int ne,
+                                         int PW, int C, int maxp, int tid) {
+  float* S = reinterpret_cast<float*>(Vq);
+  const int pitch = maxp * 4;
+  for (int e = tid; e < va * maxp; e += 256) {
+    const int rr = e / maxp, q = e - rr * maxp;
+    const long long e0 = (vbase + (long long)(a0 + rr) * PW + b0) * C, al = e0 & ~3LL;   // the run is floats [e0, e0 + ne) of p
+    const long long lo = al + 4 * q;
+    if (lo >= e0 + ne) continue;
+    if (lo + 4 <= total) Vq[rr * maxp + q] = ldg16(p + lo);
+    else for (long long x = lo; x < total; ++x) S[rr * pitch + (int)(x - al)] = p[x];
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void scene_stitch_maps(MapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint4 Mq[];      // T * maxp pieces of staging; the byte image of the tile lies over it at the end
+  const float* S = reinterpret_cast<const float*>(Mq);
+  const int tid = threadIdx.x, Ch = a.Ch, PH = a.PH, PW = a.PW, T = a.T, maxp = a.maxp, pitch = maxp * 4;
+  const MapGroup& w = a.g[blockIdx.y];
+  const int tiles_x = (PW + T - 1) / T;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int i0 = w.r0 + ty * T, j0 = w.c0 + tx * T;
+  if (i0 >= w.r1 || j0 >= w.c1) return;        // the whole block: nothing of the rectangle lies here (an empty rectangle: every block)
+  const int th = min(T, w.r1 - i0), tw = min(T, w.c1 - j0);
+  // this thread's items: mode 0 element e = (ti * tw + tj) * Ch + c of the tile, mode 1 pixel e = ti * tw + tj, for e = tid + 256 m
+  constexpr int NS = MODE ? SM_PIX : SV_SLOTS, NA = MODE ? 3 : 1;
+  const int items = MODE ? th * tw : th * tw * Ch;
+  int pk[NS];
+  uint32_t acc[NS][NA];
+#pragma unroll
+  for (int m = 0; m < NS; ++m) {
+    const int e = tid + 256 * m;
+    pk[m] = 0;
+#pragma unroll
+    for (int n = 0; n < NA; ++n) acc[m][n] = 0u;
+    if (e < items) {
+      const int px = MODE ? e : e / Ch, c = MODE ? 0 : e - px * Ch, ti = px / tw, tj = px - ti * tw;
+      pk[m] = (ti << 16) | (tj << 8) | c;
+    }
+  }
+  const long long group = a.first + (long long)blockIdx.y;
+  for (int k = 0; k < a.K; ++k) {
+    const int code = (int)(w.codes >> (3 * k)) & 7;
+    const bool tr = code == 1 || code == 5 || code == 6 || code == 7;
+    const bool fr = code == 2 || code == 3 || code == 5 || code == 7;
+    const bool fc = code == 1 || code == 2 || code == 4 || code == 7;
+    // the tile in the view, as scene_stitch_views finds it: va rows of vb pixels at (a0, b0)
+    const int x0 = fr ? PH - i0 - th : i0, y0 = fc ? PW - j0 - tw : j0;
+    const int a0 = tr ? y0 : x0, b0 = tr ? x0 : y0, va = tr ? tw : th, vb = tr ? th : tw;
+    const long long vbase = (group * a.K + k) * PH * PW;
+    __syncthreads();                           // the last view's reads of S are done
+    sm_stage(Mq, a.p, a.total, vbase, a0, b0, va, vb * Ch, PW, Ch, maxp, tid);
+    __syncthreads();
+    const unsigned pb = (unsigned)vbase + (unsigned)(a0 * PW + b0);
+#pragma unroll
+    for (int m = 0; m < NS; ++m) {
+      if (tid + 256 * m < items) {
+        const int ti = pk[m] >> 16, tj = (pk[m] >> 8) & 255, c = pk[m] & 255;
+        const int xl = fr ? th - 1 - ti : ti, yl = fc ? tw - 1 - tj : tj;
+        const int ra = tr ? yl : xl, cb = tr ? xl : yl;
+        const int phase = (int)(((pb + (unsigned)(ra * PW)) * (unsigned)Ch) & 3u);
+        const float* v = S + ra * pitch + phase + cb * Ch + c;
+        if (MODE == 0) {
+          acc[m][0] += sm_q16(v[0]);           // at most 8 * 65536
+        } else {
+          uint32_t r, g, b;                    // truncation, as the reference's astype(uint8)
+          sm_hsv_rgb((179u * sm_q16(v[0])) >> 16, (255u * sm_q16(v[1])) >> 16, (255u * sm_q16(v[2])) >> 16, r, g, b);
+          acc[m][0] += r; acc[m][1] += g; acc[m][2] += b;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // the tile's bytes: row ti at the byte phase of its scene row, pitch a whole number of dwords
+  uint8_t* B = reinterpret_cast<uint8_t*>(Mq);
+  const int nb = tw * Ch, nd = (nb + 6) / 4, bp = nd * 4;
+  const unsigned K = (unsigned)a.K;
+  const unsigned o0 = (unsigned)(uintptr_t)w.out + ((unsigned)i0 * (unsigned)w.W + (unsigned)j0) * (unsigned)Ch;   // low address bits of tile row 0
+  const unsigned ostep = (unsigned)w.W * (unsigned)Ch;
+#pragma unroll
+  for (int m = 0; m < NS; ++m) {
+    if (tid + 256 * m < items) {
+      const int ti = pk[m] >> 16, tj = (pk[m] >> 8) & 255, c = pk[m] & 255;
+      uint8_t* d = B + ti * bp + (int)((o0 + (unsigned)ti * ostep) & 3u) + tj * Ch + c;
+      if (MODE == 0) {
+        d[0] = (uint8_t)((255u * acc[m][0] + K * 32768u) / (K * 65536u));   // below 2^27 + 2^18
+      } else {
+#pragma unroll
+        for (int n = 0; n < 3; ++n) d[n] = (uint8_t)((2u * acc[m][n] + K) / (2u * K));
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t* Bd = reinterpret_cast<const uint32_t*>(Mq);
+  for (int e = tid; e < th * nd; e += 256) {
+    const int ti = e / nd, q = e - ti * nd;
+    uint8_t* row = w.out + ((size_t)(i0 + ti) * w.W + j0) * Ch;
+    const int s = (int)((uintptr_t)row & 3);
+    const int lo = max(4 * q, s), hi = min(4 * q + 4, s + nb);
+    uint8_t* al = row - s;                     // the row's bytes go to al + [s, s + nb)
+    if (hi - lo == 4) *reinterpret_cast<uint32_t*>(al + 4 * q) = Bd[ti * nd + q];
+    else for (int x = lo; x < hi; ++x) al[x] = B[ti * bp + x];
+  }
+}
+
+}  // namespace
+
+extern "C" int rua_scene_stitch_maps(const float* p, int G, int K, int PH, int PW, int Ch, const int32_t* windows, const int32_t* own,
+                                     uint8_t* const* scene_out, const int32_t* scene_h, const int32_t* scene_w, int nscenes, int mode,
+                                     void* stream) {
+  RUA_CHECK_ARG(p && windows && own && scene_out && scene_h && scene_w,
+                "rua_scene_stitch_maps: p, windows, own, scene_out, scene_h and scene_w are required");
+  RUA_CHECK_ARG(nscenes >= 1 && G >= 1, "rua_scene_stitch_maps: nscenes %d, G %d (both >= 1)", nscenes, G);
+  RUA_CHECK_ARG(K >= 1 && K <= SV_MAXK, "rua_scene_stitch_maps: K %d outside 1..8", K);
+  RUA_CHECK_ARG(Ch >= 1 && Ch <= SS_MAXC, "rua_scene_stitch_maps: Ch %d outside 1..64", Ch);
+  RUA_CHECK_ARG(mode == 0 || mode == 1, "rua_scene_stitch_maps: mode %d (0 plain, 1 hsv_rgb)", mode);
+  RUA_CHECK_ARG(mode == 0 || Ch == 3, "rua_scene_stitch_maps: mode 1 (hsv_rgb) reads H, S, V: Ch 3, got %d", Ch);
+  RUA_CHECK_ARG(PH >= 1 && PW >= 1 && PH <= SW_MAXP && PW <= SW_MAXP, "rua_scene_stitch_maps: PH %d, PW %d (1 <= PH, PW <= 512)", PH, PW);
+  RUA_CHECK_ARG(((uintptr_t)p & 15) == 0, "rua_scene_stitch_maps: p must be 16-byte aligned");
+  for (int s = 0; s < nscenes; ++s) {
+    RUA_CHECK_ARG(scene_out[s], "rua_scene_stitch_maps: scene %d: null pointer", s);
+    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] * Ch < ((int64_t)1 << 40),
+                  "rua_scene_stitch_maps: scene %d: size %d x %d x %d", s, scene_h[s], scene_w[s], Ch);
+  }
+  for (int g = 0; g < G; ++g) {
+    const int32_t* t0 = windows + 4 * (size_t)g * K;
+    const int32_t* o = own + 4 * (size_t)g;
+    for (int v = 0; v < K; ++v) {
+      const int32_t* t = t0 + 4 * v;
+      const int k = g * K + v, s = t[0], r = t[1], c = t[2], code = t[3];
+      RUA_CHECK_ARG(s >= 0 && s < nscenes, "rua_scene_stitch_maps: row %d: scene %d outside 0..%d", k, s, nscenes - 1);
+      RUA_CHECK_ARG(r >= 0 && c >= 0 && (int64_t)r + PH <= scene_h[s] && (int64_t)c + PW <= scene_w[s],
+                    "rua_scene_stitch_maps: row %d: window (%d, %d) + %d x %d leaves its %d x %d scene", k, r, c, PH, PW, scene_h[s], scene_w[s]);
+      RUA_CHECK_ARG(s == t0[0] && r == t0[1] && c == t0[2],
+                    "rua_scene_stitch_maps: row %d: scene %d, window (%d, %d), but its group %d is scene %d, window (%d, %d)",
+                    k, s, r, c, g, t0[0], t0[1], t0[2]);
+      RUA_CHECK_ARG(code >= 0 && code <= 7, "rua_scene_stitch_maps: row %d: code %d outside 0..7", k, code);
+      RUA_CHECK_ARG(PH == PW || !(code == 1 || code >= 5),
+                    "rua_scene_stitch_maps: row %d: code %d transposes and needs a square patch (got %d x %d)", k, code, PH, PW);
+    }
+    RUA_CHECK_ARG(0 <= o[0] && o[0] <= o[1] && o[1] <= PH && 0 <= o[2] && o[2] <= o[3] && o[3] <= PW,
+                  "rua_scene_stitch_maps: group %d: owned rows %d..%d, columns %d..%d outside the %d x %d window", g, o[0], o[1], o[2], o[3], PH, PW);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  MapArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p = p;
+  a.total = (long long)G * K * PH * PW * Ch;
+  a.PH = PH; a.PW = PW; a.Ch = Ch; a.K = K;
+  a.T = 32;
+  while (a.T * a.T * Ch > SV_ACCF) a.T -= 4;                   // as rua_scene_stitch_views; Ch = 3 (mode 1): 32
+  a.maxp = ((a.T * Ch + 6) / 4) | 1;
+  const int blocks = ((PH + a.T - 1) / a.T) * ((PW + a.T - 1) / a.T);
+  const size_t lds = (size_t)a.T * a.maxp * 16;                // 17 KiB at most (Ch = 4: 32 x 33 pieces); the byte image, T rows of at most T * Ch + 6 bytes, fits in it
+  for (int g0 = 0; g0 < G; g0 += SM_CHUNK) {
+    const int ng = G - g0 < SM_CHUNK ? G - g0 : SM_CHUNK;
+    for (int g = 0; g < ng; ++g) {
+      const int32_t* t = windows + 4 * (size_t)(g0 + g) * K;
+      const int32_t* o = own + 4 * (size_t)(g0 + g);
+      const int s = t[0];
+      MapGroup& w = a.g[g];
+      w.out = scene_out[s] + ((size_t)t[1] * scene_w[s] + t[2]) * Ch;
+      w.W = scene_w[s];
+      w.r0 = (uint16_t)o[0]; w.r1 = (uint16_t)o[1]; w.c0 = (uint16_t)o[2]; w.c1 = (uint16_t)o[3];
+      w.codes = 0;
+      for (int v = 0; v < K; ++v) w.codes |= (uint32_t)t[4 * v + 3] << (3 * v);
+    }
+    a.first = g0;
+    if (mode) hipLaunchKernelGGL(scene_stitch_maps<1>, dim3(blocks, ng), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL(scene_stitch_maps<0>, dim3(blocks, ng), dim3(256), lds, st, a);
+    RUA_LAUNCH_CHECK("rua_scene_stitch_maps");
+  }
+  return RUA_OK;
+}
+
 // ---- rua_scene_class_counts: how many pixels of each class lie in each window of a table ------------------------------------------
 // counts[n][c] for c < C is the number of pixels equal to c in window n of the class map, counts[n][C] the number of pixels >= C
 // (scenes.host_class_counts is the definition).  A symmetry code permutes pixels, so it is checked and otherwise ignored.

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .scenes import AffineSceneBatch, SceneBatch, check_radius, check_views, view_rows
+from .scenes import MAP_HEADS, AffineSceneBatch, SceneBatch, check_radius, check_views, view_rows
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -2286,7 +2286,7 @@ class Engine:
             cap.replay()
 
     def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None, views=(0,),
-                      erode: int = 0):
+                      erode: int = 0, heads=(), on_heads=None):
         """The class map of a whole resident scene: (uint8 [H][W] prediction, int64 [C][C] confusion matrix indexed [true][pred], None
         for a pool without class maps).  scenes.predict_table covers the scene with windows `stride` apart (None: the patch) and gives
         every pixel to the window it is most central in; the windows go through the forward `batch` at a time - rua_scene_windows,
@@ -2305,11 +2305,21 @@ class Engine:
         (scenes.host_erode: class-map pixels within that radius of another value become "no class"; the ISPRS benchmark uses 3):
         after the window loop one rua_scene_erode call counts the stitched prediction against the eroded class map into a second
         matrix, on the compute stream, and the return value is (prediction, confusion matrix, confusion matrix on the eroded ground
-        truth).  It scores the stitched map, so it works under any views.  ValueError for a pool without class maps."""
+        truth).  It scores the stitched map, so it works under any views.  ValueError for a pool without class maps.
+        heads: () is the path and the return value above.  Otherwise a tuple out of "seg", "bound", "dist", "color" and "color_rgb":
+        after each forward one rua_scene_stitch_maps call per requested head follows the seg stitch on the compute stream, with the
+        batch's same rows and own (K = 1 for views (0,)), into a uint8 [H][W][Ch] map of the head on the device - the K views turned
+        back, quantised and averaged in integers (scenes.host_stitch_maps is the definition): the seg probabilities, the boundary
+        and distance maps, the colour head's HSV, each times 255 and rounded; "color_rgb" is the colour head turned into an RGB
+        picture (mode "hsv_rgb"), which needs norm_type 1 (under 2 the colour target is not HSV / (179, 255, 255): labels.color_label).
+        The maps come back once, at the end, as a last element of the return tuple: {head: uint8 [H][W][Ch]}.  ValueError for a head
+        the model does not have (single task: only "seg").  on_heads(rows, own, {head: device tensor [batch][H][W][Ch]}): called
+        after the batch's stitches have been issued, with the head outputs the next batch overwrites ("color_rgb" is "color"'s)."""
         H, W, _ = self.cfg.input_shape
         Cn = self.cfg.num_classes
         views = check_views(views, (H, W))
         erode = check_radius(erode)
+        heads = self._check_map_heads(heads, norm_type)
         if erode and pool.cls_ptrs is None:
             raise ValueError(f"predict_scene(erode={erode}) needs the pool's class maps: there is no ground truth to erode")
         if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
@@ -2331,6 +2341,12 @@ class Engine:
         sc = int(scene)
         pred_ptr, cls_ptr = (C.c_void_p * 1)(pred.data_ptr()), (C.c_void_p * 1)(pool.cls_dev[sc].data_ptr()) if counted else None
         sh, sw = (C.c_int32 * 1)(SH), (C.c_int32 * 1)(SW)
+        # one resident map per requested head: (source tensor, channels, mode, map, its one-entry pointer array)
+        head_maps = {}
+        for h in heads:
+            src = g.outputs["color" if h == "color_rgb" else h]["p"]
+            m = torch.zeros((SH, SW, src.C), dtype=torch.uint8, device=self.dev)
+            head_maps[h] = (src, src.C, 1 if h == "color_rgb" else 0, m, (C.c_void_p * 1)(m.data_ptr()))
         nothing = np.zeros((1, 4), np.int32)
         for k0 in range(0, len(rows), G):
             r, o = rows[k0:k0 + G], own[k0:k0 + G]
@@ -2350,13 +2366,39 @@ class Engine:
             else:
                 L.lib().call("rua_scene_stitch", seg.ptr, B, H, W, Cn, r0.ctypes.data, o.ctypes.data, pred_ptr, cls_ptr, sh, sw, 1,
                              conf.data_ptr() if counted else None, C.c_void_p(self._stream()))
+            for src, ch, mode, _, ptr in head_maps.values():
+                L.lib().call("rua_scene_stitch_maps", src.ptr, G, K, H, W, ch, r0.ctypes.data, o.ctypes.data, ptr, sh, sw, 1, mode,
+                             C.c_void_p(self._stream()))
             if on_batch is not None:
                 on_batch(r, o, seg.t)
+            if on_heads is not None:
+                on_heads(r, o, {h: v[0].t for h, v in head_maps.items()})
+        more = ({h: v[3].cpu().numpy() for h, v in head_maps.items()},) if heads else ()
         if erode:
             conf_e = torch.zeros((Cn, Cn), dtype=torch.int64, device=self.dev)
             L.lib().call("rua_scene_erode", cls_ptr, sh, sw, 1, erode, None, pred_ptr, Cn, conf_e.data_ptr(), C.c_void_p(self._stream()))
-            return pred.cpu().numpy(), conf.cpu().numpy(), conf_e.cpu().numpy()
-        return pred.cpu().numpy(), (conf.cpu().numpy() if counted else None)
+            return (pred.cpu().numpy(), conf.cpu().numpy(), conf_e.cpu().numpy()) + more
+        return (pred.cpu().numpy(), (conf.cpu().numpy() if counted else None)) + more
+
+    def _check_map_heads(self, heads, norm_type) -> Tuple[str, ...]:
+        """predict_scene's heads as a tuple of distinct names out of scenes.MAP_HEADS that this model and norm_type can give."""
+        if isinstance(heads, str):
+            heads = (heads,)
+        try:
+            heads = tuple(heads)
+        except TypeError:
+            raise ValueError(f"heads {heads!r}: a tuple out of {MAP_HEADS}") from None
+        have = ("seg", "bound", "dist", "color") if self.cfg.multitasking else ("seg",)
+        for k, h in enumerate(heads):
+            if h not in MAP_HEADS:
+                raise ValueError(f"heads: {h!r} is not one of {MAP_HEADS}")
+            if h in heads[:k]:
+                raise ValueError(f"heads {heads}: {h!r} occurs twice")
+            if ("color" if h == "color_rgb" else h) not in have:
+                raise ValueError(f"heads: this model has no {h!r} head (it has {have})")
+            if h == "color_rgb" and norm_type != 1:
+                raise ValueError(f"heads: 'color_rgb' needs norm_type 1: under norm_type {norm_type!r} the colour head's target is not HSV / (179, 255, 255)")
+        return heads
 
     def logits(self, training: bool, batch: int) -> Dict[str, np.ndarray]:
         g = self.graph(batch, training)

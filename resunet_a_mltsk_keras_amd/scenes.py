@@ -37,6 +37,11 @@ code-0 table K times with the codes of VIEW_SETS (or any distinct codes), the K 
 forward batch, and rua_scene_stitch_views turns them back (INVERSE), sums each pixel's K probability vectors in float32 in view
 order and takes the arg-max of the sum (host_stitch_views is its definition, Engine.predict_scene(views=) its user).
 
+Whole-scene maps of every head use the same tables: rua_scene_stitch_maps takes any head's float32 window outputs under K views,
+turns them back, quantises each value to Q16 (quantise_q16), averages in integers and writes a resident uint8 [H][W][Ch] map - the
+seg probabilities, the boundary and distance maps, the colour head's HSV, or that HSV turned into an RGB picture (hsv_to_rgb_u8,
+averaged over the views in RGB); host_stitch_maps is its definition, Engine.predict_scene(heads=) its user.
+
 Class counts close the loop on the dataset: host_class_counts() says how many pixels of each class (and how many of none, a
 value >= C) lie in each window of a table, rua_scene_class_counts is its kernel on the resident class maps and
 ScenePool.class_counts() its user; class_weights() turns the counts of the training rows into the reference's weighted-CE weights
@@ -490,6 +495,98 @@ def host_stitch_views(p: np.ndarray, rows: np.ndarray, own: np.ndarray, shapes: 
             keep = true < C
             cm += np.bincount(true[keep] * C + pred[keep], minlength=C * C).reshape(C, C)
     return maps, cm
+
+
+# ---- whole-scene maps of any head: the window outputs under K views, turned back, averaged and quantised to uint8 ---------------
+MAP_MODES = {"plain": 0, "hsv_rgb": 1}
+MAP_HEADS = ("seg", "bound", "dist", "color", "color_rgb")     # what predict_scene(heads=) takes; color_rgb is the colour head in mode 1
+
+
+def quantise_q16(x) -> np.ndarray:
+    """float32 of any shape -> int64 a = rint(min(max(x, 0), 1) * 65536), ties to even; NaN and -inf give 0, +inf 65536.  The
+    multiply is by a power of two and exact, so from here on a map is a function of integers (rua_scene_stitch_maps: sm_q16)."""
+    x = np.asarray(x)
+    if x.dtype != np.float32:
+        raise ValueError(f"quantise_q16 is defined on float32, got {x.dtype}")
+    y = np.where(x > 0, x, np.float32(0))                       # NaN > 0 is False
+    y = np.minimum(y, np.float32(1))
+    a = np.rint(y * np.float32(65536))
+    assert a.dtype == np.float32
+    return a.astype(np.int64)
+
+
+def hsv_to_rgb_u8(hsv) -> np.ndarray:
+    """uint8 [..., 3] HSV with H in 0..179 (degrees / 2, as labels.rgb_to_hsv_u8 gives it), S and V in 0..255 -> uint8 [..., 3] RGB:
+    the textbook sector formula rounded exactly, in integers.  sec = h // 30, f = h % 30, p = (v (255 - s) + 127) // 255,
+    q = (v (7650 - s f) + 3825) // 7650, t = (v (7650 - s (30 - f)) + 3825) // 7650 and (r, g, b) = (v,t,p), (q,v,p), (p,v,t),
+    (p,q,v), (t,p,v), (v,p,q) for sec 0..5.  ValueError for an H above 179."""
+    a = np.asarray(hsv)
+    if a.dtype != np.uint8 or a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError(f"hsv_to_rgb_u8 takes uint8 [..., 3], got {a.dtype} {a.shape}")
+    h, s, v = (a[..., k].astype(np.int64) for k in range(3))
+    if h.size and int(h.max()) > 179:
+        raise ValueError(f"hsv_to_rgb_u8: H {int(h.max())} above 179 (H is degrees / 2)")
+    sec, f = h // 30, h % 30
+    p = (v * (255 - s) + 127) // 255
+    q = (v * (7650 - s * f) + 3825) // 7650
+    t = (v * (7650 - s * (30 - f)) + 3825) // 7650
+    r = np.choose(sec, [v, q, p, p, t, v])
+    g = np.choose(sec, [t, v, v, q, p, p])
+    b = np.choose(sec, [p, p, t, v, v, q])
+    return np.stack([r, g, b], axis=-1).astype(np.uint8)
+
+
+def host_stitch_maps(p: np.ndarray, rows: np.ndarray, own: np.ndarray, shapes: Sequence[Sequence[int]], K: int, mode: str = "plain",
+                     maps: Optional[Sequence[np.ndarray]] = None, patch=None) -> List[np.ndarray]:
+    """The numpy definition of what rua_scene_stitch_maps writes.  p: float32 [G*K][PH][PW][Ch], any head's outputs for the K views
+    of G windows (rows [G*K][4], view_rows' layout; own [G][4]; the checks are check_view_table's).  Returns one uint8 [H][W][Ch] map
+    per scene of `shapes`: `maps` (written in place, only inside the owned rectangles) or fresh ones that start at 0.  With q_k view
+    k turned back (INVERSE) and a_k = quantise_q16(q_k[i][j][c]):
+      mode "plain":    A = sum of a_k;  out = (255 A + K 32768) // (K 65536), the rounded mean in 0..255;
+      mode "hsv_rgb":  (Ch = 3) per view h = 179 a_k[0] >> 16, s = 255 a_k[1] >> 16, v = 255 a_k[2] >> 16 (truncation, as the
+                       reference's (hsv * [179, 255, 255]).astype(uint8)), rgb_k = hsv_to_rgb_u8; out = (2 sum of rgb_k + K) // (2 K).
+                       The views are averaged in RGB: hue is circular, and the mean of two reds at 0.005 and 0.995 would be cyan.
+    Integers from the first step on: the order of the views cannot matter.  patch: (PH, PW) to hold p against (None: p's own)."""
+    p = np.asarray(p)
+    if mode not in MAP_MODES:
+        raise ValueError(f"rua_scene_stitch_maps: mode {mode!r} (one of {sorted(MAP_MODES)})")
+    if p.ndim != 4 or p.dtype != np.float32:
+        raise ValueError(f"p is float32 [G*K][PH][PW][Ch], got {p.dtype} {p.shape}")
+    ph, pw = _patch2(p.shape[1:3] if patch is None else patch)
+    if (ph, pw) != tuple(p.shape[1:3]):
+        raise ValueError(f"p holds {p.shape[1]} x {p.shape[2]} windows, the patch is {ph} x {pw}")
+    Ch = int(p.shape[3])
+    if mode == "hsv_rgb" and Ch != 3:
+        raise ValueError(f"rua_scene_stitch_maps: mode 1 (hsv_rgb) reads H, S, V: Ch 3, got {Ch}")
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)):
+        raise ValueError(f"K {K!r} must be an integer")
+    t, o, K = check_view_table(shapes, rows, own, int(K), (ph, pw), Ch)
+    if len(p) != len(t):
+        raise ValueError(f"p is [G*K][PH][PW][Ch] with one view per table row, got {p.shape} for {len(t)} rows")
+    if maps is None:
+        maps = [np.zeros((int(h), int(w), Ch), np.uint8) for h, w in shapes]
+    else:
+        maps = list(maps)
+        for m, (h, w) in zip(maps, shapes):
+            if not isinstance(m, np.ndarray) or m.dtype != np.uint8 or m.shape != (int(h), int(w), Ch):
+                raise ValueError(f"a given map is a uint8 array [{h}][{w}][{Ch}], got {getattr(m, 'dtype', type(m))} {getattr(m, 'shape', '')}")
+        if len(maps) != len(shapes):
+            raise ValueError(f"{len(maps)} maps for {len(shapes)} scenes")
+    for g, (r0, r1, c0, c1) in enumerate(o.tolist()):
+        if r0 == r1 or c0 == c1:
+            continue
+        s, row, col, _ = t[g * K].tolist()
+        acc = np.zeros((r1 - r0, c1 - c0, Ch), np.int64)
+        for k in range(K):
+            a = quantise_q16(transform(p[g * K + k], INVERSE[int(t[g * K + k, 3])])[r0:r1, c0:c1])
+            if mode == "plain":
+                acc += a
+            else:
+                hsv = np.stack([(179 * a[..., 0]) >> 16, (255 * a[..., 1]) >> 16, (255 * a[..., 2]) >> 16], axis=-1)
+                acc += hsv_to_rgb_u8(hsv.astype(np.uint8))
+        out = (255 * acc + K * 32768) // (K * 65536) if mode == "plain" else (2 * acc + K) // (2 * K)
+        maps[s][row + r0:row + r1, col + c0:col + c1] = out
+    return maps
 
 
 # ---- class counts of windows: what class weights and a balance filter are functions of ------------------------------------------
