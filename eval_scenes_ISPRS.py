@@ -1,6 +1,6 @@
 """Evaluation of a trained model on whole scenes, on the GPU: what test_ISPRS.py does for the reference's test tile (patches,
 predict, arg-max, metrics, mosaic), for a scene directory (resunet_a_mltsk_keras_amd.scenes: scenes/<name>.npy,
-labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views, --erode_boundary and --head_maps.
+labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views, --erode_boundary, --boundary_f1 and --head_maps.
 
 Every scene stays on the GPU, is covered by windows --stride apart (default: the patch; the last window flush with the border, so
 nothing is left unpredicted), every pixel is predicted from the window it is most central in, and Model.predict_scene brings back
@@ -16,6 +16,15 @@ the turned-back probabilities (scenes.host_stitch_views).  The output files are 
 (R = 3 there): class-map pixels within a disc of radius R of a pixel of another value are left out (scenes.host_erode), on the GPU,
 against the same stitched map.  After the full block a second one follows, `Eroded ground truth (radius R)` and the same five
 entries; per scene `confusion_matrix_eroded_<name>.npy` is written, and the returned dict gains the `*_eroded` keys.
+
+--boundary_f1 R also scores the class edges themselves, which the area scores above do not and the eroded protocol leaves out: the
+boundary F1 (BF score, Csurka et al. 2013) with a tolerance of R pixels (0..16; 0 is exact coincidence) - per class the share of
+the predicted boundary pixels that have a true one of their class within R pixels (precision), the share of the true ones that
+have a predicted one (recall), and their F1 (scenes.host_boundary_counts, scenes.boundary_scores), counted on the GPU against the
+un-eroded class map.  Per scene `boundary_counts_<name>.npy` (int64 C x 4: n_pred, m_pred, n_true, m_true) is written; after the
+blocks above a block `Boundary F1 (tolerance R px)` follows, scored on the counts summed over the scenes (the published BF score
+averages per image: the per-scene files allow that); the returned dict gains `boundary_counts`, `boundary_precision`,
+`boundary_recall`, `boundary_f1` and `boundary_f1_mean`.
 
 --head_maps HEAD [HEAD ...] also writes whole-scene maps of the named heads (`seg`, `bound`, `dist`, `color`, `color_rgb`; what
 test_ISPRS.py:285-414 displays per patch): `pred_<head>_<name>.npy`, uint8 H x W x Ch - the head's output averaged over the views,
@@ -64,6 +73,8 @@ def build_parser():
                         help="test-time augmentation: none, flips, aug5, all, or symmetry codes 0..7 (e.g. --views 0 3 4)")
     parser.add_argument("--erode_boundary", type=int, default=0, metavar="R",
                         help="also score on the ground truth eroded by a disc of radius R (0..16; the ISPRS benchmark uses 3); 0: off")
+    parser.add_argument("--boundary_f1", type=int, default=None, metavar="R",
+                        help="also print the boundary F1 (BF score) with a tolerance of R pixels (0..16; 0: exact coincidence); default: off")
     parser.add_argument("--head_maps", nargs="+", default=[], metavar="HEAD",
                         help="also write uint8 whole-scene maps of these heads: seg, bound, dist, color, color_rgb (default: none)")
     return parser
@@ -97,6 +108,10 @@ def main(argv=None):
         raise SystemExit("--scene_dataset no: test_ISPRS.py evaluates Image_Test.npy / Reference_Test.npy")
     if args.norm_type not in (1, 2):
         raise SystemExit("scenes are normalised on the GPU: --norm_type 1 or 2")
+    try:
+        boundary = scenes.check_tolerance(args.boundary_f1)
+    except ValueError as exc:
+        raise SystemExit(f"--boundary_f1: {exc}") from None
     heads = tuple(args.head_maps)
     for k, h in enumerate(heads):
         if h not in scenes.MAP_HEADS or h in heads[:k]:
@@ -122,14 +137,19 @@ def main(argv=None):
         lut[str((40 * extra % 256,) * 3)] = extra
     total = np.zeros((args.num_classes, args.num_classes), np.int64)
     total_eroded = np.zeros_like(total)
+    total_boundary = np.zeros((args.num_classes, 4), np.int64)
     all_head_maps, mae_sum, mae_n = [], 0.0, 0
     print('=' * 40)
     print('[TEST]')
     print(f'views: {" ".join(str(c) for c in views)} ({len(views)} per window)')
     for s, name in enumerate(names):
         pred, cm, *more = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type, views=views,
-                                              erode=erode, heads=heads)
+                                              erode=erode, heads=heads, boundary=boundary)
         head_maps = more.pop() if heads else {}
+        if boundary is not None:
+            counts = more.pop()
+            total_boundary += counts
+            np.save(os.path.join(args.output_path, f'boundary_counts_{name}.npy'), counts)
         total += cm
         print(f'scene {name}: {pred.shape[0]} x {pred.shape[1]}, accuracy {metrics_from_confusion(cm)[0]:.4f}')
         np.save(os.path.join(args.output_path, f'pred_seg_reconstructed_{name}.npy'), pred)
@@ -167,6 +187,18 @@ def main(argv=None):
         print('Recall: ', m[2])
         print('Precision: ', m[3])
         res.update(confusion_matrix_eroded=total_eroded, accuracy_eroded=m[0], f1_eroded=m[1], recall_eroded=m[2], precision_eroded=m[3])
+    if boundary is not None:
+        b = scenes.boundary_scores(total_boundary)
+        print()
+        print(f'Boundary F1 (tolerance {boundary} px)')
+        print('Boundary counts (n_pred, m_pred, n_true, m_true) \n', total_boundary)
+        print()
+        print('Precision: ', b["precision"])
+        print('Recall: ', b["recall"])
+        print('F1score: ', b["f1"])
+        print('Mean F1score: ', b["f1_mean"])
+        res.update(boundary_counts=total_boundary, boundary_precision=b["precision"], boundary_recall=b["recall"], boundary_f1=b["f1"],
+                   boundary_f1_mean=b["f1_mean"])
     if heads:
         res["head_maps"] = all_head_maps
         res["color_mae"] = mae_sum / mae_n if mae_n else None

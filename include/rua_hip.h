@@ -582,6 +582,30 @@ int rua_scene_class_counts(const uint8_t* const* scene_cls, const int32_t* scene
 int rua_scene_erode(const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w, int nscenes, int radius,
                     uint8_t* const* scene_out, const uint8_t* const* scene_pred, int C, int64_t* confusion, void* stream);
 
+/* ---- boundary F1 of a prediction map (scenes.py, host_boundaries / host_boundary_counts / boundary_scores; the BF score of Csurka
+ * et al. 2013: per class, precision and recall of boundary pixels matched within a distance tolerance) ---------------------------
+ * scene_cls / scene_pred / scene_h / scene_w are HOST arrays of nscenes entries, as rua_scene_erode reads them: device pointers to
+ * uint8 [scene_h[s]][scene_w[s]] maps, the ground truth and the prediction; both are only read and scene_pred[s] == scene_cls[s] is
+ * allowed.  bound_cls and bound_pred (each nullable on its own) are HOST arrays of nscenes device pointers to maps of the same size.
+ * The boundary image of a map m, for every pixel (i, j):
+ *   bound[i][j] = m[i][j] if m[i][j] < C and one of the four neighbours (i - 1, j), (i + 1, j), (i, j - 1), (i, j + 1) that lie
+ *   inside the map holds a byte other than m[i][j];  otherwise bound[i][j] = 255.
+ * Bytes are compared raw: a "no class" byte (>= C) is never a boundary pixel and makes its class neighbours boundary pixels; pixels
+ * outside the map do not exist, so the scene border is no boundary.  B_c(m), the pixels where bound equals c, is the inner boundary
+ * of class c with 4-connectivity.  bound_cls receives the image of scene_cls, bound_pred that of scene_pred.
+ * counts (nullable; DEVICE memory, int64 [C][4], 8-byte aligned) is ACCUMULATED into, as the confusion matrices are (zero it first):
+ *   counts[c][0] += |B_c(pred)|     counts[c][1] += the x in B_c(pred) with some y in B_c(cls), (x - y) . (x - y) <= radius * radius
+ *   counts[c][2] += |B_c(cls)|      counts[c][3] += the x in B_c(cls)  with some y in B_c(pred) within the same distance
+ * summed over the scenes; radius 0 is exact coincidence.  One pass over each scene does all three.  Integers only, so
+ * scenes.host_boundaries and scenes.host_boundary_counts give the same bytes and counts whatever the launch or arrival order.
+ * Everything is checked on the host before anything is launched (a violation: RUA_ERR_ARG, the message names the offender, nothing is
+ * written): 0 <= radius <= 16, 1 <= C <= 64, nscenes >= 1, at least one of bound_cls, bound_pred and counts, no null entry in a
+ * given pointer array, 1 <= H, W and H * W < 2^40, no output (a boundary map of any scene, the counts) sharing a byte with an
+ * input of any scene of the call or with another output; inputs may share (one map scored against several).  The scenes travel as kernel arguments, 96 per launch (40 bytes each): no device-side table, no copy, no synchronisation. */
+int rua_scene_boundary(const uint8_t* const* scene_cls, const uint8_t* const* scene_pred, const int32_t* scene_h, const int32_t* scene_w,
+                       int nscenes, int radius, int C, uint8_t* const* bound_cls, uint8_t* const* bound_pred, int64_t* counts,
+                       void* stream);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

@@ -15,6 +15,8 @@
 // The host resolves and checks every table row; the kernel receives, per window, the address of its first pixel in either
 // plane, the scene width and the code - as kernel arguments, up to SW_CHUNK windows per launch.
 #include "common.h"
+#include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -1201,6 +1203,265 @@ extern "C" int rua_scene_erode(const uint8_t* const* scene_cls, const int32_t* s
     }
     hipLaunchKernelGGL(scene_erode, dim3(most, ns), dim3(256), scene_pred ? (size_t)C * C * sizeof(uint32_t) : 0, st, a);
     RUA_LAUNCH_CHECK("rua_scene_erode");
+  }
+  return RUA_OK;
+}
+
+// ---- rua_scene_boundary: the boundary pixels of a class map and of a prediction map, and how many of each lie near the other's ---
+// bound[i][j] = m[i][j] if m[i][j] < C and a 4-neighbour inside the map holds another byte, else 255 (scenes.host_boundaries): the
+// inner boundary of every class, B_c(m) the pixels where it equals c.  counts[c] += (|B_c(pred)|, the pixels of B_c(pred) with a
+// pixel of B_c(cls) within `radius`, |B_c(cls)|, the pixels of B_c(cls) with one of B_c(pred) within `radius`): what the boundary
+// F1 is a ratio of (scenes.host_boundary_counts is the definition).
+//
+// A block owns a tile of SB_TH rows x SB_TW columns of one scene and stages both maps with a halo of radius + 1 into LDS, four
+// pixels a dword: an unaligned global dword where the four columns lie inside the row, clamped single bytes at the scene's border -
+// a clamped neighbour equals its centre, so "outside the map does not exist" needs no case in pass A.  Pass A turns the staged
+// bytes into the two boundary images over the tile plus a halo of `radius` (a dword at any byte of LDS is se_ld4; "< C" is one add
+// that carries into bit 7); positions outside the map become 255 there, so they match nothing.  Pass B: a lane takes four pixels
+// of a tile row as one dword of either boundary image and, row by row outwards (dy = 0, +-1, ..) through the lattice disc, XORs it
+// with the OTHER image's dword at that offset; a zero byte under a boundary byte is a match (255 never equals a class byte).  A lane
+// leaves the disc as soon as all its boundary pixels are matched - a lane without any never enters it, and a wave of such lanes
+// skips it.  Counts collect in an LDS histogram of 4 C cells (a block holds 4096 pixels: 32 bits are plenty) and leave with one
+// 64-bit atomicAdd per non-zero cell.  Lanes run along a scene row: the boundary maps leave as contiguous dwords (single bytes in
+// the ragged last group of a row).
+namespace {
+
+// tests/test_scene_boundary_gpu.py places its class edges, halo matches and scene counts by TILE_H, TILE_W and CHUNK, copies of
+// SB_TH, SB_TW and SB_CHUNK: change them together, or those tests stop probing the real tile borders without failing.
+constexpr int SB_TH = 32, SB_TW = 128;         // tile: rows x columns
+constexpr int SB_MAXR = 16;
+constexpr int SB_MAXC = 64;
+constexpr int SB_CHUNK = 96;                   // scenes per launch: 40 bytes each
+
+struct BoundScene { const uint8_t* cls; const uint8_t* pred; uint8_t* bcls; uint8_t* bpred; int H, W; };
+struct BoundArgs {
+  BoundScene s[SB_CHUNK];
+  unsigned long long* counts;
+  int radius, C;
+};
+static_assert(sizeof(BoundScene) == 40 && sizeof(BoundArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+// LDS row pitch in dwords: the tile's columns plus the halo of radius + 1 on either side, and one dword that se_ld4 may read past a row
+__host__ __device__ constexpr int sb_pitch(int r) { return (SB_TW + 2 * (r + 1) + 3) / 4 + 1; }
+// dwords of one staged image (one of slack), and of everything: two raw images, two boundary images, the histogram, the disc's half widths
+__host__ __device__ constexpr int sb_image(int r) { return (SB_TH + 2 * (r + 1)) * sb_pitch(r) + 1; }
+__host__ __device__ constexpr int sb_lds_dwords(int r) { return 4 * sb_image(r) + 4 * SB_MAXC + SB_MAXR + 1; }
+static_assert(sb_lds_dwords(SB_MAXR) * 4 <= 65536, "the staged images must fit the LDS a block may have");
+
+// bit 7 of every byte of x that is below c (1 <= c <= 64)
+__device__ __forceinline__ uint32_t sb_lt(uint32_t x, int c) { return ~(((x & 0x7F7F7F7Fu) + (uint32_t)(128 - c) * 0x01010101u) | x) & 0x80808080u; }
+
+__global__ __launch_bounds__(256) void scene_boundary(BoundArgs a) {
+  extern __shared__ uint32_t bsh[];
+  const BoundScene& sc = a.s[blockIdx.y];
+  const int tid = threadIdx.x, r = a.radius, R1 = r + 1, C = a.C, H = sc.H, W = sc.W;
+  const int tiles_x = (W - 1) / SB_TW + 1;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  if (ty > (H - 1) / SB_TH) return;              // the whole block: a smaller scene of the chunk
+  const int i0 = ty * SB_TH, j0 = tx * SB_TW;
+  const int th = min(SB_TH, H - i0), tw = min(SB_TW, W - j0), ng = (tw + 3) >> 2;     // ng: groups of four pixels in a tile row
+  const int PD = sb_pitch(r), IMG = sb_image(r);
+  const int nrows = th + 2 * R1, ncd = (tw + 2 * R1 + 3) >> 2;                        // staged rows, staged dwords of a row (< PD)
+  uint32_t* raw[2] = {bsh, bsh + IMG};           // 0: the class map, 1: the prediction; staged (y, x) is scene (i0 - R1 + y, j0 - R1 + x)
+  uint32_t* bnd[2] = {bsh + 2 * IMG, bsh + 3 * IMG};
+  uint32_t* hist = bsh + 4 * IMG;
+  uint32_t* lim = hist + 4 * SB_MAXC;            // lim[d] = isqrt(r^2 - d^2): the disc's half width d rows from its centre
+  const bool count = a.counts != nullptr;
+  const uint8_t* src[2] = {sc.cls, sc.pred};
+  uint8_t* dst[2] = {sc.bcls, sc.bpred};
+  const bool need[2] = {count || sc.bcls != nullptr, count || sc.bpred != nullptr};
+  if (count) {
+    for (int e = tid; e < 4 * C; e += 256) hist[e] = 0u;
+    if (tid <= r) {
+      int l = 0;
+      while ((l + 1) * (l + 1) <= r * r - tid * tid) ++l;
+      lim[tid] = (uint32_t)l;
+    }
+  }
+#pragma unroll 1
+  for (int e = tid; e < nrows * ncd; e += 256) {
+    const int y = e / ncd, xd = e - y * ncd;
+    const int i = min(max(i0 - R1 + y, 0), H - 1), jr = 4 * xd - R1;                  // jr: the dword's first column, from j0
+    const bool whole = jr >= -j0 && jr + 3 < W - j0;                                  // its four columns exist
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      if (!need[m]) continue;
+      const uint8_t* row = src[m] + (size_t)i * W + j0;
+      uint32_t v;
+      if (whole) v = *reinterpret_cast<const se_u32u*>(row + jr);
+      else {
+        v = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) v |= (uint32_t)row[min(max(jr + b, -j0), W - 1 - j0)] << (8 * b);
+      }
+      raw[m][y * PD + xd] = v;
+    }
+  }
+  __syncthreads();
+  // Pass A.  The left neighbours of a row's first dword (xd = 0) and the right ones of its last (xd = ncd - 1) come from LDS that
+  // nobody staged (the dword before the row, dword ncd <= PD - 1 of it): in bounds, but garbage.  It reaches only the boundary
+  // image's byte at staged column 0, R1 left of the tile, and bytes from staged column 4 ncd - 1 >= tw + 2 R1 - 1 on, R1 or more
+  // right of it.  Pass B reads columns within r = R1 - 1 of the tile's pixels; the bytes a ragged last group reads beyond that sit
+  // under lanes masked to 255, which count nothing.
+#pragma unroll 1
+  for (int e = tid; e < (nrows - 2) * ncd; e += 256) {
+    const int y = 1 + e / ncd, xd = e - (y - 1) * ncd, idx = y * PD + xd;
+    const int ir = y - R1, jr = 4 * xd - R1;
+    uint32_t exist = 0u;                         // bit 7 of a byte: that position lies inside the map
+    if (ir >= -i0 && ir < H - i0) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (jr + b >= -j0 && jr + b < W - j0) exist |= 0x80u << (8 * b);
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      if (!need[m]) continue;
+      const uint32_t* T = raw[m];
+      const uint32_t v = T[idx];
+      const uint32_t d = (T[idx - PD] ^ v) | (T[idx + PD] ^ v) | (se_ld4(T, 4 * idx - 1) ^ v) | (se_ld4(T, 4 * idx + 1) ^ v);
+      bnd[m][idx] = v | se_bytes(~(se_nz(d) & sb_lt(v, C) & exist) & 0x80808080u);
+    }
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int e = tid; e < th * ng; e += 256) {
+    const int ti = e / ng, k = e - ti * ng;
+    const int at0 = 4 * (R1 + ti) * PD + R1 + 4 * k;                                  // LDS byte of the group's first pixel
+    const int np = min(4, tw - 4 * k);           // pixels of this group inside the tile
+    const size_t at = (size_t)(i0 + ti) * W + j0 + 4 * k;
+    uint32_t own[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      if (!need[m]) continue;
+      own[m] = se_ld4(bnd[m], at0);
+      if (np < 4) own[m] |= 0xFFFFFFFFu << (8 * np);                                  // a ragged group ends at the scene's border: 255 beyond it
+      if (dst[m]) {
+        if (np == 4) *reinterpret_cast<se_u32u*>(dst[m] + at) = own[m];
+        else for (int b = 0; b < np; ++b) dst[m][at + b] = (uint8_t)(own[m] >> (8 * b));
+      }
+    }
+    if (!count) continue;
+    const uint32_t isb0 = ~own[0] & 0x80808080u, isb1 = ~own[1] & 0x80808080u;       // bit 7 of a byte: a boundary pixel (a class byte is < 64)
+    uint32_t pend0 = isb0, pend1 = isb1;         // ... that has found no match yet
+    for (int d = 0; d <= r && (pend0 | pend1); ++d) {
+      const int l = (int)lim[d];
+      for (int sgn = 0; sgn < (d ? 2 : 1); ++sgn) {
+        const int base = at0 + (sgn ? -d : d) * 4 * PD;
+        for (int dx = -l; dx <= l; ++dx) {
+          pend0 &= se_nz(own[0] ^ se_ld4(bnd[1], base + dx));
+          pend1 &= se_nz(own[1] ^ se_ld4(bnd[0], base + dx));
+        }
+      }
+    }
+    const uint32_t hit0 = isb0 & ~pend0, hit1 = isb1 & ~pend1;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const uint32_t bit = 0x80u << (8 * b);
+      if (isb1 & bit) {                          // columns of counts: n_pred, m_pred, n_true, m_true
+        const int c = (own[1] >> (8 * b)) & 255;
+        atomicAdd(&hist[4 * c], 1u);
+        if (hit1 & bit) atomicAdd(&hist[4 * c + 1], 1u);
+      }
+      if (isb0 & bit) {
+        const int c = (own[0] >> (8 * b)) & 255;
+        atomicAdd(&hist[4 * c + 2], 1u);
+        if (hit0 & bit) atomicAdd(&hist[4 * c + 3], 1u);
+      }
+    }
+  }
+  if (!count) return;
+  __syncthreads();
+  for (int e = tid; e < 4 * C; e += 256) {
+    const uint32_t n = hist[e];
+    if (n) atomicAdd(a.counts + e, (unsigned long long)n);
+  }
+}
+
+// do the n bytes at p and the n bytes at q share one?
+inline bool sb_overlap(const uint8_t* p, const uint8_t* q, int64_t n) {
+  return p && q && (uintptr_t)p < (uintptr_t)q + (uint64_t)n && (uintptr_t)q < (uintptr_t)p + (uint64_t)n;
+}
+
+// a byte range that a call reads or writes: kind 0 scene_cls, 1 scene_pred, 2 bound_cls, 3 bound_pred (of scene `scene`), 4 counts
+struct SbRange { uintptr_t at; uint64_t n; int scene, kind; };
+inline void sb_name(char* to, size_t len, const SbRange& x) {
+  static const char* const names[] = {"scene_cls", "scene_pred", "bound_cls", "bound_pred"};
+  if (x.kind == 4) snprintf(to, len, "counts");
+  else snprintf(to, len, "scene %d: %s", x.scene, names[x.kind]);
+}
+
+}  // namespace
+
+extern "C" int rua_scene_boundary(const uint8_t* const* scene_cls, const uint8_t* const* scene_pred, const int32_t* scene_h,
+                                  const int32_t* scene_w, int nscenes, int radius, int C, uint8_t* const* bound_cls,
+                                  uint8_t* const* bound_pred, int64_t* counts, void* stream) {
+  RUA_CHECK_ARG(scene_cls && scene_pred && scene_h && scene_w, "rua_scene_boundary: scene_cls, scene_pred, scene_h and scene_w are required");
+  RUA_CHECK_ARG(radius >= 0 && radius <= SB_MAXR, "rua_scene_boundary: radius %d outside 0..16", radius);
+  RUA_CHECK_ARG(C >= 1 && C <= SB_MAXC, "rua_scene_boundary: C %d outside 1..64", C);
+  RUA_CHECK_ARG(nscenes >= 1, "rua_scene_boundary: nscenes %d (>= 1)", nscenes);
+  RUA_CHECK_ARG(bound_cls || bound_pred || counts, "rua_scene_boundary: nothing to do: give bound_cls, bound_pred or counts");
+  RUA_CHECK_ARG(((uintptr_t)counts & 7) == 0, "rua_scene_boundary: counts must be 8-byte aligned");
+  for (int s = 0; s < nscenes; ++s) {
+    RUA_CHECK_ARG(scene_cls[s] && scene_pred[s] && (!bound_cls || bound_cls[s]) && (!bound_pred || bound_pred[s]),
+                  "rua_scene_boundary: scene %d: null pointer", s);
+    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] < ((int64_t)1 << 40),
+                  "rua_scene_boundary: scene %d: size %d x %d", s, scene_h[s], scene_w[s]);
+    const int64_t n = (int64_t)scene_h[s] * scene_w[s];
+    uint8_t* const bc = bound_cls ? bound_cls[s] : nullptr;
+    uint8_t* const bp = bound_pred ? bound_pred[s] : nullptr;
+    RUA_CHECK_ARG(!sb_overlap(bc, scene_cls[s], n) && !sb_overlap(bc, scene_pred[s], n), "rua_scene_boundary: scene %d: bound_cls overlaps an input map (the neighbours are read while it is written)", s);
+    RUA_CHECK_ARG(!sb_overlap(bp, scene_cls[s], n) && !sb_overlap(bp, scene_pred[s], n), "rua_scene_boundary: scene %d: bound_pred overlaps an input map (the neighbours are read while it is written)", s);
+    RUA_CHECK_ARG(!sb_overlap(bc, bp, n), "rua_scene_boundary: scene %d: bound_cls overlaps bound_pred", s);
+  }
+  // ... and across the scenes of the call: no output (a boundary map, the counts) may share a byte with any input or with another
+  // output; inputs may share (one map scored against several).  One sweep over the ranges in address order: a range that starts
+  // before the furthest end so far of the other kind - or, for an output, of any kind - overlaps the range that set that end.
+  {
+    std::vector<SbRange> v;
+    v.reserve((size_t)nscenes * 4 + 1);
+    for (int s = 0; s < nscenes; ++s) {
+      const uint64_t n = (uint64_t)scene_h[s] * (uint64_t)scene_w[s];
+      v.push_back({(uintptr_t)scene_cls[s], n, s, 0});
+      if (scene_pred[s] != scene_cls[s]) v.push_back({(uintptr_t)scene_pred[s], n, s, 1});
+      if (bound_cls) v.push_back({(uintptr_t)bound_cls[s], n, s, 2});
+      if (bound_pred) v.push_back({(uintptr_t)bound_pred[s], n, s, 3});
+    }
+    if (counts) v.push_back({(uintptr_t)counts, (uint64_t)C * 4 * sizeof(int64_t), -1, 4});
+    std::sort(v.begin(), v.end(), [](const SbRange& x, const SbRange& y) { return x.at < y.at; });
+    const SbRange* far[2] = {nullptr, nullptr};    // the range that ends furthest so far: [0] among the inputs, [1] among the outputs
+    for (const SbRange& x : v) {
+      const int out = x.kind >= 2;
+      for (int k = out ? 0 : 1; k < 2; ++k) {
+        const SbRange* f = far[k];
+        if (!f || x.at >= f->at + f->n) continue;
+        char xs[48], fs[48];
+        sb_name(xs, sizeof(xs), x);
+        sb_name(fs, sizeof(fs), *f);
+        RUA_CHECK_ARG(false, "rua_scene_boundary: %s overlaps %s (an output may share no byte with an input or another output of the call)", xs, fs);
+      }
+      if (!far[out] || x.at + x.n > far[out]->at + far[out]->n) far[out] = &x;
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  BoundArgs a;
+  memset(&a, 0, sizeof(a));
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.radius = radius; a.C = C;
+  for (int s0 = 0; s0 < nscenes; s0 += SB_CHUNK) {
+    const int ns = nscenes - s0 < SB_CHUNK ? nscenes - s0 : SB_CHUNK;
+    int most = 0;
+    for (int k = 0; k < ns; ++k) {
+      const int s = s0 + k;
+      BoundScene& e = a.s[k];
+      e.cls = scene_cls[s]; e.pred = scene_pred[s];
+      e.bcls = bound_cls ? bound_cls[s] : nullptr;
+      e.bpred = bound_pred ? bound_pred[s] : nullptr;
+      e.H = scene_h[s]; e.W = scene_w[s];
+      const int tiles = ((e.H - 1) / SB_TH + 1) * ((e.W - 1) / SB_TW + 1);           // below 2^29: H * W < 2^40 and a tile holds 2^12 pixels
+      if (tiles > most) most = tiles;
+    }
+    hipLaunchKernelGGL(scene_boundary, dim3(most, ns), dim3(256), (size_t)sb_lds_dwords(radius) * sizeof(uint32_t), st, a);
+    RUA_LAUNCH_CHECK("rua_scene_boundary");
   }
   return RUA_OK;
 }

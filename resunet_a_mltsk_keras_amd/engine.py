@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .scenes import MAP_HEADS, AffineSceneBatch, SceneBatch, check_radius, check_views, view_rows
+from .scenes import MAP_HEADS, AffineSceneBatch, SceneBatch, check_radius, check_tolerance, check_views, view_rows
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -2286,7 +2286,7 @@ class Engine:
             cap.replay()
 
     def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None, views=(0,),
-                      erode: int = 0, heads=(), on_heads=None):
+                      erode: int = 0, heads=(), on_heads=None, boundary: Optional[int] = None):
         """The class map of a whole resident scene: (uint8 [H][W] prediction, int64 [C][C] confusion matrix indexed [true][pred], None
         for a pool without class maps).  scenes.predict_table covers the scene with windows `stride` apart (None: the patch) and gives
         every pixel to the window it is most central in; the windows go through the forward `batch` at a time - rua_scene_windows,
@@ -2314,14 +2314,24 @@ class Engine:
         picture (mode "hsv_rgb"), which needs norm_type 1 (under 2 the colour target is not HSV / (179, 255, 255): labels.color_label).
         The maps come back once, at the end, as a last element of the return tuple: {head: uint8 [H][W][Ch]}.  ValueError for a head
         the model does not have (single task: only "seg").  on_heads(rows, own, {head: device tensor [batch][H][W][Ch]}): called
-        after the batch's stitches have been issued, with the head outputs the next batch overwrites ("color_rgb" is "color"'s)."""
+        after the batch's stitches have been issued, with the head outputs the next batch overwrites ("color_rgb" is "color"'s).
+        boundary: None is the path and the return value above, call for call.  A tolerance 0..16 (0: exact coincidence) also counts
+        the boundary pixels of the finished map against those of the pool's un-eroded class map (scenes.host_boundary_counts: per
+        class n_pred, m_pred, n_true, m_true - what scenes.boundary_scores turns into the boundary precision, recall and F1): one
+        rua_scene_boundary call after the window loop, on the compute stream, into a zeroed int64 [C][4] buffer that is fetched at
+        the end.  It scores the stitched map, so it works under any views and together with erode and heads; the return value is
+        (prediction, confusion matrix[, matrix on the eroded ground truth][, boundary counts][, head maps]).  ValueError for a pool
+        without class maps."""
         H, W, _ = self.cfg.input_shape
         Cn = self.cfg.num_classes
         views = check_views(views, (H, W))
         erode = check_radius(erode)
         heads = self._check_map_heads(heads, norm_type)
+        boundary = check_tolerance(boundary)
         if erode and pool.cls_ptrs is None:
             raise ValueError(f"predict_scene(erode={erode}) needs the pool's class maps: there is no ground truth to erode")
+        if boundary is not None and pool.cls_ptrs is None:
+            raise ValueError(f"predict_scene(boundary={boundary}) needs the pool's class maps: there are no true boundaries to match")
         if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
             raise ValueError(f"batch {batch!r} must be a positive integer")
         if pool.patch is None or tuple(pool.patch) != (H, W):
@@ -2373,11 +2383,18 @@ class Engine:
                 on_batch(r, o, seg.t)
             if on_heads is not None:
                 on_heads(r, o, {h: v[0].t for h, v in head_maps.items()})
-        more = ({h: v[3].cpu().numpy() for h, v in head_maps.items()},) if heads else ()
+        # what scores the stitched map is issued first, kernel after kernel on the compute stream; every fetch comes after
+        if boundary is not None:
+            bcounts = torch.zeros((Cn, 4), dtype=torch.int64, device=self.dev)
+            L.lib().call("rua_scene_boundary", cls_ptr, pred_ptr, sh, sw, 1, boundary, Cn, None, None, bcounts.data_ptr(), C.c_void_p(self._stream()))
         if erode:
             conf_e = torch.zeros((Cn, Cn), dtype=torch.int64, device=self.dev)
             L.lib().call("rua_scene_erode", cls_ptr, sh, sw, 1, erode, None, pred_ptr, Cn, conf_e.data_ptr(), C.c_void_p(self._stream()))
-            return (pred.cpu().numpy(), conf.cpu().numpy(), conf_e.cpu().numpy()) + more
+        more = ({h: v[3].cpu().numpy() for h, v in head_maps.items()},) if heads else ()
+        if boundary is not None:
+            more = (bcounts.cpu().numpy(),) + more
+        if erode:
+            more = (conf_e.cpu().numpy(),) + more
         return (pred.cpu().numpy(), (conf.cpu().numpy() if counted else None)) + more
 
     def _check_map_heads(self, heads, norm_type) -> Tuple[str, ...]:

@@ -355,34 +355,44 @@ class Model:
             return {h: np.concatenate([o[h] for o in outs], axis=0) for h in HEADS}
         return np.concatenate(outs, axis=0)
 
-    def predict_scene(self, pool, scene, stride=None, batch=8, norm_type=1, on_batch=None, views=(0,), erode=0, heads=(), on_heads=None):
+    def predict_scene(self, pool, scene, stride=None, batch=8, norm_type=1, on_batch=None, views=(0,), erode=0, heads=(), on_heads=None,
+                      boundary=None):
         """Engine.predict_scene: (uint8 [H][W] class map of the pool's scene `scene`, int64 [C][C] confusion matrix [true][pred] or None
         without class maps), the windows cut, predicted and stitched on the GPU; only these two arrays come back.  views: test-time
         augmentation, a tuple of symmetry codes or a scenes.VIEW_SETS name ("none", "flips", "aug5", "all").  erode: a radius 1..16
         adds a third value, the confusion matrix on the eroded ground truth (scenes.host_erode; the ISPRS benchmark uses 3).  heads: a
         tuple out of "seg", "bound", "dist", "color", "color_rgb" adds a last value, {head: uint8 [H][W][Ch] map} - the head's output
-        over the whole scene, averaged over the views and quantised on the GPU (scenes.host_stitch_maps); () adds nothing."""
+        over the whole scene, averaged over the views and quantised on the GPU (scenes.host_stitch_maps); () adds nothing.  boundary: a
+        tolerance 0..16 adds, after the matrices and before the head maps, the int64 [C][4] boundary counts of the map against the
+        class map (scenes.host_boundary_counts; scenes.boundary_scores gives the boundary F1); None adds nothing."""
         if self.engine.loss is None:                      # load_model(..., compile=False), as predict
             self.engine.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in HEADS}, weight={h: 1.0 for h in HEADS}))
         return self.engine.predict_scene(pool, scene, stride=stride, batch=batch, norm_type=norm_type, on_batch=on_batch, views=views, erode=erode,
-                                         heads=heads, on_heads=on_heads)
+                                         heads=heads, on_heads=on_heads, boundary=boundary)
 
-    def evaluate_scenes(self, pool, stride=None, batch_size=8, norm_type=1, views=(0,), erode=0, heads=()):
+    def evaluate_scenes(self, pool, stride=None, batch_size=8, norm_type=1, views=(0,), erode=0, heads=(), boundary=None):
         """predict_scene of every scene of the pool: (list of uint8 class maps, the confusion matrices summed - None without class maps);
-        with erode >= 1 a third value, the matrices on the eroded ground truth summed; with heads a last value, the list of the
-        scenes' {head: uint8 [H][W][Ch] map} dicts."""
+        with erode >= 1 a third value, the matrices on the eroded ground truth summed; with boundary (a tolerance 0..16) a next
+        value, the int64 [C][4] boundary counts summed over the scenes; with heads a last value, the list of the scenes'
+        {head: uint8 [H][W][Ch] map} dicts."""
         heads = (heads,) if isinstance(heads, str) else tuple(heads)
-        maps, total, total_e, head_maps = [], None, None, []
+        maps, total, total_e, total_b, head_maps = [], None, None, None, []
         for s in range(len(pool)):
-            m, cm, *more = self.predict_scene(pool, s, stride=stride, batch=batch_size, norm_type=norm_type, views=views, erode=erode, heads=heads)
+            m, cm, *more = self.predict_scene(pool, s, stride=stride, batch=batch_size, norm_type=norm_type, views=views, erode=erode, heads=heads,
+                                              boundary=boundary)
             maps.append(m)
             if cm is not None:
                 total = cm if total is None else total + cm
             if heads:
                 head_maps.append(more.pop())
+            if boundary is not None:
+                b = more.pop()
+                total_b = b if total_b is None else total_b + b
             if more:
                 total_e = more[0] if total_e is None else total_e + more[0]
         res = (maps, total, total_e) if erode else (maps, total)
+        if boundary is not None:
+            res += (total_b,)
         return res + (head_maps,) if heads else res
 
     # -- checkpoints (train_ISPRS.py:292,474-480): real HDF5 in the Keras layout, written / read by h5lite (no h5py needed) --

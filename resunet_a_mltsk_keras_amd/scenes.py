@@ -54,6 +54,13 @@ class boundaries; the scene border is no boundary.  rua_scene_erode is its kerne
 map, counts a prediction map against it into a confusion matrix (host_erode_confusion), or both -, ScenePool.eroded_maps() and
 Engine.predict_scene(erode=) are its users.
 
+The boundary F1 (BF score, Csurka et al. 2013) says whether the predicted class edges are where the true ones are, which no area
+score does and the eroded protocol leaves out on purpose: host_boundaries() marks the inner 4-connected boundary pixels of every
+class of a map, host_boundary_counts() counts, per class, the boundary pixels of the prediction that have one of the ground truth
+within `radius` pixels and the other way round, and boundary_scores() turns such counts into precision, recall and F1.
+rua_scene_boundary is the kernel of the first two on resident maps, ScenePool.boundary_counts() / boundary_maps() and
+Engine.predict_scene(boundary=) are its users.  Radius 0 is exact coincidence, a real tolerance: "off" is None (check_tolerance).
+
 `python -m resunet_a_mltsk_keras_amd.scenes --image Image_Train.npy --reference Reference_Train.npy --dst DIR` writes a scene
 directory from the reference's two inputs (C x H x W arrays, the reference colour-coded); `--materialize DST` also writes the
 compact patch layout (compact.py) of its window table, for users who want files.
@@ -698,6 +705,105 @@ def host_erode_confusion(class_map: np.ndarray, pred: np.ndarray, radius: int, n
     return np.bincount(t[keep] * C_ + p[keep].astype(np.int64), minlength=C_ * C_).reshape(C_, C_)
 
 
+# ---- boundary F1: are the predicted class edges where the true ones are ------------------------------------------------------------
+def check_tolerance(radius) -> Optional[int]:
+    """The boundary tolerance as an int, or None for None ("off": 0 is a real tolerance, exact coincidence); ValueError, in
+    rua_scene_boundary's own words, unless it is an integer in 0..16."""
+    if radius is None:
+        return None
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)):
+        raise ValueError(f"rua_scene_boundary: radius {radius!r} is no integer")
+    if not 0 <= int(radius) <= MAX_RADIUS:
+        raise ValueError(f"rua_scene_boundary: radius {int(radius)} outside 0..16")
+    return int(radius)
+
+
+def _check_boundary_classes(num_classes) -> int:
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 1 <= int(num_classes) <= MAX_CLASSES:
+        raise ValueError(f"rua_scene_boundary: C {num_classes} outside 1..64")
+    return int(num_classes)
+
+
+def _check_boundary_map(a, what: str) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.size == 0:
+        raise ValueError(f"rua_scene_boundary: {what} is a non-empty uint8 H x W array, got {a.dtype} {a.shape}")
+    return a
+
+
+def host_boundaries(m: np.ndarray, num_classes: int) -> np.ndarray:
+    """The numpy definition of the boundary image rua_scene_boundary writes, uint8 [H][W]: out[i, j] = m[i, j] if m[i, j] < C and
+    one of the 4-neighbours of (i, j) that lie inside the map holds another byte, otherwise 255.  Bytes are compared raw: a value
+    >= C is never a boundary pixel itself and makes its class neighbours boundary pixels; pixels outside the map do not exist (the
+    scene border is no boundary, as in host_erode).  B_c(m), the pixels where the result equals c, is the inner boundary of class c
+    with 4-connectivity."""
+    m = _check_boundary_map(m, "a map")
+    C_ = _check_boundary_classes(num_classes)
+    edge = np.zeros(m.shape, bool)
+    v, h = m[1:] != m[:-1], m[:, 1:] != m[:, :-1]
+    edge[1:] |= v
+    edge[:-1] |= v
+    edge[:, 1:] |= h
+    edge[:, :-1] |= h
+    return np.where(edge & (m < C_), m, np.uint8(255)).astype(np.uint8)
+
+
+def host_boundary_counts(class_map: np.ndarray, pred: np.ndarray, radius: int, num_classes: int) -> np.ndarray:
+    """The numpy definition of what rua_scene_boundary adds to its counts, int64 [C][4]: row c is (n_pred, m_pred, n_true, m_true)
+    with n_pred = |B_c(pred)| (host_boundaries), m_pred the number of x in B_c(pred) for which some y in B_c(class_map) has
+    (x - y) . (x - y) <= radius^2, and n_true, m_true the same with the two maps exchanged.  radius is an integer 0..16, 0 exact
+    coincidence.  100 m_pred / n_pred is the boundary precision of class c, 100 m_true / n_true its recall (boundary_scores)."""
+    t = _check_boundary_map(class_map, "the class map")
+    p = _check_boundary_map(pred, "the prediction map")
+    r = check_tolerance(radius)
+    if r is None:
+        raise ValueError("rua_scene_boundary: radius None is no integer")
+    C_ = _check_boundary_classes(num_classes)
+    if p.shape != t.shape:
+        raise ValueError(f"rua_scene_boundary: the prediction map is {p.shape}, the class map {t.shape}")
+    H, W = t.shape
+    bt, bp = host_boundaries(t, C_), host_boundaries(p, C_)
+    hit_t, hit_p = np.zeros((H, W), bool), np.zeros((H, W), bool)
+    for dy in range(-min(r, H - 1), min(r, H - 1) + 1):
+        lim = min(int(np.sqrt(r * r - dy * dy) + 1e-9), W - 1)               # isqrt: the argument is an integer below 2^9
+        for dx in range(-lim, lim + 1):
+            i0, i1, j0, j1 = max(0, -dy), min(H, H - dy), max(0, -dx), min(W, W - dx)    # the pixels whose partner exists
+            hit_p[i0:i1, j0:j1] |= bp[i0:i1, j0:j1] == bt[i0 + dy:i1 + dy, j0 + dx:j1 + dx]
+            hit_t[i0:i1, j0:j1] |= bt[i0:i1, j0:j1] == bp[i0 + dy:i1 + dy, j0 + dx:j1 + dx]
+    out = np.empty((C_, 4), np.int64)
+    for col, (b, hit) in enumerate(((bp, hit_p), (bt, hit_t))):                 # 255 == 255 "hits" too: only class bytes are counted
+        out[:, 2 * col] = np.bincount(b[b < C_], minlength=C_)
+        out[:, 2 * col + 1] = np.bincount(b[(b < C_) & hit], minlength=C_)
+    return out
+
+
+def boundary_scores(counts) -> dict:
+    """Boundary precision, recall and F1 in percent (as eval_scenes_ISPRS.metrics_from_confusion gives its scores) from int [C][4]
+    counts of (n_pred, m_pred, n_true, m_true) rows; [n][C][4] counts of several scenes are SUMMED first.  The published BF score
+    averages per image instead; Engine.predict_scene and ScenePool.boundary_counts return the per-scene counts, so a user can do
+    that by scoring each and averaging.  {"precision": float64 [C] = 100 m_pred / n_pred, nan where n_pred == 0; "recall":
+    100 m_true / n_true, nan where n_true == 0; "f1": 2 P R / (P + R) - nan where both n are 0 (the class has no boundary in either
+    map), 0 where exactly one n is 0 and 0 where P + R == 0; "f1_mean": the mean of the f1 that are not nan, nan if there is none}."""
+    a = np.asarray(counts)
+    if a.ndim == 3 and a.shape[0] >= 1:
+        a = a.astype(np.int64).sum(0) if np.issubdtype(a.dtype, np.integer) else a
+    if a.ndim != 2 or a.shape[1] != 4 or a.shape[0] < 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"boundary counts are an integer [C][4] (or [n][C][4]) array of (n_pred, m_pred, n_true, m_true) rows, got {a.dtype} {a.shape}")
+    a = a.astype(np.int64)
+    if (a < 0).any() or (a[:, 1] > a[:, 0]).any() or (a[:, 3] > a[:, 2]).any():
+        raise ValueError("boundary counts: 0 <= m_pred <= n_pred and 0 <= m_true <= n_true in every row")
+    n_p, m_p, n_t, m_t = (a[:, k].astype(np.float64) for k in range(4))
+    nan = np.full(len(a), np.nan)
+    prec = np.divide(100 * m_p, n_p, out=nan.copy(), where=n_p > 0)
+    rec = np.divide(100 * m_t, n_t, out=nan.copy(), where=n_t > 0)
+    f1 = np.zeros(len(a), np.float64)
+    both = (n_p > 0) & (n_t > 0) & (np.nan_to_num(prec) + np.nan_to_num(rec) > 0)
+    f1[both] = 2 * prec[both] * rec[both] / (prec[both] + rec[both])
+    f1[(n_p == 0) & (n_t == 0)] = np.nan
+    have = ~np.isnan(f1)
+    return {"precision": prec, "recall": rec, "f1": f1, "f1_mean": float(f1[have].mean()) if have.any() else float("nan")}
+
+
 def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]]) -> int:
     """Scenes are uint8 H x W x C with one C for all, class maps uint8 H x W of their image's size.  Returns C."""
     if len(images) < 1:
@@ -867,6 +973,74 @@ class ScenePool:
             out = torch.empty((int(first[-1]),), dtype=torch.uint8, device=self.device)
             out_ptrs = (C.c_void_p * len(self))(*[out.data_ptr() + int(o) for o in first[:-1]])
             L.lib().call("rua_scene_erode", self.cls_ptrs, self.heights, self.widths, len(self), r, out_ptrs, None, 0, None,
+                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            got = out.cpu().numpy()
+        return [got[first[s]:first[s + 1]].reshape(self.shapes[s]).copy() for s in range(len(self))]
+
+    def _check_preds(self, preds) -> list:
+        preds = list(preds)
+        if len(preds) != len(self):
+            raise ValueError(f"rua_scene_boundary: {len(preds)} prediction maps for {len(self)} scenes (one per scene, None to skip one)")
+        out = []
+        for s, p in enumerate(preds):
+            if p is not None:
+                p = np.ascontiguousarray(_check_boundary_map(p, f"scene {s}: the prediction map"))
+                if p.shape != self.shapes[s]:
+                    raise ValueError(f"rua_scene_boundary: scene {s}: the prediction map is {p.shape}, the class map {self.shapes[s]}")
+            out.append(p)
+        return out
+
+    def boundary_counts(self, preds, radius: int, num_classes: int) -> np.ndarray:
+        """int64 [n][C][4], host_boundary_counts of every scene's class map and preds[s], a uint8 [H][W] map per scene of the pool
+        (a None entry skips its scene: its rows stay 0) - the boundary F1 of maps that come from files, without a model
+        (boundary_scores of the result, or of one scene's rows).  The maps are uploaded in one copy, rua_scene_boundary is called once per scored
+        scene into that scene's [C][4] cells of one device buffer (the call sums its scenes into one set of counts), and the buffer
+        is fetched once; a "cpu" pool returns the host definition."""
+        if self.class_maps is None:
+            raise ValueError("boundary_counts needs the pool's class maps")
+        r = check_tolerance(radius)
+        if r is None:
+            raise ValueError("rua_scene_boundary: radius None is no integer")
+        C_ = _check_boundary_classes(num_classes)
+        preds = self._check_preds(preds)
+        if self.device.type != "cuda":
+            out = np.zeros((len(self), C_, 4), np.int64)
+            for s, p in enumerate(preds):
+                if p is not None:
+                    out[s] = host_boundary_counts(self.class_maps[s], p, r, C_)
+            return out
+        import torch
+        from . import _lib as L
+        with torch.cuda.device(self.device):
+            counts = torch.zeros((len(self), C_, 4), dtype=torch.int64, device=self.device)
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            scored = [s for s, p in enumerate(preds) if p is not None]
+            if not scored:
+                return counts.cpu().numpy()
+            first = np.concatenate([[0], np.cumsum([preds[s].size for s in scored])]).astype(np.int64)
+            dev = torch.from_numpy(np.concatenate([preds[s].ravel() for s in scored])).to(self.device)      # one upload for all maps
+            for k, s in enumerate(scored):
+                H, W = self.shapes[s]
+                L.lib().call("rua_scene_boundary", (C.c_void_p * 1)(self.cls_dev[s].data_ptr()), (C.c_void_p * 1)(dev.data_ptr() + int(first[k])),
+                             (C.c_int32 * 1)(H), (C.c_int32 * 1)(W), 1, r, C_, None, None, counts[s].data_ptr(), st)
+            return counts.cpu().numpy()
+
+    def boundary_maps(self, num_classes: int) -> List[np.ndarray]:
+        """host_boundaries of every class map of the pool, a list of uint8 [H][W] arrays: one rua_scene_boundary call over all
+        resident class maps into one device buffer, fetched once; a "cpu" pool returns host_boundaries of each map."""
+        if self.class_maps is None:
+            raise ValueError("boundary_maps needs the pool's class maps")
+        C_ = _check_boundary_classes(num_classes)
+        if self.device.type != "cuda":
+            return [host_boundaries(cm, C_) for cm in self.class_maps]
+        import torch
+        from . import _lib as L
+        sizes = [h * w for h, w in self.shapes]
+        first = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        with torch.cuda.device(self.device):
+            out = torch.empty((int(first[-1]),), dtype=torch.uint8, device=self.device)
+            out_ptrs = (C.c_void_p * len(self))(*[out.data_ptr() + int(o) for o in first[:-1]])
+            L.lib().call("rua_scene_boundary", self.cls_ptrs, self.cls_ptrs, self.heights, self.widths, len(self), 0, C_, out_ptrs, None, None,
                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
             got = out.cpu().numpy()
         return [got[first[s]:first[s + 1]].reshape(self.shapes[s]).copy() for s in range(len(self))]
