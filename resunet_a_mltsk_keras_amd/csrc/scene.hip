@@ -34,6 +34,14 @@ struct SceneArgs {
 };
 static_assert(sizeof(SceneArgs) <= 4096, "kernel arguments are limited to 4 KiB");
 
+// a symmetry code as "transpose or not, then flip": the source row (column) runs against its destination index under fr (fc)
+struct Sym {
+  int code;
+  __device__ __forceinline__ bool tr() const { return code == 1 || code == 5 || code == 6 || code == 7; }
+  __device__ __forceinline__ bool fr() const { return code == 2 || code == 3 || code == 5 || code == 7; }
+  __device__ __forceinline__ bool fc() const { return code == 1 || code == 2 || code == 4 || code == 7; }
+};
+
 template <int U> struct StoreUnit;
 template <> struct StoreUnit<16> { static __device__ __forceinline__ void st(uint8_t* p, const uint32_t* v) { stg16(p, make_uint4(v[0], v[1], v[2], v[3])); } };
 template <> struct StoreUnit<4> { static __device__ __forceinline__ void st(uint8_t* p, const uint32_t* v) { *reinterpret_cast<uint32_t*>(p) = v[0]; } };
@@ -74,10 +82,8 @@ __global__ __launch_bounds__(256) void scene_windows(SceneArgs a) {
   const uint8_t* src = plane ? w.cls : w.img;
   uint8_t* out = (plane ? a.cls_out : a.img_out) + (size_t)n * PH * PW * cb;
   const size_t pitch = (size_t)w.W * cb;
-  const int code = w.code;
-  const bool tr = code == 1 || code == 5 || code == 6 || code == 7;
-  const bool fr = code == 2 || code == 3 || code == 5 || code == 7;     // source row runs against its destination index
-  const bool fc = code == 1 || code == 2 || code == 4 || code == 7;     // source column likewise
+  const Sym y{w.code};
+  const bool tr = y.tr(), fr = y.fr(), fc = y.fc();
   // source tile: sh rows x sw pixels at (r0, c0) of the window.  Transposing codes have PH == PW (checked on the host).
   const int a0 = tr ? j0 : i0, an = tr ? tw : th, A = tr ? PW : PH;     // destination index range the source ROW follows
   const int b0 = tr ? i0 : j0, bn = tr ? th : tw, Bn = tr ? PH : PW;    // ... the source COLUMN follows
@@ -110,6 +116,76 @@ int store_unit(const void* out, int row_bytes) {
   return 1;
 }
 
+// ---- the argument checks the entry points share: each speaks under the name `fn` of the entry point that called it ---------------
+#define SC_TRY(call) do { const int rc_ = (call); if (rc_ != RUA_OK) return rc_; } while (0)
+
+// scene s of a call: its pointers (ptrs: all that the call needs are there), and h * w * bpp bytes below 2^40
+int check_scene(const char* fn, int s, bool ptrs, int h, int w, int bpp, bool say_bpp = false) {
+  RUA_CHECK_ARG(ptrs, "%s: scene %d: null pointer", fn, s);
+  if (h >= 1 && w >= 1 && (int64_t)h * w * bpp < ((int64_t)1 << 40)) return RUA_OK;
+  if (say_bpp) rua_set_error("%s: scene %d: size %d x %d x %d", fn, s, h, w, bpp);
+  else rua_set_error("%s: scene %d: size %d x %d", fn, s, h, w);
+  return RUA_ERR_ARG;
+}
+
+// every scene of a call: `must` holds a pointer per scene, `may` is either absent or holds one per scene too
+int check_scene_list(const char* fn, const uint8_t* const* must, const uint8_t* const* may, const int32_t* scene_h, const int32_t* scene_w,
+                     int nscenes, int bpp, bool say_bpp = false) {
+  for (int s = 0; s < nscenes; ++s) SC_TRY(check_scene(fn, s, must[s] && (!may || may[s]), scene_h[s], scene_w[s], bpp, say_bpp));
+  return RUA_OK;
+}
+
+// table row k = (scene, row, col, code): the scene exists and the PH x PW window lies inside it ...
+int check_row_place(const char* fn, int k, const int32_t* t, int PH, int PW, const int32_t* scene_h, const int32_t* scene_w, int nscenes) {
+  const int s = t[0], r = t[1], c = t[2];
+  RUA_CHECK_ARG(s >= 0 && s < nscenes, "%s: row %d: scene %d outside 0..%d", fn, k, s, nscenes - 1);
+  RUA_CHECK_ARG(r >= 0 && c >= 0 && (int64_t)r + PH <= scene_h[s] && (int64_t)c + PW <= scene_w[s],
+                "%s: row %d: window (%d, %d) + %d x %d leaves its %d x %d scene", fn, k, r, c, PH, PW, scene_h[s], scene_w[s]);
+  return RUA_OK;
+}
+
+// ... and its code is one of the eight symmetries, a transposing one only on a square patch
+int check_row_code(const char* fn, int k, int code, int PH, int PW) {
+  RUA_CHECK_ARG(code >= 0 && code <= 7, "%s: row %d: code %d outside 0..7", fn, k, code);
+  RUA_CHECK_ARG(PH == PW || !(code == 1 || code >= 5), "%s: row %d: code %d transposes and needs a square patch (got %d x %d)", fn, k, code, PH, PW);
+  return RUA_OK;
+}
+
+// an ownership row (r0, r1, c0, c1) of the `what` ("row" or "group") with index k
+int check_owned(const char* fn, const char* what, int k, const int32_t* o, int PH, int PW) {
+  RUA_CHECK_ARG(0 <= o[0] && o[0] <= o[1] && o[1] <= PH && 0 <= o[2] && o[2] <= o[3] && o[3] <= PW,
+                "%s: %s %d: owned rows %d..%d, columns %d..%d outside the %d x %d window", fn, what, k, o[0], o[1], o[2], o[3], PH, PW);
+  return RUA_OK;
+}
+
+// a window table [N][4] whose codes matter
+int check_window_rows(const char* fn, const int32_t* windows, int N, int PH, int PW, const int32_t* scene_h, const int32_t* scene_w, int nscenes) {
+  for (int k = 0; k < N; ++k) {
+    const int32_t* t = windows + 4 * (size_t)k;
+    SC_TRY(check_row_place(fn, k, t, PH, PW, scene_h, scene_w, nscenes));
+    SC_TRY(check_row_code(fn, k, t[3], PH, PW));
+  }
+  return RUA_OK;
+}
+
+// G groups of K views: rows g K .. g K + K - 1 of windows [G*K][4] are one window under K codes, own [G][4] its owned rectangle
+int check_groups(const char* fn, const int32_t* windows, const int32_t* own, int G, int K, int PH, int PW, const int32_t* scene_h,
+                 const int32_t* scene_w, int nscenes) {
+  for (int g = 0; g < G; ++g) {
+    const int32_t* t0 = windows + 4 * (size_t)g * K;
+    for (int v = 0; v < K; ++v) {
+      const int32_t* t = t0 + 4 * v;
+      const int k = g * K + v;
+      SC_TRY(check_row_place(fn, k, t, PH, PW, scene_h, scene_w, nscenes));
+      RUA_CHECK_ARG(t[0] == t0[0] && t[1] == t0[1] && t[2] == t0[2], "%s: row %d: scene %d, window (%d, %d), but its group %d is scene %d, window (%d, %d)",
+                    fn, k, t[0], t[1], t[2], g, t0[0], t0[1], t0[2]);
+      SC_TRY(check_row_code(fn, k, t[3], PH, PW));
+    }
+    SC_TRY(check_owned(fn, "group", g, own + 4 * (size_t)g, PH, PW));
+  }
+  return RUA_OK;
+}
+
 }  // namespace
 
 extern "C" int rua_scene_windows(const uint8_t* const* scene_img, const uint8_t* const* scene_cls, const int32_t* scene_h, const int32_t* scene_w,
@@ -121,21 +197,8 @@ extern "C" int rua_scene_windows(const uint8_t* const* scene_img, const uint8_t*
   RUA_CHECK_ARG(Cin >= 1 && Cin <= SW_MAXPIX, "rua_scene_windows: Cin %d outside 1..16", Cin);
   RUA_CHECK_ARG(PH >= 1 && PW >= 1 && PH <= SW_MAXP && PW <= SW_MAXP, "rua_scene_windows: PH %d, PW %d (1 <= PH, PW <= 512)", PH, PW);
   RUA_CHECK_ARG(((uintptr_t)img_out & 3) == 0 && ((uintptr_t)cls_out & 3) == 0, "rua_scene_windows: img_out and cls_out must be 4-byte aligned");
-  for (int s = 0; s < nscenes; ++s) {
-    RUA_CHECK_ARG(scene_img[s] && (!scene_cls || scene_cls[s]), "rua_scene_windows: scene %d: null pointer", s);
-    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] * Cin < ((int64_t)1 << 40),
-                  "rua_scene_windows: scene %d: size %d x %d", s, scene_h[s], scene_w[s]);
-  }
-  for (int k = 0; k < N; ++k) {
-    const int32_t* t = windows + 4 * (size_t)k;
-    const int s = t[0], r = t[1], c = t[2], code = t[3];
-    RUA_CHECK_ARG(s >= 0 && s < nscenes, "rua_scene_windows: row %d: scene %d outside 0..%d", k, s, nscenes - 1);
-    RUA_CHECK_ARG(r >= 0 && c >= 0 && (int64_t)r + PH <= scene_h[s] && (int64_t)c + PW <= scene_w[s],
-                  "rua_scene_windows: row %d: window (%d, %d) + %d x %d leaves its %d x %d scene", k, r, c, PH, PW, scene_h[s], scene_w[s]);
-    RUA_CHECK_ARG(code >= 0 && code <= 7, "rua_scene_windows: row %d: code %d outside 0..7", k, code);
-    RUA_CHECK_ARG(PH == PW || !(code == 1 || code >= 5), "rua_scene_windows: row %d: code %d transposes and needs a square patch (got %d x %d)",
-                  k, code, PH, PW);
-  }
+  SC_TRY(check_scene_list("rua_scene_windows", scene_img, scene_cls, scene_h, scene_w, nscenes, Cin));
+  SC_TRY(check_window_rows("rua_scene_windows", windows, N, PH, PW, scene_h, scene_w, nscenes));
   hipStream_t st = (hipStream_t)stream;
   const int tiles = ((PH + SW_T - 1) / SW_T) * ((PW + SW_T - 1) / SW_T);
   SceneArgs a;
@@ -318,8 +381,7 @@ extern "C" int rua_scene_windows_affine(const uint8_t* const* scene_img, const u
 // that cover it - whole pieces straight into LDS at the same dword phase, single dwords only where a piece would reach past the end
 // of p - and then one lane takes the arg-max of one pixel out of LDS (stride C dwords: free of conflicts for odd C, two-way for
 // C = 6).  Lanes of a wave are neighbouring pixels of a scene row: the class map is read and the prediction written as contiguous
-// bytes.  Counts collect in an LDS histogram of C * C cells (a block holds at most 8 * 256 pixels: 32 bits are plenty) and every
-// non-zero cell leaves with one 64-bit atomicAdd at the end of the block.
+// bytes.  Counts collect in an LDS histogram of C * C cells (a block holds at most 8 * 256 pixels: 32 bits are plenty; ss_score, ss_flush).
 namespace {
 
 constexpr int SS_CHUNK = 120;                  // windows per launch: 32 bytes each
@@ -328,21 +390,59 @@ constexpr int SS_ROWF = 4096;                  // floats of one staged row run a
 constexpr int SS_LDSF = 4608;                  // LDS floats: >= one row's pitch (SS_ROWF + 6) / 4 * 4 = 4100
 constexpr int SS_MAXC = 64;
 
-struct StitchWin { uint8_t* pred; const uint8_t* cls; int W; uint16_t r0, r1, c0, c1; int pad; };   // pred, cls: at the window's origin
+// One window of a stitching launch, or one group of K views of it (the three stitch kernels).  out, cls: at the window's origin in
+// its scene's map (cls: null where nothing is counted); W: the scene's width; codes: 3 bits per view, view 0 lowest.
+struct StitchGroup { uint8_t* out; const uint8_t* cls; int W; uint16_t r0, r1, c0, c1; uint32_t codes; };
 struct StitchArgs {
-  StitchWin w[SS_CHUNK];
+  StitchGroup w[SS_CHUNK];
   const float* p; unsigned long long* confusion;
   long long total;                             // floats in p: nothing beyond is read
   int first, PH, PW, C, tw;                    // first: table row of w[0]; tw: columns per block
 };
-static_assert(sizeof(StitchWin) == 32 && sizeof(StitchArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+static_assert(sizeof(StitchGroup) == 32 && sizeof(StitchArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+// group g of a launch from rows t (its K table rows) and o (its ownership row); the maps hold bpp bytes per pixel
+void fill_group(StitchGroup& w, const int32_t* t, const int32_t* o, int K, uint8_t* out, const uint8_t* cls, int W, int bpp) {
+  const size_t px = (size_t)t[1] * W + t[2];
+  w.out = out + px * bpp;
+  w.cls = cls ? cls + px : nullptr;
+  w.W = W;
+  w.r0 = (uint16_t)o[0]; w.r1 = (uint16_t)o[1]; w.c0 = (uint16_t)o[2]; w.c1 = (uint16_t)o[3];
+  w.codes = 0;
+  for (int v = 0; v < K; ++v) w.codes |= (uint32_t)t[4 * v + 3] << (3 * v);
+}
+
+// The scoring tail of a stitched pixel: the arg-max of its C values at v (first index of the maximum, a strict > scan from class
+// 0) goes to window pixel (i, j) of the scene's map and, with a class map, into the block's histogram cell [t][pred] ...
+__device__ __forceinline__ void ss_score(const float* v, int C, const StitchGroup& w, int i, int j, bool count, uint32_t* hist) {
+  float best = v[0];
+  int pred = 0;
+  for (int c = 1; c < C; ++c) {
+    const float x = v[c];
+    if (x > best) { best = x; pred = c; }
+  }
+  const size_t at = (size_t)i * w.W + j;
+  w.out[at] = (uint8_t)pred;
+  if (count) {
+    const int t = w.cls[at];
+    if (t < C) atomicAdd(&hist[t * C + pred], 1u);
+  }
+}
+
+// ... and at the end of the block (after a barrier) every non-zero cell leaves with one 64-bit atomicAdd
+__device__ __forceinline__ void ss_flush(const uint32_t* hist, int C, unsigned long long* confusion, int tid) {
+  for (int e = tid; e < C * C; e += 256) {
+    const uint32_t n = hist[e];
+    if (n) atomicAdd(confusion + e, (unsigned long long)n);
+  }
+}
 
 __global__ __launch_bounds__(256) void scene_stitch(StitchArgs a) {
   __shared__ uint4 Sq[SS_LDSF / 4];
   extern __shared__ uint32_t hist[];             // C * C cells (dynamic: 144 bytes at C = 6, not the 16 KiB of C = 64)
   float* S = reinterpret_cast<float*>(Sq);
   const int tid = threadIdx.x, C = a.C, PW = a.PW;
-  const StitchWin& w = a.w[blockIdx.y];
+  const StitchGroup& w = a.w[blockIdx.y];
   const int chunks = (PW + a.tw - 1) / a.tw;
   const int band = blockIdx.x / chunks, chunk = blockIdx.x - band * chunks;
   const int i0 = w.r0 + band * SS_BAND, j0 = w.c0 + chunk * a.tw;
@@ -369,7 +469,7 @@ __global__ __launch_bounds__(256) void scene_stitch(StitchArgs a) {
     for (int e = tid; e < nr * tw; e += 256) {
       const int rr = e / tw, tj = e - rr * tw, i = i0 + ib + rr, j = j0 + tj;
       const int phase = (int)(((wbase + (long long)i * PW + j0) * C) & 3);
-      const float* v = S + rr * pitch + phase + tj * C;
+      const float* v = S + rr * pitch + phase + tj * C;              // ss_score, written out: see DESIGN.md
       float best = v[0];
       int pred = 0;
       for (int c = 1; c < C; ++c) {
@@ -377,7 +477,7 @@ __global__ __launch_bounds__(256) void scene_stitch(StitchArgs a) {
         if (x > best) { best = x; pred = c; }
       }
       const size_t at = (size_t)i * w.W + j;
-      w.pred[at] = (uint8_t)pred;
+      w.out[at] = (uint8_t)pred;
       if (count) {
         const int t = w.cls[at];
         if (t < C) atomicAdd(&hist[t * C + pred], 1u);
@@ -386,7 +486,7 @@ __global__ __launch_bounds__(256) void scene_stitch(StitchArgs a) {
   }
   if (!count) return;
   __syncthreads();
-  for (int e = tid; e < C * C; e += 256) {
+  for (int e = tid; e < C * C; e += 256) {     // ss_flush, written out
     const uint32_t n = hist[e];
     if (n) atomicAdd(a.confusion + e, (unsigned long long)n);
   }
@@ -403,21 +503,12 @@ extern "C" int rua_scene_stitch(const float* p, int N, int PH, int PW, int C, co
   RUA_CHECK_ARG(C >= 1 && C <= SS_MAXC, "rua_scene_stitch: C %d outside 1..64", C);
   RUA_CHECK_ARG(PH >= 1 && PW >= 1 && PH <= SW_MAXP && PW <= SW_MAXP, "rua_scene_stitch: PH %d, PW %d (1 <= PH, PW <= 512)", PH, PW);
   RUA_CHECK_ARG(((uintptr_t)p & 15) == 0 && ((uintptr_t)confusion & 7) == 0, "rua_scene_stitch: p must be 16-byte, confusion 8-byte aligned");
-  for (int s = 0; s < nscenes; ++s) {
-    RUA_CHECK_ARG(scene_pred[s] && (!scene_cls || scene_cls[s]), "rua_scene_stitch: scene %d: null pointer", s);
-    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] < ((int64_t)1 << 40),
-                  "rua_scene_stitch: scene %d: size %d x %d", s, scene_h[s], scene_w[s]);
-  }
-  for (int k = 0; k < N; ++k) {
+  SC_TRY(check_scene_list("rua_scene_stitch", scene_pred, scene_cls, scene_h, scene_w, nscenes, 1));
+  for (int k = 0; k < N; ++k) {                  // check_groups' order for K = 1, with this entry point's own rule for the code
     const int32_t* t = windows + 4 * (size_t)k;
-    const int32_t* o = own + 4 * (size_t)k;
-    const int s = t[0], r = t[1], c = t[2];
-    RUA_CHECK_ARG(s >= 0 && s < nscenes, "rua_scene_stitch: row %d: scene %d outside 0..%d", k, s, nscenes - 1);
-    RUA_CHECK_ARG(r >= 0 && c >= 0 && (int64_t)r + PH <= scene_h[s] && (int64_t)c + PW <= scene_w[s],
-                  "rua_scene_stitch: row %d: window (%d, %d) + %d x %d leaves its %d x %d scene", k, r, c, PH, PW, scene_h[s], scene_w[s]);
+    SC_TRY(check_row_place("rua_scene_stitch", k, t, PH, PW, scene_h, scene_w, nscenes));
     RUA_CHECK_ARG(t[3] == 0, "rua_scene_stitch: row %d: code %d (a prediction window is cut as it is: code 0)", k, t[3]);
-    RUA_CHECK_ARG(0 <= o[0] && o[0] <= o[1] && o[1] <= PH && 0 <= o[2] && o[2] <= o[3] && o[3] <= PW,
-                  "rua_scene_stitch: row %d: owned rows %d..%d, columns %d..%d outside the %d x %d window", k, o[0], o[1], o[2], o[3], PH, PW);
+    SC_TRY(check_owned("rua_scene_stitch", "row", k, own + 4 * (size_t)k, PH, PW));
   }
   hipStream_t st = (hipStream_t)stream;
   StitchArgs a;
@@ -432,14 +523,8 @@ extern "C" int rua_scene_stitch(const float* p, int N, int PH, int PW, int C, co
     const int nk = N - k0 < SS_CHUNK ? N - k0 : SS_CHUNK;
     for (int k = 0; k < nk; ++k) {
       const int32_t* t = windows + 4 * (size_t)(k0 + k);
-      const int32_t* o = own + 4 * (size_t)(k0 + k);
       const int s = t[0];
-      const size_t px = (size_t)t[1] * scene_w[s] + t[2];
-      StitchWin& w = a.w[k];
-      w.pred = scene_pred[s] + px;
-      w.cls = scene_cls ? scene_cls[s] + px : nullptr;
-      w.W = scene_w[s];
-      w.r0 = (uint16_t)o[0]; w.r1 = (uint16_t)o[1]; w.c0 = (uint16_t)o[2]; w.c1 = (uint16_t)o[3];
+      fill_group(a.w[k], t, own + 4 * (size_t)(k0 + k), 1, scene_pred[s], scene_cls ? scene_cls[s] : nullptr, scene_w[s], 1);
     }
     a.first = k0;
     hipLaunchKernelGGL(scene_stitch, dim3(blocks, nk), dim3(256), scene_cls ? (size_t)C * C * sizeof(uint32_t) : 0, st, a);
@@ -455,15 +540,12 @@ extern "C" int rua_scene_stitch(const float* p, int N, int PH, int PW, int C, co
 // where rua_scene_stitch puts the arg-max of p.  scenes.host_stitch_views gives the same bytes.
 //
 // A block owns a T x T tile of a group's owned rectangle (clipped to it); T, a multiple of 4 up to 32, is the largest with
-// T * T * C <= SV_ACCF, so a thread holds at most SV_SLOTS = 16 (pixel, class) sums in registers, the same ones under every view:
-// the order of a sum is the order of the view loop.  Under any of the eight symmetries the tile is a (transposed, mirrored)
-// rectangle of the view, so every view is read ALONG ITS OWN ROWS: the run of vb * C floats of a view row comes in as the aligned
-// 16-byte pieces that cover it (single dwords only where a piece would reach past the end of p), into LDS at the same dword
-// phase; the turn back happens in the LDS read, whose row pitch is an odd number of 16-byte pieces so that the rows a transposed
-// read walks start in different banks.  A barrier on either side of the staging separates the views.  At the end the sums go to
-// LDS (over the staging area), one lane takes the arg-max of one pixel - lanes along scene rows, so the class map is read and the
-// prediction written as contiguous bytes - and the counts leave as in scene_stitch: an LDS histogram, one 64-bit atomicAdd per
-// non-zero cell.
+// T * T * C <= SV_ACCF (tile_of), so a thread holds at most SV_SLOTS = 16 (pixel, class) sums in registers, the same ones under
+// every view: the order of a sum is the order of the view loop.  Under any of the eight symmetries the tile is a (transposed,
+// mirrored) rectangle of the view (view_tile), so every view is read ALONG ITS OWN ROWS (sv_stage); the turn back happens in the
+// LDS read (sv_at), whose row pitch is an odd number of 16-byte pieces so that the rows a transposed read walks start in different
+// banks.  A barrier on either side of the staging separates the views.  At the end the sums go to LDS (over the staging area) and
+// one lane scores one pixel as in scene_stitch (ss_score, ss_flush), lanes along scene rows.
 namespace {
 
 constexpr int SV_CHUNK = 120;                  // groups per launch: 32 bytes each
@@ -471,21 +553,69 @@ constexpr int SV_MAXK = 8;
 constexpr int SV_ACCF = 4096;                  // sums of one tile at most: T * T * C
 constexpr int SV_SLOTS = SV_ACCF / 256;        // ... and of one thread
 
-struct ViewGroup { uint8_t* pred; const uint8_t* cls; int W; uint16_t r0, r1, c0, c1; uint32_t codes; };   // codes: 3 bits per view, view 0 lowest
 struct ViewArgs {
-  ViewGroup g[SV_CHUNK];
+  StitchGroup g[SV_CHUNK];
   const float* p; unsigned long long* confusion;
   long long total;                             // floats in p: nothing beyond is read
   int first, PH, PW, C, K, T, maxp;            // first: group of g[0]; maxp: LDS row pitch in 16-byte pieces (odd)
 };
-static_assert(sizeof(ViewGroup) == 32 && sizeof(ViewArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+static_assert(sizeof(ViewArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+// the tile edge T and the LDS row pitch maxp (pieces that cover a run of T * C floats at any phase, made odd) for C values a pixel
+void tile_of(int C, int& T, int& maxp) {
+  T = 32;
+  while (T * T * C > SV_ACCF) T -= 4;                          // C = 64: 8
+  maxp = ((T * C + 6) / 4) | 1;
+}
+
+// The tile [i0, i0 + th) x [j0, j0 + tw) of a PH x PW window under a view: window pixel (i, j) sits at view (tr ? (y, x) : (x, y))
+// with x = fr ? PH-1-i : i, y = fc ? PW-1-j : j (PH == PW when tr), so the tile is va rows of vb pixels at (a0, b0) of the view.
+struct ViewTile { int a0, b0, va, vb; };
+__device__ __forceinline__ ViewTile view_tile(bool tr, bool fr, bool fc, int PH, int PW, int i0, int j0, int th, int tw) {
+  const int x0 = fr ? PH - i0 - th : i0, y0 = fc ? PW - j0 - tw : j0;
+  return {tr ? y0 : x0, tr ? x0 : y0, tr ? tw : th, tr ? th : tw};
+}
+
+// the read side of a view: va rows of ne floats, row rr the run that starts at pixel vbase + (a0 + rr) * PW + b0 of p, as the aligned
+// 16-byte pieces that cover it (single dwords only where a piece would reach past the end of p) into LDS rows of maxp pieces at the
+// run's own dword phase
+__device__ __forceinline__ void sv_stage(uint4* Vq, const float* p, long long total, long long vbase, int a0, int b0, int va, int ne,
+                                         int PW, int C, int maxp, int tid) {
+  float* S = reinterpret_cast<float*>(Vq);
+  const int pitch = maxp * 4;
+  for (int e = tid; e < va * maxp; e += 256) {
+    const int rr = e / maxp, q = e - rr * maxp;
+    const long long e0 = (vbase + (long long)(a0 + rr) * PW + b0) * C, al = e0 & ~3LL;   // the run is floats [e0, e0 + ne) of p
+    const long long lo = al + 4 * q;
+    if (lo >= e0 + ne) continue;
+    if (lo + 4 <= total) Vq[rr * maxp + q] = ldg16(p + lo);
+    else for (long long x = lo; x < total; ++x) S[rr * pitch + (int)(x - al)] = p[x];
+  }
+}
+
+// item e of a tile of tw columns and C values a pixel, e = (ti * tw + tj) * C + c, kept as one register over the view loop
+struct TileItem { int ti, tj, c; };
+__device__ __forceinline__ int sv_pack(int e, int C, int tw) {
+  const int px = e / C, c = e - px * C, ti = px / tw, tj = px - ti * tw;
+  return (ti << 16) | (tj << 8) | c;
+}
+__device__ __forceinline__ TileItem sv_unpack(int pk) { return {pk >> 16, (pk >> 8) & 255, pk & 255}; }
+
+// the turn back: the LDS float of a tile item in the staged view.  pb: the low bits of the pixel index of the view tile's first
+// pixel, of which a row's dword phase follows
+__device__ __forceinline__ int sv_at(bool tr, bool fr, bool fc, const TileItem& it, int th, int tw, unsigned pb, int PW, int C, int pitch) {
+  const int xl = fr ? th - 1 - it.ti : it.ti, yl = fc ? tw - 1 - it.tj : it.tj;
+  const int ra = tr ? yl : xl, cb = tr ? xl : yl;
+  const int phase = (int)(((pb + (unsigned)(ra * PW)) * (unsigned)C) & 3u);
+  return ra * pitch + phase + cb * C + it.c;
+}
 
 __global__ __launch_bounds__(256) void scene_stitch_views(ViewArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint4 Vq[];      // T * maxp pieces of staging, then C * C histogram cells
   float* S = reinterpret_cast<float*>(Vq);
   const int tid = threadIdx.x, C = a.C, PH = a.PH, PW = a.PW, T = a.T, maxp = a.maxp, pitch = maxp * 4;
   uint32_t* hist = reinterpret_cast<uint32_t*>(Vq + T * maxp);
-  const ViewGroup& w = a.g[blockIdx.y];
+  const StitchGroup& w = a.g[blockIdx.y];
   const int tiles_x = (PW + T - 1) / T;
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int i0 = w.r0 + ty * T, j0 = w.c0 + tx * T;
@@ -502,41 +632,22 @@ __global__ __launch_bounds__(256) void scene_stitch_views(ViewArgs a) {
     const int e = tid + 256 * m;
     pk[m] = 0;
     acc[m] = 0.f;
-    if (e < ne_tile) {
-      const int px = e / C, c = e - px * C, ti = px / tw, tj = px - ti * tw;
-      pk[m] = (ti << 16) | (tj << 8) | c;
-    }
+    if (e < ne_tile) pk[m] = sv_pack(e, C, tw);
   }
   const long long group = a.first + (long long)blockIdx.y;
   for (int k = 0; k < a.K; ++k) {
-    const int code = (int)(w.codes >> (3 * k)) & 7;
-    const bool tr = code == 1 || code == 5 || code == 6 || code == 7;
-    const bool fr = code == 2 || code == 3 || code == 5 || code == 7;
-    const bool fc = code == 1 || code == 2 || code == 4 || code == 7;
-    // window pixel (i, j) sits at view (tr ? (y, x) : (x, y)) with x = fr ? PH-1-i : i, y = fc ? PW-1-j : j (PH == PW when tr)
-    const int x0 = fr ? PH - i0 - th : i0, y0 = fc ? PW - j0 - tw : j0;
-    const int a0 = tr ? y0 : x0, b0 = tr ? x0 : y0, va = tr ? tw : th, vb = tr ? th : tw;   // the tile in the view: va rows of vb pixels at (a0, b0)
-    const int ne = vb * C;
+    const Sym y{(int)(w.codes >> (3 * k)) & 7};
+    const bool tr = y.tr(), fr = y.fr(), fc = y.fc();
+    const ViewTile vt = view_tile(tr, fr, fc, PH, PW, i0, j0, th, tw);
     const long long vbase = (group * a.K + k) * PH * PW;            // pixel index of the view in p
     __syncthreads();                           // the last view's reads of S are done
-    for (int e = tid; e < va * maxp; e += 256) {
-      const int rr = e / maxp, q = e - rr * maxp;
-      const long long e0 = (vbase + (long long)(a0 + rr) * PW + b0) * C, al = e0 & ~3LL;   // the run is floats [e0, e0 + ne) of p
-      const long long lo = al + 4 * q;
-      if (lo >= e0 + ne) continue;
-      if (lo + 4 <= a.total) Vq[rr * maxp + q] = ldg16(a.p + lo);
-      else for (long long x = lo; x < a.total; ++x) S[rr * pitch + (int)(x - al)] = a.p[x];
-    }
+    sv_stage(Vq, a.p, a.total, vbase, vt.a0, vt.b0, vt.va, vt.vb * C, PW, C, maxp, tid);
     __syncthreads();
-    const unsigned pb = (unsigned)vbase + (unsigned)(a0 * PW + b0);  // low bits of a row's first pixel index: its dword phase
+    const unsigned pb = (unsigned)vbase + (unsigned)(vt.a0 * PW + vt.b0);
 #pragma unroll
     for (int m = 0; m < SV_SLOTS; ++m) {
       if (tid + 256 * m < ne_tile) {
-        const int ti = pk[m] >> 16, tj = (pk[m] >> 8) & 255, c = pk[m] & 255;
-        const int xl = fr ? th - 1 - ti : ti, yl = fc ? tw - 1 - tj : tj;
-        const int ra = tr ? yl : xl, cb = tr ? xl : yl;
-        const int phase = (int)(((pb + (unsigned)(ra * PW)) * (unsigned)C) & 3u);
-        const float v = S[ra * pitch + phase + cb * C + c];
+        const float v = S[sv_at(tr, fr, fc, sv_unpack(pk[m]), th, tw, pb, PW, C, pitch)];
         acc[m] = k == 0 ? v : acc[m] + v;      // sequential fp32 adds in view order
       }
     }
@@ -548,26 +659,11 @@ __global__ __launch_bounds__(256) void scene_stitch_views(ViewArgs a) {
   __syncthreads();
   for (int e = tid; e < th * tw; e += 256) {
     const int ti = e / tw, tj = e - ti * tw;
-    const float* v = S + e * C;
-    float best = v[0];
-    int pred = 0;
-    for (int c = 1; c < C; ++c) {
-      const float x = v[c];
-      if (x > best) { best = x; pred = c; }
-    }
-    const size_t at = (size_t)(i0 + ti) * w.W + (j0 + tj);
-    w.pred[at] = (uint8_t)pred;
-    if (count) {
-      const int t = w.cls[at];
-      if (t < C) atomicAdd(&hist[t * C + pred], 1u);
-    }
+    ss_score(S + e * C, C, w, i0 + ti, j0 + tj, count, hist);
   }
   if (!count) return;
   __syncthreads();
-  for (int e = tid; e < C * C; e += 256) {
-    const uint32_t n = hist[e];
-    if (n) atomicAdd(a.confusion + e, (unsigned long long)n);
-  }
+  ss_flush(hist, C, a.confusion, tid);
 }
 
 }  // namespace
@@ -583,55 +679,23 @@ extern "C" int rua_scene_stitch_views(const float* p, int G, int K, int PH, int 
   RUA_CHECK_ARG(C >= 1 && C <= SS_MAXC, "rua_scene_stitch_views: C %d outside 1..64", C);
   RUA_CHECK_ARG(PH >= 1 && PW >= 1 && PH <= SW_MAXP && PW <= SW_MAXP, "rua_scene_stitch_views: PH %d, PW %d (1 <= PH, PW <= 512)", PH, PW);
   RUA_CHECK_ARG(((uintptr_t)p & 15) == 0 && ((uintptr_t)confusion & 7) == 0, "rua_scene_stitch_views: p must be 16-byte, confusion 8-byte aligned");
-  for (int s = 0; s < nscenes; ++s) {
-    RUA_CHECK_ARG(scene_pred[s] && (!scene_cls || scene_cls[s]), "rua_scene_stitch_views: scene %d: null pointer", s);
-    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] < ((int64_t)1 << 40),
-                  "rua_scene_stitch_views: scene %d: size %d x %d", s, scene_h[s], scene_w[s]);
-  }
-  for (int g = 0; g < G; ++g) {
-    const int32_t* t0 = windows + 4 * (size_t)g * K;
-    const int32_t* o = own + 4 * (size_t)g;
-    for (int v = 0; v < K; ++v) {
-      const int32_t* t = t0 + 4 * v;
-      const int k = g * K + v, s = t[0], r = t[1], c = t[2], code = t[3];
-      RUA_CHECK_ARG(s >= 0 && s < nscenes, "rua_scene_stitch_views: row %d: scene %d outside 0..%d", k, s, nscenes - 1);
-      RUA_CHECK_ARG(r >= 0 && c >= 0 && (int64_t)r + PH <= scene_h[s] && (int64_t)c + PW <= scene_w[s],
-                    "rua_scene_stitch_views: row %d: window (%d, %d) + %d x %d leaves its %d x %d scene", k, r, c, PH, PW, scene_h[s], scene_w[s]);
-      RUA_CHECK_ARG(s == t0[0] && r == t0[1] && c == t0[2],
-                    "rua_scene_stitch_views: row %d: scene %d, window (%d, %d), but its group %d is scene %d, window (%d, %d)",
-                    k, s, r, c, g, t0[0], t0[1], t0[2]);
-      RUA_CHECK_ARG(code >= 0 && code <= 7, "rua_scene_stitch_views: row %d: code %d outside 0..7", k, code);
-      RUA_CHECK_ARG(PH == PW || !(code == 1 || code >= 5),
-                    "rua_scene_stitch_views: row %d: code %d transposes and needs a square patch (got %d x %d)", k, code, PH, PW);
-    }
-    RUA_CHECK_ARG(0 <= o[0] && o[0] <= o[1] && o[1] <= PH && 0 <= o[2] && o[2] <= o[3] && o[3] <= PW,
-                  "rua_scene_stitch_views: group %d: owned rows %d..%d, columns %d..%d outside the %d x %d window", g, o[0], o[1], o[2], o[3], PH, PW);
-  }
+  SC_TRY(check_scene_list("rua_scene_stitch_views", scene_pred, scene_cls, scene_h, scene_w, nscenes, 1));
+  SC_TRY(check_groups("rua_scene_stitch_views", windows, own, G, K, PH, PW, scene_h, scene_w, nscenes));
   hipStream_t st = (hipStream_t)stream;
   ViewArgs a;
   memset(&a, 0, sizeof(a));
   a.p = p; a.confusion = reinterpret_cast<unsigned long long*>(confusion);
   a.total = (long long)G * K * PH * PW * C;
   a.PH = PH; a.PW = PW; a.C = C; a.K = K;
-  a.T = 32;
-  while (a.T * a.T * C > SV_ACCF) a.T -= 4;                    // C = 64: 8
-  a.maxp = ((a.T * C + 6) / 4) | 1;                            // pieces that cover a run at any phase, made odd
+  tile_of(C, a.T, a.maxp);
   const int blocks = ((PH + a.T - 1) / a.T) * ((PW + a.T - 1) / a.T);
   const size_t lds = (size_t)a.T * a.maxp * 16 + (scene_cls ? (size_t)C * C * sizeof(uint32_t) : 0);   // 33 KiB at most (C = 64)
   for (int g0 = 0; g0 < G; g0 += SV_CHUNK) {
     const int ng = G - g0 < SV_CHUNK ? G - g0 : SV_CHUNK;
     for (int g = 0; g < ng; ++g) {
       const int32_t* t = windows + 4 * (size_t)(g0 + g) * K;
-      const int32_t* o = own + 4 * (size_t)(g0 + g);
       const int s = t[0];
-      const size_t px = (size_t)t[1] * scene_w[s] + t[2];
-      ViewGroup& w = a.g[g];
-      w.pred = scene_pred[s] + px;
-      w.cls = scene_cls ? scene_cls[s] + px : nullptr;
-      w.W = scene_w[s];
-      w.r0 = (uint16_t)o[0]; w.r1 = (uint16_t)o[1]; w.c0 = (uint16_t)o[2]; w.c1 = (uint16_t)o[3];
-      w.codes = 0;
-      for (int v = 0; v < K; ++v) w.codes |= (uint32_t)t[4 * v + 3] << (3 * v);
+      fill_group(a.g[g], t, own + 4 * (size_t)(g0 + g), K, scene_pred[s], scene_cls ? scene_cls[s] : nullptr, scene_w[s], 1);
     }
     a.first = g0;
     hipLaunchKernelGGL(scene_stitch_views, dim3(blocks, ng), dim3(256), lds, st, a);
@@ -649,7 +713,7 @@ extern "C" int rua_scene_stitch_views(const float* p, int G, int K, int PH, int 
 // and the views are averaged in RGB, out = (2 sum + K) / (2 K): hue is circular, its mean is not a hue.
 //
 // The read side is scene_stitch_views': a block owns a T x T tile of a group's rectangle, each view comes in along its own rows
-// (sm_stage), the turn back happens in the LDS read and the sums stay in registers over the view loop - in mode 0 a thread holds
+// (sv_stage), the turn back happens in the LDS read (sv_at) and the sums stay in registers over the view loop - in mode 0 a thread holds
 // (pixel, channel) elements tid + 256 m, consecutive lanes consecutive floats of a window row (free of bank conflicts under a
 // code that keeps rows, stride Ch dwords under a transposing one: odd pitch, so 2-way at most for even Ch); in mode 1 it holds
 // whole pixels tid + 256 m (T = 32: four of them), three floats at a stride of 3 dwords between lanes, conflict-free.
@@ -663,14 +727,13 @@ namespace {
 constexpr int SM_CHUNK = 120;                  // groups per launch: 32 bytes each
 constexpr int SM_PIX = 4;                      // pixels of one thread in mode 1: 32 * 32 / 256
 
-struct MapGroup { uint8_t* out; int W; uint16_t r0, r1, c0, c1; uint32_t codes; int pad; };   // out: at the window's origin; codes as ViewGroup's
 struct MapArgs {
-  MapGroup g[SM_CHUNK];
+  StitchGroup g[SM_CHUNK];                     // out: the Ch-channel map; cls unused
   const float* p;
   long long total;                             // floats in p: nothing beyond is read
   int first, PH, PW, Ch, K, T, maxp;           // as ViewArgs
 };
-static_assert(sizeof(MapGroup) == 32 && sizeof(MapArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+static_assert(sizeof(MapArgs) <= 4096, "kernel arguments are limited to 4 KiB");
 
 // NaN and everything <= 0 give 0, everything >= 1 (+inf too) 65536; ties to even
 __device__ __forceinline__ uint32_t sm_q16(float x) {
@@ -689,28 +752,12 @@ __device__ __forceinline__ void sm_hsv_rgb(uint32_t h, uint32_t s, uint32_t v, u
   b = sec == 3 || sec == 4 ? v : sec == 2 ? t : sec == 5 ? q : p;
 }
 
-// the read side of a view, scene_stitch_views' staging loop as a function: va rows of ne floats, row rr the run that starts at pixel
-// vbase + (a0 + rr) * PW + b0 of p, into LDS rows of maxp 16-byte pieces at the run's own dword phase
-__device__ __forceinline__ void sm_stage(uint4* Vq, const float* p, long long total, long long vbase, int a0, int b0, int va, int ne,
-                                         int PW, int C, int maxp, int tid) {
-  float* S = reinterpret_cast<float*>(Vq);
-  const int pitch = maxp * 4;
-  for (int e = tid; e < va * maxp; e += 256) {
-    const int rr = e / maxp, q = e - rr * maxp;
-    const long long e0 = (vbase + (long long)(a0 + rr) * PW + b0) * C, al = e0 & ~3LL;   // the run is floats [e0, e0 + ne) of p
-    const long long lo = al + 4 * q;
-    if (lo >= e0 + ne) continue;
-    if (lo + 4 <= total) Vq[rr * maxp + q] = ldg16(p + lo);
-    else for (long long x = lo; x < total; ++x) S[rr * pitch + (int)(x - al)] = p[x];
-  }
-}
-
 template <int MODE>
 __global__ __launch_bounds__(256) void scene_stitch_maps(MapArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint4 Mq[];      // T * maxp pieces of staging; the byte image of the tile lies over it at the end
   const float* S = reinterpret_cast<const float*>(Mq);
   const int tid = threadIdx.x, Ch = a.Ch, PH = a.PH, PW = a.PW, T = a.T, maxp = a.maxp, pitch = maxp * 4;
-  const MapGroup& w = a.g[blockIdx.y];
+  const StitchGroup& w = a.g[blockIdx.y];
   const int tiles_x = (PW + T - 1) / T;
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int i0 = w.r0 + ty * T, j0 = w.c0 + tx * T;
@@ -727,33 +774,22 @@ __global__ __launch_bounds__(256) void scene_stitch_maps(MapArgs a) {
     pk[m] = 0;
 #pragma unroll
     for (int n = 0; n < NA; ++n) acc[m][n] = 0u;
-    if (e < items) {
-      const int px = MODE ? e : e / Ch, c = MODE ? 0 : e - px * Ch, ti = px / tw, tj = px - ti * tw;
-      pk[m] = (ti << 16) | (tj << 8) | c;
-    }
+    if (e < items) pk[m] = sv_pack(e, MODE ? 1 : Ch, tw);      // mode 1: c = 0, the pixel's first channel
   }
   const long long group = a.first + (long long)blockIdx.y;
   for (int k = 0; k < a.K; ++k) {
-    const int code = (int)(w.codes >> (3 * k)) & 7;
-    const bool tr = code == 1 || code == 5 || code == 6 || code == 7;
-    const bool fr = code == 2 || code == 3 || code == 5 || code == 7;
-    const bool fc = code == 1 || code == 2 || code == 4 || code == 7;
-    // the tile in the view, as scene_stitch_views finds it: va rows of vb pixels at (a0, b0)
-    const int x0 = fr ? PH - i0 - th : i0, y0 = fc ? PW - j0 - tw : j0;
-    const int a0 = tr ? y0 : x0, b0 = tr ? x0 : y0, va = tr ? tw : th, vb = tr ? th : tw;
+    const Sym y{(int)(w.codes >> (3 * k)) & 7};
+    const bool tr = y.tr(), fr = y.fr(), fc = y.fc();
+    const ViewTile vt = view_tile(tr, fr, fc, PH, PW, i0, j0, th, tw);
     const long long vbase = (group * a.K + k) * PH * PW;
     __syncthreads();                           // the last view's reads of S are done
-    sm_stage(Mq, a.p, a.total, vbase, a0, b0, va, vb * Ch, PW, Ch, maxp, tid);
+    sv_stage(Mq, a.p, a.total, vbase, vt.a0, vt.b0, vt.va, vt.vb * Ch, PW, Ch, maxp, tid);
     __syncthreads();
-    const unsigned pb = (unsigned)vbase + (unsigned)(a0 * PW + b0);
+    const unsigned pb = (unsigned)vbase + (unsigned)(vt.a0 * PW + vt.b0);
 #pragma unroll
     for (int m = 0; m < NS; ++m) {
       if (tid + 256 * m < items) {
-        const int ti = pk[m] >> 16, tj = (pk[m] >> 8) & 255, c = pk[m] & 255;
-        const int xl = fr ? th - 1 - ti : ti, yl = fc ? tw - 1 - tj : tj;
-        const int ra = tr ? yl : xl, cb = tr ? xl : yl;
-        const int phase = (int)(((pb + (unsigned)(ra * PW)) * (unsigned)Ch) & 3u);
-        const float* v = S + ra * pitch + phase + cb * Ch + c;
+        const float* v = S + sv_at(tr, fr, fc, sv_unpack(pk[m]), th, tw, pb, PW, Ch, pitch);
         if (MODE == 0) {
           acc[m][0] += sm_q16(v[0]);           // at most 8 * 65536
         } else {
@@ -774,8 +810,8 @@ __global__ __launch_bounds__(256) void scene_stitch_maps(MapArgs a) {
 #pragma unroll
   for (int m = 0; m < NS; ++m) {
     if (tid + 256 * m < items) {
-      const int ti = pk[m] >> 16, tj = (pk[m] >> 8) & 255, c = pk[m] & 255;
-      uint8_t* d = B + ti * bp + (int)((o0 + (unsigned)ti * ostep) & 3u) + tj * Ch + c;
+      const TileItem it = sv_unpack(pk[m]);
+      uint8_t* d = B + it.ti * bp + (int)((o0 + (unsigned)it.ti * ostep) & 3u) + it.tj * Ch + it.c;
       if (MODE == 0) {
         d[0] = (uint8_t)((255u * acc[m][0] + K * 32768u) / (K * 65536u));   // below 2^27 + 2^18
       } else {
@@ -811,53 +847,23 @@ extern "C" int rua_scene_stitch_maps(const float* p, int G, int K, int PH, int P
   RUA_CHECK_ARG(mode == 0 || Ch == 3, "rua_scene_stitch_maps: mode 1 (hsv_rgb) reads H, S, V: Ch 3, got %d", Ch);
   RUA_CHECK_ARG(PH >= 1 && PW >= 1 && PH <= SW_MAXP && PW <= SW_MAXP, "rua_scene_stitch_maps: PH %d, PW %d (1 <= PH, PW <= 512)", PH, PW);
   RUA_CHECK_ARG(((uintptr_t)p & 15) == 0, "rua_scene_stitch_maps: p must be 16-byte aligned");
-  for (int s = 0; s < nscenes; ++s) {
-    RUA_CHECK_ARG(scene_out[s], "rua_scene_stitch_maps: scene %d: null pointer", s);
-    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] * Ch < ((int64_t)1 << 40),
-                  "rua_scene_stitch_maps: scene %d: size %d x %d x %d", s, scene_h[s], scene_w[s], Ch);
-  }
-  for (int g = 0; g < G; ++g) {
-    const int32_t* t0 = windows + 4 * (size_t)g * K;
-    const int32_t* o = own + 4 * (size_t)g;
-    for (int v = 0; v < K; ++v) {
-      const int32_t* t = t0 + 4 * v;
-      const int k = g * K + v, s = t[0], r = t[1], c = t[2], code = t[3];
-      RUA_CHECK_ARG(s >= 0 && s < nscenes, "rua_scene_stitch_maps: row %d: scene %d outside 0..%d", k, s, nscenes - 1);
-      RUA_CHECK_ARG(r >= 0 && c >= 0 && (int64_t)r + PH <= scene_h[s] && (int64_t)c + PW <= scene_w[s],
-                    "rua_scene_stitch_maps: row %d: window (%d, %d) + %d x %d leaves its %d x %d scene", k, r, c, PH, PW, scene_h[s], scene_w[s]);
-      RUA_CHECK_ARG(s == t0[0] && r == t0[1] && c == t0[2],
-                    "rua_scene_stitch_maps: row %d: scene %d, window (%d, %d), but its group %d is scene %d, window (%d, %d)",
-                    k, s, r, c, g, t0[0], t0[1], t0[2]);
-      RUA_CHECK_ARG(code >= 0 && code <= 7, "rua_scene_stitch_maps: row %d: code %d outside 0..7", k, code);
-      RUA_CHECK_ARG(PH == PW || !(code == 1 || code >= 5),
-                    "rua_scene_stitch_maps: row %d: code %d transposes and needs a square patch (got %d x %d)", k, code, PH, PW);
-    }
-    RUA_CHECK_ARG(0 <= o[0] && o[0] <= o[1] && o[1] <= PH && 0 <= o[2] && o[2] <= o[3] && o[3] <= PW,
-                  "rua_scene_stitch_maps: group %d: owned rows %d..%d, columns %d..%d outside the %d x %d window", g, o[0], o[1], o[2], o[3], PH, PW);
-  }
+  SC_TRY(check_scene_list("rua_scene_stitch_maps", scene_out, nullptr, scene_h, scene_w, nscenes, Ch, true));
+  SC_TRY(check_groups("rua_scene_stitch_maps", windows, own, G, K, PH, PW, scene_h, scene_w, nscenes));
   hipStream_t st = (hipStream_t)stream;
   MapArgs a;
   memset(&a, 0, sizeof(a));
   a.p = p;
   a.total = (long long)G * K * PH * PW * Ch;
   a.PH = PH; a.PW = PW; a.Ch = Ch; a.K = K;
-  a.T = 32;
-  while (a.T * a.T * Ch > SV_ACCF) a.T -= 4;                   // as rua_scene_stitch_views; Ch = 3 (mode 1): 32
-  a.maxp = ((a.T * Ch + 6) / 4) | 1;
+  tile_of(Ch, a.T, a.maxp);                                    // Ch = 3 (mode 1): 32
   const int blocks = ((PH + a.T - 1) / a.T) * ((PW + a.T - 1) / a.T);
   const size_t lds = (size_t)a.T * a.maxp * 16;                // 17 KiB at most (Ch = 4: 32 x 33 pieces); the byte image, T rows of at most T * Ch + 6 bytes, fits in it
   for (int g0 = 0; g0 < G; g0 += SM_CHUNK) {
     const int ng = G - g0 < SM_CHUNK ? G - g0 : SM_CHUNK;
     for (int g = 0; g < ng; ++g) {
       const int32_t* t = windows + 4 * (size_t)(g0 + g) * K;
-      const int32_t* o = own + 4 * (size_t)(g0 + g);
       const int s = t[0];
-      MapGroup& w = a.g[g];
-      w.out = scene_out[s] + ((size_t)t[1] * scene_w[s] + t[2]) * Ch;
-      w.W = scene_w[s];
-      w.r0 = (uint16_t)o[0]; w.r1 = (uint16_t)o[1]; w.c0 = (uint16_t)o[2]; w.c1 = (uint16_t)o[3];
-      w.codes = 0;
-      for (int v = 0; v < K; ++v) w.codes |= (uint32_t)t[4 * v + 3] << (3 * v);
+      fill_group(a.g[g], t, own + 4 * (size_t)(g0 + g), K, scene_out[s], nullptr, scene_w[s], Ch);
     }
     a.first = g0;
     if (mode) hipLaunchKernelGGL(scene_stitch_maps<1>, dim3(blocks, ng), dim3(256), lds, st, a);
@@ -969,21 +975,8 @@ extern "C" int rua_scene_class_counts(const uint8_t* const* scene_cls, const int
   RUA_CHECK_ARG(C >= 1 && C <= SC_MAXC, "rua_scene_class_counts: C %d outside 1..64", C);
   RUA_CHECK_ARG(PH >= 1 && PW >= 1 && PH <= SW_MAXP && PW <= SW_MAXP, "rua_scene_class_counts: PH %d, PW %d (1 <= PH, PW <= 512)", PH, PW);
   RUA_CHECK_ARG(((uintptr_t)counts & 3) == 0, "rua_scene_class_counts: counts must be 4-byte aligned");
-  for (int s = 0; s < nscenes; ++s) {
-    RUA_CHECK_ARG(scene_cls[s], "rua_scene_class_counts: scene %d: null pointer", s);
-    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] < ((int64_t)1 << 40),
-                  "rua_scene_class_counts: scene %d: size %d x %d", s, scene_h[s], scene_w[s]);
-  }
-  for (int k = 0; k < N; ++k) {
-    const int32_t* t = windows + 4 * (size_t)k;
-    const int s = t[0], r = t[1], c = t[2], code = t[3];
-    RUA_CHECK_ARG(s >= 0 && s < nscenes, "rua_scene_class_counts: row %d: scene %d outside 0..%d", k, s, nscenes - 1);
-    RUA_CHECK_ARG(r >= 0 && c >= 0 && (int64_t)r + PH <= scene_h[s] && (int64_t)c + PW <= scene_w[s],
-                  "rua_scene_class_counts: row %d: window (%d, %d) + %d x %d leaves its %d x %d scene", k, r, c, PH, PW, scene_h[s], scene_w[s]);
-    RUA_CHECK_ARG(code >= 0 && code <= 7, "rua_scene_class_counts: row %d: code %d outside 0..7", k, code);
-    RUA_CHECK_ARG(PH == PW || !(code == 1 || code >= 5), "rua_scene_class_counts: row %d: code %d transposes and needs a square patch (got %d x %d)",
-                  k, code, PH, PW);
-  }
+  SC_TRY(check_scene_list("rua_scene_class_counts", scene_cls, nullptr, scene_h, scene_w, nscenes, 1));
+  SC_TRY(check_window_rows("rua_scene_class_counts", windows, N, PH, PW, scene_h, scene_w, nscenes));
   // the bands add into their window's cells: zeroed here, on the same stream, so the call overwrites
   const int rc = rua_fill_zero(counts, (int64_t)N * (C + 1) * (int64_t)sizeof(int32_t), stream);
   if (rc != RUA_OK) return rc;
@@ -1178,9 +1171,7 @@ extern "C" int rua_scene_erode(const uint8_t* const* scene_cls, const int32_t* s
     RUA_CHECK_ARG(((uintptr_t)confusion & 7) == 0, "rua_scene_erode: confusion must be 8-byte aligned");
   }
   for (int s = 0; s < nscenes; ++s) {
-    RUA_CHECK_ARG(scene_cls[s] && (!scene_out || scene_out[s]) && (!scene_pred || scene_pred[s]), "rua_scene_erode: scene %d: null pointer", s);
-    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] < ((int64_t)1 << 40),
-                  "rua_scene_erode: scene %d: size %d x %d", s, scene_h[s], scene_w[s]);
+    SC_TRY(check_scene("rua_scene_erode", s, scene_cls[s] && (!scene_out || scene_out[s]) && (!scene_pred || scene_pred[s]), scene_h[s], scene_w[s], 1));
     RUA_CHECK_ARG(!scene_out || scene_out[s] != scene_cls[s], "rua_scene_erode: scene %d: scene_out is scene_cls (an erosion in place would read its own output)", s);
   }
   hipStream_t st = (hipStream_t)stream;
@@ -1402,10 +1393,8 @@ extern "C" int rua_scene_boundary(const uint8_t* const* scene_cls, const uint8_t
   RUA_CHECK_ARG(bound_cls || bound_pred || counts, "rua_scene_boundary: nothing to do: give bound_cls, bound_pred or counts");
   RUA_CHECK_ARG(((uintptr_t)counts & 7) == 0, "rua_scene_boundary: counts must be 8-byte aligned");
   for (int s = 0; s < nscenes; ++s) {
-    RUA_CHECK_ARG(scene_cls[s] && scene_pred[s] && (!bound_cls || bound_cls[s]) && (!bound_pred || bound_pred[s]),
-                  "rua_scene_boundary: scene %d: null pointer", s);
-    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && (int64_t)scene_h[s] * scene_w[s] < ((int64_t)1 << 40),
-                  "rua_scene_boundary: scene %d: size %d x %d", s, scene_h[s], scene_w[s]);
+    SC_TRY(check_scene("rua_scene_boundary", s, scene_cls[s] && scene_pred[s] && (!bound_cls || bound_cls[s]) && (!bound_pred || bound_pred[s]),
+                       scene_h[s], scene_w[s], 1));
     const int64_t n = (int64_t)scene_h[s] * scene_w[s];
     uint8_t* const bc = bound_cls ? bound_cls[s] : nullptr;
     uint8_t* const bp = bound_pred ? bound_pred[s] : nullptr;

@@ -133,27 +133,67 @@ def window_table(shapes: Sequence[Sequence[int]], patch, stride: int, data_aug: 
     return np.concatenate(parts) if parts else np.zeros((0, 4), np.int32)
 
 
+def _is_table4(a: np.ndarray) -> bool:
+    return a.ndim == 2 and a.shape[1] == 4 and bool(np.issubdtype(a.dtype, np.integer))
+
+
+def _window_table(table) -> np.ndarray:
+    t = np.asarray(table)
+    if not _is_table4(t):
+        raise ValueError(f"a window table is an integer [N][4] array of (scene, row, col, code) rows, got {t.dtype} {t.shape}")
+    return t
+
+
+def _two_tables(fn: str, rows, own, code: str):
+    t, o = np.asarray(rows), np.asarray(own)
+    for a, what in ((t, f"(scene, row, col, {code})"), (o, "(r0, r1, c0, c1)")):
+        if not _is_table4(a):
+            raise ValueError(f"{fn} takes integer [N][4] arrays of {what} rows, got {a.dtype} {a.shape}")
+    return t, o
+
+
+def _check_rows(fn: str, shapes, rows: list, ph: int, pw: int, own: Optional[list] = None, K: int = 1, views=None, code0: bool = False):
+    """csrc/scene.hip's row checks (check_window_rows, check_groups) in their order and words, spoken as `fn`: `rows` in groups of K
+    views with an `own` row each (None: none).  code0: rua_scene_stitch's rule, its groups are "rows"; views: the codes of a group."""
+    n = len(shapes)
+    for g in range(len(rows) // K):
+        s0, ra, ca, _ = rows[g * K]
+        for v in range(K):
+            k = g * K + v
+            s, r, c, code = rows[k]
+            if not 0 <= s < n:
+                raise ValueError(f"{fn}: row {k}: scene {s} outside 0..{n - 1}")
+            H, W = int(shapes[s][0]), int(shapes[s][1])
+            if r < 0 or c < 0 or r + ph > H or c + pw > W:
+                raise ValueError(f"{fn}: row {k}: window ({r}, {c}) + {ph} x {pw} leaves its {H} x {W} scene")
+            if (s, r, c) != (s0, ra, ca):
+                raise ValueError(f"{fn}: row {k}: scene {s}, window ({r}, {c}), but its group {g} is scene {s0}, window ({ra}, {ca})")
+            if code0:
+                if code != 0:
+                    raise ValueError(f"{fn}: row {k}: code {code} (a prediction window is cut as it is: code 0)")
+                continue
+            if not 0 <= code < NUM_CODES:
+                raise ValueError(f"{fn}: row {k}: code {code} outside 0..7")
+            if ph != pw and code in TRANSPOSING:
+                raise ValueError(f"{fn}: row {k}: code {code} transposes and needs a square patch (got {ph} x {pw})")
+            if views is not None and code != views[v]:
+                raise ValueError(f"{fn}: row {k}: code {code}, but view {v} of {views} is code {views[v]}")
+        if own is not None:
+            r0, r1, c0, c1 = own[g]
+            if not (0 <= r0 <= r1 <= ph and 0 <= c0 <= c1 <= pw):
+                raise ValueError(f"{fn}: {'row' if code0 else 'group'} {g}: owned rows {r0}..{r1}, columns {c0}..{c1} outside the {ph} x {pw} window")
+
+
 def check_table(shapes: Sequence[Sequence[int]], table: np.ndarray, patch) -> np.ndarray:
     """The table as a contiguous int32 [N][4] array; ValueError, in rua_scene_windows' own words, for the first bad row."""
     ph, pw = _patch2(patch)
-    t = np.asarray(table)
-    if t.ndim != 2 or t.shape[1] != 4 or not np.issubdtype(t.dtype, np.integer):
-        raise ValueError(f"a window table is an integer [N][4] array of (scene, row, col, code) rows, got {t.dtype} {t.shape}")
+    t = _window_table(table)
     n = len(shapes)
     if n < 1 or t.shape[0] < 1:
         raise ValueError(f"rua_scene_windows: nscenes {n}, N {t.shape[0]} (both >= 1)")
     if not (1 <= ph <= MAX_PATCH and 1 <= pw <= MAX_PATCH):
         raise ValueError(f"rua_scene_windows: PH {ph}, PW {pw} (1 <= PH, PW <= 512)")
-    for k, (s, r, c, code) in enumerate(t.tolist()):
-        if not 0 <= s < n:
-            raise ValueError(f"rua_scene_windows: row {k}: scene {s} outside 0..{n - 1}")
-        H, W = int(shapes[s][0]), int(shapes[s][1])
-        if r < 0 or c < 0 or r + ph > H or c + pw > W:
-            raise ValueError(f"rua_scene_windows: row {k}: window ({r}, {c}) + {ph} x {pw} leaves its {H} x {W} scene")
-        if not 0 <= code < NUM_CODES:
-            raise ValueError(f"rua_scene_windows: row {k}: code {code} outside 0..7")
-        if ph != pw and code in TRANSPOSING:
-            raise ValueError(f"rua_scene_windows: row {k}: code {code} transposes and needs a square patch (got {ph} x {pw})")
+    _check_rows("rua_scene_windows", shapes, t.tolist(), ph, pw)
     return np.ascontiguousarray(t, dtype=np.int32)
 
 
@@ -244,10 +284,7 @@ def affine_rows(rows4: np.ndarray, patch, rotate_deg=0.0, zoom=1.0, shift_q16=(0
     M = (1 / zoom) R(theta) S(code), a = rint(65536 M); the origin puts the patch centre on the window centre (+ shift).  With no
     rotation, zoom 1 and no shift host_windows_affine of the result is host_windows of rows4, bit for bit."""
     ph, pw = _patch2(patch)
-    r4 = np.asarray(rows4)
-    if r4.ndim != 2 or r4.shape[1] != 4 or not np.issubdtype(r4.dtype, np.integer):
-        raise ValueError(f"a window table is an integer [N][4] array of (scene, row, col, code) rows, got {r4.dtype} {r4.shape}")
-    r4 = r4.astype(np.int64)
+    r4 = _window_table(rows4).astype(np.int64)
     N, code = len(r4), r4[:, 3]
     bad = np.flatnonzero((code < 0) | (code >= NUM_CODES))
     if bad.size:
@@ -318,10 +355,7 @@ def predict_table(shape_hw: Sequence[int], patch, stride: int):
 def check_own(shapes: Sequence[Sequence[int]], rows: np.ndarray, own: np.ndarray, patch, num_classes: int = 1):
     """(rows, own) as contiguous int32 [N][4] arrays; ValueError, in rua_scene_stitch's own words, for the first violation."""
     ph, pw = _patch2(patch)
-    t, o = np.asarray(rows), np.asarray(own)
-    for a, what in ((t, "(scene, row, col, 0)"), (o, "(r0, r1, c0, c1)")):
-        if a.ndim != 2 or a.shape[1] != 4 or not np.issubdtype(a.dtype, np.integer):
-            raise ValueError(f"rua_scene_stitch takes integer [N][4] arrays of {what} rows, got {a.dtype} {a.shape}")
+    t, o = _two_tables("rua_scene_stitch", rows, own, "0")
     n = len(shapes)
     if n < 1 or t.shape[0] < 1 or o.shape[0] != t.shape[0]:
         raise ValueError(f"rua_scene_stitch: nscenes {n}, N {t.shape[0]} windows, {o.shape[0]} ownership rows (both >= 1, one per window)")
@@ -329,16 +363,7 @@ def check_own(shapes: Sequence[Sequence[int]], rows: np.ndarray, own: np.ndarray
         raise ValueError(f"rua_scene_stitch: PH {ph}, PW {pw} (1 <= PH, PW <= 512)")
     if not 1 <= num_classes <= MAX_CLASSES:
         raise ValueError(f"rua_scene_stitch: C {num_classes} outside 1..64")
-    for k, ((s, r, c, code), (r0, r1, c0, c1)) in enumerate(zip(t.tolist(), o.tolist())):
-        if not 0 <= s < n:
-            raise ValueError(f"rua_scene_stitch: row {k}: scene {s} outside 0..{n - 1}")
-        H, W = int(shapes[s][0]), int(shapes[s][1])
-        if r < 0 or c < 0 or r + ph > H or c + pw > W:
-            raise ValueError(f"rua_scene_stitch: row {k}: window ({r}, {c}) + {ph} x {pw} leaves its {H} x {W} scene")
-        if code != 0:
-            raise ValueError(f"rua_scene_stitch: row {k}: code {code} (a prediction window is cut as it is: code 0)")
-        if not (0 <= r0 <= r1 <= ph and 0 <= c0 <= c1 <= pw):
-            raise ValueError(f"rua_scene_stitch: row {k}: owned rows {r0}..{r1}, columns {c0}..{c1} outside the {ph} x {pw} window")
+    _check_rows("rua_scene_stitch", shapes, t.tolist(), ph, pw, own=o.tolist(), code0=True)
     return np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(o, dtype=np.int32)
 
 
@@ -356,15 +381,22 @@ def host_stitch(p: np.ndarray, rows: np.ndarray, own: np.ndarray, shapes: Sequen
     if C != p.shape[3]:
         raise ValueError(f"p holds {p.shape[3]} classes, num_classes is {C}")
     t, o = check_own(shapes, rows, own, p.shape[1:3], C)
+    return _score_groups(t, o, 1, shapes, class_maps, C, fill, lambda k, r0, r1, c0, c1: p[k, r0:r1, c0:c1])
+
+
+def _score_groups(t, o, K: int, shapes, class_maps, C: int, fill: int, values):
+    """The map-and-matrix half of host_stitch and host_stitch_views: the arg-max of values(g, r0, r1, c0, c1), group g's
+    [r1 - r0][c1 - c0][C] array, goes to the scene maps (unowned: `fill`) and into the confusion matrix (None without class maps)."""
     maps = [np.full((int(h), int(w)), fill, np.uint8) for h, w in shapes]
     cm = None if class_maps is None else np.zeros((C, C), np.int64)
-    for k, ((s, r, c, _), (r0, r1, c0, c1)) in enumerate(zip(t.tolist(), o.tolist())):
+    for g, (r0, r1, c0, c1) in enumerate(o.tolist()):
         if r0 == r1 or c0 == c1:
             continue
-        pred = np.argmax(p[k, r0:r1, c0:c1], axis=-1)
-        maps[s][r + r0:r + r1, c + c0:c + c1] = pred
+        s, row, col, _ = t[g * K].tolist()
+        pred = np.argmax(values(g, r0, r1, c0, c1), axis=-1)
+        maps[s][row + r0:row + r1, col + c0:col + c1] = pred
         if cm is not None:
-            true = np.asarray(class_maps[s])[r + r0:r + r1, c + c0:c + c1].astype(np.int64)
+            true = np.asarray(class_maps[s])[row + r0:row + r1, col + c0:col + c1].astype(np.int64)
             keep = true < C
             cm += np.bincount(true[keep] * C + pred[keep], minlength=C * C).reshape(C, C)
     return maps, cm
@@ -408,9 +440,7 @@ def check_views(views, patch=None) -> Tuple[int, ...]:
 def view_rows(rows: np.ndarray, views) -> np.ndarray:
     """int32 [G*K][4]: rows g*K .. g*K+K-1 repeat row g of the code-0 table `rows` [G][4] with the codes of `views`, in that order."""
     v = check_views(views)
-    r = np.asarray(rows)
-    if r.ndim != 2 or r.shape[1] != 4 or not np.issubdtype(r.dtype, np.integer):
-        raise ValueError(f"a window table is an integer [N][4] array of (scene, row, col, code) rows, got {r.dtype} {r.shape}")
+    r = _window_table(rows)
     out = np.repeat(r.astype(np.int32), len(v), axis=0)
     out[:, 3] = np.tile(np.asarray(v, np.int32), len(r))
     return out
@@ -420,10 +450,7 @@ def check_view_table(shapes: Sequence[Sequence[int]], rows: np.ndarray, own: np.
     """(rows [G*K][4], own [G][4], K) as contiguous int32 arrays; ValueError, in rua_scene_stitch_views' own words, for the first
     violation.  views_or_K: K, or the views every group must carry in order (then check_views applies to them too)."""
     ph, pw = _patch2(patch)
-    t, o = np.asarray(rows), np.asarray(own)
-    for a, what in ((t, "(scene, row, col, code)"), (o, "(r0, r1, c0, c1)")):
-        if a.ndim != 2 or a.shape[1] != 4 or not np.issubdtype(a.dtype, np.integer):
-            raise ValueError(f"rua_scene_stitch_views takes integer [N][4] arrays of {what} rows, got {a.dtype} {a.shape}")
+    t, o = _two_tables("rua_scene_stitch_views", rows, own, "code")
     views = None
     if isinstance(views_or_K, (int, np.integer)) and not isinstance(views_or_K, bool):
         K = int(views_or_K)
@@ -441,27 +468,7 @@ def check_view_table(shapes: Sequence[Sequence[int]], rows: np.ndarray, own: np.
         raise ValueError(f"rua_scene_stitch_views: C {num_classes} outside 1..64")
     if not (1 <= ph <= MAX_PATCH and 1 <= pw <= MAX_PATCH):
         raise ValueError(f"rua_scene_stitch_views: PH {ph}, PW {pw} (1 <= PH, PW <= 512)")
-    tl = t.tolist()
-    for g, (r0, r1, c0, c1) in enumerate(o.tolist()):
-        s0, ra, ca, _ = tl[g * K]
-        for v in range(K):
-            k = g * K + v
-            s, r, c, code = tl[k]
-            if not 0 <= s < n:
-                raise ValueError(f"rua_scene_stitch_views: row {k}: scene {s} outside 0..{n - 1}")
-            H, W = int(shapes[s][0]), int(shapes[s][1])
-            if r < 0 or c < 0 or r + ph > H or c + pw > W:
-                raise ValueError(f"rua_scene_stitch_views: row {k}: window ({r}, {c}) + {ph} x {pw} leaves its {H} x {W} scene")
-            if (s, r, c) != (s0, ra, ca):
-                raise ValueError(f"rua_scene_stitch_views: row {k}: scene {s}, window ({r}, {c}), but its group {g} is scene {s0}, window ({ra}, {ca})")
-            if not 0 <= code < NUM_CODES:
-                raise ValueError(f"rua_scene_stitch_views: row {k}: code {code} outside 0..7")
-            if ph != pw and code in TRANSPOSING:
-                raise ValueError(f"rua_scene_stitch_views: row {k}: code {code} transposes and needs a square patch (got {ph} x {pw})")
-            if views is not None and code != views[v]:
-                raise ValueError(f"rua_scene_stitch_views: row {k}: code {code}, but view {v} of {views} is code {views[v]}")
-        if not (0 <= r0 <= r1 <= ph and 0 <= c0 <= c1 <= pw):
-            raise ValueError(f"rua_scene_stitch_views: group {g}: owned rows {r0}..{r1}, columns {c0}..{c1} outside the {ph} x {pw} window")
+    _check_rows("rua_scene_stitch_views", shapes, t.tolist(), ph, pw, own=o.tolist(), K=K, views=views)
     return np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(o, dtype=np.int32), K
 
 
@@ -484,24 +491,16 @@ def host_stitch_views(p: np.ndarray, rows: np.ndarray, own: np.ndarray, shapes: 
     if C != p.shape[3]:
         raise ValueError(f"p holds {p.shape[3]} classes, num_classes is {C}")
     t, o, K = check_view_table(shapes, r, o, len(r) // len(o), p.shape[1:3], C)
-    maps = [np.full((int(h), int(w)), fill, np.uint8) for h, w in shapes]
-    cm = None if class_maps is None else np.zeros((C, C), np.int64)
-    for g, (r0, r1, c0, c1) in enumerate(o.tolist()):
-        if r0 == r1 or c0 == c1:
-            continue
-        s, row, col, _ = t[g * K].tolist()
+
+    def summed(g, r0, r1, c0, c1):
         acc = None
         for k in range(K):
             q = transform(p[g * K + k], INVERSE[int(t[g * K + k, 3])])[r0:r1, c0:c1]
             acc = q.astype(np.float32, copy=True) if acc is None else acc + q
         assert acc.dtype == np.float32
-        pred = np.argmax(acc, axis=-1)
-        maps[s][row + r0:row + r1, col + c0:col + c1] = pred
-        if cm is not None:
-            true = np.asarray(class_maps[s])[row + r0:row + r1, col + c0:col + c1].astype(np.int64)
-            keep = true < C
-            cm += np.bincount(true[keep] * C + pred[keep], minlength=C * C).reshape(C, C)
-    return maps, cm
+        return acc
+
+    return _score_groups(t, o, K, shapes, class_maps, C, fill, summed)
 
 
 # ---- whole-scene maps of any head: the window outputs under K views, turned back, averaged and quantised to uint8 ---------------

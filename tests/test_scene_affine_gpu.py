@@ -3,7 +3,6 @@ and, without a jitter, against rua_scene_windows; the engine's buffers after _up
 _upload_compact fed with its host() arrays; the Keras-style surface against the compact path on the same patches; the CLI with
 --random_aug yes."""
 import ctypes
-import json
 import os
 import subprocess
 import sys
@@ -15,17 +14,12 @@ import torch
 from resunet_a_mltsk_keras_amd import _lib as L
 from resunet_a_mltsk_keras_amd import scenes
 
+from _scene_util import GUARD, HEADS, NCLS as C, assert_same, blob_pool, blob_scene, make_scenes, new_engine, new_training_model, read_scalars, state
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADS = ["seg", "bound", "dist", "color"]
-GUARD = 4096                                                 # bytes behind each output that must come back untouched
 Q = 65536
-
-
-def make_scenes(rng, shapes, Cin):
-    return ([rng.integers(0, 256, (H, W, Cin)).astype(np.uint8) for H, W in shapes],
-            [rng.integers(0, 256, (H, W)).astype(np.uint8) for H, W in shapes])
 
 
 def run_windows(name, images, maps, table, PH, PW, image_only=False):
@@ -45,12 +39,6 @@ def run_windows(name, images, maps, table, PH, PW, image_only=False):
     assert (gi[ni:] == 0xA5).all(), "bytes behind img_out were written"
     assert (gc[nc if not image_only else 0:] == 0x5A).all(), "bytes behind cls_out were written (or cls_out in the image-only form)"
     return gi[:ni].reshape(N, PH, PW, Cin), (None if image_only else gc[:nc].reshape(N, PH, PW))
-
-
-def assert_same(got, want, table, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (what, len(bad), "first at", tuple(bad[0]), "table row", table[bad[0][0]].tolist())
 
 
 def affine_table(rng, shapes, PH, PW, N):
@@ -113,21 +101,6 @@ def test_affine_rows_without_jitter_equal_scene_windows(PH, PW, codes, Cin):
 
 
 # ---- engine / model level -----------------------------------------------------------------------------------------------------
-SHAPE, C = (64, 64, 3), 4
-
-
-def blob_scene(seed, H=150, W=171):
-    """An image with pure hues and a grey pixel, a blocky class map with speckle (as tests/test_scenes_gpu.py builds its scenes)."""
-    rng = np.random.default_rng(seed)
-    img = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
-    img[::17, ::13] = [255, 0, 0]
-    img[5::19, 3::11] = [7, 7, 7]
-    f = rng.integers(0, C, (H // 8 + 2, W // 8 + 2))
-    cls = np.kron(f, np.ones((8, 8), np.int64))[:H, :W]
-    cls[rng.random(cls.shape) < 0.01] = int(rng.integers(0, C))
-    return img, cls.astype(np.uint8)
-
-
 def affine_batch(pool, seed, B=2, nscenes=2):
     """B windows anywhere in the scenes (borders included), each under its own rotation, zoom in [0.5, 2] and shift of up to 20 px."""
     rng = np.random.default_rng(seed)
@@ -140,16 +113,7 @@ def affine_batch(pool, seed, B=2, nscenes=2):
 
 @pytest.fixture(scope="module")
 def pool():
-    sc = [blob_scene(100), blob_scene(101)]
-    return scenes.ScenePool([s[0] for s in sc], [s[1] for s in sc], patch=64)
-
-
-def new_engine(multitask, seed=7):
-    from resunet_a_mltsk_keras_amd.engine import Engine, LossSpec, ModelConfig
-    heads = HEADS if multitask else ["seg"]
-    eng = Engine(ModelConfig(input_shape=SHAPE, num_classes=C, multitasking=multitask), dtype="f32", seed=seed, split_k=False)
-    eng.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in heads}, weight={h: 1.0 for h in heads}))
-    return eng
+    return blob_pool()
 
 
 @pytest.mark.parametrize("multitask", [True, False])
@@ -175,23 +139,6 @@ def test_engine_buffers_hold_the_compact_paths_bytes(pool, multitask):
             got = [g.x_in.t] + [h["y"].t for h in g.heads]
             for w, v in zip(want, got):
                 assert torch.equal(w.view(torch.int32), v.view(torch.int32)), (training, norm_type)
-
-
-def new_model(use_graph, seed=3):
-    from multitasking_utils import Tanimoto_dual_loss
-    from resunet_a_mltsk_keras_amd.engine import ModelConfig
-    from resunet_a_mltsk_keras_amd.keras_api import Adam, Model
-    m = Model(ModelConfig(input_shape=SHAPE, num_classes=C, multitasking=True), dtype="f32", seed=seed)
-    m.engine.split_k = False
-    m.engine.use_graph = use_graph
-    loss = Tanimoto_dual_loss()
-    m.compile(optimizer=Adam(lr=1e-3, beta_1=0.9), loss={h: loss for h in HEADS}, loss_weights={h: 1.0 for h in HEADS},
-              metrics={"seg": ["accuracy"]})
-    return m
-
-
-def state(m):
-    return np.concatenate([m.engine.P.detach().cpu().numpy().ravel(), m.engine.S.detach().cpu().numpy().ravel()])
 
 
 def run_sequence(m, pool, scene_input):
@@ -226,17 +173,12 @@ def compare_with_twins(twins, cand, what):
 
 @pytest.mark.parametrize("use_graph", [True, False])
 def test_model_affine_batches_train_like_compact_batches(pool, use_graph):
-    twins = [run_sequence(new_model(use_graph), pool, False) for _ in range(3)]
-    cand = run_sequence(new_model(use_graph), pool, True)
+    twins = [run_sequence(new_training_model(use_graph), pool, False) for _ in range(3)]
+    cand = run_sequence(new_training_model(use_graph), pool, True)
     compare_with_twins(twins, cand, f"use_graph={use_graph}")
 
 
 # ---- CLI --------------------------------------------------------------------------------------------------------------------------
-def read_scalars(path):
-    with open(path) as f:
-        return [json.loads(l) for l in f]
-
-
 def run_cli(results, dataset, extra):
     cmd = [sys.executable, os.path.join(ROOT, "train_ISPRS.py"), "--resunet_a", "yes", "--multitasking", "yes", "--loss", "tanimoto", "-rp", results,
            "-dp", dataset, "-bs", "4", "-ps", "64", "--num_classes", str(C), "--epochs", "2", "--dtype", "f32", "--norm_type", "1", "--seed", "5",

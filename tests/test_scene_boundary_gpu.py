@@ -14,12 +14,12 @@ import torch
 from resunet_a_mltsk_keras_amd import _lib as L
 from resunet_a_mltsk_keras_amd import scenes
 
+from _scene_util import FILL, NCLS, blob_scene, guarded_maps, new_model
+
 pytestmark = pytest.mark.gpu
 
 TILE_H, TILE_W = 32, 128                                     # csrc/scene.hip: SB_TH, SB_TW
 CHUNK = 96                                                   # csrc/scene.hip: SB_CHUNK, scenes per launch
-GUARD = 4096                                                 # bytes behind each boundary map that must come back untouched
-FILL = 0xEE
 CNT_GUARD = 64                                               # int64 cells behind the counts
 RADII = [0, 1, 2, 3, 7, 16]
 # one call: a single pixel, a flat and a tall sliver, a scene smaller than every radius from 3 on in both directions, and one that
@@ -63,7 +63,7 @@ def run_boundary(maps, preds, r, C, want=ALL, expect_error=None, nscenes=None, t
     shapes = [m.shape for m in maps]
     cls = [torch.from_numpy(np.ascontiguousarray(m)).to(dev) for m in maps]
     prd = cls if same else [torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in preds]
-    outs = {k: [torch.full((H * W + GUARD,), FILL, dtype=torch.uint8, device=dev) for H, W in shapes] for k in ("cls", "pred")}
+    outs = {k: guarded_maps(shapes) for k in ("cls", "pred")}
     cells = 4 * min(max(C, 1), 64)
     cnt0 = np.concatenate([cnt_pattern(cells // 4), np.full(CNT_GUARD, -7, np.int64)])
     cnt = torch.from_numpy(cnt0).to(dev)
@@ -319,28 +319,6 @@ def test_pool_counts_and_maps_equal_the_cpu_pools(five):
 
 
 # ---- 4. predict_scene(boundary=), as tests/test_scene_predict_gpu.py builds its model and scenes ---------------------------------
-SHAPE, NCLS = (64, 64, 3), 4
-
-
-def blob_scene(seed, H=150, W=171):
-    rng = np.random.default_rng(seed)
-    img = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
-    img[::17, ::13] = [255, 0, 0]
-    img[5::19, 3::11] = [7, 7, 7]
-    f = rng.integers(0, NCLS, (H // 8 + 2, W // 8 + 2))
-    cls = np.kron(f, np.ones((8, 8), np.int64))[:H, :W]
-    cls[rng.random(cls.shape) < 0.01] = int(rng.integers(0, NCLS))
-    return img, cls.astype(np.uint8)
-
-
-def new_model(seed=3, depth=6, split_k=False):
-    from resunet_a_mltsk_keras_amd.engine import ModelConfig
-    from resunet_a_mltsk_keras_amd.keras_api import Model
-    m = Model(ModelConfig(input_shape=SHAPE, num_classes=NCLS, multitasking=True, depth=depth), dtype="f32", seed=seed)
-    m.engine.split_k = split_k
-    return m
-
-
 @pytest.fixture(scope="module")
 def model_and_pool():
     sc = [blob_scene(200, 97, 113), blob_scene(201, 64, 80)]

@@ -12,11 +12,11 @@ import torch
 from resunet_a_mltsk_keras_amd import _lib as L
 from resunet_a_mltsk_keras_amd import scenes
 
+from _scene_util import FILL, NCLS, blob_scene, conf_pattern, guarded_maps, new_model
+
 pytestmark = pytest.mark.gpu
 
 TILE_H, TILE_W = 32, 256                                     # csrc/scene.hip: SE_TH, SE_TW
-GUARD = 4096                                                 # bytes behind each eroded map that must come back untouched
-FILL = 0xEE
 CONF_GUARD = 64                                              # int64 cells behind the matrix
 RADII = [0, 1, 2, 3, 7, 16]
 # one call: a single pixel, a flat and a tall sliver, a scene smaller than every radius from 3 on in both directions, and one that
@@ -34,10 +34,6 @@ def blocky(seed, H, W, C=5, region=16):
     return m
 
 
-def conf_pattern(C):
-    return (np.arange(C * C, dtype=np.int64).reshape(C, C) * 7 + 3) * (1 << 33) + 5      # non-zero in both halves of every cell
-
-
 def run_erode(maps, r, preds=None, C=0, out=True, expect_error=None, nscenes=None, tweak=None):
     """rua_scene_erode on these class maps: the eroded maps into FILL-ed buffers with a guard region behind each (out=False: no
     scene_out), the matrix (with preds) into a pre-filled one with guard cells behind it.  Calls twice: the maps must be identical
@@ -48,7 +44,7 @@ def run_erode(maps, r, preds=None, C=0, out=True, expect_error=None, nscenes=Non
     n = len(maps)
     shapes = [m.shape for m in maps]
     cls = [torch.from_numpy(np.ascontiguousarray(m)).to(dev) for m in maps]
-    outs = [torch.full((H * W + GUARD,), FILL, dtype=torch.uint8, device=dev) for H, W in shapes]
+    outs = guarded_maps(shapes)
     prd = None if preds is None else [torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in preds]
     cells = max(C, 1) ** 2
     conf0 = np.concatenate([conf_pattern(max(C, 1)).ravel(), np.full(CONF_GUARD, -7, np.int64)])
@@ -216,28 +212,6 @@ def test_pool_eroded_maps_equal_the_cpu_pools(five_maps):
 
 
 # ---- 5. predict_scene(erode=), as tests/test_scene_predict_gpu.py builds its model and scenes ----------------------------------
-SHAPE, NCLS = (64, 64, 3), 4
-
-
-def blob_scene(seed, H=150, W=171):
-    rng = np.random.default_rng(seed)
-    img = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
-    img[::17, ::13] = [255, 0, 0]
-    img[5::19, 3::11] = [7, 7, 7]
-    f = rng.integers(0, NCLS, (H // 8 + 2, W // 8 + 2))
-    cls = np.kron(f, np.ones((8, 8), np.int64))[:H, :W]
-    cls[rng.random(cls.shape) < 0.01] = int(rng.integers(0, NCLS))
-    return img, cls.astype(np.uint8)
-
-
-def new_model(seed=3, depth=6, split_k=False):
-    from resunet_a_mltsk_keras_amd.engine import ModelConfig
-    from resunet_a_mltsk_keras_amd.keras_api import Model
-    m = Model(ModelConfig(input_shape=SHAPE, num_classes=NCLS, multitasking=True, depth=depth), dtype="f32", seed=seed)
-    m.engine.split_k = split_k
-    return m
-
-
 def test_predict_scene_scores_on_the_eroded_ground_truth():
     sc = [blob_scene(200, 97, 113), blob_scene(201, 64, 80)]
     pool = scenes.ScenePool([s[0] for s in sc], [s[1] for s in sc], patch=64)

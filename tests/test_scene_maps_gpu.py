@@ -12,25 +12,15 @@ import torch
 from resunet_a_mltsk_keras_amd import _lib as L
 from resunet_a_mltsk_keras_amd import scenes
 
+from _scene_util import FILL, NCLS, blob_pool, blob_scene, guarded_maps, new_engine, new_model, read_guarded, table_of
+
 pytestmark = pytest.mark.gpu
 
-HEADS = ["seg", "bound", "dist", "color"]
 ALL_MAPS = ("seg", "bound", "dist", "color", "color_rgb")
-GUARD = 4096                                                 # bytes behind each scene map that must come back untouched
-FILL = 0xEE
 f32 = np.float32
 # quantise_q16's hard values: the clamps, NaN and the infinities, a subnormal, and exact halves (n + 0.5) / 65536 for even and odd n
 SPECIAL = np.array([0.0, 1.0, 1.5, -0.25, np.nan, np.inf, -np.inf, 2.0 ** -140]
                    + [(n + 0.5) / 65536 for n in (0, 1, 2, 3, 128, 129, 32767, 32768, 65534, 65535)], f32)
-
-
-def table_of(shapes, patch, stride):
-    parts = []
-    for s, shp in enumerate(shapes):
-        rows, own = scenes.predict_table(shp, patch, stride)
-        rows[:, 0] = s
-        parts.append((rows, own))
-    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
 
 
 def make_inputs(seed, G, codes, PH, PW, Ch, mode="plain"):
@@ -87,7 +77,7 @@ def run_maps(p, rows, own, shapes, K=None, Ch=None, mode=0, expect_error=None, p
     PH, PW = (PH, PW) if patch is None else patch
     n = len(shapes)
     pd = torch.from_numpy(np.ascontiguousarray(p)).to(dev)
-    out = [torch.full((H * W * Cp + GUARD,), FILL, dtype=torch.uint8, device=dev) for H, W in shapes]
+    out = guarded_maps(shapes, Cp)
     ptrs = (ctypes.c_void_p * n)(*[None if s == null_scene else t.data_ptr() for s, t in enumerate(out)])
     hw = shapes if sizes is None else sizes
     hs, ws = (ctypes.c_int32 * n)(*[h for h, _ in hw]), (ctypes.c_int32 * n)(*[w for _, w in hw])
@@ -101,10 +91,7 @@ def run_maps(p, rows, own, shapes, K=None, Ch=None, mode=0, expect_error=None, p
     else:
         L.lib().call("rua_scene_stitch_maps", *args)
     torch.cuda.synchronize()
-    got = [t.cpu().numpy() for t in out]
-    for g, (H, W) in zip(got, shapes):
-        assert (g[H * W * Cp:] == FILL).all(), "bytes behind a scene map were written"
-    maps = [g[:H * W * Cp].reshape(H, W, Cp) for g, (H, W) in zip(got, shapes)]
+    maps = read_guarded(out, shapes, Cp)
     if expect_error is not None:
         assert all((m == FILL).all() for m in maps), "a refused call wrote something"
     return maps
@@ -278,34 +265,9 @@ def test_stitch_maps_refuses_bad_arguments():
 
 
 # ---- engine / model level -------------------------------------------------------------------------------------------------
-SHAPE, NCLS = (64, 64, 3), 4
-
-
-def blob_scene(seed, H=150, W=171):
-    """As tests/test_scene_views_gpu.py builds its scenes: pure hues and a grey pixel, a blocky class map with speckle."""
-    rng = np.random.default_rng(seed)
-    img = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
-    img[::17, ::13] = [255, 0, 0]
-    img[5::19, 3::11] = [7, 7, 7]
-    f = rng.integers(0, NCLS, (H // 8 + 2, W // 8 + 2))
-    cls = np.kron(f, np.ones((8, 8), np.int64))[:H, :W]
-    cls[rng.random(cls.shape) < 0.01] = int(rng.integers(0, NCLS))
-    return img, cls.astype(np.uint8)
-
-
 @pytest.fixture(scope="module")
 def pool():
-    sc = [blob_scene(100), blob_scene(101, 128, 128)]
-    return scenes.ScenePool([s[0] for s in sc], [s[1] for s in sc], patch=64)
-
-
-def new_engine(multitask, use_graph, seed=7, shape=SHAPE, depth=6):
-    from resunet_a_mltsk_keras_amd.engine import Engine, LossSpec, ModelConfig
-    heads = HEADS if multitask else ["seg"]
-    eng = Engine(ModelConfig(input_shape=shape, num_classes=NCLS, multitasking=multitask, depth=depth), dtype="f32", seed=seed, split_k=False)
-    eng.use_graph = use_graph
-    eng.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in heads}, weight={h: 1.0 for h in heads}))
-    return eng
+    return blob_pool((128, 128))
 
 
 @pytest.mark.parametrize("use_graph", [True, False])
@@ -375,14 +337,6 @@ def test_predict_scene_heads_refusals(pool):
     with pytest.raises(ValueError, match="'seg' occurs twice"):
         multi.predict_scene(pool, 1, heads=("seg", "seg"))
     assert set(multi.predict_scene(pool, 1, stride=64, norm_type=2, heads=("color",))[2]) == {"color"}
-
-
-def new_model(seed=3, depth=6, split_k=False):
-    from resunet_a_mltsk_keras_amd.engine import ModelConfig
-    from resunet_a_mltsk_keras_amd.keras_api import Model
-    m = Model(ModelConfig(input_shape=SHAPE, num_classes=NCLS, multitasking=True, depth=depth), dtype="f32", seed=seed)
-    m.engine.split_k = split_k
-    return m
 
 
 def test_cli_writes_head_maps(tmp_path, capsys):

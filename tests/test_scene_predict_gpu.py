@@ -11,20 +11,9 @@ import torch
 from resunet_a_mltsk_keras_amd import _lib as L
 from resunet_a_mltsk_keras_amd import scenes
 
+from _scene_util import FILL, NCLS, blob_pool, blob_scene, conf_pattern, guarded_maps, new_engine, new_model, read_guarded, table_of
+
 pytestmark = pytest.mark.gpu
-
-HEADS = ["seg", "bound", "dist", "color"]
-GUARD = 4096                                                 # bytes behind each scene map that must come back untouched
-FILL = 0xEE
-
-
-def table_of(shapes, patch, stride):
-    parts = []
-    for s, shp in enumerate(shapes):
-        rows, own = scenes.predict_table(shp, patch, stride)
-        rows[:, 0] = s
-        parts.append((rows, own))
-    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
 
 
 def make_inputs(seed, shapes, N, PH, PW, C):
@@ -44,10 +33,6 @@ def make_inputs(seed, shapes, N, PH, PW, C):
     return p, maps
 
 
-def conf_pattern(C):
-    return (np.arange(C * C, dtype=np.int64).reshape(C, C) * 7 + 3) * (1 << 33) + 5      # non-zero in both halves of every cell
-
-
 def run_stitch(p, rows, own, shapes, class_maps, C=None, expect_error=None):
     """rua_scene_stitch into 0xEE-filled maps with a guard region behind each and a pre-filled confusion matrix; returns
     (maps, confusion - its initial pattern or None) and checks the guards.  expect_error: the call must fail with this text and
@@ -57,7 +42,7 @@ def run_stitch(p, rows, own, shapes, class_maps, C=None, expect_error=None):
     C = Cp if C is None else C
     n = len(shapes)
     pd = torch.from_numpy(np.ascontiguousarray(p)).to(dev)
-    pred = [torch.full((H * W + GUARD,), FILL, dtype=torch.uint8, device=dev) for H, W in shapes]
+    pred = guarded_maps(shapes)
     cls = None if class_maps is None else [torch.from_numpy(m).to(dev) for m in class_maps]
     conf0 = conf_pattern(C)
     conf = None if class_maps is None else torch.from_numpy(conf0).to(dev)
@@ -73,10 +58,7 @@ def run_stitch(p, rows, own, shapes, class_maps, C=None, expect_error=None):
     else:
         L.lib().call("rua_scene_stitch", *args)
     torch.cuda.synchronize()
-    got = [t.cpu().numpy() for t in pred]
-    for g, (H, W) in zip(got, shapes):
-        assert (g[H * W:] == FILL).all(), "bytes behind a scene map were written"
-    maps = [g[:H * W].reshape(H, W) for g, (H, W) in zip(got, shapes)]
+    maps = read_guarded(pred, shapes)
     cm = None if conf is None else conf.cpu().numpy() - conf0
     if expect_error is not None:
         assert all((m == FILL).all() for m in maps) and (cm is None or (cm == 0).all()), "a refused call wrote something"
@@ -174,35 +156,60 @@ def test_stitch_refuses_bad_arguments():
         scenes.host_stitch(p, rows, with_row(own, 3, 1, 33), shapes, maps)
 
 
+def test_every_table_entry_point_refuses_the_same_rows_in_the_same_words():
+    """The five table rules (scene out of range, window leaving its scene, code 9, a transposing code on a 16 x 48 patch, an owned
+    rectangle outside the window) through every entry point that takes a window table: the message is the shared text under the
+    entry point's own name, and nothing is written.  A rule an entry point does not have is skipped for it: rua_scene_stitch has
+    its own rule for the code, rua_scene_windows and rua_scene_class_counts take no ownership table."""
+    shapes, C, N = [(40, 57), (32, 32)], 5, 2
+    good, full = np.array([[0, 0, 0, 0], [1, 0, 0, 0]], np.int32), np.array([[0, 32, 0, 32]] * 2, np.int32)
+    # rule -> (PH, PW), rows, own, the text behind "NAME: " with the subject of an ownership row left open
+    rules = {
+        "scene": ((32, 32), [[0, 0, 0, 0], [2, 0, 0, 0]], full, "row 1: scene 2 outside 0..1"),
+        "leaves": ((32, 32), [[0, 0, 0, 0], [0, 0, 26, 0]], full, "row 1: window (0, 26) + 32 x 32 leaves its 40 x 57 scene"),
+        "code 9": ((32, 32), [[0, 0, 0, 0], [1, 0, 0, 9]], full, "row 1: code 9 outside 0..7"),
+        "transposing": ((16, 48), [[0, 0, 0, 0], [0, 3, 5, 6]], [[0, 16, 0, 48]] * 2, "row 1: code 6 transposes and needs a square patch (got 16 x 48)"),
+        "owned": ((32, 32), good, [[0, 32, 0, 32], [0, 33, 0, 32]], "{what} 1: owned rows 0..33, columns 0..32 outside the 32 x 32 window"),
+    }
+    has = {"rua_scene_windows": ("scene", "leaves", "code 9", "transposing"), "rua_scene_class_counts": ("scene", "leaves", "code 9", "transposing"),
+           "rua_scene_stitch": ("scene", "leaves", "owned"), "rua_scene_stitch_views": tuple(rules), "rua_scene_stitch_maps": tuple(rules)}
+    dev = torch.device("cuda")
+    n = len(shapes)
+    img = [torch.zeros((H, W, 3), dtype=torch.uint8, device=dev) for H, W in shapes]
+    cls = [torch.zeros((H, W), dtype=torch.uint8, device=dev) for H, W in shapes]
+    p = torch.zeros((N, 32, 32, C), dtype=torch.float32, device=dev)
+    outs = {k: torch.full((size,), FILL, dtype=torch.uint8, device=dev) for k, size in
+            (("img", N * 32 * 32 * 3), ("cls", N * 32 * 32), ("conf", C * C * 8), ("counts", N * (C + 1) * 4))}
+    maps = guarded_maps(shapes, C)                             # the widest scene map any of the five writes
+    ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+    hs, ws = (ctypes.c_int32 * n)(*[h for h, _ in shapes]), (ctypes.c_int32 * n)(*[w for _, w in shapes])
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    calls = 0
+    for name, mine in has.items():
+        for rule in mine:
+            (PH, PW), rows, own, text = rules[rule]
+            r, o = np.ascontiguousarray(rows, dtype=np.int32), np.ascontiguousarray(own, dtype=np.int32)
+            args = {
+                "rua_scene_windows": (ptrs(img), ptrs(cls), hs, ws, n, r.ctypes.data, N, PH, PW, 3, outs["img"].data_ptr(), outs["cls"].data_ptr(), stream),
+                "rua_scene_class_counts": (ptrs(cls), hs, ws, n, r.ctypes.data, N, PH, PW, C, outs["counts"].data_ptr(), stream),
+                "rua_scene_stitch": (p.data_ptr(), N, PH, PW, C, r.ctypes.data, o.ctypes.data, ptrs(maps), ptrs(cls), hs, ws, n, outs["conf"].data_ptr(), stream),
+                "rua_scene_stitch_views": (p.data_ptr(), N, 1, PH, PW, C, r.ctypes.data, o.ctypes.data, ptrs(maps), ptrs(cls), hs, ws, n,
+                                           outs["conf"].data_ptr(), stream),
+                "rua_scene_stitch_maps": (p.data_ptr(), N, 1, PH, PW, C, r.ctypes.data, o.ctypes.data, ptrs(maps), hs, ws, n, 0, stream),
+            }[name]
+            assert L.lib().raw(name)(*args) == -1, (name, rule)
+            want = name + ": " + text.format(what="row" if name == "rua_scene_stitch" else "group")
+            assert L.lib().dll.rua_last_error().decode() == want, (name, rule)
+            calls += 1
+    assert calls == 4 + 4 + 3 + 5 + 5
+    torch.cuda.synchronize()
+    assert all((t.cpu().numpy() == FILL).all() for t in list(outs.values()) + maps), "a refused call wrote something"
+
+
 # ---- engine / model level -------------------------------------------------------------------------------------------------
-SHAPE, NCLS = (64, 64, 3), 4
-
-
-def blob_scene(seed, H=150, W=171):
-    """As tests/test_scenes_gpu.py builds its scenes: pure hues and a grey pixel, a blocky class map with speckle."""
-    rng = np.random.default_rng(seed)
-    img = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
-    img[::17, ::13] = [255, 0, 0]
-    img[5::19, 3::11] = [7, 7, 7]
-    f = rng.integers(0, NCLS, (H // 8 + 2, W // 8 + 2))
-    cls = np.kron(f, np.ones((8, 8), np.int64))[:H, :W]
-    cls[rng.random(cls.shape) < 0.01] = int(rng.integers(0, NCLS))
-    return img, cls.astype(np.uint8)
-
-
 @pytest.fixture(scope="module")
 def pool():
-    sc = [blob_scene(100), blob_scene(101, 128, 128)]
-    return scenes.ScenePool([s[0] for s in sc], [s[1] for s in sc], patch=64)
-
-
-def new_engine(multitask, use_graph, seed=7):
-    from resunet_a_mltsk_keras_amd.engine import Engine, LossSpec, ModelConfig
-    heads = HEADS if multitask else ["seg"]
-    eng = Engine(ModelConfig(input_shape=SHAPE, num_classes=NCLS, multitasking=multitask), dtype="f32", seed=seed, split_k=False)
-    eng.use_graph = use_graph
-    eng.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in heads}, weight={h: 1.0 for h in heads}))
-    return eng
+    return blob_pool((128, 128))
 
 
 @pytest.mark.parametrize("use_graph", [True, False])
@@ -249,14 +256,6 @@ def test_predict_scene_without_class_maps_and_refusals(pool):
         eng.predict_scene(pool, 0, batch=0)
     with pytest.raises(ValueError, match="patch"):
         eng.predict_scene(scenes.ScenePool(pool.images, None, patch=32), 0)
-
-
-def new_model(seed=3, depth=6, split_k=False):
-    from resunet_a_mltsk_keras_amd.engine import ModelConfig
-    from resunet_a_mltsk_keras_amd.keras_api import Model
-    m = Model(ModelConfig(input_shape=SHAPE, num_classes=NCLS, multitasking=True, depth=depth), dtype="f32", seed=seed)
-    m.engine.split_k = split_k
-    return m
 
 
 def test_predict_scene_against_the_predict_route(pool):

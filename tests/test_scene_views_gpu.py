@@ -12,21 +12,11 @@ import torch
 from resunet_a_mltsk_keras_amd import _lib as L
 from resunet_a_mltsk_keras_amd import scenes
 
+from _scene_util import FILL, NCLS, blob_pool, blob_scene, conf_pattern, guarded_maps, new_engine, new_model, read_guarded, table_of
+
 pytestmark = pytest.mark.gpu
 
-HEADS = ["seg", "bound", "dist", "color"]
-GUARD = 4096                                                 # bytes behind each scene map that must come back untouched
-FILL = 0xEE
 E = np.float32(2.0 ** -24)
-
-
-def table_of(shapes, patch, stride):
-    parts = []
-    for s, shp in enumerate(shapes):
-        rows, own = scenes.predict_table(shp, patch, stride)
-        rows[:, 0] = s
-        parts.append((rows, own))
-    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
 
 
 def make_inputs(seed, shapes, G, codes, PH, PW, C):
@@ -78,10 +68,6 @@ def test_the_order_pattern_tells_orders_and_precisions_apart():
     assert (back[planted] == a[planted]).all()
 
 
-def conf_pattern(C):
-    return (np.arange(C * C, dtype=np.int64).reshape(C, C) * 7 + 3) * (1 << 33) + 5      # non-zero in both halves of every cell
-
-
 def run_stitch(p, rows, own, shapes, class_maps, K=None, C=None, expect_error=None, name="rua_scene_stitch_views"):
     """rua_scene_stitch_views (or, with name, rua_scene_stitch) into 0xEE-filled maps with a guard region behind each and a
     pre-filled confusion matrix; returns (maps, confusion - its initial pattern or None) and checks the guards.  expect_error: the
@@ -91,7 +77,7 @@ def run_stitch(p, rows, own, shapes, class_maps, K=None, C=None, expect_error=No
     C = Cp if C is None else C
     n = len(shapes)
     pd = torch.from_numpy(np.ascontiguousarray(p)).to(dev)
-    pred = [torch.full((H * W + GUARD,), FILL, dtype=torch.uint8, device=dev) for H, W in shapes]
+    pred = guarded_maps(shapes)
     cls = None if class_maps is None else [torch.from_numpy(m).to(dev) for m in class_maps]
     conf0 = conf_pattern(C)
     conf = None if class_maps is None else torch.from_numpy(conf0).to(dev)
@@ -112,10 +98,7 @@ def run_stitch(p, rows, own, shapes, class_maps, K=None, C=None, expect_error=No
     else:
         L.lib().call(name, *args)
     torch.cuda.synchronize()
-    got = [t.cpu().numpy() for t in pred]
-    for g, (H, W) in zip(got, shapes):
-        assert (g[H * W:] == FILL).all(), "bytes behind a scene map were written"
-    maps = [g[:H * W].reshape(H, W) for g, (H, W) in zip(got, shapes)]
+    maps = read_guarded(pred, shapes)
     cm = None if conf is None else conf.cpu().numpy() - conf0
     if expect_error is not None:
         assert all((m == FILL).all() for m in maps) and (cm is None or (cm == 0).all()), "a refused call wrote something"
@@ -266,34 +249,9 @@ def test_stitch_views_refuses_bad_arguments():
 
 
 # ---- engine / model level -------------------------------------------------------------------------------------------------
-SHAPE, NCLS = (64, 64, 3), 4
-
-
-def blob_scene(seed, H=150, W=171):
-    """As tests/test_scene_predict_gpu.py builds its scenes: pure hues and a grey pixel, a blocky class map with speckle."""
-    rng = np.random.default_rng(seed)
-    img = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
-    img[::17, ::13] = [255, 0, 0]
-    img[5::19, 3::11] = [7, 7, 7]
-    f = rng.integers(0, NCLS, (H // 8 + 2, W // 8 + 2))
-    cls = np.kron(f, np.ones((8, 8), np.int64))[:H, :W]
-    cls[rng.random(cls.shape) < 0.01] = int(rng.integers(0, NCLS))
-    return img, cls.astype(np.uint8)
-
-
 @pytest.fixture(scope="module")
 def pool():
-    sc = [blob_scene(100), blob_scene(101, 128, 128)]
-    return scenes.ScenePool([s[0] for s in sc], [s[1] for s in sc], patch=64)
-
-
-def new_engine(multitask, use_graph, seed=7, shape=SHAPE, depth=6):
-    from resunet_a_mltsk_keras_amd.engine import Engine, LossSpec, ModelConfig
-    heads = HEADS if multitask else ["seg"]
-    eng = Engine(ModelConfig(input_shape=shape, num_classes=NCLS, multitasking=multitask, depth=depth), dtype="f32", seed=seed, split_k=False)
-    eng.use_graph = use_graph
-    eng.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in heads}, weight={h: 1.0 for h in heads}))
-    return eng
+    return blob_pool((128, 128))
 
 
 @pytest.mark.parametrize("use_graph", [True, False])
@@ -356,14 +314,6 @@ def test_views_none_is_the_call_without_views_and_refusals(pool):
     fpool = scenes.ScenePool(pool.images, pool.class_maps, patch=(32, 64))
     with pytest.raises(ValueError, match=r"code 1 transposes and needs a square patch \(got 32 x 64\)"):
         flat.predict_scene(fpool, 1, views="aug5")
-
-
-def new_model(seed=3, depth=6, split_k=False):
-    from resunet_a_mltsk_keras_amd.engine import ModelConfig
-    from resunet_a_mltsk_keras_amd.keras_api import Model
-    m = Model(ModelConfig(input_shape=SHAPE, num_classes=NCLS, multitasking=True, depth=depth), dtype="f32", seed=seed)
-    m.engine.split_k = split_k
-    return m
 
 
 @pytest.mark.parametrize("views", ["flips", "all"])

@@ -138,6 +138,31 @@ def test_scene_windows_argument_validation_without_launch():
         scenes.ScenePool([np.zeros((40, 50, 3), np.uint8)], [np.zeros((40, 51), np.uint8)], device="cpu")
 
 
+def test_the_three_table_checkers_share_their_words():
+    """One bad table per row rule: check_table, check_own and check_view_table (those of them that have the rule) refuse it with
+    the same text under their own kernel's name - only an ownership row's subject differs, a "row" for rua_scene_stitch and a
+    "group" for rua_scene_stitch_views.  check_own has its own rule for the code, check_table takes no ownership table."""
+    shapes = [(40, 57), (32, 32)]
+    good, full = [[0, 0, 0, 0], [1, 0, 0, 0]], [[0, 32, 0, 32]] * 2
+    checkers = {"rua_scene_windows": lambda rows, own, patch: scenes.check_table(shapes, np.array(rows), patch),
+                "rua_scene_stitch": lambda rows, own, patch: scenes.check_own(shapes, np.array(rows), np.array(own), patch, 5),
+                "rua_scene_stitch_views": lambda rows, own, patch: scenes.check_view_table(shapes, np.array(rows), np.array(own), 1, patch, 5)}
+    for name, check in checkers.items():                       # the good table passes all three
+        check(good, full, 32)
+    rules = [((32, 32), [[0, 0, 0, 0], [2, 0, 0, 0]], full, "row 1: scene 2 outside 0..1", tuple(checkers)),
+             ((32, 32), [[0, 0, 0, 0], [0, 0, 26, 0]], full, "row 1: window (0, 26) + 32 x 32 leaves its 40 x 57 scene", tuple(checkers)),
+             ((32, 32), [[0, 0, 0, 0], [1, 0, 0, 9]], full, "row 1: code 9 outside 0..7", ("rua_scene_windows", "rua_scene_stitch_views")),
+             ((16, 48), [[0, 0, 0, 0], [0, 3, 5, 6]], [[0, 16, 0, 48]] * 2, "row 1: code 6 transposes and needs a square patch (got 16 x 48)",
+              ("rua_scene_windows", "rua_scene_stitch_views")),
+             ((32, 32), good, [[0, 32, 0, 32], [0, 33, 0, 32]], "{what} 1: owned rows 0..33, columns 0..32 outside the 32 x 32 window",
+              ("rua_scene_stitch", "rua_scene_stitch_views"))]
+    for patch, rows, own, text, who in rules:
+        for name in who:
+            with pytest.raises(ValueError) as exc:
+                checkers[name](rows, own, patch)
+            assert str(exc.value) == name + ": " + text.format(what="row" if name == "rua_scene_stitch" else "group"), (name, text)
+
+
 # ---- 4. converter, scene directories, materialize -----------------------------------------------------------------------------
 def test_converter_round_trip_and_scene_directories(tmp_path):
     rng = np.random.default_rng(4)

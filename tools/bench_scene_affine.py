@@ -25,7 +25,6 @@ import ctypes
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -33,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from bench_scenes import B, CIN, CLASSES, P, make_scene  # noqa: E402
+from _scene_bench import B, CIN, CLASSES, P, call_us, cfg3_model, clock_ms, make_scene  # noqa: E402
 
 STRIDE = 32                                                    # the CLI's default: --aug_shift defaults to half of it
 
@@ -48,17 +47,7 @@ def windows_us(pool, size, reps):
     cls_out = torch.empty((B, P, P), dtype=torch.uint8, device="cuda")
     nbytes = img_out.numel() + cls_out.numel()
 
-    def timed(fn):
-        for _ in range(5):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / reps
+    timed = lambda fn: call_us(fn, reps)
 
     def figure(name, t):
         t = np.ascontiguousarray(t, dtype=np.int32)
@@ -94,8 +83,8 @@ def main():
     import torch
     from multitasking_utils import Tanimoto_dual_loss
     from resunet_a_mltsk_keras_amd import scenes
-    from resunet_a_mltsk_keras_amd.engine import HEADS, ModelConfig
-    from resunet_a_mltsk_keras_amd.keras_api import Adam, Model
+    from resunet_a_mltsk_keras_amd.engine import HEADS
+    from resunet_a_mltsk_keras_amd.keras_api import Adam
     if not torch.cuda.is_available():
         sys.exit("bench_scene_affine.py needs a GPU")
     img, cls = make_scene(args.scene)
@@ -103,7 +92,7 @@ def main():
     wus = windows_us(pool, args.scene, args.reps)
     res = {"scene": [args.scene, args.scene, CIN], "windows_us": {"B": B, "patch": P, "reps": args.reps, **wus}}
 
-    m = Model(ModelConfig(input_shape=(P, P, CIN), num_classes=CLASSES, multitasking=True), dtype="bf16", seed=0)
+    m = cfg3_model()
     loss = Tanimoto_dual_loss()
     m.compile(optimizer=Adam(lr=1e-3, beta_1=0.9), loss={h: loss for h in HEADS}, loss_weights={h: 1.0 for h in HEADS},
               metrics={"seg": ["accuracy"]})
@@ -123,15 +112,7 @@ def main():
         m._sync_lr()
         m.engine.train_step(None, None)
 
-    def timed(fn):
-        for k in range(args.warmup):
-            fn(k)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for k in range(args.steps):
-            fn(k)
-        torch.cuda.synchronize()
-        return round((time.perf_counter() - t0) * 1e3 / args.steps, 3)
+    timed = lambda fn: round(clock_ms(fn, args.warmup, args.steps, takes_index=True)[0], 3)
 
     steps = {"scene": [], "affine": [], "resident": []}
     for _ in range(args.rounds):

@@ -31,16 +31,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CLASSES = 6
-B, P, CIN = 8, 256, 3
-
-
-def make_maps(size, seed=0):
-    rng = np.random.default_rng(seed)
-    f = rng.integers(0, CLASSES, (size // 16 + 1, size // 16 + 1), dtype=np.uint8)
-    blocky = np.ascontiguousarray(np.kron(f, np.ones((16, 16), np.uint8))[:size, :size])
-    noise = rng.integers(0, CLASSES, (size, size), dtype=np.uint8)
-    return {"blocky": blocky, "noise": noise, "uniform": np.full((size, size), 2, np.uint8)}
+from _scene_bench import B, CIN, CLASSES, P, cfg3_model, clock_ms, make_maps, median_row, rounds_ms  # noqa: E402
 
 
 def make_pred(m, seed):
@@ -55,24 +46,14 @@ def scene_rows(args):
     """predict_scene without and with boundary=3 on a seeded scene, and the host definition on the map it fetched."""
     import torch
     from resunet_a_mltsk_keras_amd import scenes
-    from resunet_a_mltsk_keras_amd.engine import ModelConfig
-    from resunet_a_mltsk_keras_amd.keras_api import Model
     S = args.net_scene
     rng = np.random.default_rng(0)
     img = rng.integers(0, 256, (S, S, CIN), dtype=np.uint8)
     cls = make_maps(S)["blocky"]
     pool = scenes.ScenePool([img], [cls], patch=P)
-    m = Model(ModelConfig(input_shape=(P, P, CIN), num_classes=CLASSES, multitasking=True), dtype="bf16", seed=0)
+    m = cfg3_model()
 
-    def timed(fn):
-        for _ in range(args.net_warmup):
-            fn()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.net_reps):
-            last = fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / args.net_reps, last
+    timed = lambda fn: clock_ms(fn, args.net_warmup, args.net_reps)
     plain, with_b = [], []
     for _ in range(args.rounds):
         t, _ = timed(lambda: m.predict_scene(pool, 0, stride=P, batch=B, norm_type=1))
@@ -127,21 +108,7 @@ def main():
     def erode(which):
         lib.call("rua_scene_erode", ptr1(cls[which]), hs, hs, 1, 3, ptr1(eroded), ptr1(prd[which]), CLASSES, conf.data_ptr(), stream)
 
-    def timed(fn):
-        for _ in range(2):
-            fn()
-        per_call = []
-        for _ in range(args.rounds):
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(args.reps):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            per_call.append(e0.elapsed_time(e1) / args.reps)
-        return {"ms_per_call": [round(v, 4) for v in per_call], "ms": round(float(np.median(per_call)), 4),
-                "spread_ms": round(max(per_call) - min(per_call), 4)}
+    timed = lambda fn: median_row(rounds_ms(fn, args.rounds, args.reps))
 
     res = {"scene": [S, S], "classes": CLASSES, "reps": args.reps, "rounds": args.rounds}
     for r in (0, 1, 3, 16):

@@ -27,15 +27,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-P, STRIDE, CLASSES = 256, 32, 6
+from _scene_bench import CLASSES, P, make_maps, rounds_ms  # noqa: E402
 
-
-def make_maps(size, seed=0):
-    rng = np.random.default_rng(seed)
-    f = rng.integers(0, CLASSES, (size // 16 + 1, size // 16 + 1), dtype=np.uint8)
-    blocky = np.ascontiguousarray(np.kron(f, np.ones((16, 16), np.uint8))[:size, :size])
-    noise = rng.integers(0, CLASSES, (size, size), dtype=np.uint8)
-    return {"blocky": blocky, "noise": noise, "uniform": np.full((size, size), 2, np.uint8)}
+STRIDE = 32
 
 
 def main():
@@ -65,20 +59,7 @@ def main():
         lib.call("rua_scene_class_counts", pool.cls_ptrs, pool.heights, pool.widths, len(pool), t.ctypes.data, len(t), P, P, CLASSES,
                  out.data_ptr(), ctypes.c_void_p(st.cuda_stream))
 
-    def timed(t, reps):
-        per_call = []
-        for _ in range(2):
-            call(t)
-        for _ in range(args.rounds):
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(reps):
-                call(t)
-            e1.record()
-            torch.cuda.synchronize()
-            per_call.append(e0.elapsed_time(e1) / reps)
-        return per_call
+    timed = lambda t, reps: rounds_ms(lambda: call(t), args.rounds, reps)
 
     def on(name, rows):
         t = rows.copy()

@@ -31,16 +31,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CLASSES = 6
+from _scene_bench import CLASSES, make_maps, median_row, rounds_ms  # noqa: E402
+
 HBM_BYTES_PER_MS = 6.3e9                                       # 6.3 TB/s
-
-
-def make_maps(size, seed=0):
-    rng = np.random.default_rng(seed)
-    f = rng.integers(0, CLASSES, (size // 16 + 1, size // 16 + 1), dtype=np.uint8)
-    blocky = np.ascontiguousarray(np.kron(f, np.ones((16, 16), np.uint8))[:size, :size])
-    noise = rng.integers(0, CLASSES, (size, size), dtype=np.uint8)
-    return {"blocky": blocky, "noise": noise, "uniform": np.full((size, size), 2, np.uint8)}
 
 
 def main():
@@ -76,20 +69,8 @@ def main():
                  CLASSES, conf.data_ptr() if with_pred else None, ctypes.c_void_p(st.cuda_stream))
 
     def timed(which, r, with_out, with_pred):
-        for _ in range(2):
-            call(which, r, with_out, with_pred)
-        per_call = []
-        for _ in range(args.rounds):
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(args.reps):
-                call(which, r, with_out, with_pred)
-            e1.record()
-            torch.cuda.synchronize()
-            per_call.append(e0.elapsed_time(e1) / args.reps)
-        ms = float(np.median(per_call))
-        row = {"ms_per_call": [round(v, 4) for v in per_call], "ms": round(ms, 4), "spread_ms": round(max(per_call) - min(per_call), 4)}
+        per_call = rounds_ms(lambda: call(which, r, with_out, with_pred), args.rounds, args.reps)
+        ms, row = float(np.median(per_call)), median_row(per_call)
         if r == 3:
             nbytes = (1 if which else n) * S * S * (1 + int(with_out) + int(with_pred))
             row.update(bytes=nbytes, GBps=round(nbytes / ms / 1e6, 1), floor_ms=round(nbytes / HBM_BYTES_PER_MS, 4),

@@ -26,23 +26,16 @@ import hashlib
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-B, P, CIN, CLASSES = 8, 256, 3, 6
+from _scene_bench import B, CIN, CLASSES, P, call_us, cfg3_model, clock_ms, make_scene  # noqa: E402
+
 ALL_HEADS = ("seg", "bound", "dist", "color", "color_rgb")
 VIEWS = ("none", "all")
-
-
-def make_scene(size, seed=0):
-    rng = np.random.default_rng(seed)
-    img = rng.integers(0, 256, (size, size, CIN), dtype=np.uint8)
-    f = rng.integers(0, CLASSES, (size // 16 + 1, size // 16 + 1), dtype=np.uint8)
-    return img, np.ascontiguousarray(np.kron(f, np.ones((16, 16), np.uint8))[:size, :size])
 
 
 def stitch_us(reps):
@@ -59,17 +52,7 @@ def stitch_us(reps):
     pred = torch.empty((size, size), dtype=torch.uint8, device="cuda")
     pp = ptr1(pred)
 
-    def timed(fn):
-        for _ in range(5):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / reps
+    timed = lambda fn: call_us(fn, reps)
 
     out = {}
     for name, ch, K, mode in (("plain_C6_K1", CLASSES, 1, 0), ("plain_C6_K8", CLASSES, 8, 0), ("hsv_rgb_C3_K1", 3, 1, 1)):
@@ -119,23 +102,15 @@ def main():
     args = ap.parse_args()
     import torch
     from resunet_a_mltsk_keras_amd import scenes
-    from resunet_a_mltsk_keras_amd.engine import ModelConfig
-    from resunet_a_mltsk_keras_amd.keras_api import Model
     if not torch.cuda.is_available():
         sys.exit("bench_scene_maps.py needs a GPU")
     img, cls = make_scene(args.scene)
     pool = scenes.ScenePool([img], [cls], patch=P)
-    m = Model(ModelConfig(input_shape=(P, P, CIN), num_classes=CLASSES, multitasking=True), dtype="bf16", seed=0)
+    m = cfg3_model()
 
     def timed(fn, warmup=args.warmup, reps=args.reps):
-        for _ in range(warmup):
-            fn()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            last = fn()
-        torch.cuda.synchronize()
-        return round((time.perf_counter() - t0) * 1e3 / reps, 2), last
+        ms, last = clock_ms(fn, warmup, reps)
+        return round(ms, 2), last
 
     base = {"scene": [args.scene, args.scene, CIN], "model": {"shape": [B, P, P, CIN], "classes": CLASSES, "dtype": "bf16", "path": "graph"},
             "stride": P, "windows": len(pool.predict_table(0, P)[0]), "warmup": args.warmup, "reps": args.reps, "rounds": args.rounds}

@@ -25,22 +25,15 @@ import ctypes
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-B, P, CIN, CLASSES = 8, 256, 3, 6
+from _scene_bench import B, CIN, CLASSES, P, call_us, cfg3_model, clock_ms, make_scene  # noqa: E402
+
 VARIANTS = ("none", "flips", "aug5", "all")
-
-
-def make_scene(size, seed=0):
-    rng = np.random.default_rng(seed)
-    img = rng.integers(0, 256, (size, size, CIN), dtype=np.uint8)
-    f = rng.integers(0, CLASSES, (size // 16 + 1, size // 16 + 1), dtype=np.uint8)
-    return img, np.ascontiguousarray(np.kron(f, np.ones((16, 16), np.uint8))[:size, :size])
 
 
 def stitch_us(reps):
@@ -59,17 +52,7 @@ def stitch_us(reps):
     own = np.array([[0, P, 0, P]] * B, np.int32)
     stream = ctypes.c_void_p(st.cuda_stream)
 
-    def timed(fn):
-        for _ in range(5):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / reps
+    timed = lambda fn: call_us(fn, reps)
 
     def figure(us, patches, windows):
         moved = patches * P * P * 4 * CLASSES + windows * P * P * 2          # the probabilities and the label read, the prediction written
@@ -104,23 +87,15 @@ def main():
     args = ap.parse_args()
     import torch
     from resunet_a_mltsk_keras_amd import scenes
-    from resunet_a_mltsk_keras_amd.engine import ModelConfig
-    from resunet_a_mltsk_keras_amd.keras_api import Model
     if not torch.cuda.is_available():
         sys.exit("bench_scene_views.py needs a GPU")
     img, cls = make_scene(args.scene)
     pool = scenes.ScenePool([img], [cls], patch=P)
-    m = Model(ModelConfig(input_shape=(P, P, CIN), num_classes=CLASSES, multitasking=True), dtype="bf16", seed=0)
+    m = cfg3_model()
 
     def timed(fn):
-        for _ in range(args.warmup):
-            fn()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.reps):
-            last = fn()
-        torch.cuda.synchronize()
-        return round((time.perf_counter() - t0) * 1e3 / args.reps, 2), last
+        ms, last = clock_ms(fn, args.warmup, args.reps)
+        return round(ms, 2), last
 
     windows = len(pool.predict_table(0, P)[0])
     ms, maps = {v: [] for v in VARIANTS}, {}

@@ -18,21 +18,13 @@ import ctypes
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-B, P, CIN, CLASSES = 8, 256, 3, 6
-
-
-def make_scene(size, seed=0):
-    rng = np.random.default_rng(seed)
-    img = rng.integers(0, 256, (size, size, CIN), dtype=np.uint8)
-    f = rng.integers(0, CLASSES, (size // 16 + 1, size // 16 + 1), dtype=np.uint8)
-    return img, np.ascontiguousarray(np.kron(f, np.ones((16, 16), np.uint8))[:size, :size])
+from _scene_bench import B, CIN, CLASSES, P, call_us, cfg3_model, clock_ms, make_scene  # noqa: E402
 
 
 def windows_us(pool, size, reps):
@@ -44,17 +36,7 @@ def windows_us(pool, size, reps):
     cls_out = torch.empty((B, P, P), dtype=torch.uint8, device="cuda")
     moved = 2 * (img_out.numel() + cls_out.numel())              # every byte is read once and written once
 
-    def timed(fn):
-        for _ in range(5):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / reps
+    timed = lambda fn: call_us(fn, reps)
 
     def figure(codes):
         t = np.array([[0, int(rng.integers(0, size - P + 1)), int(rng.integers(0, size - P + 1)), c] for c in codes], np.int32)
@@ -85,15 +67,15 @@ def main():
     import torch
     from multitasking_utils import Tanimoto_dual_loss
     from resunet_a_mltsk_keras_amd import scenes
-    from resunet_a_mltsk_keras_amd.engine import HEADS, ModelConfig
-    from resunet_a_mltsk_keras_amd.keras_api import Adam, Model
+    from resunet_a_mltsk_keras_amd.engine import HEADS
+    from resunet_a_mltsk_keras_amd.keras_api import Adam
     if not torch.cuda.is_available():
         sys.exit("bench_scenes.py needs a GPU")
     img, cls = make_scene(args.scene)
     pool = scenes.ScenePool([img], [cls], patch=P)
     res = {"scene": [args.scene, args.scene, CIN], "windows_us": {"B": B, "patch": P, "reps": args.reps, **windows_us(pool, args.scene, args.reps)}}
 
-    m = Model(ModelConfig(input_shape=(P, P, CIN), num_classes=CLASSES, multitasking=True), dtype="bf16", seed=0)
+    m = cfg3_model()
     loss = Tanimoto_dual_loss()
     m.compile(optimizer=Adam(lr=1e-3, beta_1=0.9), loss={h: loss for h in HEADS}, loss_weights={h: 1.0 for h in HEADS},
               metrics={"seg": ["accuracy"]})
@@ -114,15 +96,7 @@ def main():
         m._sync_lr()
         m.engine.train_step(None, None)
 
-    def timed(fn):
-        for k in range(args.warmup):
-            fn(k)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for k in range(args.steps):
-            fn(k)
-        torch.cuda.synchronize()
-        return round((time.perf_counter() - t0) * 1e3 / args.steps, 3)
+    timed = lambda fn: round(clock_ms(fn, args.warmup, args.steps, takes_index=True)[0], 3)
 
     steps = {"compact": [], "scene": [], "resident": []}
     for _ in range(args.rounds):

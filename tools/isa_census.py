@@ -1,12 +1,18 @@
 """Instruction census of the MFMA loops of a HIP source file (gfx950), from hipcc's own assembly.
 
     python3 tools/isa_census.py resunet_a_mltsk_keras_amd/csrc/conv_strip.hip [name-filter] [-D...] [--ops]
+    python3 tools/isa_census.py NEW.hip [name-filter] [-I...] --against OLD.hip
 
 For every kernel whose (demangled) name contains the filter, every innermost-first loop (a label .. the last
 backward branch to it) that holds MFMAs is listed with the STATIC count of its instructions by issue class:
 MFMA, VALU (everything else v_*), SALU (s_* without waits / nops / barriers / branches), LDS (ds_*), VMEM
 (buffer_* / global_*), wait (s_waitcnt, s_nop, s_barrier), branch.  Static = every path of the loop body once;
 bodies here are straight-line apart from uniform skips.  --ops adds the histogram of VALU mnemonics.
+
+--against OTHER.hip compiles both files and says, kernel by kernel, whether the instruction streams are the same (comments and
+directives stripped, block labels numbered in order of appearance), with the instruction count and the metadata's .vgpr_count,
+.sgpr_count, .group_segment_fixed_size (LDS) and .private_segment_fixed_size (scratch) of either file: what a refactor that
+means to leave a kernel alone has to show.
 """
 import collections
 import re
@@ -102,9 +108,65 @@ def census(body):
     return out
 
 
+def stream(body):
+    """The instructions of a function body: no comments, no directives, block labels renamed by first appearance."""
+    names, out = {}, []
+    for line in body:
+        s = line.split(";")[0].strip()
+        if not s or (s.startswith(".") and not re.match(r"^\.LBB\w+:", s)):
+            continue
+        out.append(re.sub(r"\.LBB\w+", lambda m: names.setdefault(m.group(0), "L%d" % len(names)), " ".join(s.split())))
+    return out
+
+
+META = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size")
+
+
+def metadata(text):
+    """{mangled kernel name: {key: int}} from the kernel entries of the amdhsa metadata."""
+    out, cur = {}, {}
+    for line in text.splitlines() + ["  - ."]:
+        if line.startswith("  - ."):
+            if ".name" in cur:
+                out[cur[".name"]] = cur
+            cur = {}
+            line = "    " + line[4:]
+        m = re.match(r"^    (\.\w+):\s+(\S+)\s*$", line)
+        if m:
+            cur[m.group(1)] = m.group(2)
+    return out
+
+
+def against(src, other, filt, defs):
+    sides = []
+    for f in (other, src):
+        text = asm_of(f, defs)
+        funcs = dict(functions(text))
+        names = demangle(list(funcs))
+        meta = metadata(text)
+        sides.append({names[f].replace("(anonymous namespace)::", "").split("(")[0]: (stream(b), meta.get(f, {})) for f, b in funcs.items() if f in meta})
+    old, new = sides
+    print("%-52s %-9s %13s %9s %9s %13s %9s" % ("kernel (old / new)", "identical", "instructions", "VGPR", "SGPR", "LDS", "scratch"))
+    for name in sorted(set(old) | set(new)):
+        if filt and filt not in name:
+            continue
+        (so, mo), (sn, mn) = old.get(name, ([], {})), new.get(name, ([], {}))
+        cols = ["%s / %s" % (mo.get("." + k, "-"), mn.get("." + k, "-")) for k in META]
+        print("%-52s %-9s %13s %9s %9s %13s %9s" % (name, "yes" if so == sn else "no",
+                                                   "%d / %d" % tuple(sum(not i.endswith(":") for i in x) for x in (so, sn)), *cols))
+
+
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("-")]
-    defs = [a for a in sys.argv[1:] if a.startswith("-") and a != "--ops"]
+    argv = sys.argv[1:]
+    other = None
+    if "--against" in argv:
+        i = argv.index("--against")
+        other = argv[i + 1]
+        del argv[i:i + 2]
+    args = [a for a in argv if not a.startswith("-")]
+    defs = [a for a in argv if a.startswith("-") and a != "--ops"]
+    if other:
+        return against(args[0], other, args[1] if len(args) > 1 else "", defs)
     show_ops = "--ops" in sys.argv
     src = args[0]
     filt = args[1] if len(args) > 1 else ""
