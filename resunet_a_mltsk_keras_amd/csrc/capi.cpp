@@ -56,6 +56,16 @@ extern "C" int rua_prof_event_elapsed_us(void* start, void* stop, double* us) {
   return RUA_OK;
 }
 extern "C" void rua_prof_event_destroy(void* ev) { (void)hipEventDestroy((hipEvent_t)ev); }
+// An event recorded BETWEEN the main kernel of a call and its second launch (split-K finisher, wgrad_taps_reduce, slab reduction), so that
+// per-kernel durations can be compared with rocprofv3's per-kernel-name averages.  One shot; the launchers of conv_mfma.hip, conv_img2.hip
+// (through rua_splitk_finish_bf16) and conv_wgrad.hip all record through rua_record_mid_event: ONE armed event per thread, not one per file.
+static thread_local hipEvent_t g_mid_event = nullptr;
+static thread_local int g_mid_fired = 0;
+extern "C" void rua_profile_mid_event(void* ev) { g_mid_event = (hipEvent_t)ev; if (ev) g_mid_fired = 0; }
+extern "C" int rua_profile_mid_event_fired(void) { return g_mid_fired; }     // 1: the call since the last arm had a second launch
+void rua_record_mid_event(hipStream_t st) {
+  if (g_mid_event) { (void)hipEventRecord(g_mid_event, st); g_mid_event = nullptr; g_mid_fired = 1; }
+}
 
 // Kernel nodes of a captured HIP graph (bench.py: dispatches per step of the whole-step graph, counted instead of read off a profile).
 extern "C" int rua_graph_kernel_nodes(void* graph, int* kernels, int* total) {

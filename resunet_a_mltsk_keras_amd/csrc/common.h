@@ -122,6 +122,7 @@ struct RuaTuning {
 extern RuaTuning g_tune;
 int rua_cu_count();          // compute units of the current device (queried once per device, cached)
 int rua_device_index();      // the calling thread's current HIP device
+void rua_record_mid_event(hipStream_t st);   // capi.cpp: fires the event armed by rua_profile_mid_event, in front of a call's second launch
 // "done once" flags of the launchers (hipFuncSetAttribute is per device): one flag per device, not per process - a process that drives
 // several devices (not this package's model: one process per GPU) would otherwise configure a kernel on the first device only
 struct RuaPerDevFlag { bool f[64] = {}; bool& get() { return f[rua_device_index() & 63]; } };
@@ -221,7 +222,7 @@ __device__ __forceinline__ void rua_fold_members(GetF&& getf, Has&& has, int nme
   __syncthreads();
 }
 
-// ---- kernel-side view of a rua_conv_desc (filled by rua_conv_fwd, shared by the conv kernels of conv_mfma.hip / conv_strip.hip)
+// ---- kernel-side view of a rua_conv_desc (filled by rua_conv_fwd, shared by the conv kernels of conv_mfma.hip / conv_strip.hip / conv_img2.hip)
 struct SegK { const unsigned char* x; const unsigned char* w; int C, Hs, Ws, up, dil, taps, nchunk, ubegin; unsigned xbytes, wbytes; };
 struct ConvK {
   SegK seg[RUA_MAX_SEG];

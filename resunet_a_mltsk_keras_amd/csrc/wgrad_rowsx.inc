@@ -1,4 +1,4 @@
-// wgrad_rowsx<MODE> (round 5; included by conv_mfma.hip behind wgrad_rows128): the whole-row weight gradient of wgrad_rows128 with its rows dealt as ONE stream.
+// wgrad_rowsx<MODE> (round 5; included by conv_wgrad.hip behind wgrad_rows128): the whole-row weight gradient of wgrad_rows128 with its rows dealt as ONE stream.
 //   MODE 0: C = Cout = 128 on 64-pixel rows (the level-3 ResBlock, model2.py:105-106) - wgrad_rows128's case;
 //   MODE 1: C = Cout = 256 on 32-pixel rows (the level-4 ResBlock at 32 x 32, model2.py:107-108; was wgrad_dmap: 128 x 128 tiles per TAP, 22 - 26 us per 9.66 GFLOP).
 // wgrad_rows128 walks (chain, segment) JOBS: a chain is the rows h = r, r + d, ... of one image (there the dilated 3x3 is a plain 3x3 over a sliding window of three

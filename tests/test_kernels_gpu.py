@@ -346,6 +346,63 @@ def _wgrad_all_taps(case):
 WGRAD_ROWS_DEFAULT = 127                                       # csrc/common.h: Tuning::wgrad_rows
 
 
+def test_profile_mid_event_fires_for_conv_and_wgrad():
+    """rua_profile_mid_event arms ONE event per thread for every launcher with a second launch: the split-K finisher of a forward convolution
+    (conv_mfma.hip) and the reduction of a weight gradient's block partials (conv_wgrad.hip) both fire it, a single-launch call leaves it armed.
+    (bench.py's per-kernel roofline splits a call's time at this event; a copy of the hook's state per translation unit would arm only one side.)"""
+    lib = L.lib()
+    dt = L.RUA_BF16
+    rng = np.random.default_rng(12)
+    arm, fired = lib.raw("rua_profile_mid_event"), lib.raw("rua_profile_mid_event_fired")
+    events = [C.c_void_p(lib.raw("rua_prof_event_create")()) for _ in range(3)]
+    assert all(e.value for e in events)
+    # forward: the bf16 case of test_conv_split_k_matches_single_pass
+    N, H, W, Cs, Cout = 2, 8, 8, 256, 128
+    xd = to_dev(rng.standard_normal((N, H, W, Cs)), dt)
+    wd = to_dev(rng.standard_normal((9, Cout, Cs)) / np.sqrt(9 * Cs), dt)
+    y = torch.empty((N, H, W, Cout), dtype=tdt(dt), device=dev())
+    ws = torch.zeros(16 * N * H * W * Cout + 1024, dtype=torch.float32, device=dev())
+    d = L.ConvDesc()
+    d.nseg = 1
+    s = d.seg[0]
+    s.x, s.w, s.C, s.Hs, s.Ws, s.up_shift, s.dil, s.taps = xd.data_ptr(), wd.data_ptr(), Cs, H, W, 0, 1, 9
+    d.N, d.H, d.W, d.Cout, d.stride, d.dtype = N, H, W, Cout, 1, dt
+    d.y, d.out_stride, d.OH, d.OW = y.data_ptr(), 1, H, W
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    # weight gradient: case (2, 64, 64, 32, 1) of test_wgrad_all_taps_kernel
+    Nw, Hw, Ww, Cc = 2, 64, 64, 32
+    ad, dyd = to_dev(rng.standard_normal((Nw, Hw, Ww, Cc)), dt), to_dev(rng.standard_normal((Nw, Hw, Ww, Cc)), dt)
+    dw = torch.zeros((9, Cc, Cc), dtype=torch.float32, device=dev())
+    wws = torch.empty(256 * 9 * 32 * Cc, dtype=torch.float32, device=dev())
+    g = L.WgradDesc()
+    g.a, g.C, g.Hs, g.Ws = ad.data_ptr(), Cc, Hw, Ww
+    g.dy, g.Cout, g.H, g.W = dyd.data_ptr(), Cc, Hw, Ww
+    g.N, g.stride, g.dil, g.taps, g.dtype = Nw, 1, 1, 9, dt
+    g.dw, g.workspace, g.workspace_bytes = dw.data_ptr(), wws.data_ptr(), wws.numel() * 4
+    assert lib.raw("rua_wgrad_kind")(C.byref(g)) == 1 and not g.defer
+    try:
+        arm(events[0])
+        lib.call("rua_conv_fwd", C.byref(d), stream())
+        torch.cuda.synchronize()
+        assert lib.raw("rua_conv_last_ksplit")() > 1
+        assert fired() == 1
+        arm(events[1])
+        lib.call("rua_conv_wgrad", C.byref(g), stream())
+        torch.cuda.synchronize()
+        assert fired() == 1
+        d.workspace, d.workspace_bytes = 0, 0                  # no K split: one launch, the event stays armed
+        arm(events[2])
+        lib.call("rua_conv_fwd", C.byref(d), stream())
+        torch.cuda.synchronize()
+        assert lib.raw("rua_conv_last_ksplit")() == 1
+        assert fired() == 0
+    finally:
+        arm(None)
+        torch.cuda.synchronize()
+        for e in events:
+            lib.raw("rua_prof_event_destroy")(e)
+
+
 @pytest.mark.parametrize("case", [(2, 64, 64, 128, 1), (1, 64, 64, 128, 15), (3, 40, 64, 128, 3), (8, 64, 64, 128, 31), (1, 7, 64, 128, 3),     # C = 128 on 64-pixel rows
                                   (8, 32, 32, 256, 1), (8, 32, 32, 256, 3), (8, 32, 32, 256, 15), (2, 32, 32, 256, 15), (4, 20, 32, 256, 16), (6, 48, 32, 256, 7),
                                   (2, 3, 32, 256, 1)])                                                                                            # C = 256 on 32-pixel rows, image pairs
