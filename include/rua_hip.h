@@ -416,6 +416,29 @@ int rua_head_dz(int kind, int act, const float* p, const float* y, const float* 
 /* out[5] += {#argmax matches, TP, FP, TN, FN at threshold .5} */
 int rua_seg_metrics(const float* p, const float* y, int64_t M, int C, double* out, void* stream);
 
+/* ---- void pixels: training on partly labelled patches -------------------------------------------------------------------------
+ * void_mask is a device uint8 [B*HW] array (one byte per sample and pixel, any alignment); a NON-ZERO byte marks a void pixel, one
+ * that is outside the training data.  void_mask == NULL: exactly the entry point without the suffix.  A void pixel is left out by
+ * select, never by a multiplication: p, z and y may hold NaN or Inf there and every result stays finite.
+ *   rua_tanimoto_sums_void   the six moments over the valid pixels of a sample, as if the void ones were cut out of the image;
+ *                            the finalisers need only the sums and are used unchanged
+ *   rua_head_fwd_loss_void   rua_head_fwd_loss_rep whose moments and counts leave the void pixels out; z and p are stored for every pixel
+ *   rua_pixel_loss_void      loss_out[0] += the sum over the VALID pixels; the caller still divides by M, the count of all pixels
+ *                            (Keras' sample_weight rule with 0 / 1 weights); per_pixel is 0 at a void pixel
+ *   rua_head_dz_void         dz is +0.0f in every class of a void pixel (written, not skipped); grad_scale as without the mask
+ *   rua_head_dz_multi_void   the same for n heads and ONE mask: the heads must agree in B and HW (RUA_ERR_ARG otherwise)
+ *   rua_seg_metrics_void     matches and TP / FP / TN / FN over the valid pixels: (TP + FP + TN + FN) / C is their number */
+int rua_tanimoto_sums_void(const float* p, const float* y, const uint8_t* void_mask, int B, int64_t HW, int C, double* sums, void* stream);
+int rua_head_fwd_loss_void(const void* x, const float* w, const float* b, float* z, float* p, const float* y, double* tanimoto_sums,
+                           int sums_replicas, double* metrics, int B, int64_t HW, int Cin, int Cout, int act, int dtype,
+                           const uint8_t* void_mask, void* stream);
+int rua_pixel_loss_void(int kind, const float* p, const float* z, const float* y, const float* class_w, const uint8_t* void_mask,
+                        int64_t M, int C, double* loss_out, float* per_pixel, void* stream);
+int rua_head_dz_void(int kind, int act, const float* p, const float* y, const float* coef, const float* class_w,
+                     float grad_scale, int B, int64_t HW, int C, const uint8_t* void_mask, float* dz, void* stream);
+int rua_head_dz_multi_void(const rua_dz_head* heads, int n, const uint8_t* void_mask, void* stream);
+int rua_seg_metrics_void(const float* p, const float* y, const uint8_t* void_mask, int64_t M, int C, double* out, void* stream);
+
 /* ---- optimizers on the flat parameter buffer (train_ISPRS.py:404-407) --------------------- */
 /* Keras Adam: theta -= lr_t * m / (sqrt(v) + eps); g is read as g*grad_scale and zeroed if zero_grad.
  * lr_t_dev (optional): device scalar overriding lr_t, so a captured HIP graph can be replayed every step */
@@ -444,6 +467,12 @@ int rua_sgd_step_w(float* theta, float* g, float* vel, int64_t n, float lr, cons
 int64_t rua_targets_scratch_bytes(int N, int num_classes);
 int rua_multitask_targets(const uint8_t* img, const uint8_t* cls, int N, int H, int W, int Cin, int num_classes, int norm_type,
                           float* x, float* seg, float* bound, float* dist, float* color, void* scratch, int64_t scratch_bytes, void* stream);
+/* The void mask of class-map patches (labels.host_void_mask, bit for bit): mask[n][i][j] = 255 if a pixel of patch n within Chebyshev
+ * distance `margin` of (i, j) has a class value >= num_classes, else 0.  Pixels outside the patch are not void and patches never leak
+ * into each other.  margin 0: mask = 255 * (cls >= num_classes).  cls and mask are device uint8 [N][H][W], any alignment, not overlapping.
+ * Limits: 1 <= H, W <= 512, 1 <= num_classes <= 255, 0 <= margin <= 16, 1 <= N <= 65535, N*H*W < 2^31 (RUA_ERR_ARG before any launch).
+ * One launch. */
+int rua_void_mask(const uint8_t* cls, int N, int H, int W, int num_classes, int margin, uint8_t* mask, void* stream);
 
 /* ---- training windows cut and augmented from resident scenes (scenes.py; the reference's preprocess_save_patches_ISPRS.py:28-48,
  * utils.py:69-95 done per step on the device) ------------------------------------------------------------------------------------

@@ -169,6 +169,13 @@ _SIGS = {
     "rua_sgd_step": ([vp, vp, vp, i64, f32, vp, f32, f32, i32, vp], i32),
     "rua_adam_step_w": ([vp, vp, vp, vp, i64, f32, vp, f32, f32, f32, f32, i32, vp, vp], i32),
     "rua_sgd_step_w": ([vp, vp, vp, i64, f32, vp, f32, f32, i32, vp, vp], i32),
+    "rua_tanimoto_sums_void": ([vp, vp, vp, i32, i64, i32, vp, vp], i32),
+    "rua_head_fwd_loss_void": ([vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i64, i32, i32, i32, i32, vp, vp], i32),
+    "rua_pixel_loss_void": ([i32, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp], i32),
+    "rua_head_dz_void": ([i32, i32, vp, vp, vp, vp, f32, i32, i64, i32, vp, vp, vp], i32),
+    "rua_head_dz_multi_void": ([vp, i32, vp, vp], i32),
+    "rua_seg_metrics_void": ([vp, vp, vp, i64, i32, vp, vp], i32),
+    "rua_void_mask": ([vp, i32, i32, i32, i32, i32, vp, vp], i32),
     "rua_targets_scratch_bytes": ([i32, i32], i64),
     "rua_multitask_targets": ([vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp], i32),
     "rua_scene_windows": ([vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp], i32),

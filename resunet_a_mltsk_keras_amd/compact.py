@@ -60,14 +60,21 @@ def image_to_u8(img: np.ndarray, norm_type: int) -> np.ndarray:
     return u8
 
 
-def seg_to_classes(seg: np.ndarray) -> np.ndarray:
-    """argmax of a one-hot label (ValueError if it is not one-hot)."""
-    if seg.ndim != 3 or seg.shape[-1] > 256 or not (((seg == 0) | (seg == 1)).all() and (seg.sum(-1) == 1).all()):
+def seg_to_classes(seg: np.ndarray, zero_rows_void: bool = False) -> np.ndarray:
+    """argmax of a one-hot label (ValueError if it is not one-hot).  zero_rows_void: an all-zero row - a pixel without a class - is
+    accepted and becomes 255 (C <= 255 then)."""
+    if seg.ndim != 3 or seg.shape[-1] > (255 if zero_rows_void else 256) or not ((seg == 0) | (seg == 1)).all():
         raise ValueError("labels/seg must be one-hot H x W x C with C <= 256")
-    return seg.argmax(-1).astype(np.uint8)
+    rows = seg.sum(-1)
+    if not ((rows == 1) | (rows == 0)).all() if zero_rows_void else not (rows == 1).all():
+        raise ValueError("labels/seg must be one-hot H x W x C with C <= 256")
+    cls = seg.argmax(-1).astype(np.uint8)
+    if zero_rows_void:
+        cls[rows == 0] = 255
+    return cls
 
 
-def convert(src: str, dst: str, norm_type: int) -> int:
+def convert(src: str, dst: str, norm_type: int, zero_rows_void: bool = False) -> int:
     """Reference layout -> compact layout, paired by file name; returns the number of patches written."""
     names = sorted(n for n in os.listdir(os.path.join(src, "train")) if n.endswith(".npy"))
     have = set(os.listdir(os.path.join(src, "labels", "seg")))
@@ -79,7 +86,7 @@ def convert(src: str, dst: str, norm_type: int) -> int:
     for n in names:
         try:
             img = image_to_u8(np.load(os.path.join(src, "train", n)), norm_type)
-            cls = seg_to_classes(np.load(os.path.join(src, "labels", "seg", n)))
+            cls = seg_to_classes(np.load(os.path.join(src, "labels", "seg", n)), zero_rows_void)
         except ValueError as exc:
             raise ValueError(f"{n}: {exc}") from None
         np.save(os.path.join(dst, "images", n), img)
@@ -92,8 +99,9 @@ def main(argv=None) -> int:
     p.add_argument("--src", required=True, help="dataset with train/ and labels/seg/")
     p.add_argument("--dst", required=True, help="output: images/ and labels/classes/")
     p.add_argument("--norm_type", type=int, default=1, choices=[1, 2])
+    p.add_argument("--zero_rows_void", action="store_true", help="accept all-zero label rows as class 255, 'no class' (default: refuse them)")
     a = p.parse_args(argv)
-    n = convert(a.src, a.dst, a.norm_type)
+    n = convert(a.src, a.dst, a.norm_type, a.zero_rows_void)
     print(f"{n} patches written to {a.dst}")
     return 0
 

@@ -15,8 +15,11 @@ __device__ __forceinline__ void block_atomic_add(double* dst, float v, float* sh
 
 // ---- Tanimoto with complement (multitasking_utils.py:38-85) ------------------------------
 // sums[n][c][6] = { sum p, sum (1-l), sum p*l, sum p^2+l^2, sum (1-p)(1-l), sum (1-p)^2+(1-l)^2 }
+// VM: void_mask[n * HW + i] != 0 takes pixel i of sample n out of every sum (by select: p and y may hold anything there), as if it were cut out
+// of the image; the unmasked instantiation is the code it was.
+template <bool VM>
 __global__ __launch_bounds__(256) void tanimoto_sums_kernel(const float* __restrict__ p, const float* __restrict__ y, long long HW, int C,
-                                                            int pix_per_block, double* sums) {
+                                                            int pix_per_block, double* sums, const uint8_t* __restrict__ vm) {
   __shared__ float sh[4 * 48];
   const int n = blockIdx.y;
   float acc[8][6];
@@ -27,6 +30,7 @@ __global__ __launch_bounds__(256) void tanimoto_sums_kernel(const float* __restr
   long long i = (long long)blockIdx.x * pix_per_block + threadIdx.x;
   long long iend = (long long)(blockIdx.x + 1) * pix_per_block; if (iend > HW) iend = HW;
   for (; i < iend; i += 256) {
+    if constexpr (VM) { if (vm[(size_t)n * HW + i]) continue; }
     const float* pp = p + ((size_t)n * HW + i) * C;
     const float* yy = y + ((size_t)n * HW + i) * C;
 #pragma unroll
@@ -59,9 +63,9 @@ __global__ __launch_bounds__(256) void tanimoto_sums_kernel(const float* __restr
 // Same sums with 16-byte loads for the class counts the reference's heads use: a thread takes G pixels (G * C floats = NV
 // float4) per iteration from each tensor, all loads issued before the first use; the class of every element is a
 // compile-time constant.  (The scalar kernel above streams at ~1.5 TB/s.)
-template <int C, int G>
+template <int C, int G, bool VM>
 __global__ __launch_bounds__(256) void tanimoto_sums_vec(const float* __restrict__ p, const float* __restrict__ y, long long HW,
-                                                         int groups_per_block, double* sums) {
+                                                         int groups_per_block, double* sums, const uint8_t* __restrict__ vm) {
   constexpr int NV = G * C / 4;
   static_assert(G * C % 4 == 0, "group must be whole float4s");
   __shared__ float sh[4 * 48];
@@ -80,12 +84,16 @@ __global__ __launch_bounds__(256) void tanimoto_sums_vec(const float* __restrict
     float4 a4[NV], l4[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) { a4[v] = pp[gi * NV + v]; l4[v] = yy[gi * NV + v]; }
+    bool vd[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) vd[g] = VM ? vm[(size_t)n * HW + gi * G + g] != 0 : false;      // (byte loads: the mask has no alignment)
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const float av[4] = {a4[v].x, a4[v].y, a4[v].z, a4[v].w}, lv[4] = {l4[v].x, l4[v].y, l4[v].z, l4[v].w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int c = (v * 4 + j) % C;
+        if (VM && vd[(v * 4 + j) / C]) continue;
         const float a = av[j], l = lv[j], q = 1.f - a, m = 1.f - l;
         acc[c][0] += a; acc[c][1] += m; acc[c][2] = fmaf(a, l, acc[c][2]);
         acc[c][3] += a * a + l * l; acc[c][4] = fmaf(q, m, acc[c][4]); acc[c][5] += q * q + m * m;
@@ -108,31 +116,36 @@ __global__ __launch_bounds__(256) void tanimoto_sums_vec(const float* __restrict
 }
 
 template <int C, int G>
-static void launch_tanimoto_vec(const float* p, const float* y, int B, int64_t HW, double* sums, hipStream_t st) {
+static void launch_tanimoto_vec(const float* p, const float* y, const uint8_t* vm, int B, int64_t HW, double* sums, hipStream_t st) {
   const int64_t ngroups = HW / G;
   int64_t gpb = (ngroups + 63) / 64; if (gpb < 256) gpb = 256;         // ~64 blocks per sample
   gpb = (gpb + 255) / 256 * 256;
   const int gx = (int)((ngroups + gpb - 1) / gpb);
-  hipLaunchKernelGGL((tanimoto_sums_vec<C, G>), dim3(gx, B), dim3(256), 0, st, p, y, (long long)HW, (int)gpb, sums);
+  if (vm) hipLaunchKernelGGL((tanimoto_sums_vec<C, G, true>), dim3(gx, B), dim3(256), 0, st, p, y, (long long)HW, (int)gpb, sums, vm);
+  else hipLaunchKernelGGL((tanimoto_sums_vec<C, G, false>), dim3(gx, B), dim3(256), 0, st, p, y, (long long)HW, (int)gpb, sums, vm);
 }
 
-extern "C" int rua_tanimoto_sums(const float* p, const float* y, int B, int64_t HW, int C, double* sums, void* stream) {
+extern "C" int rua_tanimoto_sums_void(const float* p, const float* y, const uint8_t* void_mask, int B, int64_t HW, int C, double* sums, void* stream) {
   RUA_CHECK_ARG(p && y && sums && B > 0 && HW > 0, "rua_tanimoto_sums: bad arguments");
   RUA_CHECK_ARG(C >= 1 && C <= 8, "rua_tanimoto_sums: C=%d must be in 1..8", C);
   const int vec_on = g_tune.tani_vec;
   if (vec_on && HW % 4 == 0 && ((size_t)p & 15) == 0 && ((size_t)y & 15) == 0 && (C == 6 || C == 3 || C == 2)) {
-    if (C == 6) launch_tanimoto_vec<6, 2>(p, y, B, HW, sums, (hipStream_t)stream);
-    else if (C == 3) launch_tanimoto_vec<3, 4>(p, y, B, HW, sums, (hipStream_t)stream);
-    else launch_tanimoto_vec<2, 2>(p, y, B, HW, sums, (hipStream_t)stream);
+    if (C == 6) launch_tanimoto_vec<6, 2>(p, y, void_mask, B, HW, sums, (hipStream_t)stream);
+    else if (C == 3) launch_tanimoto_vec<3, 4>(p, y, void_mask, B, HW, sums, (hipStream_t)stream);
+    else launch_tanimoto_vec<2, 2>(p, y, void_mask, B, HW, sums, (hipStream_t)stream);
     RUA_LAUNCH_CHECK("rua_tanimoto_sums");
     return RUA_OK;
   }
   int64_t ppb = (HW + 127) / 128; if (ppb < 1024) ppb = 1024;      // measured: 64..256 blocks per sample all ~17 us, 16: 21, 8: 35
   ppb = (ppb + 255) / 256 * 256;
   const int gx = (int)((HW + ppb - 1) / ppb);
-  hipLaunchKernelGGL(tanimoto_sums_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, p, y, (long long)HW, C, (int)ppb, sums);
+  if (void_mask) hipLaunchKernelGGL(tanimoto_sums_kernel<true>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, p, y, (long long)HW, C, (int)ppb, sums, void_mask);
+  else hipLaunchKernelGGL(tanimoto_sums_kernel<false>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, p, y, (long long)HW, C, (int)ppb, sums, void_mask);
   RUA_LAUNCH_CHECK("rua_tanimoto_sums");
   return RUA_OK;
+}
+extern "C" int rua_tanimoto_sums(const float* p, const float* y, int B, int64_t HW, int C, double* sums, void* stream) {
+  return rua_tanimoto_sums_void(p, y, nullptr, B, HW, C, sums, stream);
 }
 
 // One block.  Follows Tanimoto_dual_loss: loss1 = T(label:=pred, pred:=label) so the class weights of
@@ -270,13 +283,19 @@ extern "C" int rua_tanimoto_ratio(const double* sums, int B, int C, double* mean
 // ---- per-pixel losses (utils.py:481-490; Keras CategoricalCrossentropy / BinaryCrossentropy /
 // MeanSquaredError as train_ISPRS.py:411-428 selects them) -----------------------------------
 #define KERAS_EPS 1e-7f
+// VM: a void pixel adds nothing and its per_pixel entry is 0; the caller still divides by M, the count of ALL pixels (Keras' sample_weight rule with
+// 0 / 1 weights: grad_scale = weight / M stays a host constant)
+template <bool VM>
 __global__ __launch_bounds__(256) void pixel_loss_kernel(int kind, const float* __restrict__ p, const float* __restrict__ z,
                                                          const float* __restrict__ y, const float* __restrict__ cw,
-                                                         long long M, int C, double* out, float* per_pixel) {
+                                                         long long M, int C, double* out, float* per_pixel, const uint8_t* __restrict__ vm) {
   __shared__ float sh[4];
   float acc = 0.f;
   for (long long m = (long long)blockIdx.x * 256 + threadIdx.x; m < M; m += (long long)gridDim.x * 256) {
     float l = 0.f;
+    if constexpr (VM) {
+      if (vm[m]) { if (per_pixel) per_pixel[m] = 0.f; continue; }
+    }
     if (kind == RUA_LOSS_WCE) {
       float S = 0.f;
       for (int c = 0; c < C; ++c) S += p[m * C + c];
@@ -307,24 +326,30 @@ __global__ __launch_bounds__(256) void pixel_loss_kernel(int kind, const float* 
   block_atomic_add(out, acc, sh, 0);
 }
 
-extern "C" int rua_pixel_loss(int kind, const float* p, const float* z, const float* y, const float* class_w,
-                              int64_t M, int C, double* loss_out, float* per_pixel, void* stream) {
+extern "C" int rua_pixel_loss_void(int kind, const float* p, const float* z, const float* y, const float* class_w, const uint8_t* void_mask,
+                                   int64_t M, int C, double* loss_out, float* per_pixel, void* stream) {
   RUA_CHECK_ARG(p && y && loss_out && M > 0 && C >= 1 && C <= 64, "rua_pixel_loss: bad arguments");
   RUA_CHECK_ARG(kind >= RUA_LOSS_WCE && kind <= RUA_LOSS_MSE, "rua_pixel_loss: kind %d is not a per-pixel loss", kind);
   RUA_CHECK_ARG(kind != RUA_LOSS_WCE || class_w, "rua_pixel_loss: weighted CE needs class weights");
   RUA_CHECK_ARG((kind != RUA_LOSS_CE_LOGITS && kind != RUA_LOSS_BCE_LOGITS) || z, "rua_pixel_loss: logits needed");
   int64_t g = (M + 255) / 256; if (g > 1024) g = 1024;
-  hipLaunchKernelGGL(pixel_loss_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, kind, p, z, y, class_w, (long long)M, C, loss_out, per_pixel);
+  if (void_mask) hipLaunchKernelGGL(pixel_loss_kernel<true>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, kind, p, z, y, class_w, (long long)M, C, loss_out, per_pixel, void_mask);
+  else hipLaunchKernelGGL(pixel_loss_kernel<false>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, kind, p, z, y, class_w, (long long)M, C, loss_out, per_pixel, void_mask);
   RUA_LAUNCH_CHECK("rua_pixel_loss");
   return RUA_OK;
+}
+extern "C" int rua_pixel_loss(int kind, const float* p, const float* z, const float* y, const float* class_w,
+                              int64_t M, int C, double* loss_out, float* per_pixel, void* stream) {
+  return rua_pixel_loss_void(kind, p, z, y, class_w, nullptr, M, C, loss_out, per_pixel, stream);
 }
 
 // d(total loss)/d(logits), one thread per pixel
 // CT: the class count as a template constant (6, 3; 0: runtime, <= 8) - with a runtime C every `c < C` became a branch around one scalar access
-template <int CT>
+// VM: dz is +0.0f at a void pixel (written, not skipped: rua_head_bwd_sums reads every element); p and y are not read there
+template <int CT, bool VM>
 __device__ __forceinline__ void head_dz_body(int kind, int act, const float* __restrict__ p, const float* __restrict__ y,
                                              const float* __restrict__ coef, const float* __restrict__ cw, float gs,
-                                             long long HW, int C_rt, float* dz) {
+                                             long long HW, int C_rt, float* dz, const uint8_t* __restrict__ vm) {
   const int C = CT > 0 ? CT : C_rt;
   auto load_row = [&](const float* src, long long m, float* v) {
     if constexpr (CT == 6) {                              // 24-byte rows: three 8-byte accesses
@@ -351,9 +376,12 @@ __device__ __forceinline__ void head_dz_body(int kind, int act, const float* __r
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long long)gridDim.x * 256) {
     const long long m = (long long)n * HW + i;
     float pv[8], yv[8], g[8], o[8];
-    load_row(p, m, pv); load_row(y, m, yv);
 #pragma unroll
     for (int c = 0; c < 8; ++c) { g[c] = 0.f; o[c] = 0.f; }
+    if constexpr (VM) {
+      if (vm[m]) { store_row(m, o); continue; }
+    }
+    load_row(p, m, pv); load_row(y, m, yv);
     if (kind == RUA_LOSS_CE_LOGITS) {
       float sy = 0.f;
 #pragma unroll
@@ -412,24 +440,26 @@ __device__ __forceinline__ void head_dz_body(int kind, int act, const float* __r
   }
 }
 
+template <bool VM>
 __global__ __launch_bounds__(256) void head_dz_kernel(int kind, int act, const float* __restrict__ p, const float* __restrict__ y,
                                                       const float* __restrict__ coef, const float* __restrict__ cw, float gs,
-                                                      long long HW, long long M, int C, float* dz) {
+                                                      long long HW, long long M, int C, float* dz, const uint8_t* __restrict__ vm) {
   (void)M;
-  if (C == 6) head_dz_body<6>(kind, act, p, y, coef, cw, gs, HW, C, dz);
-  else if (C == 3) head_dz_body<3>(kind, act, p, y, coef, cw, gs, HW, C, dz);
-  else head_dz_body<0>(kind, act, p, y, coef, cw, gs, HW, C, dz);
+  if (C == 6) head_dz_body<6, VM>(kind, act, p, y, coef, cw, gs, HW, C, dz, vm);
+  else if (C == 3) head_dz_body<3, VM>(kind, act, p, y, coef, cw, gs, HW, C, dz, vm);
+  else head_dz_body<0, VM>(kind, act, p, y, coef, cw, gs, HW, C, dz, vm);
 }
 // d(loss)/d(logits) of several heads in ONE launch: blockIdx.z = head (the four heads of the multitask model: four launches of 4 - 12 us)
 struct DzMulti { rua_dz_head h[RUA_MAX_HEADS]; };
-__global__ __launch_bounds__(256) void head_dz_multi_kernel(const DzMulti a) {
+template <bool VM>
+__global__ __launch_bounds__(256) void head_dz_multi_kernel(const DzMulti a, const uint8_t* __restrict__ vm) {
   const rua_dz_head& h = a.h[blockIdx.z];
   if ((int)blockIdx.y >= h.B) return;
-  if (h.C == 6) head_dz_body<6>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, h.grad_scale, (long long)h.HW, h.C, h.dz);
-  else if (h.C == 3) head_dz_body<3>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, h.grad_scale, (long long)h.HW, h.C, h.dz);
-  else head_dz_body<0>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, h.grad_scale, (long long)h.HW, h.C, h.dz);
+  if (h.C == 6) head_dz_body<6, VM>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, h.grad_scale, (long long)h.HW, h.C, h.dz, vm);
+  else if (h.C == 3) head_dz_body<3, VM>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, h.grad_scale, (long long)h.HW, h.C, h.dz, vm);
+  else head_dz_body<0, VM>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, h.grad_scale, (long long)h.HW, h.C, h.dz, vm);
 }
-extern "C" int rua_head_dz_multi(const rua_dz_head* heads, int n, void* stream) {
+extern "C" int rua_head_dz_multi_void(const rua_dz_head* heads, int n, const uint8_t* void_mask, void* stream) {
   RUA_CHECK_ARG(heads && n >= 1 && n <= RUA_MAX_HEADS, "rua_head_dz_multi: 1..%d heads", RUA_MAX_HEADS);
   DzMulti a;
   int64_t g = 1; int Bm = 1;
@@ -439,19 +469,25 @@ extern "C" int rua_head_dz_multi(const rua_dz_head* heads, int n, void* stream) 
                   "rua_head_dz_multi: head %d: bad arguments", i);
     RUA_CHECK_ARG(h.kind != RUA_LOSS_TANIMOTO || h.coef, "rua_head_dz_multi: Tanimoto needs coefficients");
     RUA_CHECK_ARG(h.kind != RUA_LOSS_WCE || h.class_w, "rua_head_dz_multi: weighted CE needs class weights");
+    // one mask [B * HW] serves every head: it is indexed by (sample, pixel), so the heads must agree in both
+    RUA_CHECK_ARG(!void_mask || (h.B == heads[0].B && h.HW == heads[0].HW), "rua_head_dz_multi_void: head %d: B %d, HW %lld differ from head 0's", i, h.B, (long long)h.HW);
     a.h[i] = h;
     const int64_t gi = (h.HW + 255) / 256; if (gi > g) g = gi;
     if (h.B > Bm) Bm = h.B;
   }
   const int64_t cap = 4096 / ((int64_t)Bm * n) > 0 ? 4096 / ((int64_t)Bm * n) : 1;
   if (g > cap) g = cap;
-  hipLaunchKernelGGL(head_dz_multi_kernel, dim3((int)g, Bm, n), dim3(256), 0, (hipStream_t)stream, a);
+  if (void_mask) hipLaunchKernelGGL(head_dz_multi_kernel<true>, dim3((int)g, Bm, n), dim3(256), 0, (hipStream_t)stream, a, void_mask);
+  else hipLaunchKernelGGL(head_dz_multi_kernel<false>, dim3((int)g, Bm, n), dim3(256), 0, (hipStream_t)stream, a, void_mask);
   RUA_LAUNCH_CHECK("rua_head_dz_multi");
   return RUA_OK;
 }
+extern "C" int rua_head_dz_multi(const rua_dz_head* heads, int n, void* stream) {
+  return rua_head_dz_multi_void(heads, n, nullptr, stream);
+}
 
-extern "C" int rua_head_dz(int kind, int act, const float* p, const float* y, const float* coef, const float* class_w,
-                           float grad_scale, int B, int64_t HW, int C, float* dz, void* stream) {
+extern "C" int rua_head_dz_void(int kind, int act, const float* p, const float* y, const float* coef, const float* class_w,
+                                float grad_scale, int B, int64_t HW, int C, const uint8_t* void_mask, float* dz, void* stream) {
   RUA_CHECK_ARG(p && y && dz && B > 0 && HW > 0, "rua_head_dz: bad arguments");
   RUA_CHECK_ARG(C >= 1 && C <= 8, "rua_head_dz: C=%d must be in 1..8", C);
   RUA_CHECK_ARG(kind >= 0 && kind <= 4 && act >= 0 && act <= 2, "rua_head_dz: bad kind/act");
@@ -462,17 +498,27 @@ extern "C" int rua_head_dz(int kind, int act, const float* p, const float* y, co
   const int64_t cap = 4096 / B > 0 ? 4096 / B : 1;       // ~4096 blocks over the batch; blockIdx.y = sample
   if (g > cap) g = cap;
   RUA_CHECK_ARG(B <= 65535, "rua_head_dz: B=%d too large", B);
-  hipLaunchKernelGGL(head_dz_kernel, dim3((int)g, B), dim3(256), 0, (hipStream_t)stream, kind, act, p, y, coef, class_w, grad_scale,
-                     (long long)HW, (long long)M, C, dz);
+  if (void_mask) hipLaunchKernelGGL(head_dz_kernel<true>, dim3((int)g, B), dim3(256), 0, (hipStream_t)stream, kind, act, p, y, coef, class_w, grad_scale,
+                                    (long long)HW, (long long)M, C, dz, void_mask);
+  else hipLaunchKernelGGL(head_dz_kernel<false>, dim3((int)g, B), dim3(256), 0, (hipStream_t)stream, kind, act, p, y, coef, class_w, grad_scale,
+                          (long long)HW, (long long)M, C, dz, void_mask);
   RUA_LAUNCH_CHECK("rua_head_dz");
   return RUA_OK;
 }
+extern "C" int rua_head_dz(int kind, int act, const float* p, const float* y, const float* coef, const float* class_w,
+                           float grad_scale, int B, int64_t HW, int C, float* dz, void* stream) {
+  return rua_head_dz_void(kind, act, p, y, coef, class_w, grad_scale, B, HW, C, nullptr, dz, stream);
+}
 
 // accuracy + TP/FP/TN/FN (Keras 'accuracy' = categorical accuracy; confusion counts at .5)
-__global__ __launch_bounds__(256) void seg_metrics_kernel(const float* __restrict__ p, const float* __restrict__ y, long long M, int C, double* out) {
+// VM: void pixels are counted nowhere, so (TP + FP + TN + FN) / C is the number of valid pixels
+template <bool VM>
+__global__ __launch_bounds__(256) void seg_metrics_kernel(const float* __restrict__ p, const float* __restrict__ y, long long M, int C, double* out,
+                                                          const uint8_t* __restrict__ vm) {
   __shared__ float sh[5 * 4];
   float a[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   for (long long m = (long long)blockIdx.x * 256 + threadIdx.x; m < M; m += (long long)gridDim.x * 256) {
+    if constexpr (VM) { if (vm[m]) continue; }
     int ip = 0, iy = 0; float bp = p[m * C], by = y[m * C];
     for (int c = 0; c < C; ++c) {
       const float pv = p[m * C + c], yv = y[m * C + c];
@@ -487,8 +533,9 @@ __global__ __launch_bounds__(256) void seg_metrics_kernel(const float* __restric
 }
 
 // 16-byte loads: G pixels (G * C floats = NV float4) per thread per iteration, element classes are compile-time constants
-template <int C, int G>
-__global__ __launch_bounds__(256) void seg_metrics_vec(const float* __restrict__ p, const float* __restrict__ y, long long M, double* out) {
+template <int C, int G, bool VM>
+__global__ __launch_bounds__(256) void seg_metrics_vec(const float* __restrict__ p, const float* __restrict__ y, long long M, double* out,
+                                                       const uint8_t* __restrict__ vm) {
   constexpr int NV = G * C / 4;
   __shared__ float sh[5 * 4];
   float a[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
@@ -505,6 +552,7 @@ __global__ __launch_bounds__(256) void seg_metrics_vec(const float* __restrict__
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
+      if constexpr (VM) { if (vm[gi * G + g]) continue; }
       int ip = 0, iy = 0; float bp = pv[g * C], by = yv[g * C];
 #pragma unroll
       for (int c = 0; c < C; ++c) {
@@ -520,12 +568,14 @@ __global__ __launch_bounds__(256) void seg_metrics_vec(const float* __restrict__
   for (int k = 0; k < 5; ++k) block_atomic_add(&out[k], a[k], sh, k);
 }
 
-extern "C" int rua_seg_metrics(const float* p, const float* y, int64_t M, int C, double* out, void* stream) {
+extern "C" int rua_seg_metrics_void(const float* p, const float* y, const uint8_t* void_mask, int64_t M, int C, double* out, void* stream) {
   RUA_CHECK_ARG(p && y && out && M > 0 && C >= 1, "rua_seg_metrics: bad arguments");
   if ((C == 6 || C == 2) && M % 2 == 0 && ((size_t)p & 15) == 0 && ((size_t)y & 15) == 0) {
     int64_t g = (M / 2 + 255) / 256; if (g > 256) g = 256;
-    if (C == 6) hipLaunchKernelGGL((seg_metrics_vec<6, 2>), dim3((int)g), dim3(256), 0, (hipStream_t)stream, p, y, (long long)M, out);
-    else hipLaunchKernelGGL((seg_metrics_vec<2, 2>), dim3((int)g), dim3(256), 0, (hipStream_t)stream, p, y, (long long)M, out);
+    if (C == 6 && void_mask) hipLaunchKernelGGL((seg_metrics_vec<6, 2, true>), dim3((int)g), dim3(256), 0, (hipStream_t)stream, p, y, (long long)M, out, void_mask);
+    else if (C == 6) hipLaunchKernelGGL((seg_metrics_vec<6, 2, false>), dim3((int)g), dim3(256), 0, (hipStream_t)stream, p, y, (long long)M, out, void_mask);
+    else if (void_mask) hipLaunchKernelGGL((seg_metrics_vec<2, 2, true>), dim3((int)g), dim3(256), 0, (hipStream_t)stream, p, y, (long long)M, out, void_mask);
+    else hipLaunchKernelGGL((seg_metrics_vec<2, 2, false>), dim3((int)g), dim3(256), 0, (hipStream_t)stream, p, y, (long long)M, out, void_mask);
     RUA_LAUNCH_CHECK("rua_seg_metrics");
     return RUA_OK;
   }
@@ -533,9 +583,13 @@ extern "C" int rua_seg_metrics(const float* p, const float* y, int64_t M, int C,
   // 64 blocks 36 us, 128: 23, 256: 24, 512: 37
   const int cap = g_tune.metrics_blocks > 0 ? g_tune.metrics_blocks : rua_cu_count() / 2;      // 128 on MI355X
   int64_t g = (M + 255) / 256; if (g > cap) g = cap;
-  hipLaunchKernelGGL(seg_metrics_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, p, y, (long long)M, C, out);
+  if (void_mask) hipLaunchKernelGGL(seg_metrics_kernel<true>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, p, y, (long long)M, C, out, void_mask);
+  else hipLaunchKernelGGL(seg_metrics_kernel<false>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, p, y, (long long)M, C, out, void_mask);
   RUA_LAUNCH_CHECK("rua_seg_metrics");
   return RUA_OK;
+}
+extern "C" int rua_seg_metrics(const float* p, const float* y, int64_t M, int C, double* out, void* stream) {
+  return rua_seg_metrics_void(p, y, nullptr, M, C, out, stream);
 }
 
 // ---- optimizers on the flat parameter buffer ---------------------------------------------------

@@ -382,10 +382,12 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const unsigned char* x, c
 // registers (the first form re-read them from LDS: 192 broadcast reads per pixel, 22 us for a 59 MB pass), the partial dot products
 // are folded over the CGI lanes by xor shuffles, every lane finishes the activation, and lane cp stores / accounts for the classes
 // cp, cp + CGI: logits, probabilities, and - LOSS - the Tanimoto moments and the accuracy / confusion counts of those classes.
-template <typename T, int CO, bool LOSS>
+// VM (with LOSS): vm[n * HW + i] != 0 marks a void pixel - z and p are stored as ever, the moments and counts skip it (rua_head_fwd_loss_void);
+// VM false is the code it was.
+template <typename T, int CO, bool LOSS, bool VM = false>
 __global__ __launch_bounds__(256) void head_fwd2_kernel(const unsigned char* x, const float* __restrict__ w, const float* __restrict__ b,
                                                          float* z, float* p, const float* __restrict__ y, double* sums, double* metrics,
-                                                         long long HW, int pix_per_block, int Cin, int Cout, int act) {
+                                                         long long HW, int pix_per_block, int Cin, int Cout, int act, const uint8_t* __restrict__ vm) {
   constexpr int VEC = ET<T>::VEC;
   constexpr int CGI = 32 / VEC;                       // 4 (bf16) or 8 (fp32) lanes per pixel
   constexpr int PL = 256 / CGI;                       // pixels per pass and block
@@ -414,22 +416,24 @@ __global__ __launch_bounds__(256) void head_fwd2_kernel(const unsigned char* x, 
   float yv[NOWN];
 #pragma unroll
   for (int o = 0; o < NOWN; ++o) yv[o] = 0.f;
-  auto fetch = [&](long long ii, uint4& q, float* yy) {
+  int vd = 0, vd_n = 0;                               // (VM) this pass's / the next pass's pixel is void
+  auto fetch = [&](long long ii, uint4& q, float* yy, int& vv) {
     const long long mm_ = (long long)n * HW + ii;
     q = ldg16(x + ((size_t)mm_ * CGI + cp) * 16);
     if constexpr (LOSS) {
 #pragma unroll
       for (int o = 0; o < NOWN; ++o) yy[o] = (cp + o * CGI) < Cout ? y[mm_ * Cout + cp + o * CGI] : 0.f;
+      if constexpr (VM) vv = vm[mm_];
     }
   };
-  if (i < iend) fetch(i, xq, yv);
+  if (i < iend) fetch(i, xq, yv, vd);
   for (; i < iend; i += PL) {
     const long long m = (long long)n * HW + i;
     uint4 xq_n = make_uint4(0, 0, 0, 0);
     float yv_n[NOWN];
 #pragma unroll
     for (int o = 0; o < NOWN; ++o) yv_n[o] = 0.f;
-    if (i + PL < iend) fetch(i + PL, xq_n, yv_n);
+    if (i + PL < iend) fetch(i + PL, xq_n, yv_n, vd_n);
     float xv[VEC], acc[CO];
     ET<T>::unpack(xq, xv);
 #pragma unroll
@@ -470,6 +474,7 @@ __global__ __launch_bounds__(256) void head_fwd2_kernel(const unsigned char* x, 
         if (z) z[m * Cout + c] = zo;
         p[m * Cout + c] = po;
         if constexpr (LOSS) {
+          if (VM && vd) continue;
           const float a = po, l = yv[o], q = 1.f - a, mm = 1.f - l;
           ts[o][0] += a; ts[o][1] += mm; ts[o][2] = fmaf(a, l, ts[o][2]);
           ts[o][3] += a * a + l * l; ts[o][4] = fmaf(q, mm, ts[o][4]); ts[o][5] += q * q + mm * mm;
@@ -491,10 +496,11 @@ __global__ __launch_bounds__(256) void head_fwd2_kernel(const unsigned char* x, 
           const float ov = __shfl_xor(by, o, 64); const int oi = __shfl_xor(iy, o, 64);
           if (ov > by || (ov == by && oi < iy)) { by = ov; iy = oi; }     // first maximum wins, as a scan in class order
         }
-        if (cp == 0) mt[0] += (ip == iy);
+        if (cp == 0 && !(VM && vd)) mt[0] += (ip == iy);
       }
     }
     xq = xq_n;
+    vd = vd_n;
 #pragma unroll
     for (int o = 0; o < NOWN; ++o) yv[o] = yv_n[o];
   }
@@ -543,10 +549,12 @@ __global__ __launch_bounds__(256) void head_fwd2_kernel(const unsigned char* x, 
 // through one accumulator, pixels 32 - 63 through a second one; class rows 0 - 3 sit in lanes 0 - 31 and rows 4 - 7 in lanes 32 - 63, so four
 // v_permlane32_swap leave EVERY lane with all classes of ITS pixel (lane l: pixel l of the pass): bias, softmax / sigmoid, stores,
 // Tanimoto moments and confusion counts run once per pixel, one lane each.  The loads of pass k + 1 are issued before the arithmetic of pass k.
-template <int CO, bool LOSS>
+// VM (with LOSS): the lane that owns a pixel loads its void byte with the labels and leaves the pixel out of the moments and counts; VM false is the
+// code it was.
+template <int CO, bool LOSS, bool VM = false>
 __global__ __launch_bounds__(256) void head_fwd3_kernel(const unsigned char* x, const float* __restrict__ w, const float* __restrict__ b,
                                                          float* z, float* p, const float* __restrict__ y, double* sums, double* metrics,
-                                                         long long HW, int pix_per_block, int Cout, int act, int replicas) {
+                                                         long long HW, int pix_per_block, int Cout, int act, int replicas, const uint8_t* __restrict__ vm) {
   __shared__ float sh[4 * 56];
   constexpr bool EXACT = CO != 8;                     // CO = 6 / 3 are launched for Cout == CO only: no runtime per-class tests
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -578,7 +586,8 @@ __global__ __launch_bounds__(256) void head_fwd3_kernel(const unsigned char* x, 
   const unsigned char* xn = x + (size_t)n * HW * 64;
   const size_t row0 = (size_t)n * HW;
   // B fragments of a pass: [pixel group][k-step]; labels of this lane's pixel
-  auto fetch = [&](long long g0, uint4 (&q)[2][2], float (&yy)[CO]) {
+  int vd = 0, vd_n = 0;                               // (VM) this lane's pixel of the pass / of the next pass is void
+  auto fetch = [&](long long g0, uint4 (&q)[2][2], float (&yy)[CO], int& vv) {
 #pragma unroll
     for (int pg = 0; pg < 2; ++pg) {
       const long long pb = g0 + 32 * pg + pl;
@@ -597,6 +606,7 @@ __global__ __launch_bounds__(256) void head_fwd3_kernel(const unsigned char* x, 
 #pragma unroll
         for (int c = 0; c < CO; ++c) yy[c] = (ok && (EXACT || c < Cout)) ? yr[c] : 0.f;
       }
+      if constexpr (VM) vv = ok ? vm[row0 + (size_t)pm] : 0;
     }
   };
   uint4 xq[2][2], xq_n[2][2];
@@ -604,9 +614,9 @@ __global__ __launch_bounds__(256) void head_fwd3_kernel(const unsigned char* x, 
 #pragma unroll
   for (int c = 0; c < CO; ++c) { yv[c] = 0.f; yv_n[c] = 0.f; }
   long long g0 = blk0 + (long long)wid * 64;
-  if (g0 < blk_end) fetch(g0, xq, yv);
+  if (g0 < blk_end) fetch(g0, xq, yv, vd);
   for (; g0 < blk_end; g0 += 256) {
-    if (g0 + 256 < blk_end) fetch(g0 + 256, xq_n, yv_n);
+    if (g0 + 256 < blk_end) fetch(g0 + 256, xq_n, yv_n, vd_n);
     f32x16 d1, d2;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { d1[i] = 0.f; d2[i] = 0.f; }
@@ -668,7 +678,7 @@ __global__ __launch_bounds__(256) void head_fwd3_kernel(const unsigned char* x, 
         int ip = 0, iy = 0; float bp = pr[0], by = yv[0];
 #pragma unroll
         for (int c = 0; c < CO; ++c) {
-          if (EXACT || c < Cout) {
+          if ((EXACT || c < Cout) && !(VM && vd)) {
             const float a = pr[c], l = yv[c], q = 1.f - a, mm = 1.f - l;
             ts[c][0] += a; ts[c][1] += mm; ts[c][2] = fmaf(a, l, ts[c][2]);
             ts[c][3] += a * a + l * l; ts[c][4] = fmaf(q, mm, ts[c][4]); ts[c][5] += q * q + mm * mm;
@@ -680,9 +690,10 @@ __global__ __launch_bounds__(256) void head_fwd3_kernel(const unsigned char* x, 
             }
           }
         }
-        if (metrics) mt[0] += (ip == iy);
+        if (metrics && !(VM && vd)) mt[0] += (ip == iy);
       }
     }
+    vd = vd_n;
 #pragma unroll
     for (int pg = 0; pg < 2; ++pg)
 #pragma unroll
@@ -722,28 +733,28 @@ __global__ __launch_bounds__(256) void head_fwd3_kernel(const unsigned char* x, 
   }
 }
 
-template <bool LOSS>
+template <bool LOSS, bool VM = false>
 static void launch_head_fwd3(const void* x, const float* w, const float* b, float* z, float* p, const float* y, double* sums, double* metrics,
-                             int B, int64_t HW, int Cout, int act, int replicas, hipStream_t st) {
+                             int B, int64_t HW, int Cout, int act, int replicas, hipStream_t st, const uint8_t* vm = nullptr) {
   const int bpc = g_tune.head_fwd3_bpc > 0 ? g_tune.head_fwd3_bpc : (LOSS ? 3 : 4);       // blocks per CU over the batch (LOSS: a block holds a 42 KB reduction tile and ends in <= 53 fp64 atomics)
   int64_t per_sample = ((int64_t)bpc * rua_cu_count() + B - 1) / B; if (per_sample < 1) per_sample = 1;
   int64_t ppb = (HW + per_sample - 1) / per_sample; if (ppb < 256) ppb = 256;
   ppb = (ppb + 255) / 256 * 256;
   const int gx = (int)((HW + ppb - 1) / ppb);
-#define RUA_HEAD3(CO_) hipLaunchKernelGGL((head_fwd3_kernel<CO_, LOSS>), dim3(gx, B), dim3(256), 0, st, (const unsigned char*)x, w, b, z, p, y, sums, metrics, (long long)HW, (int)ppb, Cout, act, replicas)
+#define RUA_HEAD3(CO_) hipLaunchKernelGGL((head_fwd3_kernel<CO_, LOSS, VM>), dim3(gx, B), dim3(256), 0, st, (const unsigned char*)x, w, b, z, p, y, sums, metrics, (long long)HW, (int)ppb, Cout, act, replicas, vm)
   if (Cout == 6) RUA_HEAD3(6); else if (Cout == 3) RUA_HEAD3(3); else RUA_HEAD3(8);
 #undef RUA_HEAD3
 }
 
-template <typename T, bool LOSS>
+template <typename T, bool LOSS, bool VM = false>
 static void launch_head_fwd2(const void* x, const float* w, const float* b, float* z, float* p, const float* y, double* sums, double* metrics,
-                             int B, int64_t HW, int Cin, int Cout, int act, hipStream_t st) {
+                             int B, int64_t HW, int Cin, int Cout, int act, hipStream_t st, const uint8_t* vm = nullptr) {
   int64_t per_sample = (4 * (int64_t)rua_cu_count() + B - 1) / B; if (per_sample < 1) per_sample = 1;      // ~4 blocks per CU over the batch
   constexpr int PL = 256 / (32 / ET<T>::VEC);
   int64_t ppb = (HW + per_sample - 1) / per_sample; if (ppb < PL) ppb = PL;
   ppb = (ppb + PL - 1) / PL * PL;
   const int gx = (int)((HW + ppb - 1) / ppb);
-#define RUA_HEAD2(CO_) hipLaunchKernelGGL((head_fwd2_kernel<T, CO_, LOSS>), dim3(gx, B), dim3(256), 0, st, (const unsigned char*)x, w, b, z, p, y, sums, metrics, (long long)HW, (int)ppb, Cin, Cout, act)
+#define RUA_HEAD2(CO_) hipLaunchKernelGGL((head_fwd2_kernel<T, CO_, LOSS, VM>), dim3(gx, B), dim3(256), 0, st, (const unsigned char*)x, w, b, z, p, y, sums, metrics, (long long)HW, (int)ppb, Cin, Cout, act, vm)
   if (Cout == 6) RUA_HEAD2(6); else if (Cout == 3) RUA_HEAD2(3); else RUA_HEAD2(8);
 #undef RUA_HEAD2
 }
@@ -752,10 +763,11 @@ static void launch_head_fwd2(const void* x, const float* w, const float* b, floa
 // confusion counts of the 'seg' head) need them, so rua_tanimoto_sums / rua_seg_metrics do not read p again (four + one passes
 // over 12.6 MB and five launches per step).  A block stays inside ONE sample (blockIdx.y): sums[n][c][6] as rua_tanimoto_sums
 // defines them, metrics[5] as rua_seg_metrics.
-template <typename T>
+// VM: vm[n * HW + i] != 0 leaves the pixel out of the moments and counts (z and p are stored as ever); VM false is the code it was.
+template <typename T, bool VM = false>
 __global__ __launch_bounds__(256) void head_fwd_loss_kernel(const unsigned char* x, const float* __restrict__ w, const float* __restrict__ b,
                                                              float* z, float* p, const float* __restrict__ y, double* sums, double* metrics,
-                                                             long long HW, int pix_per_block, int Cin, int Cout, int act) {
+                                                             long long HW, int pix_per_block, int Cin, int Cout, int act, const uint8_t* __restrict__ vm) {
   constexpr int VEC = ET<T>::VEC;
   extern __shared__ float sw[];                       // [Cout][Cin] + [Cout], then [4 waves][53]
   float* sh = sw + Cout * Cin + Cout;
@@ -810,6 +822,7 @@ __global__ __launch_bounds__(256) void head_fwd_loss_kernel(const unsigned char*
     }
 #pragma unroll
     for (int co = 0; co < 8; ++co) if (co < Cout) { if (z) z[m * Cout + co] = acc[co]; p[m * Cout + co] = pr[co]; }
+    if constexpr (VM) { if (vm[m]) continue; }
     // moments (rua_tanimoto_sums) and counts (rua_seg_metrics) of this pixel
     int ip = 0, iy = 0; float bp = pr[0], by = yv[0];
 #pragma unroll
@@ -1034,8 +1047,18 @@ extern "C" int rua_head_fwd_loss(const void* x, const float* w, const float* b, 
 }
 // tanimoto_sums [sums_replicas][B][Cout][6]: a block adds into copy blockIdx.x % sums_replicas (every block ends in <= 48 fp64 atomics on its sample's
 // sums: with one copy the ~64 blocks of a sample queue up on each of them - 11 us of a 24 us launch); rua_tanimoto_finalize_rep adds the copies
+extern "C" int rua_head_fwd_loss_void(const void* x, const float* w, const float* b, float* z, float* p, const float* y, double* tanimoto_sums,
+                                      int sums_replicas, double* metrics, int B, int64_t HW, int Cin, int Cout, int act, int dtype,
+                                      const uint8_t* void_mask, void* stream);
 extern "C" int rua_head_fwd_loss_rep(const void* x, const float* w, const float* b, float* z, float* p, const float* y, double* tanimoto_sums,
                                      int sums_replicas, double* metrics, int B, int64_t HW, int Cin, int Cout, int act, int dtype, void* stream) {
+  return rua_head_fwd_loss_void(x, w, b, z, p, y, tanimoto_sums, sums_replicas, metrics, B, HW, Cin, Cout, act, dtype, nullptr, stream);
+}
+// void_mask [B * HW] (device bytes, any alignment; NULL: none): a non-zero byte takes the pixel out of the moments and counts.  Same dispatch as ever;
+// the masked kernels are instantiations of their own (VM), so the unmasked launches run the code they ran
+extern "C" int rua_head_fwd_loss_void(const void* x, const float* w, const float* b, float* z, float* p, const float* y, double* tanimoto_sums,
+                                      int sums_replicas, double* metrics, int B, int64_t HW, int Cin, int Cout, int act, int dtype,
+                                      const uint8_t* void_mask, void* stream) {
   RUA_CHECK_ARG(sums_replicas >= 1 && sums_replicas <= 64, "rua_head_fwd_loss_rep: sums_replicas=%d must be in 1..64", sums_replicas);
   RUA_CHECK_ARG(x && w && p && y && B > 0 && HW > 0, "rua_head_fwd_loss: bad arguments");
   RUA_CHECK_ARG(tanimoto_sums || metrics, "rua_head_fwd_loss: nothing to accumulate (use rua_head_fwd)");
@@ -1049,19 +1072,26 @@ extern "C" int rua_head_fwd_loss_rep(const void* x, const float* w, const float*
   ppb = (ppb + 255) / 256 * 256;
   const int gx = (int)((HW + ppb - 1) / ppb);
   hipStream_t st = (hipStream_t)stream;
+  const uint8_t* vm = void_mask;
   if (Cin == 32 && dtype == RUA_BF16 && g_tune.head_fwd3) {
-    launch_head_fwd3<true>(x, w, b, z, p, y, tanimoto_sums, metrics, B, HW, Cout, act, sums_replicas, st);
+    if (vm) launch_head_fwd3<true, true>(x, w, b, z, p, y, tanimoto_sums, metrics, B, HW, Cout, act, sums_replicas, st, vm);
+    else launch_head_fwd3<true>(x, w, b, z, p, y, tanimoto_sums, metrics, B, HW, Cout, act, sums_replicas, st);
     RUA_LAUNCH_CHECK("rua_head_fwd_loss");
     return RUA_OK;
   }
   if (Cin == 32 && g_tune.head_fwd2) {
-    if (dtype == RUA_BF16) launch_head_fwd2<bf16_t, true>(x, w, b, z, p, y, tanimoto_sums, metrics, B, HW, Cin, Cout, act, st);
-    else launch_head_fwd2<float, true>(x, w, b, z, p, y, tanimoto_sums, metrics, B, HW, Cin, Cout, act, st);
+    if (dtype == RUA_BF16) { if (vm) launch_head_fwd2<bf16_t, true, true>(x, w, b, z, p, y, tanimoto_sums, metrics, B, HW, Cin, Cout, act, st, vm); else launch_head_fwd2<bf16_t, true>(x, w, b, z, p, y, tanimoto_sums, metrics, B, HW, Cin, Cout, act, st); }
+    else { if (vm) launch_head_fwd2<float, true, true>(x, w, b, z, p, y, tanimoto_sums, metrics, B, HW, Cin, Cout, act, st, vm); else launch_head_fwd2<float, true>(x, w, b, z, p, y, tanimoto_sums, metrics, B, HW, Cin, Cout, act, st); }
     RUA_LAUNCH_CHECK("rua_head_fwd_loss");
     return RUA_OK;
   }
-  if (dtype == RUA_BF16) hipLaunchKernelGGL((head_fwd_loss_kernel<bf16_t>), dim3(gx, B), dim3(256), smem, st, (const unsigned char*)x, w, b, z, p, y, tanimoto_sums, metrics, (long long)HW, (int)ppb, Cin, Cout, act);
-  else hipLaunchKernelGGL((head_fwd_loss_kernel<float>), dim3(gx, B), dim3(256), smem, st, (const unsigned char*)x, w, b, z, p, y, tanimoto_sums, metrics, (long long)HW, (int)ppb, Cin, Cout, act);
+  if (dtype == RUA_BF16) {
+    if (vm) hipLaunchKernelGGL((head_fwd_loss_kernel<bf16_t, true>), dim3(gx, B), dim3(256), smem, st, (const unsigned char*)x, w, b, z, p, y, tanimoto_sums, metrics, (long long)HW, (int)ppb, Cin, Cout, act, vm);
+    else hipLaunchKernelGGL((head_fwd_loss_kernel<bf16_t, false>), dim3(gx, B), dim3(256), smem, st, (const unsigned char*)x, w, b, z, p, y, tanimoto_sums, metrics, (long long)HW, (int)ppb, Cin, Cout, act, vm);
+  } else {
+    if (vm) hipLaunchKernelGGL((head_fwd_loss_kernel<float, true>), dim3(gx, B), dim3(256), smem, st, (const unsigned char*)x, w, b, z, p, y, tanimoto_sums, metrics, (long long)HW, (int)ppb, Cin, Cout, act, vm);
+    else hipLaunchKernelGGL((head_fwd_loss_kernel<float, false>), dim3(gx, B), dim3(256), smem, st, (const unsigned char*)x, w, b, z, p, y, tanimoto_sums, metrics, (long long)HW, (int)ppb, Cin, Cout, act, vm);
+  }
   RUA_LAUNCH_CHECK("rua_head_fwd_loss");
   return RUA_OK;
 }

@@ -281,7 +281,60 @@ __global__ __launch_bounds__(256) void tgt_bound(const uint8_t* __restrict__ cls
   }
 }
 
+// ---- void mask: square dilation (radius mg) of cls >= C inside each patch.  A 32 x 64 output tile with the flags of its halo in LDS (zero outside
+// the patch), ORed along the rows, then along the columns; a thread finishes four neighbouring pixels and stores them as one dword where the address
+// allows it (the mask has no alignment of its own: a row of odd width starts anywhere), byte by byte at ragged ends. ------------------------------
+constexpr int VTH = 32, VTW = 64, VMG = 16;
+__global__ __launch_bounds__(256) void void_mask_kernel(const uint8_t* __restrict__ cls, int H, int W, int C, int mg, uint8_t* __restrict__ mask) {
+  __shared__ uint8_t F[(VTH + 2 * VMG) * (VTW + 2 * VMG)];
+  __shared__ uint8_t R[(VTH + 2 * VMG) * VTW];
+  const int tid = threadIdx.x, j0 = blockIdx.x * VTW, i0 = blockIdx.y * VTH, n = blockIdx.z;
+  const int fh = VTH + 2 * mg, fw = VTW + 2 * mg;
+  const uint8_t* src = cls + (size_t)n * H * W;
+  for (int e = tid; e < fh * fw; e += 256) {
+    const int r = e / fw, q = e - r * fw, gi = i0 - mg + r, gj = j0 - mg + q;
+    F[e] = (gi >= 0 && gi < H && gj >= 0 && gj < W && src[(size_t)gi * W + gj] >= C) ? 1 : 0;
+  }
+  __syncthreads();
+  for (int e = tid; e < fh * VTW; e += 256) {
+    const int r = e / VTW, q = e % VTW;
+    int v = 0;
+    for (int t = 0; t <= 2 * mg; ++t) v |= F[r * fw + q + t];
+    R[e] = (uint8_t)v;
+  }
+  __syncthreads();
+  for (int e = tid; e < VTH * (VTW / 4); e += 256) {
+    const int r = e / (VTW / 4), q4 = (e % (VTW / 4)) * 4, i = i0 + r, j = j0 + q4;
+    if (i >= H || j >= W) continue;
+    uint32_t word = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      int v = 0;
+      for (int t = 0; t <= 2 * mg; ++t) v |= R[(r + t) * VTW + q4 + k];
+      word |= (v ? 255u : 0u) << (8 * k);
+    }
+    uint8_t* out = mask + (size_t)n * H * W + (size_t)i * W + j;
+    if (j + 3 < W && ((uintptr_t)out & 3) == 0) {
+      *reinterpret_cast<uint32_t*>(out) = word;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) if (j + k < W) out[k] = (uint8_t)(word >> (8 * k));
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int rua_void_mask(const uint8_t* cls, int N, int H, int W, int num_classes, int margin, uint8_t* mask, void* stream) {
+  RUA_CHECK_ARG(cls && mask, "rua_void_mask: cls and mask are required");
+  RUA_CHECK_ARG(N >= 1 && N <= 65535 && H >= 1 && W >= 1 && H <= TGT_MAXHW && W <= TGT_MAXHW, "rua_void_mask: N %d, H %d, W %d (1 <= N <= 65535, 1 <= H, W <= 512)", N, H, W);
+  RUA_CHECK_ARG(num_classes >= 1 && num_classes <= 255, "rua_void_mask: num_classes %d outside 1..255", num_classes);
+  RUA_CHECK_ARG(margin >= 0 && margin <= VMG, "rua_void_mask: margin %d outside 0..%d", margin, VMG);
+  RUA_CHECK_ARG((int64_t)N * H * W < ((int64_t)1 << 31), "rua_void_mask: N*H*W must stay below 2^31");
+  hipLaunchKernelGGL(void_mask_kernel, dim3((W + VTW - 1) / VTW, (H + VTH - 1) / VTH, N), dim3(256), 0, (hipStream_t)stream, cls, H, W, num_classes, margin, mask);
+  RUA_LAUNCH_CHECK("rua_void_mask");
+  return RUA_OK;
+}
 
 extern "C" int64_t rua_targets_scratch_bytes(int N, int num_classes) {
   return N > 0 && num_classes > 0 ? (int64_t)N * num_classes * 4 : 0;

@@ -52,6 +52,8 @@ class LossSpec:
     beta_1: float = 0.9
     beta_2: float = 0.999
     momentum: float = 0.8
+    ignore_void: Optional[int] = None                        # None: off.  An int (0..16): void pixels leave every loss and metric; the void mask of
+                                                             # a class-map batch is cls >= num_classes dilated by this margin (labels.host_void_mask)
 
 
 # ---------------------------------------------------------------------------------------
@@ -328,6 +330,12 @@ class Graph:
         self.stats_used = 16                 # the first 16 doubles of the arena are the loss / metric scalars
         self.act_bytes = 0
         self.img_u8 = self.cls_u8 = self.tgt_scratch = None     # compact batches (Engine._upload_compact): allocated on first use
+        # LossSpec.ignore_void: the batch's void mask [B,H,W] (non-zero: void).  The plans hold its address, so it exists before they are recorded and
+        # stays where it is: a captured step reads whatever mask the latest batch put there
+        self.void_u8 = None
+        if not dry and eng.loss is not None and eng.loss.ignore_void is not None:
+            self.void_u8 = torch.zeros((batch,) + tuple(eng.cfg.input_shape[:2]), dtype=torch.uint8, device=self.dev)
+        self.void_ptr = self.void_u8.data_ptr() if self.void_u8 is not None else None
         self._build()
 
     def compact_buffers(self):
@@ -1414,8 +1422,12 @@ class Graph:
                 h["sums"] = self.salloc((SUMS_REPLICAS + 1) * x.N * cout * 6)
             if hname == "seg":
                 h["metrics_done"] = True
-            F.add("rua_head_fwd_loss_rep", x.ptr, self.P(lay["segs"][0]["off"]), self.P(lay["bias"]), z.ptr, p.ptr, y.ptr, h.get("sums"),
-                  h.get("sums_rep", 1), self.e.scalars_ptr + 8 * 8 if hname == "seg" else None, x.N, x.H * x.W, x.C, cout, act, self.dt)
+            head_args = (x.ptr, self.P(lay["segs"][0]["off"]), self.P(lay["bias"]), z.ptr, p.ptr, y.ptr, h.get("sums"),
+                         h.get("sums_rep", 1), self.e.scalars_ptr + 8 * 8 if hname == "seg" else None, x.N, x.H * x.W, x.C, cout, act, self.dt)
+            if self.void_ptr is not None:
+                F.add("rua_head_fwd_loss_void", *head_args, self.void_ptr)
+            else:
+                F.add("rua_head_fwd_loss_rep", *head_args)
         else:
             F.add("rua_head_fwd", x.ptr, self.P(lay["segs"][0]["off"]), self.P(lay["bias"]), z.ptr, p.ptr, x.M, x.C, cout, act, self.dt)
         self.heads.append(h)
@@ -1503,7 +1515,10 @@ class Graph:
             sums = h.get("sums")
             if sums is None:                                # (the head's forward did not take the moments itself)
                 sums = self.salloc(B * Cc * 6)
-                LP.add("rua_tanimoto_sums", h["p"].ptr, h["y"].ptr, B, HW, Cc, sums)
+                if self.void_ptr is not None:
+                    LP.add("rua_tanimoto_sums_void", h["p"].ptr, h["y"].ptr, self.void_ptr, B, HW, Cc, sums)
+                else:
+                    LP.add("rua_tanimoto_sums", h["p"].ptr, h["y"].ptr, B, HW, Cc, sums)
             if self.multi_head:                             # one launch for all heads (_record_losses)
                 th = L.TaniHead()
                 th.sums, th.replicas, th.B, th.C, th.grad_scale, th.loss_out, th.coef, th.per_sample = sums, h.get("sums_rep", 1), B, Cc, wgt / B, slot, coef.data_ptr(), None
@@ -1512,7 +1527,10 @@ class Graph:
                 LP.add("rua_tanimoto_finalize_rep", sums, h.get("sums_rep", 1), B, HW, Cc, wgt / B, slot, coef.data_ptr(), None)
             h["norm"] = 1.0
         else:
-            LP.add("rua_pixel_loss", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, M, Cc, slot, None)
+            if self.void_ptr is not None:                   # the sum over the valid pixels, still divided by M (Keras' sample_weight rule with 0 / 1 weights)
+                LP.add("rua_pixel_loss_void", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, self.void_ptr, M, Cc, slot, None)
+            else:
+                LP.add("rua_pixel_loss", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, M, Cc, slot, None)
             h["norm"] = 1.0 / M
         if not self.training:
             return
@@ -1531,8 +1549,14 @@ class Graph:
                 if not self._dz_emitted:                    # the first backward step of the loss section: d(loss)/d(logits) of ALL heads in one launch
                     arr = (L.DzHead * len(self._dz_multi))(*self._dz_multi)
                     Bp.keep.append(arr)
-                    Bp.add("rua_head_dz_multi", arr, len(self._dz_multi))
+                    if self.void_ptr is not None:
+                        Bp.add("rua_head_dz_multi_void", arr, len(self._dz_multi), self.void_ptr)
+                    else:
+                        Bp.add("rua_head_dz_multi", arr, len(self._dz_multi))
                     self._dz_emitted = True
+            elif self.void_ptr is not None:
+                Bp.add("rua_head_dz_void", kind, h["act"], h["p"].ptr, h["y"].ptr, coef.data_ptr() if coef is not None else None,
+                       self.e.class_w_ptr, gs, B, HW, Cc, self.void_ptr, dz.ptr)
             else:
                 Bp.add("rua_head_dz", kind, h["act"], h["p"].ptr, h["y"].ptr, coef.data_ptr() if coef is not None else None,
                        self.e.class_w_ptr, gs, B, HW, Cc, dz.ptr)
@@ -1657,7 +1681,10 @@ class Graph:
         self.cur_tag = self.loss_plan.scope = None
         seg = self.outputs["seg"]
         if not seg.get("metrics_done"):
-            self.loss_plan.add("rua_seg_metrics", seg["p"].ptr, seg["y"].ptr, seg["x"].M, seg["C"], self.e.scalars_ptr + 8 * 8)
+            if self.void_ptr is not None:
+                self.loss_plan.add("rua_seg_metrics_void", seg["p"].ptr, seg["y"].ptr, self.void_ptr, seg["x"].M, seg["C"], self.e.scalars_ptr + 8 * 8)
+            else:
+                self.loss_plan.add("rua_seg_metrics", seg["p"].ptr, seg["y"].ptr, seg["x"].M, seg["C"], self.e.scalars_ptr + 8 * 8)
         if self.training:
             for step in reversed(self.back_steps):
                 step()
@@ -1808,6 +1835,9 @@ class Engine:
         self._captured, self._captured_eval, self._captured_dp = {}, {}, {}
         self._eval_seen = set()
         self._opt_graph = None
+        iv = spec.ignore_void
+        if iv is not None and (isinstance(iv, bool) or not isinstance(iv, (int, np.integer)) or not 0 <= iv <= 16):
+            raise ValueError(f"ignore_void {iv!r}: None (off) or a margin in 0..16")
         if self.loss is not None and (self.loss.optimizer != spec.optimizer):
             self._t_dev, self._lr_base_dev = -1, None          # device-side step counter / base rate are pushed again
         self.loss = spec
@@ -1872,7 +1902,34 @@ class Engine:
             self.weights_dirty = True
             self._prep_weights(self._stream())
 
-    def _upload(self, g: Graph, x, y):
+    def _check_void(self, x, norm_type, void_mask):
+        """The host-side conditions of a caller-supplied void mask (no-op for None): the public entry points call it before they build or
+        launch anything."""
+        if void_mask is None:
+            return
+        if self.loss is None or self.loss.ignore_void is None:
+            raise ValueError("void_mask needs a model compiled with ignore_void")
+        if isinstance(x, SceneBatch) or norm_type is not None:
+            raise ValueError("void_mask goes with float batches only: class-map and scene batches derive their own mask from the class map")
+        if x is None:
+            raise ValueError("void_mask without a batch")
+        want = (x.shape[0],) + tuple(self.cfg.input_shape[:2])
+        ok = (isinstance(void_mask, np.ndarray) and void_mask.dtype in (np.dtype(np.uint8), np.dtype(np.bool_))) or \
+             (isinstance(void_mask, torch.Tensor) and void_mask.dtype in (torch.uint8, torch.bool))
+        if not ok:
+            raise ValueError(f"void_mask must be a uint8 or bool array, got {getattr(void_mask, 'dtype', type(void_mask))}")
+        if tuple(void_mask.shape) != want:
+            raise ValueError(f"void_mask must have shape {want}, got {tuple(void_mask.shape)}")
+
+    def _upload(self, g: Graph, x, y, void_mask=None):
+        if g.void_u8 is not None and x is not None:
+            # float batches: the caller's mask, or none.  (Uploaded with the batch: x None replays the batch - and the mask - already there.)
+            if void_mask is None:
+                g.void_u8.zero_()
+            else:
+                m = torch.from_numpy(np.ascontiguousarray(void_mask)) if isinstance(void_mask, np.ndarray) else void_mask
+                g.void_u8.copy_(m.to(torch.uint8) if m.dtype == torch.bool else m, non_blocking=bool(m.is_pinned()) and m.dtype == torch.uint8)
+
         def put(dst: torch.Tensor, src):
             if src is None:
                 return
@@ -1924,6 +1981,9 @@ class Engine:
             labels = (cls.data_ptr(), ptr("seg")) + ((ptr("bound"), ptr("dist"), ptr("color")) if mt else (None, None, None))
         L.lib().call("rua_multitask_targets", img.data_ptr(), labels[0], g.B, H, W, Cin, self.cfg.num_classes, int(norm_type), g.x_in.ptr,
                      labels[1], labels[2], labels[3], labels[4], scratch.data_ptr(), scratch.numel(), C.c_void_p(self._stream()))
+        if with_labels and g.void_u8 is not None:           # the batch's void mask, from the class map the targets were made of
+            L.lib().call("rua_void_mask", cls.data_ptr(), g.B, H, W, self.cfg.num_classes, int(self.loss.ignore_void), g.void_ptr,
+                         C.c_void_p(self._stream()))
 
     def _check_scene(self, x, y, norm_type, with_labels: bool = True):
         """The host-side conditions of a scene batch (no-op for any other x): the public entry points call it before they build or
@@ -1960,7 +2020,7 @@ class Engine:
                      rows.ctypes.data, g.B, H, W, Cin, img.data_ptr(), cls.data_ptr() if with_labels else None, C.c_void_p(self._stream()))
         self._compact_targets(g, with_labels, int(norm_type))
 
-    def _put_batch(self, g: Graph, x, y, norm_type: Optional[int], with_labels: bool = True):
+    def _put_batch(self, g: Graph, x, y, norm_type: Optional[int], with_labels: bool = True, void_mask=None):
         """norm_type None: float batch (_upload); 1 or 2: compact uint8 batch (_upload_compact).  x a SceneBatch: _upload_scene
         (y is None: the labels are the pool's class maps; with_labels False: predict)."""
         if isinstance(x, SceneBatch):
@@ -1968,7 +2028,7 @@ class Engine:
                 raise ValueError("a scene batch carries its own labels: y must be None")
             self._upload_scene(g, x, norm_type, with_labels)
         elif norm_type is None:
-            self._upload(g, x, y)
+            self._upload(g, x, y, void_mask)
         elif x is not None:
             self._upload_compact(g, x, y, norm_type)
 
@@ -1987,7 +2047,9 @@ class Engine:
         per = [float(sc[h["slot"]] * h["norm"] / w) for h in g.heads]
         total = sum(self.loss.weight[h["name"]] * v for h, v in zip(g.heads, per))
         M = g.outputs["seg"]["x"].M * w
-        mets = [float(sc[8] / M), float(sc[9]), float(sc[10]), float(sc[11]), float(sc[12])]
+        if g.void_u8 is not None:                           # every valid pixel is counted once per class in TP + FP + TN + FN; no valid pixel: accuracy 0
+            M = float(sc[9] + sc[10] + sc[11] + sc[12]) / g.outputs["seg"]["C"]
+        mets = [float(sc[8] / M) if M > 0 else 0.0, float(sc[9]), float(sc[10]), float(sc[11]), float(sc[12])]
         if self.cfg.multitasking:
             return [total] + per + mets
         return [total] + mets
@@ -1997,11 +2059,12 @@ class Engine:
             self.ow_flag.fill_(v)
             self._ow = v
 
-    def forward_backward(self, x=None, y=None, _whole_step: bool = False, norm_type: Optional[int] = None):
+    def forward_backward(self, x=None, y=None, _whole_step: bool = False, norm_type: Optional[int] = None, void_mask=None):
         """forward + losses + backward on the current stream; gradients are ADDED to self.G (several calls before one optimizer_step accumulate, e.g. the
         replicas of a data-parallel step played one after the other); _whole_step (train_step): the arena is zero and this is the step's only backward.
         norm_type 1 / 2: x, y are a compact batch (uint8 image, uint8 class map; _upload_compact)."""
         self._check_scene(x, y, norm_type)
+        self._check_void(x, norm_type, void_mask)
         # first-writer overwrite needs a ZERO gradient arena: after a standalone forward_backward() (which accumulates) the arena holds
         # unapplied gradients, and the next whole step must accumulate on top of them too (mixing the two calls keeps its old meaning)
         self._set_overwrite(1 if (_whole_step and self.wgrad_overwrite and not self._g_pending) else 0)
@@ -2011,7 +2074,7 @@ class Engine:
         self._last_B = B
         g = self.graph(B, True)
         s = self._stream()
-        self._put_batch(g, x, y, norm_type)
+        self._put_batch(g, x, y, norm_type, void_mask=void_mask)
         self._zero_arena(g, s)
         self._prep_weights(s)
         g.fwd.run(s)
@@ -2087,13 +2150,13 @@ class Engine:
         g.bwd.run(s)
         self._launch_optimizer(1.0, s)
 
-    def _graph_step(self, x, y, norm_type: Optional[int] = None):
+    def _graph_step(self, x, y, norm_type: Optional[int] = None, void_mask=None):
         """Single-GPU fast path: the whole step (arena zeroing, weight refresh, forward, losses, backward, optimizer)
         captured once into a HIP graph and replayed; only the input upload and the lr scalar stay outside."""
         B = x.shape[0] if x is not None else self._last_B
         self._last_B = B
         g = self.graph(B, True)
-        self._put_batch(g, x, y, norm_type)
+        self._put_batch(g, x, y, norm_type, void_mask=void_mask)
         self._set_lr()
         self._set_overwrite(1 if (self.wgrad_overwrite and not self._g_pending) else 0)
         self._g_pending = False                             # the step's optimizer launch zeroes the arena
@@ -2134,14 +2197,14 @@ class Engine:
             torch.cuda.synchronize()
             return None
 
-    def _graph_step_dp(self, x, y, norm_type: Optional[int] = None):
+    def _graph_step_dp(self, x, y, norm_type: Optional[int] = None, void_mask=None):
         """Data-parallel fast path: the step is cut at the launches after which a gradient bucket is complete; every
         piece is its own HIP graph, the bucket all-reduces are issued eagerly between the replays on the reducer's side
         stream (RCCL stays outside the captures), so they overlap the next pieces exactly like in the eager path."""
         B = x.shape[0] if x is not None else self._last_B
         self._last_B = B
         g = self.graph(B, True)
-        self._put_batch(g, x, y, norm_type)
+        self._put_batch(g, x, y, norm_type, void_mask=void_mask)
         red = self.dist.reducer
         pieces = self._captured_dp.get(B)
         if pieces is None:
@@ -2216,30 +2279,33 @@ class Engine:
         self.weights_dirty = True
         return g
 
-    def train_step(self, x=None, y=None, fetch: bool = True, norm_type: Optional[int] = None):
+    def train_step(self, x=None, y=None, fetch: bool = True, norm_type: Optional[int] = None, void_mask=None):
         """One Keras train_on_batch (train_ISPRS.py:131,148): returns the metric list in the reference's order.
         norm_type 1 / 2: x, y are a compact batch - uint8 image [B,H,W,Cin], uint8 class map [B,H,W] - whose float input and targets
         are built on the device (_upload_compact) before the step.  x a scenes.SceneBatch (y None, norm_type 1 / 2): the patches are cut
-        from the resident scenes on the device (_upload_scene)."""
+        from the resident scenes on the device (_upload_scene).  void_mask (float batches of a model compiled with ignore_void): uint8 or bool
+        [B,H,W], non-zero = void; class-map and scene batches derive theirs from the class map (rua_void_mask)."""
         self._check_scene(x, y, norm_type)
+        self._check_void(x, norm_type, void_mask)
         if self.use_graph and self.dist is None:
-            g = self._graph_step(x, y, norm_type)
+            g = self._graph_step(x, y, norm_type, void_mask)
             return self._results(g) if fetch else None
         if self.use_graph and self.dp_graph and not self.dist.host_staged:
-            g = self._graph_step_dp(x, y, norm_type)
+            g = self._graph_step_dp(x, y, norm_type, void_mask)
             return self._results(g) if fetch else None
-        g = self.forward_backward(x, y, _whole_step=True, norm_type=norm_type)
+        g = self.forward_backward(x, y, _whole_step=True, norm_type=norm_type, void_mask=void_mask)
         if self.dist is not None:
             self.dist.reduce_gradients(self)
         self.optimizer_step(1.0 / self.world)
         return self._results(g) if fetch else None
 
-    def test_step(self, x, y, norm_type: Optional[int] = None):
-        """Keras test_on_batch (train_ISPRS.py:167,186): BN uses moving statistics, nothing is updated.  norm_type: as train_step."""
+    def test_step(self, x, y, norm_type: Optional[int] = None, void_mask=None):
+        """Keras test_on_batch (train_ISPRS.py:167,186): BN uses moving statistics, nothing is updated.  norm_type, void_mask: as train_step."""
         self._check_scene(x, y, norm_type)
+        self._check_void(x, norm_type, void_mask)
         g = self.graph(x.shape[0], False)
         s = self._stream()
-        self._put_batch(g, x, y, norm_type)
+        self._put_batch(g, x, y, norm_type, void_mask=void_mask)
         self._zero_arena(g, s)
         self._prep_weights(s)
         g.fwd.run(s)

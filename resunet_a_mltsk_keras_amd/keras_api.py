@@ -212,6 +212,18 @@ def compact_batch(x, y):
     return x, y
 
 
+def void_margin(ignore_void) -> Optional[int]:
+    """compile(ignore_void=...) as LossSpec.ignore_void: None / False -> None (off), True -> labels.VOID_MARGIN, an int 0..16 -> itself."""
+    from .labels import VOID_MARGIN
+    if ignore_void is None or ignore_void is False:
+        return None
+    if ignore_void is True:
+        return VOID_MARGIN
+    if not isinstance(ignore_void, (int, np.integer)) or not 0 <= ignore_void <= 16:
+        raise ValueError(f"ignore_void {ignore_void!r}: None, True (margin {VOID_MARGIN}) or a margin in 0..16")
+    return int(ignore_void)
+
+
 # ---- the model ---------------------------------------------------------------------------------------
 class Model:
     """Keras-Model duck type over the recorded HIP plan."""
@@ -249,7 +261,11 @@ class Model:
     def count_params(self):
         return self.engine.count_params()
 
-    def compile(self, optimizer=None, loss=None, loss_weights=None, metrics=None, **_):
+    def compile(self, optimizer=None, loss=None, loss_weights=None, metrics=None, ignore_void=None, **_):
+        """ignore_void None: off.  True or a margin 0..16 (True = labels.VOID_MARGIN, 2): void pixels - a class value >= num_classes in a
+        class-map or scene batch, dilated by the margin; the void_mask of a float batch - leave every head's loss, the gradients and the
+        metrics.  The option is NOT stored in .h5 files: a loaded model is compiled without it, compile() again to set it."""
+        margin = void_margin(ignore_void)
         if optimizer is None or isinstance(optimizer, str):
             optimizer = {"adam": Adam, "sgd": SGD}[optimizer or "adam"]()
         self.optimizer = optimizer
@@ -267,7 +283,7 @@ class Model:
             weights.update({h: float(loss_weights[h]) for h in heads if h in loss_weights})
         spec = LossSpec(kind=kinds, weight=weights, class_weights=cw, optimizer=optimizer.kind, lr=optimizer.lr.value,
                         beta_1=getattr(optimizer, "beta_1", 0.9), beta_2=getattr(optimizer, "beta_2", 0.999),
-                        momentum=getattr(optimizer, "momentum", 0.0))
+                        momentum=getattr(optimizer, "momentum", 0.0), ignore_void=margin)
         self.engine.compile(spec)
         self._finish_compile()
 
@@ -320,19 +336,31 @@ class Model:
         x, y = self._local_batch(x, y, local_shard)
         return x, y, (int(norm_type) if cb is not None else None)
 
-    def train_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, **_):
+    def _void(self, x, y, void_mask, local_shard):
+        """This rank's void mask (None: none), refused - before anything is uploaded or launched - where it has no meaning: a model compiled
+        without ignore_void, a class-map or scene batch (those derive their own mask), a wrong shape or dtype."""
+        if void_mask is None:
+            return None
+        cb = None if isinstance(x, SceneBatch) else compact_batch(x, y)
+        self.engine._check_void(x, 1 if (cb is not None or isinstance(x, SceneBatch)) else None, void_mask)
+        return self._local_batch(void_mask, None, local_shard)[0]
+
+    def train_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, void_mask=None, **_):
         """y an integer class map [B,H,W] (x then uint8 [B,H,W,Cin]): the compact path - x / norm_type and the targets seg, bound, dist
-        and color (labels.py) are built on the GPU."""
+        and color (labels.py) are built on the GPU.  void_mask (float batches, compile(ignore_void=...)): uint8 or bool [B,H,W], non-zero =
+        void; sharded like y under data parallel."""
         assert self._compiled, "compile() first"
         self._sync_lr()
+        vm = self._void(x, y, void_mask, local_shard)
         x, y, nt = self._batch(x, y, norm_type, local_shard)
-        res = self.engine.train_step(x, y, norm_type=nt)
+        res = self.engine.train_step(x, y, norm_type=nt, void_mask=vm)
         return dict(zip(self.metrics_names, res)) if return_dict else res
 
-    def test_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, **_):
+    def test_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, void_mask=None, **_):
         assert self._compiled, "compile() first"
+        vm = self._void(x, y, void_mask, local_shard)
         x, y, nt = self._batch(x, y, norm_type, local_shard)
-        res = self.engine.test_step(x, y, norm_type=nt)
+        res = self.engine.test_step(x, y, norm_type=nt, void_mask=vm)
         return dict(zip(self.metrics_names, res)) if return_dict else res
 
     def predict(self, x, batch_size=1, norm_type=None, **_):

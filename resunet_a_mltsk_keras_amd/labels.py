@@ -92,6 +92,26 @@ def get_distance_label(label: np.ndarray) -> np.ndarray:
     return out
 
 
+VOID_MARGIN = 2        # Canny + the 3x3 cross put a boundary target at most 2 pixels (Chebyshev) into the labelled side of a class / void interface
+
+
+def host_void_mask(cls: np.ndarray, num_classes: int, margin: int = VOID_MARGIN) -> np.ndarray:
+    """uint8 [N,H,W] void mask of uint8 class maps [N,H,W]: 255 where a pixel of the same patch within Chebyshev distance `margin`
+    has a class value >= num_classes ("no class"), else 0.  Pixels outside the patch are not void, patches never leak into each
+    other; margin 0 is exactly cls >= num_classes.  The definition rua_void_mask reproduces bit for bit."""
+    cls = np.asarray(cls)
+    if cls.dtype != np.uint8 or cls.ndim != 3:
+        raise ValueError(f"class maps are uint8 [N,H,W], got {cls.dtype} {cls.shape}")
+    if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or not 0 <= margin <= 16:
+        raise ValueError(f"margin {margin!r} outside 0..16")
+    if not 1 <= num_classes <= 255:
+        raise ValueError(f"num_classes {num_classes} outside 1..255")
+    void = cls >= num_classes
+    if margin:
+        void = ndimage.maximum_filter(void.astype(np.uint8), size=(1, 2 * margin + 1, 2 * margin + 1), mode="constant", cval=0) > 0
+    return np.where(void, 255, 0).astype(np.uint8)
+
+
 _SDIV = np.zeros(256, np.int64)
 _HDIV = np.zeros(256, np.int64)
 _i = np.arange(1, 256)

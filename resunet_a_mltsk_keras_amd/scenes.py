@@ -1161,8 +1161,11 @@ def materialize(root: str, dst: str, patch, stride: int, data_aug: bool, chunk: 
 
 
 # ---- the reference's inputs -------------------------------------------------------------------------------------------------
-def colours_to_classes(ref_hwc: np.ndarray, colours=None) -> np.ndarray:
-    """uint8 class map of a colour-coded H x W x 3 label image; ValueError naming the first (row-major) pixel of an unknown colour."""
+def colours_to_classes(ref_hwc: np.ndarray, colours=None, unknown: str = "error") -> np.ndarray:
+    """uint8 class map of a colour-coded H x W x 3 label image.  unknown "error": ValueError naming the first (row-major) pixel of an
+    unknown colour; "void": such pixels become 255, "no class" (the ISPRS benchmark's clutter (255, 0, 0) is in neither colour table)."""
+    if unknown not in ("error", "void"):
+        raise ValueError(f"unknown={unknown!r}: 'error' or 'void'")
     colours = ISPRS_COLOURS if colours is None else colours
     a = np.asarray(ref_hwc)
     if a.ndim != 3 or a.shape[2] != 3:
@@ -1174,14 +1177,17 @@ def colours_to_classes(ref_hwc: np.ndarray, colours=None) -> np.ndarray:
         m = key == ((r << 16) | (g << 8) | b)
         out[m] = v
         known |= m
-    if not known.all():
+    if unknown == "void":
+        out[~known] = 255
+    elif not known.all():
         i, j = np.unravel_index(int(np.argmin(known)), known.shape)
         raise ValueError(f"unknown colour {tuple(int(v) for v in a[i, j])} at row {i}, column {j}: not one of {sorted(colours)}")
     return out
 
 
-def convert_reference_inputs(image_chw: np.ndarray, reference_chw: np.ndarray):
-    """(uint8 H x W x C image, uint8 H x W class map) from the reference's C x H x W Image_Train / Reference_Train arrays."""
+def convert_reference_inputs(image_chw: np.ndarray, reference_chw: np.ndarray, unknown: str = "error"):
+    """(uint8 H x W x C image, uint8 H x W class map) from the reference's C x H x W Image_Train / Reference_Train arrays
+    (unknown: colours_to_classes)."""
     if image_chw.ndim != 3 or reference_chw.ndim != 3:
         raise ValueError(f"C x H x W arrays expected, got {image_chw.shape} and {reference_chw.shape}")
     if image_chw.dtype != np.uint8:
@@ -1189,7 +1195,7 @@ def convert_reference_inputs(image_chw: np.ndarray, reference_chw: np.ndarray):
     if image_chw.shape[1:] != reference_chw.shape[1:]:
         raise ValueError(f"image is {image_chw.shape[1:]}, reference {reference_chw.shape[1:]}")
     img = np.ascontiguousarray(image_chw.transpose(1, 2, 0))
-    return img, colours_to_classes(reference_chw.transpose(1, 2, 0))
+    return img, colours_to_classes(reference_chw.transpose(1, 2, 0), unknown=unknown)
 
 
 def _yes(v) -> bool:
@@ -1211,8 +1217,10 @@ def main(argv=None) -> int:
     p.add_argument("-ps", "--patch_size", type=int, default=256)
     p.add_argument("--stride", type=int, default=32)
     p.add_argument("--data_aug", type=_yes, default=True)
+    p.add_argument("--unknown_colour", choices=["error", "void"], default="error",
+                   help="a label colour outside the table: refuse it (error), or write class 255, 'no class' (void; train with --ignore_void yes)")
     a = p.parse_args(argv)
-    img, cls = convert_reference_inputs(np.load(a.image), np.load(a.reference))
+    img, cls = convert_reference_inputs(np.load(a.image), np.load(a.reference), unknown=a.unknown_colour)
     save_scene_dir(a.dst, [a.name], [img], [cls])
     print(f"scene {a.name}: {img.shape[0]} x {img.shape[1]} x {img.shape[2]} written to {a.dst}")
     if a.materialize:

@@ -100,7 +100,24 @@ def build_parser():
     p.add_argument("--balance_class", type=int, default=None, metavar="K",
                    help="scene directory: train only on windows in which class K covers at least --balance_percent of the pixels")
     p.add_argument("--balance_percent", type=float, default=None, metavar="P", help="balance_class: the share of the window, in percent")
+    p.add_argument("--ignore_void", type=str2bool, default=False,
+                   help="class-map layouts (--compact_dataset / --scene_dataset yes): pixels whose class value is >= --num_classes are no label; they leave every loss, gradient and metric")
+    p.add_argument("--void_margin", type=int, default=2, metavar="N",
+                   help="ignore_void: pixels within N (Chebyshev, 0..16) of a void pixel are void too; 2 covers the boundary target's reach across a class / void interface")
     return p
+
+
+def check_void_flags(args):
+    """--ignore_void / --void_margin checked against the rest of the command line, before anything is loaded: returns the margin, or None (off)."""
+    if not args.ignore_void:
+        return None
+    if not (args.compact_dataset or args.scene_dataset):
+        sys.exit("--ignore_void yes reads the void pixels off a class map: it needs --compact_dataset yes or --scene_dataset yes (the float layout has none)")
+    if args.checkpoint_path is not None:
+        sys.exit("--ignore_void: the option is not stored in a checkpoint, and --checkpoint_path compiles the model from the checkpoint")
+    if not 0 <= args.void_margin <= 16:
+        sys.exit(f"--void_margin {args.void_margin} outside 0..16")
+    return args.void_margin
 
 
 def check_class_flags(args):
@@ -308,6 +325,7 @@ def main(argv=None):
     if args.random_aug and not args.scene_dataset:
         sys.exit("--random_aug yes resamples windows of resident scenes: it needs --scene_dataset yes")
     class_weights = check_class_flags(args)
+    void_margin = check_void_flags(args)
     import torch
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -386,10 +404,12 @@ def main(argv=None):
             lw = {"seg": 1.0, "bound": args.bound_weight, "dist": args.dist_weight, "color": args.color_weight}
             say(f"Loss Weights: {lw}")
             model.compile(optimizer=optm, loss={"seg": loss, "bound": loss_bound, "dist": loss_reg, "color": loss_reg},
-                          loss_weights=lw, metrics={"seg": ["accuracy"]})
+                          loss_weights=lw, metrics={"seg": ["accuracy"]}, ignore_void=void_margin)
         else:
             say("Using simple ResUnet-a")
-            model.compile(optimizer=optm, loss=loss, metrics=["accuracy"])
+            model.compile(optimizer=optm, loss=loss, metrics=["accuracy"], ignore_void=void_margin)
+        if void_margin is not None:
+            say(f"Void pixels (class value >= {args.num_classes}, margin {void_margin}) are ignored")
         say("ResUnet-a compiled!")
     else:
         say(f"[INFO] loading {args.checkpoint_path}...")
