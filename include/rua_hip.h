@@ -365,7 +365,7 @@ int rua_upsample_nearest(const void* x, void* y, int N, int H, int W, int C, int
 
 /* ---- elementwise ------------------------------------------------------------------------- */
 int rua_add_n(int n, const void* const* in, void* out, int accumulate, int64_t elems, int dtype, void* stream);
-int rua_relu_mask(void* dy, const void* y, int64_t elems, int dtype, void* stream);   /* dy *= (y>0) */
+int rua_relu_mask(void* dy, const void* y, int64_t elems, int dtype, void* stream);   /* dy = y > 0 ? dy : +0 - a select, not a product: an Inf or NaN in dy leaves as +0 where y <= 0 */
 int rua_relu(const void* x, void* y, int64_t elems, int dtype, void* stream);
 int rua_cast_f32_to(const float* x, void* y, int64_t elems, int dtype, void* stream);
 int rua_cast_to_f32(const void* x, float* y, int64_t elems, int dtype, void* stream);

@@ -1241,7 +1241,7 @@ extern "C" int rua_add_n(int n, const void* const* in, void* out, int accumulate
   return RUA_OK;
 }
 
-template <typename T, int MODE>   // 0: dy *= (y>0) in place ; 1: out = relu(x)
+template <typename T, int MODE>   // 0: dy = y > 0 ? dy : +0 in place (a select: Inf / NaN in dy do not survive y <= 0) ; 1: out = relu(x)
 __global__ void relu_kernel(unsigned char* a, const unsigned char* b, long long pieces) {
   constexpr int VEC = ET<T>::VEC;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < pieces; i += (long long)gridDim.x * blockDim.x) {

@@ -1055,13 +1055,19 @@ def test_metrics_and_optimizers():
     th = rng.standard_normal(n).astype(np.float32); g = rng.standard_normal(n).astype(np.float32)
     thd, gd, md, vd = f(th), f(g), f(np.zeros(n)), f(np.zeros(n))
     e_th, e_m, e_v = th.astype(np.float64), np.zeros(n), np.zeros(n)
+    # the moments against the betas the kernel receives: float32(0.999) leaves 1 - beta2 1.3e-5 (relative) off 0.001, more than the rtol below
+    b1f, b2f = float(np.float32(0.9)), float(np.float32(0.999))
+    r_m, r_v = np.zeros(n), np.zeros(n)
     for step in (1, 2):
         lr_t = 1e-3 * np.sqrt(1 - 0.999 ** step) / (1 - 0.9 ** step)
         gd.copy_(f(g))
         lib.call("rua_adam_step", thd.data_ptr(), gd.data_ptr(), md.data_ptr(), vd.data_ptr(), n, lr_t, None, 0.9, 0.999, 1e-7, 0.5, 1, stream())
         e_th, e_m, e_v = nv.adam_step(e_th, 0.5 * g.astype(np.float64), e_m, e_v, step, 1e-3)
+        _, r_m, r_v = nv.adam_step(e_th, 0.5 * g.astype(np.float64), r_m, r_v, step, 1e-3, b1f, b2f)
     torch.cuda.synchronize()
     assert np.allclose(thd.cpu().numpy(), e_th, rtol=1e-5, atol=1e-6)
+    assert np.allclose(md.cpu().numpy(), r_m, rtol=1e-5, atol=0)
+    assert np.allclose(vd.cpu().numpy(), r_v, rtol=1e-5, atol=0)
     assert float(gd.abs().max()) == 0.0
     thd, gd, vd = f(th), f(g), f(np.zeros(n))
     lib.call("rua_sgd_step", thd.data_ptr(), gd.data_ptr(), vd.data_ptr(), n, 0.1, None, 0.8, 1.0, 0, stream())
