@@ -645,7 +645,16 @@ int rua_graph_kernel_nodes(void* graph, int* kernels, int* total);
 
 /* ---- tuning switches (experiments, A/B runs).  The launchers never read the environment and keep no other global
  * state: a heuristic changes only through this call.  Keys: rua_tuning_key(0..) until NULL.  Grid-size keys
- * ("*_blocks", "*_target", "*_grid") default to 0 = derived from the device's compute-unit count. */
+ * ("*_blocks", "*_target", "*_grid") default to 0 = derived from the device's compute-unit count.
+ * The keys (meaning and default of each: struct RuaTuning, csrc/common.h; any other name is RUA_ERR_ARG):
+ *   conv_force_bn, conv_force_bm, conv_dma, conv_pw, conv_pw_minm, conv_pw_blocks, conv_halo, conv_dmap,
+ *   dmap_target, dmap_fused_finish, dmap_rowb, dmap_bm64, wgrad_pw, wgpw_blocks, wgpw_r, wgd_blocks,
+ *   wgrad_dmap, wgd_mintiles, wgrad_blocks, bn_grid, tani_vec, metrics_blocks, stem_blocks, head_blocks,
+ *   conv_img, conv_strip, wgrad_slabs, strip_narrow_maxd, conv_group, wgrad_group, wgrad_batch_blocks,
+ *   wgd_ks_slow, head_fwd2, head_fwd3, head_fwd3_bpc, stem_reg, stats_blocks, conv_band, conv_band64,
+ *   conv_band64m, strip_group_share, band_dbg, fill_kernel, bn_regs, wgrad_taps_share, dmap_chain, epi_fast,
+ *   dmap_spread, bn_bwd_group, conv_small, strip_stag, cu_reserve, wgrad_rows, strip_seglen, band_stag,
+ *   conv_band128m, conv_img2, dbg_ptr */
 int rua_set_tuning(const char* key, int64_t value);
 int rua_get_tuning(const char* key, int64_t* value);
 const char* rua_tuning_key(int index);

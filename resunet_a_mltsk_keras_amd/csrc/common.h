@@ -72,8 +72,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 struct RuaTuning {
   int conv_force_bn = 0, conv_force_bm = 0, conv_dma = -1, conv_pw = 1;
   long long conv_pw_minm = 65536;
-  int conv_pw_blocks = 0, conv_halo = 1, halo64_maxd = 0 /* conv_halo<64> at d = 1 was 28 vs 34 us alone, but as the 4th member of the
-                                                              grouped conv_igemm grid the d = 1 branch costs less: +0.35 % on the step */, conv_dmap = 1, dmap_target = 0, dmap_fused_finish = 0, dmap_rowb = 64, dmap_bm64 = 1;
+  int conv_pw_blocks = 0, conv_halo = 1, conv_dmap = 1, dmap_target = 0, dmap_fused_finish = 0, dmap_rowb = 64, dmap_bm64 = 1;
   int wgrad_pw = 3 /* bit 1 (round 5): block partials + the batched reduction instead of replicas, tickets and a finishing block */, wgpw_blocks = 0, wgpw_r = 0, wgd_blocks = 0, wgrad_dmap = 1, wgd_mintiles = 10 /* 9 took the 64x64x128 level too: a wash alone, -0.55 % in the step since its K slabs (28 x 0.6 MB) */, wgrad_blocks = 0;
   int bn_grid = 0, tani_vec = 1, metrics_blocks = 0, stem_blocks = 0, head_blocks = 0;
   int conv_strip = 1, wgrad_slabs = 1, strip_narrow_maxd = 0, strip_group_share = 1;
@@ -88,14 +87,9 @@ struct RuaTuning {
   int conv_img = 0;                     // 1: conv_img - the 3x3 convolutions of the 8 x 8 / 16 x 16 levels with a whole image resident in LDS instead of conv_dmap + split K (measured level: 28 - 29 us either way)
   int conv_small = 4096;                // conv_small serves 1x1 convolutions of at most this many output pixels (0: off)
   int bn_bwd_group = 1;                 // rua_bn_bwd_group: the one-branch BatchNorm backwards of a ResBlock in one grid
-  int dmap_spread = 1;                  // conv_dmap: 0 the DMA instructions of a stage in one burst behind its barrier, 1 spread between the MFMAs (conv_dmap_s), 2 issued by waves of their own (conv_dmap_w; | 4: the 64-row tiles too).
-                                        // Launch by launch 2 is the fastest (8 x 64 x 64 x 128: 18.5 - 20.2 us against 19.3 - 20.7 and 22 - 23; conv_dmap<128,128> 0.665 against 0.72 ms per step summed over
-                                        // its launches), but the STEP is slower with it (8.05 - 8.07 against 8.02 ms on one box): 512-thread blocks of 239 registers leave no room on a CU for the blocks of
-                                        // the launches the step's graph runs beside them
+  int dmap_spread = 1;                  // conv_dmap: 0 the DMA instructions of a stage in one burst behind its barrier, 1 spread between the MFMAs (conv_dmap_s); any other value acts as 0
   int epi_fast = 1;                     // conv_dmap: compile-time forms of the epilogue for whole tiles (conv_epilogue KIND)
   int dmap_chain = 0;                   // grouped conv_dmap members back to back inside one block (conv_dmap_chain): bit 0 the 128-row tiles, bit 1 the 64-row tiles
-  int dmap_group_bm128 = 0;             // grouped conv_dmap members keep 128-row tiles where the group as a whole fills the chip: measured no gain (8.308 vs 8.290 ms per step), off
-  int wgrad_kernel_share = 0;           // the same for the K-split weight gradients (wgrad_kernel) of a group: measured SLOWER (8.47 vs 8.28 ms per step: that kernel is not persistent, fewer K slices = fewer blocks to hide latency with), off
   int wgrad_taps_share = 1;             // all-taps weight gradients of a group share one round of blocks (rua_wgrad_desc.group_members)
   int bn_regs = 1;                      // BatchNorm sweeps with the thread's coefficients in registers (0: read from the LDS table per piece)
   int fill_kernel = 1;                  // rua_fill_zero as a kernel, not hipMemsetAsync: no memset nodes in captured graphs (0: experiments, tools/dp_graph_check.py)
@@ -108,10 +102,10 @@ struct RuaTuning {
                                         // for plain first convolutions, 68 / 88 vs 69 / 92 for data gradients - and SLOWER in the step, 6.62 vs 6.53 ms: its in-place BatchNorm pass runs behind
                                         // the MFMAs of a stage, conv_band64m's between them, and the level-2 first convolutions normalise on load), bit 2 at C = 256 on 32-pixel rows (else grouped conv_dmap),
                                         // bit 3: a rua_conv_fwd of several 3x3 segments at those channel counts (the summed second convolutions of levels 3 - 4) in the same form with the sum kept on chip
-                                        // (else conv_dmap_chain: 40 -> 32 us at level 3, 50 -> 44 at level 4, step -0.024 ms)
+                                        // (else conv_dmap over K x 3: 40 -> 32 us at level 3, 50 -> 44 at level 4, step -0.024 ms)
   int conv_band = 1;                    // rua_conv_fwd_sum: the branches' second convs of a C = 32 ResBlock as ONE launch with the sum kept on chip (conv_band32)
   int wgd_ks_slow = 1;                  // wgrad_dmap block order: K slice slowest (blocks that read the same pixels share an XCD's L2)
-  int wgrad_rows = 127;                 // bit 0: wgrad_rows32 (the all-taps weight gradient at C = 32 on whole rows, W = 256 / 128, one shared LDS-DMA ring), bit 1: wgrad_rows64 (C = 64, W = 128), bit 2: wgrad_rows128, bits 3 - 4: wgrad_img / wgrad_imgs, bit 5: wgrad_rowsx<1> (C = 256 on 32-pixel rows, was wgrad_dmap), bit 6: wgrad_rowsx<0> instead of wgrad_rows128, bit 7 (off): wgrad_rows32 / wgrad_rows64 deal their rows as a slot stream too (WgSlots) - measured: level 2 48 - 50 -> 46 - 50 us per group, level 1 55 - 59 -> 56 - 59 (at d = 1 the cursor work costs the stage loop 10 %, what the short chains of d = 31 gain); 0: wgrad_taps_kernel
+  int wgrad_rows = 127;                 // bit 0: wgrad_rows32 (the all-taps weight gradient at C = 32 on whole rows, W = 256 / 128, one shared LDS-DMA ring), bit 1: wgrad_rows64 (C = 64, W = 128), bit 2: wgrad_rowsx<0> (C = 128 on 64-pixel rows), bits 3 - 4: wgrad_img / wgrad_imgs, bit 5: wgrad_rowsx<1> (C = 256 on 32-pixel rows, was wgrad_dmap), bit 6: accepted and ignored (it chose wgrad_rowsx<0> over the round-4 job-walking kernel, which is gone), bit 7 (off): wgrad_rows32 / wgrad_rows64 deal their rows as a slot stream too (WgSlots) - measured: level 2 48 - 50 -> 46 - 50 us per group, level 1 55 - 59 -> 56 - 59 (at d = 1 the cursor work costs the stage loop 10 %, what the short chains of d = 31 gain); 0: wgrad_taps_kernel
   int cu_reserve = 0;                   // CUs the one-round grids leave free (rua_cu_count() = CUs - cu_reserve): room for RCCL's kernels under data parallel
   int strip_seglen = 0;                 // experiments (tools/bench_conv3x3.py): rows per block of conv_strip, 0 = one round of blocks
   int band_stag = 1;                    // conv_band32s (staggered halves) for full-width BatchNorm + ReLU sums (0: conv_band32; >= 4: that many ring slots)

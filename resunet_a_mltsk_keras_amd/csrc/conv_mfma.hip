@@ -1,5 +1,5 @@
 // Forward and data-gradient convolutions: a segmented implicit GEMM on MFMA (gfx950), channels-last.
-// Kernels: conv_igemm, conv_dma, conv_dmap (+ _s / _w / _chain), conv_halo, conv_pw, conv_img, conv_small, conv_splitk_finish.
+// Kernels: conv_igemm, conv_dma, conv_dmap (+ _s / _chain), conv_halo, conv_pw, conv_img, conv_small, conv_splitk_finish.
 // Exports: rua_conv_fwd, rua_conv_fwd_group and the rua_conv_* queries; rua_splitk_finish_bf16 for conv_img2.hip (common.h).
 // The weight gradients (rua_conv_wgrad, launch_wgrad_taps, ...) live in conv_wgrad.hip, the weight copies in weight_prep.hip.
 //
@@ -741,13 +741,9 @@ __global__ __launch_bounds__(256) void conv_dma(const ConvK p) {
 // without its MFMAs 6.1 us - the two do NOT overlap: the texture path takes one 1-KiB DMA instruction per ~10.6 ns and CU, all four waves issue
 // their eight right behind the barrier and sit in the issue queue ~0.3 us per stage with the MFMA pipes drained.  Four stage buffers: the
 // quarters of stage s + 3 go into the buffer of stage s - 1 while stage s multiplies.
-// SPEC (conv_dmap_w): 512 threads - waves 0-3 read fragments and multiply, waves 4-7 issue the DMA instructions (each the share wave
-// w - 4 issues in the other forms), wait for their landing and meet the consumers at the stage barrier.  A consumer never stands in the
-// texture path's issue queue, a producer never holds an MFMA back; after the K loop the producers end and the four consumer waves run
-// the epilogue (a barrier counts only the waves of a workgroup that are still alive).
-template <int BM, int BN, int ROWB, bool CHAIN = false, bool SPREAD = false, bool SPEC = false>
+template <int BM, int BN, int ROWB, bool CHAIN = false, bool SPREAD = false>
 __device__ __forceinline__ void conv_dmap_body(const ConvK* pk, int nmem) {
-  static_assert(!(SPEC && (CHAIN || SPREAD)), "conv_dmap: one issue form at a time");
+  static_assert(!(CHAIN && SPREAD), "conv_dmap: one issue form at a time");
   typedef bf16_t T;
   const ConvK& p = pk[0];                               // geometry (the same for every member of a chain)
   // a stage = 64 channels, 4 k-steps of 16.  ROWB = 128: one LDS image [rows][128 B], every DMA row a full line;
@@ -775,9 +771,7 @@ __device__ __forceinline__ void conv_dmap_body(const ConvK* pk, int nmem) {
   const int ks_i = vid / (p.nbn * p.nbm);
   const long long m0 = (long long)bm_i * BM;
   const int n0 = bn_i * BN;
-  const int tid = threadIdx.x, lane = tid & 63, wid0 = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool producer = SPEC && wid0 >= 4;
-  const int wid = SPEC ? (wid0 & 3) : wid0;             // consumer w multiplies the tile quarter of wave w, producer w + 4 issues wave w's DMA share
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int HW = p.H * p.W;
 
   // LDS image: [row][8 slots of 16 B]; slot = piece ^ ((row >> 1) & 7) makes the ds_read_b128 fragment reads
@@ -918,31 +912,12 @@ __device__ __forceinline__ void conv_dmap_body(const ConvK* pk, int nmem) {
   }
   st_left = nst;
   enter_segment(); enter_tap();
-  if (SPEC && producer) {                               // ---- the DMA waves: issue, wait for the landing, meet the consumers at the barrier
-    issue_next(0);
-    issue_next(1);
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER_STAGE) : "memory");
-    __builtin_amdgcn_s_barrier();                       // stage 0 is in LDS
-    issue_next(2);
-    int pbuf = 0;
-    for (int st = 0; st < nst; ++st) {
-      asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER_STAGE) : "memory");     // stage st + 1 landed (st + 2 stays in flight)
-      __builtin_amdgcn_s_barrier();                     // ... and every consumer has read its last fragment of stage st
-      issue_next(pbuf);                                 // stage st + 3 into the buffer of stage st
-      pbuf = pbuf + 1 == NBUF ? 0 : pbuf + 1;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the zero fills issued past the end of the K range too: the epilogue reuses this LDS
-    __builtin_amdgcn_s_barrier();
-    return;
-  }
   static_assert(!SPREAD || PER_STAGE % 4 == 0, "SPREAD: a stage's DMA instructions split into four equal parts");
-  if (!SPEC) {
 #pragma unroll
-    for (int b = 0; b < NBUF - 1; ++b) issue_next(b);
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"((NBUF - 2) * PER_STAGE) : "memory");
-  }
+  for (int b = 0; b < NBUF - 1; ++b) issue_next(b);
+  asm volatile("s_waitcnt vmcnt(%0)" :: "n"((NBUF - 2) * PER_STAGE) : "memory");
   __builtin_amdgcn_s_barrier();
-  if (!SPREAD && !SPEC) issue_next(NBUF - 1);
+  if (!SPREAD) issue_next(NBUF - 1);
   bf16x8 fa[2][TM], fb[2][TN];
   load_frags(0, 0, fa[0], fb[0]);
   int buf = 0;
@@ -955,10 +930,6 @@ __device__ __forceinline__ void conv_dmap_body(const ConvK* pk, int nmem) {
       const int cur = kk & 1;
       if (kk < KS - 1) {
         load_frags(buf, kk + 1, fa[cur ^ 1], fb[cur ^ 1]);
-      } else if (SPEC) {                               // the producers waited for stage s + 1; they refill this buffer behind the barrier
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        load_frags(nxt, 0, fa[cur ^ 1], fb[cur ^ 1]);
       } else if (SPREAD) {                             // in flight here: stages s + 1, s + 2 and three quarters of s + 3
         asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" :: "n"(2 * PER_STAGE - PER_STAGE / 4) : "memory");
         __builtin_amdgcn_s_barrier();
@@ -1010,8 +981,7 @@ __device__ __forceinline__ void conv_dmap_body(const ConvK* pk, int nmem) {
     }
   }
   RUA_TS(2);
-  if (SPEC) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   if (CHAIN) return;
 
@@ -1074,8 +1044,6 @@ template <int BM, int BN, int ROWB> __global__ __launch_bounds__(256) void conv_
 template <int BM, int BN, int ROWB> __global__ __launch_bounds__(256) void conv_dmap_g(const ConvKG g) { conv_dmap_body<BM, BN, ROWB>(&g.k[blockIdx.y], 1); }
 template <int BM, int BN, int ROWB> __global__ __launch_bounds__(256) void conv_dmap_s(const ConvK p) { conv_dmap_body<BM, BN, ROWB, false, true>(&p, 1); }
 template <int BM, int BN, int ROWB> __global__ __launch_bounds__(256) void conv_dmap_gs(const ConvKG g) { conv_dmap_body<BM, BN, ROWB, false, true>(&g.k[blockIdx.y], 1); }
-template <int BM, int BN, int ROWB> __global__ __launch_bounds__(512) void conv_dmap_w(const ConvK p) { conv_dmap_body<BM, BN, ROWB, false, false, true>(&p, 1); }
-template <int BM, int BN, int ROWB> __global__ __launch_bounds__(512) void conv_dmap_gw(const ConvKG g) { conv_dmap_body<BM, BN, ROWB, false, false, true>(&g.k[blockIdx.y], 1); }
 template <int BM, int BN, int ROWB> __global__ __launch_bounds__(256) void conv_dmap_chain(const ConvKG g, int nmem) { conv_dmap_body<BM, BN, ROWB, true>(g.k, nmem); }
 
 template <int BM, int BN, int NBUF = RUA_DMAP_NBUF> static constexpr int conv_dmap_smem() {
@@ -1114,29 +1082,25 @@ __device__ __forceinline__ int fdiv(int x, unsigned m, int dv) { return dv == 1 
 
 template <int C, int MAXMT>                           // MAXMT: MFMA row tiles per wave (rows <= MAXMT * 128)
 __global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(C == 64 ? 2 : (MAXMT == 2 ? 4 : 4), C == 64 ? 2 : (MAXMT == 2 ? 6 : 4))))     // = blocks per CU the LDS footprint allows
+__attribute__((amdgpu_waves_per_eu(4, MAXMT == 2 ? 6 : 4)))     // = blocks per CU the LDS footprint allows
 void conv_halo(const HaloK q) {
   typedef bf16_t T;
-  static_assert(C == 32 || C == 64, "conv_halo: C = Cout in {32, 64}");
+  static_assert(C == 32, "conv_halo: C = Cout = 32");
   constexpr int ROWB = C * 2, SPR = ROWB / 16;        // bytes per LDS pixel row, 16-B slots per row
-  constexpr int SW = (C == 32) ? 2 : 1;               // swizzle: slot = piece ^ ((row >> SW) & (SPR - 1)) (conflict-free b128 reads)
-  constexpr int CSTR = 32 + 4;                        // a block computes 32 output channels (C = 64: blockIdx.y picks the half)
+  constexpr int SW = 2;                               // swizzle: slot = piece ^ ((row >> SW) & (SPR - 1)) (conflict-free b128 reads)
+  constexpr int CSTR = 32 + 4;                        // a block computes all 32 output channels
   constexpr int KST = C / 16;                         // k-steps per tap
-  constexpr bool BLDS = (C == 64);                    // weights of the block's 32 output channels: LDS (C = 64) or registers
-  constexpr int B_BYTES = BLDS ? 9 * 32 * ROWB : 0;
-  const int n0 = BLDS ? blockIdx.y * 32 : 0;
   const ConvK& p = q.c;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* sC = reinterpret_cast<float*>(smem);         // aliases the halo images after the MFMA phase
   // fixed carve-up behind the halo / epilogue area (sizes from the launcher): row->pixel table, row->LDS-row table, sub-tile records
   const int halo_b = ((q.NS * q.HP * ROWB + 1023) / 1024) * 1024;
   const int area = 128 * CSTR * 4 > halo_b ? 128 * CSTR * 4 : halo_b;       // the fp32 tile is transposed 128 rows at a time
-  unsigned char* sB = smem + area;                     // [9 taps * 32 output channels][C] bf16, swizzled like the halo rows
-  int* rowtab = reinterpret_cast<int*>(smem + area + B_BYTES);
+  int* rowtab = reinterpret_cast<int*>(smem + area);
   int* subrec = rowtab + q.rows;                      // [NS][4]: n, y0, x0, valid   (halo origin in image coordinates)
   float* sred = reinterpret_cast<float*>(subrec + 4 * 12);
 
-  const int nwg = gridDim.x, bid = blockIdx.x;         // (gridDim.y = output-channel halves)
+  const int nwg = gridDim.x, bid = blockIdx.x;
   const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
   const int vid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -1170,24 +1134,13 @@ void conv_halo(const HaloK q) {
   const int lr = lane & 31, lh = lane >> 5;
   // C = 32: B fragments of ONE kernel row (3 taps) live in registers; the fragment of tap t + 3 is loaded into the
   // registers of tap t right after the MFMAs that consumed it (72 -> 24 VGPRs: one to two more blocks per CU)
-  bf16x8 fb[BLDS ? 1 : 3][BLDS ? 1 : KST];
+  bf16x8 fb[3][KST];
   const unsigned char* wlane = p.seg[0].w + ((size_t)lr * C + lh * 8) * 2;      // this lane's (cout row, k half) in tap 0
-  if constexpr (!BLDS) {
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
+  for (int t = 0; t < 3; ++t)
 #pragma unroll
-      for (int ks = 0; ks < KST; ++ks)
-        fb[t][ks] = *reinterpret_cast<const bf16x8*>(wlane + ((size_t)t * C * C + ks * 16) * 2);
-  } else {
-    // 288 rows (tap, output channel) x 128 B -> LDS by DMA, 8 rows per wave-instruction, same source-side swizzle
-    const __amdgpu_buffer_rsrc_t rw_ = make_rsrc(p.seg[0].w, p.seg[0].wbytes);
-    for (int it = wid; it < 9 * 32 / 8; it += 4) {
-      const int row = it * 8 + (lane >> 3), slot = lane & 7;
-      const int t = row >> 5, co = row & 31;
-      const unsigned off = (unsigned)((((t * C + n0 + co) * C) + ((slot ^ ((row >> SW) & (SPR - 1))) * 8)) * 2);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw_, (lds_void_p)(sB + it * 1024), 16, off, 0, 0, 0);
-    }
-  }
+    for (int ks = 0; ks < KST; ++ks)
+      fb[t][ks] = *reinterpret_cast<const bf16x8*>(wlane + ((size_t)t * C * C + ks * 16) * 2);
 
   // ---- halo images: HBM/L2 -> LDS, one pass (lane-linear destination, swizzle on the source piece) ------------------
   {
@@ -1238,15 +1191,11 @@ void conv_halo(const HaloK q) {
         const int row = r0[a] + toff;
         fa[a] = *reinterpret_cast<const bf16x8*>(smem + row * ROWB + (((ks * 2 + lh) ^ ((row >> SW) & (SPR - 1))) * 16));
       }
-      bf16x8 fbv;
-      if constexpr (BLDS) fbv = *reinterpret_cast<const bf16x8*>(sB + (t * 32 + lr) * ROWB + (((ks * 2 + lh) ^ ((lr >> SW) & (SPR - 1))) * 16));
-      else fbv = fb[t % 3][ks];
+      const bf16x8 fbv = fb[t % 3][ks];
 #pragma unroll
       for (int a = 0; a < MAXMT; ++a)          // unconditional (a branch around MFMAs makes hipcc shuttle the accumulators):
         acc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[a], fbv, acc[a], 0, 0, 0);     // a missing row tile computes garbage, never stored
-      if constexpr (!BLDS) {
-        if (t < 6) fb[t % 3][ks] = *reinterpret_cast<const bf16x8*>(wlane + ((size_t)(t + 3) * C * C + ks * 16) * 2);
-      }
+      if (t < 6) fb[t % 3][ks] = *reinterpret_cast<const bf16x8*>(wlane + ((size_t)(t + 3) * C * C + ks * 16) * 2);
     }
   }
   // ---- epilogue, 128 rows (one row tile per wave) at a time: a small fp32 tile keeps LDS per block low (more blocks per CU) --
@@ -1263,7 +1212,7 @@ void conv_halo(const HaloK q) {
     }
     __syncthreads();
     // tile rows of pass a: row tile (wid + 4a) of wave wid sits at LDS rows wid*32.., i.e. tile row r <-> m = (a*4 + r/32)*32 + r%32
-    conv_epilogue<T, 128, 32>(p, 0, n0, vid, sC, CSTR, sred, rowtab + a * 128, q.rows - a * 128, carry, a == MAXMT - 1);
+    conv_epilogue<T, 128, 32>(p, 0, 0, vid, sC, CSTR, sred, rowtab + a * 128, q.rows - a * 128, carry, a == MAXMT - 1);
   }
 }
 
@@ -1372,30 +1321,13 @@ template <int BM, int BN, int ROWB> static int launch_conv_dmap(const ConvK& k, 
     if constexpr (BM == 128 && ROWB == 64)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dmap_s<BM, BN, ROWB>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 conv_dmap_smem<BM, BN, 4>());
-    if constexpr (ROWB == 64)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dmap_w<BM, BN, ROWB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                conv_dmap_smem<BM, BN>());
     attr_set = true;
   }
-  // DMA waves beside the MFMA waves (conv_dmap_w, 512 threads): the 128-row tiles (2); the 64-row tiles run two blocks per CU that already
-  // fill each other's gaps and would lose the second block to the register file (6: measured 0.39 vs 0.33 ms per step on their group launches)
-  const bool spec = ROWB == 64 && (g_tune.dmap_spread & 2) && (BM == 128 || (g_tune.dmap_spread & 4));
   const bool spread = BM == 128 && ROWB == 64 && g_tune.dmap_spread == 1; // DMA instructions between the MFMAs of the same waves (four stage buffers)
   const int smem = spread ? conv_dmap_smem<BM, BN, 4>() : conv_dmap_smem<BM, BN>();
   if (g_conv_group && (g_tune.conv_group & (BM == 128 ? 4 : 8)) && k.ksplit == 1 && ROWB == 64) {
-    if (!g_conv_group->add(BM == 128 ? (spec ? 4 : spread ? 6 : 1) : (spec ? 5 : 2),     /* capture kinds: 1 / 2 conv_dmap 128- / 64-row tiles, 3 conv_igemm<256,64>, 4 / 5 conv_dmap_w, 6 conv_dmap_s */ (unsigned)(k.nbm * k.nbn), smem, k)) { rua_set_error("rua_conv_fwd_group: more than %d captured members", RUA_MAX_BRANCH); return RUA_ERR_ARG; }
+    if (!g_conv_group->add(BM == 128 ? (spread ? 6 : 1) : 2,     /* capture kinds: 1 / 2 conv_dmap 128- / 64-row tiles, 3 conv_igemm<256,64>, 4 / 5 retired, 6 conv_dmap_s */ (unsigned)(k.nbm * k.nbn), smem, k)) { rua_set_error("rua_conv_fwd_group: more than %d captured members", RUA_MAX_BRANCH); return RUA_ERR_ARG; }
     return RUA_OK;
-  }
-  if constexpr (ROWB == 64) {
-    if (spec) {
-      hipLaunchKernelGGL((conv_dmap_w<BM, BN, ROWB>), dim3(k.nbm * k.nbn * k.ksplit), dim3(512), smem, st, k);
-      RUA_LAUNCH_CHECK("conv_dmap_w");
-      if (k.ksplit > 1 && k.cnt == nullptr) {
-        launch_splitk_finish<bf16_t>(k, st);
-        RUA_LAUNCH_CHECK("conv_splitk_finish");
-      }
-      return RUA_OK;
-    }
   }
   if constexpr (BM == 128 && ROWB == 64) {
     if (spread) hipLaunchKernelGGL((conv_dmap_s<BM, BN, ROWB>), dim3(k.nbm * k.nbn * k.ksplit), dim3(256), smem, st, k);
@@ -1672,11 +1604,7 @@ static bool pick_halo(const rua_conv_desc* d) {
   const int mode = g_tune.conv_halo;      // 0: off (experiments)
   if (!mode || d->dtype != RUA_BF16 || d->nseg != 1) return false;
   const rua_conv_seg& g = d->seg[0];
-  // C = 64: measured against conv_igemm<256,64> on 128x128 maps - d = 1: 28.0 vs 30.3 us, d = 15: 46 vs 29 us (the small
-  // lattices leave 192-row blocks at two per CU), so only the small dilations take the halo kernel there
-  const int maxd64 = g_tune.halo64_maxd;
-  if (g.C == 64 && g.dil > maxd64) return false;
-  return g.taps == 9 && g.up_shift == 0 && (g.C == 32 || g.C == 64) && d->Cout == g.C && d->stride == 1 && d->out_stride == 1 &&
+  return g.taps == 9 && g.up_shift == 0 && g.C == 32 && d->Cout == g.C && d->stride == 1 && d->out_stride == 1 &&
          d->OH == d->H && d->OW == d->W && g.Hs == d->H && g.Ws == d->W && d->H >= 16 && d->W >= 16 &&
          (long long)d->N * d->H * d->W >= 65536;
 }
@@ -1686,7 +1614,7 @@ static unsigned magic_div(int dv) { return dv <= 1 ? 0u : (unsigned)(((1ull << 3
 // minimise padded slots (MFMA waste) with a penalty for halo bytes; at most 384 rows and 40 KiB of halo images per block
 static void halo_tiling(int H, int W, int d, int rowb, int* TH_, int* TW_, int* NS_) {
   const int ny = (H + d - 1) / d, nx = (W + d - 1) / d;
-  const int lim = 41 * 1024;                           // halo images per block (C = 64: + 36 KiB of weights = 2 blocks per CU)
+  const int lim = 41 * 1024;                           // halo images per block
   double best = 1e30;
   int bth = 1, btw = 1;
   for (int th = 1; th <= ny && th <= 32; ++th)
@@ -1723,19 +1651,11 @@ static int launch_conv_halo(const ConvK& k, int dil, hipStream_t st) {
   const int halo_bytes = (q.NS * q.HP * rowb + 1023) / 1024 * 1024;
   const int epi_bytes = 128 * 36 * 4;
   const int area = epi_bytes > halo_bytes ? epi_bytes : halo_bytes;
-  const int smem = area + (Cc == 64 ? 9 * 32 * 128 : 0) + q.rows * 4 + 4 * 12 * 4 + 4 * 4 * 16 * 4;
+  const int smem = area + q.rows * 4 + 4 * 12 * 4 + 4 * 4 * 16 * 4;
   const int blocks = (int)((total + q.NS - 1) / q.NS);
-  static RuaPerDevFlag attr2_, attr3_, attr642_, attr643_;
-  bool &attr2 = attr2_.get(), &attr3 = attr3_.get(), &attr642 = attr642_.get(), &attr643 = attr643_.get();
-  if (Cc == 64) {
-    if (q.rows <= 256) {
-      if (!attr642) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo<64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr642 = true; }
-      hipLaunchKernelGGL((conv_halo<64, 2>), dim3(blocks, 2), dim3(256), smem, st, q);
-    } else {
-      if (!attr643) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo<64, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr643 = true; }
-      hipLaunchKernelGGL((conv_halo<64, 3>), dim3(blocks, 2), dim3(256), smem, st, q);
-    }
-  } else if (q.rows <= 256) {
+  static RuaPerDevFlag attr2_, attr3_;
+  bool &attr2 = attr2_.get(), &attr3 = attr3_.get();
+  if (q.rows <= 256) {
     if (!attr2) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo<32, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr2 = true; }
     hipLaunchKernelGGL((conv_halo<32, 2>), dim3(blocks), dim3(256), smem, st, q);
   } else {
@@ -2173,13 +2093,7 @@ extern "C" int rua_conv_fwd(const rua_conv_desc* d, void* stream) {
     // the unsplit half-chip case (32x32 level: 128 tiles of 128 x 128, 36 stages): 64-row tiles put a block on every CU
     // (measured there: 25.5 / 23.7 / 22.6 us vs 30.1 / 30.0 / 28.6 for d = 1 / d = 15 / plain)
     const int bm64 = g_tune.dmap_bm64;
-    // (the members of a grouped launch fill the chip together: 3 x 128 tiles of 128 x 128 need no 64-row tiles, which stage
-    //  50 % more bytes per FLOP; tuning key dmap_group_bm128)
-    const bool group_fills = g_tune.dmap_group_bm128 && g_conv_group && (g_tune.conv_group & 4) && (long long)g_conv_group->members * tiles >= target;
-    // (dmap_bm64 & 2, experiment: the members of a group whose 128-row tiles fill the chip exactly once take 64-row tiles too - two blocks
-    //  per CU, one in its epilogue while the other multiplies)
-    const bool group64 = (bm64 & 2) && g_conv_group && k.ksplit == 1 && tiles == target;
-    if (((bm64 & 1) && k.ksplit == 1 && tiles < target && tiles * 2 >= target && !group_fills) || group64) {
+    if (bm64 && k.ksplit == 1 && tiles < target && tiles * 2 >= target) {
       k.nbm = (int)((k.M + 63) / 64);
       return launch_conv_dmap<64, 128, 64>(k, st);
     }
@@ -2221,16 +2135,16 @@ extern "C" int rua_conv_group_last_band(void) { return g_group_last_band; }     
 extern "C" int rua_conv_group_band_ok(const rua_conv_desc* d, int n) { return (d && (rua_band64m_ok(d, n) || rua_band128m_ok(d, n))) ? 1 : 0; }   // grids the calling thread's latest rua_conv_fwd_group issued (1: one grid for all members)
 
 template <typename KG, typename F1, typename FG>
-static int issue_group(const ConvGroupCapture& c, const int* idx, int m, F1 single, FG grouped, int smem_attr, hipStream_t st, const char* what, int threads = 256) {
+static int issue_group(const ConvGroupCapture& c, const int* idx, int m, F1 single, FG grouped, int smem_attr, hipStream_t st, const char* what) {
   if (m == 1) {
-    hipLaunchKernelGGL(single, dim3(c.grid[idx[0]]), dim3(threads), c.smem[idx[0]], st, c.k[idx[0]]);
+    hipLaunchKernelGGL(single, dim3(c.grid[idx[0]]), dim3(256), c.smem[idx[0]], st, c.k[idx[0]]);
   } else {
     static RuaPerDevFlag attr[8];                        // per device, not per thread (the instantiations of this template are per kernel pair)
     const int slot = c.kind[idx[0]];
     if (!attr[slot].get()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(grouped), hipFuncAttributeMaxDynamicSharedMemorySize, smem_attr); attr[slot].get() = true; }
     KG g;
     for (int i = 0; i < m; ++i) g.k[i] = c.k[idx[i]];
-    hipLaunchKernelGGL(grouped, dim3(c.grid[idx[0]], m), dim3(threads), c.smem[idx[0]], st, g);
+    hipLaunchKernelGGL(grouped, dim3(c.grid[idx[0]], m), dim3(256), c.smem[idx[0]], st, g);
   }
   RUA_LAUNCH_CHECK(what);
   return RUA_OK;
@@ -2324,8 +2238,6 @@ extern "C" int rua_conv_fwd_group(const rua_conv_desc* d, int n, void* stream) {
     if (chain && cap.kind[i] == 1) rc = issue_chain(cap, idx, m, conv_dmap_chain<128, 128, 64>, conv_dmap_chain_smem<128, 128>(), 0, st);
     else if (chain) rc = issue_chain(cap, idx, m, conv_dmap_chain<64, 128, 64>, conv_dmap_chain_smem<64, 128>(), 1, st);
     else if (cap.kind[i] == 1) rc = issue_group<ConvKG>(cap, idx, m, conv_dmap<128, 128, 64>, conv_dmap_g<128, 128, 64>, conv_dmap_smem<128, 128>(), st, "conv_dmap (group)");
-    else if (cap.kind[i] == 4) rc = issue_group<ConvKG>(cap, idx, m, conv_dmap_w<128, 128, 64>, conv_dmap_gw<128, 128, 64>, conv_dmap_smem<128, 128>(), st, "conv_dmap_w (group)", 512);
-    else if (cap.kind[i] == 5) rc = issue_group<ConvKG>(cap, idx, m, conv_dmap_w<64, 128, 64>, conv_dmap_gw<64, 128, 64>, conv_dmap_smem<64, 128>(), st, "conv_dmap_w (group)", 512);
     else if (cap.kind[i] == 6) rc = issue_group<ConvKG>(cap, idx, m, conv_dmap_s<128, 128, 64>, conv_dmap_gs<128, 128, 64>, conv_dmap_smem<128, 128, 4>(), st, "conv_dmap_s (group)");
     else if (cap.kind[i] == 2) rc = issue_group<ConvKG>(cap, idx, m, conv_dmap<64, 128, 64>, conv_dmap_g<64, 128, 64>, conv_dmap_smem<64, 128>(), st, "conv_dmap (group)");
     else rc = issue_group<ConvKG>(cap, idx, m, conv_igemm<bf16_t, 256, 64>, conv_igemm_g<bf16_t, 256, 64>, conv_smem<bf16_t, 256, 64>(), st, "conv_igemm (group)");

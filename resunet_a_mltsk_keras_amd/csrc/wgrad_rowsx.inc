@@ -1,15 +1,19 @@
-// wgrad_rowsx<MODE> (round 5; included by conv_wgrad.hip behind wgrad_rows128): the whole-row weight gradient of wgrad_rows128 with its rows dealt as ONE stream.
-//   MODE 0: C = Cout = 128 on 64-pixel rows (the level-3 ResBlock, model2.py:105-106) - wgrad_rows128's case;
+// wgrad_rowsx<MODE> (round 5; included by conv_wgrad.hip): the whole-row all-taps weight gradient with its rows dealt as ONE stream.
+//   MODE 0: C = Cout = 128 on 64-pixel rows (the level-3 ResBlock, model2.py:105-106; its input is a materialised BatchNorm output: no normalise-on-load);
 //   MODE 1: C = Cout = 256 on 32-pixel rows (the level-4 ResBlock at 32 x 32, model2.py:107-108; was wgrad_dmap: 128 x 128 tiles per TAP, 22 - 26 us per 9.66 GFLOP).
-// wgrad_rows128 walks (chain, segment) JOBS: a chain is the rows h = r, r + d, ... of one image (there the dilated 3x3 is a plain 3x3 over a sliding window of three
-// rows), and every job drains the ring, refills three rows and starts again.  At d = 15 a chain of a 64-row image has 4 - 5 rows, of a 32-row image 2 - 3: the
+// A block owns whole rows, 128 input channels and a SLICE of 64 output channels: 12 waves = 3 kernel rows x 4 input-channel quarters, six accumulators (2 output-channel
+// halves x 3 tap columns), 24 MFMAs per wave and stage; the input rows (64 pixels x 256 B) and the slice of the dy rows (64 x 128 B, gathered from the wider pixels by
+// the DMA's per-lane source address) stream through one shared ring, one barrier per stage.  256-byte pixels put all four pixel rows of a transposing read on ONE bank
+// group: the 16-byte chunks are XOR-swizzled with bits 0 - 1 of the pixel index (chunk ^ (p & 3) << 2), the 128-byte dy pixels with bit 1 (as wgrad_rows64).
+// The round-4 form of MODE 0 walked (chain, segment) JOBS: a chain is the rows h = r, r + d, ... of one image (there the dilated 3x3 is a plain 3x3 over a sliding window
+// of three rows), and every job drained the ring, refilled three rows and started again.  At d = 15 a chain of a 64-row image has 4 - 5 rows, of a 32-row image 2 - 3: the
 // fill costs more than the work, and whole chains dealt to blocks do not divide evenly (d = 3 at level 3: 24 chains for 42 blocks).  Here the rows of all images
 // and chains form one sequence of SLOTS - per chain its rows and one separator (a row of zeros: the bottom neighbour of the chain's last row and the top
 // neighbour of the next chain's first) -, block b of gx owns slots [U b / gx, U (b + 1) / gx) and streams them through the ring without ever draining it: one
 // barrier per slot, a separator costs a barrier and its (out-of-range, zero-filling) DMA issue and no MFMA.  Three cursors (row being fetched, dy row being
 // fetched, row being multiplied) step through (image, chain, position) with scalar compares; the two divisions of a slot -> cursor decode run once per block.
 // MODE 1: a stage is the same row of TWO images (n, n + N / 2; the K dimension of the product is pixels, so the two rows are just 64 pixels of K): slot layout
-// [32 pixels of A | 16 zero | 32 pixels of B | 16 zero] - the 96 pixels of wgrad_rows128's slot, shifts up to 16 pixels stay inside the zeros - and a block owns
+// [32 pixels of A | 16 zero | 32 pixels of B | 16 zero] - the 96 pixels of a MODE 0 slot (64 + the 32-pixel zero pad), shifts up to 16 pixels stay inside the zeros - and a block owns
 // 64 output channels x 128 INPUT channels (grid.y = 4 slices x 2 halves; the 256-byte half pixels are gathered from the 512-byte pixels by the DMA's per-lane source
 // address, like the 128-byte dy slices): 24 MFMAs per wave and stage on 10 transposing reads per six, as at level 3.  Partials [output-channel 32][block][9][32][C]
 // (the two input-channel halves fill disjoint columns of the same partial) and wgrad_taps_reduce, unchanged.

@@ -88,6 +88,11 @@ def test_tuning_switches_are_the_only_global_state_and_no_environment_reads():
     assert lib.get_tuning("conv_halo") == 0 and lib.get_tuning("conv_pw_minm") == 1 << 40
     lib.set_tuning(conv_halo=1, conv_pw_minm=65536)
     assert lib.dll.rua_set_tuning(b"no_such_key", 1) == -1 and b"unknown key" in lib.dll.rua_last_error()
+    for gone in ("halo64_maxd", "dmap_group_bm128", "wgrad_kernel_share"):                 # switches of removed kernel forms: no silent acceptance
+        assert lib.dll.rua_set_tuning(gone.encode(), 1) == -1 and b"unknown key" in lib.dll.rua_last_error(), gone
+    header = open(os.path.join(ROOT, "include", "rua_hip.h")).read()
+    listed = re.search(r"The keys \([^)]*\):(.*?)\*/", header, re.S).group(1)             # the key list of the tuning comment, nothing else of the header
+    assert sorted(re.findall(r"\w+", listed)) == sorted(keys)                             # ... names exactly the keys the library enumerates
     for f in os.listdir(os.path.join(ROOT, "resunet_a_mltsk_keras_amd", "csrc")):
         assert "getenv" not in open(os.path.join(ROOT, "resunet_a_mltsk_keras_amd", "csrc", f)).read(), f
     # the library exports no collective of its own (one data-parallel path: dist.py over torch.distributed / RCCL)

@@ -301,7 +301,7 @@ def test_conv_wgrad(case, dt):
                                   (2, 40, 256, 32, 31), (1, 256, 256, 32, 15), (3, 7, 128, 32, 3), (8, 16, 256, 32, 1),      # full-width rows at C = 32: wgrad_rows32
                                   (2, 64, 64, 64, 1), (1, 64, 128, 64, 15), (1, 128, 64, 64, 31), (3, 64, 64, 64, 3),
                                   (2, 128, 128, 64, 31), (1, 128, 128, 64, 1), (3, 40, 128, 64, 3),      # C = 64 on 128-pixel rows: wgrad_rows64
-                                  (2, 64, 64, 128, 1), (1, 64, 64, 128, 15), (3, 40, 64, 128, 3), (8, 64, 64, 128, 31)])  # C = 128 on 64-pixel rows: wgrad_rows128
+                                  (2, 64, 64, 128, 1), (1, 64, 64, 128, 15), (3, 40, 64, 128, 3), (8, 64, 64, 128, 31)])  # C = 128 on 64-pixel rows: wgrad_rowsx<0>
 @pytest.mark.parametrize("rows", [127, 255])
 def test_wgrad_all_taps_kernel(case, rows):
     """Top-level weight gradient (C = Cout in {32, 64}, W % 64 == 0, bf16): all nine taps from one LDS halo,
@@ -1077,10 +1077,10 @@ def test_metrics_and_optimizers():
 
 
 @pytest.mark.parametrize("H,W,dil,Cs", [(256, 256, 1, 32), (256, 256, 3, 32), (256, 256, 15, 32), (256, 256, 31, 32), (272, 248, 3, 32),
-                                        (248, 272, 15, 32), (256, 256, 1, 64), (256, 256, 3, 64), (264, 256, 15, 64), (256, 256, 31, 64)])
+                                        (248, 272, 15, 32)])
 @pytest.mark.parametrize("mode", ["residual_stats", "mask_accumulate_stats2"])
 def test_conv_halo_lattice_tiles(H, W, dil, Cs, mode):
-    """The kernel of the two top levels (C = Cout in {32, 64}, bf16): input + halo resident in LDS, dilation by lattice decomposition.
+    """The kernel of the top level (C = Cout = 32, bf16): input + halo resident in LDS, dilation by lattice decomposition.
     Every dilation of the reference's ResBlocks, ragged maps (lattice tiles that overhang the image, residue classes of
     unequal size), and both epilogue families (forward: bias + residual + sum/sum^2; data gradient: ReLU mask from
     aux*scale+shift, accumulate into y, sum g / sum g*aux)."""
@@ -1116,7 +1116,6 @@ def test_conv_halo_lattice_tiles(H, W, dil, Cs, mode):
         d.aux, d.aux_mode, d.mscale, d.mshift, d.accumulate, d.stats_mode = ad.data_ptr(), 2, scd.data_ptr(), shd.data_ptr(), 1, 2
         exp = (conv + rnd(dt, y0).double().numpy()) * ((a * sc + sh) > 0)
         s2 = (exp * a).sum(axis=(0, 1, 2))
-    # (C = 64: conv_halo serves every dilation on request - rua_set_tuning("halo64_maxd", 31) - and none by default)
     # C = 32 with a row that splits into 128 / 256-pixel strips and one epilogue stream goes to conv_strip (its own test below)
     strip = Cs == 32 and W % 128 == 0 and mode == "residual_stats"
     if Cs == 32:
@@ -1124,14 +1123,10 @@ def test_conv_halo_lattice_tiles(H, W, dil, Cs, mode):
     if strip:
         lib.set_tuning(conv_strip=0)                             # this test is about conv_halo: route the shape back to it
         assert lib.raw("rua_conv_kernel_id")(C.byref(d)) == 3
-    if Cs == 64:                                                 # conv_halo<64> is off by default (the grouped conv_igemm grid takes d = 1 too)
-        assert lib.raw("rua_conv_kernel_id")(C.byref(d)) != 3
-        lib.set_tuning(halo64_maxd=31)
-        assert lib.raw("rua_conv_kernel_id")(C.byref(d)) == 3
     try:
         lib.call("rua_conv_fwd", C.byref(d), stream())
     finally:
-        lib.set_tuning(conv_strip=1, halo64_maxd=0)
+        lib.set_tuning(conv_strip=1)
     torch.cuda.synchronize()
     got = y.float().cpu().numpy()
     assert rel_err(got, exp) < tol(dt)
@@ -2149,9 +2144,8 @@ def _band_multi(case):
 
 @pytest.mark.parametrize("N,H,W,Cs,Cout,dil", [(8, 64, 64, 128, 128, 3), (4, 32, 32, 256, 256, 15), (8, 16, 16, 512, 512, 1), (2, 40, 24, 192, 128, 1)])
 def test_conv_dmap_issue_forms_are_bit_identical(N, H, W, Cs, Cout, dil):
-    """conv_dmap's three ways of issuing a stage's DMA instructions (tuning key dmap_spread: 0 one burst behind the stage barrier, 1 a
-    quarter per k-step between the MFMAs with four stage buffers - the default -, 2 / 6 by DMA waves of their own beside the MFMA waves,
-    512-thread blocks) stage the same bytes and multiply in the same order: outputs and statistics are bit for bit the same, with and
+    """conv_dmap's two ways of issuing a stage's DMA instructions (tuning key dmap_spread: 0 one burst behind the stage barrier, 1 a
+    quarter per k-step between the MFMAs with four stage buffers - the default) stage the same bytes and multiply in the same order: outputs and statistics are bit for bit the same, with and
     without a K split, and form 0 is the one the fp64 comparisons of test_conv_fwd were written against."""
     dt = L.RUA_BF16
     lib = L.lib()
@@ -2165,7 +2159,7 @@ def test_conv_dmap_issue_forms_are_bit_identical(N, H, W, Cs, Cout, dil):
     res = {}
     try:
         lib.set_tuning(conv_img2=0)                          # (16 x 16 x 512, d = 1 is conv_img2's by default since round 5: the subject here is conv_dmap)
-        for form in (0, 1, 2, 6):
+        for form in (0, 1):
             lib.set_tuning(dmap_spread=form)
             outs = []
             for kind in ("bias", "mask"):
@@ -2192,7 +2186,7 @@ def test_conv_dmap_issue_forms_are_bit_identical(N, H, W, Cs, Cout, dil):
         lib.set_tuning(dmap_spread=1, conv_img2=1)
     exp = ref_conv_nhwc(rnd(dt, x.float().cpu().numpy()), rnd(dt, w.float().cpu().numpy()), None, dil, 9).numpy() + bias.cpu().numpy().astype(np.float64)
     assert rel_err(res[0][0][0].float().cpu().numpy(), exp) < tol(dt)
-    for form in (1, 2, 6):
+    for form in (1,):
         for k in range(2):
             assert torch.equal(res[form][k][0], res[0][k][0]), (form, k)
             assert np.array_equal(res[form][k][1], res[0][k][1]), (form, k)

@@ -1,6 +1,6 @@
 """Micro-benchmark of the grouped 3x3 weight gradients of the level-3 / level-4 ResBlocks (8 x 64 x 64 x 128 and 8 x 32 x 32 x 256, dilations 1 / 3 / 15) through the C ABI:
-rua_conv_wgrad_group with the reductions deferred (as in the step), for values of the tuning key wgrad_rows - 31: wgrad_rows128 (level 3) / wgrad_dmap (level 4), the
-round-4 kernels; 63: + wgrad_rowsx<1> at level 4; 127: wgrad_rowsx at both - timed back to back (warm) and behind a 512 MB sweep (cold, as inside the step), and the
+rua_conv_wgrad_group with the reductions deferred (as in the step), for values of the tuning key wgrad_rows - 31: wgrad_rowsx<0> at level 3 (bit 2; the
+round-4 kernel that value used to select is gone) and wgrad_dmap at level 4; 63 / 127: + wgrad_rowsx<1> at level 4 - timed back to back (warm) and behind a 512 MB sweep (cold, as inside the step), and the
 results of the forms against each other.
 Usage: python tools/bench_wgrad_rows.py   (BW_REPS=30, BW_LEVELS=3,4, BW_VARIANTS=31,127)"""
 import ctypes as C
