@@ -508,6 +508,29 @@ int rua_scene_windows_affine(const uint8_t* const* scene_img, const uint8_t* con
                              int nscenes, const int32_t* windows /* [N][7] */, int N, int PH, int PW, int Cin,
                              uint8_t* img_out, uint8_t* cls_out, void* stream);
 
+/* ---- colour, tone and noise jitter of the staged windows (scenes.py, host_photometric / photo_rows) ---------------------------
+ * img_in and img_out are DEVICE memory, uint8 [N][PH][PW][Cin] with a 4-byte aligned base - what the two calls above write and the
+ * targets call reads -, either the same pointer (in place) or ranges that do not overlap; photo is a HOST array, int32 [N][16], one
+ * row R per window in Q16:  M[c][d] = R[3 c + d] (colour matrix),  b[c] = R[9 + c] (offsets, in levels),  t = R[12] (tone),
+ * A = R[13] (noise amplitude),  R[14] the noise seed read as uint32,  R[15] reserved, 0.  For source byte p[c] of pixel (i, j), every
+ * >> arithmetic and clamp to [0, 255]:
+ *   colour, Cin == 3:  u[c] = clamp((M[c][0] * p[0] + M[c][1] * p[1] + M[c][2] * p[2] + b[c] + 32768) >> 16)
+ *           Cin != 3:  u[c] = clamp((M[0][0] * p[c] + b[0] + 32768) >> 16)  - the row must be scalar: off-diagonals 0, the three
+ *                      diagonal entries equal, the three offsets equal
+ *   tone:              v[c] = clamp(u[c] + ((t * u[c] * (255 - u[c]) + (1 << 23)) >> 24))   (fixes 0 and 255, monotone for |t| <= 65536)
+ *   noise, A != 0:     idx = (i * PW + j) * Cin + c - the position inside the window, not in the batch;
+ *                      x = uint32(R[14]) + (idx + 1) * 0x9E3779B9 (mod 2^32);  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;
+ *                      x *= 0x846ca68b;  x ^= x >> 16;  z = (x & 255) + ((x >> 8) & 255) + ((x >> 16) & 255) + (x >> 24) - 510;
+ *                      out[c] = clamp(v[c] + ((A * z + 32768) >> 16))      (z in -510..510, standard deviation sqrt((256^2 - 1) / 3))
+ * The row M = 65536 * I, zeros elsewhere, returns the input bytes.  Integers only, so scenes.host_photometric gives the same bytes.
+ * Limits, all checked on the host before anything is launched (a violation: RUA_ERR_ARG, the message names the row and the word):
+ * |M| <= 2^20, |b| <= 2^29, |t| <= 65536, 0 <= A <= 65536, R[15] == 0, 1 <= PH, PW <= 512, 1 <= Cin <= 16, N >= 1,
+ * N*PH*PW*Cin < 2^31 - under them every intermediate fits in 32 bits:  3 * 2^20 * 255 + 2^29 + 2^15 < 2^31,
+ * 65536 * 127 * 128 + 2^23 < 2^31,  65536 * 510 + 2^15 < 2^31.  The rows travel as kernel arguments, 48 per launch: no
+ * device-side table, no copy, no synchronisation.  In place, a window whose row is the identity is left alone. */
+int rua_window_photometric(const uint8_t* img_in, uint8_t* img_out, int N, int PH, int PW, int Cin,
+                           const int32_t* photo /* HOST, [N][16] */, void* stream);
+
 /* ---- whole-scene evaluation: window probabilities -> a uint8 class map per scene and a confusion matrix (scenes.py, predict_table /
  * host_stitch; the reference's test_ISPRS.py:26-87 arg-max, mosaic and confusion_matrix done on the device) ----------------------
  * p is DEVICE memory, fp32 [N][PH][PW][C], 16-byte aligned: the class probabilities of N windows (the seg head's output).  windows

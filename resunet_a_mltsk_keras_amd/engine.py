@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .scenes import MAP_HEADS, AffineSceneBatch, SceneBatch, check_radius, check_tolerance, check_views, view_rows
+from .scenes import MAP_HEADS, AffineSceneBatch, SceneBatch, check_photo_table, check_radius, check_tolerance, check_views, view_rows
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -1921,6 +1921,33 @@ class Engine:
         if tuple(void_mask.shape) != want:
             raise ValueError(f"void_mask must have shape {want}, got {tuple(void_mask.shape)}")
 
+    def _check_photo(self, x, norm_type, photo):
+        """The host-side conditions of a caller-supplied photo table (None for None): the checked int32 [B][16] table of a compact uint8
+        batch.  A float batch has no bytes to jitter and a scene batch carries its own (SceneBatch.with_photo): ValueError, before
+        anything is uploaded or launched."""
+        if photo is None:
+            return None
+        if isinstance(x, SceneBatch):
+            raise ValueError("photo goes with compact uint8 batches only: a scene batch carries its own table (SceneBatch.with_photo)")
+        if norm_type is None:
+            raise ValueError("photo goes with compact uint8 batches only: a float batch (norm_type None) has no bytes to jitter")
+        if x is None:
+            raise ValueError("photo without a batch")
+        t = check_photo_table(photo, int(self.cfg.input_shape[2]))
+        if len(t) != x.shape[0]:
+            raise ValueError(f"{len(t)} photo rows for a batch of {x.shape[0]} patches")
+        return t
+
+    def _apply_photo(self, g: Graph, table: np.ndarray):
+        """rua_window_photometric in place on the staged image of g.compact_buffers(): on the compute stream, behind whatever put
+        the bytes there and in front of _compact_targets, outside any captured graph.  The host passes B * 16 integers."""
+        img = g.compact_buffers()[0]
+        H, W, Cin = self.cfg.input_shape
+        t = np.ascontiguousarray(table, dtype=np.int32)
+        if t.shape != (g.B, 16):
+            raise ValueError(f"photo table of shape {t.shape} for a graph of batch {g.B}")
+        L.lib().call("rua_window_photometric", img.data_ptr(), img.data_ptr(), g.B, H, W, Cin, t.ctypes.data, C.c_void_p(self._stream()))
+
     def _upload(self, g: Graph, x, y, void_mask=None):
         if g.void_u8 is not None and x is not None:
             # float batches: the caller's mask, or none.  (Uploaded with the batch: x None replays the batch - and the mask - already there.)
@@ -1948,9 +1975,9 @@ class Engine:
             else:
                 put(g.heads[0]["y"].t, y)
 
-    def _upload_compact(self, g: Graph, x, y, norm_type: int):
-        """Compact batch: x uint8 [B,H,W,Cin], y uint8 class map [B,H,W] (None: x only).  The bytes go up like _upload's, then
-        rua_multitask_targets writes x (normalised) into g.x_in and seg / bound / dist / color into the heads' label buffers on the
+    def _upload_compact(self, g: Graph, x, y, norm_type: int, photo=None):
+        """Compact batch: x uint8 [B,H,W,Cin], y uint8 class map [B,H,W] (None: x only).  The bytes go up like _upload's (photo, a
+        checked photo table: then rua_window_photometric jitters the image in place), then rua_multitask_targets writes x (normalised) into g.x_in and seg / bound / dist / color into the heads' label buffers on the
         compute stream - in front of the recorded plans, outside any captured graph."""
         img, cls, scratch = g.compact_buffers()
 
@@ -1967,6 +1994,8 @@ class Engine:
         put(img, x)
         if y is not None:
             put(cls, y)
+        if photo is not None:
+            self._apply_photo(g, photo)
         self._compact_targets(g, y is not None, norm_type)
 
     def _compact_targets(self, g: Graph, with_labels: bool, norm_type: int):
@@ -2008,7 +2037,8 @@ class Engine:
         """Scene batch (scenes.SceneBatch: resident scenes + a window table): rua_scene_windows cuts and augments the windows into
         g.compact_buffers(), then the targets call of _upload_compact - both on the compute stream, in front of the recorded plans,
         outside any captured graph.  The host passes B * 4 integers; nothing is copied.  with_labels False: images only (inference).
-        An AffineSceneBatch (B * 7 integers: rotation, zoom and shift) goes through rua_scene_windows_affine in the same place."""
+        An AffineSceneBatch (B * 7 integers: rotation, zoom and shift) goes through rua_scene_windows_affine in the same place.
+        A batch with a photo table (batch.photo, B * 16 integers) gets one in-place rua_window_photometric call between the two."""
         self._check_scene(batch, None, norm_type, with_labels)
         pool = batch.pool
         H, W, Cin = self.cfg.input_shape
@@ -2018,9 +2048,11 @@ class Engine:
         rows = np.ascontiguousarray(batch.rows, dtype=np.int32)
         L.lib().call("rua_scene_windows_affine" if isinstance(batch, AffineSceneBatch) else "rua_scene_windows", pool.img_ptrs, pool.cls_ptrs if with_labels else None, pool.heights, pool.widths, len(pool),
                      rows.ctypes.data, g.B, H, W, Cin, img.data_ptr(), cls.data_ptr() if with_labels else None, C.c_void_p(self._stream()))
+        if batch.photo is not None:
+            self._apply_photo(g, batch.photo)
         self._compact_targets(g, with_labels, int(norm_type))
 
-    def _put_batch(self, g: Graph, x, y, norm_type: Optional[int], with_labels: bool = True, void_mask=None):
+    def _put_batch(self, g: Graph, x, y, norm_type: Optional[int], with_labels: bool = True, void_mask=None, photo=None):
         """norm_type None: float batch (_upload); 1 or 2: compact uint8 batch (_upload_compact).  x a SceneBatch: _upload_scene
         (y is None: the labels are the pool's class maps; with_labels False: predict)."""
         if isinstance(x, SceneBatch):
@@ -2030,7 +2062,7 @@ class Engine:
         elif norm_type is None:
             self._upload(g, x, y, void_mask)
         elif x is not None:
-            self._upload_compact(g, x, y, norm_type)
+            self._upload_compact(g, x, y, norm_type, photo)
 
     def _zero_arena(self, g: Graph, s):
         L.lib().call("rua_fill_zero", self.stats_arena.data_ptr(), g.stats_used * 8, C.c_void_p(s))
@@ -2059,12 +2091,13 @@ class Engine:
             self.ow_flag.fill_(v)
             self._ow = v
 
-    def forward_backward(self, x=None, y=None, _whole_step: bool = False, norm_type: Optional[int] = None, void_mask=None):
+    def forward_backward(self, x=None, y=None, _whole_step: bool = False, norm_type: Optional[int] = None, void_mask=None, photo=None):
         """forward + losses + backward on the current stream; gradients are ADDED to self.G (several calls before one optimizer_step accumulate, e.g. the
         replicas of a data-parallel step played one after the other); _whole_step (train_step): the arena is zero and this is the step's only backward.
-        norm_type 1 / 2: x, y are a compact batch (uint8 image, uint8 class map; _upload_compact)."""
+        norm_type 1 / 2: x, y are a compact batch (uint8 image, uint8 class map; _upload_compact); photo: as train_step."""
         self._check_scene(x, y, norm_type)
         self._check_void(x, norm_type, void_mask)
+        photo = self._check_photo(x, norm_type, photo)
         # first-writer overwrite needs a ZERO gradient arena: after a standalone forward_backward() (which accumulates) the arena holds
         # unapplied gradients, and the next whole step must accumulate on top of them too (mixing the two calls keeps its old meaning)
         self._set_overwrite(1 if (_whole_step and self.wgrad_overwrite and not self._g_pending) else 0)
@@ -2074,7 +2107,7 @@ class Engine:
         self._last_B = B
         g = self.graph(B, True)
         s = self._stream()
-        self._put_batch(g, x, y, norm_type, void_mask=void_mask)
+        self._put_batch(g, x, y, norm_type, void_mask=void_mask, photo=photo)
         self._zero_arena(g, s)
         self._prep_weights(s)
         g.fwd.run(s)
@@ -2150,13 +2183,13 @@ class Engine:
         g.bwd.run(s)
         self._launch_optimizer(1.0, s)
 
-    def _graph_step(self, x, y, norm_type: Optional[int] = None, void_mask=None):
+    def _graph_step(self, x, y, norm_type: Optional[int] = None, void_mask=None, photo=None):
         """Single-GPU fast path: the whole step (arena zeroing, weight refresh, forward, losses, backward, optimizer)
         captured once into a HIP graph and replayed; only the input upload and the lr scalar stay outside."""
         B = x.shape[0] if x is not None else self._last_B
         self._last_B = B
         g = self.graph(B, True)
-        self._put_batch(g, x, y, norm_type, void_mask=void_mask)
+        self._put_batch(g, x, y, norm_type, void_mask=void_mask, photo=photo)
         self._set_lr()
         self._set_overwrite(1 if (self.wgrad_overwrite and not self._g_pending) else 0)
         self._g_pending = False                             # the step's optimizer launch zeroes the arena
@@ -2197,14 +2230,14 @@ class Engine:
             torch.cuda.synchronize()
             return None
 
-    def _graph_step_dp(self, x, y, norm_type: Optional[int] = None, void_mask=None):
+    def _graph_step_dp(self, x, y, norm_type: Optional[int] = None, void_mask=None, photo=None):
         """Data-parallel fast path: the step is cut at the launches after which a gradient bucket is complete; every
         piece is its own HIP graph, the bucket all-reduces are issued eagerly between the replays on the reducer's side
         stream (RCCL stays outside the captures), so they overlap the next pieces exactly like in the eager path."""
         B = x.shape[0] if x is not None else self._last_B
         self._last_B = B
         g = self.graph(B, True)
-        self._put_batch(g, x, y, norm_type, void_mask=void_mask)
+        self._put_batch(g, x, y, norm_type, void_mask=void_mask, photo=photo)
         red = self.dist.reducer
         pieces = self._captured_dp.get(B)
         if pieces is None:
@@ -2279,33 +2312,37 @@ class Engine:
         self.weights_dirty = True
         return g
 
-    def train_step(self, x=None, y=None, fetch: bool = True, norm_type: Optional[int] = None, void_mask=None):
+    def train_step(self, x=None, y=None, fetch: bool = True, norm_type: Optional[int] = None, void_mask=None, photo=None):
         """One Keras train_on_batch (train_ISPRS.py:131,148): returns the metric list in the reference's order.
         norm_type 1 / 2: x, y are a compact batch - uint8 image [B,H,W,Cin], uint8 class map [B,H,W] - whose float input and targets
         are built on the device (_upload_compact) before the step.  x a scenes.SceneBatch (y None, norm_type 1 / 2): the patches are cut
         from the resident scenes on the device (_upload_scene).  void_mask (float batches of a model compiled with ignore_void): uint8 or bool
-        [B,H,W], non-zero = void; class-map and scene batches derive theirs from the class map (rua_void_mask)."""
+        [B,H,W], non-zero = void; class-map and scene batches derive theirs from the class map (rua_void_mask).  photo (compact uint8
+        batches): an int32 [B][16] photo table (scenes.check_photo_table) - the uploaded image is jittered in place
+        (rua_window_photometric) before the targets are built; a scene batch carries its own, a float batch has none: ValueError."""
         self._check_scene(x, y, norm_type)
         self._check_void(x, norm_type, void_mask)
+        photo = self._check_photo(x, norm_type, photo)
         if self.use_graph and self.dist is None:
-            g = self._graph_step(x, y, norm_type, void_mask)
+            g = self._graph_step(x, y, norm_type, void_mask, photo)
             return self._results(g) if fetch else None
         if self.use_graph and self.dp_graph and not self.dist.host_staged:
-            g = self._graph_step_dp(x, y, norm_type, void_mask)
+            g = self._graph_step_dp(x, y, norm_type, void_mask, photo)
             return self._results(g) if fetch else None
-        g = self.forward_backward(x, y, _whole_step=True, norm_type=norm_type, void_mask=void_mask)
+        g = self.forward_backward(x, y, _whole_step=True, norm_type=norm_type, void_mask=void_mask, photo=photo)
         if self.dist is not None:
             self.dist.reduce_gradients(self)
         self.optimizer_step(1.0 / self.world)
         return self._results(g) if fetch else None
 
-    def test_step(self, x, y, norm_type: Optional[int] = None, void_mask=None):
-        """Keras test_on_batch (train_ISPRS.py:167,186): BN uses moving statistics, nothing is updated.  norm_type, void_mask: as train_step."""
+    def test_step(self, x, y, norm_type: Optional[int] = None, void_mask=None, photo=None):
+        """Keras test_on_batch (train_ISPRS.py:167,186): BN uses moving statistics, nothing is updated.  norm_type, void_mask, photo: as train_step."""
         self._check_scene(x, y, norm_type)
         self._check_void(x, norm_type, void_mask)
+        photo = self._check_photo(x, norm_type, photo)
         g = self.graph(x.shape[0], False)
         s = self._stream()
-        self._put_batch(g, x, y, norm_type, void_mask=void_mask)
+        self._put_batch(g, x, y, norm_type, void_mask=void_mask, photo=photo)
         self._zero_arena(g, s)
         self._prep_weights(s)
         g.fwd.run(s)

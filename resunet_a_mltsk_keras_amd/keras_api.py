@@ -345,22 +345,34 @@ class Model:
         self.engine._check_void(x, 1 if (cb is not None or isinstance(x, SceneBatch)) else None, void_mask)
         return self._local_batch(void_mask, None, local_shard)[0]
 
-    def train_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, void_mask=None, **_):
+    def _photo(self, x, y, photo, local_shard):
+        """This rank's photo table (None: none), refused - before anything is uploaded or launched - where it has no meaning: a scene
+        batch (it carries its own, SceneBatch.with_photo) and a float batch (no bytes to jitter)."""
+        if photo is None:
+            return None
+        cb = None if isinstance(x, SceneBatch) else compact_batch(x, y)
+        t = self.engine._check_photo(x, 1 if cb is not None else None, photo)
+        return self._local_batch(t, None, local_shard)[0]
+
+    def train_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, void_mask=None, photo=None, **_):
         """y an integer class map [B,H,W] (x then uint8 [B,H,W,Cin]): the compact path - x / norm_type and the targets seg, bound, dist
         and color (labels.py) are built on the GPU.  void_mask (float batches, compile(ignore_void=...)): uint8 or bool [B,H,W], non-zero =
-        void; sharded like y under data parallel."""
+        void; sharded like y under data parallel.  photo (compact batches): an int32 [B][16] photo table (scenes.photo_rows,
+        PhotoJitter.draw) - the image is jittered on the GPU before x and the targets are built; sharded like y."""
         assert self._compiled, "compile() first"
         self._sync_lr()
         vm = self._void(x, y, void_mask, local_shard)
+        ph = self._photo(x, y, photo, local_shard)
         x, y, nt = self._batch(x, y, norm_type, local_shard)
-        res = self.engine.train_step(x, y, norm_type=nt, void_mask=vm)
+        res = self.engine.train_step(x, y, norm_type=nt, void_mask=vm, photo=ph)
         return dict(zip(self.metrics_names, res)) if return_dict else res
 
-    def test_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, void_mask=None, **_):
+    def test_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, void_mask=None, photo=None, **_):
         assert self._compiled, "compile() first"
         vm = self._void(x, y, void_mask, local_shard)
+        ph = self._photo(x, y, photo, local_shard)
         x, y, nt = self._batch(x, y, norm_type, local_shard)
-        res = self.engine.test_step(x, y, norm_type=nt, void_mask=vm)
+        res = self.engine.test_step(x, y, norm_type=nt, void_mask=vm, photo=ph)
         return dict(zip(self.metrics_names, res)) if return_dict else res
 
     def predict(self, x, batch_size=1, norm_type=None, **_):

@@ -27,6 +27,11 @@ sy = y0 + i * a_yy + j * a_yx, sx = x0 + i * a_xy + j * a_xx, the image bilinear
 reflect padding at the scene border (host_windows_affine is the definition, rua_scene_windows_affine its kernel).  affine_rows()
 makes such rows from [N][4] rows and a rotation / zoom / shift, AffineSceneBatch carries them, SceneLoader(jitter=) draws them.
 
+Colour, tone and noise jitter is a second pass over the cut bytes: an int32 [N][16] photo table, one row per window - a 3 x 3
+colour matrix and offsets, a tone value, a noise amplitude and seed, all Q16 - (host_photometric is the definition,
+rua_window_photometric, csrc/photo.hip, its kernel).  photo_rows() makes rows from brightness, contrast, saturation, hue, tone and
+noise sigma, SceneBatch.with_photo() carries them, PhotoJitter draws them and SceneLoader(photo=) hands them out.
+
 Whole-scene evaluation goes the other way: predict_table() covers a scene with windows (the last one flush with the border) and
 gives every scene pixel to exactly one of them, an int32 [N][4] ownership table of (r0, r1, c0, c1) rectangles in window
 coordinates next to the window rows; rua_scene_stitch writes the arg-max of each owned pixel's class probabilities into a uint8
@@ -310,6 +315,138 @@ def affine_rows(rows4: np.ndarray, patch, rotate_deg=0.0, zoom=1.0, shift_q16=(0
     if (np.abs(out) > 2 ** 31 - 1).any():
         raise ValueError("affine_rows: a row leaves the int32 range")
     return out.astype(np.int32)
+
+
+# ---- photometric jitter: a colour matrix, a tone curve and hashed noise on the staged uint8 windows -------------------------------
+PHOTO_MAX_M, PHOTO_MAX_B, PHOTO_MAX_T, PHOTO_MAX_A = 1 << 20, 1 << 29, Q16, Q16
+SIGMA_Z = float(np.sqrt((256.0 ** 2 - 1.0) / 3.0))            # of z, the sum of four independent uniform bytes minus 510
+_PHOTO_LIKE = (0, -1, -1, -1, 0, -1, -1, -1, 0, 9, 9, 9)       # a scalar row: the word each of words 0..11 must equal; -1: zero
+
+
+def check_photo_table(table16, channels: int) -> np.ndarray:
+    """The photo table as a contiguous int32 [N][16] array (word 14, the seed, is taken mod 2^32); ValueError, in
+    rua_window_photometric's own words, for the first violation."""
+    t = np.asarray(table16)
+    if t.ndim != 2 or t.shape[1] != 16 or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError(f"a photo table is an integer [N][16] array of (M[3][3], b[3], tone, noise, seed, 0) rows, got {t.dtype} {t.shape}")
+    fn = "rua_window_photometric"
+    if t.shape[0] < 1:
+        raise ValueError(f"{fn}: N {t.shape[0]} (>= 1)")
+    if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or not 1 <= channels <= MAX_CHANNELS:
+        raise ValueError(f"{fn}: Cin {channels} outside 1..16")
+    t64 = t.astype(np.int64)
+    t64[:, 14] = ((t64[:, 14] + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)
+    bad = (np.abs(t64[:, :9]) > PHOTO_MAX_M).any(1) | (np.abs(t64[:, 9:12]) > PHOTO_MAX_B).any(1) | (np.abs(t64[:, 12]) > PHOTO_MAX_T)
+    bad |= (t64[:, 13] < 0) | (t64[:, 13] > PHOTO_MAX_A) | (t64[:, 15] != 0)
+    if channels != 3:
+        like = np.where(np.array(_PHOTO_LIKE)[None, :] < 0, 0, t64[:, [max(q, 0) for q in _PHOTO_LIKE]])
+        bad |= (t64[:, :12] != like).any(1)
+    if bad.any():
+        k = int(np.argmax(bad))
+        r = [int(v) for v in t64[k]]
+        for q in range(9):
+            if abs(r[q]) > PHOTO_MAX_M:
+                raise ValueError(f"{fn}: row {k}: word {q}: matrix entry {r[q]} outside -1048576..1048576 (16 in Q16)")
+        for q in range(9, 12):
+            if abs(r[q]) > PHOTO_MAX_B:
+                raise ValueError(f"{fn}: row {k}: word {q}: offset {r[q]} outside -536870912..536870912 (8192 levels in Q16)")
+        if abs(r[12]) > PHOTO_MAX_T:
+            raise ValueError(f"{fn}: row {k}: word 12: tone {r[12]} outside -65536..65536 (1 in Q16)")
+        if not 0 <= r[13] <= PHOTO_MAX_A:
+            raise ValueError(f"{fn}: row {k}: word 13: noise amplitude {r[13]} outside 0..65536")
+        if r[15] != 0:
+            raise ValueError(f"{fn}: row {k}: word 15: reserved, must be 0, got {r[15]}")
+        q = next(q for q in range(12) if r[q] != (0 if _PHOTO_LIKE[q] < 0 else r[_PHOTO_LIKE[q]]))
+        raise ValueError(f"{fn}: row {k}: word {q}: {r[q]}, but Cin {channels} != 3 takes scalar rows (off-diagonals 0, one gain, one offset)")
+    return np.ascontiguousarray(t64, dtype=np.int32)
+
+
+def host_photometric(img_u8: np.ndarray, table16) -> np.ndarray:
+    """The numpy definition of what rua_window_photometric writes (include/rua_hip.h spells the same arithmetic out), in int64:
+    uint8 [N][PH][PW][Cin] from uint8 [N][PH][PW][Cin] and an int32 [N][16] photo table - colour matrix and offsets, the tone curve,
+    then noise hashed from the row's seed and the byte's position inside its window."""
+    img = np.asarray(img_u8)
+    if img.dtype != np.uint8 or img.ndim != 4:
+        raise ValueError(f"windows are uint8 [N][PH][PW][Cin], got {img.dtype} {img.shape}")
+    N, PH, PW, Cin = img.shape
+    R = check_photo_table(table16, Cin).astype(np.int64)
+    if len(R) != N:
+        raise ValueError(f"{len(R)} photo rows for {N} windows")
+    row = lambda q: R[:, q][:, None, None, None]
+    p = img.astype(np.int64)
+    if Cin == 3:
+        u = np.einsum("ncd,nijd->nijc", R[:, :9].reshape(N, 3, 3), p) + R[:, 9:12][:, None, None, :]
+    else:
+        u = row(0) * p + row(9)
+    u = np.clip((u + 32768) >> 16, 0, 255)
+    v = np.clip(u + ((row(12) * u * (255 - u) + (1 << 23)) >> 24), 0, 255)
+    idx = np.arange(PH * PW * Cin, dtype=np.uint32).reshape(1, PH, PW, Cin)
+    x = R[:, 14].astype(np.uint32)[:, None, None, None] + (idx + np.uint32(1)) * np.uint32(0x9E3779B9)      # uint32 arrays wrap
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x7FEB352D)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x846CA68B)
+    x ^= x >> np.uint32(16)
+    x = x.astype(np.int64)
+    z = (x & 255) + ((x >> 8) & 255) + ((x >> 16) & 255) + (x >> 24) - 510
+    return np.clip(v + ((row(13) * z + 32768) >> 16), 0, 255).astype(np.uint8)       # A == 0 adds (32768 >> 16) = 0
+
+
+def photo_rows(n: int, brightness=0.0, contrast=1.0, saturation=1.0, hue_deg=0.0, tone=0.0, noise_sigma=0.0, seeds=0) -> np.ndarray:
+    """int32 [n][16] photo rows; every argument a scalar or a length-n array.  In float64 M = contrast * Sat(saturation) * Hue(hue_deg)
+    with Sat(s) = s I + (1 - s) 1 w^T, w = (0.299, 0.587, 0.114), and Hue the rotation by hue_deg about the grey axis (1, 1, 1) / sqrt 3
+    - both fix the grey axis, so grey stays grey; b = brightness * 255 + (1 - contrast) * 127.5 on every channel (contrast turns about
+    mid-grey), t = tone, A = noise_sigma / SIGMA_Z (noise_sigma in levels); each times 65536 and rounded with np.rint.  The defaults
+    give the identity row exactly.  ValueError (check_photo_table's) for a row beyond the kernel's limits."""
+    n = int(n)
+    per = lambda v: np.broadcast_to(np.asarray(v, np.float64), (n,))
+    br, co, sa, th, to, sg = per(brightness), per(contrast), per(saturation), np.deg2rad(per(hue_deg)), per(tone), per(noise_sigma)
+    I, w = np.eye(3), np.array([0.299, 0.587, 0.114])
+    sat = sa[:, None, None] * I + (1.0 - sa)[:, None, None] * np.broadcast_to(w, (3, 3))
+    K = np.array([[0.0, -1.0, 1.0], [1.0, 0.0, -1.0], [-1.0, 1.0, 0.0]]) / np.sqrt(3.0)          # the cross product with the grey axis
+    hue = np.cos(th)[:, None, None] * I + (1.0 - np.cos(th))[:, None, None] * np.full((3, 3), 1.0 / 3.0) + np.sin(th)[:, None, None] * K
+    out = np.zeros((n, 16), np.int64)
+    out[:, :9] = np.rint(Q16 * (co[:, None, None] * (sat @ hue))).reshape(n, 9)
+    out[:, 9:12] = np.rint(Q16 * (br * 255.0 + (1.0 - co) * 127.5))[:, None]
+    out[:, 12] = np.rint(Q16 * to)
+    out[:, 13] = np.rint(Q16 * sg / SIGMA_Z)
+    out[:, 14] = np.broadcast_to(np.asarray(seeds, np.int64), (n,))
+    return check_photo_table(out, 3)
+
+
+class PhotoJitter:
+    """The random part of SceneLoader's photometric augmentation: brightness uniform in [-brightness, brightness] (of full scale),
+    contrast and saturation log-uniform in their (lo, hi), the hue angle uniform in [-hue_deg, hue_deg], the tone uniform in
+    [-tone, tone], the noise sigma (in levels) uniform in its (lo, hi), one noise seed per window."""
+
+    def __init__(self, brightness: float = 0.1, contrast: Tuple[float, float] = (0.8, 1.25), saturation: Tuple[float, float] = (0.8, 1.25),
+                 hue_deg: float = 8.0, tone: float = 0.4, noise_sigma: Tuple[float, float] = (0.0, 3.0)):
+        for name, (lo, hi) in (("contrast", contrast), ("saturation", saturation)):
+            if not 0 < float(lo) <= float(hi):
+                raise ValueError(f"{name} range ({lo}, {hi}): 0 < lo <= hi")
+        if not 0 <= float(noise_sigma[0]) <= float(noise_sigma[1]):
+            raise ValueError(f"noise_sigma range ({noise_sigma[0]}, {noise_sigma[1]}): 0 <= lo <= hi")
+        if brightness < 0 or hue_deg < 0 or tone < 0:
+            raise ValueError(f"brightness {brightness}, hue_deg {hue_deg} and tone {tone} are magnitudes (>= 0)")
+        if tone > 1:
+            raise ValueError(f"tone {tone} above 1: the curve is monotone only up to 1")
+        self.brightness, self.hue_deg, self.tone = float(brightness), float(hue_deg), float(tone)
+        self.contrast, self.saturation = (float(contrast[0]), float(contrast[1])), (float(saturation[0]), float(saturation[1]))
+        self.noise_sigma = (float(noise_sigma[0]), float(noise_sigma[1]))
+
+    def draw(self, rng: np.random.Generator, n: int, channels: int = 3) -> np.ndarray:
+        """The int32 [n][16] photo table of n windows: brightness, contrast, saturation, hue, tone, sigma and seeds - drawn in this
+        order from rng, whatever `channels` is.  channels != 3: saturation and hue stay out of the rows, which are scalar then."""
+        log_uniform = lambda r: np.exp(rng.uniform(np.log(r[0]), np.log(r[1]), n))
+        br = rng.uniform(-self.brightness, self.brightness, n)
+        co, sa = log_uniform(self.contrast), log_uniform(self.saturation)
+        hue = rng.uniform(-self.hue_deg, self.hue_deg, n)
+        tone = rng.uniform(-self.tone, self.tone, n)
+        sigma = rng.uniform(self.noise_sigma[0], self.noise_sigma[1], n)
+        seeds = rng.integers(0, 1 << 31, n, dtype=np.int64)
+        if channels != 3:
+            sa, hue = 1.0, 0.0
+        return check_photo_table(photo_rows(n, br, co, sa, hue, tone, sigma, seeds), channels)
 
 
 # ---- whole-scene prediction: windows that cover a scene, every pixel owned by one of them -----------------------------------------
@@ -825,10 +962,11 @@ def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.
 
 class SceneBatch:
     """A batch named by index: a pool, int32 [B][4] table rows and the patch size.  Takes the place of x in Engine.train_step /
-    test_step / predict and Model.train_on_batch / test_on_batch / predict (y is None: the class maps are the pool's)."""
+    test_step / predict and Model.train_on_batch / test_on_batch / predict (y is None: the class maps are the pool's).
+    photo: None, or the checked int32 [B][16] photo table (check_photo_table) whose row k jitters window k after it is cut."""
 
-    def __init__(self, pool: "ScenePool", rows: np.ndarray, patch: Tuple[int, int]):
-        self.pool, self.rows, self.patch = pool, rows, patch
+    def __init__(self, pool: "ScenePool", rows: np.ndarray, patch: Tuple[int, int], photo: Optional[np.ndarray] = None):
+        self.pool, self.rows, self.patch, self.photo = pool, rows, patch, photo
 
     @property
     def shape(self):
@@ -840,7 +978,17 @@ class SceneBatch:
     def __getitem__(self, sl):
         if not isinstance(sl, slice):
             raise TypeError("a SceneBatch is sliced, not indexed")
-        return SceneBatch(self.pool, np.ascontiguousarray(self.rows[sl]), self.patch)
+        return type(self)(self.pool, np.ascontiguousarray(self.rows[sl]), self.patch,
+                          None if self.photo is None else np.ascontiguousarray(self.photo[sl]))
+
+    def with_photo(self, table16) -> "SceneBatch":
+        """A batch of the same class and rows that carries this photo table, one row per window (None: none)."""
+        if table16 is None:
+            return type(self)(self.pool, self.rows, self.patch, None)
+        t = check_photo_table(table16, self.pool.channels)
+        if len(t) != len(self):
+            raise ValueError(f"{len(t)} photo rows for a batch of {len(self)} windows")
+        return type(self)(self.pool, self.rows, self.patch, t)
 
     def shard(self, rank: int, world: int) -> "SceneBatch":
         """This rank's contiguous share of a global batch (the split Model._local_batch makes)."""
@@ -849,21 +997,20 @@ class SceneBatch:
             raise ValueError(f"global batch {B} not divisible by {world} replicas")
         return self[rank * (B // world):(rank + 1) * (B // world)]
 
-    def host(self):
-        """host_windows of this batch."""
+    def _cut(self):
         return host_windows(self.pool.images, self.pool.class_maps, self.rows, self.patch)
+
+    def host(self):
+        """host_windows of this batch; with a photo table, host_photometric of its image (the class map is untouched)."""
+        img, cls = self._cut()
+        return (img if self.photo is None else host_photometric(img, self.photo)), cls
 
 
 class AffineSceneBatch(SceneBatch):
-    """A SceneBatch whose rows are the int32 [B][7] affine table (check_affine_table): rua_scene_windows_affine cuts it."""
+    """A SceneBatch whose rows are the int32 [B][7] affine table (check_affine_table): rua_scene_windows_affine cuts it;
+    host() is host_windows_affine of it (and host_photometric of that, with a photo table)."""
 
-    def __getitem__(self, sl):
-        if not isinstance(sl, slice):
-            raise TypeError("a SceneBatch is sliced, not indexed")
-        return AffineSceneBatch(self.pool, np.ascontiguousarray(self.rows[sl]), self.patch)
-
-    def host(self):
-        """host_windows_affine of this batch."""
+    def _cut(self):
         return host_windows_affine(self.pool.images, self.pool.class_maps, self.rows, self.patch)
 
 
@@ -1063,10 +1210,13 @@ class SceneLoader:
     Yields (SceneBatch, None); order: indices into `table` (default: all of it, in order).
     jitter (a Jitter): batch k of pass e (e counts __iter__ calls from 0) draws one rotation, zoom and shift per row of the GLOBAL
     batch from np.random.default_rng([seed, e, k]), turns its rows into affine rows (affine_rows) and every rank takes its own:
-    a world of 2 sees exactly the windows a world of 1 sees.  Yields (AffineSceneBatch, None) then."""
+    a world of 2 sees exactly the windows a world of 1 sees.  Yields (AffineSceneBatch, None) then.
+    photo (a PhotoJitter): batch k of pass e draws the GLOBAL batch's photo table from np.random.default_rng([seed, e, k, 1]) - a
+    stream of its own: the draws of jitter= are what they are without it -, every rank takes its own rows, and the batches carry
+    them (SceneBatch.photo).  Passes are counted with photo alone as with jitter."""
 
     def __init__(self, pool: ScenePool, table: np.ndarray, batch_size: int, patch=None, order: Optional[Sequence[int]] = None,
-                 rank: int = 0, world: int = 1, jitter: Optional[Jitter] = None, seed: int = 0):
+                 rank: int = 0, world: int = 1, jitter: Optional[Jitter] = None, seed: int = 0, photo: Optional[PhotoJitter] = None):
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")
         if world < 1 or not (0 <= rank < world):
@@ -1076,7 +1226,7 @@ class SceneLoader:
         self.pool, self.table, self.patch = pool, np.asarray(table), patch
         self.B, self.rank, self.local_B = int(batch_size), int(rank), int(batch_size) // int(world)
         self.order = np.arange(len(self.table)) if order is None else np.asarray(order, dtype=np.int64)
-        self.jitter, self.seed, self.passes = jitter, int(seed), 0
+        self.jitter, self.photo, self.seed, self.passes = jitter, photo, int(seed), 0
 
     def __len__(self) -> int:
         return len(self.order) // self.B
@@ -1085,15 +1235,21 @@ class SceneLoader:
         self.order = np.asarray(order, dtype=np.int64)
 
     def __iter__(self):
-        if self.jitter is not None:
-            e, self.passes = self.passes, self.passes + 1
-            return self._jittered(e)
-        return self._plain()
+        if self.jitter is None and self.photo is None:
+            return self._plain(None)
+        e, self.passes = self.passes, self.passes + 1
+        return self._jittered(e) if self.jitter is not None else self._plain(e)
 
-    def _plain(self):
+    def _with_photo(self, batch: SceneBatch, e: Optional[int], k: int) -> SceneBatch:
+        if self.photo is None:
+            return batch
+        table = self.photo.draw(np.random.default_rng([self.seed, e, k, 1]), self.B, self.pool.channels)
+        return batch.with_photo(table[self.rank * self.local_B:(self.rank + 1) * self.local_B])
+
+    def _plain(self, e: Optional[int]):
         for k in range(len(self)):
             first = k * self.B + self.rank * self.local_B
-            yield self.pool.batch(self.table[self.order[first:first + self.local_B]], self.patch), None
+            yield self._with_photo(self.pool.batch(self.table[self.order[first:first + self.local_B]], self.patch), e, k), None
 
     def _jittered(self, e: int):
         patch = self.pool.patch if self.patch is None else _patch2(self.patch)
@@ -1102,7 +1258,7 @@ class SceneLoader:
         for k in range(len(self)):
             angle, zoom, shift = self.jitter.draw(np.random.default_rng([self.seed, e, k]), self.B)
             rows = affine_rows(self.table[self.order[k * self.B:(k + 1) * self.B]], patch, angle, zoom, shift)
-            yield self.pool.affine_batch(rows[self.rank * self.local_B:(self.rank + 1) * self.local_B], patch), None
+            yield self._with_photo(self.pool.affine_batch(rows[self.rank * self.local_B:(self.rank + 1) * self.local_B], patch), e, k), None
 
 
 # ---- scene directories ------------------------------------------------------------------------------------------------------

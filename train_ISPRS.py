@@ -22,6 +22,13 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
     rotated by a random angle in [-DEG, DEG], zoomed by a log-uniform factor in [LO, HI] and shifted by up to PX pixels (default
     `--stride` / 2), with reflect padding at the scene border, drawn afresh every epoch from `--seed` (scenes.SceneLoader(jitter=)).
     The validation windows and the split are untouched, so validation numbers compare between runs with and without the flag.
+  * `--photo_aug yes --photo_brightness V --photo_contrast LO HI --photo_saturation LO HI --photo_hue DEG --photo_tone V
+    --photo_noise LO HI` (with `--scene_dataset yes`): every training window gets a random brightness offset in [-V, V] of full
+    scale, a log-uniform contrast and saturation, a hue rotation in [-DEG, DEG], a tone-curve strength in [-V, V] and hashed noise
+    of a sigma in [LO, HI] levels, applied to the cut uint8 window on the GPU (rua_window_photometric) before the input and the
+    targets are built from it - the colour head's HSV target follows the jittered image.  Drawn afresh every epoch from `--seed`
+    (scenes.SceneLoader(photo=)), in a random stream of its own: `--random_aug` draws what it draws without it.  The validation
+    windows and the split are untouched.  The option is not stored in a checkpoint.
   * `--class_weights auto` (with `--scene_dataset yes --loss weighted_cross_entropy`): the weighted-CE class weights are total /
     pixels of the class over the training windows (scenes.class_weights; the reference's five numbers are that rule on its own
     patch set), counted on the GPU from the resident class maps (ScenePool.class_counts).  `--class_weights w0 ... wC-1` gives
@@ -95,6 +102,14 @@ def build_parser():
     p.add_argument("--aug_rotate", type=float, default=180.0, metavar="DEG", help="random_aug: the angle is uniform in [-DEG, DEG]")
     p.add_argument("--aug_zoom", type=float, nargs=2, default=[0.75, 1.33], metavar=("LO", "HI"), help="random_aug: the zoom is log-uniform in [LO, HI]")
     p.add_argument("--aug_shift", type=float, default=None, metavar="PX", help="random_aug: shift of up to PX pixels per axis (default: stride / 2)")
+    p.add_argument("--photo_aug", type=str2bool, default=False,
+                   help="scene directory: random brightness, contrast, saturation, hue, tone and noise of every training window, applied on the GPU")
+    p.add_argument("--photo_brightness", type=float, default=0.1, metavar="V", help="photo_aug: the offset is uniform in [-V, V] of full scale")
+    p.add_argument("--photo_contrast", type=float, nargs=2, default=[0.8, 1.25], metavar=("LO", "HI"), help="photo_aug: the contrast is log-uniform in [LO, HI]")
+    p.add_argument("--photo_saturation", type=float, nargs=2, default=[0.8, 1.25], metavar=("LO", "HI"), help="photo_aug: the saturation is log-uniform in [LO, HI] (3 channels)")
+    p.add_argument("--photo_hue", type=float, default=8.0, metavar="DEG", help="photo_aug: the hue turns by an angle uniform in [-DEG, DEG] (3 channels)")
+    p.add_argument("--photo_tone", type=float, default=0.4, metavar="V", help="photo_aug: the tone-curve strength is uniform in [-V, V], V <= 1")
+    p.add_argument("--photo_noise", type=float, nargs=2, default=[0.0, 3.0], metavar=("LO", "HI"), help="photo_aug: the noise sigma, in levels, is uniform in [LO, HI]")
     p.add_argument("--class_weights", type=str, nargs="+", default=None, metavar="W",
                    help="weighted_cross_entropy: `auto` (scene directory: total / pixels of the class over the training windows) or one weight per class")
     p.add_argument("--balance_class", type=int, default=None, metavar="K",
@@ -118,6 +133,36 @@ def check_void_flags(args):
     if not 0 <= args.void_margin <= 16:
         sys.exit(f"--void_margin {args.void_margin} outside 0..16")
     return args.void_margin
+
+
+def check_photo_flags(args):
+    """--photo_aug and its ranges checked against the rest of the command line, before anything is loaded: returns the PhotoJitter, or
+    None (off); SystemExit with a message otherwise."""
+    if not args.photo_aug:
+        return None
+    if not args.scene_dataset:
+        sys.exit("--photo_aug yes jitters windows of resident scenes: it needs --scene_dataset yes")
+    from resunet_a_mltsk_keras_amd.scenes import PhotoJitter
+    try:
+        return PhotoJitter(args.photo_brightness, tuple(args.photo_contrast), tuple(args.photo_saturation), args.photo_hue, args.photo_tone,
+                           tuple(args.photo_noise))
+    except ValueError as exc:
+        sys.exit(f"--photo_aug: {exc}")
+
+
+def scene_loaders(args, pool, table, x_tr, x_va, batch_size, rank=0, world=1):
+    """(training SceneLoader, validation SceneLoader) of a scene run: x_tr / x_va are patch_{k}.npy names of table rows k.
+    --random_aug and --photo_aug reach the training loader alone: it draws a rotation, zoom and shift and a photo row per window and
+    pass (the same on every rank); the validation loader is the same with and without them."""
+    from resunet_a_mltsk_keras_amd.scenes import Jitter, SceneLoader, patch_index
+    jitter = None
+    if getattr(args, "random_aug", False):
+        jitter = Jitter(args.aug_rotate, tuple(args.aug_zoom), args.stride / 2 if args.aug_shift is None else args.aug_shift)
+    photo = check_photo_flags(args) if getattr(args, "photo_aug", False) else None
+    ld_tr = SceneLoader(pool, table[[patch_index(n) for n in x_tr]], batch_size, args.patch_size, rank=rank, world=world,
+                        jitter=jitter, seed=args.seed, photo=photo)
+    ld_va = SceneLoader(pool, table[[patch_index(n) for n in x_va]], batch_size, args.patch_size, rank=rank, world=world)
+    return ld_tr, ld_va
 
 
 def check_class_flags(args):
@@ -259,16 +304,8 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
     else:
         # scenes = (ScenePool, window table): x_tr / x_va are patch_{k}.npy names of table rows k; no files, no loader threads - a
         # batch is its rows of the table, and every rank holds the pool and takes its own rows
-        from resunet_a_mltsk_keras_amd.scenes import SceneLoader, patch_index
         pool, table = scenes
-        # --random_aug: the training loader alone draws a rotation, zoom and shift per window and pass (the same on every rank)
-        jitter = None
-        if getattr(args, "random_aug", False):
-            from resunet_a_mltsk_keras_amd.scenes import Jitter
-            jitter = Jitter(args.aug_rotate, tuple(args.aug_zoom), args.stride / 2 if args.aug_shift is None else args.aug_shift)
-        ld_tr = SceneLoader(pool, table[[patch_index(n) for n in x_tr]], batch_size, args.patch_size, rank=rank, world=world,
-                            jitter=jitter, seed=args.seed)
-        ld_va = SceneLoader(pool, table[[patch_index(n) for n in x_va]], batch_size, args.patch_size, rank=rank, world=world)
+        ld_tr, ld_va = scene_loaders(args, pool, table, x_tr, x_va, batch_size, rank, world)
     shard = dict(local_shard=True) if world > 1 else {}
     if compact or scenes is not None:
         shard["norm_type"] = args.norm_type
@@ -324,6 +361,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.random_aug and not args.scene_dataset:
         sys.exit("--random_aug yes resamples windows of resident scenes: it needs --scene_dataset yes")
+    check_photo_flags(args)
     class_weights = check_class_flags(args)
     void_margin = check_void_flags(args)
     import torch
