@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .wgrad_queue import WgradQueue, WSpec
 from .scenes import MAP_HEADS, AffineSceneBatch, SceneBatch, check_photo_table, check_radius, check_tolerance, check_views, view_rows
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
@@ -322,11 +323,8 @@ class Graph:
         self.back_steps: List = _BackSteps(self)
         self.cur_tag: Optional[str] = None      # composite being recorded (stem, down, PSP, combine, heads): per-composite timing in bench.py
         self.block_tag = ""
-        self.pending: List[tuple] = []          # deferred weight-gradient reductions (record, dW offset)
-        self.pending_bytes = 0                  # ... and the bytes of partials they will read (Engine.flush_bytes)
-        self.pending_bucket = 0
-        self.later: List[tuple] = []            # generic-tile weight gradients held back for ONE batched launch in front of the next flush (descriptor, dW offset)
         self.allocs: List[torch.Tensor] = []
+        self.wq = WgradQueue(eng, self.bwd, self.dt, dry, self.alloc, self.allocs.append, self.G, self.issue)     # every weight gradient of the backward goes through it
         self.stats_used = 16                 # the first 16 doubles of the arena are the loss / metric scalars
         self.act_bytes = 0
         self.img_u8 = self.cls_u8 = self.tgt_scratch = None     # compact batches (Engine._upload_compact): allocated on first use
@@ -461,7 +459,7 @@ class Graph:
 
     def issue(self, plan: Plan, descs: List, one: str, group: Optional[str] = None):
         """Descriptors of one type as ONE launch: `one` on the descriptor itself, or `group` over a packed copy of them all.  The launch
-        names the gradients its descriptors write (the `grads` that wgrad_desc / bn_bwd give them)."""
+        names the gradients its descriptors write (the `grads` that WgradQueue.desc / bn_bwd give them)."""
         grads = [o for d in descs for o in getattr(d, "grads", ())]
         if len(descs) == 1:
             plan.keep.append(descs[0])
@@ -616,13 +614,20 @@ class Graph:
         sg.x, sg.w, sg.C, sg.Hs, sg.Ws, sg.up_shift, sg.dil, sg.taps = x.ptr, x.ptr, x.C, x.H, x.W, 0, dil, 9
         d.N, d.H, d.W, d.Cout, d.stride, d.dtype = x.N, x.H, x.W, nf, 1, self.dt
         d.y, d.out_stride, d.OH, d.OW = x.ptr, 1, x.H, x.W
+        return L.lib().raw("rua_conv_fused_input_ok")(C.byref(d)) == 1 and self.wgrad_all_taps(x, nf, [dil])
+
+    def wgrad_all_taps(self, x: Ten, nf: int, dils: List[int]) -> bool:
+        """Do the weight gradients of the 3x3 convs x -> nf channels at these dilations run on the all-taps kernel (rua_wgrad_kind 1)?  A throw-away
+        descriptor: only its geometry is read."""
         w = L.WgradDesc()
         w.a, w.C, w.Hs, w.Ws, w.dy, w.Cout, w.H, w.W = x.ptr, x.C, x.H, x.W, x.ptr, nf, x.H, x.W
-        w.N, w.stride, w.dil, w.taps, w.dtype = x.N, 1, dil, 9, self.dt
-        sc = self.e.scratch
-        w.workspace, w.workspace_bytes = sc.data_ptr(), sc.numel() * 4
-        lib = L.lib()
-        return lib.raw("rua_conv_fused_input_ok")(C.byref(d)) == 1 and lib.raw("rua_wgrad_kind")(C.byref(w)) == 1
+        w.N, w.stride, w.taps, w.dtype = x.N, 1, 9, self.dt
+        w.workspace, w.workspace_bytes = self.e.scratch.data_ptr(), self.e.scratch.numel() * 4
+        for dil in dils:
+            w.dil = dil
+            if L.lib().raw("rua_wgrad_kind")(C.byref(w)) != 1:
+                return False
+        return True
 
     def _ws(self, d):
         """Shared split-K scratch (launches are serialised on one stream, so one buffer serves every conv)."""
@@ -667,192 +672,18 @@ class Graph:
         self._ws(d)
         return d
 
-    def wgrad_desc(self, plan: Plan, a: Ten, dy: Ten, dw_off: int, stride: int, dil: int, taps: int, in_bn: Optional["Coef"] = None,
-                   may_flush: bool = True, group: int = 0, defer_ok: bool = True):
-        d = L.WgradDesc()
-        d.group_members = group                            # members of the rua_conv_wgrad_group call this descriptor belongs to
-        d.a, d.C, d.Hs, d.Ws = a.ptr, a.C, a.H, a.W
-        if in_bn is not None:                               # a is read as relu(scale * a + shift) (normalise on load)
-            d.in_scale, d.in_shift, d.in_relu = in_bn.scale, in_bn.shift, 1
-        d.dy, d.Cout, d.H, d.W = dy.ptr, dy.C, dy.H, dy.W
-        d.N, d.stride, d.dil, d.taps, d.dtype = dy.N, stride, dil, taps, self.dt
-        if not self.dry and self.e.wgrad_overwrite:
-            d.overwrite_dev = self.e.ow_flag.data_ptr()    # whole steps store dW instead of adding to the zeroed arena (Engine._set_overwrite)
-        defer = (not self.dry) and self.e.defer_reduce and plan is self.bwd and defer_ok
-        if defer and may_flush:
-            bucket = self.e.dist.bucket_of(dw_off) if self.e.dist is not None else 0
-            if (self.pending or self.later) and (bucket != self.pending_bucket or self.pending_bytes > self.e.flush_bytes):
-                self.flush_wgrad(plan)
-            self.pending_bucket = bucket
-        d.dw, d.grads = self.G(dw_off), (dw_off,)
-        if not self.dry:
-            d.workspace, d.workspace_bytes = self.e.scratch.data_ptr(), self.e.scratch.numel() * 4
-            if defer:
-                self._defer_wgrad(plan, d, dw_off)
-        return d
-
-    def wgrad(self, plan: Plan, a: Ten, dy: Ten, dw_off: int, stride: int, dil: int, taps: int, in_bn: Optional["Coef"] = None):
-        if not self.wgrad_later(plan, a, dy, dw_off, stride, dil, taps, in_bn):
-            self.issue(plan, [self.wgrad_desc(plan, a, dy, dw_off, stride, dil, taps, in_bn)], "rua_conv_wgrad")
-
-    # -- batched weight gradients: the generic-tile weight gradients of a step (the wide 1x1 convolutions on small maps: 2 - 13 us apiece, each a launch that
-    #    splits its K range to fill the chip alone) are not launched where they are recorded.  They wait in `later` and go out as ONE rua_conv_wgrad_group call
-    #    (its batched form: one compact grid, one block budget) IMMEDIATELY IN FRONT OF every flush_wgrad - a bucket change, Engine.flush_bytes, the end of
-    #    backward.  The flush invariant: the pending records of a held-back member are created by that call's recording (_issue_later), so they can never be
-    #    reduced before their slabs are written, and under data parallel a bucket's gradients are final at the same flush as with one launch each.
-    def wgrad_later(self, plan: Plan, a: Ten, dy: Ten, dw_off: int, stride: int, dil: int, taps: int, in_bn: Optional["Coef"] = None) -> bool:
-        """Hold this weight gradient back for the batched launch in front of the next flush; False: the caller launches it here.  Candidates: bf16 backward
-        plans with deferred reductions, rua_wgrad_kind() == 0 and no whole-image kernel.  Holding a launch back is sound only while nothing writes its operands
-        between the recorded position and the flush: `a` is a forward activation (or its pooled / normalised copy) and `dy` the finished gradient of the
-        convolution's output; the graph owns every buffer for its lifetime (alloc) and the backward rewrites neither.  The one explicit storage reuse of the
-        backward, the ResBlocks' g1s = g2s, holds gradients of 3x3 branch convolutions: all-taps / wgrad_dmap / whole-image launches, never candidates here."""
-        if self.dry or plan is not self.bwd or in_bn is not None or self.dt != L.RUA_BF16 or not (self.e.batch_wgrad and self.e.defer_reduce):
-            return False
-        d = self.wgrad_desc(plan, a, dy, dw_off, stride, dil, taps, defer_ok=False)          # (no side effects: neither a flush nor a workspace)
-        lib = L.lib()
-        if lib.raw("rua_wgrad_kind")(C.byref(d)) != 0 or lib.raw("rua_wgrad_img_kind")(C.byref(d)) != 0:
-            return False
-        bucket = self.e.dist.bucket_of(dw_off) if self.e.dist is not None else 0
-        if (self.pending or self.later) and (bucket != self.pending_bucket or self.pending_bytes > self.e.flush_bytes):
-            self.flush_wgrad(plan)
-        self.pending_bucket = bucket
-        d.batch, d.defer = 1, 1
-        self.later.append((d, dw_off))
-        return True
-
-    def _issue_later(self, plan: Plan):
-        """The held-back weight gradients as one rua_conv_wgrad_group call, and the pending records of the slabs it leaves."""
-        if not self.later:
-            return
-        lib = L.lib()
-        n = len(self.later)
-        arr = (L.WgradDesc * n)(*[d for d, _ in self.later])
-        recs = (L.WgradPending * n)()
-        lib.call("rua_wgrad_group_plan", arr, n, recs)                   # with the shared scratch: which members leave slabs, and how many
-        for i in range(n):
-            if recs[i].kind != 0:
-                nbytes = recs[i].parts * recs[i].n * 4 + (264 << 10)
-                ws = self.alloc(((nbytes + 3) // 4,), torch.float32, zero=True)   # private until the flush, as in _defer_wgrad
-                arr[i].workspace, arr[i].workspace_bytes = ws.data_ptr(), ws.numel() * 4
-                self.pending_bytes += nbytes
-        first = [(recs[i].kind, recs[i].parts) for i in range(n)]
-        lib.call("rua_wgrad_group_plan", arr, n, recs)                   # the records for the private workspaces
-        assert first == [(recs[i].kind, recs[i].parts) for i in range(n)]
-        for i, (_, off) in enumerate(self.later):
-            if recs[i].kind != 0:
-                self.pending.append((L.WgradPending.from_buffer_copy(recs[i]), off))
-        plan.keep.append(arr)
-        prev, plan.scope = plan.scope, "wgrad_batch"
-        plan.add("rua_conv_wgrad_group", arr, n, grads=[off for _, off in self.later])
-        plan.scope = prev
-        self.later = []
-
-    def wgrad_group(self, plan: Plan, specs: List[tuple]):
-        """Independent weight gradients (the dilation branches of a ResBlock) in one call: members on the same kernel share ONE
-        grid.  specs: (a, dy, dw_off, stride, dil, taps, in_bn).  Under data parallel the group counts as one launch of the
-        bucket of its first member (a pending-reduction flush can only come in front of the whole group)."""
-        if len(specs) == 1 or self.dry:
-            for sp in specs:
-                self.wgrad(plan, *sp)
-            return
-        if len(specs) > L.RUA_MAX_WGRAD_GROUP:
-            self.wgrad_group(plan, specs[:L.RUA_MAX_WGRAD_GROUP])
-            self.wgrad_group(plan, specs[L.RUA_MAX_WGRAD_GROUP:])
-            return
-        descs = [self.wgrad_desc(plan, *sp, may_flush=(i == 0), group=len(specs)) for i, sp in enumerate(specs)]
-        self.issue(plan, descs, "rua_conv_wgrad", "rua_conv_wgrad_group")
-
-    def wgrad_now_or_later(self, plan: Plan, specs: List[tuple]) -> List[tuple]:
-        """The weight gradients of a ResBlock's SECOND convolutions: issued here - or returned, to ride in ONE group with the first convolutions' (whose
-        dy exists three launches later).  Twice the members per grid = half the blocks per member: half the block partials to write and to reduce
-        (levels 3 - 4: 24 MB per member) and half the ring fills per row of work.  Engine.merge_wgrad holds the channel counts that do."""
-        if self.dry or len(specs) < 2 or 2 * len(specs) > L.RUA_MAX_WGRAD_GROUP or specs[0][0].C not in self.e.merge_wgrad:
-            self.wgrad_group(plan, specs)
-            return []
-        return specs
-
-    def wgrad_pw_group(self, plan: Plan, specs: List[tuple]):
-        """The narrow 1x1 weight gradients of one composite (the sources of a concatenating conv, the branch convs of a PSPPooling: independent, 2 - 15 us
-        apiece and mostly launch ramp + drain) as ONE rua_conv_wgrad_group call.  The library runs them as one grid when every member is a wgrad_pw launch with
-        replicas / tickets of its own - so each member gets a private (zeroed) workspace here; anything else falls back to one launch each, as before."""
-        lib = L.lib()
-        if self.dry or len(specs) < 2 or self.dt != L.RUA_BF16 or not self.e.group_wgrad_pw or len(specs) > L.RUA_MAX_BRANCH:
-            if len(specs) > L.RUA_MAX_BRANCH and not self.dry and self.dt == L.RUA_BF16 and self.e.group_wgrad_pw:
-                self.wgrad_pw_group(plan, specs[:L.RUA_MAX_BRANCH])
-                self.wgrad_pw_group(plan, specs[L.RUA_MAX_BRANCH:])
-                return
-            for sp in specs:
-                self.wgrad(plan, *sp)
-            return
-        if not all(lib.raw("rua_wgrad_kind")(C.byref(self.wgrad_desc(plan, *sp, defer_ok=False))) == 3 for sp in specs):
-            for sp in specs:                                   # one launch each - or, generic tiles, held back for the step's batched launch (wgrad_later)
-                self.wgrad(plan, *sp)
-            return
-        descs = [self.wgrad_desc(plan, *sp, may_flush=(i == 0)) for i, sp in enumerate(specs)]
-        for d in descs:
-            if d.defer:                                        # block partials, summed by the next rua_wgrad_reduce_batch: _defer_wgrad gave it a private workspace
-                continue
-            nbytes = int(lib.raw("rua_wgrad_workspace_bytes")(C.byref(d)))
-            ws = self.alloc(((nbytes + 3) // 4,), torch.float32, zero=True)
-            d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        self.issue(plan, descs, "rua_conv_wgrad", "rua_conv_wgrad_group")
-
-    # -- deferred weight-gradient reductions: the partial sums of many weight gradients (all-taps block partials, K-slice slabs)
-    #    are added into dW by ONE batched launch instead of one small launch each (80 of them per cfg3 step).  Under data
-    #    parallel the batch is flushed whenever the next weight gradient belongs to another all-reduce bucket, so a bucket's
-    #    gradients are final - and its all-reduce starts - as early as before.
-    def _defer_wgrad(self, plan: Plan, d, dw_off: int):
-        lib = L.lib()
-        rec = L.WgradPending()
-        d.defer = 1
-        lib.call("rua_wgrad_plan", C.byref(d), C.byref(rec))           # with the shared scratch: which kind of partials, if any
-        if rec.kind == 0:
-            d.defer = 0
-            return
-        # exactly the partials this call writes (all-taps: one per CU and output-channel half; slabs: one dW per K slice) + the tail
-        nbytes = (self.e.cu_count * 9 * 32 * rec.CC * 4 if rec.kind == 1 else rec.parts * rec.n * 4) + (264 << 10)
-        ws = self.alloc(((nbytes + 3) // 4,), torch.float32, zero=True)   # private until the flush (zeroed: the tail convention)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        lib.call("rua_wgrad_plan", C.byref(d), C.byref(rec))           # the record for the private workspace
-        assert rec.kind != 0
-        self.pending.append((rec, dw_off))
-        self.pending_bytes += nbytes
-
-    def flush_wgrad(self, plan: Plan):
-        self._issue_later(plan)
-        self.pending_bytes = 0
-        if not self.pending:
-            return
-        blocks = 0
-        for r, _ in self.pending:
-            r.block_begin = blocks
-            blocks += r.blocks
-        recs = (L.WgradPending * len(self.pending))(*[r for r, _ in self.pending])
-        table = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(self.dev)
-        self.allocs.append(table)
-        plan.add("rua_wgrad_reduce_batch", table.data_ptr(), len(self.pending), blocks, grads=[off for _, off in self.pending])
-        self.pending = []
-
     def bias_grad(self, plan: Plan, dy: Ten, bias_offs: List[int]):
         s = self.col_stats(plan, dy)
         self.stats_to_grads(plan, s, dy.C, bias_offs)
 
     def stats_to_grads(self, plan: Plan, s: Stat, Cc: int, offs: List[int]):
         """G[off .. off + C) += per-channel sums of `s` for every offset: its own small launch, or - deferred - records of the next
-        batched reduction launch (see _defer_wgrad)."""
-        if self.dry or not (self.e.defer_reduce and plan is self.bwd):
-            dst = L.ptr_array([self.G(o) for o in offs])
-            plan.keep.append(dst)
-            plan.add("rua_stats_to_f32", s.ptr, s.R, Cc, dst, len(offs), grads=offs)
-            return
-        for o in offs:
-            bucket = self.e.dist.bucket_of(o) if self.e.dist is not None else 0
-            if (self.pending or self.later) and bucket != self.pending_bucket:
-                self.flush_wgrad(plan)
-            self.pending_bucket = bucket
-            rec = L.WgradPending()
-            rec.kind, rec.parts, rec.n, rec.partials, rec.dw, rec.blocks = 3, s.R, Cc, s.ptr, self.G(o), (Cc + 255) // 256
-            self.pending.append((rec, o))
+        batched reduction launch (WgradQueue.stats_records)."""
+        if self.wq.defers(plan):
+            return self.wq.stats_records(s, Cc, offs)
+        dst = L.ptr_array([self.G(o) for o in offs])
+        plan.keep.append(dst)
+        plan.add("rua_stats_to_f32", s.ptr, s.R, Cc, dst, len(offs), grads=offs)
 
     def bn_bwd_finalize(self, plan: Plan, stats2, count, bn, coef: Coef):
         plan.add("rua_bn_bwd_finalize", stats2.ptr, stats2.R, float(count), self.P(bn["gamma"]), coef.mean, coef.rstd,
@@ -917,34 +748,8 @@ class Graph:
         if not tr:
             return out
 
-        def back():
-            Bp = self.bwd
-            Bp.scope = scope
-            dO = out.grad
-            if not v2:
-                self.bias_grad(Bp, dO, [l[3]["bias"] for l in lay])      # (model2: summed by the final bn_bwd, which reads dO as the skip gradient)
-            if sum2:                                           # y1_b normalised on load by the weight gradient too
-                w2 = [(y, dO, l[3]["segs"][0]["off"], 1, d, 9, c2) for d, l, y, c2 in zip(dils, lay, y1, coef2)]
-            else:
-                w2 = [(a_2, dO, l[3]["segs"][0]["off"], 1, d, 9, None) for d, l, a_2 in zip(dils, lay, a2)]
-            w2 = self.wgrad_now_or_later(Bp, w2)
-            g2s = [self.like(x) for _ in dils]
-            s2s = [self.stat(nf, (cnt + 127) // 128) for _ in dils]
-            self.conv_group(Bp, [self.dgrad_desc(dO, self.Wd(l[3]["segs"][0]["dst"]), nf, d, 9, g2, 0, mask=(y, c2.scale, c2.shift), stats2=s2)
-                                 for d, l, y, c2, g2, s2 in zip(dils, lay, y1, coef2, g2s, s2s)])
-            dy1s = [self.like(x) for _ in dils]
-            self.bn_bwd_group(Bp, [(g2, c2, l[2], s2, y, dy1, cnt) for l, y, c2, g2, s2, dy1 in zip(lay, y1, coef2, g2s, s2s, dy1s)])
-            # no bias gradient launch: the output of a BN backward sums to zero per channel, so d b1 == 0 exactly
-            self.wgrad_group(Bp, w2 + [(a_1, dy1, l[1]["segs"][0]["off"], 1, d, 9, None) for d, l, a_1, dy1 in zip(dils, lay, a1, dy1s)])
-            g1s = g2s                                          # g2 is dead after its bn_bwd: reuse the storage
-            s1s = [self.stat(nf, (cnt + 127) // 128) for _ in dils]
-            self.conv_group(Bp, [self.dgrad_desc(dy1, self.Wd(l[1]["segs"][0]["dst"]), nf, d, 9, g1, 0, mask=(x, c1.scale, c1.shift), stats2=s1)
-                                 for d, l, dy1, c1, g1, s1 in zip(dils, lay, dy1s, coef1, g1s, s1s)])
-            gx, acc = self.gacc(x)
-            self.bn_bwd(Bp, g1s, coef1, [l[0] for l in lay], s1s, x, gx, acc, cnt, dskip=dO if v2 else None,
-                        skip_bias=[l[3]["bias"] for l in lay] if v2 else None, dx_bias=True)
-            Bp.scope = None
-        self.back_steps.append(back)
+        in2 = list(zip(y1, coef2)) if sum2 else [(a, None) for a in a2]      # (sum2: y1_b normalised on load by the weight gradient too)
+        self.resblock_back(x, out, nf, dils, lay, scope, y1, coef1, coef2, in2, [(a, None) for a in a1])
         return out
 
     def group_fused_ok(self, x: Ten, nf: int, dils: List[int]) -> bool:
@@ -970,18 +775,7 @@ class Graph:
         for bi in range(len(dils)):                          # ... and the second convs as one summed launch
             arr[bi].y = outs[0]
             arr[bi].accumulate = 1 if bi > 0 else 0
-        if lib.raw("rua_conv_sum_kernel")(arr, len(dils)) == 0:
-            return False
-        w = L.WgradDesc()
-        w.a, w.C, w.Hs, w.Ws, w.dy, w.Cout, w.H, w.W = x.ptr, x.C, x.H, x.W, x.ptr, nf, x.H, x.W
-        w.N, w.stride, w.taps, w.dtype = x.N, 1, 9, self.dt
-        sc = self.e.scratch
-        w.workspace, w.workspace_bytes = sc.data_ptr(), sc.numel() * 4
-        for d in dils:
-            w.dil = d
-            if lib.raw("rua_wgrad_kind")(C.byref(w)) != 1:
-                return False
-        return True
+        return lib.raw("rua_conv_sum_kernel")(arr, len(dils)) != 0 and self.wgrad_all_taps(x, nf, dils)
 
     def second_stage_sum_ok(self, x: Ten, y1: List[Ten], nf: int, dils: List[int], lay, out: Ten) -> bool:
         """Does the library run `out = x + sum_b conv(relu(BN2_b(y1_b)))` as ONE launch with the BatchNorms applied on load
@@ -1001,18 +795,7 @@ class Graph:
             q.accumulate = 1 if bi > 0 else 0
             q.in_fold, q.in_relu = C.addressof(dummy), 1
         lib = L.lib()
-        if lib.raw("rua_conv_sum_kernel")(arr, len(dils)) == 0:
-            return False
-        w = L.WgradDesc()
-        w.a, w.C, w.Hs, w.Ws, w.dy, w.Cout, w.H, w.W = x.ptr, x.C, x.H, x.W, x.ptr, nf, x.H, x.W
-        w.N, w.stride, w.taps, w.dtype = x.N, 1, 9, self.dt
-        sc = self.e.scratch
-        w.workspace, w.workspace_bytes = sc.data_ptr(), sc.numel() * 4
-        for d in dils:
-            w.dil = d
-            if lib.raw("rua_wgrad_kind")(C.byref(w)) != 1:
-                return False
-        return True
+        return lib.raw("rua_conv_sum_kernel")(arr, len(dils)) != 0 and self.wgrad_all_taps(x, nf, dils)
 
     def resblock_fused(self, x: Ten, nf: int, dils: List[int], lay, scope: str) -> Ten:
         """The same ResBlock (model2.py:15-34) with every BatchNorm + ReLU applied ON LOAD by the consuming kernel: no
@@ -1049,21 +832,30 @@ class Graph:
         if not tr:
             return out
 
+        self.resblock_back(x, out, nf, dils, lay, scope, y1, coef1, coef2, list(zip(y1, coef2)), [(x, c1) for c1 in coef1])
+        return out
+
+    def resblock_back(self, x: Ten, out: Ten, nf: int, dils: List[int], lay, scope: str, y1: List[Ten], coef1, coef2, in2: List[tuple], in1: List[tuple]):
+        """The backward of both ResBlock forms.  in2 / in1: per branch, what its second / first convolution read - (tensor, the Coef it was normalised with
+        on load, or None for a materialised BatchNorm + ReLU output) - and so what their weight gradients read."""
+        v2, cnt = self.cfg.variant == "model2", x.M
+
         def back():
             Bp = self.bwd
             Bp.scope = scope
             dO = out.grad
             if not v2:
-                self.bias_grad(Bp, dO, [l[3]["bias"] for l in lay])
-            w2 = self.wgrad_now_or_later(Bp, [(y, dO, l[3]["segs"][0]["off"], 1, d, 9, c2) for d, l, y, c2 in zip(dils, lay, y1, coef2)])
+                self.bias_grad(Bp, dO, [l[3]["bias"] for l in lay])      # (model2: summed by the final bn_bwd, which reads dO as the skip gradient)
+            w2 = self.wq.now_or_later(Bp, [WSpec(a, dO, l[3]["segs"][0]["off"], 1, d, 9, c) for d, l, (a, c) in zip(dils, lay, in2)])
             g2s = [self.like(x) for _ in dils]
             s2s = [self.stat(nf, (cnt + 127) // 128) for _ in dils]
             self.conv_group(Bp, [self.dgrad_desc(dO, self.Wd(l[3]["segs"][0]["dst"]), nf, d, 9, g2, 0, mask=(y, c2.scale, c2.shift), stats2=s2)
                                  for d, l, y, c2, g2, s2 in zip(dils, lay, y1, coef2, g2s, s2s)])
             dy1s = [self.like(x) for _ in dils]
             self.bn_bwd_group(Bp, [(g2, c2, l[2], s2, y, dy1, cnt) for l, y, c2, g2, s2, dy1 in zip(lay, y1, coef2, g2s, s2s, dy1s)])
-            self.wgrad_group(Bp, w2 + [(x, dy1, l[1]["segs"][0]["off"], 1, d, 9, c1) for d, l, c1, dy1 in zip(dils, lay, coef1, dy1s)])
-            g1s = g2s
+            # no bias gradient launch: the output of a BN backward sums to zero per channel, so d b1 == 0 exactly
+            self.wq.group(Bp, w2 + [WSpec(a, dy1, l[1]["segs"][0]["off"], 1, d, 9, c) for d, l, (a, c), dy1 in zip(dils, lay, in1, dy1s)])
+            g1s = g2s                                          # g2 is dead after its bn_bwd: reuse the storage
             s1s = [self.stat(nf, (cnt + 127) // 128) for _ in dils]
             self.conv_group(Bp, [self.dgrad_desc(dy1, self.Wd(l[1]["segs"][0]["dst"]), nf, d, 9, g1, 0, mask=(x, c1.scale, c1.shift), stats2=s1)
                                  for d, l, dy1, c1, g1, s1 in zip(dils, lay, dy1s, coef1, g1s, s1s)])
@@ -1072,7 +864,6 @@ class Graph:
                         skip_bias=[l[3]["bias"] for l in lay] if v2 else None, dx_bias=True)
             Bp.scope = None
         self.back_steps.append(back)
-        return out
 
     def down(self, x: Ten, nf: int) -> Ten:
         """Conv2D(nf,(1,1),strides=(2,2)) model2.py:103-111: samples pixels 0,2,4,..; no BN, no activation."""
@@ -1089,7 +880,7 @@ class Graph:
                 dy = y.grad
                 if not y.bias_done:
                     self.bias_grad(Bp, dy, [lay["bias"]])
-                self.wgrad(Bp, x, dy, lay["segs"][0]["off"], 2, 1, 1)
+                self.wq.one(Bp, WSpec(x, dy, lay["segs"][0]["off"], 2, 1, 1))
                 gx, acc = self.gacc(x)
                 if not acc:
                     Bp.add("rua_fill_zero", gx.ptr, gx.t.numel() * gx.t.element_size())
@@ -1169,7 +960,7 @@ class Graph:
         ddescs = []
         # the per-source weight gradients: one grid where every member is a wgrad_pw launch (round 5), else one launch each (as a generic group these
         # unequal, tiny weight gradients measured slower - 18 vs 12 us)
-        self.wgrad_pw_group(Bp, [(t, pooled[up], seg["off"], 1, 1, 1) for (t, up), seg in zip(segs, lay["segs"])])
+        self.wq.pw_group(Bp, [WSpec(t, pooled[up], seg["off"], 1, 1, 1) for (t, up), seg in zip(segs, lay["segs"])])
         for (t, up), seg, tg in zip(segs, lay["segs"], targets):
             d = pooled[up]
             if tg is None:
@@ -1248,7 +1039,7 @@ class Graph:
                     self.issue(Bp, bbs, "rua_bn_bwd", "rua_bn_bwd_group")
                 if bbs is not None and pyramid and bdescs is not None:
                     # the branch convolutions' data gradients as one group (independent: own source gradients)
-                    self.wgrad_pw_group(Bp, [(p, z.grad, lay["segs"][0]["off"], 1, 1, 1) for (k, p, z, lay, zb, node) in br])
+                    self.wq.pw_group(Bp, [WSpec(p, z.grad, lay["segs"][0]["off"], 1, 1, 1) for (k, p, z, lay, zb, node) in br])
                     dd = []
                     for (k, p, z, lay, zb, node) in br:
                         gx, acc = self.gacc(p)
@@ -1389,7 +1180,7 @@ class Graph:
                     Bp.add("rua_relu_mask", dy.ptr, y.ptr, y.t.numel(), self.dt)
                 if not y.bias_done:
                     self.bias_grad(Bp, dy, [lay["bias"]])
-                self.wgrad(Bp, x, dy, lay["segs"][0]["off"], 1, 1, 9)
+                self.wq.one(Bp, WSpec(x, dy, lay["segs"][0]["off"], 1, 1, 9))
                 gx, acc = self.gacc(x, masked=x.relu_out)
                 sx = None
                 if x.bias_offs and x.relu_out and not acc and not self.dry and self.e.bn_dx_bias:
@@ -1471,9 +1262,9 @@ class Graph:
                         Bp.add("rua_relu_mask", y.grad.ptr, y.ptr, y.t.numel(), self.dt)
                     if not y.bias_done:
                         self.bias_grad(Bp, y.grad, [ly["bias"]])
-                wg = list(carried) + [(x, y.grad, ly["segs"][0]["off"], 1, 1, 9, None) for x, y, ly in convs]
-                if not later:                               # (later: these ride in the next phase's group - as the two groups of a ResBlock do, wgrad_now_or_later)
-                    self.wgrad_group(Bp, wg)
+                wg = list(carried) + [WSpec(x, y.grad, ly["segs"][0]["off"], 1, 1, 9) for x, y, ly in convs]
+                if not later:                               # (later: these ride in the next phase's group - as the two groups of a ResBlock do, WgradQueue.now_or_later)
+                    self.wq.group(Bp, wg)
                 descs, sums = [], []
                 for x, y, ly in convs:
                     gx, acc = self.gacc(x, masked=x.relu_out)
@@ -1616,7 +1407,7 @@ class Graph:
                 Bp = self.bwd
                 if pack:
                     tmp = self.alloc((w0 * 16,), torch.float32, zero=True)          # [Cout][16]: zero before every launch (the fold leaves it so)
-                    d = self.wgrad_desc(Bp, xpack, c1.grad, stem["segs"][0]["off"], 1, 1, 1, defer_ok=False)      # the fold reads tmp right behind the call: its partials are summed by the call itself
+                    d = self.wq.desc(WSpec(xpack, c1.grad, stem["segs"][0]["off"], 1, 1, 1))      # never deferred: the fold reads tmp right behind the call: its partials are summed by the call itself
                     d.dw, d.grads = tmp.data_ptr(), ()
                     self.issue(Bp, [d], "rua_conv_wgrad")
                     Bp.add("rua_stem_bwd_fold", tmp.data_ptr(), self.G(stem["segs"][0]["off"]), self.G(stem["bias"]), Cin, w0,
@@ -1689,7 +1480,7 @@ class Graph:
             for step in reversed(self.back_steps):
                 step()
             self.back_steps = []
-            self.flush_wgrad(self.bwd)
+            self.wq.flush()
 
 
 # ---------------------------------------------------------------------------------------
@@ -1781,9 +1572,9 @@ class Engine:
         self.group_1x1 = os.environ.get("RUA_GROUP_1X1", "1") != "0"       # PSPPooling's branch convolutions and the per-source gradients of concatenating 1x1 convolutions as groups
         self.group_heads = os.environ.get("RUA_GROUP_HEADS", "1") != "0"   # the heads' 3x3 convolutions (and their gradients) grouped across the heads
         self.multi_head = os.environ.get("RUA_MULTI_HEAD", "1") != "0"     # the heads' loss finalisation / d(loss)/d(logits) as one launch each
-        self.merge_wgrad = {int(v) for v in os.environ.get("RUA_MERGE_WGRAD", "1,32,64,128,256").split(",") if v}     # channel counts whose ResBlocks issue both weight-gradient groups as one (Graph.wgrad_now_or_later)
-        self.group_wgrad_pw = os.environ.get("RUA_GROUP_WGRAD_PW", "1") != "0"   # the narrow 1x1 weight gradients of a composite as one grid (Graph.wgrad_pw_group)
-        self.batch_wgrad = os.environ.get("RUA_BATCH_WGRAD", "1") != "0"         # bf16: a step's generic-tile weight gradients as one batched launch in front of each flush (Graph.wgrad_later)
+        self.merge_wgrad = {int(v) for v in os.environ.get("RUA_MERGE_WGRAD", "1,32,64,128,256").split(",") if v}     # channel counts whose ResBlocks issue both weight-gradient groups as one (WgradQueue.now_or_later)
+        self.group_wgrad_pw = os.environ.get("RUA_GROUP_WGRAD_PW", "1") != "0"   # the narrow 1x1 weight gradients of a composite as one grid (WgradQueue.pw_group)
+        self.batch_wgrad = os.environ.get("RUA_BATCH_WGRAD", "1") != "0"         # bf16: a step's generic-tile weight gradients as one batched launch in front of each flush (WgradQueue.hold_back)
         self.stem_mfma = os.environ.get("RUA_STEM_MFMA", "1") != "0"       # bf16: the stem's weight gradient through rua_stem_fwd_pack / rua_conv_wgrad / rua_stem_bwd_fold
         self.stem_stats = os.environ.get("RUA_STEM_STATS", "1") != "0"     # rua_stem_fwd_stats instead of a rua_col_stats pass over the stem's output
         self._captured: Dict[int, object] = {}

@@ -591,7 +591,7 @@ def test_conv_pointwise_group_members_share_a_grid():
 
 def test_wgrad_pointwise_group_is_one_grid():
     """rua_conv_wgrad_group over narrow 1x1 weight gradients with workspaces of their own (round 5: the per-source weight gradients of a concatenating
-    1x1 conv, the branch convs of a PSPPooling - Graph.wgrad_pw_group): members of UNEQUAL size and channel counts run as one wgrad_pw_g grid per
+    1x1 conv, the branch convs of a PSPPooling - WgradQueue.pw_group): members of UNEQUAL size and channel counts run as one wgrad_pw_g grid per
     (NCO, NCI) form, bit for bit what the members give one by one apart from the replica atomics' order, against the fp64 gradient; replicas and
     tickets are left zero; members sharing a workspace fall back to one launch each."""
     dt = L.RUA_BF16

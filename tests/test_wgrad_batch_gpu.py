@@ -1,5 +1,5 @@
 """The batched form of rua_conv_wgrad_group (rua_wgrad_desc.batch) and the engine's deferral of a step's generic-tile weight
-gradients to ONE launch in front of each flush (Graph.wgrad_later).
+gradients to ONE launch in front of each flush (WgradQueue.hold_back).
 
 Library level: the member shapes are read off the recorded cfg3 bf16 backward plan.  With bit 5 of the tuning key wgrad_group
 (every member keeps the K split it would take alone) a batch equals the single launches bit for bit; with the default split
