@@ -1,7 +1,7 @@
 // Forward and data-gradient convolutions: a segmented implicit GEMM on MFMA (gfx950), channels-last.
 // Kernels: conv_igemm, conv_dma, conv_dmap (+ _s / _chain), conv_halo, conv_pw, conv_img, conv_small, conv_splitk_finish.
 // Exports: rua_conv_fwd, rua_conv_fwd_group and the rua_conv_* queries; rua_splitk_finish_bf16 for conv_img2.hip (common.h).
-// The weight gradients (rua_conv_wgrad, launch_wgrad_taps, ...) live in conv_wgrad.hip, the weight copies in weight_prep.hip.
+// The weight gradients (rua_conv_wgrad, wgrad_plan_one, ...) live in conv_wgrad.hip, the weight copies in weight_prep.hip.
 //
 // GEMM view: rows = output pixels (n,h,w), cols = output channels, K = (segment, tap, channel).
 // A "unit" is 32 channels of one tap of one segment; a stage stages KU units of the A tile

@@ -1,19 +1,11 @@
 // Weight gradients of the convolutions on MFMA (gfx950): dW[t][co][c] += sum_pix dy[pix][co] * a[src(pix,t)][c].
-// Kernels: wgrad_kernel (generic, K split over pixels), wgrad_dmap (LDS-DMA), wgrad_taps (all taps per block), wgrad_rows32 / 64 / 128 and
+// Kernels: wgrad_kernel (generic, K split over pixels), wgrad_dmap (LDS-DMA), wgrad_taps (all taps per block), wgrad_rows32 / 64 and
 // wgrad_rowsx (wgrad_rowsx.inc: whole rows in one LDS-DMA ring), wgrad_img / wgrad_imgs (whole images resident), wgrad_pw (1x1), the
 // deterministic reductions of their partials.
-// Exports: rua_conv_wgrad, rua_conv_wgrad_group, rua_wgrad_kind, rua_wgrad_plan and the other rua_wgrad_* queries, rua_wgrad_reduce_batch.
+// Host side (behind the kernels): wgrad_plan_one() - descriptor -> WgLaunch, a pure function of descriptor, tuning and CU count - and wgrad_issue() /
+// wgrad_reduce(), which launch plans through one table of kernels (WG_KERNEL).
+// Exports, each a composition of those: rua_conv_wgrad, rua_conv_wgrad_group, rua_wgrad_kind, rua_wgrad_plan and the other rua_wgrad_* queries, rua_wgrad_reduce_batch.
 #include "common.h"
-
-// rua_wgrad_plan(): the launchers below run with g_wgrad_dry set - every geometry decision is taken, nothing is launched - and
-// report the reduction they would leave pending through g_wgrad_pending (also filled by real deferred calls).
-static thread_local bool g_wgrad_dry = false;
-static thread_local rua_wgrad_pending* g_wgrad_pending = nullptr;
-static inline void note_pending(int kind, int parts, long long n, const float* partials, float* dw, int CC, int blocks) {
-  if (!g_wgrad_pending) return;
-  g_wgrad_pending->kind = kind; g_wgrad_pending->parts = parts; g_wgrad_pending->n = n; g_wgrad_pending->partials = partials;
-  g_wgrad_pending->dw = dw; g_wgrad_pending->CC = CC; g_wgrad_pending->blocks = blocks;
-}
 
 // =========================================================================================
 // Weight gradient: dW[t][co][c] += sum_pix dy[pix][co] * a[src(pix,t)][c]
@@ -209,14 +201,6 @@ __device__ __forceinline__ void wgrad_slab_reduce_body(const float* __restrict__
 __global__ __launch_bounds__(256) void wgrad_slab_reduce(const float* __restrict__ slabs, float* __restrict__ dw, long long n4, int ksplit) {
   wgrad_slab_reduce_body(slabs, dw, n4, ksplit, (int)blockIdx.x);
 }
-static int launch_slab_reduce(const float* slabs, float* dw, long long n, int ksplit, hipStream_t st) {
-  const long long n4 = n / 4;
-  hipLaunchKernelGGL(wgrad_slab_reduce, dim3((unsigned)((n4 + SLAB_RED_COLS - 1) / SLAB_RED_COLS)), dim3(256), 0, st, slabs, dw, n4, ksplit);
-  RUA_LAUNCH_CHECK("wgrad_slab_reduce");
-  return RUA_OK;
-}
-// K slices that fit the caller's workspace as fp32 slabs (the last WG_PW_TAIL bytes belong to wgrad_pw); 1: no room
-static int slab_capacity(const rua_wgrad_desc* d, long long ndw);
 
 // =========================================================================================
 // wgrad_dmap: the weight gradient of the wide levels (C, Cout multiples of 128, bf16, stride 1, power-of-two maps) on the
@@ -1434,198 +1418,6 @@ __global__ __launch_bounds__(256) void wgrad_taps_reduce(const float* __restrict
   wgrad_taps_reduce_body(scratch, dw, CC, gx, (int)blockIdx.x);
 }
 
-// rua_conv_wgrad_group: the launchers below record instead of launching while g_wg_group is set
-struct WgGroupCapture {
-  int n;
-  int kind[RUA_MAX_WGRAD_GROUP];                 // 0 wgrad_kernel<bf16>, 1 wgrad_taps<32>, 2 wgrad_taps<64>, 3 wgrad_dmap
-  unsigned gx[RUA_MAX_WGRAD_GROUP]; int smem[RUA_MAX_WGRAD_GROUP];
-  WgK g[RUA_MAX_WGRAD_GROUP]; WgdK d[RUA_MAX_WGRAD_GROUP]; WgtK t[RUA_MAX_WGRAD_GROUP];
-  int post[RUA_MAX_WGRAD_GROUP];                 // reduction the member wants right after its grid (not deferred): 0 none, 1 block partials, 2 slabs
-  const float* part[RUA_MAX_WGRAD_GROUP]; float* dw[RUA_MAX_WGRAD_GROUP]; long long ndw[RUA_MAX_WGRAD_GROUP]; int parts[RUA_MAX_WGRAD_GROUP], CC[RUA_MAX_WGRAD_GROUP], rblocks[RUA_MAX_WGRAD_GROUP];
-};
-static thread_local WgGroupCapture* g_wg_group = nullptr;
-
-// wgrad_rows32 variants: kind 4 + 2 * (NPG == 2) + (no BatchNorm on load)
-static bool launch_rows32(int kind, bool grouped, dim3 grid, int smem, hipStream_t st, const WgtK* one, const WgtKG* many) {
-  static RuaPerDevFlag attr_[18];
-  bool& attr = attr_[(kind - 4) * 2 + (grouped ? 1 : 0)].get();
-#define RUA_ROWS_GO(NPG_, BN_) do { \
-    if (grouped) { if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_rows32_g<NPG_, BN_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-                   hipLaunchKernelGGL((wgrad_rows32_g<NPG_, BN_>), grid, dim3(NPG_ * 192), smem, st, *many); } \
-    else { if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_rows32<NPG_, BN_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-           hipLaunchKernelGGL((wgrad_rows32<NPG_, BN_>), grid, dim3(NPG_ * 192), smem, st, *one); } } while (0)
-#define RUA_ROWS64_GO(BN_) do { \
-    if (grouped) { if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_rows64_g<BN_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-                   hipLaunchKernelGGL((wgrad_rows64_g<BN_>), grid, dim3(768), smem, st, *many); } \
-    else { if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_rows64<BN_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-           hipLaunchKernelGGL((wgrad_rows64<BN_>), grid, dim3(768), smem, st, *one); } } while (0)
-#define RUA_ROWSX_GO(MODE_) do { \
-    if (grouped) { if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_rowsx_g<MODE_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-                   hipLaunchKernelGGL((wgrad_rowsx_g<MODE_>), grid, dim3(768), smem, st, *many); } \
-    else { if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_rowsx<MODE_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-           hipLaunchKernelGGL((wgrad_rowsx<MODE_>), grid, dim3(768), smem, st, *one); } } while (0)
-  switch (kind) {
-    case 4: RUA_ROWS_GO(4, true); break;
-    case 5: RUA_ROWS_GO(4, false); break;
-    case 6: RUA_ROWS_GO(2, true); break;
-    case 7: RUA_ROWS_GO(2, false); break;
-    case 8: RUA_ROWS64_GO(true); break;                  // C = 64, 128-pixel rows
-    case 9: RUA_ROWS64_GO(false); break;
-    case 11: RUA_ROWSX_GO(0); break;                     // the slot-stream form (wgrad_rowsx.inc): C = 128 on 64-pixel rows (grid.y = 2) ...
-    case 12: RUA_ROWSX_GO(1); break;                     // ... and C = 256 on 32-pixel rows, two images per stage (grid.y = 4 output-channel slices x 2 input-channel halves)
-    default: rua_set_error("launch_rows32: no kernel of kind %d", kind); return false;      // (10 was the round-4 C = 128 kernel)
-  }
-#undef RUA_ROWSX_GO
-#undef RUA_ROWS64_GO
-#undef RUA_ROWS_GO
-  return true;
-}
-
-static int launch_wgrad_taps(const rua_wgrad_desc* d, hipStream_t st) {
-  const int CC = d->C;
-  WgtK k;
-  k.a = (const unsigned char*)d->a; k.dy = (const unsigned char*)d->dy; k.scratch = (float*)d->workspace; k.dw = d->dw;
-  k.H = d->H; k.W = d->W; k.N = d->N; k.dil = d->dil;
-  k.in_scale = d->in_scale; k.in_shift = d->in_shift; k.in_relu = d->in_relu; k.sx = 0;
-  const long long M = (long long)d->N * d->H * d->W;
-  if (CC == 256 || CC == 128) {
-    // wgrad_rowsx: gx blocks per grid row share the slot stream of the member evenly; grid.y = (output-channel slice, input-channel half); a block leaves two
-    // partials [9][32][C] (or its 128 columns of them), so C / 32 x gx of them <= one per CU - the workspace contract of the all-taps kernels
-    const int ncu_ = rua_cu_count();
-    const int gy_ = CC == 256 ? 8 : 2;
-    const int share_ = (g_tune.wgrad_taps_share && d->group_members > 1) ? d->group_members : 1;
-    int gx_ = ncu_ / share_ / gy_;
-    if (gx_ > ncu_ / (CC / 32)) gx_ = ncu_ / (CC / 32);
-    const long long U_ = (long long)(CC == 256 ? d->N / 2 : d->N) * (d->H + d->dil);
-    if (gx_ > U_ / 4) gx_ = (int)(U_ / 4);               // >= 4 slots behind a block's three-row fill
-    if (gx_ < 1) gx_ = 1;
-    k.NPG = 1; k.strips = 1; k.halo = 0; k.halo4 = 0; k.group_bytes = 0; k.nchains = 0; k.spc = 0; k.seglen = 0; k.njobs = 0; k.jpw = 0;
-    k.gx = gx_; k.nworkers = gx_;
-    k.abytes = (unsigned)((size_t)M * CC * 2); k.dybytes = k.abytes;
-    const size_t smem_ = (size_t)32 * 256 + 5 * (size_t)96 * 256 + 3 * (size_t)64 * 128;
-    const int rblocks_ = rua_div_up(9 * CC * CC / 4, TAPS_RED_COLS);
-    const int kd_ = CC == 256 ? 12 : 11;
-    note_pending(1, gx_, (long long)9 * CC * CC, (const float*)k.scratch, d->dw, CC, rblocks_);
-    if (g_wgrad_dry) return RUA_OK;
-    if (g_wg_group && (g_tune.wgrad_group & 4) && g_wg_group->n < RUA_MAX_WGRAD_GROUP) {
-      WgGroupCapture& c = *g_wg_group; const int i = c.n++;
-      c.kind[i] = kd_; c.gx[i] = gx_; c.smem[i] = (int)smem_; c.t[i] = k;
-      c.post[i] = d->defer ? 0 : 1; c.part[i] = k.scratch; c.dw[i] = d->dw; c.CC[i] = CC; c.parts[i] = gx_; c.rblocks[i] = rblocks_; c.ndw[i] = 0;
-      return RUA_OK;
-    }
-    if (!launch_rows32(kd_, false, dim3(gx_, gy_), (int)smem_, st, &k, nullptr)) return RUA_ERR_ARG;
-    RUA_LAUNCH_CHECK("wgrad_rowsx");
-    if (d->defer) return RUA_OK;
-    rua_record_mid_event(st);
-    hipLaunchKernelGGL(wgrad_taps_reduce, dim3(rblocks_), dim3(256), 0, st, (const float*)k.scratch, d->dw, CC, gx_);
-    RUA_LAUNCH_CHECK("wgrad_taps_reduce");
-    return RUA_OK;
-  }
-  k.halo = 64 + 2 * d->dil;
-  k.halo4 = (k.halo + 3) / 4 * 4;
-  k.group_bytes = 64 * 64 + 3 * k.halo4 * CC * 2;
-  k.NPG = (CC == 32) ? 4 : 2;                          // 12 waves per block either way (3 kernel rows x CC/32 halves per group)
-  const int gy = CC / 32;
-  const int ncu = rua_cu_count();
-  // the members of a grouped launch share ONE round of blocks (four members of 256 blocks each ran four rounds, every block with
-  // its own prologue and 36 - 74 KB of partials to write and to reduce): tuning key wgrad_taps_share
-  const int share = (g_tune.wgrad_taps_share && (g_tune.wgrad_group & (CC == 32 ? 2 : 4)) && d->group_members > 1) ? d->group_members : 1;
-  const int target = (ncu / gy) * k.NPG / share;       // pixel groups wanted: one block per CU and output-channel half
-  k.strips = d->W / 64;
-  k.nchains = d->N * k.strips * d->dil;
-  const int ny = (d->H + d->dil - 1) / d->dil;         // lattice rows of the longest chain
-  int spc = target / k.nchains;                        // segments per chain (jobs <= groups where possible: one round)
-  if (spc < 1) spc = 1;
-  if (spc > ny) spc = ny;
-  k.seglen = (ny + spc - 1) / spc;
-  k.spc = (ny + k.seglen - 1) / k.seglen;
-  k.njobs = k.nchains * k.spc;
-  int gx = (k.njobs + k.NPG - 1) / k.NPG;
-  if (gx > ncu / gy / share) gx = ncu / gy / share;    // one block per CU and output-channel half (of this member's share); extra jobs are queued
-  if (gx < 1) gx = 1;
-  k.gx = gx;
-  k.nworkers = gx * k.NPG;
-  k.jpw = (k.njobs + k.nworkers - 1) / k.nworkers;
-  k.abytes = (unsigned)((size_t)M * CC * 2); k.dybytes = k.abytes;
-  size_t smem = (size_t)k.group_bytes * k.NPG;
-  const size_t red = (size_t)(k.NPG - 1) * 3 * (CC / 32) * 3 * 16 * 64 * 4;
-  if (red > smem) smem = red;
-  // full-width rows at C = 32: wgrad_rows32 (tuning key wgrad_rows) - the block's pixel groups share ONE ring of whole rows; a worker is a block
-  int rows_kind = 0;
-  if (g_tune.wgrad_rows && CC == 32 && (d->W == 256 || d->W == 128) && d->dil <= 31 && (!d->in_scale || d->in_relu) && (size_t)M * CC * 2 < 0x80000000ull) {
-    const int npg = d->W / 64;
-    rows_kind = 4 + (npg == 2 ? 2 : 0) + (d->in_scale ? 0 : 1);
-    k.NPG = npg; k.strips = 1;
-    k.nchains = d->N * d->dil;
-    const int blocks = ncu / share > 0 ? ncu / share : 1;
-    int spc2 = blocks / k.nchains;
-    if (spc2 < 1) spc2 = 1;
-    if (spc2 > (ny + 3) / 4) spc2 = (ny + 3) / 4;       // >= 4 rows per segment (a segment re-reads two window rows)
-    if (spc2 < 1) spc2 = 1;
-    k.seglen = (ny + spc2 - 1) / spc2;
-    k.spc = (ny + k.seglen - 1) / k.seglen;
-    k.njobs = k.nchains * k.spc;
-    gx = k.njobs < blocks ? k.njobs : blocks;
-    if (g_tune.wgrad_rows & 128) {                       // the slot stream (WgSlots): every block an equal share of the rows + separators
-      const long long U_ = (long long)d->N * (d->H + d->dil);
-      k.sx = 1; gx = (int)(U_ / 4 < blocks ? (U_ / 4 > 0 ? U_ / 4 : 1) : blocks);
-    }
-    k.gx = gx; k.nworkers = gx;
-    k.jpw = (k.njobs + gx - 1) / gx;
-    smem = (size_t)32 * 64 + 6 * (size_t)(d->W + 32) * 64 + 3 * (size_t)d->W * 64 + 128 * 4;
-    const size_t red2 = (size_t)(npg - 1) * 3 * 3 * 16 * 64 * 4;
-    if (red2 > smem) smem = red2;
-  }
-  // C = 64 on 128-pixel rows (the level-2 ResBlock): wgrad_rows64 - a block owns whole rows and BOTH output-channel halves (tuning key wgrad_rows & 2)
-  if ((g_tune.wgrad_rows & 2) && CC == 64 && d->W == 128 && d->dil <= 31 && (!d->in_scale || d->in_relu) && (size_t)M * CC * 2 < 0x80000000ull) {
-    rows_kind = 8 + (d->in_scale ? 0 : 1);
-    k.NPG = 2; k.strips = 1;
-    k.nchains = d->N * d->dil;
-    int blocks = ncu / share > 0 ? ncu / share : 1;     // one round of blocks for the group; a block leaves TWO partials (one per output-channel half) and the
-    if (blocks > ncu / 2) blocks = ncu / 2;             // scratch of wgrad_taps_kernel<64> holds ncu of them per weight gradient
-    int spc2 = blocks / k.nchains;
-    if (spc2 < 1) spc2 = 1;
-    if (spc2 > (ny + 3) / 4) spc2 = (ny + 3) / 4;       // >= 4 rows per segment (a segment re-reads two window rows)
-    if (spc2 < 1) spc2 = 1;
-    k.seglen = (ny + spc2 - 1) / spc2;
-    k.spc = (ny + k.seglen - 1) / k.seglen;
-    k.njobs = k.nchains * k.spc;
-    gx = k.njobs < blocks ? k.njobs : blocks;
-    if (g_tune.wgrad_rows & 128) {
-      const long long U_ = (long long)d->N * (d->H + d->dil);
-      k.sx = 1; gx = (int)(U_ / 4 < blocks ? (U_ / 4 > 0 ? U_ / 4 : 1) : blocks);
-    }
-    k.gx = gx; k.nworkers = gx;
-    k.jpw = (k.njobs + gx - 1) / gx;
-    smem = (size_t)32 * 128 + 5 * (size_t)(128 + 32) * 128 + 3 * (size_t)128 * 128 + 256 * 4;
-  }
-  const int rblocks = rua_div_up(9 * CC * CC / 4, TAPS_RED_COLS);
-  note_pending(1, gx, (long long)9 * CC * CC, (const float*)k.scratch, d->dw, CC, rblocks);
-  if (g_wgrad_dry) return RUA_OK;
-  if (g_wg_group && (g_tune.wgrad_group & (CC == 32 ? 2 : 4)) && g_wg_group->n < RUA_MAX_WGRAD_GROUP) {
-    WgGroupCapture& c = *g_wg_group; const int i = c.n++;
-    c.kind[i] = rows_kind ? rows_kind : (CC == 32 ? 1 : 2); c.gx[i] = gx; c.smem[i] = (int)smem; c.t[i] = k;
-    c.post[i] = d->defer ? 0 : 1; c.part[i] = k.scratch; c.dw[i] = d->dw; c.CC[i] = CC; c.parts[i] = gx; c.rblocks[i] = rblocks; c.ndw[i] = 0;
-    return RUA_OK;
-  }
-  static RuaPerDevFlag attr32f, attr64f;
-  bool& attr32 = attr32f.get(); bool& attr64 = attr64f.get();
-  if (rows_kind) { if (!launch_rows32(rows_kind, false, dim3(gx), (int)smem, st, &k, nullptr)) return RUA_ERR_ARG; }
-  else if (CC == 32) {
-    if (!attr32) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_taps_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr32 = true; }
-    hipLaunchKernelGGL((wgrad_taps_kernel<32>), dim3(gx, gy), dim3(768), smem, st, k);
-  } else {
-    if (!attr64) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_taps_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr64 = true; }
-    hipLaunchKernelGGL((wgrad_taps_kernel<64>), dim3(gx, gy), dim3(768), smem, st, k);
-  }
-  RUA_LAUNCH_CHECK("wgrad_taps_kernel");
-  if (d->defer) return RUA_OK;                         // the caller sums the block partials later (rua_wgrad_reduce_batch)
-  rua_record_mid_event(st);
-  hipLaunchKernelGGL(wgrad_taps_reduce, dim3(rblocks), dim3(256), 0, st, (const float*)k.scratch, d->dw, CC, gx);
-  RUA_LAUNCH_CHECK("wgrad_taps_reduce");
-  return RUA_OK;
-}
-
 // =========================================================================================
 // wgrad_pw: the weight gradient of the narrow 1x1 convolutions (C, Cout <= 64: stem, PSP branches, combine / upsampling
 // convs of the top levels).  These are memory-bound (67 MB in for a 4 KB..16 KB dW at 256x256x32) and were slow on
@@ -1646,9 +1438,6 @@ struct WgpK {
   float* slabs;                     // round 5: block b stores its sum as partial [b][Cout][C] here (summed in a fixed order by wgrad_slab_reduce / rua_wgrad_reduce_batch); null: replicas + tickets
 };
 struct WgpKG { WgpK k[RUA_MAX_BRANCH]; };
-// rua_conv_wgrad_group: wgrad_pw members (own workspaces: own replicas and tickets) are recorded here and issued as ONE grid per (NCO, NCI) form
-struct WgPwCapture { int n; WgpK k[RUA_MAX_BRANCH]; int form[RUA_MAX_BRANCH]; int post[RUA_MAX_BRANCH]; };      // post: the member's partials are summed right behind the grid (not deferred)
-static thread_local WgPwCapture* g_wg_pw = nullptr;
 constexpr int WG_PW_REPLICAS = 16;
 constexpr int64_t WG_PW_TAIL = (int64_t)WG_PW_REPLICAS * 64 * 64 * 4 + 8192;   // replicas + two ticket pages at the end of the workspace
 
@@ -1880,7 +1669,74 @@ template <int NCO, int NCI> __global__ __launch_bounds__(1024) void wgrad_pw_g(c
   wgrad_pw_body<NCO, NCI>(p);
 }
 
+// =========================================================================================
+// Host side: plan, then issue.  wgrad_plan_one() turns a descriptor into a WgLaunch - kernel, grid, LDS, kernel arguments, the reduction it leaves
+// pending - as a pure function of the descriptor, g_tune and rua_cu_count(): it launches nothing and keeps no state.  wgrad_issue() puts plans of
+// one kernel on a stream (one: the kernel itself; several: its grouped form), wgrad_reduce() a plan's reduction.  Every export below is a composition
+// of these, so what rua_wgrad_plan / rua_wgrad_group_plan report is what the launch does.
+enum WgKernel {
+  WG_TILES_BF16, WG_TILES_F32, WG_TAPS32, WG_TAPS64,
+  WG_ROWS32_N4_BN, WG_ROWS32_N4, WG_ROWS32_N2_BN, WG_ROWS32_N2, WG_ROWS64_BN, WG_ROWS64, WG_ROWSX0, WG_ROWSX1,      // rows32: + 2 (two pixel groups) + 1 (no BatchNorm on load)
+  WG_DMAP, WG_IMG8, WG_IMG16, WG_IMGS8, WG_IMGS16,
+  WG_PW11, WG_PW12, WG_PW21, WG_PW22,                                                                                // + 2 (Cout > 32) + 1 (C > 32)
+  WG_KERNELS
+};
+enum WgArgs { WG_ARGS_K, WG_ARGS_D, WG_ARGS_T, WG_ARGS_P };      // WgK, WgdK, WgtK, WgpK
+struct WgLaunch {
+  int kernel;                                  // WgKernel
+  unsigned gx, gy, block; int smem;            // grid of a launch of its own, threads per block, dynamic LDS bytes
+  union { WgK g; WgdK d; WgtK t; WgpK p; } k;  // the member of WgKernelRow.args
+  rua_wgrad_pending pending;                   // the reduction the kernel leaves behind (kind 0: none)
+  bool defer;                                  // rua_wgrad_desc.defer: the caller runs that reduction (rua_wgrad_reduce_batch)
+  bool groupable;                              // rua_conv_wgrad_group may put it into a grid shared with other members on the same kernel (tuning key wgrad_group)
+};
+
+// one row per WgKernel: the kernel, its grouped form (null: none), which arguments they take, the dynamic LDS to allow through hipFuncSetAttribute (0: the default will do)
+struct WgKernelRow { const char* name; const void* one; const void* many; int args; int lds; };
+#define WG_FN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+static const WgKernelRow WG_KERNEL[WG_KERNELS] = {
+  {"wgrad_kernel", WG_FN(wgrad_kernel<bf16_t>), WG_FN(wgrad_kernel_g), WG_ARGS_K, 0},
+  {"wgrad_kernel", WG_FN(wgrad_kernel<float>), nullptr, WG_ARGS_K, 0},
+  {"wgrad_taps_kernel", WG_FN(wgrad_taps_kernel<32>), WG_FN(wgrad_taps_kernel_g<32>), WG_ARGS_T, 160 * 1024},
+  {"wgrad_taps_kernel", WG_FN(wgrad_taps_kernel<64>), WG_FN(wgrad_taps_kernel_g<64>), WG_ARGS_T, 160 * 1024},
+  {"wgrad_rows32", WG_FN(wgrad_rows32<4, true>), WG_FN(wgrad_rows32_g<4, true>), WG_ARGS_T, 160 * 1024},
+  {"wgrad_rows32", WG_FN(wgrad_rows32<4, false>), WG_FN(wgrad_rows32_g<4, false>), WG_ARGS_T, 160 * 1024},
+  {"wgrad_rows32", WG_FN(wgrad_rows32<2, true>), WG_FN(wgrad_rows32_g<2, true>), WG_ARGS_T, 160 * 1024},
+  {"wgrad_rows32", WG_FN(wgrad_rows32<2, false>), WG_FN(wgrad_rows32_g<2, false>), WG_ARGS_T, 160 * 1024},
+  {"wgrad_rows64", WG_FN(wgrad_rows64<true>), WG_FN(wgrad_rows64_g<true>), WG_ARGS_T, 160 * 1024},
+  {"wgrad_rows64", WG_FN(wgrad_rows64<false>), WG_FN(wgrad_rows64_g<false>), WG_ARGS_T, 160 * 1024},
+  {"wgrad_rowsx", WG_FN(wgrad_rowsx<0>), WG_FN(wgrad_rowsx_g<0>), WG_ARGS_T, 160 * 1024},
+  {"wgrad_rowsx", WG_FN(wgrad_rowsx<1>), WG_FN(wgrad_rowsx_g<1>), WG_ARGS_T, 160 * 1024},
+  {"wgrad_dmap", WG_FN(wgrad_dmap), WG_FN(wgrad_dmap_g), WG_ARGS_D, 96 * 1024},
+  {"wgrad_img", WG_FN(wgrad_img<8>), nullptr, WG_ARGS_K, 160 * 1024},
+  {"wgrad_img", WG_FN(wgrad_img<16>), nullptr, WG_ARGS_K, 160 * 1024},
+  {"wgrad_imgs", WG_FN(wgrad_imgs<8>), nullptr, WG_ARGS_K, 160 * 1024},
+  {"wgrad_imgs", WG_FN(wgrad_imgs<16>), nullptr, WG_ARGS_K, 160 * 1024},
+  {"wgrad_pw", WG_FN(wgrad_pw<1, 1>), WG_FN(wgrad_pw_g<1, 1>), WG_ARGS_P, 0},
+  {"wgrad_pw", WG_FN(wgrad_pw<1, 2>), WG_FN(wgrad_pw_g<1, 2>), WG_ARGS_P, wgrad_pw_smem<1, 2>()},
+  {"wgrad_pw", WG_FN(wgrad_pw<2, 1>), WG_FN(wgrad_pw_g<2, 1>), WG_ARGS_P, wgrad_pw_smem<2, 1>()},
+  {"wgrad_pw", WG_FN(wgrad_pw<2, 2>), WG_FN(wgrad_pw_g<2, 2>), WG_ARGS_P, wgrad_pw_smem<2, 2>()},
+};
+#undef WG_FN
+
 static int64_t wg_taps_bytes(const rua_wgrad_desc* d) { return (int64_t)rua_cu_count() * 9 * 32 * (int64_t)d->C * 4; }   // one block partial of [9][32][C] fp32 per CU
+
+extern "C" int64_t rua_wgrad_workspace_bytes(const rua_wgrad_desc* d) {
+  if (!d) return 0;
+  // all-taps block partials, or 64 K-slice slabs of dW (capped at 64 MiB: the planner splits K no further than the slabs that
+  // fit), + wgrad_pw's replicas and ticket (the tail)
+  int64_t slabs = (int64_t)64 * d->taps * d->Cout * d->C * 4;
+  if (slabs > (64ll << 20)) slabs = 64ll << 20;
+  const int64_t taps = wg_taps_bytes(d);
+  return (taps > slabs ? taps : slabs) + WG_PW_TAIL;
+}
+
+// K slices that fit the caller's workspace as fp32 slabs (the last WG_PW_TAIL bytes belong to wgrad_pw); 1: no room
+static int slab_capacity(const rua_wgrad_desc* d, long long ndw) {
+  if (!d->workspace || d->workspace_bytes <= WG_PW_TAIL) return 1;
+  const long long n = (d->workspace_bytes - WG_PW_TAIL) / (ndw * 4);
+  return n > 64 ? 64 : (int)n;
+}
 
 static bool pick_wgrad_pw(const rua_wgrad_desc* d) {
   const int on = g_tune.wgrad_pw;
@@ -1893,126 +1749,13 @@ static bool pick_wgrad_pw(const rua_wgrad_desc* d) {
          (long long)d->N * d->Hs * d->Ws * d->C * 2 < (1ll << 31) &&
          (long long)(d->H - 1) * d->stride < d->Hs && (long long)(d->W - 1) * d->stride < d->Ws;
 }
-
-static int launch_wgrad_pw(const rua_wgrad_desc* d, hipStream_t st) {
-  WgpK k;
-  k.a = (const unsigned char*)d->a; k.dy = (const unsigned char*)d->dy; k.dw = d->dw;
-  char* tail = (char*)d->workspace + d->workspace_bytes - WG_PW_TAIL;
-  k.rep = (float*)tail; k.cnt = (int*)(tail + WG_PW_TAIL - 8192);
-  k.C = d->C; k.Cout = d->Cout; k.Hs = d->Hs; k.Ws = d->Ws; k.H = d->H; k.W = d->W; k.stride = d->stride;
-  k.dense = (d->stride == 1 && d->Hs == d->H && d->Ws == d->W) ? 1 : 0;
-  int ws = 0, hs = 0; while ((1 << ws) < d->W) ++ws; while ((1 << hs) < d->H) ++hs;
-  k.wshift = ws; k.hshift = hs;
-  k.M = (int)((long long)d->N * d->H * d->W);
-  k.abytes = (unsigned)((size_t)d->N * d->Hs * d->Ws * d->C * 2); k.dybytes = (unsigned)((size_t)k.M * d->Cout * 2);
-  const int nco = d->Cout > 32 ? 2 : 1, nci = d->C > 32 ? 2 : 1;
-  const int pxw = (nco + nci <= 2) ? 32 : 16;
-  const int target = g_tune.wgpw_blocks > 0 ? g_tune.wgpw_blocks : rua_cu_count();    // blocks of 16 waves, one per CU
-  long long waves = (long long)target * 16;
-  if (waves > k.M / 128) waves = k.M / 128;                // >= 128 pixels per wave
-  if (waves < 16) waves = 16;
-  long long ppw = (k.M + waves - 1) / waves;
-  ppw = (ppw + 2 * pxw - 1) / (2 * pxw) * (2 * pxw);       // whole double iterations
-  k.px_per_wave = (int)ppw;
-  {   // replicas: atomic chains of ~64 blocks per address; fewer replicas = fewer exchanges for the finishing block
-    const long long nblk = (k.M + ppw * 16 - 1) / (ppw * 16);
-    k.R = (int)(nblk / 32); if (k.R < 1) k.R = 1; if (k.R > WG_PW_REPLICAS) k.R = WG_PW_REPLICAS;
-    if (g_tune.wgpw_r > 0) k.R = g_tune.wgpw_r > WG_PW_REPLICAS ? WG_PW_REPLICAS : g_tune.wgpw_r;
-  }
-  const unsigned grid = (unsigned)((k.M + ppw * 16 - 1) / (ppw * 16));
-  k.nblk = (int)grid;
-  // block partials in front of the tail (tuning key wgrad_pw, bit 1) where the workspace holds one per block; else replicas + tickets (nothing pending)
-  const long long nel = (long long)d->Cout * d->C;
-  // (a call that reduces right away keeps the replicas unless bit 2 is set: one block walking 256 partials of a 2 KB dW - the stem's - takes 10 us longer than the tickets)
-  const bool slab = (g_tune.wgrad_pw & 2) && (d->defer || (g_tune.wgrad_pw & 4)) && (long long)grid * nel * 4 <= (long long)d->workspace_bytes - WG_PW_TAIL;
-  k.slabs = slab ? (float*)d->workspace : nullptr;
-  if (slab) note_pending(2, (int)grid, nel, k.slabs, d->dw, 0, (int)((nel / 4 + SLAB_RED_COLS - 1) / SLAB_RED_COLS));
-  if (g_wgrad_dry) return RUA_OK;
-  if (g_wg_pw && g_wg_pw->n < RUA_MAX_BRANCH) {            // a member of a group: recorded, issued by rua_conv_wgrad_group
-    WgPwCapture& c = *g_wg_pw; const int i = c.n++;
-    c.k[i] = k; c.form[i] = (nco - 1) * 2 + (nci - 1); c.post[i] = (slab && !d->defer) ? 1 : 0;
-    return RUA_OK;
-  }
-  constexpr int s11 = wgrad_pw_smem<1, 1>(), s21 = wgrad_pw_smem<2, 1>(), s12 = wgrad_pw_smem<1, 2>(), s22 = wgrad_pw_smem<2, 2>();
-  static RuaPerDevFlag attr_;
-  bool& attr = attr_.get();
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pw<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, s21);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pw<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, s12);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pw<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, s22);
-    attr = true;
-  }
-  if (nco == 1 && nci == 1) hipLaunchKernelGGL((wgrad_pw<1, 1>), dim3(grid), dim3(1024), s11, st, k);
-  else if (nco == 2 && nci == 1) hipLaunchKernelGGL((wgrad_pw<2, 1>), dim3(grid), dim3(1024), s21, st, k);
-  else if (nco == 1 && nci == 2) hipLaunchKernelGGL((wgrad_pw<1, 2>), dim3(grid), dim3(1024), s12, st, k);
-  else hipLaunchKernelGGL((wgrad_pw<2, 2>), dim3(grid), dim3(1024), s22, st, k);
-  RUA_LAUNCH_CHECK("wgrad_pw");
-  if (slab && !d->defer) { rua_record_mid_event(st); return launch_slab_reduce(k.slabs, d->dw, nel, (int)grid, st); }
-  return RUA_OK;
-}
-
-extern "C" int64_t rua_wgrad_workspace_bytes(const rua_wgrad_desc* d) {
-  if (!d) return 0;
-  // all-taps block partials, or 64 K-slice slabs of dW (capped at 64 MiB: the launchers split K no further than the slabs that
-  // fit), + wgrad_pw's replicas and ticket (the tail)
-  int64_t slabs = (int64_t)64 * d->taps * d->Cout * d->C * 4;
-  if (slabs > (64ll << 20)) slabs = 64ll << 20;
-  const int64_t taps = wg_taps_bytes(d);
-  return (taps > slabs ? taps : slabs) + WG_PW_TAIL;
-}
-
-static int slab_capacity(const rua_wgrad_desc* d, long long ndw) {
-  if (!d->workspace || d->workspace_bytes <= WG_PW_TAIL) return 1;
-  const long long n = (d->workspace_bytes - WG_PW_TAIL) / (ndw * 4);
-  return n > 64 ? 64 : (int)n;
-}
-
-// which kernel a descriptor launches: 1 = all-taps (top levels), 0 = generic tiled
-static int launch_wgrad_dmap(const rua_wgrad_desc* d, hipStream_t st) {
-  WgdK k;
-  k.a = (const unsigned char*)d->a; k.dy = (const unsigned char*)d->dy; k.dw = d->dw;
-  k.C = d->C; k.Cout = d->Cout; k.H = d->H; k.W = d->W; k.dil = d->dil; k.taps = d->taps;
-  k.M = (long long)d->N * d->H * d->W;
-  int wsh = 0; while ((1 << wsh) < d->W) ++wsh;
-  k.wsh = wsh;
-  k.ntc = d->Cout / 128; k.nti = d->C / 128;
-  const long long tiles = (long long)k.ntc * k.nti * d->taps;
-  const int stages = (int)((k.M + 63) / 64);
-  const int target = g_tune.wgd_blocks > 0 ? g_tune.wgd_blocks : rua_cu_count();
-  long long want = target / tiles; if (want < 1) want = 1;
-  if (want > stages / 4) want = stages / 4;             // >= 4 stages per K slice
-  if (want < 1) want = 1;
-  const long long ndw = (long long)d->taps * d->Cout * d->C;
-  const int cap = g_tune.wgrad_slabs ? slab_capacity(d, ndw) : 0;
-  if (cap >= 2 && want > cap) want = cap;               // deterministic K split: one fp32 slab per slice must fit the workspace
-  k.stages_per_split = (int)((stages + want - 1) / want);
-  k.ksplit = (stages + k.stages_per_split - 1) / k.stages_per_split;
-  k.slabs = (cap >= 2 && k.ksplit > 1) ? (float*)d->workspace : nullptr;
-  k.abytes = (unsigned)((size_t)k.M * d->C * 2); k.dybytes = (unsigned)((size_t)k.M * d->Cout * 2);
-  k.ks_slow = g_tune.wgd_ks_slow;
-  if (k.slabs) note_pending(2, k.ksplit, ndw, k.slabs, d->dw, 0, (int)((ndw / 4 + SLAB_RED_COLS - 1) / SLAB_RED_COLS));
-  if (g_wgrad_dry) return RUA_OK;
-  if (g_wg_group && (g_tune.wgrad_group & 8) && g_wg_group->n < RUA_MAX_WGRAD_GROUP) {
-    WgGroupCapture& c = *g_wg_group; const int i = c.n++;
-    c.kind[i] = 3; c.gx[i] = (unsigned)(tiles * k.ksplit); c.smem[i] = 96 * 1024; c.d[i] = k;
-    c.post[i] = (k.slabs && !d->defer) ? 2 : 0; c.part[i] = k.slabs; c.dw[i] = d->dw; c.ndw[i] = ndw; c.parts[i] = k.ksplit; c.CC[i] = 0; c.rblocks[i] = 0;
-    return RUA_OK;
-  }
-  static RuaPerDevFlag attr_;
-  bool& attr = attr_.get();
-  if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_dmap), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr = true; }
-  hipLaunchKernelGGL(wgrad_dmap, dim3((unsigned)(tiles * k.ksplit)), dim3(256), 96 * 1024, st, k);
-  RUA_LAUNCH_CHECK("wgrad_dmap");
-  if (k.slabs && !d->defer) { rua_record_mid_event(st); return launch_slab_reduce(k.slabs, d->dw, ndw, k.ksplit, st); }
-  return RUA_OK;
-}
-
 // wgrad_rowsx<1>: C = Cout = 256 on 32-pixel rows, an even number of images (the level-4 ResBlock), dilation <= 16 (the zeros between the two rows of a slot)
 static bool wgrad_rows256_ok(const rua_wgrad_desc* d) {
   return (g_tune.wgrad_rows & 32) && d->dtype == RUA_BF16 && d->taps == 9 && d->stride == 1 && d->C == 256 && d->Cout == 256 && d->W == 32 && d->N % 2 == 0 && d->N >= 2 &&
          d->Hs == d->H && d->Ws == d->W && d->dil >= 1 && d->dil <= 16 && !d->in_scale && d->workspace && d->workspace_bytes >= wg_taps_bytes(d) &&
          (long long)d->N * d->H * d->W * d->C * 2 < (1ll << 31);
 }
+// which kernel family a descriptor lands on: 0 generic tiles (or a whole-image kernel: wgrad_img_pick), 1 all-taps, 2 wgrad_dmap, 3 wgrad_pw
 extern "C" int rua_wgrad_kind(const rua_wgrad_desc* d) {
   if (!d) return RUA_ERR_ARG;
   if (pick_wgrad_pw(d)) return 3;
@@ -2052,23 +1795,193 @@ static int wgrad_img_pick(const rua_wgrad_desc* d) {
 }
 extern "C" int rua_wgrad_img_kind(const rua_wgrad_desc* d) { return (d && rua_wgrad_kind(d) == 0) ? wgrad_img_pick(d) : 0; }
 
-// a member of a batched launch (wgrad_batch_launch / rua_wgrad_group_plan): rua_conv_wgrad takes the K split from here and hands its kernel arguments back
-struct WgBatchMember { long long want; WgK k; unsigned grid; long long ndw; };
-static thread_local WgBatchMember* g_wg_batch = nullptr;
+// ---- planning ----------------------------------------------------------------------------------------------------------
+static void wgrad_plan_grid(WgLaunch* L, int kernel, unsigned gx, unsigned gy, unsigned block, size_t smem, int group_bit) {
+  L->kernel = kernel; L->gx = gx; L->gy = gy; L->block = block; L->smem = (int)smem; L->groupable = (g_tune.wgrad_group & group_bit) != 0;
+}
+static void wgrad_plan_pending(WgLaunch* L, int kind, int parts, long long n, const float* partials, float* dw, int CC) {
+  rua_wgrad_pending& r = L->pending;
+  r.kind = kind; r.parts = parts; r.n = n; r.partials = partials; r.dw = dw; r.CC = CC;
+  r.blocks = kind == 1 ? rua_div_up((int)(n / 4), TAPS_RED_COLS) : (int)((n / 4 + SLAB_RED_COLS - 1) / SLAB_RED_COLS);
+}
 
-extern "C" int rua_conv_wgrad(const rua_wgrad_desc* d, void* stream) {
+// wgrad_rows32 / wgrad_rows64: a worker is a block that owns whole rows.  The N x dil chains are cut into segments of >= 4 lattice rows (a segment re-reads two
+// window rows) for `blocks` blocks - one round for the members that share the chip, at most `most`: the workspace holds one partial per CU, and a block that owns
+// both output-channel halves leaves two.  Returns grid.x.
+static int wgrad_rows_split(const rua_wgrad_desc* d, WgtK& k, int npg, int blocks, int most) {
+  if (blocks < 1) blocks = 1;
+  if (blocks > most) blocks = most;
+  const int ny = (d->H + d->dil - 1) / d->dil;         // lattice rows of the longest chain
+  k.NPG = npg; k.strips = 1;
+  k.nchains = d->N * d->dil;
+  int spc = blocks / k.nchains;
+  if (spc < 1) spc = 1;
+  if (spc > (ny + 3) / 4) spc = (ny + 3) / 4;
+  if (spc < 1) spc = 1;
+  k.seglen = (ny + spc - 1) / spc;
+  k.spc = (ny + k.seglen - 1) / k.seglen;
+  k.njobs = k.nchains * k.spc;
+  int gx = k.njobs < blocks ? k.njobs : blocks;
+  if (g_tune.wgrad_rows & 128) {                       // the slot stream (WgSlots): every block an equal share of the rows + separators
+    const long long U = (long long)d->N * (d->H + d->dil);
+    k.sx = 1; gx = (int)(U / 4 < blocks ? (U / 4 > 0 ? U / 4 : 1) : blocks);
+  }
+  k.gx = gx; k.nworkers = gx;
+  k.jpw = (k.njobs + gx - 1) / gx;
+  return gx;
+}
+
+// rua_wgrad_kind() == 1: the all-taps kernels and the row kernels that took over most of their shapes
+static void wgrad_plan_taps(const rua_wgrad_desc* d, WgLaunch* L) {
+  const int CC = d->C, ncu = rua_cu_count();
+  WgtK& k = L->k.t;
+  k.a = (const unsigned char*)d->a; k.dy = (const unsigned char*)d->dy; k.scratch = (float*)d->workspace; k.dw = d->dw;
+  k.H = d->H; k.W = d->W; k.N = d->N; k.dil = d->dil;
+  k.in_scale = d->in_scale; k.in_shift = d->in_shift; k.in_relu = d->in_relu; k.sx = 0;
+  const long long M = (long long)d->N * d->H * d->W;
+  k.abytes = (unsigned)((size_t)M * CC * 2); k.dybytes = k.abytes;
+  if (CC == 256 || CC == 128) {
+    // wgrad_rowsx: gx blocks per grid row share the slot stream of the member evenly; grid.y = (output-channel slice, input-channel half); a block leaves two
+    // partials [9][32][C] (or its 128 columns of them), so C / 32 x gx of them <= one per CU - the workspace contract of the all-taps kernels
+    const int gy = CC == 256 ? 8 : 2;
+    const int share = (g_tune.wgrad_taps_share && d->group_members > 1) ? d->group_members : 1;
+    int gx = ncu / share / gy;
+    if (gx > ncu / (CC / 32)) gx = ncu / (CC / 32);
+    const long long U = (long long)(CC == 256 ? d->N / 2 : d->N) * (d->H + d->dil);
+    if (gx > U / 4) gx = (int)(U / 4);                 // >= 4 slots behind a block's three-row fill
+    if (gx < 1) gx = 1;
+    k.NPG = 1; k.strips = 1; k.halo = 0; k.halo4 = 0; k.group_bytes = 0; k.nchains = 0; k.spc = 0; k.seglen = 0; k.njobs = 0; k.jpw = 0;
+    k.gx = gx; k.nworkers = gx;
+    wgrad_plan_grid(L, CC == 256 ? WG_ROWSX1 : WG_ROWSX0, gx, gy, 768, (size_t)32 * 256 + 5 * (size_t)96 * 256 + 3 * (size_t)64 * 128, 4);
+    wgrad_plan_pending(L, 1, gx, (long long)9 * CC * CC, k.scratch, d->dw, CC);
+    return;
+  }
+  k.halo = 64 + 2 * d->dil;
+  k.halo4 = (k.halo + 3) / 4 * 4;
+  k.group_bytes = 64 * 64 + 3 * k.halo4 * CC * 2;
+  k.NPG = (CC == 32) ? 4 : 2;                          // 12 waves per block either way (3 kernel rows x CC/32 halves per group)
+  const int gy = CC / 32, group_bit = CC == 32 ? 2 : 4;
+  // the members of a grouped launch share ONE round of blocks (four members of 256 blocks each ran four rounds, every block with
+  // its own prologue and 36 - 74 KB of partials to write and to reduce): tuning key wgrad_taps_share
+  const int share = (g_tune.wgrad_taps_share && (g_tune.wgrad_group & group_bit) && d->group_members > 1) ? d->group_members : 1;
+  const int target = (ncu / gy) * k.NPG / share;       // pixel groups wanted: one block per CU and output-channel half
+  k.strips = d->W / 64;
+  k.nchains = d->N * k.strips * d->dil;
+  const int ny = (d->H + d->dil - 1) / d->dil;         // lattice rows of the longest chain
+  int spc = target / k.nchains;                        // segments per chain (jobs <= groups where possible: one round)
+  if (spc < 1) spc = 1;
+  if (spc > ny) spc = ny;
+  k.seglen = (ny + spc - 1) / spc;
+  k.spc = (ny + k.seglen - 1) / k.seglen;
+  k.njobs = k.nchains * k.spc;
+  int gx = (k.njobs + k.NPG - 1) / k.NPG;
+  if (gx > ncu / gy / share) gx = ncu / gy / share;    // one block per CU and output-channel half (of this member's share); extra jobs are queued
+  if (gx < 1) gx = 1;
+  k.gx = gx;
+  k.nworkers = gx * k.NPG;
+  k.jpw = (k.njobs + k.nworkers - 1) / k.nworkers;
+  size_t smem = (size_t)k.group_bytes * k.NPG;
+  const size_t red = (size_t)(k.NPG - 1) * 3 * (CC / 32) * 3 * 16 * 64 * 4;
+  if (red > smem) smem = red;
+  wgrad_plan_grid(L, CC == 32 ? WG_TAPS32 : WG_TAPS64, gx, gy, 768, smem, group_bit);
+  const bool rows_ok = d->dil <= 31 && (!d->in_scale || d->in_relu) && (size_t)M * CC * 2 < 0x80000000ull;
+  if (g_tune.wgrad_rows && CC == 32 && (d->W == 256 || d->W == 128) && rows_ok) {
+    // full-width rows at C = 32: wgrad_rows32 (tuning key wgrad_rows) - the block's pixel groups share ONE ring of whole rows
+    const int npg = d->W / 64;
+    gx = wgrad_rows_split(d, k, npg, ncu / share, ncu);
+    smem = (size_t)32 * 64 + 6 * (size_t)(d->W + 32) * 64 + 3 * (size_t)d->W * 64 + 128 * 4;
+    const size_t red2 = (size_t)(npg - 1) * 3 * 3 * 16 * 64 * 4;
+    if (red2 > smem) smem = red2;
+    wgrad_plan_grid(L, WG_ROWS32_N4_BN + (npg == 2 ? 2 : 0) + (d->in_scale ? 0 : 1), gx, 1, npg * 192, smem, group_bit);
+  } else if ((g_tune.wgrad_rows & 2) && CC == 64 && d->W == 128 && rows_ok) {
+    // C = 64 on 128-pixel rows (the level-2 ResBlock): wgrad_rows64 - a block owns whole rows and BOTH output-channel halves (tuning key wgrad_rows & 2)
+    gx = wgrad_rows_split(d, k, 2, ncu / share, ncu / 2);
+    wgrad_plan_grid(L, d->in_scale ? WG_ROWS64_BN : WG_ROWS64, gx, 1, 768, (size_t)32 * 128 + 5 * (size_t)(128 + 32) * 128 + 3 * (size_t)128 * 128 + 256 * 4, group_bit);
+  }
+  wgrad_plan_pending(L, 1, gx, (long long)9 * CC * CC, k.scratch, d->dw, CC);
+}
+
+// rua_wgrad_kind() == 3: every wave streams a pixel range of its own
+static void wgrad_plan_pw(const rua_wgrad_desc* d, WgLaunch* L) {
+  WgpK& k = L->k.p;
+  k.a = (const unsigned char*)d->a; k.dy = (const unsigned char*)d->dy; k.dw = d->dw;
+  char* tail = (char*)d->workspace + d->workspace_bytes - WG_PW_TAIL;
+  k.rep = (float*)tail; k.cnt = (int*)(tail + WG_PW_TAIL - 8192);
+  k.C = d->C; k.Cout = d->Cout; k.Hs = d->Hs; k.Ws = d->Ws; k.H = d->H; k.W = d->W; k.stride = d->stride;
+  k.dense = (d->stride == 1 && d->Hs == d->H && d->Ws == d->W) ? 1 : 0;
+  int ws = 0, hs = 0; while ((1 << ws) < d->W) ++ws; while ((1 << hs) < d->H) ++hs;
+  k.wshift = ws; k.hshift = hs;
+  k.M = (int)((long long)d->N * d->H * d->W);
+  k.abytes = (unsigned)((size_t)d->N * d->Hs * d->Ws * d->C * 2); k.dybytes = (unsigned)((size_t)k.M * d->Cout * 2);
+  const int nco = d->Cout > 32 ? 2 : 1, nci = d->C > 32 ? 2 : 1;
+  const int pxw = (nco + nci <= 2) ? 32 : 16;
+  const int target = g_tune.wgpw_blocks > 0 ? g_tune.wgpw_blocks : rua_cu_count();    // blocks of 16 waves, one per CU
+  long long waves = (long long)target * 16;
+  if (waves > k.M / 128) waves = k.M / 128;                // >= 128 pixels per wave
+  if (waves < 16) waves = 16;
+  long long ppw = (k.M + waves - 1) / waves;
+  ppw = (ppw + 2 * pxw - 1) / (2 * pxw) * (2 * pxw);       // whole double iterations
+  k.px_per_wave = (int)ppw;
+  const unsigned grid = (unsigned)((k.M + ppw * 16 - 1) / (ppw * 16));
+  k.nblk = (int)grid;
+  // replicas: atomic chains of ~64 blocks per address; fewer replicas = fewer exchanges for the finishing block
+  k.R = k.nblk / 32; if (k.R < 1) k.R = 1; if (k.R > WG_PW_REPLICAS) k.R = WG_PW_REPLICAS;
+  if (g_tune.wgpw_r > 0) k.R = g_tune.wgpw_r > WG_PW_REPLICAS ? WG_PW_REPLICAS : g_tune.wgpw_r;
+  // block partials in front of the tail (tuning key wgrad_pw, bit 1) where the workspace holds one per block; else replicas + tickets (nothing pending)
+  const long long nel = (long long)d->Cout * d->C;
+  // (a call that reduces right away keeps the replicas unless bit 2 is set: one block walking 256 partials of a 2 KB dW - the stem's - takes 10 us longer than the tickets)
+  const bool slab = (g_tune.wgrad_pw & 2) && (d->defer || (g_tune.wgrad_pw & 4)) && (long long)grid * nel * 4 <= (long long)d->workspace_bytes - WG_PW_TAIL;
+  k.slabs = slab ? (float*)d->workspace : nullptr;
+  constexpr int lds[4] = {wgrad_pw_smem<1, 1>(), wgrad_pw_smem<1, 2>(), wgrad_pw_smem<2, 1>(), wgrad_pw_smem<2, 2>()};
+  const int form = (nco - 1) * 2 + (nci - 1);
+  wgrad_plan_grid(L, WG_PW11 + form, grid, 1, 1024, lds[form], 16);      // (bit 16: only a group of nothing but wgrad_pw members shares grids)
+  if (slab) wgrad_plan_pending(L, 2, (int)grid, nel, k.slabs, d->dw, 0);
+}
+
+// rua_wgrad_kind() == 2
+static void wgrad_plan_dmap(const rua_wgrad_desc* d, WgLaunch* L) {
+  WgdK& k = L->k.d;
+  k.a = (const unsigned char*)d->a; k.dy = (const unsigned char*)d->dy; k.dw = d->dw;
+  k.C = d->C; k.Cout = d->Cout; k.H = d->H; k.W = d->W; k.dil = d->dil; k.taps = d->taps;
+  k.M = (long long)d->N * d->H * d->W;
+  int wsh = 0; while ((1 << wsh) < d->W) ++wsh;
+  k.wsh = wsh;
+  k.ntc = d->Cout / 128; k.nti = d->C / 128;
+  const long long tiles = (long long)k.ntc * k.nti * d->taps;
+  const int stages = (int)((k.M + 63) / 64);
+  const int target = g_tune.wgd_blocks > 0 ? g_tune.wgd_blocks : rua_cu_count();
+  long long want = target / tiles; if (want < 1) want = 1;
+  if (want > stages / 4) want = stages / 4;             // >= 4 stages per K slice
+  if (want < 1) want = 1;
+  const long long ndw = (long long)d->taps * d->Cout * d->C;
+  const int cap = g_tune.wgrad_slabs ? slab_capacity(d, ndw) : 0;
+  if (cap >= 2 && want > cap) want = cap;               // deterministic K split: one fp32 slab per slice must fit the workspace
+  k.stages_per_split = (int)((stages + want - 1) / want);
+  k.ksplit = (stages + k.stages_per_split - 1) / k.stages_per_split;
+  k.slabs = (cap >= 2 && k.ksplit > 1) ? (float*)d->workspace : nullptr;
+  k.abytes = (unsigned)((size_t)k.M * d->C * 2); k.dybytes = (unsigned)((size_t)k.M * d->Cout * 2);
+  k.ks_slow = g_tune.wgd_ks_slow;
+  wgrad_plan_grid(L, WG_DMAP, (unsigned)(tiles * k.ksplit), 1, 256, 96 * 1024, 8);
+  if (k.slabs) wgrad_plan_pending(L, 2, k.ksplit, ndw, k.slabs, d->dw, 0);
+}
+
+// The plan of one weight gradient.  want: K slices a batched launch asks this member to take (wgrad_batch_split; only the generic tile kernel listens), 0: its own split.
+static int wgrad_plan_one(const rua_wgrad_desc* d, long long want_hint, WgLaunch* L) {
+  memset(L, 0, sizeof(*L));
   RUA_CHECK_ARG(d && d->a && d->dy && d->dw, "rua_conv_wgrad: null pointer");
   RUA_CHECK_ARG(d->dtype == RUA_F32 || d->dtype == RUA_BF16, "rua_conv_wgrad: bad dtype");
   const int vec = d->dtype == RUA_BF16 ? 8 : 4;
   RUA_CHECK_ARG(d->C % vec == 0 && d->Cout % vec == 0, "rua_conv_wgrad: C=%d Cout=%d must be multiples of %d", d->C, d->Cout, vec);
   RUA_CHECK_ARG(d->taps == 1 || d->taps == 9, "rua_conv_wgrad: taps must be 1 or 9");
-  if (rua_wgrad_kind(d) == 1) return launch_wgrad_taps(d, (hipStream_t)stream);
+  L->defer = d->defer != 0;
+  const int kind = rua_wgrad_kind(d);
+  if (kind == 1) { wgrad_plan_taps(d, L); return RUA_OK; }
   RUA_CHECK_ARG(d->in_scale == nullptr, "rua_conv_wgrad: in_scale / in_shift (normalise on load) needs the all-taps kernel (rua_wgrad_kind() == 1)");
-  if (rua_wgrad_kind(d) == 2) return launch_wgrad_dmap(d, (hipStream_t)stream);
-  if (rua_wgrad_kind(d) == 3) return launch_wgrad_pw(d, (hipStream_t)stream);
+  if (kind == 2) { wgrad_plan_dmap(d, L); return RUA_OK; }
+  if (kind == 3) { wgrad_plan_pw(d, L); return RUA_OK; }
   RUA_CHECK_ARG((long long)(d->H - 1) * d->stride < d->Hs && (long long)(d->W - 1) * d->stride < d->Ws,
                 "rua_conv_wgrad: input %dx%d too small for gradient %dx%d stride %d", d->Hs, d->Ws, d->H, d->W, d->stride);
-  WgK k;
+  WgK& k = L->k.g;
   k.a = (const unsigned char*)d->a; k.dy = (const unsigned char*)d->dy; k.dw = d->dw; k.overwrite = d->overwrite_dev;
   k.C = d->C; k.Hs = d->Hs; k.Ws = d->Ws; k.Cout = d->Cout; k.H = d->H; k.W = d->W; k.N = d->N;
   k.stride = d->stride; k.dil = d->dil; k.taps = d->taps;
@@ -2079,47 +1992,23 @@ extern "C" int rua_conv_wgrad(const rua_wgrad_desc* d, void* stream) {
   k.wshift = lg2(d->W); k.hshift = lg2(d->H);
   if (k.wshift < 0 || k.hshift < 0) k.wshift = k.hshift = -1;
   k.ntc = (d->Cout + 63) / 64; k.nti = (d->C + 63) / 64;
+  const long long ndw = (long long)d->taps * d->Cout * d->C;
   const int img_kind = wgrad_img_pick(d);
-  if (img_kind) {
-    // wgrad_img: whole images resident in LDS, a 64 x 64 tile of dW for all nine taps per block, 512-pixel chunks as K slices
-    hipStream_t st_ = (hipStream_t)stream;
-    const long long ndw_ = (long long)9 * d->Cout * d->C;
-    if (img_kind == 2) {
-      // wgrad_imgs: 32 x 32 tiles, the chunks streamed through a two-stage ring - no K slices, no slabs
-      if (g_wgrad_dry) return RUA_OK;
-      k.ksplit = (int)(k.M / 512); k.pix_per_block = 512; k.slabs = nullptr;
-      k.nti = d->C / 32; k.ntc = d->Cout / 32;
-      constexpr int smems_ = 4 * 9 * 16 * 64 * 4;             // the ring (2 x 67 840 B) and, after it, the four k-quarters' accumulators (147 456 B)
-      static RuaPerDevFlag attrs_;
-      bool& attrs = attrs_.get();
-      if (!attrs) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_imgs<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_imgs<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attrs = true;
-      }
-      if (d->W == 8) hipLaunchKernelGGL(wgrad_imgs<8>, dim3((unsigned)(k.nti * k.ntc)), dim3(768), smems_, st_, k);
-      else hipLaunchKernelGGL(wgrad_imgs<16>, dim3((unsigned)(k.nti * k.ntc)), dim3(768), smems_, st_, k);
-      RUA_LAUNCH_CHECK("wgrad_imgs");
-      return RUA_OK;
-    }
+  if (img_kind == 2) {
+    // wgrad_imgs: whole images resident in LDS, 32 x 32 tiles of dW for all nine taps, the 512-pixel chunks streamed through a two-stage ring - no K slices, no slabs
+    k.ksplit = (int)(k.M / 512); k.pix_per_block = 512; k.slabs = nullptr;
+    k.nti = d->C / 32; k.ntc = d->Cout / 32;
+    // LDS: the ring (2 x 67 840 B) and, after it, the four k-quarters' accumulators (147 456 B)
+    wgrad_plan_grid(L, d->W == 8 ? WG_IMGS8 : WG_IMGS16, (unsigned)(k.nti * k.ntc), 1, 768, 4 * 9 * 16 * 64 * 4, 0);
+    return RUA_OK;
+  }
+  if (img_kind == 1) {
+    // wgrad_img: a 64 x 64 tile of dW for all nine taps per block, 512-pixel chunks as K slices
     k.ksplit = (int)(k.M / 512);
     k.pix_per_block = 512;
     k.slabs = k.ksplit > 1 ? (float*)d->workspace : nullptr;
-    if (k.slabs) note_pending(2, k.ksplit, ndw_, k.slabs, d->dw, 0, (int)((ndw_ / 4 + SLAB_RED_COLS - 1) / SLAB_RED_COLS));
-    if (g_wgrad_dry) return RUA_OK;
-    const unsigned grid_ = (unsigned)(k.ntc * k.nti * k.ksplit);
-    constexpr int smem_ = 2 * 512 * 128 + 2 * 18 * 128;
-    static RuaPerDevFlag attr_;
-    bool& attr = attr_.get();
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_img<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_img<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr = true;
-    }
-    if (d->W == 8) hipLaunchKernelGGL(wgrad_img<8>, dim3(grid_), dim3(768), smem_, st_, k);
-    else hipLaunchKernelGGL(wgrad_img<16>, dim3(grid_), dim3(768), smem_, st_, k);
-    RUA_LAUNCH_CHECK("wgrad_img");
-    if (k.slabs && !d->defer) { rua_record_mid_event(st_); return launch_slab_reduce(k.slabs, d->dw, ndw_, k.ksplit, st_); }
+    wgrad_plan_grid(L, d->W == 8 ? WG_IMG8 : WG_IMG16, (unsigned)(k.ntc * k.nti * k.ksplit), 1, 768, 2 * 512 * 128 + 2 * 18 * 128, 0);
+    if (k.slabs) wgrad_plan_pending(L, 2, k.ksplit, ndw, k.slabs, d->dw, 0);
     return RUA_OK;
   }
   const long long tiles = (long long)k.ntc * k.nti * d->taps;
@@ -2128,9 +2017,8 @@ extern "C" int rua_conv_wgrad(const rua_wgrad_desc* d, void* stream) {
   const int target = (g_tune.wgrad_blocks > 0 ? g_tune.wgrad_blocks : 2 * rua_cu_count());      // 512 on MI355X
   long long want = target / tiles; if (want < 1) want = 1;
   long long stages = (k.M + 63) / 64;
-  if (g_wg_batch && g_wg_batch->want > 0) want = g_wg_batch->want;      // a member of a batched launch: its share of the batch's blocks (wgrad_batch_split)
+  if (want_hint > 0) want = want_hint;                 // a member of a batched launch: its share of the batch's blocks
   if (want > stages) want = stages;
-  const long long ndw = (long long)d->taps * d->Cout * d->C;
   const int cap = (g_tune.wgrad_slabs && ndw % 4 == 0) ? slab_capacity(d, ndw) : 0;
   if (cap >= 2 && want > cap) want = cap;              // deterministic K split: one fp32 slab per slice must fit the workspace
   long long spb = (stages + want - 1) / want;          // stages per block
@@ -2139,28 +2027,93 @@ extern "C" int rua_conv_wgrad(const rua_wgrad_desc* d, void* stream) {
   k.slabs = (cap >= 2 && k.ksplit > 1) ? (float*)d->workspace : nullptr;
   const long long grid = tiles * k.ksplit;
   RUA_CHECK_ARG(grid < (1ll << 31), "rua_conv_wgrad: grid too large");
-  hipStream_t st = (hipStream_t)stream;
-  if (k.slabs) note_pending(2, k.ksplit, ndw, k.slabs, d->dw, 0, (int)((ndw / 4 + SLAB_RED_COLS - 1) / SLAB_RED_COLS));
-  if (g_wgrad_dry) return RUA_OK;
-  if (g_wg_batch) { g_wg_batch->k = k; g_wg_batch->grid = (unsigned)grid; g_wg_batch->ndw = ndw; return RUA_OK; }      // issued by wgrad_batch_launch
-  if (g_wg_group && (g_tune.wgrad_group & 1) && g_wg_group->n < RUA_MAX_WGRAD_GROUP && d->dtype == RUA_BF16) {
-    WgGroupCapture& c = *g_wg_group; const int i = c.n++;
-    c.kind[i] = 0; c.gx[i] = (unsigned)grid; c.smem[i] = 0; c.g[i] = k;
-    c.post[i] = (k.slabs && !d->defer) ? 2 : 0; c.part[i] = k.slabs; c.dw[i] = d->dw; c.ndw[i] = ndw; c.parts[i] = k.ksplit; c.CC[i] = 0; c.rblocks[i] = 0;
-    return RUA_OK;
-  }
-  if (d->dtype == RUA_BF16) hipLaunchKernelGGL((wgrad_kernel<bf16_t>), dim3((unsigned)grid), dim3(256), 0, st, k);
-  else hipLaunchKernelGGL((wgrad_kernel<float>), dim3((unsigned)grid), dim3(256), 0, st, k);
-  RUA_LAUNCH_CHECK("wgrad_kernel");
-  if (k.slabs && !d->defer) { rua_record_mid_event(st); return launch_slab_reduce(k.slabs, d->dw, ndw, k.ksplit, st); }
+  wgrad_plan_grid(L, d->dtype == RUA_BF16 ? WG_TILES_BF16 : WG_TILES_F32, (unsigned)grid, 1, 256, 0, d->dtype == RUA_BF16 ? 1 : 0);
+  if (k.slabs) wgrad_plan_pending(L, 2, k.ksplit, ndw, k.slabs, d->dw, 0);
   return RUA_OK;
+}
+// plan + the record the call leaves for rua_wgrad_reduce_batch
+static int wgrad_plan_record(const rua_wgrad_desc* d, long long want, WgLaunch* L, rua_wgrad_pending* out) {
+  const int rc = wgrad_plan_one(d, want, L);
+  *out = L->pending;
+  out->overwrite_dev = d->overwrite_dev;
+  return rc;
+}
+
+// ---- issuing -----------------------------------------------------------------------------------------------------------
+// One grid for m >= 1 plans of the SAME kernel.  One plan: the kernel itself.  Several: its grouped form - blockIdx.y picks the member (blockIdx.z in the all-taps
+// family, whose grid.y is the output-channel slice); the grid and the LDS are the largest member's, the others' surplus blocks leave at once.  always_grouped: the
+// grouped form for a single member too (the wgrad_pw forms of an all-wgrad_pw group, as they always went out).
+static int wgrad_issue(const WgLaunch* const* L, int m, hipStream_t st, bool always_grouped = false) {
+  const WgLaunch& first = *L[0];
+  const WgKernelRow& row = WG_KERNEL[first.kernel];
+  const bool grouped = m > 1 || always_grouped;
+  const void* fn = grouped ? row.many : row.one;
+  const int slots = row.args == WG_ARGS_P ? RUA_MAX_BRANCH : RUA_MAX_WGRAD_GROUP;
+  RUA_CHECK_ARG(fn && m <= slots, "rua_conv_wgrad_group: %d members of %s in one grid", m, row.name);
+  static RuaPerDevFlag allowed[WG_KERNELS][2];        // hipFuncSetAttribute: once per (kernel, device)
+  bool& ok = allowed[first.kernel][grouped].get();
+  if (!ok && row.lds) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, row.lds);
+  ok = true;
+  dim3 grid(first.gx, first.gy);
+  int smem = first.smem;
+  union { WgKG g; WgdKG d; WgtKG t; WgpKG p; } many;
+  void* args[1] = {const_cast<void*>(static_cast<const void*>(&first.k))};
+  if (grouped) {
+    for (int i = 0; i < slots; ++i) {                  // (unused slots repeat member 0)
+      const WgLaunch& x = *L[i < m ? i : 0];
+      if (x.gx > grid.x) grid.x = x.gx;
+      if (x.smem > smem) smem = x.smem;
+      switch (row.args) {
+        case WG_ARGS_K: many.g.k[i] = x.k.g; break;
+        case WG_ARGS_D: many.d.k[i] = x.k.d; break;
+        case WG_ARGS_T: many.t.k[i] = x.k.t; break;
+        default: many.p.k[i] = x.k.p; break;
+      }
+    }
+    if (first.kernel == WG_DMAP) grid.x = (grid.x + 7) / 8 * 8;
+    if (row.args == WG_ARGS_T) grid.z = m; else grid.y = m;
+    args[0] = &many;
+  }
+  (void)hipLaunchKernel(fn, grid, dim3(first.block), args, (size_t)smem, st);
+  RUA_LAUNCH_CHECK(row.name);
+  return RUA_OK;
+}
+// the reduction a plan leaves pending, as a launch of its own (deferred ones go through rua_wgrad_reduce_batch instead)
+static int wgrad_reduce(const rua_wgrad_pending& r, hipStream_t st) {
+  if (r.kind == 1) {
+    hipLaunchKernelGGL(wgrad_taps_reduce, dim3(r.blocks), dim3(256), 0, st, r.partials, r.dw, r.CC, r.parts);
+    RUA_LAUNCH_CHECK("wgrad_taps_reduce");
+  } else if (r.kind == 2) {
+    hipLaunchKernelGGL(wgrad_slab_reduce, dim3(r.blocks), dim3(256), 0, st, r.partials, r.dw, r.n / 4, r.parts);
+    RUA_LAUNCH_CHECK("wgrad_slab_reduce");
+  }
+  return RUA_OK;
+}
+// a plan on its own: its grid, then - unless deferred - the mid event and its reduction
+static int wgrad_issue_alone(const WgLaunch& L, hipStream_t st) {
+  const WgLaunch* one = &L;
+  const int rc = wgrad_issue(&one, 1, st);
+  if (rc != RUA_OK || L.defer || !L.pending.kind) return rc;
+  rua_record_mid_event(st);
+  return wgrad_reduce(L.pending, st);
+}
+
+// ---- exports -----------------------------------------------------------------------------------------------------------
+extern "C" int rua_wgrad_plan(const rua_wgrad_desc* d, rua_wgrad_pending* out) {
+  RUA_CHECK_ARG(d && out, "rua_wgrad_plan: null pointer");
+  WgLaunch L;
+  return wgrad_plan_record(d, 0, &L, out);
+}
+extern "C" int rua_conv_wgrad(const rua_wgrad_desc* d, void* stream) {
+  WgLaunch L;
+  const int rc = wgrad_plan_one(d, 0, &L);
+  return rc != RUA_OK ? rc : wgrad_issue_alone(L, (hipStream_t)stream);
 }
 
 // rua_conv_wgrad_group: n INDEPENDENT weight gradients (the dilation branches of a ResBlock) with the results of n rua_conv_wgrad
-// calls.  Members that land on the same kernel go out as ONE grid (blockIdx.y / .z = member; the grid is the largest member's,
-// the others' surplus blocks leave at once), the rest one by one.  Members that share partial-sum workspace cannot overlap:
-// such a group runs member by member.
-static thread_local int g_wg_group_last_grids = 0;
+// calls.  Members that land on the same kernel go out as ONE grid, the rest one by one.  Members that share partial-sum workspace
+// cannot overlap: such a group runs member by member.
+static thread_local int g_wg_group_last_grids = 0;     // per calling thread: rua_hip.h promises the count of the thread's own latest call
 extern "C" int rua_wgrad_group_last_grids(void) { return g_wg_group_last_grids; }
 
 // The batched form: every member lands on the generic bf16 tile kernel (rua_wgrad_kind() == 0, no whole-image kernel) and asks for it
@@ -2179,7 +2132,7 @@ static bool wgrad_batch_ok(const rua_wgrad_desc* d, int n) {
 }
 // One block budget for the members [0, n) of ONE grid, dealt by work (a pure function of the descriptors): a member's work is stages x tiles (64-pixel stages of
 // its K range, 64 x 64 tiles of its dW), and it gets that share of the budget as blocks - so every block of the grid runs about work / budget stages, whichever
-// member it belongs to.  want[i] = K slices asked for (rua_conv_wgrad bounds it by the member's stages and slab capacity); 0: the split it would take alone
+// member it belongs to.  want[i] = K slices asked for (wgrad_plan_one bounds it by the member's stages and slab capacity); 0: the split it would take alone
 // (bit 5 of wgrad_group: the batch is then bit-identical to the single launches).
 static void wgrad_batch_split(const rua_wgrad_desc* d, int n, long long* want) {
   long long work = 0;
@@ -2192,38 +2145,55 @@ static void wgrad_batch_split(const rua_wgrad_desc* d, int n, long long* want) {
     want[i] = (g_tune.wgrad_group & 32) ? 0 : (w < 1 ? 1 : w);
   }
 }
-// geometry of the members of one grid: kernel arguments, grid and (through g_wgrad_pending, one record per member) the partials each leaves
-static int wgrad_batch_members(const rua_wgrad_desc* d, int n, WgBatchMember* mem, rua_wgrad_pending* recs, bool dry) {
-  long long want[RUA_MAX_WGRAD_BATCH];
-  wgrad_batch_split(d, n, want);
-  int rc = RUA_OK;
-  for (int i = 0; i < n && rc == RUA_OK; ++i) {
-    mem[i].want = want[i]; mem[i].grid = 0;
-    if (recs) { memset(recs + i, 0, sizeof(*recs)); g_wgrad_pending = recs + i; }
-    g_wg_batch = mem + i; g_wgrad_dry = dry;
-    rc = rua_conv_wgrad(d + i, nullptr);
-    g_wg_batch = nullptr; g_wgrad_dry = false; g_wgrad_pending = nullptr;
-    if (recs) recs[i].overwrite_dev = d[i].overwrite_dev;
+// the plans and records of a batched call (wgrad_batch_ok): consecutive runs of RUA_MAX_WGRAD_BATCH members share a grid and its block budget
+static int wgrad_batch_plan(const rua_wgrad_desc* d, int n, WgLaunch* L, rua_wgrad_pending* out) {
+  for (int base = 0; base < n; base += RUA_MAX_WGRAD_BATCH) {
+    const int m = n - base < RUA_MAX_WGRAD_BATCH ? n - base : RUA_MAX_WGRAD_BATCH;
+    long long want[RUA_MAX_WGRAD_BATCH];
+    wgrad_batch_split(d + base, m, want);
+    for (int i = base; i < base + m; ++i) { const int rc = wgrad_plan_record(d + i, want[i - base], L + i, out + i); if (rc != RUA_OK) return rc; }
   }
-  return rc;
+  return RUA_OK;
+}
+extern "C" int rua_wgrad_group_plan(const rua_wgrad_desc* d, int n, rua_wgrad_pending* out) {
+  RUA_CHECK_ARG(d && out && n >= 1, "rua_wgrad_group_plan: bad arguments");
+  WgLaunch L[WG_BATCH_MAX_MEMBERS];
+  if (wgrad_batch_ok(d, n)) return wgrad_batch_plan(d, n, L, out);
+  for (int i = 0; i < n; ++i) { const int rc = wgrad_plan_record(d + i, 0, L, out + i); if (rc != RUA_OK) return rc; }
+  return RUA_OK;
 }
 static int wgrad_batch_launch(const rua_wgrad_desc* d, int n, hipStream_t st) {
+  WgLaunch L[WG_BATCH_MAX_MEMBERS];
+  rua_wgrad_pending recs[WG_BATCH_MAX_MEMBERS];
+  const int rp = wgrad_batch_plan(d, n, L, recs);
+  if (rp != RUA_OK) return rp;
+  // members whose slabs overlap (a shared workspace) cannot run at once: member by member, as any group that shares workspace
+  bool overlap = false;
+  for (int i = 0; i < n && !overlap; ++i)
+    for (int j = i + 1; j < n && !overlap; ++j) {
+      if (recs[i].kind != 2 || recs[j].kind != 2) continue;
+      const float* a0 = recs[i].partials; const float* b0 = recs[j].partials;
+      overlap = a0 < b0 + (long long)recs[j].parts * recs[j].n && b0 < a0 + (long long)recs[i].parts * recs[i].n;
+    }
+  if (overlap) {
+    g_wg_group_last_grids = n;
+    for (int i = 0; i < n; ++i) { const int rc = rua_conv_wgrad(d + i, st); if (rc != RUA_OK) return rc; }
+    return RUA_OK;
+  }
   int grids = 0;
   for (int base = 0; base < n; base += RUA_MAX_WGRAD_BATCH) {
     const int m = n - base < RUA_MAX_WGRAD_BATCH ? n - base : RUA_MAX_WGRAD_BATCH;
-    WgBatchMember mem[RUA_MAX_WGRAD_BATCH];
-    const int rc = wgrad_batch_members(d + base, m, mem, nullptr, false);
-    if (rc != RUA_OK) return rc;
+    const WgLaunch* mem = L + base;
     int order[RUA_MAX_WGRAD_BATCH];
     for (int i = 0; i < m; ++i) order[i] = i;
     for (int i = 1; i < m; ++i) {                          // longest blocks first (stable: equal members keep the caller's order)
       const int o = order[i]; int j = i;
-      while (j > 0 && mem[order[j - 1]].k.pix_per_block < mem[o].k.pix_per_block) { order[j] = order[j - 1]; --j; }
+      while (j > 0 && mem[order[j - 1]].k.g.pix_per_block < mem[o].k.g.pix_per_block) { order[j] = order[j - 1]; --j; }
       order[j] = o;
     }
     WgKB g;
     unsigned long long total = 0;
-    for (int i = 0; i < m; ++i) { g.k[i] = mem[order[i]].k; total += mem[order[i]].grid; g.end[i] = (unsigned)total; }
+    for (int i = 0; i < m; ++i) { g.k[i] = mem[order[i]].k.g; total += mem[order[i]].gx; g.end[i] = (unsigned)total; }
     for (int i = m; i < RUA_MAX_WGRAD_BATCH; ++i) { g.k[i] = g.k[0]; g.end[i] = (unsigned)total; }
     g.n = m;
     RUA_CHECK_ARG(total >= 1 && total < (1ull << 31), "rua_conv_wgrad_group: grid too large");
@@ -2231,168 +2201,64 @@ static int wgrad_batch_launch(const rua_wgrad_desc* d, int n, hipStream_t st) {
     RUA_LAUNCH_CHECK("wgrad_kernel_b");
     ++grids;
     for (int i = 0; i < m; ++i)                            // members that did not defer their reduction
-      if (mem[i].k.slabs && !d[base + i].defer) { const int rr = launch_slab_reduce(mem[i].k.slabs, mem[i].k.dw, mem[i].ndw, mem[i].k.ksplit, st); if (rr != RUA_OK) return rr; }
+      if (!mem[i].defer) { const int rr = wgrad_reduce(mem[i].pending, st); if (rr != RUA_OK) return rr; }
   }
   g_wg_group_last_grids = grids;
-  return RUA_OK;
-}
-extern "C" int rua_wgrad_group_plan(const rua_wgrad_desc* d, int n, rua_wgrad_pending* out) {
-  RUA_CHECK_ARG(d && out && n >= 1, "rua_wgrad_group_plan: bad arguments");
-  if (!wgrad_batch_ok(d, n)) {
-    for (int i = 0; i < n; ++i) { const int rc = rua_wgrad_plan(d + i, out + i); if (rc != RUA_OK) return rc; }
-    return RUA_OK;
-  }
-  for (int base = 0; base < n; base += RUA_MAX_WGRAD_BATCH) {
-    const int m = n - base < RUA_MAX_WGRAD_BATCH ? n - base : RUA_MAX_WGRAD_BATCH;
-    WgBatchMember mem[RUA_MAX_WGRAD_BATCH];
-    const int rc = wgrad_batch_members(d + base, m, mem, out + base, true);
-    if (rc != RUA_OK) return rc;
-  }
   return RUA_OK;
 }
 extern "C" int rua_conv_wgrad_group(const rua_wgrad_desc* d, int n, void* stream) {
   RUA_CHECK_ARG(d && n >= 1, "rua_conv_wgrad_group: no members");
   hipStream_t st = (hipStream_t)stream;
-  if (wgrad_batch_ok(d, n)) {
-    // members whose slabs overlap (a shared workspace) cannot run at once: member by member, as any group that shares workspace
-    static thread_local rua_wgrad_pending recs[WG_BATCH_MAX_MEMBERS];
-    const int rp = rua_wgrad_group_plan(d, n, recs);
-    if (rp != RUA_OK) return rp;
-    bool overlap = false;
-    for (int i = 0; i < n && !overlap; ++i)
-      for (int j = i + 1; j < n && !overlap; ++j) {
-        if (recs[i].kind != 2 || recs[j].kind != 2) continue;
-        const float* a0 = recs[i].partials; const float* b0 = recs[j].partials;
-        overlap = a0 < b0 + (long long)recs[j].parts * recs[j].n && b0 < a0 + (long long)recs[i].parts * recs[i].n;
-      }
-    if (!overlap) return wgrad_batch_launch(d, n, st);
-    g_wg_group_last_grids = n;
-    for (int i = 0; i < n; ++i) { const int rc = rua_conv_wgrad(d + i, stream); if (rc != RUA_OK) return rc; }
-    return RUA_OK;
-  }
+  if (wgrad_batch_ok(d, n)) return wgrad_batch_launch(d, n, st);
   RUA_CHECK_ARG(n <= RUA_MAX_WGRAD_GROUP, "rua_conv_wgrad_group: 1..%d members (more only in the batched form)", RUA_MAX_WGRAD_GROUP);
-  bool shared = false;
-  for (int i = 0; i < n; ++i)
+  WgLaunch L[RUA_MAX_WGRAD_GROUP];
+  for (int i = 0; i < n; ++i) { const int rc = wgrad_plan_one(d + i, 0, L + i); if (rc != RUA_OK) return rc; }
+  // which members go into shared grids
+  bool shared = false;                                 // partial-sum workspace or dw in common: one by one
+  bool allpw = n >= 2;                                 // nothing but wgrad_pw members with replicas / tickets (the workspace tails) of their own: one grid per (NCO, NCI) form
+  for (int i = 0; i < n; ++i) {
+    allpw = allpw && WG_KERNEL[L[i].kernel].args == WG_ARGS_P && L[i].groupable;
     for (int j = i + 1; j < n; ++j) {
       const char* a0 = (const char*)d[i].workspace; const char* b0 = (const char*)d[j].workspace;
       if (a0 && b0 && a0 < b0 + d[j].workspace_bytes && b0 < a0 + d[i].workspace_bytes) shared = true;
       if (d[i].dw == d[j].dw) shared = true;
     }
-  g_wg_group_last_grids = n;
-  {
-    // all members narrow 1x1 weight gradients (wgrad_pw) with replicas / tickets of their own: one grid per (NCO, NCI) form
-    bool allpw = n >= 2 && (g_tune.wgrad_group & 16);
-    for (int i = 0; i < n && allpw; ++i) allpw = rua_wgrad_kind(d + i) == 3;
-    for (int i = 0; i < n && allpw; ++i)
-      for (int j = i + 1; j < n; ++j) {
-        const char* ti = (const char*)d[i].workspace + d[i].workspace_bytes - WG_PW_TAIL; const char* tj = (const char*)d[j].workspace + d[j].workspace_bytes - WG_PW_TAIL;
-        if (ti < tj + WG_PW_TAIL && tj < ti + WG_PW_TAIL) allpw = false;        // shared replicas: one by one
-        if (d[i].dw == d[j].dw) allpw = false;
-      }
-    if (allpw) {
-      WgPwCapture cap;
-      cap.n = 0;
-      g_wg_pw = &cap;
-      int rc = RUA_OK;
-      for (int i = 0; i < n && rc == RUA_OK; ++i) rc = rua_conv_wgrad(d + i, stream);
-      g_wg_pw = nullptr;
-      if (rc != RUA_OK) return rc;
-      int grids = n - cap.n;
-      constexpr int s11 = wgrad_pw_smem<1, 1>(), s21 = wgrad_pw_smem<2, 1>(), s12 = wgrad_pw_smem<1, 2>(), s22 = wgrad_pw_smem<2, 2>();
-      static RuaPerDevFlag attr_;
-      if (!attr_.get()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pw_g<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, s21);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pw_g<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, s12);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pw_g<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, s22);
-        attr_.get() = true;
-      }
-      for (int form = 0; form < 4; ++form) {
-        WgpKG g; int m = 0; unsigned gx = 0;
-        for (int i = 0; i < cap.n; ++i) if (cap.form[i] == form) { g.k[m++] = cap.k[i]; if ((unsigned)cap.k[i].nblk > gx) gx = (unsigned)cap.k[i].nblk; }
-        if (m == 0) continue;
-        for (int i = m; i < RUA_MAX_BRANCH; ++i) g.k[i] = g.k[0];
-        if (form == 0) hipLaunchKernelGGL((wgrad_pw_g<1, 1>), dim3(gx, m), dim3(1024), s11, st, g);
-        else if (form == 1) hipLaunchKernelGGL((wgrad_pw_g<1, 2>), dim3(gx, m), dim3(1024), s12, st, g);
-        else if (form == 2) hipLaunchKernelGGL((wgrad_pw_g<2, 1>), dim3(gx, m), dim3(1024), s21, st, g);
-        else hipLaunchKernelGGL((wgrad_pw_g<2, 2>), dim3(gx, m), dim3(1024), s22, st, g);
-        RUA_LAUNCH_CHECK("wgrad_pw (group)");
-        ++grids;
-      }
-      g_wg_group_last_grids = grids;
-      for (int i = 0; i < cap.n; ++i)
-        if (cap.post[i]) { rc = launch_slab_reduce(cap.k[i].slabs, cap.k[i].dw, (long long)cap.k[i].Cout * cap.k[i].C, cap.k[i].nblk, st); if (rc != RUA_OK) return rc; }
-      return RUA_OK;
+  }
+  for (int i = 0; i < n && allpw; ++i)
+    for (int j = i + 1; j < n; ++j) {
+      const char* ti = (const char*)d[i].workspace + d[i].workspace_bytes - WG_PW_TAIL; const char* tj = (const char*)d[j].workspace + d[j].workspace_bytes - WG_PW_TAIL;
+      if ((ti < tj + WG_PW_TAIL && tj < ti + WG_PW_TAIL) || d[i].dw == d[j].dw) allpw = false;
     }
+  bool grouped[RUA_MAX_WGRAD_GROUP];
+  for (int i = 0; i < n; ++i) {
+    if (allpw) grouped[i] = i < RUA_MAX_BRANCH;                                    // (the slots of wgrad_pw_g)
+    else grouped[i] = n > 1 && !shared && L[i].groupable && WG_KERNEL[L[i].kernel].args != WG_ARGS_P;
   }
-  if (n == 1 || shared || !g_tune.wgrad_group) {
-    for (int i = 0; i < n; ++i) { const int rc = rua_conv_wgrad(d + i, stream); if (rc != RUA_OK) return rc; }
-    return RUA_OK;
-  }
-  WgGroupCapture cap;
-  cap.n = 0;
-  g_wg_group = &cap;
-  int rc = RUA_OK;
-  for (int i = 0; i < n && rc == RUA_OK; ++i) rc = rua_conv_wgrad(d + i, stream);      // members no launcher captures launch right here
-  g_wg_group = nullptr;
-  if (rc != RUA_OK) return rc;
-  int grids = n - cap.n;
+  // the others first, in member order, each followed at once by its own reduction
+  int grids = 0;
+  for (int i = 0; i < n; ++i)
+    if (!grouped[i]) { const int rc = wgrad_issue_alone(L[i], st); if (rc != RUA_OK) return rc; ++grids; }
+  // then one grid per kernel: in order of first appearance (the wgrad_pw forms: in order of the form)
   bool done[RUA_MAX_WGRAD_GROUP] = {false};
-  for (int i = 0; i < cap.n; ++i) {
-    if (done[i]) continue;
-    int idx[RUA_MAX_WGRAD_GROUP], m = 0; unsigned gx = 0; int smem = 0;
-    for (int j = i; j < cap.n; ++j)
-      if (!done[j] && cap.kind[j] == cap.kind[i]) { idx[m++] = j; done[j] = true; if (cap.gx[j] > gx) gx = cap.gx[j]; if (cap.smem[j] > smem) smem = cap.smem[j]; }
-    static RuaPerDevFlag attrf[4];
-    bool* attr[4] = {&attrf[0].get(), &attrf[1].get(), &attrf[2].get(), &attrf[3].get()};
-    const int kd = cap.kind[i];
-    if (kd == 0) {
-      if (m == 1) hipLaunchKernelGGL((wgrad_kernel<bf16_t>), dim3(gx), dim3(256), 0, st, cap.g[idx[0]]);
-      else { WgKG g; for (int q = 0; q < m; ++q) g.k[q] = cap.g[idx[q]]; hipLaunchKernelGGL(wgrad_kernel_g, dim3(gx, m), dim3(256), 0, st, g); }
-    } else if (kd == 3) {
-      if (!*attr[3]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_dmap), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_dmap_g), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); *attr[3] = true;
-      }
-      if (m == 1) hipLaunchKernelGGL(wgrad_dmap, dim3(gx), dim3(256), smem, st, cap.d[idx[0]]);
-      else { WgdKG g; for (int q = 0; q < m; ++q) g.k[q] = cap.d[idx[q]]; hipLaunchKernelGGL(wgrad_dmap_g, dim3((gx + 7) / 8 * 8, m), dim3(256), smem, st, g); }
-    } else if (kd >= 4) {
-      WgtKG g; for (int q = 0; q < m; ++q) g.k[q] = cap.t[idx[q]];
-      const unsigned gyr = kd == 12 ? 8u : kd == 11 ? 2u : 1u;     // wgrad_rowsx: grid.y = output-channel slice (x input-channel half)
-      if (!(m == 1 ? launch_rows32(kd, false, dim3(gx, gyr), smem, st, &g.k[0], nullptr) : launch_rows32(kd, true, dim3(gx, gyr, m), smem, st, nullptr, &g))) return RUA_ERR_ARG;
-    } else {
-      const int gy = kd == 1 ? 1 : 2;
-      if (!*attr[kd]) {
-        if (kd == 1) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_taps_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_taps_kernel_g<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
-        else { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_taps_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-               (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_taps_kernel_g<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
-        *attr[kd] = true;
-      }
-      WgtKG g; for (int q = 0; q < m; ++q) g.k[q] = cap.t[idx[q]];
-      if (m == 1) { if (kd == 1) hipLaunchKernelGGL((wgrad_taps_kernel<32>), dim3(gx, gy), dim3(768), smem, st, g.k[0]);
-                    else hipLaunchKernelGGL((wgrad_taps_kernel<64>), dim3(gx, gy), dim3(768), smem, st, g.k[0]); }
-      else if (kd == 1) hipLaunchKernelGGL((wgrad_taps_kernel_g<32>), dim3(gx, gy, m), dim3(768), smem, st, g);
-      else hipLaunchKernelGGL((wgrad_taps_kernel_g<64>), dim3(gx, gy, m), dim3(768), smem, st, g);
-    }
-    RUA_LAUNCH_CHECK("rua_conv_wgrad_group");
+  auto issue_kernel = [&](int kernel) {                // (all of wgrad_pw: the grouped kernel even for a form with one member)
+    const WgLaunch* same[RUA_MAX_WGRAD_GROUP]; int m = 0;
+    for (int j = 0; j < n; ++j)
+      if (grouped[j] && !done[j] && L[j].kernel == kernel) { same[m++] = L + j; done[j] = true; }
+    if (m == 0) return (int)RUA_OK;
     ++grids;
+    return wgrad_issue(same, m, st, allpw);
+  };
+  if (allpw) {
+    for (int kernel = WG_PW11; kernel <= WG_PW22; ++kernel) { const int rc = issue_kernel(kernel); if (rc != RUA_OK) return rc; }
+  } else {
+    for (int i = 0; i < n; ++i)
+      if (grouped[i] && !done[i]) { const int rc = issue_kernel(L[i].kernel); if (rc != RUA_OK) return rc; }
   }
   g_wg_group_last_grids = grids;
-  for (int i = 0; i < cap.n; ++i) {                      // members that did not defer their reduction
-    if (cap.post[i] == 1) { hipLaunchKernelGGL(wgrad_taps_reduce, dim3(cap.rblocks[i]), dim3(256), 0, st, cap.part[i], cap.dw[i], cap.CC[i], cap.parts[i]); RUA_LAUNCH_CHECK("wgrad_taps_reduce"); }
-    else if (cap.post[i] == 2) { rc = launch_slab_reduce(cap.part[i], cap.dw[i], cap.ndw[i], cap.parts[i], st); if (rc != RUA_OK) return rc; }
-  }
+  // then the reductions of the grouped members that did not defer theirs, in member order
+  for (int i = 0; i < n; ++i)
+    if (grouped[i] && !L[i].defer) { const int rc = wgrad_reduce(L[i].pending, st); if (rc != RUA_OK) return rc; }
   return RUA_OK;
-}
-
-extern "C" int rua_wgrad_plan(const rua_wgrad_desc* d, rua_wgrad_pending* out) {
-  RUA_CHECK_ARG(d && out, "rua_wgrad_plan: null pointer");
-  memset(out, 0, sizeof(*out));
-  g_wgrad_pending = out; g_wgrad_dry = true;
-  const int rc = rua_conv_wgrad(d, nullptr);
-  g_wgrad_pending = nullptr; g_wgrad_dry = false;
-  out->overwrite_dev = d->overwrite_dev;
-  return rc;
 }
 
 // One launch for any number of pending weight-gradient reductions: block -> record by binary search over block_begin, then the

@@ -1595,6 +1595,71 @@ def test_wgrad_group_equals_separate_launches(shape):
         assert torch.equal(keep[3 * i + 2], sep[i]), ("shared", i, dils[i])
 
 
+def test_wgrad_group_of_mixed_kernels():
+    """rua_conv_wgrad_group over members that land on DIFFERENT kernels, each with a workspace and a dw of its own: two all-taps members (dilation 1 and 3) share
+    one grid, a generic member with K slabs takes a grid of its own behind them, a narrow 1x1 (wgrad_pw) and a whole-image member (wgrad_img) are launched at
+    once, in front - four grids.  Every dw is bit-identical to the member's own rua_conv_wgrad: no member adds with float atomics here (block partials, slabs, one
+    writer per element; wgrad_pw leaves slabs under wgrad_pw=7, set around both runs), with the reductions run by the call and deferred to rua_wgrad_reduce_batch."""
+    dt = L.RUA_BF16
+    lib = L.lib()
+    rng = np.random.default_rng(5)
+    members = [(2, 64, 32, 32, 9, 1), (2, 64, 32, 32, 9, 3), (3, 20, 24, 40, 9, 2), (2, 64, 32, 32, 1, 1), (8, 8, 64, 64, 9, 1)]      # N, H = W, C, Cout, taps, dilation
+    want_kind = [(1, 0), (1, 0), (0, 0), (3, 0), (0, 1)]                                                                                # rua_wgrad_kind, rua_wgrad_img_kind
+    keep, descs, dws = [], [], []
+    for N, H, Cs, Co, taps, dil in members:
+        a = to_dev(rng.standard_normal((N, H, H, Cs)).astype(np.float32), dt)
+        dy = to_dev(rng.standard_normal((N, H, H, Co)).astype(np.float32), dt)
+        d = L.WgradDesc()
+        d.a, d.C, d.Hs, d.Ws, d.dy, d.Cout, d.H, d.W = a.data_ptr(), Cs, H, H, dy.data_ptr(), Co, H, H
+        d.N, d.stride, d.dil, d.taps, d.dtype = N, 1, dil, taps, dt
+        ws = torch.zeros(lib.raw("rua_wgrad_workspace_bytes")(C.byref(d)) // 4 + 16, dtype=torch.float32, device=dev())
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+        dw = torch.zeros(taps * Co * Cs, dtype=torch.float32, device=dev())
+        d.dw = dw.data_ptr()
+        keep += [a, dy, ws]
+        descs.append(d)
+        dws.append(dw)
+    arr = (L.WgradDesc * len(descs))()
+    old = lib.get_tuning("wgrad_pw")
+    try:
+        lib.set_tuning(wgrad_pw=7)
+        assert [(lib.raw("rua_wgrad_kind")(C.byref(d)), lib.raw("rua_wgrad_img_kind")(C.byref(d))) for d in descs] == want_kind
+        sep = []
+        for d, dw in zip(descs, dws):
+            lib.call("rua_conv_wgrad", C.byref(d), stream())
+            torch.cuda.synchronize()
+            sep.append(dw.clone())
+            assert float(dw.abs().max()) > 0
+            dw.zero_()
+        for defer in (0, 1):
+            recs = []
+            for i, d in enumerate(descs):
+                d.defer = defer
+                C.memmove(C.byref(arr, i * C.sizeof(L.WgradDesc)), C.byref(d), C.sizeof(L.WgradDesc))
+                r = L.WgradPending()
+                lib.call("rua_wgrad_plan", C.byref(d), C.byref(r))
+                if r.kind != 0:
+                    recs.append(r)
+            assert len(recs) == 4                                  # the whole-image member leaves nothing to reduce
+            lib.call("rua_conv_wgrad_group", arr, len(descs), stream())
+            assert lib.raw("rua_wgrad_group_last_grids")() == 4
+            if defer:
+                table = (L.WgradPending * len(recs))()
+                blocks = 0
+                for i, r in enumerate(recs):
+                    r.block_begin = blocks
+                    blocks += r.blocks
+                    C.memmove(C.byref(table, i * C.sizeof(L.WgradPending)), C.byref(r), C.sizeof(L.WgradPending))
+                tdev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev())
+                lib.call("rua_wgrad_reduce_batch", tdev.data_ptr(), len(recs), blocks, stream())
+            torch.cuda.synchronize()
+            for i, dw in enumerate(dws):
+                assert torch.equal(dw, sep[i]), ("deferred" if defer else "own reductions", i, members[i])
+                dw.zero_()
+    finally:
+        lib.set_tuning(wgrad_pw=old)
+
+
 @pytest.mark.parametrize("N,H,W,dil,R", [(2, 256, 256, 1, 32), (1, 256, 256, 31, 8), (4, 128, 128, 3, 1), (1, 200, 512, 15, 16)])
 def test_conv_strip_folded_batchnorm_coefficients(N, H, W, dil, R):
     """rua_conv_desc.in_fold: the convolution derives the training-mode BatchNorm coefficients of its input from the replicated
