@@ -103,7 +103,9 @@ typedef struct rua_conv_desc {
 } rua_conv_desc;
 int rua_conv_fwd(const rua_conv_desc* d, void* stream);
 /* n (<= RUA_MAX_BRANCH) INDEPENDENT convolutions - the dilation branches of a ResBlock (model2.py:26-31) - with the results of n
- * rua_conv_fwd calls; members that land on the same kernel are issued as ONE grid (no drain / launch gap between the branches) */
+ * rua_conv_fwd calls; members that land on the same kernel are issued as ONE grid (no drain / launch gap between the branches).
+ * Every member is planned before anything is launched: a group with a rejected member returns its error, launches nothing and
+ * leaves nothing behind (the thread's ..._last_* values keep what the call before left). */
 int rua_conv_fwd_group(const rua_conv_desc* d, int n, void* stream);
 int rua_conv_group_last_grids(void);             /* grids the calling thread's latest rua_conv_fwd_group issued (1: all members in one) */
 /* C = Cout = 64, 3x3, bf16, W % 128 == 0, H % 4 == 0: the members run as ONE conv_band64m launch (row streaming, 4-row bands, every
@@ -141,6 +143,21 @@ int rua_conv_kernel_id(const rua_conv_desc* d); /* 0: conv_igemm (register-stage
                                                    5: conv_strip (row-streaming 3x3 at C = Cout = 32, BatchNorm + ReLU applied on load) */
 int rua_conv_fused_input_ok(const rua_conv_desc* d);   /* 1: this shape runs on a kernel that honours in_scale / in_shift / in_relu */
 int rua_conv_tile_bm(const rua_conv_desc* d);   /* 128 / 256: which conv_igemm<T,BM,BN> instantiation a descriptor launches */
+/* What rua_conv_fwd(d) / rua_conv_fwd_group(d, n) would launch, computed by the planner the launch itself runs - nothing is launched, no pointer is followed
+ * (but in_fold, which is part of the descriptor), no device is needed (the chip then counts as 256 CUs).  The descriptors are validated as for the launch. */
+typedef struct rua_conv_launch_info {
+  int32_t kernel_id;    /* rua_conv_kernel_id of the first member (-1: the whole group is one conv_band64m / conv_band128m launch, see band) */
+  int32_t form;         /* which instantiation of that kernel: its row in the library's kernel table (-1: a launcher of conv_band*.hip takes the call) */
+  int32_t grid_x, grid_y, block, lds_bytes;   /* blocks (grid_y: members side by side in a grouped grid), threads per block, dynamic LDS */
+  int32_t bm, bn;       /* tile of kernel ids 0 - 2 (pixel rows x output channels; rua_conv_tile_bm / _bn), else 0 */
+  int32_t ksplit;       /* K slices (rua_conv_last_ksplit after the launch) */
+  int32_t finisher;     /* 1: a conv_splitk_finish launch follows */
+  int32_t members;      /* bit i: member i of the group is in this launch (rua_conv_plan: 1) */
+  int32_t band, chain;  /* rua_conv_group_plan: what rua_conv_group_last_band / _last_chain report after the call, in every entry */
+} rua_conv_launch_info;
+int rua_conv_plan(const rua_conv_desc* d, rua_conv_launch_info* out);
+/* the launches of rua_conv_fwd_group(d, n) in issue order: out[0 .. *n_out - 1] (room for n entries); *n_out = rua_conv_group_last_grids after the call */
+int rua_conv_group_plan(const rua_conv_desc* d, int n, rua_conv_launch_info* out, int* n_out);
 
 /* ---- weight gradient (MFMA, split over pixels, fp32 atomic accumulation) ----------------
  * dW[t][co][c] += sum_pixels dy[n,h,w,co] * a[n, h*stride+dy_t*dil, w*stride+dx_t*dil, c]

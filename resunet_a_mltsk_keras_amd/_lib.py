@@ -28,6 +28,10 @@ class ConvDesc(C.Structure):
                 ("bias_more", vp * 3), ("in_scale", vp), ("in_shift", vp), ("in_relu", i32), ("pad_fold", i32), ("in_fold", vp)]
 
 
+class ConvLaunchInfo(C.Structure):
+    _fields_ = [(k, i32) for k in ("kernel_id", "form", "grid_x", "grid_y", "block", "lds_bytes", "bm", "bn", "ksplit", "finisher", "members", "band", "chain")]
+
+
 class BnFold(C.Structure):
     _fields_ = [("stats", vp), ("replicas", i32), ("pad", i32), ("count", f64), ("bessel_n", f64), ("eps", f32), ("momentum", f32),
                 ("gamma", vp), ("beta", vp), ("moving_mean", vp), ("moving_var", vp), ("scale", vp), ("shift", vp), ("mean", vp), ("rstd", vp)]
@@ -90,6 +94,8 @@ _SIGS = {
     "rua_conv_tile_bm": ([C.POINTER(ConvDesc)], i32),
     "rua_conv_kernel_id": ([C.POINTER(ConvDesc)], i32),
     "rua_conv_fused_input_ok": ([C.POINTER(ConvDesc)], i32),
+    "rua_conv_plan": ([C.POINTER(ConvDesc), C.POINTER(ConvLaunchInfo)], i32),
+    "rua_conv_group_plan": ([C.POINTER(ConvDesc), i32, C.POINTER(ConvLaunchInfo), C.POINTER(i32)], i32),
     "rua_conv_last_ksplit": ([], i32),
     "rua_conv_group_last_grids": ([], i32),
     "rua_conv_group_band_ok": ([C.POINTER(ConvDesc), i32], i32),

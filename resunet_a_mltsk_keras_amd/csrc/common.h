@@ -233,20 +233,72 @@ struct ConvK {
 typedef __attribute__((address_space(3))) void* lds_void_p;
 struct ConvKG { ConvK k[RUA_MAX_BRANCH]; };           // members of a grouped launch: blockIdx.y picks one
 static_assert(sizeof(ConvKG) <= 4096, "grouped launch: kernel arguments are limited to 4 KiB");
-// capture mode of the launchers (rua_conv_fwd_group): a groupable launch is recorded instead of issued
-struct ConvGroupCapture {
-  int members;   // convolutions in the group being captured (launchers that size their grid by the CU count share the chip)
-  int n; int kind[RUA_MAX_BRANCH]; unsigned grid[RUA_MAX_BRANCH]; int smem[RUA_MAX_BRANCH]; ConvK k[RUA_MAX_BRANCH];
-  bool add(int kd, unsigned g, int sm, const ConvK& kk) {
-    if (n >= RUA_MAX_BRANCH) return false;
-    kind[n] = kd; grid[n] = g; smem[n] = sm; k[n] = kk; ++n;
-    return true;
-  }
+// arguments of the kernels that take more than a ConvK (conv_halo and conv_pw: conv_mfma.hip, conv_strip*: conv_strip.hip, conv_img2: conv_img2.hip)
+struct HaloK {
+  ConvK c;
+  int d, TH, TW, PT, NS, HPW, HP, nty, ntx, total_sub, rows;     // PT: slots per sub-tile (multiple of 32), rows = NS * PT
+  unsigned mHP, mHPW, mPT, mTW;                                  // ceil(2^32 / divisor): x / dv == umulhi(x, m) for x, dv < 2^16, dv > 1
 };
-extern thread_local ConvGroupCapture* g_conv_group;
-int rua_strip_group_flush(hipStream_t st, int* grids); // conv_strip.hip: issues the conv_strip members captured since the group began (+1 on *grids per launch)
-int rua_strip_group_pending(void);                     // members captured and not yet issued
-void rua_strip_group_reset(void);                      // drops captured members (group entry, error paths)
+struct PwStep { const unsigned char* x; const unsigned char* w; unsigned xbytes, wbytes; int C, kofs, up, Hs, Ws, dense; };
+template <int KS> struct PwK { ConvK c; PwStep st[KS]; int px_per_wave, wsh, hsh, nblk; };
+struct StripK {
+  ConvK c;
+  const unsigned char* ep;                // epilogue stream: aux (aux_mode 1 / 2) or the old output (accumulate); null: none
+  unsigned epbytes;
+  int d, strips, spc, seglen, njobs, nchains;
+  int slot_bytes, SWH;                    // bytes of one x-ring slot (multiple of 1024), pixels per slot row (SW + 2 d)
+  int dbg;                                // experiments (tuning key band_dbg; conv_strip32s): 1 no stages (prologue + tail only), 2 no row DMAs in the prologue
+  int has_fold; rua_bn_fold f;            // BatchNorm coefficients derived in the prologue from the input's statistics (in_fold)
+};
+struct StripKG { StripK k[RUA_MAX_BRANCH]; };
+static_assert(sizeof(StripKG) <= 4096, "a grouped launch passes its members by value: HIP kernel arguments are limited to 4 KiB");
+struct Img2K {
+  const unsigned char* x; const unsigned char* w; float* ws;
+  int C, Cout, H, M, ngrp, nco, ksplit, cpb;     // ngrp pixel groups of 256, nco output slices of 64, cpb input chunks of 128 per block
+  unsigned xbytes, wbytes;
+};
+
+// ---- forward convolutions: plan, then issue (conv_mfma.hip) ---------------------------------------------------------------------------------------
+// One name per kernel instantiation that rua_conv_fwd / rua_conv_fwd_group can launch; the row of the same number (ConvKernelRow) holds its entry points.
+enum ConvKernel {
+  CK_IGEMM_BF16 = 0,                      // conv_igemm<bf16>, + tile form: 0 128 x 32, 1 128 x 64, 2 256 x 32, 3 256 x 64, 4 128 x 128 (rows x output channels)
+  CK_IGEMM_F32 = 5,                       // conv_igemm<float>, + tile form
+  CK_DMA = 10,                            // conv_dma, + tile form
+  CK_DMAP128 = 15, CK_DMAP128_R128, CK_DMAP64, CK_DMAP_S,        // conv_dmap<128,128,64>, <128,128,128> (128-byte rows), <64,128,64>, conv_dmap_s<128,128,64>
+  CK_HALO2, CK_HALO3,                     // conv_halo<32, 2 | 3>
+  CK_PW2, CK_PW2_DENSE, CK_PW4, CK_PW4_DENSE, CK_PW6, CK_PW6_DENSE,
+  CK_SMALL,                               // conv_small<2>
+  CK_IMG8_24, CK_IMG8_12, CK_IMG16, CK_IMG16_K2,                 // conv_img<8,1,24>, <8,1,12>, <16,1,12>, <16,2,18>
+  CK_MFMA_KERNELS,                        // (the rows of conv_mfma.hip end here)
+  CK_IMG2_8 = CK_MFMA_KERNELS, CK_IMG2_16,                       // conv_img2<8 | 16>: RUA_IMG2_ROWS
+  CK_STRIP,                               // conv_strip32, + 2 (four waves: 128-pixel strips) + 1 (no epilogue stream): RUA_STRIP_ROWS
+  CK_STRIPS = CK_STRIP + 4,               // conv_strip32s, + 2 * form (kStripS) + 1 (four waves)
+  CK_KERNELS = CK_STRIPS + 16
+};
+enum ConvArgs { CA_CONV, CA_HALO, CA_PW2, CA_PW4, CA_PW6, CA_STRIP, CA_STRIPS, CA_IMG2 };     // ConvK, HaloK, PwK<2 | 4 | 6>, StripK, StripSG (made of StripKs when issued), Img2K
+enum ConvRoute { CONV_LAUNCH = 0, CONV_ROUTE_BAND128_SUM };                                    // a plan either launches a row or names the launcher that takes the whole call
+// one row per ConvKernel: the kernel, its grouped form (blockIdx.y = member; null: none), its chain form (conv_dmap_chain; null: none), which arguments they
+// take, the dynamic LDS to allow through hipFuncSetAttribute (0: the default will do) for the first two and for the chain form
+struct ConvKernelRow { const char* name; const void* one; const void* many; const void* chain; int args; int lds; int lds_chain; };
+#define RUA_KERNEL_FN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+extern const ConvKernelRow RUA_STRIP_ROWS[CK_KERNELS - CK_STRIP];   // conv_strip.hip
+extern const ConvKernelRow RUA_IMG2_ROWS[2];                        // conv_img2.hip
+// What one convolution launches - filled by conv_plan_one (conv_mfma.hip) from descriptor, tuning and CU count alone; nothing in it is launched or looked up later.
+struct ConvLaunch {
+  int kernel;                             // ConvKernel
+  int route;                              // ConvRoute (not CONV_LAUNCH: only kid and ksplit mean anything)
+  int kid;                                // the public kernel id, rua_conv_kernel_id
+  unsigned gx, block; int smem;           // grid of a launch of its own, threads per block, dynamic LDS bytes
+  int bm, bn;                             // tile of the conv_igemm / conv_dma / conv_dmap forms (0: the kernel has none)
+  int ksplit, finisher;                   // K slices; 0: no finisher, 1: conv_splitk_finish<bf16> follows, 2: conv_splitk_finish<float>
+  bool groupable;                         // a member of a group whose kernel family is on in the tuning key conv_group: rua_conv_fwd_group may put it into a grid shared with others
+  int per_cu;                             // conv_strip: blocks per CU its LDS allows (members of one grid agree in it)
+  union { ConvK c; HaloK h; PwK<2> p2; PwK<4> p4; PwK<6> p6; StripK s; } a;     // the member of ConvKernelRow.args; all begin with the ConvK, which the finisher takes
+  Img2K i2;                               // ... CA_IMG2: conv_img2's own arguments, beside the ConvK of its finisher
+};
+// conv_strip.hip: the strip part of a plan (L->a.c is filled); the StripSG of m conv_strip32s members, their grid and LDS
+int rua_plan_conv_strip(const rua_conv_desc* d, int members, bool in_group, ConvLaunch* L);
+int rua_strip_s_pack(const ConvLaunch* const* L, int m, void* sg, unsigned* gx, int* smem);
 // conv_band64.hip
 bool rua_band64_ok(const rua_conv_desc* d, int n);
 int rua_launch_band64(const rua_conv_desc* d, int n, hipStream_t st);
@@ -258,11 +310,9 @@ int rua_launch_band128m(const rua_conv_desc* d, int n, hipStream_t st);
 bool rua_band128_sum_ok(const rua_conv_desc* d);         // rua_conv_fwd with several 3x3 segments (the summed second convolutions of a level-3 / level-4 ResBlock) in conv_band128m's form
 int rua_launch_band128_sum(const rua_conv_desc* d, hipStream_t st);
 // conv_img2.hip
-int rua_pick_img2(const rua_conv_desc* d);             // K slices (0: not this kernel)
-int rua_launch_conv_img2(ConvK& k, const rua_conv_desc* d, int KS, hipStream_t st);
-int rua_splitk_finish_bf16(const ConvK& k, hipStream_t st);   // conv_mfma.hip: conv_splitk_finish over the K slices' slabs
+int rua_pick_img2(const rua_conv_desc* d, bool in_group);   // K slices (0: not this kernel)
+void rua_plan_conv_img2(const rua_conv_desc* d, int KS, ConvLaunch* L);   // its part of a plan (L->a.c is filled)
 // conv_strip.hip
 bool rua_pick_strip(const rua_conv_desc* d);
-int rua_launch_conv_strip(const ConvK& k, const rua_conv_desc* d, hipStream_t st);
 
 static inline int rua_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

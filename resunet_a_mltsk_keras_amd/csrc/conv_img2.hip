@@ -17,11 +17,7 @@
 // -0.047 vs -0.07 ms.  The ANDs sit between a fragment read and its MFMA.)
 #include "common.h"
 
-struct Img2K {
-  const unsigned char* x; const unsigned char* w; float* ws;
-  int C, Cout, H, M, ngrp, nco, ksplit, cpb;     // ngrp pixel groups of 256, nco output slices of 64, cpb input chunks of 128 per block
-  unsigned xbytes, wbytes;
-};
+// Img2K (common.h): ngrp pixel groups of 256, nco output slices of 64, cpb input chunks of 128 per block
 template <int V> struct Img2IC { static constexpr int value = V; };
 
 template <int W>
@@ -163,9 +159,9 @@ __device__ __forceinline__ void conv_img2_body(const Img2K& q) {
 }
 template <int W> __global__ __launch_bounds__(512) void conv_img2(const Img2K q) { conv_img2_body<W>(q); }
 
-// eligibility + K slices (0: not this kernel)
-int rua_pick_img2(const rua_conv_desc* d) {
-  if (!g_tune.conv_img2 || g_conv_group || d->dtype != RUA_BF16 || d->nseg != 1 || d->in_scale || d->in_fold) return 0;
+// eligibility + K slices (0: not this kernel; nor inside a group)
+int rua_pick_img2(const rua_conv_desc* d, bool in_group) {
+  if (!g_tune.conv_img2 || in_group || d->dtype != RUA_BF16 || d->nseg != 1 || d->in_scale || d->in_fold) return 0;
   const rua_conv_seg& g = d->seg[0];
   if (g.taps != 9 || g.dil != 1 || d->stride != 1 || d->out_stride != 1 || g.up_shift != 0 || g.Hs != d->H || g.Ws != d->W || d->H != d->W || (d->W != 8 && d->W != 16) ||
       d->OH != d->H || d->OW != d->W) return 0;
@@ -183,23 +179,19 @@ int rua_pick_img2(const rua_conv_desc* d) {
   return ks;
 }
 
-int rua_launch_conv_img2(ConvK& k, const rua_conv_desc* d, int KS, hipStream_t st) {
+extern const ConvKernelRow RUA_IMG2_ROWS[2] = {
+  {"conv_img2", RUA_KERNEL_FN(conv_img2<8>), nullptr, nullptr, CA_IMG2, 256 * 256 + 256 + 3 * 64 * 256, 0},
+  {"conv_img2", RUA_KERNEL_FN(conv_img2<16>), nullptr, nullptr, CA_IMG2, 256 * 256 + 256 + 3 * 64 * 256, 0},
+};
+void rua_plan_conv_img2(const rua_conv_desc* d, int KS, ConvLaunch* L) {
   const rua_conv_seg& g = d->seg[0];
-  Img2K q;
+  ConvK& k = L->a.c;
+  Img2K& q = L->i2;
   q.x = (const unsigned char*)g.x; q.w = (const unsigned char*)g.w; q.ws = (float*)d->workspace;
   q.C = g.C; q.Cout = d->Cout; q.H = d->H; q.M = (int)k.M; q.ngrp = (int)(k.M / 256); q.nco = d->Cout / 64; q.ksplit = KS; q.cpb = (g.C / 128) / KS;
   q.xbytes = (unsigned)((size_t)k.M * g.C * 2); q.wbytes = (unsigned)((size_t)9 * d->Cout * g.C * 2);
   k.nbn = (d->Cout + 63) / 64; k.nbm = (int)(k.M / 256); k.ksplit = KS; k.stages_per_split = 0; k.ws = (float*)d->workspace; k.cnt = nullptr;
-  const unsigned grid = (unsigned)(q.ngrp * q.nco * KS);
-  constexpr int smem = 256 * 256 + 256 + 3 * 64 * 256;
-  static RuaPerDevFlag attr;
-  if (!attr.get()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_img2<8>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_img2<16>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr.get() = true;
-  }
-  if (d->W == 8) hipLaunchKernelGGL((conv_img2<8>), dim3(grid), dim3(512), smem, st, q);
-  else hipLaunchKernelGGL((conv_img2<16>), dim3(grid), dim3(512), smem, st, q);
-  RUA_LAUNCH_CHECK("conv_img2");
-  return rua_splitk_finish_bf16(k, st);
+  L->kernel = d->W == 8 ? CK_IMG2_8 : CK_IMG2_16;
+  L->gx = (unsigned)(q.ngrp * q.nco * KS); L->block = 512; L->smem = RUA_IMG2_ROWS[0].lds;
+  L->ksplit = KS; L->finisher = 1;
 }

@@ -1,6 +1,7 @@
 // Forward and data-gradient convolutions: a segmented implicit GEMM on MFMA (gfx950), channels-last.
 // Kernels: conv_igemm, conv_dma, conv_dmap (+ _s / _chain), conv_halo, conv_pw, conv_img, conv_small, conv_splitk_finish.
-// Exports: rua_conv_fwd, rua_conv_fwd_group and the rua_conv_* queries; rua_splitk_finish_bf16 for conv_img2.hip (common.h).
+// Host side (at the end): conv_plan_one() - descriptor -> ConvLaunch -, the kernel table and conv_issue().
+// Exports: rua_conv_fwd, rua_conv_fwd_group, rua_conv_plan, rua_conv_group_plan and the rua_conv_* queries.
 // The weight gradients (rua_conv_wgrad, wgrad_plan_one, ...) live in conv_wgrad.hip, the weight copies in weight_prep.hip.
 //
 // GEMM view: rows = output pixels (n,h,w), cols = output channels, K = (segment, tap, channel).
@@ -502,12 +503,6 @@ template <typename T> static void launch_splitk_finish(const ConvK& k, hipStream
   const long long t128 = ((k.M + 127) / 128) * nbn;
   if (t128 >= 512) hipLaunchKernelGGL((conv_splitk_finish<T, 128>), dim3((unsigned)t128), dim3(256), 0, st, k);
   else hipLaunchKernelGGL((conv_splitk_finish<T, 32>), dim3((unsigned)(((k.M + 31) / 32) * nbn)), dim3(256), 0, st, k);
-}
-
-int rua_splitk_finish_bf16(const ConvK& k, hipStream_t st) {
-  launch_splitk_finish<bf16_t>(k, st);
-  RUA_LAUNCH_CHECK("conv_splitk_finish");
-  return RUA_OK;
 }
 
 // =========================================================================================
@@ -1073,11 +1068,7 @@ template <int BM, int BN> static constexpr int conv_dma_base() {
 // still fill 8..12 MFMA row tiles).  No barrier inside the K loop: one DMA phase, one barrier, 9 taps x C/16 k-steps of
 // MFMAs whose A fragments are LDS reads at (row + tap offset) and whose B fragments (all 9 taps) live in registers.
 // Overlap of load / compute / epilogue comes from 2-3 co-resident blocks per CU.
-struct HaloK {
-  ConvK c;
-  int d, TH, TW, PT, NS, HPW, HP, nty, ntx, total_sub, rows;     // PT: slots per sub-tile (multiple of 32), rows = NS * PT
-  unsigned mHP, mHPW, mPT, mTW;                                  // ceil(2^32 / divisor): x / dv == umulhi(x, m) for x, dv < 2^16, dv > 1
-};
+// HaloK: common.h
 __device__ __forceinline__ int fdiv(int x, unsigned m, int dv) { return dv == 1 ? x : (int)__umulhi((unsigned)x, m); }
 
 template <int C, int MAXMT>                           // MAXMT: MFMA row tiles per wave (rows <= MAXMT * 128)
@@ -1219,30 +1210,6 @@ void conv_halo(const HaloK q) {
 #define RUA_MAX_UNITS 1024
 template <typename T, int BM, int BN> static constexpr int conv_smem() { return conv_smem_base<T, BM, BN>() + RUA_MAX_UNITS * 16; }
 
-template <typename T, int BM, int BN> static int launch_conv(const ConvK& k, int nbm, hipStream_t st) {
-  static RuaPerDevFlag attr_set_;
-  bool& attr_set = attr_set_.get();
-  constexpr int smem = conv_smem<T, BM, BN>();
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm<T, BM, BN>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  // split-K invariant: the workspace is all zeros on entry (caller zero-fills it once) and the finisher writes the
-  // zeros back after consuming the sums, so no memset is launched per convolution.
-  const int smem_now = conv_smem_base<T, BM, BN>() + ((k.nunits * 16 + 255) / 256) * 256;     // unit table sized to this launch
-  if (g_conv_group && (g_tune.conv_group & 2) && k.ksplit == 1 && sizeof(T) == 2 && BM == 256 && BN == 64) {           // the C = 64 level's 3x3 convs
-    if (!g_conv_group->add(3, (unsigned)(nbm * k.nbn), smem_now, k)) { rua_set_error("rua_conv_fwd_group: more than %d captured members", RUA_MAX_BRANCH); return RUA_ERR_ARG; }
-    return RUA_OK;
-  }
-  hipLaunchKernelGGL((conv_igemm<T, BM, BN>), dim3(nbm * k.nbn * k.ksplit), dim3(256), smem_now, st, k);
-  RUA_LAUNCH_CHECK("conv_igemm");
-  if (k.ksplit > 1) {
-    launch_splitk_finish<T>(k, st);
-    RUA_LAUNCH_CHECK("conv_splitk_finish");
-  }
-  return RUA_OK;
-}
-
 // split-K factor: only when the output grid cannot fill the chip and the K loop is long
 static int pick_ksplit(long long tiles, int nstages, long long M, int Cout, size_t ws_bytes) {
   const long long slabs = (long long)(ws_bytes / ((size_t)M * Cout * sizeof(float)));     // one fp32 slab per K slice
@@ -1285,64 +1252,6 @@ static bool pick_dma(const rua_conv_desc* d, int bn) {
   return dma;
 }
 
-extern "C" int rua_conv_smem_bytes(const rua_conv_desc* d) {
-  const long long M = (long long)d->N * d->H * d->W;
-  const int bn = pick_bn(d, M), bm = pick_bm(d, M, bn);
-  const bool h = d->dtype == RUA_BF16;
-  if (bn == 128) return h ? conv_smem<bf16_t, 128, 128>() : conv_smem<float, 128, 128>();
-  if (bm == 256) return bn == 32 ? (h ? conv_smem<bf16_t, 256, 32>() : conv_smem<float, 256, 32>()) : (h ? conv_smem<bf16_t, 256, 64>() : conv_smem<float, 256, 64>());
-  return bn == 32 ? (h ? conv_smem<bf16_t, 128, 32>() : conv_smem<float, 128, 32>()) : (h ? conv_smem<bf16_t, 128, 64>() : conv_smem<float, 128, 64>());
-}
-
-template <int BM, int BN> static int launch_conv_dma(const ConvK& k, int nbm, hipStream_t st) {
-  static RuaPerDevFlag attr_set_;
-  bool& attr_set = attr_set_.get();
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma<BM, BN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              conv_dma_base<BM, BN>());
-    attr_set = true;
-  }
-  const int smem_now = conv_dma_base<BM, BN>();
-  hipLaunchKernelGGL((conv_dma<BM, BN>), dim3(nbm * k.nbn * k.ksplit), dim3(256), smem_now, st, k);
-  RUA_LAUNCH_CHECK("conv_dma");
-  if (k.ksplit > 1) {
-    launch_splitk_finish<bf16_t>(k, st);
-    RUA_LAUNCH_CHECK("conv_splitk_finish");
-  }
-  return RUA_OK;
-}
-
-template <int BM, int BN, int ROWB> static int launch_conv_dmap(const ConvK& k, hipStream_t st) {
-  static RuaPerDevFlag attr_set_;
-  bool& attr_set = attr_set_.get();
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dmap<BM, BN, ROWB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              conv_dmap_smem<BM, BN>());
-    if constexpr (BM == 128 && ROWB == 64)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dmap_s<BM, BN, ROWB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                conv_dmap_smem<BM, BN, 4>());
-    attr_set = true;
-  }
-  const bool spread = BM == 128 && ROWB == 64 && g_tune.dmap_spread == 1; // DMA instructions between the MFMAs of the same waves (four stage buffers)
-  const int smem = spread ? conv_dmap_smem<BM, BN, 4>() : conv_dmap_smem<BM, BN>();
-  if (g_conv_group && (g_tune.conv_group & (BM == 128 ? 4 : 8)) && k.ksplit == 1 && ROWB == 64) {
-    if (!g_conv_group->add(BM == 128 ? (spread ? 6 : 1) : 2,     /* capture kinds: 1 / 2 conv_dmap 128- / 64-row tiles, 3 conv_igemm<256,64>, 4 / 5 retired, 6 conv_dmap_s */ (unsigned)(k.nbm * k.nbn), smem, k)) { rua_set_error("rua_conv_fwd_group: more than %d captured members", RUA_MAX_BRANCH); return RUA_ERR_ARG; }
-    return RUA_OK;
-  }
-  if constexpr (BM == 128 && ROWB == 64) {
-    if (spread) hipLaunchKernelGGL((conv_dmap_s<BM, BN, ROWB>), dim3(k.nbm * k.nbn * k.ksplit), dim3(256), smem, st, k);
-    else hipLaunchKernelGGL((conv_dmap<BM, BN, ROWB>), dim3(k.nbm * k.nbn * k.ksplit), dim3(256), smem, st, k);
-  } else {
-    hipLaunchKernelGGL((conv_dmap<BM, BN, ROWB>), dim3(k.nbm * k.nbn * k.ksplit), dim3(256), smem, st, k);
-  }
-  RUA_LAUNCH_CHECK("conv_dmap");
-  if (k.ksplit > 1 && k.cnt == nullptr) {
-    launch_splitk_finish<bf16_t>(k, st);
-    RUA_LAUNCH_CHECK("conv_splitk_finish");
-  }
-  return RUA_OK;
-}
-
 // =========================================================================================
 // conv_pw: the narrow 1x1 convolutions of the two top levels (Cout <= 32, K <= 96: combine / PSP / upsampling convs and their
 // data gradients) are memory-bound, and on conv_igemm they streamed at ~2.8 TB/s (one 256-row tile per block: load ->
@@ -1354,12 +1263,8 @@ template <int BM, int BN, int ROWB> static int launch_conv_dmap(const ConvK& k, 
 // interleaved between the wave halves) into 8-channel pieces for the shared epilogue semantics (bias, accumulate, residual /
 // mask, ReLU, statistics) and 16-byte stores.  Statistics stay in registers over all tiles of a wave and leave through
 // shuffles -> LDS -> one fp64 atomic per channel and block, like everywhere else.
-struct PwStep { const unsigned char* x; const unsigned char* w; unsigned xbytes, wbytes; int C, kofs, up, Hs, Ws, dense; };
-template <int KS> struct PwK { ConvK c; PwStep st[KS]; int px_per_wave, wsh, hsh, nblk; };
-// members of a group (rua_conv_fwd_group: the four branch convolutions of the top-level PSPPooling, the per-source data gradients of a concatenating 1x1
-// conv): recorded by the launcher, issued as ONE grid (blockIdx.y = member, grids of unequal size) - each was a launch of 8 - 15 us, half of it ramp and drain
-struct PwGroupCapture { int n; PwK<2> k[RUA_MAX_BRANCH]; bool dense[RUA_MAX_BRANCH]; };
-static thread_local PwGroupCapture* g_pw_group = nullptr;
+// PwStep, PwK<KS>: common.h.  PwKG: the members of a group (rua_conv_fwd_group: the four branch convolutions of the top-level PSPPooling, the per-source data gradients of a
+// concatenating 1x1 conv) as ONE grid (blockIdx.y = member, grids of unequal size) - each was a launch of 8 - 15 us, half of it ramp and drain
 template <int KS> struct PwKG { PwK<KS> k[RUA_MAX_BRANCH]; };
 static_assert(sizeof(PwKG<2>) <= 4096, "grouped launch: kernel arguments are limited to 4 KiB");
 
@@ -1561,9 +1466,8 @@ static bool pick_pw(const rua_conv_desc* d) {
   }
   return true;
 }
-template <int KS> static int launch_conv_pw(const ConvK& k, const rua_conv_desc* d, hipStream_t st) {
-  PwK<KS> q;
-  q.c = k;
+template <int KS> static void plan_conv_pw(PwK<KS>& q, const rua_conv_desc* d, ConvLaunch* L) {       // q: the member of L->a for KS, its ConvK filled
+  const ConvK& k = q.c;
   int n = 0;
   for (int s = 0; s < d->nseg; ++s) {
     const SegK& g = k.seg[s];
@@ -1587,16 +1491,8 @@ template <int KS> static int launch_conv_pw(const ConvK& k, const rua_conv_desc*
   q.nblk = (int)grid;
   bool all_dense = true;
   for (int i = 0; i < KS; ++i) all_dense = all_dense && (q.st[i].dense || q.st[i].C == 0);
-  if constexpr (KS == 2) {
-    if (g_pw_group && g_pw_group->n < RUA_MAX_BRANCH) {      // a member of a group: recorded, issued by rua_conv_fwd_group
-      g_pw_group->dense[g_pw_group->n] = all_dense; g_pw_group->k[g_pw_group->n++] = q;
-      return RUA_OK;
-    }
-  }
-  if (all_dense) hipLaunchKernelGGL((conv_pw<KS, true>), dim3(grid), dim3(256), 0, st, q);
-  else hipLaunchKernelGGL((conv_pw<KS, false>), dim3(grid), dim3(256), 0, st, q);
-  RUA_LAUNCH_CHECK("conv_pw");
-  return RUA_OK;
+  L->kernel = (KS == 2 ? CK_PW2 : KS == 4 ? CK_PW4 : CK_PW6) + (all_dense ? 1 : 0);
+  L->gx = grid; L->smem = 0;
 }
 
 // ---- conv_halo launcher -------------------------------------------------------------------------------------------------
@@ -1633,9 +1529,9 @@ static void halo_tiling(int H, int W, int d, int rowb, int* TH_, int* TW_, int* 
   *TH_ = bth; *TW_ = btw; *NS_ = ns < 1 ? 1 : ns;
 }
 
-static int launch_conv_halo(const ConvK& k, int dil, hipStream_t st) {
-  HaloK q;
-  q.c = k;
+static int plan_conv_halo(int dil, ConvLaunch* L) {
+  HaloK& q = L->a.h;
+  const ConvK& k = q.c;
   q.d = dil;
   const int Cc = k.seg[0].C, rowb = Cc * 2;
   halo_tiling(k.H, k.W, dil, rowb, &q.TH, &q.TW, &q.NS);
@@ -1651,18 +1547,9 @@ static int launch_conv_halo(const ConvK& k, int dil, hipStream_t st) {
   const int halo_bytes = (q.NS * q.HP * rowb + 1023) / 1024 * 1024;
   const int epi_bytes = 128 * 36 * 4;
   const int area = epi_bytes > halo_bytes ? epi_bytes : halo_bytes;
-  const int smem = area + q.rows * 4 + 4 * 12 * 4 + 4 * 4 * 16 * 4;
-  const int blocks = (int)((total + q.NS - 1) / q.NS);
-  static RuaPerDevFlag attr2_, attr3_;
-  bool &attr2 = attr2_.get(), &attr3 = attr3_.get();
-  if (q.rows <= 256) {
-    if (!attr2) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo<32, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr2 = true; }
-    hipLaunchKernelGGL((conv_halo<32, 2>), dim3(blocks), dim3(256), smem, st, q);
-  } else {
-    if (!attr3) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo<32, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr3 = true; }
-    hipLaunchKernelGGL((conv_halo<32, 3>), dim3(blocks), dim3(256), smem, st, q);
-  }
-  RUA_LAUNCH_CHECK("conv_halo");
+  L->smem = area + q.rows * 4 + 4 * 12 * 4 + 4 * 4 * 16 * 4;
+  L->gx = (unsigned)((total + q.NS - 1) / q.NS);
+  L->kernel = q.rows <= 256 ? CK_HALO2 : CK_HALO3;
   return RUA_OK;
 }
 
@@ -1789,8 +1676,8 @@ template <int W, int KS> static constexpr int conv_img_smem() {
   return (tile > redb ? tile : redb) + 4 * 4 * 16 * 4;
 }
 // eligibility + K slices (0: not this kernel)
-static int pick_img(const rua_conv_desc* d) {
-  if (!g_tune.conv_img || g_conv_group || d->dtype != RUA_BF16 || d->nseg != 1 || d->in_scale || d->in_fold) return 0;
+static int pick_img(const rua_conv_desc* d, bool in_group) {
+  if (!g_tune.conv_img || in_group || d->dtype != RUA_BF16 || d->nseg != 1 || d->in_scale || d->in_fold) return 0;
   const rua_conv_seg& g = d->seg[0];
   if (g.taps != 9 || g.dil != 1 || d->stride != 1 || g.up_shift != 0 || g.Hs != d->H || g.Ws != d->W || d->H != d->W || (d->W != 8 && d->W != 16)) return 0;
   const int HW = d->H * d->W;
@@ -1807,27 +1694,18 @@ static int pick_img(const rua_conv_desc* d) {
   }
   return KS;
 }
-static int launch_conv_img(ConvK& k, const rua_conv_desc* d, int KS, hipStream_t st) {
+static int plan_conv_img(const rua_conv_desc* d, int KS, ConvLaunch* L) {
+  ConvK& k = L->a.c;
   k.nbn = d->Cout / 32; k.nbm = d->N; k.ksplit = KS; k.stages_per_split = 0; k.ws = KS > 1 ? (float*)d->workspace : nullptr; k.cnt = nullptr;
-  const unsigned grid = (unsigned)(d->N * (d->Cout / 32) * KS);
-  static RuaPerDevFlag attr_;
-  bool& attr = attr_.get();
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_img<8, 1, 24>), hipFuncAttributeMaxDynamicSharedMemorySize, conv_img_smem<8, 1>());
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_img<8, 1, 12>), hipFuncAttributeMaxDynamicSharedMemorySize, conv_img_smem<8, 1>());
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_img<16, 1, 12>), hipFuncAttributeMaxDynamicSharedMemorySize, conv_img_smem<16, 1>());
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_img<16, 2, 18>), hipFuncAttributeMaxDynamicSharedMemorySize, conv_img_smem<16, 2>());
-    attr = true;
-  }
-  constexpr int s81 = conv_img_smem<8, 1>(), s161 = conv_img_smem<16, 1>(), s162 = conv_img_smem<16, 2>();
+  L->gx = (unsigned)(d->N * (d->Cout / 32) * KS);
   const int nk = 9 * (d->seg[0].C / KS / 16) / 4;        // k-steps per wave: 144 (CS = 1024), 72, 36 (CS = 256) - a multiple of the prefetch depth
-  if (d->W == 8 && KS == 1 && nk % 24 == 0) hipLaunchKernelGGL((conv_img<8, 1, 24>), dim3(grid), dim3(256), s81, st, k);
-  else if (d->W == 8 && KS == 1) hipLaunchKernelGGL((conv_img<8, 1, 12>), dim3(grid), dim3(256), s81, st, k);
-  else if (d->W == 16 && KS == 1) hipLaunchKernelGGL((conv_img<16, 1, 12>), dim3(grid), dim3(256), s161, st, k);
-  else if (d->W == 16 && KS == 2) hipLaunchKernelGGL((conv_img<16, 2, 18>), dim3(grid), dim3(256), s162, st, k);
+  if (d->W == 8 && KS == 1 && nk % 24 == 0) L->kernel = CK_IMG8_24;
+  else if (d->W == 8 && KS == 1) L->kernel = CK_IMG8_12;
+  else if (d->W == 16 && KS == 1) L->kernel = CK_IMG16;
+  else if (d->W == 16 && KS == 2) L->kernel = CK_IMG16_K2;
   else { rua_set_error("conv_img: no instantiation for W=%d KS=%d", d->W, KS); return RUA_ERR_ARG; }
-  RUA_LAUNCH_CHECK("conv_img");
-  if (KS > 1) { launch_splitk_finish<bf16_t>(k, st); RUA_LAUNCH_CHECK("conv_splitk_finish"); }
+  L->smem = d->W == 8 ? conv_img_smem<8, 1>() : KS == 1 ? conv_img_smem<16, 1>() : conv_img_smem<16, 2>();
+  L->ksplit = KS; L->finisher = KS > 1 ? 1 : 0;
   return RUA_OK;
 }
 
@@ -1839,19 +1717,6 @@ static bool pick_dmap(const rua_conv_desc* d) {
     if (d->seg[s_].C % 64 != 0) return false;
   return true;
 }
-
-static int dispatch_conv_dma(const ConvK& k, int bm, int bn, int nbm, hipStream_t st) {
-  if (bn == 128) return launch_conv_dma<128, 128>(k, nbm, st);
-  if (bm == 256) return bn == 32 ? launch_conv_dma<256, 32>(k, nbm, st) : launch_conv_dma<256, 64>(k, nbm, st);
-  return bn == 32 ? launch_conv_dma<128, 32>(k, nbm, st) : launch_conv_dma<128, 64>(k, nbm, st);
-}
-
-template <typename T> static int dispatch_conv(const ConvK& k, int bm, int bn, int nbm, hipStream_t st) {
-  if (bn == 128) return launch_conv<T, 128, 128>(k, nbm, st);
-  if (bm == 256) return bn == 32 ? launch_conv<T, 256, 32>(k, nbm, st) : launch_conv<T, 256, 64>(k, nbm, st);
-  return bn == 32 ? launch_conv<T, 128, 32>(k, nbm, st) : launch_conv<T, 128, 64>(k, nbm, st);
-}
-
 
 // =========================================================================================
 // conv_small: 1x1 convolutions over at most a few thousand output pixels, bf16 - the PSPPooling at the bottleneck (model2.py:41-79 at 8 x 8 x 1024:
@@ -1957,23 +1822,128 @@ static bool pick_small(const rua_conv_desc* d) {
     if (d->seg[s_].taps != 1 || d->seg[s_].C % 16 != 0) return false;
   return true;
 }
-static int launch_conv_small(ConvK& k, hipStream_t st) {
+static void plan_conv_small(ConvLaunch* L) {
+  ConvK& k = L->a.c;
   k.nbm = (int)((k.M + 31) / 32); k.nbn = (k.Cout + 63) / 64;
   k.ksplit = 1; k.stages_per_split = 0; k.ws = nullptr; k.cnt = nullptr;
-  constexpr int smem = (4 * 32 * 68 + 4 * 8 * 16) * 4;
-  if (g_conv_group && (g_tune.conv_group & 16)) {       // capture mode: issued by rua_conv_fwd_group, side by side with its siblings
-    if (!g_conv_group->add(7, (unsigned)(k.nbm * k.nbn), smem, k)) { rua_set_error("rua_conv_fwd_group: more than %d captured members", RUA_MAX_BRANCH); return RUA_ERR_ARG; }
-    return RUA_OK;
-  }
-  hipLaunchKernelGGL((conv_small<2>), dim3(k.nbm * k.nbn), dim3(256), smem, st, k);
-  RUA_LAUNCH_CHECK("conv_small");
-  return RUA_OK;
+  L->kernel = CK_SMALL; L->gx = (unsigned)(k.nbm * k.nbn); L->smem = (4 * 32 * 68 + 4 * 8 * 16) * 4;
 }
 
-static thread_local int g_last_ksplit = 1;
-extern "C" int rua_conv_last_ksplit(void) { return g_last_ksplit; }    // K slices of this thread's latest rua_conv_fwd launch (1: no finisher ran)
+// =========================================================================================
+// Host side: plan, then issue.  conv_plan_one() turns a descriptor into a ConvLaunch - kernel row, grid, LDS, kernel arguments, K slices, finisher - as a pure
+// function of the descriptor, whether it is one of `members` convolutions of a group, g_tune and rua_cu_count(): it launches nothing and keeps no state.
+// conv_pack() joins m plans on the same row into the arguments, grid and LDS of one launch, conv_issue() puts that on a stream.  Every export below is a
+// composition of these, so what rua_conv_plan / rua_conv_group_plan report is what the launch does.
 
-extern "C" int rua_conv_fwd(const rua_conv_desc* d, void* stream) {
+// which kernel serves a descriptor: the public id of rua_conv_kernel_id; *ks: the K slices of conv_img2 / conv_img
+static int conv_pick(const rua_conv_desc* d, bool in_group, int* ks) {
+  *ks = 1;
+  if (rua_pick_strip(d)) return 5;
+  if (pick_halo(d)) return 3;
+  if (pick_pw(d)) return 4;
+  if (pick_small(d)) return 6;
+  if (const int img2_ks = rua_pick_img2(d, in_group)) { *ks = img2_ks; return 8; }      // the two deepest levels (round 5, conv_img2.hip)
+  if (!in_group && rua_band128_sum_ok(d)) return 9;         // several 3x3 segments at C = 128 / 256 (the summed second convolutions of levels 3 - 4): conv_band128m, the sum on chip
+  if (const int img_ks = pick_img(d, in_group)) { *ks = img_ks; return 7; }
+  if (pick_dmap(d)) return 2;
+  return pick_dma(d, pick_bn(d, (long long)d->N * d->H * d->W)) ? 1 : 0;
+}
+
+// tile, grid and K split of the tiled kernels (ids 0 - 2): what conv_plan_one launches and rua_conv_tile_bm / _bn report
+struct ConvTiling { bool dmap; int bm, bn, nbm, nbn, ksplit, stages_per_split; };
+static void conv_tiling(const rua_conv_desc* d, ConvTiling* t) {
+  const long long M = (long long)d->N * d->H * d->W;
+  int units = 0;
+  for (int s = 0; s < d->nseg && s < RUA_MAX_SEG; ++s) units += d->seg[s].taps * ((d->seg[s].C + 31) / 32);
+  const bool sized = M > 0 && d->Cout > 0;                  // (the queries answer for any descriptor)
+  const size_t ws_usable = d->workspace_bytes > 4096 ? (size_t)d->workspace_bytes - 4096 : 0;
+  t->dmap = pick_dmap(d);
+  if (t->dmap) {
+    // 128 x 128 tiles; split K until the grid covers the chip once (every level of the reference network then runs
+    // 256 blocks of >= 18 stages: one block per CU, no tail)
+    const int target = g_tune.dmap_target > 0 ? g_tune.dmap_target : rua_cu_count();      // one block per CU
+    t->bm = 128; t->bn = 128;
+    t->nbn = (d->Cout + 127) / 128;
+    t->nbm = (int)((M + 127) / 128);
+    const int nstages = units / 2;
+    const long long tiles = (long long)t->nbm * t->nbn;
+    int want = 1;
+    const long long slabs = (d->workspace && sized) ? (long long)(ws_usable / ((size_t)M * d->Cout * sizeof(float))) : 0;
+    if (slabs >= 2 && tiles < target) {
+      want = (int)((target + tiles - 1) / tiles);
+      if (want > nstages / 4) want = nstages / 4;
+      if (want > 32) want = 32;
+      if (want > slabs) want = (int)slabs;
+      if (want < 1) want = 1;
+      // half the chip busy for a short K beats two slices + slab traffic + a finisher launch
+      // (measured at the 32x32 level: 28.4 vs 32.5 us for K = 36 stages; the 108-stage convs still split: 46 vs 68)
+      if (tiles * 2 >= target && nstages <= 40) want = 1;
+    }
+    t->stages_per_split = (nstages + want - 1) / want;
+    t->ksplit = t->stages_per_split > 0 ? (nstages + t->stages_per_split - 1) / t->stages_per_split : 1;
+    // the unsplit half-chip case (32x32 level: 128 tiles of 128 x 128, 36 stages): 64-row tiles put a block on every CU
+    // (measured there: 25.5 / 23.7 / 22.6 us vs 30.1 / 30.0 / 28.6 for d = 1 / d = 15 / plain)
+    if (g_tune.dmap_bm64 && t->ksplit == 1 && tiles < target && tiles * 2 >= target) {
+      t->bm = 64;
+      t->nbm = (int)((M + 63) / 64);
+    }
+    return;
+  }
+  t->bn = pick_bn(d, M);
+  t->bm = pick_bm(d, M, t->bn);
+  t->nbn = (d->Cout + t->bn - 1) / t->bn;
+  t->nbm = (int)((M + t->bm - 1) / t->bm);
+  const int nstages = (units + 1) / 2;
+  t->ksplit = (d->workspace && t->bm == 128 && sized) ? pick_ksplit((long long)t->nbm * t->nbn, nstages, M, d->Cout, ws_usable) : 1;
+  t->stages_per_split = (nstages + t->ksplit - 1) / t->ksplit;
+  t->ksplit = t->stages_per_split > 0 ? (nstages + t->stages_per_split - 1) / t->stages_per_split : 1;
+}
+static int tile_form(int bm, int bn) { return bn == 128 ? 4 : (bm == 256 ? 2 : 0) + (bn == 64 ? 1 : 0); }       // ConvKernel: 0 128 x 32, 1 128 x 64, 2 256 x 32, 3 256 x 64, 4 128 x 128
+
+// one row per ConvKernel below CK_MFMA_KERNELS (conv_img2's and conv_strip's rows stand beside their kernels)
+#define FN RUA_KERNEL_FN
+#define RUA_TILE_ROWS(NAME, KERN, LDS, ...) \
+  {NAME, FN(KERN<__VA_ARGS__ 128, 32>), nullptr, nullptr, CA_CONV, LDS<__VA_ARGS__ 128, 32>(), 0}, {NAME, FN(KERN<__VA_ARGS__ 128, 64>), nullptr, nullptr, CA_CONV, LDS<__VA_ARGS__ 128, 64>(), 0}, \
+  {NAME, FN(KERN<__VA_ARGS__ 256, 32>), nullptr, nullptr, CA_CONV, LDS<__VA_ARGS__ 256, 32>(), 0}
+static const ConvKernelRow CONV_ROWS[CK_MFMA_KERNELS] = {
+  RUA_TILE_ROWS("conv_igemm", conv_igemm, conv_smem, bf16_t,),
+  {"conv_igemm", FN(conv_igemm<bf16_t, 256, 64>), FN(conv_igemm_g<bf16_t, 256, 64>), nullptr, CA_CONV, conv_smem<bf16_t, 256, 64>(), 0},     // the C = 64 level's 3x3 convs
+  {"conv_igemm", FN(conv_igemm<bf16_t, 128, 128>), nullptr, nullptr, CA_CONV, conv_smem<bf16_t, 128, 128>(), 0},
+  RUA_TILE_ROWS("conv_igemm", conv_igemm, conv_smem, float,),
+  {"conv_igemm", FN(conv_igemm<float, 256, 64>), nullptr, nullptr, CA_CONV, conv_smem<float, 256, 64>(), 0},
+  {"conv_igemm", FN(conv_igemm<float, 128, 128>), nullptr, nullptr, CA_CONV, conv_smem<float, 128, 128>(), 0},
+  RUA_TILE_ROWS("conv_dma", conv_dma, conv_dma_base,),
+  {"conv_dma", FN(conv_dma<256, 64>), nullptr, nullptr, CA_CONV, conv_dma_base<256, 64>(), 0},
+  {"conv_dma", FN(conv_dma<128, 128>), nullptr, nullptr, CA_CONV, conv_dma_base<128, 128>(), 0},
+  {"conv_dmap", FN(conv_dmap<128, 128, 64>), FN(conv_dmap_g<128, 128, 64>), FN(conv_dmap_chain<128, 128, 64>), CA_CONV, conv_dmap_smem<128, 128>(), conv_dmap_chain_smem<128, 128>()},
+  {"conv_dmap", FN(conv_dmap<128, 128, 128>), nullptr, nullptr, CA_CONV, conv_dmap_smem<128, 128>(), 0},
+  {"conv_dmap", FN(conv_dmap<64, 128, 64>), FN(conv_dmap_g<64, 128, 64>), FN(conv_dmap_chain<64, 128, 64>), CA_CONV, conv_dmap_smem<64, 128>(), conv_dmap_chain_smem<64, 128>()},
+  {"conv_dmap_s", FN(conv_dmap_s<128, 128, 64>), FN(conv_dmap_gs<128, 128, 64>), nullptr, CA_CONV, conv_dmap_smem<128, 128, 4>(), 0},      // DMA instructions between the MFMAs of the same waves (four stage buffers)
+  {"conv_halo", FN(conv_halo<32, 2>), nullptr, nullptr, CA_HALO, 96 * 1024, 0},
+  {"conv_halo", FN(conv_halo<32, 3>), nullptr, nullptr, CA_HALO, 96 * 1024, 0},
+  {"conv_pw", FN(conv_pw<2, false>), FN(conv_pw_g<2, false>), nullptr, CA_PW2, 0, 0},
+  {"conv_pw", FN(conv_pw<2, true>), FN(conv_pw_g<2, true>), nullptr, CA_PW2, 0, 0},
+  {"conv_pw", FN(conv_pw<4, false>), nullptr, nullptr, CA_PW4, 0, 0},
+  {"conv_pw", FN(conv_pw<4, true>), nullptr, nullptr, CA_PW4, 0, 0},
+  {"conv_pw", FN(conv_pw<6, false>), nullptr, nullptr, CA_PW6, 0, 0},
+  {"conv_pw", FN(conv_pw<6, true>), nullptr, nullptr, CA_PW6, 0, 0},
+  {"conv_small", FN(conv_small<2>), FN(conv_small_g<2>), nullptr, CA_CONV, 0, 0},
+  {"conv_img", FN(conv_img<8, 1, 24>), nullptr, nullptr, CA_CONV, conv_img_smem<8, 1>(), 0},
+  {"conv_img", FN(conv_img<8, 1, 12>), nullptr, nullptr, CA_CONV, conv_img_smem<8, 1>(), 0},
+  {"conv_img", FN(conv_img<16, 1, 12>), nullptr, nullptr, CA_CONV, conv_img_smem<16, 1>(), 0},
+  {"conv_img", FN(conv_img<16, 2, 18>), nullptr, nullptr, CA_CONV, conv_img_smem<16, 2>(), 0},
+};
+#undef RUA_TILE_ROWS
+#undef FN
+static const ConvKernelRow& conv_row(int kernel) {
+  return kernel >= CK_STRIP ? RUA_STRIP_ROWS[kernel - CK_STRIP] : kernel >= CK_IMG2_8 ? RUA_IMG2_ROWS[kernel - CK_IMG2_8] : CONV_ROWS[kernel];
+}
+
+// ---- planning ----------------------------------------------------------------------------------------------------------
+// in_group: the convolution is one of `members` of a rua_conv_fwd_group call that groups (members >= 2, tuning key conv_group not 0); rua_conv_fwd alone is
+// members = 1, in_group = false.  A group shares the chip: conv_strip sizes its round of blocks by `members`, and the kernels that want the chip to themselves
+// (conv_img2, conv_img, the summed form of conv_band128m) stay out of it.
+static int conv_plan_one(const rua_conv_desc* d, int members, bool in_group, ConvLaunch* L) {
   RUA_CHECK_ARG(d && d->nseg >= 1 && d->nseg <= RUA_MAX_SEG, "rua_conv_fwd: nseg out of range");
   RUA_CHECK_ARG(d->dtype == RUA_F32 || d->dtype == RUA_BF16, "rua_conv_fwd: bad dtype");
   const int vec = d->dtype == RUA_BF16 ? 8 : 4;
@@ -1986,7 +1956,7 @@ extern "C" int rua_conv_fwd(const rua_conv_desc* d, void* stream) {
   RUA_CHECK_ARG(d->aux_mode == 0 || d->aux != nullptr, "rua_conv_fwd: aux_mode without aux");
   RUA_CHECK_ARG(d->stats_mode == 0 || d->stats != nullptr, "rua_conv_fwd: stats_mode without stats");
   RUA_CHECK_ARG(d->stats_mode != 2 || d->aux != nullptr, "rua_conv_fwd: stats_mode 2 needs aux");
-  ConvK k;
+  ConvK& k = L->a.c;
   k.nseg = d->nseg;
   int units = 0;
   for (int s = 0; s < d->nseg; ++s) {
@@ -2023,228 +1993,264 @@ extern "C" int rua_conv_fwd(const rua_conv_desc* d, void* stream) {
   RUA_CHECK_ARG((k.stats_R & (k.stats_R - 1)) == 0, "rua_conv_fwd: stats_replicas must be a power of two");
   k.in_scale = d->in_scale; k.in_shift = d->in_shift; k.in_relu = d->in_relu;
   k.epi_fast = g_tune.epi_fast;
-  hipStream_t st = (hipStream_t)stream;
-  if (rua_pick_strip(d)) {
-    k.nbn = 1; k.nbm = 1; k.ksplit = 1; k.stages_per_split = 0; k.ws = nullptr; k.cnt = nullptr;
-    g_last_ksplit = 1;
-    return rua_launch_conv_strip(k, d, st);
-  }
+  k.nbn = 1; k.nbm = 1; k.ksplit = 1; k.stages_per_split = 0; k.ws = nullptr; k.cnt = nullptr;      // the kernels without tiles or K slices leave it so
+  int ks;
+  L->kid = conv_pick(d, in_group, &ks);
+  L->route = CONV_LAUNCH; L->kernel = -1; L->gx = 0; L->block = 256; L->smem = 0; L->bm = L->bn = 0; L->ksplit = 1; L->finisher = 0; L->groupable = false; L->per_cu = 0;
+  if (L->kid == 5) return rua_plan_conv_strip(d, members, in_group, L);
   RUA_CHECK_ARG(d->in_scale == nullptr && d->in_fold == nullptr, "rua_conv_fwd: in_scale / in_shift / in_fold (normalise on load) is not available for "
                                         "this shape: ask rua_conv_fused_input_ok() first");
-  if (pick_halo(d)) {
-    k.nbn = 1; k.nbm = 1; k.ksplit = 1; k.stages_per_split = 0; k.ws = nullptr; k.cnt = nullptr;
-    g_last_ksplit = 1;
-    return launch_conv_halo(k, d->seg[0].dil, st);
+  switch (L->kid) {
+    case 3: return plan_conv_halo(d->seg[0].dil, L);
+    case 4: {
+      const int steps = pw_steps(d);
+      if (steps <= 2) plan_conv_pw<2>(L->a.p2, d, L); else if (steps <= 4) plan_conv_pw<4>(L->a.p4, d, L); else plan_conv_pw<6>(L->a.p6, d, L);
+      L->groupable = in_group && steps <= 2 && (g_tune.conv_group & 32);
+      return RUA_OK;
+    }
+    case 6: plan_conv_small(L); L->groupable = in_group && (g_tune.conv_group & 16); return RUA_OK;
+    case 8: rua_plan_conv_img2(d, ks, L); return RUA_OK;
+    case 9: L->route = CONV_ROUTE_BAND128_SUM; return RUA_OK;
+    case 7: return plan_conv_img(d, ks, L);
+    default: break;
   }
-  if (pick_pw(d)) {
-    k.nbn = 1; k.nbm = 1; k.ksplit = 1; k.stages_per_split = 0; k.ws = nullptr; k.cnt = nullptr;
-    g_last_ksplit = 1;
-    const int ks = pw_steps(d);
-    return ks <= 2 ? launch_conv_pw<2>(k, d, st) : ks <= 4 ? launch_conv_pw<4>(k, d, st) : launch_conv_pw<6>(k, d, st);
-  }
-  if (pick_small(d)) {
-    g_last_ksplit = 1;
-    return launch_conv_small(k, st);
-  }
-  if (const int img2_ks = rua_pick_img2(d)) {                // the two deepest levels (round 5, conv_img2.hip)
-    g_last_ksplit = img2_ks;
-    return rua_launch_conv_img2(k, d, img2_ks, st);
-  }
-  if (!g_conv_group && rua_band128_sum_ok(d)) {              // several 3x3 segments at C = 128 / 256 (the summed second convolutions of levels 3 - 4): conv_band128m, the sum on chip
-    g_last_ksplit = 1;
-    return rua_launch_band128_sum(d, st);
-  }
-  if (const int img_ks = pick_img(d)) {
-    g_last_ksplit = img_ks;
-    return launch_conv_img(k, d, img_ks, st);
-  }
-  if (pick_dmap(d)) {
-    // 128 x 128 tiles; split K until the grid covers the chip once (every level of the reference network then runs
-    // 256 blocks of >= 18 stages: one block per CU, no tail)
-    const int target = g_tune.dmap_target > 0 ? g_tune.dmap_target : rua_cu_count();      // one block per CU
-    k.nbn = (d->Cout + 127) / 128;
-    k.nbm = (int)((k.M + 127) / 128);
-    const int nstages = units / 2;
-    const long long tiles = (long long)k.nbm * k.nbn;
-    int want = 1;
+  ConvTiling t;
+  conv_tiling(d, &t);
+  k.nbn = t.nbn; k.nbm = t.nbm; k.ksplit = t.ksplit; k.stages_per_split = t.stages_per_split;
+  k.ws = (float*)d->workspace;
+  L->bm = t.bm; L->bn = t.bn; L->ksplit = t.ksplit;
+  L->gx = (unsigned)(t.nbm * t.nbn * t.ksplit);
+  if (t.dmap) {
     // the last 4 KiB of the workspace hold the tile ticket counters of the in-launch reduction (zero between launches:
     // the caller zero-fills the workspace once, every last arriver resets its counter)
     // OFF by default - measured: the single last-arriving block reads ksplit x 64 KB of slabs serially (8x8 level: 45 vs 26 us,
     // 16x16: 39 vs 28 us); the separate finisher spreads the same bytes over 1024 blocks.  Kept (and tested) as an option.
-    const int fused = g_tune.dmap_fused_finish;
     const size_t ws_usable = d->workspace_bytes > 4096 ? (size_t)d->workspace_bytes - 4096 : 0;
-    const long long slabs = d->workspace ? (long long)(ws_usable / ((size_t)k.M * d->Cout * sizeof(float))) : 0;
-    k.cnt = (fused && d->workspace && tiles <= 1024) ? reinterpret_cast<int*>((char*)d->workspace + ws_usable) : nullptr;
-    if (slabs >= 2 && tiles < target) {
-      want = (int)((target + tiles - 1) / tiles);
-      if (want > nstages / 4) want = nstages / 4;
-      if (want > 32) want = 32;
-      if (want > slabs) want = (int)slabs;
-      if (want < 1) want = 1;
-      // half the chip busy for a short K beats two slices + slab traffic + a finisher launch
-      // (measured at the 32x32 level: 28.4 vs 32.5 us for K = 36 stages; the 108-stage convs still split: 46 vs 68)
-      if (tiles * 2 >= target && nstages <= 40) want = 1;
-    }
-    k.ws = (float*)d->workspace;
-    k.stages_per_split = (nstages + want - 1) / want;
-    k.ksplit = (nstages + k.stages_per_split - 1) / k.stages_per_split;
-    g_last_ksplit = k.ksplit;
-    const int rowb = g_tune.dmap_rowb == 128 ? 128 : 64;
-    // the unsplit half-chip case (32x32 level: 128 tiles of 128 x 128, 36 stages): 64-row tiles put a block on every CU
-    // (measured there: 25.5 / 23.7 / 22.6 us vs 30.1 / 30.0 / 28.6 for d = 1 / d = 15 / plain)
-    const int bm64 = g_tune.dmap_bm64;
-    if (bm64 && k.ksplit == 1 && tiles < target && tiles * 2 >= target) {
-      k.nbm = (int)((k.M + 63) / 64);
-      return launch_conv_dmap<64, 128, 64>(k, st);
-    }
-    return rowb == 128 ? launch_conv_dmap<128, 128, 128>(k, st) : launch_conv_dmap<128, 128, 64>(k, st);
+    k.cnt = (g_tune.dmap_fused_finish && d->workspace && (long long)((k.M + 127) / 128) * t.nbn <= 1024) ? reinterpret_cast<int*>((char*)d->workspace + ws_usable) : nullptr;
+    const bool rows64 = g_tune.dmap_rowb != 128;            // bytes per LDS row
+    L->kernel = t.bm == 64 ? CK_DMAP64 : !rows64 ? CK_DMAP128_R128 : g_tune.dmap_spread == 1 ? CK_DMAP_S : CK_DMAP128;
+    L->finisher = (t.ksplit > 1 && k.cnt == nullptr) ? 1 : 0;
+    L->groupable = in_group && (g_tune.conv_group & (t.bm == 128 ? 4 : 8)) && t.ksplit == 1 && (rows64 || t.bm == 64);
+    L->smem = conv_row(L->kernel).lds;
+    return RUA_OK;
   }
-  const int bn = pick_bn(d, k.M);
-  int bm = pick_bm(d, k.M, bn);
-  k.nbn = (d->Cout + bn - 1) / bn;
-  int nbm = (int)((k.M + bm - 1) / bm);
-  k.nbm = nbm;
-  const int nstages = (units + 1) / 2;
-  k.ws = (float*)d->workspace;
-  k.cnt = nullptr;
-  k.ksplit = (d->workspace && bm == 128) ? pick_ksplit((long long)nbm * k.nbn, nstages, k.M, d->Cout,
-                                                       d->workspace_bytes > 4096 ? (size_t)d->workspace_bytes - 4096 : 0) : 1;
-  k.stages_per_split = (nstages + k.ksplit - 1) / k.ksplit;
-  k.ksplit = (nstages + k.stages_per_split - 1) / k.stages_per_split;
-  g_last_ksplit = k.ksplit;
   // Kernel choice (measured per level, scratch/bench_conv.py): the LDS-DMA kernel wins where K is long and the grid is
   // small (Cout >= 128: 5-12 %); the register-staged kernel wins on the two top levels (short K, occupancy-bound) and,
   // with 128-wide tiles, on the very long K of the multi-branch convs at Cout >= 256.
-  if (pick_dma(d, bn)) return dispatch_conv_dma(k, bm, bn, nbm, st);
-  if (d->dtype == RUA_BF16) return dispatch_conv<bf16_t>(k, bm, bn, nbm, st);
-  return dispatch_conv<float>(k, bm, bn, nbm, st);
-}
-
-// ---- grouped launch --------------------------------------------------------------------------------------------------
-// rua_conv_fwd_group: n INDEPENDENT convolutions (the dilation branches of a ResBlock: model2.py:26-31).  Every member goes
-// through rua_conv_fwd's own dispatch with the launchers in capture mode; members that land on the same kernel with the same
-// grid are then issued as ONE grid (blockIdx.y = member), the rest one by one.  Results are those of n separate calls.
-thread_local ConvGroupCapture* g_conv_group = nullptr;
-static thread_local int g_group_last_grids = 0;
-static thread_local int g_group_last_band = 0;
-extern "C" int rua_conv_group_last_grids(void) { return g_group_last_grids; }
-static thread_local int g_group_last_chain = 0;
-extern "C" int rua_conv_group_last_chain(void) { return g_group_last_chain; }    // members the latest rua_conv_fwd_group ran back to back inside one conv_dmap_chain grid (0: none)
-extern "C" int rua_conv_group_last_band(void) { return g_group_last_band; }      // 1: the calling thread's latest rua_conv_fwd_group ran as one conv_band64m launch
-// would rua_conv_fwd_group run these members as one conv_band64m launch (which honours in_fold / in_scale of every member)?
-extern "C" int rua_conv_group_band_ok(const rua_conv_desc* d, int n) { return (d && (rua_band64m_ok(d, n) || rua_band128m_ok(d, n))) ? 1 : 0; }   // grids the calling thread's latest rua_conv_fwd_group issued (1: one grid for all members)
-
-template <typename KG, typename F1, typename FG>
-static int issue_group(const ConvGroupCapture& c, const int* idx, int m, F1 single, FG grouped, int smem_attr, hipStream_t st, const char* what) {
-  if (m == 1) {
-    hipLaunchKernelGGL(single, dim3(c.grid[idx[0]]), dim3(256), c.smem[idx[0]], st, c.k[idx[0]]);
-  } else {
-    static RuaPerDevFlag attr[8];                        // per device, not per thread (the instantiations of this template are per kernel pair)
-    const int slot = c.kind[idx[0]];
-    if (!attr[slot].get()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(grouped), hipFuncAttributeMaxDynamicSharedMemorySize, smem_attr); attr[slot].get() = true; }
-    KG g;
-    for (int i = 0; i < m; ++i) g.k[i] = c.k[idx[i]];
-    hipLaunchKernelGGL(grouped, dim3(c.grid[idx[0]], m), dim3(256), c.smem[idx[0]], st, g);
+  // split-K invariant: the workspace is all zeros on entry (caller zero-fills it once) and the finisher writes the
+  // zeros back after consuming the sums, so no memset is launched per convolution.
+  L->finisher = t.ksplit > 1 ? (d->dtype == RUA_BF16 ? 1 : 2) : 0;
+  if (L->kid == 1) {
+    L->kernel = CK_DMA + tile_form(t.bm, t.bn);
+    L->smem = conv_row(L->kernel).lds;
+    return RUA_OK;
   }
-  RUA_LAUNCH_CHECK(what);
+  L->kernel = (d->dtype == RUA_BF16 ? CK_IGEMM_BF16 : CK_IGEMM_F32) + tile_form(t.bm, t.bn);
+  L->smem = conv_row(L->kernel).lds - RUA_MAX_UNITS * 16 + ((k.nunits * 16 + 255) / 256) * 256;     // unit table sized to this launch
+  L->groupable = in_group && (g_tune.conv_group & 2) && t.ksplit == 1 && L->kernel == CK_IGEMM_BF16 + 3;
   return RUA_OK;
 }
 
-// conv_dmap_chain: the captured conv_dmap members as ONE grid of the members' common size, every block walking all of them
-static bool chain_ok(const ConvGroupCapture& c, const int* idx, int m) {
-  const ConvK& a = c.k[idx[0]];
-  for (int i = 0; i < m; ++i) {
-    const ConvK& k = c.k[idx[i]];
+// ---- issuing -----------------------------------------------------------------------------------------------------------
+// One launch for m >= 1 plans on the SAME row.  One plan: the kernel itself, with the plan's own grid and LDS.  Several: its grouped form - blockIdx.y picks the
+// member, the grid and the LDS are the largest member's (the others' surplus blocks leave at once; conv_strip32 rounds the grid up to a multiple
+// of 8), unused slots repeat member 0 - or, chain, conv_dmap_chain: ONE grid of the members' common size, every block walking all of them.
+// conv_strip32s is one grid whatever m is (rua_strip_s_pack).
+struct ConvPacked {
+  const ConvKernelRow* row; const void* fn; int form;   // form: 0 the kernel, 1 its grouped form, 2 its chain form
+  dim3 grid; unsigned block; int smem, nmem;
+  void* args[2];
+  union alignas(16) { ConvKG c; PwKG<2> p; StripKG s; unsigned char raw[4096]; } many;
+};
+static int conv_pack(const ConvLaunch* const* L, int m, bool chain, ConvPacked* P) {
+  const ConvLaunch& first = *L[0];
+  const ConvKernelRow& row = conv_row(first.kernel);
+  P->row = &row; P->form = chain ? 2 : m > 1 ? 1 : 0;
+  P->fn = chain ? row.chain : m > 1 ? row.many : row.one;
+  RUA_CHECK_ARG(P->fn && m <= RUA_MAX_BRANCH, "rua_conv_fwd_group: %d members of %s in one grid", m, row.name);
+  P->grid = dim3(first.gx); P->block = first.block; P->smem = first.smem; P->nmem = m;
+  P->args[0] = row.args == CA_IMG2 ? const_cast<void*>(static_cast<const void*>(&first.i2)) : const_cast<void*>(static_cast<const void*>(&first.a));
+  P->args[1] = &P->nmem;
+  if (row.args == CA_STRIPS) { P->args[0] = &P->many; return rua_strip_s_pack(L, m, &P->many, &P->grid.x, &P->smem); }
+  if (m == 1) return RUA_OK;
+  for (int i = 0; i < RUA_MAX_BRANCH; ++i) {
+    const ConvLaunch& x = *L[i < m ? i : 0];
+    if (x.gx > P->grid.x) P->grid.x = x.gx;
+    if (x.smem > P->smem) P->smem = x.smem;
+    if (row.args == CA_CONV) P->many.c.k[i] = x.a.c; else if (row.args == CA_PW2) P->many.p.k[i] = x.a.p2; else P->many.s.k[i] = x.a.s;
+  }
+  if (row.args == CA_STRIP) P->grid.x = (P->grid.x + 7) / 8 * 8;
+  if (chain) P->smem = row.lds_chain; else P->grid.y = m;
+  P->args[0] = &P->many;
+  return RUA_OK;
+}
+static int conv_issue(const ConvLaunch* const* L, int m, bool chain, hipStream_t st) {
+  ConvPacked P;
+  const int rc = conv_pack(L, m, chain, &P);
+  if (rc != RUA_OK) return rc;
+  static RuaPerDevFlag allowed[CK_KERNELS][3];          // hipFuncSetAttribute: once per (kernel, form, device)
+  bool& ok = allowed[L[0]->kernel][P.form].get();
+  const int lds = chain ? P.row->lds_chain : P.row->lds;
+  if (!ok && lds) (void)hipFuncSetAttribute(P.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  ok = true;
+  (void)hipLaunchKernel(P.fn, P.grid, dim3(P.block), P.args, (size_t)P.smem, st);
+  RUA_LAUNCH_CHECK(P.row->name);
+  return RUA_OK;
+}
+// a plan on its own: a route's launcher, or its grid and then its finisher over the K slices' slabs
+static int conv_issue_alone(const rua_conv_desc* d, const ConvLaunch& L, hipStream_t st) {
+  if (L.route == CONV_ROUTE_BAND128_SUM) return rua_launch_band128_sum(d, st);
+  const ConvLaunch* one = &L;
+  const int rc = conv_issue(&one, 1, false, st);
+  if (rc != RUA_OK || !L.finisher) return rc;
+  if (L.finisher == 2) launch_splitk_finish<float>(L.a.c, st); else launch_splitk_finish<bf16_t>(L.a.c, st);
+  RUA_LAUNCH_CHECK("conv_splitk_finish");
+  return RUA_OK;
+}
+
+// ---- groups ------------------------------------------------------------------------------------------------------------
+// rua_conv_fwd_group: n INDEPENDENT convolutions (the dilation branches of a ResBlock: model2.py:26-31).  Every member is planned as rua_conv_fwd would plan it,
+// told that it shares the chip; members that land on the same kernel with the same grid are then issued as ONE grid (blockIdx.y = member), the rest one by
+// one.  Results are those of n separate calls.  Nothing is launched before every member has a plan.
+struct ConvBatch { int idx[RUA_MAX_BRANCH]; int m; bool chain; };                // members of one launch
+struct ConvGroupPlan { ConvLaunch L[RUA_MAX_BRANCH]; ConvBatch b[RUA_MAX_BRANCH]; int nb, band, chain; };     // band: 1 conv_band64m / 2 conv_band128m takes the whole call (nb = 0)
+
+// conv_dmap_chain wants members of one shape
+static bool chain_ok(const ConvLaunch* L, const ConvBatch& b) {
+  const ConvK& a = L[b.idx[0]].a.c;
+  for (int i = 0; i < b.m; ++i) {
+    const ConvK& k = L[b.idx[i]].a.c;
     if (k.ksplit != 1 || k.M != a.M || k.Cout != a.Cout || k.nbm != a.nbm || k.nbn != a.nbn || k.H != a.H || k.W != a.W || k.stride != a.stride) return false;
   }
   return true;
 }
-template <typename FC>
-static int issue_chain(const ConvGroupCapture& c, const int* idx, int m, FC kern, int smem, int slot, hipStream_t st) {
-  static RuaPerDevFlag attr[2];
-  if (!attr[slot].get()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr[slot].get() = true; }
-  ConvKG g;
-  for (int i = 0; i < m; ++i) g.k[i] = c.k[idx[i]];
-  hipLaunchKernelGGL(kern, dim3(c.grid[idx[0]]), dim3(256), smem, st, g, m);
-  RUA_LAUNCH_CHECK("conv_dmap_chain");
+// The launches of a group, in issue order: (1) members that go alone, in member order; (2) the conv_pw grids, non-dense then dense (grids of unequal size: the
+// largest member's); (3) the conv_strip grids, by first member - one row and one blocks-per-CU class each; (4) the other grouped kinds by first member:
+// conv_small all together (unequal grids), conv_dmap / conv_igemm members of equal grid and LDS - as a chain where the tuning key dmap_chain asks for it.
+static void conv_partition(ConvGroupPlan* P, int n) {
+  const ConvLaunch* L = P->L;
+  bool done[RUA_MAX_BRANCH] = {false};
+  P->nb = 0; P->chain = 0;
+  auto collect = [&](int from, auto&& same) -> ConvBatch* {          // the members from `from` on that no launch has yet and `same` accepts: one more launch, or none
+    ConvBatch b;
+    b.m = 0; b.chain = false;
+    for (int j = from; j < n; ++j)
+      if (!done[j] && same(L[j])) { b.idx[b.m++] = j; done[j] = true; }
+    if (!b.m) return nullptr;
+    P->b[P->nb] = b;
+    return &P->b[P->nb++];
+  };
+  for (int i = 0; i < n; ++i)
+    if (!L[i].groupable) { ConvBatch& b = P->b[P->nb++]; b.idx[0] = i; b.m = 1; b.chain = false; done[i] = true; }
+  for (int kern = CK_PW2; kern <= CK_PW2_DENSE; ++kern) collect(0, [&](const ConvLaunch& x) { return x.kernel == kern; });
+  for (int i = 0; i < n; ++i)
+    if (!done[i] && L[i].kernel >= CK_STRIP) collect(i, [&](const ConvLaunch& x) { return x.kernel == L[i].kernel && x.per_cu == L[i].per_cu; });
+  for (int i = 0; i < n; ++i) {
+    if (done[i]) continue;
+    if (L[i].kernel == CK_SMALL) { collect(i, [&](const ConvLaunch& x) { return x.kernel == CK_SMALL; }); continue; }
+    ConvBatch& b = *collect(i, [&](const ConvLaunch& x) { return x.kernel == L[i].kernel && x.gx == L[i].gx && x.smem == L[i].smem; });      // (member i itself, at the least)
+    const int bit = L[i].kernel == CK_DMAP128 ? 1 : L[i].kernel == CK_DMAP64 ? 2 : 0;
+    b.chain = b.m >= 2 && (g_tune.dmap_chain & bit) && chain_ok(L, b);
+    if (b.chain) P->chain = b.m;
+  }
+}
+static int conv_plan_group(const rua_conv_desc* d, int n, ConvGroupPlan* P) {
+  RUA_CHECK_ARG(d && n >= 1 && n <= RUA_MAX_BRANCH, "rua_conv_fwd_group: 1..%d members", RUA_MAX_BRANCH);
+  P->nb = 0; P->chain = 0;
+  P->band = (n >= 2 && rua_band128m_ok(d, n)) ? 2      // C = 128 / C = 64 on whole rows: two-row stages, weights of a kernel row in registers (conv_band128.hip)
+          : rua_band64m_ok(d, n) ? 1 : 0;              // the C = 64 level, round-3 form: one row-streaming launch for all members (conv_band64.hip)
+  if (P->band) return RUA_OK;
+  const bool in_group = n >= 2 && g_tune.conv_group != 0;
+  for (int i = 0; i < n; ++i) {
+    const int rc = conv_plan_one(d + i, in_group ? n : 1, in_group, &P->L[i]);
+    if (rc != RUA_OK) return rc;
+  }
+  conv_partition(P, n);
   return RUA_OK;
 }
 
+// ---- exports -----------------------------------------------------------------------------------------------------------
+static thread_local int g_last_ksplit = 1;
+static thread_local int g_group_last_grids = 0, g_group_last_band = 0, g_group_last_chain = 0;
+extern "C" int rua_conv_last_ksplit(void) { return g_last_ksplit; }    // K slices of this thread's latest rua_conv_fwd launch (1: no finisher ran)
+extern "C" int rua_conv_group_last_grids(void) { return g_group_last_grids; }    // grids the calling thread's latest rua_conv_fwd_group issued (1: one grid for all members)
+extern "C" int rua_conv_group_last_chain(void) { return g_group_last_chain; }    // members the latest rua_conv_fwd_group ran back to back inside one conv_dmap_chain grid (0: none)
+extern "C" int rua_conv_group_last_band(void) { return g_group_last_band; }      // 1: the calling thread's latest rua_conv_fwd_group ran as one conv_band64m launch, 2: conv_band128m
+// would rua_conv_fwd_group run these members as one conv_band64m / conv_band128m launch (which honours in_fold / in_scale of every member)?
+extern "C" int rua_conv_group_band_ok(const rua_conv_desc* d, int n) { return (d && (rua_band64m_ok(d, n) || rua_band128m_ok(d, n))) ? 1 : 0; }
+
+extern "C" int rua_conv_fwd(const rua_conv_desc* d, void* stream) {
+  ConvLaunch L;
+  const int rc = conv_plan_one(d, 1, false, &L);
+  if (rc != RUA_OK) return rc;
+  g_last_ksplit = L.ksplit;
+  return conv_issue_alone(d, L, (hipStream_t)stream);
+}
 extern "C" int rua_conv_fwd_group(const rua_conv_desc* d, int n, void* stream) {
-  RUA_CHECK_ARG(d && n >= 1 && n <= RUA_MAX_BRANCH, "rua_conv_fwd_group: 1..%d members", RUA_MAX_BRANCH);
+  ConvGroupPlan P;
+  int rc = conv_plan_group(d, n, &P);
+  if (rc != RUA_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   g_group_last_grids = n;
   g_group_last_band = 0;
-  g_group_last_chain = 0;
-  if (n >= 2 && rua_band128m_ok(d, n)) {                    // C = 128 / C = 64 on whole rows: two-row stages, weights of a kernel row in registers (conv_band128.hip)
-    const int rc = rua_launch_band128m(d, n, st);
-    if (rc == RUA_OK) { g_group_last_grids = 1; g_group_last_band = 2; }
+  g_group_last_chain = P.chain;
+  if (P.band) {
+    rc = P.band == 2 ? rua_launch_band128m(d, n, st) : rua_launch_band64m(d, n, st);
+    if (rc == RUA_OK) { g_group_last_grids = 1; g_group_last_band = P.band; }
     return rc;
   }
-  if (rua_band64m_ok(d, n)) {                               // the C = 64 level, round-3 form: one row-streaming launch for all members (conv_band64.hip)
-    const int rc = rua_launch_band64m(d, n, st);
-    if (rc == RUA_OK) { g_group_last_grids = 1; g_group_last_band = 1; }
-    return rc;
+  for (int b = 0; b < P.nb; ++b) {
+    const ConvBatch& B = P.b[b];
+    const ConvLaunch* mem[RUA_MAX_BRANCH];
+    for (int i = 0; i < B.m; ++i) mem[i] = &P.L[B.idx[i]];
+    rc = B.m == 1 ? conv_issue_alone(d + B.idx[0], *mem[0], st) : conv_issue(mem, B.m, B.chain, st);
+    if (rc != RUA_OK) return rc;
   }
-  if (n == 1 || !g_tune.conv_group) {
-    for (int i = 0; i < n; ++i) { const int rc = rua_conv_fwd(d + i, stream); if (rc != RUA_OK) return rc; }
+  g_last_ksplit = P.L[n - 1].ksplit;
+  g_group_last_grids = P.nb;
+  return RUA_OK;
+}
+
+static void conv_report(const ConvLaunch& L, const ConvPacked* P, unsigned members, const ConvGroupPlan* G, rua_conv_launch_info* o) {
+  memset(o, 0, sizeof(*o));
+  o->kernel_id = L.kid; o->form = P ? L.kernel : -1;
+  if (P) { o->grid_x = (int)P->grid.x; o->grid_y = (int)P->grid.y; o->block = (int)P->block; o->lds_bytes = P->smem; }
+  o->bm = L.bm; o->bn = L.bn; o->ksplit = L.ksplit; o->finisher = L.finisher ? 1 : 0;
+  o->members = (int)members;
+  if (G) { o->band = G->band; o->chain = G->chain; }
+}
+extern "C" int rua_conv_plan(const rua_conv_desc* d, rua_conv_launch_info* out) {
+  RUA_CHECK_ARG(out, "rua_conv_plan: null pointer");
+  ConvLaunch L;
+  ConvPacked P;
+  const ConvLaunch* one = &L;
+  int rc = conv_plan_one(d, 1, false, &L);
+  if (rc == RUA_OK && L.route == CONV_LAUNCH) rc = conv_pack(&one, 1, false, &P);
+  if (rc == RUA_OK) conv_report(L, L.route == CONV_LAUNCH ? &P : nullptr, 1u, nullptr, out);
+  return rc;
+}
+extern "C" int rua_conv_group_plan(const rua_conv_desc* d, int n, rua_conv_launch_info* out, int* n_out) {
+  RUA_CHECK_ARG(out && n_out, "rua_conv_group_plan: null pointer");
+  ConvGroupPlan G;
+  int rc = conv_plan_group(d, n, &G);
+  if (rc != RUA_OK) return rc;
+  if (G.band) {                                         // the whole call is one launch of conv_band64.hip / conv_band128.hip
+    memset(out, 0, sizeof(*out));
+    out->kernel_id = -1; out->form = -1; out->members = (1 << n) - 1; out->band = G.band;
+    *n_out = 1;
     return RUA_OK;
   }
-  ConvGroupCapture cap;
-  cap.n = 0;
-  cap.members = n;
-  PwGroupCapture pwc;
-  pwc.n = 0;
-  rua_strip_group_reset();                                  // nothing stale from a group that failed half-way
-  g_conv_group = &cap;
-  g_pw_group = (g_tune.conv_group & 32) ? &pwc : nullptr;
-  int rc = RUA_OK;
-  for (int i = 0; i < n && rc == RUA_OK; ++i) rc = rua_conv_fwd(d + i, stream);      // non-groupable members launch right here
-  g_conv_group = nullptr;
-  g_pw_group = nullptr;
-  if (rc != RUA_OK) { rua_strip_group_reset(); return rc; }  // captured members are dropped, not issued by the next group
-  int grids = n - cap.n - pwc.n - rua_strip_group_pending();        // members no launcher captured were launched one by one above
-  for (int dense = 0; dense < 2; ++dense) {                 // conv_pw members: one grid per addressing form
-    PwKG<2> g; int m = 0; unsigned gx = 0;
-    for (int i = 0; i < pwc.n; ++i) if ((int)pwc.dense[i] == dense) { g.k[m++] = pwc.k[i]; if ((unsigned)pwc.k[i].nblk > gx) gx = (unsigned)pwc.k[i].nblk; }
-    if (m == 0) continue;
-    for (int i = m; i < RUA_MAX_BRANCH; ++i) g.k[i] = g.k[0];
-    if (m == 1) { if (dense) hipLaunchKernelGGL((conv_pw<2, true>), dim3(gx), dim3(256), 0, st, g.k[0]); else hipLaunchKernelGGL((conv_pw<2, false>), dim3(gx), dim3(256), 0, st, g.k[0]); }
-    else if (dense) hipLaunchKernelGGL((conv_pw_g<2, true>), dim3(gx, m), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((conv_pw_g<2, false>), dim3(gx, m), dim3(256), 0, st, g);
-    RUA_LAUNCH_CHECK("conv_pw (group)");
-    ++grids;
+  for (int b = 0; b < G.nb; ++b) {
+    const ConvBatch& B = G.b[b];
+    const ConvLaunch* mem[RUA_MAX_BRANCH];
+    unsigned mask = 0;
+    for (int i = 0; i < B.m; ++i) { mem[i] = &G.L[B.idx[i]]; mask |= 1u << B.idx[i]; }
+    ConvPacked P;
+    const bool launch = mem[0]->route == CONV_LAUNCH;
+    if (launch && (rc = conv_pack(mem, B.m, B.chain, &P)) != RUA_OK) return rc;
+    conv_report(*mem[0], launch ? &P : nullptr, mask, &G, out + b);
   }
-  rc = rua_strip_group_flush(st, &grids);
-  if (rc != RUA_OK) return rc;
-  bool done[RUA_MAX_BRANCH] = {false};
-  for (int i = 0; i < cap.n; ++i) {
-    if (done[i]) continue;
-    int idx[RUA_MAX_BRANCH], m = 0;
-    if (cap.kind[i] == 7) {                                 // conv_small: members of unequal grids share one launch (the grid of the largest)
-      unsigned gmax = 0;
-      for (int j = i; j < cap.n; ++j)
-        if (!done[j] && cap.kind[j] == 7) { idx[m++] = j; done[j] = true; if (cap.grid[j] > gmax) gmax = cap.grid[j]; }
-      if (m == 1) hipLaunchKernelGGL((conv_small<2>), dim3(cap.grid[idx[0]]), dim3(256), cap.smem[idx[0]], st, cap.k[idx[0]]);
-      else { ConvKG g; for (int q = 0; q < m; ++q) g.k[q] = cap.k[idx[q]]; hipLaunchKernelGGL((conv_small_g<2>), dim3(gmax, m), dim3(256), cap.smem[idx[0]], st, g); }
-      RUA_LAUNCH_CHECK("conv_small (group)");
-      ++grids;
-      continue;
-    }
-    for (int j = i; j < cap.n; ++j)
-      if (!done[j] && cap.kind[j] == cap.kind[i] && cap.grid[j] == cap.grid[i] && cap.smem[j] == cap.smem[i]) { idx[m++] = j; done[j] = true; }
-    const bool chain = m >= 2 && (cap.kind[i] == 1 || cap.kind[i] == 2) && (g_tune.dmap_chain & cap.kind[i]) && chain_ok(cap, idx, m);
-    if (chain) g_group_last_chain = m;
-    if (chain && cap.kind[i] == 1) rc = issue_chain(cap, idx, m, conv_dmap_chain<128, 128, 64>, conv_dmap_chain_smem<128, 128>(), 0, st);
-    else if (chain) rc = issue_chain(cap, idx, m, conv_dmap_chain<64, 128, 64>, conv_dmap_chain_smem<64, 128>(), 1, st);
-    else if (cap.kind[i] == 1) rc = issue_group<ConvKG>(cap, idx, m, conv_dmap<128, 128, 64>, conv_dmap_g<128, 128, 64>, conv_dmap_smem<128, 128>(), st, "conv_dmap (group)");
-    else if (cap.kind[i] == 6) rc = issue_group<ConvKG>(cap, idx, m, conv_dmap_s<128, 128, 64>, conv_dmap_gs<128, 128, 64>, conv_dmap_smem<128, 128, 4>(), st, "conv_dmap_s (group)");
-    else if (cap.kind[i] == 2) rc = issue_group<ConvKG>(cap, idx, m, conv_dmap<64, 128, 64>, conv_dmap_g<64, 128, 64>, conv_dmap_smem<64, 128>(), st, "conv_dmap (group)");
-    else rc = issue_group<ConvKG>(cap, idx, m, conv_igemm<bf16_t, 256, 64>, conv_igemm_g<bf16_t, 256, 64>, conv_smem<bf16_t, 256, 64>(), st, "conv_igemm (group)");
-    if (rc != RUA_OK) return rc;
-    ++grids;
-  }
-  g_group_last_grids = grids;
+  *n_out = G.nb;
   return RUA_OK;
 }
 
@@ -2253,43 +2259,33 @@ extern "C" int64_t rua_conv_workspace_bytes(const rua_conv_desc* d) {
   if (!d) return 0;
   return (int64_t)d->N * d->H * d->W * d->Cout * (int64_t)sizeof(float);
 }
-
-// tile width (output channels per block) the launcher picks for a descriptor: identifies the kernel instantiation
-extern "C" int rua_conv_tile_bn(const rua_conv_desc* d) {
-  if (!d) return RUA_ERR_ARG;
-  if (pick_dmap(d)) return 128;
-  return pick_bn(d, (long long)d->N * d->H * d->W);
-}
-extern "C" int rua_conv_fused_input_ok(const rua_conv_desc* d) { return (d && rua_pick_strip(d)) ? 1 : 0; }
-
+// The queries below answer for any descriptor - before its buffers exist, too - from the pickers conv_plan_one itself calls.
 // 0: conv_igemm (register-staged), 1: conv_dma (LDS-DMA), 2: conv_dmap (LDS-DMA, pipelined across the stage barrier),
 // 3: conv_halo (input + halo resident in LDS, lattice tiles), 4: conv_pw (narrow 1x1, per-wave streaming), 5: conv_strip (conv_strip.hip),
 // 6: conv_small (1x1 over few pixels, no K split), 7: conv_img (whole image resident in LDS), 8: conv_img2 (conv_img2.hip),
 // 9: conv_band128m's form of several summed 3x3 segments (conv_band128.hip)
 extern "C" int rua_conv_kernel_id(const rua_conv_desc* d) {
+  int ks;
+  return d ? conv_pick(d, false, &ks) : RUA_ERR_ARG;
+}
+extern "C" int rua_conv_fused_input_ok(const rua_conv_desc* d) { return (d && rua_pick_strip(d)) ? 1 : 0; }
+// tile (pixel rows, output channels per block) of the tiled kernels: identifies the kernel instantiation
+extern "C" int rua_conv_tile_bn(const rua_conv_desc* d) {
   if (!d) return RUA_ERR_ARG;
-  if (rua_pick_strip(d)) return 5;
-  if (pick_halo(d)) return 3;
-  if (pick_pw(d)) return 4;
-  if (pick_small(d)) return 6;
-  if (rua_pick_img2(d)) return 8;
-  if (!g_conv_group && rua_band128_sum_ok(d)) return 9;
-  if (pick_img(d)) return 7;
-  if (pick_dmap(d)) return 2;
-  return pick_dma(d, pick_bn(d, (long long)d->N * d->H * d->W)) ? 1 : 0;
+  ConvTiling t;
+  conv_tiling(d, &t);
+  return t.bn;
 }
 extern "C" int rua_conv_tile_bm(const rua_conv_desc* d) {
   if (!d) return RUA_ERR_ARG;
-  const long long M = (long long)d->N * d->H * d->W;
-  if (pick_dmap(d)) {                                   // mirrors the launcher: 64-row tiles in the unsplit half-chip case
-    const int target = g_tune.dmap_target > 0 ? g_tune.dmap_target : rua_cu_count();
-    const int bm64 = g_tune.dmap_bm64;
-    const long long tiles = ((M + 127) / 128) * ((d->Cout + 127) / 128);
-    int units = 0;
-    for (int i = 0; i < d->nseg; ++i) units += d->seg[i].taps * (d->seg[i].C / 32);
-    const bool split = d->workspace && d->workspace_bytes > 4096 &&
-                       (size_t)(d->workspace_bytes - 4096) / ((size_t)M * d->Cout * sizeof(float)) >= 2 && units / 2 > 40;
-    return (bm64 && !split && tiles < target && tiles * 2 >= target) ? 64 : 128;
-  }
-  return pick_bm(d, M, pick_bn(d, M));
+  ConvTiling t;
+  conv_tiling(d, &t);
+  return t.bm;
 }
+// LDS of the conv_igemm instantiation with the tile pick_bn / pick_bm choose (the unit table at its capacity)
+extern "C" int rua_conv_smem_bytes(const rua_conv_desc* d) {
+  const long long M = (long long)d->N * d->H * d->W;
+  const int bn = pick_bn(d, M), bm = pick_bm(d, M, bn);
+  return CONV_ROWS[(d->dtype == RUA_BF16 ? CK_IGEMM_BF16 : CK_IGEMM_F32) + tile_form(bm, bn)].lds;
+}
+

@@ -28,15 +28,7 @@
 #include "common.h"
 #include <type_traits>
 
-struct StripK {
-  ConvK c;
-  const unsigned char* ep;                // epilogue stream: aux (aux_mode 1 / 2) or the old output (accumulate); null: none
-  unsigned epbytes;
-  int d, strips, spc, seglen, njobs, nchains;
-  int slot_bytes, SWH;                    // bytes of one x-ring slot (multiple of 1024), pixels per slot row (SW + 2 d)
-  int dbg;                                // experiments (tuning key band_dbg; conv_strip32s): 1 no stages (prologue + tail only), 2 no row DMAs in the prologue
-  int has_fold; rua_bn_fold f;            // BatchNorm coefficients derived in the prologue from the input's statistics (in_fold)
-};
+// StripK: common.h
 
 template <int NW, bool HAS_EP, int R>
 __device__ __forceinline__ void conv_strip32_body(const StripK& q) {
@@ -383,8 +375,6 @@ __device__ __forceinline__ void conv_strip32_body(const StripK& q) {
   }
 }
 
-struct StripKG { StripK k[RUA_MAX_BRANCH]; };
-static_assert(sizeof(StripKG) <= 4096, "a grouped launch passes its members by value: HIP kernel arguments are limited to 4 KiB");
 template <int NW, bool HAS_EP, int R> __global__ __launch_bounds__(NW * 64) void conv_strip32(const StripK q) { conv_strip32_body<NW, HAS_EP, R>(q); }
 // grouped launch (rua_conv_fwd_group): the four dilation branches of the d6 block in one grid, blockIdx.y = branch
 template <int NW, bool HAS_EP, int R> __global__ __launch_bounds__(NW * 64) void conv_strip32_g(const StripKG g) { conv_strip32_body<NW, HAS_EP, R>(g.k[blockIdx.y]); }
@@ -411,67 +401,7 @@ bool rua_pick_strip(const rua_conv_desc* d) {
   return true;
 }
 
-// members captured while rua_conv_fwd_group runs its members' dispatch (see conv_mfma.hip)
-struct StripCapture { int n; int variant[RUA_MAX_BRANCH]; int smem[RUA_MAX_BRANCH]; StripK k[RUA_MAX_BRANCH]; };
-static thread_local StripCapture g_strip_cap = {0, {0}, {0}, {}};
-
-template <int NW, bool HAS_EP, int R> static int launch_strip_members(const StripK* ks, const int* smems, int m, hipStream_t st) {
-  static RuaPerDevFlag attr_, attr_g_;
-  bool &attr = attr_.get(), &attr_g = attr_g_.get();
-  if (m == 1) {
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_strip32<NW, HAS_EP, R>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-    hipLaunchKernelGGL((conv_strip32<NW, HAS_EP, R>), dim3(ks[0].njobs), dim3(NW * 64), smems[0], st, ks[0]);
-  } else {
-    if (!attr_g) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_strip32_g<NW, HAS_EP, R>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_g = true; }
-    StripKG g;
-    int grid = 0, smem = 0;
-    for (int i = 0; i < m; ++i) { g.k[i] = ks[i]; if (ks[i].njobs > grid) grid = ks[i].njobs; if (smems[i] > smem) smem = smems[i]; }
-    hipLaunchKernelGGL((conv_strip32_g<NW, HAS_EP, R>), dim3((grid + 7) / 8 * 8, m), dim3(NW * 64), smem, st, g);
-  }
-  RUA_LAUNCH_CHECK("conv_strip32");
-  return RUA_OK;
-}
-// conv_strip32s: ONE grid for all members (a lone convolution is a group of one); the members' row stages form one line of cost units
-// that the blocks - one per CU - cut into equal pieces (conv_strip2.inc)
-template <int NW, int IN, int EP, int ST, int ORELU, int R, int BIAS> static int launch_strip_s(const StripK* ks, const int* smems, int m, hipStream_t st) {
-  static RuaPerDevFlag attr_;
-  bool& attr = attr_.get();
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_strip32s_g<NW, IN, EP, ST, ORELU, R, BIAS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_strip32s<NW, IN, EP, ST, ORELU, R, BIAS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  StripSG g;
-  memset(&g, 0, sizeof(g));
-  int smem = 0;
-  g.nmem = m; g.N = ks[0].c.N; g.H = ks[0].c.H; g.dbg = ks[0].dbg;
-  g.c0 = 3;                                             // a restart: three rows of DMA latency, their BatchNorm, two barriers - about three row stages
-  g.tbytes = (unsigned)((size_t)ks[0].c.M * 64);
-  int units = 0;
-  for (int i = 0; i < m; ++i) {
-    const StripK& k = ks[i];
-    RUA_CHECK_ARG(k.c.N == g.N && k.c.H == g.H && k.c.M == ks[0].c.M, "conv_strip32s: the members of a group differ in shape");
-    StripSM& M = g.m[i];
-    M.x = k.c.seg[0].x; M.w = k.c.seg[0].w; M.y = k.c.y; M.ep = k.ep;
-    M.bias = k.c.bias; for (int r = 0; r < 3; ++r) M.bias_more[r] = k.c.bias_more[r];
-    M.mscale = k.c.mscale; M.mshift = k.c.mshift; M.in_scale = k.c.in_scale; M.in_shift = k.c.in_shift;
-    M.stats = k.c.stats; M.stats_R = k.c.stats_R > 0 ? k.c.stats_R : 1; M.d = k.d; M.has_fold = k.has_fold; M.f = k.f;
-    g.ustart[i] = units;
-    units += g.H + k.d * g.c0;
-    if (smems[i] > smem) smem = smems[i];
-  }
-  g.ustart[m] = units;                                  // the units of one image
-  units *= g.N;
-  int nb = units / (g.c0 + 5);                          // a piece is worth a block's setup from about five row stages on
-  if (nb > rua_cu_count()) nb = rua_cu_count();
-  if (nb < 1) nb = 1;
-  g.nblocks = nb;
-  if (m == 1) hipLaunchKernelGGL((conv_strip32s<NW, IN, EP, ST, ORELU, R, BIAS>), dim3((nb + 7) / 8 * 8), dim3(NW * 64), smem, st, g);
-  else hipLaunchKernelGGL((conv_strip32s_g<NW, IN, EP, ST, ORELU, R, BIAS>), dim3((nb + 7) / 8 * 8), dim3(NW * 64), smem, st, g);
-  RUA_LAUNCH_CHECK("conv_strip32s");
-  return RUA_OK;
-}
-// the (IN, EP, ST, ORELU) forms the step uses; everything else stays on conv_strip32
+// the (IN, EP, ST, ORELU) forms of conv_strip32s that the step uses; everything else stays on conv_strip32
 struct StripSForm { int in, ep, st, orelu, R, bias; };
 static const StripSForm kStripS[] = {
   {1, 0, 1, 0, 6, 1},   // first convs of a ResBlock: BatchNorm + ReLU on load, statistics of the output
@@ -493,54 +423,52 @@ static int strip_s_form(const rua_conv_desc* d) {
         (kStripS[i].bias || !has_bias)) return i;
   return -1;
 }
-static int launch_strip_variant(int variant, const StripK* ks, const int* smems, int m, hipStream_t st) {
-  if (variant >= 16) {
-    const int form = (variant - 16) >> 1;
-    const bool w4 = (variant & 1) != 0;
-#define RUA_STRIP_S(F_, IN_, EP_, ST_, OR_, R_, B_) case F_: return w4 ? launch_strip_s<4, IN_, EP_, ST_, OR_, R_, B_>(ks, smems, m, st) : launch_strip_s<8, IN_, EP_, ST_, OR_, R_, B_>(ks, smems, m, st)
-    switch (form) {
-      RUA_STRIP_S(0, 1, 0, 1, 0, 6, 1);
-      RUA_STRIP_S(1, 1, 0, 0, 0, 6, 1);
-      RUA_STRIP_S(2, 0, 2, 2, 0, 5, 0);
-      RUA_STRIP_S(3, 0, 2, 0, 0, 5, 0);
-      RUA_STRIP_S(4, 0, 0, 0, 1, 6, 1);
-      RUA_STRIP_S(5, 0, 0, 0, 0, 6, 1);
-      RUA_STRIP_S(6, 1, 1, 0, 0, 5, 1);
-      default: RUA_STRIP_S(7, 0, 1, 0, 0, 5, 0);
-    }
-#undef RUA_STRIP_S
+// rows CK_STRIP .. of the kernel table (common.h).  conv_strip32: several members are blockIdx.y of one grid.  conv_strip32s: ONE grid for all members (a lone
+// convolution is a group of one); the members' row stages form one line of cost units that the blocks - one per CU - cut into equal pieces (conv_strip2.inc)
+#define RUA_STRIP_ROW(NW_, EP_, R_) {"conv_strip32", RUA_KERNEL_FN(conv_strip32<NW_, EP_, R_>), RUA_KERNEL_FN(conv_strip32_g<NW_, EP_, R_>), nullptr, CA_STRIP, 160 * 1024, 0}
+#define RUA_STRIP_S_ROWS(...) {"conv_strip32s", RUA_KERNEL_FN(conv_strip32s<8, __VA_ARGS__>), RUA_KERNEL_FN(conv_strip32s_g<8, __VA_ARGS__>), nullptr, CA_STRIPS, 160 * 1024, 0}, \
+                              {"conv_strip32s", RUA_KERNEL_FN(conv_strip32s<4, __VA_ARGS__>), RUA_KERNEL_FN(conv_strip32s_g<4, __VA_ARGS__>), nullptr, CA_STRIPS, 160 * 1024, 0}
+extern const ConvKernelRow RUA_STRIP_ROWS[CK_KERNELS - CK_STRIP] = {
+  RUA_STRIP_ROW(8, true, 5), RUA_STRIP_ROW(8, false, 7), RUA_STRIP_ROW(4, true, 5), RUA_STRIP_ROW(4, false, 7),
+  RUA_STRIP_S_ROWS(1, 0, 1, 0, 6, 1), RUA_STRIP_S_ROWS(1, 0, 0, 0, 6, 1), RUA_STRIP_S_ROWS(0, 2, 2, 0, 5, 0), RUA_STRIP_S_ROWS(0, 2, 0, 0, 5, 0),     // kStripS, in its order
+  RUA_STRIP_S_ROWS(0, 0, 0, 1, 6, 1), RUA_STRIP_S_ROWS(0, 0, 0, 0, 6, 1), RUA_STRIP_S_ROWS(1, 1, 0, 0, 5, 1), RUA_STRIP_S_ROWS(0, 1, 0, 0, 5, 0),
+};
+
+// the StripSG of m conv_strip32s members (plans on the same row), the grid and the LDS of their one launch
+int rua_strip_s_pack(const ConvLaunch* const* L, int m, void* sg, unsigned* gx, int* smem_out) {
+  StripSG& g = *static_cast<StripSG*>(sg);
+  memset(&g, 0, sizeof(g));
+  const StripK& k0 = L[0]->a.s;
+  int smem = 0;
+  g.nmem = m; g.N = k0.c.N; g.H = k0.c.H; g.dbg = k0.dbg;
+  g.c0 = 3;                                             // a restart: three rows of DMA latency, their BatchNorm, two barriers - about three row stages
+  g.tbytes = (unsigned)((size_t)k0.c.M * 64);
+  int units = 0;
+  for (int i = 0; i < m; ++i) {
+    const StripK& k = L[i]->a.s;
+    RUA_CHECK_ARG(k.c.N == g.N && k.c.H == g.H && k.c.M == k0.c.M, "conv_strip32s: the members of a group differ in shape");
+    StripSM& M = g.m[i];
+    M.x = k.c.seg[0].x; M.w = k.c.seg[0].w; M.y = k.c.y; M.ep = k.ep;
+    M.bias = k.c.bias; for (int r = 0; r < 3; ++r) M.bias_more[r] = k.c.bias_more[r];
+    M.mscale = k.c.mscale; M.mshift = k.c.mshift; M.in_scale = k.c.in_scale; M.in_shift = k.c.in_shift;
+    M.stats = k.c.stats; M.stats_R = k.c.stats_R > 0 ? k.c.stats_R : 1; M.d = k.d; M.has_fold = k.has_fold; M.f = k.f;
+    g.ustart[i] = units;
+    units += g.H + k.d * g.c0;
+    if (L[i]->smem > smem) smem = L[i]->smem;
   }
-  switch (variant) {
-    case 0: return launch_strip_members<8, true, 5>(ks, smems, m, st);
-    case 1: return launch_strip_members<8, false, 7>(ks, smems, m, st);
-    case 2: return launch_strip_members<4, true, 5>(ks, smems, m, st);
-    default: return launch_strip_members<4, false, 7>(ks, smems, m, st);
-  }
-}
-int rua_strip_group_pending(void) { return g_strip_cap.n; }
-void rua_strip_group_reset(void) { g_strip_cap.n = 0; }
-int rua_strip_group_flush(hipStream_t st, int* grids) {
-  StripCapture& c = g_strip_cap;
-  bool done[RUA_MAX_BRANCH] = {false};
-  int rc = RUA_OK;
-  for (int i = 0; i < c.n && rc == RUA_OK; ++i) {
-    if (done[i]) continue;
-    StripK ks[RUA_MAX_BRANCH]; int sm[RUA_MAX_BRANCH], m = 0;
-    // one grid takes the largest member's LDS size for every block: only members that keep their own number of blocks per CU
-    // under it go together (128-pixel strips at d = 1 run two blocks per CU, at d = 31 one: grouped, d = 1 lost half its occupancy)
-    const int per_cu = (160 * 1024) / c.smem[i];
-    for (int j = i; j < c.n; ++j)
-      if (!done[j] && c.variant[j] == c.variant[i] && (160 * 1024) / c.smem[j] == per_cu) { ks[m] = c.k[j]; sm[m] = c.smem[j]; ++m; done[j] = true; }
-    rc = launch_strip_variant(c.variant[i], ks, sm, m, st);
-    if (grids) ++*grids;
-  }
-  c.n = 0;
-  return rc;
+  g.ustart[m] = units;                                  // the units of one image
+  units *= g.N;
+  int nb = units / (g.c0 + 5);                          // a piece is worth a block's setup from about five row stages on
+  if (nb > rua_cu_count()) nb = rua_cu_count();
+  if (nb < 1) nb = 1;
+  g.nblocks = nb;
+  *gx = (unsigned)((nb + 7) / 8 * 8); *smem_out = smem;
+  return RUA_OK;
 }
 
-int rua_launch_conv_strip(const ConvK& k, const rua_conv_desc* d, hipStream_t st) {
-  StripK q;
-  q.c = k;
+int rua_plan_conv_strip(const rua_conv_desc* d, int members, bool in_group, ConvLaunch* L) {
+  StripK& q = L->a.s;
+  const ConvK& k = q.c;
   const int sw = strip_width(d), nw = sw / 32, dil = d->seg[0].dil;
   const bool has_ep = d->aux_mode != 0 || d->accumulate;
   q.ep = has_ep ? (d->aux_mode != 0 ? (const unsigned char*)d->aux : (const unsigned char*)d->y) : nullptr;
@@ -556,7 +484,8 @@ int rua_launch_conv_strip(const ConvK& k, const rua_conv_desc* d, hipStream_t st
   // one round of blocks where the chains allow it; the members of a grouped launch share that round (tuning key strip_group_share:
   // four members of 256 blocks each ran four blocks per CU back to back, every one with its own prologue, window fill and
   // statistics fold - longer segments amortise them)
-  const int share = (g_conv_group && (g_tune.conv_group & 1) && g_tune.strip_group_share) ? g_conv_group->members : 1;
+  const bool grouped = in_group && (g_tune.conv_group & 1);
+  const int share = (grouped && g_tune.strip_group_share) ? members : 1;
   int spc = rua_cu_count() / (q.nchains * share);
   if (spc < 1) spc = 1;
   if (spc > (ny + 3) / 4) spc = (ny + 3) / 4;          // >= 4 rows per segment (a segment re-reads two window rows)
@@ -580,12 +509,16 @@ int rua_launch_conv_strip(const ConvK& k, const rua_conv_desc* d, hipStream_t st
     RUA_CHECK_ARG(nw * 2 * 2 * 32 * 8 <= R * q.slot_bytes, "conv_strip: no room for the in_fold scratch");
   } else memset(&q.f, 0, sizeof(q.f));
   RUA_CHECK_ARG(smem <= 160 * 1024, "conv_strip: %d bytes of LDS", smem);
-  const int variant = sform >= 0 ? 16 + sform * 2 + (nw == 4 ? 1 : 0) : (nw == 8 ? 0 : 2) + (has_ep ? 0 : 1);
-  if (g_conv_group && (g_tune.conv_group & 1)) {        // capture mode: issued by rua_strip_group_flush, grouped with its siblings
-    StripCapture& c = g_strip_cap;
-    RUA_CHECK_ARG(c.n < RUA_MAX_BRANCH, "conv_strip: group capture overflow");
-    c.variant[c.n] = variant; c.smem[c.n] = smem; c.k[c.n] = q; ++c.n;
-    return RUA_OK;
+  L->kernel = sform >= 0 ? CK_STRIPS + sform * 2 + (nw == 4 ? 1 : 0) : CK_STRIP + (nw == 8 ? 0 : 2) + (has_ep ? 0 : 1);
+  L->block = (unsigned)(nw * 64); L->smem = smem; L->gx = (unsigned)q.njobs;
+  // one grid takes the largest member's LDS size for every block: only members that keep their own number of blocks per CU
+  // under it go together (128-pixel strips at d = 1 run two blocks per CU, at d = 31 one: grouped, d = 1 lost half its occupancy)
+  L->per_cu = (160 * 1024) / smem;
+  L->groupable = grouped;
+  if (sform >= 0) {                                     // its grid on its own (a group's: rua_strip_s_pack over its members)
+    StripSG g; int sm;
+    const ConvLaunch* one = L;
+    return rua_strip_s_pack(&one, 1, &g, &L->gx, &sm);
   }
-  return launch_strip_variant(variant, &q, &smem, 1, st);
+  return RUA_OK;
 }

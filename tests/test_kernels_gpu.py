@@ -38,6 +38,28 @@ def tol(dt):
     return 2e-2 if dt == L.RUA_BF16 else 2e-5
 
 
+def fwd_planned(lib, d):
+    """rua_conv_fwd, and the K slices it took are those rua_conv_plan reports for the descriptor"""
+    info = L.ConvLaunchInfo()
+    lib.call("rua_conv_plan", C.byref(d), C.byref(info))
+    lib.call("rua_conv_fwd", C.byref(d), stream())
+    assert lib.raw("rua_conv_last_ksplit")() == info.ksplit
+    assert info.kernel_id == lib.raw("rua_conv_kernel_id")(C.byref(d)) and info.finisher == (1 if info.ksplit > 1 else 0)
+
+
+def group_planned(lib, arr, n):
+    """rua_conv_fwd_group, and its launch count, chain and band are those rua_conv_group_plan reports for the descriptors; returns the planned launches"""
+    out, n_out = (L.ConvLaunchInfo * n)(), C.c_int32(-1)
+    lib.call("rua_conv_group_plan", arr, n, out, C.byref(n_out))
+    lib.call("rua_conv_fwd_group", arr, n, stream())
+    assert 1 <= n_out.value <= n
+    assert lib.raw("rua_conv_group_last_grids")() == n_out.value
+    assert lib.raw("rua_conv_group_last_chain")() == out[0].chain and lib.raw("rua_conv_group_last_band")() == out[0].band
+    masks = [out[i].members for i in range(n_out.value)]
+    assert sum(masks) == (1 << n) - 1 and all(a & b == 0 for i, a in enumerate(masks) for b in masks[i + 1:])
+    return [out[i] for i in range(n_out.value)]
+
+
 def rnd(dt, a):
     """what the device sees after storage rounding"""
     t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
@@ -1434,7 +1456,7 @@ def _group_equals_separate(shape):
         descs.append(d)
     sep = []
     for d in descs:
-        lib.call("rua_conv_fwd", C.byref(d), stream())
+        fwd_planned(lib, d)
     split = lib.raw("rua_conv_last_ksplit")() > 1               # K-split members are launched one by one
     torch.cuda.synchronize()
     for i in range(len(dils)):
@@ -1443,7 +1465,7 @@ def _group_equals_separate(shape):
     arr = (L.ConvDesc * len(descs))()
     for i, d in enumerate(descs):
         C.memmove(C.byref(arr, i * C.sizeof(L.ConvDesc)), C.byref(d), C.sizeof(L.ConvDesc))
-    lib.call("rua_conv_fwd_group", arr, len(descs), stream())
+    group_planned(lib, arr, len(descs))
     # 16x16x512: split-K members launch one by one; members of unequal job counts are renumbered each over their own jobs.  (128-pixel
     # strips, W = 128, on conv_strip32: d = 31 needs more LDS than two blocks per CU allow and did not share a grid with d = 1, 3, 15;
     # conv_strip32s lays its slots out for the largest dilation, so full-width strips of every dilation share ONE grid)
@@ -1471,7 +1493,7 @@ def _group_equals_separate(shape):
             keep[4 * i + 2].zero_(); keep[4 * i + 3].zero_()
         lib.set_tuning(dmap_chain=3, dmap_spread=0)             # (the chain is built on the burst-issue form of the kernel)
         try:
-            lib.call("rua_conv_fwd_group", arr, len(descs), stream())
+            group_planned(lib, arr, len(descs))
             assert lib.raw("rua_conv_group_last_chain")() == len(dils) and lib.raw("rua_conv_group_last_grids")() == 1
             torch.cuda.synchronize()
         finally:
@@ -2164,7 +2186,7 @@ def _band_multi(case):
 
     arr, ys, sts, keep = build(True)
     assert lib.raw("rua_conv_group_band_ok")(arr, nb) == 1
-    lib.call("rua_conv_fwd_group", arr, nb, stream())
+    group_planned(lib, arr, nb)
     assert lib.raw("rua_conv_group_last_band")() == 2 and lib.raw("rua_conv_group_last_grids")() == 1
     torch.cuda.synchronize()
     if kind == "first" and Cs == 64:                          # every member published its coefficients and moved its moving statistics once
@@ -2197,7 +2219,7 @@ def _band_multi(case):
             lib.set_tuning(**dict(keys))
             try:
                 arr2, ys2, sts2, _ = build(True)
-                lib.call("rua_conv_fwd_group", arr2, nb, stream())
+                group_planned(lib, arr2, nb)
                 assert lib.raw("rua_conv_group_last_band")() == flag
                 torch.cuda.synchronize()
             finally:
@@ -2424,11 +2446,11 @@ def test_conv_small_members_of_unequal_size_share_one_launch():
             pair.append(d)
         descs.append(pair)
     for pair in descs:
-        lib.call("rua_conv_fwd", C.byref(pair[0]), stream())
+        fwd_planned(lib, pair[0])
     arr = (L.ConvDesc * 4)()
     for i, pair in enumerate(descs):
         C.memmove(C.byref(arr, i * C.sizeof(L.ConvDesc)), C.byref(pair[1]), C.sizeof(L.ConvDesc))
-    lib.call("rua_conv_fwd_group", arr, 4, stream())
+    group_planned(lib, arr, 4)
     assert lib.raw("rua_conv_group_last_grids")() == 1
     torch.cuda.synchronize()
     for i in range(4):
@@ -2439,13 +2461,95 @@ def test_conv_small_members_of_unequal_size_share_one_launch():
     try:
         for i in range(4):
             keep[5 * i + 3][1].zero_(); keep[5 * i + 4][1].zero_()
-        lib.call("rua_conv_fwd_group", arr, 4, stream())
+        group_planned(lib, arr, 4)
         assert lib.raw("rua_conv_group_last_grids")() == 4
         torch.cuda.synchronize()
     finally:
         lib.set_tuning(conv_group=31)
     for i in range(4):
         assert torch.equal(keep[5 * i + 3][0], keep[5 * i + 3][1]) and torch.equal(keep[5 * i + 4][0], keep[5 * i + 4][1]), i
+
+
+def _plain_conv(rng, N, H, Cs, Cout, taps, keep):
+    """a bf16 convolution with bias on an N x H x H map and its output tensor"""
+    dt = L.RUA_BF16
+    x = to_dev(rng.standard_normal((N, H, H, Cs)).astype(np.float32), dt)
+    w = to_dev((rng.standard_normal((taps, Cout, Cs)) / np.sqrt(taps * Cs)).astype(np.float32), dt)
+    b = torch.from_numpy(rng.standard_normal(Cout).astype(np.float32)).to(dev())
+    y = torch.zeros((N, H, H, Cout), dtype=torch.bfloat16, device=dev())
+    d = L.ConvDesc()
+    d.nseg = 1
+    sg = d.seg[0]
+    sg.x, sg.w, sg.C, sg.Hs, sg.Ws, sg.up_shift, sg.dil, sg.taps = x.data_ptr(), w.data_ptr(), Cs, H, H, 0, 1, taps
+    d.N, d.H, d.W, d.Cout, d.stride, d.dtype = N, H, H, Cout, 1, dt
+    d.bias = b.data_ptr()
+    d.y, d.out_stride, d.OH, d.OW = y.data_ptr(), 1, H, H
+    keep += [x, w, b]
+    return d, y
+
+
+def _as_array(descs):
+    arr = (L.ConvDesc * len(descs))()
+    for i, d in enumerate(descs):
+        C.memmove(C.byref(arr, i * C.sizeof(L.ConvDesc)), C.byref(d), C.sizeof(L.ConvDesc))
+    return arr
+
+
+MIXED_GROUP = [(1, 256, 32, 32, 9, 5), (1, 256, 16, 32, 1, 4), (1, 8, 128, 64, 1, 6), (1, 32, 64, 64, 9, 0)]      # N, H, C, Cout, taps, rua_conv_kernel_id
+
+
+def _mixed_group_equals_separate(lib, rng):
+    keep, descs, ys = [], [], []
+    for N, H, Cs, Cout, taps, kid in MIXED_GROUP:
+        d, y = _plain_conv(rng, N, H, Cs, Cout, taps, keep)
+        assert lib.raw("rua_conv_kernel_id")(C.byref(d)) == kid
+        descs.append(d); ys.append(y)
+    for d in descs:
+        fwd_planned(lib, d)
+    torch.cuda.synchronize()
+    sep = [y.clone() for y in ys]
+    for y in ys:
+        y.zero_()
+    launches = group_planned(lib, _as_array(descs), len(descs))
+    torch.cuda.synchronize()
+    for i, (y, want) in enumerate(zip(ys, sep)):
+        assert torch.equal(y, want) and want.float().abs().sum().item() > 0, MIXED_GROUP[i]
+    return launches
+
+
+def test_conv_group_of_four_kernels_equals_separate_launches():
+    """One rua_conv_fwd_group whose members land on four kernels - conv_strip, conv_pw, conv_small, conv_igemm: outputs bit-equal to four rua_conv_fwd
+    calls, and as many launches as rua_conv_group_plan reports - the member no group takes first, then conv_pw, conv_strip, conv_small."""
+    lib = L.lib()
+    before = lib.get_tuning("conv_group")
+    lib.set_tuning(conv_group=63)                          # every kernel family groups (the default)
+    try:
+        launches = _mixed_group_equals_separate(lib, np.random.default_rng(77))
+    finally:
+        lib.set_tuning(conv_group=before)
+    assert [(r.kernel_id, r.members) for r in launches] == [(0, 8), (4, 2), (5, 1), (6, 4)]
+    assert lib.raw("rua_conv_group_last_grids")() == 4
+
+
+def test_conv_group_with_a_rejected_member_launches_nothing():
+    """A member with Cout = 12 makes the group return RUA_ERR_ARG before anything is launched: the valid member's output keeps its sentinel.  The next
+    group on the thread - four valid members on four kernels - equals separate launches: nothing of the failed call is left to be issued."""
+    lib = L.lib()
+    rng = np.random.default_rng(78)
+    keep = []
+    good, y = _plain_conv(rng, 1, 32, 64, 64, 9, keep)
+    bad, _ = _plain_conv(rng, 1, 32, 64, 16, 9, keep)
+    bad.Cout = 12
+    y.fill_(-7.0)
+    torch.cuda.synchronize()
+    n_out = C.c_int32(-1)
+    for arr in (_as_array([good, bad]), _as_array([bad, good])):
+        assert lib.raw("rua_conv_group_plan")(arr, 2, (L.ConvLaunchInfo * 2)(), C.byref(n_out)) == -1
+        assert lib.raw("rua_conv_fwd_group")(arr, 2, stream()) == -1
+        assert b"Cout=12" in lib.dll.rua_last_error()
+        torch.cuda.synchronize()
+        assert torch.equal(y, torch.full_like(y, -7.0))
+    _mixed_group_equals_separate(lib, rng)
 
 
 @pytest.mark.parametrize("dt", [L.RUA_F32, L.RUA_BF16])
