@@ -1,6 +1,7 @@
 """Evaluation of a trained model on whole scenes, on the GPU: what test_ISPRS.py does for the reference's test tile (patches,
 predict, arg-max, metrics, mosaic), for a scene directory (resunet_a_mltsk_keras_amd.scenes: scenes/<name>.npy,
-labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views, --erode_boundary, --boundary_f1 and --head_maps.
+labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views, --scales, --erode_boundary,
+--boundary_f1 and --head_maps.
 
 Every scene stays on the GPU, is covered by windows --stride apart (default: the patch; the last window flush with the border, so
 nothing is left unpredicted), every pixel is predicted from the window it is most central in, and Model.predict_scene brings back
@@ -11,6 +12,12 @@ precision of test_ISPRS.compute_metrics_hw.  Per scene it writes `pred_seg_recon
 --views is test-time augmentation: every window is predicted under the named symmetries (`none`, `flips`, `aug5` - the five copies
 `--data_aug` trains on -, `all`, or a list of codes 0..7 of scenes.transform) in one forward, and the arg-max is taken of the sum of
 the turned-back probabilities (scenes.host_stitch_views).  The output files are the same.
+
+--scales Z [Z ...] is multi-scale test-time augmentation, the evaluation side of `train_ISPRS.py --aug_zoom`: the scene is covered once
+per zoom Z (> 1 zooms in; a window covers patch / Z scene pixels per axis, scenes.scale_footprint), every cover under all --views, the
+probabilities are resampled back onto the scene grid and summed in an int32 accumulator on the GPU (scenes.host_accumulate), and the
+arg-max of the sums is the class map (scenes.host_argmax).  `--scales 1` is the single-scale path; --scales and --head_maps exclude
+each other.  The output files are the same.
 
 --erode_boundary R also scores on the eroded ground truth, the one the ISPRS benchmark and the ResUNet-a paper publish numbers on
 (R = 3 there): class-map pixels within a disc of radius R of a pixel of another value are left out (scenes.host_erode), on the GPU,
@@ -71,6 +78,8 @@ def build_parser():
     parser.add_argument("--stride", type=int, default=None, help="distance between windows (default: the patch size)")
     parser.add_argument("--views", nargs="+", default=["none"], metavar="SET|CODE",
                         help="test-time augmentation: none, flips, aug5, all, or symmetry codes 0..7 (e.g. --views 0 3 4)")
+    parser.add_argument("--scales", nargs="+", type=float, default=None, metavar="Z",
+                        help="multi-scale test-time augmentation: 1 to 8 distinct zooms, e.g. --scales 0.75 1 1.5 (default: the scene's own scale only)")
     parser.add_argument("--erode_boundary", type=int, default=0, metavar="R",
                         help="also score on the ground truth eroded by a disc of radius R (0..16; the ISPRS benchmark uses 3); 0: off")
     parser.add_argument("--boundary_f1", type=int, default=None, metavar="R",
@@ -94,6 +103,20 @@ def parse_views(words):
         raise SystemExit(f"--views: {exc}") from None
 
 
+def parse_scales(zooms, patch, head_maps=()):
+    """--scales' zooms as a tuple (None: absent), refused together with --head_maps and for what scenes.check_scales refuses."""
+    from resunet_a_mltsk_keras_amd import scenes
+    if zooms is None:
+        return None
+    if head_maps:
+        raise SystemExit("--scales and --head_maps exclude each other: multi-scale maps of the other heads are not built")
+    try:
+        scenes.check_scales(tuple(zooms), patch)
+    except ValueError as exc:
+        raise SystemExit(f"--scales: {exc}") from None
+    return tuple(zooms)
+
+
 def write_ppm(path, rgb):
     h, w = rgb.shape[:2]
     with open(path, 'wb') as f:                                                               # dependency-free image
@@ -113,6 +136,7 @@ def main(argv=None):
     except ValueError as exc:
         raise SystemExit(f"--boundary_f1: {exc}") from None
     heads = tuple(args.head_maps)
+    scales = parse_scales(args.scales, args.patch_size, heads)
     for k, h in enumerate(heads):
         if h not in scenes.MAP_HEADS or h in heads[:k]:
             raise SystemExit(f"--head_maps {' '.join(heads)}: distinct names out of {', '.join(scenes.MAP_HEADS)}")
@@ -142,9 +166,16 @@ def main(argv=None):
     print('=' * 40)
     print('[TEST]')
     print(f'views: {" ".join(str(c) for c in views)} ({len(views)} per window)')
+    if scales is not None:
+        print(f'scales: {" ".join(f"{z:g}" for z in scales)} ({len(scales)} passes per view)')
+        for name, shape in zip(names, pool.shapes):
+            try:
+                scenes.check_scales(scales, args.patch_size, shape)
+            except ValueError as exc:
+                raise SystemExit(f"--scales: scene {name}: {exc}") from None
     for s, name in enumerate(names):
         pred, cm, *more = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type, views=views,
-                                              erode=erode, heads=heads, boundary=boundary)
+                                              erode=erode, heads=heads, boundary=boundary, scales=scales)
         head_maps = more.pop() if heads else {}
         if boundary is not None:
             counts = more.pop()

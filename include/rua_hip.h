@@ -614,6 +614,43 @@ int rua_scene_stitch_maps(const float* p, int G, int K, int PH, int PW, int Ch, 
                           const int32_t* own /* [G][4] */, uint8_t* const* scene_out, const int32_t* scene_h,
                           const int32_t* scene_w, int nscenes, int mode /* 0 plain, 1 hsv_rgb */, void* stream);
 
+/* Multi-scale test-time augmentation, the way back (scenes.py, scale_table / host_accumulate / host_argmax): the class
+ * probabilities of windows that were cut ZOOMED out of a scene (rua_scene_windows_affine under an axis-aligned matrix) are resampled
+ * onto the scene grid and added to a scene-sized int32 accumulator, pass after pass; one arg-max at the end gives the class map.
+ * p is DEVICE fp32 [G*K][PH][PW][C], 16-byte aligned: group g holds K views of one footprint.  windows7 (HOST int32 [G*K][7], rows
+ * (scene, y0, x0, a_yy, a_yx, a_xy, a_xx) in Q16 exactly as rua_scene_windows_affine read them: window pixel (i, j) sampled the scene at
+ * sy = y0 + i a_yy + j a_yx, sx = x0 + i a_xy + j a_xx) and own (HOST int32 [G][4], the rectangle (r0, r1, c0, c1) of SCENE pixels the
+ * group owns) name the groups.  scene_acc / scene_h / scene_w are HOST arrays of nscenes entries; scene_acc[s] is a device pointer to
+ * int32 [scene_h[s]][scene_w[s]][C].  Every row is axis-aligned: either a_yx = a_xy = 0 (y follows the row index i through a_yy, x
+ * the column index j through a_xx) or a_yy = a_xx = 0 (y follows j through a_yx, x follows i through a_xy; PH == PW only); the other
+ * two entries are nonzero.  For a scene coordinate s on an axis with origin o, coefficient a and n window pixels along its index:
+ *   t = 65536 s - o;  if a < 0: t = -t, a = -a;   w = floor((256 t + (a >> 1)) / a)     (64 bit; the window coordinate in 1/256 pixels)
+ *   w = min(max(w, 0), 256 (n - 1));  i0 = w >> 8;  f = w & 255;  i1 = min(i0 + 1, n - 1)
+ * and with q = rint(min(max(p, 0), 1) * 65536) as rua_scene_stitch_maps quantises (NaN gives 0), read at the four index pairs, fy and
+ * fx the weights of the y and the x axis:
+ *   val = ((256 - fy) ((256 - fx) q00 + fx q01) + fy ((256 - fx) q10 + fx q11) + 32768) >> 16     (the sum reaches 2^32: 64 bit)
+ *   scene_acc[scene][y][x][c] += val_0 + .. + val_{K-1}          for every (y, x) of the rectangle and every channel c.
+ * The K views are summed in a register, the update is one plain read-add-write: the groups of ONE call must own disjoint pixels
+ * (scenes.scale_table guarantees it), calls on one stream are ordered - no atomics.  Integers from the first step on: the order of
+ * views, groups and passes cannot change a bit, scenes.host_accumulate gives the same numbers.  An empty rectangle adds nothing.
+ * Everything is checked on the host before anything is launched (a violation: RUA_ERR_ARG, the message names the row, the group or
+ * the scene, nothing is written): 1 <= K <= 8, 1 <= C <= 64, 1 <= PH, PW <= 512, p 16-byte aligned, 1 <= H, W <= 16384, no null entry in
+ * scene_acc, 0 <= scene < nscenes, the K rows of a group at one scene, axis-aligned matrices, a transposing one only with PH == PW,
+ * the rectangle inside its scene, and - unless empty - inside every view's footprint: the unclamped w of its first and last row and of
+ * its first and last column lies in [-256, 256 n].  The resolved groups travel as kernel arguments, 24 per launch: no device-side
+ * table, no copy, no synchronisation. */
+int rua_scene_accumulate(const float* p, int G, int K, int PH, int PW, int C, const int32_t* windows7 /* [G*K][7] */,
+                         const int32_t* own /* [G][4], scene coordinates */, int32_t* const* scene_acc, const int32_t* scene_h,
+                         const int32_t* scene_w, int nscenes, void* stream);
+
+/* The class map of finished accumulators: scene_pred[s][y][x] = the first index of the maximum of scene_acc[s][y][x][0..C-1], and,
+ * with class maps, confusion[t][pred] += 1 for the label t = scene_cls[s][y][x] < C - accumulated into, as rua_scene_stitch does;
+ * scene_cls and confusion are null together.  All array arguments but confusion are HOST arrays of nscenes entries of device
+ * pointers (int32 [H][W][C], uint8 [H][W], uint8 [H][W]) and sizes; 1 <= C <= 64, H * W * C * 4 < 2^40; the scenes travel as kernel
+ * arguments, 100 per launch.  scenes.host_argmax gives the same bytes and counts. */
+int rua_scene_argmax(const int32_t* const* scene_acc, uint8_t* const* scene_pred, const uint8_t* const* scene_cls,
+                     const int32_t* scene_h, const int32_t* scene_w, int nscenes, int C, int64_t* confusion, void* stream);
+
 /* ---- class counts of scene windows (scenes.py, host_class_counts / class_weights / balance_rows; what the reference's class weights,
  * train_ISPRS.py:424, and its balance filter, utils.py:383, are functions of) ------------------------------------------------------
  * Array arguments other than counts are HOST arrays: scene_cls / scene_h / scene_w and windows, int32 [N][4] rows (scene, row, col,

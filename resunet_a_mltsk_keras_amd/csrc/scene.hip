@@ -873,6 +873,274 @@ extern "C" int rua_scene_stitch_maps(const float* p, int G, int K, int PH, int P
   return RUA_OK;
 }
 
+// ---- rua_scene_accumulate: the way back of a zoomed window - K views resampled onto the scene grid and added to an int32 accumulator --
+// Multi-scale test-time augmentation (scenes.py, scale_table): a pass covers the scene with footprints of FH x FW scene pixels, each
+// cut into a PH x PW window by rua_scene_windows_affine under K view codes (an axis-aligned matrix: a zoom per axis, flips, maybe a
+// transposition).  Group g of p [G*K][PH][PW][C] holds the network's answers to those K windows, own[g] the rectangle of SCENE pixels
+// the footprint owns.  For each owned pixel, each view and channel the window is sampled bilinearly at the pixel's window coordinate
+// - in 1/256 pixels, an exact 64-bit floor division - from the quantised values sm_q16(p), and the K results are summed in a register
+// and added to scene_acc[y][x][c] with one plain read-add-write: the groups of a call own disjoint pixels, passes are ordered by the
+// stream, so there are no atomics.  Integers from the first step on; scenes.host_accumulate gives the same numbers.
+//
+// A block owns a SQ_TH x SQ_TW tile of one group's rectangle.  First its threads work out, per view, the taps of the tile's rows and
+// columns (index pair and weight, one division each: SQ_TH + SQ_TW per view, not one per pixel and channel) into LDS; then thread e
+// walks the elements (row, column, channel) e = tid + 256 m of the tile, channel fastest: consecutive lanes are consecutive int32 of
+// an accumulator row - the 2 x 4 C bytes of accumulator traffic per pixel are coalesced - and read the four taps of their channel,
+// neighbouring lanes neighbouring floats of p wherever the view keeps rows (a gather served by the caches: p of a batch is a few MB).
+namespace {
+
+constexpr int SQ_CHUNK = 24;                   // groups per launch: 160 bytes each
+constexpr int SQ_TH = 16, SQ_TW = 64;          // tile of scene pixels per block
+
+// one axis of one view: scene coordinate s -> window coordinate in 1/256 pixels, w = floor((256 (65536 s - o) + (|a| >> 1)) / |a|), mirrored for a < 0
+struct AccAxis { int o, a; };
+struct AccGroup {
+  int32_t* acc;                                // the scene's accumulator [H][W][C]
+  int W, r0, r1, c0, c1;
+  uint32_t turns;                              // bit k: view k transposes (y feeds the column index, x the row index)
+  AccAxis y[SV_MAXK], x[SV_MAXK];
+};
+struct AccArgs {
+  AccGroup g[SQ_CHUNK];
+  const float* p;
+  int first, PH, PW, C, K;
+};
+static_assert(sizeof(AccGroup) == 160 && sizeof(AccArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+__host__ __device__ __forceinline__ long long sq_floordiv(long long n, long long d) {      // d > 0
+  const long long q = n / d;
+  return (n % d != 0 && n < 0) ? q - 1 : q;
+}
+
+// the unclamped window coordinate of scene coordinate s, in 1/256 pixels (|256 t| < 2^41, a != 0)
+__host__ __device__ __forceinline__ long long sq_coord(int s, AccAxis ax) {
+  long long t = (long long)s * 65536 - ax.o, a = ax.a;
+  if (a < 0) { t = -t; a = -a; }
+  return sq_floordiv(t * 256 + (a >> 1), a);
+}
+
+// taps of scene coordinate s along an index of n window pixels, packed: i0 | i1 << 10 | f << 20
+__device__ __forceinline__ uint32_t sq_taps(int s, AccAxis ax, int n) {
+  long long w = sq_coord(s, ax);
+  const long long hi = (long long)(n - 1) * 256;
+  w = w < 0 ? 0 : w > hi ? hi : w;
+  const uint32_t i0 = (uint32_t)(w >> 8), f = (uint32_t)(w & 255);
+  const uint32_t i1 = i0 + 1 < (uint32_t)n ? i0 + 1 : (uint32_t)(n - 1);
+  return i0 | (i1 << 10) | (f << 20);
+}
+
+__global__ __launch_bounds__(256) void scene_accumulate(AccArgs a) {
+  __shared__ uint32_t ytab[SV_MAXK][SQ_TH], xtab[SV_MAXK][SQ_TW];
+  const int tid = threadIdx.x, C = a.C, PH = a.PH, PW = a.PW, K = a.K;
+  const AccGroup& w = a.g[blockIdx.y];
+  const int tiles_x = (w.c1 - w.c0 + SQ_TW - 1) / SQ_TW;
+  if (tiles_x <= 0) return;                    // an empty rectangle: every block
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int y0 = w.r0 + ty * SQ_TH, x0 = w.c0 + tx * SQ_TW;
+  if (y0 >= w.r1) return;                      // the whole block: the grid is sized for the launch's largest rectangle
+  const int th = min(SQ_TH, w.r1 - y0), tw = min(SQ_TW, w.c1 - x0);
+  for (int e = tid; e < K * (SQ_TH + SQ_TW); e += 256) {
+    const int k = e / (SQ_TH + SQ_TW), r = e - k * (SQ_TH + SQ_TW);
+    const bool turns = (w.turns >> k) & 1u;
+    if (r < SQ_TH) {
+      if (r < th) ytab[k][r] = sq_taps(y0 + r, w.y[k], turns ? PW : PH);
+    } else if (r - SQ_TH < tw) {
+      xtab[k][r - SQ_TH] = sq_taps(x0 + r - SQ_TH, w.x[k], turns ? PH : PW);
+    }
+  }
+  __syncthreads();
+  const int rowe = tw * C, items = th * rowe;
+  const size_t vsize = (size_t)PH * PW * C;
+  const float* pg = a.p + (size_t)(a.first + blockIdx.y) * K * vsize;
+  for (int e = tid; e < items; e += 256) {
+    const int r = e / rowe, rem = e - r * rowe, j = rem / C, c = rem - j * C;
+    uint32_t sum = 0u;                         // at most 8 * 65536
+    for (int k = 0; k < K; ++k) {
+      const uint32_t ty_ = ytab[k][r], tx_ = xtab[k][j];
+      const uint32_t u0 = ty_ & 1023u, u1 = (ty_ >> 10) & 1023u, fy = ty_ >> 20;
+      const uint32_t v0 = tx_ & 1023u, v1 = (tx_ >> 10) & 1023u, fx = tx_ >> 20;
+      const float* v = pg + (size_t)k * vsize + c;
+      // window pixel (row, column) of tap (u, v): (u, v) where the view keeps rows, (v, u) where it transposes
+      const bool turns = (w.turns >> k) & 1u;
+      const uint32_t su = turns ? (uint32_t)C : (uint32_t)(PW * C), sv = turns ? (uint32_t)(PW * C) : (uint32_t)C;
+      const uint32_t q00 = sm_q16(v[u0 * su + v0 * sv]), q01 = sm_q16(v[u0 * su + v1 * sv]);
+      const uint32_t q10 = sm_q16(v[u1 * su + v0 * sv]), q11 = sm_q16(v[u1 * su + v1 * sv]);
+      const uint32_t top = (256u - fx) * q00 + fx * q01, bot = (256u - fx) * q10 + fx * q11;      // at most 2^24
+      sum += (uint32_t)(((unsigned long long)(256u - fy) * top + (unsigned long long)fy * bot + 32768ull) >> 16);   // the sum reaches 2^32
+    }
+    int32_t* d = w.acc + ((size_t)(y0 + r) * w.W + x0) * C + rem;
+    *d += (int32_t)sum;
+  }
+}
+
+// ---- rua_scene_argmax: the finished accumulators -> a uint8 class map per scene and a confusion matrix ----------------------------
+// A block owns `np` neighbouring pixels of one scene (256, fewer where 256 C sums would not fit: np C <= SX_LDSW): their np C int32
+// sums are one contiguous run of the accumulator and come in with consecutive lanes on consecutive dwords, into LDS at a pixel pitch
+// of C | 1 dwords; then one lane per pixel scans its C sums out of LDS (first index of the maximum, a strict > scan from class 0; the
+// odd pitch keeps the lanes on different banks), lanes along the scene row: the map is written and the class map read as contiguous
+// bytes.  Counts collect in the block's LDS histogram as in scene_stitch; a launch has at most SX_BLOCKS blocks per scene and a block
+// sweeps through its scene in steps of the grid, so a 6000 x 6000 scene ends in 1024 x C x C atomic adds on the C x C counters, not
+// in 140 000 x C x C (a scene holds fewer than 2^38 pixels, a block sees 2^28 of them at most: 32-bit cells are plenty).
+constexpr int SX_CHUNK = 100;                  // scenes per launch: 32 bytes each
+constexpr int SX_LDSW = 4096;                  // int32 sums a block stages (C = 64: 64 pixels)
+constexpr int SX_BLOCKS = 1024;                // blocks per scene at most: four for each of 256 compute units
+struct ArgmaxScene { const int32_t* acc; uint8_t* pred; const uint8_t* cls; long long npix; };
+struct ArgmaxArgs {
+  ArgmaxScene s[SX_CHUNK];
+  unsigned long long* confusion;
+  int C, np;                                   // np: pixels per block, at most 256
+};
+static_assert(sizeof(ArgmaxArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+__global__ __launch_bounds__(256) void scene_argmax(ArgmaxArgs a) {
+  __shared__ int32_t S[SX_LDSW + 256];         // np pixels at a pitch of C | 1
+  extern __shared__ uint32_t hist[];             // C * C cells, only with class maps
+  const int tid = threadIdx.x, C = a.C, pitch = C | 1;
+  const ArgmaxScene& s = a.s[blockIdx.y];
+  const long long step = (long long)gridDim.x * a.np;
+  if ((long long)blockIdx.x * a.np >= s.npix) return;       // the whole block: the grid is sized for the launch's largest scene
+  const bool count = s.cls != nullptr;
+  if (count)
+    for (int e = tid; e < C * C; e += 256) hist[e] = 0u;
+  for (long long first = (long long)blockIdx.x * a.np; first < s.npix; first += step) {      // the same trips for every thread of the block
+    const int n = (int)min((long long)a.np, s.npix - first);
+    const int32_t* run = s.acc + (size_t)first * C;
+    __syncthreads();                           // the last sweep's reads of S (and the zeroing of hist) are done
+    for (int e = tid; e < n * C; e += 256) {
+      const int px = e / C;
+      S[px * pitch + (e - px * C)] = run[e];
+    }
+    __syncthreads();
+    if (tid < n) {
+      const int32_t* v = S + tid * pitch;
+      int32_t best = v[0];
+      int pred = 0;
+      for (int c = 1; c < C; ++c) {
+        const int32_t x = v[c];
+        if (x > best) { best = x; pred = c; }
+      }
+      s.pred[first + tid] = (uint8_t)pred;
+      if (count) {
+        const int t = s.cls[first + tid];
+        if (t < C) atomicAdd(&hist[t * C + pred], 1u);
+      }
+    }
+  }
+  if (!count) return;
+  __syncthreads();
+  ss_flush(hist, C, a.confusion, tid);
+}
+
+}  // namespace
+
+extern "C" int rua_scene_accumulate(const float* p, int G, int K, int PH, int PW, int C, const int32_t* windows7, const int32_t* own,
+                                    int32_t* const* scene_acc, const int32_t* scene_h, const int32_t* scene_w, int nscenes, void* stream) {
+  const char* fn = "rua_scene_accumulate";
+  RUA_CHECK_ARG(p && windows7 && own && scene_acc && scene_h && scene_w, "%s: p, windows7, own, scene_acc, scene_h and scene_w are required", fn);
+  RUA_CHECK_ARG(nscenes >= 1 && G >= 1, "%s: nscenes %d, G %d (both >= 1)", fn, nscenes, G);
+  RUA_CHECK_ARG(K >= 1 && K <= SV_MAXK, "%s: K %d outside 1..8", fn, K);
+  RUA_CHECK_ARG(C >= 1 && C <= SS_MAXC, "%s: C %d outside 1..64", fn, C);
+  RUA_CHECK_ARG(PH >= 1 && PW >= 1 && PH <= SW_MAXP && PW <= SW_MAXP, "%s: PH %d, PW %d (1 <= PH, PW <= 512)", fn, PH, PW);
+  RUA_CHECK_ARG(((uintptr_t)p & 15) == 0, "%s: p must be 16-byte aligned", fn);
+  for (int s = 0; s < nscenes; ++s) {
+    RUA_CHECK_ARG(scene_h[s] >= 1 && scene_w[s] >= 1 && scene_h[s] <= SA_MAXDIM && scene_w[s] <= SA_MAXDIM,
+                  "%s: scene %d: size %d x %d (1 <= H, W <= 16384)", fn, s, scene_h[s], scene_w[s]);
+    RUA_CHECK_ARG(scene_acc[s] && ((uintptr_t)scene_acc[s] & 3) == 0, "%s: scene %d: null or misaligned accumulator", fn, s);
+  }
+  // every row and rectangle before anything is launched, in scenes.check_accumulate's order and words
+  for (int g = 0; g < G; ++g) {
+    const int32_t* t0 = windows7 + 7 * (size_t)g * K;
+    for (int v = 0; v < K; ++v) {
+      const int32_t* t = t0 + 7 * v;
+      const int k = g * K + v;
+      RUA_CHECK_ARG(t[0] >= 0 && t[0] < nscenes, "%s: row %d: scene %d outside 0..%d", fn, k, t[0], nscenes - 1);
+      RUA_CHECK_ARG(t[0] == t0[0], "%s: row %d: scene %d, but its group %d is scene %d", fn, k, t[0], g, t0[0]);
+      const bool keeps = t[4] == 0 && t[5] == 0 && t[3] != 0 && t[6] != 0, turns = t[3] == 0 && t[6] == 0 && t[4] != 0 && t[5] != 0;
+      RUA_CHECK_ARG(keeps || turns, "%s: row %d: matrix (%d, %d, %d, %d) is not axis-aligned (a_yx = a_xy = 0 or a_yy = a_xx = 0, the other two nonzero)",
+                    fn, k, t[3], t[4], t[5], t[6]);
+      RUA_CHECK_ARG(!turns || PH == PW, "%s: row %d: matrix (%d, %d, %d, %d) transposes and needs a square patch (got %d x %d)",
+                    fn, k, t[3], t[4], t[5], t[6], PH, PW);
+    }
+    const int H = scene_h[t0[0]], W = scene_w[t0[0]];
+    const int32_t* o = own + 4 * (size_t)g;
+    RUA_CHECK_ARG(0 <= o[0] && o[0] <= o[1] && o[1] <= H && 0 <= o[2] && o[2] <= o[3] && o[3] <= W,
+                  "%s: group %d: rectangle rows %d..%d, columns %d..%d outside its %d x %d scene", fn, g, o[0], o[1], o[2], o[3], H, W);
+    if (o[0] == o[1] || o[2] == o[3]) continue;
+    for (int v = 0; v < K; ++v) {
+      const int32_t* t = t0 + 7 * v;
+      const bool turns = t[3] == 0;
+      const AccAxis ay{t[1], turns ? t[4] : t[3]}, ax{t[2], turns ? t[5] : t[6]};
+      const long long ny = 256LL * (turns ? PW : PH), nx = 256LL * (turns ? PH : PW);
+      const long long wy0 = sq_coord(o[0], ay), wy1 = sq_coord(o[1] - 1, ay), wx0 = sq_coord(o[2], ax), wx1 = sq_coord(o[3] - 1, ax);
+      RUA_CHECK_ARG(wy0 >= -256 && wy0 <= ny && wy1 >= -256 && wy1 <= ny && wx0 >= -256 && wx0 <= nx && wx1 >= -256 && wx1 <= nx,
+                    "%s: row %d: rectangle rows %d..%d, columns %d..%d of group %d leaves the window's footprint", fn, g * K + v, o[0], o[1], o[2], o[3], g);
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  AccArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p = p; a.PH = PH; a.PW = PW; a.C = C; a.K = K;
+  for (int g0 = 0; g0 < G; g0 += SQ_CHUNK) {
+    const int ng = G - g0 < SQ_CHUNK ? G - g0 : SQ_CHUNK;
+    int blocks = 0;
+    for (int g = 0; g < ng; ++g) {
+      const int32_t* t0 = windows7 + 7 * (size_t)(g0 + g) * K;
+      const int32_t* o = own + 4 * (size_t)(g0 + g);
+      AccGroup& w = a.g[g];
+      w.acc = scene_acc[t0[0]]; w.W = scene_w[t0[0]];
+      w.r0 = o[0]; w.r1 = o[1]; w.c0 = o[2]; w.c1 = o[3];
+      if (w.r0 == w.r1) w.c1 = w.c0;           // empty either way: the kernel tests the columns
+      w.turns = 0;
+      for (int v = 0; v < K; ++v) {
+        const int32_t* t = t0 + 7 * v;
+        const bool turns = t[3] == 0;
+        if (turns) w.turns |= 1u << v;
+        w.y[v] = AccAxis{t[1], turns ? t[4] : t[3]};
+        w.x[v] = AccAxis{t[2], turns ? t[5] : t[6]};
+      }
+      const int nb = ((w.r1 - w.r0 + SQ_TH - 1) / SQ_TH) * ((w.c1 - w.c0 + SQ_TW - 1) / SQ_TW);
+      if (nb > blocks) blocks = nb;
+    }
+    if (blocks == 0) continue;                 // nothing but empty rectangles
+    a.first = g0;
+    hipLaunchKernelGGL(scene_accumulate, dim3(blocks, ng), dim3(256), 0, st, a);
+    RUA_LAUNCH_CHECK("rua_scene_accumulate");
+  }
+  return RUA_OK;
+}
+
+extern "C" int rua_scene_argmax(const int32_t* const* scene_acc, uint8_t* const* scene_pred, const uint8_t* const* scene_cls,
+                                const int32_t* scene_h, const int32_t* scene_w, int nscenes, int C, int64_t* confusion, void* stream) {
+  const char* fn = "rua_scene_argmax";
+  RUA_CHECK_ARG(scene_acc && scene_pred && scene_h && scene_w, "%s: scene_acc, scene_pred, scene_h and scene_w are required", fn);
+  RUA_CHECK_ARG(!scene_cls == !confusion, "%s: scene_cls and confusion go together", fn);
+  RUA_CHECK_ARG(nscenes >= 1, "%s: nscenes %d (>= 1)", fn, nscenes);
+  RUA_CHECK_ARG(C >= 1 && C <= SS_MAXC, "%s: C %d outside 1..64", fn, C);
+  RUA_CHECK_ARG(((uintptr_t)confusion & 7) == 0, "%s: confusion must be 8-byte aligned", fn);
+  for (int s = 0; s < nscenes; ++s) {
+    SC_TRY(check_scene(fn, s, scene_acc[s] && scene_pred[s] && (!scene_cls || scene_cls[s]), scene_h[s], scene_w[s], 4 * C, true));
+    RUA_CHECK_ARG(((uintptr_t)scene_acc[s] & 3) == 0, "%s: scene %d: misaligned accumulator", fn, s);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ArgmaxArgs a;
+  memset(&a, 0, sizeof(a));
+  a.confusion = reinterpret_cast<unsigned long long*>(confusion);
+  a.C = C;
+  a.np = SX_LDSW / C < 256 ? SX_LDSW / C : 256;
+  for (int s0 = 0; s0 < nscenes; s0 += SX_CHUNK) {
+    const int ns = nscenes - s0 < SX_CHUNK ? nscenes - s0 : SX_CHUNK;
+    long long most = 0;
+    for (int s = 0; s < ns; ++s) {
+      a.s[s] = ArgmaxScene{scene_acc[s0 + s], scene_pred[s0 + s], scene_cls ? scene_cls[s0 + s] : nullptr, (long long)scene_h[s0 + s] * scene_w[s0 + s]};
+      if (a.s[s].npix > most) most = a.s[s].npix;
+    }
+    const long long sweeps = (most + a.np - 1) / a.np;
+    hipLaunchKernelGGL(scene_argmax, dim3((unsigned)(sweeps < SX_BLOCKS ? sweeps : SX_BLOCKS), ns), dim3(256), scene_cls ? (size_t)C * C * sizeof(uint32_t) : 0, st, a);
+    RUA_LAUNCH_CHECK("rua_scene_argmax");
+  }
+  return RUA_OK;
+}
+
 // ---- rua_scene_class_counts: how many pixels of each class lie in each window of a table ------------------------------------------
 // counts[n][c] for c < C is the number of pixels equal to c in window n of the class map, counts[n][C] the number of pixels >= C
 // (scenes.host_class_counts is the definition).  A symmetry code permutes pixels, so it is checked and otherwise ignored.

@@ -20,7 +20,8 @@ import torch
 
 from . import _lib as L
 from .wgrad_queue import WgradQueue, WSpec
-from .scenes import MAP_HEADS, AffineSceneBatch, SceneBatch, check_photo_table, check_radius, check_tolerance, check_views, view_rows
+from .scenes import (MAP_HEADS, AffineSceneBatch, SceneBatch, check_photo_table, check_radius, check_scales, check_tolerance, check_views,
+                     scale_table, view_rows)
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -2180,7 +2181,7 @@ class Engine:
             cap.replay()
 
     def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None, views=(0,),
-                      erode: int = 0, heads=(), on_heads=None, boundary: Optional[int] = None):
+                      erode: int = 0, heads=(), on_heads=None, boundary: Optional[int] = None, scales=None):
         """The class map of a whole resident scene: (uint8 [H][W] prediction, int64 [C][C] confusion matrix indexed [true][pred], None
         for a pool without class maps).  scenes.predict_table covers the scene with windows `stride` apart (None: the patch) and gives
         every pixel to the window it is most central in; the windows go through the forward `batch` at a time - rua_scene_windows,
@@ -2215,13 +2216,31 @@ class Engine:
         rua_scene_boundary call after the window loop, on the compute stream, into a zeroed int64 [C][4] buffer that is fetched at
         the end.  It scores the stitched map, so it works under any views and together with erode and heads; the return value is
         (prediction, confusion matrix[, matrix on the eroded ground truth][, boundary counts][, head maps]).  ValueError for a pool
-        without class maps."""
+        without class maps.
+        scales: None or (1.0,) is the path and the return value above, call for call.  Otherwise multi-scale test-time augmentation,
+        a tuple of 1 to 8 distinct zooms (> 1 zooms in; scenes.check_scales): an int32 [H][W][C] accumulator (4 H W C bytes) is zeroed
+        on the compute stream and, scale after scale in the order given, the scene is covered by scenes.scale_table - footprints of
+        patch / zoom scene pixels, the stride scaled with them, every pixel owned by the footprint it is most central in -, batches
+        of G = max(1, batch // K) footprints under the K views are cut by rua_scene_windows_affine (pool.affine_batch), go through the
+        same forward plan / captured graph and are resampled onto the scene grid and added by one rua_scene_accumulate call each
+        (scenes.host_accumulate is the definition; nothing is blended between neighbouring windows of a pass, only the passes are
+        summed); the last batch of a pass is padded with repeats of its last group that own an empty rectangle.  One
+        rua_scene_argmax call then writes the class map and the confusion matrix (scenes.host_argmax); erode and boundary score that
+        map as above.  on_batch(rows7, own, p) sees the [G * K][7] affine rows, the [G][4] rectangles in scene coordinates and the
+        device tensor.  ValueError, before any GPU work, with heads (multi-scale maps of the other heads are not built), for a
+        footprint larger than the scene, a transposing view with a non-square patch or a malformed `scales`."""
         H, W, _ = self.cfg.input_shape
         Cn = self.cfg.num_classes
         views = check_views(views, (H, W))
         erode = check_radius(erode)
         heads = self._check_map_heads(heads, norm_type)
         boundary = check_tolerance(boundary)
+        if scales is not None:
+            if not 0 <= int(scene) < len(pool):
+                raise ValueError(f"scene {scene} outside 0..{len(pool) - 1}")
+            scales = check_scales(scales, (H, W), pool.shapes[int(scene)])           # None for (1.0,): the single-scale path
+            if scales is not None and heads:
+                raise ValueError(f"predict_scene(scales=, heads={heads}): multi-scale maps of the heads are not built; give one of the two")
         if erode and pool.cls_ptrs is None:
             raise ValueError(f"predict_scene(erode={erode}) needs the pool's class maps: there is no ground truth to erode")
         if boundary is not None and pool.cls_ptrs is None:
@@ -2252,7 +2271,31 @@ class Engine:
             m = torch.zeros((SH, SW, src.C), dtype=torch.uint8, device=self.dev)
             head_maps[h] = (src, src.C, 1 if h == "color_rgb" else 0, m, (C.c_void_p * 1)(m.data_ptr()))
         nothing = np.zeros((1, 4), np.int32)
-        for k0 in range(0, len(rows), G):
+        if scales is not None:
+            if stride is None:
+                stride = (H, W)
+            acc = torch.zeros((SH, SW, Cn), dtype=torch.int32, device=self.dev)
+            acc_ptr = (C.c_void_p * 1)(acc.data_ptr())
+            for fp in scales:
+                rows7, own7 = scale_table((SH, SW), (H, W), fp, stride, views)
+                rows7[:, 0] = sc
+                for g0 in range(0, len(own7), G):
+                    r, o = rows7[g0 * K:(g0 + G) * K], own7[g0:g0 + G]
+                    if len(o) < G:
+                        r = np.concatenate([r, np.tile(r[-K:], (G - len(o), 1))])
+                        o = np.concatenate([o, np.repeat(nothing, G - len(o), 0)])
+                    r, o = np.ascontiguousarray(r, dtype=np.int32), np.ascontiguousarray(o, dtype=np.int32)
+                    self._upload_scene(g, pool.affine_batch(r), norm_type, with_labels=False)
+                    self._forward_eval(g)
+                    r0 = r.copy()
+                    r0[:, 0] = 0
+                    L.lib().call("rua_scene_accumulate", seg.ptr, G, K, H, W, Cn, r0.ctypes.data, o.ctypes.data, acc_ptr, sh, sw, 1,
+                                 C.c_void_p(self._stream()))
+                    if on_batch is not None:
+                        on_batch(r, o, seg.t)
+            L.lib().call("rua_scene_argmax", acc_ptr, pred_ptr, cls_ptr, sh, sw, 1, Cn, conf.data_ptr() if counted else None,
+                         C.c_void_p(self._stream()))
+        for k0 in range(0, len(rows), G) if scales is None else ():       # the single-scale window loop
             r, o = rows[k0:k0 + G], own[k0:k0 + G]
             if len(r) < G:
                 r = np.concatenate([r, np.repeat(r[-1:], G - len(r), 0)])

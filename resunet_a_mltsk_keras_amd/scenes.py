@@ -47,6 +47,14 @@ turns them back, quantises each value to Q16 (quantise_q16), averages in integer
 seg probabilities, the boundary and distance maps, the colour head's HSV, or that HSV turned into an RGB picture (hsv_to_rgb_u8,
 averaged over the views in RGB); host_stitch_maps is its definition, Engine.predict_scene(heads=) its user.
 
+Multi-scale test-time augmentation is the evaluation side of the zoom jitter: scale_footprint() says how many scene pixels a window
+covers at a zoom, scale_table() covers the scene with such footprints - predict_table's ownership, in scene coordinates - and makes
+the affine rows that cut each footprint into a patch under K views (rua_scene_windows_affine), and rua_scene_accumulate brings the
+class probabilities back: every owned scene pixel samples its window bilinearly at an exact fixed-point coordinate, in Q16 integers,
+and the K views' sum is added to a scene-sized int32 accumulator, pass after pass (host_accumulate is its definition); nothing is
+blended between the windows of a pass.  rua_scene_argmax then writes the class map and the confusion matrix (host_argmax);
+check_scales() reads predict_scene's `scales`, Engine.predict_scene(scales=) is their user.
+
 Class counts close the loop on the dataset: host_class_counts() says how many pixels of each class (and how many of none, a
 value >= C) lie in each window of a table, rua_scene_class_counts is its kernel on the resident class maps and
 ScenePool.class_counts() its user; class_weights() turns the counts of the training rows into the reference's weighted-CE weights
@@ -730,6 +738,243 @@ def host_stitch_maps(p: np.ndarray, rows: np.ndarray, own: np.ndarray, shapes: S
         out = (255 * acc + K * 32768) // (K * 65536) if mode == "plain" else (2 * acc + K) // (2 * K)
         maps[s][row + r0:row + r1, col + c0:col + c1] = out
     return maps
+
+
+# ---- multi-scale test-time augmentation: a scene covered at several zooms, the passes summed in a scene-sized accumulator --------
+MAX_SCALES = 8
+_ACC = "rua_scene_accumulate"
+
+
+def scale_footprint(patch, zoom) -> Tuple[int, int]:
+    """The footprint F = (FH, FW) of a scale: the scene pixels per axis that one PH x PW window covers at `zoom` (> 1 zooms in, as in
+    affine_rows), F = floor(P / zoom + 1/2).  ValueError unless 1 <= F, P <= 4 F and F <= 4 P on both axes: 4 is
+    rua_scene_windows_affine's coefficient limit (Q16), and a window that covers less than a quarter of its pixels says little."""
+    ph, pw = _patch2(patch)
+    if isinstance(zoom, bool) or not isinstance(zoom, (int, float, np.integer, np.floating)) or not np.isfinite(zoom) or not zoom > 0:
+        raise ValueError(f"scale_footprint: zoom {zoom!r} must be a positive number")
+    f = tuple(int(np.floor(p / float(zoom) + 0.5)) for p in (ph, pw))
+    for P, F, what in ((ph, f[0], "rows"), (pw, f[1], "columns")):
+        if not (1 <= F and P <= 4 * F and F <= 4 * P):
+            raise ValueError(f"scale_footprint: {what}: zoom {zoom} gives a footprint of {F} for a patch of {P} (1 <= F, P <= 4 F, F <= 4 P)")
+    return f
+
+
+def scale_table(shape_hw: Sequence[int], patch, footprint, stride, views=(0,)):
+    """One pass of a multi-scale prediction: (rows7 int32 [G*K][7], own int32 [G][4]).  The cover is predict_table(shape_hw, F, SF) with
+    the stride scaled to the footprint, SF = clamp(rint(stride F / P), 1, F) per axis; group g is footprint g of the cover, `own` its
+    owned rectangle (r0, r1, c0, c1) in ABSOLUTE scene coordinates, and its K rows - consecutive, in the order of `views`, view_rows'
+    layout - are the affine rows (scene 0) that cut the footprint into a PH x PW window under view code c:
+    A = diag(a_y, a_x) SYMMETRY[c], a_y = rint(65536 FH / PH), a_x likewise, the origin by affine_rows' rule with the footprint's
+    centre in place of the window's.  All integers.  With F == P and code 0 host_windows_affine of the rows is host_windows of the cover."""
+    ph, pw = _patch2(patch)
+    fh, fw = _patch2(footprint)
+    pair = stride if isinstance(stride, (tuple, list)) and len(stride) == 2 else (stride, stride)
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in pair):
+        raise ValueError(f"stride {stride!r} must be an integer (or a pair of them: rows, columns)")
+    for P, F, S, what in ((ph, fh, int(pair[0]), "rows"), (pw, fw, int(pair[1]), "columns")):
+        if not (1 <= F and P <= 4 * F and F <= 4 * P):
+            raise ValueError(f"scale_table: {what}: footprint {F}, patch {P} (1 <= F, P <= 4 F, F <= 4 P)")
+        if not 1 <= S <= P:
+            raise ValueError(f"scale_table: {what}: stride {S}, patch {P} (1 <= stride <= patch)")
+    v = check_views(views, (ph, pw))
+    sf = tuple(min(max((2 * int(S) * F + P) // (2 * P), 1), F) for S, F, P in ((pair[0], fh, ph), (pair[1], fw, pw)))
+    rows4, own4 = predict_table(shape_hw, (fh, fw), sf)
+    G, K = len(rows4), len(v)
+    r, c = rows4[:, 1].astype(np.int64), rows4[:, 2].astype(np.int64)
+    own = own4.astype(np.int64)
+    own[:, 0:2] += r[:, None]
+    own[:, 2:4] += c[:, None]
+    ay, ax = (2 * Q16 * fh + ph) // (2 * ph), (2 * Q16 * fw + pw) // (2 * pw)
+    A = SYMMETRY[list(v)] * np.array([[ay], [ax]], np.int64)                    # [K][2][2]: diag(a_y, a_x) S
+    rows7 = np.zeros((G, K, 7), np.int64)
+    rows7[:, :, 3:] = A.reshape(K, 4)[None]
+    rows7[:, :, 1] = ((2 * r + fh - 1) * (Q16 // 2))[:, None] - ((A[:, 0, 0] * (ph - 1) + A[:, 0, 1] * (pw - 1)) >> 1)[None, :]
+    rows7[:, :, 2] = ((2 * c + fw - 1) * (Q16 // 2))[:, None] - ((A[:, 1, 0] * (ph - 1) + A[:, 1, 1] * (pw - 1)) >> 1)[None, :]
+    if (np.abs(rows7) > 2 ** 31 - 1).any():
+        raise ValueError("scale_table: a row leaves the int32 range")
+    return rows7.reshape(G * K, 7).astype(np.int32), own.astype(np.int32)
+
+
+def check_scales(scales, patch, shape_hw=None) -> Optional[Tuple[Tuple[int, int], ...]]:
+    """predict_scene's scales as footprints: None for None or (1.0,) - the single-scale path -, otherwise one scale_footprint per zoom
+    of a tuple of 1 to 8 distinct positive zooms with distinct footprints, each no larger than the scene (shape_hw None: not checked)."""
+    if scales is None:
+        return None
+    if isinstance(scales, (str, bytes)):
+        raise ValueError(f"scales {scales!r}: a tuple of 1 to {MAX_SCALES} distinct positive zooms")
+    try:
+        z = tuple(scales)
+    except TypeError:
+        raise ValueError(f"scales {scales!r}: a tuple of 1 to {MAX_SCALES} distinct positive zooms") from None
+    if not 1 <= len(z) <= MAX_SCALES:
+        raise ValueError(f"scales {scales!r}: a tuple of 1 to {MAX_SCALES} distinct positive zooms")
+    fps = tuple(scale_footprint(patch, zoom) for zoom in z)
+    for k, zoom in enumerate(z):
+        if any(float(zoom) == float(y) for y in z[:k]):
+            raise ValueError(f"scales {z}: zoom {zoom} occurs twice")
+        if fps[k] in fps[:k]:
+            raise ValueError(f"scales {z}: zooms {z[fps.index(fps[k])]} and {zoom} give the same footprint {fps[k][0]} x {fps[k][1]}")
+        if shape_hw is not None and (fps[k][0] > int(shape_hw[0]) or fps[k][1] > int(shape_hw[1])):
+            raise ValueError(f"scales {z}: zoom {zoom} gives a footprint of {fps[k][0]} x {fps[k][1]}, larger than the "
+                             f"{int(shape_hw[0])} x {int(shape_hw[1])} scene")
+    if len(z) == 1 and float(z[0]) == 1.0:
+        return None
+    return fps
+
+
+def _axis_w(y: int, o: int, a: int) -> int:
+    """The unclamped window coordinate, in 1/256 pixels, of scene coordinate y on an axis with origin o and coefficient a != 0 (Q16)."""
+    t = y * Q16 - o
+    if a < 0:
+        t, a = -t, -a
+    return (t * 256 + (a >> 1)) // a
+
+
+def _axis_taps(lo: int, hi: int, o: int, a: int, n: int):
+    """(i0, i1, f), int64 [hi - lo] each: the two window indices and the weight of the second, in 1/256, for scene coordinates lo..hi-1."""
+    w = np.array([_axis_w(y, o, a) for y in range(lo, hi)], np.int64).reshape(-1)
+    w = np.clip(w, 0, (n - 1) * 256)
+    i0 = w >> 8
+    return i0, np.minimum(i0 + 1, n - 1), w & 255
+
+
+def check_accumulate(shapes: Sequence[Sequence[int]], rows7, own, K, patch, num_classes: int = 1):
+    """(rows7 [G*K][7], own [G][4]) as contiguous int32 arrays; ValueError, in rua_scene_accumulate's own words, for the first violation."""
+    ph, pw = _patch2(patch)
+    t, o = np.asarray(rows7), np.asarray(own)
+    if t.ndim != 2 or t.shape[1] != 7 or not np.issubdtype(t.dtype, np.integer) or not _is_table4(o):
+        raise ValueError(f"{_ACC} takes integer [G*K][7] rows (scene, y0, x0, a_yy, a_yx, a_xy, a_xx) and [G][4] rows (r0, r1, c0, c1), "
+                         f"got {t.dtype} {t.shape} and {o.dtype} {o.shape}")
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)):
+        raise ValueError(f"K {K!r} must be an integer")
+    K, n, G = int(K), len(shapes), o.shape[0]
+    if n < 1 or G < 1:
+        raise ValueError(f"{_ACC}: nscenes {n}, G {G} (both >= 1)")
+    if not 1 <= K <= MAX_VIEWS:
+        raise ValueError(f"{_ACC}: K {K} outside 1..8")
+    if t.shape[0] != G * K:
+        raise ValueError(f"{_ACC}: {t.shape[0]} window rows for {G} groups of K {K} views (K rows per ownership row)")
+    if not 1 <= num_classes <= MAX_CLASSES:
+        raise ValueError(f"{_ACC}: C {num_classes} outside 1..64")
+    if not (1 <= ph <= MAX_PATCH and 1 <= pw <= MAX_PATCH):
+        raise ValueError(f"{_ACC}: PH {ph}, PW {pw} (1 <= PH, PW <= 512)")
+    for s, shp in enumerate(shapes):
+        if not (1 <= int(shp[0]) <= MAX_SCENE and 1 <= int(shp[1]) <= MAX_SCENE):
+            raise ValueError(f"{_ACC}: scene {s}: size {int(shp[0])} x {int(shp[1])} (1 <= H, W <= 16384)")
+    rows, owns = t.tolist(), o.tolist()
+    for g in range(G):
+        s0 = rows[g * K][0]
+        for v in range(K):
+            k = g * K + v
+            s, _, _, ayy, ayx, axy, axx = rows[k]
+            if not 0 <= s < n:
+                raise ValueError(f"{_ACC}: row {k}: scene {s} outside 0..{n - 1}")
+            if s != s0:
+                raise ValueError(f"{_ACC}: row {k}: scene {s}, but its group {g} is scene {s0}")
+            keeps, turns = ayx == 0 and axy == 0 and ayy != 0 and axx != 0, ayy == 0 and axx == 0 and ayx != 0 and axy != 0
+            if not (keeps or turns):
+                raise ValueError(f"{_ACC}: row {k}: matrix ({ayy}, {ayx}, {axy}, {axx}) is not axis-aligned "
+                                 "(a_yx = a_xy = 0 or a_yy = a_xx = 0, the other two nonzero)")
+            if turns and ph != pw:
+                raise ValueError(f"{_ACC}: row {k}: matrix ({ayy}, {ayx}, {axy}, {axx}) transposes and needs a square patch (got {ph} x {pw})")
+        H, W = int(shapes[s0][0]), int(shapes[s0][1])
+        r0, r1, c0, c1 = owns[g]
+        if not (0 <= r0 <= r1 <= H and 0 <= c0 <= c1 <= W):
+            raise ValueError(f"{_ACC}: group {g}: rectangle rows {r0}..{r1}, columns {c0}..{c1} outside its {H} x {W} scene")
+        if r0 == r1 or c0 == c1:
+            continue
+        for v in range(K):
+            k = g * K + v
+            _, y0, x0, ayy, ayx, axy, axx = rows[k]
+            ay, ny, ax, nx = (ayy, ph, axx, pw) if ayx == 0 else (ayx, pw, axy, ph)
+            ends = [(_axis_w(y, y0, ay), ny) for y in (r0, r1 - 1)] + [(_axis_w(x, x0, ax), nx) for x in (c0, c1 - 1)]
+            if any(not -256 <= w <= m * 256 for w, m in ends):
+                raise ValueError(f"{_ACC}: row {k}: rectangle rows {r0}..{r1}, columns {c0}..{c1} of group {g} leaves the window's footprint")
+    return np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(o, dtype=np.int32)
+
+
+def host_accumulate(p: np.ndarray, rows7, own, shapes: Sequence[Sequence[int]], K: int, acc: Optional[Sequence[np.ndarray]] = None) -> List[np.ndarray]:
+    """The numpy definition of what rua_scene_accumulate adds: the way back of scale_table.  p: float32 [G*K][PH][PW][C], the class
+    probabilities of the K views of G windows cut by the affine rows rows7 [G*K][7]; own [G][4]: each group's rectangle in scene
+    coordinates.  acc: one int32 [H][W][C] array per scene of `shapes`, added into in place (None: fresh zeros); returned.
+    Every row is axis-aligned: a_yx = a_xy = 0 (scene y follows the window's row index through a_yy, x its column index through
+    a_xx) or a_yy = a_xx = 0 (y follows the column index through a_yx, x the row index through a_xy; square patches only).  For
+    a scene coordinate y on an axis with origin o, coefficient a and n window pixels along the index it feeds:
+        t = y 65536 - o;  a < 0: t, a = -t, -a;   w = floor((256 t + (a >> 1)) / a), the window coordinate in 1/256 pixels;
+        w = clamp(w, 0, 256 (n - 1));  i0 = w >> 8;  f = w & 255;  i1 = min(i0 + 1, n - 1)
+    and with q = quantise_q16(p[g K + k]) at the four index pairs, fy and fx the weights from the y and the x axis,
+        val = ((256 - fy) ((256 - fx) q00 + fx q01) + fy ((256 - fx) q10 + fx q11) + 32768) >> 16
+    acc[scene][y, x, c] += the sum of val over the K views, for every (y, x) of the rectangle and every channel.  Integers from the
+    first step on: the order of views, groups and passes cannot matter.  An empty rectangle adds nothing; a rectangle must lie in
+    its scene and in every view's footprint (the unclamped w of its first and last row and column in [-256, 256 n])."""
+    p = np.asarray(p)
+    if p.ndim != 4 or p.dtype != np.float32:
+        raise ValueError(f"p is float32 [G*K][PH][PW][C], got {p.dtype} {p.shape}")
+    PH, PW, Cn = (int(v) for v in p.shape[1:])
+    t, o = check_accumulate(shapes, rows7, own, K, (PH, PW), Cn)
+    K = int(K)
+    if len(p) != len(t):
+        raise ValueError(f"p is [G*K][PH][PW][C] with one view per table row, got {p.shape} for {len(t)} rows")
+    if acc is None:
+        acc = [np.zeros((int(h), int(w), Cn), np.int32) for h, w in shapes]
+    else:
+        acc = list(acc)
+        if len(acc) != len(shapes):
+            raise ValueError(f"{len(acc)} accumulators for {len(shapes)} scenes")
+        for m, (h, w) in zip(acc, shapes):
+            if not isinstance(m, np.ndarray) or m.dtype != np.int32 or m.shape != (int(h), int(w), Cn):
+                raise ValueError(f"an accumulator is an int32 array [{h}][{w}][{Cn}], got {getattr(m, 'dtype', type(m))} {getattr(m, 'shape', '')}")
+    rows = t.tolist()
+    for g, (r0, r1, c0, c1) in enumerate(o.tolist()):
+        if r0 == r1 or c0 == c1:
+            continue
+        total = np.zeros((r1 - r0, c1 - c0, Cn), np.int64)
+        for k in range(g * K, g * K + K):
+            _, y0, x0, ayy, ayx, axy, axx = rows[k]
+            q = quantise_q16(p[k])
+            if ayx == 0:
+                u0, u1, fy = _axis_taps(r0, r1, y0, ayy, PH)
+                v0, v1, fx = _axis_taps(c0, c1, x0, axx, PW)
+            else:                                                              # y feeds the column index, x the row index
+                u0, u1, fy = _axis_taps(r0, r1, y0, ayx, PW)
+                v0, v1, fx = _axis_taps(c0, c1, x0, axy, PH)
+                q = q.swapaxes(0, 1)
+            fy, fx = fy[:, None, None], fx[None, :, None]
+            at = lambda u, v: q[u[:, None], v[None, :]]
+            top, bot = (256 - fx) * at(u0, v0) + fx * at(u0, v1), (256 - fx) * at(u1, v0) + fx * at(u1, v1)
+            total += ((256 - fy) * top + fy * bot + 32768) >> 16
+        acc[rows[g * K][0]][r0:r1, c0:c1] += total.astype(np.int32)
+    return acc
+
+
+def host_argmax(acc: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]] = None, num_classes: Optional[int] = None):
+    """The numpy definition of what rua_scene_argmax writes: (uint8 [H][W] map per scene, int64 [C][C] confusion matrix indexed
+    [true][pred], None without class maps).  pred is the first index of the maximum of acc[y, x, :]; a label >= C is not counted."""
+    acc = [np.asarray(a) for a in acc]
+    if len(acc) < 1:
+        raise ValueError("rua_scene_argmax: nscenes 0 (>= 1)")
+    for s, a in enumerate(acc):
+        if a.ndim != 3 or a.dtype != np.int32 or a.shape[2] != acc[0].shape[2] or a.shape[0] < 1 or a.shape[1] < 1:
+            raise ValueError(f"scene {s}: an accumulator is an int32 array [H][W][C] with one C for all, got {a.dtype} {a.shape}")
+    Cn = int(acc[0].shape[2]) if num_classes is None else int(num_classes)
+    if Cn != acc[0].shape[2]:
+        raise ValueError(f"the accumulators hold {acc[0].shape[2]} classes, num_classes is {Cn}")
+    if not 1 <= Cn <= MAX_CLASSES:
+        raise ValueError(f"rua_scene_argmax: C {Cn} outside 1..64")
+    if class_maps is not None and len(class_maps) != len(acc):
+        raise ValueError(f"{len(class_maps)} class maps for {len(acc)} scenes")
+    maps = [np.argmax(a, axis=-1).astype(np.uint8) for a in acc]
+    if class_maps is None:
+        return maps, None
+    cm = np.zeros((Cn, Cn), np.int64)
+    for s, (m, c) in enumerate(zip(maps, class_maps)):
+        true = np.asarray(c)
+        if true.shape != m.shape:
+            raise ValueError(f"scene {s}: its class map is {m.shape[0]} x {m.shape[1]}, got {true.shape}")
+        true = true.astype(np.int64)
+        keep = true < Cn
+        cm += np.bincount(true[keep] * Cn + m[keep].astype(np.int64), minlength=Cn * Cn).reshape(Cn, Cn)
+    return maps, cm
 
 
 # ---- class counts of windows: what class weights and a balance filter are functions of ------------------------------------------
