@@ -1,6 +1,6 @@
 """Evaluation of a trained model on whole scenes, on the GPU: what test_ISPRS.py does for the reference's test tile (patches,
 predict, arg-max, metrics, mosaic), for a scene directory (resunet_a_mltsk_keras_amd.scenes: scenes/<name>.npy,
-labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views, --scales, --erode_boundary,
+labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views, --scales, --blend, --erode_boundary,
 --boundary_f1 and --head_maps.
 
 Every scene stays on the GPU, is covered by windows --stride apart (default: the patch; the last window flush with the border, so
@@ -18,6 +18,12 @@ per zoom Z (> 1 zooms in; a window covers patch / Z scene pixels per axis, scene
 probabilities are resampled back onto the scene grid and summed in an int32 accumulator on the GPU (scenes.host_accumulate), and the
 arg-max of the sums is the class map (scenes.host_argmax).  `--scales 1` is the single-scale path; --scales and --head_maps exclude
 each other.  The output files are the same.
+
+--blend linear blends overlapping windows instead of giving every pixel to the window it is most central in: each window's
+probabilities enter an int32 accumulator on the GPU under a linear taper (scenes.blend_weight: full weight in the middle and towards
+the scene's border, 1/16 at least), summed over the --views and the --scales, and the arg-max of the sums is the class map
+(scenes.host_accumulate_blend, scenes.host_argmax).  --stride then defaults to half the patch; --blend and --head_maps exclude each
+other.  The output files are the same, plus `eval_settings.json` with the views, scales, stride and blend of the run.
 
 --erode_boundary R also scores on the eroded ground truth, the one the ISPRS benchmark and the ResUNet-a paper publish numbers on
 (R = 3 there): class-map pixels within a disc of radius R of a pixel of another value are left out (scenes.host_erode), on the GPU,
@@ -42,6 +48,7 @@ difference from the scene image is printed.  The returned dict gains `head_maps`
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import sys
 
@@ -80,6 +87,8 @@ def build_parser():
                         help="test-time augmentation: none, flips, aug5, all, or symmetry codes 0..7 (e.g. --views 0 3 4)")
     parser.add_argument("--scales", nargs="+", type=float, default=None, metavar="Z",
                         help="multi-scale test-time augmentation: 1 to 8 distinct zooms, e.g. --scales 0.75 1 1.5 (default: the scene's own scale only)")
+    parser.add_argument("--blend", choices=["linear"], default=None,
+                        help="blend overlapping windows under a linear taper instead of cutting between them (--stride then defaults to half the patch)")
     parser.add_argument("--erode_boundary", type=int, default=0, metavar="R",
                         help="also score on the ground truth eroded by a disc of radius R (0..16; the ISPRS benchmark uses 3); 0: off")
     parser.add_argument("--boundary_f1", type=int, default=None, metavar="R",
@@ -137,6 +146,8 @@ def main(argv=None):
         raise SystemExit(f"--boundary_f1: {exc}") from None
     heads = tuple(args.head_maps)
     scales = parse_scales(args.scales, args.patch_size, heads)
+    if args.blend is not None and heads:
+        raise SystemExit("--blend and --head_maps exclude each other: blended maps of the other heads are not built")
     for k, h in enumerate(heads):
         if h not in scenes.MAP_HEADS or h in heads[:k]:
             raise SystemExit(f"--head_maps {' '.join(heads)}: distinct names out of {', '.join(scenes.MAP_HEADS)}")
@@ -173,9 +184,13 @@ def main(argv=None):
                 scenes.check_scales(scales, args.patch_size, shape)
             except ValueError as exc:
                 raise SystemExit(f"--scales: scene {name}: {exc}") from None
+    if args.blend is not None:
+        print(f'blend: {args.blend}')
+        with open(os.path.join(args.output_path, 'eval_settings.json'), 'w') as f:
+            json.dump({"views": list(views), "scales": None if scales is None else list(scales), "stride": args.stride, "blend": args.blend}, f)
     for s, name in enumerate(names):
         pred, cm, *more = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type, views=views,
-                                              erode=erode, heads=heads, boundary=boundary, scales=scales)
+                                              erode=erode, heads=heads, boundary=boundary, scales=scales, blend=args.blend)
         head_maps = more.pop() if heads else {}
         if boundary is not None:
             counts = more.pop()
@@ -207,6 +222,8 @@ def main(argv=None):
     print('Recall: ', metrics[2])
     print('Precision: ', metrics[3])
     res = {"accuracy": metrics[0], "f1": metrics[1], "recall": metrics[2], "precision": metrics[3], "confusion_matrix": total}
+    if args.blend is not None:
+        res["blend"] = args.blend
     if erode:
         m = metrics_from_confusion(total_eroded)
         print()

@@ -643,6 +643,25 @@ int rua_scene_accumulate(const float* p, int G, int K, int PH, int PW, int C, co
                          const int32_t* own /* [G][4], scene coordinates */, int32_t* const* scene_acc, const int32_t* scene_h,
                          const int32_t* scene_w, int nscenes, void* stream);
 
+/* Blended whole-scene prediction (scenes.py, blend_table / blend_weight / host_accumulate_blend): rua_scene_accumulate for footprints
+ * that OVERLAP, each under a linear taper.  The arguments are rua_scene_accumulate's, but foot (HOST int32 [G][4]) holds each group's
+ * FULL footprint (r0, r1, c0, c1) in scene pixels, and the rectangles of a call may share pixels.  With FH = r1 - r0, FW = c1 - c0 and,
+ * along an axis of F pixels, for position t (0 <= t < F)
+ *   w(t) = 256                                        where the footprint touches the scene's low border and 2 t + 1 <= F,
+ *                                                     or its high border and 2 t + 1 >= F,
+ *   w(t) = max(16, (256 (2 min(t, F - 1 - t) + 1)) / F)   otherwise                                  (integer division),
+ * the K views' sum v = val_0 + .. + val_{K-1} of rua_scene_accumulate enters as
+ *   scene_acc[scene][y][x][c] += (w(y - r0) w(x - c0) v + 32768) >> 16            (64 bit; at most K 65536)
+ * with an integer atomic add whose value is not read, so the groups of a call - and of calls on different streams - may overlap and
+ * the sums are the same in any order.  The weight lives in scene space: the K views of a group share it.  The caller keeps K times
+ * the number of footprints over one pixel, summed over all calls, below 32768 (scenes.check_blend_budget): the sums are int32.
+ * Checked on the host before anything is launched, nothing written on a refusal: everything rua_scene_accumulate checks, under this
+ * function's name, and every non-empty rectangle of a call has the size of the first one (a call is one pass).  The resolved groups
+ * travel as kernel arguments, 24 per launch.  scenes.host_accumulate_blend gives the same numbers. */
+int rua_scene_accumulate_blend(const float* p, int G, int K, int PH, int PW, int C, const int32_t* windows7 /* [G*K][7] */,
+                               const int32_t* foot /* [G][4], scene coordinates */, int32_t* const* scene_acc, const int32_t* scene_h,
+                               const int32_t* scene_w, int nscenes, void* stream);
+
 /* The class map of finished accumulators: scene_pred[s][y][x] = the first index of the maximum of scene_acc[s][y][x][0..C-1], and,
  * with class maps, confusion[t][pred] += 1 for the label t = scene_cls[s][y][x] < C - accumulated into, as rua_scene_stitch does;
  * scene_cls and confusion are null together.  All array arguments but confusion are HOST arrays of nscenes entries of device

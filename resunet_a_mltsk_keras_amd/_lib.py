@@ -191,6 +191,7 @@ _SIGS = {
     "rua_scene_stitch_views": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp], i32),
     "rua_scene_stitch_maps": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp], i32),
     "rua_scene_accumulate": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp], i32),
+    "rua_scene_accumulate_blend": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp], i32),
     "rua_scene_argmax": ([vp, vp, vp, vp, vp, i32, i32, vp, vp], i32),
     "rua_scene_class_counts": ([vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp], i32),
     "rua_scene_erode": ([vp, vp, vp, i32, i32, vp, vp, i32, vp, vp], i32),

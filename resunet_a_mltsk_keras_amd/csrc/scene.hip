@@ -973,6 +973,88 @@ __global__ __launch_bounds__(256) void scene_accumulate(AccArgs a) {
   }
 }
 
+// ---- rua_scene_accumulate_blend: scene_accumulate for OVERLAPPING footprints, each under a linear taper ------------------------------
+// scenes.py, blend_table / host_accumulate_blend: a group's rectangle is its whole footprint, the footprints of a call overlap, and
+// the K views' sum v of a pixel enters the accumulator as (wy wx v + 32768) >> 16 with wy, wx = blend_weight of the pixel's row and
+// column inside the footprint (out of 256: a linear taper, flat towards a scene border, never below 16).  Everything up to the sum
+// is scene_accumulate's - structs, tap helpers, tile, channel-fastest walk; three things differ: the weights of the tile's rows and
+// columns are worked out once per tile into LDS next to the taps, the weight is applied once to the views' sum with a 64-bit
+// product, and the add is an integer atomicAdd whose value nobody reads (the returnless vector atomic): two groups of a call, in
+// one launch or in two, may hold the same pixel.  Integer addition commutes, so the accumulator is the same in any order; a wave's
+// atomics are consecutive dwords of an accumulator row.
+constexpr int SL_CHUNK = 24;                   // groups per launch: 168 bytes each
+struct BlendGroup {
+  AccGroup g;                                  // r0..r1, c0..c1: the full footprint
+  uint32_t flat;                               // bit 0: r0 == 0, bit 1: r1 == H, bit 2: c0 == 0, bit 3: c1 == W
+};
+struct BlendArgs {
+  BlendGroup g[SL_CHUNK];
+  const float* p;
+  int first, PH, PW, C, K;
+};
+static_assert(sizeof(BlendGroup) == 168 && sizeof(BlendArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+// scenes.blend_weight: position t of a footprint of F pixels along one axis (256 (2 t + 1) < 2^24: F is a few window sizes at most)
+__host__ __device__ __forceinline__ uint32_t sl_weight(int t, int F, bool flat_lo, bool flat_hi) {
+  if ((flat_lo && 2 * t + 1 <= F) || (flat_hi && 2 * t + 1 >= F)) return 256u;
+  const int m = t < F - 1 - t ? t : F - 1 - t;
+  const int w = (256 * (2 * m + 1)) / F;
+  return (uint32_t)(w < 16 ? 16 : w);
+}
+
+__global__ __launch_bounds__(256) void scene_accumulate_blend(BlendArgs a) {
+  __shared__ uint32_t ytab[SV_MAXK][SQ_TH], xtab[SV_MAXK][SQ_TW], wytab[SQ_TH], wxtab[SQ_TW];
+  const int tid = threadIdx.x, C = a.C, PH = a.PH, PW = a.PW, K = a.K;
+  const AccGroup& w = a.g[blockIdx.y].g;
+  const uint32_t flat = a.g[blockIdx.y].flat;
+  const int tiles_x = (w.c1 - w.c0 + SQ_TW - 1) / SQ_TW;
+  if (tiles_x <= 0) return;                    // an empty rectangle: every block
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int y0 = w.r0 + ty * SQ_TH, x0 = w.c0 + tx * SQ_TW;
+  if (y0 >= w.r1) return;                      // the whole block: the grid is sized for the launch's largest rectangle
+  const int th = min(SQ_TH, w.r1 - y0), tw = min(SQ_TW, w.c1 - x0);
+  for (int e = tid; e < (K + 1) * (SQ_TH + SQ_TW); e += 256) {      // row K of the table: the weights
+    const int k = e / (SQ_TH + SQ_TW), r = e - k * (SQ_TH + SQ_TW);
+    if (k == K) {
+      if (r < SQ_TH) {
+        if (r < th) wytab[r] = sl_weight(y0 + r - w.r0, w.r1 - w.r0, flat & 1u, flat & 2u);
+      } else if (r - SQ_TH < tw) {
+        wxtab[r - SQ_TH] = sl_weight(x0 + r - SQ_TH - w.c0, w.c1 - w.c0, flat & 4u, flat & 8u);
+      }
+      continue;
+    }
+    const bool turns = (w.turns >> k) & 1u;
+    if (r < SQ_TH) {
+      if (r < th) ytab[k][r] = sq_taps(y0 + r, w.y[k], turns ? PW : PH);
+    } else if (r - SQ_TH < tw) {
+      xtab[k][r - SQ_TH] = sq_taps(x0 + r - SQ_TH, w.x[k], turns ? PH : PW);
+    }
+  }
+  __syncthreads();
+  const int rowe = tw * C, items = th * rowe;
+  const size_t vsize = (size_t)PH * PW * C;
+  const float* pg = a.p + (size_t)(a.first + blockIdx.y) * K * vsize;
+  for (int e = tid; e < items; e += 256) {
+    const int r = e / rowe, rem = e - r * rowe, j = rem / C, c = rem - j * C;
+    uint32_t sum = 0u;                         // at most 8 * 65536
+    for (int k = 0; k < K; ++k) {
+      const uint32_t ty_ = ytab[k][r], tx_ = xtab[k][j];
+      const uint32_t u0 = ty_ & 1023u, u1 = (ty_ >> 10) & 1023u, fy = ty_ >> 20;
+      const uint32_t v0 = tx_ & 1023u, v1 = (tx_ >> 10) & 1023u, fx = tx_ >> 20;
+      const float* v = pg + (size_t)k * vsize + c;
+      const bool turns = (w.turns >> k) & 1u;
+      const uint32_t su = turns ? (uint32_t)C : (uint32_t)(PW * C), sv = turns ? (uint32_t)(PW * C) : (uint32_t)C;
+      const uint32_t q00 = sm_q16(v[u0 * su + v0 * sv]), q01 = sm_q16(v[u0 * su + v1 * sv]);
+      const uint32_t q10 = sm_q16(v[u1 * su + v0 * sv]), q11 = sm_q16(v[u1 * su + v1 * sv]);
+      const uint32_t top = (256u - fx) * q00 + fx * q01, bot = (256u - fx) * q10 + fx * q11;      // at most 2^24
+      sum += (uint32_t)(((unsigned long long)(256u - fy) * top + (unsigned long long)fy * bot + 32768ull) >> 16);   // the sum reaches 2^32
+    }
+    const uint32_t wgt = wytab[r] * wxtab[j];  // at most 2^16
+    const int32_t add = (int32_t)(((unsigned long long)wgt * sum + 32768ull) >> 16);              // the product reaches 2^35; add <= K * 65536
+    atomicAdd(w.acc + ((size_t)(y0 + r) * w.W + x0) * C + rem, add);                               // the value is not read: no return
+  }
+}
+
 // ---- rua_scene_argmax: the finished accumulators -> a uint8 class map per scene and a confusion matrix ----------------------------
 // A block owns `np` neighbouring pixels of one scene (256, fewer where 256 C sums would not fit: np C <= SX_LDSW): their np C int32
 // sums are one contiguous run of the accumulator and come in with consecutive lanes on consecutive dwords, into LDS at a pixel pitch
@@ -1033,9 +1115,12 @@ __global__ __launch_bounds__(256) void scene_argmax(ArgmaxArgs a) {
 
 }  // namespace
 
-extern "C" int rua_scene_accumulate(const float* p, int G, int K, int PH, int PW, int C, const int32_t* windows7, const int32_t* own,
-                                    int32_t* const* scene_acc, const int32_t* scene_h, const int32_t* scene_w, int nscenes, void* stream) {
-  const char* fn = "rua_scene_accumulate";
+namespace {
+
+// the argument checks of rua_scene_accumulate and rua_scene_accumulate_blend under the caller's name, in scenes._check_accumulate's
+// order and words; one_size: the non-empty rectangles of the call have one size (a blended call is one pass)
+int check_accumulate(const char* fn, const float* p, int G, int K, int PH, int PW, int C, const int32_t* windows7, const int32_t* own,
+                     int32_t* const* scene_acc, const int32_t* scene_h, const int32_t* scene_w, int nscenes, bool one_size) {
   RUA_CHECK_ARG(p && windows7 && own && scene_acc && scene_h && scene_w, "%s: p, windows7, own, scene_acc, scene_h and scene_w are required", fn);
   RUA_CHECK_ARG(nscenes >= 1 && G >= 1, "%s: nscenes %d, G %d (both >= 1)", fn, nscenes, G);
   RUA_CHECK_ARG(K >= 1 && K <= SV_MAXK, "%s: K %d outside 1..8", fn, K);
@@ -1047,7 +1132,7 @@ extern "C" int rua_scene_accumulate(const float* p, int G, int K, int PH, int PW
                   "%s: scene %d: size %d x %d (1 <= H, W <= 16384)", fn, s, scene_h[s], scene_w[s]);
     RUA_CHECK_ARG(scene_acc[s] && ((uintptr_t)scene_acc[s] & 3) == 0, "%s: scene %d: null or misaligned accumulator", fn, s);
   }
-  // every row and rectangle before anything is launched, in scenes.check_accumulate's order and words
+  int first = -1, fh = 0, fw = 0;               // the first non-empty rectangle and its size
   for (int g = 0; g < G; ++g) {
     const int32_t* t0 = windows7 + 7 * (size_t)g * K;
     for (int v = 0; v < K; ++v) {
@@ -1066,6 +1151,10 @@ extern "C" int rua_scene_accumulate(const float* p, int G, int K, int PH, int PW
     RUA_CHECK_ARG(0 <= o[0] && o[0] <= o[1] && o[1] <= H && 0 <= o[2] && o[2] <= o[3] && o[3] <= W,
                   "%s: group %d: rectangle rows %d..%d, columns %d..%d outside its %d x %d scene", fn, g, o[0], o[1], o[2], o[3], H, W);
     if (o[0] == o[1] || o[2] == o[3]) continue;
+    if (one_size && first < 0) { first = g; fh = o[1] - o[0]; fw = o[3] - o[2]; }
+    RUA_CHECK_ARG(!one_size || (o[1] - o[0] == fh && o[3] - o[2] == fw),
+                  "%s: group %d: rectangle of %d x %d, but group %d has %d x %d (the footprints of one call have one size)", fn, g, o[1] - o[0],
+                  o[3] - o[2], first, fh, fw);
     for (int v = 0; v < K; ++v) {
       const int32_t* t = t0 + 7 * v;
       const bool turns = t[3] == 0;
@@ -1076,6 +1165,31 @@ extern "C" int rua_scene_accumulate(const float* p, int G, int K, int PH, int PW
                     "%s: row %d: rectangle rows %d..%d, columns %d..%d of group %d leaves the window's footprint", fn, g * K + v, o[0], o[1], o[2], o[3], g);
     }
   }
+  return RUA_OK;
+}
+
+// group g of a checked call as a kernel argument; returns the blocks its rectangle takes
+int fill_acc_group(AccGroup& w, const int32_t* t0, const int32_t* o, int K, int32_t* const* scene_acc, const int32_t* scene_w) {
+  w.acc = scene_acc[t0[0]]; w.W = scene_w[t0[0]];
+  w.r0 = o[0]; w.r1 = o[1]; w.c0 = o[2]; w.c1 = o[3];
+  if (w.r0 == w.r1) w.c1 = w.c0;               // empty either way: the kernel tests the columns
+  w.turns = 0;
+  for (int v = 0; v < K; ++v) {
+    const int32_t* t = t0 + 7 * v;
+    const bool turns = t[3] == 0;
+    if (turns) w.turns |= 1u << v;
+    w.y[v] = AccAxis{t[1], turns ? t[4] : t[3]};
+    w.x[v] = AccAxis{t[2], turns ? t[5] : t[6]};
+  }
+  return ((w.r1 - w.r0 + SQ_TH - 1) / SQ_TH) * ((w.c1 - w.c0 + SQ_TW - 1) / SQ_TW);
+}
+
+}  // namespace
+
+extern "C" int rua_scene_accumulate(const float* p, int G, int K, int PH, int PW, int C, const int32_t* windows7, const int32_t* own,
+                                    int32_t* const* scene_acc, const int32_t* scene_h, const int32_t* scene_w, int nscenes, void* stream) {
+  // every row and rectangle before anything is launched, in scenes.check_accumulate's order and words
+  SC_TRY(check_accumulate("rua_scene_accumulate", p, G, K, PH, PW, C, windows7, own, scene_acc, scene_h, scene_w, nscenes, false));
   hipStream_t st = (hipStream_t)stream;
   AccArgs a;
   memset(&a, 0, sizeof(a));
@@ -1084,27 +1198,39 @@ extern "C" int rua_scene_accumulate(const float* p, int G, int K, int PH, int PW
     const int ng = G - g0 < SQ_CHUNK ? G - g0 : SQ_CHUNK;
     int blocks = 0;
     for (int g = 0; g < ng; ++g) {
-      const int32_t* t0 = windows7 + 7 * (size_t)(g0 + g) * K;
-      const int32_t* o = own + 4 * (size_t)(g0 + g);
-      AccGroup& w = a.g[g];
-      w.acc = scene_acc[t0[0]]; w.W = scene_w[t0[0]];
-      w.r0 = o[0]; w.r1 = o[1]; w.c0 = o[2]; w.c1 = o[3];
-      if (w.r0 == w.r1) w.c1 = w.c0;           // empty either way: the kernel tests the columns
-      w.turns = 0;
-      for (int v = 0; v < K; ++v) {
-        const int32_t* t = t0 + 7 * v;
-        const bool turns = t[3] == 0;
-        if (turns) w.turns |= 1u << v;
-        w.y[v] = AccAxis{t[1], turns ? t[4] : t[3]};
-        w.x[v] = AccAxis{t[2], turns ? t[5] : t[6]};
-      }
-      const int nb = ((w.r1 - w.r0 + SQ_TH - 1) / SQ_TH) * ((w.c1 - w.c0 + SQ_TW - 1) / SQ_TW);
+      const int nb = fill_acc_group(a.g[g], windows7 + 7 * (size_t)(g0 + g) * K, own + 4 * (size_t)(g0 + g), K, scene_acc, scene_w);
       if (nb > blocks) blocks = nb;
     }
     if (blocks == 0) continue;                 // nothing but empty rectangles
     a.first = g0;
     hipLaunchKernelGGL(scene_accumulate, dim3(blocks, ng), dim3(256), 0, st, a);
     RUA_LAUNCH_CHECK("rua_scene_accumulate");
+  }
+  return RUA_OK;
+}
+
+extern "C" int rua_scene_accumulate_blend(const float* p, int G, int K, int PH, int PW, int C, const int32_t* windows7, const int32_t* foot,
+                                          int32_t* const* scene_acc, const int32_t* scene_h, const int32_t* scene_w, int nscenes, void* stream) {
+  // scenes.check_accumulate_blend's order and words; nothing is launched before every group has passed
+  SC_TRY(check_accumulate("rua_scene_accumulate_blend", p, G, K, PH, PW, C, windows7, foot, scene_acc, scene_h, scene_w, nscenes, true));
+  hipStream_t st = (hipStream_t)stream;
+  BlendArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p = p; a.PH = PH; a.PW = PW; a.C = C; a.K = K;
+  for (int g0 = 0; g0 < G; g0 += SL_CHUNK) {
+    const int ng = G - g0 < SL_CHUNK ? G - g0 : SL_CHUNK;
+    int blocks = 0;
+    for (int g = 0; g < ng; ++g) {
+      const int32_t* t0 = windows7 + 7 * (size_t)(g0 + g) * K;
+      const int32_t* o = foot + 4 * (size_t)(g0 + g);
+      const int nb = fill_acc_group(a.g[g].g, t0, o, K, scene_acc, scene_w);
+      a.g[g].flat = (o[0] == 0 ? 1u : 0u) | (o[1] == scene_h[t0[0]] ? 2u : 0u) | (o[2] == 0 ? 4u : 0u) | (o[3] == scene_w[t0[0]] ? 8u : 0u);
+      if (nb > blocks) blocks = nb;
+    }
+    if (blocks == 0) continue;                 // nothing but empty rectangles
+    a.first = g0;
+    hipLaunchKernelGGL(scene_accumulate_blend, dim3(blocks, ng), dim3(256), 0, st, a);
+    RUA_LAUNCH_CHECK("rua_scene_accumulate_blend");
   }
   return RUA_OK;
 }

@@ -20,8 +20,8 @@ import torch
 
 from . import _lib as L
 from .wgrad_queue import WgradQueue, WSpec
-from .scenes import (MAP_HEADS, AffineSceneBatch, SceneBatch, check_photo_table, check_radius, check_scales, check_tolerance, check_views,
-                     scale_table, view_rows)
+from .scenes import (BLEND_MODES, MAP_HEADS, AffineSceneBatch, SceneBatch, blend_table, check_blend_budget, check_photo_table, check_radius,
+                     check_scales, check_tolerance, check_views, scale_table, view_rows)
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -2181,7 +2181,7 @@ class Engine:
             cap.replay()
 
     def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None, views=(0,),
-                      erode: int = 0, heads=(), on_heads=None, boundary: Optional[int] = None, scales=None):
+                      erode: int = 0, heads=(), on_heads=None, boundary: Optional[int] = None, scales=None, blend=None):
         """The class map of a whole resident scene: (uint8 [H][W] prediction, int64 [C][C] confusion matrix indexed [true][pred], None
         for a pool without class maps).  scenes.predict_table covers the scene with windows `stride` apart (None: the patch) and gives
         every pixel to the window it is most central in; the windows go through the forward `batch` at a time - rua_scene_windows,
@@ -2228,7 +2228,18 @@ class Engine:
         rua_scene_argmax call then writes the class map and the confusion matrix (scenes.host_argmax); erode and boundary score that
         map as above.  on_batch(rows7, own, p) sees the [G * K][7] affine rows, the [G][4] rectangles in scene coordinates and the
         device tensor.  ValueError, before any GPU work, with heads (multi-scale maps of the other heads are not built), for a
-        footprint larger than the scene, a transposing view with a non-square patch or a malformed `scales`."""
+        footprint larger than the scene, a transposing view with a non-square patch or a malformed `scales`.
+        blend: None is every path above, call for call.  "linear" blends overlapping windows instead of giving each pixel to one of
+        them, always through the accumulator: scales None or (1.0,) is one pass with the patch as its footprint, and stride None
+        then means patch // 2 per axis (blending windows that do not overlap does nothing).  Per pass scenes.blend_table hands out
+        scale_table's rows and, in place of an owned rectangle, each group's FULL footprint; batches of G = max(1, batch // K) groups
+        go through pool.affine_batch and the same forward plan / captured graph, and one rua_scene_accumulate_blend per batch adds
+        (wy wx v + 32768) >> 16 of the K views' sum v under the footprint's linear taper (scenes.blend_weight, out of 256, flat
+        towards the scene's border, never below 16) with integer atomics - scenes.host_accumulate_blend is the definition, and the
+        sums do not depend on the order.  The last batch of a pass is padded with groups whose rectangle is empty; one
+        rua_scene_argmax follows, erode and boundary score its map; on_batch(rows7, foot, p).  scenes.check_blend_budget keeps the
+        int32 sums in range (K times the footprints over one pixel, summed over the passes, below 32768).  ValueError, before any
+        GPU work, for another value, over the budget, and with heads (blended maps of the other heads are not built)."""
         H, W, _ = self.cfg.input_shape
         Cn = self.cfg.num_classes
         views = check_views(views, (H, W))
@@ -2241,6 +2252,17 @@ class Engine:
             scales = check_scales(scales, (H, W), pool.shapes[int(scene)])           # None for (1.0,): the single-scale path
             if scales is not None and heads:
                 raise ValueError(f"predict_scene(scales=, heads={heads}): multi-scale maps of the heads are not built; give one of the two")
+        if blend is not None:
+            if not isinstance(blend, str) or blend not in BLEND_MODES:
+                raise ValueError(f"blend {blend!r}: None or one of {BLEND_MODES}")
+            if heads:
+                raise ValueError(f"predict_scene(blend=, heads={heads}): blended maps of the heads are not built; give one of the two")
+            if not 0 <= int(scene) < len(pool):
+                raise ValueError(f"scene {scene} outside 0..{len(pool) - 1}")
+            if scales is None:
+                scales = ((H, W),)                                                   # one pass, the patch its footprint
+            if stride is None:
+                stride = (max(1, H // 2), max(1, W // 2))
         if erode and pool.cls_ptrs is None:
             raise ValueError(f"predict_scene(erode={erode}) needs the pool's class maps: there is no ground truth to erode")
         if boundary is not None and pool.cls_ptrs is None:
@@ -2250,6 +2272,8 @@ class Engine:
         if pool.patch is None or tuple(pool.patch) != (H, W):
             raise ValueError(f"the scene pool's patch is {pool.patch}, the model's input {H} x {W}")
         rows, own = pool.predict_table(scene, stride)
+        if blend is not None:
+            check_blend_budget(pool.shapes[int(scene)], (H, W), scales, stride, len(views))
         self._check_scene(pool.batch(rows[:1]), None, norm_type, with_labels=False)
         K = len(views)
         tta = views != (0,)
@@ -2274,10 +2298,11 @@ class Engine:
         if scales is not None:
             if stride is None:
                 stride = (H, W)
+            table, entry = (scale_table, "rua_scene_accumulate") if blend is None else (blend_table, "rua_scene_accumulate_blend")
             acc = torch.zeros((SH, SW, Cn), dtype=torch.int32, device=self.dev)
             acc_ptr = (C.c_void_p * 1)(acc.data_ptr())
             for fp in scales:
-                rows7, own7 = scale_table((SH, SW), (H, W), fp, stride, views)
+                rows7, own7 = table((SH, SW), (H, W), fp, stride, views)
                 rows7[:, 0] = sc
                 for g0 in range(0, len(own7), G):
                     r, o = rows7[g0 * K:(g0 + G) * K], own7[g0:g0 + G]
@@ -2289,7 +2314,7 @@ class Engine:
                     self._forward_eval(g)
                     r0 = r.copy()
                     r0[:, 0] = 0
-                    L.lib().call("rua_scene_accumulate", seg.ptr, G, K, H, W, Cn, r0.ctypes.data, o.ctypes.data, acc_ptr, sh, sw, 1,
+                    L.lib().call(entry, seg.ptr, G, K, H, W, Cn, r0.ctypes.data, o.ctypes.data, acc_ptr, sh, sw, 1,
                                  C.c_void_p(self._stream()))
                     if on_batch is not None:
                         on_batch(r, o, seg.t)

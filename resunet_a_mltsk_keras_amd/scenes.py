@@ -55,6 +55,12 @@ and the K views' sum is added to a scene-sized int32 accumulator, pass after pas
 blended between the windows of a pass.  rua_scene_argmax then writes the class map and the confusion matrix (host_argmax);
 check_scales() reads predict_scene's `scales`, Engine.predict_scene(scales=) is their user.
 
+Blending is the one path on which neighbouring windows share pixels: blend_table() hands out each group's full footprint in place
+of an owned rectangle, blend_weight() is a linear taper per axis in 1/256 (flat towards a scene border, never below 16), and
+rua_scene_accumulate_blend adds (wy wx v + 32768) >> 16 of the K views' sum v to the same accumulator with integer atomics
+(host_accumulate_blend is its definition: integer sums do not depend on the order); check_blend_budget() keeps the int32 sums in
+range, Engine.predict_scene(blend="linear") is their user.
+
 Class counts close the loop on the dataset: host_class_counts() says how many pixels of each class (and how many of none, a
 value >= C) lie in each window of a table, rua_scene_class_counts is its kernel on the resident class maps and
 ScenePool.class_counts() its user; class_weights() turns the counts of the training rows into the reference's weighted-CE weights
@@ -766,19 +772,8 @@ def scale_table(shape_hw: Sequence[int], patch, footprint, stride, views=(0,)):
     layout - are the affine rows (scene 0) that cut the footprint into a PH x PW window under view code c:
     A = diag(a_y, a_x) SYMMETRY[c], a_y = rint(65536 FH / PH), a_x likewise, the origin by affine_rows' rule with the footprint's
     centre in place of the window's.  All integers.  With F == P and code 0 host_windows_affine of the rows is host_windows of the cover."""
-    ph, pw = _patch2(patch)
-    fh, fw = _patch2(footprint)
-    pair = stride if isinstance(stride, (tuple, list)) and len(stride) == 2 else (stride, stride)
-    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in pair):
-        raise ValueError(f"stride {stride!r} must be an integer (or a pair of them: rows, columns)")
-    for P, F, S, what in ((ph, fh, int(pair[0]), "rows"), (pw, fw, int(pair[1]), "columns")):
-        if not (1 <= F and P <= 4 * F and F <= 4 * P):
-            raise ValueError(f"scale_table: {what}: footprint {F}, patch {P} (1 <= F, P <= 4 F, F <= 4 P)")
-        if not 1 <= S <= P:
-            raise ValueError(f"scale_table: {what}: stride {S}, patch {P} (1 <= stride <= patch)")
+    ph, pw, fh, fw, rows4, own4 = _scale_cover(shape_hw, patch, footprint, stride)
     v = check_views(views, (ph, pw))
-    sf = tuple(min(max((2 * int(S) * F + P) // (2 * P), 1), F) for S, F, P in ((pair[0], fh, ph), (pair[1], fw, pw)))
-    rows4, own4 = predict_table(shape_hw, (fh, fw), sf)
     G, K = len(rows4), len(v)
     r, c = rows4[:, 1].astype(np.int64), rows4[:, 2].astype(np.int64)
     own = own4.astype(np.int64)
@@ -793,6 +788,29 @@ def scale_table(shape_hw: Sequence[int], patch, footprint, stride, views=(0,)):
     if (np.abs(rows7) > 2 ** 31 - 1).any():
         raise ValueError("scale_table: a row leaves the int32 range")
     return rows7.reshape(G * K, 7).astype(np.int32), own.astype(np.int32)
+
+
+def _scaled_stride(patch, footprint, stride, fn: str = "scale_table"):
+    """(PH, PW, FH, FW, (SFH, SFW)): scale_table's arguments read, and the stride scaled to the footprint, SF = clamp(rint(stride F / P), 1, F)."""
+    ph, pw = _patch2(patch)
+    fh, fw = _patch2(footprint)
+    pair = stride if isinstance(stride, (tuple, list)) and len(stride) == 2 else (stride, stride)
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in pair):
+        raise ValueError(f"stride {stride!r} must be an integer (or a pair of them: rows, columns)")
+    for P, F, S, what in ((ph, fh, int(pair[0]), "rows"), (pw, fw, int(pair[1]), "columns")):
+        if not (1 <= F and P <= 4 * F and F <= 4 * P):
+            raise ValueError(f"{fn}: {what}: footprint {F}, patch {P} (1 <= F, P <= 4 F, F <= 4 P)")
+        if not 1 <= S <= P:
+            raise ValueError(f"{fn}: {what}: stride {S}, patch {P} (1 <= stride <= patch)")
+    sf = tuple(min(max((2 * int(S) * F + P) // (2 * P), 1), F) for S, F, P in ((pair[0], fh, ph), (pair[1], fw, pw)))
+    return ph, pw, fh, fw, sf
+
+
+def _scale_cover(shape_hw, patch, footprint, stride):
+    """(PH, PW, FH, FW, rows4, own4): the cover predict_table(shape_hw, F, SF) of one pass, the stride scaled to the footprint."""
+    ph, pw, fh, fw, sf = _scaled_stride(patch, footprint, stride)
+    rows4, own4 = predict_table(shape_hw, (fh, fw), sf)
+    return ph, pw, fh, fw, rows4, own4
 
 
 def check_scales(scales, patch, shape_hw=None) -> Optional[Tuple[Tuple[int, int], ...]]:
@@ -838,29 +856,30 @@ def _axis_taps(lo: int, hi: int, o: int, a: int, n: int):
     return i0, np.minimum(i0 + 1, n - 1), w & 255
 
 
-def check_accumulate(shapes: Sequence[Sequence[int]], rows7, own, K, patch, num_classes: int = 1):
-    """(rows7 [G*K][7], own [G][4]) as contiguous int32 arrays; ValueError, in rua_scene_accumulate's own words, for the first violation."""
+def _check_accumulate(fn: str, shapes, rows7, own, K, patch, num_classes: int, one_size: bool):
+    """check_accumulate and check_accumulate_blend under the entry point's name `fn`; one_size: the non-empty rectangles have one size."""
     ph, pw = _patch2(patch)
+    size, first = None, 0
     t, o = np.asarray(rows7), np.asarray(own)
     if t.ndim != 2 or t.shape[1] != 7 or not np.issubdtype(t.dtype, np.integer) or not _is_table4(o):
-        raise ValueError(f"{_ACC} takes integer [G*K][7] rows (scene, y0, x0, a_yy, a_yx, a_xy, a_xx) and [G][4] rows (r0, r1, c0, c1), "
+        raise ValueError(f"{fn} takes integer [G*K][7] rows (scene, y0, x0, a_yy, a_yx, a_xy, a_xx) and [G][4] rows (r0, r1, c0, c1), "
                          f"got {t.dtype} {t.shape} and {o.dtype} {o.shape}")
     if isinstance(K, bool) or not isinstance(K, (int, np.integer)):
         raise ValueError(f"K {K!r} must be an integer")
     K, n, G = int(K), len(shapes), o.shape[0]
     if n < 1 or G < 1:
-        raise ValueError(f"{_ACC}: nscenes {n}, G {G} (both >= 1)")
+        raise ValueError(f"{fn}: nscenes {n}, G {G} (both >= 1)")
     if not 1 <= K <= MAX_VIEWS:
-        raise ValueError(f"{_ACC}: K {K} outside 1..8")
+        raise ValueError(f"{fn}: K {K} outside 1..8")
     if t.shape[0] != G * K:
-        raise ValueError(f"{_ACC}: {t.shape[0]} window rows for {G} groups of K {K} views (K rows per ownership row)")
+        raise ValueError(f"{fn}: {t.shape[0]} window rows for {G} groups of K {K} views (K rows per ownership row)")
     if not 1 <= num_classes <= MAX_CLASSES:
-        raise ValueError(f"{_ACC}: C {num_classes} outside 1..64")
+        raise ValueError(f"{fn}: C {num_classes} outside 1..64")
     if not (1 <= ph <= MAX_PATCH and 1 <= pw <= MAX_PATCH):
-        raise ValueError(f"{_ACC}: PH {ph}, PW {pw} (1 <= PH, PW <= 512)")
+        raise ValueError(f"{fn}: PH {ph}, PW {pw} (1 <= PH, PW <= 512)")
     for s, shp in enumerate(shapes):
         if not (1 <= int(shp[0]) <= MAX_SCENE and 1 <= int(shp[1]) <= MAX_SCENE):
-            raise ValueError(f"{_ACC}: scene {s}: size {int(shp[0])} x {int(shp[1])} (1 <= H, W <= 16384)")
+            raise ValueError(f"{fn}: scene {s}: size {int(shp[0])} x {int(shp[1])} (1 <= H, W <= 16384)")
     rows, owns = t.tolist(), o.tolist()
     for g in range(G):
         s0 = rows[g * K][0]
@@ -868,29 +887,38 @@ def check_accumulate(shapes: Sequence[Sequence[int]], rows7, own, K, patch, num_
             k = g * K + v
             s, _, _, ayy, ayx, axy, axx = rows[k]
             if not 0 <= s < n:
-                raise ValueError(f"{_ACC}: row {k}: scene {s} outside 0..{n - 1}")
+                raise ValueError(f"{fn}: row {k}: scene {s} outside 0..{n - 1}")
             if s != s0:
-                raise ValueError(f"{_ACC}: row {k}: scene {s}, but its group {g} is scene {s0}")
+                raise ValueError(f"{fn}: row {k}: scene {s}, but its group {g} is scene {s0}")
             keeps, turns = ayx == 0 and axy == 0 and ayy != 0 and axx != 0, ayy == 0 and axx == 0 and ayx != 0 and axy != 0
             if not (keeps or turns):
-                raise ValueError(f"{_ACC}: row {k}: matrix ({ayy}, {ayx}, {axy}, {axx}) is not axis-aligned "
+                raise ValueError(f"{fn}: row {k}: matrix ({ayy}, {ayx}, {axy}, {axx}) is not axis-aligned "
                                  "(a_yx = a_xy = 0 or a_yy = a_xx = 0, the other two nonzero)")
             if turns and ph != pw:
-                raise ValueError(f"{_ACC}: row {k}: matrix ({ayy}, {ayx}, {axy}, {axx}) transposes and needs a square patch (got {ph} x {pw})")
+                raise ValueError(f"{fn}: row {k}: matrix ({ayy}, {ayx}, {axy}, {axx}) transposes and needs a square patch (got {ph} x {pw})")
         H, W = int(shapes[s0][0]), int(shapes[s0][1])
         r0, r1, c0, c1 = owns[g]
         if not (0 <= r0 <= r1 <= H and 0 <= c0 <= c1 <= W):
-            raise ValueError(f"{_ACC}: group {g}: rectangle rows {r0}..{r1}, columns {c0}..{c1} outside its {H} x {W} scene")
+            raise ValueError(f"{fn}: group {g}: rectangle rows {r0}..{r1}, columns {c0}..{c1} outside its {H} x {W} scene")
         if r0 == r1 or c0 == c1:
             continue
+        if one_size and size is None:
+            size, first = (r1 - r0, c1 - c0), g
+        if one_size and (r1 - r0, c1 - c0) != size:
+            raise ValueError(f"{fn}: group {g}: rectangle of {r1 - r0} x {c1 - c0}, but group {first} has {size[0]} x {size[1]} (the footprints of one call have one size)")
         for v in range(K):
             k = g * K + v
             _, y0, x0, ayy, ayx, axy, axx = rows[k]
             ay, ny, ax, nx = (ayy, ph, axx, pw) if ayx == 0 else (ayx, pw, axy, ph)
             ends = [(_axis_w(y, y0, ay), ny) for y in (r0, r1 - 1)] + [(_axis_w(x, x0, ax), nx) for x in (c0, c1 - 1)]
             if any(not -256 <= w <= m * 256 for w, m in ends):
-                raise ValueError(f"{_ACC}: row {k}: rectangle rows {r0}..{r1}, columns {c0}..{c1} of group {g} leaves the window's footprint")
+                raise ValueError(f"{fn}: row {k}: rectangle rows {r0}..{r1}, columns {c0}..{c1} of group {g} leaves the window's footprint")
     return np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(o, dtype=np.int32)
+
+
+def check_accumulate(shapes: Sequence[Sequence[int]], rows7, own, K, patch, num_classes: int = 1):
+    """(rows7 [G*K][7], own [G][4]) as contiguous int32 arrays; ValueError, in rua_scene_accumulate's own words, for the first violation."""
+    return _check_accumulate(_ACC, shapes, rows7, own, K, patch, num_classes, False)
 
 
 def host_accumulate(p: np.ndarray, rows7, own, shapes: Sequence[Sequence[int]], K: int, acc: Optional[Sequence[np.ndarray]] = None) -> List[np.ndarray]:
@@ -907,11 +935,16 @@ def host_accumulate(p: np.ndarray, rows7, own, shapes: Sequence[Sequence[int]], 
     acc[scene][y, x, c] += the sum of val over the K views, for every (y, x) of the rectangle and every channel.  Integers from the
     first step on: the order of views, groups and passes cannot matter.  An empty rectangle adds nothing; a rectangle must lie in
     its scene and in every view's footprint (the unclamped w of its first and last row and column in [-256, 256 n])."""
+    return _accumulate(p, rows7, own, shapes, K, acc, False)
+
+
+def _accumulate(p, rows7, own, shapes, K, acc, blend: bool):
+    """host_accumulate (blend False) and host_accumulate_blend (blend True): the K views' sums of every group, weighted or not, added to acc."""
     p = np.asarray(p)
     if p.ndim != 4 or p.dtype != np.float32:
         raise ValueError(f"p is float32 [G*K][PH][PW][C], got {p.dtype} {p.shape}")
     PH, PW, Cn = (int(v) for v in p.shape[1:])
-    t, o = check_accumulate(shapes, rows7, own, K, (PH, PW), Cn)
+    t, o = _check_accumulate(_ACCB if blend else _ACC, shapes, rows7, own, K, (PH, PW), Cn, blend)
     K = int(K)
     if len(p) != len(t):
         raise ValueError(f"p is [G*K][PH][PW][C] with one view per table row, got {p.shape} for {len(t)} rows")
@@ -943,6 +976,10 @@ def host_accumulate(p: np.ndarray, rows7, own, shapes: Sequence[Sequence[int]], 
             at = lambda u, v: q[u[:, None], v[None, :]]
             top, bot = (256 - fx) * at(u0, v0) + fx * at(u0, v1), (256 - fx) * at(u1, v0) + fx * at(u1, v1)
             total += ((256 - fy) * top + fy * bot + 32768) >> 16
+        if blend:
+            H, W = int(shapes[rows[g * K][0]][0]), int(shapes[rows[g * K][0]][1])
+            wy, wx = _blend_axis(0, r1 - r0, r1 - r0, r0 == 0, r1 == H), _blend_axis(0, c1 - c0, c1 - c0, c0 == 0, c1 == W)
+            total = ((wy[:, None] * wx[None, :])[:, :, None] * total + 32768) >> 16
         acc[rows[g * K][0]][r0:r1, c0:c1] += total.astype(np.int32)
     return acc
 
@@ -975,6 +1012,91 @@ def host_argmax(acc: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndar
         keep = true < Cn
         cm += np.bincount(true[keep] * Cn + m[keep].astype(np.int64), minlength=Cn * Cn).reshape(Cn, Cn)
     return maps, cm
+
+
+# ---- blended whole-scene prediction: overlapping footprints added under a linear taper, in integers ----------------------------------
+_ACCB = "rua_scene_accumulate_blend"
+BLEND_MODES = ("linear",)
+BLEND_ONE, BLEND_FLOOR = 256, 16
+BLEND_BUDGET = 32768                            # K * footprints per pixel stay below it: a contribution is at most K * 65536, the sum int32
+
+
+def blend_weight(t: int, F: int, flat_lo: bool, flat_hi: bool) -> int:
+    """The weight, out of 256, of position t (0 <= t < F) along one axis of a footprint of F scene pixels: a linear taper
+    max(16, (256 (2 min(t, F - 1 - t) + 1)) // F), and 256 on the half that touches the scene's low (flat_lo: 2 t + 1 <= F) or high
+    (flat_hi: 2 t + 1 >= F) border, where no other footprint covers the pixel better.  With a stride of F / 2 and even F the tapers of
+    neighbouring footprints sum to 256 wherever the floor does not bind; the floor keeps 8 bits of a probability at a footprint's corner."""
+    t, F = int(t), int(F)
+    if not 0 <= t < F:
+        raise ValueError(f"blend_weight: position {t} outside 0..{F - 1}")
+    if (flat_lo and 2 * t + 1 <= F) or (flat_hi and 2 * t + 1 >= F):
+        return BLEND_ONE
+    return max(BLEND_FLOOR, (BLEND_ONE * (2 * min(t, F - 1 - t) + 1)) // F)
+
+
+def _blend_axis(lo: int, hi: int, F: int, flat_lo: bool, flat_hi: bool) -> np.ndarray:
+    """blend_weight of the positions lo..hi-1, int64 [hi - lo]."""
+    t = np.arange(lo, hi, dtype=np.int64)
+    w = np.maximum(BLEND_FLOOR, (BLEND_ONE * (2 * np.minimum(t, F - 1 - t) + 1)) // F)
+    flat = np.zeros(len(t), bool)
+    if flat_lo:
+        flat |= 2 * t + 1 <= F
+    if flat_hi:
+        flat |= 2 * t + 1 >= F
+    return np.where(flat, BLEND_ONE, w)
+
+
+def blend_table(shape_hw: Sequence[int], patch, footprint, stride, views=(0,)):
+    """One pass of a blended prediction: (rows7 int32 [G*K][7], foot int32 [G][4]).  rows7 is scale_table's; foot takes the place of its
+    owned rectangle: the FULL footprint (r, r + FH, c, c + FW) of each group in absolute scene coordinates.  Footprints never leave
+    the scene, and they overlap: host_accumulate_blend weights them."""
+    rows7, _ = scale_table(shape_hw, patch, footprint, stride, views)
+    _, _, fh, fw, rows4, _ = _scale_cover(shape_hw, patch, footprint, stride)
+    r, c = rows4[:, 1].astype(np.int64), rows4[:, 2].astype(np.int64)
+    return rows7, np.stack([r, r + fh, c, c + fw], 1).astype(np.int32)
+
+
+def check_accumulate_blend(shapes: Sequence[Sequence[int]], rows7, foot, K, patch, num_classes: int = 1):
+    """(rows7 [G*K][7], foot [G][4]) as contiguous int32 arrays; ValueError, in rua_scene_accumulate_blend's own words, for the first
+    violation: everything check_accumulate refuses, and non-empty rectangles of two sizes in one call (a call is one pass)."""
+    return _check_accumulate(_ACCB, shapes, rows7, foot, K, patch, num_classes, True)
+
+
+def host_accumulate_blend(p: np.ndarray, rows7, foot, shapes: Sequence[Sequence[int]], K: int, acc: Optional[Sequence[np.ndarray]] = None) -> List[np.ndarray]:
+    """The numpy definition of what rua_scene_accumulate_blend adds: host_accumulate's arguments, but foot [G][4] holds each group's
+    FULL footprint (r0, r1, c0, c1), and footprints of one call overlap.  For each group and each scene pixel (y, x) of its footprint
+    v[c] is the sum over the K views of host_accumulate's bilinear Q16 sample (the same coordinate, taps and (.. + 32768) >> 16 per
+    view), and
+        acc[scene][y, x, c] += (wy wx v[c] + 32768) >> 16,   wy = blend_weight(y - r0, r1 - r0, r0 == 0, r1 == H), wx likewise for columns.
+    The weight lives in scene space: the K views of a group share it, flips and transpositions do not touch it.  A contribution is
+    at most K 65536 (check_blend_budget keeps the int32 sums in range); integer sums are the same in any order of groups and calls."""
+    return _accumulate(p, rows7, foot, shapes, K, acc, True)
+
+
+def _axis_depth(L: int, F: int, S: int) -> int:
+    """The greatest number of footprints of _axis_cover(L, F, S) that cover one pixel of the axis."""
+    o, _ = _axis_cover(L, F, S)
+    d = np.zeros(L + 1, np.int64)
+    np.add.at(d, o, 1)
+    np.add.at(d, o + F, -1)
+    return int(np.cumsum(d).max())
+
+
+def check_blend_budget(shape_hw: Sequence[int], patch, footprints, stride, K) -> int:
+    """K * the sum over the passes (one per footprint of `footprints`, covered as blend_table covers) of cover_y * cover_x, the greatest
+    number of footprints per axis over one pixel; ValueError unless it is below 32768: the accumulator is int32 and a contribution
+    reaches K * 65536."""
+    H, W = int(shape_hw[0]), int(shape_hw[1])
+    total = 0
+    for fp in footprints:
+        _, _, fh, fw, sf = _scaled_stride(patch, fp, stride, "check_blend_budget")
+        if fh > H or fw > W:
+            raise ValueError(f"check_blend_budget: footprint {fh} x {fw} is larger than the {H} x {W} scene")
+        total += _axis_depth(H, fh, sf[0]) * _axis_depth(W, fw, sf[1])
+    if not int(K) * total < BLEND_BUDGET:
+        raise ValueError(f"check_blend_budget: K {int(K)} views times {total} footprints over one pixel (cover_y * cover_x, summed over the passes) "
+                         f"is {int(K) * total}: the int32 accumulator takes fewer than {BLEND_BUDGET}; use a larger stride")
+    return int(K) * total
 
 
 # ---- class counts of windows: what class weights and a balance filter are functions of ------------------------------------------
