@@ -472,6 +472,55 @@ int rua_adam_step_w(float* theta, float* g, float* m, float* v, int64_t n, float
 int rua_sgd_step_w(float* theta, float* g, float* vel, int64_t n, float lr, const float* lr_dev, float momentum, float grad_scale,
                    int zero_grad, void* wcopy_bf16, void* stream);
 
+/* ---- gradient clipping, decoupled weight decay and the non-finite step skip (clip.py holds the host definitions) ----------------
+ * The flat parameter buffer is described by a CHUNK TABLE built once on the host (clip.build_chunk_table): every entry of the parameter
+ * store is cut into chunks of at most RUA_OPT_CHUNK elements; off is a multiple of 16 elements (slices are 64-byte aligned), a chunk never
+ * spans entries and the padding between slices belongs to no chunk.  A VARIABLE is one Keras name (the cin segments of a split kernel are
+ * one variable): rows chunk_begin <= k < chunk_end of the chunk table, and a decay flag.
+ * RUA_OPT_CHUNK = 8192: one chunk is one 256-thread block, eight 16-byte accesses per thread and stream - enough loads in flight per
+ * thread to cover HBM latency without a grid-stride loop - while the partial count stays small: the largest kernel of the flagship graph
+ * (3x3x1024x1024, 9.4 M elements) is 1152 chunks, which ONE thread of the finisher adds in order (the price of a fixed summation order). */
+#define RUA_OPT_CHUNK 8192
+typedef struct rua_opt_chunk { int64_t off; int32_t len; int32_t var; } rua_opt_chunk;
+typedef struct rua_opt_var { int32_t chunk_begin, chunk_end, decay, pad; } rua_opt_var;
+#define RUA_CLIP_NONE 0
+#define RUA_CLIP_GLOBAL_NORM 1
+#define RUA_CLIP_NORM 2
+#define RUA_CLIP_VALUE 3
+/* partials[k] = sum of (double)g[i]^2 over chunk k, one block per chunk, no atomics: a lane adds its elements in index order, the 64 lanes
+ * of a wave are folded by a fixed butterfly, the four waves are added in order.  The square of an fp32 value is exact in fp64, so the
+ * result is the same bits on every run and every replay.  g 16-byte aligned; 0 < len <= RUA_OPT_CHUNK and off % 4 == 0 are the caller's
+ * contract (the table is built by clip.build_chunk_table, which checks them). */
+int rua_grad_sumsq(const float* g, const rua_opt_chunk* chunks, int n_chunks, double* partials, void* stream);
+/* One block.  var_sumsq[v] = partials of variable v added in chunk order; total = var_sumsq added in variable order.
+ *   norm        = grad_scale * sqrt(total)                       (per variable: grad_scale * sqrt(var_sumsq[v]))
+ *   coef[v]     = (float)(c / max(norm, c))                      RUA_CLIP_GLOBAL_NORM: the same value for every v; RUA_CLIP_NORM: from the
+ *                                                                variable's own norm; RUA_CLIP_NONE / RUA_CLIP_VALUE: 1.  A zero norm gives 1.
+ *   flag[0]     = skip_nonfinite && !isfinite(total)             (int32: 1 = the optimizer launched next leaves theta and the moments alone)
+ *   report[0]   = this step's global norm, report[1] = the smallest coefficient of this step,
+ *   report[2]  += flag[0] (steps skipped), report[3] += (report[1] < 1 && !flag[0]) (steps clipped by a norm; clipvalue does not count)
+ * c > 0 is required in the two norm modes and ignored otherwise.  n_chunks: the rows of the chunk table (the partials); the variables'
+ * chunk ranges must tile [0, n_chunks) in order, as clip.build_chunk_table leaves them. */
+int rua_clip_finish(const double* partials, int n_chunks, const rua_opt_var* vars, int n_vars, int mode, double c, double grad_scale,
+                    int skip_nonfinite, double* var_sumsq, float* coef, int32_t* flag, double* report, void* stream);
+/* The optimizers over the chunk table instead of the flat range; padding is never read or written.  Per element of a chunk of variable v:
+ *   th1 = vars[v].decay && weight_decay != 0 ? th - th * d : th,      d = (float)(weight_decay * lr_state[1])   (decoupled decay; lr_state
+ *                                                                      is the device pair of the rate kernel: [1] = the BASE rate)
+ *   gg  = clampv((g * grad_scale) * coef[v]),                          clampv(x) = x < -c ? -c : x > c ? c : x for clipvalue = c > 0 (a NaN
+ *                                                                      stays a NaN), the identity for clipvalue <= 0
+ *   Adam: m, v, theta as the flat kernel computes them, on th1 and gg;  SGD: vel = momentum * vel - lr * gg, theta = th1 + vel
+ * flag (NULL: never) != 0 skips the step: theta, the moments keep their bits, no decay; g is still zeroed (zero_grad) and wcopy_bf16 (NULL:
+ * none) still receives bf16(theta).  lr_dev: the device rate of the rate kernel (required).  Buffers 16-byte aligned, wcopy 8-byte. */
+int rua_adam_step_seg(float* theta, float* g, float* m, float* v, const rua_opt_chunk* chunks, int n_chunks, const rua_opt_var* vars,
+                      const float* coef, const int32_t* flag, const float* lr_dev, const double* lr_state, float beta1, float beta2, float eps,
+                      float grad_scale, float clipvalue, double weight_decay, int zero_grad, void* wcopy_bf16, void* stream);
+int rua_sgd_step_seg(float* theta, float* g, float* vel, const rua_opt_chunk* chunks, int n_chunks, const rua_opt_var* vars,
+                     const float* coef, const int32_t* flag, const float* lr_dev, const double* lr_state, float momentum,
+                     float grad_scale, float clipvalue, double weight_decay, int zero_grad, void* wcopy_bf16, void* stream);
+/* dst[0 .. n) = src[0 .. n) if flag is NULL or flag[0] != 0, nothing otherwise: the BatchNorm moving statistics' backup when a step begins
+ * (flag NULL) and their restore behind a skipped step (flag = the finisher's).  A kernel, not a copy node: a captured step holds kernels only. */
+int rua_state_copy(float* dst, const float* src, int64_t n, const int32_t* flag, void* stream);
+
 /* ---- multitask training targets from uint8 patches (labels.py; the reference's preprocess_save_patches_ISPRS.py:206-228,
  * multitasking_utils.py:6-35) ------------------------------------------------------------------------------------------------
  * img [N][H][W][Cin] and cls [N][H][W] are uint8 (4-byte aligned); x [N][H][W][Cin], seg / bound / dist [N][H][W][C] and

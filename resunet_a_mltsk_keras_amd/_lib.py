@@ -175,6 +175,11 @@ _SIGS = {
     "rua_sgd_step": ([vp, vp, vp, i64, f32, vp, f32, f32, i32, vp], i32),
     "rua_adam_step_w": ([vp, vp, vp, vp, i64, f32, vp, f32, f32, f32, f32, i32, vp, vp], i32),
     "rua_sgd_step_w": ([vp, vp, vp, i64, f32, vp, f32, f32, i32, vp, vp], i32),
+    "rua_grad_sumsq": ([vp, vp, i32, vp, vp], i32),
+    "rua_clip_finish": ([vp, i32, vp, i32, i32, f64, f64, i32, vp, vp, vp, vp, vp], i32),
+    "rua_adam_step_seg": ([vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f64, i32, vp, vp], i32),
+    "rua_sgd_step_seg": ([vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, f64, i32, vp, vp], i32),
+    "rua_state_copy": ([vp, vp, i64, vp, vp], i32),
     "rua_tanimoto_sums_void": ([vp, vp, vp, i32, i64, i32, vp, vp], i32),
     "rua_head_fwd_loss_void": ([vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i64, i32, i32, i32, i32, vp, vp], i32),
     "rua_pixel_loss_void": ([i32, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp], i32),

@@ -682,3 +682,233 @@ extern "C" int rua_sgd_step(float* theta, float* g, float* vel, int64_t n, float
                             int zero_grad, void* stream) {
   return rua_sgd_step_w(theta, g, vel, n, lr, lr_dev, momentum, grad_scale, zero_grad, nullptr, stream);
 }
+
+// ---- clipping, decoupled decay and the non-finite step skip: the optimizers over a chunk table (include/rua_hip.h) ------------------------
+// One 256-thread block per chunk of at most RUA_OPT_CHUNK elements.  Fixed reduction order, no atomics: a lane adds the squares of its
+// 16-byte groups in index order (x, y, z, w), the ragged tail (len % 4 elements) goes to lanes 0 .. 2 of wave 0 after their groups, the
+// lanes of a wave are folded by the xor butterfly 32, 16, .. 1, thread 0 adds the four waves in order.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, const rua_opt_chunk* __restrict__ chunks, double* __restrict__ partials) {
+  __shared__ double sh[4];
+  const rua_opt_chunk ck = chunks[blockIdx.x];
+  const float* gp = g + ck.off;
+  const int n4 = ck.len >> 2;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    const float4 q = reinterpret_cast<const float4*>(gp)[i];
+    acc += (double)q.x * (double)q.x; acc += (double)q.y * (double)q.y; acc += (double)q.z * (double)q.z; acc += (double)q.w * (double)q.w;
+  }
+  const int t = (n4 << 2) + threadIdx.x;
+  if (t < ck.len) { const double x = (double)gp[t]; acc += x * x; }
+  acc = wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+extern "C" int rua_grad_sumsq(const float* g, const rua_opt_chunk* chunks, int n_chunks, double* partials, void* stream) {
+  RUA_CHECK_ARG(g && chunks && partials && n_chunks > 0, "rua_grad_sumsq: bad arguments");
+  RUA_CHECK_ARG(((size_t)g & 15) == 0 && ((size_t)chunks & 15) == 0 && ((size_t)partials & 7) == 0, "rua_grad_sumsq: g and the chunk table must be 16-byte aligned");
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, g, chunks, partials);
+  RUA_LAUNCH_CHECK("rua_grad_sumsq");
+  return RUA_OK;
+}
+
+// One block.  The partials pass through LDS in tiles of FIN_TILE (coalesced loads by all threads: a thread that walked its variable's partials in
+// global memory paid one exposed load latency per chunk, 105 us for the flagship table's 5519 chunks); thread v % 256 adds variable v's partials of
+// the tile in chunk order onto its running sum (var_sumsq[v], which only it touches), so the order of every addition is what a serial loop's is.
+// The variables' sums pass through LDS the same way and thread 0 adds them in order.  The smallest coefficient is a min: any order gives the same.
+#define FIN_TILE 4096
+// s + x[0] + x[1] + ... in index order; the LDS reads go out eight at a time so that their latency is paid once per eight additions
+__device__ __forceinline__ double add_in_order(double s, const double* x, int n) {
+  int k = 0;
+  for (; k + 8 <= n; k += 8) {
+    double t[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) t[j] = x[k + j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += t[j];
+  }
+  for (; k < n; ++k) s += x[k];
+  return s;
+}
+__global__ __launch_bounds__(256) void clip_finish_kernel(const double* __restrict__ partials, int n_chunks, const rua_opt_var* __restrict__ vars, int n_vars,
+                                                          int mode, double c, double gs, int skip_nonfinite, double* __restrict__ var_sumsq,
+                                                          float* __restrict__ coef, int32_t* __restrict__ flag, double* __restrict__ report) {
+  __shared__ double tile[FIN_TILE];
+  __shared__ double s_total;
+  __shared__ float s_coef, s_min[4];
+  __shared__ int s_skip;
+  const int tid = threadIdx.x;
+  for (int t0 = 0; t0 < n_chunks; t0 += FIN_TILE) {
+    const int tn = n_chunks - t0 < FIN_TILE ? n_chunks - t0 : FIN_TILE;
+    for (int i = tid; i < tn; i += 256) tile[i] = partials[t0 + i];
+    __syncthreads();
+    for (int v = tid; v < n_vars; v += 256) {
+      const rua_opt_var vr = vars[v];
+      const int a = vr.chunk_begin > t0 ? vr.chunk_begin : t0, b = vr.chunk_end < t0 + tn ? vr.chunk_end : t0 + tn;
+      if (t0 == 0 || a < b) {
+        double s = vr.chunk_begin >= t0 ? 0.0 : var_sumsq[v];              // the variable's first tile starts its sum
+        var_sumsq[v] = add_in_order(s, tile + (a - t0), b > a ? b - a : 0);
+      }
+    }
+    __syncthreads();
+  }
+  double total = 0.0;                                                       // thread 0's
+  for (int t0 = 0; t0 < n_vars; t0 += FIN_TILE) {
+    const int tn = n_vars - t0 < FIN_TILE ? n_vars - t0 : FIN_TILE;
+    for (int i = tid; i < tn; i += 256) tile[i] = var_sumsq[t0 + i];
+    __syncthreads();
+    if (tid == 0) total = add_in_order(total, tile, tn);
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double norm = gs * sqrt(total);
+    s_total = norm;
+    s_coef = mode == RUA_CLIP_GLOBAL_NORM ? (float)(c / fmax(norm, c)) : 1.f;
+    s_skip = (skip_nonfinite && !isfinite(total)) ? 1 : 0;
+  }
+  __syncthreads();
+  float mn = s_coef;
+  for (int v = tid; v < n_vars; v += 256) {
+    float cf = s_coef;
+    if (mode == RUA_CLIP_NORM) cf = (float)(c / fmax(gs * sqrt(var_sumsq[v]), c));
+    coef[v] = cf;
+    mn = cf < mn ? cf : mn;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const float w = __shfl_xor(mn, o, 64); mn = w < mn ? w : mn; }
+  if ((tid & 63) == 0) s_min[tid >> 6] = mn;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) mn = s_min[w] < mn ? s_min[w] : mn;
+    const int skip = s_skip;
+    flag[0] = skip;
+    report[0] = s_total;
+    report[1] = (double)mn;
+    report[2] += (double)skip;
+    report[3] += (mn < 1.f && !skip) ? 1.0 : 0.0;
+  }
+}
+extern "C" int rua_clip_finish(const double* partials, int n_chunks, const rua_opt_var* vars, int n_vars, int mode, double c, double grad_scale,
+                               int skip_nonfinite, double* var_sumsq, float* coef, int32_t* flag, double* report, void* stream) {
+  RUA_CHECK_ARG(partials && vars && var_sumsq && coef && flag && report && n_vars > 0 && n_chunks > 0, "rua_clip_finish: bad arguments");
+  RUA_CHECK_ARG(mode >= RUA_CLIP_NONE && mode <= RUA_CLIP_VALUE, "rua_clip_finish: unknown mode %d", mode);
+  RUA_CHECK_ARG((mode != RUA_CLIP_GLOBAL_NORM && mode != RUA_CLIP_NORM) || c > 0.0, "rua_clip_finish: the clip norm must be positive");
+  RUA_CHECK_ARG((((size_t)partials | (size_t)var_sumsq | (size_t)report) & 7) == 0 && ((size_t)vars & 15) == 0 && (((size_t)coef | (size_t)flag) & 3) == 0,
+                "rua_clip_finish: misaligned buffers");
+  hipLaunchKernelGGL(clip_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_chunks, vars, n_vars, mode, c, grad_scale, skip_nonfinite, var_sumsq,
+                     coef, flag, report);
+  RUA_LAUNCH_CHECK("rua_clip_finish");
+  return RUA_OK;
+}
+
+// The segmented optimizers.  ADAM: m2 is Adam's v; SGD: m is the velocity and m2 is not touched.  The element arithmetic of the flat kernels with the
+// decay in front and the coefficient / clamp on the gradient; a skipped step stores only the zeroed gradient and the bf16 copy of the unchanged theta.
+struct seg_args {
+  float lr, b1, b2, eps, mu, gs, cv, d;
+};
+template <bool ADAM>
+__device__ __forceinline__ void seg_update(const seg_args& a, bool dec, float cf, float g_, float& mm, float& vv, float& tt) {
+  if (dec) tt = tt - tt * a.d;
+  float gg = (g_ * a.gs) * cf;
+  if (a.cv > 0.f) gg = gg < -a.cv ? -a.cv : (gg > a.cv ? a.cv : gg);
+  if constexpr (ADAM) {
+    mm = a.b1 * mm + (1.f - a.b1) * gg;
+    vv = a.b2 * vv + (1.f - a.b2) * gg * gg;
+    tt -= a.lr * mm / (sqrtf(vv) + a.eps);
+  } else {
+    mm = a.mu * mm - a.lr * gg;
+    tt = tt + mm;
+  }
+}
+template <bool ADAM, bool WC>
+__global__ __launch_bounds__(256) void opt_seg_kernel(float* __restrict__ th, float* __restrict__ g, float* __restrict__ m, float* __restrict__ m2,
+                                                      const rua_opt_chunk* __restrict__ chunks, const rua_opt_var* __restrict__ vars, const float* __restrict__ coef,
+                                                      const int32_t* __restrict__ flag, const float* __restrict__ lr_dev, const double* __restrict__ lr_state,
+                                                      seg_args a, double wd, int zero, bf16_t* __restrict__ wcopy) {
+  const rua_opt_chunk ck = chunks[blockIdx.x];
+  const bool skip = flag != nullptr && flag[0] != 0;
+  const bool dec = wd != 0.0 && vars[ck.var].decay != 0;
+  const float cf = coef[ck.var];
+  a.lr = lr_dev[0];
+  a.d = dec ? (float)(wd * lr_state[1]) : 0.f;
+  th += ck.off; g += ck.off; m += ck.off;
+  if constexpr (ADAM) m2 += ck.off;
+  if constexpr (WC) wcopy += ck.off;
+  const int n4 = ck.len >> 2;
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    float4 t4 = reinterpret_cast<float4*>(th)[i];
+    if (!skip) {
+      const float4 g4 = reinterpret_cast<const float4*>(g)[i];
+      float4 m4 = reinterpret_cast<float4*>(m)[i], v4 = z4;
+      if constexpr (ADAM) v4 = reinterpret_cast<float4*>(m2)[i];
+      seg_update<ADAM>(a, dec, cf, g4.x, m4.x, v4.x, t4.x); seg_update<ADAM>(a, dec, cf, g4.y, m4.y, v4.y, t4.y);
+      seg_update<ADAM>(a, dec, cf, g4.z, m4.z, v4.z, t4.z); seg_update<ADAM>(a, dec, cf, g4.w, m4.w, v4.w, t4.w);
+      reinterpret_cast<float4*>(m)[i] = m4; reinterpret_cast<float4*>(th)[i] = t4;
+      if constexpr (ADAM) reinterpret_cast<float4*>(m2)[i] = v4;
+    }
+    if (zero) reinterpret_cast<float4*>(g)[i] = z4;
+    if constexpr (WC) reinterpret_cast<uint2*>(wcopy)[i] = make_uint2(ET<bf16_t>::pk(t4.x, t4.y), ET<bf16_t>::pk(t4.z, t4.w));
+  }
+  const int i = (n4 << 2) + threadIdx.x;
+  if (i < ck.len) {
+    float tt = th[i];
+    if (!skip) {
+      float mm = m[i], vv = 0.f;
+      if constexpr (ADAM) vv = m2[i];
+      seg_update<ADAM>(a, dec, cf, g[i], mm, vv, tt);
+      m[i] = mm; th[i] = tt;
+      if constexpr (ADAM) m2[i] = vv;
+    }
+    if (zero) g[i] = 0.f;
+    if constexpr (WC) wcopy[i] = (bf16_t)tt;
+  }
+}
+template <bool ADAM>
+static int opt_seg_launch(const char* name, float* theta, float* g, float* m, float* m2, const rua_opt_chunk* chunks, int n_chunks, const rua_opt_var* vars,
+                          const float* coef, const int32_t* flag, const float* lr_dev, const double* lr_state, seg_args a, double wd, int zero,
+                          void* wcopy_bf16, void* stream) {
+  RUA_CHECK_ARG(theta && g && m && (m2 || !ADAM) && chunks && vars && coef && lr_dev && lr_state && n_chunks > 0, "%s: bad arguments", name);
+  RUA_CHECK_ARG((((size_t)theta | (size_t)g | (size_t)m | (size_t)m2 | (size_t)chunks | (size_t)vars) & 15) == 0 && ((size_t)wcopy_bf16 & 7) == 0 &&
+                (((size_t)coef | (size_t)flag | (size_t)lr_dev) & 3) == 0 && ((size_t)lr_state & 7) == 0, "%s: buffers must be 16-byte aligned", name);
+  RUA_CHECK_ARG(wd >= 0.0, "%s: negative weight decay", name);
+  if (wcopy_bf16) hipLaunchKernelGGL((opt_seg_kernel<ADAM, true>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, theta, g, m, m2, chunks, vars, coef, flag, lr_dev,
+                                     lr_state, a, wd, zero, (bf16_t*)wcopy_bf16);
+  else hipLaunchKernelGGL((opt_seg_kernel<ADAM, false>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, theta, g, m, m2, chunks, vars, coef, flag, lr_dev,
+                          lr_state, a, wd, zero, (bf16_t*)nullptr);
+  RUA_LAUNCH_CHECK(name);
+  return RUA_OK;
+}
+extern "C" int rua_adam_step_seg(float* theta, float* g, float* m, float* v, const rua_opt_chunk* chunks, int n_chunks, const rua_opt_var* vars,
+                                 const float* coef, const int32_t* flag, const float* lr_dev, const double* lr_state, float beta1, float beta2, float eps,
+                                 float grad_scale, float clipvalue, double weight_decay, int zero_grad, void* wcopy_bf16, void* stream) {
+  seg_args a = {0.f, beta1, beta2, eps, 0.f, grad_scale, clipvalue, 0.f};
+  return opt_seg_launch<true>("rua_adam_step_seg", theta, g, m, v, chunks, n_chunks, vars, coef, flag, lr_dev, lr_state, a, weight_decay, zero_grad, wcopy_bf16, stream);
+}
+extern "C" int rua_sgd_step_seg(float* theta, float* g, float* vel, const rua_opt_chunk* chunks, int n_chunks, const rua_opt_var* vars,
+                                const float* coef, const int32_t* flag, const float* lr_dev, const double* lr_state, float momentum,
+                                float grad_scale, float clipvalue, double weight_decay, int zero_grad, void* wcopy_bf16, void* stream) {
+  seg_args a = {0.f, 0.f, 0.f, 0.f, momentum, grad_scale, clipvalue, 0.f};
+  return opt_seg_launch<false>("rua_sgd_step_seg", theta, g, vel, nullptr, chunks, n_chunks, vars, coef, flag, lr_dev, lr_state, a, weight_decay, zero_grad, wcopy_bf16, stream);
+}
+
+__global__ __launch_bounds__(256) void state_copy_kernel(float* __restrict__ dst, const float* __restrict__ src, long long n, const int32_t* __restrict__ flag) {
+  if (flag != nullptr && flag[0] == 0) return;
+  const long long n4 = n >> 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256)
+    reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i];
+  for (long long i = (n4 << 2) + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) dst[i] = src[i];
+}
+extern "C" int rua_state_copy(float* dst, const float* src, int64_t n, const int32_t* flag, void* stream) {
+  RUA_CHECK_ARG(dst && src && n > 0, "rua_state_copy: bad arguments");
+  RUA_CHECK_ARG((((size_t)dst | (size_t)src) & 15) == 0 && ((size_t)flag & 3) == 0, "rua_state_copy: buffers must be 16-byte aligned");
+  int64_t gr = (n / 4 + 255) / 256; if (gr > 1024) gr = 1024; if (gr < 1) gr = 1;
+  hipLaunchKernelGGL(state_copy_kernel, dim3((int)gr), dim3(256), 0, (hipStream_t)stream, dst, src, (long long)n, flag);
+  RUA_LAUNCH_CHECK("rua_state_copy");
+  return RUA_OK;
+}

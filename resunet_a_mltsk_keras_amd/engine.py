@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import clip as CL
 from .wgrad_queue import WgradQueue, WSpec
 from .scenes import (BLEND_MODES, MAP_HEADS, AffineSceneBatch, SceneBatch, blend_table, check_blend_budget, check_photo_table, check_radius,
                      check_scales, check_tolerance, check_views, scale_table, view_rows)
@@ -56,6 +57,23 @@ class LossSpec:
     momentum: float = 0.8
     ignore_void: Optional[int] = None                        # None: off.  An int (0..16): void pixels leave every loss and metric; the void mask of
                                                              # a class-map batch is cls >= num_classes dilated by this margin (labels.host_void_mask)
+    # Gradient clipping, decoupled weight decay, non-finite step skip (clip.py holds the definitions).  All off: the optimizer issues the calls it always did.
+    clipnorm: Optional[float] = None                         # per variable (one Keras name; the cin segments of a split kernel share one norm)
+    global_clipnorm: Optional[float] = None                  # over all trainable elements; at most one of the three clip options
+    clipvalue: Optional[float] = None
+    weight_decay: Optional[float] = None                     # decoupled: theta -= theta * (weight_decay * base rate) in front of the gradient update
+    decay_exclude: Optional[List[str]] = None                # substrings of variable names that do not decay
+    skip_nonfinite: bool = False                             # a step whose gradient's sum of squares is not finite changes nothing but the step counter
+                                                             # (it still advances: a skipped step costs one t of Adam's bias correction)
+
+    def clip_options(self) -> Dict[str, object]:
+        """The six options as a dict (checkpoint metadata, Model.compile)."""
+        return dict(clipnorm=self.clipnorm, global_clipnorm=self.global_clipnorm, clipvalue=self.clipvalue, weight_decay=self.weight_decay,
+                    decay_exclude=list(self.decay_exclude) if self.decay_exclude else None, skip_nonfinite=bool(self.skip_nonfinite))
+
+    def clip_on(self) -> bool:
+        return (self.clipnorm is not None or self.global_clipnorm is not None or self.clipvalue is not None or bool(self.weight_decay)
+                or bool(self.skip_nonfinite))
 
 
 # ---------------------------------------------------------------------------------------
@@ -1517,6 +1535,8 @@ class Engine:
         self.cursor = 0
         self.built = False
         self.loss: Optional[LossSpec] = None
+        self.clip: Optional[dict] = None                    # device tables of clip.py's options (_setup_clip); None: every option off
+        self._s_backed = False
         self.graphs: Dict[Tuple[int, bool], Graph] = {}
         self.class_w_ptr = None
         self.scalars_ptr = 0
@@ -1630,6 +1650,7 @@ class Engine:
         iv = spec.ignore_void
         if iv is not None and (isinstance(iv, bool) or not isinstance(iv, (int, np.integer)) or not 0 <= iv <= 16):
             raise ValueError(f"ignore_void {iv!r}: None (off) or a margin in 0..16")
+        CL.check_options(spec.clipnorm, spec.global_clipnorm, spec.clipvalue, spec.weight_decay)
         if self.loss is not None and (self.loss.optimizer != spec.optimizer):
             self._t_dev, self._lr_base_dev = -1, None          # device-side step counter / base rate are pushed again
         self.loss = spec
@@ -1639,6 +1660,41 @@ class Engine:
             self.class_w_ptr = self.class_w.data_ptr()
         else:
             self.class_w_ptr = None
+        self._setup_clip(spec)
+
+    def _setup_clip(self, spec: LossSpec):
+        """The device side of clip.py's options: chunk and variable tables (built once, here), the per-chunk partials, the per-variable sums and
+        coefficients, the skip flag, the report and the BatchNorm state's backup.  Nothing is allocated and self.clip is None with every option off."""
+        self.clip = None
+        self._s_backed = False
+        if not spec.clip_on() or self.dev is None:
+            return
+        chunks, vars_, names = CL.build_chunk_table(self.params.entries, spec.decay_exclude or ())
+        mode, c = CL.clip_mode(spec.clipnorm, spec.global_clipnorm, spec.clipvalue)
+        raw = lambda a: torch.from_numpy(np.frombuffer(a.tobytes(), dtype=np.uint8).copy()).to(self.dev)
+        zd = lambda n, dt: torch.zeros(max(n, 4), dtype=dt, device=self.dev)
+        self.clip = dict(chunks=raw(chunks), vars=raw(vars_), names=names, n_chunks=len(chunks), n_vars=len(vars_), mode=mode, c=c,
+                         cv=c if mode == CL.CLIP_VALUE else 0.0, wd=float(spec.weight_decay or 0.0), skip=1 if spec.skip_nonfinite else 0,
+                         partials=zd(len(chunks), torch.float64), var_sumsq=zd(len(vars_), torch.float64), coef=zd(len(vars_), torch.float32),
+                         flag=zd(4, torch.int32), report=zd(4, torch.float64),
+                         s_backup=zd(self.params.ns, torch.float32) if spec.skip_nonfinite and self.params.ns > 0 else None)
+
+    def clip_report(self) -> Optional[Dict[str, float]]:
+        """What the last optimizer step's finisher wrote (None with every clip / decay / skip option off): norm - that step's global gradient norm
+        (grad_scale included) -, min_coef - the smallest coefficient it applied (1 when nothing was clipped; clipvalue does not show here) -, and the
+        counts since compile() of steps skipped and of steps a norm clipped.  Synchronises the device: the only host read of the whole feature."""
+        if self.clip is None:
+            return None
+        torch.cuda.synchronize()
+        r = self.clip["report"].cpu().numpy()
+        return dict(norm=float(r[0]), min_coef=float(r[1]), skipped=int(r[2]), clipped=int(r[3]))
+
+    def _backup_state(self, s):
+        """skip_nonfinite: the BatchNorm moving statistics as the step finds them (the forward folds the batch into them before anyone knows
+        whether the gradient is finite); rua_state_copy puts them back behind a skipped step (_launch_optimizer)."""
+        ck = self.clip
+        if ck is not None and ck["s_backup"] is not None:
+            L.lib().call("rua_state_copy", ck["s_backup"].data_ptr(), self.S.data_ptr(), self.params.ns, None, C.c_void_p(s))
 
     def drop_plans(self):
         """Forget every recorded plan and captured graph (they are rebuilt on the next step): a launch heuristic that is read when a plan
@@ -1901,6 +1957,9 @@ class Engine:
         s = self._stream()
         self._put_batch(g, x, y, norm_type, void_mask=void_mask, photo=photo)
         self._zero_arena(g, s)
+        if not self._s_backed:                              # the first forward since an optimizer step: the state this step begins with
+            self._backup_state(s)
+            self._s_backed = True
         self._prep_weights(s)
         g.fwd.run(s)
         g.loss_plan.run(s)
@@ -1950,6 +2009,28 @@ class Engine:
         L.lib().call("rua_lr_step", self.lr_state.data_ptr(), self.lr_dev.data_ptr(), 1 if sp.optimizer == "adam" else 0,
                      float(sp.beta_1), float(sp.beta_2), C.c_void_p(s))
         wc = self.Wf.data_ptr() if self.opt_wcopy else None    # bf16 storage: the updated weights leave as the forward-layout copy in the same pass
+        ck = self.clip
+        if ck is not None:
+            # clip.py's options: sum of squares per chunk, the one-block finisher (coefficients, skip flag, report), the optimizer over the chunk table
+            # and - skip_nonfinite - the BatchNorm state put back behind a skipped step.  Everything is decided on the device: a replay needs no host
+            # scalar.  Under data parallel this runs on the REDUCED gradient (dist.reduce_gradients comes first and has already copied the reduced
+            # state out of G's tail into S, so the restore is the last writer of S): every rank takes the same decision.
+            lib, sv = L.lib(), C.c_void_p(s)
+            lib.call("rua_grad_sumsq", self.G.data_ptr(), ck["chunks"].data_ptr(), ck["n_chunks"], ck["partials"].data_ptr(), sv)
+            lib.call("rua_clip_finish", ck["partials"].data_ptr(), ck["n_chunks"], ck["vars"].data_ptr(), ck["n_vars"], ck["mode"], ck["c"], float(grad_scale), ck["skip"],
+                     ck["var_sumsq"].data_ptr(), ck["coef"].data_ptr(), ck["flag"].data_ptr(), ck["report"].data_ptr(), sv)
+            flag = ck["flag"].data_ptr() if ck["skip"] else None
+            if sp.optimizer == "adam":
+                lib.call("rua_adam_step_seg", self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.V1.data_ptr(), ck["chunks"].data_ptr(),
+                         ck["n_chunks"], ck["vars"].data_ptr(), ck["coef"].data_ptr(), flag, self.lr_dev.data_ptr(), self.lr_state.data_ptr(),
+                         sp.beta_1, sp.beta_2, KERAS_EPS, grad_scale, ck["cv"], ck["wd"], 1, wc, sv)
+            else:
+                lib.call("rua_sgd_step_seg", self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), ck["chunks"].data_ptr(), ck["n_chunks"],
+                         ck["vars"].data_ptr(), ck["coef"].data_ptr(), flag, self.lr_dev.data_ptr(), self.lr_state.data_ptr(), sp.momentum,
+                         grad_scale, ck["cv"], ck["wd"], 1, wc, sv)
+            if ck["s_backup"] is not None:
+                lib.call("rua_state_copy", self.S.data_ptr(), ck["s_backup"].data_ptr(), self.params.ns, flag, sv)
+            return
         if sp.optimizer == "adam":
             L.lib().call("rua_adam_step_w", self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.V1.data_ptr(), self.params.n,
                          0.0, self.lr_dev.data_ptr(), sp.beta_1, sp.beta_2, KERAS_EPS, grad_scale, 1, wc, C.c_void_p(s))
@@ -1962,12 +2043,14 @@ class Engine:
         self._launch_optimizer(grad_scale, self._stream())
         self.weights_dirty = True
         self._g_pending = False                             # the optimizer zeroed the arena as it consumed it
+        self._s_backed = False                              # skip_nonfinite: the next forward_backward opens a new step
 
     def _issue_step(self, g: Graph):
         """The whole training step on the current stream: arena fill, weight refresh (forced), forward, losses, backward, optimizer -
         what _graph_step runs and captures and count_step_dispatches counts."""
         s = self._stream()
         self._zero_arena(g, s)
+        self._backup_state(s)
         self.weights_dirty = True
         self._prep_weights(s)
         g.fwd.run(s)
@@ -2051,7 +2134,7 @@ class Engine:
                     with torch.cuda.graph(cap, capture_error_mode="thread_local"):
                         s = self._stream()
                         if first == 0:
-                            self._zero_arena(g, s); self.weights_dirty = True; self._prep_weights(s)
+                            self._zero_arena(g, s); self._backup_state(s); self.weights_dirty = True; self._prep_weights(s)
                             g.fwd.run(s); g.loss_plan.run(s)
                         g.bwd.run(s, first=first, last=idx + 1)
                     pieces.append((cap, marks.get(idx, []) if ci < len(cuts) else []))

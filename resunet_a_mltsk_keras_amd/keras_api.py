@@ -39,8 +39,36 @@ class _Var:
         return self.value
 
 
-class Adam:
-    def __init__(self, lr=None, learning_rate=None, beta_1=0.9, beta_2=0.999, epsilon=1e-7, **_):
+class _ClipOptions:
+    """Keras' clipnorm / global_clipnorm / clipvalue / weight_decay (clip.py has the definitions) and this package's skip_nonfinite, shared by
+    Adam and SGD: at most one clip option, each positive; exclude_from_weight_decay takes substrings of variable names, as Keras does."""
+
+    def _set_clip(self, clipnorm, global_clipnorm, clipvalue, weight_decay, skip_nonfinite):
+        from .clip import check_options
+        check_options(clipnorm, global_clipnorm, clipvalue, weight_decay)
+        self.clipnorm, self.global_clipnorm, self.clipvalue = clipnorm, global_clipnorm, clipvalue
+        self.weight_decay, self.skip_nonfinite = weight_decay, bool(skip_nonfinite)
+        self.decay_exclude: List[str] = []
+
+    def exclude_from_weight_decay(self, var_list=None, var_names=None):
+        """Variables whose name contains one of var_names do not decay (call before compile).  var_list - Keras' list of variable objects -
+        has no meaning here: the variables live in one flat buffer."""
+        if var_list:
+            raise ValueError("exclude_from_weight_decay: pass var_names (substrings of variable names); there are no variable objects to list")
+        names = [var_names] if isinstance(var_names, str) else list(var_names or [])
+        if not all(isinstance(n, str) and n for n in names):
+            raise ValueError("exclude_from_weight_decay: var_names is a list of non-empty strings")
+        self.decay_exclude = names
+
+    def clip_options(self):
+        return dict(clipnorm=self.clipnorm, global_clipnorm=self.global_clipnorm, clipvalue=self.clipvalue, weight_decay=self.weight_decay,
+                    decay_exclude=list(self.decay_exclude) or None, skip_nonfinite=self.skip_nonfinite)
+
+
+class Adam(_ClipOptions):
+    def __init__(self, lr=None, learning_rate=None, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, global_clipnorm=None, clipvalue=None,
+                 weight_decay=None, skip_nonfinite=False, **_):
+        self._set_clip(clipnorm, global_clipnorm, clipvalue, weight_decay, skip_nonfinite)
         v = learning_rate if learning_rate is not None else (lr if lr is not None else 1e-3)
         self.lr = _Var(v)
         self.learning_rate = self.lr
@@ -49,8 +77,10 @@ class Adam:
             raise ValueError("the HIP Adam kernel is built with Keras' default epsilon 1e-7")
 
 
-class SGD:
-    def __init__(self, lr=None, learning_rate=None, momentum=0.0, nesterov=False, **_):
+class SGD(_ClipOptions):
+    def __init__(self, lr=None, learning_rate=None, momentum=0.0, nesterov=False, clipnorm=None, global_clipnorm=None, clipvalue=None,
+                 weight_decay=None, skip_nonfinite=False, **_):
+        self._set_clip(clipnorm, global_clipnorm, clipvalue, weight_decay, skip_nonfinite)
         v = learning_rate if learning_rate is not None else (lr if lr is not None else 1e-2)
         self.lr = _Var(v)
         self.learning_rate = self.lr
@@ -264,7 +294,11 @@ class Model:
     def compile(self, optimizer=None, loss=None, loss_weights=None, metrics=None, ignore_void=None, **_):
         """ignore_void None: off.  True or a margin 0..16 (True = labels.VOID_MARGIN, 2): void pixels - a class value >= num_classes in a
         class-map or scene batch, dilated by the margin; the void_mask of a float batch - leave every head's loss, the gradients and the
-        metrics.  The option is NOT stored in .h5 files: a loaded model is compiled without it, compile() again to set it."""
+        metrics.  The option is NOT stored in .h5 files: a loaded model is compiled without it, compile() again to set it.
+        The optimizer's clipnorm / global_clipnorm / clipvalue / weight_decay (and exclude_from_weight_decay) / skip_nonfinite go into the
+        LossSpec as they are (clip.py has the definitions; they ARE stored in .h5 files).  skip_nonfinite: a step whose gradient is not finite
+        changes neither weights nor moments nor BatchNorm statistics, but still advances the step counter - it costs one t of Adam's bias
+        correction.  clip_report() tells how many steps were skipped and clipped."""
         margin = void_margin(ignore_void)
         if optimizer is None or isinstance(optimizer, str):
             optimizer = {"adam": Adam, "sgd": SGD}[optimizer or "adam"]()
@@ -283,7 +317,8 @@ class Model:
             weights.update({h: float(loss_weights[h]) for h in heads if h in loss_weights})
         spec = LossSpec(kind=kinds, weight=weights, class_weights=cw, optimizer=optimizer.kind, lr=optimizer.lr.value,
                         beta_1=getattr(optimizer, "beta_1", 0.9), beta_2=getattr(optimizer, "beta_2", 0.999),
-                        momentum=getattr(optimizer, "momentum", 0.0), ignore_void=margin)
+                        momentum=getattr(optimizer, "momentum", 0.0), ignore_void=margin,
+                        **(optimizer.clip_options() if hasattr(optimizer, "clip_options") else {}))
         self.engine.compile(spec)
         self._finish_compile()
 
@@ -302,6 +337,11 @@ class Model:
         else:
             self.metrics_names = ["loss"] + m
         self._compiled = True
+
+    def clip_report(self):
+        """Engine.clip_report: dict(norm, min_coef, skipped, clipped) of the last step and the counts since compile(), or None when the optimizer
+        was given no clipnorm / global_clipnorm / clipvalue / weight_decay / skip_nonfinite.  Synchronises the device."""
+        return self.engine.clip_report()
 
     def _sync_lr(self):
         self.engine.loss.lr = self.optimizer.lr.value          # K.set_value(model.optimizer.lr, ...) takes effect
@@ -455,7 +495,7 @@ class Model:
         if e.loss is not None:
             sp = e.loss
             meta["loss"] = dict(kind=sp.kind, weight=sp.weight, class_weights=sp.class_weights, optimizer=sp.optimizer, lr=sp.lr,
-                                beta_1=sp.beta_1, beta_2=sp.beta_2, momentum=sp.momentum)
+                                beta_1=sp.beta_1, beta_2=sp.beta_2, momentum=sp.momentum, **sp.clip_options())
             og = root.require_group("optimizer_weights")
             og.set("rua/m:0", e.M1.cpu().numpy()); og.set("rua/v:0", e.V1.cpu().numpy())
             og.set("rua/iterations:0", np.array(e.t, np.int64))
@@ -567,6 +607,14 @@ def _cfg_from_keras_file(root, weights, input_shape):
     raise ValueError(f"the variables fit neither ResUnet_a/model2.py nor ResUnet_a/model.py ({err})")
 
 
+def loss_clip_options(lo: dict) -> dict:
+    """The clip / decay / skip options out of a checkpoint's `loss` metadata; a file written before they existed has none of the keys: all off."""
+    ex = lo.get("decay_exclude")
+    return dict(clipnorm=lo.get("clipnorm"), global_clipnorm=lo.get("global_clipnorm"), clipvalue=lo.get("clipvalue"),
+                weight_decay=lo.get("weight_decay"), decay_exclude=[str(x) for x in ex] if ex else None,
+                skip_nonfinite=bool(lo.get("skip_nonfinite", False)))
+
+
 def load_model(path, compile=True, custom_objects=None, dtype=None, input_shape=None, **_):
     """`load_model('best_model.h5')` (train_ISPRS.py:474, test_ISPRS.py:278).  Reads HDF5 only - nothing is unpickled, so a
     checkpoint cannot run code.  A file written by Model.save() restores graph, compile arguments and optimizer state; a file
@@ -591,10 +639,14 @@ def load_model(path, compile=True, custom_objects=None, dtype=None, input_shape=
     m.engine.set_weights(canonical_keras_names(weights, m.engine.get_weights()))
     if compile and "loss" in meta:
         lo = meta["loss"]
-        opt = Adam(lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"]) if lo["optimizer"] == "adam" else SGD(lr=lo["lr"], momentum=lo["momentum"])
+        co = loss_clip_options(lo)
+        ko = {k: v for k, v in co.items() if k != "decay_exclude"}
+        opt = Adam(lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], **ko) if lo["optimizer"] == "adam" else SGD(lr=lo["lr"], momentum=lo["momentum"], **ko)
+        if co["decay_exclude"]:
+            opt.exclude_from_weight_decay(var_names=co["decay_exclude"])
         m.optimizer = opt
         m.engine.compile(LossSpec(kind={k: int(v) for k, v in lo["kind"].items()}, weight=lo["weight"], class_weights=lo["class_weights"],
-                                  optimizer=lo["optimizer"], lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], momentum=lo["momentum"]))
+                                  optimizer=lo["optimizer"], lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], momentum=lo["momentum"], **co))
         og = root["optimizer_weights"]
         m.engine.M1.copy_(torch.from_numpy(np.ascontiguousarray(og["rua/m:0"]))); m.engine.V1.copy_(torch.from_numpy(np.ascontiguousarray(og["rua/v:0"])))
         m.engine.t = int(og["rua/iterations:0"])

@@ -36,6 +36,11 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
   * `--balance_class K --balance_percent P` (with `--scene_dataset yes`): only the training windows in which class K covers at
     least P percent of the pixels are trained on (the reference's bal_aug_patches, utils.py:383, with the class a parameter;
     scenes.balance_rows).  The validation windows and the split are untouched.
+  * `--clipnorm C` / `--global_clipnorm C` / `--clipvalue C` (at most one), `--weight_decay WD [--decay_all yes]`, `--skip_nonfinite yes`:
+    Keras' gradient clipping and decoupled weight decay (kernels only unless --decay_all yes: names with bias / gamma / beta are
+    excluded) and a guard that leaves weights, moments and BatchNorm statistics alone in a step whose gradient holds an Inf or a NaN,
+    all decided on the GPU (resunet_a_mltsk_keras_amd/clip.py).  After each epoch the counts of skipped and clipped steps and the last
+    gradient norm are printed.  With `-cp` the options come from the checkpoint.
   * `--dtype {bf16,f32}`, `--seed`: engine options.  Launch with torch.distributed.run for multi-GPU data
     parallel (`-bs` is then the GLOBAL batch, as under MirroredStrategy).
 """
@@ -119,7 +124,26 @@ def build_parser():
                    help="class-map layouts (--compact_dataset / --scene_dataset yes): pixels whose class value is >= --num_classes are no label; they leave every loss, gradient and metric")
     p.add_argument("--void_margin", type=int, default=2, metavar="N",
                    help="ignore_void: pixels within N (Chebyshev, 0..16) of a void pixel are void too; 2 covers the boundary target's reach across a class / void interface")
+    p.add_argument("--clipnorm", type=float, default=None, metavar="C", help="clip every variable's gradient to the norm C (Keras' clipnorm)")
+    p.add_argument("--global_clipnorm", type=float, default=None, metavar="C", help="clip the whole gradient to the norm C (Keras' global_clipnorm)")
+    p.add_argument("--clipvalue", type=float, default=None, metavar="C", help="limit every gradient element to [-C, C] (Keras' clipvalue); at most one clip flag")
+    p.add_argument("--weight_decay", type=float, default=None, metavar="WD", help="decoupled weight decay: theta -= theta * WD * learning rate before every update")
+    p.add_argument("--decay_all", type=str2bool, default=False, help="weight_decay: decay biases and BatchNorm gamma / beta too (default: kernels only)")
+    p.add_argument("--skip_nonfinite", type=str2bool, default=False,
+                   help="leave weights, moments and BatchNorm statistics alone in a step whose gradient holds an Inf or a NaN")
     return p
+
+
+def optimizer_options(args):
+    """--clipnorm / --global_clipnorm / --clipvalue / --weight_decay / --skip_nonfinite as the optimizer's keywords, checked before anything is
+    built (resunet_a_mltsk_keras_amd/clip.py has the definitions): at most one clip flag, each positive."""
+    from resunet_a_mltsk_keras_amd.clip import check_options
+    kw = dict(clipnorm=args.clipnorm, global_clipnorm=args.global_clipnorm, clipvalue=args.clipvalue, weight_decay=args.weight_decay)
+    try:
+        check_options(**kw)
+    except ValueError as exc:
+        sys.exit(f"optimizer flags: {exc}")
+    return dict(kw, skip_nonfinite=bool(args.skip_nonfinite))
 
 
 def check_void_flags(args):
@@ -342,6 +366,9 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
                 vw.scalar("Segmentation/MCC", mcc, epoch)
                 print(f"| {'Total':8s}{tm['loss']:13.5f}{vm['loss']:13.5f}{0:13d}{0:13d} |\n+{'-' * 62}+")
                 tw.scalar("Total/Loss", tm["loss"], epoch); vw.scalar("Total/Loss", vm["loss"], epoch)
+        rep = net.clip_report() if hasattr(net, "clip_report") else None        # None: no clip / decay / skip option is on
+        if rep is not None:
+            say(f"Optimizer: {rep['skipped']} steps skipped (non-finite gradient), {rep['clipped']} clipped by a norm so far; last gradient norm {rep['norm']:.6g}")
         val_loss = agree_from_rank0(vm["loss"], world)
         if val_loss >= min_loss + delta:
             cont += 1
@@ -417,7 +444,11 @@ def main(argv=None):
                 sys.exit(f"--class_weights auto: {exc}")
     rows = cols = args.patch_size
     channels = args.channels or (int(images[0].shape[-1]) if scenes is not None else int(np.load(xs[0]).shape[-1]))
-    optm = Adam(lr=args.learning_rate, beta_1=0.9) if args.optimizer == "adam" else SGD(lr=args.learning_rate, momentum=0.8)
+    opt_kw = optimizer_options(args)
+    optm = Adam(lr=args.learning_rate, beta_1=0.9, **opt_kw) if args.optimizer == "adam" else SGD(lr=args.learning_rate, momentum=0.8, **opt_kw)
+    if args.weight_decay and not args.decay_all:
+        from resunet_a_mltsk_keras_amd.clip import DEFAULT_DECAY_EXCLUDE
+        optm.exclude_from_weight_decay(var_names=list(DEFAULT_DECAY_EXCLUDE))
     say("=" * 60)
     if args.loss == "cross_entropy":
         say("Using Cross Entropy")
