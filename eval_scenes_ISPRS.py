@@ -83,6 +83,8 @@ def build_parser():
     parser = _patch_parser()                                   # test_ISPRS.py's flags; --dataset_path is the scene directory
     parser.add_argument("--scene_dataset", type=_yes, default=True, help="as train_ISPRS.py names the layout; this script reads no other")
     parser.add_argument("--stride", type=int, default=None, help="distance between windows (default: the patch size)")
+    parser.add_argument("--weights", choices=["model", "ema"], default="model",
+                        help="model: the trained weights; ema: their moving average (a file saved by train_ISPRS.py --ema yes)")
     parser.add_argument("--views", nargs="+", default=["none"], metavar="SET|CODE",
                         help="test-time augmentation: none, flips, aug5, all, or symmetry codes 0..7 (e.g. --views 0 3 4)")
     parser.add_argument("--scales", nargs="+", type=float, default=None, metavar="Z",
@@ -154,7 +156,12 @@ def main(argv=None):
     if "color_rgb" in heads and args.norm_type != 1:
         raise SystemExit("--head_maps color_rgb needs --norm_type 1 (the colour target is HSV / (179, 255, 255) only there)")
     names, images, class_maps = scenes.load_scene_dir(args.dataset_path)
-    model = load_model(args.model_path, compile=False)
+    try:
+        model = load_model(args.model_path, compile=False, weights=args.weights)
+    except ValueError as exc:
+        if args.weights != "ema":
+            raise
+        raise SystemExit(f"--weights ema: {exc}")
     model.summary()
     if model.cfg.num_classes != args.num_classes:
         raise SystemExit(f"--num_classes {args.num_classes}, but the model predicts {model.cfg.num_classes} classes")

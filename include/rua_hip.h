@@ -521,6 +521,49 @@ int rua_sgd_step_seg(float* theta, float* g, float* vel, const rua_opt_chunk* ch
  * (flag NULL) and their restore behind a skipped step (flag = the finisher's).  A kernel, not a copy node: a captured step holds kernels only. */
 int rua_state_copy(float* dst, const float* src, int64_t n, const int32_t* flag, void* stream);
 
+/* ---- learning-rate schedules and the weights' moving average (schedules.py holds the host definitions) -----------------------------
+ * A schedule travels to the rate kernel BY VALUE: its constants are kernel arguments, so a captured step replays them and the device
+ * state stays the pair of rua_lr_step - state[0] = optimizer steps taken, state[1] = the BASE rate of the current step, which this
+ * kernel now WRITES (rua_lr_step only reads it).  Fields a kind does not use are ignored.
+ *   RUA_SCHED_CONSTANT      initial
+ *   RUA_SCHED_COSINE        initial, decay_steps, alpha; warmup != 0: warmup_target, warmup_steps (linear from initial to the target,
+ *                           then the cosine from the target)
+ *   RUA_SCHED_EXPONENTIAL   initial * decay_rate ^ (step / decay_steps)            staircase != 0: floor of the exponent
+ *   RUA_SCHED_POLYNOMIAL    (initial - end) * (1 - step / decay_steps) ^ power + end, step clamped to decay_steps; cycle != 0: decay_steps
+ *                           times ceil(step / decay_steps) instead of the clamp
+ *   RUA_SCHED_PIECEWISE     values[i] for the first i < n_boundaries with step <= boundaries[i], values[n_boundaries] beyond
+ *   RUA_SCHED_INVERSE_TIME  initial / (1 + decay_rate * step / decay_steps)        staircase != 0: floor of the quotient */
+#define RUA_SCHED_CONSTANT 0
+#define RUA_SCHED_COSINE 1
+#define RUA_SCHED_EXPONENTIAL 2
+#define RUA_SCHED_POLYNOMIAL 3
+#define RUA_SCHED_PIECEWISE 4
+#define RUA_SCHED_INVERSE_TIME 5
+#define RUA_SCHED_MAX_BOUNDARIES 16
+typedef struct rua_lr_schedule {
+  int32_t kind, staircase, cycle, warmup, n_boundaries, pad;
+  double initial, decay_steps, decay_rate, alpha, end, power, warmup_target, warmup_steps;
+  double boundaries[RUA_SCHED_MAX_BOUNDARIES];
+  double values[RUA_SCHED_MAX_BOUNDARIES + 1];
+} rua_lr_schedule;
+/* rua_lr_step under a schedule, launch for launch (one thread): t = state[0] + 1 is stored to state[0]; r = schedules.host_lr(sched,
+ * t - 1) in fp64 is stored to state[1], where rua_adam_step_seg / rua_sgd_step_seg read the base rate of the decoupled weight decay (the
+ * decay follows the schedule); lr_out[0] = (float)r, for adam != 0 (float)(r * sqrt(1 - beta2^t) / (1 - beta1^t)).  A step the optimizer
+ * skips (skip_nonfinite) has advanced t all the same.  decay_steps > 0, 0 <= n_boundaries <= RUA_SCHED_MAX_BOUNDARIES and a known kind
+ * are checked; state 8-byte aligned. */
+int rua_lr_schedule_step(double* state, float* lr_out, rua_lr_schedule sched, int adam, double beta1, double beta2, void* stream);
+/* The exponential moving average of the weights, launched right behind the optimizer kernel of the same step.  One streaming pass, 16-byte
+ * accesses.  t = (int64)lr_state[0], the counter the rate kernel of THIS step has advanced.  flag (NULL: never) != 0 - a skipped step -:
+ * nothing is read or written.  Otherwise per element
+ *   e' = theta                                                                        t == 1 (Keras 3: the average starts as a copy)
+ *   e' = fadd(fmul(momentum, ema), fmul(fsub(1, momentum), theta))                    each operation rounded on its own, no contraction:
+ *                                                                                      bit for bit schedules.host_ema
+ *   ema = e';  overwrite_every > 0 && t % overwrite_every == 0: theta = e' and wcopy_bf16 (NULL: none) = bf16(e') - the forward-layout
+ *   copy the optimizer left fresh stays fresh.  The optimizer's moments are not touched.
+ * ema, theta 16-byte aligned, wcopy 8-byte; 0 <= momentum <= 1; n > 0. */
+int rua_ema_step(float* ema, float* theta, void* wcopy_bf16, int64_t n, float momentum, const double* lr_state, int overwrite_every,
+                 const int32_t* flag, void* stream);
+
 /* ---- multitask training targets from uint8 patches (labels.py; the reference's preprocess_save_patches_ISPRS.py:206-228,
  * multitasking_utils.py:6-35) ------------------------------------------------------------------------------------------------
  * img [N][H][W][Cin] and cls [N][H][W] are uint8 (4-byte aligned); x [N][H][W][Cin], seg / bound / dist [N][H][W][C] and

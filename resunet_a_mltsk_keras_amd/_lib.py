@@ -48,6 +48,13 @@ class WgradPending(C.Structure):
                 ("block_begin", i32), ("pad", i32), ("overwrite_dev", vp)]
 
 
+class LrSchedule(C.Structure):
+    """rua_lr_schedule: passed to rua_lr_schedule_step by value (schedules.to_struct fills it)."""
+    _fields_ = [("kind", i32), ("staircase", i32), ("cycle", i32), ("warmup", i32), ("n_boundaries", i32), ("pad", i32), ("initial", f64),
+                ("decay_steps", f64), ("decay_rate", f64), ("alpha", f64), ("end", f64), ("power", f64), ("warmup_target", f64),
+                ("warmup_steps", f64), ("boundaries", f64 * 16), ("values", f64 * 17)]
+
+
 class TaniHead(C.Structure):
     _fields_ = [("sums", vp), ("replicas", i32), ("B", i32), ("C", i32), ("grad_scale", f32), ("loss_out", vp), ("coef", vp), ("per_sample", vp)]
 
@@ -180,6 +187,8 @@ _SIGS = {
     "rua_adam_step_seg": ([vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f64, i32, vp, vp], i32),
     "rua_sgd_step_seg": ([vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, f64, i32, vp, vp], i32),
     "rua_state_copy": ([vp, vp, i64, vp, vp], i32),
+    "rua_lr_schedule_step": ([vp, vp, LrSchedule, i32, f64, f64, vp], i32),
+    "rua_ema_step": ([vp, vp, vp, i64, f32, vp, i32, vp, vp], i32),
     "rua_tanimoto_sums_void": ([vp, vp, vp, i32, i64, i32, vp, vp], i32),
     "rua_head_fwd_loss_void": ([vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i64, i32, i32, i32, i32, vp, vp], i32),
     "rua_pixel_loss_void": ([i32, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp], i32),

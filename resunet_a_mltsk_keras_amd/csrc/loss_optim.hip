@@ -912,3 +912,121 @@ extern "C" int rua_state_copy(float* dst, const float* src, int64_t n, const int
   RUA_LAUNCH_CHECK("rua_state_copy");
   return RUA_OK;
 }
+
+// ---- learning-rate schedules and the weights' moving average (include/rua_hip.h; schedules.py holds the host definitions) ------------------
+// schedules.host_lr in fp64, operation for operation.  Contraction is asked off; the device's pow and cos - and a multiply-add the backend
+// fuses all the same - may differ from numpy's result by a few fp64 ulps.  The table look-up, the clamped tails (cos(pi) = -1 and
+// 0^power = 0 are exact, and x * 0 + y is y fused or not) and the constant kind are exact.
+__device__ double sched_rate(const rua_lr_schedule& k, double s) {
+#pragma clang fp contract(off)
+  switch (k.kind) {
+    case RUA_SCHED_COSINE: {
+      double base = k.initial;
+      if (k.warmup) {
+        if (s < k.warmup_steps) return (k.warmup_target - k.initial) * (s / k.warmup_steps) + k.initial;
+        s = fmin(s, k.warmup_steps + k.decay_steps) - k.warmup_steps;
+        base = k.warmup_target;
+      } else {
+        s = fmin(s, k.decay_steps);
+      }
+      const double cosine = 0.5 * (1.0 + cos(3.14159265358979323846 * (s / k.decay_steps)));
+      return base * ((1.0 - k.alpha) * cosine + k.alpha);
+    }
+    case RUA_SCHED_EXPONENTIAL: {
+      double p = s / k.decay_steps;
+      if (k.staircase) p = floor(p);
+      return k.initial * pow(k.decay_rate, p);
+    }
+    case RUA_SCHED_POLYNOMIAL: {
+      double d = k.decay_steps;
+      if (k.cycle) d = d * (s == 0.0 ? 1.0 : ceil(s / d));
+      else s = fmin(s, d);
+      return (k.initial - k.end) * pow(1.0 - s / d, k.power) + k.end;
+    }
+    case RUA_SCHED_PIECEWISE: {
+      for (int i = 0; i < k.n_boundaries; ++i)
+        if (s <= k.boundaries[i]) return k.values[i];
+      return k.values[k.n_boundaries];
+    }
+    case RUA_SCHED_INVERSE_TIME: {
+      double p = s / k.decay_steps;
+      if (k.staircase) p = floor(p);
+      return k.initial / (1.0 + k.decay_rate * p);
+    }
+    default: return k.initial;
+  }
+}
+__global__ void lr_schedule_step_kernel(double* state, float* lr_out, const rua_lr_schedule sched, int adam, double beta1, double beta2) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const double t = state[0] + 1.0;
+    state[0] = t;
+    double lr = sched_rate(sched, t - 1.0);
+    state[1] = lr;                                       // the base rate the segmented optimizers' weight decay reads
+    if (adam) lr = lr * sqrt(1.0 - pow(beta2, t)) / (1.0 - pow(beta1, t));
+    lr_out[0] = (float)lr;
+  }
+}
+extern "C" int rua_lr_schedule_step(double* state, float* lr_out, rua_lr_schedule sched, int adam, double beta1, double beta2, void* stream) {
+  RUA_CHECK_ARG(state && lr_out && ((size_t)state & 7) == 0 && ((size_t)lr_out & 3) == 0, "rua_lr_schedule_step: null or misaligned pointer");
+  RUA_CHECK_ARG(sched.kind >= RUA_SCHED_CONSTANT && sched.kind <= RUA_SCHED_INVERSE_TIME, "rua_lr_schedule_step: unknown kind %d", sched.kind);
+  RUA_CHECK_ARG(sched.kind == RUA_SCHED_CONSTANT || sched.kind == RUA_SCHED_PIECEWISE || sched.decay_steps > 0.0, "rua_lr_schedule_step: decay_steps must be positive");
+  RUA_CHECK_ARG(sched.kind != RUA_SCHED_PIECEWISE || (sched.n_boundaries >= 0 && sched.n_boundaries <= RUA_SCHED_MAX_BOUNDARIES),
+                "rua_lr_schedule_step: %d boundaries (at most %d)", sched.n_boundaries, RUA_SCHED_MAX_BOUNDARIES);
+  RUA_CHECK_ARG(!(sched.kind == RUA_SCHED_COSINE && sched.warmup) || sched.warmup_steps >= 0.0, "rua_lr_schedule_step: negative warmup_steps");
+  hipLaunchKernelGGL(lr_schedule_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, lr_out, sched, adam, beta1, beta2);
+  RUA_LAUNCH_CHECK("rua_lr_schedule_step");
+  return RUA_OK;
+}
+
+// Four elements per thread and stream (16-byte accesses; 8-byte for the bf16 copy), grid sized like adam_kernel's, the n % 4 tail element by
+// element.  The step counter and the skip flag are read once per thread; both are uniform, so a skipped step costs an empty grid.
+// __fmul_rn / __fadd_rn / __fsub_rn are plain operators in HIP's headers, and the backend fuses a product into the sum that follows it whatever
+// the source says about contraction.  The two products therefore pass through an empty asm statement: no instruction, but the sum no longer
+// sees where its operands came from, so each of the three operations is rounded on its own.
+__device__ __forceinline__ float ema_update(bool first, float mom, float om, float e, float x) {
+  float a = __fmul_rn(mom, e), b = __fmul_rn(om, x);
+  asm volatile("" : "+v"(a), "+v"(b));
+  return first ? x : __fadd_rn(a, b);
+}
+template <bool WC>
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, float* __restrict__ th, bf16_t* __restrict__ wcopy, long long n, float mom,
+                                                  const double* __restrict__ lr_state, int every, const int32_t* __restrict__ flag) {
+  if (flag != nullptr && flag[0] != 0) return;
+  const long long t = (long long)lr_state[0];
+  const bool first = t == 1;
+  const bool over = every > 0 && t % every == 0;
+  const float om = __fsub_rn(1.f, mom);
+  auto upd = [&](float e, float x) { return ema_update(first, mom, om, e, x); };
+  const long long n4 = n >> 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    const float4 t4 = reinterpret_cast<const float4*>(th)[i];
+    float4 e4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!first) e4 = reinterpret_cast<const float4*>(ema)[i];
+    e4.x = upd(e4.x, t4.x); e4.y = upd(e4.y, t4.y); e4.z = upd(e4.z, t4.z); e4.w = upd(e4.w, t4.w);
+    reinterpret_cast<float4*>(ema)[i] = e4;
+    if (over) {
+      reinterpret_cast<float4*>(th)[i] = e4;
+      if constexpr (WC) reinterpret_cast<uint2*>(wcopy)[i] = make_uint2(ET<bf16_t>::pk(e4.x, e4.y), ET<bf16_t>::pk(e4.z, e4.w));
+    }
+  }
+  for (long long i = (n4 << 2) + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const float e = upd(first ? 0.f : ema[i], th[i]);
+    ema[i] = e;
+    if (over) {
+      th[i] = e;
+      if constexpr (WC) wcopy[i] = (bf16_t)e;
+    }
+  }
+}
+extern "C" int rua_ema_step(float* ema, float* theta, void* wcopy_bf16, int64_t n, float momentum, const double* lr_state, int overwrite_every,
+                            const int32_t* flag, void* stream) {
+  RUA_CHECK_ARG(ema && theta && lr_state && n > 0 && ema != theta, "rua_ema_step: bad arguments");
+  RUA_CHECK_ARG((((size_t)ema | (size_t)theta) & 15) == 0 && ((size_t)wcopy_bf16 & 7) == 0 && ((size_t)lr_state & 7) == 0 && ((size_t)flag & 3) == 0,
+                "rua_ema_step: buffers must be 16-byte aligned");
+  RUA_CHECK_ARG(momentum >= 0.f && momentum <= 1.f && overwrite_every >= 0, "rua_ema_step: momentum in [0, 1], overwrite_every >= 0");
+  int64_t gr = (n / 4 + 255) / 256; if (gr > 4096) gr = 4096; if (gr < 1) gr = 1;
+  if (wcopy_bf16) hipLaunchKernelGGL((ema_kernel<true>), dim3((int)gr), dim3(256), 0, (hipStream_t)stream, ema, theta, (bf16_t*)wcopy_bf16, (long long)n, momentum, lr_state, overwrite_every, flag);
+  else hipLaunchKernelGGL((ema_kernel<false>), dim3((int)gr), dim3(256), 0, (hipStream_t)stream, ema, theta, (bf16_t*)nullptr, (long long)n, momentum, lr_state, overwrite_every, flag);
+  RUA_LAUNCH_CHECK("rua_ema_step");
+  return RUA_OK;
+}

@@ -185,6 +185,8 @@ class DataParallel:
         rank 0: train_ISPRS.py:474-480 resume)."""
         eng = self.eng
         self._bcast(eng.M1); self._bcast(eng.V1)
+        if getattr(eng, "E", None) is not None:               # use_ema: the weights' moving average travels with the moments
+            self._bcast(eng.E)
         t = torch.tensor([float(eng.t)], dtype=torch.float64)
         if self.host_staged or not eng.P.is_cuda:
             dist.broadcast(t, 0, group=self.group)

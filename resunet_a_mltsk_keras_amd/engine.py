@@ -9,6 +9,7 @@ and torch.distributed only.  Reference call sites replaced: ResUnet_a/model2.py:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -20,6 +21,7 @@ import torch
 
 from . import _lib as L
 from . import clip as CL
+from . import schedules as SC
 from .wgrad_queue import WgradQueue, WSpec
 from .scenes import (BLEND_MODES, MAP_HEADS, AffineSceneBatch, SceneBatch, blend_table, check_blend_budget, check_photo_table, check_radius,
                      check_scales, check_tolerance, check_views, scale_table, view_rows)
@@ -65,6 +67,18 @@ class LossSpec:
     decay_exclude: Optional[List[str]] = None                # substrings of variable names that do not decay
     skip_nonfinite: bool = False                             # a step whose gradient's sum of squares is not finite changes nothing but the step counter
                                                              # (it still advances: a skipped step costs one t of Adam's bias correction)
+
+    # Learning-rate schedule and the weights' moving average (schedules.py holds the definitions).  Both off: the optimizer issues the calls it always did.
+    lr_schedule: Optional[object] = None                     # a schedules.LearningRateSchedule: the rate of every step is computed on the device from
+                                                             # the device's step counter (rua_lr_schedule_step); lr is then not looked at
+    use_ema: bool = False                                    # E = momentum * E + (1 - momentum) * P behind every optimizer step (rua_ema_step)
+    ema_momentum: float = 0.99
+    ema_overwrite_frequency: Optional[int] = None            # every that many steps P takes E's values
+
+    def sched_options(self) -> Dict[str, object]:
+        """The schedule (as its get_config dict, or None) and the three EMA options as a dict (checkpoint metadata)."""
+        return dict(lr_schedule=self.lr_schedule.get_config() if self.lr_schedule is not None else None, use_ema=bool(self.use_ema),
+                    ema_momentum=float(self.ema_momentum), ema_overwrite_frequency=self.ema_overwrite_frequency)
 
     def clip_options(self) -> Dict[str, object]:
         """The six options as a dict (checkpoint metadata, Model.compile)."""
@@ -1537,6 +1551,9 @@ class Engine:
         self.loss: Optional[LossSpec] = None
         self.clip: Optional[dict] = None                    # device tables of clip.py's options (_setup_clip); None: every option off
         self._s_backed = False
+        self.E: Optional[torch.Tensor] = None               # use_ema: the moving average of P (fp32, P's layout), allocated by compile()
+        self._sched = None                                  # lr_schedule: the rua_lr_schedule the rate kernel takes by value
+        self._in_ema = False                                # inside ema_weights(): P and E have swapped contents
         self.graphs: Dict[Tuple[int, bool], Graph] = {}
         self.class_w_ptr = None
         self.scalars_ptr = 0
@@ -1651,6 +1668,11 @@ class Engine:
         if iv is not None and (isinstance(iv, bool) or not isinstance(iv, (int, np.integer)) or not 0 <= iv <= 16):
             raise ValueError(f"ignore_void {iv!r}: None (off) or a margin in 0..16")
         CL.check_options(spec.clipnorm, spec.global_clipnorm, spec.clipvalue, spec.weight_decay)
+        SC.check_ema_options(spec.use_ema, spec.ema_momentum, spec.ema_overwrite_frequency)
+        if spec.lr_schedule is not None and not isinstance(spec.lr_schedule, SC.LearningRateSchedule):
+            raise ValueError(f"lr_schedule {spec.lr_schedule!r}: None or a schedule of resunet_a_mltsk_keras_amd.schedules")
+        if self._in_ema:
+            raise RuntimeError("compile() inside ema_weights(): leave the block first")
         if self.loss is not None and (self.loss.optimizer != spec.optimizer):
             self._t_dev, self._lr_base_dev = -1, None          # device-side step counter / base rate are pushed again
         self.loss = spec
@@ -1661,6 +1683,52 @@ class Engine:
         else:
             self.class_w_ptr = None
         self._setup_clip(spec)
+        self._sched = SC.to_struct(spec.lr_schedule) if spec.lr_schedule is not None else None
+        self.E = None
+        if spec.use_ema and self.dev is not None:
+            self.E = torch.empty_like(self.P)
+            self.reset_ema()
+
+    def reset_ema(self):
+        """use_ema: E = P (compile(), weights from a file without an average, a broadcast): padding stays zero and the average starts sane."""
+        if self.E is not None:
+            self.E.copy_(self.P)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the block under the averaged weights: the CONTENTS of P and E are swapped on the device (the recorded plans hold P's
+        pointer, so the buffers stay), the weight copies are marked stale, and everything is swapped back on exit.  A training step inside
+        the block raises.  BatchNorm moving statistics are not averaged: the block runs with the current ones."""
+        if self.E is None:
+            raise RuntimeError("ema_weights(): the model was compiled without use_ema")
+        if self._in_ema:
+            raise RuntimeError("ema_weights() blocks do not nest")
+        self._swap_ema()
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self._in_ema = False
+            self._swap_ema()
+
+    def _swap_ema(self):
+        tmp = self.P.clone()
+        self.P.copy_(self.E); self.E.copy_(tmp)
+        self.params_changed()
+
+    def finalize_ema(self):
+        """P = E for good (Keras' optimizer.finalize_variable_values); E keeps its values."""
+        if self.E is None:
+            raise RuntimeError("finalize_ema(): the model was compiled without use_ema")
+        if self._in_ema:
+            raise RuntimeError("finalize_ema() inside ema_weights(): leave the block first")
+        self.P.copy_(self.E)
+        self.params_changed()
+
+    def current_lr(self) -> float:
+        """The base rate of the NEXT optimizer step: schedules.host_lr at the step counter under a schedule, loss.lr otherwise."""
+        sp = self.loss
+        return SC.host_lr(sp.lr_schedule, self.t) if sp.lr_schedule is not None else float(sp.lr)
 
     def _setup_clip(self, spec: LossSpec):
         """The device side of clip.py's options: chunk and variable tables (built once, here), the per-chunk partials, the per-variable sums and
@@ -1998,7 +2066,14 @@ class Engine:
         (`rua_lr_step`), so a captured step replays with no host-side scalar update in between; the host only pushes the
         base rate / the counter when they were changed from outside (K.set_value(optimizer.lr), a loaded checkpoint)."""
         sp = self.loss
-        if self._t_dev != self.t or self._lr_base_dev != sp.lr:
+        if self._in_ema:
+            raise RuntimeError("a training step inside ema_weights(): P holds the averaged weights; leave the block first")
+        if sp.lr_schedule is not None:
+            # the rate kernel writes the base rate itself (lr_state[1]) from the counter: only a counter changed from outside (a checkpoint) is pushed
+            if self._t_dev != self.t:
+                self.lr_state.copy_(torch.tensor([float(self.t), SC.host_lr(sp.lr_schedule, self.t)], dtype=torch.float64))
+                self._t_dev, self._lr_base_dev = self.t, None
+        elif self._t_dev != self.t or self._lr_base_dev != sp.lr:
             self.lr_state.copy_(torch.tensor([float(self.t), float(sp.lr)], dtype=torch.float64))
             self._t_dev, self._lr_base_dev = self.t, sp.lr
         self.t += 1
@@ -2006,8 +2081,12 @@ class Engine:
 
     def _launch_optimizer(self, grad_scale, s):
         sp = self.loss
-        L.lib().call("rua_lr_step", self.lr_state.data_ptr(), self.lr_dev.data_ptr(), 1 if sp.optimizer == "adam" else 0,
-                     float(sp.beta_1), float(sp.beta_2), C.c_void_p(s))
+        if self._sched is not None:                         # the same one-thread launch, with the schedule's constants by value
+            L.lib().call("rua_lr_schedule_step", self.lr_state.data_ptr(), self.lr_dev.data_ptr(), self._sched, 1 if sp.optimizer == "adam" else 0,
+                         float(sp.beta_1), float(sp.beta_2), C.c_void_p(s))
+        else:
+            L.lib().call("rua_lr_step", self.lr_state.data_ptr(), self.lr_dev.data_ptr(), 1 if sp.optimizer == "adam" else 0,
+                         float(sp.beta_1), float(sp.beta_2), C.c_void_p(s))
         wc = self.Wf.data_ptr() if self.opt_wcopy else None    # bf16 storage: the updated weights leave as the forward-layout copy in the same pass
         ck = self.clip
         if ck is not None:
@@ -2028,6 +2107,7 @@ class Engine:
                 lib.call("rua_sgd_step_seg", self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), ck["chunks"].data_ptr(), ck["n_chunks"],
                          ck["vars"].data_ptr(), ck["coef"].data_ptr(), flag, self.lr_dev.data_ptr(), self.lr_state.data_ptr(), sp.momentum,
                          grad_scale, ck["cv"], ck["wd"], 1, wc, sv)
+            self._launch_ema(wc, flag, s)
             if ck["s_backup"] is not None:
                 lib.call("rua_state_copy", self.S.data_ptr(), ck["s_backup"].data_ptr(), self.params.ns, flag, sv)
             return
@@ -2037,6 +2117,16 @@ class Engine:
         else:
             L.lib().call("rua_sgd_step_w", self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.params.n, 0.0,
                          self.lr_dev.data_ptr(), sp.momentum, grad_scale, 1, wc, C.c_void_p(s))
+        self._launch_ema(wc, None, s)
+
+    def _launch_ema(self, wc, flag, s):
+        """use_ema: the moving average right behind the optimizer kernel, inside the same capture.  The step counter (first-step copy, overwrite
+        period) and the skip flag are read on the device; an overwrite refreshes the forward-layout copy the optimizer wrote (wc) as well."""
+        if self.E is None:
+            return
+        sp = self.loss
+        L.lib().call("rua_ema_step", self.E.data_ptr(), self.P.data_ptr(), wc, self.params.n, float(sp.ema_momentum), self.lr_state.data_ptr(),
+                     int(sp.ema_overwrite_frequency or 0), flag, C.c_void_p(s))
 
     def optimizer_step(self, grad_scale: float = 1.0):
         self._set_lr()

@@ -39,9 +39,34 @@ class _Var:
         return self.value
 
 
+class _SchedVar(_Var):
+    """optimizer.lr under a learning-rate schedule: K.get_value gives schedules.host_lr at the engine's step counter (step 0 before the
+    optimizer is compiled into a model); K.set_value raises, as Keras does for an optimizer built with a schedule."""
+
+    def __init__(self, schedule):
+        self.schedule = schedule
+        self.engine = None
+
+    @property
+    def value(self):
+        from .schedules import host_lr
+        return host_lr(self.schedule, self.engine.t if self.engine is not None else 0)
+
+    @value.setter
+    def value(self, x):
+        raise TypeError("this optimizer was created with a learning-rate schedule as its learning_rate, hence its learning rate is not settable")
+
+
+def _lr_var(learning_rate, lr, default):
+    from .schedules import LearningRateSchedule
+    v = learning_rate if learning_rate is not None else (lr if lr is not None else default)
+    return _SchedVar(v) if isinstance(v, LearningRateSchedule) else _Var(v)
+
+
 class _ClipOptions:
     """Keras' clipnorm / global_clipnorm / clipvalue / weight_decay (clip.py has the definitions) and this package's skip_nonfinite, shared by
-    Adam and SGD: at most one clip option, each positive; exclude_from_weight_decay takes substrings of variable names, as Keras does."""
+    Adam and SGD: at most one clip option, each positive; exclude_from_weight_decay takes substrings of variable names, as Keras does.
+    Also the two optimizers' share of the learning-rate schedule and of use_ema / ema_momentum / ema_overwrite_frequency (schedules.py)."""
 
     def _set_clip(self, clipnorm, global_clipnorm, clipvalue, weight_decay, skip_nonfinite):
         from .clip import check_options
@@ -49,6 +74,27 @@ class _ClipOptions:
         self.clipnorm, self.global_clipnorm, self.clipvalue = clipnorm, global_clipnorm, clipvalue
         self.weight_decay, self.skip_nonfinite = weight_decay, bool(skip_nonfinite)
         self.decay_exclude: List[str] = []
+
+    def _set_ema(self, use_ema, ema_momentum, ema_overwrite_frequency):
+        """Keras' use_ema / ema_momentum / ema_overwrite_frequency (schedules.py has the definition), validated as Keras validates them."""
+        from .schedules import check_ema_options
+        check_ema_options(use_ema, ema_momentum, ema_overwrite_frequency)
+        self.use_ema, self.ema_momentum, self.ema_overwrite_frequency = bool(use_ema), float(ema_momentum), ema_overwrite_frequency
+        self._model = None
+
+    @property
+    def lr_schedule(self):
+        return self.lr.schedule if isinstance(self.lr, _SchedVar) else None
+
+    def sched_options(self):
+        return dict(lr_schedule=self.lr_schedule, use_ema=self.use_ema, ema_momentum=self.ema_momentum,
+                    ema_overwrite_frequency=self.ema_overwrite_frequency)
+
+    def finalize_variable_values(self, var_list=None):
+        """Keras' name for Model.finalize_ema: the averaged weights become the model's weights for good (use_ema only)."""
+        if self._model is None:
+            raise RuntimeError("finalize_variable_values: compile the optimizer into a model first")
+        self._model.finalize_ema()
 
     def exclude_from_weight_decay(self, var_list=None, var_names=None):
         """Variables whose name contains one of var_names do not decay (call before compile).  var_list - Keras' list of variable objects -
@@ -67,10 +113,10 @@ class _ClipOptions:
 
 class Adam(_ClipOptions):
     def __init__(self, lr=None, learning_rate=None, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, global_clipnorm=None, clipvalue=None,
-                 weight_decay=None, skip_nonfinite=False, **_):
+                 weight_decay=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, **_):
         self._set_clip(clipnorm, global_clipnorm, clipvalue, weight_decay, skip_nonfinite)
-        v = learning_rate if learning_rate is not None else (lr if lr is not None else 1e-3)
-        self.lr = _Var(v)
+        self._set_ema(use_ema, ema_momentum, ema_overwrite_frequency)
+        self.lr = _lr_var(learning_rate, lr, 1e-3)
         self.learning_rate = self.lr
         self.beta_1, self.beta_2, self.epsilon, self.kind = beta_1, beta_2, epsilon, "adam"
         if abs(epsilon - 1e-7) > 1e-12:
@@ -79,10 +125,10 @@ class Adam(_ClipOptions):
 
 class SGD(_ClipOptions):
     def __init__(self, lr=None, learning_rate=None, momentum=0.0, nesterov=False, clipnorm=None, global_clipnorm=None, clipvalue=None,
-                 weight_decay=None, skip_nonfinite=False, **_):
+                 weight_decay=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, **_):
         self._set_clip(clipnorm, global_clipnorm, clipvalue, weight_decay, skip_nonfinite)
-        v = learning_rate if learning_rate is not None else (lr if lr is not None else 1e-2)
-        self.lr = _Var(v)
+        self._set_ema(use_ema, ema_momentum, ema_overwrite_frequency)
+        self.lr = _lr_var(learning_rate, lr, 1e-2)
         self.learning_rate = self.lr
         self.momentum, self.kind = momentum, "sgd"
         if nesterov:
@@ -98,7 +144,7 @@ class _Backend:
 
     @staticmethod
     def set_value(v, x):
-        v.value = float(x)
+        v.value = float(x)                                     # raises under a learning-rate schedule (_SchedVar)
 
     @staticmethod
     def epsilon():
@@ -298,7 +344,9 @@ class Model:
         The optimizer's clipnorm / global_clipnorm / clipvalue / weight_decay (and exclude_from_weight_decay) / skip_nonfinite go into the
         LossSpec as they are (clip.py has the definitions; they ARE stored in .h5 files).  skip_nonfinite: a step whose gradient is not finite
         changes neither weights nor moments nor BatchNorm statistics, but still advances the step counter - it costs one t of Adam's bias
-        correction.  clip_report() tells how many steps were skipped and clipped."""
+        correction.  clip_report() tells how many steps were skipped and clipped.
+        A schedules.LearningRateSchedule as the optimizer's learning_rate and use_ema / ema_momentum / ema_overwrite_frequency go the same
+        way (schedules.py has the definitions; stored in .h5 files, the averaged weights with them)."""
         margin = void_margin(ignore_void)
         if optimizer is None or isinstance(optimizer, str):
             optimizer = {"adam": Adam, "sgd": SGD}[optimizer or "adam"]()
@@ -318,8 +366,10 @@ class Model:
         spec = LossSpec(kind=kinds, weight=weights, class_weights=cw, optimizer=optimizer.kind, lr=optimizer.lr.value,
                         beta_1=getattr(optimizer, "beta_1", 0.9), beta_2=getattr(optimizer, "beta_2", 0.999),
                         momentum=getattr(optimizer, "momentum", 0.0), ignore_void=margin,
-                        **(optimizer.clip_options() if hasattr(optimizer, "clip_options") else {}))
+                        **(optimizer.clip_options() if hasattr(optimizer, "clip_options") else {}),
+                        **(optimizer.sched_options() if hasattr(optimizer, "sched_options") else {}))
         self.engine.compile(spec)
+        self._attach_optimizer()
         self._finish_compile()
 
     def _finish_compile(self, restored_optimizer_state: bool = False):
@@ -330,7 +380,9 @@ class Model:
             from .dist import DataParallel
             dp = DataParallel(self.engine)                   # broadcasts rank 0's weights and BN state
             if restored_optimizer_state:
-                dp.broadcast_optimizer_state()               # ... and rank 0's Adam moments / step count on resume
+                dp.broadcast_optimizer_state()               # ... and rank 0's Adam moments / step count / weight average on resume
+            else:
+                self.engine.reset_ema()                      # use_ema: the average starts from the broadcast weights
         m = ["accuracy", "true_positives", "false_positives", "true_negatives", "false_negatives"]
         if self.cfg.multitasking:
             self.metrics_names = ["loss"] + [h + "_loss" for h in HEADS] + ["seg_" + x for x in m]
@@ -343,8 +395,27 @@ class Model:
         was given no clipnorm / global_clipnorm / clipvalue / weight_decay / skip_nonfinite.  Synchronises the device."""
         return self.engine.clip_report()
 
+    def _attach_optimizer(self):
+        """The optimizer's way back to the model: K.get_value(optimizer.lr) under a schedule reads the engine's step counter, and
+        optimizer.finalize_variable_values() is Model.finalize_ema."""
+        if isinstance(self.optimizer.lr, _SchedVar):
+            self.optimizer.lr.engine = self.engine
+        if hasattr(self.optimizer, "_model"):
+            self.optimizer._model = self
+
     def _sync_lr(self):
-        self.engine.loss.lr = self.optimizer.lr.value          # K.set_value(model.optimizer.lr, ...) takes effect
+        if self.engine.loss.lr_schedule is None:               # under a schedule the rate is the device's business (and set_value raises)
+            self.engine.loss.lr = self.optimizer.lr.value      # K.set_value(model.optimizer.lr, ...) takes effect
+
+    def ema_weights(self):
+        """`with model.ema_weights(): ...` - the block (predict, test_on_batch, predict_scene, evaluate_scenes, save_weights) runs under the
+        moving average of the weights (Adam / SGD(use_ema=True)); the trained weights are back on exit.  train_on_batch inside raises.
+        BatchNorm moving statistics are not averaged."""
+        return self.engine.ema_weights()
+
+    def finalize_ema(self):
+        """The averaged weights become the model's weights for good (Keras: optimizer.finalize_variable_values)."""
+        self.engine.finalize_ema()
 
     def _local_batch(self, x, y, local_shard=False):
         """Under DP `-bs` is the GLOBAL batch (train_ISPRS.py:314,347): each rank takes its contiguous shard.
@@ -495,11 +566,17 @@ class Model:
         if e.loss is not None:
             sp = e.loss
             meta["loss"] = dict(kind=sp.kind, weight=sp.weight, class_weights=sp.class_weights, optimizer=sp.optimizer, lr=sp.lr,
-                                beta_1=sp.beta_1, beta_2=sp.beta_2, momentum=sp.momentum, **sp.clip_options())
+                                beta_1=sp.beta_1, beta_2=sp.beta_2, momentum=sp.momentum, **sp.clip_options(), **sp.sched_options())
             og = root.require_group("optimizer_weights")
             og.set("rua/m:0", e.M1.cpu().numpy()); og.set("rua/v:0", e.V1.cpu().numpy())
             og.set("rua/iterations:0", np.array(e.t, np.int64))
-            og.attrs["weight_names"] = np.array([b"rua/iterations:0", b"rua/m:0", b"rua/v:0"])
+            names = [b"rua/iterations:0", b"rua/m:0", b"rua/v:0"]
+            if e.E is not None:
+                if e._in_ema:
+                    raise RuntimeError("save() inside ema_weights(): leave the block first (the file holds both sets of weights)")
+                og.set("rua/ema:0", e.E.cpu().numpy())
+                names.append(b"rua/ema:0")
+            og.attrs["weight_names"] = np.array(names)
         root.attrs["keras_version"] = b"2.4.0"
         root.attrs["backend"] = b"tensorflow"
         root.attrs["rua_checkpoint"] = json.dumps(meta).encode("utf8")
@@ -538,6 +615,7 @@ class Model:
             from . import h5lite
             given = h5lite.keras_weights_from_group(h5lite.read_h5(path))
         self.engine.set_weights(canonical_keras_names(given, self.engine.get_weights()))
+        self.engine.reset_ema()                                # a weights file holds no average: it starts again from these weights
 
 
 def canonical_keras_names(given: Dict[str, np.ndarray], want: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
@@ -615,15 +693,33 @@ def loss_clip_options(lo: dict) -> dict:
                 skip_nonfinite=bool(lo.get("skip_nonfinite", False)))
 
 
-def load_model(path, compile=True, custom_objects=None, dtype=None, input_shape=None, **_):
+def loss_sched_options(lo: dict) -> dict:
+    """The learning-rate schedule and the EMA options out of a checkpoint's `loss` metadata; a file written before they existed has none of
+    the keys: a constant rate, no average."""
+    from .schedules import schedule_from_config
+    q = lo.get("ema_overwrite_frequency")
+    return dict(lr_schedule=schedule_from_config(lo.get("lr_schedule")), use_ema=bool(lo.get("use_ema", False)),
+                ema_momentum=float(lo.get("ema_momentum", 0.99)), ema_overwrite_frequency=None if q is None else int(q))
+
+
+def load_model(path, compile=True, custom_objects=None, dtype=None, input_shape=None, weights="model", **_):
     """`load_model('best_model.h5')` (train_ISPRS.py:474, test_ISPRS.py:278).  Reads HDF5 only - nothing is unpickled, so a
     checkpoint cannot run code.  A file written by Model.save() restores graph, compile arguments and optimizer state; a file
     written by Keras itself (`model.save` / `save_weights` of the reference) is loaded as weights into a model whose
-    configuration is read off the variable shapes (compile it yourself afterwards)."""
+    configuration is read off the variable shapes (compile it yourself afterwards).
+    weights="ema": the model's weights are the file's moving average (`optimizer_weights/rua/ema:0`, written by a model trained with
+    use_ema) instead of the trained ones; a file without one is a ValueError."""
     from . import h5lite
+    if weights not in ("model", "ema"):
+        raise ValueError(f"weights {weights!r}: 'model' or 'ema'")
     if not h5lite.is_hdf5(path):
         raise ValueError(f"{path} is not an HDF5 file (checkpoints of this package and of Keras are HDF5; nothing else is read)")
     root = h5lite.read_h5(path)
+    ema = None
+    if weights == "ema":
+        if "optimizer_weights" not in root or "rua/ema:0" not in root["optimizer_weights"]:
+            raise ValueError(f"{path} holds no averaged weights (it was not saved by a model trained with use_ema)")
+        ema = np.ascontiguousarray(root["optimizer_weights"]["rua/ema:0"], dtype=np.float32)
     weights = h5lite.keras_weights_from_group(root)
     meta_raw = root.attrs.get("rua_checkpoint")
     if meta_raw is None:
@@ -640,17 +736,28 @@ def load_model(path, compile=True, custom_objects=None, dtype=None, input_shape=
     if compile and "loss" in meta:
         lo = meta["loss"]
         co = loss_clip_options(lo)
+        so = loss_sched_options(lo)
         ko = {k: v for k, v in co.items() if k != "decay_exclude"}
-        opt = Adam(lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], **ko) if lo["optimizer"] == "adam" else SGD(lr=lo["lr"], momentum=lo["momentum"], **ko)
+        ko.update({k: v for k, v in so.items() if k != "lr_schedule"})
+        rate = so["lr_schedule"] if so["lr_schedule"] is not None else lo["lr"]
+        opt = Adam(lr=rate, beta_1=lo["beta_1"], beta_2=lo["beta_2"], **ko) if lo["optimizer"] == "adam" else SGD(lr=rate, momentum=lo["momentum"], **ko)
         if co["decay_exclude"]:
             opt.exclude_from_weight_decay(var_names=co["decay_exclude"])
         m.optimizer = opt
         m.engine.compile(LossSpec(kind={k: int(v) for k, v in lo["kind"].items()}, weight=lo["weight"], class_weights=lo["class_weights"],
-                                  optimizer=lo["optimizer"], lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], momentum=lo["momentum"], **co))
+                                  optimizer=lo["optimizer"], lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], momentum=lo["momentum"], **co, **so))
+        m._attach_optimizer()
         og = root["optimizer_weights"]
         m.engine.M1.copy_(torch.from_numpy(np.ascontiguousarray(og["rua/m:0"]))); m.engine.V1.copy_(torch.from_numpy(np.ascontiguousarray(og["rua/v:0"])))
         m.engine.t = int(og["rua/iterations:0"])
+        if m.engine.E is not None and "rua/ema:0" in og:      # a file without an average: compile() left E = P
+            m.engine.E.copy_(torch.from_numpy(np.ascontiguousarray(og["rua/ema:0"])))
         m._finish_compile(restored_optimizer_state=True)
+    if ema is not None:
+        if ema.shape != tuple(m.engine.P.shape):
+            raise ValueError(f"{path}: the averaged weights have {ema.size} elements, the model's parameter buffer {m.engine.P.numel()}")
+        m.engine.P.copy_(torch.from_numpy(ema))
+        m.engine.params_changed()
     return m
 
 

@@ -41,10 +41,19 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
     excluded) and a guard that leaves weights, moments and BatchNorm statistics alone in a step whose gradient holds an Inf or a NaN,
     all decided on the GPU (resunet_a_mltsk_keras_amd/clip.py).  After each epoch the counts of skipped and clipped steps and the last
     gradient norm are printed.  With `-cp` the options come from the checkpoint.
+  * `--lr_schedule {constant,cosine,exponential,polynomial,piecewise,inverse_time}` with `--lr_decay_steps`, `--lr_warmup_steps`,
+    `--lr_warmup_target`, `--lr_alpha`, `--lr_decay_rate`, `--lr_end`, `--lr_power`, `--lr_staircase`, `--lr_cycle`, `--lr_boundaries`,
+    `--lr_values`: Keras' learning-rate schedules with `-lr` as the initial rate, computed on the GPU from the device's step counter
+    (resunet_a_mltsk_keras_amd/schedules.py).  The current rate is printed once per epoch.  With `-cp` the schedule comes from the
+    checkpoint and continues at its iteration; `-lr` is then not applied.
+  * `--ema yes --ema_momentum M --ema_overwrite_frequency N`: Keras' moving average of the weights (use_ema), updated on the GPU behind
+    every optimizer step.  Each epoch's validation and the best-model criterion then run under the averaged weights; the saved file
+    holds both sets (eval_scenes_ISPRS.py --weights ema evaluates the averaged one).
   * `--dtype {bf16,f32}`, `--seed`: engine options.  Launch with torch.distributed.run for multi-GPU data
     parallel (`-bs` is then the GLOBAL batch, as under MirroredStrategy).
 """
 import argparse
+import contextlib
 import json
 import math
 import os
@@ -131,7 +140,51 @@ def build_parser():
     p.add_argument("--decay_all", type=str2bool, default=False, help="weight_decay: decay biases and BatchNorm gamma / beta too (default: kernels only)")
     p.add_argument("--skip_nonfinite", type=str2bool, default=False,
                    help="leave weights, moments and BatchNorm statistics alone in a step whose gradient holds an Inf or a NaN")
+    p.add_argument("--lr_schedule", choices=["constant", "cosine", "exponential", "polynomial", "piecewise", "inverse_time"], default="constant",
+                   help="learning-rate schedule (Keras' formulas, computed on the GPU); -lr is the initial rate")
+    p.add_argument("--lr_decay_steps", type=int, default=None, metavar="N", help="lr_schedule: optimizer steps of one decay (every kind but piecewise)")
+    p.add_argument("--lr_warmup_steps", type=int, default=0, metavar="N", help="cosine: linear warm-up from -lr to --lr_warmup_target over N steps")
+    p.add_argument("--lr_warmup_target", type=float, default=None, metavar="LR", help="cosine: the rate the warm-up ends at and the cosine starts from")
+    p.add_argument("--lr_alpha", type=float, default=0.0, metavar="A", help="cosine: the final rate as a fraction of the start of the decay")
+    p.add_argument("--lr_decay_rate", type=float, default=None, metavar="R", help="exponential / inverse_time: the decay rate")
+    p.add_argument("--lr_staircase", type=str2bool, default=False, help="exponential / inverse_time: decay in whole multiples of --lr_decay_steps")
+    p.add_argument("--lr_end", type=float, default=1e-4, metavar="LR", help="polynomial: the final rate")
+    p.add_argument("--lr_power", type=float, default=1.0, metavar="P", help="polynomial: the power")
+    p.add_argument("--lr_cycle", type=str2bool, default=False, help="polynomial: start a new, longer decay when one ends")
+    p.add_argument("--lr_boundaries", type=str, default=None, metavar="S1,S2,..", help="piecewise: at most 16 increasing step counts")
+    p.add_argument("--lr_values", type=str, default=None, metavar="LR0,LR1,..", help="piecewise: one rate more than boundaries; LRi holds while step <= Si")
+    p.add_argument("--ema", type=str2bool, default=False, help="keep a moving average of the weights; validation and the best-model criterion use it")
+    p.add_argument("--ema_momentum", type=float, default=0.99, metavar="M", help="ema: average = M * average + (1 - M) * weights after every step")
+    p.add_argument("--ema_overwrite_frequency", type=int, default=None, metavar="N", help="ema: every N steps the weights take the average's values")
     return p
+
+
+def schedule_options(args):
+    """--lr_schedule and its numeric flags as the optimizer's learning_rate (a float for `constant`), --ema* as its keywords; checked before
+    anything is built (resunet_a_mltsk_keras_amd/schedules.py has the definitions)."""
+    from resunet_a_mltsk_keras_amd import schedules as SC
+    kind, lr = args.lr_schedule, args.learning_rate
+    need = lambda flag, v: sys.exit(f"--lr_schedule {kind} needs {flag}") if v is None else v
+    try:
+        if kind == "constant":
+            rate = lr
+        elif kind == "piecewise":
+            b = [int(v) for v in need("--lr_boundaries", args.lr_boundaries).split(",")]
+            rate = SC.PiecewiseConstantDecay(b, [float(v) for v in need("--lr_values", args.lr_values).split(",")])
+        else:
+            steps = need("--lr_decay_steps", args.lr_decay_steps)
+            if kind == "cosine":
+                rate = SC.CosineDecay(lr, steps, alpha=args.lr_alpha, warmup_target=args.lr_warmup_target, warmup_steps=args.lr_warmup_steps)
+            elif kind == "polynomial":
+                rate = SC.PolynomialDecay(lr, steps, end_learning_rate=args.lr_end, power=args.lr_power, cycle=args.lr_cycle)
+            else:
+                cls = SC.ExponentialDecay if kind == "exponential" else SC.InverseTimeDecay
+                rate = cls(lr, steps, need("--lr_decay_rate", args.lr_decay_rate), staircase=args.lr_staircase)
+        kw = dict(use_ema=bool(args.ema), ema_momentum=args.ema_momentum, ema_overwrite_frequency=args.ema_overwrite_frequency)
+        SC.check_ema_options(**kw)
+    except ValueError as exc:
+        sys.exit(f"learning-rate schedule / ema flags: {exc}")
+    return rate, kw
 
 
 def optimizer_options(args):
@@ -335,6 +388,8 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
         shard["norm_type"] = args.norm_type
     labels = (lambda yb: None) if scenes is not None else (lambda yb: yb["classes"]) if compact else (lambda yb: yb if args.multitasking else yb["seg"])
     min_loss, cont = float("inf"), 0
+    use_ema = bool(getattr(getattr(net, "optimizer", None), "use_ema", False))
+    from resunet_a_mltsk_keras_amd.keras_api import K
     rng = np.random.default_rng(args.seed)
     say(net.output_names)
     for epoch in range(epochs):
@@ -344,8 +399,10 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
         for xb, yb in ld_tr:
             acc_tr += np.asarray(net.train_on_batch(x=xb, y=labels(yb), return_dict=False, **shard))
         acc_tr /= max(n_tr, 1)
-        for xb, yb in ld_va:
-            acc_va += np.asarray(net.test_on_batch(x=xb, y=labels(yb), **shard))
+        # --ema yes: the validation - and with it the best-model criterion - runs under the averaged weights (the trained ones are back after it)
+        with (net.ema_weights() if use_ema else contextlib.nullcontext()):
+            for xb, yb in ld_va:
+                acc_va += np.asarray(net.test_on_batch(x=xb, y=labels(yb), **shard))
         acc_va /= max(n_va, 1)
         tm, vm = dict(zip(metrics_names, acc_tr)), dict(zip(metrics_names, acc_va))
         pre = "seg_" if args.multitasking else ""
@@ -366,6 +423,8 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
                 vw.scalar("Segmentation/MCC", mcc, epoch)
                 print(f"| {'Total':8s}{tm['loss']:13.5f}{vm['loss']:13.5f}{0:13d}{0:13d} |\n+{'-' * 62}+")
                 tw.scalar("Total/Loss", tm["loss"], epoch); vw.scalar("Total/Loss", vm["loss"], epoch)
+        if getattr(net, "optimizer", None) is not None:
+            say(f"Learning rate: {K.get_value(net.optimizer.lr):.6g}" + (" (validated under the averaged weights)" if use_ema else ""))
         rep = net.clip_report() if hasattr(net, "clip_report") else None        # None: no clip / decay / skip option is on
         if rep is not None:
             say(f"Optimizer: {rep['skipped']} steps skipped (non-finite gradient), {rep['clipped']} clipped by a norm so far; last gradient norm {rep['norm']:.6g}")
@@ -445,7 +504,9 @@ def main(argv=None):
     rows = cols = args.patch_size
     channels = args.channels or (int(images[0].shape[-1]) if scenes is not None else int(np.load(xs[0]).shape[-1]))
     opt_kw = optimizer_options(args)
-    optm = Adam(lr=args.learning_rate, beta_1=0.9, **opt_kw) if args.optimizer == "adam" else SGD(lr=args.learning_rate, momentum=0.8, **opt_kw)
+    rate, ema_kw = schedule_options(args)
+    opt_kw.update(ema_kw)
+    optm = Adam(lr=rate, beta_1=0.9, **opt_kw) if args.optimizer == "adam" else SGD(lr=rate, momentum=0.8, **opt_kw)
     if args.weight_decay and not args.decay_all:
         from resunet_a_mltsk_keras_amd.clip import DEFAULT_DECAY_EXCLUDE
         optm.exclude_from_weight_decay(var_names=list(DEFAULT_DECAY_EXCLUDE))
@@ -484,8 +545,11 @@ def main(argv=None):
         say(f"[INFO] loading {args.checkpoint_path}...")
         model = load_model(args.checkpoint_path)
         say(f"[INFO] old learning rate: {K.get_value(model.optimizer.lr)}")
-        K.set_value(model.optimizer.lr, args.learning_rate)
-        say(f"[INFO] new learning rate: {K.get_value(model.optimizer.lr)}")
+        if model.optimizer.lr_schedule is not None:
+            say(f"[INFO] the checkpoint trains under {model.optimizer.lr_schedule!r}: -lr is not applied, the schedule continues at its iteration")
+        else:
+            K.set_value(model.optimizer.lr, args.learning_rate)
+            say(f"[INFO] new learning rate: {K.get_value(model.optimizer.lr)}")
 
     if rank == 0:
         os.makedirs(args.results_path, exist_ok=True)
