@@ -564,6 +564,31 @@ int rua_lr_schedule_step(double* state, float* lr_out, rua_lr_schedule sched, in
 int rua_ema_step(float* ema, float* theta, void* wcopy_bf16, int64_t n, float momentum, const double* lr_state, int overwrite_every,
                  const int32_t* flag, void* stream);
 
+/* ---- gradient accumulation inside the step (accum.py holds the host definition; Keras 3's gradient_accumulation_steps) ---------------------
+ * With K steps the optimizer applies the mean of K consecutive gradients once every K calls.  Per call the step issues, behind the backward (and
+ * the all-reduce) and in front of everything else of the optimizer tail:
+ *   rua_accum_gate        one thread: m = acc_state[0] + 1; hold[0] = m < k (1: a HOLD step, 0: an UPDATE step); acc_state[0] = hold ? m : 0.
+ *                         acc_state[0] - the gradients of this cycle already accumulated, 0 .. k - 1 - is device state: a captured step replays
+ *                         the decision.  The host pushes it only when it changed outside (a checkpoint, a re-compile).
+ *   rua_accum_step        one streaming pass, 16-byte accesses, no atomics, every operation rounded on its own in fp32, Inf / NaN propagate:
+ *                           hold[0] != 0:  a = fadd(a, g)                                 (g is left as it is: the flagged optimizer zeroes it)
+ *                           hold[0] == 0:  g = fdiv(fadd(g, a), (float)k) - a correctly rounded division -, a = 0
+ *                         g and a 16-byte aligned and distinct, n > 0, 2 <= k <= 2^24.
+ *   the *_gated forms     of rua_lr_step, rua_lr_schedule_step, rua_grad_sumsq and rua_clip_finish: the same kernels with hold (not NULL) as
+ *                         a last argument.  hold[0] != 0: state, rate, partials, per-variable sums, coefficients and report keep their bits.
+ *                         hold[0] == 0: exactly the ungated entry point.  rua_clip_finish_gated writes TWO flags: flag2[0] = this update was
+ *                         skipped (skip_nonfinite; 0 on a hold step) - rua_state_copy's restore of the BatchNorm statistics reads this one, so
+ *                         it never fires on a hold step -, flag2[1] = hold or skipped - rua_adam_step_seg / rua_sgd_step_seg (which then only
+ *                         zero g and rewrite the bf16 copy of the unchanged weights) and rua_ema_step read this one. */
+int rua_accum_gate(int32_t* acc_state, int k, int32_t* hold, void* stream);
+int rua_accum_step(float* g, float* a, int64_t n, int k, const int32_t* hold, void* stream);
+int rua_lr_step_gated(double* state, float* lr_out, int adam, double beta1, double beta2, const int32_t* hold, void* stream);
+int rua_lr_schedule_step_gated(double* state, float* lr_out, rua_lr_schedule sched, int adam, double beta1, double beta2, const int32_t* hold,
+                               void* stream);
+int rua_grad_sumsq_gated(const float* g, const rua_opt_chunk* chunks, int n_chunks, double* partials, const int32_t* hold, void* stream);
+int rua_clip_finish_gated(const double* partials, int n_chunks, const rua_opt_var* vars, int n_vars, int mode, double c, double grad_scale,
+                          int skip_nonfinite, double* var_sumsq, float* coef, int32_t* flag2, double* report, const int32_t* hold, void* stream);
+
 /* ---- multitask training targets from uint8 patches (labels.py; the reference's preprocess_save_patches_ISPRS.py:206-228,
  * multitasking_utils.py:6-35) ------------------------------------------------------------------------------------------------
  * img [N][H][W][Cin] and cls [N][H][W] are uint8 (4-byte aligned); x [N][H][W][Cin], seg / bound / dist [N][H][W][C] and

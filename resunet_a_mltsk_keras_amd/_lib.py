@@ -189,6 +189,12 @@ _SIGS = {
     "rua_state_copy": ([vp, vp, i64, vp, vp], i32),
     "rua_lr_schedule_step": ([vp, vp, LrSchedule, i32, f64, f64, vp], i32),
     "rua_ema_step": ([vp, vp, vp, i64, f32, vp, i32, vp, vp], i32),
+    "rua_accum_gate": ([vp, i32, vp, vp], i32),
+    "rua_accum_step": ([vp, vp, i64, i32, vp, vp], i32),
+    "rua_lr_step_gated": ([vp, vp, i32, f64, f64, vp, vp], i32),
+    "rua_lr_schedule_step_gated": ([vp, vp, LrSchedule, i32, f64, f64, vp, vp], i32),
+    "rua_grad_sumsq_gated": ([vp, vp, i32, vp, vp, vp], i32),
+    "rua_clip_finish_gated": ([vp, i32, vp, i32, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp], i32),
     "rua_tanimoto_sums_void": ([vp, vp, vp, i32, i64, i32, vp, vp], i32),
     "rua_head_fwd_loss_void": ([vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i64, i32, i32, i32, i32, vp, vp], i32),
     "rua_pixel_loss_void": ([i32, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp], i32),

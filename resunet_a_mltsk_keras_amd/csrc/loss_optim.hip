@@ -640,8 +640,9 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ th, float*
 // Step-dependent learning rate on the device, so that a captured training step needs no host-side scalar update between
 // replays: state[0] = optimizer steps taken (advanced here), state[1] = base learning rate; lr_out[0] = the rate the
 // optimizer kernel launched next reads (Adam: Keras' lr * sqrt(1 - beta2^t) / (1 - beta1^t), train_ISPRS.py:404-407).
-__global__ void lr_step_kernel(double* state, float* lr_out, int adam, double beta1, double beta2) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
+// hold (NULL: never) != 0 - a hold step of gradient accumulation -: nothing is read or written (the gated entry points further down).
+__global__ void lr_step_kernel(double* state, float* lr_out, int adam, double beta1, double beta2, const int32_t* hold) {
+  if (blockIdx.x == 0 && threadIdx.x == 0 && !(hold != nullptr && hold[0] != 0)) {
     const double t = state[0] + 1.0;
     state[0] = t;
     double lr = state[1];
@@ -651,8 +652,14 @@ __global__ void lr_step_kernel(double* state, float* lr_out, int adam, double be
 }
 extern "C" int rua_lr_step(double* state, float* lr_out, int adam, double beta1, double beta2, void* stream) {
   RUA_CHECK_ARG(state && lr_out, "rua_lr_step: null pointer");
-  hipLaunchKernelGGL(lr_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, lr_out, adam, beta1, beta2);
+  hipLaunchKernelGGL(lr_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, lr_out, adam, beta1, beta2, (const int32_t*)nullptr);
   RUA_LAUNCH_CHECK("rua_lr_step");
+  return RUA_OK;
+}
+extern "C" int rua_lr_step_gated(double* state, float* lr_out, int adam, double beta1, double beta2, const int32_t* hold, void* stream) {
+  RUA_CHECK_ARG(state && lr_out && hold && ((size_t)hold & 3) == 0, "rua_lr_step_gated: null or misaligned pointer");
+  hipLaunchKernelGGL(lr_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, lr_out, adam, beta1, beta2, hold);
+  RUA_LAUNCH_CHECK("rua_lr_step_gated");
   return RUA_OK;
 }
 extern "C" int rua_adam_step_w(float* theta, float* g, float* m, float* v, int64_t n, float lr_t, const float* lr_t_dev, float beta1, float beta2,
@@ -692,8 +699,10 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, const rua_opt_chunk* __restrict__ chunks, double* __restrict__ partials) {
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, const rua_opt_chunk* __restrict__ chunks, double* __restrict__ partials,
+                                                         const int32_t* __restrict__ hold) {
   __shared__ double sh[4];
+  if (hold != nullptr && hold[0] != 0) return;          // a hold step of gradient accumulation (uniform): the gated finisher will not look at the partials
   const rua_opt_chunk ck = chunks[blockIdx.x];
   const float* gp = g + ck.off;
   const int n4 = ck.len >> 2;
@@ -712,8 +721,16 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict
 extern "C" int rua_grad_sumsq(const float* g, const rua_opt_chunk* chunks, int n_chunks, double* partials, void* stream) {
   RUA_CHECK_ARG(g && chunks && partials && n_chunks > 0, "rua_grad_sumsq: bad arguments");
   RUA_CHECK_ARG(((size_t)g & 15) == 0 && ((size_t)chunks & 15) == 0 && ((size_t)partials & 7) == 0, "rua_grad_sumsq: g and the chunk table must be 16-byte aligned");
-  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, g, chunks, partials);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, g, chunks, partials, (const int32_t*)nullptr);
   RUA_LAUNCH_CHECK("rua_grad_sumsq");
+  return RUA_OK;
+}
+extern "C" int rua_grad_sumsq_gated(const float* g, const rua_opt_chunk* chunks, int n_chunks, double* partials, const int32_t* hold, void* stream) {
+  RUA_CHECK_ARG(g && chunks && partials && hold && n_chunks > 0, "rua_grad_sumsq_gated: bad arguments");
+  RUA_CHECK_ARG(((size_t)g & 15) == 0 && ((size_t)chunks & 15) == 0 && ((size_t)partials & 7) == 0 && ((size_t)hold & 3) == 0,
+                "rua_grad_sumsq_gated: g and the chunk table must be 16-byte aligned");
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, g, chunks, partials, hold);
+  RUA_LAUNCH_CHECK("rua_grad_sumsq_gated");
   return RUA_OK;
 }
 
@@ -737,8 +754,17 @@ __device__ __forceinline__ double add_in_order(double s, const double* x, int n)
 }
 __global__ __launch_bounds__(256) void clip_finish_kernel(const double* __restrict__ partials, int n_chunks, const rua_opt_var* __restrict__ vars, int n_vars,
                                                           int mode, double c, double gs, int skip_nonfinite, double* __restrict__ var_sumsq,
-                                                          float* __restrict__ coef, int32_t* __restrict__ flag, double* __restrict__ report) {
+                                                          float* __restrict__ coef, int32_t* __restrict__ flag, double* __restrict__ report,
+                                                          const int32_t* __restrict__ hold) {
   __shared__ double tile[FIN_TILE];
+  if (hold != nullptr) {
+    // gradient accumulation (rua_clip_finish_gated): flag[0] stays "this update was skipped" - what the BatchNorm restore reads -, flag[1] is
+    // "hold or skipped" - what the optimizer and the moving average read.  A hold step writes the two flags and nothing else.
+    if (hold[0] != 0) {                                  // uniform: the whole block leaves before the first barrier
+      if (threadIdx.x == 0) { flag[0] = 0; flag[1] = 1; }
+      return;
+    }
+  }
   __shared__ double s_total;
   __shared__ float s_coef, s_min[4];
   __shared__ int s_skip;
@@ -787,6 +813,7 @@ __global__ __launch_bounds__(256) void clip_finish_kernel(const double* __restri
     for (int w = 1; w < 4; ++w) mn = s_min[w] < mn ? s_min[w] : mn;
     const int skip = s_skip;
     flag[0] = skip;
+    if (hold != nullptr) flag[1] = skip;
     report[0] = s_total;
     report[1] = (double)mn;
     report[2] += (double)skip;
@@ -801,8 +828,20 @@ extern "C" int rua_clip_finish(const double* partials, int n_chunks, const rua_o
   RUA_CHECK_ARG((((size_t)partials | (size_t)var_sumsq | (size_t)report) & 7) == 0 && ((size_t)vars & 15) == 0 && (((size_t)coef | (size_t)flag) & 3) == 0,
                 "rua_clip_finish: misaligned buffers");
   hipLaunchKernelGGL(clip_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_chunks, vars, n_vars, mode, c, grad_scale, skip_nonfinite, var_sumsq,
-                     coef, flag, report);
+                     coef, flag, report, (const int32_t*)nullptr);
   RUA_LAUNCH_CHECK("rua_clip_finish");
+  return RUA_OK;
+}
+extern "C" int rua_clip_finish_gated(const double* partials, int n_chunks, const rua_opt_var* vars, int n_vars, int mode, double c, double grad_scale,
+                                     int skip_nonfinite, double* var_sumsq, float* coef, int32_t* flag2, double* report, const int32_t* hold, void* stream) {
+  RUA_CHECK_ARG(partials && vars && var_sumsq && coef && flag2 && report && hold && n_vars > 0 && n_chunks > 0, "rua_clip_finish_gated: bad arguments");
+  RUA_CHECK_ARG(mode >= RUA_CLIP_NONE && mode <= RUA_CLIP_VALUE, "rua_clip_finish_gated: unknown mode %d", mode);
+  RUA_CHECK_ARG((mode != RUA_CLIP_GLOBAL_NORM && mode != RUA_CLIP_NORM) || c > 0.0, "rua_clip_finish_gated: the clip norm must be positive");
+  RUA_CHECK_ARG((((size_t)partials | (size_t)var_sumsq | (size_t)report) & 7) == 0 && ((size_t)vars & 15) == 0 &&
+                (((size_t)coef | (size_t)flag2 | (size_t)hold) & 3) == 0 && flag2 != hold, "rua_clip_finish_gated: misaligned buffers");
+  hipLaunchKernelGGL(clip_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_chunks, vars, n_vars, mode, c, grad_scale, skip_nonfinite, var_sumsq,
+                     coef, flag2, report, hold);
+  RUA_LAUNCH_CHECK("rua_clip_finish_gated");
   return RUA_OK;
 }
 
@@ -956,8 +995,9 @@ __device__ double sched_rate(const rua_lr_schedule& k, double s) {
     default: return k.initial;
   }
 }
-__global__ void lr_schedule_step_kernel(double* state, float* lr_out, const rua_lr_schedule sched, int adam, double beta1, double beta2) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
+__global__ void lr_schedule_step_kernel(double* state, float* lr_out, const rua_lr_schedule sched, int adam, double beta1, double beta2,
+                                        const int32_t* hold) {
+  if (blockIdx.x == 0 && threadIdx.x == 0 && !(hold != nullptr && hold[0] != 0)) {
     const double t = state[0] + 1.0;
     state[0] = t;
     double lr = sched_rate(sched, t - 1.0);
@@ -966,16 +1006,25 @@ __global__ void lr_schedule_step_kernel(double* state, float* lr_out, const rua_
     lr_out[0] = (float)lr;
   }
 }
-extern "C" int rua_lr_schedule_step(double* state, float* lr_out, rua_lr_schedule sched, int adam, double beta1, double beta2, void* stream) {
+static int lr_schedule_launch(const char* name, double* state, float* lr_out, const rua_lr_schedule& sched, int adam, double beta1, double beta2,
+                              const int32_t* hold, void* stream) {
   RUA_CHECK_ARG(state && lr_out && ((size_t)state & 7) == 0 && ((size_t)lr_out & 3) == 0, "rua_lr_schedule_step: null or misaligned pointer");
   RUA_CHECK_ARG(sched.kind >= RUA_SCHED_CONSTANT && sched.kind <= RUA_SCHED_INVERSE_TIME, "rua_lr_schedule_step: unknown kind %d", sched.kind);
   RUA_CHECK_ARG(sched.kind == RUA_SCHED_CONSTANT || sched.kind == RUA_SCHED_PIECEWISE || sched.decay_steps > 0.0, "rua_lr_schedule_step: decay_steps must be positive");
   RUA_CHECK_ARG(sched.kind != RUA_SCHED_PIECEWISE || (sched.n_boundaries >= 0 && sched.n_boundaries <= RUA_SCHED_MAX_BOUNDARIES),
                 "rua_lr_schedule_step: %d boundaries (at most %d)", sched.n_boundaries, RUA_SCHED_MAX_BOUNDARIES);
   RUA_CHECK_ARG(!(sched.kind == RUA_SCHED_COSINE && sched.warmup) || sched.warmup_steps >= 0.0, "rua_lr_schedule_step: negative warmup_steps");
-  hipLaunchKernelGGL(lr_schedule_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, lr_out, sched, adam, beta1, beta2);
-  RUA_LAUNCH_CHECK("rua_lr_schedule_step");
+  hipLaunchKernelGGL(lr_schedule_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, lr_out, sched, adam, beta1, beta2, hold);
+  RUA_LAUNCH_CHECK(name);
   return RUA_OK;
+}
+extern "C" int rua_lr_schedule_step(double* state, float* lr_out, rua_lr_schedule sched, int adam, double beta1, double beta2, void* stream) {
+  return lr_schedule_launch("rua_lr_schedule_step", state, lr_out, sched, adam, beta1, beta2, nullptr, stream);
+}
+extern "C" int rua_lr_schedule_step_gated(double* state, float* lr_out, rua_lr_schedule sched, int adam, double beta1, double beta2, const int32_t* hold,
+                                          void* stream) {
+  RUA_CHECK_ARG(hold && ((size_t)hold & 3) == 0, "rua_lr_schedule_step_gated: null or misaligned hold flag");
+  return lr_schedule_launch("rua_lr_schedule_step_gated", state, lr_out, sched, adam, beta1, beta2, hold, stream);
 }
 
 // Four elements per thread and stream (16-byte accesses; 8-byte for the bf16 copy), grid sized like adam_kernel's, the n % 4 tail element by
@@ -1028,5 +1077,61 @@ extern "C" int rua_ema_step(float* ema, float* theta, void* wcopy_bf16, int64_t 
   if (wcopy_bf16) hipLaunchKernelGGL((ema_kernel<true>), dim3((int)gr), dim3(256), 0, (hipStream_t)stream, ema, theta, (bf16_t*)wcopy_bf16, (long long)n, momentum, lr_state, overwrite_every, flag);
   else hipLaunchKernelGGL((ema_kernel<false>), dim3((int)gr), dim3(256), 0, (hipStream_t)stream, ema, theta, (bf16_t*)nullptr, (long long)n, momentum, lr_state, overwrite_every, flag);
   RUA_LAUNCH_CHECK("rua_ema_step");
+  return RUA_OK;
+}
+
+// ---- gradient accumulation (include/rua_hip.h; accum.py holds the host definition) ----------------------------------------------------------
+// The gate: one thread.  acc_state[0] = gradients of the current cycle already in the accumulator (0 .. k - 1).  Everything behind it in the step
+// reads hold[0]; the decision is device state, so a captured step replays it.
+__global__ void accum_gate_kernel(int32_t* acc_state, int k, int32_t* hold) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const int m = acc_state[0] + 1;
+    const int h = m < k ? 1 : 0;
+    acc_state[0] = h ? m : 0;
+    hold[0] = h;
+  }
+}
+extern "C" int rua_accum_gate(int32_t* acc_state, int k, int32_t* hold, void* stream) {
+  RUA_CHECK_ARG(acc_state && hold && (((size_t)acc_state | (size_t)hold) & 3) == 0, "rua_accum_gate: null or misaligned pointer");
+  RUA_CHECK_ARG(k >= 2, "rua_accum_gate: k = %d (at least 2)", k);
+  hipLaunchKernelGGL(accum_gate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc_state, k, hold);
+  RUA_LAUNCH_CHECK("rua_accum_gate");
+  return RUA_OK;
+}
+// ema_kernel's shape: four elements per thread and stream (16-byte accesses), a grid-stride loop, the n % 4 tail element by element, hold read once
+// per thread (uniform).  A hold step reads g and a and writes a (12 bytes per parameter; the flagged optimizer behind it zeroes g), an update step
+// reads both and writes both (16).  The quotient is an IEEE division (__fdiv_rn), not a product with 1 / k: accum.host_accumulate bit for bit.
+__global__ __launch_bounds__(256) void accum_kernel(float* __restrict__ g, float* __restrict__ a, long long n, float kf, const int32_t* __restrict__ hold) {
+  const bool h = hold[0] != 0;
+  const long long n4 = n >> 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    const float4 g4 = reinterpret_cast<const float4*>(g)[i];
+    float4 a4 = reinterpret_cast<const float4*>(a)[i];
+    if (h) {
+      a4.x = __fadd_rn(a4.x, g4.x); a4.y = __fadd_rn(a4.y, g4.y); a4.z = __fadd_rn(a4.z, g4.z); a4.w = __fadd_rn(a4.w, g4.w);
+      reinterpret_cast<float4*>(a)[i] = a4;
+    } else {
+      a4.x = __fdiv_rn(__fadd_rn(g4.x, a4.x), kf); a4.y = __fdiv_rn(__fadd_rn(g4.y, a4.y), kf);
+      a4.z = __fdiv_rn(__fadd_rn(g4.z, a4.z), kf); a4.w = __fdiv_rn(__fadd_rn(g4.w, a4.w), kf);
+      reinterpret_cast<float4*>(g)[i] = a4;
+      reinterpret_cast<float4*>(a)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  for (long long i = (n4 << 2) + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    if (h) {
+      a[i] = __fadd_rn(a[i], g[i]);
+    } else {
+      g[i] = __fdiv_rn(__fadd_rn(g[i], a[i]), kf);
+      a[i] = 0.f;
+    }
+  }
+}
+extern "C" int rua_accum_step(float* g, float* a, int64_t n, int k, const int32_t* hold, void* stream) {
+  RUA_CHECK_ARG(g && a && hold && n > 0 && g != a, "rua_accum_step: bad arguments");
+  RUA_CHECK_ARG((((size_t)g | (size_t)a) & 15) == 0 && ((size_t)hold & 3) == 0, "rua_accum_step: buffers must be 16-byte aligned");
+  RUA_CHECK_ARG(k >= 2 && k <= (1 << 24), "rua_accum_step: k = %d (2 .. 2^24: exact in fp32)", k);
+  int64_t gr = (n / 4 + 255) / 256; if (gr > 4096) gr = 4096; if (gr < 1) gr = 1;
+  hipLaunchKernelGGL(accum_kernel, dim3((int)gr), dim3(256), 0, (hipStream_t)stream, g, a, (long long)n, (float)k, hold);
+  RUA_LAUNCH_CHECK("rua_accum_step");
   return RUA_OK;
 }

@@ -187,13 +187,17 @@ class DataParallel:
         self._bcast(eng.M1); self._bcast(eng.V1)
         if getattr(eng, "E", None) is not None:               # use_ema: the weights' moving average travels with the moments
             self._bcast(eng.E)
-        t = torch.tensor([float(eng.t)], dtype=torch.float64)
+        if getattr(eng, "A", None) is not None:               # gradient accumulation: an open cycle's accumulator (and its counter, below) travels too
+            self._bcast(eng.A)
+        t = torch.tensor([float(eng.t), float(getattr(eng, "micro", 0))], dtype=torch.float64)
         if self.host_staged or not eng.P.is_cuda:
             dist.broadcast(t, 0, group=self.group)
         else:
             t = t.to(eng.P.device); dist.broadcast(t, 0, group=self.group)
-        eng.t = int(t.item())
+        eng.t = int(t[0].item())
         eng._t_dev = -1                                       # the device-side counter is pushed again at the next step
+        if getattr(eng, "A", None) is not None:
+            eng.micro, eng._micro_dev = int(t[1].item()), -1
 
     def reduce_scalars(self, sc: torch.Tensor) -> torch.Tensor:
         """Sum over the replicas of the step's loss / metric scalars ("all-reduce of ~10 floats"); returns a

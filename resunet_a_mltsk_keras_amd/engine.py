@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import accum as AC
 from . import clip as CL
 from . import schedules as SC
 from .wgrad_queue import WgradQueue, WSpec
@@ -74,6 +75,14 @@ class LossSpec:
     use_ema: bool = False                                    # E = momentum * E + (1 - momentum) * P behind every optimizer step (rua_ema_step)
     ema_momentum: float = 0.99
     ema_overwrite_frequency: Optional[int] = None            # every that many steps P takes E's values
+
+    # Gradient accumulation (accum.py holds the definition).  Off: the optimizer issues the calls it always did.
+    gradient_accumulation_steps: Optional[int] = None        # K >= 2: the optimizer applies the mean of K consecutive gradients once every K calls; the
+                                                             # step counter, the schedules and the moving average count updates (rua_accum_gate, rua_accum_step)
+
+    def accum_options(self) -> Dict[str, object]:
+        """The accumulation option as a dict (checkpoint metadata, Model.compile)."""
+        return dict(gradient_accumulation_steps=self.gradient_accumulation_steps)
 
     def sched_options(self) -> Dict[str, object]:
         """The schedule (as its get_config dict, or None) and the three EMA options as a dict (checkpoint metadata)."""
@@ -1554,6 +1563,9 @@ class Engine:
         self.E: Optional[torch.Tensor] = None               # use_ema: the moving average of P (fp32, P's layout), allocated by compile()
         self._sched = None                                  # lr_schedule: the rua_lr_schedule the rate kernel takes by value
         self._in_ema = False                                # inside ema_weights(): P and E have swapped contents
+        self.A: Optional[torch.Tensor] = None               # gradient_accumulation_steps: the accumulator (fp32, P's layout), allocated by compile()
+        self.acc_state: Optional[torch.Tensor] = None       # ... int32 [0] gradients of the current cycle in A, [1] this step's hold flag (rua_accum_gate)
+        self.micro, self._micro_dev = 0, -1                 # ... the host's mirror of acc_state[0] and what the device copy holds (as t / _t_dev)
         self.graphs: Dict[Tuple[int, bool], Graph] = {}
         self.class_w_ptr = None
         self.scalars_ptr = 0
@@ -1671,6 +1683,7 @@ class Engine:
         SC.check_ema_options(spec.use_ema, spec.ema_momentum, spec.ema_overwrite_frequency)
         if spec.lr_schedule is not None and not isinstance(spec.lr_schedule, SC.LearningRateSchedule):
             raise ValueError(f"lr_schedule {spec.lr_schedule!r}: None or a schedule of resunet_a_mltsk_keras_amd.schedules")
+        AC.check_steps(spec.gradient_accumulation_steps)
         if self._in_ema:
             raise RuntimeError("compile() inside ema_weights(): leave the block first")
         if self.loss is not None and (self.loss.optimizer != spec.optimizer):
@@ -1688,6 +1701,18 @@ class Engine:
         if spec.use_ema and self.dev is not None:
             self.E = torch.empty_like(self.P)
             self.reset_ema()
+        # gradient accumulation: a re-compile drops accumulator and counter (an open cycle is lost with the optimizer it belonged to)
+        self.A, self.acc_state = None, None
+        self.micro, self._micro_dev = 0, -1
+        if spec.gradient_accumulation_steps is not None and self.dev is not None:
+            self.A = torch.zeros_like(self.P)
+            self.acc_state = torch.zeros(4, dtype=torch.int32, device=self.dev)
+
+    def accumulation_state(self) -> Optional[Dict[str, int]]:
+        """gradient_accumulation_steps: dict(steps=K, micro=gradients of the current cycle already accumulated, 0 .. K - 1); None with the
+        option off.  The host's mirror: no device read."""
+        k = self.loss.gradient_accumulation_steps if self.loss is not None else None
+        return None if k is None else dict(steps=int(k), micro=int(self.micro))
 
     def reset_ema(self):
         """use_ema: E = P (compile(), weights from a file without an average, a broadcast): padding stays zero and the average starts sane."""
@@ -1735,7 +1760,8 @@ class Engine:
         coefficients, the skip flag, the report and the BatchNorm state's backup.  Nothing is allocated and self.clip is None with every option off."""
         self.clip = None
         self._s_backed = False
-        if not spec.clip_on() or self.dev is None:
+        # gradient accumulation takes the chunk-table route too (mode RUA_CLIP_NONE with no clip option): its optimizers honour the hold flag
+        if not (spec.clip_on() or spec.gradient_accumulation_steps is not None) or self.dev is None:
             return
         chunks, vars_, names = CL.build_chunk_table(self.params.entries, spec.decay_exclude or ())
         mode, c = CL.clip_mode(spec.clipnorm, spec.global_clipnorm, spec.clipvalue)
@@ -1750,8 +1776,9 @@ class Engine:
     def clip_report(self) -> Optional[Dict[str, float]]:
         """What the last optimizer step's finisher wrote (None with every clip / decay / skip option off): norm - that step's global gradient norm
         (grad_scale included) -, min_coef - the smallest coefficient it applied (1 when nothing was clipped; clipvalue does not show here) -, and the
-        counts since compile() of steps skipped and of steps a norm clipped.  Synchronises the device: the only host read of the whole feature."""
-        if self.clip is None:
+        counts since compile() of steps skipped and of steps a norm clipped.  Synchronises the device: the only host read of the whole feature.
+        Under gradient accumulation the four describe and count UPDATE steps (the norm is the mean gradient's); a hold step changes none."""
+        if self.clip is None or not self.loss.clip_on():      # gradient accumulation alone walks the chunk table too, but has nothing to report
             return None
         torch.cuda.synchronize()
         r = self.clip["report"].cpu().numpy()
@@ -2076,11 +2103,24 @@ class Engine:
         elif self._t_dev != self.t or self._lr_base_dev != sp.lr:
             self.lr_state.copy_(torch.tensor([float(self.t), float(sp.lr)], dtype=torch.float64))
             self._t_dev, self._lr_base_dev = self.t, sp.lr
+        k = sp.gradient_accumulation_steps
+        if k is not None:
+            # gradient accumulation: the gate of this step's optimizer launch advances the device's micro counter and decides hold / update from
+            # it; the host mirrors it the way it mirrors t, and a hold step advances neither t nor the device's step counter
+            if self._micro_dev != self.micro:
+                self.acc_state.copy_(torch.tensor([self.micro, 0, 0, 0], dtype=torch.int32))
+            hold = AC.is_hold(self.micro, k)
+            self.micro = self.micro + 1 if hold else 0
+            self._micro_dev = self.micro
+            if hold:
+                return
         self.t += 1
         self._t_dev += 1                                    # the optimizer launch of this step advances the device counter
 
     def _launch_optimizer(self, grad_scale, s):
         sp = self.loss
+        if self.A is not None:
+            return self._launch_optimizer_accum(grad_scale, s)
         if self._sched is not None:                         # the same one-thread launch, with the schedule's constants by value
             L.lib().call("rua_lr_schedule_step", self.lr_state.data_ptr(), self.lr_dev.data_ptr(), self._sched, 1 if sp.optimizer == "adam" else 0,
                          float(sp.beta_1), float(sp.beta_2), C.c_void_p(s))
@@ -2118,6 +2158,41 @@ class Engine:
             L.lib().call("rua_sgd_step_w", self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.params.n, 0.0,
                          self.lr_dev.data_ptr(), sp.momentum, grad_scale, 1, wc, C.c_void_p(s))
         self._launch_ema(wc, None, s)
+
+    def _launch_optimizer_accum(self, grad_scale, s):
+        """gradient_accumulation_steps: the optimizer tail of a micro-step, the same launches on a hold and on an update step (a captured step
+        replays either): the gate decides from the device's micro counter, rua_accum_step adds G[:n] to the accumulator (hold) or turns it into
+        the cycle's mean (update), and the chunk-table route of clip.py follows in its gated forms - rate kernel, sum of squares and finisher
+        keep every bit on a hold step; the finisher writes flag[0] = skipped, which only the BatchNorm restore reads, and flag[1] = hold or
+        skipped, which the optimizer (it then only zeroes G and rewrites the bf16 copy of the unchanged weights) and the moving average read.
+        Two launches more than the chunk-table route, four more than the flat one.  Under data parallel G is the reduced gradient, and its
+        tail - the BatchNorm state - is not accumulated."""
+        sp, ck, lib, sv = self.loss, self.clip, L.lib(), C.c_void_p(s)
+        k, adam = int(sp.gradient_accumulation_steps), 1 if sp.optimizer == "adam" else 0
+        hold = self.acc_state.data_ptr() + 4
+        flag = ck["flag"].data_ptr()
+        both = flag + 4
+        wc = self.Wf.data_ptr() if self.opt_wcopy else None
+        lib.call("rua_accum_gate", self.acc_state.data_ptr(), k, hold, sv)
+        lib.call("rua_accum_step", self.G.data_ptr(), self.A.data_ptr(), self.params.n, k, hold, sv)
+        if self._sched is not None:
+            lib.call("rua_lr_schedule_step_gated", self.lr_state.data_ptr(), self.lr_dev.data_ptr(), self._sched, adam, float(sp.beta_1), float(sp.beta_2), hold, sv)
+        else:
+            lib.call("rua_lr_step_gated", self.lr_state.data_ptr(), self.lr_dev.data_ptr(), adam, float(sp.beta_1), float(sp.beta_2), hold, sv)
+        lib.call("rua_grad_sumsq_gated", self.G.data_ptr(), ck["chunks"].data_ptr(), ck["n_chunks"], ck["partials"].data_ptr(), hold, sv)
+        lib.call("rua_clip_finish_gated", ck["partials"].data_ptr(), ck["n_chunks"], ck["vars"].data_ptr(), ck["n_vars"], ck["mode"], ck["c"], float(grad_scale),
+                 ck["skip"], ck["var_sumsq"].data_ptr(), ck["coef"].data_ptr(), flag, ck["report"].data_ptr(), hold, sv)
+        if adam:
+            lib.call("rua_adam_step_seg", self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.V1.data_ptr(), ck["chunks"].data_ptr(),
+                     ck["n_chunks"], ck["vars"].data_ptr(), ck["coef"].data_ptr(), both, self.lr_dev.data_ptr(), self.lr_state.data_ptr(),
+                     sp.beta_1, sp.beta_2, KERAS_EPS, grad_scale, ck["cv"], ck["wd"], 1, wc, sv)
+        else:
+            lib.call("rua_sgd_step_seg", self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), ck["chunks"].data_ptr(), ck["n_chunks"],
+                     ck["vars"].data_ptr(), ck["coef"].data_ptr(), both, self.lr_dev.data_ptr(), self.lr_state.data_ptr(), sp.momentum,
+                     grad_scale, ck["cv"], ck["wd"], 1, wc, sv)
+        self._launch_ema(wc, both, s)
+        if ck["s_backup"] is not None:
+            lib.call("rua_state_copy", self.S.data_ptr(), ck["s_backup"].data_ptr(), self.params.ns, flag, sv)
 
     def _launch_ema(self, wc, flag, s):
         """use_ema: the moving average right behind the optimizer kernel, inside the same capture.  The step counter (first-step copy, overwrite

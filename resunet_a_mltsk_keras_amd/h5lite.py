@@ -317,7 +317,7 @@ class _Reader:
             shape = self.space(q); q += ssz
         else:
             raise H5Error(f"attribute message version {ver}")
-        return name, self.decode(dt, shape, self.d[q:])
+        return name, self.decode(dt, shape, memoryview(self.d)[q:])      # a view: slicing the bytes copied the rest of the file per attribute
 
     # -- groups -----------------------------------------------------------------------------------------------------------
     def heap_name(self, heap_addr: int, off: int) -> str:

@@ -82,6 +82,14 @@ class _ClipOptions:
         self.use_ema, self.ema_momentum, self.ema_overwrite_frequency = bool(use_ema), float(ema_momentum), ema_overwrite_frequency
         self._model = None
 
+    def _set_accum(self, gradient_accumulation_steps):
+        """Keras 3's gradient_accumulation_steps (accum.py has the definition): None or an integer >= 2, checked as Keras checks it."""
+        from .accum import check_steps
+        self.gradient_accumulation_steps = check_steps(gradient_accumulation_steps)
+
+    def accum_options(self):
+        return dict(gradient_accumulation_steps=self.gradient_accumulation_steps)
+
     @property
     def lr_schedule(self):
         return self.lr.schedule if isinstance(self.lr, _SchedVar) else None
@@ -113,8 +121,10 @@ class _ClipOptions:
 
 class Adam(_ClipOptions):
     def __init__(self, lr=None, learning_rate=None, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, global_clipnorm=None, clipvalue=None,
-                 weight_decay=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, **_):
+                 weight_decay=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None,
+                 gradient_accumulation_steps=None, **_):
         self._set_clip(clipnorm, global_clipnorm, clipvalue, weight_decay, skip_nonfinite)
+        self._set_accum(gradient_accumulation_steps)
         self._set_ema(use_ema, ema_momentum, ema_overwrite_frequency)
         self.lr = _lr_var(learning_rate, lr, 1e-3)
         self.learning_rate = self.lr
@@ -125,8 +135,10 @@ class Adam(_ClipOptions):
 
 class SGD(_ClipOptions):
     def __init__(self, lr=None, learning_rate=None, momentum=0.0, nesterov=False, clipnorm=None, global_clipnorm=None, clipvalue=None,
-                 weight_decay=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, **_):
+                 weight_decay=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None,
+                 gradient_accumulation_steps=None, **_):
         self._set_clip(clipnorm, global_clipnorm, clipvalue, weight_decay, skip_nonfinite)
+        self._set_accum(gradient_accumulation_steps)
         self._set_ema(use_ema, ema_momentum, ema_overwrite_frequency)
         self.lr = _lr_var(learning_rate, lr, 1e-2)
         self.learning_rate = self.lr
@@ -346,7 +358,10 @@ class Model:
         changes neither weights nor moments nor BatchNorm statistics, but still advances the step counter - it costs one t of Adam's bias
         correction.  clip_report() tells how many steps were skipped and clipped.
         A schedules.LearningRateSchedule as the optimizer's learning_rate and use_ema / ema_momentum / ema_overwrite_frequency go the same
-        way (schedules.py has the definitions; stored in .h5 files, the averaged weights with them)."""
+        way (schedules.py has the definitions; stored in .h5 files, the averaged weights with them).
+        gradient_accumulation_steps=K on the optimizer (accum.py has the definition): train_on_batch changes the weights on every K-th call
+        only, with the mean of the K gradients; iterations, schedules and the average count those updates.  accumulation_state() tells where
+        the cycle stands; the .h5 file holds the option and an open cycle."""
         margin = void_margin(ignore_void)
         if optimizer is None or isinstance(optimizer, str):
             optimizer = {"adam": Adam, "sgd": SGD}[optimizer or "adam"]()
@@ -367,7 +382,8 @@ class Model:
                         beta_1=getattr(optimizer, "beta_1", 0.9), beta_2=getattr(optimizer, "beta_2", 0.999),
                         momentum=getattr(optimizer, "momentum", 0.0), ignore_void=margin,
                         **(optimizer.clip_options() if hasattr(optimizer, "clip_options") else {}),
-                        **(optimizer.sched_options() if hasattr(optimizer, "sched_options") else {}))
+                        **(optimizer.sched_options() if hasattr(optimizer, "sched_options") else {}),
+                        **(optimizer.accum_options() if hasattr(optimizer, "accum_options") else {}))
         self.engine.compile(spec)
         self._attach_optimizer()
         self._finish_compile()
@@ -394,6 +410,11 @@ class Model:
         """Engine.clip_report: dict(norm, min_coef, skipped, clipped) of the last step and the counts since compile(), or None when the optimizer
         was given no clipnorm / global_clipnorm / clipvalue / weight_decay / skip_nonfinite.  Synchronises the device."""
         return self.engine.clip_report()
+
+    def accumulation_state(self):
+        """Adam / SGD(gradient_accumulation_steps=K): dict(steps=K, micro=calls of train_on_batch since the last update, 0 .. K - 1); None with
+        the option off.  An incomplete cycle at the end of an epoch carries over into the next one."""
+        return self.engine.accumulation_state()
 
     def _attach_optimizer(self):
         """The optimizer's way back to the model: K.get_value(optimizer.lr) under a schedule reads the engine's step counter, and
@@ -566,7 +587,7 @@ class Model:
         if e.loss is not None:
             sp = e.loss
             meta["loss"] = dict(kind=sp.kind, weight=sp.weight, class_weights=sp.class_weights, optimizer=sp.optimizer, lr=sp.lr,
-                                beta_1=sp.beta_1, beta_2=sp.beta_2, momentum=sp.momentum, **sp.clip_options(), **sp.sched_options())
+                                beta_1=sp.beta_1, beta_2=sp.beta_2, momentum=sp.momentum, **sp.clip_options(), **sp.sched_options(), **sp.accum_options())
             og = root.require_group("optimizer_weights")
             og.set("rua/m:0", e.M1.cpu().numpy()); og.set("rua/v:0", e.V1.cpu().numpy())
             og.set("rua/iterations:0", np.array(e.t, np.int64))
@@ -576,6 +597,9 @@ class Model:
                     raise RuntimeError("save() inside ema_weights(): leave the block first (the file holds both sets of weights)")
                 og.set("rua/ema:0", e.E.cpu().numpy())
                 names.append(b"rua/ema:0")
+            if e.A is not None:                              # gradient accumulation: an open cycle continues bit for bit after a resume
+                og.set("rua/accum:0", e.A.cpu().numpy()); og.set("rua/accum_micro:0", np.array(e.micro, np.int64))
+                names += [b"rua/accum:0", b"rua/accum_micro:0"]
             og.attrs["weight_names"] = np.array(names)
         root.attrs["keras_version"] = b"2.4.0"
         root.attrs["backend"] = b"tensorflow"
@@ -702,6 +726,12 @@ def loss_sched_options(lo: dict) -> dict:
                 ema_momentum=float(lo.get("ema_momentum", 0.99)), ema_overwrite_frequency=None if q is None else int(q))
 
 
+def loss_accum_options(lo: dict) -> dict:
+    """gradient_accumulation_steps out of a checkpoint's `loss` metadata; a file written before the option existed has no such key: off."""
+    k = lo.get("gradient_accumulation_steps")
+    return dict(gradient_accumulation_steps=None if k is None else int(k))
+
+
 def load_model(path, compile=True, custom_objects=None, dtype=None, input_shape=None, weights="model", **_):
     """`load_model('best_model.h5')` (train_ISPRS.py:474, test_ISPRS.py:278).  Reads HDF5 only - nothing is unpickled, so a
     checkpoint cannot run code.  A file written by Model.save() restores graph, compile arguments and optimizer state; a file
@@ -739,19 +769,24 @@ def load_model(path, compile=True, custom_objects=None, dtype=None, input_shape=
         so = loss_sched_options(lo)
         ko = {k: v for k, v in co.items() if k != "decay_exclude"}
         ko.update({k: v for k, v in so.items() if k != "lr_schedule"})
+        ao = loss_accum_options(lo)
+        ko.update(ao)
         rate = so["lr_schedule"] if so["lr_schedule"] is not None else lo["lr"]
         opt = Adam(lr=rate, beta_1=lo["beta_1"], beta_2=lo["beta_2"], **ko) if lo["optimizer"] == "adam" else SGD(lr=rate, momentum=lo["momentum"], **ko)
         if co["decay_exclude"]:
             opt.exclude_from_weight_decay(var_names=co["decay_exclude"])
         m.optimizer = opt
         m.engine.compile(LossSpec(kind={k: int(v) for k, v in lo["kind"].items()}, weight=lo["weight"], class_weights=lo["class_weights"],
-                                  optimizer=lo["optimizer"], lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], momentum=lo["momentum"], **co, **so))
+                                  optimizer=lo["optimizer"], lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], momentum=lo["momentum"], **co, **so, **ao))
         m._attach_optimizer()
         og = root["optimizer_weights"]
         m.engine.M1.copy_(torch.from_numpy(np.ascontiguousarray(og["rua/m:0"]))); m.engine.V1.copy_(torch.from_numpy(np.ascontiguousarray(og["rua/v:0"])))
         m.engine.t = int(og["rua/iterations:0"])
         if m.engine.E is not None and "rua/ema:0" in og:      # a file without an average: compile() left E = P
             m.engine.E.copy_(torch.from_numpy(np.ascontiguousarray(og["rua/ema:0"])))
+        if m.engine.A is not None and "rua/accum:0" in og:    # a file without an accumulator: compile() left it zero, the cycle starts over
+            m.engine.A.copy_(torch.from_numpy(np.ascontiguousarray(og["rua/accum:0"], dtype=np.float32)))
+            m.engine.micro, m.engine._micro_dev = int(og["rua/accum_micro:0"]), -1
         m._finish_compile(restored_optimizer_state=True)
     if ema is not None:
         if ema.shape != tuple(m.engine.P.shape):

@@ -49,6 +49,11 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
   * `--ema yes --ema_momentum M --ema_overwrite_frequency N`: Keras' moving average of the weights (use_ema), updated on the GPU behind
     every optimizer step.  Each epoch's validation and the best-model criterion then run under the averaged weights; the saved file
     holds both sets (eval_scenes_ISPRS.py --weights ema evaluates the averaged one).
+  * `--grad_accum K`: Keras 3's gradient_accumulation_steps - the optimizer applies the mean of K consecutive batches' gradients once every
+    K batches, decided on the GPU (resunet_a_mltsk_keras_amd/accum.py).  `--lr_decay_steps`, `--lr_warmup_steps`, `--lr_boundaries` and
+    `--ema_overwrite_frequency` then count updates, not batches; an incomplete cycle at the end of an epoch carries over into the next.
+    The per-epoch line prints the updates taken next to the batches seen.  `--grad_accum 1` is off.  With `-cp` the option comes from
+    the checkpoint, an open cycle with it.
   * `--dtype {bf16,f32}`, `--seed`: engine options.  Launch with torch.distributed.run for multi-GPU data
     parallel (`-bs` is then the GLOBAL batch, as under MirroredStrategy).
 """
@@ -142,8 +147,8 @@ def build_parser():
                    help="leave weights, moments and BatchNorm statistics alone in a step whose gradient holds an Inf or a NaN")
     p.add_argument("--lr_schedule", choices=["constant", "cosine", "exponential", "polynomial", "piecewise", "inverse_time"], default="constant",
                    help="learning-rate schedule (Keras' formulas, computed on the GPU); -lr is the initial rate")
-    p.add_argument("--lr_decay_steps", type=int, default=None, metavar="N", help="lr_schedule: optimizer steps of one decay (every kind but piecewise)")
-    p.add_argument("--lr_warmup_steps", type=int, default=0, metavar="N", help="cosine: linear warm-up from -lr to --lr_warmup_target over N steps")
+    p.add_argument("--lr_decay_steps", type=int, default=None, metavar="N", help="lr_schedule: optimizer steps of one decay (every kind but piecewise); under --grad_accum these are updates, not batches")
+    p.add_argument("--lr_warmup_steps", type=int, default=0, metavar="N", help="cosine: linear warm-up from -lr to --lr_warmup_target over N steps (under --grad_accum: updates, not batches)")
     p.add_argument("--lr_warmup_target", type=float, default=None, metavar="LR", help="cosine: the rate the warm-up ends at and the cosine starts from")
     p.add_argument("--lr_alpha", type=float, default=0.0, metavar="A", help="cosine: the final rate as a fraction of the start of the decay")
     p.add_argument("--lr_decay_rate", type=float, default=None, metavar="R", help="exponential / inverse_time: the decay rate")
@@ -155,7 +160,10 @@ def build_parser():
     p.add_argument("--lr_values", type=str, default=None, metavar="LR0,LR1,..", help="piecewise: one rate more than boundaries; LRi holds while step <= Si")
     p.add_argument("--ema", type=str2bool, default=False, help="keep a moving average of the weights; validation and the best-model criterion use it")
     p.add_argument("--ema_momentum", type=float, default=0.99, metavar="M", help="ema: average = M * average + (1 - M) * weights after every step")
-    p.add_argument("--ema_overwrite_frequency", type=int, default=None, metavar="N", help="ema: every N steps the weights take the average's values")
+    p.add_argument("--ema_overwrite_frequency", type=int, default=None, metavar="N", help="ema: every N steps the weights take the average's values (under --grad_accum: updates, not batches)")
+    p.add_argument("--grad_accum", type=int, default=1, metavar="K",
+                   help="apply the mean of K consecutive batches' gradients once every K batches (1: off); schedules, Adam's bias correction and the "
+                        "moving average then count updates, not batches")
     return p
 
 
@@ -197,6 +205,15 @@ def optimizer_options(args):
     except ValueError as exc:
         sys.exit(f"optimizer flags: {exc}")
     return dict(kw, skip_nonfinite=bool(args.skip_nonfinite))
+
+
+def accum_options(args):
+    """--grad_accum as the optimizer's keyword (1 is off), checked before anything is built (resunet_a_mltsk_keras_amd/accum.py)."""
+    from resunet_a_mltsk_keras_amd.accum import check_steps
+    try:
+        return dict(gradient_accumulation_steps=check_steps(None if args.grad_accum == 1 else args.grad_accum))
+    except ValueError as exc:
+        sys.exit(f"--grad_accum: {exc}")
 
 
 def check_void_flags(args):
@@ -396,6 +413,7 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
         acc_tr = np.zeros(len(metrics_names)); acc_va = np.zeros(len(metrics_names))
         ld_tr.set_order(rng.permutation(len(x_tr)))
         n_tr, n_va = len(ld_tr), len(ld_va)
+        t_before = getattr(getattr(net, "engine", None), "t", None)
         for xb, yb in ld_tr:
             acc_tr += np.asarray(net.train_on_batch(x=xb, y=labels(yb), return_dict=False, **shard))
         acc_tr /= max(n_tr, 1)
@@ -423,6 +441,9 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
                 vw.scalar("Segmentation/MCC", mcc, epoch)
                 print(f"| {'Total':8s}{tm['loss']:13.5f}{vm['loss']:13.5f}{0:13d}{0:13d} |\n+{'-' * 62}+")
                 tw.scalar("Total/Loss", tm["loss"], epoch); vw.scalar("Total/Loss", vm["loss"], epoch)
+        acc = net.accumulation_state() if hasattr(net, "accumulation_state") else None
+        if acc is not None:                                     # --grad_accum: updates taken next to batches seen; an open cycle carries over
+            say(f"Gradient accumulation: {net.engine.t - t_before} updates from {n_tr} batches (K = {acc['steps']}; {acc['micro']} batches wait in the accumulator)")
         if getattr(net, "optimizer", None) is not None:
             say(f"Learning rate: {K.get_value(net.optimizer.lr):.6g}" + (" (validated under the averaged weights)" if use_ema else ""))
         rep = net.clip_report() if hasattr(net, "clip_report") else None        # None: no clip / decay / skip option is on
@@ -506,6 +527,7 @@ def main(argv=None):
     opt_kw = optimizer_options(args)
     rate, ema_kw = schedule_options(args)
     opt_kw.update(ema_kw)
+    opt_kw.update(accum_options(args))
     optm = Adam(lr=rate, beta_1=0.9, **opt_kw) if args.optimizer == "adam" else SGD(lr=rate, momentum=0.8, **opt_kw)
     if args.weight_decay and not args.decay_all:
         from resunet_a_mltsk_keras_amd.clip import DEFAULT_DECAY_EXCLUDE
