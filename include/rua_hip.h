@@ -365,6 +365,9 @@ int rua_bn_bwd_group(const rua_bn_bwd_desc* d, int n, void* stream);
 int rua_bn_bwd_group_last_grids(void);
 
 /* ---- pooling / resampling (PSPPooling model2.py:47-60; decoder model2.py:91) ---------- */
+/* The max-pool (rua_maxpool_fwd, and rua_maxpool_derive with the same results) scans its window row-major with `v > best` from -inf: the FIRST maximum wins
+ * (-0.0 and +0.0 tie), NaN never wins, and a window that holds only NaN and / or -inf yields -inf with argmax byte 0 - so rua_maxpool_bwd / _bwd_multi route
+ * the gradient of such a window to its position 0. */
 int rua_maxpool_fwd(const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, int k, int dtype, void* stream);
 int rua_maxpool_bwd(const void* dy, const uint8_t* idx, void* dx, int accumulate, int N, int H, int W, int C, int k, int dtype, void* stream);
 /* y[n,h,w,c] = sum over the k x k block (adjoint of nearest upsampling) */

@@ -262,6 +262,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const ApplyK p) {
 extern "C" int rua_bn_apply(const void* x, int nb, const float* const* scale, const float* const* shift, int relu,
                             void* const* out, int64_t M, int C, int dtype, void* stream) {
   RUA_CHECK_ARG(x && scale && shift && out && nb >= 1 && nb <= RUA_MAX_BRANCH && M > 0, "rua_bn_apply: bad arguments");
+  RUA_CHECK_ARG(dtype == RUA_F32 || dtype == RUA_BF16, "rua_bn_apply: bad dtype");
   const int vec = dtype == RUA_BF16 ? 8 : 4;
   RUA_CHECK_ARG(C % vec == 0, "rua_bn_apply: C=%d not a multiple of %d", C, vec);
   ApplyK k;
@@ -333,6 +334,7 @@ extern "C" int rua_bn_bwd_apply(int nb, const void* const* g, const float* const
                                 const float* const* coefC, const float* const* mscale, const float* const* mshift, int masked,
                                 const void* x, const void* dskip, void* dx, int accumulate, int64_t M, int C, int dtype, void* stream) {
   RUA_CHECK_ARG(nb >= 1 && nb <= RUA_MAX_BRANCH && g && coefA && coefB && coefC && x && dx && M > 0, "rua_bn_bwd_apply: bad arguments");
+  RUA_CHECK_ARG(dtype == RUA_F32 || dtype == RUA_BF16, "rua_bn_bwd_apply: bad dtype");
   const int vec = dtype == RUA_BF16 ? 8 : 4;
   RUA_CHECK_ARG(C % vec == 0, "rua_bn_bwd_apply: C=%d not a multiple of %d", C, vec);
   BwdApplyK k;

@@ -1,5 +1,5 @@
-"""What tests/test_tail_gpu.py and tests/test_elementwise_gpu.py share: device and stream handles, uploads that keep every bit, bit views
-of what comes back, and the worst ratio of an error to its bound.  A plain module (no tests, no fixtures): the test files import from it by name."""
+"""What tests/test_tail_gpu.py, tests/test_elementwise_gpu.py, tests/test_bn_gpu.py and tests/test_pool_gpu.py share: device and stream handles, uploads
+that keep every bit, bit views of what comes back, the worst ratio of an error to its bound, ulps and guarded device buffers.  A plain module (no tests, no fixtures): the test files import from it by name."""
 import ctypes as C
 
 import numpy as np
@@ -59,6 +59,35 @@ def worst_ratio(err, bound):
     err, bound = np.asarray(err, np.float64), np.asarray(bound, np.float64)
     r = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err == 0, 0.0, np.inf))
     return float(r.max())
+
+
+def ulp_of(ref, dt):
+    """One unit in the last place of the storage type (RUA_F32 / RUA_BF16) in the binade of |ref|; the subnormal spacing below the smallest normal."""
+    a = np.abs(np.asarray(ref, np.float64))
+    e = np.where(a > 0, np.frexp(a)[1] - 1, -126)
+    return np.ldexp(1.0, np.maximum(e, -126) - (7 if dt == L.RUA_BF16 else 23))
+
+
+GUARD = 256                                                  # bytes in front of and behind a guarded buffer (a multiple of 16: the data stay aligned)
+GUARD_BYTE = 0xA5
+
+
+class Guarded:
+    """A device buffer between two guard regions: `ptr` is the address of the data, get() returns the data as a numpy array of the dtype and shape
+    it was made from and asserts that no guard byte changed.  bf16 tensors travel as their uint16 bit patterns."""
+
+    def __init__(self, init, guard=GUARD):
+        init = np.ascontiguousarray(init)
+        self.dtype, self.shape, self.n, self.guard = init.dtype, init.shape, init.nbytes, guard
+        host = np.full(self.n + 2 * guard, GUARD_BYTE, np.uint8)
+        host[guard:guard + self.n] = init.view(np.uint8).reshape(-1)
+        self.buf = torch.from_numpy(host).to(dev())
+        self.ptr = self.buf.data_ptr() + guard
+
+    def get(self):
+        h, g = self.buf.cpu().numpy(), self.guard
+        assert (h[:g] == GUARD_BYTE).all() and (h[g + self.n:] == GUARD_BYTE).all(), "a guard region changed"
+        return h[g:g + self.n].view(self.dtype).reshape(self.shape).copy()
 
 
 def frozen(*arrays):
