@@ -459,6 +459,29 @@ int rua_head_dz_void(int kind, int act, const float* p, const float* y, const fl
 int rua_head_dz_multi_void(const rua_dz_head* heads, int n, const uint8_t* void_mask, void* stream);
 int rua_seg_metrics_void(const float* p, const float* y, const uint8_t* void_mask, int64_t M, int C, double* out, void* stream);
 
+/* ---- focal losses and label smoothing (Keras' CategoricalFocalCrossentropy / BinaryFocalCrossentropy and label_smoothing=; the package's
+ * losses.py holds the definitions as fp64 functions).  Two more kinds and one struct of options; the entries above and rua_dz_head are unchanged.
+ * With e = label_smoothing, g = gamma, C classes and the clip bounds 1e-7, 1 - 1e-7:
+ *   smoothing        t = y (1 - e) + e / C under a softmax (kinds 1, 2, 5), t = y (1 - e) + e / 2 per sigmoid channel (kinds 3, 6); kinds 1, 2, 3
+ *                    keep their formula with t in place of y; kinds 0 and 4 take none (RUA_ERR_ARG)
+ *   RUA_LOSS_FOCAL_CE   u_c = clip(p_c / sum_k p_k); L = - sum_c a_c t_c (1 - u_c)^g log u_c; a = class_w[C], required; act must be softmax
+ *   RUA_LOSS_FOCAL_BCE  per channel o = clip(p), bce = -(t log o + (1 - t) log(1 - o)), p_t = t p + (1 - t)(1 - p) on the unclipped p,
+ *                       l_c = w_c (1 - p_t)^g bce, w_c = t alpha + (1 - t)(1 - alpha) if class_balance else 1; L = mean_c l_c; act must be sigmoid
+ * The gradient passes a clip strictly inside it only.  Range: g = 0 or 1 <= g <= 8 (0 < g < 1 has no finite derivative at p_t = 1), 0 <= e < 1,
+ * 0 <= alpha <= 1, C <= 8; violations are RUA_ERR_ARG before any launch.  g = 0 gives factor 1 and derivative term 0 by a branch.
+ * void_mask (optional) as in the _void entries.  Kinds 0..4 with zeroed options run the kernels of the entries above: the same bytes. */
+#define RUA_LOSS_FOCAL_CE 5
+#define RUA_LOSS_FOCAL_BCE 6
+typedef struct rua_loss_opts { float gamma, label_smoothing, alpha; int32_t class_balance; } rua_loss_opts;
+/* kinds 1..6 (Tanimoto is no per-pixel loss): loss_out[0] += the sum over the valid pixels, per_pixel[M] optional */
+int rua_pixel_loss_opts(int kind, const float* p, const float* z, const float* y, const float* class_w, const uint8_t* void_mask,
+                        const rua_loss_opts* opts, int64_t M, int C, double* loss_out, float* per_pixel, void* stream);
+/* kinds 0..6 */
+int rua_head_dz_opts(int kind, int act, const float* p, const float* y, const float* coef, const float* class_w, float grad_scale,
+                     int B, int64_t HW, int C, const uint8_t* void_mask, const rua_loss_opts* opts, float* dz, void* stream);
+/* n heads of mixed kinds in ONE launch, opts[i] belongs to heads[i] */
+int rua_head_dz_multi_opts(const rua_dz_head* heads, const rua_loss_opts* opts, int n, const uint8_t* void_mask, void* stream);
+
 /* ---- optimizers on the flat parameter buffer (train_ISPRS.py:404-407) --------------------- */
 /* Keras Adam: theta -= lr_t * m / (sqrt(v) + eps); g is read as g*grad_scale and zeroed if zero_grad.
  * lr_t_dev (optional): device scalar overriding lr_t, so a captured HIP graph can be replayed every step */

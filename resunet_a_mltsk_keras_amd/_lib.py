@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("RUA_LIB_PATH") or os.path.join(HERE, "librua_hip.so")
 
 RUA_F32, RUA_BF16 = 0, 1
 RUA_MAX_SEG, RUA_MAX_BRANCH, RUA_MAX_WGRAD_GROUP, RUA_MAX_WGRAD_BATCH = 6, 4, 8, 32
-LOSS_TANIMOTO, LOSS_WCE, LOSS_CE_LOGITS, LOSS_BCE_LOGITS, LOSS_MSE = 0, 1, 2, 3, 4
+LOSS_TANIMOTO, LOSS_WCE, LOSS_CE_LOGITS, LOSS_BCE_LOGITS, LOSS_MSE, LOSS_FOCAL_CE, LOSS_FOCAL_BCE = 0, 1, 2, 3, 4, 5, 6
 ACT_NONE, ACT_SOFTMAX, ACT_SIGMOID = 0, 1, 2
 
 vp, i32, i64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
@@ -62,6 +62,11 @@ class TaniHead(C.Structure):
 class DzHead(C.Structure):
     _fields_ = [("kind", i32), ("act", i32), ("p", vp), ("y", vp), ("coef", vp), ("class_w", vp), ("grad_scale", f32), ("B", i32), ("HW", i64),
                 ("C", i32), ("pad", i32), ("dz", vp)]
+
+
+class LossOpts(C.Structure):
+    """rua_loss_opts: all zero = no option (losses.py holds the definitions)."""
+    _fields_ = [("gamma", f32), ("label_smoothing", f32), ("alpha", f32), ("class_balance", i32)]
 
 
 class BnBranch(C.Structure):
@@ -201,6 +206,9 @@ _SIGS = {
     "rua_head_dz_void": ([i32, i32, vp, vp, vp, vp, f32, i32, i64, i32, vp, vp, vp], i32),
     "rua_head_dz_multi_void": ([vp, i32, vp, vp], i32),
     "rua_seg_metrics_void": ([vp, vp, vp, i64, i32, vp, vp], i32),
+    "rua_pixel_loss_opts": ([i32, vp, vp, vp, vp, vp, C.POINTER(LossOpts), i64, i32, vp, vp, vp], i32),
+    "rua_head_dz_opts": ([i32, i32, vp, vp, vp, vp, f32, i32, i64, i32, vp, C.POINTER(LossOpts), vp, vp], i32),
+    "rua_head_dz_multi_opts": ([vp, vp, i32, vp, vp], i32),
     "rua_void_mask": ([vp, i32, i32, i32, i32, i32, vp, vp], i32),
     "rua_targets_scratch_bytes": ([i32, i32], i64),
     "rua_multitask_targets": ([vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp], i32),

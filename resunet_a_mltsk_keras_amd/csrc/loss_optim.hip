@@ -283,6 +283,40 @@ extern "C" int rua_tanimoto_ratio(const double* sums, int B, int C, double* mean
 // ---- per-pixel losses (utils.py:481-490; Keras CategoricalCrossentropy / BinaryCrossentropy /
 // MeanSquaredError as train_ISPRS.py:411-428 selects them) -----------------------------------
 #define KERAS_EPS 1e-7f
+// ---- the options of the rua_*_opts entries (include/rua_hip.h; losses.py holds the definitions) ----
+// (q^gamma, d/dq q^gamma).  gamma == 0: factor 1 and derivative 0 by a branch, never pow(0, 0) or 0 * inf; gamma == 2: the squared form; otherwise
+// gamma >= 1 (checked on the host), so q^(gamma - 1) is finite at q == 0
+__device__ __forceinline__ void focal_factor(float q, float gamma, float& f, float& df) {
+  if (gamma == 0.f) { f = 1.f; df = 0.f; }
+  else if (gamma == 2.f) { f = q * q; df = 2.f * q; }
+  else { const float r = powf(q, gamma - 1.f); f = r * q; df = gamma * r; }
+}
+__device__ __forceinline__ bool smooth_is_binary(int kind) { return kind == RUA_LOSS_BCE_LOGITS || kind == RUA_LOSS_FOCAL_BCE; }
+// binary focal, one sigmoid channel: l = w (1 - p_t)^gamma bce with o = clip(p), bce = -(t log o + (1 - t) log(1 - o)), p_t = t p + (1 - t)(1 - p) on the
+// unclipped p, w = t alpha + (1 - t)(1 - alpha) under class balancing.  (1 - p_t is held at >= 0: rounding may carry p_t an ulp past 1)
+// 1 - o is taken as clip(1 - p), the same number: 1.f - (1.f - 1e-7f) is 1.19e-7, which would move log(1 - o) at the upper bound by 0.17
+__device__ __forceinline__ float focal_bce_terms(float pc, float t, const rua_loss_opts& lo, float& f, float& df, float& w, float& o, float& om) {
+  o = fminf(fmaxf(pc, KERAS_EPS), 1.f - KERAS_EPS);
+  om = fminf(fmaxf(1.f - pc, KERAS_EPS), 1.f - KERAS_EPS);
+  const float bce = -(t * logf(o) + (1.f - t) * logf(om));
+  const float q = fmaxf(1.f - (t * pc + (1.f - t) * (1.f - pc)), 0.f);
+  focal_factor(q, lo.gamma, f, df);
+  w = lo.class_balance ? t * lo.alpha + (1.f - t) * (1.f - lo.alpha) : 1.f;
+  return bce;
+}
+__device__ __forceinline__ float focal_bce_loss(float pc, float t, const rua_loss_opts& lo) {
+  float f, df, w, o, om;
+  const float bce = focal_bce_terms(pc, t, lo, f, df, w, o, om);
+  return w * f * bce;
+}
+// dl/dp: d(1 - p_t)/dp = 1 - 2t; the clip passes bce's gradient strictly inside only
+__device__ __forceinline__ float focal_bce_dp(float pc, float t, const rua_loss_opts& lo) {
+  float f, df, w, o, om;
+  const float bce = focal_bce_terms(pc, t, lo, f, df, w, o, om);
+  const bool inside = pc >= KERAS_EPS && pc <= 1.f - KERAS_EPS;
+  const float dbce = inside ? (1.f - t) / om - t / o : 0.f;
+  return w * (df * (1.f - 2.f * t) * bce + f * dbce);
+}
 // VM: a void pixel adds nothing and its per_pixel entry is 0; the caller still divides by M, the count of ALL pixels (Keras' sample_weight rule with
 // 0 / 1 weights: grad_scale = weight / M stays a host constant)
 template <bool VM>
@@ -343,13 +377,115 @@ extern "C" int rua_pixel_loss(int kind, const float* p, const float* z, const fl
   return rua_pixel_loss_void(kind, p, z, y, class_w, nullptr, M, C, loss_out, per_pixel, stream);
 }
 
+// pixel_loss_kernel with the options: t = the smoothed label in the three cross-entropies' formulas, and the two focal kinds.  Same traversal,
+// same accumulation (fp32 per thread, block_atomic_add); C <= 8.
+template <bool VM>
+__global__ __launch_bounds__(256) void pixel_loss_opts_kernel(int kind, const float* __restrict__ p, const float* __restrict__ z,
+                                                              const float* __restrict__ y, const float* __restrict__ cw, const rua_loss_opts lo,
+                                                              long long M, int C, double* out, float* per_pixel, const uint8_t* __restrict__ vm) {
+  __shared__ float sh[4];
+  float acc = 0.f;
+  const bool smooth = lo.label_smoothing != 0.f;
+  const float sa = 1.f - lo.label_smoothing, sb = lo.label_smoothing / (smooth_is_binary(kind) ? 2.f : (float)C);
+  for (long long m = (long long)blockIdx.x * 256 + threadIdx.x; m < M; m += (long long)gridDim.x * 256) {
+    float l = 0.f;
+    if constexpr (VM) {
+      if (vm[m]) { if (per_pixel) per_pixel[m] = 0.f; continue; }
+    }
+    float t[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) t[c] = c < C ? y[m * C + c] : 0.f;
+    if (smooth) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) t[c] = c < C ? fmaf(t[c], sa, sb) : 0.f;
+    }
+    if (kind == RUA_LOSS_WCE || kind == RUA_LOSS_FOCAL_CE) {
+      float S = 0.f;
+      for (int c = 0; c < C; ++c) S += p[m * C + c];
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        if (c < C) {
+          const float u = fminf(fmaxf(p[m * C + c] / S, KERAS_EPS), 1.f - KERAS_EPS);
+          if (kind == RUA_LOSS_WCE) l -= t[c] * logf(u) * cw[c];
+          else {
+            float f, df;
+            focal_factor(1.f - u, lo.gamma, f, df);
+            l -= t[c] * logf(u) * cw[c] * f;
+          }
+        }
+      }
+    } else if (kind == RUA_LOSS_CE_LOGITS) {
+      float mx = -INFINITY;
+      for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[m * C + c]);
+      float s = 0.f;
+      for (int c = 0; c < C; ++c) s += expf(z[m * C + c] - mx);
+      const float lse = mx + logf(s);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) if (c < C) l -= t[c] * (z[m * C + c] - lse);
+    } else if (kind == RUA_LOSS_BCE_LOGITS) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        if (c < C) {
+          const float zz = z[m * C + c];
+          l += fmaxf(zz, 0.f) - zz * t[c] + log1pf(expf(-fabsf(zz)));
+        }
+      }
+      l /= C;
+    } else {      // RUA_LOSS_FOCAL_BCE (MSE takes no option: the entry sends it to pixel_loss_kernel)
+#pragma unroll
+      for (int c = 0; c < 8; ++c) if (c < C) l += focal_bce_loss(p[m * C + c], t[c], lo);
+      l /= C;
+    }
+    if (per_pixel) per_pixel[m] = l;
+    acc += l;
+  }
+  block_atomic_add(out, acc, sh, 0);
+}
+
+// The range of the options (include/rua_hip.h), checked before any launch; why: the violated rule
+static const char* loss_opts_error(int kind, const rua_loss_opts& o) {
+  if (!(o.label_smoothing >= 0.f && o.label_smoothing < 1.f)) return "label_smoothing must be in [0, 1)";
+  if (o.label_smoothing != 0.f && (kind == RUA_LOSS_TANIMOTO || kind == RUA_LOSS_MSE)) return "Tanimoto and MSE take no label smoothing";
+  if (kind == RUA_LOSS_FOCAL_CE || kind == RUA_LOSS_FOCAL_BCE) {
+    if (!(o.gamma == 0.f || (o.gamma >= 1.f && o.gamma <= 8.f))) return "gamma must be 0 or in [1, 8]";
+  }
+  if (kind == RUA_LOSS_FOCAL_BCE) {
+    if (o.class_balance != 0 && o.class_balance != 1) return "class_balance must be 0 or 1";
+    if (o.class_balance && !(o.alpha >= 0.f && o.alpha <= 1.f)) return "alpha must be in [0, 1]";
+  }
+  return nullptr;
+}
+static bool loss_needs_opts(int kind, const rua_loss_opts& o) { return kind > RUA_LOSS_MSE || o.label_smoothing != 0.f; }
+
+extern "C" int rua_pixel_loss_opts(int kind, const float* p, const float* z, const float* y, const float* class_w, const uint8_t* void_mask,
+                                   const rua_loss_opts* opts, int64_t M, int C, double* loss_out, float* per_pixel, void* stream) {
+  RUA_CHECK_ARG(opts, "rua_pixel_loss_opts: null options");
+  RUA_CHECK_ARG(kind >= RUA_LOSS_WCE && kind <= RUA_LOSS_FOCAL_BCE, "rua_pixel_loss_opts: kind %d is not a per-pixel loss", kind);
+  const char* why = loss_opts_error(kind, *opts);
+  RUA_CHECK_ARG(!why, "rua_pixel_loss_opts: kind %d: %s", kind, why);
+  if (!loss_needs_opts(kind, *opts))                      // kinds 1..4 with nothing set: the kernel, and so the bytes, of rua_pixel_loss_void
+    return rua_pixel_loss_void(kind, p, z, y, class_w, void_mask, M, C, loss_out, per_pixel, stream);
+  RUA_CHECK_ARG(p && y && loss_out && M > 0, "rua_pixel_loss_opts: bad arguments");
+  RUA_CHECK_ARG(C >= 1 && C <= 8, "rua_pixel_loss_opts: C=%d must be in 1..8", C);
+  RUA_CHECK_ARG((kind != RUA_LOSS_WCE && kind != RUA_LOSS_FOCAL_CE) || class_w, "rua_pixel_loss_opts: weighted and focal CE need the per-class vector");
+  RUA_CHECK_ARG((kind != RUA_LOSS_CE_LOGITS && kind != RUA_LOSS_BCE_LOGITS) || z, "rua_pixel_loss_opts: logits needed");
+  int64_t g = (M + 255) / 256; if (g > 1024) g = 1024;
+  if (void_mask) hipLaunchKernelGGL(pixel_loss_opts_kernel<true>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, kind, p, z, y, class_w, *opts, (long long)M, C, loss_out, per_pixel, void_mask);
+  else hipLaunchKernelGGL(pixel_loss_opts_kernel<false>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, kind, p, z, y, class_w, *opts, (long long)M, C, loss_out, per_pixel, void_mask);
+  RUA_LAUNCH_CHECK("rua_pixel_loss_opts");
+  return RUA_OK;
+}
+
 // d(total loss)/d(logits), one thread per pixel
 // CT: the class count as a template constant (6, 3; 0: runtime, <= 8) - with a runtime C every `c < C` became a branch around one scalar access
 // VM: dz is +0.0f at a void pixel (written, not skipped: rua_head_bwd_sums reads every element); p and y are not read there
-template <int CT, bool VM>
+// OP: the rua_*_opts entries - label smoothing on the cross-entropies and the two focal kinds (focal_factor above); the instantiations without it
+// are the code they were
+template <int CT, bool VM, bool OP = false>
 __device__ __forceinline__ void head_dz_body(int kind, int act, const float* __restrict__ p, const float* __restrict__ y,
                                              const float* __restrict__ coef, const float* __restrict__ cw, float gs,
-                                             long long HW, int C_rt, float* dz, const uint8_t* __restrict__ vm) {
+                                             long long HW, int C_rt, float* dz, const uint8_t* __restrict__ vm,
+                                             const rua_loss_opts lo = rua_loss_opts{0.f, 0.f, 0.f, 0}) {
   const int C = CT > 0 ? CT : C_rt;
   auto load_row = [&](const float* src, long long m, float* v) {
     if constexpr (CT == 6) {                              // 24-byte rows: three 8-byte accesses
@@ -382,6 +518,13 @@ __device__ __forceinline__ void head_dz_body(int kind, int act, const float* __r
       if (vm[m]) { store_row(m, o); continue; }
     }
     load_row(p, m, pv); load_row(y, m, yv);
+    if constexpr (OP) {
+      if (lo.label_smoothing != 0.f) {                    // t = y (1 - e) + e / K; K = C under a softmax, 2 per sigmoid channel (a branch: e == 0 leaves y's bytes)
+        const float sa = 1.f - lo.label_smoothing, sb = lo.label_smoothing / (smooth_is_binary(kind) ? 2.f : (float)C);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) yv[c] = c < C ? fmaf(yv[c], sa, sb) : 0.f;
+      }
+    }
     if (kind == RUA_LOSS_CE_LOGITS) {
       float sy = 0.f;
 #pragma unroll
@@ -397,7 +540,31 @@ __device__ __forceinline__ void head_dz_body(int kind, int act, const float* __r
       store_row(m, o);
       continue;
     }
-    if (kind == RUA_LOSS_TANIMOTO) {
+    if (OP && kind == RUA_LOSS_FOCAL_CE) {
+      // L = - sum_c a_c t_c (1 - u_c)^gamma log u_c: dL/du_c = -a_c t_c [(1 - u)^gamma / u - gamma (1 - u)^(gamma - 1) log u] inside the clip, 0 outside;
+      // gamma == 0 is weighted CE's line below, byte for byte
+      float S = 0.f;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) S += pv[c];
+      float h[8], hu = 0.f;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        h[c] = 0.f;
+        if (c < C) {
+          const float u = pv[c] / S;
+          const bool inside = u >= KERAS_EPS && u <= 1.f - KERAS_EPS;
+          float f, df;
+          focal_factor(1.f - u, lo.gamma, f, df);
+          h[c] = inside ? -yv[c] * cw[c] * (f - df * u * logf(u)) / u : 0.f;
+          hu = fmaf(h[c], u, hu);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 8; ++c) g[c] = (h[c] - hu) / S * gs;
+    } else if (OP && kind == RUA_LOSS_FOCAL_BCE) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) if (c < C) g[c] = focal_bce_dp(pv[c], yv[c], lo) * gs / C;
+    } else if (kind == RUA_LOSS_TANIMOTO) {
 #pragma unroll
       for (int c = 0; c < 8; ++c) if (c < C) { const float* k = coef + ((size_t)n * C + c) * 3; g[c] = fmaf(k[1], pv[c], fmaf(k[2], yv[c], k[0])); }
     } else if (kind == RUA_LOSS_WCE) {
@@ -508,6 +675,85 @@ extern "C" int rua_head_dz_void(int kind, int act, const float* p, const float* 
 extern "C" int rua_head_dz(int kind, int act, const float* p, const float* y, const float* coef, const float* class_w,
                            float grad_scale, int B, int64_t HW, int C, float* dz, void* stream) {
   return rua_head_dz_void(kind, act, p, y, coef, class_w, grad_scale, B, HW, C, nullptr, dz, stream);
+}
+
+// ---- the same two launches with rua_loss_opts: all seven kinds.  Same grids; a call in which no head has an option set or a new kind goes to the
+// kernels above
+template <bool VM>
+__global__ __launch_bounds__(256) void head_dz_opts_kernel(int kind, int act, const float* __restrict__ p, const float* __restrict__ y,
+                                                           const float* __restrict__ coef, const float* __restrict__ cw, float gs,
+                                                           long long HW, int C, float* dz, const uint8_t* __restrict__ vm, const rua_loss_opts lo) {
+  if (C == 6) head_dz_body<6, VM, true>(kind, act, p, y, coef, cw, gs, HW, C, dz, vm, lo);
+  else if (C == 3) head_dz_body<3, VM, true>(kind, act, p, y, coef, cw, gs, HW, C, dz, vm, lo);
+  else head_dz_body<0, VM, true>(kind, act, p, y, coef, cw, gs, HW, C, dz, vm, lo);
+}
+struct DzMultiOpts { rua_dz_head h[RUA_MAX_HEADS]; rua_loss_opts o[RUA_MAX_HEADS]; };
+template <bool VM>
+__global__ __launch_bounds__(256) void head_dz_multi_opts_kernel(const DzMultiOpts a, const uint8_t* __restrict__ vm) {
+  const rua_dz_head& h = a.h[blockIdx.z];
+  const rua_loss_opts lo = a.o[blockIdx.z];
+  if ((int)blockIdx.y >= h.B) return;
+  if (h.C == 6) head_dz_body<6, VM, true>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, h.grad_scale, (long long)h.HW, h.C, h.dz, vm, lo);
+  else if (h.C == 3) head_dz_body<3, VM, true>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, h.grad_scale, (long long)h.HW, h.C, h.dz, vm, lo);
+  else head_dz_body<0, VM, true>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, h.grad_scale, (long long)h.HW, h.C, h.dz, vm, lo);
+}
+// what a head of the opts entries must satisfy beyond rua_head_dz's own rules; NULL: fine
+static const char* dz_opts_error(int kind, int act, const float* class_w, const rua_loss_opts& o) {
+  if (kind == RUA_LOSS_FOCAL_CE && act != RUA_ACT_SOFTMAX) return "focal CE needs a softmax head";
+  if (kind == RUA_LOSS_FOCAL_BCE && act != RUA_ACT_SIGMOID) return "binary focal needs a sigmoid head";
+  if (kind == RUA_LOSS_FOCAL_CE && !class_w) return "focal CE needs the per-class alpha vector (class_w)";
+  return loss_opts_error(kind, o);
+}
+
+extern "C" int rua_head_dz_multi_opts(const rua_dz_head* heads, const rua_loss_opts* opts, int n, const uint8_t* void_mask, void* stream) {
+  RUA_CHECK_ARG(heads && opts && n >= 1 && n <= RUA_MAX_HEADS, "rua_head_dz_multi_opts: 1..%d heads, each with its options", RUA_MAX_HEADS);
+  DzMultiOpts a;
+  int64_t g = 1; int Bm = 1;
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    const rua_dz_head& h = heads[i];
+    RUA_CHECK_ARG(h.p && h.y && h.dz && h.B > 0 && h.B <= 65535 && h.HW > 0 && h.C >= 1 && h.C <= 8 && h.kind >= 0 && h.kind <= RUA_LOSS_FOCAL_BCE && h.act >= 0 && h.act <= 2,
+                  "rua_head_dz_multi_opts: head %d: bad arguments", i);
+    RUA_CHECK_ARG(h.kind != RUA_LOSS_TANIMOTO || h.coef, "rua_head_dz_multi_opts: Tanimoto needs coefficients");
+    RUA_CHECK_ARG(h.kind != RUA_LOSS_WCE || h.class_w, "rua_head_dz_multi_opts: weighted CE needs class weights");
+    const char* why = dz_opts_error(h.kind, h.act, h.class_w, opts[i]);
+    RUA_CHECK_ARG(!why, "rua_head_dz_multi_opts: head %d: %s", i, why);
+    RUA_CHECK_ARG(!void_mask || (h.B == heads[0].B && h.HW == heads[0].HW), "rua_head_dz_multi_opts: head %d: B %d, HW %lld differ from head 0's", i, h.B, (long long)h.HW);
+    a.h[i] = h; a.o[i] = opts[i];
+    any = any || loss_needs_opts(h.kind, opts[i]);
+    const int64_t gi = (h.HW + 255) / 256; if (gi > g) g = gi;
+    if (h.B > Bm) Bm = h.B;
+  }
+  if (!any) return rua_head_dz_multi_void(heads, n, void_mask, stream);
+  const int64_t cap = 4096 / ((int64_t)Bm * n) > 0 ? 4096 / ((int64_t)Bm * n) : 1;
+  if (g > cap) g = cap;
+  if (void_mask) hipLaunchKernelGGL(head_dz_multi_opts_kernel<true>, dim3((int)g, Bm, n), dim3(256), 0, (hipStream_t)stream, a, void_mask);
+  else hipLaunchKernelGGL(head_dz_multi_opts_kernel<false>, dim3((int)g, Bm, n), dim3(256), 0, (hipStream_t)stream, a, void_mask);
+  RUA_LAUNCH_CHECK("rua_head_dz_multi_opts");
+  return RUA_OK;
+}
+
+extern "C" int rua_head_dz_opts(int kind, int act, const float* p, const float* y, const float* coef, const float* class_w, float grad_scale,
+                                int B, int64_t HW, int C, const uint8_t* void_mask, const rua_loss_opts* opts, float* dz, void* stream) {
+  RUA_CHECK_ARG(opts, "rua_head_dz_opts: null options");
+  RUA_CHECK_ARG(p && y && dz && B > 0 && HW > 0, "rua_head_dz_opts: bad arguments");
+  RUA_CHECK_ARG(C >= 1 && C <= 8, "rua_head_dz_opts: C=%d must be in 1..8", C);
+  RUA_CHECK_ARG(kind >= 0 && kind <= RUA_LOSS_FOCAL_BCE && act >= 0 && act <= 2, "rua_head_dz_opts: bad kind/act");
+  RUA_CHECK_ARG(kind != RUA_LOSS_TANIMOTO || coef, "rua_head_dz_opts: Tanimoto needs coefficients");
+  RUA_CHECK_ARG(kind != RUA_LOSS_WCE || class_w, "rua_head_dz_opts: weighted CE needs class weights");
+  const char* why = dz_opts_error(kind, act, class_w, *opts);
+  RUA_CHECK_ARG(!why, "rua_head_dz_opts: kind %d: %s", kind, why);
+  RUA_CHECK_ARG(B <= 65535, "rua_head_dz_opts: B=%d too large", B);
+  if (!loss_needs_opts(kind, *opts)) return rua_head_dz_void(kind, act, p, y, coef, class_w, grad_scale, B, HW, C, void_mask, dz, stream);
+  int64_t g = (HW + 255) / 256;
+  const int64_t cap = 4096 / B > 0 ? 4096 / B : 1;
+  if (g > cap) g = cap;
+  if (void_mask) hipLaunchKernelGGL(head_dz_opts_kernel<true>, dim3((int)g, B), dim3(256), 0, (hipStream_t)stream, kind, act, p, y, coef, class_w, grad_scale,
+                                    (long long)HW, C, dz, void_mask, *opts);
+  else hipLaunchKernelGGL(head_dz_opts_kernel<false>, dim3((int)g, B), dim3(256), 0, (hipStream_t)stream, kind, act, p, y, coef, class_w, grad_scale,
+                          (long long)HW, C, dz, void_mask, *opts);
+  RUA_LAUNCH_CHECK("rua_head_dz_opts");
+  return RUA_OK;
 }
 
 // accuracy + TP/FP/TN/FN (Keras 'accuracy' = categorical accuracy; confusion counts at .5)

@@ -22,6 +22,7 @@ import torch
 from . import _lib as L
 from . import accum as AC
 from . import clip as CL
+from . import losses as LS
 from . import schedules as SC
 from .wgrad_queue import WgradQueue, WSpec
 from .scenes import (BLEND_MODES, MAP_HEADS, AffineSceneBatch, SceneBatch, blend_table, check_blend_budget, check_photo_table, check_radius,
@@ -79,6 +80,25 @@ class LossSpec:
     # Gradient accumulation (accum.py holds the definition).  Off: the optimizer issues the calls it always did.
     gradient_accumulation_steps: Optional[int] = None        # K >= 2: the optimizer applies the mean of K consecutive gradients once every K calls; the
                                                              # step counter, the schedules and the moving average count updates (rua_accum_gate, rua_accum_step)
+
+    # Focal losses and label smoothing (losses.py holds the definitions), by head.  A head that is in none of them issues the calls it always did.
+    focal_gamma: Dict[str, float] = field(default_factory=dict)       # heads of kind LOSS_FOCAL_CE / LOSS_FOCAL_BCE; focal CE's per-class alpha is class_weights
+    focal_alpha: Dict[str, float] = field(default_factory=dict)       # binary focal: the scalar alpha of class balancing
+    class_balance: Dict[str, bool] = field(default_factory=dict)      # binary focal: apply_class_balancing
+    label_smoothing: Dict[str, float] = field(default_factory=dict)   # the three cross-entropies and the two focal kinds
+
+    def loss_options(self) -> Dict[str, object]:
+        """The four per-head dicts (checkpoint metadata); a spec without them gives {}: its file carries none."""
+        d = dict(focal_gamma=dict(self.focal_gamma), focal_alpha=dict(self.focal_alpha), class_balance=dict(self.class_balance),
+                 label_smoothing=dict(self.label_smoothing))
+        return {k: v for k, v in d.items() if v}
+
+    def head_opts(self, head: str):
+        """rua_loss_opts of a head whose kind is new or whose label_smoothing > 0; None: the head takes the entries without options."""
+        kind, e = self.kind[head], float(self.label_smoothing.get(head, 0.0))
+        if kind not in LS.FOCAL_KINDS and e == 0.0:
+            return None
+        return LS.to_struct(self.focal_gamma.get(head, 0.0), e, self.focal_alpha.get(head), self.class_balance.get(head, False))
 
     def accum_options(self) -> Dict[str, object]:
         """The accumulation option as a dict (checkpoint metadata, Model.compile)."""
@@ -1342,6 +1362,7 @@ class Graph:
         M = B * HW
         slot = self.e.scalars_ptr + h["slot"] * 8
         coef = None
+        opts = sp.head_opts(h["name"])
         if kind == L.LOSS_TANIMOTO:
             coef = self.alloc((B * Cc * 3,), torch.float32, zero=True)
             LP.keep.append(coef)
@@ -1360,7 +1381,10 @@ class Graph:
                 LP.add("rua_tanimoto_finalize_rep", sums, h.get("sums_rep", 1), B, HW, Cc, wgt / B, slot, coef.data_ptr(), None)
             h["norm"] = 1.0
         else:
-            if self.void_ptr is not None:                   # the sum over the valid pixels, still divided by M (Keras' sample_weight rule with 0 / 1 weights)
+            if opts is not None:                            # a focal kind or label smoothing: the entry with options (mask optional)
+                LP.keep.append(opts)
+                LP.add("rua_pixel_loss_opts", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, self.void_ptr, C.byref(opts), M, Cc, slot, None)
+            elif self.void_ptr is not None:                 # the sum over the valid pixels, still divided by M (Keras' sample_weight rule with 0 / 1 weights)
                 LP.add("rua_pixel_loss_void", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, self.void_ptr, M, Cc, slot, None)
             else:
                 LP.add("rua_pixel_loss", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, M, Cc, slot, None)
@@ -1375,6 +1399,7 @@ class Graph:
             dh.kind, dh.act, dh.p, dh.y, dh.coef, dh.class_w = kind, h["act"], h["p"].ptr, h["y"].ptr, coef.data_ptr() if coef is not None else None, self.e.class_w_ptr
             dh.grad_scale, dh.B, dh.HW, dh.C, dh.dz = gs, B, HW, Cc, dz.ptr
             self._dz_multi.append(dh)
+            self._dz_multi_opts.append(opts)
 
         def back():
             Bp = self.bwd
@@ -1382,11 +1407,19 @@ class Graph:
                 if not self._dz_emitted:                    # the first backward step of the loss section: d(loss)/d(logits) of ALL heads in one launch
                     arr = (L.DzHead * len(self._dz_multi))(*self._dz_multi)
                     Bp.keep.append(arr)
-                    if self.void_ptr is not None:
+                    if any(o is not None for o in self._dz_multi_opts):      # still one launch: every head with its options, zeroed where it has none
+                        oarr = (L.LossOpts * len(self._dz_multi))(*[o if o is not None else L.LossOpts() for o in self._dz_multi_opts])
+                        Bp.keep.append(oarr)
+                        Bp.add("rua_head_dz_multi_opts", arr, oarr, len(self._dz_multi), self.void_ptr)
+                    elif self.void_ptr is not None:
                         Bp.add("rua_head_dz_multi_void", arr, len(self._dz_multi), self.void_ptr)
                     else:
                         Bp.add("rua_head_dz_multi", arr, len(self._dz_multi))
                     self._dz_emitted = True
+            elif opts is not None:
+                Bp.keep.append(opts)
+                Bp.add("rua_head_dz_opts", kind, h["act"], h["p"].ptr, h["y"].ptr, coef.data_ptr() if coef is not None else None,
+                       self.e.class_w_ptr, gs, B, HW, Cc, self.void_ptr, C.byref(opts), dz.ptr)
             elif self.void_ptr is not None:
                 Bp.add("rua_head_dz_void", kind, h["act"], h["p"].ptr, h["y"].ptr, coef.data_ptr() if coef is not None else None,
                        self.e.class_w_ptr, gs, B, HW, Cc, self.void_ptr, dz.ptr)
@@ -1502,7 +1535,7 @@ class Graph:
         """Loss / metric launches and (training) the whole backward plan, in reverse creation order."""
         # multitask: the heads' Tanimoto finalisations and their d(loss)/d(logits) as one launch each (rua_tanimoto_finalize_multi, rua_head_dz_multi)
         self.multi_head = len(self.heads) > 1 and self.e.multi_head
-        self._tani_multi, self._dz_multi, self._dz_emitted = [], [], False
+        self._tani_multi, self._dz_multi, self._dz_multi_opts, self._dz_emitted = [], [], [], False
         for h in self.heads:
             self.cur_tag = self.loss_plan.scope = "loss_" + h["name"]
             self.head_loss(h)
@@ -1684,6 +1717,7 @@ class Engine:
         if spec.lr_schedule is not None and not isinstance(spec.lr_schedule, SC.LearningRateSchedule):
             raise ValueError(f"lr_schedule {spec.lr_schedule!r}: None or a schedule of resunet_a_mltsk_keras_amd.schedules")
         AC.check_steps(spec.gradient_accumulation_steps)
+        self._check_loss_options(spec)
         if self._in_ema:
             raise RuntimeError("compile() inside ema_weights(): leave the block first")
         if self.loss is not None and (self.loss.optimizer != spec.optimizer):
@@ -1707,6 +1741,26 @@ class Engine:
         if spec.gradient_accumulation_steps is not None and self.dev is not None:
             self.A = torch.zeros_like(self.P)
             self.acc_state = torch.zeros(4, dtype=torch.int32, device=self.dev)
+
+    def _check_loss_options(self, spec: LossSpec):
+        """The focal kinds and the per-head options against the heads (activation, channels) and losses.py's range: ValueError before any launch."""
+        acts = dict(seg=L.ACT_SOFTMAX, bound=L.ACT_SIGMOID, dist=L.ACT_SOFTMAX, color=L.ACT_SIGMOID)
+        for name in LS.OPTION_KEYS:
+            for h in getattr(spec, name):
+                if h not in spec.kind:
+                    raise ValueError(f"{name}: '{h}' is not a head of this model ({', '.join(spec.kind)})")
+        for h, kind in spec.kind.items():
+            if kind == L.LOSS_FOCAL_CE and acts[h] != L.ACT_SOFTMAX:
+                raise ValueError(f"{h}: categorical focal cross-entropy needs a softmax head")
+            if kind == L.LOSS_FOCAL_BCE and acts[h] != L.ACT_SIGMOID:
+                raise ValueError(f"{h}: binary focal cross-entropy needs a sigmoid head")
+            if kind not in LS.FOCAL_KINDS and (h in spec.focal_gamma or h in spec.focal_alpha or h in spec.class_balance):
+                raise ValueError(f"{h}: focal_gamma / focal_alpha / class_balance belong to the focal losses")
+            if kind == L.LOSS_FOCAL_CE and spec.class_weights is None:
+                raise ValueError(f"{h}: categorical focal cross-entropy needs its per-class alpha (class_weights)")
+            nc = 3 if h == "color" else self.cfg.num_classes
+            LS.check_options(kind, nc, spec.focal_gamma.get(h, 0.0), spec.class_weights if kind == L.LOSS_FOCAL_CE else spec.focal_alpha.get(h, 0.0),
+                             spec.class_balance.get(h, False), spec.label_smoothing.get(h, 0.0), what=h)
 
     def accumulation_state(self) -> Optional[Dict[str, int]]:
         """gradient_accumulation_steps: dict(steps=K, micro=gradients of the current cycle already accumulated, 0 .. K - 1); None with the

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import losses as LS
 from .engine import HEADS, Engine, LossSpec, ModelConfig
 from .scenes import SceneBatch
 
@@ -221,8 +222,9 @@ class WeightedCategoricalCrossentropy:
     kind = L.LOSS_WCE
     __name__ = "loss"
 
-    def __init__(self, weights):
+    def __init__(self, weights, label_smoothing=0.0):
         self.weights = [float(w) for w in np.asarray(weights).reshape(-1)]
+        self.label_smoothing = float(label_smoothing)
 
     def __call__(self, y_true, y_pred):
         y_true, y_pred = np.asarray(y_true, np.float32), np.asarray(y_pred, np.float32)
@@ -235,20 +237,84 @@ class WeightedCategoricalCrossentropy:
         p, y, w = _dev_f32(y_pred), _dev_f32(y_true), _dev_f32(self.weights + [0.0] * 8)
         out = torch.zeros(1, dtype=torch.float64, device="cuda")
         per = torch.zeros(M, dtype=torch.float32, device="cuda")
-        lib.call("rua_pixel_loss", L.LOSS_WCE, p.data_ptr(), None, y.data_ptr(), w.data_ptr(), M, Cc, out.data_ptr(), per.data_ptr(), s)
+        if self.label_smoothing:
+            LS.check_options(self.kind, Cc, label_smoothing=self.label_smoothing, what="weighted_categorical_crossentropy")
+            lib.call("rua_pixel_loss_opts", L.LOSS_WCE, p.data_ptr(), None, y.data_ptr(), w.data_ptr(), None, C.byref(LS.to_struct(0.0, self.label_smoothing)),
+                     M, Cc, out.data_ptr(), per.data_ptr(), s)
+        else:
+            lib.call("rua_pixel_loss", L.LOSS_WCE, p.data_ptr(), None, y.data_ptr(), w.data_ptr(), M, Cc, out.data_ptr(), per.data_ptr(), s)
         return per.cpu().numpy().reshape(y_true.shape[:-1])
 
 
-def weighted_categorical_crossentropy(weights):
-    return WeightedCategoricalCrossentropy(weights)
+def weighted_categorical_crossentropy(weights, label_smoothing=0.0):
+    return WeightedCategoricalCrossentropy(weights, label_smoothing=label_smoothing)
 
 
 class CategoricalCrossentropy:      # tf.keras.losses.* as train_ISPRS.py:414-416,427-428 instantiates them
     kind = L.LOSS_CE_LOGITS
 
+    def __init__(self, label_smoothing=0.0):
+        self.label_smoothing = float(label_smoothing)
+
 
 class BinaryCrossentropy:
     kind = L.LOSS_BCE_LOGITS
+
+    def __init__(self, label_smoothing=0.0):
+        self.label_smoothing = float(label_smoothing)
+
+
+def _focal_map(kind, y_true, y_pred, class_w, opts):
+    """The (B,H,W) map of a focal loss from the GPU (rua_pixel_loss_opts)."""
+    y_true, y_pred = np.asarray(y_true, np.float32), np.asarray(y_pred, np.float32)
+    if y_true.shape != y_pred.shape:
+        raise ValueError(f"y_true {y_true.shape} and y_pred {y_pred.shape} differ")
+    Cc = y_true.shape[-1]
+    M = int(np.prod(y_true.shape[:-1]))
+    lib = L.lib()
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p, y = _dev_f32(y_pred), _dev_f32(y_true)
+    w = _dev_f32(list(class_w) + [0.0] * 8) if class_w is not None else None
+    out = torch.zeros(1, dtype=torch.float64, device="cuda")
+    per = torch.zeros(M, dtype=torch.float32, device="cuda")
+    lib.call("rua_pixel_loss_opts", kind, p.data_ptr(), None, y.data_ptr(), w.data_ptr() if w is not None else None, None, C.byref(opts), M, Cc,
+             out.data_ptr(), per.data_ptr(), s)
+    return per.cpu().numpy().reshape(y_true.shape[:-1])
+
+
+class CategoricalFocalCrossentropy:
+    """Keras' CategoricalFocalCrossentropy on a softmax head (losses.host_categorical_focal is the definition).  alpha: Keras' scalar, or - this
+    package's extension - one value per class.  Calling it gives the (B,H,W) map."""
+    kind = L.LOSS_FOCAL_CE
+    __name__ = "loss"
+
+    def __init__(self, alpha=0.25, gamma=2.0, label_smoothing=0.0):
+        a = np.asarray(alpha, np.float64).reshape(-1)
+        self.alpha = float(a[0]) if a.size == 1 and np.ndim(alpha) == 0 else [float(v) for v in a]
+        self.gamma, self.label_smoothing = float(gamma), float(label_smoothing)
+
+    def alpha_vector(self, num_classes):
+        return [self.alpha] * num_classes if isinstance(self.alpha, float) else list(self.alpha)
+
+    def __call__(self, y_true, y_pred):
+        Cc = np.shape(y_true)[-1]
+        a = self.alpha_vector(Cc)
+        LS.check_options(self.kind, Cc, self.gamma, a, False, self.label_smoothing, what="CategoricalFocalCrossentropy")
+        return _focal_map(self.kind, y_true, y_pred, a, LS.to_struct(self.gamma, self.label_smoothing))
+
+
+class BinaryFocalCrossentropy:
+    """Keras' BinaryFocalCrossentropy on a sigmoid head (losses.host_binary_focal is the definition).  Calling it gives the (B,H,W) map."""
+    kind = L.LOSS_FOCAL_BCE
+    __name__ = "loss"
+
+    def __init__(self, apply_class_balancing=False, alpha=0.25, gamma=2.0, label_smoothing=0.0):
+        self.apply_class_balancing, self.alpha = bool(apply_class_balancing), float(alpha)
+        self.gamma, self.label_smoothing = float(gamma), float(label_smoothing)
+
+    def __call__(self, y_true, y_pred):
+        LS.check_options(self.kind, np.shape(y_true)[-1], self.gamma, self.alpha, self.apply_class_balancing, self.label_smoothing, what="BinaryFocalCrossentropy")
+        return _focal_map(self.kind, y_true, y_pred, None, LS.to_struct(self.gamma, self.label_smoothing, self.alpha, self.apply_class_balancing))
 
 
 class MeanSquaredError:
@@ -256,10 +322,19 @@ class MeanSquaredError:
 
 
 _LOSS_NAMES = {"categorical_crossentropy": L.LOSS_CE_LOGITS, "binary_crossentropy": L.LOSS_BCE_LOGITS,
-               "mse": L.LOSS_MSE, "mean_squared_error": L.LOSS_MSE, "tanimoto": L.LOSS_TANIMOTO}
+               "mse": L.LOSS_MSE, "mean_squared_error": L.LOSS_MSE, "tanimoto": L.LOSS_TANIMOTO,
+               "categorical_focal_crossentropy": L.LOSS_FOCAL_CE, "binary_focal_crossentropy": L.LOSS_FOCAL_BCE}
+
+
+def _named_loss(loss):
+    """A focal loss given by its Keras name: the object with Keras' defaults.  Other names and objects pass."""
+    if isinstance(loss, str) and _LOSS_NAMES.get(loss) in LS.FOCAL_KINDS:
+        return CategoricalFocalCrossentropy() if _LOSS_NAMES[loss] == L.LOSS_FOCAL_CE else BinaryFocalCrossentropy()
+    return loss
 
 
 def _loss_kind(loss, head):
+    loss = _named_loss(loss)
     if isinstance(loss, str):
         if loss not in _LOSS_NAMES:
             raise ValueError(f"unknown loss '{loss}'")
@@ -272,7 +347,24 @@ def _loss_kind(loss, head):
         raise ValueError("categorical cross-entropy needs a softmax head")
     if kind == L.LOSS_BCE_LOGITS and head in ("seg", "dist"):
         raise ValueError("binary cross-entropy needs a sigmoid head")
+    if kind == L.LOSS_FOCAL_CE and head in ("bound", "color"):
+        raise ValueError("categorical focal cross-entropy needs a softmax head")
+    if kind == L.LOSS_FOCAL_BCE and head in ("seg", "dist"):
+        raise ValueError("binary focal cross-entropy needs a sigmoid head")
     return kind, getattr(loss, "weights", None)
+
+
+def _loss_head_options(loss, head, spec_opts):
+    """The options a loss object carries (label_smoothing, and the focal ones) into LossSpec's per-head dicts."""
+    loss = _named_loss(loss)
+    e = float(getattr(loss, "label_smoothing", 0.0) or 0.0)
+    if e != 0.0:
+        spec_opts["label_smoothing"][head] = e
+    if getattr(loss, "kind", None) in LS.FOCAL_KINDS:
+        spec_opts["focal_gamma"][head] = loss.gamma
+    if getattr(loss, "kind", None) == L.LOSS_FOCAL_BCE and loss.apply_class_balancing:
+        spec_opts["class_balance"][head] = True
+        spec_opts["focal_alpha"][head] = loss.alpha
 
 
 # ---- compact batches ---------------------------------------------------------------------------------
@@ -361,16 +453,27 @@ class Model:
         way (schedules.py has the definitions; stored in .h5 files, the averaged weights with them).
         gradient_accumulation_steps=K on the optimizer (accum.py has the definition): train_on_batch changes the weights on every K-th call
         only, with the mean of the K gradients; iterations, schedules and the average count those updates.  accumulation_state() tells where
-        the cycle stands; the .h5 file holds the option and an open cycle."""
+        the cycle stands; the .h5 file holds the option and an open cycle.
+        Losses: CategoricalFocalCrossentropy / BinaryFocalCrossentropy (or their Keras names as strings) and label_smoothing= on the
+        cross-entropies go into LossSpec's per-head dicts (losses.py has the definitions; stored in .h5 files).  Focal CE's per-class alpha
+        travels as the class weights: one vector per model."""
         margin = void_margin(ignore_void)
         if optimizer is None or isinstance(optimizer, str):
             optimizer = {"adam": Adam, "sgd": SGD}[optimizer or "adam"]()
         self.optimizer = optimizer
         heads = HEADS if self.cfg.multitasking else ["seg"]
         kinds, cw = {}, None
+        lopts = {k: {} for k in LS.OPTION_KEYS}
         for h in heads:
-            l = loss[h] if isinstance(loss, dict) else loss
+            l = _named_loss(loss[h] if isinstance(loss, dict) else loss)
             kinds[h], w = _loss_kind(l, h)
+            _loss_head_options(l, h, lopts)
+            if kinds[h] == L.LOSS_FOCAL_CE:                  # the per-class alpha travels as the class weights (one vector per model, as weighted CE's)
+                w = l.alpha_vector(self.cfg.num_classes)
+                if len(w) != self.cfg.num_classes:
+                    raise ValueError(f"{len(w)} alpha values for {self.cfg.num_classes} classes")
+                if cw is not None and list(cw) != list(w):
+                    raise ValueError("one per-class vector per model: the weighted / focal CE heads must agree in it")
             if w is not None:
                 if len(w) != self.cfg.num_classes:
                     raise ValueError(f"{len(w)} class weights for {self.cfg.num_classes} classes")
@@ -380,7 +483,7 @@ class Model:
             weights.update({h: float(loss_weights[h]) for h in heads if h in loss_weights})
         spec = LossSpec(kind=kinds, weight=weights, class_weights=cw, optimizer=optimizer.kind, lr=optimizer.lr.value,
                         beta_1=getattr(optimizer, "beta_1", 0.9), beta_2=getattr(optimizer, "beta_2", 0.999),
-                        momentum=getattr(optimizer, "momentum", 0.0), ignore_void=margin,
+                        momentum=getattr(optimizer, "momentum", 0.0), ignore_void=margin, **lopts,
                         **(optimizer.clip_options() if hasattr(optimizer, "clip_options") else {}),
                         **(optimizer.sched_options() if hasattr(optimizer, "sched_options") else {}),
                         **(optimizer.accum_options() if hasattr(optimizer, "accum_options") else {}))
@@ -587,7 +690,8 @@ class Model:
         if e.loss is not None:
             sp = e.loss
             meta["loss"] = dict(kind=sp.kind, weight=sp.weight, class_weights=sp.class_weights, optimizer=sp.optimizer, lr=sp.lr,
-                                beta_1=sp.beta_1, beta_2=sp.beta_2, momentum=sp.momentum, **sp.clip_options(), **sp.sched_options(), **sp.accum_options())
+                                beta_1=sp.beta_1, beta_2=sp.beta_2, momentum=sp.momentum, **sp.clip_options(), **sp.sched_options(), **sp.accum_options(),
+                                **sp.loss_options())
             og = root.require_group("optimizer_weights")
             og.set("rua/m:0", e.M1.cpu().numpy()); og.set("rua/v:0", e.V1.cpu().numpy())
             og.set("rua/iterations:0", np.array(e.t, np.int64))
@@ -777,7 +881,8 @@ def load_model(path, compile=True, custom_objects=None, dtype=None, input_shape=
             opt.exclude_from_weight_decay(var_names=co["decay_exclude"])
         m.optimizer = opt
         m.engine.compile(LossSpec(kind={k: int(v) for k, v in lo["kind"].items()}, weight=lo["weight"], class_weights=lo["class_weights"],
-                                  optimizer=lo["optimizer"], lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], momentum=lo["momentum"], **co, **so, **ao))
+                                  optimizer=lo["optimizer"], lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], momentum=lo["momentum"], **co, **so, **ao,
+                                  **LS.options_from_meta(lo)))
         m._attach_optimizer()
         og = root["optimizer_weights"]
         m.engine.M1.copy_(torch.from_numpy(np.ascontiguousarray(og["rua/m:0"]))); m.engine.V1.copy_(torch.from_numpy(np.ascontiguousarray(og["rua/v:0"])))

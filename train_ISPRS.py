@@ -54,6 +54,13 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
     `--ema_overwrite_frequency` then count updates, not batches; an incomplete cycle at the end of an epoch carries over into the next.
     The per-epoch line prints the updates taken next to the batches seen.  `--grad_accum 1` is off.  With `-cp` the option comes from
     the checkpoint, an open cycle with it.
+  * `--loss focal` with `--focal_gamma G` (default 2; 0 or 1..8), `--focal_alpha A [A ...]` (one value or one per class, default 0.25)
+    and `--bound_alpha A` (default: no class balancing): Keras' categorical focal cross-entropy on the seg head and, with
+    `--multitasking yes`, the binary focal cross-entropy on the boundary head; dist and color get MSE, as with the two cross-entropy
+    choices.  `--class_weights` (a list, or `auto`) is accepted with it and becomes the per-class alpha as given; with `--focal_gamma 0`
+    that is weighted cross entropy.  `--label_smoothing E` smooths the targets of the cross-entropy and focal losses (not `--loss
+    tanimoto`; the MSE heads take none).  All on the GPU (resunet_a_mltsk_keras_amd/losses.py); with `-cp` the loss and its options come
+    from the checkpoint.
   * `--dtype {bf16,f32}`, `--seed`: engine options.  Launch with torch.distributed.run for multi-GPU data
     parallel (`-bs` is then the GLOBAL batch, as under MirroredStrategy).
 """
@@ -97,7 +104,7 @@ def build_parser():
     p.add_argument("-dp", "--dataset_path", type=str, default="./DATASETS/patch_size=256_stride=32", help="Path where to load dataset")
     p.add_argument("-bs", "--batch_size", type=int, default=4, help="Batch size on training")
     p.add_argument("-lr", "--learning_rate", type=float, default=1e-3, help="Learning rate on training")
-    p.add_argument("--loss", type=str, default="weighted_cross_entropy", choices=["weighted_cross_entropy", "cross_entropy", "tanimoto"])
+    p.add_argument("--loss", type=str, default="weighted_cross_entropy", choices=["weighted_cross_entropy", "cross_entropy", "tanimoto", "focal"])
     p.add_argument("-optm", "--optimizer", type=str, choices=["adam", "sgd"], default="adam")
     p.add_argument("--num_classes", type=int, default=5)
     p.add_argument("--epochs", type=int, default=500)
@@ -130,7 +137,14 @@ def build_parser():
     p.add_argument("--photo_tone", type=float, default=0.4, metavar="V", help="photo_aug: the tone-curve strength is uniform in [-V, V], V <= 1")
     p.add_argument("--photo_noise", type=float, nargs=2, default=[0.0, 3.0], metavar=("LO", "HI"), help="photo_aug: the noise sigma, in levels, is uniform in [LO, HI]")
     p.add_argument("--class_weights", type=str, nargs="+", default=None, metavar="W",
-                   help="weighted_cross_entropy: `auto` (scene directory: total / pixels of the class over the training windows) or one weight per class")
+                   help="weighted_cross_entropy (class weights) / focal (per-class alpha): `auto` (scene directory: total / pixels of the class over the training windows) or one weight per class")
+    p.add_argument("--focal_gamma", type=float, default=2.0, metavar="G", help="--loss focal: the focusing exponent, 0 or 1..8 (0 with --class_weights is weighted cross entropy)")
+    p.add_argument("--focal_alpha", type=float, nargs="+", default=None, metavar="A",
+                   help="--loss focal: the seg head's alpha, one value or one per class (default 0.25; --class_weights gives it instead)")
+    p.add_argument("--bound_alpha", type=float, default=None, metavar="A",
+                   help="--loss focal, multitasking: class balancing of the boundary head's binary focal loss with this alpha (default: none)")
+    p.add_argument("--label_smoothing", type=float, default=0.0, metavar="E",
+                   help="label smoothing of the cross-entropy and focal losses, in [0, 1) (not --loss tanimoto; the MSE heads take none)")
     p.add_argument("--balance_class", type=int, default=None, metavar="K",
                    help="scene directory: train only on windows in which class K covers at least --balance_percent of the pixels")
     p.add_argument("--balance_percent", type=float, default=None, metavar="P", help="balance_class: the share of the window, in percent")
@@ -276,8 +290,8 @@ def check_class_flags(args):
         return None
     if args.checkpoint_path is not None:
         sys.exit("--class_weights: with --checkpoint_path the loss, its class weights included, comes from the checkpoint")
-    if args.loss != "weighted_cross_entropy":
-        sys.exit(f"--class_weights are the weights of --loss weighted_cross_entropy, not of --loss {args.loss}")
+    if args.loss not in ("weighted_cross_entropy", "focal"):
+        sys.exit(f"--class_weights are the weights of --loss weighted_cross_entropy or the per-class alpha of --loss focal, not of --loss {args.loss}")
     if len(cw) == 1 and cw[0].lower() == "auto":
         if not args.scene_dataset:
             sys.exit("--class_weights auto counts the classes of resident scenes: it needs --scene_dataset yes")
@@ -291,6 +305,41 @@ def check_class_flags(args):
     if not all(math.isfinite(v) and v >= 0 for v in w):
         sys.exit(f"--class_weights {' '.join(cw)}: the weights are finite and not negative")
     return w
+
+
+def check_loss_flags(args):
+    """--focal_* / --bound_alpha / --label_smoothing checked against --loss and the rest of the command line, before anything is loaded:
+    returns the seg head's explicit alpha vector (None: --class_weights or the default 0.25); SystemExit with a message otherwise."""
+    from resunet_a_mltsk_keras_amd import _lib as L
+    from resunet_a_mltsk_keras_amd import losses as LS
+    focal = args.loss == "focal"
+    given = [n for n, v, d in (("--focal_gamma", args.focal_gamma, 2.0), ("--focal_alpha", args.focal_alpha, None), ("--bound_alpha", args.bound_alpha, None),
+                               ("--label_smoothing", args.label_smoothing, 0.0)) if v != d]
+    if given and args.checkpoint_path is not None:
+        sys.exit(f"{given[0]}: with --checkpoint_path the loss, its options included, comes from the checkpoint")
+    if not focal:
+        for n in given:
+            if n != "--label_smoothing":
+                sys.exit(f"{n} belongs to --loss focal, not to --loss {args.loss}")
+    if args.label_smoothing and args.loss == "tanimoto":
+        sys.exit("--label_smoothing: the Tanimoto loss takes no label smoothing")
+    alpha = None
+    if args.focal_alpha is not None:
+        if args.class_weights is not None:
+            sys.exit("--focal_alpha and --class_weights both name the seg head's per-class alpha: give one of them")
+        if len(args.focal_alpha) not in (1, args.num_classes):
+            sys.exit(f"--focal_alpha: {len(args.focal_alpha)} values; one, or one per class (--num_classes {args.num_classes})")
+        alpha = LS.scalar_or_vector(args.focal_alpha, args.num_classes)
+    if args.bound_alpha is not None and not args.multitasking:
+        sys.exit("--bound_alpha balances the boundary head's loss: it needs --multitasking yes")
+    try:
+        kind = {"focal": L.LOSS_FOCAL_CE, "tanimoto": L.LOSS_TANIMOTO, "cross_entropy": L.LOSS_CE_LOGITS}.get(args.loss, L.LOSS_WCE)
+        LS.check_options(kind, args.num_classes, args.focal_gamma, alpha, False, args.label_smoothing, what="--loss " + args.loss)
+        if focal and args.bound_alpha is not None:
+            LS.check_options(L.LOSS_FOCAL_BCE, args.num_classes, args.focal_gamma, args.bound_alpha, True, args.label_smoothing, what="--bound_alpha")
+    except ValueError as exc:
+        sys.exit(str(exc))
+    return alpha
 
 
 def print_class_histogram(say, counts, num_classes):
@@ -470,6 +519,7 @@ def main(argv=None):
         sys.exit("--random_aug yes resamples windows of resident scenes: it needs --scene_dataset yes")
     check_photo_flags(args)
     class_weights = check_class_flags(args)
+    focal_alpha = check_loss_flags(args)
     void_margin = check_void_flags(args)
     import torch
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -487,8 +537,8 @@ def main(argv=None):
 
     from ResUnet_a.model2 import Resunet_a
     from multitasking_utils import Tanimoto_dual_loss
-    from resunet_a_mltsk_keras_amd.keras_api import (SGD, Adam, BinaryCrossentropy, CategoricalCrossentropy, K, MeanSquaredError,
-                                                   load_model, weighted_categorical_crossentropy)
+    from resunet_a_mltsk_keras_amd.keras_api import (SGD, Adam, BinaryCrossentropy, BinaryFocalCrossentropy, CategoricalCrossentropy,
+                                                   CategoricalFocalCrossentropy, K, MeanSquaredError, load_model, weighted_categorical_crossentropy)
 
     scenes = None
     if args.scene_dataset:
@@ -533,9 +583,17 @@ def main(argv=None):
         from resunet_a_mltsk_keras_amd.clip import DEFAULT_DECAY_EXCLUDE
         optm.exclude_from_weight_decay(var_names=list(DEFAULT_DECAY_EXCLUDE))
     say("=" * 60)
+    ls = args.label_smoothing
     if args.loss == "cross_entropy":
         say("Using Cross Entropy")
-        loss, loss_bound, loss_reg = CategoricalCrossentropy(), BinaryCrossentropy(), MeanSquaredError()
+        loss, loss_bound, loss_reg = CategoricalCrossentropy(label_smoothing=ls), BinaryCrossentropy(label_smoothing=ls), MeanSquaredError()
+    elif args.loss == "focal":
+        alpha = class_weights if class_weights is not None else focal_alpha if focal_alpha is not None else 0.25
+        say(f"Using Focal loss (gamma {args.focal_gamma:g}, alpha {alpha}, boundary alpha {args.bound_alpha}, label smoothing {ls:g})")
+        loss = CategoricalFocalCrossentropy(alpha=alpha, gamma=args.focal_gamma, label_smoothing=ls)
+        loss_bound = BinaryFocalCrossentropy(apply_class_balancing=args.bound_alpha is not None, alpha=args.bound_alpha if args.bound_alpha is not None else 0.25,
+                                             gamma=args.focal_gamma, label_smoothing=ls)
+        loss_reg = MeanSquaredError()
     elif args.loss == "tanimoto":
         say("Using Tanimoto Dual Loss")
         loss = loss_bound = loss_reg = Tanimoto_dual_loss()
@@ -543,7 +601,7 @@ def main(argv=None):
         say("Using Weighted cross entropy")
         weights = class_weights if class_weights is not None else REFERENCE_WCE_WEIGHTS if args.num_classes == 5 else [1.0] * args.num_classes
         say(weights)
-        loss, loss_bound, loss_reg = weighted_categorical_crossentropy(weights), BinaryCrossentropy(), MeanSquaredError()
+        loss, loss_bound, loss_reg = weighted_categorical_crossentropy(weights, label_smoothing=ls), BinaryCrossentropy(label_smoothing=ls), MeanSquaredError()
     say("=" * 60)
 
     if args.checkpoint_path is None:
