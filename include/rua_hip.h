@@ -615,6 +615,45 @@ int rua_grad_sumsq_gated(const float* g, const rua_opt_chunk* chunks, int n_chun
 int rua_clip_finish_gated(const double* partials, int n_chunks, const rua_opt_var* vars, int n_vars, int mode, double c, double grad_scale,
                           int skip_nonfinite, double* var_sumsq, float* coef, int32_t* flag2, double* report, const int32_t* hold, void* stream);
 
+/* ---- LAMB: Adam's direction scaled per variable by ||w|| / ||update|| (lamb.py holds the host definition; You et al. 2019, Keras 3's Lamb) ----
+ * Three launches over the chunk table where rua_adam_step_seg is one.  The rate kernel in front of them runs with adam = 0: the bias
+ * correction is applied per element here.  Every fp32 operation is rounded on its own (no contraction), divisions and square roots are IEEE,
+ * so m', v', u and theta' are bit for bit lamb.host_lamb_step's.  Padding is never read or written.
+ *   t = (int64)lr_state[0], the update count the rate kernel of THIS step has advanced; c1 = (float)(1 - beta1^t), c2 = (float)(1 - beta2^t)
+ *   with beta^t = lamb.host_powi: binary exponentiation on fp64 (value, remainder) pairs in a fixed order - within one ulp of beta^t, the
+ *   same bits on both sides, no pow on either.
+ *
+ * rua_lamb_moments - pass 1, one block per chunk.  Per element of a chunk of variable var:
+ *   th1 = vars[var].decay && weight_decay != 0 ? th - th * d : th,     d = (float)(weight_decay * lr_state[1])      (as rua_adam_step_seg)
+ *   gg  = clampv((g * grad_scale) * coef[var])                                                                      (as rua_adam_step_seg)
+ *   m'  = m + (gg - m) * (1 - beta1),   v' = v + (gg * gg - v) * (1 - beta2)                                        (Keras' form)
+ *   u   = (m' / c1) / (sqrt(v' / c2) + eps)
+ * m and v receive m' and v'; g RECEIVES u (the gradient is consumed; pass 2 reads u there and zeroes the slot); theta is only read.
+ * pw[k] = sum of (double)th1^2, pu[k] = sum of (double)u^2 over chunk k, in rua_grad_sumsq's reduction order (a lane adds its elements in
+ * index order, a fixed butterfly over the wave, the four waves in order, no atomics): the same bits on every run and every replay.
+ *
+ * rua_lamb_finish - one block.  W[v], U[v] = the partials of variable v added in chunk order (var_wu[v] and var_wu[n_vars + v], scratch of
+ * 2 * n_vars doubles; the variables' chunk ranges tile [0, n_chunks) in order);
+ *   ratio[v] = (W > 0 && U > 0) ? (float)(sqrt(W) / sqrt(U)) : 1        (a zero or NaN sum gives 1, as Keras' nested where does)
+ *   report[0] = the smallest, report[1] = the largest ratio of this update, report[2] = the variables of this update whose ratio the rule
+ *   forced to 1, report[3] += 1 (updates taken).
+ *
+ * rua_lamb_apply - pass 2, one block per chunk:  theta' = th1 - (ratio[var] * lr_dev[0]) * u, with th1 recomputed as above and u read from
+ * g's slot; g = 0 when zero_grad is set; wcopy_bf16 (NULL: none) receives bf16(theta').
+ *
+ * flag (NULL: never) != 0 - a skipped update (skip_nonfinite) or a hold step of gradient accumulation, the flags rua_adam_step_seg takes -:
+ * theta, m, v, pw, pu, var_wu, ratio and report keep their bits; pass 1 only zeroes g, pass 2 only rewrites wcopy_bf16 from the unchanged theta.
+ * 0 <= beta < 1, eps > 0, weight_decay >= 0, n_chunks > 0, n_vars > 0; float buffers and tables 16-byte aligned, doubles 8-byte, wcopy 8-byte,
+ * coef / ratio / flag / lr_dev 4-byte; pw != pu.  A violation is RUA_ERR_ARG before anything is launched. */
+int rua_lamb_moments(const float* theta, float* g, float* m, float* v, const rua_opt_chunk* chunks, int n_chunks, const rua_opt_var* vars,
+                     const float* coef, const int32_t* flag, const double* lr_state, float beta1, float beta2, float eps, float grad_scale,
+                     float clipvalue, double weight_decay, double* pw, double* pu, void* stream);
+int rua_lamb_finish(const double* pw, const double* pu, int n_chunks, const rua_opt_var* vars, int n_vars, const int32_t* flag, double* var_wu,
+                    float* ratio, double* report, void* stream);
+int rua_lamb_apply(float* theta, float* g, const rua_opt_chunk* chunks, int n_chunks, const rua_opt_var* vars, const float* ratio,
+                   const int32_t* flag, const float* lr_dev, const double* lr_state, double weight_decay, int zero_grad, void* wcopy_bf16,
+                   void* stream);
+
 /* ---- multitask training targets from uint8 patches (labels.py; the reference's preprocess_save_patches_ISPRS.py:206-228,
  * multitasking_utils.py:6-35) ------------------------------------------------------------------------------------------------
  * img [N][H][W][Cin] and cls [N][H][W] are uint8 (4-byte aligned); x [N][H][W][Cin], seg / bound / dist [N][H][W][C] and

@@ -200,6 +200,9 @@ _SIGS = {
     "rua_lr_schedule_step_gated": ([vp, vp, LrSchedule, i32, f64, f64, vp, vp], i32),
     "rua_grad_sumsq_gated": ([vp, vp, i32, vp, vp, vp], i32),
     "rua_clip_finish_gated": ([vp, i32, vp, i32, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp], i32),
+    "rua_lamb_moments": ([vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, f32, f32, f32, f32, f32, f64, vp, vp, vp], i32),
+    "rua_lamb_finish": ([vp, vp, i32, vp, i32, vp, vp, vp, vp, vp], i32),
+    "rua_lamb_apply": ([vp, vp, vp, i32, vp, vp, vp, vp, vp, f64, i32, vp, vp], i32),
     "rua_tanimoto_sums_void": ([vp, vp, vp, i32, i64, i32, vp, vp], i32),
     "rua_head_fwd_loss_void": ([vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i64, i32, i32, i32, i32, vp, vp], i32),
     "rua_pixel_loss_void": ([i32, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp], i32),

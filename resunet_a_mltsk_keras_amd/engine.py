@@ -22,6 +22,7 @@ import torch
 from . import _lib as L
 from . import accum as AC
 from . import clip as CL
+from . import lamb as LB
 from . import losses as LS
 from . import schedules as SC
 from .wgrad_queue import WgradQueue, WSpec
@@ -59,6 +60,7 @@ class LossSpec:
     beta_1: float = 0.9
     beta_2: float = 0.999
     momentum: float = 0.8
+    epsilon: float = 1e-7                                    # "lamb" only (lamb.py holds the definition): Adam's kernels are built with Keras' default
     ignore_void: Optional[int] = None                        # None: off.  An int (0..16): void pixels leave every loss and metric; the void mask of
                                                              # a class-map batch is cls >= num_classes dilated by this margin (labels.host_void_mask)
     # Gradient clipping, decoupled weight decay, non-finite step skip (clip.py holds the definitions).  All off: the optimizer issues the calls it always did.
@@ -1717,6 +1719,10 @@ class Engine:
         if spec.lr_schedule is not None and not isinstance(spec.lr_schedule, SC.LearningRateSchedule):
             raise ValueError(f"lr_schedule {spec.lr_schedule!r}: None or a schedule of resunet_a_mltsk_keras_amd.schedules")
         AC.check_steps(spec.gradient_accumulation_steps)
+        if spec.optimizer not in ("adam", "sgd", "lamb"):
+            raise ValueError(f"optimizer {spec.optimizer!r}: 'adam', 'sgd' or 'lamb'")
+        if spec.optimizer == "lamb":
+            LB.check_options(spec.beta_1, spec.beta_2, spec.epsilon)
         self._check_loss_options(spec)
         if self._in_ema:
             raise RuntimeError("compile() inside ema_weights(): leave the block first")
@@ -1814,8 +1820,10 @@ class Engine:
         coefficients, the skip flag, the report and the BatchNorm state's backup.  Nothing is allocated and self.clip is None with every option off."""
         self.clip = None
         self._s_backed = False
-        # gradient accumulation takes the chunk-table route too (mode RUA_CLIP_NONE with no clip option): its optimizers honour the hold flag
-        if not (spec.clip_on() or spec.gradient_accumulation_steps is not None) or self.dev is None:
+        # gradient accumulation takes the chunk-table route too (mode RUA_CLIP_NONE with no clip option): its optimizers honour the hold flag.
+        # So does LAMB, always: its trust ratio is per variable
+        lamb = spec.optimizer == "lamb"
+        if not (spec.clip_on() or spec.gradient_accumulation_steps is not None or lamb) or self.dev is None:
             return
         chunks, vars_, names = CL.build_chunk_table(self.params.entries, spec.decay_exclude or ())
         mode, c = CL.clip_mode(spec.clipnorm, spec.global_clipnorm, spec.clipvalue)
@@ -1826,6 +1834,38 @@ class Engine:
                          partials=zd(len(chunks), torch.float64), var_sumsq=zd(len(vars_), torch.float64), coef=zd(len(vars_), torch.float32),
                          flag=zd(4, torch.int32), report=zd(4, torch.float64),
                          s_backup=zd(self.params.ns, torch.float32) if spec.skip_nonfinite and self.params.ns > 0 else None)
+        if lamb:
+            # pass 1's per-chunk sums, the finisher's per-variable sums (W then U), ratios and report.  With no clip option, no decay, no skip and
+            # no accumulation the sum of squares and the clip finisher are not launched: the coefficients are ones for good
+            self.clip["plain"] = not spec.clip_on() and spec.gradient_accumulation_steps is None
+            if self.clip["plain"]:
+                self.clip["coef"].fill_(1.0)
+            self.clip.update(pw=zd(len(chunks), torch.float64), pu=zd(len(chunks), torch.float64), var_wu=zd(2 * len(vars_), torch.float64),
+                             ratio=zd(len(vars_), torch.float32), trust=zd(4, torch.float64))
+
+    def trust_report(self) -> Optional[Dict[str, object]]:
+        """LAMB: what the last update's finisher wrote (None for the other optimizers) - min_ratio, max_ratio: the smallest and largest trust
+        ratio ||w|| / ||update|| it applied; forced: the variables whose ratio a zero or non-finite norm set to 1; updates: updates taken since
+        compile() (a skipped or a hold step is none); ratios: {variable name: ratio}.  Synchronises the device."""
+        if self.clip is None or "ratio" not in self.clip:
+            return None
+        torch.cuda.synchronize()
+        r = self.clip["trust"].cpu().numpy()
+        ratios = self.clip["ratio"].cpu().numpy()[:self.clip["n_vars"]]
+        return dict(min_ratio=float(r[0]), max_ratio=float(r[1]), forced=int(r[2]), updates=int(r[3]),
+                    ratios={n: float(x) for n, x in zip(self.clip["names"], ratios)})
+
+    def _launch_lamb(self, flag, grad_scale, wc, sv):
+        """The three LAMB launches where rua_adam_step_seg stands (lamb.py): moments and direction with the per-chunk sums, the one-block
+        finisher (ratios, report), the update.  flag: the flag rua_adam_step_seg would take."""
+        sp, ck, lib = self.loss, self.clip, L.lib()
+        lib.call("rua_lamb_moments", self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.V1.data_ptr(), ck["chunks"].data_ptr(), ck["n_chunks"],
+                 ck["vars"].data_ptr(), ck["coef"].data_ptr(), flag, self.lr_state.data_ptr(), sp.beta_1, sp.beta_2, sp.epsilon, grad_scale, ck["cv"], ck["wd"],
+                 ck["pw"].data_ptr(), ck["pu"].data_ptr(), sv)
+        lib.call("rua_lamb_finish", ck["pw"].data_ptr(), ck["pu"].data_ptr(), ck["n_chunks"], ck["vars"].data_ptr(), ck["n_vars"], flag, ck["var_wu"].data_ptr(),
+                 ck["ratio"].data_ptr(), ck["trust"].data_ptr(), sv)
+        lib.call("rua_lamb_apply", self.P.data_ptr(), self.G.data_ptr(), ck["chunks"].data_ptr(), ck["n_chunks"], ck["vars"].data_ptr(), ck["ratio"].data_ptr(), flag,
+                 self.lr_dev.data_ptr(), self.lr_state.data_ptr(), ck["wd"], 1, wc, sv)
 
     def clip_report(self) -> Optional[Dict[str, float]]:
         """What the last optimizer step's finisher wrote (None with every clip / decay / skip option off): norm - that step's global gradient norm
@@ -2189,11 +2229,14 @@ class Engine:
             # scalar.  Under data parallel this runs on the REDUCED gradient (dist.reduce_gradients comes first and has already copied the reduced
             # state out of G's tail into S, so the restore is the last writer of S): every rank takes the same decision.
             lib, sv = L.lib(), C.c_void_p(s)
-            lib.call("rua_grad_sumsq", self.G.data_ptr(), ck["chunks"].data_ptr(), ck["n_chunks"], ck["partials"].data_ptr(), sv)
-            lib.call("rua_clip_finish", ck["partials"].data_ptr(), ck["n_chunks"], ck["vars"].data_ptr(), ck["n_vars"], ck["mode"], ck["c"], float(grad_scale), ck["skip"],
-                     ck["var_sumsq"].data_ptr(), ck["coef"].data_ptr(), ck["flag"].data_ptr(), ck["report"].data_ptr(), sv)
+            if not ck.get("plain"):                         # plain LAMB: nothing to clip, decay or skip - the coefficients are ones
+                lib.call("rua_grad_sumsq", self.G.data_ptr(), ck["chunks"].data_ptr(), ck["n_chunks"], ck["partials"].data_ptr(), sv)
+                lib.call("rua_clip_finish", ck["partials"].data_ptr(), ck["n_chunks"], ck["vars"].data_ptr(), ck["n_vars"], ck["mode"], ck["c"], float(grad_scale),
+                         ck["skip"], ck["var_sumsq"].data_ptr(), ck["coef"].data_ptr(), ck["flag"].data_ptr(), ck["report"].data_ptr(), sv)
             flag = ck["flag"].data_ptr() if ck["skip"] else None
-            if sp.optimizer == "adam":
+            if sp.optimizer == "lamb":
+                self._launch_lamb(flag, grad_scale, wc, sv)
+            elif sp.optimizer == "adam":
                 lib.call("rua_adam_step_seg", self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.V1.data_ptr(), ck["chunks"].data_ptr(),
                          ck["n_chunks"], ck["vars"].data_ptr(), ck["coef"].data_ptr(), flag, self.lr_dev.data_ptr(), self.lr_state.data_ptr(),
                          sp.beta_1, sp.beta_2, KERAS_EPS, grad_scale, ck["cv"], ck["wd"], 1, wc, sv)
@@ -2236,7 +2279,9 @@ class Engine:
         lib.call("rua_grad_sumsq_gated", self.G.data_ptr(), ck["chunks"].data_ptr(), ck["n_chunks"], ck["partials"].data_ptr(), hold, sv)
         lib.call("rua_clip_finish_gated", ck["partials"].data_ptr(), ck["n_chunks"], ck["vars"].data_ptr(), ck["n_vars"], ck["mode"], ck["c"], float(grad_scale),
                  ck["skip"], ck["var_sumsq"].data_ptr(), ck["coef"].data_ptr(), flag, ck["report"].data_ptr(), hold, sv)
-        if adam:
+        if sp.optimizer == "lamb":
+            self._launch_lamb(both, grad_scale, wc, sv)
+        elif adam:
             lib.call("rua_adam_step_seg", self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.V1.data_ptr(), ck["chunks"].data_ptr(),
                      ck["n_chunks"], ck["vars"].data_ptr(), ck["coef"].data_ptr(), both, self.lr_dev.data_ptr(), self.lr_state.data_ptr(),
                      sp.beta_1, sp.beta_2, KERAS_EPS, grad_scale, ck["cv"], ck["wd"], 1, wc, sv)

@@ -134,6 +134,23 @@ class Adam(_ClipOptions):
             raise ValueError("the HIP Adam kernel is built with Keras' default epsilon 1e-7")
 
 
+class Lamb(_ClipOptions):
+    """Keras 3's Lamb (lamb.py has the definition): Adam's direction, each variable's step scaled by ||w|| / ||update|| on the GPU.  Every
+    keyword Adam takes from _ClipOptions composes with it; epsilon is free (Adam's is built in).  Model.trust_report() shows the ratios."""
+
+    def __init__(self, learning_rate=None, beta_1=0.9, beta_2=0.999, epsilon=1e-7, lr=None, clipnorm=None, global_clipnorm=None, clipvalue=None,
+                 weight_decay=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None,
+                 gradient_accumulation_steps=None, **_):
+        from .lamb import check_options
+        check_options(beta_1, beta_2, epsilon)
+        self._set_clip(clipnorm, global_clipnorm, clipvalue, weight_decay, skip_nonfinite)
+        self._set_accum(gradient_accumulation_steps)
+        self._set_ema(use_ema, ema_momentum, ema_overwrite_frequency)
+        self.lr = _lr_var(learning_rate, lr, 1e-3)
+        self.learning_rate = self.lr
+        self.beta_1, self.beta_2, self.epsilon, self.kind = float(beta_1), float(beta_2), float(epsilon), "lamb"
+
+
 class SGD(_ClipOptions):
     def __init__(self, lr=None, learning_rate=None, momentum=0.0, nesterov=False, clipnorm=None, global_clipnorm=None, clipvalue=None,
                  weight_decay=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None,
@@ -459,7 +476,7 @@ class Model:
         travels as the class weights: one vector per model."""
         margin = void_margin(ignore_void)
         if optimizer is None or isinstance(optimizer, str):
-            optimizer = {"adam": Adam, "sgd": SGD}[optimizer or "adam"]()
+            optimizer = {"adam": Adam, "sgd": SGD, "lamb": Lamb}[optimizer or "adam"]()
         self.optimizer = optimizer
         heads = HEADS if self.cfg.multitasking else ["seg"]
         kinds, cw = {}, None
@@ -483,7 +500,7 @@ class Model:
             weights.update({h: float(loss_weights[h]) for h in heads if h in loss_weights})
         spec = LossSpec(kind=kinds, weight=weights, class_weights=cw, optimizer=optimizer.kind, lr=optimizer.lr.value,
                         beta_1=getattr(optimizer, "beta_1", 0.9), beta_2=getattr(optimizer, "beta_2", 0.999),
-                        momentum=getattr(optimizer, "momentum", 0.0), ignore_void=margin, **lopts,
+                        momentum=getattr(optimizer, "momentum", 0.0), epsilon=getattr(optimizer, "epsilon", 1e-7), ignore_void=margin, **lopts,
                         **(optimizer.clip_options() if hasattr(optimizer, "clip_options") else {}),
                         **(optimizer.sched_options() if hasattr(optimizer, "sched_options") else {}),
                         **(optimizer.accum_options() if hasattr(optimizer, "accum_options") else {}))
@@ -513,6 +530,11 @@ class Model:
         """Engine.clip_report: dict(norm, min_coef, skipped, clipped) of the last step and the counts since compile(), or None when the optimizer
         was given no clipnorm / global_clipnorm / clipvalue / weight_decay / skip_nonfinite.  Synchronises the device."""
         return self.engine.clip_report()
+
+    def trust_report(self):
+        """Engine.trust_report: dict(min_ratio, max_ratio, forced, updates, ratios={variable name: ratio}) of the last LAMB update, or None when
+        the optimizer is not Lamb.  Synchronises the device."""
+        return self.engine.trust_report()
 
     def accumulation_state(self):
         """Adam / SGD(gradient_accumulation_steps=K): dict(steps=K, micro=calls of train_on_batch since the last update, 0 .. K - 1); None with
@@ -692,6 +714,8 @@ class Model:
             meta["loss"] = dict(kind=sp.kind, weight=sp.weight, class_weights=sp.class_weights, optimizer=sp.optimizer, lr=sp.lr,
                                 beta_1=sp.beta_1, beta_2=sp.beta_2, momentum=sp.momentum, **sp.clip_options(), **sp.sched_options(), **sp.accum_options(),
                                 **sp.loss_options())
+            if sp.optimizer == "lamb":                       # the one optimizer whose epsilon is an option
+                meta["loss"]["epsilon"] = float(sp.epsilon)
             og = root.require_group("optimizer_weights")
             og.set("rua/m:0", e.M1.cpu().numpy()); og.set("rua/v:0", e.V1.cpu().numpy())
             og.set("rua/iterations:0", np.array(e.t, np.int64))
@@ -876,12 +900,17 @@ def load_model(path, compile=True, custom_objects=None, dtype=None, input_shape=
         ao = loss_accum_options(lo)
         ko.update(ao)
         rate = so["lr_schedule"] if so["lr_schedule"] is not None else lo["lr"]
-        opt = Adam(lr=rate, beta_1=lo["beta_1"], beta_2=lo["beta_2"], **ko) if lo["optimizer"] == "adam" else SGD(lr=rate, momentum=lo["momentum"], **ko)
+        eo = {}
+        if lo["optimizer"] == "lamb":
+            eo = dict(epsilon=float(lo.get("epsilon", 1e-7)))
+            opt = Lamb(learning_rate=rate, beta_1=lo["beta_1"], beta_2=lo["beta_2"], **eo, **ko)
+        else:
+            opt = Adam(lr=rate, beta_1=lo["beta_1"], beta_2=lo["beta_2"], **ko) if lo["optimizer"] == "adam" else SGD(lr=rate, momentum=lo["momentum"], **ko)
         if co["decay_exclude"]:
             opt.exclude_from_weight_decay(var_names=co["decay_exclude"])
         m.optimizer = opt
         m.engine.compile(LossSpec(kind={k: int(v) for k, v in lo["kind"].items()}, weight=lo["weight"], class_weights=lo["class_weights"],
-                                  optimizer=lo["optimizer"], lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], momentum=lo["momentum"], **co, **so, **ao,
+                                  optimizer=lo["optimizer"], lr=lo["lr"], beta_1=lo["beta_1"], beta_2=lo["beta_2"], momentum=lo["momentum"], **eo, **co, **so, **ao,
                                   **LS.options_from_meta(lo)))
         m._attach_optimizer()
         og = root["optimizer_weights"]

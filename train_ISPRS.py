@@ -54,6 +54,9 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
     `--ema_overwrite_frequency` then count updates, not batches; an incomplete cycle at the end of an epoch carries over into the next.
     The per-epoch line prints the updates taken next to the batches seen.  `--grad_accum 1` is off.  With `-cp` the option comes from
     the checkpoint, an open cycle with it.
+  * `-optm lamb [--lamb_epsilon E]`: the LAMB optimizer (resunet_a_mltsk_keras_amd/lamb.py) - Adam's direction with each variable's step scaled
+    by ||w|| / ||update|| on the GPU, so that one `-lr` carries across `-bs` x GPUs x `--grad_accum`.  Every option above composes with it; the
+    per-epoch line prints the smallest and largest trust ratio of the last update.
   * `--loss focal` with `--focal_gamma G` (default 2; 0 or 1..8), `--focal_alpha A [A ...]` (one value or one per class, default 0.25)
     and `--bound_alpha A` (default: no class balancing): Keras' categorical focal cross-entropy on the seg head and, with
     `--multitasking yes`, the binary focal cross-entropy on the boundary head; dist and color get MSE, as with the two cross-entropy
@@ -105,7 +108,8 @@ def build_parser():
     p.add_argument("-bs", "--batch_size", type=int, default=4, help="Batch size on training")
     p.add_argument("-lr", "--learning_rate", type=float, default=1e-3, help="Learning rate on training")
     p.add_argument("--loss", type=str, default="weighted_cross_entropy", choices=["weighted_cross_entropy", "cross_entropy", "tanimoto", "focal"])
-    p.add_argument("-optm", "--optimizer", type=str, choices=["adam", "sgd"], default="adam")
+    p.add_argument("-optm", "--optimizer", type=str, choices=["adam", "sgd", "lamb"], default="adam")
+    p.add_argument("--lamb_epsilon", type=float, default=1e-7, metavar="E", help="-optm lamb: the epsilon of the Adam direction (default 1e-7, as the Adam of this package)")
     p.add_argument("--num_classes", type=int, default=5)
     p.add_argument("--epochs", type=int, default=500)
     p.add_argument("-ps", "--patch_size", type=int, default=256)
@@ -498,6 +502,10 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
         rep = net.clip_report() if hasattr(net, "clip_report") else None        # None: no clip / decay / skip option is on
         if rep is not None:
             say(f"Optimizer: {rep['skipped']} steps skipped (non-finite gradient), {rep['clipped']} clipped by a norm so far; last gradient norm {rep['norm']:.6g}")
+        trust = net.trust_report() if hasattr(net, "trust_report") else None   # None: the optimizer is not LAMB
+        if trust is not None:
+            say(f"LAMB trust ratio: {trust['min_ratio']:.6g} .. {trust['max_ratio']:.6g} over {len(trust['ratios'])} variables "
+                f"({trust['forced']} forced to 1; {trust['updates']} updates so far)")
         val_loss = agree_from_rank0(vm["loss"], world)
         if val_loss >= min_loss + delta:
             cont += 1
@@ -537,7 +545,7 @@ def main(argv=None):
 
     from ResUnet_a.model2 import Resunet_a
     from multitasking_utils import Tanimoto_dual_loss
-    from resunet_a_mltsk_keras_amd.keras_api import (SGD, Adam, BinaryCrossentropy, BinaryFocalCrossentropy, CategoricalCrossentropy,
+    from resunet_a_mltsk_keras_amd.keras_api import (SGD, Adam, Lamb, BinaryCrossentropy, BinaryFocalCrossentropy, CategoricalCrossentropy,
                                                    CategoricalFocalCrossentropy, K, MeanSquaredError, load_model, weighted_categorical_crossentropy)
 
     scenes = None
@@ -578,7 +586,13 @@ def main(argv=None):
     rate, ema_kw = schedule_options(args)
     opt_kw.update(ema_kw)
     opt_kw.update(accum_options(args))
-    optm = Adam(lr=rate, beta_1=0.9, **opt_kw) if args.optimizer == "adam" else SGD(lr=rate, momentum=0.8, **opt_kw)
+    if args.optimizer == "lamb":
+        try:
+            optm = Lamb(learning_rate=rate, beta_1=0.9, epsilon=args.lamb_epsilon, **opt_kw)
+        except ValueError as exc:
+            sys.exit(f"--lamb_epsilon: {exc}")
+    else:
+        optm = Adam(lr=rate, beta_1=0.9, **opt_kw) if args.optimizer == "adam" else SGD(lr=rate, momentum=0.8, **opt_kw)
     if args.weight_decay and not args.decay_all:
         from resunet_a_mltsk_keras_amd.clip import DEFAULT_DECAY_EXCLUDE
         optm.exclude_from_weight_decay(var_names=list(DEFAULT_DECAY_EXCLUDE))

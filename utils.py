@@ -3,7 +3,7 @@ The U-Net / ResNet50 baselines and the numpy patch plumbing of the reference's u
 import numpy as np  # noqa: F401
 
 from resunet_a_mltsk_keras_amd.keras_api import (  # noqa: F401
-    SGD, Adam, K, load_model, weighted_categorical_crossentropy)
+    SGD, Adam, K, Lamb, load_model, weighted_categorical_crossentropy)
 
 
 def unet(*_a, **_k):
