@@ -1,7 +1,7 @@
 """Evaluation of a trained model on whole scenes, on the GPU: what test_ISPRS.py does for the reference's test tile (patches,
 predict, arg-max, metrics, mosaic), for a scene directory (resunet_a_mltsk_keras_amd.scenes: scenes/<name>.npy,
 labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views, --scales, --blend, --erode_boundary,
---boundary_f1 and --head_maps.
+--boundary_f1, --sieve and --head_maps.
 
 Every scene stays on the GPU, is covered by windows --stride apart (default: the patch; the last window flush with the border, so
 nothing is left unpredicted), every pixel is predicted from the window it is most central in, and Model.predict_scene brings back
@@ -38,6 +38,16 @@ un-eroded class map.  Per scene `boundary_counts_<name>.npy` (int64 C x 4: n_pre
 blocks above a block `Boundary F1 (tolerance R px)` follows, scored on the counts summed over the scenes (the published BF score
 averages per image: the per-scene files allow that); the returned dict gains `boundary_counts`, `boundary_precision`,
 `boundary_recall`, `boundary_f1` and `boundary_f1_mean`.
+
+--sieve N [--sieve_mode fill|void] [--sieve_connectivity 4|8] [--sieve_classes c ...] [--sieve_rounds R] cleans the finished map
+with a minimum mapping unit before anything scores it: the connected regions (of equal class, 4- or 8-connected) of fewer than N
+pixels are removed on the GPU (scenes.host_sieve) - `fill` gives each the class most of its kept 4-neighbours have, `void` turns
+them into 255, which no score counts -, only those of the classes --sieve_classes names (default: all), --sieve_rounds times.
+`--sieve 69 --sieve_mode void --sieve_classes 1` is the reference's `prediction` protocol (an area opening of 69 pixels, the removed
+pixels left out of the score).  The written map and every block of scores are then the sieved map's; per scene the region counts of
+the un-sieved map (per class: regions, regions below N pixels, their pixels) and the pixels changed are printed and
+`region_counts_<name>.npy` (int64 C x 3) is written; after the sieved scores a block `Before the sieve` prints those of the raw map;
+the returned dict gains `confusion_matrix_raw`, `region_counts` and `sieve_changed`.
 
 --head_maps HEAD [HEAD ...] also writes whole-scene maps of the named heads (`seg`, `bound`, `dist`, `color`, `color_rgb`; what
 test_ISPRS.py:285-414 displays per patch): `pred_<head>_<name>.npy`, uint8 H x W x Ch - the head's output averaged over the views,
@@ -95,6 +105,13 @@ def build_parser():
                         help="also score on the ground truth eroded by a disc of radius R (0..16; the ISPRS benchmark uses 3); 0: off")
     parser.add_argument("--boundary_f1", type=int, default=None, metavar="R",
                         help="also print the boundary F1 (BF score) with a tolerance of R pixels (0..16; 0: exact coincidence); default: off")
+    parser.add_argument("--sieve", type=int, default=None, metavar="N",
+                        help="remove connected regions of fewer than N pixels from the class map before it is scored; default: off")
+    parser.add_argument("--sieve_mode", choices=["fill", "void"], default="fill",
+                        help="fill: a removed region takes the class most of its kept 4-neighbours have; void: it becomes 255 and leaves every score")
+    parser.add_argument("--sieve_connectivity", type=int, default=4, metavar="4|8", help="what connects the pixels of a region: 4- or 8-neighbours")
+    parser.add_argument("--sieve_classes", nargs="+", type=int, default=None, metavar="c", help="sieve only regions of these classes (default: all)")
+    parser.add_argument("--sieve_rounds", type=int, default=1, metavar="R", help="apply the sieve R times (1..4): a second round removes speckle nested in speckle")
     parser.add_argument("--head_maps", nargs="+", default=[], metavar="HEAD",
                         help="also write uint8 whole-scene maps of these heads: seg, bound, dist, color, color_rgb (default: none)")
     return parser
@@ -146,6 +163,13 @@ def main(argv=None):
         boundary = scenes.check_tolerance(args.boundary_f1)
     except ValueError as exc:
         raise SystemExit(f"--boundary_f1: {exc}") from None
+    sieve = None
+    if args.sieve is not None:
+        sieve = dict(min_area=args.sieve, mode=args.sieve_mode, connectivity=args.sieve_connectivity, classes=args.sieve_classes, rounds=args.sieve_rounds)
+        try:
+            scenes.sieve_params(sieve, args.num_classes)
+        except ValueError as exc:
+            raise SystemExit(f"--sieve: {exc}") from None
     heads = tuple(args.head_maps)
     scales = parse_scales(args.scales, args.patch_size, heads)
     if args.blend is not None and heads:
@@ -177,9 +201,12 @@ def main(argv=None):
     lut = {k: v for k, v in LABEL_DICT.items() if v < args.num_classes}
     for extra in range(len(lut), args.num_classes):                                              # classes beyond the ISPRS colours: greys
         lut[str((40 * extra % 256,) * 3)] = extra
+    if sieve is not None and args.sieve_mode == "void":
+        lut[str((0, 0, 0))] = 255                                                                # the removed regions: black in the .ppm
     total = np.zeros((args.num_classes, args.num_classes), np.int64)
     total_eroded = np.zeros_like(total)
     total_boundary = np.zeros((args.num_classes, 4), np.int64)
+    total_raw, total_regions, total_changed = np.zeros_like(total), np.zeros((args.num_classes, 3), np.int64), 0
     all_head_maps, mae_sum, mae_n = [], 0.0, 0
     print('=' * 40)
     print('[TEST]')
@@ -197,8 +224,15 @@ def main(argv=None):
             json.dump({"views": list(views), "scales": None if scales is None else list(scales), "stride": args.stride, "blend": args.blend}, f)
     for s, name in enumerate(names):
         pred, cm, *more = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type, views=views,
-                                              erode=erode, heads=heads, boundary=boundary, scales=scales, blend=args.blend)
+                                              erode=erode, heads=heads, boundary=boundary, scales=scales, blend=args.blend, sieve=sieve)
         head_maps = more.pop() if heads else {}
+        if sieve is not None:
+            report = more.pop()
+            total_raw += report["confusion_raw"]
+            total_regions += report["counts"]
+            total_changed += report["changed"]
+            np.save(os.path.join(args.output_path, f'region_counts_{name}.npy'), report["counts"])
+            print(f'scene {name}: regions per class (all, below {args.sieve} px, their pixels) {report["counts"].tolist()}, {report["changed"]} pixels changed')
         if boundary is not None:
             counts = more.pop()
             total_boundary += counts
@@ -231,6 +265,18 @@ def main(argv=None):
     res = {"accuracy": metrics[0], "f1": metrics[1], "recall": metrics[2], "precision": metrics[3], "confusion_matrix": total}
     if args.blend is not None:
         res["blend"] = args.blend
+    if sieve is not None:
+        m = metrics_from_confusion(total_raw)
+        print()
+        print(f'Before the sieve (--sieve {args.sieve}, {args.sieve_mode}: {total_changed} pixels changed)')
+        print('Region counts (regions, small regions, their pixels) \n', total_regions)
+        print('Confusion  matrix \n', total_raw)
+        print()
+        print('Accuracy: ', m[0])
+        print('F1score: ', m[1])
+        print('Recall: ', m[2])
+        print('Precision: ', m[3])
+        res.update(confusion_matrix_raw=total_raw, region_counts=total_regions, sieve_changed=total_changed)
     if erode:
         m = metrics_from_confusion(total_eroded)
         print()

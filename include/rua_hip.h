@@ -913,6 +913,56 @@ int rua_scene_boundary(const uint8_t* const* scene_cls, const uint8_t* const* sc
                        int nscenes, int radius, int C, uint8_t* const* bound_cls, uint8_t* const* bound_pred, int64_t* counts,
                        void* stream);
 
+/* ---- connected regions of a class map and the sieve that removes the small ones (scenes.py, host_regions / host_region_counts /
+ * host_sieve; the reference's utils.prediction cleans a prediction with an area opening before it scores it) -----------------------
+ * scene_map / scene_h / scene_w are HOST arrays of nscenes entries, as rua_scene_erode reads them: device pointers to uint8
+ * [scene_h[s]][scene_w[s]] maps.  A region is a maximal set of pixels of equal byte value connected through 4-neighbours
+ * (connectivity 4) or 8-neighbours (8).  Bytes are compared raw, so "no class" bytes (>= C) form regions like any other; pixels
+ * outside the map do not exist.  labels and areas (nullable) are HOST arrays of nscenes device pointers to int32 [H][W] arrays:
+ *   labels[i][j] = the smallest row-major index i' * W + j' of the region of (i, j) - its root, canonical;
+ *   areas[i][j]  = the pixel count of the region if (i, j) is its root (labels[i][j] == i * W + j), otherwise 0.
+ * counts (nullable, needs areas; DEVICE memory, int64 [C][3], 8-byte aligned) is ACCUMULATED into, as the confusion matrices are
+ * (zero it first), over the regions of every scene whose byte c is < C:
+ *   counts[c][0] += 1     counts[c][1] += 1 if area < min_area     counts[c][2] += area if area < min_area
+ * min_area and C are read only with counts.  Four launches per chunk of scenes whatever the maps hold (label each 32 x 32 tile in
+ * LDS, join across tile seams with atomicMin on the int32 parents, flatten and sum the areas per tile, count): no block waits for
+ * another, nothing is read back, and every walk through the forest strictly lowers an index.  Integers only, and a root is the
+ * smallest index of its set, so scenes.host_regions and scenes.host_region_counts give the same bytes and counts whatever the launch
+ * or arrival order.  Everything is checked on the host before anything is launched (a violation: RUA_ERR_ARG, the message names the
+ * offender, nothing is written): connectivity 4 or 8, nscenes >= 1, no null entry in a given pointer array, 1 <= H, W and
+ * H * W < 2^31 (a label is an int32), labels and areas 4-byte aligned, with counts 1 <= min_area < 2^31 and 1 <= C <= 64, no output
+ * (labels, areas, counts) sharing a byte with a map of the call or with another output.  The scenes travel as kernel arguments, 120
+ * per launch (32 bytes each): no device-side table, no copy, no synchronisation. */
+int rua_scene_regions(const uint8_t* const* scene_map, const int32_t* scene_h, const int32_t* scene_w, int nscenes, int connectivity,
+                      int32_t* const* labels, int32_t* const* areas, int64_t min_area, int C, int64_t* counts, void* stream);
+
+/* One round of scenes.host_sieve on maps whose labels and areas rua_scene_regions produced (same maps, same connectivity, earlier on
+ * the same stream).  A region is SMALL if its byte c is < C, bit c of class_mask is set and its area is < min_area (min_area 1: none
+ * is); every other region with a byte < C is KEPT; regions of bytes >= C are never changed and never donate.  scene_out is a HOST
+ * array of nscenes device pointers to uint8 [H][W] maps:
+ *   mode RUA_SIEVE_VOID: out = 255 on the pixels of small regions, the map's byte elsewhere;
+ *   mode RUA_SIEVE_FILL: every small region takes one class for all its pixels.  One vote is cast for the byte of y per ordered
+ *     pair (x in the region, y a 4-neighbour of x inside the map and in a kept region) - 4-neighbours also under connectivity 8 -;
+ *     the class with the most votes wins, a tie goes to the lowest class, a region with no vote stays as it is.  All small regions
+ *     decide at once, from the input map.
+ * changed (nullable; DEVICE memory, one int64, 8-byte aligned) is ACCUMULATED into: the pixels whose byte changed.
+ * work (mode fill; DEVICE memory, 4-byte aligned, work_bytes >= the sum over the scenes of rua_scene_sieve_work_bytes(H, W, C))
+ * holds the votes: 12 bytes per pixel - at every region's root two uint32 vote counters, used alternately class after class, and
+ * the best count so far; the winner itself collects in scene_out at the root.  Fill takes C + 3 launches per chunk of scenes, void
+ * one, whatever the maps hold; the result does not depend on how the votes are kept.  Integers only: scenes.host_sieve gives the same
+ * bytes whatever the launch or arrival order.  Everything is checked on the host before anything is launched (RUA_ERR_ARG, the
+ * message names the offender, nothing is written): connectivity 4 or 8, 1 <= min_area < 2^31, 1 <= C <= 64, no bit >= C in
+ * class_mask, mode 0 or 1, nscenes >= 1, no null entry in a pointer array, 1 <= H, W and H * W < 2^31, the work buffer in mode fill,
+ * no output (scene_out, work, changed) sharing a byte with an input of any scene or with another output.  The scenes travel as
+ * kernel arguments, 80 per launch (48 bytes each): no device-side table, no copy, no synchronisation. */
+#define RUA_SIEVE_VOID 0
+#define RUA_SIEVE_FILL 1
+int rua_scene_sieve(const uint8_t* const* scene_map, const int32_t* scene_h, const int32_t* scene_w, int nscenes, int connectivity,
+                    int64_t min_area, int C, uint64_t class_mask, int mode, const int32_t* const* labels, const int32_t* const* areas,
+                    uint8_t* const* scene_out, void* work, int64_t work_bytes, int64_t* changed, void* stream);
+/* bytes of work one H x W scene needs in mode fill (12 H W; -1 for sizes or a C the call would refuse) */
+int64_t rua_scene_sieve_work_bytes(int H, int W, int C);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

@@ -27,7 +27,7 @@ from . import losses as LS
 from . import schedules as SC
 from .wgrad_queue import WgradQueue, WSpec
 from .scenes import (BLEND_MODES, MAP_HEADS, AffineSceneBatch, SceneBatch, blend_table, check_blend_budget, check_photo_table, check_radius,
-                     check_scales, check_tolerance, check_views, scale_table, view_rows)
+                     check_scales, check_tolerance, check_views, scale_table, sieve_params, view_rows)
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -2528,7 +2528,7 @@ class Engine:
             cap.replay()
 
     def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None, views=(0,),
-                      erode: int = 0, heads=(), on_heads=None, boundary: Optional[int] = None, scales=None, blend=None):
+                      erode: int = 0, heads=(), on_heads=None, boundary: Optional[int] = None, scales=None, blend=None, sieve=None):
         """The class map of a whole resident scene: (uint8 [H][W] prediction, int64 [C][C] confusion matrix indexed [true][pred], None
         for a pool without class maps).  scenes.predict_table covers the scene with windows `stride` apart (None: the patch) and gives
         every pixel to the window it is most central in; the windows go through the forward `batch` at a time - rua_scene_windows,
@@ -2586,9 +2586,23 @@ class Engine:
         sums do not depend on the order.  The last batch of a pass is padded with groups whose rectangle is empty; one
         rua_scene_argmax follows, erode and boundary score its map; on_batch(rows7, foot, p).  scenes.check_blend_budget keeps the
         int32 sums in range (K times the footprints over one pixel, summed over the passes, below 32768).  ValueError, before any
-        GPU work, for another value, over the budget, and with heads (blended maps of the other heads are not built)."""
+        GPU work, for another value, over the budget, and with heads (blended maps of the other heads are not built).
+        sieve: None is every path and return value above, call for call.  Otherwise a minimum mapping unit for the finished map: a
+        minimum area in pixels, or a dict {min_area, mode="fill", connectivity=4, classes=None, rounds=1} (scenes.check_sieve;
+        scenes.host_sieve is the definition).  After the window loop or rua_scene_argmax, on the compute stream, rua_scene_regions
+        labels the connected regions of the map and rua_scene_sieve removes those of fewer than min_area pixels - "fill" gives each
+        the class most of its kept 4-neighbours have, "void" turns them into 255, which no score counts (the reference's area
+        opening) - `rounds` times, from one resident map into a second and back; one rua_scene_erode call at radius 0 then counts the
+        sieved map into a fresh matrix.  The returned prediction, the confusion matrix, the matrix on the eroded ground truth and the
+        boundary counts are those of the SIEVED map, and a region report is inserted in the tuple in front of the head maps:
+        {"confusion_raw": the matrix of the un-sieved map (None without class maps), "counts": int64 [C][3], per class the regions
+        of the un-sieved map, the small ones among them and their pixels (scenes.host_region_counts), "changed": the bytes changed,
+        summed over the rounds}, fetched once at the end.  It works under any views, scales, blend, erode, boundary and heads, and
+        on a pool without class maps (only the scores need them).  ValueError, before any GPU work, for a malformed `sieve`."""
         H, W, _ = self.cfg.input_shape
         Cn = self.cfg.num_classes
+        if sieve is not None:
+            sieve = sieve_params(sieve, Cn)
         views = check_views(views, (H, W))
         erode = check_radius(erode)
         heads = self._check_map_heads(heads, norm_type)
@@ -2692,6 +2706,28 @@ class Engine:
                 on_batch(r, o, seg.t)
             if on_heads is not None:
                 on_heads(r, o, {h: v[0].t for h, v in head_maps.items()})
+        if sieve is not None:
+            # the stitched map is sieved before anything scores it: regions, then sieve, round after round between two resident maps
+            mn, _, mode, conn, mask, rounds = sieve
+            st = C.c_void_p(self._stream())
+            conf_raw = conf
+            labels, areas = (torch.empty((SH, SW), dtype=torch.int32, device=self.dev) for _ in range(2))
+            lab_ptr, area_ptr = (C.c_void_p * 1)(labels.data_ptr()), (C.c_void_p * 1)(areas.data_ptr())
+            rcounts = torch.zeros((Cn, 3), dtype=torch.int64, device=self.dev)
+            changed = torch.zeros((1,), dtype=torch.int64, device=self.dev)
+            nwork = int(L.lib().raw("rua_scene_sieve_work_bytes")(SH, SW, Cn)) if mode == 1 else 0
+            work = torch.empty((nwork // 4,), dtype=torch.int32, device=self.dev) if nwork else None
+            other = torch.empty_like(pred)
+            for k in range(rounds):
+                src_ptr, dst_ptr = (C.c_void_p * 1)(pred.data_ptr()), (C.c_void_p * 1)(other.data_ptr())
+                L.lib().call("rua_scene_regions", src_ptr, sh, sw, 1, conn, lab_ptr, area_ptr, mn, Cn, rcounts.data_ptr() if k == 0 else None, st)
+                L.lib().call("rua_scene_sieve", src_ptr, sh, sw, 1, conn, mn, Cn, mask, mode, lab_ptr, area_ptr, dst_ptr,
+                             work.data_ptr() if nwork else None, nwork, changed.data_ptr(), st)
+                pred, other = other, pred
+            pred_ptr = (C.c_void_p * 1)(pred.data_ptr())
+            if counted:
+                conf = torch.zeros((Cn, Cn), dtype=torch.int64, device=self.dev)
+                L.lib().call("rua_scene_erode", cls_ptr, sh, sw, 1, 0, None, pred_ptr, Cn, conf.data_ptr(), st)
         # what scores the stitched map is issued first, kernel after kernel on the compute stream; every fetch comes after
         if boundary is not None:
             bcounts = torch.zeros((Cn, 4), dtype=torch.int64, device=self.dev)
@@ -2700,6 +2736,9 @@ class Engine:
             conf_e = torch.zeros((Cn, Cn), dtype=torch.int64, device=self.dev)
             L.lib().call("rua_scene_erode", cls_ptr, sh, sw, 1, erode, None, pred_ptr, Cn, conf_e.data_ptr(), C.c_void_p(self._stream()))
         more = ({h: v[3].cpu().numpy() for h, v in head_maps.items()},) if heads else ()
+        if sieve is not None:
+            more = ({"confusion_raw": conf_raw.cpu().numpy() if counted else None, "counts": rcounts.cpu().numpy(),
+                     "changed": int(changed.cpu().numpy()[0])},) + more
         if boundary is not None:
             more = (bcounts.cpu().numpy(),) + more
         if erode:

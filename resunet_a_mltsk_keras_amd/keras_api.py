@@ -653,7 +653,7 @@ class Model:
         return np.concatenate(outs, axis=0)
 
     def predict_scene(self, pool, scene, stride=None, batch=8, norm_type=1, on_batch=None, views=(0,), erode=0, heads=(), on_heads=None,
-                      boundary=None, scales=None, blend=None):
+                      boundary=None, scales=None, blend=None, sieve=None):
         """Engine.predict_scene: (uint8 [H][W] class map of the pool's scene `scene`, int64 [C][C] confusion matrix [true][pred] or None
         without class maps), the windows cut, predicted and stitched on the GPU; only these two arrays come back.  views: test-time
         augmentation, a tuple of symmetry codes or a scenes.VIEW_SETS name ("none", "flips", "aug5", "all").  erode: a radius 1..16
@@ -666,27 +666,36 @@ class Model:
         all views and the resampled probabilities are summed on the GPU (scenes.host_accumulate, scenes.host_argmax); not together
         with heads; None or (1.0,) is the single-scale path.  blend: "linear" blends overlapping windows under a linear taper instead
         of giving each pixel to one window (scenes.host_accumulate_blend; stride None then means half the patch; not together with
-        heads); None changes nothing."""
+        heads); None changes nothing.  sieve: a minimum area in pixels, or a dict {min_area, mode="fill" | "void", connectivity=4 | 8,
+        classes=None, rounds=1}, removes the connected regions below that area from the finished map on the GPU before anything
+        scores it (scenes.host_sieve); every returned score is then the sieved map's, and a report {"confusion_raw", "counts",
+        "changed"} is added in front of the head maps; None changes nothing."""
         if self.engine.loss is None:                      # load_model(..., compile=False), as predict
             self.engine.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in HEADS}, weight={h: 1.0 for h in HEADS}))
         return self.engine.predict_scene(pool, scene, stride=stride, batch=batch, norm_type=norm_type, on_batch=on_batch, views=views, erode=erode,
-                                         heads=heads, on_heads=on_heads, boundary=boundary, scales=scales, blend=blend)
+                                         heads=heads, on_heads=on_heads, boundary=boundary, scales=scales, blend=blend, sieve=sieve)
 
-    def evaluate_scenes(self, pool, stride=None, batch_size=8, norm_type=1, views=(0,), erode=0, heads=(), boundary=None, scales=None, blend=None):
+    def evaluate_scenes(self, pool, stride=None, batch_size=8, norm_type=1, views=(0,), erode=0, heads=(), boundary=None, scales=None, blend=None,
+                        sieve=None):
         """predict_scene of every scene of the pool: (list of uint8 class maps, the confusion matrices summed - None without class maps);
         with erode >= 1 a third value, the matrices on the eroded ground truth summed; with boundary (a tolerance 0..16) a next
         value, the int64 [C][4] boundary counts summed over the scenes; with heads a last value, the list of the scenes'
-        {head: uint8 [H][W][Ch] map} dicts.  scales, blend: predict_scene's, for every scene."""
+        {head: uint8 [H][W][Ch] map} dicts.  scales, blend: predict_scene's, for every scene.  sieve: predict_scene's; the maps and
+        every score are then the sieved maps', and in front of the head maps comes the region report summed over the scenes
+        ({"confusion_raw": None without class maps, "counts", "changed"})."""
         heads = (heads,) if isinstance(heads, str) else tuple(heads)
-        maps, total, total_e, total_b, head_maps = [], None, None, None, []
+        maps, total, total_e, total_b, head_maps, report = [], None, None, None, [], None
         for s in range(len(pool)):
             m, cm, *more = self.predict_scene(pool, s, stride=stride, batch=batch_size, norm_type=norm_type, views=views, erode=erode, heads=heads,
-                                              boundary=boundary, scales=scales, blend=blend)
+                                              boundary=boundary, scales=scales, blend=blend, sieve=sieve)
             maps.append(m)
             if cm is not None:
                 total = cm if total is None else total + cm
             if heads:
                 head_maps.append(more.pop())
+            if sieve is not None:
+                r = more.pop()
+                report = r if report is None else {k: (None if r[k] is None else report[k] + r[k]) for k in r}
             if boundary is not None:
                 b = more.pop()
                 total_b = b if total_b is None else total_b + b
@@ -695,6 +704,8 @@ class Model:
         res = (maps, total, total_e) if erode else (maps, total)
         if boundary is not None:
             res += (total_b,)
+        if sieve is not None:
+            res += (report,)
         return res + (head_maps,) if heads else res
 
     # -- checkpoints (train_ISPRS.py:292,474-480): real HDF5 in the Keras layout, written / read by h5lite (no h5py needed) --

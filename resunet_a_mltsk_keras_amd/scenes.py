@@ -80,6 +80,14 @@ within `radius` pixels and the other way round, and boundary_scores() turns such
 rua_scene_boundary is the kernel of the first two on resident maps, ScenePool.boundary_counts() / boundary_maps() and
 Engine.predict_scene(boundary=) are its users.  Radius 0 is exact coincidence, a real tolerance: "off" is None (check_tolerance).
 
+A minimum mapping unit cleans a class map of speckle, as the reference's `prediction` does with an area opening before it scores:
+host_regions() labels the connected regions of equal bytes of a map (4- or 8-connected) with their smallest row-major index and
+gives each region's pixel count at that root, host_region_counts() counts per class the regions and the small ones among them, and
+host_sieve() removes the regions below `min_area` pixels - mode "void" turns them into 255, which every score leaves out (the
+reference's protocol), mode "fill" gives each the class most of its kept 4-neighbours have.  rua_scene_regions and
+rua_scene_sieve (csrc/regions.hip) are their kernels on resident maps, ScenePool.region_counts() / sieved_maps() and
+Engine.predict_scene(sieve=) their users; check_sieve() checks the parameters in the kernels' words.
+
 `python -m resunet_a_mltsk_keras_amd.scenes --image Image_Train.npy --reference Reference_Train.npy --dst DIR` writes a scene
 directory from the reference's two inputs (C x H x W arrays, the reference colour-coded); `--materialize DST` also writes the
 compact patch layout (compact.py) of its window table, for users who want files.
@@ -1307,6 +1315,178 @@ def boundary_scores(counts) -> dict:
     return {"precision": prec, "recall": rec, "f1": f1, "f1_mean": float(f1[have].mean()) if have.any() else float("nan")}
 
 
+# ---- connected regions and the sieve: a minimum mapping unit for class maps -------------------------------------------------------
+SIEVE_MODES = ("void", "fill")                 # the C ABI's mode 0 and 1
+MAX_ROUNDS = 4
+
+
+def _is_int(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+def _check_connectivity(fn: str, connectivity) -> int:
+    if not _is_int(connectivity) or int(connectivity) not in (4, 8):
+        raise ValueError(f"{fn}: connectivity {connectivity!r} is neither 4 nor 8")
+    return int(connectivity)
+
+
+def _check_region_map(fn: str, a, what: str = "a map") -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.size == 0:
+        raise ValueError(f"{fn}: {what} is a non-empty uint8 H x W array, got {a.dtype} {a.shape}")
+    if a.size >= 1 << 31:
+        raise ValueError(f"{fn}: {what}: size {a.shape[0]} x {a.shape[1]} (H * W < 2^31: a label is an int32 pixel index)")
+    return a
+
+
+def check_sieve(min_area, num_classes, mode="fill", connectivity=4, classes=None, rounds=1, fn: str = "rua_scene_sieve"):
+    """The parameters of a sieve as (min_area, C, mode number, connectivity, class mask, rounds) - mode 0 is "void", 1 "fill", bit c
+    of the mask is set if class c is sieved (classes None: every class below C); ValueError, in rua_scene_sieve's own words, unless
+    1 <= min_area < 2^31, 1 <= C <= 64, the mode is one of SIEVE_MODES, the connectivity 4 or 8, every class an integer in 0..C-1
+    and rounds in 1..4."""
+    if not _is_int(min_area) or not 1 <= int(min_area) < 1 << 31:
+        raise ValueError(f"{fn}: min_area {min_area!r} outside 1..2147483647")
+    if not _is_int(num_classes) or not 1 <= int(num_classes) <= MAX_CLASSES:
+        raise ValueError(f"{fn}: C {num_classes} outside 1..64")
+    C_ = int(num_classes)
+    if not isinstance(mode, str) or mode not in SIEVE_MODES:
+        raise ValueError(f"{fn}: mode {mode!r} is neither void (0) nor fill (1)")
+    conn = _check_connectivity(fn, connectivity)
+    if classes is None:
+        mask = (1 << C_) - 1
+    else:
+        if isinstance(classes, (str, bytes)) or _is_int(classes):
+            classes = (classes,)
+        mask = 0
+        for c in classes:
+            if not _is_int(c) or not 0 <= int(c) < C_:
+                raise ValueError(f"{fn}: class_mask names class {c!r}, outside 0..{C_ - 1}")
+            mask |= 1 << int(c)
+    if not _is_int(rounds) or not 1 <= int(rounds) <= MAX_ROUNDS:
+        raise ValueError(f"{fn}: rounds {rounds!r} outside 1..{MAX_ROUNDS}")
+    return int(min_area), C_, SIEVE_MODES.index(mode), conn, mask, int(rounds)
+
+
+def sieve_params(sieve, num_classes):
+    """Engine.predict_scene's `sieve` as check_sieve's tuple: an integer is min_area with mode "fill", connectivity 4, every class
+    and one round; a dict may hold min_area (required), mode, connectivity, classes and rounds.  ValueError for anything else."""
+    if _is_int(sieve):
+        return check_sieve(sieve, num_classes)
+    if not isinstance(sieve, dict):
+        raise ValueError(f"sieve {sieve!r}: None, a minimum area in pixels or a dict of min_area, mode, connectivity, classes, rounds")
+    unknown = sorted(set(sieve) - {"min_area", "mode", "connectivity", "classes", "rounds"})
+    if unknown:
+        raise ValueError(f"sieve: unknown key {unknown[0]!r} (min_area, mode, connectivity, classes, rounds)")
+    if "min_area" not in sieve:
+        raise ValueError("sieve: the dict needs min_area")
+    return check_sieve(sieve["min_area"], num_classes, sieve.get("mode", "fill"), sieve.get("connectivity", 4), sieve.get("classes"),
+                       sieve.get("rounds", 1))
+
+
+def host_regions(class_map: np.ndarray, connectivity: int = 4):
+    """The numpy definition of what rua_scene_regions writes: (labels int32 [H][W], areas int32 [H][W]).  A region is a maximal set
+    of pixels of equal byte value connected through 4-neighbours (connectivity 4) or 8-neighbours (8); bytes are compared raw, so
+    "no class" bytes form regions like any other, and pixels outside the map do not exist.  labels[i, j] is the smallest row-major
+    index i' * W + j' of the pixel's region - its root, canonical, so label maps compare bit for bit -, areas holds the region's
+    pixel count at the root and 0 everywhere else.  H * W < 2^31.
+    Rows are cut into runs of equal bytes; a union-find over the runs (the larger root always points to the smaller) joins the
+    runs of neighbouring rows that touch, and a run's root is the first pixel of the first run of its set."""
+    m = _check_region_map("rua_scene_regions", class_map)
+    conn = _check_connectivity("rua_scene_regions", connectivity)
+    H, W = m.shape
+    start = np.ones((H, W), bool)
+    start[:, 1:] = m[:, 1:] != m[:, :-1]
+    run = (np.cumsum(start.ravel()) - 1).reshape(H, W)                   # the run of every pixel, numbered in row-major order
+    first = np.flatnonzero(start.ravel())                                 # ... and the first pixel of every run: ascending
+    pairs = [np.stack([run[1:][m[1:] == m[:-1]], run[:-1][m[1:] == m[:-1]]], 1)]
+    if conn == 8:
+        d = m[1:, 1:] == m[:-1, :-1]
+        pairs.append(np.stack([run[1:, 1:][d], run[:-1, :-1][d]], 1))
+        d = m[1:, :-1] == m[:-1, 1:]
+        pairs.append(np.stack([run[1:, :-1][d], run[:-1, 1:][d]], 1))
+    parent = list(range(len(first)))
+
+    def find(a: int) -> int:
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    for a, b in np.unique(np.concatenate(pairs), axis=0).tolist():
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)
+    root = np.fromiter((find(a) for a in range(len(first))), np.int64, len(first))
+    labels = first[root][run]
+    areas = np.bincount(labels.ravel(), minlength=H * W).reshape(H, W)
+    return labels.astype(np.int32), areas.astype(np.int32)
+
+
+def host_region_counts(class_map: np.ndarray, min_area: int, num_classes: int, connectivity: int = 4) -> np.ndarray:
+    """The numpy definition of what rua_scene_regions adds to its counts, int64 [C][3]: per class c < C the regions of byte c
+    (host_regions), how many of them have fewer than min_area pixels, and how many pixels those small regions hold."""
+    mn, C_, _, conn, _, _ = check_sieve(min_area, num_classes, connectivity=connectivity, fn="rua_scene_regions")
+    m = _check_region_map("rua_scene_regions", class_map)
+    _, areas = host_regions(m, conn)
+    at = areas > 0
+    byte, area = m[at].astype(np.int64), areas[at].astype(np.int64)
+    keep = byte < C_
+    byte, area = byte[keep], area[keep]
+    small = area < mn
+    out = np.zeros((C_, 3), np.int64)
+    out[:, 0] = np.bincount(byte, minlength=C_)
+    out[:, 1] = np.bincount(byte[small], minlength=C_)
+    out[:, 2] = np.bincount(byte[small], weights=area[small], minlength=C_).astype(np.int64)
+    return out
+
+
+def _sieve_round(m: np.ndarray, mn: int, C_: int, mode: int, conn: int, mask: int) -> np.ndarray:
+    H, W = m.shape
+    labels, areas = host_regions(m, conn)
+    sieved = np.array([(mask >> c) & 1 for c in range(256)], bool)       # bits >= C are never set
+    small = sieved[m] & (areas.ravel()[labels] < mn)
+    out = m.copy()
+    if mode == 0:
+        out[small] = 255
+        return out
+    kept = (m < C_) & ~small
+    roots, slot = np.unique(labels[small], return_inverse=True)          # the small regions, and the region of every small pixel
+    if not len(roots):
+        return out
+    votes = np.zeros((len(roots), C_), np.int64)
+    slot_of = np.full((H, W), -1, np.int64)
+    slot_of[small] = np.asarray(slot).reshape(-1)
+    for dy, dx in ((-1, 0), (1, 0), (0, -1), (0, 1)):                    # x at [i0:i1, j0:j1], its neighbour y at the same plus (dy, dx)
+        i0, i1, j0, j1 = max(0, -dy), min(H, H - dy), max(0, -dx), min(W, W - dx)
+        pair = small[i0:i1, j0:j1] & kept[i0 + dy:i1 + dy, j0 + dx:j1 + dx]
+        np.add.at(votes, (slot_of[i0:i1, j0:j1][pair], m[i0 + dy:i1 + dy, j0 + dx:j1 + dx][pair].astype(np.int64)), 1)
+    winner = votes.argmax(1).astype(np.uint8)                            # the first maximum: a tie goes to the lowest class
+    voted = votes.sum(1) > 0
+    s = slot_of[small]
+    out[small] = np.where(voted[s], winner[s], m[small])
+    return out
+
+
+def host_sieve(class_map: np.ndarray, min_area: int, num_classes: int, mode: str, connectivity: int = 4, classes=None,
+               rounds: int = 1) -> np.ndarray:
+    """The numpy definition of what `rounds` rounds of rua_scene_regions and rua_scene_sieve leave, uint8 [H][W].  A region
+    (host_regions) is SMALL if its byte c is < C, c is in `classes` (None: every class) and it has fewer than min_area pixels -
+    min_area 1 is the identity, and a region of exactly min_area pixels stays, as under skimage's area_opening.  Every other
+    region with a byte < C is KEPT, those of a class outside `classes` too; regions of bytes >= C are never changed and never
+    donate.  mode "void": the pixels of small regions become 255, so they drop out of every score through the p < C rule of the
+    confusion and boundary counts (the reference's protocol; restricted to class 1 of a binary map it is area_opening followed by
+    the exclusion).  mode "fill": every small region R takes one class for all its pixels - one vote is cast for the byte of y per
+    ordered pair (x in R, y a 4-neighbour of x inside the map and in a kept region), also under connectivity 8; the class with the
+    most votes wins, a tie goes to the lowest class, and a region with no vote stays as it is.  All small regions decide at once,
+    from the input map.  rounds (1..4) applies the whole operation again to its own output: a second round removes speckle nested
+    inside speckle, which after round 1 lies inside a kept region; further rounds on a stable map change nothing."""
+    mn, C_, md, conn, mask, n = check_sieve(min_area, num_classes, mode, connectivity, classes, rounds)
+    out = _check_region_map("rua_scene_sieve", class_map)
+    for _ in range(n):
+        out = _sieve_round(out, mn, C_, md, conn, mask)
+    return out
+
+
 def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]]) -> int:
     """Scenes are uint8 H x W x C with one C for all, class maps uint8 H x W of their image's size.  Returns C."""
     if len(images) < 1:
@@ -1557,6 +1737,95 @@ class ScenePool:
                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
             got = out.cpu().numpy()
         return [got[first[s]:first[s + 1]].reshape(self.shapes[s]).copy() for s in range(len(self))]
+
+    def _check_region_maps(self, fn: str, maps) -> list:
+        maps = list(maps)
+        if len(maps) != len(self):
+            raise ValueError(f"{fn}: {len(maps)} maps for {len(self)} scenes (one per scene, None to skip one)")
+        out = []
+        for s, m in enumerate(maps):
+            if m is not None:
+                m = np.ascontiguousarray(_check_region_map(fn, m, f"scene {s}: the map"))
+                if m.shape != self.shapes[s]:
+                    raise ValueError(f"{fn}: scene {s}: the map is {m.shape}, the scene {self.shapes[s]}")
+            out.append(m)
+        return out
+
+    def _region_buffers(self, maps):
+        """One upload of these maps, and int32 labels and areas beside them: (scenes given, device tensors map / labels / areas, the
+        ctypes arrays of per-scene pointers map / labels / areas / heights / widths, the first pixel of every scene in the buffers)."""
+        import torch
+        given = [s for s, m in enumerate(maps) if m is not None]
+        first = np.concatenate([[0], np.cumsum([maps[s].size for s in given])]).astype(np.int64)
+        dev = torch.from_numpy(np.concatenate([maps[s].ravel() for s in given])).to(self.device)
+        labels, areas = (torch.empty((int(first[-1]),), dtype=torch.int32, device=self.device) for _ in range(2))
+        n = len(given)
+        ptrs = lambda t, unit: (C.c_void_p * n)(*[t.data_ptr() + unit * int(o) for o in first[:-1]])
+        hs, ws = (C.c_int32 * n)(*[self.shapes[s][0] for s in given]), (C.c_int32 * n)(*[self.shapes[s][1] for s in given])
+        return given, (dev, labels, areas), (ptrs(dev, 1), ptrs(labels, 4), ptrs(areas, 4), hs, ws), first
+
+    def region_counts(self, maps=None, *, min_area: int, num_classes: int, connectivity: int = 4) -> np.ndarray:
+        """int64 [n][C][3], host_region_counts of every scene: per class the connected regions, those of fewer than min_area pixels and
+        the pixels these hold - of the pool's class maps (maps None), or of maps[s], a uint8 [H][W] map per scene of the pool that
+        came from a file (a None entry skips its scene: its rows stay 0).  The maps are uploaded in one copy, rua_scene_regions is
+        called once per counted scene into that scene's [C][3] cells of one device buffer (a call sums its scenes into one set of
+        counts), and the buffer is fetched once; a "cpu" pool returns the host definition."""
+        fn = "rua_scene_regions"
+        mn, C_, _, conn, _, _ = check_sieve(min_area, num_classes, connectivity=connectivity, fn=fn)
+        if maps is None:
+            if self.class_maps is None:
+                raise ValueError("region_counts needs maps, or the pool's class maps")
+            maps = self.class_maps
+        maps = self._check_region_maps(fn, maps)
+        if self.device.type != "cuda":
+            out = np.zeros((len(self), C_, 3), np.int64)
+            for s, m in enumerate(maps):
+                if m is not None:
+                    out[s] = host_region_counts(m, mn, C_, conn)
+            return out
+        import torch
+        from . import _lib as L
+        with torch.cuda.device(self.device):
+            counts = torch.zeros((len(self), C_, 3), dtype=torch.int64, device=self.device)
+            if all(m is None for m in maps):
+                return counts.cpu().numpy()
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            given, keep, (mp, lp, ap, hs, ws), _ = self._region_buffers(maps)
+            one = lambda a, k, t: (t * 1)(a[k])
+            for k, s in enumerate(given):
+                L.lib().call(fn, one(mp, k, C.c_void_p), one(hs, k, C.c_int32), one(ws, k, C.c_int32), 1, conn, one(lp, k, C.c_void_p),
+                             one(ap, k, C.c_void_p), mn, C_, counts[s].data_ptr(), st)
+            return counts.cpu().numpy()
+
+    def sieved_maps(self, maps, min_area: int, num_classes: int, mode: str, connectivity: int = 4, classes=None, rounds: int = 1) -> List[np.ndarray]:
+        """host_sieve of maps[s], a uint8 [H][W] map per scene of the pool (a None entry skips its scene and gives None), as a list of
+        uint8 maps: one upload of all maps, `rounds` times one rua_scene_regions and one rua_scene_sieve call over all of them
+        between two device buffers, and one fetch; a "cpu" pool returns the host definition."""
+        fn = "rua_scene_sieve"
+        mn, C_, md, conn, mask, n = check_sieve(min_area, num_classes, mode, connectivity, classes, rounds)
+        maps = self._check_region_maps(fn, maps)
+        if self.device.type != "cuda":
+            return [None if m is None else host_sieve(m, mn, C_, mode, conn, classes, n) for m in maps]
+        if all(m is None for m in maps):
+            return [None] * len(maps)
+        import torch
+        from . import _lib as L
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            given, (dev, labels, areas), (mp, lp, ap, hs, ws), first = self._region_buffers(maps)
+            other = torch.empty_like(dev)
+            op = (C.c_void_p * len(given))(*[other.data_ptr() + int(o) for o in first[:-1]])
+            nwork = sum(int(L.lib().raw("rua_scene_sieve_work_bytes")(*self.shapes[s], C_)) for s in given) if md == 1 else 0
+            work = torch.empty((nwork // 4,), dtype=torch.int32, device=self.device) if nwork else None
+            for _ in range(n):
+                L.lib().call("rua_scene_regions", mp, hs, ws, len(given), conn, lp, ap, mn, C_, None, st)
+                L.lib().call(fn, mp, hs, ws, len(given), conn, mn, C_, mask, md, lp, ap, op, work.data_ptr() if nwork else None, nwork, None, st)
+                dev, other, mp, op = other, dev, op, mp
+            got = dev.cpu().numpy()
+        out = [None] * len(maps)
+        for k, s in enumerate(given):
+            out[s] = got[first[k]:first[k + 1]].reshape(self.shapes[s]).copy()
+        return out
 
     def predict_table(self, scene: int, stride: Optional[int] = None):
         """predict_table of scene `scene` with the pool's patch (stride None: the patch, non-overlapping windows), rows naming it."""
