@@ -1,7 +1,7 @@
 """Evaluation of a trained model on whole scenes, on the GPU: what test_ISPRS.py does for the reference's test tile (patches,
 predict, arg-max, metrics, mosaic), for a scene directory (resunet_a_mltsk_keras_amd.scenes: scenes/<name>.npy,
 labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views, --scales, --blend, --erode_boundary,
---boundary_f1, --sieve and --head_maps.
+--boundary_f1, --sieve, --pr_curve and --head_maps.
 
 Every scene stays on the GPU, is covered by windows --stride apart (default: the patch; the last window flush with the border, so
 nothing is left unpredicted), every pixel is predicted from the window it is most central in, and Model.predict_scene brings back
@@ -48,6 +48,17 @@ pixels left out of the score).  The written map and every block of scores are th
 the un-sieved map (per class: regions, regions below N pixels, their pixels) and the pixels changed are printed and
 `region_counts_<name>.npy` (int64 C x 3) is written; after the sieved scores a block `Before the sieve` prints those of the raw map;
 the returned dict gains `confusion_matrix_raw`, `region_counts` and `sieve_changed`.
+
+--pr_curve C [--pr_thresholds T ...] [--pr_min_area A] [--pr_connectivity 4|8] [--pr_opened yes] also sweeps a threshold over the
+stitched probability of class C instead of judging the arg-max map at one operating point - the reference's second protocol
+(matrics_AA_recall): at every level (all 255 bytes, or --pr_thresholds as probabilities in (0, 1] or bytes 1..255) the probability
+is binarised, the connected regions of fewer than A pixels are removed and left out of the count (an area opening; A = 1: none),
+and class-map bytes >= --num_classes are counted nowhere.  One opened map and one histogram per scene, built on the GPU
+(scenes.host_area_open, scenes.host_sweep_hist), give every level at once.  Per scene and summed, a table of threshold, recall,
+precision, F1 and alarm area at up to ten evenly spaced levels and the average precision are printed; `pr_hist_<name>.npy` (int64
+2 x 2 x 256), `pr_curve.npy` (float64 9 x T of the sum: level, tp, fp, fn, removed, recall, precision, f1, alarm area) and, with
+--pr_opened yes, `pr_opened_<name>.npy` (uint8 H x W) are written; the returned dict gains `pr_hist`, `pr_levels`, `pr_scores` and
+`average_precision`.  Not together with --scales or --blend.
 
 --head_maps HEAD [HEAD ...] also writes whole-scene maps of the named heads (`seg`, `bound`, `dist`, `color`, `color_rgb`; what
 test_ISPRS.py:285-414 displays per patch): `pred_<head>_<name>.npy`, uint8 H x W x Ch - the head's output averaged over the views,
@@ -112,6 +123,13 @@ def build_parser():
     parser.add_argument("--sieve_connectivity", type=int, default=4, metavar="4|8", help="what connects the pixels of a region: 4- or 8-neighbours")
     parser.add_argument("--sieve_classes", nargs="+", type=int, default=None, metavar="c", help="sieve only regions of these classes (default: all)")
     parser.add_argument("--sieve_rounds", type=int, default=1, metavar="R", help="apply the sieve R times (1..4): a second round removes speckle nested in speckle")
+    parser.add_argument("--pr_curve", type=int, default=None, metavar="C",
+                        help="also sweep a threshold over the probability of class C: recall, precision, F1, alarm area, average precision; default: off")
+    parser.add_argument("--pr_thresholds", nargs="+", type=float, default=None, metavar="T",
+                        help="the thresholds of --pr_curve: probabilities in (0, 1], or bytes 1..255 (default: all 255 bytes)")
+    parser.add_argument("--pr_min_area", type=int, default=1, metavar="A", help="area opening of every binarised map: regions below A pixels leave the count")
+    parser.add_argument("--pr_connectivity", type=int, default=4, metavar="4|8", help="what connects the pixels of a region: 4- or 8-neighbours")
+    parser.add_argument("--pr_opened", type=_yes, default=False, help="also write the opened map of every scene")
     parser.add_argument("--head_maps", nargs="+", default=[], metavar="HEAD",
                         help="also write uint8 whole-scene maps of these heads: seg, bound, dist, color, color_rgb (default: none)")
     return parser
@@ -145,6 +163,35 @@ def parse_scales(zooms, patch, head_maps=()):
     return tuple(zooms)
 
 
+def parse_sweep(args):
+    """--pr_curve and its companions as predict_scene's `sweep` dict (None: absent); thresholds above 1 are bytes."""
+    from resunet_a_mltsk_keras_amd import scenes
+    if args.pr_curve is None:
+        return None
+    if args.scales is not None or args.blend is not None:
+        raise SystemExit("--pr_curve excludes --scales and --blend: the probabilities then live in an int32 accumulator, no maps of the heads are built")
+    thr = args.pr_thresholds
+    if thr is not None:
+        thr = [int(t) if t > 1 and float(t).is_integer() else float(t) for t in thr]
+    sweep = dict(positive=args.pr_curve, thresholds=thr, min_area=args.pr_min_area, connectivity=args.pr_connectivity, opened=bool(args.pr_opened))
+    try:
+        scenes.sweep_params(sweep, args.num_classes)
+    except ValueError as exc:
+        raise SystemExit(f"--pr_curve: {exc}") from None
+    return sweep
+
+
+def print_curve(title, scores):
+    """threshold / recall / precision / F1 / alarm area at up to ten evenly spaced levels of the curve, and the average precision"""
+    n = len(scores["levels"])
+    rows = sorted(set(np.rint(np.linspace(0, n - 1, min(n, 10))).astype(int).tolist()))
+    print(f'{title}: average precision {scores["average_precision"]:.6f}')
+    print('  threshold   recall  precision       F1  alarm area')
+    for k in rows:
+        print(f'  {int(scores["levels"][k]):3d} ({int(scores["levels"][k]) / 255:.3f}) {scores["recall"][k]:8.4f} {scores["precision"][k]:10.4f} '
+              f'{scores["f1"][k]:8.4f} {scores["alarm_area"][k]:11.6f}')
+
+
 def write_ppm(path, rgb):
     h, w = rgb.shape[:2]
     with open(path, 'wb') as f:                                                               # dependency-free image
@@ -170,6 +217,7 @@ def main(argv=None):
             scenes.sieve_params(sieve, args.num_classes)
         except ValueError as exc:
             raise SystemExit(f"--sieve: {exc}") from None
+    sweep = parse_sweep(args)
     heads = tuple(args.head_maps)
     scales = parse_scales(args.scales, args.patch_size, heads)
     if args.blend is not None and heads:
@@ -208,6 +256,7 @@ def main(argv=None):
     total_boundary = np.zeros((args.num_classes, 4), np.int64)
     total_raw, total_regions, total_changed = np.zeros_like(total), np.zeros((args.num_classes, 3), np.int64), 0
     all_head_maps, mae_sum, mae_n = [], 0.0, 0
+    total_hist = np.zeros((2, 2, 256), np.int64)
     print('=' * 40)
     print('[TEST]')
     print(f'views: {" ".join(str(c) for c in views)} ({len(views)} per window)')
@@ -224,8 +273,15 @@ def main(argv=None):
             json.dump({"views": list(views), "scales": None if scales is None else list(scales), "stride": args.stride, "blend": args.blend}, f)
     for s, name in enumerate(names):
         pred, cm, *more = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type, views=views,
-                                              erode=erode, heads=heads, boundary=boundary, scales=scales, blend=args.blend, sieve=sieve)
+                                              erode=erode, heads=heads, boundary=boundary, scales=scales, blend=args.blend, sieve=sieve, sweep=sweep)
         head_maps = more.pop() if heads else {}
+        if sweep is not None:
+            swept = more.pop()
+            total_hist += swept["hist"]
+            np.save(os.path.join(args.output_path, f'pr_hist_{name}.npy'), swept["hist"])
+            if swept["opened"] is not None:
+                np.save(os.path.join(args.output_path, f'pr_opened_{name}.npy'), swept["opened"])
+            print_curve(f'scene {name}: class {args.pr_curve}, min_area {args.pr_min_area}', scenes.sweep_scores(swept["hist"], swept["levels"]))
         if sieve is not None:
             report = more.pop()
             total_raw += report["confusion_raw"]
@@ -300,6 +356,13 @@ def main(argv=None):
         print('Mean F1score: ', b["f1_mean"])
         res.update(boundary_counts=total_boundary, boundary_precision=b["precision"], boundary_recall=b["recall"], boundary_f1=b["f1"],
                    boundary_f1_mean=b["f1_mean"])
+    if sweep is not None:
+        sc = scenes.sweep_scores(total_hist, swept["levels"])
+        print()
+        print_curve(f'Precision-recall sweep of class {args.pr_curve} (min_area {args.pr_min_area}, connectivity {args.pr_connectivity}, {len(sc["levels"])} levels)', sc)
+        np.save(os.path.join(args.output_path, 'pr_curve.npy'),
+                np.stack([np.asarray(sc[k], np.float64) for k in ("levels", "tp", "fp", "fn", "removed", "recall", "precision", "f1", "alarm_area")]))
+        res.update(pr_hist=total_hist, pr_levels=sc["levels"], pr_scores=sc, average_precision=sc["average_precision"])
     if heads:
         res["head_maps"] = all_head_maps
         res["color_mae"] = mae_sum / mae_n if mae_n else None

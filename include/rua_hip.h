@@ -963,6 +963,44 @@ int rua_scene_sieve(const uint8_t* const* scene_map, const int32_t* scene_h, con
 /* bytes of work one H x W scene needs in mode fill (12 H W; -1 for sizes or a C the call would refuse) */
 int64_t rua_scene_sieve_work_bytes(int H, int W, int C);
 
+/* ---- the precision-recall sweep of one class's probabilities (scenes.py, sweep_levels / host_area_open / host_sweep_hist /
+ * sweep_scores; the reference's matrics_AA_recall binarises at about 50 thresholds and area-opens each binary map) -----------------
+ * scene_prob / scene_h / scene_w are HOST arrays of nscenes entries.  scene_prob[s] is a device pointer to the first byte of ONE
+ * channel of a uint8 [H][W][pix_stride] map (1 <= pix_stride <= 64): pixel (i, j) is read at scene_prob[s][(i * W + j) * pix_stride],
+ * so the seg map of rua_scene_stitch_maps is read where it lies; pix_stride 1 is a dense [H][W] map.  levels is a HOST array of T
+ * bytes, strictly descending, each in 1..255; level t stands for "byte >= t".
+ * rua_scene_area_open writes the OPENED map into scene_open (HOST array of device pointers to dense uint8 [H][W] maps):
+ *   open[x] = the largest listed level t such that x lies in a connected component (connectivity 4 or 8) of {prob >= t} that has at
+ *             least min_area pixels; 0 if there is none.
+ * Thresholding commutes with the area opening and the kept sets are nested, so {open >= t} IS the area opening of {prob >= t} at
+ * every listed t: one map serves the whole curve.  min_area 1: one streaming pass through a 256-entry table (the largest listed
+ * level <= the byte), labels and areas are not read and may be null.  min_area > 1: labels and areas are work arrays (HOST arrays of
+ * nscenes device pointers to int32 [H][W], 4-byte aligned, contents undefined afterwards); open is zeroed and, level after level, only
+ * the still unsettled pixels U = {prob >= t and open == 0} are labelled: a block per 32 x 32 tile leaves at once if the tile holds
+ * none, otherwise labels U in LDS; tile seams are joined with atomicMin on the int32 parents; a flatten pass sums the areas per tile
+ * and marks (bit 31 of the areas word) the roots of components that touch a settled pixel; a last pass writes t on the pixels of U
+ * whose component has min_area pixels or the mark.  One launch to zero and four per level and chunk of scenes, whatever the maps
+ * hold; no block waits for another, nothing is read back, every walk through the forest strictly lowers an index.
+ * rua_scene_sweep_hist ACCUMULATES into hist (DEVICE memory, int64 [2][2][256], 8-byte aligned; zero it first), over the pixels x of
+ * every scene with scene_cls[s][x] < C (scene_cls: HOST array of device pointers to dense uint8 [H][W] class maps):
+ *   hist[0][k][prob[x]] += 1      hist[1][k][open[x]] += 1      k = 1 if cls[x] == positive, else 0
+ * scene_open null stands for prob itself (no area opening).  Suffix sums over the last index give TP, FP, FN and the pixels the
+ * opening removed at every threshold at once (scenes.sweep_scores).  Integers only: scenes.host_area_open and scenes.host_sweep_hist
+ * give the same bytes and counts whatever the launch or arrival order.
+ * Everything is checked on the host before anything is launched (a violation: RUA_ERR_ARG, the message names the offender, nothing is
+ * written): 1 <= T <= 255 and the levels as above, 1 <= min_area < 2^31, connectivity 4 or 8, 1 <= pix_stride <= 64, 1 <= C <= 64,
+ * 0 <= positive < C, nscenes >= 1, no null entry in a required array, 1 <= H, W and H * W < 2^31, the work arrays when min_area > 1,
+ * hist's alignment, no output (open, labels, areas, hist) sharing a byte with an input of any scene or with another output.  The
+ * footprint of scene_prob[s] runs from its first byte to the byte of its last pixel, (H * W - 1) * pix_stride + 1 bytes: the other
+ * channels' bytes beyond it belong to the map, not to this channel.  The scenes travel as kernel arguments, 96 per launch of the
+ * labelling kernels (40 bytes each), 120 of the table and histogram kernels: no device-side table, no copy, no synchronisation. */
+int rua_scene_area_open(const uint8_t* const* scene_prob, const int32_t* scene_h, const int32_t* scene_w, int nscenes, int pix_stride,
+                        const uint8_t* levels, int T, int64_t min_area, int connectivity, uint8_t* const* scene_open,
+                        int32_t* const* labels, int32_t* const* areas, void* stream);
+int rua_scene_sweep_hist(const uint8_t* const* scene_prob, const uint8_t* const* scene_open, const uint8_t* const* scene_cls,
+                         const int32_t* scene_h, const int32_t* scene_w, int nscenes, int pix_stride, int positive, int C,
+                         int64_t* hist, void* stream);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

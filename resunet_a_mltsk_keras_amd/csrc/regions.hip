@@ -31,9 +31,9 @@
 // and zeroes that plane for launch c + 1.  A last launch copies out[root] to the region's pixels and counts the changed bytes.
 // C + 3 launches, whatever the map holds.  A count fits 32 bits: a region with a vote has a kept neighbour region, which is larger
 // than it, so it holds fewer than H * W / 2 < 2^30 pixels and casts at most four votes per pixel.
-#include "common.h"
-#include <algorithm>
-#include <vector>
+//
+// The forest's walks and unions, row_breaks and the overlap check live in unionfind.h, which sweep.hip shares.
+#include "unionfind.h"
 
 namespace {
 
@@ -51,54 +51,6 @@ struct RegArgs {
 };
 static_assert(sizeof(RegScene) == 32 && sizeof(RegArgs) <= 4096, "kernel arguments are limited to 4 KiB");
 
-// ---- the forest in LDS (a tile) ---------------------------------------------------------------------------------------------------
-// The root of x.  P[y] <= y for every y, so each step goes to a strictly smaller index: at most x steps.
-__device__ __forceinline__ int lds_find(const int* P, int x) {
-  for (;;) {
-    const int q = __hip_atomic_load(P + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (q == x) return x;
-    x = q;
-  }
-}
-// Join the sets of a and b.  With a > b the two roots, atomicMin(P[a], b) links a below b if a still was a root (it returns a); if
-// not, a had meanwhile been given the parent `old` < a and now points to min(old, b), and what remains is to join old and b.  The
-// larger of the two indices in hand is strictly smaller in every retry (old < a and b < a), so the loop ends.
-__device__ __forceinline__ void lds_union(int* P, int a, int b) {
-  for (;;) {
-    a = lds_find(P, a);
-    b = lds_find(P, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(P + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
-// ---- the same forest in global memory (a scene) -----------------------------------------------------------------------------------
-__device__ __forceinline__ int g_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// parent[y] <= y for every y - regions_tile writes it so and atomicMin only lowers -, so each step goes to a strictly smaller
-// index: at most x steps.  A stale parent is an earlier one: larger, and still above the root.
-__device__ __forceinline__ int g_find(const int32_t* P, int x) {
-  for (;;) {
-    const int q = g_load(P + x);
-    if (q == x) return x;
-    x = q;
-  }
-}
-// as lds_union: the larger index in hand strictly falls with every retry
-__device__ __forceinline__ void g_union(int32_t* P, int a, int b) {
-  for (;;) {
-    a = g_find(P, a);
-    b = g_find(P, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(P + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
 // the tile of a block: false for the whole block when the scene has no such tile (a smaller scene of the chunk)
 struct Tile { int i0, j0, th, tw; };
 __device__ __forceinline__ bool tile_of(const RegScene& sc, Tile& t) {
@@ -108,13 +60,6 @@ __device__ __forceinline__ bool tile_of(const RegScene& sc, Tile& t) {
   t.i0 = ty * RG_T; t.j0 = tx * RG_T;
   t.th = min(RG_T, sc.H - t.i0); t.tw = min(RG_T, sc.W - t.j0);
   return true;
-}
-
-// Bit x of the result: column x of this lane's tile row starts a run (brk of the lane that holds it).  All 64 lanes call it; a
-// wave holds two tile rows, the lane's own is the half its bit 5 names.
-__device__ __forceinline__ uint32_t row_breaks(bool brk) {
-  const unsigned long long m = __ballot(brk);
-  return (uint32_t)(m >> (threadIdx.x & 32));
 }
 
 __global__ __launch_bounds__(256) void regions_tile(RegArgs a) {
@@ -374,41 +319,10 @@ __global__ __launch_bounds__(256) void sieve_fill_apply(SieveArgs a) {
 }
 
 // ---- argument checks --------------------------------------------------------------------------------------------------------------
-#define RG_TRY(call) do { const int rc_ = (call); if (rc_ != RUA_OK) return rc_; } while (0)
-
-int rg_check_size(const char* fn, int s, int h, int w) {
-  RUA_CHECK_ARG(h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31),
-                "%s: scene %d: size %d x %d (H * W < 2^31: a label is an int32 pixel index)", fn, s, h, w);
-  return RUA_OK;
-}
-
 int rg_check_params(const char* fn, int connectivity, int64_t min_area, int C) {
   RUA_CHECK_ARG(connectivity == 4 || connectivity == 8, "%s: connectivity %d is neither 4 nor 8", fn, connectivity);
   RUA_CHECK_ARG(min_area >= 1 && min_area < ((int64_t)1 << 31), "%s: min_area %lld outside 1..2147483647", fn, (long long)min_area);
   RUA_CHECK_ARG(C >= 1 && C <= RG_MAXC, "%s: C %d outside 1..64", fn, C);
-  return RUA_OK;
-}
-
-// a byte range that a call reads (out == false) or writes
-struct RgRange { uintptr_t at; uint64_t n; int scene; const char* name; bool out; };
-
-// No output may share a byte with an input or with another output; inputs may share.  One sweep over the ranges in address order:
-// a range that starts before the furthest end so far of the other kind - or, for an output, of either kind - overlaps the range
-// that set that end.
-int rg_check_overlap(const char* fn, std::vector<RgRange>& v) {
-  std::sort(v.begin(), v.end(), [](const RgRange& x, const RgRange& y) { return x.at < y.at; });
-  const RgRange* far[2] = {nullptr, nullptr};    // the range that ends furthest so far: [0] among the inputs, [1] among the outputs
-  for (const RgRange& x : v) {
-    for (int k = x.out ? 0 : 1; k < 2; ++k) {
-      const RgRange* f = far[k];
-      if (!f || x.at >= f->at + f->n) continue;
-      char xs[48], fs[48];
-      if (x.scene < 0) snprintf(xs, sizeof(xs), "%s", x.name); else snprintf(xs, sizeof(xs), "scene %d: %s", x.scene, x.name);
-      if (f->scene < 0) snprintf(fs, sizeof(fs), "%s", f->name); else snprintf(fs, sizeof(fs), "scene %d: %s", f->scene, f->name);
-      RUA_CHECK_ARG(false, "%s: %s overlaps %s (an output may share no byte with an input or another output of the call)", fn, xs, fs);
-    }
-    if (!far[x.out] || x.at + x.n > far[x.out]->at + far[x.out]->n) far[x.out] = &x;
-  }
   return RUA_OK;
 }
 

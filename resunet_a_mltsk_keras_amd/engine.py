@@ -27,7 +27,7 @@ from . import losses as LS
 from . import schedules as SC
 from .wgrad_queue import WgradQueue, WSpec
 from .scenes import (BLEND_MODES, MAP_HEADS, AffineSceneBatch, SceneBatch, blend_table, check_blend_budget, check_photo_table, check_radius,
-                     check_scales, check_tolerance, check_views, scale_table, sieve_params, view_rows)
+                     check_scales, check_tolerance, check_views, scale_table, sieve_params, sweep_params, view_rows)
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -2528,7 +2528,7 @@ class Engine:
             cap.replay()
 
     def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None, views=(0,),
-                      erode: int = 0, heads=(), on_heads=None, boundary: Optional[int] = None, scales=None, blend=None, sieve=None):
+                      erode: int = 0, heads=(), on_heads=None, boundary: Optional[int] = None, scales=None, blend=None, sieve=None, sweep=None):
         """The class map of a whole resident scene: (uint8 [H][W] prediction, int64 [C][C] confusion matrix indexed [true][pred], None
         for a pool without class maps).  scenes.predict_table covers the scene with windows `stride` apart (None: the patch) and gives
         every pixel to the window it is most central in; the windows go through the forward `batch` at a time - rua_scene_windows,
@@ -2598,11 +2598,27 @@ class Engine:
         {"confusion_raw": the matrix of the un-sieved map (None without class maps), "counts": int64 [C][3], per class the regions
         of the un-sieved map, the small ones among them and their pixels (scenes.host_region_counts), "changed": the bytes changed,
         summed over the rounds}, fetched once at the end.  It works under any views, scales, blend, erode, boundary and heads, and
-        on a pool without class maps (only the scores need them).  ValueError, before any GPU work, for a malformed `sieve`."""
+        on a pool without class maps (only the scores need them).  ValueError, before any GPU work, for a malformed `sieve`.
+        sweep: None is every path and return value above, call for call.  Otherwise the precision-recall sweep of one class's
+        probabilities (the reference's second protocol, matrics_AA_recall): a class index, or a dict {positive, thresholds=None,
+        min_area=1, connectivity=4, opened=False} (scenes.sweep_params; thresholds as scenes.sweep_levels takes them).  The seg head's
+        uint8 [H][W][C] map is stitched as heads=("seg",) stitches it, whether or not the caller asked for it (it is returned only if
+        asked for).  After the window loop, on the compute stream, rua_scene_area_open builds the opened map of channel `positive`
+        of that resident map, read where it lies (min_area > 1, or opened=True: scenes.host_area_open is the definition), and
+        rua_scene_sweep_hist counts probabilities and opened bytes against the pool's class map into a zeroed int64 [2][2][256]
+        histogram (scenes.host_sweep_hist; min_area 1 opens nothing, hist[1] is hist[0]).  A report {"hist", "levels": uint8 [T],
+        "opened": uint8 [H][W] or None} is added after the sieve report and in front of the head maps, fetched once at the end;
+        scenes.sweep_scores(hist, levels) is the curve.  The sweep reads probabilities, not the sieved class map; it composes with
+        views, erode, boundary, sieve and heads.  ValueError, before any GPU work, for a malformed `sweep`, a pool without class
+        maps, and with scales or blend (the probabilities then live in an int32 accumulator: no maps of the heads are built)."""
         H, W, _ = self.cfg.input_shape
         Cn = self.cfg.num_classes
         if sieve is not None:
             sieve = sieve_params(sieve, Cn)
+        if sweep is not None:
+            sweep = sweep_params(sweep, Cn)
+            if pool.cls_ptrs is None:
+                raise ValueError("predict_scene(sweep=) needs the pool's class maps: there is no ground truth to count against")
         views = check_views(views, (H, W))
         erode = check_radius(erode)
         heads = self._check_map_heads(heads, norm_type)
@@ -2613,11 +2629,15 @@ class Engine:
             scales = check_scales(scales, (H, W), pool.shapes[int(scene)])           # None for (1.0,): the single-scale path
             if scales is not None and heads:
                 raise ValueError(f"predict_scene(scales=, heads={heads}): multi-scale maps of the heads are not built; give one of the two")
+            if scales is not None and sweep is not None:
+                raise ValueError("predict_scene(scales=, sweep=): multi-scale maps of the heads are not built; give one of the two")
         if blend is not None:
             if not isinstance(blend, str) or blend not in BLEND_MODES:
                 raise ValueError(f"blend {blend!r}: None or one of {BLEND_MODES}")
             if heads:
                 raise ValueError(f"predict_scene(blend=, heads={heads}): blended maps of the heads are not built; give one of the two")
+            if sweep is not None:
+                raise ValueError("predict_scene(blend=, sweep=): blended maps of the heads are not built; give one of the two")
             if not 0 <= int(scene) < len(pool):
                 raise ValueError(f"scene {scene} outside 0..{len(pool) - 1}")
             if scales is None:
@@ -2651,7 +2671,7 @@ class Engine:
         sh, sw = (C.c_int32 * 1)(SH), (C.c_int32 * 1)(SW)
         # one resident map per requested head: (source tensor, channels, mode, map, its one-entry pointer array)
         head_maps = {}
-        for h in heads:
+        for h in heads + (("seg",) if sweep is not None and "seg" not in heads else ()):      # the sweep reads the seg map, asked for or not
             src = g.outputs["color" if h == "color_rgb" else h]["p"]
             m = torch.zeros((SH, SW, src.C), dtype=torch.uint8, device=self.dev)
             head_maps[h] = (src, src.C, 1 if h == "color_rgb" else 0, m, (C.c_void_p * 1)(m.data_ptr()))
@@ -2705,7 +2725,7 @@ class Engine:
             if on_batch is not None:
                 on_batch(r, o, seg.t)
             if on_heads is not None:
-                on_heads(r, o, {h: v[0].t for h, v in head_maps.items()})
+                on_heads(r, o, {h: head_maps[h][0].t for h in heads})
         if sieve is not None:
             # the stitched map is sieved before anything scores it: regions, then sieve, round after round between two resident maps
             mn, _, mode, conn, mask, rounds = sieve
@@ -2728,6 +2748,21 @@ class Engine:
             if counted:
                 conf = torch.zeros((Cn, Cn), dtype=torch.int64, device=self.dev)
                 L.lib().call("rua_scene_erode", cls_ptr, sh, sw, 1, 0, None, pred_ptr, Cn, conf.data_ptr(), st)
+        if sweep is not None:
+            # the sweep reads the stitched probabilities of one class where they lie: channel `positive` of the seg map
+            positive, levels, mn, conn, want_opened = sweep
+            st = C.c_void_p(self._stream())
+            _, seg_ch, _, seg_map, _ = head_maps["seg"]
+            prob_ptr = (C.c_void_p * 1)(seg_map.data_ptr() + positive)
+            shist = torch.zeros((2, 2, 256), dtype=torch.int64, device=self.dev)
+            opened = torch.empty((SH, SW), dtype=torch.uint8, device=self.dev) if mn > 1 or want_opened else None
+            open_ptr = (C.c_void_p * 1)(opened.data_ptr()) if opened is not None else None
+            if opened is not None:
+                slab, sarea = (torch.empty((SH, SW), dtype=torch.int32, device=self.dev) for _ in range(2)) if mn > 1 else (None, None)
+                L.lib().call("rua_scene_area_open", prob_ptr, sh, sw, 1, seg_ch, levels.ctypes.data, len(levels), mn, conn, open_ptr,
+                             (C.c_void_p * 1)(slab.data_ptr()) if mn > 1 else None, (C.c_void_p * 1)(sarea.data_ptr()) if mn > 1 else None, st)
+            L.lib().call("rua_scene_sweep_hist", prob_ptr, open_ptr if mn > 1 else None, (C.c_void_p * 1)(pool.cls_dev[sc].data_ptr()), sh, sw, 1,
+                         seg_ch, positive, Cn, shist.data_ptr(), st)
         # what scores the stitched map is issued first, kernel after kernel on the compute stream; every fetch comes after
         if boundary is not None:
             bcounts = torch.zeros((Cn, 4), dtype=torch.int64, device=self.dev)
@@ -2735,7 +2770,9 @@ class Engine:
         if erode:
             conf_e = torch.zeros((Cn, Cn), dtype=torch.int64, device=self.dev)
             L.lib().call("rua_scene_erode", cls_ptr, sh, sw, 1, erode, None, pred_ptr, Cn, conf_e.data_ptr(), C.c_void_p(self._stream()))
-        more = ({h: v[3].cpu().numpy() for h, v in head_maps.items()},) if heads else ()
+        more = ({h: head_maps[h][3].cpu().numpy() for h in heads},) if heads else ()
+        if sweep is not None:
+            more = ({"hist": shist.cpu().numpy(), "levels": levels, "opened": opened.cpu().numpy() if want_opened else None},) + more
         if sieve is not None:
             more = ({"confusion_raw": conf_raw.cpu().numpy() if counted else None, "counts": rcounts.cpu().numpy(),
                      "changed": int(changed.cpu().numpy()[0])},) + more

@@ -653,7 +653,7 @@ class Model:
         return np.concatenate(outs, axis=0)
 
     def predict_scene(self, pool, scene, stride=None, batch=8, norm_type=1, on_batch=None, views=(0,), erode=0, heads=(), on_heads=None,
-                      boundary=None, scales=None, blend=None, sieve=None):
+                      boundary=None, scales=None, blend=None, sieve=None, sweep=None):
         """Engine.predict_scene: (uint8 [H][W] class map of the pool's scene `scene`, int64 [C][C] confusion matrix [true][pred] or None
         without class maps), the windows cut, predicted and stitched on the GPU; only these two arrays come back.  views: test-time
         augmentation, a tuple of symmetry codes or a scenes.VIEW_SETS name ("none", "flips", "aug5", "all").  erode: a radius 1..16
@@ -669,30 +669,43 @@ class Model:
         heads); None changes nothing.  sieve: a minimum area in pixels, or a dict {min_area, mode="fill" | "void", connectivity=4 | 8,
         classes=None, rounds=1}, removes the connected regions below that area from the finished map on the GPU before anything
         scores it (scenes.host_sieve); every returned score is then the sieved map's, and a report {"confusion_raw", "counts",
-        "changed"} is added in front of the head maps; None changes nothing."""
+        "changed"} is added in front of the head maps; None changes nothing.  sweep: a class index, or a dict {positive,
+        thresholds=None, min_area=1, connectivity=4 | 8, opened=False}: the precision-recall sweep of that class's stitched
+        probabilities against the class map, area-opened on the GPU (scenes.host_area_open, scenes.host_sweep_hist); a report
+        {"hist": int64 [2][2][256], "levels", "opened": the opened map or None} is added after the sieve report and before the head
+        maps, and scenes.sweep_scores(hist, levels) is the curve; needs class maps, not together with scales or blend; None changes
+        nothing."""
         if self.engine.loss is None:                      # load_model(..., compile=False), as predict
             self.engine.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in HEADS}, weight={h: 1.0 for h in HEADS}))
         return self.engine.predict_scene(pool, scene, stride=stride, batch=batch, norm_type=norm_type, on_batch=on_batch, views=views, erode=erode,
-                                         heads=heads, on_heads=on_heads, boundary=boundary, scales=scales, blend=blend, sieve=sieve)
+                                         heads=heads, on_heads=on_heads, boundary=boundary, scales=scales, blend=blend, sieve=sieve, sweep=sweep)
 
     def evaluate_scenes(self, pool, stride=None, batch_size=8, norm_type=1, views=(0,), erode=0, heads=(), boundary=None, scales=None, blend=None,
-                        sieve=None):
+                        sieve=None, sweep=None):
         """predict_scene of every scene of the pool: (list of uint8 class maps, the confusion matrices summed - None without class maps);
         with erode >= 1 a third value, the matrices on the eroded ground truth summed; with boundary (a tolerance 0..16) a next
         value, the int64 [C][4] boundary counts summed over the scenes; with heads a last value, the list of the scenes'
         {head: uint8 [H][W][Ch] map} dicts.  scales, blend: predict_scene's, for every scene.  sieve: predict_scene's; the maps and
         every score are then the sieved maps', and in front of the head maps comes the region report summed over the scenes
-        ({"confusion_raw": None without class maps, "counts", "changed"})."""
+        ({"confusion_raw": None without class maps, "counts", "changed"}).  sweep: predict_scene's; after the region report comes
+        {"hist": the scenes' histograms summed, "levels", "opened": the list of the scenes' opened maps, or None}."""
         heads = (heads,) if isinstance(heads, str) else tuple(heads)
-        maps, total, total_e, total_b, head_maps, report = [], None, None, None, [], None
+        maps, total, total_e, total_b, head_maps, report, swept = [], None, None, None, [], None, None
         for s in range(len(pool)):
             m, cm, *more = self.predict_scene(pool, s, stride=stride, batch=batch_size, norm_type=norm_type, views=views, erode=erode, heads=heads,
-                                              boundary=boundary, scales=scales, blend=blend, sieve=sieve)
+                                              boundary=boundary, scales=scales, blend=blend, sieve=sieve, sweep=sweep)
             maps.append(m)
             if cm is not None:
                 total = cm if total is None else total + cm
             if heads:
                 head_maps.append(more.pop())
+            if sweep is not None:
+                r = more.pop()
+                if swept is None:
+                    swept = {"hist": np.zeros_like(r["hist"]), "levels": r["levels"], "opened": None if r["opened"] is None else []}
+                swept["hist"] = swept["hist"] + r["hist"]
+                if r["opened"] is not None:
+                    swept["opened"].append(r["opened"])
             if sieve is not None:
                 r = more.pop()
                 report = r if report is None else {k: (None if r[k] is None else report[k] + r[k]) for k in r}
@@ -706,6 +719,8 @@ class Model:
             res += (total_b,)
         if sieve is not None:
             res += (report,)
+        if sweep is not None:
+            res += (swept,)
         return res + (head_maps,) if heads else res
 
     # -- checkpoints (train_ISPRS.py:292,474-480): real HDF5 in the Keras layout, written / read by h5lite (no h5py needed) --

@@ -88,6 +88,14 @@ reference's protocol), mode "fill" gives each the class most of its kept 4-neigh
 rua_scene_sieve (csrc/regions.hip) are their kernels on resident maps, ScenePool.region_counts() / sieved_maps() and
 Engine.predict_scene(sieve=) their users; check_sieve() checks the parameters in the kernels' words.
 
+A precision-recall sweep judges one class's probability instead of the arg-max map, as the reference's matrics_AA_recall does:
+at every threshold the probability is binarised and area-opened, removed and "no class" pixels leave the count.  Thresholding
+commutes with the area opening and the kept sets are nested, so host_area_open() builds ONE opened map per scene for all levels
+(sweep_levels()), host_sweep_hist() one histogram of probabilities and opened bytes against the class map, and sweep_scores()
+reads recall, precision, F1, alarm area and the average precision at every level from its suffix sums.  rua_scene_area_open and
+rua_scene_sweep_hist (csrc/sweep.hip) are their kernels on resident maps, ScenePool.opened_maps() / sweep_hist() and
+Engine.predict_scene(sweep=) their users.
+
 `python -m resunet_a_mltsk_keras_amd.scenes --image Image_Train.npy --reference Reference_Train.npy --dst DIR` writes a scene
 directory from the reference's two inputs (C x H x W arrays, the reference colour-coded); `--materialize DST` also writes the
 compact patch layout (compact.py) of its window table, for users who want files.
@@ -1487,6 +1495,145 @@ def host_sieve(class_map: np.ndarray, min_area: int, num_classes: int, mode: str
     return out
 
 
+def sweep_levels(thresholds=None) -> np.ndarray:
+    """The levels of a precision-recall sweep as rua_scene_area_open takes them: a uint8 array of distinct levels in 1..255, strictly
+    descending.  Level t means "byte >= t", the byte being what rua_scene_stitch_maps mode 0 wrote: the rounded 255 p.  None gives
+    all 255 levels; a float threshold thr in (0, 1] gives the level max(1, rint(255 thr)); an integer is taken as a level;
+    duplicates are dropped.  ValueError, in rua_scene_area_open's own words, for an empty list, a level 0 or a level above 255."""
+    fn = "rua_scene_area_open"
+    if thresholds is None:
+        return np.arange(255, 0, -1).astype(np.uint8)
+    if isinstance(thresholds, (str, bytes)):
+        raise ValueError(f"{fn}: thresholds {thresholds!r}: None or a list of levels 1..255 or of thresholds in (0, 1]")
+    if np.ndim(thresholds) == 0:
+        thresholds = (thresholds,)
+    out = []
+    for k, thr in enumerate(np.asarray(thresholds).ravel().tolist() if isinstance(thresholds, np.ndarray) else list(thresholds)):
+        if _is_int(thr):
+            v = int(thr)
+        elif isinstance(thr, (float, np.floating)) and not isinstance(thr, bool):
+            if not 0.0 < float(thr) <= 1.0:
+                raise ValueError(f"{fn}: thresholds[{k}] = {thr!r} outside (0, 1] (an integer is taken as a level 1..255)")
+            v = max(1, int(np.rint(255.0 * float(thr))))
+        else:
+            raise ValueError(f"{fn}: thresholds[{k}] = {thr!r} is neither an integer level nor a float threshold")
+        if not 1 <= v <= 255:
+            raise ValueError(f"{fn}: levels[{k}] = {v} outside 1..255")
+        out.append(v)
+    if not out:
+        raise ValueError(f"{fn}: T 0 outside 1..255")
+    return np.array(sorted(set(out), reverse=True), np.uint8)
+
+
+def _check_min_area(fn: str, min_area) -> int:
+    if not _is_int(min_area) or not 1 <= int(min_area) < 1 << 31:
+        raise ValueError(f"{fn}: min_area {min_area!r} outside 1..2147483647")
+    return int(min_area)
+
+
+def host_area_open(prob: np.ndarray, levels, min_area: int, connectivity: int = 4) -> np.ndarray:
+    """The numpy definition of what rua_scene_area_open writes, the OPENED map G, uint8 [H][W], of the uint8 probability map prob:
+    G[x] is the largest listed level t (sweep_levels) such that x lies in a connected component of {prob >= t} - 4- or 8-connected -
+    with at least min_area pixels, and 0 if there is none.  {G >= t} is then, for every listed t, exactly the binary map the
+    reference's protocol scores at that threshold: {prob >= t} after skimage's area_opening(area_threshold=min_area) (a component of
+    exactly min_area pixels stays).  One map serves every threshold because thresholding commutes with the opening and the kept sets
+    are nested: a component of at least min_area pixels at level t lies inside one at every lower level.
+    Written from scratch per level: host_regions of the binarised map, nothing carried from one level to the next.  min_area 1:
+    G[x] is the largest listed level <= prob[x]."""
+    fn = "rua_scene_area_open"
+    p = _check_region_map(fn, prob, "the probability map")
+    lv = sweep_levels(levels)
+    mn = _check_min_area(fn, min_area)
+    conn = _check_connectivity(fn, connectivity)
+    out = np.zeros(p.shape, np.uint8)
+    for t in lv.tolist():
+        binary = (p >= t).astype(np.uint8)
+        labels, areas = host_regions(binary, conn)
+        kept = (binary == 1) & (areas.ravel()[labels] >= mn)
+        out[kept & (out == 0)] = t
+    return out
+
+
+def host_sweep_hist(prob: np.ndarray, opened: Optional[np.ndarray], cls: np.ndarray, positive: int, num_classes: int) -> np.ndarray:
+    """The numpy definition of what rua_scene_sweep_hist adds to its histogram, int64 [2][2][256]: hist[0][k][l] counts the pixels
+    with prob == l, hist[1][k][l] those with opened == l (opened None stands for prob: no area opening); k = 1 where cls ==
+    positive, k = 0 where cls < num_classes and cls != positive.  Pixels with cls >= num_classes - the project's "no class", which is
+    how a user encodes the reference's "past deforestation / buffer = 2" and the outside of its mask - are counted nowhere."""
+    fn = "rua_scene_sweep_hist"
+    p = _check_region_map(fn, prob, "the probability map")
+    o = p if opened is None else _check_region_map(fn, opened, "the opened map")
+    c = _check_region_map(fn, cls, "the class map")
+    if o.shape != p.shape or c.shape != p.shape:
+        raise ValueError(f"{fn}: the probability map is {p.shape}, the opened map {o.shape}, the class map {c.shape}")
+    if not _is_int(num_classes) or not 1 <= int(num_classes) <= MAX_CLASSES:
+        raise ValueError(f"{fn}: C {num_classes} outside 1..64")
+    if not _is_int(positive) or not 0 <= int(positive) < int(num_classes):
+        raise ValueError(f"{fn}: positive {positive!r} outside 0..{int(num_classes) - 1}")
+    out = np.zeros((2, 2, 256), np.int64)
+    for k, sel in enumerate(((c < int(num_classes)) & (c != int(positive)), c == int(positive))):
+        out[0, k] = np.bincount(p[sel], minlength=256)
+        out[1, k] = np.bincount(o[sel], minlength=256)
+    return out
+
+
+def sweep_scores(hist, levels=None) -> dict:
+    """The precision-recall curve of a histogram of host_sweep_hist / rua_scene_sweep_hist (int64 [2][2][256], or a sum of such over
+    scenes) at these levels (sweep_levels; they must be levels the opened map was built with, or any levels if it was not opened).
+    A dict of arrays over the descending levels, with S_t(a) = sum of a[l] over l >= t:
+      tp = S_t(hist[1][1])    fp = S_t(hist[1][0])    fn = sum of hist[0][1][l] over l < t
+      removed = S_t(hist[0][0] + hist[0][1]) - S_t(hist[1][0] + hist[1][1]): predicted pixels that sit in a region below min_area;
+                they are left out of tp, fp and fn, as the reference leaves them out
+      recall = tp / (tp + fn)    precision = tp / (tp + fp)    f1 = 2 tp / (2 tp + fp + fn)    alarm_area = (tp + fp) / valid
+    each 0 where it would be 0 / 0; "levels" the levels, "valid" (an int) the total of hist[0], and "average_precision" (a float)
+    the sum over k of (recall_k - recall_{k-1}) precision_k along the descending levels with recall_{-1} = 0.
+    Recall is non-decreasing along the descending levels because the kept sets are nested: tp only grows as t falls and fn only
+    shrinks, with or without an opening.  One deliberate difference from the reference's
+    matrics_AA_recall: the denominator of its alarm area also counts its "not considered" pixels, ours counts only valid ones."""
+    h = np.asarray(hist)
+    if h.shape != (2, 2, 256) or h.dtype.kind not in "iu":
+        raise ValueError(f"sweep_scores: hist is an integer [2][2][256] array, got {h.dtype} {h.shape}")
+    h = h.astype(np.int64)
+    lv = sweep_levels(levels)
+    at = lv.astype(np.int64)
+    suffix = lambda a: np.cumsum(a[::-1])[::-1][at]
+    tp, fp = suffix(h[1, 1]), suffix(h[1, 0])
+    fn_ = int(h[0, 1].sum()) - suffix(h[0, 1])
+    removed = suffix(h[0, 0] + h[0, 1]) - suffix(h[1, 0] + h[1, 1])
+    valid = int(h[0].sum())
+
+    def ratio(a, b):
+        a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+        return np.divide(a, b, out=np.zeros_like(a), where=b != 0)
+
+    recall, precision = ratio(tp, tp + fn_), ratio(tp, tp + fp)
+    ap = float(np.sum(np.diff(np.concatenate([[0.0], recall])) * precision))
+    return {"levels": lv, "tp": tp, "fp": fp, "fn": fn_, "removed": removed, "valid": valid, "recall": recall, "precision": precision,
+            "f1": ratio(2 * tp, 2 * tp + fp + fn_), "alarm_area": ratio(tp + fp, np.full(len(lv), valid)), "average_precision": ap}
+
+
+def sweep_params(sweep, num_classes):
+    """Engine.predict_scene's `sweep` as (positive, levels, min_area, connectivity, opened): an integer is the positive class with
+    all 255 levels, min_area 1, connectivity 4 and no opened map returned; a dict may hold positive (required), thresholds,
+    min_area, connectivity and opened.  ValueError, in the C entries' words, for anything else."""
+    fn = "rua_scene_sweep_hist"
+    if _is_int(sweep):
+        sweep = {"positive": sweep}
+    if not isinstance(sweep, dict):
+        raise ValueError(f"sweep {sweep!r}: None, a class index or a dict of positive, thresholds, min_area, connectivity, opened")
+    unknown = sorted(set(sweep) - {"positive", "thresholds", "min_area", "connectivity", "opened"})
+    if unknown:
+        raise ValueError(f"sweep: unknown key {unknown[0]!r} (positive, thresholds, min_area, connectivity, opened)")
+    if "positive" not in sweep:
+        raise ValueError("sweep: the dict needs positive")
+    if not _is_int(num_classes) or not 1 <= int(num_classes) <= MAX_CLASSES:
+        raise ValueError(f"{fn}: C {num_classes} outside 1..64")
+    pos = sweep["positive"]
+    if not _is_int(pos) or not 0 <= int(pos) < int(num_classes):
+        raise ValueError(f"{fn}: positive {pos!r} outside 0..{int(num_classes) - 1}")
+    return (int(pos), sweep_levels(sweep.get("thresholds")), _check_min_area("rua_scene_area_open", sweep.get("min_area", 1)),
+            _check_connectivity("rua_scene_area_open", sweep.get("connectivity", 4)), bool(sweep.get("opened", False)))
+
+
 def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]]) -> int:
     """Scenes are uint8 H x W x C with one C for all, class maps uint8 H x W of their image's size.  Returns C."""
     if len(images) < 1:
@@ -1826,6 +1973,86 @@ class ScenePool:
         for k, s in enumerate(given):
             out[s] = got[first[k]:first[k + 1]].reshape(self.shapes[s]).copy()
         return out
+
+    def _area_open(self, given, dev, first, lv, mn, conn, st):
+        """rua_scene_area_open of the dense maps of the scenes `given` that lie in `dev` from first[k] on: the opened maps in one
+        device buffer of the same layout, and the ctypes arrays of per-scene pointers map / opened / heights / widths."""
+        import torch
+        from . import _lib as L
+        n = len(given)
+        ptrs = lambda t, unit: (C.c_void_p * n)(*[t.data_ptr() + unit * int(o) for o in first[:-1]])
+        hs, ws = (C.c_int32 * n)(*[self.shapes[s][0] for s in given]), (C.c_int32 * n)(*[self.shapes[s][1] for s in given])
+        opened = torch.empty_like(dev)
+        mp, op = ptrs(dev, 1), ptrs(opened, 1)
+        lp = ap = None
+        if mn > 1:
+            labels, areas = (torch.empty((int(first[-1]),), dtype=torch.int32, device=self.device) for _ in range(2))
+            lp, ap = ptrs(labels, 4), ptrs(areas, 4)
+        L.lib().call("rua_scene_area_open", mp, hs, ws, n, 1, lv.ctypes.data, len(lv), mn, conn, op, lp, ap, st)
+        return opened, (mp, op, hs, ws)
+
+    def opened_maps(self, probs, thresholds=None, min_area: int = 1, connectivity: int = 4) -> List[np.ndarray]:
+        """host_area_open of probs[s], a uint8 [H][W] probability map per scene of the pool (a None entry skips its scene and gives
+        None), as a list of uint8 maps: one upload of all maps, one rua_scene_area_open call over all of them and one fetch; a "cpu"
+        pool returns the host definition."""
+        fn = "rua_scene_area_open"
+        lv, mn, conn = sweep_levels(thresholds), _check_min_area(fn, min_area), _check_connectivity(fn, connectivity)
+        probs = self._check_region_maps(fn, probs)
+        if self.device.type != "cuda":
+            return [None if p is None else host_area_open(p, lv, mn, conn) for p in probs]
+        given = [s for s, p in enumerate(probs) if p is not None]
+        if not given:
+            return [None] * len(probs)
+        import torch
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            first = np.concatenate([[0], np.cumsum([probs[s].size for s in given])]).astype(np.int64)
+            dev = torch.from_numpy(np.concatenate([probs[s].ravel() for s in given])).to(self.device)
+            opened, _ = self._area_open(given, dev, first, lv, mn, conn, st)
+            got = opened.cpu().numpy()
+        out = [None] * len(probs)
+        for k, s in enumerate(given):
+            out[s] = got[first[k]:first[k + 1]].reshape(self.shapes[s]).copy()
+        return out
+
+    def sweep_hist(self, probs, positive: int, num_classes: int, thresholds=None, min_area: int = 1, connectivity: int = 4) -> np.ndarray:
+        """int64 [n][2][2][256], host_sweep_hist of probs[s] - a uint8 [H][W] map of class `positive`'s probability per scene of the
+        pool, None to skip a scene (its cells stay 0) - against the pool's class maps; sweep_scores of a scene's cells, or of their
+        sum, is the precision-recall curve.  min_area 1 opens nothing: hist[1] is hist[0].  Otherwise the opened map is
+        host_area_open at these thresholds (sweep_levels), and the curve is read at those levels.  One upload of all maps, one
+        rua_scene_area_open call over all of them (min_area > 1), one rua_scene_sweep_hist call per scene into that scene's cells
+        of one device buffer (a call sums its scenes into one histogram) and one fetch; a "cpu" pool returns the host definition."""
+        fn = "rua_scene_sweep_hist"
+        if self.class_maps is None:
+            raise ValueError("sweep_hist needs the pool's class maps")
+        pos, lv, mn, conn, _ = sweep_params({"positive": positive, "thresholds": thresholds, "min_area": min_area, "connectivity": connectivity},
+                                            num_classes)
+        C_ = int(num_classes)
+        probs = self._check_region_maps(fn, probs)
+        given = [s for s, p in enumerate(probs) if p is not None]
+        if self.device.type != "cuda":
+            out = np.zeros((len(self), 2, 2, 256), np.int64)
+            for s in given:
+                out[s] = host_sweep_hist(probs[s], host_area_open(probs[s], lv, mn, conn) if mn > 1 else None, self.class_maps[s], pos, C_)
+            return out
+        import torch
+        from . import _lib as L
+        with torch.cuda.device(self.device):
+            hist = torch.zeros((len(self), 2, 2, 256), dtype=torch.int64, device=self.device)
+            if not given:
+                return hist.cpu().numpy()
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            first = np.concatenate([[0], np.cumsum([probs[s].size for s in given])]).astype(np.int64)
+            dev = torch.from_numpy(np.concatenate([probs[s].ravel() for s in given])).to(self.device)
+            opened = None
+            if mn > 1:
+                opened, _ = self._area_open(given, dev, first, lv, mn, conn, st)
+            one = lambda v, t=C.c_void_p: (t * 1)(v)
+            for k, s in enumerate(given):
+                H, W = self.shapes[s]
+                L.lib().call(fn, one(dev.data_ptr() + int(first[k])), None if opened is None else one(opened.data_ptr() + int(first[k])),
+                             one(self.cls_dev[s].data_ptr()), one(H, C.c_int32), one(W, C.c_int32), 1, 1, pos, C_, hist[s].data_ptr(), st)
+            return hist.cpu().numpy()
 
     def predict_table(self, scene: int, stride: Optional[int] = None):
         """predict_table of scene `scene` with the pool's patch (stride None: the patch, non-overlapping windows), rows naming it."""
