@@ -482,6 +482,43 @@ int rua_head_dz_opts(int kind, int act, const float* p, const float* y, const fl
 /* n heads of mixed kinds in ONE launch, opts[i] belongs to heads[i] */
 int rua_head_dz_multi_opts(const rua_dz_head* heads, const rua_loss_opts* opts, int n, const uint8_t* void_mask, void* stream);
 
+/* ---- online hard example mining (OHEM, bootstrapped cross-entropy): per step and per head only the hardest pixels contribute - those whose
+ * loss lies above a threshold, but never fewer than a floor.  The package's losses.py holds the definition as a host function, host_ohem; the
+ * kernels are csrc/ohem.hip.  For one head and one batch, with L[M] the per_pixel map of a loss entry above (kinds 1..6) and valid = every pixel,
+ * or byte == 0 of void_mask:
+ *   key        the float32 bit pattern as an order-preserving uint32: all bits of a negative flipped, the sign bit of a non-negative set
+ *              (-0 < +0); every NaN is 0xFFFFFFFF, the hardest key (always kept, so a non-finite step skip still sees it)
+ *   n_valid    = sum(valid)
+ *   q          = keep_q16 (1..65536: the kept share of the valid pixels in Q16), or under a warm-up of `warmup` > 0 optimizer updates
+ *              65536 - ((65536 - keep_q16) * min(t, warmup)) / warmup in integers, t = (int64)step_state[0] (the device's step counter;
+ *              step_state NULL: no warm-up)
+ *   K          = min(n_valid, max(min_kept, (n_valid * q + 65535) >> 16))
+ *   tau_key    = the K-th largest valid key; with has_thresh: min(that, key(thresh)); no valid pixel: 0xFFFFFFFF in place of the K-th key
+ *   kept       = valid and key(L) >= tau_key: ties at the threshold are all kept, n_kept >= K, no order enters
+ *   loss       = (fp64 sum of L over the kept pixels) / n_kept, 0 for n_kept = 0;  scale = (float)((double)loss_weight / (double)n_kept), or 0
+ * rua_ohem_select writes drop_mask[M] (0 kept, 1 dropped or void; every byte, always), adds the kept mean into loss_out[0] (the fp64 slot
+ * contract of rua_pixel_loss; unchanged for n_kept = 0) and fills result_dev.  An exact radix select over the key in three digit passes of
+ * 11 / 11 / 10 bits: per-block LDS histograms, flushed to global ones with integer atomics; every block derives the digit chosen so far from the
+ * previous passes' histograms itself.  SIX launches whatever the map holds (zero, three histogram passes, the mask pass, a one-block finisher),
+ * no block waits for another, no host readback; all sums are integers but the kept sum, which is added in a fixed order (per thread in index
+ * order, a fixed butterfly per wave, waves and blocks in order): the same bits on every run and every replay.  workspace: at least
+ * rua_ohem_workspace_bytes of M, 8-byte aligned, contents irrelevant.  RUA_ERR_ARG before any launch: M < 1 (or > 2^40), keep_q16 outside
+ * 1..65536, min_kept < 0, warmup < 0, a NaN thresh with has_thresh, a workspace that is too small, a null or misaligned buffer. */
+typedef struct rua_ohem_opts { int64_t min_kept; int32_t keep_q16, warmup; float thresh; int32_t has_thresh; } rua_ohem_opts;
+typedef struct rua_ohem_result { uint32_t tau_key; float tau; int64_t n_valid, n_kept, K; double kept_sum; float scale; int32_t q16_used; } rua_ohem_result;
+int64_t rua_ohem_workspace_bytes(int64_t M);
+int rua_ohem_select(const float* per_pixel, const uint8_t* void_mask, int64_t M, const rua_ohem_opts* opts, const double* step_state,
+                    float loss_weight, void* workspace, int64_t workspace_bytes, uint8_t* drop_mask, double* loss_out,
+                    rua_ohem_result* result_dev, void* stream);
+/* d(total)/d(logits) with the mask and the normaliser taken from device memory, per head: the bytes of rua_head_dz_opts called with
+ * grad_scale = scale_dev[0] and void_mask = drop_mask (which already holds the void pixels).  rua_head_dz_multi_sel: n heads in ONE launch;
+ * a head whose sel entry is zeroed behaves exactly as in rua_head_dz_multi_opts (its host grad_scale, the shared void_mask), a head with a
+ * selection ignores both.  drop_mask and scale_dev of a head are both set or both NULL (RUA_ERR_ARG otherwise). */
+typedef struct rua_dz_sel { const uint8_t* drop_mask; const float* scale_dev; } rua_dz_sel;
+int rua_head_dz_sel(int kind, int act, const float* p, const float* y, const float* coef, const float* class_w, int B, int64_t HW, int C,
+                    const rua_loss_opts* opts, const uint8_t* drop_mask, const float* scale_dev, float* dz, void* stream);
+int rua_head_dz_multi_sel(const rua_dz_head* heads, const rua_loss_opts* opts, const rua_dz_sel* sel, int n, const uint8_t* void_mask, void* stream);
+
 /* ---- optimizers on the flat parameter buffer (train_ISPRS.py:404-407) --------------------- */
 /* Keras Adam: theta -= lr_t * m / (sqrt(v) + eps); g is read as g*grad_scale and zeroed if zero_grad.
  * lr_t_dev (optional): device scalar overriding lr_t, so a captured HIP graph can be replayed every step */

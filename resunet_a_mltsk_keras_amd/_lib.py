@@ -69,6 +69,21 @@ class LossOpts(C.Structure):
     _fields_ = [("gamma", f32), ("label_smoothing", f32), ("alpha", f32), ("class_balance", i32)]
 
 
+class OhemOpts(C.Structure):
+    """rua_ohem_opts (losses.py holds the definition, host_ohem)."""
+    _fields_ = [("min_kept", i64), ("keep_q16", i32), ("warmup", i32), ("thresh", f32), ("has_thresh", i32)]
+
+
+class OhemResult(C.Structure):
+    """rua_ohem_result: what rua_ohem_select leaves on the device."""
+    _fields_ = [("tau_key", C.c_uint32), ("tau", f32), ("n_valid", i64), ("n_kept", i64), ("K", i64), ("kept_sum", f64), ("scale", f32), ("q16_used", i32)]
+
+
+class DzSel(C.Structure):
+    """rua_dz_sel: zeroed = the head takes no selection."""
+    _fields_ = [("drop_mask", vp), ("scale_dev", vp)]
+
+
 class BnBranch(C.Structure):
     _fields_ = [("gamma", vp), ("beta", vp), ("moving_mean", vp), ("moving_var", vp), ("scale", vp), ("shift", vp),
                 ("mean", vp), ("rstd", vp), ("out", vp), ("stats", vp), ("replicas", i32), ("pad", i32), ("out_stats", vp)]
@@ -212,6 +227,10 @@ _SIGS = {
     "rua_pixel_loss_opts": ([i32, vp, vp, vp, vp, vp, C.POINTER(LossOpts), i64, i32, vp, vp, vp], i32),
     "rua_head_dz_opts": ([i32, i32, vp, vp, vp, vp, f32, i32, i64, i32, vp, C.POINTER(LossOpts), vp, vp], i32),
     "rua_head_dz_multi_opts": ([vp, vp, i32, vp, vp], i32),
+    "rua_ohem_workspace_bytes": ([i64], i64),
+    "rua_ohem_select": ([vp, vp, i64, C.POINTER(OhemOpts), vp, f32, vp, i64, vp, vp, vp, vp], i32),
+    "rua_head_dz_sel": ([i32, i32, vp, vp, vp, vp, i32, i64, i32, C.POINTER(LossOpts), vp, vp, vp, vp], i32),
+    "rua_head_dz_multi_sel": ([vp, vp, vp, i32, vp, vp], i32),
     "rua_void_mask": ([vp, i32, i32, i32, i32, i32, vp, vp], i32),
     "rua_targets_scratch_bytes": ([i32, i32], i64),
     "rua_multitask_targets": ([vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp], i32),

@@ -756,6 +756,71 @@ extern "C" int rua_head_dz_opts(int kind, int act, const float* p, const float* 
   return RUA_OK;
 }
 
+// ---- online hard example mining: the same launch with a head's mask and normaliser read from device memory (rua_dz_sel; csrc/ohem.hip writes them).
+// A head with a selection runs the instantiation rua_head_dz_opts would run for it - its own drop_mask as the mask, scale_dev[0] as grad_scale,
+// the options form only if the head needs it -, a head without one the instantiation rua_head_dz_multi_opts would: the same bytes either way.
+struct DzMultiSel { rua_dz_head h[RUA_MAX_HEADS]; rua_loss_opts o[RUA_MAX_HEADS]; rua_dz_sel s[RUA_MAX_HEADS]; unsigned char op[RUA_MAX_HEADS]; };
+template <bool VM, bool OP>
+__device__ __forceinline__ void head_dz_sel_body(const rua_dz_head& h, const rua_loss_opts lo, float gs, const uint8_t* __restrict__ vm) {
+  if (h.C == 6) head_dz_body<6, VM, OP>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, gs, (long long)h.HW, h.C, h.dz, vm, lo);
+  else if (h.C == 3) head_dz_body<3, VM, OP>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, gs, (long long)h.HW, h.C, h.dz, vm, lo);
+  else head_dz_body<0, VM, OP>(h.kind, h.act, h.p, h.y, h.coef, h.class_w, gs, (long long)h.HW, h.C, h.dz, vm, lo);
+}
+__global__ __launch_bounds__(256) void head_dz_multi_sel_kernel(const DzMultiSel a, const uint8_t* __restrict__ vm) {
+  const rua_dz_head& h = a.h[blockIdx.z];
+  if ((int)blockIdx.y >= h.B) return;
+  const rua_loss_opts lo = a.o[blockIdx.z];
+  const rua_dz_sel s = a.s[blockIdx.z];
+  const uint8_t* m = s.drop_mask ? s.drop_mask : vm;
+  const float gs = s.drop_mask ? s.scale_dev[0] : h.grad_scale;
+  if (a.op[blockIdx.z]) {
+    if (m) head_dz_sel_body<true, true>(h, lo, gs, m); else head_dz_sel_body<false, true>(h, lo, gs, m);
+  } else {
+    if (m) head_dz_sel_body<true, false>(h, lo, gs, m); else head_dz_sel_body<false, false>(h, lo, gs, m);
+  }
+}
+extern "C" int rua_head_dz_multi_sel(const rua_dz_head* heads, const rua_loss_opts* opts, const rua_dz_sel* sel, int n, const uint8_t* void_mask, void* stream) {
+  RUA_CHECK_ARG(heads && opts && sel && n >= 1 && n <= RUA_MAX_HEADS, "rua_head_dz_multi_sel: 1..%d heads, each with its options and its selection", RUA_MAX_HEADS);
+  DzMultiSel a;
+  int64_t g = 1; int Bm = 1, first_plain = -1;
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    const rua_dz_head& h = heads[i];
+    RUA_CHECK_ARG(h.p && h.y && h.dz && h.B > 0 && h.B <= 65535 && h.HW > 0 && h.C >= 1 && h.C <= 8 && h.kind >= 0 && h.kind <= RUA_LOSS_FOCAL_BCE && h.act >= 0 && h.act <= 2,
+                  "rua_head_dz_multi_sel: head %d: bad arguments", i);
+    RUA_CHECK_ARG(h.kind != RUA_LOSS_TANIMOTO || h.coef, "rua_head_dz_multi_sel: Tanimoto needs coefficients");
+    RUA_CHECK_ARG(h.kind != RUA_LOSS_WCE || h.class_w, "rua_head_dz_multi_sel: weighted CE needs class weights");
+    const char* why = dz_opts_error(h.kind, h.act, h.class_w, opts[i]);
+    RUA_CHECK_ARG(!why, "rua_head_dz_multi_sel: head %d: %s", i, why);
+    RUA_CHECK_ARG((sel[i].drop_mask != nullptr) == (sel[i].scale_dev != nullptr), "rua_head_dz_multi_sel: head %d: drop_mask and scale_dev go together", i);
+    RUA_CHECK_ARG(!sel[i].scale_dev || ((size_t)sel[i].scale_dev & 3) == 0, "rua_head_dz_multi_sel: head %d: misaligned scale_dev", i);
+    if (!sel[i].drop_mask) {                              // the shared mask is indexed by (sample, pixel): the heads that read it must agree in both
+      if (first_plain < 0) first_plain = i;
+      RUA_CHECK_ARG(!void_mask || (h.B == heads[first_plain].B && h.HW == heads[first_plain].HW),
+                    "rua_head_dz_multi_sel: head %d: B %d, HW %lld differ from head %d's", i, h.B, (long long)h.HW, first_plain);
+    }
+    a.h[i] = h; a.o[i] = opts[i]; a.s[i] = sel[i];
+    any = any || loss_needs_opts(h.kind, opts[i]);
+    const int64_t gi = (h.HW + 255) / 256; if (gi > g) g = gi;
+    if (h.B > Bm) Bm = h.B;
+  }
+  for (int i = 0; i < n; ++i) a.op[i] = sel[i].drop_mask ? loss_needs_opts(heads[i].kind, opts[i]) : any;
+  const int64_t cap = 4096 / ((int64_t)Bm * n) > 0 ? 4096 / ((int64_t)Bm * n) : 1;
+  if (g > cap) g = cap;
+  hipLaunchKernelGGL(head_dz_multi_sel_kernel, dim3((int)g, Bm, n), dim3(256), 0, (hipStream_t)stream, a, void_mask);
+  RUA_LAUNCH_CHECK("rua_head_dz_multi_sel");
+  return RUA_OK;
+}
+extern "C" int rua_head_dz_sel(int kind, int act, const float* p, const float* y, const float* coef, const float* class_w, int B, int64_t HW, int C,
+                               const rua_loss_opts* opts, const uint8_t* drop_mask, const float* scale_dev, float* dz, void* stream) {
+  RUA_CHECK_ARG(opts && drop_mask && scale_dev, "rua_head_dz_sel: options, drop_mask and scale_dev are required");
+  rua_dz_head h;
+  memset(&h, 0, sizeof(h));
+  h.kind = kind; h.act = act; h.p = p; h.y = y; h.coef = coef; h.class_w = class_w; h.grad_scale = 0.f; h.B = B; h.HW = HW; h.C = C; h.dz = dz;
+  const rua_dz_sel s = {drop_mask, scale_dev};
+  return rua_head_dz_multi_sel(&h, opts, &s, 1, nullptr, stream);
+}
+
 // accuracy + TP/FP/TN/FN (Keras 'accuracy' = categorical accuracy; confusion counts at .5)
 // VM: void pixels are counted nowhere, so (TP + FP + TN + FN) / C is the number of valid pixels
 template <bool VM>

@@ -89,11 +89,21 @@ class LossSpec:
     class_balance: Dict[str, bool] = field(default_factory=dict)      # binary focal: apply_class_balancing
     label_smoothing: Dict[str, float] = field(default_factory=dict)   # the three cross-entropies and the two focal kinds
 
+    # Online hard example mining (losses.py holds the definition, host_ohem), by head: head -> losses.ohem_options(...).  A training step of such a
+    # head keeps only its hardest pixels (rua_ohem_select) and takes the gradient's mask and normaliser from device memory; evaluation reports the
+    # plain mean.  A head that is not in it issues the calls it always did.
+    ohem: Dict[str, dict] = field(default_factory=dict)
+
     def loss_options(self) -> Dict[str, object]:
-        """The four per-head dicts (checkpoint metadata); a spec without them gives {}: its file carries none."""
+        """The per-head dicts (checkpoint metadata); a spec without them gives {}: its file carries none."""
         d = dict(focal_gamma=dict(self.focal_gamma), focal_alpha=dict(self.focal_alpha), class_balance=dict(self.class_balance),
-                 label_smoothing=dict(self.label_smoothing))
+                 label_smoothing=dict(self.label_smoothing), ohem={h: dict(o) for h, o in self.ohem.items()})
         return {k: v for k, v in d.items() if v}
+
+    def head_ohem(self, head: str) -> Optional[dict]:
+        """The head's mining options with every field filled in; None: the head does not mine."""
+        o = self.ohem.get(head)
+        return None if o is None else {**LS.ohem_options(), **o}
 
     def head_opts(self, head: str):
         """rua_loss_opts of a head whose kind is new or whose label_smoothing > 0; None: the head takes the entries without options."""
@@ -1383,25 +1393,50 @@ class Graph:
                 LP.add("rua_tanimoto_finalize_rep", sums, h.get("sums_rep", 1), B, HW, Cc, wgt / B, slot, coef.data_ptr(), None)
             h["norm"] = 1.0
         else:
+            # online hard example mining (training plans only: evaluation reports the plain mean): the loss entry leaves the per-pixel map - its own sum
+            # goes to a scratch slot nobody reads -, rua_ohem_select turns the map into the head's drop mask, its normaliser and the kept mean, which it
+            # adds into the head's slot.  Everything stays on the device: a replay needs no host scalar
+            oh = sp.head_ohem(h["name"]) if self.training else None
+            pp, lslot = None, slot
+            if oh is not None:
+                pp = self.alloc((M,), torch.float32)
+                lslot = self.salloc(1)
             if opts is not None:                            # a focal kind or label smoothing: the entry with options (mask optional)
                 LP.keep.append(opts)
-                LP.add("rua_pixel_loss_opts", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, self.void_ptr, C.byref(opts), M, Cc, slot, None)
+                LP.add("rua_pixel_loss_opts", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, self.void_ptr, C.byref(opts), M, Cc, lslot,
+                       pp.data_ptr() if pp is not None else None)
             elif self.void_ptr is not None:                 # the sum over the valid pixels, still divided by M (Keras' sample_weight rule with 0 / 1 weights)
-                LP.add("rua_pixel_loss_void", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, self.void_ptr, M, Cc, slot, None)
+                LP.add("rua_pixel_loss_void", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, self.void_ptr, M, Cc, lslot,
+                       pp.data_ptr() if pp is not None else None)
             else:
-                LP.add("rua_pixel_loss", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, M, Cc, slot, None)
+                LP.add("rua_pixel_loss", kind, h["p"].ptr, h["z"].ptr, h["y"].ptr, self.e.class_w_ptr, M, Cc, lslot, pp.data_ptr() if pp is not None else None)
             h["norm"] = 1.0 / M
+            if oh is not None:
+                nws = int(L.lib().raw("rua_ohem_workspace_bytes")(M))
+                drop, res, ws = self.alloc((M,), torch.uint8), self.alloc((C.sizeof(L.OhemResult) // 8,), torch.float64, zero=True), self.alloc((nws // 8 + 1,), torch.float64)
+                oo = LS.to_ohem_struct(oh)
+                LP.keep.append(oo)
+                LP.add("rua_ohem_select", pp.data_ptr(), self.void_ptr, M, C.byref(oo), self.e.lr_state.data_ptr() if oo.warmup > 0 else None, wgt,
+                       ws.data_ptr(), nws, drop.data_ptr(), slot, res.data_ptr())
+                h["norm"] = 1.0
+                h["ohem"] = dict(per_pixel=pp, drop_mask=drop, result=res, opts=oh)
         if not self.training:
             return
+        sel = h.get("ohem")
 
         dz = self.new(B, h["x"].H, h["x"].W, Cc, f32=True)
         gs = wgt / B if kind == L.LOSS_TANIMOTO else wgt / M
+        scale_ptr = sel["result"].data_ptr() + L.OhemResult.scale.offset if sel is not None else None
         if self.multi_head:
             dh = L.DzHead()
             dh.kind, dh.act, dh.p, dh.y, dh.coef, dh.class_w = kind, h["act"], h["p"].ptr, h["y"].ptr, coef.data_ptr() if coef is not None else None, self.e.class_w_ptr
             dh.grad_scale, dh.B, dh.HW, dh.C, dh.dz = gs, B, HW, Cc, dz.ptr
             self._dz_multi.append(dh)
             self._dz_multi_opts.append(opts)
+            ds = L.DzSel()                                  # zeroed: the head takes no selection
+            if sel is not None:
+                ds.drop_mask, ds.scale_dev = sel["drop_mask"].data_ptr(), scale_ptr
+            self._dz_multi_sel.append(ds)
 
         def back():
             Bp = self.bwd
@@ -1409,7 +1444,12 @@ class Graph:
                 if not self._dz_emitted:                    # the first backward step of the loss section: d(loss)/d(logits) of ALL heads in one launch
                     arr = (L.DzHead * len(self._dz_multi))(*self._dz_multi)
                     Bp.keep.append(arr)
-                    if any(o is not None for o in self._dz_multi_opts):      # still one launch: every head with its options, zeroed where it has none
+                    if any(d.drop_mask for d in self._dz_multi_sel):         # a mining head: still one launch, its mask and normaliser read on the device
+                        oarr = (L.LossOpts * len(self._dz_multi))(*[o if o is not None else L.LossOpts() for o in self._dz_multi_opts])
+                        sarr = (L.DzSel * len(self._dz_multi))(*self._dz_multi_sel)
+                        Bp.keep += [oarr, sarr]
+                        Bp.add("rua_head_dz_multi_sel", arr, oarr, sarr, len(self._dz_multi), self.void_ptr)
+                    elif any(o is not None for o in self._dz_multi_opts):      # still one launch: every head with its options, zeroed where it has none
                         oarr = (L.LossOpts * len(self._dz_multi))(*[o if o is not None else L.LossOpts() for o in self._dz_multi_opts])
                         Bp.keep.append(oarr)
                         Bp.add("rua_head_dz_multi_opts", arr, oarr, len(self._dz_multi), self.void_ptr)
@@ -1418,6 +1458,11 @@ class Graph:
                     else:
                         Bp.add("rua_head_dz_multi", arr, len(self._dz_multi))
                     self._dz_emitted = True
+            elif sel is not None:
+                o = opts if opts is not None else L.LossOpts()
+                Bp.keep.append(o)
+                Bp.add("rua_head_dz_sel", kind, h["act"], h["p"].ptr, h["y"].ptr, coef.data_ptr() if coef is not None else None,
+                       self.e.class_w_ptr, B, HW, Cc, C.byref(o), sel["drop_mask"].data_ptr(), scale_ptr, dz.ptr)
             elif opts is not None:
                 Bp.keep.append(opts)
                 Bp.add("rua_head_dz_opts", kind, h["act"], h["p"].ptr, h["y"].ptr, coef.data_ptr() if coef is not None else None,
@@ -1537,7 +1582,7 @@ class Graph:
         """Loss / metric launches and (training) the whole backward plan, in reverse creation order."""
         # multitask: the heads' Tanimoto finalisations and their d(loss)/d(logits) as one launch each (rua_tanimoto_finalize_multi, rua_head_dz_multi)
         self.multi_head = len(self.heads) > 1 and self.e.multi_head
-        self._tani_multi, self._dz_multi, self._dz_multi_opts, self._dz_emitted = [], [], [], False
+        self._tani_multi, self._dz_multi, self._dz_multi_opts, self._dz_multi_sel, self._dz_emitted = [], [], [], [], False
         for h in self.heads:
             self.cur_tag = self.loss_plan.scope = "loss_" + h["name"]
             self.head_loss(h)
@@ -1767,6 +1812,21 @@ class Engine:
             nc = 3 if h == "color" else self.cfg.num_classes
             LS.check_options(kind, nc, spec.focal_gamma.get(h, 0.0), spec.class_weights if kind == L.LOSS_FOCAL_CE else spec.focal_alpha.get(h, 0.0),
                              spec.class_balance.get(h, False), spec.label_smoothing.get(h, 0.0), what=h)
+        # online hard example mining: per-pixel losses only (Tanimoto has no per-pixel map); a probability threshold means -log p only where the
+        # per-pixel loss IS -log p of the true class: plain CE, or weighted CE with unit weights, without smoothing
+        for h, o in spec.ohem.items():
+            if h not in spec.kind:
+                raise ValueError(f"ohem: '{h}' is not a head of this model ({', '.join(spec.kind)})")
+            if spec.kind[h] == L.LOSS_TANIMOTO:
+                raise ValueError(f"{h}: online hard example mining needs a per-pixel loss, the Tanimoto loss has none")
+            if not isinstance(o, dict):
+                raise ValueError(f"{h}: ohem options are a dict (losses.ohem_options), got {type(o).__name__}")
+            LS.check_ohem(o, what=f"{h}: ohem")
+            if o.get("prob_thresh") is not None:
+                unit = spec.kind[h] == L.LOSS_WCE and spec.class_weights is not None and all(float(w) == 1.0 for w in spec.class_weights)
+                if not (spec.kind[h] == L.LOSS_CE_LOGITS or unit) or float(spec.label_smoothing.get(h, 0.0)) != 0.0:
+                    raise ValueError(f"{h}: prob_thresh goes with plain categorical cross-entropy (or weighted CE with unit weights) without label "
+                                     "smoothing only; give loss_thresh for the other losses")
 
     def accumulation_state(self) -> Optional[Dict[str, int]]:
         """gradient_accumulation_steps: dict(steps=K, micro=gradients of the current cycle already accumulated, 0 .. K - 1); None with the
@@ -1877,6 +1937,25 @@ class Engine:
         torch.cuda.synchronize()
         r = self.clip["report"].cpu().numpy()
         return dict(norm=float(r[0]), min_coef=float(r[1]), skipped=int(r[2]), clipped=int(r[3]))
+
+    def ohem_report(self) -> Optional[Dict[str, dict]]:
+        """Online hard example mining: what rua_ohem_select left for the last training step, per mining head - kept (n_kept / n_valid, 0 with no
+        valid pixel), tau (the loss value of the threshold key), tau_key, K, n_kept, n_valid, q16_used, kept_sum, scale.  None when no head mines
+        or no training step has run.  Under data parallel and accumulation these are this rank's, this micro-batch's.  Synchronises the device."""
+        if self.loss is None or not self.loss.ohem:
+            return None
+        g = self.graphs.get((getattr(self, "_last_B", None), True))
+        if g is None:
+            return None
+        torch.cuda.synchronize()
+        out = {}
+        for h in g.heads:
+            if "ohem" not in h:
+                continue
+            r = L.OhemResult.from_buffer_copy(h["ohem"]["result"].cpu().numpy().tobytes())
+            out[h["name"]] = dict(kept=r.n_kept / r.n_valid if r.n_valid else 0.0, tau=float(r.tau), tau_key=int(r.tau_key), K=int(r.K), n_kept=int(r.n_kept),
+                                  n_valid=int(r.n_valid), q16_used=int(r.q16_used), kept_sum=float(r.kept_sum), scale=float(r.scale))
+        return out
 
     def _backup_state(self, s):
         """skip_nonfinite: the BatchNorm moving statistics as the step finds them (the forward folds the batch into them before anyone knows
@@ -2145,6 +2224,8 @@ class Engine:
         g = self.graph(B, True)
         s = self._stream()
         self._put_batch(g, x, y, norm_type, void_mask=void_mask, photo=photo)
+        if any(o.get("warmup") for o in self.loss.ohem.values()):      # rua_ohem_select reads the step counter in front of the optimizer launch
+            self._sync_lr_state()
         self._zero_arena(g, s)
         if not self._s_backed:                              # the first forward since an optimizer step: the state this step begins with
             self._backup_state(s)
@@ -2189,14 +2270,7 @@ class Engine:
         sp = self.loss
         if self._in_ema:
             raise RuntimeError("a training step inside ema_weights(): P holds the averaged weights; leave the block first")
-        if sp.lr_schedule is not None:
-            # the rate kernel writes the base rate itself (lr_state[1]) from the counter: only a counter changed from outside (a checkpoint) is pushed
-            if self._t_dev != self.t:
-                self.lr_state.copy_(torch.tensor([float(self.t), SC.host_lr(sp.lr_schedule, self.t)], dtype=torch.float64))
-                self._t_dev, self._lr_base_dev = self.t, None
-        elif self._t_dev != self.t or self._lr_base_dev != sp.lr:
-            self.lr_state.copy_(torch.tensor([float(self.t), float(sp.lr)], dtype=torch.float64))
-            self._t_dev, self._lr_base_dev = self.t, sp.lr
+        self._sync_lr_state()
         k = sp.gradient_accumulation_steps
         if k is not None:
             # gradient accumulation: the gate of this step's optimizer launch advances the device's micro counter and decides hold / update from
@@ -2210,6 +2284,20 @@ class Engine:
                 return
         self.t += 1
         self._t_dev += 1                                    # the optimizer launch of this step advances the device counter
+
+    def _sync_lr_state(self):
+        """The device pair [steps taken, base rate] brought up to the host's, where they were changed from outside.  _set_lr's first half; a
+        forward_backward() of a model that mines hard examples under a warm-up calls it too, since rua_ohem_select reads the counter in front of
+        the optimizer launch."""
+        sp = self.loss
+        if sp.lr_schedule is not None:
+            # the rate kernel writes the base rate itself (lr_state[1]) from the counter: only a counter changed from outside (a checkpoint) is pushed
+            if self._t_dev != self.t:
+                self.lr_state.copy_(torch.tensor([float(self.t), SC.host_lr(sp.lr_schedule, self.t)], dtype=torch.float64))
+                self._t_dev, self._lr_base_dev = self.t, None
+        elif self._t_dev != self.t or self._lr_base_dev != sp.lr:
+            self.lr_state.copy_(torch.tensor([float(self.t), float(sp.lr)], dtype=torch.float64))
+            self._t_dev, self._lr_base_dev = self.t, sp.lr
 
     def _launch_optimizer(self, grad_scale, s):
         sp = self.loss

@@ -338,6 +338,60 @@ class MeanSquaredError:
     kind = L.LOSS_MSE
 
 
+class OnlineHardExampleMining:
+    """Online hard example mining (bootstrapped cross-entropy) around any per-pixel loss object or name the package accepts: per training step
+    only the head's hardest pixels contribute - the keep_ratio share of the valid pixels with the largest loss, never fewer than min_kept, and
+    every pixel whose loss is at least loss_thresh (prob_thresh = p: loss_thresh = float32(-log p), mmsegmentation's OHEMPixelSampler for plain
+    cross-entropy).  warmup_steps: optimizer updates over which the share falls from 1 to keep_ratio.  losses.host_ohem is the definition; the
+    selection runs on the GPU (rua_ohem_select) inside the training step; evaluation reports the plain mean.  Calling the object on
+    (y_true, y_pred) returns the (B,H,W) keep map (1 = kept) of that batch from the GPU, taken with the final share (no warm-up)."""
+
+    def __init__(self, loss, keep_ratio=0.25, min_kept=0, loss_thresh=None, prob_thresh=None, warmup_steps=0):
+        if loss_thresh is not None and prob_thresh is not None:
+            raise ValueError("loss_thresh and prob_thresh: one of them")
+        self.loss = _named_loss(loss)
+        if isinstance(self.loss, OnlineHardExampleMining):
+            raise ValueError("OnlineHardExampleMining does not nest")
+        self.keep_ratio, self.min_kept, self.warmup_steps = float(keep_ratio), min_kept, warmup_steps
+        self.loss_thresh, self.prob_thresh = loss_thresh, prob_thresh
+        self.options = LS.ohem_options(LS.ohem_q16(keep_ratio), min_kept, loss_thresh, prob_thresh, warmup_steps)
+        LS.check_ohem(self.options, what="OnlineHardExampleMining")
+
+    @property
+    def kind(self):
+        if isinstance(self.loss, str):
+            if self.loss not in _LOSS_NAMES:
+                raise ValueError(f"unknown loss '{self.loss}'")
+            return _LOSS_NAMES[self.loss]
+        return getattr(self.loss, "kind", None)
+
+    @property
+    def weights(self):
+        return getattr(self.loss, "weights", None)
+
+    def __getattr__(self, name):                         # label_smoothing, gamma, alpha, ...: the wrapped loss's
+        if name in ("loss", "options"):
+            raise AttributeError(name)
+        return getattr(self.loss, name)
+
+    def __call__(self, y_true, y_pred):
+        if not callable(self.loss):
+            raise TypeError("the keep map needs a loss object that returns its (B,H,W) map when called")
+        per = np.ascontiguousarray(self.loss(y_true, y_pred), np.float32)
+        M = per.size
+        lib = L.lib()
+        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        pp = _dev_f32(per.reshape(-1))
+        nws = int(lib.raw("rua_ohem_workspace_bytes")(M))
+        ws = torch.empty(nws // 8 + 1, dtype=torch.float64, device="cuda")
+        drop = torch.empty(M, dtype=torch.uint8, device="cuda")
+        out = torch.zeros(1, dtype=torch.float64, device="cuda")
+        res = torch.zeros(C.sizeof(L.OhemResult) // 8, dtype=torch.float64, device="cuda")
+        o = LS.to_ohem_struct(self.options)
+        lib.call("rua_ohem_select", pp.data_ptr(), None, M, C.byref(o), None, 1.0, ws.data_ptr(), nws, drop.data_ptr(), out.data_ptr(), res.data_ptr(), s)
+        return (1 - drop.cpu().numpy()).astype(np.uint8).reshape(per.shape)
+
+
 _LOSS_NAMES = {"categorical_crossentropy": L.LOSS_CE_LOGITS, "binary_crossentropy": L.LOSS_BCE_LOGITS,
                "mse": L.LOSS_MSE, "mean_squared_error": L.LOSS_MSE, "tanimoto": L.LOSS_TANIMOTO,
                "categorical_focal_crossentropy": L.LOSS_FOCAL_CE, "binary_focal_crossentropy": L.LOSS_FOCAL_BCE}
@@ -481,10 +535,13 @@ class Model:
         heads = HEADS if self.cfg.multitasking else ["seg"]
         kinds, cw = {}, None
         lopts = {k: {} for k in LS.OPTION_KEYS}
+        mining = {}
         for h in heads:
             l = _named_loss(loss[h] if isinstance(loss, dict) else loss)
             kinds[h], w = _loss_kind(l, h)
             _loss_head_options(l, h, lopts)
+            if isinstance(l, OnlineHardExampleMining):
+                mining[h] = dict(l.options)
             if kinds[h] == L.LOSS_FOCAL_CE:                  # the per-class alpha travels as the class weights (one vector per model, as weighted CE's)
                 w = l.alpha_vector(self.cfg.num_classes)
                 if len(w) != self.cfg.num_classes:
@@ -500,7 +557,7 @@ class Model:
             weights.update({h: float(loss_weights[h]) for h in heads if h in loss_weights})
         spec = LossSpec(kind=kinds, weight=weights, class_weights=cw, optimizer=optimizer.kind, lr=optimizer.lr.value,
                         beta_1=getattr(optimizer, "beta_1", 0.9), beta_2=getattr(optimizer, "beta_2", 0.999),
-                        momentum=getattr(optimizer, "momentum", 0.0), epsilon=getattr(optimizer, "epsilon", 1e-7), ignore_void=margin, **lopts,
+                        momentum=getattr(optimizer, "momentum", 0.0), epsilon=getattr(optimizer, "epsilon", 1e-7), ignore_void=margin, **lopts, ohem=mining,
                         **(optimizer.clip_options() if hasattr(optimizer, "clip_options") else {}),
                         **(optimizer.sched_options() if hasattr(optimizer, "sched_options") else {}),
                         **(optimizer.accum_options() if hasattr(optimizer, "accum_options") else {}))
@@ -535,6 +592,11 @@ class Model:
         """Engine.trust_report: dict(min_ratio, max_ratio, forced, updates, ratios={variable name: ratio}) of the last LAMB update, or None when
         the optimizer is not Lamb.  Synchronises the device."""
         return self.engine.trust_report()
+
+    def ohem_report(self):
+        """Engine.ohem_report: per mining head dict(kept - the kept share of the last training step's valid pixels -, tau, tau_key, K, n_kept,
+        n_valid, q16_used, kept_sum, scale), or None when no head was compiled with OnlineHardExampleMining.  Synchronises the device."""
+        return self.engine.ohem_report()
 
     def accumulation_state(self):
         """Adam / SGD(gradient_accumulation_steps=K): dict(steps=K, micro=calls of train_on_batch since the last update, 0 .. K - 1); None with

@@ -101,8 +101,145 @@ def to_struct(gamma: float = 0.0, label_smoothing: float = 0.0, alpha: Optional[
 
 
 def options_from_meta(lo: dict) -> Dict[str, dict]:
-    """The four per-head dicts out of a checkpoint's `loss` metadata; a file written before the options existed has none: empty dicts."""
-    return {k: dict(lo.get(k) or {}) for k in OPTION_KEYS}
+    """The four per-head dicts out of a checkpoint's `loss` metadata; a file written before the options existed has none: empty dicts.  A file
+    whose model mined hard examples carries a fifth, `ohem` (head -> ohem_options' dict); it is handed on only where the file has it."""
+    out = {k: dict(lo.get(k) or {}) for k in OPTION_KEYS}
+    if lo.get(OHEM_KEY):
+        out[OHEM_KEY] = {h: ohem_options(**dict(o)) for h, o in lo[OHEM_KEY].items()}
+    return out
+
+
+# ---- online hard example mining (OHEM, bootstrapped cross-entropy) ----------------------------------------------------------------------------
+# Per step and per head only the hardest pixels contribute: those whose loss lies above a threshold, but never fewer than a floor.  host_ohem is
+# the definition; rua_ohem_select (csrc/ohem.hip) computes the same selection on the device bit for bit, and the head's gradient takes the mask and
+# the normaliser from device memory (rua_head_dz_sel / rua_head_dz_multi_sel).  All parameters are integers or one float32, so that host and
+# device agree exactly:
+#   min_kept   int >= 0               the floor
+#   keep_q16   int in 1..65536        the kept share of the valid pixels in Q16 (ohem_q16 turns a ratio into it)
+#   thresh     a float32 or None      a loss value: every valid pixel at or above it is kept as well
+#   warmup     int >= 0               optimizer updates over which the share falls linearly from 1 to keep_q16
+# With thresh = -log(0.7), keep_q16 = 1 and min_kept = 100000 this is mmsegmentation's OHEMPixelSampler for plain cross-entropy; with no thresh and
+# keep_q16 = 0.25 * 65536 it is bootstrapped cross-entropy at 25 %.
+OHEM_KEY = "ohem"                                        # LossSpec's fifth per-head dict and the checkpoint's key
+OHEM_FIELDS = ("keep_q16", "min_kept", "thresh", "prob_thresh", "warmup")
+NO_KEY = 0xFFFFFFFF                                      # the key of a NaN, and tau_key's stand-in for "no valid pixel"
+
+
+def ohem_key(values) -> np.ndarray:
+    """The order-preserving uint32 key of float32 values: all bits of a negative flipped, the sign bit of a non-negative set (so -0 < +0);
+    every NaN maps to 0xFFFFFFFF, the hardest key."""
+    b = np.ascontiguousarray(values, np.float32).view(np.uint32)
+    k = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+    return np.where((b & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000), np.uint32(NO_KEY), k).astype(np.uint32)
+
+
+def ohem_unkey(key: int) -> np.float32:
+    """The float32 a key stands for (0xFFFFFFFF: a NaN)."""
+    k = int(key) & 0xFFFFFFFF
+    b = (k ^ 0x80000000) if k & 0x80000000 else (~k & 0xFFFFFFFF)
+    return np.array([b], np.uint32).view(np.float32)[0]
+
+
+def ohem_q16(keep_ratio: float) -> int:
+    """A kept share in (0, 1] as the Q16 integer the selection works with (rounded to nearest, at least 1)."""
+    r = float(keep_ratio)
+    if not 0.0 < r <= 1.0:
+        raise ValueError(f"keep_ratio {keep_ratio!r} must be in (0, 1]")
+    return min(65536, max(1, int(round(r * 65536.0))))
+
+
+def ohem_share(keep_q16: int, warmup: int, t: int) -> int:
+    """q(t): the share in Q16 after t optimizer updates - 65536 - ((65536 - keep_q16) * min(t, warmup)) // warmup, keep_q16 with no warm-up."""
+    if int(warmup) <= 0:
+        return int(keep_q16)
+    return 65536 - ((65536 - int(keep_q16)) * min(max(int(t), 0), int(warmup))) // int(warmup)
+
+
+def ohem_count(n_valid: int, q16: int, min_kept: int) -> int:
+    """K = min(n_valid, max(min_kept, (n_valid * q + 65535) >> 16))."""
+    return min(int(n_valid), max(int(min_kept), (int(n_valid) * int(q16) + 65535) >> 16))
+
+
+def prob_to_thresh(prob_thresh: float) -> float:
+    """mmsegmentation's probability threshold as a loss value of plain cross-entropy: float32(-log p)."""
+    p = float(prob_thresh)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"prob_thresh {prob_thresh!r} must be in (0, 1]")
+    return float(np.float32(-np.log(p)))
+
+
+def ohem_options(keep_q16: int = 16384, min_kept: int = 0, thresh: Optional[float] = None, prob_thresh: Optional[float] = None, warmup: int = 0) -> dict:
+    """One head's options as the plain dict LossSpec.ohem and the checkpoint hold; prob_thresh = p stands for thresh = float32(-log p)."""
+    if prob_thresh is not None:
+        if thresh is not None and float(np.float32(thresh)) != prob_to_thresh(prob_thresh):
+            raise ValueError("loss_thresh and prob_thresh: one of them")
+        thresh = prob_to_thresh(prob_thresh)
+    return dict(keep_q16=keep_q16, min_kept=min_kept, thresh=None if thresh is None else float(np.float32(thresh)),
+                prob_thresh=None if prob_thresh is None else float(prob_thresh), warmup=warmup)
+
+
+def check_ohem(o: dict, what: str = "ohem"):
+    """The range of one head's options; raises ValueError."""
+    unknown = [k for k in o if k not in OHEM_FIELDS]
+    if unknown:
+        raise ValueError(f"{what}: unknown option(s) {unknown}")
+    isint = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    q, mk, wu, th = o.get("keep_q16", 16384), o.get("min_kept", 0), o.get("warmup", 0), o.get("thresh")
+    if not isint(q) or not 1 <= q <= 65536:
+        raise ValueError(f"{what}: keep_q16 {q!r} must be an integer in 1..65536")
+    if not isint(mk) or not 0 <= mk < 2 ** 62:
+        raise ValueError(f"{what}: min_kept {mk!r} must be an integer >= 0")
+    if not isint(wu) or not 0 <= wu < 2 ** 31:
+        raise ValueError(f"{what}: warmup {wu!r} must be an integer >= 0")
+    if th is not None and np.isnan(np.float32(th)):
+        raise ValueError(f"{what}: thresh is NaN")
+    if o.get("prob_thresh") is not None:
+        if th is None or float(np.float32(th)) != prob_to_thresh(o["prob_thresh"]):
+            raise ValueError(f"{what}: prob_thresh {o['prob_thresh']!r} and thresh {th!r} disagree")
+
+
+def to_ohem_struct(o: dict) -> "L.OhemOpts":
+    """rua_ohem_opts of one head."""
+    s = L.OhemOpts()
+    th = o.get("thresh")
+    s.min_kept, s.keep_q16, s.warmup = int(o.get("min_kept", 0)), int(o.get("keep_q16", 16384)), int(o.get("warmup", 0))
+    s.thresh, s.has_thresh = (float(np.float32(th)), 1) if th is not None else (0.0, 0)
+    return s
+
+
+def host_ohem(per_pixel, valid=None, keep_q16: int = 16384, min_kept: int = 0, thresh: Optional[float] = None, warmup: int = 0, t: int = 0,
+              loss_weight: float = 1.0) -> dict:
+    """The selection over one head's float32 per-pixel loss map L (any shape, as rua_pixel_loss* writes per_pixel) and valid (None: every pixel;
+    else non-zero = valid, the void mask's "byte == 0"):
+
+      n_valid = sum(valid);  q = ohem_share(keep_q16, warmup, t);  K = ohem_count(n_valid, q, min_kept)
+      tau_key = the K-th largest valid key (0xFFFFFFFF with no valid pixel), with thresh: min(tau_key, key(thresh))
+      kept    = valid and key(L) >= tau_key - ties at the threshold are all kept, so n_kept >= K and no order enters
+      loss    = (fp64 sum of L over the kept pixels) / n_kept, 0 for n_kept = 0;  scale = float32(float64(loss_weight) / n_kept), or 0
+
+    Returns dict(drop_mask uint8 of L's shape (0 kept, 1 dropped or void), tau_key, tau (float32), n_valid, n_kept, K, q16_used, kept_sum,
+    loss, scale (float32))."""
+    Lm = np.ascontiguousarray(per_pixel, np.float32)
+    key = ohem_key(Lm).reshape(-1)
+    v = np.ones(key.shape, bool) if valid is None else (np.asarray(valid).reshape(-1) != 0)
+    n_valid = int(v.sum())
+    q = ohem_share(keep_q16, warmup, t)
+    K = ohem_count(n_valid, q, min_kept)
+    tau_key = NO_KEY
+    if K > 0:
+        vk = key[v]
+        tau_key = int(np.partition(vk, n_valid - K)[n_valid - K])          # the K-th largest = the (n_valid - K)-th smallest, 0-based
+    if thresh is not None:
+        th = np.float32(thresh)
+        if np.isnan(th):
+            raise ValueError("thresh is NaN")
+        tau_key = min(tau_key, int(ohem_key(th).reshape(-1)[0]))
+    kept = v & (key >= np.uint32(tau_key))
+    n_kept = int(kept.sum())
+    kept_sum = float(np.sum(Lm.reshape(-1)[kept].astype(np.float64))) if n_kept else 0.0
+    return dict(drop_mask=(~kept).astype(np.uint8).reshape(Lm.shape), tau_key=tau_key, tau=ohem_unkey(tau_key), n_valid=n_valid, n_kept=n_kept, K=K,
+                q16_used=q, kept_sum=kept_sum, loss=kept_sum / n_kept if n_kept else 0.0,
+                scale=np.float32(np.float64(np.float32(loss_weight)) / np.float64(n_kept)) if n_kept else np.float32(0.0))     # (the C ABI takes loss_weight as a float32)
 
 
 def scalar_or_vector(alpha, num_classes: int) -> Sequence[float]:

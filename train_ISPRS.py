@@ -64,6 +64,12 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
     that is weighted cross entropy.  `--label_smoothing E` smooths the targets of the cross-entropy and focal losses (not `--loss
     tanimoto`; the MSE heads take none).  All on the GPU (resunet_a_mltsk_keras_amd/losses.py); with `-cp` the loss and its options come
     from the checkpoint.
+  * `--ohem yes [--ohem_keep 0.25] [--ohem_min_kept N] [--ohem_thresh T | --ohem_prob P] [--ohem_warmup N] [--ohem_heads seg bound]`: online
+    hard example mining (bootstrapped cross-entropy) - per step only the hardest pixels of the mining heads (default: seg) contribute to
+    loss and gradient: the `--ohem_keep` share of the valid pixels, never fewer than N, and every pixel whose loss is at least T
+    (`--ohem_prob P`, `--loss cross_entropy` only: T = -log P).  The exact selection runs on the GPU inside the captured step
+    (resunet_a_mltsk_keras_amd/losses.py, csrc/ohem.hip); validation reports the plain mean.  Not with `--loss tanimoto`.  The per-epoch
+    line prints the kept share and the threshold of the last step.
   * `--dtype {bf16,f32}`, `--seed`: engine options.  Launch with torch.distributed.run for multi-GPU data
     parallel (`-bs` is then the GLOBAL batch, as under MirroredStrategy).
 """
@@ -149,6 +155,15 @@ def build_parser():
                    help="--loss focal, multitasking: class balancing of the boundary head's binary focal loss with this alpha (default: none)")
     p.add_argument("--label_smoothing", type=float, default=0.0, metavar="E",
                    help="label smoothing of the cross-entropy and focal losses, in [0, 1) (not --loss tanimoto; the MSE heads take none)")
+    p.add_argument("--ohem", type=str2bool, default=False,
+                   help="online hard example mining: per step only the hardest pixels of the --ohem_heads contribute to loss and gradient, selected on the GPU")
+    p.add_argument("--ohem_keep", type=float, default=0.25, metavar="R", help="ohem: the kept share of the valid pixels, in (0, 1]")
+    p.add_argument("--ohem_min_kept", type=int, default=0, metavar="N", help="ohem: never fewer than N pixels per step (and head)")
+    p.add_argument("--ohem_thresh", type=float, default=None, metavar="T", help="ohem: keep every pixel whose loss is at least T as well")
+    p.add_argument("--ohem_prob", type=float, default=None, metavar="P",
+                   help="ohem, --loss cross_entropy: the threshold as a probability of the true class, T = -log P (mmsegmentation's OHEMPixelSampler)")
+    p.add_argument("--ohem_warmup", type=int, default=0, metavar="N", help="ohem: the kept share falls from 1 to --ohem_keep over the first N optimizer updates")
+    p.add_argument("--ohem_heads", nargs="+", choices=["seg", "bound"], default=["seg"], help="ohem: the mining heads (bound needs --multitasking yes)")
     p.add_argument("--balance_class", type=int, default=None, metavar="K",
                    help="scene directory: train only on windows in which class K covers at least --balance_percent of the pixels")
     p.add_argument("--balance_percent", type=float, default=None, metavar="P", help="balance_class: the share of the window, in percent")
@@ -346,6 +361,34 @@ def check_loss_flags(args):
     return alpha
 
 
+def check_ohem_flags(args):
+    """--ohem and its flags checked against --loss and the rest of the command line, before anything is loaded: returns the keyword arguments of
+    keras_api.OnlineHardExampleMining (None: off); SystemExit with a message otherwise."""
+    from resunet_a_mltsk_keras_amd import losses as LS
+    given = [n for n, v, d in (("--ohem_keep", args.ohem_keep, 0.25), ("--ohem_min_kept", args.ohem_min_kept, 0), ("--ohem_thresh", args.ohem_thresh, None),
+                               ("--ohem_prob", args.ohem_prob, None), ("--ohem_warmup", args.ohem_warmup, 0), ("--ohem_heads", args.ohem_heads, ["seg"])) if v != d]
+    if not args.ohem:
+        if given:
+            sys.exit(f"{given[0]} belongs to --ohem yes")
+        return None
+    if args.checkpoint_path is not None:
+        sys.exit("--ohem: with --checkpoint_path the loss, its options included, comes from the checkpoint")
+    if args.loss == "tanimoto":
+        sys.exit("--ohem needs a per-pixel loss: the Tanimoto loss has none")
+    if "bound" in args.ohem_heads and not args.multitasking:
+        sys.exit("--ohem_heads bound: the boundary head needs --multitasking yes")
+    if args.ohem_thresh is not None and args.ohem_prob is not None:
+        sys.exit("--ohem_thresh and --ohem_prob both name the threshold: give one of them")
+    if args.ohem_prob is not None and (args.loss != "cross_entropy" or args.label_smoothing or args.ohem_heads != ["seg"]):
+        sys.exit("--ohem_prob means -log P of the true class: --loss cross_entropy without --label_smoothing, on the seg head; give --ohem_thresh otherwise")
+    try:
+        kw = dict(keep_ratio=args.ohem_keep, min_kept=args.ohem_min_kept, loss_thresh=args.ohem_thresh, prob_thresh=args.ohem_prob, warmup_steps=args.ohem_warmup)
+        LS.check_ohem(LS.ohem_options(LS.ohem_q16(kw["keep_ratio"]), kw["min_kept"], kw["loss_thresh"], kw["prob_thresh"], kw["warmup_steps"]), what="--ohem")
+    except ValueError as exc:
+        sys.exit(f"--ohem: {exc}")
+    return kw
+
+
 def print_class_histogram(say, counts, num_classes):
     """Pixels and share per class of int64 [N][C + 1] window counts, and the share of pixels that carry no class (>= C)."""
     n = counts.sum(0)
@@ -506,6 +549,9 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
         if trust is not None:
             say(f"LAMB trust ratio: {trust['min_ratio']:.6g} .. {trust['max_ratio']:.6g} over {len(trust['ratios'])} variables "
                 f"({trust['forced']} forced to 1; {trust['updates']} updates so far)")
+        mined = net.ohem_report() if hasattr(net, "ohem_report") else None     # None: no head mines hard examples
+        if mined:
+            say("Hard example mining (last step): " + "; ".join(f"{h} kept {r['kept']:.4f} of {r['n_valid']} valid pixels, tau {r['tau']:.6g}" for h, r in mined.items()))
         val_loss = agree_from_rank0(vm["loss"], world)
         if val_loss >= min_loss + delta:
             cont += 1
@@ -528,6 +574,7 @@ def main(argv=None):
     check_photo_flags(args)
     class_weights = check_class_flags(args)
     focal_alpha = check_loss_flags(args)
+    ohem_kw = check_ohem_flags(args)
     void_margin = check_void_flags(args)
     import torch
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -616,6 +663,14 @@ def main(argv=None):
         weights = class_weights if class_weights is not None else REFERENCE_WCE_WEIGHTS if args.num_classes == 5 else [1.0] * args.num_classes
         say(weights)
         loss, loss_bound, loss_reg = weighted_categorical_crossentropy(weights, label_smoothing=ls), BinaryCrossentropy(label_smoothing=ls), MeanSquaredError()
+    if ohem_kw is not None:
+        from resunet_a_mltsk_keras_amd.keras_api import OnlineHardExampleMining
+        say(f"Online hard example mining on {', '.join(args.ohem_heads)}: keep {args.ohem_keep:g} of the valid pixels, at least {args.ohem_min_kept}, "
+            f"loss threshold {args.ohem_thresh if args.ohem_prob is None else f'-log {args.ohem_prob:g}'}, warm-up {args.ohem_warmup} updates")
+        if "seg" in args.ohem_heads:
+            loss = OnlineHardExampleMining(loss, **ohem_kw)
+        if "bound" in args.ohem_heads:
+            loss_bound = OnlineHardExampleMining(loss_bound, **ohem_kw)
     say("=" * 60)
 
     if args.checkpoint_path is None:
