@@ -363,6 +363,14 @@ int rua_bn_bwd(const rua_bn_bwd_desc* d, void* stream);
  * that cannot share a grid - several branches, skip statistics, unequal shapes - are launched one by one).  ..._last_grids: 1 or n. */
 int rua_bn_bwd_group(const rua_bn_bwd_desc* d, int n, void* stream);
 int rua_bn_bwd_group_last_grids(void);
+/* The form a fused BatchNorm launch takes, from the descriptor alone (no device needed, nothing launched): 0 = pixel-major (blocks cut the tensor along
+ * pixels, every block derives every channel's coefficients), else S | P << 8 = channel-sliced (small maps: a block owns S 16-byte pieces per pixel - S = 8 is one
+ * 128-byte line - of one of P contiguous pixel parts, rua_bn_part_range, and derives its own S * 8 bf16 / S * 4 fp32 channels only).  P never exceeds the replica
+ * count of a statistics output (skip_stats, dx_stats), so each address receives one add and the sums are reproducible bit for bit.  out and dx are bit-identical
+ * between the forms; tuning key bn_sliced = 0 keeps every launch pixel-major.  A group is sliced when every member's own route is; each member keeps its own P. */
+int rua_bn_fwd_route(const rua_bn_fwd_desc* d);
+int rua_bn_bwd_route(const rua_bn_bwd_desc* d);
+int rua_bn_part_range(int64_t M, int P, int part, int64_t* begin, int64_t* end);   /* pixels [begin, end) of part 0 <= part < P <= M */
 
 /* ---- pooling / resampling (PSPPooling model2.py:47-60; decoder model2.py:91) ---------- */
 /* The max-pool (rua_maxpool_fwd, and rua_maxpool_derive with the same results) scans its window row-major with `v > best` from -inf: the FIRST maximum wins
@@ -1057,7 +1065,7 @@ int rua_graph_kernel_nodes(void* graph, int* kernels, int* total);
  *   wgd_ks_slow, head_fwd2, head_fwd3, head_fwd3_bpc, stem_reg, stats_blocks, conv_band, conv_band64,
  *   conv_band64m, strip_group_share, band_dbg, fill_kernel, bn_regs, wgrad_taps_share, dmap_chain, epi_fast,
  *   dmap_spread, bn_bwd_group, conv_small, strip_stag, cu_reserve, wgrad_rows, strip_seglen, band_stag,
- *   conv_band128m, conv_img2, dbg_ptr */
+ *   conv_band128m, conv_img2, bn_sliced, bn_sliced_parts, bn_sliced_s, dbg_ptr */
 int rua_set_tuning(const char* key, int64_t value);
 int rua_get_tuning(const char* key, int64_t* value);
 const char* rua_tuning_key(int index);

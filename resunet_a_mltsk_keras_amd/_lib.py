@@ -175,6 +175,9 @@ _SIGS = {
     "rua_bn_bwd": ([C.POINTER(BnBwdDesc), vp], i32),
     "rua_bn_bwd_group": ([C.POINTER(BnBwdDesc), i32, vp], i32),
     "rua_bn_bwd_group_last_grids": ([], i32),
+    "rua_bn_fwd_route": ([C.POINTER(BnFwdDesc)], i32),
+    "rua_bn_bwd_route": ([C.POINTER(BnBwdDesc)], i32),
+    "rua_bn_part_range": ([i64, i32, i32, C.POINTER(i64), C.POINTER(i64)], i32),
     "rua_maxpool_fwd": ([vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     "rua_maxpool_bwd": ([vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "rua_sumpool": ([vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),

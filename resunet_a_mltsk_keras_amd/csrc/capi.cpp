@@ -129,6 +129,7 @@ static const TuneKey* tune_table(int* n) {
     {"bn_bwd_group", &g_tune.bn_bwd_group, nullptr}, {"conv_small", &g_tune.conv_small, nullptr}, {"strip_stag", &g_tune.strip_stag, nullptr},
     {"cu_reserve", &g_tune.cu_reserve, nullptr}, {"wgrad_rows", &g_tune.wgrad_rows, nullptr}, {"strip_seglen", &g_tune.strip_seglen, nullptr},
     {"band_stag", &g_tune.band_stag, nullptr}, {"conv_band128m", &g_tune.conv_band128m, nullptr}, {"conv_img2", &g_tune.conv_img2, nullptr},
+    {"bn_sliced", &g_tune.bn_sliced, nullptr}, {"bn_sliced_parts", &g_tune.bn_sliced_parts, nullptr}, {"bn_sliced_s", &g_tune.bn_sliced_s, nullptr},
     {"dbg_ptr", nullptr, &g_tune.dbg_ptr},
   };
   *n = (int)(sizeof(t) / sizeof(t[0]));

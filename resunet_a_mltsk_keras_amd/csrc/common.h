@@ -91,7 +91,9 @@ struct RuaTuning {
   int epi_fast = 1;                     // conv_dmap: compile-time forms of the epilogue for whole tiles (conv_epilogue KIND)
   int dmap_chain = 0;                   // grouped conv_dmap members back to back inside one block (conv_dmap_chain): bit 0 the 128-row tiles, bit 1 the 64-row tiles
   int wgrad_taps_share = 1;             // all-taps weight gradients of a group share one round of blocks (rua_wgrad_desc.group_members)
-  int bn_regs = 1;                      // BatchNorm sweeps with the thread's coefficients in registers (0: read from the LDS table per piece)
+  int bn_sliced = 1;                    // the fused BatchNorm launches on small maps in the channel-sliced form (elementwise.hip, bn_route): 0 pixel-major everywhere, 2 sliced wherever eligible (tools/bench_bn_small.py)
+  int bn_sliced_parts = 0, bn_sliced_s = 0;   // experiments and tests: that many pixel parts (0: the chooser's) / half-line slices (4) where whole lines fit too
+  int bn_regs = 1;                    // BatchNorm sweeps with the thread's coefficients in registers (0: read from the LDS table per piece)
   int fill_kernel = 1;                  // rua_fill_zero as a kernel, not hipMemsetAsync: no memset nodes in captured graphs (0: experiments, tools/dp_graph_check.py)
   int band_dbg = 0;                     // experiments only (tools/bench_conv_band.py): 1 rows from an L2-resident region, 2 no BatchNorm pass
   int conv_band64m = 1;                 // the independent 3x3 convs of a C = 64 ResBlock (first convs, data gradients) as ONE conv_band64m launch

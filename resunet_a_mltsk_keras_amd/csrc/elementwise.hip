@@ -359,53 +359,84 @@ extern "C" int rua_bn_bwd_apply(int nb, const void* const* g, const float* const
 // block 0 also publishes the coefficients for later kernels (ReLU masks of data-gradient epilogues, backward) and
 // updates the moving statistics / parameter gradients.
 // NB > 0: the branch count, coefficients in registers (needs 256 % CG == 0); NB == 0: any shape, coefficients read from the LDS table
+//
+// Two forms share the coefficient formulas (bn_fwd_moments / bn_fwd_coef, bn_bwd_coef) and the per-piece expressions (bn_fwd_piece,
+// RUA_BN_BWD_PIECE): the pixel-major form (bn_fwd_body / bn_bwd_body: blocks cut the tensor along pixels, every block derives every channel)
+// and the channel-sliced form for small maps (bn_fwd_sliced_body / bn_bwd_sliced_body: a block owns S pieces per pixel and one of P pixel
+// parts, derives its own S * VEC channels only).  bn_route() chooses.
+
+// mean and variance of channel c from the statistics all branches share (training), else (0, 1)
+__device__ __forceinline__ void bn_fwd_moments(const rua_bn_fwd_desc& p, int c, double& mean, double& var) {
+  if (p.training && p.stats) {
+    double s1, s2;
+    replica_sum(p.stats, p.replicas, p.C, c, s1, s2);
+    mean = s1 / p.count;
+    var = s2 / p.count - mean * mean;
+    if (var < 0) var = 0;
+  } else { mean = 0; var = 1; }
+}
+// scale and shift of (branch, channel); `publish`: this thread also writes what later kernels read and updates the moving statistics
+__device__ __forceinline__ void bn_fwd_coef(const rua_bn_fwd_desc& p, const rua_bn_branch& br, int c, double mean, double var, bool publish,
+                                            float& scale, float& shift) {
+  const int C = p.C;
+  double m = mean, v = var;
+  if (p.training && br.stats) {                    // this branch normalises its own tensor (coefficient-only launches)
+    double s1, s2;
+    replica_sum(br.stats, br.replicas, C, c, s1, s2);
+    m = s1 / p.count;
+    v = s2 / p.count - m * m;
+    if (v < 0) v = 0;
+  }
+  if (!p.training) { m = br.moving_mean[c]; v = br.moving_var[c]; }
+  const double r = 1.0 / sqrt(v + (double)p.eps);
+  const double sc = (double)br.gamma[c] * r;
+  scale = (float)sc;
+  shift = (float)((double)br.beta[c] - m * sc);
+  if (publish) {
+    br.scale[c] = (float)sc; br.shift[c] = (float)((double)br.beta[c] - m * sc);
+    if (br.mean) br.mean[c] = (float)m;
+    if (br.rstd) br.rstd[c] = (float)r;
+    if (p.training && br.out_stats) {               // statistics of the OUTPUT (no ReLU), from the coefficients: exact up to the output's rounding
+      const double be = (double)br.beta[c];
+      br.out_stats[c] = p.count * be;
+      br.out_stats[C + c] = p.count * (be * be + sc * sc * v);
+    }
+    if (p.training && br.moving_mean) {
+      const double unb = p.bessel_n > 1 ? v * (p.bessel_n / (p.bessel_n - 1)) : v;
+      br.moving_mean[c] = (float)((double)br.moving_mean[c] * p.momentum + m * (1.0 - p.momentum));
+      br.moving_var[c] = (float)((double)br.moving_var[c] * p.momentum + unb * (1.0 - p.momentum));
+    }
+  }
+}
+// one piece of the sweep with the thread's coefficients in registers
+template <typename T, int NB>
+__device__ __forceinline__ void bn_fwd_piece(const unsigned char* x, unsigned char* const (&outs)[NB], long long i,
+                                             const float (&sc)[NB][ET<T>::VEC], const float (&sh)[NB][ET<T>::VEC], bool relu) {
+  constexpr int VEC = ET<T>::VEC;
+  float xv[VEC];
+  ET<T>::unpack(ldg16(x + i * 16), xv);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    float o[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      o[j] = fmaf(sc[b][j], xv[j], sh[b][j]);
+      if (relu) o[j] = fmaxf(o[j], 0.f);
+    }
+    stg16(outs[b] + i * 16, ET<T>::pack(o));
+  }
+}
+
 template <typename T, int NB>
 __device__ __forceinline__ void bn_fwd_body(const rua_bn_fwd_desc& p, long long pieces, int CG) {
   constexpr int VEC = ET<T>::VEC;
-  extern __shared__ float tab[];                       // [nb][2][C] scale/shift, then [2][C] mean/rstd
+  extern __shared__ float tab[];                       // [nb][2][C] scale/shift
   const int C = p.C;
-  float* mr = tab + p.nb * 2 * C;
   for (int c = threadIdx.x; c < C; c += 256) {
     double mean, var;
-    if (p.training && p.stats) {
-      double s1, s2;
-      replica_sum(p.stats, p.replicas, C, c, s1, s2);
-      mean = s1 / p.count;
-      var = s2 / p.count - mean * mean;
-      if (var < 0) var = 0;
-    } else { mean = 0; var = 1; }
-    for (int b = 0; b < p.nb; ++b) {
-      const rua_bn_branch& br = p.br[b];
-      double m = mean, v = var;
-      if (p.training && br.stats) {                    // this branch normalises its own tensor (coefficient-only launches)
-        double s1, s2;
-        replica_sum(br.stats, br.replicas, C, c, s1, s2);
-        m = s1 / p.count;
-        v = s2 / p.count - m * m;
-        if (v < 0) v = 0;
-      }
-      if (!p.training) { m = br.moving_mean[c]; v = br.moving_var[c]; }
-      const double r = 1.0 / sqrt(v + (double)p.eps);
-      const double sc = (double)br.gamma[c] * r;
-      tab[(b * 2) * C + c] = (float)sc;
-      tab[(b * 2 + 1) * C + c] = (float)((double)br.beta[c] - m * sc);
-      if (blockIdx.x == 0) {
-        br.scale[c] = (float)sc; br.shift[c] = (float)((double)br.beta[c] - m * sc);
-        if (br.mean) br.mean[c] = (float)m;
-        if (br.rstd) br.rstd[c] = (float)r;
-        if (p.training && br.out_stats) {               // statistics of the OUTPUT (no ReLU), from the coefficients: exact up to the output's rounding
-          const double be = (double)br.beta[c];
-          br.out_stats[c] = p.count * be;
-          br.out_stats[C + c] = p.count * (be * be + sc * sc * v);
-        }
-        if (p.training && br.moving_mean) {
-          const double unb = p.bessel_n > 1 ? v * (p.bessel_n / (p.bessel_n - 1)) : v;
-          br.moving_mean[c] = (float)((double)br.moving_mean[c] * p.momentum + m * (1.0 - p.momentum));
-          br.moving_var[c] = (float)((double)br.moving_var[c] * p.momentum + unb * (1.0 - p.momentum));
-        }
-      }
-    }
-    (void)mr;
+    bn_fwd_moments(p, c, mean, var);
+    for (int b = 0; b < p.nb; ++b)
+      bn_fwd_coef(p, p.br[b], c, mean, var, blockIdx.x == 0, tab[(b * 2) * C + c], tab[(b * 2 + 1) * C + c]);
   }
   __syncthreads();
   if (p.br[0].out == nullptr) return;                  // coefficients only
@@ -425,20 +456,7 @@ __device__ __forceinline__ void bn_fwd_body(const rua_bn_fwd_desc& p, long long 
 #pragma unroll
     for (int b = 0; b < NB; ++b) outs[b] = (unsigned char*)p.br[b].out;
     const bool relu = p.relu != 0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pieces; i += stride) {
-      float xv[VEC];
-      ET<T>::unpack(ldg16(x + i * 16), xv);
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        float o[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-          o[j] = fmaf(sc[b][j], xv[j], sh[b][j]);
-          if (relu) o[j] = fmaxf(o[j], 0.f);
-        }
-        stg16(outs[b] + i * 16, ET<T>::pack(o));
-      }
-    }
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pieces; i += stride) bn_fwd_piece<T, NB>(x, outs, i, sc, sh, relu);
   } else {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pieces; i += stride) {
       const int c = (int)(i % CG) * VEC;
@@ -466,20 +484,142 @@ static_assert(sizeof(BnFwdG) <= 4096, "grouped launch: kernel arguments are limi
 template <typename T>
 __global__ __launch_bounds__(256) void bn_fwd_kernel_g(const BnFwdG g, int CG) { bn_fwd_body<T, 1>(g.k[blockIdx.y], g.pieces[blockIdx.y], CG); }
 
+// ---- the channel-sliced form -------------------------------------------------------------------------------------------------------------
+// Block bx owns slice bx % slices (S pieces per pixel: S * VEC channels, S * 16 contiguous bytes) of part bx / slices of P contiguous pixel
+// parts.  Lane l holds piece l % S of pixel l / S for the whole sweep (256 / S pixels per step, every access a whole S * 16-byte segment), its
+// coefficients in registers.  The prologue derives the slice's channels only, one thread per (branch, channel); the blocks of part 0 publish.
+__host__ __device__ __forceinline__ long long bn_part_begin(long long M, int P, int part) { return M * part / P; }
+extern "C" int rua_bn_part_range(int64_t M, int P, int part, int64_t* begin, int64_t* end) {
+  RUA_CHECK_ARG(M > 0 && P >= 1 && P <= M && part >= 0 && part < P && begin && end, "rua_bn_part_range: bad arguments");
+  *begin = bn_part_begin(M, P, part); *end = bn_part_begin(M, P, part + 1);
+  return RUA_OK;
+}
+
+template <typename T, int NB, int S>
+__device__ __forceinline__ void bn_fwd_sliced_body(const rua_bn_fwd_desc& p, int P, int bx) {
+  constexpr int VEC = ET<T>::VEC, SV = S * VEC;
+  __shared__ float tab[NB * 2 * SV];                   // [nb][2][S * VEC] scale/shift of the slice
+  const int CG = p.C / VEC, slices = CG / S;
+  const int slice = bx % slices, part = bx / slices;
+  if (part >= P) return;                               // (a group's grid is as wide as its member of most parts)
+  for (int it = threadIdx.x; it < NB * SV; it += 256) {
+    const int b = it / SV, cl = it - b * SV, c = slice * SV + cl;
+    double mean, var;
+    bn_fwd_moments(p, c, mean, var);
+    bn_fwd_coef(p, p.br[b], c, mean, var, part == 0, tab[(b * 2) * SV + cl], tab[(b * 2 + 1) * SV + cl]);
+  }
+  __syncthreads();
+  const int q = (int)(threadIdx.x % S);
+  float sc[NB][VEC], sh[NB][VEC];
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) { sc[b][j] = tab[(b * 2) * SV + q * VEC + j]; sh[b][j] = tab[(b * 2 + 1) * SV + q * VEC + j]; }
+  unsigned char* outs[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) outs[b] = (unsigned char*)p.br[b].out;
+  const unsigned char* x = (const unsigned char*)p.x;
+  const bool relu = p.relu != 0;
+  const long long m1 = bn_part_begin(p.M, P, part + 1);
+  for (long long m = bn_part_begin(p.M, P, part) + threadIdx.x / S; m < m1; m += 256 / S)
+    bn_fwd_piece<T, NB>(x, outs, m * CG + slice * S + q, sc, sh, relu);
+}
+template <typename T, int NB, int S>
+__global__ __launch_bounds__(256) void bn_fwd_sliced_kernel(const rua_bn_fwd_desc p, int P) { bn_fwd_sliced_body<T, NB, S>(p, P, blockIdx.x); }
+struct BnFwdGS { rua_bn_fwd_desc k[RUA_MAX_BRANCH]; int P[RUA_MAX_BRANCH]; };
+static_assert(sizeof(BnFwdGS) <= 4096, "grouped launch: kernel arguments are limited to 4 KiB");
+template <typename T, int S>
+__global__ __launch_bounds__(256) void bn_fwd_sliced_kernel_g(const BnFwdGS g) { bn_fwd_sliced_body<T, 1, S>(g.k[blockIdx.y], g.P[blockIdx.y], blockIdx.x); }
+
+// The chooser.  Pixel-major launches at the HBM roof on large maps; on small maps its cost is the prologue (every block derives all nb * C
+// channels from r_in replicas) and the per-block, per-channel atomics of the statistics outputs.  r_out: the smallest replica count of the
+// launch's statistics outputs (0: none) - P stays at or below it, so every address receives ONE add and the sums are reproducible bit for bit.
+// Constants from tools/bench_bn_small.py (profiles/bn_sliced/): see DESIGN section 4.
+struct BnRoute { int S, P; };                          // S == 0: pixel-major
+constexpr long long RUA_BN_SLICED_BLOCKS = 512;        // blocks a launch aims at (two per CU of an MI355X; a constant, so a route never depends on the device)
+constexpr long long RUA_BN_SLICED_MAX_PIECES = 262144; // the crossover: launches of more 16-byte pieces (level 4 of cfg3: 8192 x 256 bf16) stay pixel-major ...
+constexpr long long RUA_BN_SLICED_MAX_STEPS = 8;       // ... and so do those whose blocks would sweep more steps each (P held down by the replicas of a statistics output)
+static BnRoute bn_route(long long M, int C, int dtype, int nb, int r_in, int r_out) {
+  BnRoute none = {0, 0};
+  if (g_tune.bn_sliced == 0 || M <= 0 || C <= 0 || nb < 1 || nb > RUA_MAX_BRANCH) return none;
+  const int vec = dtype == RUA_BF16 ? 8 : 4;
+  int S = C % (8 * vec) == 0 ? 8 : C % (4 * vec) == 0 ? 4 : 0;
+  if (g_tune.bn_sliced_s == 4 && C % (4 * vec) == 0) S = 4;              // experiments: half-line slices where whole lines fit too
+  if (S == 0) return none;
+  const long long slices = C / (S * vec), steps = (M + 256 / S - 1) / (256 / S);
+  long long P = (RUA_BN_SLICED_BLOCKS + slices - 1) / slices;             // enough blocks for the chip ...
+  if (P > steps) P = steps;                                               // ... of at least one step of pixels each
+  if (r_out > 0 && P > r_out) P = r_out;
+  if (g_tune.bn_sliced_parts > 0) P = g_tune.bn_sliced_parts < M ? g_tune.bn_sliced_parts : M;    // experiments and tests: any P in 1 .. M
+  if (P > 65535) P = 65535;
+  // the crossover (2: wherever eligible - the sweep of tools/bench_bn_small.py).  Measured, it is a matter of size alone: more branches and more input replicas
+  // only lengthen the pixel-major prologue, so nb and r_in move it nowhere a shipped shape reaches
+  (void)r_in;
+  if (g_tune.bn_sliced != 2 && (M * (C / vec) > RUA_BN_SLICED_MAX_PIECES || steps > RUA_BN_SLICED_MAX_STEPS * P)) return none;
+  BnRoute r = {S, (int)P};
+  return r;
+}
+static BnRoute bn_fwd_route_of(const rua_bn_fwd_desc& d) {
+  BnRoute none = {0, 0};
+  if (d.nb < 1 || d.nb > RUA_MAX_BRANCH || d.br[0].out == nullptr || (d.dtype != RUA_F32 && d.dtype != RUA_BF16)) return none;   // coefficient-only launches stay one block
+  int r_in = 0;
+  if (d.training) {
+    if (d.stats) r_in = d.replicas;
+    for (int b = 0; b < d.nb; ++b) if (d.br[b].stats && d.br[b].replicas > r_in) r_in = d.br[b].replicas;
+  }
+  return bn_route(d.M, d.C, d.dtype, d.nb, r_in, 0);
+}
+extern "C" int rua_bn_fwd_route(const rua_bn_fwd_desc* d) {
+  if (!d) return 0;
+  const BnRoute r = bn_fwd_route_of(*d);
+  return r.S ? (r.S | r.P << 8) : 0;
+}
+template <typename T, int S>
+static void bn_fwd_sliced_launch(const rua_bn_fwd_desc& d, int P, hipStream_t st) {
+  const dim3 g((unsigned)(d.C / (S * ET<T>::VEC) * P));
+  switch (d.nb) {
+    case 1: hipLaunchKernelGGL((bn_fwd_sliced_kernel<T, 1, S>), g, dim3(256), 0, st, d, P); break;
+    case 2: hipLaunchKernelGGL((bn_fwd_sliced_kernel<T, 2, S>), g, dim3(256), 0, st, d, P); break;
+    case 3: hipLaunchKernelGGL((bn_fwd_sliced_kernel<T, 3, S>), g, dim3(256), 0, st, d, P); break;
+    default: hipLaunchKernelGGL((bn_fwd_sliced_kernel<T, 4, S>), g, dim3(256), 0, st, d, P); break;
+  }
+}
+
 extern "C" int rua_bn_fwd(const rua_bn_fwd_desc* d, void* stream);
 static thread_local int g_bn_fwd_group_last = 0;
 extern "C" int rua_bn_fwd_group_last_grids(void) { return g_bn_fwd_group_last; }
 extern "C" int rua_bn_fwd_group(const rua_bn_fwd_desc* d, int n, void* stream) {
   RUA_CHECK_ARG(d && n >= 1 && n <= RUA_MAX_BRANCH, "rua_bn_fwd_group: 1..%d members", RUA_MAX_BRANCH);
   const int vec = d[0].dtype == RUA_BF16 ? 8 : 4;
-  bool one = n > 1 && g_tune.bn_bwd_group && d[0].C % vec == 0 && d[0].C / vec <= 256 && 256 % (d[0].C / vec) == 0 && g_tune.bn_regs &&
-             (d[0].dtype == RUA_F32 || d[0].dtype == RUA_BF16) && (size_t)4 * d[0].C * 4 <= 64 * 1024;
-  for (int i = 0; i < n && one; ++i) {
+  bool same = n > 1 && g_tune.bn_bwd_group && d[0].C > 0 && d[0].C % vec == 0 && (d[0].dtype == RUA_F32 || d[0].dtype == RUA_BF16);    // valid members of one shape family
+  for (int i = 0; i < n && same; ++i) {
     const rua_bn_fwd_desc& m = d[i];
     const rua_bn_branch& br = m.br[0];
-    one = m.x && m.nb == 1 && m.M > 0 && m.C == d[0].C && m.dtype == d[0].dtype && m.training == d[0].training && m.relu == d[0].relu && br.out &&
-          br.gamma && br.beta && br.scale && br.shift && (!m.training || (m.count > 0 && (br.stats ? br.replicas >= 1 : (m.stats && m.replicas >= 1)))) &&
-          (m.training || (br.moving_mean && br.moving_var)) && (br.out_stats == nullptr || (m.relu == 0 && m.training));
+    same = m.x && m.nb == 1 && m.M > 0 && m.C == d[0].C && m.dtype == d[0].dtype && m.training == d[0].training && m.relu == d[0].relu && br.out &&
+           br.gamma && br.beta && br.scale && br.shift && (!m.training || (m.count > 0 && (br.stats ? br.replicas >= 1 : (m.stats && m.replicas >= 1)))) &&
+           (m.training || (br.moving_mean && br.moving_var)) && (br.out_stats == nullptr || (m.relu == 0 && m.training));
+  }
+  const bool one = same && d[0].C / vec <= 256 && 256 % (d[0].C / vec) == 0 && g_tune.bn_regs && (size_t)4 * d[0].C * 4 <= 64 * 1024;
+  if (same) {                                            // channel-sliced where every member's own route is: each member keeps its own P
+    BnFwdGS a;
+    int S = 0, pmax = 0;
+    bool sliced = true;
+    for (int i = 0; i < n && sliced; ++i) {
+      const BnRoute r = bn_fwd_route_of(d[i]);
+      sliced = r.S != 0 && (i == 0 || r.S == S);
+      S = r.S; a.k[i] = d[i]; a.P[i] = r.P; if (r.P > pmax) pmax = r.P;
+    }
+    if (sliced) {
+      const dim3 g((unsigned)(d[0].C / (S * vec) * pmax), n);
+      hipStream_t st = (hipStream_t)stream;
+      if (d[0].dtype == RUA_BF16) { if (S == 8) hipLaunchKernelGGL((bn_fwd_sliced_kernel_g<bf16_t, 8>), g, dim3(256), 0, st, a);
+                                    else hipLaunchKernelGGL((bn_fwd_sliced_kernel_g<bf16_t, 4>), g, dim3(256), 0, st, a); }
+      else { if (S == 8) hipLaunchKernelGGL((bn_fwd_sliced_kernel_g<float, 8>), g, dim3(256), 0, st, a);
+             else hipLaunchKernelGGL((bn_fwd_sliced_kernel_g<float, 4>), g, dim3(256), 0, st, a); }
+      RUA_LAUNCH_CHECK("rua_bn_fwd_group");
+      g_bn_fwd_group_last = 1;
+      return RUA_OK;
+    }
   }
   g_bn_fwd_group_last = n;
   if (!one) {                                            // same results member by member
@@ -518,6 +658,13 @@ extern "C" int rua_bn_fwd(const rua_bn_fwd_desc* d, void* stream) {
     RUA_CHECK_ARG(d->training || (br.moving_mean && br.moving_var), "rua_bn_fwd: inference needs moving statistics");
     RUA_CHECK_ARG(br.out_stats == nullptr || (d->relu == 0 && d->training), "rua_bn_fwd: out_stats is the statistics of a training-mode BatchNorm WITHOUT ReLU");
   }
+  hipStream_t st = (hipStream_t)stream;
+  if (const BnRoute rt = bn_fwd_route_of(*d); rt.S) {
+    if (d->dtype == RUA_BF16) { if (rt.S == 8) bn_fwd_sliced_launch<bf16_t, 8>(*d, rt.P, st); else bn_fwd_sliced_launch<bf16_t, 4>(*d, rt.P, st); }
+    else { if (rt.S == 8) bn_fwd_sliced_launch<float, 8>(*d, rt.P, st); else bn_fwd_sliced_launch<float, 4>(*d, rt.P, st); }
+    RUA_LAUNCH_CHECK("rua_bn_fwd");
+    return RUA_OK;
+  }
   const size_t smem = (size_t)(d->nb * 2 + 2) * d->C * 4;
   RUA_CHECK_ARG(smem <= 64 * 1024, "rua_bn_fwd: coefficient table too large");
   const int CG = d->C / vec;
@@ -526,7 +673,6 @@ extern "C" int rua_bn_fwd(const rua_bn_fwd_desc* d, void* stream) {
   const int cap = g_tune.bn_grid > 0 ? g_tune.bn_grid : 2 * rua_cu_count();      // 512 on MI355X
   if ((long long)d->replicas * d->C >= 512 && g > cap) g = cap;      // the prologue re-reads replicas*C*2 doubles per block
   if (coef_only) g = 1;
-  hipStream_t st = (hipStream_t)stream;
   const int nbk = (!coef_only && CG <= 256 && 256 % CG == 0 && g_tune.bn_regs) ? d->nb : 0;
 #define RUA_BN_FWD_GO(T_, NB_) hipLaunchKernelGGL((bn_fwd_kernel<T_, NB_>), dim3(g), dim3(256), smem, st, *d, pieces, CG)
   if (d->dtype == RUA_BF16) {
@@ -545,6 +691,67 @@ extern "C" int rua_bn_fwd(const rua_bn_fwd_desc* d, void* stream) {
 // sweep in registers - 9.70 vs 9.68 ms per step; the blocks of one launch already overlap each other's prologue.)
 // DXS: the launch also takes the per-channel sums of dx and of dx * x (rua_bn_bwd_desc.dx_stats).  A template flag: the 16 accumulators take the
 // four-branch form from 124 to 144 registers (four waves per SIMD -> three: 42 -> 55 us on the 256 x 256 x 32 launch), which only the launches that ask pay.
+// backward coefficients of (branch, channel): dx = A g m + B x + C with the ReLU mask m = ms x + mt > 0; tb / tc are this branch's terms of B and C.
+// `publish`: this thread also adds the parameter gradients
+__device__ __forceinline__ void bn_bwd_coef(const rua_bn_bwd_desc& p, const rua_bn_bwd_branch& br, int c, bool publish,
+                                            float& A, float& ms, float& mt, float& tb, float& tc) {
+  double sg, sgx;
+  replica_sum(br.stats2, br.replicas, p.C, c, sg, sgx);
+  const double mu = br.mean[c], r = br.rstd[c], gm = br.gamma[c];
+  if (br.stats2_out) {                               // slot 1 holds sum g * (scale x + shift): back to sum g * x
+    const double sc = br.scale[c], sh = br.shift[c];
+    sgx = sc != 0.0 ? (sgx - sh * sg) / sc : mu * sg;
+  }
+  const double dga = r * (sgx - mu * sg);
+  const double s = gm * r;
+  A = (float)s;
+  ms = (p.masked && br.scale) ? br.scale[c] : 1.f;
+  mt = (p.masked && br.shift) ? br.shift[c] : 0.f;
+  tb = (float)(-s * r * dga / p.count);
+  tc = (float)(-s * sg / p.count + s * r * mu * dga / p.count);
+  if (publish) {
+    if (br.dgamma) br.dgamma[c] += (float)dga;
+    if (br.dbeta) br.dbeta[c] += (float)sg;
+  }
+}
+// One piece of the backward sweep with the thread's coefficients in registers, for both forms; every load of the piece is issued before the first use.
+// In scope: T, VEC, NB, MASKED, DXS, x, gp[NB], dskip, dx, accum, cA, cS, cT, cB, cC and sk / so / so2, the thread's per-channel sums of dskip, of dx and
+// of dx * x.  A macro: as an inlined function the same text took four registers more in the dx_stats forms (bn_bwd_kernel<bf16, 4, false, true>: 128 -> 132,
+// three waves per SIMD instead of four on the level-1 launches).
+#define RUA_BN_BWD_PIECE(i_) do { \
+  const long long pi_ = (i_); \
+  const uint4 xr = ldg16(x + pi_ * 16); \
+  uint4 gr[NB]; \
+  _Pragma("unroll") for (int b = 0; b < NB; ++b) gr[b] = ldg16(gp[b] + pi_ * 16); \
+  uint4 dr = make_uint4(0, 0, 0, 0), ar = make_uint4(0, 0, 0, 0); \
+  if (dskip) dr = ldg16(dskip + pi_ * 16); \
+  if (accum) ar = ldg16(dx + pi_ * 16); \
+  float xv[VEC], acc[VEC]; \
+  ET<T>::unpack(xr, xv); \
+  _Pragma("unroll") for (int j = 0; j < VEC; ++j) acc[j] = fmaf(cB[j], xv[j], cC[j]); \
+  if (dskip) { \
+    float dd[VEC]; \
+    ET<T>::unpack(dr, dd); \
+    _Pragma("unroll") for (int j = 0; j < VEC; ++j) { acc[j] += dd[j]; sk[j] += dd[j]; } \
+  } \
+  if (accum) { \
+    float dd[VEC]; \
+    ET<T>::unpack(ar, dd); \
+    _Pragma("unroll") for (int j = 0; j < VEC; ++j) acc[j] += dd[j]; \
+  } \
+  _Pragma("unroll") for (int b = 0; b < NB; ++b) { \
+    float gv[VEC]; \
+    ET<T>::unpack(gr[b], gv); \
+    _Pragma("unroll") for (int j = 0; j < VEC; ++j) { \
+      bool on = true; \
+      if constexpr (MASKED) on = fmaf(cS[b][j], xv[j], cT[b][j]) > 0.f; \
+      acc[j] = fmaf(cA[b][j], on ? gv[j] : 0.f, acc[j]); \
+    } \
+  } \
+  _Pragma("unroll") for (int j = 0; j < VEC; ++j) if constexpr (DXS) { so[j] += acc[j]; so2[j] = fmaf(acc[j], xv[j], so2[j]); } \
+  stg16(dx + pi_ * 16, ET<T>::pack(acc)); \
+} while (0)
+
 template <typename T, int NB, bool MASKED, bool DXS = false>
 __device__ __forceinline__ void bn_bwd_body(const rua_bn_bwd_desc& p, long long pieces, int CG) {
   constexpr int VEC = ET<T>::VEC;
@@ -556,25 +763,8 @@ __device__ __forceinline__ void bn_bwd_body(const rua_bn_bwd_desc& p, long long 
   // the block instead of one per branch (a four-branch launch began with ~8 of them before its first tensor load)
   for (int it = threadIdx.x; it < p.nb * C; it += 256) {
     const int b = it / C, c = it - b * C;
-    const rua_bn_bwd_branch& br = p.br[b];
-    double sg, sgx;
-    replica_sum(br.stats2, br.replicas, C, c, sg, sgx);
-    const double mu = br.mean[c], r = br.rstd[c], gm = br.gamma[c];
-    if (br.stats2_out) {                               // slot 1 holds sum g * (scale x + shift): back to sum g * x
-      const double sc = br.scale[c], sh = br.shift[c];
-      sgx = sc != 0.0 ? (sgx - sh * sg) / sc : mu * sg;
-    }
-    const double dga = r * (sgx - mu * sg);
-    const double s = gm * r;
-    tab[(b * 3) * C + c] = (float)s;
-    tab[(b * 3 + 1) * C + c] = (p.masked && br.scale) ? br.scale[c] : 1.f;
-    tab[(b * 3 + 2) * C + c] = (p.masked && br.shift) ? br.shift[c] : 0.f;
-    tT[(b * 2) * C + c] = (float)(-s * r * dga / p.count);
-    tT[(b * 2 + 1) * C + c] = (float)(-s * sg / p.count + s * r * mu * dga / p.count);
-    if (blockIdx.x == 0) {
-      if (br.dgamma) br.dgamma[c] += (float)dga;
-      if (br.dbeta) br.dbeta[c] += (float)sg;
-    }
+    bn_bwd_coef(p, p.br[b], c, blockIdx.x == 0, tab[(b * 3) * C + c], tab[(b * 3 + 1) * C + c], tab[(b * 3 + 2) * C + c],
+                tT[(b * 2) * C + c], tT[(b * 2 + 1) * C + c]);
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += 256) {         // the branches' terms in branch order (the sums of the sequential form, bit for bit)
@@ -608,46 +798,7 @@ __device__ __forceinline__ void bn_bwd_body(const rua_bn_bwd_desc& p, long long 
 #pragma unroll
     for (int b = 0; b < NB; ++b) gp[b] = (const unsigned char*)p.br[b].g;
     const bool accum = p.accumulate != 0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pieces; i += stride) {
-      // every load of the piece is issued before the first use
-      const uint4 xr = ldg16(x + i * 16);
-      uint4 gr[NB];
-#pragma unroll
-      for (int b = 0; b < NB; ++b) gr[b] = ldg16(gp[b] + i * 16);
-      uint4 dr = make_uint4(0, 0, 0, 0), ar = make_uint4(0, 0, 0, 0);
-      if (dskip) dr = ldg16(dskip + i * 16);
-      if (accum) ar = ldg16(dx + i * 16);
-      float xv[VEC], acc[VEC];
-      ET<T>::unpack(xr, xv);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) acc[j] = fmaf(cB[j], xv[j], cC[j]);
-      if (dskip) {
-        float dd[VEC];
-        ET<T>::unpack(dr, dd);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) { acc[j] += dd[j]; sk[j] += dd[j]; }
-      }
-      if (accum) {
-        float dd[VEC];
-        ET<T>::unpack(ar, dd);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) acc[j] += dd[j];
-      }
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        float gv[VEC];
-        ET<T>::unpack(gr[b], gv);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-          bool on = true;
-          if constexpr (MASKED) on = fmaf(cS[b][j], xv[j], cT[b][j]) > 0.f;
-          acc[j] = fmaf(cA[b][j], on ? gv[j] : 0.f, acc[j]);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) if constexpr (DXS) { so[j] += acc[j]; so2[j] = fmaf(acc[j], xv[j], so2[j]); }
-      stg16(dx + i * 16, ET<T>::pack(acc));
-    }
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pieces; i += stride) RUA_BN_BWD_PIECE(i);
   } else {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pieces; i += stride) {
     const int c = (int)(i % CG) * VEC;
@@ -727,18 +878,155 @@ static_assert(sizeof(BnBwdG) <= 4096, "grouped launch: kernel arguments are limi
 template <typename T, bool MASKED>
 __global__ __launch_bounds__(256) void bn_bwd_kernel_g(const BnBwdG g, int CG) { bn_bwd_body<T, 1, MASKED>(g.k[blockIdx.y], g.pieces[blockIdx.y], CG); }
 
+// The channel-sliced form (see bn_fwd_sliced_body).  Sums: the lanes of equal piece index fold with shuffles, the four waves through
+// [4][S * VEC] floats of LDS, then ONE fp64 add per channel and block into replica part & (R - 1).
+template <typename T, int NB, bool MASKED, bool DXS, int S>
+__device__ __forceinline__ void bn_bwd_sliced_body(const rua_bn_bwd_desc& p, int P, int bx) {
+  constexpr int VEC = ET<T>::VEC, SV = S * VEC;
+  __shared__ float tab[(NB * 5 + 2) * SV];             // [nb][3][SV] : A, ms, mt ; [2][SV] : sumB, sumC ; [nb][2][SV] : the branches' terms of sumB, sumC
+  static_assert((NB * 5 + 2) >= 4, "the folds reuse the table as [4][SV]");
+  float* tB = tab + NB * 3 * SV;
+  float* tT = tB + 2 * SV;
+  const int C = p.C, CG = C / VEC, slices = CG / S;
+  const int slice = bx % slices, part = bx / slices;
+  if (part >= P) return;                               // (a group's grid is as wide as its member of most parts)
+  for (int it = threadIdx.x; it < NB * SV; it += 256) {
+    const int b = it / SV, cl = it - b * SV;
+    bn_bwd_coef(p, p.br[b], slice * SV + cl, part == 0, tab[(b * 3) * SV + cl], tab[(b * 3 + 1) * SV + cl], tab[(b * 3 + 2) * SV + cl],
+                tT[(b * 2) * SV + cl], tT[(b * 2 + 1) * SV + cl]);
+  }
+  __syncthreads();
+  if (threadIdx.x < SV) {                              // the branches' terms in branch order, as the pixel-major form adds them
+    const int cl = threadIdx.x;
+    float sb = 0.f, sc_ = 0.f;
+    for (int b = 0; b < NB; ++b) { sb += tT[(b * 2) * SV + cl]; sc_ += tT[(b * 2 + 1) * SV + cl]; }
+    tB[cl] = sb; tB[SV + cl] = sc_;
+  }
+  __syncthreads();
+  const int q = (int)(threadIdx.x % S);
+  float sk[VEC], so[VEC], so2[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) { sk[j] = 0.f; so[j] = 0.f; so2[j] = 0.f; }
+  float cA[NB][VEC], cS[MASKED ? NB : 1][VEC], cT[MASKED ? NB : 1][VEC], cB[VEC], cC[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) { cB[j] = tB[q * VEC + j]; cC[j] = tB[SV + q * VEC + j]; }
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      cA[b][j] = tab[(b * 3) * SV + q * VEC + j];
+      if constexpr (MASKED) { cS[b][j] = tab[(b * 3 + 1) * SV + q * VEC + j]; cT[b][j] = tab[(b * 3 + 2) * SV + q * VEC + j]; }
+    }
+  const unsigned char* gp[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) gp[b] = (const unsigned char*)p.br[b].g;
+  const unsigned char* x = (const unsigned char*)p.x;
+  const unsigned char* dskip = (const unsigned char*)p.dskip;
+  unsigned char* dx = (unsigned char*)p.dx;
+  const bool accum = p.accumulate != 0;
+  const long long m1 = bn_part_begin(p.M, P, part + 1);
+  for (long long m = bn_part_begin(p.M, P, part) + threadIdx.x / S; m < m1; m += 256 / S)
+    RUA_BN_BWD_PIECE(m * CG + slice * S + q);
+  auto fold = [&](float* v, double* dst, int replicas, int slot) {
+    float* red = tab;                                    // the coefficient table is dead
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+#pragma unroll
+      for (int o = S; o < 64; o <<= 1) v[j] += __shfl_xor(v[j], o, 64);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane < S) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) red[wv * SV + lane * VEC + j] = v[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < SV) {
+      const int cl = threadIdx.x;
+      const float t = (red[cl] + red[SV + cl]) + (red[2 * SV + cl] + red[3 * SV + cl]);
+      unsafeAtomicAdd(&dst[(size_t)(part & (replicas - 1)) * 2 * C + slot * C + slice * SV + cl], (double)t);
+    }
+  };
+  if (p.skip_stats && dskip) fold(sk, p.skip_stats, p.skip_replicas, 0);      // (uniform branches)
+  if constexpr (DXS) { fold(so, p.dx_stats, p.dx_replicas, 0); fold(so2, p.dx_stats, p.dx_replicas, 1); }
+}
+#undef RUA_BN_BWD_PIECE
+template <typename T, int NB, bool MASKED, bool DXS, int S>
+__global__ __launch_bounds__(256) void bn_bwd_sliced_kernel(const rua_bn_bwd_desc p, int P) { bn_bwd_sliced_body<T, NB, MASKED, DXS, S>(p, P, blockIdx.x); }
+struct BnBwdGS { rua_bn_bwd_desc k[RUA_MAX_BRANCH]; int P[RUA_MAX_BRANCH]; };
+static_assert(sizeof(BnBwdGS) <= 4096, "grouped launch: kernel arguments are limited to 4 KiB");
+template <typename T, bool MASKED, int S>
+__global__ __launch_bounds__(256) void bn_bwd_sliced_kernel_g(const BnBwdGS g) { bn_bwd_sliced_body<T, 1, MASKED, false, S>(g.k[blockIdx.y], g.P[blockIdx.y], blockIdx.x); }
+
+static BnRoute bn_bwd_route_of(const rua_bn_bwd_desc& d) {
+  BnRoute none = {0, 0};
+  if (d.nb < 1 || d.nb > RUA_MAX_BRANCH || (d.dtype != RUA_F32 && d.dtype != RUA_BF16)) return none;
+  int r_in = 1, r_out = 0;
+  for (int b = 0; b < d.nb; ++b) if (d.br[b].replicas > r_in) r_in = d.br[b].replicas;
+  if (d.skip_stats) r_out = d.skip_replicas;
+  if (d.dx_stats && (r_out == 0 || d.dx_replicas < r_out)) r_out = d.dx_replicas;
+  return bn_route(d.M, d.C, d.dtype, d.nb, r_in, r_out);
+}
+extern "C" int rua_bn_bwd_route(const rua_bn_bwd_desc* d) {
+  if (!d) return 0;
+  const BnRoute r = bn_bwd_route_of(*d);
+  return r.S ? (r.S | r.P << 8) : 0;
+}
+template <typename T, int NB, int S>
+static void bn_bwd_sliced_launch_nb(const rua_bn_bwd_desc& d, int P, hipStream_t st) {
+  const dim3 g((unsigned)(d.C / (S * ET<T>::VEC) * P));
+  switch ((d.masked ? 2 : 0) + (d.dx_stats ? 1 : 0)) {
+    case 0: hipLaunchKernelGGL((bn_bwd_sliced_kernel<T, NB, false, false, S>), g, dim3(256), 0, st, d, P); break;
+    case 1: hipLaunchKernelGGL((bn_bwd_sliced_kernel<T, NB, false, true, S>), g, dim3(256), 0, st, d, P); break;
+    case 2: hipLaunchKernelGGL((bn_bwd_sliced_kernel<T, NB, true, false, S>), g, dim3(256), 0, st, d, P); break;
+    default: hipLaunchKernelGGL((bn_bwd_sliced_kernel<T, NB, true, true, S>), g, dim3(256), 0, st, d, P); break;
+  }
+}
+template <typename T, int S>
+static void bn_bwd_sliced_launch(const rua_bn_bwd_desc& d, int P, hipStream_t st) {
+  switch (d.nb) {
+    case 1: bn_bwd_sliced_launch_nb<T, 1, S>(d, P, st); break;
+    case 2: bn_bwd_sliced_launch_nb<T, 2, S>(d, P, st); break;
+    case 3: bn_bwd_sliced_launch_nb<T, 3, S>(d, P, st); break;
+    default: bn_bwd_sliced_launch_nb<T, 4, S>(d, P, st); break;
+  }
+}
+
 extern "C" int rua_bn_bwd(const rua_bn_bwd_desc* d, void* stream);
 static thread_local int g_bn_bwd_group_last = 0;
 extern "C" int rua_bn_bwd_group_last_grids(void) { return g_bn_bwd_group_last; }     // grids the calling thread's latest rua_bn_bwd_group issued
 extern "C" int rua_bn_bwd_group(const rua_bn_bwd_desc* d, int n, void* stream) {
   RUA_CHECK_ARG(d && n >= 1 && n <= RUA_MAX_BRANCH, "rua_bn_bwd_group: 1..%d members", RUA_MAX_BRANCH);
   const int vec = d[0].dtype == RUA_BF16 ? 8 : 4;
-  bool one = n > 1 && g_tune.bn_bwd_group && d[0].C % vec == 0 && d[0].C / vec <= 256 && 256 % (d[0].C / vec) == 0 && g_tune.bn_regs;
-  for (int i = 0; i < n && one; ++i) {
+  bool same = n > 1 && g_tune.bn_bwd_group && d[0].C > 0 && d[0].C % vec == 0;      // valid members of one shape family
+  for (int i = 0; i < n && same; ++i) {
     const rua_bn_bwd_desc& m = d[i];
-    one = m.x && m.dx && m.nb == 1 && m.M > 0 && m.C == d[0].C && m.dtype == d[0].dtype && m.masked == d[0].masked && !m.skip_stats && !m.dx_stats && m.count > 0 &&
-          m.br[0].g && m.br[0].stats2 && m.br[0].replicas >= 1 && m.br[0].gamma && m.br[0].mean && m.br[0].rstd &&
-          (d[0].dtype == RUA_F32 || d[0].dtype == RUA_BF16);
+    same = m.x && m.dx && m.nb == 1 && m.M > 0 && m.C == d[0].C && m.dtype == d[0].dtype && m.masked == d[0].masked && !m.skip_stats && !m.dx_stats && m.count > 0 &&
+           m.br[0].g && m.br[0].stats2 && m.br[0].replicas >= 1 && m.br[0].gamma && m.br[0].mean && m.br[0].rstd &&
+           (d[0].dtype == RUA_F32 || d[0].dtype == RUA_BF16);
+  }
+  const bool one = same && d[0].C / vec <= 256 && 256 % (d[0].C / vec) == 0 && g_tune.bn_regs;
+  if (same) {                                            // channel-sliced where every member's own route is: each member keeps its own P
+    BnBwdGS a;
+    int S = 0, pmax = 0;
+    bool sliced = true;
+    for (int i = 0; i < n && sliced; ++i) {
+      const BnRoute r = bn_bwd_route_of(d[i]);
+      sliced = r.S != 0 && (i == 0 || r.S == S);
+      S = r.S; a.k[i] = d[i]; a.P[i] = r.P; if (r.P > pmax) pmax = r.P;
+    }
+    if (sliced) {
+      const dim3 g((unsigned)(d[0].C / (S * vec) * pmax), n);
+      hipStream_t st = (hipStream_t)stream;
+      const bool mk = d[0].masked != 0;
+#define RUA_BN_BWD_GS(T_, MK_) do { if (S == 8) hipLaunchKernelGGL((bn_bwd_sliced_kernel_g<T_, MK_, 8>), g, dim3(256), 0, st, a); \
+                                    else hipLaunchKernelGGL((bn_bwd_sliced_kernel_g<T_, MK_, 4>), g, dim3(256), 0, st, a); } while (0)
+      if (d[0].dtype == RUA_BF16) { if (mk) RUA_BN_BWD_GS(bf16_t, true); else RUA_BN_BWD_GS(bf16_t, false); }
+      else { if (mk) RUA_BN_BWD_GS(float, true); else RUA_BN_BWD_GS(float, false); }
+#undef RUA_BN_BWD_GS
+      RUA_LAUNCH_CHECK("rua_bn_bwd_group");
+      g_bn_bwd_group_last = 1;
+      return RUA_OK;
+    }
   }
   g_bn_bwd_group_last = n;
   if (!one) {                                            // same results member by member
@@ -779,7 +1067,6 @@ extern "C" int rua_bn_bwd(const rua_bn_bwd_desc* d, void* stream) {
     if (br.replicas > rmax) rmax = br.replicas;
   }
   size_t smem = (size_t)(d->nb * 5 + 2) * d->C * 4;
-  RUA_CHECK_ARG(smem <= 160 * 1024, "rua_bn_bwd: coefficient table too large");      // (5 nb + 2) C floats: nb = 4 up to C = 1861, nb = 1 up to C = 5851
   const int CG = d->C / vec;
   if (d->skip_stats) {
     RUA_CHECK_ARG(d->dskip && d->skip_replicas >= 1 && (d->skip_replicas & (d->skip_replicas - 1)) == 0 && CG <= 256 && 256 % CG == 0,
@@ -791,13 +1078,20 @@ extern "C" int rua_bn_bwd(const rua_bn_bwd_desc* d, void* stream) {
                   "rua_bn_bwd: dx_stats needs a power-of-two replica count and C / %d dividing 256", vec);
     if (smem < (size_t)256 * vec * 4) smem = (size_t)256 * vec * 4;
   }
+  hipStream_t st = (hipStream_t)stream;
+  if (const BnRoute rt = bn_bwd_route_of(*d); rt.S) {
+    if (d->dtype == RUA_BF16) { if (rt.S == 8) bn_bwd_sliced_launch<bf16_t, 8>(*d, rt.P, st); else bn_bwd_sliced_launch<bf16_t, 4>(*d, rt.P, st); }
+    else { if (rt.S == 8) bn_bwd_sliced_launch<float, 8>(*d, rt.P, st); else bn_bwd_sliced_launch<float, 4>(*d, rt.P, st); }
+    RUA_LAUNCH_CHECK("rua_bn_bwd");
+    return RUA_OK;
+  }
+  RUA_CHECK_ARG(smem <= 160 * 1024, "rua_bn_bwd: coefficient table too large");      // (5 nb + 2) C floats: nb = 4 up to C = 1861, nb = 1 up to C = 5851
   const long long pieces = d->M * CG;
   int g = grid_for(pieces);
   // measured (4 branches): 256x256x32 53 -> 46 us, 128x128x64 35 -> 31 us with 1024 blocks; smaller tensors prefer 512
   const int cap_env = g_tune.bn_grid;
   const int cap = cap_env > 0 ? cap_env : (pieces >= (1ll << 20) ? 4 : 2) * rua_cu_count();      // 1024 / 512 on MI355X
   if ((long long)rmax * d->C * d->nb >= 512 && g > cap) g = cap;
-  hipStream_t st = (hipStream_t)stream;
   const int nbk = (CG <= 256 && 256 % CG == 0 && g_tune.bn_regs) ? d->nb : 0;
   const bool mk = d->masked != 0;
   // a table beyond 64 KB (wider variants than the shipped configurations) needs the kernel's dynamic-LDS limit raised: a rare path, set per launch
