@@ -527,6 +527,37 @@ int rua_head_dz_sel(int kind, int act, const float* p, const float* y, const flo
                     const rua_loss_opts* opts, const uint8_t* drop_mask, const float* scale_dev, float* dz, void* stream);
 int rua_head_dz_multi_sel(const rua_dz_head* heads, const rua_loss_opts* opts, const rua_dz_sel* sel, int n, const uint8_t* void_mask, void* stream);
 
+/* ---- Lovasz-Softmax (Berman, Triki, Blaschko, CVPR 2018): the Lovasz extension of the Jaccard index over a head's probabilities.  The package's
+ * losses.py holds the definitions as host functions, host_lovasz and host_lovasz_dz; the kernels are csrc/lovasz.hip.  p[M][C], y[M][C] fp32,
+ * void_mask[M] optional (non-zero = void).  Per class c over the n valid pixels: fg = y > 0.5, e = |fg - p| (one fp32 subtraction), G_c = sum fg;
+ * the pixels ordered by ohem's key of e DESCENDING (NaN first), ties in ascending pixel index; F_r the foreground count of ranks 0..r;
+ * J_r = 1 - (G_c - F_r) / (G_c + (r + 1) - F_r) in fp64, J_-1 = 0; w_r = J_r - J_{r-1}; loss_c = sum_r (double)e_(r) * w_r;
+ * dp[pixel][c] = (float)w_r for a background pixel, -(float)w_r for a foreground one, +0.0f for void pixels and for classes that are not counted.
+ * Counted: G_c > 0, or every class with all_classes.  loss = sum_counted loss_c / n_cls; scale = (float)((double)loss_weight / n_cls); n = 0 or
+ * n_cls = 0: loss 0, scale 0, dp all zero, the slot unchanged.
+ * rua_lovasz_grad adds loss_weight * loss into loss_out[0] (an fp64 slot), writes dp[M][C] (NULL: the value only), order_out[C][M] (NULL: not; the
+ * sorted pixel indices, entries from n on unspecified) and fills result_dev.  A stable LSD radix sort of (key, pixel) pairs in four 8-bit passes
+ * (histogram, scan, scatter as separate launches), a tile-wise prefix count and a one-block finisher: 18 launches whatever the maps hold, no block
+ * waits for another, plain stores and integer atomics, no host readback; the fp64 sums are added in a fixed order: the same bits on every run
+ * and replay.  rua_lovasz_tile: the sort's tile size in pairs.  workspace: at least rua_lovasz_workspace_bytes(M, C) (-1 for a shape out of
+ * range), 8-byte aligned, contents irrelevant.  RUA_ERR_ARG before any launch: C outside 1..16, M < 1 or >= 2^31, M * C >= 2^32, a workspace
+ * that is too small, a null or misaligned buffer.
+ * rua_lovasz_dz: dz[M][C] = d(total)/d(logits) from dp in one streaming pass, every fp32 operation rounded on its own:
+ *   softmax  s = ((g_0 p_0 + g_1 p_1) + ..), dz_k = scale * (p_k * (g_k - s));   sigmoid  dz_c = scale * (g_c * (p_c * (1 - p_c)))
+ * with scale = scale_dev[0] (rua_lovasz_result.scale: a replayed graph needs no host scalar).  A softmax pixel whose dp is zero in every class
+ * and a sigmoid element whose dp is zero (every void pixel) leave as +0.0f by a select: p may hold anything there. */
+#define RUA_LOSS_LOVASZ 7
+#define RUA_LOVASZ_MAX_C 16
+typedef struct rua_lovasz_result {
+  int64_t n_valid; int32_t n_cls; float scale; int64_t G[RUA_LOVASZ_MAX_C]; double loss_c[RUA_LOVASZ_MAX_C]; double loss;
+} rua_lovasz_result;
+int rua_lovasz_tile(void);
+int64_t rua_lovasz_workspace_bytes(int64_t M, int C);
+int rua_lovasz_grad(const float* p, const float* y, const uint8_t* void_mask, int64_t M, int C, int all_classes, float loss_weight,
+                    void* workspace, int64_t workspace_bytes, double* loss_out, float* dp, uint32_t* order_out,
+                    rua_lovasz_result* result_dev, void* stream);
+int rua_lovasz_dz(int act, const float* p, const float* dp, const float* scale_dev, int64_t M, int C, float* dz, void* stream);
+
 /* ---- optimizers on the flat parameter buffer (train_ISPRS.py:404-407) --------------------- */
 /* Keras Adam: theta -= lr_t * m / (sqrt(v) + eps); g is read as g*grad_scale and zeroed if zero_grad.
  * lr_t_dev (optional): device scalar overriding lr_t, so a captured HIP graph can be replayed every step */

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("RUA_LIB_PATH") or os.path.join(HERE, "librua_hip.so")
 RUA_F32, RUA_BF16 = 0, 1
 RUA_MAX_SEG, RUA_MAX_BRANCH, RUA_MAX_WGRAD_GROUP, RUA_MAX_WGRAD_BATCH = 6, 4, 8, 32
 LOSS_TANIMOTO, LOSS_WCE, LOSS_CE_LOGITS, LOSS_BCE_LOGITS, LOSS_MSE, LOSS_FOCAL_CE, LOSS_FOCAL_BCE = 0, 1, 2, 3, 4, 5, 6
+LOSS_LOVASZ, RUA_LOVASZ_MAX_C = 7, 16
 ACT_NONE, ACT_SOFTMAX, ACT_SIGMOID = 0, 1, 2
 
 vp, i32, i64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
@@ -77,6 +78,11 @@ class OhemOpts(C.Structure):
 class OhemResult(C.Structure):
     """rua_ohem_result: what rua_ohem_select leaves on the device."""
     _fields_ = [("tau_key", C.c_uint32), ("tau", f32), ("n_valid", i64), ("n_kept", i64), ("K", i64), ("kept_sum", f64), ("scale", f32), ("q16_used", i32)]
+
+
+class LovaszResult(C.Structure):
+    """rua_lovasz_result: what rua_lovasz_grad leaves on the device (losses.py holds the definition, host_lovasz)."""
+    _fields_ = [("n_valid", i64), ("n_cls", i32), ("scale", f32), ("G", i64 * RUA_LOVASZ_MAX_C), ("loss_c", f64 * RUA_LOVASZ_MAX_C), ("loss", f64)]
 
 
 class DzSel(C.Structure):
@@ -234,6 +240,10 @@ _SIGS = {
     "rua_ohem_select": ([vp, vp, i64, C.POINTER(OhemOpts), vp, f32, vp, i64, vp, vp, vp, vp], i32),
     "rua_head_dz_sel": ([i32, i32, vp, vp, vp, vp, i32, i64, i32, C.POINTER(LossOpts), vp, vp, vp, vp], i32),
     "rua_head_dz_multi_sel": ([vp, vp, vp, i32, vp, vp], i32),
+    "rua_lovasz_tile": ([], i32),
+    "rua_lovasz_workspace_bytes": ([i64, i32], i64),
+    "rua_lovasz_grad": ([vp, vp, vp, i64, i32, i32, f32, vp, i64, vp, vp, vp, vp, vp], i32),
+    "rua_lovasz_dz": ([i32, vp, vp, vp, i64, i32, vp, vp], i32),
     "rua_void_mask": ([vp, i32, i32, i32, i32, i32, vp, vp], i32),
     "rua_targets_scratch_bytes": ([i32, i32], i64),
     "rua_multitask_targets": ([vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp], i32),

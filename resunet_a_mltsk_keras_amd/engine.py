@@ -94,11 +94,23 @@ class LossSpec:
     # plain mean.  A head that is not in it issues the calls it always did.
     ohem: Dict[str, dict] = field(default_factory=dict)
 
+    # Lovasz-Softmax (losses.py holds the definitions, host_lovasz / host_lovasz_dz), by head: head -> losses.lovasz_options(...) for the heads of
+    # kind LOSS_LOVASZ ('seg', 'bound').  Such a head's loss and d(loss)/d(probabilities) come from rua_lovasz_grad (a device-wide sort), its
+    # d(total)/d(logits) from a rua_lovasz_dz launch of its own.  With no head on it every plan issues the calls it always did.
+    lovasz: Dict[str, dict] = field(default_factory=dict)
+
     def loss_options(self) -> Dict[str, object]:
         """The per-head dicts (checkpoint metadata); a spec without them gives {}: its file carries none."""
         d = dict(focal_gamma=dict(self.focal_gamma), focal_alpha=dict(self.focal_alpha), class_balance=dict(self.class_balance),
-                 label_smoothing=dict(self.label_smoothing), ohem={h: dict(o) for h, o in self.ohem.items()})
+                 label_smoothing=dict(self.label_smoothing), ohem={h: dict(o) for h, o in self.ohem.items()},
+                 lovasz={h: self.head_lovasz(h) for h, k in self.kind.items() if k == L.LOSS_LOVASZ})
         return {k: v for k, v in d.items() if v}
+
+    def head_lovasz(self, head: str) -> Optional[dict]:
+        """The options of a head on the Lovasz loss with every field filled in; None: the head is on another loss."""
+        if self.kind.get(head) != L.LOSS_LOVASZ:
+            return None
+        return {**LS.lovasz_options(), **self.lovasz.get(head, {})}
 
     def head_ohem(self, head: str) -> Optional[dict]:
         """The head's mining options with every field filled in; None: the head does not mine."""
@@ -1392,6 +1404,22 @@ class Graph:
             else:
                 LP.add("rua_tanimoto_finalize_rep", sums, h.get("sums_rep", 1), B, HW, Cc, wgt / B, slot, coef.data_ptr(), None)
             h["norm"] = 1.0
+        elif kind == L.LOSS_LOVASZ:
+            # the Lovasz extension of the Jaccard index: rua_lovasz_grad sorts every class's pixels by their error on the device, adds
+            # weight * loss into the head's slot and leaves d(loss)/d(p) and the normaliser in device memory (training; evaluation takes the
+            # value only).  Nothing is read back: a replay needs no host scalar
+            lo = sp.head_lovasz(h["name"])
+            nws = int(L.lib().raw("rua_lovasz_workspace_bytes")(M, Cc))
+            if nws < 0:
+                raise ValueError(f"{h['name']}: {M} pixels x {Cc} classes is out of the Lovasz kernels' range")
+            res, ws = self.alloc((C.sizeof(L.LovaszResult) // 8,), torch.float64, zero=True), self.alloc((nws // 8 + 1,), torch.float64)
+            dp = self.alloc((M * Cc,), torch.float32) if self.training else None
+            LP.keep += [res, ws]
+            LP.add("rua_lovasz_grad", h["p"].ptr, h["y"].ptr, self.void_ptr, M, Cc, 1 if lo["classes"] == "all" else 0, wgt, ws.data_ptr(), nws, slot,
+                   dp.data_ptr() if dp is not None else None, None, res.data_ptr())
+            w32 = float(np.float32(wgt))                  # the slot holds float32(weight) * loss: the norm takes the weight out again (1.0 exactly for a unit weight)
+            h["norm"] = 1.0 / w32 if w32 != 0 else 1.0
+            h["lovasz"] = dict(result=res, dp=dp, opts=lo)
         else:
             # online hard example mining (training plans only: evaluation reports the plain mean): the loss entry leaves the per-pixel map - its own sum
             # goes to a scratch slot nobody reads -, rua_ohem_select turns the map into the head's drop mask, its normaliser and the kept mean, which it
@@ -1423,11 +1451,13 @@ class Graph:
         if not self.training:
             return
         sel = h.get("ohem")
+        lov = h.get("lovasz")
 
         dz = self.new(B, h["x"].H, h["x"].W, Cc, f32=True)
+        h["dz"] = dz
         gs = wgt / B if kind == L.LOSS_TANIMOTO else wgt / M
         scale_ptr = sel["result"].data_ptr() + L.OhemResult.scale.offset if sel is not None else None
-        if self.multi_head:
+        if self.multi_head and lov is None:             # (a Lovasz head stays out of the heads' single launch: it has its own, below)
             dh = L.DzHead()
             dh.kind, dh.act, dh.p, dh.y, dh.coef, dh.class_w = kind, h["act"], h["p"].ptr, h["y"].ptr, coef.data_ptr() if coef is not None else None, self.e.class_w_ptr
             dh.grad_scale, dh.B, dh.HW, dh.C, dh.dz = gs, B, HW, Cc, dz.ptr
@@ -1440,8 +1470,10 @@ class Graph:
 
         def back():
             Bp = self.bwd
+            if lov is not None:
+                Bp.add("rua_lovasz_dz", h["act"], h["p"].ptr, lov["dp"].data_ptr(), lov["result"].data_ptr() + L.LovaszResult.scale.offset, M, Cc, dz.ptr)
             if self.multi_head:
-                if not self._dz_emitted:                    # the first backward step of the loss section: d(loss)/d(logits) of ALL heads in one launch
+                if not self._dz_emitted and self._dz_multi:                    # the first backward step of the loss section: d(loss)/d(logits) of ALL heads in one launch
                     arr = (L.DzHead * len(self._dz_multi))(*self._dz_multi)
                     Bp.keep.append(arr)
                     if any(d.drop_mask for d in self._dz_multi_sel):         # a mining head: still one launch, its mask and normaliser read on the device
@@ -1458,6 +1490,8 @@ class Graph:
                     else:
                         Bp.add("rua_head_dz_multi", arr, len(self._dz_multi))
                     self._dz_emitted = True
+            elif lov is not None:
+                pass
             elif sel is not None:
                 o = opts if opts is not None else L.LossOpts()
                 Bp.keep.append(o)
@@ -1800,6 +1834,20 @@ class Engine:
             for h in getattr(spec, name):
                 if h not in spec.kind:
                     raise ValueError(f"{name}: '{h}' is not a head of this model ({', '.join(spec.kind)})")
+        # the Lovasz loss: binary targets only ('seg' under its softmax, 'bound' per sigmoid channel), and none of the per-pixel options
+        for h in spec.lovasz:
+            if h not in spec.kind:
+                raise ValueError(f"lovasz: '{h}' is not a head of this model ({', '.join(spec.kind)})")
+            if spec.kind[h] != L.LOSS_LOVASZ:
+                raise ValueError(f"{h}: lovasz options belong to a head on the Lovasz loss")
+        for h, kind in spec.kind.items():
+            if kind != L.LOSS_LOVASZ:
+                continue
+            LS.check_lovasz(spec.lovasz.get(h, {}), what=f"{h}: lovasz", head=h, num_classes=3 if h == "color" else self.cfg.num_classes)
+            if h in spec.ohem:
+                raise ValueError(f"{h}: the Lovasz loss has no per-pixel map, online hard example mining does not combine with it")
+            if float(spec.label_smoothing.get(h, 0.0)) != 0.0:
+                raise ValueError(f"{h}: the Lovasz loss takes no label smoothing")
         for h, kind in spec.kind.items():
             if kind == L.LOSS_FOCAL_CE and acts[h] != L.ACT_SOFTMAX:
                 raise ValueError(f"{h}: categorical focal cross-entropy needs a softmax head")
@@ -1955,6 +2003,26 @@ class Engine:
             r = L.OhemResult.from_buffer_copy(h["ohem"]["result"].cpu().numpy().tobytes())
             out[h["name"]] = dict(kept=r.n_kept / r.n_valid if r.n_valid else 0.0, tau=float(r.tau), tau_key=int(r.tau_key), K=int(r.K), n_kept=int(r.n_kept),
                                   n_valid=int(r.n_valid), q16_used=int(r.q16_used), kept_sum=float(r.kept_sum), scale=float(r.scale))
+        return out
+
+    def lovasz_report(self) -> Optional[Dict[str, dict]]:
+        """The Lovasz loss: what rua_lovasz_grad left for the last step, per head on it - n_valid, n_cls, G and loss_c per class, loss, scale.
+        None when no head is on the loss or no step has run; the last training step's, or an evaluation step's while none has run.  Under data parallel and accumulation these are this rank's, this micro-batch's.
+        Synchronises the device."""
+        if self.loss is None or L.LOSS_LOVASZ not in self.loss.kind.values():
+            return None
+        B = getattr(self, "_last_B", None)                  # the last training step's plan; with none yet, an evaluation plan
+        g = self.graphs.get((B, True)) or self.graphs.get((B, False)) or next(iter(reversed(list(self.graphs.values()))), None)
+        if g is None:
+            return None
+        torch.cuda.synchronize()
+        out = {}
+        for h in g.heads:
+            if "lovasz" not in h:
+                continue
+            r = LS.lovasz_result(h["lovasz"]["result"].cpu().numpy().tobytes())
+            Cc = h["C"]
+            out[h["name"]] = dict(n_valid=r["n_valid"], n_cls=r["n_cls"], G=r["G"][:Cc], loss_c=r["loss_c"][:Cc], loss=r["loss"], scale=float(r["scale"]))
         return out
 
     def _backup_state(self, s):

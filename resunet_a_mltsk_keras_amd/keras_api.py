@@ -338,6 +338,51 @@ class MeanSquaredError:
     kind = L.LOSS_MSE
 
 
+def lovasz_on_gpu(y_true, y_pred, void_mask=None, classes="present", loss_weight=1.0, want_dp=False):
+    """rua_lovasz_grad on host arrays [..., C]: dict(loss, n_valid, n_cls, scale, G, loss_c[, dp]) as losses.lovasz_result gives them."""
+    y_true, y_pred = np.asarray(y_true, np.float32), np.asarray(y_pred, np.float32)
+    if y_true.shape != y_pred.shape:
+        raise ValueError(f"y_true {y_true.shape} and y_pred {y_pred.shape} differ")
+    Cc = y_true.shape[-1]
+    M = int(np.prod(y_true.shape[:-1]))
+    LS.check_lovasz(LS.lovasz_options(classes), what="LovaszSoftmax", num_classes=Cc)
+    lib = L.lib()
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p, y = _dev_f32(y_pred.reshape(-1)), _dev_f32(y_true.reshape(-1))
+    vm = torch.from_numpy(np.ascontiguousarray(np.asarray(void_mask).reshape(-1) != 0, np.uint8)).to("cuda") if void_mask is not None else None
+    nws = int(lib.raw("rua_lovasz_workspace_bytes")(M, Cc))
+    if nws < 0:
+        raise ValueError(f"LovaszSoftmax: {M} pixels x {Cc} classes is out of the kernels' range")
+    ws = torch.empty(nws // 8 + 1, dtype=torch.float64, device="cuda")
+    out = torch.zeros(1, dtype=torch.float64, device="cuda")
+    res = torch.zeros(C.sizeof(L.LovaszResult) // 8, dtype=torch.float64, device="cuda")
+    dp = torch.empty(M * Cc, dtype=torch.float32, device="cuda") if want_dp else None
+    lib.call("rua_lovasz_grad", p.data_ptr(), y.data_ptr(), vm.data_ptr() if vm is not None else None, M, Cc, int(classes == "all"), float(loss_weight),
+             ws.data_ptr(), nws, out.data_ptr(), dp.data_ptr() if dp is not None else None, None, res.data_ptr(), s)
+    r = LS.lovasz_result(res.cpu().numpy().tobytes())
+    if want_dp:
+        r["dp"] = dp.cpu().numpy().reshape(y_pred.shape)
+    return r
+
+
+class LovaszSoftmax:
+    """The Lovasz-Softmax loss (Berman, Triki, Blaschko, CVPR 2018) on the softmax 'seg' head or - per channel, the binary Lovasz loss on
+    probabilities - the sigmoid 'bound' head: the Lovasz extension of the Jaccard index, the loss to fine-tune directly for mean IoU.
+    classes: "present" (classes with foreground in the batch count, the paper's default) or "all".  losses.host_lovasz is the definition; the
+    sort and the gradient run on the GPU (rua_lovasz_grad, rua_lovasz_dz) inside the training step.  Calling the object on (y_true, y_pred)
+    returns the scalar from the GPU.  Not offered: per_image=True, the hinge form on logits, a built-in mix with cross-entropy on one head."""
+    kind = L.LOSS_LOVASZ
+    __name__ = "loss"
+
+    def __init__(self, classes="present"):
+        self.options = LS.lovasz_options(classes)
+        LS.check_lovasz(self.options, what="LovaszSoftmax")
+        self.classes = classes
+
+    def __call__(self, y_true, y_pred):
+        return lovasz_on_gpu(y_true, y_pred, classes=self.classes)["loss"]
+
+
 class OnlineHardExampleMining:
     """Online hard example mining (bootstrapped cross-entropy) around any per-pixel loss object or name the package accepts: per training step
     only the head's hardest pixels contribute - the keep_ratio share of the valid pixels with the largest loss, never fewer than min_kept, and
@@ -394,11 +439,14 @@ class OnlineHardExampleMining:
 
 _LOSS_NAMES = {"categorical_crossentropy": L.LOSS_CE_LOGITS, "binary_crossentropy": L.LOSS_BCE_LOGITS,
                "mse": L.LOSS_MSE, "mean_squared_error": L.LOSS_MSE, "tanimoto": L.LOSS_TANIMOTO,
-               "categorical_focal_crossentropy": L.LOSS_FOCAL_CE, "binary_focal_crossentropy": L.LOSS_FOCAL_BCE}
+               "categorical_focal_crossentropy": L.LOSS_FOCAL_CE, "binary_focal_crossentropy": L.LOSS_FOCAL_BCE,
+               "lovasz": L.LOSS_LOVASZ, "lovasz_softmax": L.LOSS_LOVASZ}
 
 
 def _named_loss(loss):
-    """A focal loss given by its Keras name: the object with Keras' defaults.  Other names and objects pass."""
+    """A focal loss given by its Keras name: the object with Keras' defaults; "lovasz" / "lovasz_softmax": LovaszSoftmax().  Other names and objects pass."""
+    if isinstance(loss, str) and _LOSS_NAMES.get(loss) == L.LOSS_LOVASZ:
+        return LovaszSoftmax()
     if isinstance(loss, str) and _LOSS_NAMES.get(loss) in LS.FOCAL_KINDS:
         return CategoricalFocalCrossentropy() if _LOSS_NAMES[loss] == L.LOSS_FOCAL_CE else BinaryFocalCrossentropy()
     return loss
@@ -422,6 +470,8 @@ def _loss_kind(loss, head):
         raise ValueError("categorical focal cross-entropy needs a softmax head")
     if kind == L.LOSS_FOCAL_BCE and head in ("seg", "dist"):
         raise ValueError("binary focal cross-entropy needs a sigmoid head")
+    if kind == L.LOSS_LOVASZ and head not in LS.LOVASZ_HEADS:
+        raise ValueError(f"the Lovasz loss needs binary targets: heads {', '.join(LS.LOVASZ_HEADS)} only, '{head}' has continuous ones")
     return kind, getattr(loss, "weights", None)
 
 
@@ -527,7 +577,9 @@ class Model:
         the cycle stands; the .h5 file holds the option and an open cycle.
         Losses: CategoricalFocalCrossentropy / BinaryFocalCrossentropy (or their Keras names as strings) and label_smoothing= on the
         cross-entropies go into LossSpec's per-head dicts (losses.py has the definitions; stored in .h5 files).  Focal CE's per-class alpha
-        travels as the class weights: one vector per model."""
+        travels as the class weights: one vector per model.
+        LovaszSoftmax(classes=) (or "lovasz" / "lovasz_softmax") on 'seg' and 'bound' goes into LossSpec.lovasz (stored in .h5 files); it combines
+        with no OnlineHardExampleMining, label smoothing or focal option on the same head.  lovasz_report() gives the last step's class counts."""
         margin = void_margin(ignore_void)
         if optimizer is None or isinstance(optimizer, str):
             optimizer = {"adam": Adam, "sgd": SGD, "lamb": Lamb}[optimizer or "adam"]()
@@ -535,13 +587,15 @@ class Model:
         heads = HEADS if self.cfg.multitasking else ["seg"]
         kinds, cw = {}, None
         lopts = {k: {} for k in LS.OPTION_KEYS}
-        mining = {}
+        mining, lovasz = {}, {}
         for h in heads:
             l = _named_loss(loss[h] if isinstance(loss, dict) else loss)
             kinds[h], w = _loss_kind(l, h)
             _loss_head_options(l, h, lopts)
             if isinstance(l, OnlineHardExampleMining):
                 mining[h] = dict(l.options)
+            if kinds[h] == L.LOSS_LOVASZ:
+                lovasz[h] = dict((l.loss if isinstance(l, OnlineHardExampleMining) else l).options)
             if kinds[h] == L.LOSS_FOCAL_CE:                  # the per-class alpha travels as the class weights (one vector per model, as weighted CE's)
                 w = l.alpha_vector(self.cfg.num_classes)
                 if len(w) != self.cfg.num_classes:
@@ -557,7 +611,7 @@ class Model:
             weights.update({h: float(loss_weights[h]) for h in heads if h in loss_weights})
         spec = LossSpec(kind=kinds, weight=weights, class_weights=cw, optimizer=optimizer.kind, lr=optimizer.lr.value,
                         beta_1=getattr(optimizer, "beta_1", 0.9), beta_2=getattr(optimizer, "beta_2", 0.999),
-                        momentum=getattr(optimizer, "momentum", 0.0), epsilon=getattr(optimizer, "epsilon", 1e-7), ignore_void=margin, **lopts, ohem=mining,
+                        momentum=getattr(optimizer, "momentum", 0.0), epsilon=getattr(optimizer, "epsilon", 1e-7), ignore_void=margin, **lopts, ohem=mining, lovasz=lovasz,
                         **(optimizer.clip_options() if hasattr(optimizer, "clip_options") else {}),
                         **(optimizer.sched_options() if hasattr(optimizer, "sched_options") else {}),
                         **(optimizer.accum_options() if hasattr(optimizer, "accum_options") else {}))
@@ -597,6 +651,11 @@ class Model:
         """Engine.ohem_report: per mining head dict(kept - the kept share of the last training step's valid pixels -, tau, tau_key, K, n_kept,
         n_valid, q16_used, kept_sum, scale), or None when no head was compiled with OnlineHardExampleMining.  Synchronises the device."""
         return self.engine.ohem_report()
+
+    def lovasz_report(self):
+        """Engine.lovasz_report: per head on the Lovasz loss dict(n_valid, n_cls, G, loss_c, loss, scale) of the last step, or None when no head
+        was compiled with LovaszSoftmax.  Synchronises the device."""
+        return self.engine.lovasz_report()
 
     def accumulation_state(self):
         """Adam / SGD(gradient_accumulation_steps=K): dict(steps=K, micro=calls of train_on_batch since the last update, 0 .. K - 1); None with

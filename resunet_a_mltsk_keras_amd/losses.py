@@ -106,6 +106,8 @@ def options_from_meta(lo: dict) -> Dict[str, dict]:
     out = {k: dict(lo.get(k) or {}) for k in OPTION_KEYS}
     if lo.get(OHEM_KEY):
         out[OHEM_KEY] = {h: ohem_options(**dict(o)) for h, o in lo[OHEM_KEY].items()}
+    if lo.get(LOVASZ_KEY):                                # ... a sixth where a head is on the Lovasz loss
+        out[LOVASZ_KEY] = {h: lovasz_options(**dict(o)) for h, o in lo[LOVASZ_KEY].items()}
     return out
 
 
@@ -240,6 +242,121 @@ def host_ohem(per_pixel, valid=None, keep_q16: int = 16384, min_kept: int = 0, t
     return dict(drop_mask=(~kept).astype(np.uint8).reshape(Lm.shape), tau_key=tau_key, tau=ohem_unkey(tau_key), n_valid=n_valid, n_kept=n_kept, K=K,
                 q16_used=q, kept_sum=kept_sum, loss=kept_sum / n_kept if n_kept else 0.0,
                 scale=np.float32(np.float64(np.float32(loss_weight)) / np.float64(n_kept)) if n_kept else np.float32(0.0))     # (the C ABI takes loss_weight as a float32)
+
+
+# ---- Lovasz-Softmax (Berman, Triki, Blaschko, CVPR 2018: lovasz_softmax) -----------------------------------------------------------------------
+# The Lovasz extension of the Jaccard index: per class the valid pixels are ordered by their error and the error vector is weighted with the
+# discrete gradient of the Jaccard loss along that order.  host_lovasz is the definition of the value and of d(loss)/d(probabilities),
+# host_lovasz_dz of the step from there to the logits; rua_lovasz_grad / rua_lovasz_dz (csrc/lovasz.hip) compute the same bits on the device - the
+# order, the weights and the gradient exactly, the fp64 sums up to their order.  One option:
+#   classes    "present" (the paper's default): the classes with at least one foreground pixel among the valid ones count;  "all": every class
+# Out of scope: per_image=True, the hinge form on logits, a built-in mix with cross-entropy on one head, sorting as a public utility.
+LOVASZ_KEY = "lovasz"                                    # LossSpec's sixth per-head dict and the checkpoint's key
+LOVASZ_FIELDS = ("classes",)
+LOVASZ_CLASSES = ("present", "all")
+LOVASZ_MAX_CLASSES = L.RUA_LOVASZ_MAX_C
+LOVASZ_HEADS = {"seg": L.ACT_SOFTMAX, "bound": L.ACT_SIGMOID}          # the heads with binary targets; dist and color have continuous ones
+
+
+def lovasz_options(classes: str = "present") -> dict:
+    """One head's options as the plain dict LossSpec.lovasz and the checkpoint hold."""
+    return dict(classes=classes)
+
+
+def check_lovasz(o: dict, what: str = "lovasz", head: Optional[str] = None, num_classes: Optional[int] = None):
+    """The range of one head's options, and (when given) the head and its channel count; raises ValueError."""
+    if not isinstance(o, dict):
+        raise ValueError(f"{what}: lovasz options are a dict (losses.lovasz_options), got {type(o).__name__}")
+    unknown = [k for k in o if k not in LOVASZ_FIELDS]
+    if unknown:
+        raise ValueError(f"{what}: unknown option(s) {unknown}")
+    if o.get("classes", "present") not in LOVASZ_CLASSES:
+        raise ValueError(f"{what}: classes {o.get('classes')!r} must be one of {LOVASZ_CLASSES}")
+    if head is not None and head not in LOVASZ_HEADS:
+        raise ValueError(f"{what}: the Lovasz loss needs binary targets: heads {', '.join(LOVASZ_HEADS)} only, '{head}' has continuous ones")
+    if num_classes is not None and not 1 <= int(num_classes) <= LOVASZ_MAX_CLASSES:
+        raise ValueError(f"{what}: {num_classes} classes, the Lovasz kernels take 1..{LOVASZ_MAX_CLASSES}")
+
+
+def lovasz_result(buf: bytes) -> dict:
+    """rua_lovasz_result (the bytes read back from the device) as a dict: n_valid, n_cls, scale (float32), G and loss_c (16 entries), loss."""
+    r = L.LovaszResult.from_buffer_copy(buf)
+    return dict(n_valid=int(r.n_valid), n_cls=int(r.n_cls), scale=np.float32(r.scale), G=[int(v) for v in r.G], loss_c=[float(v) for v in r.loss_c],
+                loss=float(r.loss))
+
+
+def host_lovasz(y_pred, y_true, void=None, classes: str = "present", loss_weight: float = 1.0) -> dict:
+    """The Lovasz-Softmax loss of probabilities p [..., C] (float32) against targets y [..., C], void [...] (non-zero = void) or None.  Per class c,
+    over the n valid pixels in flat index order:
+
+      fg = y > 0.5;  e = |float32(fg) - p| (one float32 subtraction);  G = sum fg
+      order   = the valid pixels by ohem_key(e) DESCENDING (NaN first), ties in ascending pixel index
+      F_r     = number of foreground pixels among the ranks 0..r;  J_r = 1 - (G - F_r) / (G + (r + 1) - F_r) in float64, J_-1 = 0
+      w_r     = J_r - J_{r-1};  loss_c = sum_r float64(e_(r)) w_r
+      dp      = float32(w_r) at a background pixel, -float32(w_r) at a foreground one; +0 at void pixels and in classes that are not counted
+
+    counted = G > 0 ("present") or every class ("all"); loss = sum_counted loss_c / n_cls; scale = float32(float64(float32(loss_weight)) / n_cls);
+    n = 0 or n_cls = 0: loss 0, scale 0, dp zero.  Returns dict(loss, loss_c [C] (0 where not counted), G [C], n_valid, n_cls, scale, dp (p's
+    shape, float32), order (list of C arrays of n pixel indices), w (list of C float64 arrays, by rank))."""
+    if classes not in LOVASZ_CLASSES:
+        raise ValueError(f"classes {classes!r} must be one of {LOVASZ_CLASSES}")
+    p = np.ascontiguousarray(y_pred, np.float32)
+    Cc = p.shape[-1]
+    p2 = p.reshape(-1, Cc)
+    y2 = np.asarray(y_true).reshape(-1, Cc)
+    M = p2.shape[0]
+    valid = np.ones(M, bool) if void is None else (np.asarray(void).reshape(-1) == 0)
+    idx = np.flatnonzero(valid)
+    n = int(idx.size)
+    dp = np.zeros((M, Cc), np.float32)
+    G = [int((y2[idx, c] > 0.5).sum()) for c in range(Cc)]
+    counted = [n > 0 and (classes == "all" or G[c] > 0) for c in range(Cc)]
+    n_cls = int(sum(counted))
+    loss_c, order, ws = [0.0] * Cc, [], []
+    for c in range(Cc):
+        fg = y2[idx, c] > 0.5
+        e = np.abs(fg.astype(np.float32) - p2[idx, c]).astype(np.float32)
+        key = ohem_key(e).astype(np.int64)
+        perm = np.argsort(-key, kind="stable")             # descending key; stable: ties keep the ascending pixel index
+        order.append(idx[perm].astype(np.int64))
+        fgs = fg[perm].astype(np.int64)
+        F = np.cumsum(fgs)
+        r1 = np.arange(1, n + 1, dtype=np.int64)
+        J = 1.0 - (G[c] - F).astype(np.float64) / (G[c] + r1 - F).astype(np.float64)
+        w = J - np.concatenate([[0.0], J[:-1]])
+        ws.append(w)
+        if counted[c]:
+            loss_c[c] = float(np.sum(e[perm].astype(np.float64) * w))
+            wf = w.astype(np.float32)
+            dp[idx[perm], c] = np.where(fgs == 1, -wf, wf)
+    loss = float(sum(loss_c[c] for c in range(Cc) if counted[c]) / n_cls) if n_cls else 0.0
+    scale = np.float32(np.float64(np.float32(loss_weight)) / np.float64(n_cls)) if n_cls else np.float32(0.0)
+    return dict(loss=loss, loss_c=loss_c, G=G, n_valid=n, n_cls=n_cls, scale=scale, dp=dp.reshape(p.shape), order=order, w=ws)
+
+
+def host_lovasz_dz(act: int, y_pred, dp, scale) -> np.ndarray:
+    """d(total)/d(logits) from host_lovasz's dp, in float32 with every operation rounded on its own, in this order:
+
+      softmax   s = (((g_0 p_0) + g_1 p_1) + ..) over c = 0..C-1;  dz_k = scale (p_k (g_k - s))
+      sigmoid   dz_c = scale (g_c (p_c (1 - p_c)))
+
+    A softmax pixel whose dp is zero in every class and a sigmoid element whose dp is zero - every void pixel - are +0.0f by a select, whatever p
+    holds there (the formula gives the same zero for finite p and scale >= 0)."""
+    p = np.ascontiguousarray(y_pred, np.float32)
+    g = np.ascontiguousarray(dp, np.float32)
+    sc = np.float32(scale)
+    Cc = p.shape[-1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        if act == L.ACT_SOFTMAX:
+            s = (g[..., 0] * p[..., 0]).astype(np.float32)
+            for c in range(1, Cc):
+                s = (s + (g[..., c] * p[..., c]).astype(np.float32)).astype(np.float32)
+            dz = (sc * (p * (g - s[..., None]).astype(np.float32)).astype(np.float32)).astype(np.float32)
+            return np.where((g != 0).any(-1, keepdims=True), dz, np.float32(0.0)).astype(np.float32)
+        if act == L.ACT_SIGMOID:
+            dz = (sc * (g * (p * (np.float32(1.0) - p).astype(np.float32)).astype(np.float32)).astype(np.float32)).astype(np.float32)
+            return np.where(g != 0, dz, np.float32(0.0)).astype(np.float32)
+    raise ValueError("host_lovasz_dz: act is softmax or sigmoid")
 
 
 def scalar_or_vector(alpha, num_classes: int) -> Sequence[float]:

@@ -64,6 +64,12 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
     that is weighted cross entropy.  `--label_smoothing E` smooths the targets of the cross-entropy and focal losses (not `--loss
     tanimoto`; the MSE heads take none).  All on the GPU (resunet_a_mltsk_keras_amd/losses.py); with `-cp` the loss and its options come
     from the checkpoint.
+  * `--loss lovasz [--lovasz_classes present|all]`: the Lovasz-Softmax loss (the Lovasz extension of the Jaccard index; Berman, Triki,
+    Blaschko, CVPR 2018) on the seg head and, with `--multitasking yes`, on the boundary head; dist and color get MSE.  The sort it needs
+    runs on the GPU inside the captured step (resunet_a_mltsk_keras_amd/losses.py, csrc/lovasz.hip).  It is the loss to fine-tune for mean
+    IoU: with `-cp` the checkpoint gives the weights and the optimizer's moments and step count, the command line this loss and the optimizer's settings.  `--ignore_void`
+    composes; `--ohem`, `--label_smoothing` and the focal flags do not.  Not offered: per-image averaging, the hinge form on logits, a
+    built-in mix with cross-entropy on one head.
   * `--ohem yes [--ohem_keep 0.25] [--ohem_min_kept N] [--ohem_thresh T | --ohem_prob P] [--ohem_warmup N] [--ohem_heads seg bound]`: online
     hard example mining (bootstrapped cross-entropy) - per step only the hardest pixels of the mining heads (default: seg) contribute to
     loss and gradient: the `--ohem_keep` share of the valid pixels, never fewer than N, and every pixel whose loss is at least T
@@ -113,7 +119,9 @@ def build_parser():
     p.add_argument("-dp", "--dataset_path", type=str, default="./DATASETS/patch_size=256_stride=32", help="Path where to load dataset")
     p.add_argument("-bs", "--batch_size", type=int, default=4, help="Batch size on training")
     p.add_argument("-lr", "--learning_rate", type=float, default=1e-3, help="Learning rate on training")
-    p.add_argument("--loss", type=str, default="weighted_cross_entropy", choices=["weighted_cross_entropy", "cross_entropy", "tanimoto", "focal"])
+    p.add_argument("--loss", type=str, default="weighted_cross_entropy", choices=["weighted_cross_entropy", "cross_entropy", "tanimoto", "focal", "lovasz"])
+    p.add_argument("--lovasz_classes", type=str, default="present", choices=["present", "all"],
+                   help="--loss lovasz: the classes that count in a batch - those with foreground among its valid pixels (the paper's default) or all")
     p.add_argument("-optm", "--optimizer", type=str, choices=["adam", "sgd", "lamb"], default="adam")
     p.add_argument("--lamb_epsilon", type=float, default=1e-7, metavar="E", help="-optm lamb: the epsilon of the Adam direction (default 1e-7, as the Adam of this package)")
     p.add_argument("--num_classes", type=int, default=5)
@@ -255,7 +263,7 @@ def check_void_flags(args):
         return None
     if not (args.compact_dataset or args.scene_dataset):
         sys.exit("--ignore_void yes reads the void pixels off a class map: it needs --compact_dataset yes or --scene_dataset yes (the float layout has none)")
-    if args.checkpoint_path is not None:
+    if args.checkpoint_path is not None and args.loss != "lovasz":      # (--loss lovasz -cp compiles the loaded model from the command line)
         sys.exit("--ignore_void: the option is not stored in a checkpoint, and --checkpoint_path compiles the model from the checkpoint")
     if not 0 <= args.void_margin <= 16:
         sys.exit(f"--void_margin {args.void_margin} outside 0..16")
@@ -342,6 +350,12 @@ def check_loss_flags(args):
                 sys.exit(f"{n} belongs to --loss focal, not to --loss {args.loss}")
     if args.label_smoothing and args.loss == "tanimoto":
         sys.exit("--label_smoothing: the Tanimoto loss takes no label smoothing")
+    if args.label_smoothing and args.loss == "lovasz":
+        sys.exit("--label_smoothing: the Lovasz loss takes no label smoothing")
+    if args.lovasz_classes != "present" and args.loss != "lovasz":
+        sys.exit(f"--lovasz_classes belongs to --loss lovasz, not to --loss {args.loss}")
+    if args.loss == "lovasz" and not 1 <= args.num_classes <= LS.LOVASZ_MAX_CLASSES:
+        sys.exit(f"--loss lovasz: --num_classes {args.num_classes}, the Lovasz kernels take 1..{LS.LOVASZ_MAX_CLASSES}")
     alpha = None
     if args.focal_alpha is not None:
         if args.class_weights is not None:
@@ -375,6 +389,8 @@ def check_ohem_flags(args):
         sys.exit("--ohem: with --checkpoint_path the loss, its options included, comes from the checkpoint")
     if args.loss == "tanimoto":
         sys.exit("--ohem needs a per-pixel loss: the Tanimoto loss has none")
+    if args.loss == "lovasz":
+        sys.exit("--ohem needs a per-pixel loss: the Lovasz loss has none")
     if "bound" in args.ohem_heads and not args.multitasking:
         sys.exit("--ohem_heads bound: the boundary head needs --multitasking yes")
     if args.ohem_thresh is not None and args.ohem_prob is not None:
@@ -549,6 +565,9 @@ def train_model(args, net, x_tr, y_tr, x_va, y_va, batch_size, epochs, x_shape, 
         if trust is not None:
             say(f"LAMB trust ratio: {trust['min_ratio']:.6g} .. {trust['max_ratio']:.6g} over {len(trust['ratios'])} variables "
                 f"({trust['forced']} forced to 1; {trust['updates']} updates so far)")
+        lov = net.lovasz_report() if hasattr(net, "lovasz_report") else None   # None: no head is on the Lovasz loss
+        if lov:
+            say("Lovasz loss (last step): " + "; ".join(f"{h} {r['loss']:.6g} over {r['n_cls']} classes, {r['n_valid']} valid pixels" for h, r in lov.items()))
         mined = net.ohem_report() if hasattr(net, "ohem_report") else None     # None: no head mines hard examples
         if mined:
             say("Hard example mining (last step): " + "; ".join(f"{h} kept {r['kept']:.4f} of {r['n_valid']} valid pixels, tau {r['tau']:.6g}" for h, r in mined.items()))
@@ -658,6 +677,10 @@ def main(argv=None):
     elif args.loss == "tanimoto":
         say("Using Tanimoto Dual Loss")
         loss = loss_bound = loss_reg = Tanimoto_dual_loss()
+    elif args.loss == "lovasz":
+        from resunet_a_mltsk_keras_amd.keras_api import LovaszSoftmax
+        say(f"Using Lovasz-Softmax loss (classes {args.lovasz_classes}) on seg and, multitasking, bound; MSE on dist and color")
+        loss, loss_bound, loss_reg = LovaszSoftmax(args.lovasz_classes), LovaszSoftmax(args.lovasz_classes), MeanSquaredError()
     else:
         say("Using Weighted cross entropy")
         weights = class_weights if class_weights is not None else REFERENCE_WCE_WEIGHTS if args.num_classes == 5 else [1.0] * args.num_classes
@@ -673,9 +696,18 @@ def main(argv=None):
             loss_bound = OnlineHardExampleMining(loss_bound, **ohem_kw)
     say("=" * 60)
 
-    if args.checkpoint_path is None:
-        resuneta = Resunet_a((rows, cols, channels), args.num_classes, args)
-        model = resuneta.model
+    # --loss lovasz with --checkpoint_path fine-tunes: the checkpoint gives the weights, the BatchNorm statistics, the moments and the step count,
+    # the command line the loss and the optimizer's settings (every other --loss keeps the checkpoint's loss and optimizer)
+    finetune = args.checkpoint_path is not None and args.loss == "lovasz"
+    if args.checkpoint_path is None or finetune:
+        if finetune:
+            say(f"[INFO] loading {args.checkpoint_path} to fine-tune under the Lovasz loss (the command line's optimizer settings, -lr {args.learning_rate})...")
+            model = load_model(args.checkpoint_path)
+            if bool(model.cfg.multitasking) != bool(args.multitasking):
+                sys.exit(f"--multitasking {'yes' if args.multitasking else 'no'}: the checkpoint's model is {'' if model.cfg.multitasking else 'not '}multitasking")
+        else:
+            resuneta = Resunet_a((rows, cols, channels), args.num_classes, args)
+            model = resuneta.model
         if rank == 0:
             model.summary()
         if args.multitasking:
