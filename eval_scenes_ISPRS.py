@@ -1,7 +1,7 @@
 """Evaluation of a trained model on whole scenes, on the GPU: what test_ISPRS.py does for the reference's test tile (patches,
 predict, arg-max, metrics, mosaic), for a scene directory (resunet_a_mltsk_keras_amd.scenes: scenes/<name>.npy,
 labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views, --scales, --blend, --erode_boundary,
---boundary_f1, --sieve, --pr_curve and --head_maps.
+--boundary_f1, --sieve, --pr_curve, --instances and --head_maps.
 
 Every scene stays on the GPU, is covered by windows --stride apart (default: the patch; the last window flush with the border, so
 nothing is left unpredicted), every pixel is predicted from the window it is most central in, and Model.predict_scene brings back
@@ -59,6 +59,20 @@ precision, F1 and alarm area at up to ten evenly spaced levels and the average p
 2 x 2 x 256), `pr_curve.npy` (float64 9 x T of the sum: level, tp, fp, fn, removed, recall, precision, f1, alarm area) and, with
 --pr_opened yes, `pr_opened_<name>.npy` (uint8 H x W) are written; the returned dict gains `pr_hist`, `pr_levels`, `pr_scores` and
 `average_precision`.  Not together with --scales or --blend.
+
+--instances C [C ...] [--inst_bound 0.5] [--inst_dist 0] [--inst_min_seed 8] [--inst_radius 4] [--inst_connectivity 4|8]
+[--inst_map yes] also counts and scores OBJECTS of the classes C (buildings, cars): a row of touching cars predicted as one blob is
+almost perfect per pixel and one object instead of five.  Seeds are the pixels of the finished (sieved) map of those classes whose
+predicted boundary probability is below --inst_bound and whose distance-map value is at least --inst_dist (probabilities in 0..1,
+quantised as the head maps are; --inst_bound 1.0 and --inst_dist 0 switch the tests off, which a single-task model, --scales and
+--blend need); seed regions of at least --inst_min_seed pixels are numbered and grown back over their class within --inst_radius
+pixels (0..16), all on the GPU (scenes.host_seed_map, scenes.host_instances).  The true objects are the connected regions of the
+same classes of the class map; a predicted object is a true positive at an IoU threshold t if it and a true object of its class
+overlap with IoU > t (scenes.host_instance_match, scenes.instance_scores).  Per class the predicted and true object counts, the
+object precision, recall and F1 at IoU 0.5 and the mean F1 over 0.5:0.05:0.95 are printed, summed over the scenes;
+`instances_<name>.npy` (int32 n x 8: root, class, area, seed_area, i_min, j_min, i_max, j_max), `instance_scores.npy` (float64
+C x 6: n_pred, n_true, precision, recall, F1 at 0.5, mean F1) and, with --inst_map yes, `inst_map_<name>.npy` (int32 H x W, -1
+off the objects) are written; the returned dict gains `instance_scores` and `instance_counts`.
 
 --head_maps HEAD [HEAD ...] also writes whole-scene maps of the named heads (`seg`, `bound`, `dist`, `color`, `color_rgb`; what
 test_ISPRS.py:285-414 displays per patch): `pred_<head>_<name>.npy`, uint8 H x W x Ch - the head's output averaged over the views,
@@ -130,6 +144,14 @@ def build_parser():
     parser.add_argument("--pr_min_area", type=int, default=1, metavar="A", help="area opening of every binarised map: regions below A pixels leave the count")
     parser.add_argument("--pr_connectivity", type=int, default=4, metavar="4|8", help="what connects the pixels of a region: 4- or 8-neighbours")
     parser.add_argument("--pr_opened", type=_yes, default=False, help="also write the opened map of every scene")
+    parser.add_argument("--instances", nargs="+", type=int, default=None, metavar="C",
+                        help="also count and score the objects of these classes (seeds off the predicted boundaries, grown back); default: off")
+    parser.add_argument("--inst_bound", type=float, default=0.5, metavar="P", help="a seed pixel's boundary probability lies below P (1.0: no test)")
+    parser.add_argument("--inst_dist", type=float, default=0.0, metavar="P", help="a seed pixel's distance-map value is at least P (0: no test)")
+    parser.add_argument("--inst_min_seed", type=int, default=8, metavar="N", help="seed regions of fewer than N pixels are no objects")
+    parser.add_argument("--inst_radius", type=int, default=4, metavar="R", help="seeds are grown back over their class within R pixels (0..16)")
+    parser.add_argument("--inst_connectivity", type=int, default=4, metavar="4|8", help="what connects the pixels of a seed: 4- or 8-neighbours")
+    parser.add_argument("--inst_map", type=_yes, default=False, help="also write the instance map of every scene")
     parser.add_argument("--head_maps", nargs="+", default=[], metavar="HEAD",
                         help="also write uint8 whole-scene maps of these heads: seg, bound, dist, color, color_rgb (default: none)")
     return parser
@@ -181,6 +203,22 @@ def parse_sweep(args):
     return sweep
 
 
+def parse_instances(args):
+    """--instances and its companions as predict_scene's `instances` dict (None: absent); a bound of 1.0 switches that test off."""
+    from resunet_a_mltsk_keras_amd import scenes
+    if args.instances is None:
+        return None
+    inst = dict(classes=args.instances, bound_below=256 if args.inst_bound == 1.0 else float(args.inst_bound), dist_at_least=float(args.inst_dist),
+                min_seed=args.inst_min_seed, radius=args.inst_radius, connectivity=args.inst_connectivity, map=bool(args.inst_map))
+    try:
+        p = scenes.instance_params(inst, args.num_classes)
+    except ValueError as exc:
+        raise SystemExit(f"--instances: {exc}") from None
+    if (p["bound_below"] < 256 or p["dist_at_least"] > 0) and (args.scales is not None or args.blend is not None):
+        raise SystemExit("--instances with --inst_bound below 1 or --inst_dist above 0 excludes --scales and --blend: no maps of the heads are built there")
+    return inst
+
+
 def print_curve(title, scores):
     """threshold / recall / precision / F1 / alarm area at up to ten evenly spaced levels of the curve, and the average precision"""
     n = len(scores["levels"])
@@ -218,6 +256,7 @@ def main(argv=None):
         except ValueError as exc:
             raise SystemExit(f"--sieve: {exc}") from None
     sweep = parse_sweep(args)
+    instances = parse_instances(args)
     heads = tuple(args.head_maps)
     scales = parse_scales(args.scales, args.patch_size, heads)
     if args.blend is not None and heads:
@@ -245,6 +284,8 @@ def main(argv=None):
         raise SystemExit(f"--erode_boundary: {exc}") from None
     if heads and not (model.cfg.multitasking or heads == ("seg",)):
         raise SystemExit(f"--head_maps {' '.join(heads)}: a single-task model has only the seg head")
+    if instances is not None and not model.cfg.multitasking and (instances["bound_below"] != 256 or instances["dist_at_least"] > 0):
+        raise SystemExit("--instances: a single-task model has no boundary and distance heads; give --inst_bound 1 --inst_dist 0")
     os.makedirs(args.output_path, exist_ok=True)
     lut = {k: v for k, v in LABEL_DICT.items() if v < args.num_classes}
     for extra in range(len(lut), args.num_classes):                                              # classes beyond the ISPRS colours: greys
@@ -257,6 +298,7 @@ def main(argv=None):
     total_raw, total_regions, total_changed = np.zeros_like(total), np.zeros((args.num_classes, 3), np.int64), 0
     all_head_maps, mae_sum, mae_n = [], 0.0, 0
     total_hist = np.zeros((2, 2, 256), np.int64)
+    object_scores = []
     print('=' * 40)
     print('[TEST]')
     print(f'views: {" ".join(str(c) for c in views)} ({len(views)} per window)')
@@ -273,8 +315,16 @@ def main(argv=None):
             json.dump({"views": list(views), "scales": None if scales is None else list(scales), "stride": args.stride, "blend": args.blend}, f)
     for s, name in enumerate(names):
         pred, cm, *more = model.predict_scene(pool, s, stride=args.stride, batch=max(1, args.batch_size), norm_type=args.norm_type, views=views,
-                                              erode=erode, heads=heads, boundary=boundary, scales=scales, blend=args.blend, sieve=sieve, sweep=sweep)
+                                              erode=erode, heads=heads, boundary=boundary, scales=scales, blend=args.blend, sieve=sieve, sweep=sweep,
+                                              instances=instances)
         head_maps = more.pop() if heads else {}
+        if instances is not None:
+            objects = more.pop()
+            np.save(os.path.join(args.output_path, f'instances_{name}.npy'), objects["table"])
+            if "inst" in objects:
+                np.save(os.path.join(args.output_path, f'inst_map_{name}.npy'), objects["inst"])
+            object_scores.append(objects["scores"])
+            print(f'scene {name}: {objects["n"]} predicted objects, {objects["gt_n"]} true objects, {objects["ungrown"]} pixels of the classes outside every object')
         if sweep is not None:
             swept = more.pop()
             total_hist += swept["hist"]
@@ -363,6 +413,19 @@ def main(argv=None):
         np.save(os.path.join(args.output_path, 'pr_curve.npy'),
                 np.stack([np.asarray(sc[k], np.float64) for k in ("levels", "tp", "fp", "fn", "removed", "recall", "precision", "f1", "alarm_area")]))
         res.update(pr_hist=total_hist, pr_levels=sc["levels"], pr_scores=sc, average_precision=sc["average_precision"])
+    if instances is not None:
+        sc = scenes.sum_instance_scores(object_scores)
+        at50 = int(np.flatnonzero(sc["iou_percent"] == 50)[0])
+        print()
+        print(f'Objects of the classes {" ".join(str(c) for c in args.instances)} (seeds: boundary below {args.inst_bound:g}, distance at least {args.inst_dist:g}, '
+              f'{args.inst_min_seed} px; grown {args.inst_radius} px)')
+        print('  class  predicted     true  precision   recall       F1  mean F1 (IoU 0.5:0.05:0.95)')
+        table = np.stack([sc["n_pred"].astype(np.float64), sc["n_true"].astype(np.float64), sc["precision"][:, at50], sc["recall"][:, at50],
+                          sc["f1_50"], sc["f1_mean"]], 1)
+        for c in sorted(set(args.instances)):
+            print(f'  {c:5d} {int(table[c, 0]):10d} {int(table[c, 1]):8d} {table[c, 2]:10.4f} {table[c, 3]:8.4f} {table[c, 4]:8.4f} {table[c, 5]:8.4f}')
+        np.save(os.path.join(args.output_path, 'instance_scores.npy'), table)
+        res.update(instance_scores=sc, instance_counts=np.stack([sc["n_pred"], sc["n_true"]], 1))
     if heads:
         res["head_maps"] = all_head_maps
         res["color_mae"] = mae_sum / mae_n if mae_n else None

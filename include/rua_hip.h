@@ -1077,6 +1077,55 @@ int rua_scene_sweep_hist(const uint8_t* const* scene_prob, const uint8_t* const*
                          const int32_t* scene_h, const int32_t* scene_w, int nscenes, int pix_stride, int positive, int C,
                          int64_t* hist, void* stream);
 
+/* ---- instances from whole-scene maps: seeds, grow and the object match (scenes.py, host_seed_map / host_instances /
+ * host_instance_match / instance_scores; the boundary and distance heads exist to tell touching objects of one class apart) ---------
+ * One scene per call: ids and tables are per scene.  Every pointer is DEVICE memory.
+ * rua_scene_seed_map: cls is a uint8 [H][W] class map, bound and dist (each nullable) uint8 [H][W][C] maps as rua_scene_stitch_maps
+ * writes them, marker a uint8 [H][W] map:
+ *   marker[x] = c = cls[x]  if c < C, bit c of class_mask is set, (bound null or bound[x][c] < bound_below) and
+ *                              (dist null or dist[x][c] >= dist_at_least);      255 otherwise.
+ * bound_below 1..256 (256 switches the test off), dist_at_least 0..255.  One streaming pass.
+ * rua_scene_instances: labels and areas are what rua_scene_regions wrote for `marker` (same connectivity, earlier on the same
+ * stream).  A SEED is a region of marker with a byte c < C and at least min_seed pixels; seeds are numbered 0..N-1 in ascending order
+ * of their root.  inst is int32 [H][W]: a pixel x is ELIGIBLE if c = cls[x] < C and bit c of class_mask is set; its candidates are
+ * the seed pixels y with marker[y] == c and (x - y) . (x - y) <= radius^2 (Euclidean, not geodesic; pixels outside the map do not
+ * exist); inst[x] = the id of the candidate that minimises (squared distance, id) lexicographically, -1 if there is none and on every
+ * pixel that is not eligible.  table is int32 [max_instances][8]; row k < min(N, max_instances) is written:
+ *   root, class, area, seed_area, i_min, j_min, i_max, j_max     area and box over the pixels with inst == k
+ * (an instance without a pixel: area 0, box H, W, -1, -1); rows from N on are not touched, inst always holds the true ids.
+ * n is int32 [2]: n[0] = N, the uncapped seed count, n[1] = the eligible pixels with inst == -1.  work: 4-byte aligned, work_bytes >=
+ * rua_scene_instances_work_bytes(H, W) (4 bytes per pixel and per chunk of 1024 pixels; -1 for sizes the call would refuse).
+ * Four launches whatever the map holds: count the qualifying roots per chunk of 1024 pixels; ONE block scans the chunk counts (256
+ * per pass, ceil(chunks / 256) passes) and writes N; every root takes its id and the fixed columns of its row; a block per
+ * 32 x 32 tile stages ids and marker bytes of the tile and a halo of `radius` in LDS ((32 + 2 radius)^2 entries of 5 bytes), takes
+ * the exact minimum of (d^2 << 32) | id over the disc - at most (2 radius + 1)^2 steps - for every eligible pixel and adds area and
+ * box to the table per run of equal ids along a tile row.  No block waits for another, nothing is read back, integer atomics only:
+ * scenes.host_instances gives the same bytes whatever the launch or arrival order.
+ * rua_scene_instance_match: inst_p and inst_g are int32 [H][W] instance maps, area_p points to the area cell of row 0 of the
+ * predicted table (row P's area is area_p[8 P]), match is int32 [Np][2]:
+ *   match[P] = (g, inter)  if 2 |{x : inst_p[x] == P and inst_g[x] == g}| > area_P for some 0 <= g < Ng, inter being that count;
+ *              (-1, 0)     otherwise.
+ * Ids outside 0..Np-1 and 0..Ng-1 are no instance, so Np and Ng may be upper bounds of the true counts if the rows beyond hold
+ * area 0.  The exact strict majority without a hash table or a sort: votes[P][b] counts the pixels of P whose ground-truth id has
+ * bit b set (b < bit_length(Ng - 1)), the candidate is assembled from the bits with 2 votes > area_P, a second pass counts the pixels
+ * of P on exactly that candidate, the last writes the row.  A strict-majority id collects more than half of P's pixels on each of its
+ * set bits and fewer on every other, so the candidate is that id; without one the verification rejects whatever the bits spelled.
+ * work: 4-byte aligned, work_bytes >= rua_scene_instance_match_work_bytes(Np, Ng) = 4 Np (bit_length(Ng - 1) + 2).  Five
+ * launches (four when Ng <= 1, none when Np == 0), one atomic per run of equal (P, g) inside a wave.
+ * Everything is checked on the host before anything is launched (a violation: RUA_ERR_ARG, the message names the offender, nothing is
+ * written): the required pointers, 1 <= H, W and H * W < 2^31, 1 <= C <= 64, no bit >= C in class_mask, bound_below, dist_at_least,
+ * 1 <= min_seed < 2^31, 0 <= radius <= 16, 1 <= max_instances < 2^31, 0 <= Np, Ng < 2^31, 4-byte alignment of every int32 array,
+ * the work buffers, no output sharing a byte with an input or with another output of the call. */
+int rua_scene_seed_map(const uint8_t* cls, const uint8_t* bound, const uint8_t* dist, int H, int W, int C, uint64_t class_mask,
+                       int bound_below, int dist_at_least, uint8_t* marker, void* stream);
+int64_t rua_scene_instances_work_bytes(int H, int W);
+int rua_scene_instances(const uint8_t* cls, const uint8_t* marker, const int32_t* labels, const int32_t* areas, int H, int W, int C,
+                        uint64_t class_mask, int64_t min_seed, int radius, void* work, int64_t work_bytes, int32_t* inst, int32_t* table,
+                        int64_t max_instances, int32_t* n /* device int32[2]: N, ungrown */, void* stream);
+int64_t rua_scene_instance_match_work_bytes(int64_t Np, int64_t Ng);
+int rua_scene_instance_match(const int32_t* inst_p, const int32_t* area_p /* table_p, column 2 */, int64_t Np, const int32_t* inst_g,
+                             int64_t Ng, int H, int W, void* work, int64_t work_bytes, int32_t* match, void* stream);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

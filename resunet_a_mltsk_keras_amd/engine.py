@@ -27,7 +27,8 @@ from . import losses as LS
 from . import schedules as SC
 from .wgrad_queue import WgradQueue, WSpec
 from .scenes import (BLEND_MODES, MAP_HEADS, AffineSceneBatch, SceneBatch, blend_table, check_blend_budget, check_photo_table, check_radius,
-                     check_scales, check_tolerance, check_views, scale_table, sieve_params, sweep_params, view_rows)
+                     check_scales, check_tolerance, check_views, instance_params, instance_scores, scale_table, sieve_params, sweep_params,
+                     view_rows)
 
 BN_EPS, BN_MOMENTUM, KERAS_EPS = 1e-3, 0.99, 1e-7
 HEADS = ["seg", "bound", "dist", "color"]
@@ -2684,7 +2685,8 @@ class Engine:
             cap.replay()
 
     def predict_scene(self, pool, scene: int, stride: Optional[int] = None, batch: int = 8, norm_type: int = 1, on_batch=None, views=(0,),
-                      erode: int = 0, heads=(), on_heads=None, boundary: Optional[int] = None, scales=None, blend=None, sieve=None, sweep=None):
+                      erode: int = 0, heads=(), on_heads=None, boundary: Optional[int] = None, scales=None, blend=None, sieve=None, sweep=None,
+                      instances=None):
         """The class map of a whole resident scene: (uint8 [H][W] prediction, int64 [C][C] confusion matrix indexed [true][pred], None
         for a pool without class maps).  scenes.predict_table covers the scene with windows `stride` apart (None: the patch) and gives
         every pixel to the window it is most central in; the windows go through the forward `batch` at a time - rua_scene_windows,
@@ -2766,9 +2768,35 @@ class Engine:
         "opened": uint8 [H][W] or None} is added after the sieve report and in front of the head maps, fetched once at the end;
         scenes.sweep_scores(hist, levels) is the curve.  The sweep reads probabilities, not the sieved class map; it composes with
         views, erode, boundary, sieve and heads.  ValueError, before any GPU work, for a malformed `sweep`, a pool without class
-        maps, and with scales or blend (the probabilities then live in an int32 accumulator: no maps of the heads are built)."""
+        maps, and with scales or blend (the probabilities then live in an int32 accumulator: no maps of the heads are built).
+        instances: None is every path and return value above, call for call.  Otherwise the objects of the finished map: a class
+        index, a list of classes, or a dict {classes, bound_below=128, dist_at_least=0, min_seed=1, radius=4, connectivity=4,
+        iou_percent=(50, 55 .. 95), max_instances=2^20, map=False} (scenes.instance_params; the two thresholds are byte levels, or
+        floats in 0..1 that are quantised as the maps are).  The "bound" map is stitched when bound_below < 256 and the "dist" map
+        when dist_at_least > 0, as heads= stitches them, whether or not the caller asked for them (they are returned only if asked
+        for).  After the sieve - the instances are those of the SIEVED map when sieve= is given - and before any fetch, on the
+        compute stream: rua_scene_seed_map keeps the pixels of the chosen classes that lie off the predicted boundaries and deep
+        enough in the distance map, rua_scene_regions labels that marker and rua_scene_instances numbers the seeds and grows them
+        back over their class within `radius` pixels (scenes.host_seed_map and scenes.host_instances are the definitions).  On a
+        pool with class maps the same three calls, without head maps and at radius 0, turn the pool's class map into the true
+        objects - the connected regions of the chosen classes - and rua_scene_instance_match finds for every predicted instance
+        the object that holds more than half of it (scenes.host_instance_match).  A report {"n", "ungrown", "table": int32 [n][8]
+        (scenes.TABLE_COLUMNS), "inst": int32 [H][W] (only with map=True), "gt_n", "gt_table", "match": int32 [n][2], "scores":
+        scenes.instance_scores at iou_percent} is added after the sweep report and in front of the head maps, fetched once at the
+        end; the last four entries are None without class maps.  ValueError, before any GPU work, for a malformed value, a head
+        threshold on a single-task model (give bound_below=256 there: with both head tests off only the class map is read, and
+        it works everywhere) and a head threshold together with scales or blend (no maps of the heads are built there);
+        ValueError after the fetch if the scene holds more than max_instances seeds or objects."""
         H, W, _ = self.cfg.input_shape
         Cn = self.cfg.num_classes
+        if instances is not None:
+            instances = instance_params(instances, Cn)
+            inst_heads = (("bound",) if instances["bound_below"] < 256 else ()) + (("dist",) if instances["dist_at_least"] > 0 else ())
+            if inst_heads and not self.cfg.multitasking:
+                raise ValueError(f"predict_scene(instances=): this model has no {inst_heads[0]!r} head; give bound_below=256 and dist_at_least=0")
+            if inst_heads and (blend is not None or (scales is not None and check_scales(scales, (H, W)) is not None)):
+                raise ValueError("predict_scene(instances=) with a head threshold and scales or blend: maps of the heads are not built there; "
+                                 "give bound_below=256 and dist_at_least=0, or one of the two")
         if sieve is not None:
             sieve = sieve_params(sieve, Cn)
         if sweep is not None:
@@ -2827,7 +2855,10 @@ class Engine:
         sh, sw = (C.c_int32 * 1)(SH), (C.c_int32 * 1)(SW)
         # one resident map per requested head: (source tensor, channels, mode, map, its one-entry pointer array)
         head_maps = {}
-        for h in heads + (("seg",) if sweep is not None and "seg" not in heads else ()):      # the sweep reads the seg map, asked for or not
+        extra = ("seg",) if sweep is not None and "seg" not in heads else ()                  # the sweep reads the seg map, asked for or not
+        if instances is not None:
+            extra += tuple(h for h in inst_heads if h not in heads)                           # ... and the seed map the head maps it tests
+        for h in heads + extra:
             src = g.outputs["color" if h == "color_rgb" else h]["p"]
             m = torch.zeros((SH, SW, src.C), dtype=torch.uint8, device=self.dev)
             head_maps[h] = (src, src.C, 1 if h == "color_rgb" else 0, m, (C.c_void_p * 1)(m.data_ptr()))
@@ -2919,6 +2950,18 @@ class Engine:
                              (C.c_void_p * 1)(slab.data_ptr()) if mn > 1 else None, (C.c_void_p * 1)(sarea.data_ptr()) if mn > 1 else None, st)
             L.lib().call("rua_scene_sweep_hist", prob_ptr, open_ptr if mn > 1 else None, (C.c_void_p * 1)(pool.cls_dev[sc].data_ptr()), sh, sw, 1,
                          seg_ch, positive, Cn, shist.data_ptr(), st)
+        if instances is not None:
+            # seeds, regions, grow - and the same on the ground truth, then the match: all resident, nothing fetched yet
+            ip, st, inst_keep = instances, C.c_void_p(self._stream()), []
+            cap = min(ip["max_instances"], SH * SW)
+            head_ptr = lambda h: head_maps[h][3].data_ptr() if h in inst_heads else None
+            inst_p, table_p, n_p = pool._device_instances(pred.data_ptr(), head_ptr("bound"), head_ptr("dist"), (SH, SW), Cn, ip["mask"],
+                                                          ip["bound_below"], ip["dist_at_least"], ip["min_seed"], ip["radius"], ip["connectivity"],
+                                                          cap, st, inst_keep)
+            if counted:
+                inst_g, table_g, n_g = pool._device_instances(pool.cls_dev[sc].data_ptr(), None, None, (SH, SW), Cn, ip["mask"], 256, 0, 1, 0,
+                                                              ip["connectivity"], cap, st, inst_keep)
+                imatch = pool._device_match(inst_p, table_p, inst_g, cap, (SH, SW), st, inst_keep)
         # what scores the stitched map is issued first, kernel after kernel on the compute stream; every fetch comes after
         if boundary is not None:
             bcounts = torch.zeros((Cn, 4), dtype=torch.int64, device=self.dev)
@@ -2927,6 +2970,20 @@ class Engine:
             conf_e = torch.zeros((Cn, Cn), dtype=torch.int64, device=self.dev)
             L.lib().call("rua_scene_erode", cls_ptr, sh, sw, 1, erode, None, pred_ptr, Cn, conf_e.data_ptr(), C.c_void_p(self._stream()))
         more = ({h: head_maps[h][3].cpu().numpy() for h in heads},) if heads else ()
+        if instances is not None:
+            N, ungrown = (int(v) for v in n_p.cpu().numpy())
+            if N > cap:
+                raise ValueError(f"rua_scene_instances: the scene holds {N} seeds, max_instances is {ip['max_instances']}")
+            report = {"n": N, "ungrown": ungrown, "table": table_p[:N].cpu().numpy(), "gt_n": None, "gt_table": None, "match": None, "scores": None}
+            if ip["map"]:
+                report["inst"] = inst_p.cpu().numpy()
+            if counted:
+                Ng = int(n_g.cpu().numpy()[0])
+                if Ng > cap:
+                    raise ValueError(f"rua_scene_instances: the class map holds {Ng} objects, max_instances is {ip['max_instances']}")
+                report.update(gt_n=Ng, gt_table=table_g[:Ng].cpu().numpy(), match=imatch[:N].cpu().numpy())
+                report["scores"] = instance_scores(report["table"], report["gt_table"], report["match"], Cn, ip["iou_percent"])
+            more = (report,) + more
         if sweep is not None:
             more = ({"hist": shist.cpu().numpy(), "levels": levels, "opened": opened.cpu().numpy() if want_opened else None},) + more
         if sieve is not None:

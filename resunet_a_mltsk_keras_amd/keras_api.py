@@ -774,7 +774,7 @@ class Model:
         return np.concatenate(outs, axis=0)
 
     def predict_scene(self, pool, scene, stride=None, batch=8, norm_type=1, on_batch=None, views=(0,), erode=0, heads=(), on_heads=None,
-                      boundary=None, scales=None, blend=None, sieve=None, sweep=None):
+                      boundary=None, scales=None, blend=None, sieve=None, sweep=None, instances=None):
         """Engine.predict_scene: (uint8 [H][W] class map of the pool's scene `scene`, int64 [C][C] confusion matrix [true][pred] or None
         without class maps), the windows cut, predicted and stitched on the GPU; only these two arrays come back.  views: test-time
         augmentation, a tuple of symmetry codes or a scenes.VIEW_SETS name ("none", "flips", "aug5", "all").  erode: a radius 1..16
@@ -795,31 +795,42 @@ class Model:
         probabilities against the class map, area-opened on the GPU (scenes.host_area_open, scenes.host_sweep_hist); a report
         {"hist": int64 [2][2][256], "levels", "opened": the opened map or None} is added after the sieve report and before the head
         maps, and scenes.sweep_scores(hist, levels) is the curve; needs class maps, not together with scales or blend; None changes
-        nothing."""
+        nothing.  instances: a class index, a list of classes, or a dict {classes, bound_below=128, dist_at_least=0, min_seed=1,
+        radius=4, connectivity=4 | 8, iou_percent, max_instances, map=False}: the objects of the finished (sieved) map - seeds off
+        the predicted boundaries, grown back over their class on the GPU (scenes.host_seed_map, scenes.host_instances) - and, with
+        class maps, their match against the connected regions of the ground truth (scenes.host_instance_match,
+        scenes.instance_scores); a report {"n", "ungrown", "table", "inst" (with map=True), "gt_n", "gt_table", "match", "scores"}
+        is added after the sweep report and before the head maps; a head threshold needs a multitask model and neither scales nor
+        blend (bound_below=256 reads the class map only); None changes nothing."""
         if self.engine.loss is None:                      # load_model(..., compile=False), as predict
             self.engine.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in HEADS}, weight={h: 1.0 for h in HEADS}))
         return self.engine.predict_scene(pool, scene, stride=stride, batch=batch, norm_type=norm_type, on_batch=on_batch, views=views, erode=erode,
-                                         heads=heads, on_heads=on_heads, boundary=boundary, scales=scales, blend=blend, sieve=sieve, sweep=sweep)
+                                         heads=heads, on_heads=on_heads, boundary=boundary, scales=scales, blend=blend, sieve=sieve, sweep=sweep,
+                                         instances=instances)
 
     def evaluate_scenes(self, pool, stride=None, batch_size=8, norm_type=1, views=(0,), erode=0, heads=(), boundary=None, scales=None, blend=None,
-                        sieve=None, sweep=None):
+                        sieve=None, sweep=None, instances=None):
         """predict_scene of every scene of the pool: (list of uint8 class maps, the confusion matrices summed - None without class maps);
         with erode >= 1 a third value, the matrices on the eroded ground truth summed; with boundary (a tolerance 0..16) a next
         value, the int64 [C][4] boundary counts summed over the scenes; with heads a last value, the list of the scenes'
         {head: uint8 [H][W][Ch] map} dicts.  scales, blend: predict_scene's, for every scene.  sieve: predict_scene's; the maps and
         every score are then the sieved maps', and in front of the head maps comes the region report summed over the scenes
         ({"confusion_raw": None without class maps, "counts", "changed"}).  sweep: predict_scene's; after the region report comes
-        {"hist": the scenes' histograms summed, "levels", "opened": the list of the scenes' opened maps, or None}."""
+        {"hist": the scenes' histograms summed, "levels", "opened": the list of the scenes' opened maps, or None}.  instances:
+        predict_scene's; after the sweep report comes {"scenes": the list of the scenes' reports (ids and tables are per scene),
+        "scores": scenes.sum_instance_scores of their scores, None without class maps}."""
         heads = (heads,) if isinstance(heads, str) else tuple(heads)
-        maps, total, total_e, total_b, head_maps, report, swept = [], None, None, None, [], None, None
+        maps, total, total_e, total_b, head_maps, report, swept, objects = [], None, None, None, [], None, None, []
         for s in range(len(pool)):
             m, cm, *more = self.predict_scene(pool, s, stride=stride, batch=batch_size, norm_type=norm_type, views=views, erode=erode, heads=heads,
-                                              boundary=boundary, scales=scales, blend=blend, sieve=sieve, sweep=sweep)
+                                              boundary=boundary, scales=scales, blend=blend, sieve=sieve, sweep=sweep, instances=instances)
             maps.append(m)
             if cm is not None:
                 total = cm if total is None else total + cm
             if heads:
                 head_maps.append(more.pop())
+            if instances is not None:
+                objects.append(more.pop())
             if sweep is not None:
                 r = more.pop()
                 if swept is None:
@@ -842,6 +853,10 @@ class Model:
             res += (report,)
         if sweep is not None:
             res += (swept,)
+        if instances is not None:
+            from .scenes import sum_instance_scores
+            scored = [r["scores"] for r in objects if r["scores"] is not None]
+            res += ({"scenes": objects, "scores": sum_instance_scores(scored) if scored else None},)
         return res + (head_maps,) if heads else res
 
     # -- checkpoints (train_ISPRS.py:292,474-480): real HDF5 in the Keras layout, written / read by h5lite (no h5py needed) --

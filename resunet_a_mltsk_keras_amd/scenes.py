@@ -1634,6 +1634,297 @@ def sweep_params(sweep, num_classes):
             _check_connectivity("rua_scene_area_open", sweep.get("connectivity", 4)), bool(sweep.get("opened", False)))
 
 
+# ---- instances: seeds from the class, boundary and distance maps, grown, and matched against the true objects ---------------------
+MAX_INSTANCES = 1 << 20
+IOU_PERCENT = tuple(range(50, 100, 5))
+TABLE_COLUMNS = ("root", "class", "area", "seed_area", "i_min", "j_min", "i_max", "j_max")
+_SEED, _INST, _MATCH = "rua_scene_seed_map", "rua_scene_instances", "rua_scene_instance_match"
+
+
+def _class_mask(fn: str, classes, C_: int) -> int:
+    if isinstance(classes, (str, bytes)):
+        raise ValueError(f"{fn}: classes {classes!r}: a class index or a list of them")
+    if _is_int(classes):
+        classes = (classes,)
+    mask = 0
+    for c in classes:
+        if not _is_int(c) or not 0 <= int(c) < C_:
+            raise ValueError(f"{fn}: class_mask names class {c!r}, outside 0..{C_ - 1}")
+        mask |= 1 << int(c)
+    return mask
+
+
+def _check_num_classes(fn: str, num_classes) -> int:
+    if not _is_int(num_classes) or not 1 <= int(num_classes) <= MAX_CLASSES:
+        raise ValueError(f"{fn}: C {num_classes} outside 1..64")
+    return int(num_classes)
+
+
+def _check_head_map(fn: str, a, what: str, shape, C_: int):
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.shape != tuple(shape) + (C_,):
+        raise ValueError(f"{fn}: {what} is a uint8 [{shape[0]}][{shape[1]}][{C_}] map, got {a.dtype} {a.shape}")
+    return a
+
+
+def check_seed_map(num_classes, classes, bound_below=128, dist_at_least=0, fn: str = _SEED):
+    """(C, class mask, bound_below, dist_at_least) of a seed map; ValueError, in rua_scene_seed_map's own words, unless
+    1 <= C <= 64, every class is an integer in 0..C-1, bound_below an integer in 1..256 and dist_at_least one in 0..255."""
+    C_ = _check_num_classes(fn, num_classes)
+    mask = _class_mask(fn, classes, C_)
+    if not _is_int(bound_below) or not 1 <= int(bound_below) <= 256:
+        raise ValueError(f"{fn}: bound_below {bound_below!r} outside 1..256")
+    if not _is_int(dist_at_least) or not 0 <= int(dist_at_least) <= 255:
+        raise ValueError(f"{fn}: dist_at_least {dist_at_least!r} outside 0..255")
+    return C_, mask, int(bound_below), int(dist_at_least)
+
+
+def check_instances(num_classes, classes, min_seed=1, radius=4, connectivity=4, max_instances=MAX_INSTANCES, fn: str = _INST):
+    """(C, class mask, min_seed, radius, connectivity, max_instances) of rua_scene_instances; ValueError in its own words."""
+    C_ = _check_num_classes(fn, num_classes)
+    mask = _class_mask(fn, classes, C_)
+    if not _is_int(min_seed) or not 1 <= int(min_seed) < 1 << 31:
+        raise ValueError(f"{fn}: min_seed {min_seed!r} outside 1..2147483647")
+    if not _is_int(radius) or not 0 <= int(radius) <= MAX_RADIUS:
+        raise ValueError(f"{fn}: radius {radius!r} outside 0..16")
+    conn = _check_connectivity(fn, connectivity)
+    if not _is_int(max_instances) or not 1 <= int(max_instances) < 1 << 31:
+        raise ValueError(f"{fn}: max_instances {max_instances!r} outside 1..2147483647")
+    return C_, mask, int(min_seed), int(radius), conn, int(max_instances)
+
+
+def host_seed_map(cls: np.ndarray, bound=None, dist=None, *, num_classes, classes, bound_below=128, dist_at_least=0) -> np.ndarray:
+    """The numpy definition of what rua_scene_seed_map writes, uint8 [H][W].  cls is a uint8 [H][W] class map, bound and dist (each
+    may be None) uint8 [H][W][C] maps in the layout predict_scene(heads=) returns.  marker[x] = c = cls[x] where c < C, c is in
+    `classes`, (bound is None or bound[x][c] < bound_below) and (dist is None or dist[x][c] >= dist_at_least); 255 elsewhere.
+    bound_below 1..256 (256 switches the test off), dist_at_least 0..255."""
+    C_, mask, bb, da = check_seed_map(num_classes, classes, bound_below, dist_at_least)
+    m = _check_region_map(_SEED, cls, "the class map")
+    b = _check_head_map(_SEED, bound, "the boundary map", m.shape, C_)
+    d = _check_head_map(_SEED, dist, "the distance map", m.shape, C_)
+    chosen = np.array([(mask >> c) & 1 if c < C_ else 0 for c in range(256)], bool)
+    keep = chosen[m]
+    c = np.minimum(m, C_ - 1).astype(np.int64)[..., None]               # the channel read where the pixel is kept at all
+    if b is not None:
+        keep &= np.take_along_axis(b, c, 2)[..., 0].astype(np.int64) < bb
+    if d is not None:
+        keep &= np.take_along_axis(d, c, 2)[..., 0].astype(np.int64) >= da
+    return np.where(keep, m, np.uint8(255)).astype(np.uint8)
+
+
+def host_instances(cls: np.ndarray, marker: np.ndarray, *, num_classes, classes, min_seed=1, radius=4, connectivity=4,
+                   max_instances=MAX_INSTANCES):
+    """The numpy definition of what rua_scene_regions and rua_scene_instances leave: (inst int32 [H][W], table int32
+    [min(N, max_instances)][8], n, ungrown).  A SEED is a region (host_regions under `connectivity`) of `marker` with a byte c < C and
+    at least min_seed pixels; seeds are numbered 0..N-1 in ascending order of their root, the region's smallest row-major index.
+    A pixel x is ELIGIBLE if c = cls[x] < C and c is in `classes`; its candidates are the seed pixels y with marker[y] == c and
+    (x - y) . (x - y) <= radius^2, and inst[x] is the id of the candidate that minimises the pair (squared distance, id), compared
+    lexicographically; -1 if there is none and on every pixel that is not eligible.  Pixels outside the map do not exist.  The search
+    is EUCLIDEAN, not geodesic: a seed may claim a pixel of its class across a gap of other classes that is narrower than the
+    radius - the bounded disc of host_erode and host_boundary_counts, exact in integers and free of any iteration to a fixed point.
+    A seed pixel whose class map byte equals its marker byte takes its own id, at distance 0.  Table row k is (root, class, area,
+    seed_area, i_min, j_min, i_max, j_max) - TABLE_COLUMNS -, area and bounding box over the pixels with inst == k (an instance
+    without a pixel: area 0 and the box H, W, -1, -1); inst always holds the true ids, only the table is capped.  n = N, the
+    uncapped seed count; ungrown counts the eligible pixels with inst == -1.  radius 0..16; radius 0 leaves the seeds themselves.
+    With marker = host_seed_map(cls, num_classes=C, classes=...) and radius 0 the instances are exactly the connected regions of
+    those classes: ground-truth objects are obtained this way."""
+    C_, mask, ms, r, conn, cap = check_instances(num_classes, classes, min_seed, radius, connectivity, max_instances)
+    cm = _check_region_map(_INST, cls, "the class map")
+    mk = _check_region_map(_INST, marker, "the marker map")
+    if mk.shape != cm.shape:
+        raise ValueError(f"{_INST}: the marker map is {mk.shape}, the class map {cm.shape}")
+    H, W = cm.shape
+    labels, areas = host_regions(mk, conn)
+    flat_area = areas.ravel().astype(np.int64)
+    roots = np.flatnonzero((flat_area >= ms) & (mk.ravel() < C_) & (flat_area > 0))      # ascending: the ids
+    N = len(roots)
+    id_of_root = np.full(H * W, -1, np.int64)
+    id_of_root[roots] = np.arange(N)
+    sid = id_of_root[labels]                                              # the seed id of every pixel, -1 off the seeds
+    chosen = np.array([(mask >> c) & 1 if c < C_ else 0 for c in range(256)], bool)
+    eligible = chosen[cm]
+    none = np.int64(1) << 62
+    best = np.full((H, W), none, np.int64)
+    for dy in range(-min(r, H - 1), min(r, H - 1) + 1):
+        lim = min(int(np.sqrt(r * r - dy * dy) + 1e-9), W - 1)           # isqrt: the argument is an integer below 2^9
+        for dx in range(-lim, lim + 1):
+            i0, i1, j0, j1 = max(0, -dy), min(H, H - dy), max(0, -dx), min(W, W - dx)    # the pixels whose partner exists
+            s = sid[i0 + dy:i1 + dy, j0 + dx:j1 + dx]
+            ok = (s >= 0) & (mk[i0 + dy:i1 + dy, j0 + dx:j1 + dx] == cm[i0:i1, j0:j1])
+            key = np.where(ok, (np.int64(dy * dy + dx * dx) << 32) | s, none)
+            np.minimum(best[i0:i1, j0:j1], key, out=best[i0:i1, j0:j1])
+    found = eligible & (best != none)
+    inst = np.where(found, best & 0xFFFFFFFF, -1).astype(np.int32)
+    rows = min(N, cap)
+    table = np.zeros((rows, 8), np.int32)
+    if rows:
+        table[:, 0] = roots[:rows]
+        table[:, 1] = mk.ravel()[roots[:rows]]
+        table[:, 3] = flat_area[roots[:rows]]
+        table[:, 4], table[:, 5], table[:, 6], table[:, 7] = H, W, -1, -1
+        ii, jj = np.nonzero((inst >= 0) & (inst < rows))
+        k = inst[ii, jj].astype(np.int64)
+        table[:, 2] = np.bincount(k, minlength=rows)
+        np.minimum.at(table[:, 4], k, ii.astype(np.int32))
+        np.minimum.at(table[:, 5], k, jj.astype(np.int32))
+        np.maximum.at(table[:, 6], k, ii.astype(np.int32))
+        np.maximum.at(table[:, 7], k, jj.astype(np.int32))
+    return inst, table, int(N), int((eligible & ~found).sum())
+
+
+def _check_inst_map(fn: str, a, what: str) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype != np.int32 or a.ndim != 2 or a.size == 0 or a.size >= 1 << 31:
+        raise ValueError(f"{fn}: {what} is a non-empty int32 H x W array of fewer than 2^31 pixels, got {a.dtype} {a.shape}")
+    return a
+
+
+def _check_table(fn: str, a, what: str) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype != np.int32 or a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError(f"{fn}: {what} is an int32 [N][8] array, got {a.dtype} {a.shape}")
+    return a
+
+
+def host_instance_match(inst_p: np.ndarray, table_p: np.ndarray, inst_g: np.ndarray, n_g: int) -> np.ndarray:
+    """The numpy definition of what rua_scene_instance_match writes, int32 [Np][2] with Np = len(table_p): row P is (g, inter) if
+    some ground-truth id 0 <= g < n_g has 2 |{x : inst_p[x] == P and inst_g[x] == g}| > area_P (table_p[P][2]), inter being that
+    count; (-1, 0) otherwise.  Two sets with IoU > 1/2 share more than half of each, so every match at an IoU threshold >= 0.5 has
+    such a g, and it is unique: the table is all that object scoring at those thresholds needs."""
+    p, g = _check_inst_map(_MATCH, inst_p, "inst_p"), _check_inst_map(_MATCH, inst_g, "inst_g")
+    t = _check_table(_MATCH, table_p, "table_p")
+    if p.shape != g.shape:
+        raise ValueError(f"{_MATCH}: inst_p is {p.shape}, inst_g {g.shape}")
+    if not _is_int(n_g) or not 0 <= int(n_g) < 1 << 31:
+        raise ValueError(f"{_MATCH}: Ng {n_g!r} outside 0..2147483647")
+    Np, Ng = len(t), int(n_g)
+    out = np.zeros((Np, 2), np.int32)
+    out[:, 0] = -1
+    both = (p >= 0) & (p < Np) & (g >= 0) & (g < Ng)
+    if Np and both.any():
+        pair, count = np.unique(p[both].astype(np.int64) * max(Ng, 1) + g[both].astype(np.int64), return_counts=True)
+        P = pair // max(Ng, 1)
+        won = 2 * count > t[P, 2].astype(np.int64)
+        out[P[won], 0] = (pair[won] % max(Ng, 1)).astype(np.int32)
+        out[P[won], 1] = count[won].astype(np.int32)
+    return out
+
+
+def instance_scores(table_p, table_g, match, num_classes, iou_percent=IOU_PERCENT) -> dict:
+    """Object scores from the two instance tables and host_instance_match's table.  A predicted instance P with match row (g, inter)
+    is a true positive at the threshold t (percent) if g >= 0, the classes of P and g are equal and
+    100 inter > t (area_P + area_g - inter) - strict and in integers, and t >= 50, so no two predictions can claim one object.  A
+    dict: "iou_percent" int64 [T]; "tp", "fp" = Np_c - tp and "fn" = Ng_c - tp, int64 [C][T]; "n_pred", "n_true" int64 [C];
+    "precision", "recall" and "f1" float64 [C][T] in percent (precision nan where the class has no prediction, recall nan where it
+    has no object, f1 = 200 tp / (2 tp + fp + fn), nan where it has neither); "f1_50" float64 [C], the column of threshold 50 (nan
+    if 50 is not listed) and "f1_mean" float64 [C], the mean over the thresholds."""
+    fn = "instance_scores"
+    tp_, tg_ = _check_table(fn, table_p, "table_p"), _check_table(fn, table_g, "table_g")
+    C_ = _check_num_classes(fn, num_classes)
+    m = np.asarray(match)
+    if m.dtype.kind not in "iu" or m.shape != (len(tp_), 2):
+        raise ValueError(f"{fn}: match is an integer [{len(tp_)}][2] array, got {m.dtype} {m.shape}")
+    if np.ndim(iou_percent) == 0:
+        iou_percent = (iou_percent,)
+    thr = list(iou_percent)
+    for t in thr:
+        if not _is_int(t) or not 50 <= int(t) <= 99:
+            raise ValueError(f"{fn}: iou_percent {t!r} outside 50..99 (a match below one half is not unique)")
+    if not thr or len(set(int(t) for t in thr)) != len(thr):
+        raise ValueError(f"{fn}: iou_percent {iou_percent!r}: a non-empty list of distinct thresholds")
+    thr = np.array([int(t) for t in thr], np.int64)
+    g, inter = m[:, 0].astype(np.int64), m[:, 1].astype(np.int64)
+    if ((g < -1) | (g >= len(tg_))).any():
+        raise ValueError(f"{fn}: match names an object outside 0..{len(tg_) - 1}")
+    cp, ap = tp_[:, 1].astype(np.int64), tp_[:, 2].astype(np.int64)
+    cg, ag = tg_[:, 1].astype(np.int64), tg_[:, 2].astype(np.int64)
+    has = g >= 0
+    gs = np.where(has, g, 0)
+    same = has & (cp < C_) & (cg[gs] == cp) if len(tg_) else np.zeros(len(tp_), bool)
+    union = ap + (ag[gs] if len(tg_) else 0) - inter
+    hit = same[:, None] & (100 * inter[:, None] > thr[None, :] * union[:, None])                   # [Np][T]
+    tp = np.zeros((C_, len(thr)), np.int64)
+    np.add.at(tp, np.minimum(cp, C_ - 1)[hit.any(1)], hit[hit.any(1)].astype(np.int64))
+    n_pred = np.bincount(cp[cp < C_], minlength=C_).astype(np.int64)
+    n_true = np.bincount(cg[cg < C_], minlength=C_).astype(np.int64)
+    return _object_scores(thr, tp, n_pred, n_true)
+
+
+def _object_scores(thr: np.ndarray, tp: np.ndarray, n_pred: np.ndarray, n_true: np.ndarray) -> dict:
+    fp, fn_ = n_pred[:, None] - tp, n_true[:, None] - tp
+
+    def ratio(a, b):
+        a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+        return np.divide(100.0 * a, b, out=np.full(a.shape, np.nan), where=b != 0)
+
+    f1 = ratio(2 * tp, 2 * tp + fp + fn_)
+    at50 = np.flatnonzero(thr == 50)
+    return {"iou_percent": thr, "tp": tp, "fp": fp, "fn": fn_, "n_pred": n_pred, "n_true": n_true,
+            "precision": ratio(tp, np.broadcast_to(n_pred[:, None], tp.shape)), "recall": ratio(tp, np.broadcast_to(n_true[:, None], tp.shape)),
+            "f1": f1, "f1_50": f1[:, at50[0]] if len(at50) else np.full(len(tp), np.nan), "f1_mean": f1.mean(1)}
+
+
+def sum_instance_scores(scores: Sequence[dict]) -> dict:
+    """instance_scores of several scenes as one: the true positives and the object counts are summed per class and threshold (ids
+    are per scene, counts are not) and the ratios are taken of the sums.  ValueError unless all were scored at the same thresholds."""
+    scores = list(scores)
+    if not scores:
+        raise ValueError("sum_instance_scores: no scores")
+    thr = np.asarray(scores[0]["iou_percent"], np.int64)
+    for s in scores[1:]:
+        if not np.array_equal(s["iou_percent"], thr) or s["tp"].shape != scores[0]["tp"].shape:
+            raise ValueError("sum_instance_scores: the scores differ in their thresholds or classes")
+    return _object_scores(thr, *(sum(np.asarray(s[k], np.int64) for s in scores) for k in ("tp", "n_pred", "n_true")))
+
+
+def _byte_threshold(fn: str, key: str, v, lo: int, hi: int) -> int:
+    """An integer is a byte level; a float in 0..1 is quantised as the maps are: rint(255 v)."""
+    if isinstance(v, (float, np.floating)):
+        if not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"{fn}: {key} {v!r} outside 0..1 (an integer is taken as a byte level {lo}..{hi})")
+        v = min(max(int(np.rint(255.0 * float(v))), lo), hi)
+    if not _is_int(v) or not lo <= int(v) <= hi:
+        raise ValueError(f"{fn}: {key} {v!r} outside {lo}..{hi}")
+    return int(v)
+
+
+INSTANCE_KEYS = ("classes", "bound_below", "dist_at_least", "min_seed", "radius", "connectivity", "iou_percent", "max_instances", "map")
+
+
+def instance_params(value, C) -> dict:
+    """Engine.predict_scene's `instances` as a dict of every key of INSTANCE_KEYS, checked: a class index or a list of classes
+    takes the defaults (bound_below 128, dist_at_least 0, min_seed 1, radius 4, connectivity 4, iou_percent 50, 55 .. 95,
+    max_instances 2^20, map False); a dict may hold any of the keys, `classes` is required.  bound_below and dist_at_least may be
+    floats in 0..1: they are quantised with the rounding the maps use, rint(255 v) (bound_below at least 1).  "mask" is added:
+    bit c set for every chosen class.  ValueError, in the C entries' words, for anything else."""
+    C_ = _check_num_classes(_INST, C)
+    if _is_int(value) or isinstance(value, (list, tuple, np.ndarray)):
+        value = {"classes": value}
+    if not isinstance(value, dict):
+        raise ValueError(f"instances {value!r}: None, a class index, a list of classes or a dict of {', '.join(INSTANCE_KEYS)}")
+    unknown = sorted(set(value) - set(INSTANCE_KEYS))
+    if unknown:
+        raise ValueError(f"instances: unknown key {unknown[0]!r} ({', '.join(INSTANCE_KEYS)})")
+    if "classes" not in value:
+        raise ValueError("instances: the dict needs classes")
+    classes = value["classes"]
+    if isinstance(classes, np.ndarray):
+        classes = classes.tolist()
+    bb = _byte_threshold(_SEED, "bound_below", value.get("bound_below", 128), 1, 256)
+    da = _byte_threshold(_SEED, "dist_at_least", value.get("dist_at_least", 0), 0, 255)
+    check_seed_map(C_, classes, bb, da)
+    _, mask, ms, r, conn, cap = check_instances(C_, classes, value.get("min_seed", 1), value.get("radius", 4), value.get("connectivity", 4),
+                                                value.get("max_instances", MAX_INSTANCES))
+    iou = value.get("iou_percent", IOU_PERCENT)
+    iou = (iou,) if np.ndim(iou) == 0 else tuple(iou)
+    empty = np.zeros((0, 8), np.int32)
+    instance_scores(empty, empty, np.zeros((0, 2), np.int32), C_, iou)             # its checks
+    return {"classes": tuple(c for c in range(C_) if (mask >> c) & 1), "mask": mask, "bound_below": bb, "dist_at_least": da, "min_seed": ms,
+            "radius": r, "connectivity": conn, "iou_percent": tuple(int(t) for t in iou), "max_instances": cap, "map": bool(value.get("map", False))}
+
+
 def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]]) -> int:
     """Scenes are uint8 H x W x C with one C for all, class maps uint8 H x W of their image's size.  Returns C."""
     if len(images) < 1:
@@ -1973,6 +2264,109 @@ class ScenePool:
         for k, s in enumerate(given):
             out[s] = got[first[k]:first[k + 1]].reshape(self.shapes[s]).copy()
         return out
+
+    def _device_instances(self, cls_ptr: int, bound_ptr, dist_ptr, shape, C_, mask, bb, da, ms, r, conn, cap, st, keep: list, marker=None):
+        """The three calls that turn resident maps into instances, issued on stream `st`: rua_scene_seed_map (unless `marker`, a
+        device tensor, is given), rua_scene_regions of the marker, rua_scene_instances.  Returns the device tensors (inst int32
+        [H][W], table int32 [cap][8] - zeroed first, so rows from N on hold area 0 -, n int32 [2]); every buffer the calls use is
+        appended to `keep`, which the caller holds until the stream has run them."""
+        import torch
+        from . import _lib as L
+        H, W = shape
+        dev = self.device
+        if marker is None:
+            marker = torch.empty((H, W), dtype=torch.uint8, device=dev)
+            L.lib().call(_SEED, cls_ptr, bound_ptr, dist_ptr, H, W, C_, mask, bb, da, marker.data_ptr(), st)
+        labels, areas, inst = (torch.empty((H, W), dtype=torch.int32, device=dev) for _ in range(3))
+        one = lambda v, t=C.c_void_p: (t * 1)(v)
+        L.lib().call("rua_scene_regions", one(marker.data_ptr()), one(H, C.c_int32), one(W, C.c_int32), 1, conn, one(labels.data_ptr()),
+                     one(areas.data_ptr()), 1, 1, None, st)
+        nwork = int(L.lib().raw("rua_scene_instances_work_bytes")(H, W))
+        work = torch.empty((nwork // 4,), dtype=torch.int32, device=dev)
+        table = torch.zeros((cap, 8), dtype=torch.int32, device=dev)
+        n = torch.zeros((2,), dtype=torch.int32, device=dev)
+        L.lib().call(_INST, cls_ptr, marker.data_ptr(), labels.data_ptr(), areas.data_ptr(), H, W, C_, mask, ms, r, work.data_ptr(), nwork,
+                     inst.data_ptr(), table.data_ptr(), cap, n.data_ptr(), st)
+        keep += [marker, labels, areas, work]
+        return inst, table, n
+
+    def _device_match(self, inst_p, table_p, inst_g, Ng: int, shape, st, keep: list):
+        """rua_scene_instance_match of two resident instance maps on stream `st`: the device tensor int32 [rows of table_p][2]."""
+        import torch
+        from . import _lib as L
+        Np = int(table_p.shape[0])
+        nwork = int(L.lib().raw("rua_scene_instance_match_work_bytes")(Np, Ng))
+        work = torch.empty((max(nwork // 4, 1),), dtype=torch.int32, device=self.device)
+        match = torch.empty((Np, 2), dtype=torch.int32, device=self.device)
+        L.lib().call(_MATCH, inst_p.data_ptr(), table_p.data_ptr() + 8 if Np else None, Np, inst_g.data_ptr(), Ng, shape[0], shape[1],
+                     work.data_ptr(), nwork, match.data_ptr() if Np else None, st)
+        keep.append(work)
+        return match
+
+    def instances(self, maps, bound=None, dist=None, *, num_classes, classes, bound_below=128, dist_at_least=0, min_seed=1, radius=4,
+                  connectivity=4, max_instances=MAX_INSTANCES, want_map=True):
+        """host_seed_map and host_instances of maps[s], a uint8 [H][W] class map per scene of the pool that came from a file (a None
+        entry skips its scene and gives None), with bound[s] and dist[s], uint8 [H][W][C] maps or None, as a list of
+        (inst int32 [H][W] or None without want_map, table int32 [n][8], n, ungrown): per scene one upload, rua_scene_seed_map,
+        rua_scene_regions and rua_scene_instances on the current stream, and one fetch after all scenes were issued; a "cpu" pool
+        returns the host definitions.  ValueError naming both numbers if a scene holds more than max_instances seeds."""
+        C_, mask, bb, da = check_seed_map(num_classes, classes, bound_below, dist_at_least)
+        _, _, ms, r, conn, cap = check_instances(C_, classes, min_seed, radius, connectivity, max_instances)
+        chosen = [c for c in range(C_) if (mask >> c) & 1]
+        maps = self._check_region_maps(_INST, maps)
+        heads = []
+        for what, given in (("boundary", bound), ("distance", dist)):
+            given = [None] * len(self) if given is None else list(given)
+            if len(given) != len(self):
+                raise ValueError(f"{_SEED}: {len(given)} {what} maps for {len(self)} scenes (one per scene, or None)")
+            heads.append([None if a is None or maps[s] is None else np.ascontiguousarray(_check_head_map(_SEED, a, f"scene {s}: the {what} map", self.shapes[s], C_))
+                          for s, a in enumerate(given)])
+        out = [None] * len(self)
+        if self.device.type != "cuda":
+            for s, m in enumerate(maps):
+                if m is not None:
+                    marker = host_seed_map(m, heads[0][s], heads[1][s], num_classes=C_, classes=chosen, bound_below=bb, dist_at_least=da)
+                    out[s] = host_instances(m, marker, num_classes=C_, classes=chosen, min_seed=ms, radius=r, connectivity=conn, max_instances=cap)
+        else:
+            import torch
+            with torch.cuda.device(self.device):
+                st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+                keep, issued = [], {}
+                for s, m in enumerate(maps):
+                    if m is None:
+                        continue
+                    H, W = self.shapes[s]
+                    dev = [None if a is None else torch.from_numpy(a).to(self.device) for a in (m, heads[0][s], heads[1][s])]
+                    keep += dev
+                    issued[s] = self._device_instances(dev[0].data_ptr(), None if dev[1] is None else dev[1].data_ptr(),
+                                                       None if dev[2] is None else dev[2].data_ptr(), (H, W), C_, mask, bb, da, ms, r, conn,
+                                                       min(cap, H * W), st, keep)
+                for s, (inst, table, n) in issued.items():
+                    N, ungrown = (int(v) for v in n.cpu().numpy())
+                    out[s] = (inst.cpu().numpy(), table[:min(N, cap)].cpu().numpy(), N, ungrown)
+        for s, res in enumerate(out):
+            if res is not None:
+                if res[2] > cap:
+                    raise ValueError(f"{_INST}: scene {s} holds {res[2]} seeds, max_instances is {cap}")
+                if not want_map:
+                    out[s] = (None,) + tuple(res[1:])
+        return out
+
+    def instance_match(self, inst_p, table_p, inst_g, table_g) -> np.ndarray:
+        """host_instance_match(inst_p, table_p, inst_g, len(table_g)), int32 [Np][2], of two instance maps of one size with their
+        complete tables: one upload, one rua_scene_instance_match call and one fetch; a "cpu" pool returns the host definition."""
+        p, g = _check_inst_map(_MATCH, inst_p, "inst_p"), _check_inst_map(_MATCH, inst_g, "inst_g")
+        tp, tg = _check_table(_MATCH, table_p, "table_p"), _check_table(_MATCH, table_g, "table_g")
+        if p.shape != g.shape:
+            raise ValueError(f"{_MATCH}: inst_p is {p.shape}, inst_g {g.shape}")
+        if self.device.type != "cuda" or len(tp) == 0:
+            return host_instance_match(p, tp, g, len(tg))
+        import torch
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            keep = []
+            dp, dg, dt = (torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in (p, g, tp))
+            return self._device_match(dp, dt, dg, len(tg), p.shape, st, keep).cpu().numpy()
 
     def _area_open(self, given, dev, first, lv, mn, conn, st):
         """rua_scene_area_open of the dense maps of the scenes `given` that lie in `dev` from first[k] on: the opened maps in one
