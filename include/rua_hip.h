@@ -806,6 +806,30 @@ int rua_scene_windows_affine(const uint8_t* const* scene_img, const uint8_t* con
 int rua_window_photometric(const uint8_t* img_in, uint8_t* img_out, int N, int PH, int PW, int Cin,
                            const int32_t* photo /* HOST, [N][16] */, void* stream);
 
+/* ---- copy-paste augmentation of the staged windows (scenes.py, host_paste / paste_rows / CopyPaste) ----------------------------
+ * img [N][PH][PW][Cin] and cls [N][PH][PW] are DEVICE memory, the staged windows the cutting calls above write and the targets call
+ * reads; both are required and changed in place.  scene_img[s], scene_cls[s] are laid out as in rua_scene_windows, scene_inst[s] is
+ * a DEVICE int32 [H][W] object-id map of scene s, -1 meaning no object (rua_scene_instances at radius 0 leaves one).  pastes is a
+ * HOST array, int32 [M][16], applied IN TABLE ORDER; row R:
+ *   R[0] window   R[1] scene   R[2] id   R[3] code   R[4] top   R[5] left   R[6] i0   R[7] j0   R[8] h   R[9] w
+ *   R[10], R[11] the low and high word of the 64-bit `onto` mask   R[12] flags   R[13..15] reserved, 0
+ * The crop is the scene rectangle [i0, i0 + h) x [j0, j0 + w); T is the crop under the symmetry `code` (the table of
+ * rua_scene_windows; h x w for codes 0, 2, 3, 4 and w x h for 1, 5, 6, 7 - a non-square crop is legal under every code) placed with
+ * its first pixel at (top, left) of window R[0].  For a destination pixel (y, x) of that window inside T, with source scene pixel
+ * (i, j): it is pasted iff scene_inst[s][i][j] == id and d, the destination's CURRENT class byte (after all earlier rows), satisfies
+ * d < num_classes ? bit d of onto : flags & 1.  A pasted pixel takes the Cin image bytes and the class byte of its source.  Parts of
+ * T outside the window are clipped, a row wholly outside is a no-op; windows without a row and every byte not pasted keep their bits.
+ * Integers only, so scenes.host_paste gives the same bytes.  Limits, all checked on the host before anything is launched (a
+ * violation: RUA_ERR_ARG, the message names the row and the word): R[0] non-decreasing and in 0..N-1, 0 <= scene < nscenes, id >= 0,
+ * code in 0..7, |top|, |left| <= 1024, 1 <= h, w <= 512 and the rectangle inside its scene, flags 0 or 1, reserved words 0,
+ * 1 <= PH, PW <= 512, 1 <= Cin <= 16, 1 <= num_classes <= 64, N*PH*PW*Cin < 2^31, M >= 0; M == 0 launches nothing.  The rows
+ * travel resolved as kernel arguments, 48 per launch (a window's rows may straddle two launches: the stream orders them): no
+ * device-side table, no copy, no synchronisation. */
+int rua_window_paste(uint8_t* img, uint8_t* cls, int N, int PH, int PW, int Cin, int num_classes,
+                     const uint8_t* const* scene_img, const uint8_t* const* scene_cls, const int32_t* const* scene_inst,
+                     const int32_t* scene_h, const int32_t* scene_w, int nscenes,
+                     const int32_t* pastes /* HOST, [M][16] */, int M, void* stream);
+
 /* ---- whole-scene evaluation: window probabilities -> a uint8 class map per scene and a confusion matrix (scenes.py, predict_table /
  * host_stitch; the reference's test_ISPRS.py:26-87 arg-max, mosaic and confusion_matrix done on the device) ----------------------
  * p is DEVICE memory, fp32 [N][PH][PW][C], 16-byte aligned: the class probabilities of N windows (the seg head's output).  windows

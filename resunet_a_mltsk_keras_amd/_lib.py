@@ -250,6 +250,7 @@ _SIGS = {
     "rua_scene_windows": ([vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp], i32),
     "rua_scene_windows_affine": ([vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp], i32),
     "rua_window_photometric": ([vp, vp, i32, i32, i32, i32, vp, vp], i32),
+    "rua_window_paste": ([vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp], i32),
     "rua_scene_stitch": ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp], i32),
     "rua_scene_stitch_views": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp], i32),
     "rua_scene_stitch_maps": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp], i32),

@@ -2217,13 +2217,31 @@ class Engine:
         dev = torch.device(self.dev)
         if pool.device.type != dev.type or (dev.index is not None and pool.device.index != dev.index):
             raise ValueError(f"the scene pool lives on {pool.device}, the engine on {self.dev}")
+        if x.paste is not None:
+            if not with_labels:
+                raise ValueError("a paste table changes the labels with the image: it does not go with windows cut without labels")
+            if pool.inst_ptrs is None or pool.bank_classes != self.cfg.num_classes:
+                raise ValueError(f"the pool's object bank was built for {pool.bank_classes} classes, the model has {self.cfg.num_classes}")
+
+    def _check_paste(self, x, paste):
+        """A paste table as a keyword (no-op for None): there is no such thing - the objects live in a scene pool, so only a scene
+        batch can carry a table (SceneBatch.with_paste); ValueError, before anything is uploaded or launched."""
+        if paste is None:
+            return
+        if isinstance(x, SceneBatch):
+            raise ValueError("paste: a scene batch carries its own table (SceneBatch.with_paste)")
+        raise ValueError("paste goes with scene batches only (SceneBatch.with_paste): a compact or float batch has no scene pool to take objects from")
 
     def _upload_scene(self, g: Graph, batch: SceneBatch, norm_type: int, with_labels: bool = True):
         """Scene batch (scenes.SceneBatch: resident scenes + a window table): rua_scene_windows cuts and augments the windows into
         g.compact_buffers(), then the targets call of _upload_compact - both on the compute stream, in front of the recorded plans,
         outside any captured graph.  The host passes B * 4 integers; nothing is copied.  with_labels False: images only (inference).
         An AffineSceneBatch (B * 7 integers: rotation, zoom and shift) goes through rua_scene_windows_affine in the same place.
-        A batch with a photo table (batch.photo, B * 16 integers) gets one in-place rua_window_photometric call between the two."""
+        A batch with a photo table (batch.photo, B * 16 integers) gets one in-place rua_window_photometric call between the two.
+        A batch with a paste table (batch.paste, M * 16 integers) gets one rua_window_paste call between the cut and the photo call:
+        the photometric jitter lights a pasted object together with its new background, and the void mask, made from the staged
+        class map, follows the pasted labels.  Objects are pasted at the scene's native resolution, into a zoomed affine window too.
+        A batch without a table issues no call for it."""
         self._check_scene(batch, None, norm_type, with_labels)
         pool = batch.pool
         H, W, Cin = self.cfg.input_shape
@@ -2233,9 +2251,22 @@ class Engine:
         rows = np.ascontiguousarray(batch.rows, dtype=np.int32)
         L.lib().call("rua_scene_windows_affine" if isinstance(batch, AffineSceneBatch) else "rua_scene_windows", pool.img_ptrs, pool.cls_ptrs if with_labels else None, pool.heights, pool.widths, len(pool),
                      rows.ctypes.data, g.B, H, W, Cin, img.data_ptr(), cls.data_ptr() if with_labels else None, C.c_void_p(self._stream()))
+        if batch.paste is not None:
+            self._apply_paste(g, batch)
         if batch.photo is not None:
             self._apply_photo(g, batch.photo)
         self._compact_targets(g, with_labels, int(norm_type))
+
+    def _apply_paste(self, g: Graph, batch: SceneBatch):
+        """rua_window_paste on the staged image and class map of g.compact_buffers(): on the compute stream, behind the cut and in
+        front of the photo and targets calls, outside any captured graph.  The host passes M * 16 integers; the objects come from
+        the pool's resident scenes and id maps (ScenePool.object_bank)."""
+        pool = batch.pool
+        img, cls, _ = g.compact_buffers()
+        H, W, Cin = self.cfg.input_shape
+        t = np.ascontiguousarray(batch.paste, dtype=np.int32)
+        L.lib().call("rua_window_paste", img.data_ptr(), cls.data_ptr(), g.B, H, W, Cin, self.cfg.num_classes, pool.img_ptrs, pool.cls_ptrs,
+                     pool.inst_ptrs, pool.heights, pool.widths, len(pool), t.ctypes.data if len(t) else None, len(t), C.c_void_p(self._stream()))
 
     def _put_batch(self, g: Graph, x, y, norm_type: Optional[int], with_labels: bool = True, void_mask=None, photo=None):
         """norm_type None: float batch (_upload); 1 or 2: compact uint8 batch (_upload_compact).  x a SceneBatch: _upload_scene
@@ -2276,13 +2307,14 @@ class Engine:
             self.ow_flag.fill_(v)
             self._ow = v
 
-    def forward_backward(self, x=None, y=None, _whole_step: bool = False, norm_type: Optional[int] = None, void_mask=None, photo=None):
+    def forward_backward(self, x=None, y=None, _whole_step: bool = False, norm_type: Optional[int] = None, void_mask=None, photo=None, paste=None):
         """forward + losses + backward on the current stream; gradients are ADDED to self.G (several calls before one optimizer_step accumulate, e.g. the
         replicas of a data-parallel step played one after the other); _whole_step (train_step): the arena is zero and this is the step's only backward.
         norm_type 1 / 2: x, y are a compact batch (uint8 image, uint8 class map; _upload_compact); photo: as train_step."""
         self._check_scene(x, y, norm_type)
         self._check_void(x, norm_type, void_mask)
         photo = self._check_photo(x, norm_type, photo)
+        self._check_paste(x, paste)
         # first-writer overwrite needs a ZERO gradient arena: after a standalone forward_backward() (which accumulates) the arena holds
         # unapplied gradients, and the next whole step must accumulate on top of them too (mixing the two calls keeps its old meaning)
         self._set_overwrite(1 if (_whole_step and self.wgrad_overwrite and not self._g_pending) else 0)
@@ -2608,17 +2640,20 @@ class Engine:
         self.weights_dirty = True
         return g
 
-    def train_step(self, x=None, y=None, fetch: bool = True, norm_type: Optional[int] = None, void_mask=None, photo=None):
+    def train_step(self, x=None, y=None, fetch: bool = True, norm_type: Optional[int] = None, void_mask=None, photo=None, paste=None):
         """One Keras train_on_batch (train_ISPRS.py:131,148): returns the metric list in the reference's order.
         norm_type 1 / 2: x, y are a compact batch - uint8 image [B,H,W,Cin], uint8 class map [B,H,W] - whose float input and targets
         are built on the device (_upload_compact) before the step.  x a scenes.SceneBatch (y None, norm_type 1 / 2): the patches are cut
         from the resident scenes on the device (_upload_scene).  void_mask (float batches of a model compiled with ignore_void): uint8 or bool
         [B,H,W], non-zero = void; class-map and scene batches derive theirs from the class map (rua_void_mask).  photo (compact uint8
         batches): an int32 [B][16] photo table (scenes.check_photo_table) - the uploaded image is jittered in place
-        (rua_window_photometric) before the targets are built; a scene batch carries its own, a float batch has none: ValueError."""
+        (rua_window_photometric) before the targets are built; a scene batch carries its own, a float batch has none: ValueError.
+        paste: always a ValueError - pasted objects come from a scene pool, so only a scene batch carries a paste table
+        (SceneBatch.with_paste), which _upload_scene applies between the cut and the photo call."""
         self._check_scene(x, y, norm_type)
         self._check_void(x, norm_type, void_mask)
         photo = self._check_photo(x, norm_type, photo)
+        self._check_paste(x, paste)
         if self.use_graph and self.dist is None:
             g = self._graph_step(x, y, norm_type, void_mask, photo)
             return self._results(g) if fetch else None
@@ -2631,11 +2666,12 @@ class Engine:
         self.optimizer_step(1.0 / self.world)
         return self._results(g) if fetch else None
 
-    def test_step(self, x, y, norm_type: Optional[int] = None, void_mask=None, photo=None):
+    def test_step(self, x, y, norm_type: Optional[int] = None, void_mask=None, photo=None, paste=None):
         """Keras test_on_batch (train_ISPRS.py:167,186): BN uses moving statistics, nothing is updated.  norm_type, void_mask, photo: as train_step."""
         self._check_scene(x, y, norm_type)
         self._check_void(x, norm_type, void_mask)
         photo = self._check_photo(x, norm_type, photo)
+        self._check_paste(x, paste)
         g = self.graph(x.shape[0], False)
         s = self._stream()
         self._put_batch(g, x, y, norm_type, void_mask=void_mask, photo=photo)

@@ -732,12 +732,14 @@ class Model:
         t = self.engine._check_photo(x, 1 if cb is not None else None, photo)
         return self._local_batch(t, None, local_shard)[0]
 
-    def train_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, void_mask=None, photo=None, **_):
+    def train_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, void_mask=None, photo=None, paste=None, **_):
         """y an integer class map [B,H,W] (x then uint8 [B,H,W,Cin]): the compact path - x / norm_type and the targets seg, bound, dist
         and color (labels.py) are built on the GPU.  void_mask (float batches, compile(ignore_void=...)): uint8 or bool [B,H,W], non-zero =
         void; sharded like y under data parallel.  photo (compact batches): an int32 [B][16] photo table (scenes.photo_rows,
-        PhotoJitter.draw) - the image is jittered on the GPU before x and the targets are built; sharded like y."""
+        PhotoJitter.draw) - the image is jittered on the GPU before x and the targets are built; sharded like y.  paste: refused
+        (ValueError) - copy-paste takes its objects from a scene pool, so a scene batch carries the table (SceneBatch.with_paste)."""
         assert self._compiled, "compile() first"
+        self.engine._check_paste(x, paste)
         self._sync_lr()
         vm = self._void(x, y, void_mask, local_shard)
         ph = self._photo(x, y, photo, local_shard)
@@ -745,8 +747,9 @@ class Model:
         res = self.engine.train_step(x, y, norm_type=nt, void_mask=vm, photo=ph)
         return dict(zip(self.metrics_names, res)) if return_dict else res
 
-    def test_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, void_mask=None, photo=None, **_):
+    def test_on_batch(self, x, y=None, return_dict=False, local_shard=False, norm_type=1, void_mask=None, photo=None, paste=None, **_):
         assert self._compiled, "compile() first"
+        self.engine._check_paste(x, paste)
         vm = self._void(x, y, void_mask, local_shard)
         ph = self._photo(x, y, photo, local_shard)
         x, y, nt = self._batch(x, y, norm_type, local_shard)

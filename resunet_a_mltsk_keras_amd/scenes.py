@@ -32,6 +32,12 @@ colour matrix and offsets, a tone value, a noise amplitude and seed, all Q16 - (
 rua_window_photometric, csrc/photo.hip, its kernel).  photo_rows() makes rows from brightness, contrast, saturation, hue, tone and
 noise sigma, SceneBatch.with_photo() carries them, PhotoJitter draws them and SceneLoader(photo=) hands them out.
 
+Copy-paste augmentation (Ghiasi et al., CVPR 2021) sits between the two: an int32 [M][16] paste table whose rows drop ground-truth
+objects of the scenes - hard mask and label together - into the cut windows (host_paste is the definition, rua_window_paste,
+csrc/paste.hip, its kernel).  host_object_bank() / ScenePool.object_bank() find the objects (the connected regions of chosen classes,
+as int32 id maps and a table of class, area and bounding box), paste_rows() makes rows from bank entries, SceneBatch.with_paste()
+carries them, CopyPaste draws them - the class uniformly, so a rare class is seen more often - and SceneLoader(paste=) hands them out.
+
 Whole-scene evaluation goes the other way: predict_table() covers a scene with windows (the last one flush with the border) and
 gives every scene pixel to exactly one of them, an int32 [N][4] ownership table of (r0, r1, c0, c1) rectangles in window
 coordinates next to the window rows; rua_scene_stitch writes the arg-max of each owned pixel's class probabilities into a uint8
@@ -1925,6 +1931,236 @@ def instance_params(value, C) -> dict:
             "radius": r, "connectivity": conn, "iou_percent": tuple(int(t) for t in iou), "max_instances": cap, "map": bool(value.get("map", False))}
 
 
+# ---- copy-paste augmentation: ground-truth objects dropped into the staged windows, mask and label together ----------------------
+_PASTE = "rua_window_paste"
+MAX_PASTE_OFFSET = 1024
+BANK_COLUMNS = ("scene", "id", "class", "area", "i_min", "j_min", "i_max", "j_max")
+PASTE_WORDS = ("window", "scene", "id", "code", "top", "left", "i0", "j0", "h", "w", "onto_lo", "onto_hi", "flags")
+
+
+def check_paste_table(shapes: Sequence[Sequence[int]], pastes, N: int, patch, num_classes: int, channels: int = 1) -> np.ndarray:
+    """The paste table as a contiguous int32 [M][16] array (M may be 0); ValueError, in rua_window_paste's own words and order, for
+    the first violation.  shapes: the (H, W) of every scene; N windows of `patch`; words 10 and 11, the onto mask, are taken mod 2^32."""
+    fn = _PASTE
+    ph, pw = _patch2(patch)
+    t = np.asarray(pastes)
+    if t.ndim != 2 or t.shape[1] != 16 or not (np.issubdtype(t.dtype, np.integer) or t.size == 0):
+        raise ValueError(f"a paste table is an integer [M][16] array of (window, scene, id, code, top, left, i0, j0, h, w, onto_lo, onto_hi, "
+                         f"flags, 0, 0, 0) rows, got {t.dtype} {t.shape}")
+    if not _is_int(N) or N < 1:
+        raise ValueError(f"{fn}: N {N} (>= 1)")
+    if not _is_int(channels) or not 1 <= channels <= MAX_CHANNELS:
+        raise ValueError(f"{fn}: Cin {channels} outside 1..16")
+    if not (1 <= ph <= MAX_PATCH and 1 <= pw <= MAX_PATCH):
+        raise ValueError(f"{fn}: PH {ph}, PW {pw} (1 <= PH, PW <= 512)")
+    if not _is_int(num_classes) or not 1 <= int(num_classes) <= MAX_CLASSES:
+        raise ValueError(f"{fn}: C {num_classes} outside 1..64")
+    if int(N) * ph * pw * int(channels) >= 1 << 31:
+        raise ValueError(f"{fn}: N*PH*PW*Cin is {int(N) * ph * pw * int(channels)} (must stay below 2^31)")
+    t64 = t.astype(np.int64).reshape(-1, 16)
+    t64[:, 10:12] = ((t64[:, 10:12] + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)
+    if ((t64 < -(1 << 31)) | (t64 >= 1 << 31)).any():
+        raise ValueError(f"{fn}: a word leaves the int32 range")
+    n = len(shapes)
+    if len(t64) and n < 1:
+        raise ValueError(f"{fn}: nscenes {n} (>= 1)")
+    prev = 0
+    for k, R in enumerate(t64.tolist()):
+        if not 0 <= R[0] < N:
+            raise ValueError(f"{fn}: row {k}: word 0: window {R[0]} outside 0..{N - 1}")
+        if k and R[0] < prev:
+            raise ValueError(f"{fn}: row {k}: word 0: window {R[0]} after window {prev} (rows are sorted by window)")
+        prev = R[0]
+        if not 0 <= R[1] < n:
+            raise ValueError(f"{fn}: row {k}: word 1: scene {R[1]} outside 0..{n - 1}")
+        if R[2] < 0:
+            raise ValueError(f"{fn}: row {k}: word 2: id {R[2]} is negative")
+        if not 0 <= R[3] < NUM_CODES:
+            raise ValueError(f"{fn}: row {k}: word 3: code {R[3]} outside 0..7")
+        for q, what in ((4, "top"), (5, "left")):
+            if abs(R[q]) > MAX_PASTE_OFFSET:
+                raise ValueError(f"{fn}: row {k}: word {q}: {what} {R[q]} outside -1024..1024")
+        for q, what in ((8, "h"), (9, "w")):
+            if not 1 <= R[q] <= MAX_PATCH:
+                raise ValueError(f"{fn}: row {k}: word {q}: {what} {R[q]} outside 1..512")
+        H, W = int(shapes[R[1]][0]), int(shapes[R[1]][1])
+        if R[6] < 0 or R[6] + R[8] > H:
+            raise ValueError(f"{fn}: row {k}: word 6: rows {R[6]} + {R[8]} leave the {H} x {W} scene")
+        if R[7] < 0 or R[7] + R[9] > W:
+            raise ValueError(f"{fn}: row {k}: word 7: columns {R[7]} + {R[9]} leave the {H} x {W} scene")
+        if R[12] not in (0, 1):
+            raise ValueError(f"{fn}: row {k}: word 12: flags {R[12]} (0, or 1: paste over pixels of no class)")
+        for q in (13, 14, 15):
+            if R[q] != 0:
+                raise ValueError(f"{fn}: row {k}: word {q}: reserved, must be 0, got {R[q]}")
+    return np.ascontiguousarray(t64, dtype=np.int32)
+
+
+def host_paste(img: np.ndarray, cls: np.ndarray, images: Sequence[np.ndarray], class_maps: Sequence[np.ndarray],
+               inst_maps: Sequence[np.ndarray], pastes, num_classes: int):
+    """The numpy definition of what rua_window_paste leaves: (img uint8 [N][PH][PW][Cin], cls uint8 [N][PH][PW]), copies of the
+    arguments with the int [M][16] rows of `pastes` applied IN TABLE ORDER.  Row (window, scene, id, code, top, left, i0, j0, h, w,
+    onto_lo, onto_hi, flags, 0, 0, 0): the crop is scene[i0:i0+h, j0:j0+w], T = transform(crop, code) lies with its first pixel at
+    (top, left) of the window, clipped to it; a destination pixel inside T is pasted iff its source pixel's inst_maps[scene] value
+    is `id` and its CURRENT class byte d (after every earlier row) is allowed - d < num_classes: bit d of the 64-bit mask
+    onto_lo | onto_hi << 32; otherwise: flags & 1.  A pasted pixel takes its source's image bytes and class byte."""
+    img, cls = np.array(img, copy=True), np.array(cls, copy=True)
+    if img.dtype != np.uint8 or img.ndim != 4 or cls.dtype != np.uint8 or cls.shape != img.shape[:3]:
+        raise ValueError(f"windows are uint8 [N][PH][PW][Cin] with a uint8 [N][PH][PW] class map, got {img.dtype} {img.shape} and {cls.dtype} {cls.shape}")
+    N, PH, PW, Cin = img.shape
+    t = check_paste_table([im.shape for im in images], pastes, N, (PH, PW), num_classes, Cin)
+    for n, s, id_, code, top, left, i0, j0, h, w, lo, hi, flags in t[:, :13].tolist():
+        mask = (lo & 0xFFFFFFFF) | ((hi & 0xFFFFFFFF) << 32)
+        crop = np.s_[i0:i0 + h, j0:j0 + w]
+        Ti, Tc, Tm = transform(images[s][crop], code), transform(class_maps[s][crop], code), transform(np.asarray(inst_maps[s])[crop] == id_, code)
+        th, tw = Tm.shape
+        y0, y1, x0, x1 = max(top, 0), min(top + th, PH), max(left, 0), min(left + tw, PW)
+        if y0 >= y1 or x0 >= x1:
+            continue
+        allowed = np.array([(mask >> d) & 1 if d < num_classes else flags & 1 for d in range(256)], bool)
+        src = np.s_[y0 - top:y1 - top, x0 - left:x1 - left]
+        m = Tm[src] & allowed[cls[n, y0:y1, x0:x1]]
+        img[n, y0:y1, x0:x1][m] = Ti[src][m]
+        cls[n, y0:y1, x0:x1][m] = Tc[src][m]
+    return img, cls
+
+
+def _bank_rows(s: int, table: np.ndarray, max_area, max_extent) -> np.ndarray:
+    """The bank rows of scene s from its complete instance table: the area and extent filters of host_object_bank."""
+    t = np.asarray(table, np.int64).reshape(-1, 8)
+    keep = (t[:, 2] >= 1) & (t[:, 6] - t[:, 4] < max_extent) & (t[:, 7] - t[:, 5] < max_extent)
+    if max_area is not None:
+        keep &= t[:, 2] <= max_area
+    k = np.flatnonzero(keep)
+    out = np.empty((len(k), 8), np.int32)
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3], out[:, 4:] = s, k, t[k, 1], t[k, 2], t[k, 4:]
+    return out
+
+
+def _check_bank_filters(min_area, max_area, max_extent, default_extent: int):
+    if not _is_int(min_area) or not 1 <= int(min_area) < 1 << 31:
+        raise ValueError(f"object bank: min_area {min_area!r} outside 1..2147483647")
+    if max_area is not None and (not _is_int(max_area) or int(max_area) < int(min_area)):
+        raise ValueError(f"object bank: max_area {max_area!r} below min_area {min_area}")
+    if max_extent is None:
+        max_extent = default_extent
+    if not _is_int(max_extent) or not 1 <= int(max_extent) <= MAX_PATCH:
+        raise ValueError(f"object bank: max_extent {max_extent!r} outside 1..512 (what rua_window_paste takes)")
+    return int(min_area), None if max_area is None else int(max_area), int(max_extent)
+
+
+def host_object_bank(class_maps: Sequence[np.ndarray], num_classes: int, classes, min_area: int = 1, max_area: Optional[int] = None,
+                     max_extent: Optional[int] = None, connectivity: int = 4):
+    """The ground-truth objects of uint8 [H][W] class maps, to paste: (inst_maps, bank).  inst_maps[s] is int32 [H][W], host_instances
+    at radius 0 of host_seed_map (no heads) with min_seed = min_area: the connected regions (under `connectivity`) of the chosen
+    `classes` with at least min_area pixels, numbered per scene from 0 in ascending order of their root (smallest row-major index);
+    -1 elsewhere.  bank is int32 [K][8], rows (scene, id, class, area, i_min, j_min, i_max, j_max) - BANK_COLUMNS - in (scene, id)
+    order, of the objects with area <= max_area (None: no limit) whose bounding box is at most max_extent high and wide (None: 512,
+    the largest crop rua_window_paste takes)."""
+    mn, mx, ext = _check_bank_filters(min_area, max_area, max_extent, MAX_PATCH)
+    inst_maps, parts = [], []
+    for s, cm in enumerate(class_maps):
+        marker = host_seed_map(cm, num_classes=num_classes, classes=classes)
+        cap = min(MAX_INSTANCES, marker.size)
+        inst, table, n, _ = host_instances(cm, marker, num_classes=num_classes, classes=classes, min_seed=mn, radius=0, connectivity=connectivity,
+                                           max_instances=cap)
+        if n > cap:
+            raise ValueError(f"object bank: scene {s} holds {n} objects, more than {cap}")
+        inst_maps.append(inst)
+        parts.append(_bank_rows(s, table, mx, ext))
+    return inst_maps, (np.concatenate(parts) if parts else np.zeros((0, 8), np.int32))
+
+
+def _onto_masks(onto, classes: np.ndarray) -> np.ndarray:
+    """The uint64 onto mask of rows that paste `classes` [M]: None - every class; a sequence of classes - those, for every row; a dict
+    pasted class -> classes it may cover (a class without an entry: every class)."""
+    every = np.uint64(0xFFFFFFFFFFFFFFFF)
+    out = np.full(len(classes), every, np.uint64)
+    if onto is None:
+        return out
+    if isinstance(onto, dict):
+        for src, dst in onto.items():
+            out[classes == int(src)] = np.uint64(_class_mask("paste onto", dst, MAX_CLASSES))
+        return out
+    out[:] = np.uint64(_class_mask("paste onto", onto, MAX_CLASSES))
+    return out
+
+
+def paste_rows(bank: np.ndarray, window, bank_index, code, top, left, onto=None, over_void: bool = False) -> np.ndarray:
+    """int32 [M][16] paste rows from rows of an object bank: row m pastes object bank[bank_index[m]] - its bounding box is the crop -
+    under code[m] with its first pixel at (top[m], left[m]) of window[m]; every argument a scalar or a length-M array.  onto: None
+    (the object may cover every class), a sequence of classes, or a dict {pasted class: classes it may cover}; over_void: it may also
+    cover pixels that hold no class (a byte >= num_classes).  The rows come back in the order given: a table is sorted by window."""
+    b = _check_table("paste_rows", np.asarray(bank, np.int32), "the bank").astype(np.int64)
+    args = np.broadcast_arrays(*(np.asarray(v, np.int64) for v in (window, bank_index, code, top, left)))
+    win, idx, code, top, left = (a.reshape(-1) for a in args)
+    if len(idx) and (idx.min() < 0 or idx.max() >= len(b)):
+        raise ValueError(f"paste_rows: bank_index outside 0..{len(b) - 1}")
+    o = b[idx]
+    out = np.zeros((len(idx), 16), np.int64)
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3], out[:, 4], out[:, 5] = win, o[:, 0], o[:, 1], code, top, left
+    out[:, 6], out[:, 7], out[:, 8], out[:, 9] = o[:, 4], o[:, 5], o[:, 6] - o[:, 4] + 1, o[:, 7] - o[:, 5] + 1
+    masks = _onto_masks(onto, o[:, 2])
+    out[:, 10] = (masks & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)
+    out[:, 11] = (masks >> np.uint64(32)).astype(np.uint32).view(np.int32)
+    out[:, 12] = 1 if over_void else 0
+    return out.astype(np.int32)
+
+
+class CopyPaste:
+    """The random part of SceneLoader's copy-paste augmentation (Ghiasi et al., CVPR 2021): per window a number of pastes uniform in
+    per_window = (lo, hi), both included; per paste the class uniform over those of `classes` that have objects in the bank - not
+    over the objects, so a rare class is pasted as often as a common one -, the object uniform within its class, the code uniform
+    in 0..7 and the position uniform over the placements that lie fully inside the window.  onto, over_void: as paste_rows."""
+
+    def __init__(self, classes, per_window: Tuple[int, int] = (0, 3), onto=None, over_void: bool = False):
+        self.classes = tuple(sorted({int(c) for c in ((classes,) if _is_int(classes) else classes)}))
+        if not self.classes or min(self.classes) < 0 or max(self.classes) >= MAX_CLASSES:
+            raise ValueError(f"classes {classes!r}: one or more class indices in 0..63")
+        lo, hi = int(per_window[0]), int(per_window[1])
+        if not 0 <= lo <= hi:
+            raise ValueError(f"per_window range ({lo}, {hi}): 0 <= lo <= hi")
+        self.per_window, self.over_void = (lo, hi), bool(over_void)
+        _onto_masks(onto, np.zeros(0, np.int64))
+        self.onto = onto
+
+    def draw(self, rng: np.random.Generator, bank: np.ndarray, n: int, patch, num_classes: int) -> np.ndarray:
+        """The int32 [M][16] paste table of n windows of `patch`, sorted by window - drawn from rng in this order: the n counts, then
+        for all M pastes at once the classes, the objects, the codes, the tops, the lefts.  Objects whose bounding box does not fit
+        into the patch under every code (a side above the smaller patch side) are never drawn."""
+        ph, pw = _patch2(patch)
+        b = _check_table("CopyPaste.draw", np.asarray(bank, np.int32), "the bank").astype(np.int64)
+        if any(c >= num_classes for c in self.classes):
+            raise ValueError(f"CopyPaste: classes {self.classes} for a model of {num_classes} classes")
+        h, w = b[:, 6] - b[:, 4] + 1, b[:, 7] - b[:, 5] + 1
+        fits = np.maximum(h, w) <= min(ph, pw)
+        members = [np.flatnonzero(fits & (b[:, 2] == c)) for c in self.classes]
+        members = [m for m in members if len(m)]
+        counts = rng.integers(self.per_window[0], self.per_window[1] + 1, int(n))
+        M = int(counts.sum())
+        if not members or M == 0:
+            return np.zeros((0, 16), np.int32)
+        which = rng.integers(0, len(members), M)
+        size = np.array([len(m) for m in members], np.int64)[which]
+        pick = np.minimum((rng.random(M) * size).astype(np.int64), size - 1)
+        idx = np.array([members[c][p] for c, p in zip(which.tolist(), pick.tolist())], np.int64)
+        code = rng.integers(0, NUM_CODES, M)
+        tr = np.isin(code, TRANSPOSING)
+        th, tw = np.where(tr, w[idx], h[idx]), np.where(tr, h[idx], w[idx])
+        top = np.minimum((rng.random(M) * (ph - th + 1)).astype(np.int64), ph - th)
+        left = np.minimum((rng.random(M) * (pw - tw + 1)).astype(np.int64), pw - tw)
+        return paste_rows(b, np.repeat(np.arange(int(n)), counts), idx, code, top, left, self.onto, self.over_void)
+
+
+def _paste_take(table: np.ndarray, windows: np.ndarray) -> np.ndarray:
+    """The rows of a paste table whose window is one of `windows` (old indices, in their new order), renumbered and sorted."""
+    new = {int(old): k for k, old in enumerate(windows.tolist())}
+    keep = [k for k, wdw in enumerate(table[:, 0].tolist()) if wdw in new]
+    out = table[keep].copy()
+    out[:, 0] = [new[int(wdw)] for wdw in out[:, 0]]
+    return np.ascontiguousarray(out[np.argsort(out[:, 0], kind="stable")])
+
+
 def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.ndarray]]) -> int:
     """Scenes are uint8 H x W x C with one C for all, class maps uint8 H x W of their image's size.  Returns C."""
     if len(images) < 1:
@@ -1948,10 +2184,13 @@ def check_scenes(images: Sequence[np.ndarray], class_maps: Optional[Sequence[np.
 class SceneBatch:
     """A batch named by index: a pool, int32 [B][4] table rows and the patch size.  Takes the place of x in Engine.train_step /
     test_step / predict and Model.train_on_batch / test_on_batch / predict (y is None: the class maps are the pool's).
-    photo: None, or the checked int32 [B][16] photo table (check_photo_table) whose row k jitters window k after it is cut."""
+    photo: None, or the checked int32 [B][16] photo table (check_photo_table) whose row k jitters window k after it is cut.
+    paste: None, or the checked int32 [M][16] paste table (check_paste_table) whose rows drop objects of the pool's bank into the
+    cut windows, before the photo table lights them."""
 
-    def __init__(self, pool: "ScenePool", rows: np.ndarray, patch: Tuple[int, int], photo: Optional[np.ndarray] = None):
-        self.pool, self.rows, self.patch, self.photo = pool, rows, patch, photo
+    def __init__(self, pool: "ScenePool", rows: np.ndarray, patch: Tuple[int, int], photo: Optional[np.ndarray] = None,
+                 paste: Optional[np.ndarray] = None):
+        self.pool, self.rows, self.patch, self.photo, self.paste = pool, rows, patch, photo, paste
 
     @property
     def shape(self):
@@ -1961,19 +2200,31 @@ class SceneBatch:
         return self.rows.shape[0]
 
     def __getitem__(self, sl):
+        """The windows of a slice, with their photo rows and their paste rows (renumbered to the slice's windows)."""
         if not isinstance(sl, slice):
             raise TypeError("a SceneBatch is sliced, not indexed")
         return type(self)(self.pool, np.ascontiguousarray(self.rows[sl]), self.patch,
-                          None if self.photo is None else np.ascontiguousarray(self.photo[sl]))
+                          None if self.photo is None else np.ascontiguousarray(self.photo[sl]),
+                          None if self.paste is None else _paste_take(self.paste, np.arange(len(self))[sl]))
 
     def with_photo(self, table16) -> "SceneBatch":
         """A batch of the same class and rows that carries this photo table, one row per window (None: none)."""
         if table16 is None:
-            return type(self)(self.pool, self.rows, self.patch, None)
+            return type(self)(self.pool, self.rows, self.patch, None, self.paste)
         t = check_photo_table(table16, self.pool.channels)
         if len(t) != len(self):
             raise ValueError(f"{len(t)} photo rows for a batch of {len(self)} windows")
-        return type(self)(self.pool, self.rows, self.patch, t)
+        return type(self)(self.pool, self.rows, self.patch, t, self.paste)
+
+    def with_paste(self, table) -> "SceneBatch":
+        """A batch of the same class, rows and photo table that carries this paste table (None: none), checked against the pool in
+        rua_window_paste's words.  The ids are those of the pool's resident id maps: ValueError before ScenePool.object_bank()."""
+        if table is None:
+            return type(self)(self.pool, self.rows, self.patch, self.photo, None)
+        if self.pool.bank is None:
+            raise ValueError("with_paste: this pool has no object bank yet (ScenePool.object_bank() builds the id maps a paste row names)")
+        t = check_paste_table(self.pool.shapes, table, len(self), self.patch, self.pool.bank_classes, self.pool.channels)
+        return type(self)(self.pool, self.rows, self.patch, self.photo, t)
 
     def shard(self, rank: int, world: int) -> "SceneBatch":
         """This rank's contiguous share of a global batch (the split Model._local_batch makes)."""
@@ -1986,8 +2237,13 @@ class SceneBatch:
         return host_windows(self.pool.images, self.pool.class_maps, self.rows, self.patch)
 
     def host(self):
-        """host_windows of this batch; with a photo table, host_photometric of its image (the class map is untouched)."""
+        """host_windows of this batch; with a paste table, host_paste of both; with a photo table, host_photometric of the image
+        after that (the class map is untouched by it): cut, then paste, then photo."""
         img, cls = self._cut()
+        if self.paste is not None:
+            if cls is None:
+                raise ValueError("a paste table needs class maps: this pool holds none")
+            img, cls = host_paste(img, cls, self.pool.images, self.pool.class_maps, self.pool.inst_maps, self.paste, self.pool.bank_classes)
         return (img if self.photo is None else host_photometric(img, self.photo)), cls
 
 
@@ -2045,9 +2301,59 @@ class ScenePool:
         self.cls_ptrs = None if self.cls_dev is None else (C.c_void_p * n)(*[t.data_ptr() for t in self.cls_dev])
         self.heights = (C.c_int32 * n)(*[h for h, _ in self.shapes])
         self.widths = (C.c_int32 * n)(*[w for _, w in self.shapes])
+        # object_bank(): the objects to paste (host, int32 [K][8]), the class count they were made under, the resident id maps
+        self.bank = self.bank_classes = self.inst_dev = self.inst_ptrs = self._inst_host = None
 
     def __len__(self):
         return len(self.images)
+
+    def object_bank(self, num_classes: int, classes, min_area: int = 1, max_area: Optional[int] = None, max_extent: Optional[int] = None,
+                    connectivity: int = 4) -> np.ndarray:
+        """host_object_bank of the pool's class maps, on the device: per scene rua_scene_seed_map, rua_scene_regions and
+        rua_scene_instances at radius 0 with min_seed = min_area (the ground-truth objects), one fetch of the object table, and the
+        marker, labels, areas and work buffers are freed before the next scene.  The int32 id maps STAY RESIDENT - self.inst_dev,
+        self.inst_ptrs, what rua_window_paste reads -: 4 bytes per scene pixel, 144 MB for a 6000 x 6000 tile, next to the 4 bytes
+        per pixel of its image and class map.  self.bank is the host table, int32 [K][8] (BANK_COLUMNS), and is returned;
+        self.bank_classes is num_classes.  max_extent None: the smaller side of the pool's patch (512 without one).  A "cpu" pool
+        holds the host definition's maps.  Calling it again replaces all of it."""
+        if self.class_maps is None:
+            raise ValueError("object_bank: this scene pool holds no class maps")
+        default = MAX_PATCH if self.patch is None else min(min(self.patch), MAX_PATCH)
+        mn, mx, ext = _check_bank_filters(min_area, max_area, max_extent, default)
+        C_, mask, bb, da = check_seed_map(num_classes, classes)
+        _, _, _, _, conn, _ = check_instances(C_, classes, mn, 0, connectivity)
+        self.inst_dev = self.inst_ptrs = self._inst_host = None
+        if self.device.type != "cuda":
+            self._inst_host, self.bank = host_object_bank(self.class_maps, C_, [c for c in range(C_) if (mask >> c) & 1], mn, mx, ext, conn)
+        else:
+            import torch
+            inst_dev, parts = [], []
+            with torch.cuda.device(self.device):
+                st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+                for s, (H, W) in enumerate(self.shapes):
+                    keep, cap = [], min(MAX_INSTANCES, H * W)
+                    inst, table, n = self._device_instances(self.cls_dev[s].data_ptr(), None, None, (H, W), C_, mask, bb, da, mn, 0, conn, cap, st, keep)
+                    N = int(n.cpu().numpy()[0])                         # the fetch waits for the scene's calls
+                    del keep                                             # marker, labels, areas, work: scratch
+                    if N > cap:
+                        raise ValueError(f"object bank: scene {s} holds {N} objects, more than {cap}")
+                    parts.append(_bank_rows(s, table[:N].cpu().numpy(), mx, ext))
+                    inst_dev.append(inst)
+                    del table, n
+            self.inst_dev = inst_dev
+            self.inst_ptrs = (C.c_void_p * len(inst_dev))(*[t.data_ptr() for t in inst_dev])
+            self.bank = np.concatenate(parts)
+        self.bank_classes = C_
+        return self.bank
+
+    @property
+    def inst_maps(self) -> List[np.ndarray]:
+        """The id maps of object_bank() on the host, int32 [H][W] per scene (a device pool fetches them once, on first use)."""
+        if self.bank is None:
+            raise ValueError("no object bank yet: ScenePool.object_bank() builds the id maps")
+        if self._inst_host is None:
+            self._inst_host = [t.cpu().numpy() for t in self.inst_dev]
+        return self._inst_host
 
     def batch(self, rows, patch=None) -> SceneBatch:
         """The batch of these table rows; ValueError (rua_scene_windows' wording) for a row the kernel would refuse."""
@@ -2470,10 +2776,14 @@ class SceneLoader:
     a world of 2 sees exactly the windows a world of 1 sees.  Yields (AffineSceneBatch, None) then.
     photo (a PhotoJitter): batch k of pass e draws the GLOBAL batch's photo table from np.random.default_rng([seed, e, k, 1]) - a
     stream of its own: the draws of jitter= are what they are without it -, every rank takes its own rows, and the batches carry
-    them (SceneBatch.photo).  Passes are counted with photo alone as with jitter."""
+    them (SceneBatch.photo).  Passes are counted with photo alone as with jitter.
+    paste (a CopyPaste; the pool has its object_bank()): batch k of pass e draws the GLOBAL batch's paste table from
+    np.random.default_rng([seed, e, k, 2]) - again a stream of its own -, every rank takes the rows of its windows, renumbered, and
+    the batches carry them (SceneBatch.paste).  Passes are counted with paste alone too."""
 
     def __init__(self, pool: ScenePool, table: np.ndarray, batch_size: int, patch=None, order: Optional[Sequence[int]] = None,
-                 rank: int = 0, world: int = 1, jitter: Optional[Jitter] = None, seed: int = 0, photo: Optional[PhotoJitter] = None):
+                 rank: int = 0, world: int = 1, jitter: Optional[Jitter] = None, seed: int = 0, photo: Optional[PhotoJitter] = None,
+                 paste: Optional[CopyPaste] = None):
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")
         if world < 1 or not (0 <= rank < world):
@@ -2484,6 +2794,9 @@ class SceneLoader:
         self.B, self.rank, self.local_B = int(batch_size), int(rank), int(batch_size) // int(world)
         self.order = np.arange(len(self.table)) if order is None else np.asarray(order, dtype=np.int64)
         self.jitter, self.photo, self.seed, self.passes = jitter, photo, int(seed), 0
+        if paste is not None and pool.bank is None:
+            raise ValueError("SceneLoader(paste=): this pool has no object bank yet (ScenePool.object_bank())")
+        self.paste = paste
 
     def __len__(self) -> int:
         return len(self.order) // self.B
@@ -2492,12 +2805,16 @@ class SceneLoader:
         self.order = np.asarray(order, dtype=np.int64)
 
     def __iter__(self):
-        if self.jitter is None and self.photo is None:
+        if self.jitter is None and self.photo is None and self.paste is None:
             return self._plain(None)
         e, self.passes = self.passes, self.passes + 1
         return self._jittered(e) if self.jitter is not None else self._plain(e)
 
     def _with_photo(self, batch: SceneBatch, e: Optional[int], k: int) -> SceneBatch:
+        """The rank's batch with its rows of the global batch's photo and paste tables."""
+        if self.paste is not None:
+            table = self.paste.draw(np.random.default_rng([self.seed, e, k, 2]), self.pool.bank, self.B, batch.patch, self.pool.bank_classes)
+            batch = batch.with_paste(_paste_take(table, np.arange(self.rank * self.local_B, (self.rank + 1) * self.local_B)))
         if self.photo is None:
             return batch
         table = self.photo.draw(np.random.default_rng([self.seed, e, k, 1]), self.B, self.pool.channels)

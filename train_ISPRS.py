@@ -29,6 +29,16 @@ Deviations, all additive or forced by the reference's hard-coded values (SURVEY.
     targets are built from it - the colour head's HSV target follows the jittered image.  Drawn afresh every epoch from `--seed`
     (scenes.SceneLoader(photo=)), in a random stream of its own: `--random_aug` draws what it draws without it.  The validation
     windows and the split are untouched.  The option is not stored in a checkpoint.
+  * `--paste_aug yes --paste_classes K [K ...] [--paste_per_window LO HI] [--paste_onto SRC:DST[,DST] ...] [--paste_over_void yes]
+    [--paste_min_area A] [--paste_max_area A]` (with `--scene_dataset yes`): copy-paste augmentation (Ghiasi et al., CVPR 2021).
+    The ground-truth objects of the classes K - their connected regions in the class maps, found once on the GPU after the scenes
+    are uploaded (ScenePool.object_bank; the bank's size per class is printed) - are pasted, pixels and labels together, into the
+    cut training windows (rua_window_paste) before the photometric jitter and before the input and the targets are built, so all
+    four heads follow.  Per window LO..HI pastes; per paste the class is drawn uniformly from K (a rare class is seen as often as a
+    common one), then an object of it, one of the eight symmetries and a place inside the window; `--paste_onto 4:0` lets class 4
+    cover class 0 only.  Drawn afresh every epoch from `--seed` in a random stream of its own (scenes.SceneLoader(paste=)).  The
+    objects come from the scenes the training windows are cut from (the split is by windows, which overlap, as in the reference);
+    the validation windows are never pasted into.  The id maps cost 4 bytes per scene pixel of GPU memory.  Not stored in a checkpoint.
   * `--class_weights auto` (with `--scene_dataset yes --loss weighted_cross_entropy`): the weighted-CE class weights are total /
     pixels of the class over the training windows (scenes.class_weights; the reference's five numbers are that rule on its own
     patch set), counted on the GPU from the resident class maps (ScenePool.class_counts).  `--class_weights w0 ... wC-1` gives
@@ -154,6 +164,15 @@ def build_parser():
     p.add_argument("--photo_hue", type=float, default=8.0, metavar="DEG", help="photo_aug: the hue turns by an angle uniform in [-DEG, DEG] (3 channels)")
     p.add_argument("--photo_tone", type=float, default=0.4, metavar="V", help="photo_aug: the tone-curve strength is uniform in [-V, V], V <= 1")
     p.add_argument("--photo_noise", type=float, nargs=2, default=[0.0, 3.0], metavar=("LO", "HI"), help="photo_aug: the noise sigma, in levels, is uniform in [LO, HI]")
+    p.add_argument("--paste_aug", type=str2bool, default=False,
+                   help="scene directory: copy-paste augmentation - ground-truth objects of --paste_classes pasted into the training windows on the GPU")
+    p.add_argument("--paste_classes", type=int, nargs="+", default=None, metavar="K", help="paste_aug: the classes whose objects are pasted; each is drawn equally often")
+    p.add_argument("--paste_per_window", type=int, nargs=2, default=[0, 3], metavar=("LO", "HI"), help="paste_aug: the number of pastes per window is uniform in LO..HI")
+    p.add_argument("--paste_onto", type=str, nargs="+", default=None, metavar="SRC:DST[,DST]",
+                   help="paste_aug: class SRC may cover the classes DST only (default: every class), e.g. 4:0 - cars on impervious surface")
+    p.add_argument("--paste_over_void", type=str2bool, default=False, help="paste_aug: objects may also cover pixels that carry no class")
+    p.add_argument("--paste_min_area", type=int, default=1, metavar="A", help="paste_aug: objects of at least A pixels")
+    p.add_argument("--paste_max_area", type=int, default=None, metavar="A", help="paste_aug: objects of at most A pixels (default: no limit)")
     p.add_argument("--class_weights", type=str, nargs="+", default=None, metavar="W",
                    help="weighted_cross_entropy (class weights) / focal (per-class alpha): `auto` (scene directory: total / pixels of the class over the training windows) or one weight per class")
     p.add_argument("--focal_gamma", type=float, default=2.0, metavar="G", help="--loss focal: the focusing exponent, 0 or 1..8 (0 with --class_weights is weighted cross entropy)")
@@ -285,17 +304,67 @@ def check_photo_flags(args):
         sys.exit(f"--photo_aug: {exc}")
 
 
+def check_paste_flags(args):
+    """--paste_aug and its options checked against the rest of the command line, before anything is loaded: returns the CopyPaste, or
+    None (off); SystemExit with a message otherwise."""
+    if not args.paste_aug:
+        return None
+    if not args.scene_dataset:
+        sys.exit("--paste_aug yes pastes objects of resident scenes: it needs --scene_dataset yes")
+    if not args.paste_classes:
+        sys.exit("--paste_aug yes needs --paste_classes K [K ...]: the classes whose objects are pasted")
+    C = args.num_classes
+    bad = [c for c in args.paste_classes if not 0 <= c < C]
+    if bad:
+        sys.exit(f"--paste_classes {bad[0]} outside 0..{C - 1}")
+    onto = None
+    for item in args.paste_onto or []:
+        try:
+            src, dst = item.split(":")
+            src, dst = int(src), [int(d) for d in dst.split(",")]
+        except ValueError:
+            sys.exit(f"--paste_onto {item!r}: SRC:DST[,DST...] with class indices, as in 4:0,1")
+        if src not in args.paste_classes:
+            sys.exit(f"--paste_onto {item!r}: class {src} is not one of --paste_classes {args.paste_classes}")
+        if any(not 0 <= d < C for d in dst):
+            sys.exit(f"--paste_onto {item!r}: a destination class outside 0..{C - 1}")
+        onto = {**(onto or {}), src: dst}
+    if args.paste_min_area < 1 or (args.paste_max_area is not None and args.paste_max_area < args.paste_min_area):
+        sys.exit(f"--paste_min_area {args.paste_min_area}, --paste_max_area {args.paste_max_area}: 1 <= min <= max")
+    from resunet_a_mltsk_keras_amd.scenes import CopyPaste
+    try:
+        return CopyPaste(args.paste_classes, tuple(args.paste_per_window), onto, args.paste_over_void)
+    except ValueError as exc:
+        sys.exit(f"--paste_aug: {exc}")
+
+
+def build_object_bank(args, pool, table, x_tr, say):
+    """--paste_aug yes: the pool's object bank (ScenePool.object_bank: ground-truth objects of --paste_classes, found on the GPU, the
+    id maps resident), built once and restricted to the scenes that training windows are cut from; prints its size per class."""
+    from resunet_a_mltsk_keras_amd.scenes import patch_index
+    bank = pool.object_bank(args.num_classes, args.paste_classes, min_area=args.paste_min_area, max_area=args.paste_max_area)
+    train_scenes = np.unique(table[[patch_index(n) for n in x_tr], 0])
+    pool.bank = bank = np.ascontiguousarray(bank[np.isin(bank[:, 0], train_scenes)])
+    per_class = ", ".join(f"class {c}: {int((bank[:, 2] == c).sum())}" for c in sorted(set(args.paste_classes)))
+    say(f"Object bank: {len(bank)} objects of {len(train_scenes)} training scenes ({per_class}); area >= {args.paste_min_area}"
+        + (f", <= {args.paste_max_area}" if args.paste_max_area is not None else "") + f", box <= {min(pool.patch)} pixels")
+    if not len(bank):
+        sys.exit(f"--paste_aug yes: the training scenes hold no object of --paste_classes {args.paste_classes} within the area and size limits")
+    return bank
+
+
 def scene_loaders(args, pool, table, x_tr, x_va, batch_size, rank=0, world=1):
     """(training SceneLoader, validation SceneLoader) of a scene run: x_tr / x_va are patch_{k}.npy names of table rows k.
-    --random_aug and --photo_aug reach the training loader alone: it draws a rotation, zoom and shift and a photo row per window and
-    pass (the same on every rank); the validation loader is the same with and without them."""
+    --random_aug, --photo_aug and --paste_aug reach the training loader alone: it draws a rotation, zoom and shift, a photo row per
+    window and the paste rows of a batch per pass (the same on every rank); the validation loader is the same with and without them."""
     from resunet_a_mltsk_keras_amd.scenes import Jitter, SceneLoader, patch_index
     jitter = None
     if getattr(args, "random_aug", False):
         jitter = Jitter(args.aug_rotate, tuple(args.aug_zoom), args.stride / 2 if args.aug_shift is None else args.aug_shift)
     photo = check_photo_flags(args) if getattr(args, "photo_aug", False) else None
+    paste = check_paste_flags(args) if getattr(args, "paste_aug", False) else None
     ld_tr = SceneLoader(pool, table[[patch_index(n) for n in x_tr]], batch_size, args.patch_size, rank=rank, world=world,
-                        jitter=jitter, seed=args.seed, photo=photo)
+                        jitter=jitter, seed=args.seed, photo=photo, paste=paste)
     ld_va = SceneLoader(pool, table[[patch_index(n) for n in x_va]], batch_size, args.patch_size, rank=rank, world=world)
     return ld_tr, ld_va
 
@@ -591,6 +660,7 @@ def main(argv=None):
     if args.random_aug and not args.scene_dataset:
         sys.exit("--random_aug yes resamples windows of resident scenes: it needs --scene_dataset yes")
     check_photo_flags(args)
+    check_paste_flags(args)
     class_weights = check_class_flags(args)
     focal_alpha = check_loss_flags(args)
     ohem_kw = check_ohem_flags(args)
@@ -646,6 +716,8 @@ def main(argv=None):
                 class_weights = [float(w) for w in weights_of_counts(counts)]
             except ValueError as exc:
                 sys.exit(f"--class_weights auto: {exc}")
+    if args.paste_aug:
+        build_object_bank(args, scenes[0], scenes[1], x_tr, say)
     rows = cols = args.patch_size
     channels = args.channels or (int(images[0].shape[-1]) if scenes is not None else int(np.load(xs[0]).shape[-1]))
     opt_kw = optimizer_options(args)
