@@ -432,7 +432,9 @@ int rua_tanimoto_finalize_rep(double* sums, int replicas, int B, int64_t HW, int
                               float* per_sample, void* stream);
 /* Tanimoto_loss(label, pred) itself (multitasking_utils.py:38-68), shape (B,): take the sums with p := label, y := pred
  * (rua_tanimoto_sums(label, pred, ...)), then per_sample[n] = (sum_c w_c*Spl + 1e-5) / (sum_c w_c*(Ssq - Spl) + 1e-5) with
- * w_c = 1 / (mean_n volume of the FIRST argument)^2, inf -> largest finite weight (:46-53); mean_out[0] = mean_n. */
+ * w_c = 1 / (mean_n volume of the FIRST argument)^2, inf -> largest finite weight (:46-53); mean_out[0] = mean_n.
+ * "inf" is the reference's float32 outcome - the float32 reciprocal of the float32 square overflows, for every V^2 <= 2^-128 and not only at V == 0 -
+ * here and in both terms of rua_tanimoto_finalize; a finite weight keeps its float64 value. */
 int rua_tanimoto_ratio(const double* sums, int B, int C, double* mean_out, float* per_sample, void* stream);
 /* loss_out[0] += sum over pixels of the per-pixel loss of kind 1..4 (caller divides);
  * per_pixel[M] (optional): the (B,H,W) map the reference's loss function returns (utils.py:486) */

@@ -178,11 +178,13 @@ __device__ __forceinline__ void tanimoto_finalize_body(const double* sums, int B
     double a = 0, b = 0;
     for (int n = 0; n < B; ++n) { a += sums[((size_t)n * C + t) * 6 + 0]; b += sums[((size_t)n * C + t) * 6 + 1]; }
     a /= B; b /= B;
-    // the reference squares and takes the reciprocal in float32: overflow to inf happens only at V == 0
+    // the reference squares and takes the reciprocal in float32 (multitasking_utils.py:46-53): the reciprocal overflows to inf for every
+    // V^2 <= 2^-128 (V below ~5e-20), not only at V == 0 - a class whose softmax mass has died gets the largest finite weight, not 1e40 times it.
+    // Infinity is decided by that float32 reciprocal of the float32 square; where it is finite the weight keeps its float64 value.
     v1[t] = a;
     const float a2 = (float)a * (float)a, b2 = (float)b * (float)b;
-    w1[t] = a2 == 0.f ? INFINITY : 1.0 / (a * a);
-    w2[t] = b2 == 0.f ? INFINITY : 1.0 / (b * b);
+    w1[t] = isfinite(1.f / a2) ? 1.0 / (a * a) : INFINITY;
+    w2[t] = isfinite(1.f / b2) ? 1.0 / (b * b) : INFINITY;
   }
   __syncthreads();
   if (t == 0) {
