@@ -1,7 +1,7 @@
 """Evaluation of a trained model on whole scenes, on the GPU: what test_ISPRS.py does for the reference's test tile (patches,
 predict, arg-max, metrics, mosaic), for a scene directory (resunet_a_mltsk_keras_amd.scenes: scenes/<name>.npy,
 labels/scenes/<name>.npy) as `train_ISPRS.py --scene_dataset yes` trains from.  test_ISPRS.py's flags, plus --stride, --views, --scales, --blend, --erode_boundary,
---boundary_f1, --sieve, --pr_curve, --instances and --head_maps.
+--boundary_f1, --sieve, --pr_curve, --instances, --polygons and --head_maps.
 
 Every scene stays on the GPU, is covered by windows --stride apart (default: the patch; the last window flush with the border, so
 nothing is left unpredicted), every pixel is predicted from the window it is most central in, and Model.predict_scene brings back
@@ -73,6 +73,16 @@ object precision, recall and F1 at IoU 0.5 and the mean F1 over 0.5:0.05:0.95 ar
 `instances_<name>.npy` (int32 n x 8: root, class, area, seed_area, i_min, j_min, i_max, j_max), `instance_scores.npy` (float64
 C x 6: n_pred, n_true, precision, recall, F1 at 0.5, mean F1) and, with --inst_map yes, `inst_map_<name>.npy` (int32 H x W, -1
 off the objects) are written; the returned dict gains `instance_scores` and `instance_counts`.
+
+--polygons yes [--poly_simplify T] [--poly_min_area A] [--poly_truth yes], with --instances, also writes the objects as a vector
+layer: the predicted instance map is traced on the GPU into closed rings of pixel corners, outer rings and holes
+(scenes.host_outlines; only rings and vertices leave the GPU), every hole is given to the ring round it (scenes.outline_polygons),
+polygons of fewer than A pixels are dropped, every ring is simplified with Douglas-Peucker at a tolerance of T pixels (default 0:
+the exact pixel outline; neighbouring polygons are simplified independently and may then overlap by up to T), and
+`polygons_<name>.geojson` is written: a FeatureCollection of Polygon features with the properties id, class and area, in pixel
+coordinates (x, -y), exteriors counter-clockwise (RFC 7946).  --poly_truth yes writes the true objects alike, as
+`polygons_true_<name>.geojson`.  The polygon and hole counts per class are printed; the returned dict gains `polygon_counts`
+(int64 C x 2).
 
 --head_maps HEAD [HEAD ...] also writes whole-scene maps of the named heads (`seg`, `bound`, `dist`, `color`, `color_rgb`; what
 test_ISPRS.py:285-414 displays per patch): `pred_<head>_<name>.npy`, uint8 H x W x Ch - the head's output averaged over the views,
@@ -152,6 +162,10 @@ def build_parser():
     parser.add_argument("--inst_radius", type=int, default=4, metavar="R", help="seeds are grown back over their class within R pixels (0..16)")
     parser.add_argument("--inst_connectivity", type=int, default=4, metavar="4|8", help="what connects the pixels of a seed: 4- or 8-neighbours")
     parser.add_argument("--inst_map", type=_yes, default=False, help="also write the instance map of every scene")
+    parser.add_argument("--polygons", type=_yes, default=False, help="with --instances: also write the objects of every scene as GeoJSON polygons")
+    parser.add_argument("--poly_simplify", type=float, default=0.0, metavar="T", help="Douglas-Peucker tolerance in pixels for every ring (0: the exact outline)")
+    parser.add_argument("--poly_min_area", type=int, default=0, metavar="A", help="polygons of fewer than A pixels are left out")
+    parser.add_argument("--poly_truth", type=_yes, default=False, help="also write the polygons of the true objects")
     parser.add_argument("--head_maps", nargs="+", default=[], metavar="HEAD",
                         help="also write uint8 whole-scene maps of these heads: seg, bound, dist, color, color_rgb (default: none)")
     return parser
@@ -207,7 +221,11 @@ def parse_instances(args):
     """--instances and its companions as predict_scene's `instances` dict (None: absent); a bound of 1.0 switches that test off."""
     from resunet_a_mltsk_keras_amd import scenes
     if args.instances is None:
+        if args.polygons:
+            raise SystemExit("--polygons needs --instances: the polygons are the outlines of its objects")
         return None
+    if args.polygons and (not args.poly_simplify >= 0 or args.poly_min_area < 0):
+        raise SystemExit(f"--polygons: --poly_simplify {args.poly_simplify:g} and --poly_min_area {args.poly_min_area} must not be negative")
     inst = dict(classes=args.instances, bound_below=256 if args.inst_bound == 1.0 else float(args.inst_bound), dist_at_least=float(args.inst_dist),
                 min_seed=args.inst_min_seed, radius=args.inst_radius, connectivity=args.inst_connectivity, map=bool(args.inst_map))
     try:
@@ -216,7 +234,20 @@ def parse_instances(args):
         raise SystemExit(f"--instances: {exc}") from None
     if (p["bound_below"] < 256 or p["dist_at_least"] > 0) and (args.scales is not None or args.blend is not None):
         raise SystemExit("--instances with --inst_bound below 1 or --inst_dist above 0 excludes --scales and --blend: no maps of the heads are built there")
+    if args.polygons:
+        inst["outlines"] = True
     return inst
+
+
+def write_polygons(path, outlines, table, args, counts):
+    """One GeoJSON layer from a (rings, verts) pair and its instance table; counts int64 [C][2] gains the polygons and holes per class."""
+    from resunet_a_mltsk_keras_amd import scenes
+    polys = scenes.outline_polygons(outlines[0], outlines[1], table, args.poly_min_area)
+    for p in polys:
+        p["exterior"] = scenes.simplify_ring(p["exterior"], args.poly_simplify)
+        p["holes"] = [scenes.simplify_ring(h, args.poly_simplify) for h in p["holes"]]
+        counts[p["class"]] += (1, len(p["holes"]))
+    scenes.write_geojson(path, polys)
 
 
 def print_curve(title, scores):
@@ -299,6 +330,7 @@ def main(argv=None):
     all_head_maps, mae_sum, mae_n = [], 0.0, 0
     total_hist = np.zeros((2, 2, 256), np.int64)
     object_scores = []
+    polygon_counts, polygon_counts_true = (np.zeros((args.num_classes, 2), np.int64) for _ in range(2))
     print('=' * 40)
     print('[TEST]')
     print(f'views: {" ".join(str(c) for c in views)} ({len(views)} per window)')
@@ -324,6 +356,11 @@ def main(argv=None):
             if "inst" in objects:
                 np.save(os.path.join(args.output_path, f'inst_map_{name}.npy'), objects["inst"])
             object_scores.append(objects["scores"])
+            if args.polygons:
+                write_polygons(os.path.join(args.output_path, f'polygons_{name}.geojson'), objects["outlines"], objects["table"], args, polygon_counts)
+                if args.poly_truth and objects["outlines_true"] is not None:
+                    write_polygons(os.path.join(args.output_path, f'polygons_true_{name}.geojson'), objects["outlines_true"], objects["gt_table"], args,
+                                   polygon_counts_true)
             print(f'scene {name}: {objects["n"]} predicted objects, {objects["gt_n"]} true objects, {objects["ungrown"]} pixels of the classes outside every object')
         if sweep is not None:
             swept = more.pop()
@@ -426,6 +463,14 @@ def main(argv=None):
             print(f'  {c:5d} {int(table[c, 0]):10d} {int(table[c, 1]):8d} {table[c, 2]:10.4f} {table[c, 3]:8.4f} {table[c, 4]:8.4f} {table[c, 5]:8.4f}')
         np.save(os.path.join(args.output_path, 'instance_scores.npy'), table)
         res.update(instance_scores=sc, instance_counts=np.stack([sc["n_pred"], sc["n_true"]], 1))
+        if args.polygons:
+            print()
+            print(f'Polygons (simplified at {args.poly_simplify:g} px, at least {args.poly_min_area} px)' + (', predicted / true' if args.poly_truth else ''))
+            print('  class   polygons      holes')
+            for c in sorted(set(args.instances)):
+                true = f'   / {polygon_counts_true[c, 0]:8d} {polygon_counts_true[c, 1]:10d}' if args.poly_truth else ''
+                print(f'  {c:5d} {polygon_counts[c, 0]:10d} {polygon_counts[c, 1]:10d}{true}')
+            res["polygon_counts"] = polygon_counts
     if heads:
         res["head_maps"] = all_head_maps
         res["color_mae"] = mae_sum / mae_n if mae_n else None

@@ -1152,6 +1152,45 @@ int64_t rua_scene_instance_match_work_bytes(int64_t Np, int64_t Ng);
 int rua_scene_instance_match(const int32_t* inst_p, const int32_t* area_p /* table_p, column 2 */, int64_t Np, const int32_t* inst_g,
                              int64_t Ng, int H, int W, void* work, int64_t work_bytes, int32_t* match, void* stream);
 
+/* ---- outlines of whole-scene instance maps: one closed ring of grid corners per object piece and per hole (scenes.py, host_outlines /
+ * outline_polygons / write_geojson) ------------------------------------------------------------------------------------------------
+ * One map per call.  Every pointer is DEVICE memory.  inst is an int32 [H][W] id map (rua_scene_instances' inst, or any other): an id
+ * >= 0 is an object, a negative id is none.  A vertex is a grid corner (y, x), 0 <= y <= H, 0 <= x <= W; pixel (i, j) is the square
+ * between (i, j) and (i+1, j+1).  Pixel p = (i, j) with id k >= 0 owns a directed EDGE on side s (0 top, 1 right, 2 bottom, 3 left) if
+ * the pixel across that side lies outside the map or has another id; the pixel is on the right of the direction of travel:
+ *   s = 0: (i, j) -> (i, j+1)    s = 1: (i, j+1) -> (i+1, j+1)    s = 2: (i+1, j+1) -> (i+1, j)    s = 3: (i+1, j) -> (i, j)
+ * Its key is 4 (i W + j) + s.  With F the pixel one step along the heading from p and L the pixel across side s from F, the
+ * SUCCESSOR of (p, s) is (L, s+3 mod 4) if F and L have id k; else (F, s) if F has; else (L, s+3 mod 4) if connectivity is 8 and L
+ * has; else (p, s+1 mod 4).  The cycles of the successor are the RINGS.  A CORNER edge is one whose successor has another side; its
+ * vertex is its end point.  A ring's leader is its edge of smallest key; its vertices are those of its corner edges in walking order
+ * from the leader; rings are ordered by leader key.
+ * rua_scene_outline_count writes base int32 [H][W], base[p] = the number of edges of all pixels before p in row-major order, and
+ * n int64 [2] = (E, V): the edges and the corner edges of the map.  Three launches.
+ * rua_scene_outline_rings takes the same inst and connectivity, that base, and E and V as the host read them from n.  It writes
+ *   rings int32 [V / 4][6]: rows 0..R-1 = (id, leader key, vertex offset, vertex count, area, length); rows from R on are not touched
+ *   verts int32 [V][2]:     the rings' vertices (y, x), ring after ring
+ *   nr    int64 [1]:        R
+ * length is the ring's number of edges; area its signed enclosed area in pixels - the sum of (i + 1) over its side-2 edges minus the
+ * sum of i over its side-0 edges -, positive for an outer ring (clockwise with rows pointing down), negative for a hole.  A ring has an
+ * even number of at least 4 vertices, none of them collinear with its neighbours.  With E == 0 only nr = 0 is written (one launch;
+ * work, rings and verts may be null); otherwise 2 ceil(log2 E) + 10 launches: the edges are compacted in key order, the leader of
+ * every cycle is found by pointer jumping on (min, hop) records, the cycles are cut in front of their leaders and ranked by the same
+ * jumping on (sum, hop) records, the leaders are numbered with a chunk scan, counts, areas and lengths are added with integer
+ * atomics, and the corner edges scatter their end points.  scenes.host_outlines gives the same bytes whatever the launch or arrival
+ * order.  E and V that do not belong to (inst, base) give meaningless rings, but nothing outside the buffers is read or written.
+ * work: 16-byte aligned, work_bytes >= rua_scene_outline_work_bytes(H, W, E) - E = 0 for the count: 8 bytes per chunk of 1024 pixels;
+ * for the rings 24 bytes per edge (key, successor / leader, two 8-byte jumping records) and 5 per 1024 edges; -1 for sizes the calls
+ * would refuse.
+ * Everything is checked on the host before anything is launched (a violation: RUA_ERR_ARG, the message names the offender, nothing is
+ * written): the required pointers, 1 <= H, W and H * W <= 2^29 (keys and areas fit an int32), connectivity 4 or 8, 0 <= E <= 4 H W,
+ * V even and 4 <= V <= E (V == 0 with E == 0), 4-byte alignment of inst, base and rings, 8-byte alignment of verts, n and nr, the work
+ * buffer, no output sharing a byte with an input or with another output of the call. */
+int64_t rua_scene_outline_work_bytes(int H, int W, int64_t E);
+int rua_scene_outline_count(const int32_t* inst, int H, int W, int connectivity, int32_t* base, void* work, int64_t work_bytes,
+                            int64_t* n /* device int64[2]: E, V */, void* stream);
+int rua_scene_outline_rings(const int32_t* inst, const int32_t* base, int H, int W, int connectivity, int64_t E, int64_t V, void* work,
+                            int64_t work_bytes, int32_t* rings, int32_t* verts, int64_t* nr /* device int64[1]: R */, void* stream);
+
 /* ---- data parallel (train_ISPRS.py:347,432: the implicit NCCL all-reduce of tf.distribute.MirroredStrategy).  The library exports
  * no collective: gradients live in ONE flat fp32 buffer in parameter order, so the all-reduce is ncclAllReduce (RCCL) on contiguous
  * slices of it, issued by the host as the backward completes them (the Python engine: torch.distributed, dist.py; a C embedder:

@@ -63,23 +63,6 @@ __global__ __launch_bounds__(256) void inst_count(InstArgs a) {
   if (threadIdx.x == 0) a.chunk[blockIdx.x] = cnt;
 }
 
-// exclusive prefix of v over the 256 lanes of the block (sh: 256 ints), and the total; every lane calls it
-__device__ __forceinline__ int block_scan_256(int* sh, int v, int& total) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {            // eight doubling steps
-    const int u = t >= d ? sh[t - d] : 0;
-    __syncthreads();
-    sh[t] += u;
-    __syncthreads();
-  }
-  total = sh[255];
-  const int incl = sh[t];
-  __syncthreads();
-  return incl - v;
-}
-
 __global__ __launch_bounds__(256) void inst_scan(InstArgs a) {
   __shared__ int sh[256];
   int carry = 0;

@@ -66,6 +66,25 @@ __device__ __forceinline__ uint32_t row_breaks(bool brk) {
   return (uint32_t)(m >> (threadIdx.x & 32));
 }
 
+// ---- a block scan ------------------------------------------------------------------------------------------------------------------
+// exclusive prefix of v over the 256 lanes of the block (sh: 256 cells), and the total; every lane calls it
+template <typename T>
+__device__ __forceinline__ T block_scan_256(T* sh, T v, T& total) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {            // eight doubling steps
+    const T u = t >= d ? sh[t - d] : T(0);
+    __syncthreads();
+    sh[t] += u;
+    __syncthreads();
+  }
+  total = sh[255];
+  const T incl = sh[t];
+  __syncthreads();
+  return incl - v;
+}
+
 // ---- argument checks --------------------------------------------------------------------------------------------------------------
 #define RG_TRY(call) do { const int rc_ = (call); if (rc_ != RUA_OK) return rc_; } while (0)
 

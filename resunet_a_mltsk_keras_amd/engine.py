@@ -2807,8 +2807,8 @@ class Engine:
         maps, and with scales or blend (the probabilities then live in an int32 accumulator: no maps of the heads are built).
         instances: None is every path and return value above, call for call.  Otherwise the objects of the finished map: a class
         index, a list of classes, or a dict {classes, bound_below=128, dist_at_least=0, min_seed=1, radius=4, connectivity=4,
-        iou_percent=(50, 55 .. 95), max_instances=2^20, map=False} (scenes.instance_params; the two thresholds are byte levels, or
-        floats in 0..1 that are quantised as the maps are).  The "bound" map is stitched when bound_below < 256 and the "dist" map
+        iou_percent=(50, 55 .. 95), max_instances=2^20, map=False, outlines=False} (scenes.instance_params; the two thresholds are
+        byte levels, or floats in 0..1 that are quantised as the maps are).  The "bound" map is stitched when bound_below < 256 and the "dist" map
         when dist_at_least > 0, as heads= stitches them, whether or not the caller asked for them (they are returned only if asked
         for).  After the sieve - the instances are those of the SIEVED map when sieve= is given - and before any fetch, on the
         compute stream: rua_scene_seed_map keeps the pixels of the chosen classes that lie off the predicted boundaries and deep
@@ -2819,7 +2819,11 @@ class Engine:
         the object that holds more than half of it (scenes.host_instance_match).  A report {"n", "ungrown", "table": int32 [n][8]
         (scenes.TABLE_COLUMNS), "inst": int32 [H][W] (only with map=True), "gt_n", "gt_table", "match": int32 [n][2], "scores":
         scenes.instance_scores at iou_percent} is added after the sweep report and in front of the head maps, fetched once at the
-        end; the last four entries are None without class maps.  ValueError, before any GPU work, for a malformed value, a head
+        end; the last four entries are None without class maps.  With outlines=True the report gains "outlines" and "outlines_true",
+        each a (rings int32 [R][6], verts int32 [V][2]) pair (scenes.host_outlines; outline_polygons and write_geojson turn them into
+        a vector layer): rua_scene_outline_count and rua_scene_outline_rings trace the predicted instance map, and the true objects'
+        map on a pool with class maps (None without), where they lie, after everything else was issued - only rings and vertices
+        leave the GPU.  Without the key the calls are what they were.  ValueError, before any GPU work, for a malformed value, a head
         threshold on a single-task model (give bound_below=256 there: with both head tests off only the class map is read, and
         it works everywhere) and a head threshold together with scales or blend (no maps of the heads are built there);
         ValueError after the fetch if the scene holds more than max_instances seeds or objects."""
@@ -3019,6 +3023,10 @@ class Engine:
                     raise ValueError(f"rua_scene_instances: the class map holds {Ng} objects, max_instances is {ip['max_instances']}")
                 report.update(gt_n=Ng, gt_table=table_g[:Ng].cpu().numpy(), match=imatch[:N].cpu().numpy())
                 report["scores"] = instance_scores(report["table"], report["gt_table"], report["match"], Cn, ip["iou_percent"])
+            if ip.get("outlines"):
+                # the instance maps are traced where they lie; each costs one fetch of 16 bytes between its two calls, so they come last
+                report["outlines"] = pool._device_outlines(inst_p, (SH, SW), ip["connectivity"], st)
+                report["outlines_true"] = pool._device_outlines(inst_g, (SH, SW), ip["connectivity"], st) if counted else None
             more = (report,) + more
         if sweep is not None:
             more = ({"hist": shist.cpu().numpy(), "levels": levels, "opened": opened.cpu().numpy() if want_opened else None},) + more

@@ -102,6 +102,12 @@ reads recall, precision, F1, alarm area and the average precision at every level
 rua_scene_sweep_hist (csrc/sweep.hip) are their kernels on resident maps, ScenePool.opened_maps() / sweep_hist() and
 Engine.predict_scene(sweep=) their users.
 
+Outlines: host_outlines() is the definition of the rings of an int32 id map - the directed pixel edges between an object and
+anything else, each with one successor, their cycles, and every cycle's corners in walking order from its smallest edge -, in
+integers; rua_scene_outline_count and rua_scene_outline_rings (csrc/outlines.hip) are its kernels on resident maps (list ranking by
+pointer jumping), ScenePool.outlines() and Engine.predict_scene(instances={..., "outlines": True}) their users; outline_polygons()
+gives the holes to their rings, simplify_ring() is an exact-integer Douglas-Peucker and write_geojson() writes the vector layer.
+
 `python -m resunet_a_mltsk_keras_amd.scenes --image Image_Train.npy --reference Reference_Train.npy --dst DIR` writes a scene
 directory from the reference's two inputs (C x H x W arrays, the reference colour-coded); `--materialize DST` also writes the
 compact patch layout (compact.py) of its window table, for users who want files.
@@ -1896,7 +1902,7 @@ def _byte_threshold(fn: str, key: str, v, lo: int, hi: int) -> int:
     return int(v)
 
 
-INSTANCE_KEYS = ("classes", "bound_below", "dist_at_least", "min_seed", "radius", "connectivity", "iou_percent", "max_instances", "map")
+INSTANCE_KEYS = ("classes", "bound_below", "dist_at_least", "min_seed", "radius", "connectivity", "iou_percent", "max_instances", "map", "outlines")
 
 
 def instance_params(value, C) -> dict:
@@ -1904,7 +1910,8 @@ def instance_params(value, C) -> dict:
     takes the defaults (bound_below 128, dist_at_least 0, min_seed 1, radius 4, connectivity 4, iou_percent 50, 55 .. 95,
     max_instances 2^20, map False); a dict may hold any of the keys, `classes` is required.  bound_below and dist_at_least may be
     floats in 0..1: they are quantised with the rounding the maps use, rint(255 v) (bound_below at least 1).  "mask" is added:
-    bit c set for every chosen class.  ValueError, in the C entries' words, for anything else."""
+    bit c set for every chosen class.  "outlines" (trace the instance maps: host_outlines) is in the result only if it was given.
+    ValueError, in the C entries' words, for anything else."""
     C_ = _check_num_classes(_INST, C)
     if _is_int(value) or isinstance(value, (list, tuple, np.ndarray)):
         value = {"classes": value}
@@ -1927,11 +1934,248 @@ def instance_params(value, C) -> dict:
     iou = (iou,) if np.ndim(iou) == 0 else tuple(iou)
     empty = np.zeros((0, 8), np.int32)
     instance_scores(empty, empty, np.zeros((0, 2), np.int32), C_, iou)             # its checks
-    return {"classes": tuple(c for c in range(C_) if (mask >> c) & 1), "mask": mask, "bound_below": bb, "dist_at_least": da, "min_seed": ms,
-            "radius": r, "connectivity": conn, "iou_percent": tuple(int(t) for t in iou), "max_instances": cap, "map": bool(value.get("map", False))}
+    out = {"classes": tuple(c for c in range(C_) if (mask >> c) & 1), "mask": mask, "bound_below": bb, "dist_at_least": da, "min_seed": ms,
+           "radius": r, "connectivity": conn, "iou_percent": tuple(int(t) for t in iou), "max_instances": cap, "map": bool(value.get("map", False))}
+    if "outlines" in value:
+        out["outlines"] = bool(value["outlines"])
+    return out
 
 
-# ---- copy-paste augmentation: ground-truth objects dropped into the staged windows, mask and label together ----------------------
+# ---- outlines: the rings of an instance map, their polygons with holes, and a GeoJSON layer --------------------------------------
+_OL_COUNT, _OL_RINGS = "rua_scene_outline_count", "rua_scene_outline_rings"
+MAX_OUTLINE_PIXELS = 1 << 29                     # keys 4 (H W - 1) + 3 and areas fit an int32
+RING_COLUMNS = ("id", "leader_key", "vertex_offset", "vertex_count", "area", "length")
+_OL_ACROSS = ((-1, 0), (0, 1), (1, 0), (0, -1))  # the pixel across side s (top, right, bottom, left); the heading of side s is _OL_ACROSS[s + 1]
+_OL_END = ((0, 1), (1, 1), (1, 0), (0, 0))       # the end point of side s, from the pixel's corner (i, j)
+
+
+def check_outlines(shape, connectivity=4, fn: str = _OL_COUNT) -> Tuple[int, int, int]:
+    """(H, W, connectivity) of the outline entries; ValueError in their own words."""
+    if len(shape) != 2 or not all(_is_int(v) for v in shape) or min(shape) < 1 or int(shape[0]) * int(shape[1]) > MAX_OUTLINE_PIXELS:
+        raise ValueError(f"{fn}: size {' x '.join(str(v) for v in shape)} (1 <= H, W and H * W <= 2^29: keys and areas are int32)")
+    return int(shape[0]), int(shape[1]), _check_connectivity(fn, connectivity)
+
+
+def _outline_edges(inst: np.ndarray, conn: int):
+    """(exists bool [4 H W], successor key int64 [4 H W]) by edge key, straight from the edge and successor rules."""
+    H, W = inst.shape
+    P = np.full((H + 2, W + 2), -1, np.int64)
+    P[1:-1, 1:-1] = np.where(inst < 0, -1, inst)
+    at = lambda di, dj: P[1 + di:1 + di + H, 1 + dj:1 + dj + W]
+    k, p = at(0, 0), np.arange(H * W, dtype=np.int64).reshape(H, W)
+    exists, succ = np.zeros((H, W, 4), bool), np.zeros((H, W, 4), np.int64)
+    for s in range(4):
+        (ni, nj), (fi, fj) = _OL_ACROSS[s], _OL_ACROSS[(s + 1) % 4]
+        li, lj = fi + ni, fj + nj
+        exists[..., s] = (k >= 0) & (at(ni, nj) != k)
+        f, l = at(fi, fj) == k, at(li, lj) == k
+        left = l & (f | (conn == 8))                                                     # rules 1 and 3
+        succ[..., s] = np.where(left, 4 * (p + li * W + lj) + (s + 3) % 4, np.where(f, 4 * (p + fi * W + fj) + s, 4 * p + (s + 1) % 4))
+    return exists.reshape(-1), succ.reshape(-1)
+
+
+def host_outlines(inst: np.ndarray, connectivity: int = 4):
+    """The numpy definition of what rua_scene_outline_count and rua_scene_outline_rings leave: (rings int32 [R][6], verts int32 [V][2]).
+    An id >= 0 is an object, a negative id none.  A vertex is a grid corner (y, x), 0 <= y <= H, 0 <= x <= W; pixel (i, j) is the
+    square between (i, j) and (i+1, j+1).  Pixel p with id k owns a directed edge on side s (0 top, 1 right, 2 bottom, 3 left) if the
+    pixel across that side lies outside the map or has another id; the pixel is on the right of the direction of travel, rows
+    pointing down: top runs east (i, j) -> (i, j+1), right south, bottom west, left north.  The edge's key is 4 (i W + j) + s.  With F
+    the pixel one step along the heading and L the pixel across side s from F, the successor of (p, s) is (L, s+3 mod 4) if F and L
+    have id k (a left turn), else (F, s) if F has (straight on), else (L, s+3 mod 4) if connectivity is 8 and L has (across the
+    diagonal), else (p, s+1 mod 4) (a right turn).  The cycles are the rings: one outer ring per connected piece of an id, one per
+    hole.  A corner edge is one whose successor has another side; its vertex is its end point.  A ring's leader is its edge of smallest
+    key; its vertices are those of its corner edges in walking order from the leader (no collinear points: an even number, at least
+    4); rings are ordered by leader key and verts is their concatenation.  A ring's row is RING_COLUMNS: id, leader key, vertex
+    offset, vertex count, area, length - length the number of unit edges, area the signed enclosed area in pixels (the sum of i + 1
+    over the side-2 edges minus the sum of i over the side-0 edges), positive for an outer ring, which runs clockwise on screen,
+    negative for a hole."""
+    a = _check_inst_map(_OL_COUNT, inst, "inst")
+    H, W, conn = check_outlines(a.shape, connectivity)
+    exists, succ = _outline_edges(a, conn)
+    nxt, flat, seen = succ.tolist(), a.ravel(), bytearray(4 * H * W)
+    rings, verts = [], []
+    for lead in np.flatnonzero(exists).tolist():                                         # ascending keys: a ring is met first at its leader
+        if seen[lead]:
+            continue
+        e, area, length, first = lead, 0, 0, len(verts)
+        while True:
+            seen[e] = 1
+            (i, j), s = divmod(e >> 2, W), e & 3
+            length += 1
+            area += i + 1 if s == 2 else -i if s == 0 else 0
+            if nxt[e] & 3 != s:
+                verts.append((i + _OL_END[s][0], j + _OL_END[s][1]))
+            e = nxt[e]
+            if e == lead:
+                break
+        rings.append((int(flat[lead >> 2]), lead, first, len(verts) - first, area, length))
+    return np.array(rings, np.int32).reshape(-1, 6), np.array(verts, np.int32).reshape(-1, 2)
+
+
+def host_outlines_jumping(inst: np.ndarray, connectivity: int = 4):
+    """host_outlines by the stages of csrc/outlines.hip, in numpy arrays over the compacted edges: leaders by pointer jumping on
+    (min, hop), ranks by the same jumping on (sum, hop) after every cycle was cut in front of its leader (the terminal entry E points
+    at itself with weight 0), ceil(log2 E) rounds each, ring numbers and offsets by prefix sums.  The same arrays, without a walk."""
+    a = _check_inst_map(_OL_COUNT, inst, "inst")
+    H, W, conn = check_outlines(a.shape, connectivity)
+    exists, succ = _outline_edges(a, conn)
+    keys = np.flatnonzero(exists)
+    E = len(keys)
+    if E == 0:
+        return np.zeros((0, 6), np.int32), np.zeros((0, 2), np.int32)
+    nxt = (np.cumsum(exists) - 1)[succ[keys]]                                            # compaction keeps key order
+    side, row = keys & 3, (keys >> 2) // W
+    corner = ((succ[keys] & 3) != side).astype(np.int64)
+    rounds = int(E - 1).bit_length()                                                     # ceil(log2 E)
+    lead, hop = np.arange(E), nxt
+    for _ in range(rounds):
+        lead, hop = np.minimum(lead, lead[hop]), hop[hop]
+    tail, hop = np.append(corner, 0), np.append(np.where(nxt == lead, E, nxt), E)
+    for _ in range(rounds):
+        tail, hop = tail + tail[hop], hop[hop]
+    is_lead = lead == np.arange(E)
+    ring = (np.cumsum(is_lead) - 1)[lead]
+    R = int(is_lead.sum())
+    count = np.bincount(ring, corner, R).astype(np.int64)
+    area = np.bincount(ring, np.where(side == 2, row + 1, np.where(side == 0, -row, 0)), R).astype(np.int64)
+    offset = np.cumsum(count) - count
+    rings = np.stack([a.ravel()[keys[is_lead] >> 2], keys[is_lead], offset, count, area, np.bincount(ring, minlength=R)], 1).astype(np.int32)
+    c = corner == 1
+    verts = np.zeros((int(count.sum()), 2), np.int32)
+    end = np.array(_OL_END)[side[c]]
+    verts[offset[ring[c]] + count[ring[c]] - tail[:E][c]] = np.stack([row[c] + end[:, 0], (keys[c] >> 2) % W + end[:, 1]], 1)
+    return rings, verts
+
+
+def _check_rings(fn: str, rings, verts):
+    r, v = np.asarray(rings), np.asarray(verts)
+    if r.ndim != 2 or r.shape[1] != 6 or v.ndim != 2 or v.shape[1] != 2 or r.dtype.kind != "i" or v.dtype.kind != "i":
+        raise ValueError(f"{fn}: rings is an integer [R][6] array and verts an integer [V][2] array, got {r.dtype} {r.shape} and {v.dtype} {v.shape}")
+    if len(r) and (int(r[:, 3].sum()) != len(v) or (r[:, 2] != np.cumsum(r[:, 3]) - r[:, 3]).any()):
+        raise ValueError(f"{fn}: the rings' offsets and counts do not tile the {len(v)} vertices")
+    return r.astype(np.int64), v.astype(np.int64)
+
+
+def _ring_holds(ring: np.ndarray, i: int, j: int) -> bool:
+    """Even-odd: does the ring enclose the centre of pixel (i, j)?  The ray runs east; only vertical edges can cross it."""
+    y0, x0, y1 = ring[:, 0], ring[:, 1], np.roll(ring[:, 0], -1)
+    vertical = (x0 == np.roll(ring[:, 1], -1)) & (x0 > j) & (np.minimum(y0, y1) <= i) & (i < np.maximum(y0, y1))
+    return bool(vertical.sum() & 1)
+
+
+def outline_polygons(rings, verts, table=None, min_area: int = 0) -> List[dict]:
+    """The polygons of host_outlines' (rings, verts): a list of dicts {id, class, area, exterior, holes}, one per outer ring, in ring
+    order.  exterior is the ring's int [n][2] vertices (y, x), holes a list of such arrays.  A hole goes to the outer ring of the same id
+    with the smallest area that contains the pixel owning the hole's leader edge (even-odd; rings of one id never cross, so that ring
+    is unique); an id in several pieces gives several polygons.  area is the exterior's area plus the (negative) areas of its holes:
+    the pixels of that piece.  class is column 1 of row `id` of `table` (an instance table) or None without one.  Polygons of fewer than
+    min_area pixels are left out, with their holes."""
+    r, v = _check_rings("outline_polygons", rings, verts)
+    if table is not None:
+        table = _check_table("outline_polygons", table, "table")
+    take = lambda q: v[q[2]:q[2] + q[3]]
+    outer = [k for k in range(len(r)) if r[k, 4] > 0]
+    polys = {k: {"id": int(r[k, 0]), "class": None if table is None else int(table[r[k, 0], 1]), "area": int(r[k, 4]),
+                 "exterior": take(r[k]).astype(np.int32), "holes": []} for k in outer}
+    by_id = {}
+    for k in outer:
+        by_id.setdefault(int(r[k, 0]), []).append(k)
+    box = {k: (polys[k]["exterior"].min(0), polys[k]["exterior"].max(0)) for k in outer}
+    for q in r[r[:, 4] < 0]:
+        hole = take(q)
+        # The edges from the leader to the first vertex share its side s, so the one that ends at that vertex is owned by the pixel at
+        # vertex - _OL_END[s]: a pixel of the same piece as the leader's (the key alone does not give the pixel without W).
+        end = _OL_END[int(q[1]) & 3]
+        pi, pj = int(hole[0, 0]) - end[0], int(hole[0, 1]) - end[1]
+        best = None
+        for k in by_id.get(int(q[0]), ()):
+            lo, hi = box[k]
+            if lo[0] <= pi < hi[0] and lo[1] <= pj < hi[1] and (best is None or r[k, 4] < r[best, 4]) and _ring_holds(polys[k]["exterior"], pi, pj):
+                best = k
+        if best is None:
+            raise ValueError(f"outline_polygons: the hole with leader key {int(q[1])} lies in no outer ring of id {int(q[0])}")
+        polys[best]["holes"].append(hole.astype(np.int32))
+        polys[best]["area"] += int(q[4])
+    return [polys[k] for k in outer if polys[k]["area"] >= min_area]
+
+
+def _simplify_chain(pts: np.ndarray, lo: int, hi: int, q: int, keep: np.ndarray) -> None:
+    """Douglas-Peucker between the kept vertices lo < hi of pts (int64 [n][2]): the vertex farthest from the chord stays, and both
+    halves are treated alike, unless it lies within the tolerance: 256 cross^2 <= q^2 len^2, exact in integers."""
+    stack = [(lo, hi)]
+    while stack:
+        lo, hi = stack.pop()
+        if hi - lo < 2:
+            continue
+        d, rel = pts[hi] - pts[lo], pts[lo + 1:hi] - pts[lo]
+        len2 = int(d[0]) * int(d[0]) + int(d[1]) * int(d[1])
+        # a chord of length 0 (a ring that touches itself at a corner): the distance from that point
+        far2 = (rel[:, 0] * d[1] - rel[:, 1] * d[0]) ** 2 if len2 else (rel ** 2).sum(1)
+        k = int(far2.argmax())
+        if 256 * int(far2[k]) > q * q * (len2 or 1):
+            keep[lo + 1 + k] = True
+            stack += [(lo, lo + 1 + k), (lo + 1 + k, hi)]
+
+
+def simplify_ring(ring, tolerance: float) -> np.ndarray:
+    """Douglas-Peucker on a closed ring of vertices (y, x), int [n][2], first vertex not repeated: the ring is anchored at its first
+    vertex and at the vertex farthest from it, and both chains between the anchors are simplified with the exact integer test
+    256 cross^2 <= q^2 len^2, q = round(16 tolerance), in int64 (coordinates below 2^14 cannot overflow it).  Tolerance 0 returns the
+    input, and so does a ring that would be left with fewer than 4 vertices.  The anchors always stay: a ring whose first vertex sits on
+    a small notch keeps it.  Known limit: neighbouring polygons are simplified independently and may then overlap, or leave a gap, by up
+    to the tolerance."""
+    pts = np.asarray(ring)
+    if pts.ndim != 2 or pts.shape[1] != 2 or len(pts) < 4 or pts.dtype.kind != "i":
+        raise ValueError(f"simplify_ring: a ring is an integer [n][2] array of at least 4 vertices, got {pts.dtype} {pts.shape}")
+    if not tolerance >= 0:
+        raise ValueError(f"simplify_ring: tolerance {tolerance!r} is negative")
+    q = int(round(16 * float(tolerance)))
+    if q == 0:
+        return pts
+    p = pts.astype(np.int64)
+    far = int(((p - p[0]) ** 2).sum(1).argmax())
+    closed = np.concatenate([p, p[:1]])                                                 # the second chain ends at the first vertex again
+    keep = np.zeros(len(closed), bool)
+    keep[[0, far]] = True
+    _simplify_chain(closed, 0, far, q, keep)
+    _simplify_chain(closed, far, len(p), q, keep)
+    return pts[keep[:-1]] if keep[:-1].sum() >= 4 else pts
+
+
+def _shoelace2(xy) -> float:
+    """twice the signed area of a closed ring of (X, Y): positive counter-clockwise, Y pointing up"""
+    return sum(a[0] * b[1] - b[0] * a[1] for a, b in zip(xy, xy[1:] + xy[:1]))
+
+
+def write_geojson(path: str, polygons: Sequence[dict], transform=(0.0, 1.0, 0.0, 0.0, 0.0, -1.0), properties=None) -> int:
+    """outline_polygons' dicts as a GeoJSON FeatureCollection of Polygon features (the json module only); the number of features.
+    transform = (x0, dx, rx, y0, ry, dy) maps a vertex (y, x) to X = x0 + dx x + rx y, Y = y0 + ry x + dy y - the six numbers of a
+    world file in GDAL's order; the default maps (y, x) to (x, -y).  Rings are closed (first point repeated), the exterior
+    counter-clockwise and the holes clockwise in OUTPUT coordinates, as RFC 7946 asks: the orientation is decided from the signed area
+    after the transform.  A feature's properties are id, class and area, updated by `properties` (a dict for every feature, or a
+    function of the polygon dict that returns one)."""
+    import json
+    t = [float(v) for v in transform]
+    if len(t) != 6:
+        raise ValueError(f"write_geojson: transform {transform!r} is not six numbers (x0, dx, rx, y0, ry, dy)")
+
+    def ring_of(vertices, ccw: bool):
+        xy = [[t[0] + t[1] * float(x) + t[2] * float(y), t[3] + t[4] * float(x) + t[5] * float(y)] for y, x in np.asarray(vertices).tolist()]
+        if (_shoelace2(xy) > 0) != ccw:
+            xy.reverse()
+        return xy + [xy[0]]
+
+    features = []
+    for poly in polygons:
+        props = {"id": poly["id"], "class": poly["class"], "area": poly["area"]}
+        if properties is not None:
+            props.update(properties(poly) if callable(properties) else properties)
+        features.append({"type": "Feature", "properties": props,
+                         "geometry": {"type": "Polygon", "coordinates": [ring_of(poly["exterior"], True)] + [ring_of(h, False) for h in poly["holes"]]}})
+    with open(path, "w") as f:
+        json.dump({"type": "FeatureCollection", "features": features}, f)
+    return len(features)
+
 _PASTE = "rua_window_paste"
 MAX_PASTE_OFFSET = 1024
 BANK_COLUMNS = ("scene", "id", "class", "area", "i_min", "j_min", "i_max", "j_max")
@@ -2673,6 +2917,57 @@ class ScenePool:
             keep = []
             dp, dg, dt = (torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in (p, g, tp))
             return self._device_match(dp, dt, dg, len(tg), p.shape, st, keep).cpu().numpy()
+
+    def _device_outlines(self, inst, shape, conn: int, st):
+        """host_outlines of a resident int32 [H][W] id map, as numpy arrays: rua_scene_outline_count on stream `st`, one fetch of its
+        16 bytes (E, V) - the outputs are sized by them -, rua_scene_outline_rings, one fetch of rings, vertices and R."""
+        import torch
+        from . import _lib as L
+        H, W = shape
+        dev = self.device
+        i32 = lambda n: torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+        base, n = i32(H * W), torch.empty((2,), dtype=torch.int64, device=dev)
+        nwork = int(L.lib().raw("rua_scene_outline_work_bytes")(H, W, 0))
+        work = i32(nwork // 4)
+        L.lib().call(_OL_COUNT, inst.data_ptr(), H, W, conn, base.data_ptr(), work.data_ptr(), nwork, n.data_ptr(), st)
+        E, V = (int(v) for v in n.cpu().numpy())                                         # the one readback between the two calls
+        if E == 0:
+            return np.zeros((0, 6), np.int32), np.zeros((0, 2), np.int32)
+        nwork = int(L.lib().raw("rua_scene_outline_work_bytes")(H, W, E))
+        work = i32(nwork // 4)
+        rings, verts = i32(V // 4 * 6).view(-1, 6), i32(V * 2).view(-1, 2)
+        L.lib().call(_OL_RINGS, inst.data_ptr(), base.data_ptr(), H, W, conn, E, V, work.data_ptr(), nwork, rings.data_ptr(), verts.data_ptr(),
+                     n.data_ptr(), st)
+        R = int(n.cpu().numpy()[0])
+        return rings[:R].cpu().numpy(), verts.cpu().numpy()
+
+    def outlines(self, inst_maps=None, connectivity: int = 4):
+        """host_outlines of one int32 [H][W] id map per scene, as a list of (rings int32 [R][6], verts int32 [V][2]) (a None entry
+        skips its scene and gives None).  inst_maps None: the pool's own ground-truth id maps, where object_bank() left them resident.
+        Maps given as numpy arrays are uploaded; per scene rua_scene_outline_count, a fetch of 16 bytes, rua_scene_outline_rings and
+        the fetch of the result, on the current stream.  A "cpu" pool returns the host definition."""
+        if inst_maps is None:
+            if self.bank is None:
+                raise ValueError("no object bank yet: ScenePool.object_bank() builds the id maps")
+            maps = self.inst_dev if self.device.type == "cuda" else self._inst_host
+        else:
+            maps = list(inst_maps)
+            if len(maps) != len(self):
+                raise ValueError(f"{_OL_COUNT}: {len(maps)} maps for {len(self)} scenes (one per scene, None to skip one)")
+            maps = [None if m is None else np.ascontiguousarray(_check_inst_map(_OL_COUNT, m, f"scene {s}: the map")) for s, m in enumerate(maps)]
+        conn = _check_connectivity(_OL_COUNT, connectivity)
+        for s, m in enumerate(maps):
+            if m is not None:
+                check_outlines(tuple(m.shape), conn)
+                if tuple(m.shape) != self.shapes[s]:
+                    raise ValueError(f"{_OL_COUNT}: scene {s}: the map is {tuple(m.shape)}, the scene {self.shapes[s]}")
+        if self.device.type != "cuda":
+            return [None if m is None else host_outlines(m, conn) for m in maps]
+        import torch
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            return [None if m is None else self._device_outlines(torch.from_numpy(m).to(self.device) if isinstance(m, np.ndarray) else m,
+                                                                 self.shapes[s], conn, st) for s, m in enumerate(maps)]
 
     def _area_open(self, given, dev, first, lv, mn, conn, st):
         """rua_scene_area_open of the dense maps of the scenes `given` that lie in `dev` from first[k] on: the opened maps in one
