@@ -74,6 +74,15 @@ object precision, recall and F1 at IoU 0.5 and the mean F1 over 0.5:0.05:0.95 ar
 C x 6: n_pred, n_true, precision, recall, F1 at 0.5, mean F1) and, with --inst_map yes, `inst_map_<name>.npy` (int32 H x W, -1
 off the objects) are written; the returned dict gains `instance_scores` and `instance_counts`.
 
+--inst_flood yes [--inst_flood_rounds J] [--inst_flood_floor F] [--inst_flood_drain D], with --instances, floods the grown objects of
+the prediction over the rest of their class before they are matched, traced and written: a bounded watershed on the GPU
+(scenes.host_flood) that lets the distance map's levels 255 .. F down one by one, J rounds each, and D rounds more at the last
+level; in a round a pixel of the class that has reached the level joins the smallest object beside it.  The height is the
+predicted distance map on a multitask model without --scales and --blend, and absent elsewhere (a geodesic grow).  F is a
+probability in 0..1, quantised as the head maps are.  Buildings need it: a seed threshold high enough to split two touching
+buildings leaves cores that --inst_radius cannot grow back to the outline.  Per scene the settled pixels are printed, and a warning
+where the last round still settled some (the schedule may have cut the flood short); the returned dict gains `flood_settled`.
+
 --polygons yes [--poly_simplify T] [--poly_min_area A] [--poly_truth yes], with --instances, also writes the objects as a vector
 layer: the predicted instance map is traced on the GPU into closed rings of pixel corners, outer rings and holes
 (scenes.host_outlines; only rings and vertices leave the GPU), every hole is given to the ring round it (scenes.outline_polygons),
@@ -162,6 +171,10 @@ def build_parser():
     parser.add_argument("--inst_radius", type=int, default=4, metavar="R", help="seeds are grown back over their class within R pixels (0..16)")
     parser.add_argument("--inst_connectivity", type=int, default=4, metavar="4|8", help="what connects the pixels of a seed: 4- or 8-neighbours")
     parser.add_argument("--inst_map", type=_yes, default=False, help="also write the instance map of every scene")
+    parser.add_argument("--inst_flood", type=_yes, default=False, help="with --instances: flood the grown objects over their class, down the distance map")
+    parser.add_argument("--inst_flood_rounds", type=int, default=1, metavar="J", help="rounds per level of the flood (1..16)")
+    parser.add_argument("--inst_flood_floor", type=float, default=0.0, metavar="F", help="the lowest distance-map value the flood lets down (0..1)")
+    parser.add_argument("--inst_flood_drain", type=int, default=0, metavar="D", help="further rounds at the lowest level (0..4096)")
     parser.add_argument("--polygons", type=_yes, default=False, help="with --instances: also write the objects of every scene as GeoJSON polygons")
     parser.add_argument("--poly_simplify", type=float, default=0.0, metavar="T", help="Douglas-Peucker tolerance in pixels for every ring (0: the exact outline)")
     parser.add_argument("--poly_min_area", type=int, default=0, metavar="A", help="polygons of fewer than A pixels are left out")
@@ -223,11 +236,15 @@ def parse_instances(args):
     if args.instances is None:
         if args.polygons:
             raise SystemExit("--polygons needs --instances: the polygons are the outlines of its objects")
+        if args.inst_flood:
+            raise SystemExit("--inst_flood needs --instances: the flood grows its objects")
         return None
     if args.polygons and (not args.poly_simplify >= 0 or args.poly_min_area < 0):
         raise SystemExit(f"--polygons: --poly_simplify {args.poly_simplify:g} and --poly_min_area {args.poly_min_area} must not be negative")
     inst = dict(classes=args.instances, bound_below=256 if args.inst_bound == 1.0 else float(args.inst_bound), dist_at_least=float(args.inst_dist),
                 min_seed=args.inst_min_seed, radius=args.inst_radius, connectivity=args.inst_connectivity, map=bool(args.inst_map))
+    if args.inst_flood:
+        inst["flood"] = dict(rounds_per_level=args.inst_flood_rounds, floor=float(args.inst_flood_floor), drain=args.inst_flood_drain)
     try:
         p = scenes.instance_params(inst, args.num_classes)
     except ValueError as exc:
@@ -329,7 +346,7 @@ def main(argv=None):
     total_raw, total_regions, total_changed = np.zeros_like(total), np.zeros((args.num_classes, 3), np.int64), 0
     all_head_maps, mae_sum, mae_n = [], 0.0, 0
     total_hist = np.zeros((2, 2, 256), np.int64)
-    object_scores = []
+    object_scores, flood_settled = [], 0
     polygon_counts, polygon_counts_true = (np.zeros((args.num_classes, 2), np.int64) for _ in range(2))
     print('=' * 40)
     print('[TEST]')
@@ -362,6 +379,12 @@ def main(argv=None):
                     write_polygons(os.path.join(args.output_path, f'polygons_true_{name}.geojson'), objects["outlines_true"], objects["gt_table"], args,
                                    polygon_counts_true)
             print(f'scene {name}: {objects["n"]} predicted objects, {objects["gt_n"]} true objects, {objects["ungrown"]} pixels of the classes outside every object')
+            if "flood" in objects:
+                fl = objects["flood"]
+                flood_settled += fl["settled"]
+                cut = ' - the last round still settled pixels: the schedule may have cut the flood short' if fl["last_round"] == fl["rounds"] else ''
+                print(f'scene {name}: the flood settled {fl["settled"]} pixels ({"down the distance map" if fl["height"] else "without a height"}, '
+                      f'last round {fl["last_round"]} of {fl["rounds"]}){cut}')
         if sweep is not None:
             swept = more.pop()
             total_hist += swept["hist"]
@@ -463,6 +486,8 @@ def main(argv=None):
             print(f'  {c:5d} {int(table[c, 0]):10d} {int(table[c, 1]):8d} {table[c, 2]:10.4f} {table[c, 3]:8.4f} {table[c, 4]:8.4f} {table[c, 5]:8.4f}')
         np.save(os.path.join(args.output_path, 'instance_scores.npy'), table)
         res.update(instance_scores=sc, instance_counts=np.stack([sc["n_pred"], sc["n_true"]], 1))
+        if args.inst_flood:
+            res["flood_settled"] = flood_settled
         if args.polygons:
             print()
             print(f'Polygons (simplified at {args.poly_simplify:g} px, at least {args.poly_min_area} px)' + (', predicted / true' if args.poly_truth else ''))

@@ -1152,6 +1152,39 @@ int64_t rua_scene_instance_match_work_bytes(int64_t Np, int64_t Ng);
 int rua_scene_instance_match(const int32_t* inst_p, const int32_t* area_p /* table_p, column 2 */, int64_t Np, const int32_t* inst_g,
                              int64_t Ng, int H, int W, void* work, int64_t work_bytes, int32_t* match, void* stream);
 
+/* ---- flooding: a bounded, marker-controlled watershed of a height map in synchronous rounds (scenes.py, host_flood) ----------------
+ * One scene per call.  Every pointer is DEVICE memory.  cls is the uint8 [H][W] class map, inst the int32 [H][W] id map that
+ * rua_scene_instances left (any radius), changed in place: a pixel with inst >= 0 is SETTLED and never changes; a pixel is ELIGIBLE
+ * if c = cls[x] < C and bit c of class_mask is set.  The height of pixel x is 255 with height == NULL, else the byte
+ * height[x * pix_stride + (per_class ? cls[x] : 0)]: pix_stride 1 for a [H][W] map, C with per_class 1 for the [H][W][C] maps
+ * rua_scene_stitch_maps writes.  The schedule is R = (256 - floor) * rounds_per_level + drain rounds: the levels t = 255, 254, ..,
+ * floor, each rounds_per_level times, then `drain` more rounds at level floor.  One round at level t, every decision reading the
+ * state at the start of the round: an eligible, unsettled pixel x with height(x) >= t that has at least one settled neighbour y
+ * (under `connectivity`; pixels outside the map do not exist) with cls[y] == cls[x] takes the smallest id among those neighbours.
+ * Nothing else changes.  stats is int32 [2]: the pixels the flood settled, and 1 + the index of the last round that settled one (0
+ * if none did; equal to R, the schedule may have cut the flood short).
+ * With a table (int32 [max_instances][8], rua_scene_instances' own, n its int32 [2]): after the last round the columns area and
+ * i_min, j_min, i_max, j_max of the rows below min(n[0], max_instances) are rewritten from the final inst (ids from there on have no
+ * row), and n[1] is recounted: the eligible pixels with inst < 0.  Root, class and seed area stay.  table == NULL skips that pass;
+ * n may then be NULL and is not touched.
+ * work: 4-byte aligned, work_bytes >= rua_scene_flood_work_bytes(H, W): a second int32 map and a flag per 32 x 32 tile (-1 for sizes
+ * the call would refuse).  A launch runs 8 rounds: a block per tile stages ids, class bytes and height bytes of the tile and a halo
+ * of 8 pixels in LDS, runs the rounds there and writes its interior to the OTHER id map - the maps alternate, the result ends in
+ * inst, and no block reads what another block of the same launch writes.  A tile without an eligible unsettled pixel costs a copy,
+ * and nothing once both maps hold it.  ceil(R / 8) launches plus at most four, whatever the map holds; nothing is read back, no block
+ * waits for another, integer atomics only: scenes.host_flood gives the same bytes.
+ * Everything is checked on the host before anything is launched (a violation: RUA_ERR_ARG, the message names the offender, nothing is
+ * written): the required pointers, 1 <= H, W and H * W < 2^31, 1 <= C <= 64, no bit >= C in class_mask, connectivity 4 or 8,
+ * 1 <= rounds_per_level <= 16, 0 <= floor <= 255, 0 <= drain <= 4096, with a height per_class 0 or 1 and 1 <= pix_stride <= 256
+ * (>= C with per_class), with a table 1 <= max_instances < 2^31, 4-byte alignment of every int32 array, the work buffer, no output
+ * sharing a byte with an input or with another output of the call. */
+int64_t rua_scene_flood_work_bytes(int H, int W);
+int rua_scene_flood(const uint8_t* cls, const uint8_t* height /* or NULL */, int pix_stride, int per_class,
+                    int H, int W, int C, uint64_t class_mask, int connectivity, int rounds_per_level, int floor, int drain,
+                    void* work, int64_t work_bytes, int32_t* inst /* in, out */, int32_t* table /* or NULL */, int64_t max_instances,
+                    int32_t* n /* device int32[2] of rua_scene_instances: n[1] (ungrown) is rewritten */,
+                    int32_t* stats /* device int32[2]: settled, last_round */, void* stream);
+
 /* ---- outlines of whole-scene instance maps: one closed ring of grid corners per object piece and per hole (scenes.py, host_outlines /
  * outline_polygons / write_geojson) ------------------------------------------------------------------------------------------------
  * One map per call.  Every pointer is DEVICE memory.  inst is an int32 [H][W] id map (rua_scene_instances' inst, or any other): an id

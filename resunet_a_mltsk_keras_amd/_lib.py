@@ -270,6 +270,8 @@ _SIGS = {
     "rua_scene_instances": ([vp, vp, vp, vp, i32, i32, i32, C.c_uint64, i64, i32, vp, i64, vp, vp, i64, vp, vp], i32),
     "rua_scene_instance_match_work_bytes": ([i64, i64], i64),
     "rua_scene_instance_match": ([vp, vp, i64, vp, i64, i32, i32, vp, i64, vp, vp], i32),
+    "rua_scene_flood_work_bytes": ([i32, i32], i64),
+    "rua_scene_flood": ([vp, vp, i32, i32, i32, i32, i32, C.c_uint64, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp], i32),
     "rua_scene_outline_work_bytes": ([i32, i32, i64], i64),
     "rua_scene_outline_count": ([vp, i32, i32, i32, vp, vp, i64, vp, vp], i32),
     "rua_scene_outline_rings": ([vp, vp, i32, i32, i32, i64, i64, vp, i64, vp, vp, vp, vp], i32),

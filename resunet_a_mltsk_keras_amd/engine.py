@@ -2807,26 +2807,32 @@ class Engine:
         maps, and with scales or blend (the probabilities then live in an int32 accumulator: no maps of the heads are built).
         instances: None is every path and return value above, call for call.  Otherwise the objects of the finished map: a class
         index, a list of classes, or a dict {classes, bound_below=128, dist_at_least=0, min_seed=1, radius=4, connectivity=4,
-        iou_percent=(50, 55 .. 95), max_instances=2^20, map=False, outlines=False} (scenes.instance_params; the two thresholds are
-        byte levels, or floats in 0..1 that are quantised as the maps are).  The "bound" map is stitched when bound_below < 256 and the "dist" map
-        when dist_at_least > 0, as heads= stitches them, whether or not the caller asked for them (they are returned only if asked
-        for).  After the sieve - the instances are those of the SIEVED map when sieve= is given - and before any fetch, on the
-        compute stream: rua_scene_seed_map keeps the pixels of the chosen classes that lie off the predicted boundaries and deep
-        enough in the distance map, rua_scene_regions labels that marker and rua_scene_instances numbers the seeds and grows them
-        back over their class within `radius` pixels (scenes.host_seed_map and scenes.host_instances are the definitions).  On a
-        pool with class maps the same three calls, without head maps and at radius 0, turn the pool's class map into the true
-        objects - the connected regions of the chosen classes - and rua_scene_instance_match finds for every predicted instance
-        the object that holds more than half of it (scenes.host_instance_match).  A report {"n", "ungrown", "table": int32 [n][8]
-        (scenes.TABLE_COLUMNS), "inst": int32 [H][W] (only with map=True), "gt_n", "gt_table", "match": int32 [n][2], "scores":
-        scenes.instance_scores at iou_percent} is added after the sweep report and in front of the head maps, fetched once at the
-        end; the last four entries are None without class maps.  With outlines=True the report gains "outlines" and "outlines_true",
-        each a (rings int32 [R][6], verts int32 [V][2]) pair (scenes.host_outlines; outline_polygons and write_geojson turn them into
-        a vector layer): rua_scene_outline_count and rua_scene_outline_rings trace the predicted instance map, and the true objects'
-        map on a pool with class maps (None without), where they lie, after everything else was issued - only rings and vertices
-        leave the GPU.  Without the key the calls are what they were.  ValueError, before any GPU work, for a malformed value, a head
-        threshold on a single-task model (give bound_below=256 there: with both head tests off only the class map is read, and
-        it works everywhere) and a head threshold together with scales or blend (no maps of the heads are built there);
-        ValueError after the fetch if the scene holds more than max_instances seeds or objects."""
+        iou_percent=(50, 55 .. 95), max_instances=2^20, map=False, outlines=False, flood=None} (scenes.instance_params; the two
+        thresholds are byte levels, or floats in 0..1 that are quantised as the maps are).  The "bound" map is stitched when
+        bound_below < 256 and the "dist" map when dist_at_least > 0, as heads= stitches them, whether or not the caller asked for
+        them (they are returned only if asked for).  After the sieve - the instances are those of the SIEVED map when sieve= is given
+        - and before any fetch, on the compute stream: rua_scene_seed_map keeps the pixels of the chosen classes that lie off the
+        predicted boundaries and deep enough in the distance map, rua_scene_regions labels that marker and rua_scene_instances
+        numbers the seeds and grows them back over their class within `radius` pixels (scenes.host_seed_map and
+        scenes.host_instances are the definitions).  On a pool with class maps the same three calls, without head maps and at radius
+        0, turn the pool's class map into the true objects - the connected regions of the chosen classes - and
+        rua_scene_instance_match finds for every predicted instance the object that holds more than half of it
+        (scenes.host_instance_match).  A report {"n", "ungrown", "table": int32 [n][8] (scenes.TABLE_COLUMNS), "inst": int32 [H][W]
+        (only with map=True), "gt_n", "gt_table", "match": int32 [n][2], "scores": scenes.instance_scores at iou_percent} is added
+        after the sweep report and in front of the head maps, fetched once at the end; the last four entries are None without class
+        maps.  With flood=True or a dict {rounds_per_level=1, floor=0, drain=0} (scenes.flood_params) the grown instances of the
+        PREDICTION are flooded over their class before the match and the outlines read them - rua_scene_flood, scenes.host_flood the
+        definition; the ground truth is untouched.  On a multitask model without scales= and blend= the distance map is stitched,
+        asked for or not, and is the per-class height; elsewhere the flood runs without a height.  "ungrown", "table" and "inst" are
+        then the flooded ones and the report gains "flood": {"height": "dist" | None, "rounds", "settled", "last_round"}.  With
+        outlines=True the report gains "outlines" and "outlines_true", each a (rings int32 [R][6], verts int32 [V][2]) pair
+        (scenes.host_outlines; outline_polygons and write_geojson turn them into a vector layer): rua_scene_outline_count and
+        rua_scene_outline_rings trace the predicted instance map, and the true objects' map on a pool with class maps (None
+        without), where they lie, after everything else was issued - only rings and vertices leave the GPU.  Without the key the
+        calls are what they were.  ValueError, before any GPU work, for a malformed value, a head threshold on a single-task model
+        (give bound_below=256 there: with both head tests off only the class map is read, and it works everywhere) and a head
+        threshold together with scales or blend (no maps of the heads are built there); ValueError after the fetch if the scene
+        holds more than max_instances seeds or objects."""
         H, W, _ = self.cfg.input_shape
         Cn = self.cfg.num_classes
         if instances is not None:
@@ -2898,6 +2904,10 @@ class Engine:
         extra = ("seg",) if sweep is not None and "seg" not in heads else ()                  # the sweep reads the seg map, asked for or not
         if instances is not None:
             extra += tuple(h for h in inst_heads if h not in heads)                           # ... and the seed map the head maps it tests
+            flood = instances.get("flood")
+            flood_dist = flood is not None and self.cfg.multitasking and scales is None       # blend= sets scales: no head maps there
+            if flood_dist and "dist" not in heads + extra:
+                extra += ("dist",)                                                            # ... and the flood its height
         for h in heads + extra:
             src = g.outputs["color" if h == "color_rgb" else h]["p"]
             m = torch.zeros((SH, SW, src.C), dtype=torch.uint8, device=self.dev)
@@ -2998,6 +3008,11 @@ class Engine:
             inst_p, table_p, n_p = pool._device_instances(pred.data_ptr(), head_ptr("bound"), head_ptr("dist"), (SH, SW), Cn, ip["mask"],
                                                           ip["bound_below"], ip["dist_at_least"], ip["min_seed"], ip["radius"], ip["connectivity"],
                                                           cap, st, inst_keep)
+            if flood is not None:
+                # the grown instances flood down the distance map, in place, before anything reads them
+                fstats = pool._device_flood(pred.data_ptr(), head_maps["dist"][3].data_ptr() if flood_dist else None,
+                                            head_maps["dist"][1] if flood_dist else 1, 1 if flood_dist else 0, (SH, SW), Cn, ip["mask"],
+                                            ip["connectivity"], flood, inst_p, table_p, cap, n_p, st, inst_keep)
             if counted:
                 inst_g, table_g, n_g = pool._device_instances(pool.cls_dev[sc].data_ptr(), None, None, (SH, SW), Cn, ip["mask"], 256, 0, 1, 0,
                                                               ip["connectivity"], cap, st, inst_keep)
@@ -3015,6 +3030,9 @@ class Engine:
             if N > cap:
                 raise ValueError(f"rua_scene_instances: the scene holds {N} seeds, max_instances is {ip['max_instances']}")
             report = {"n": N, "ungrown": ungrown, "table": table_p[:N].cpu().numpy(), "gt_n": None, "gt_table": None, "match": None, "scores": None}
+            if flood is not None:
+                settled, last = (int(v) for v in fstats.cpu().numpy())
+                report["flood"] = {"height": "dist" if flood_dist else None, "rounds": flood["rounds"], "settled": settled, "last_round": last}
             if ip["map"]:
                 report["inst"] = inst_p.cpu().numpy()
             if counted:

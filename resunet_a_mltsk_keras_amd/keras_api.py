@@ -799,14 +799,17 @@ class Model:
         {"hist": int64 [2][2][256], "levels", "opened": the opened map or None} is added after the sieve report and before the head
         maps, and scenes.sweep_scores(hist, levels) is the curve; needs class maps, not together with scales or blend; None changes
         nothing.  instances: a class index, a list of classes, or a dict {classes, bound_below=128, dist_at_least=0, min_seed=1,
-        radius=4, connectivity=4 | 8, iou_percent, max_instances, map=False, outlines=False}: the objects of the finished (sieved) map - seeds off
-        the predicted boundaries, grown back over their class on the GPU (scenes.host_seed_map, scenes.host_instances) - and, with
-        class maps, their match against the connected regions of the ground truth (scenes.host_instance_match,
-        scenes.instance_scores); a report {"n", "ungrown", "table", "inst" (with map=True), "gt_n", "gt_table", "match", "scores"}
-        is added after the sweep report and before the head maps; a head threshold needs a multitask model and neither scales nor
-        blend (bound_below=256 reads the class map only); outlines=True adds "outlines" and "outlines_true", the (rings, verts) of the
-        predicted and the true instance map traced on the GPU (scenes.host_outlines; scenes.outline_polygons and scenes.write_geojson
-        make the vector layer); None changes nothing."""
+        radius=4, connectivity=4 | 8, iou_percent, max_instances, map=False, outlines=False, flood=None}: the objects of the
+        finished (sieved) map - seeds off the predicted boundaries, grown back over their class on the GPU (scenes.host_seed_map,
+        scenes.host_instances) - and, with class maps, their match against the connected regions of the ground truth
+        (scenes.host_instance_match, scenes.instance_scores); a report {"n", "ungrown", "table", "inst" (with map=True), "gt_n",
+        "gt_table", "match", "scores"} is added after the sweep report and before the head maps; a head threshold needs a multitask
+        model and neither scales nor blend (bound_below=256 reads the class map only); outlines=True adds "outlines" and
+        "outlines_true", the (rings, verts) of the predicted and the true instance map traced on the GPU (scenes.host_outlines;
+        scenes.outline_polygons and scenes.write_geojson make the vector layer); flood=True or {rounds_per_level=1, floor=0,
+        drain=0} floods the grown instances of the prediction over their class, down the stitched distance map on a multitask model
+        without scales and blend and without a height elsewhere (scenes.host_flood), before match and outlines read them, and adds
+        "flood": {"height", "rounds", "settled", "last_round"}; None changes nothing."""
         if self.engine.loss is None:                      # load_model(..., compile=False), as predict
             self.engine.compile(LossSpec(kind={h: L.LOSS_TANIMOTO for h in HEADS}, weight={h: 1.0 for h in HEADS}))
         return self.engine.predict_scene(pool, scene, stride=stride, batch=batch, norm_type=norm_type, on_batch=on_batch, views=views, erode=erode,

@@ -108,6 +108,12 @@ integers; rua_scene_outline_count and rua_scene_outline_rings (csrc/outlines.hip
 pointer jumping), ScenePool.outlines() and Engine.predict_scene(instances={..., "outlines": True}) their users; outline_polygons()
 gives the holes to their rings, simplify_ring() is an exact-integer Douglas-Peucker and write_geojson() writes the vector layer.
 
+Flooding: host_flood() is the definition of a bounded, marker-controlled watershed of a height map in synchronous rounds - the
+levels 255 .. floor let down one by one, an unsettled pixel that has reached the level taking the smallest id among its settled
+neighbours of its own class -, flood_table() of the instance table afterwards; rua_scene_flood (csrc/flood.hip) is its kernel on
+resident maps, ScenePool.instances(flood=) and Engine.predict_scene(instances={..., "flood": True}) its users: the grow step that
+brings the small seed cores of touching buildings back to their outlines, which the bounded disc of host_instances cannot.
+
 `python -m resunet_a_mltsk_keras_amd.scenes --image Image_Train.npy --reference Reference_Train.npy --dst DIR` writes a scene
 directory from the reference's two inputs (C x H x W arrays, the reference colour-coded); `--materialize DST` also writes the
 compact patch layout (compact.py) of its window table, for users who want files.
@@ -1902,16 +1908,17 @@ def _byte_threshold(fn: str, key: str, v, lo: int, hi: int) -> int:
     return int(v)
 
 
-INSTANCE_KEYS = ("classes", "bound_below", "dist_at_least", "min_seed", "radius", "connectivity", "iou_percent", "max_instances", "map", "outlines")
+INSTANCE_KEYS = ("classes", "bound_below", "dist_at_least", "min_seed", "radius", "connectivity", "iou_percent", "max_instances", "map", "outlines", "flood")
 
 
 def instance_params(value, C) -> dict:
-    """Engine.predict_scene's `instances` as a dict of every key of INSTANCE_KEYS, checked: a class index or a list of classes
-    takes the defaults (bound_below 128, dist_at_least 0, min_seed 1, radius 4, connectivity 4, iou_percent 50, 55 .. 95,
-    max_instances 2^20, map False); a dict may hold any of the keys, `classes` is required.  bound_below and dist_at_least may be
-    floats in 0..1: they are quantised with the rounding the maps use, rint(255 v) (bound_below at least 1).  "mask" is added:
-    bit c set for every chosen class.  "outlines" (trace the instance maps: host_outlines) is in the result only if it was given.
-    ValueError, in the C entries' words, for anything else."""
+    """Engine.predict_scene's `instances` as a dict of every key of INSTANCE_KEYS, checked: a class index or a list of classes takes
+    the defaults (bound_below 128, dist_at_least 0, min_seed 1, radius 4, connectivity 4, iou_percent 50, 55 .. 95, max_instances
+    2^20, map False); a dict may hold any of the keys, `classes` is required.  bound_below and dist_at_least may be floats in 0..1:
+    they are quantised with the rounding the maps use, rint(255 v) (bound_below at least 1).  "mask" is added: bit c set for every
+    chosen class.  "outlines" (trace the instance maps: host_outlines) is in the result only if it was given, and so is "flood"
+    (flood the grown instances down the distance map: host_flood), as flood_params returns it.  ValueError, in the C entries' words,
+    for anything else."""
     C_ = _check_num_classes(_INST, C)
     if _is_int(value) or isinstance(value, (list, tuple, np.ndarray)):
         value = {"classes": value}
@@ -1938,7 +1945,151 @@ def instance_params(value, C) -> dict:
            "radius": r, "connectivity": conn, "iou_percent": tuple(int(t) for t in iou), "max_instances": cap, "map": bool(value.get("map", False))}
     if "outlines" in value:
         out["outlines"] = bool(value["outlines"])
+    if "flood" in value:
+        out["flood"] = flood_params(value["flood"])
     return out
+
+
+# ---- flooding: a bounded, marker-controlled watershed of a height map in synchronous rounds ----------------------------------------
+_FLOOD = "rua_scene_flood"
+FLOOD_KEYS = ("rounds_per_level", "floor", "drain")
+MAX_FLOOD_ROUNDS_PER_LEVEL, MAX_FLOOD_DRAIN = 16, 4096
+
+
+def check_flood(num_classes, classes, connectivity=4, rounds_per_level=1, floor=0, drain=0, fn: str = _FLOOD):
+    """(C, class mask, connectivity, rounds_per_level, floor, drain) of rua_scene_flood; ValueError in its own words unless
+    1 <= C <= 64, every class is an integer in 0..C-1, connectivity is 4 or 8, rounds_per_level an integer in 1..16, floor one in
+    0..255 and drain one in 0..4096."""
+    C_ = _check_num_classes(fn, num_classes)
+    mask = _class_mask(fn, classes, C_)
+    conn = _check_connectivity(fn, connectivity)
+    if not _is_int(rounds_per_level) or not 1 <= int(rounds_per_level) <= MAX_FLOOD_ROUNDS_PER_LEVEL:
+        raise ValueError(f"{fn}: rounds_per_level {rounds_per_level!r} outside 1..16")
+    if not _is_int(floor) or not 0 <= int(floor) <= 255:
+        raise ValueError(f"{fn}: floor {floor!r} outside 0..255")
+    if not _is_int(drain) or not 0 <= int(drain) <= MAX_FLOOD_DRAIN:
+        raise ValueError(f"{fn}: drain {drain!r} outside 0..4096")
+    return C_, mask, conn, int(rounds_per_level), int(floor), int(drain)
+
+
+def flood_rounds(rounds_per_level=1, floor=0, drain=0) -> int:
+    """R, the length of the schedule: (256 - floor) rounds_per_level + drain."""
+    return (256 - int(floor)) * int(rounds_per_level) + int(drain)
+
+
+def flood_params(value):
+    """The `flood` of ScenePool.instances and of predict_scene's `instances` as a checked dict {rounds_per_level, floor, drain,
+    rounds}: True takes the defaults (1, 0, 0); a dict may hold any of FLOOD_KEYS, and its floor may be a float in 0..1, quantised
+    with the rounding the maps use, rint(255 v); None and False are None, no flood.  "rounds" is R, the length of the schedule.
+    ValueError, in rua_scene_flood's words, for anything else."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        value = {}
+    if not isinstance(value, dict):
+        raise ValueError(f"flood {value!r}: None, True or a dict of {', '.join(FLOOD_KEYS)}")
+    unknown = sorted(set(value) - set(FLOOD_KEYS))
+    if unknown:
+        raise ValueError(f"flood: unknown key {unknown[0]!r} ({', '.join(FLOOD_KEYS)})")
+    fl = _byte_threshold(_FLOOD, "floor", value.get("floor", 0), 0, 255)
+    _, _, _, J, fl, D = check_flood(1, 0, 4, value.get("rounds_per_level", 1), fl, value.get("drain", 0))
+    return {"rounds_per_level": J, "floor": fl, "drain": D, "rounds": flood_rounds(J, fl, D)}
+
+
+def _flood_height(fn: str, height, cm: np.ndarray, C_: int):
+    """The height of every pixel as a uint8 [H][W] array (None stays None), from None, a [H][W] or a [H][W][C] map."""
+    if height is None:
+        return None
+    h = np.asarray(height)
+    if h.dtype != np.uint8 or h.shape not in (cm.shape, cm.shape + (C_,)):
+        raise ValueError(f"{fn}: the height is None or a uint8 [{cm.shape[0]}][{cm.shape[1]}] or [{cm.shape[0]}][{cm.shape[1]}][{C_}] map, "
+                         f"got {h.dtype} {h.shape}")
+    if h.ndim == 3:
+        h = np.take_along_axis(h, np.minimum(cm, C_ - 1).astype(np.int64)[..., None], 2)[..., 0]    # read where the pixel is eligible
+    return h
+
+
+def host_flood(cls: np.ndarray, height, inst: np.ndarray, *, num_classes, classes, connectivity=4, rounds_per_level=1, floor=0, drain=0):
+    """The numpy definition of what rua_scene_flood leaves: (inst_out int32 [H][W], settled, last_round).  cls is the uint8 [H][W]
+    class map, inst the int32 id map host_instances left (any radius; -1: no instance).  height is None - every pixel has height
+    255 -, a uint8 [H][W] map, or a uint8 [H][W][C] map in the layout predict_scene(heads=("dist",)) returns, the height of x then
+    being height[x][cls[x]].  A pixel is ELIGIBLE as in host_instances - cls[x] < C and cls[x] chosen - and SETTLED if inst[x] >= 0.
+    The schedule is a list of R = (256 - floor) rounds_per_level + drain rounds: the levels t = 255, 254, .., floor, each
+    rounds_per_level times, then `drain` more rounds at level floor.  One round at level t is synchronous, every decision reads the
+    state at the start of the round: an eligible, unsettled pixel x with height(x) >= t that has at least one settled neighbour y
+    under `connectivity` with cls[y] == cls[x] takes the smallest id among those neighbours (pixels outside the map do not exist);
+    nothing else changes, and a settled pixel never changes again.  `settled` is the number of pixels the flood settled,
+    `last_round` 1 + the index of the last round that settled one, 0 if none did: last_round == R says that the schedule may have
+    cut the flood short.  Meyer's flooding with the priority queue replaced by rounds: breadth-first within a level, a plateau
+    wider than rounds_per_level finishes at later levels; with height None a geodesic grow of reach R.  The loop stops early
+    where every later round is provably idle; the result is that of the full schedule."""
+    C_, mask, conn, J, fl, D = check_flood(num_classes, classes, connectivity, rounds_per_level, floor, drain)
+    cm = _check_region_map(_FLOOD, cls, "the class map")
+    cur = _check_inst_map(_FLOOD, inst, "inst").copy()
+    if cur.shape != cm.shape:
+        raise ValueError(f"{_FLOOD}: inst is {cur.shape}, the class map {cm.shape}")
+    h = _flood_height(_FLOOD, height, cm, C_)
+    H, W = cm.shape
+    chosen = np.array([(mask >> c) & 1 if c < C_ else 0 for c in range(256)], bool)
+    eligible = chosen[cm]
+    key = np.where(eligible, cm, np.uint8(255))
+    steps = [(-1, 0), (1, 0), (0, -1), (0, 1)] + ([(-1, -1), (-1, 1), (1, -1), (1, 1)] if conn == 8 else [])
+    none = np.int64(1) << 40
+    levels, R = (256 - fl) * J, flood_rounds(J, fl, D)
+    settled = last = r = 0
+    while r < R:
+        t = max(255 - r // J, fl)
+        open_ = eligible & (cur < 0)
+        if not open_.any():
+            break
+        cand = open_ if h is None else open_ & (h >= t)
+        k = 0
+        if cand.any():
+            best = np.full((H, W), none, np.int64)
+            for dy, dx in steps:
+                i0, i1, j0, j1 = max(0, -dy), min(H, H - dy), max(0, -dx), min(W, W - dx)    # the pixels whose neighbour exists
+                if i0 >= i1 or j0 >= j1:
+                    continue
+                nb = cur[i0 + dy:i1 + dy, j0 + dx:j1 + dx]
+                ok = (nb >= 0) & (key[i0 + dy:i1 + dy, j0 + dx:j1 + dx] == key[i0:i1, j0:j1])
+                np.minimum(best[i0:i1, j0:j1], np.where(ok, nb.astype(np.int64), none), out=best[i0:i1, j0:j1])
+            take = cand & (best != none)
+            k = int(take.sum())
+            if k:
+                cur[take] = best[take].astype(np.int32)
+                settled, last = settled + k, r + 1
+        if k:
+            r += 1
+        elif r >= levels:
+            break                                                          # the drain: every later round is this one again
+        else:
+            r = (r // J + 1) * J                                           # so are the rounds left at this level
+    return cur, int(settled), int(last)
+
+
+def flood_table(inst: np.ndarray, table: np.ndarray, cls: np.ndarray, *, num_classes, classes):
+    """What rua_scene_flood's last pass makes of host_instances' table and count: (table, ungrown).  The columns area, i_min,
+    j_min, i_max and j_max of every row are those of the pixels with inst == row (none: area 0 and the box H, W, -1, -1; an id from
+    len(table) on has no row), root, class and seed area stay; ungrown counts the eligible pixels with inst < 0."""
+    a, t = _check_inst_map(_FLOOD, inst, "inst"), _check_table(_FLOOD, table, "table").copy()
+    cm = _check_region_map(_FLOOD, cls, "the class map")
+    C_ = _check_num_classes(_FLOOD, num_classes)
+    mask = _class_mask(_FLOOD, classes, C_)
+    if a.shape != cm.shape:
+        raise ValueError(f"{_FLOOD}: inst is {a.shape}, the class map {cm.shape}")
+    H, W = a.shape
+    rows = len(t)
+    if rows:
+        t[:, 2], t[:, 4], t[:, 5], t[:, 6], t[:, 7] = 0, H, W, -1, -1
+        ii, jj = np.nonzero((a >= 0) & (a < rows))
+        k = a[ii, jj].astype(np.int64)
+        t[:, 2] = np.bincount(k, minlength=rows)
+        np.minimum.at(t[:, 4], k, ii.astype(np.int32))
+        np.minimum.at(t[:, 5], k, jj.astype(np.int32))
+        np.maximum.at(t[:, 6], k, ii.astype(np.int32))
+        np.maximum.at(t[:, 7], k, jj.astype(np.int32))
+    chosen = np.array([(mask >> c) & 1 if c < C_ else 0 for c in range(256)], bool)
+    return t, int((chosen[cm] & (a < 0)).sum())
 
 
 # ---- outlines: the rings of an instance map, their polygons with holes, and a GeoJSON layer --------------------------------------
@@ -2840,6 +2991,23 @@ class ScenePool:
         keep += [marker, labels, areas, work]
         return inst, table, n
 
+    def _device_flood(self, cls_ptr: int, height_ptr, pix_stride: int, per_class: int, shape, C_, mask, conn, fp: dict, inst, table, cap, n,
+                      st, keep: list):
+        """rua_scene_flood of a resident instance map on stream `st`, in place: inst, and with them table and n (both may be
+        None), are the flooded ones afterwards.  fp is flood_params' dict.  Returns the device tensor stats int32 [2] (settled,
+        last_round); the work buffer is appended to `keep`."""
+        import torch
+        from . import _lib as L
+        H, W = shape
+        nwork = int(L.lib().raw("rua_scene_flood_work_bytes")(H, W))
+        work = torch.empty((nwork // 4,), dtype=torch.int32, device=self.device)
+        stats = torch.zeros((2,), dtype=torch.int32, device=self.device)
+        L.lib().call(_FLOOD, cls_ptr, height_ptr, pix_stride, per_class, H, W, C_, mask, conn, fp["rounds_per_level"], fp["floor"], fp["drain"],
+                     work.data_ptr(), nwork, inst.data_ptr(), None if table is None else table.data_ptr(), cap,
+                     None if table is None else n.data_ptr(), stats.data_ptr(), st)
+        keep.append(work)
+        return stats
+
     def _device_match(self, inst_p, table_p, inst_g, Ng: int, shape, st, keep: list):
         """rua_scene_instance_match of two resident instance maps on stream `st`: the device tensor int32 [rows of table_p][2]."""
         import torch
@@ -2854,14 +3022,18 @@ class ScenePool:
         return match
 
     def instances(self, maps, bound=None, dist=None, *, num_classes, classes, bound_below=128, dist_at_least=0, min_seed=1, radius=4,
-                  connectivity=4, max_instances=MAX_INSTANCES, want_map=True):
+                  connectivity=4, max_instances=MAX_INSTANCES, want_map=True, flood=None):
         """host_seed_map and host_instances of maps[s], a uint8 [H][W] class map per scene of the pool that came from a file (a None
         entry skips its scene and gives None), with bound[s] and dist[s], uint8 [H][W][C] maps or None, as a list of
         (inst int32 [H][W] or None without want_map, table int32 [n][8], n, ungrown): per scene one upload, rua_scene_seed_map,
         rua_scene_regions and rua_scene_instances on the current stream, and one fetch after all scenes were issued; a "cpu" pool
-        returns the host definitions.  ValueError naming both numbers if a scene holds more than max_instances seeds."""
+        returns the host definitions.  flood (True or a dict, flood_params): the grown instances are then flooded over their class
+        (host_flood; rua_scene_flood on the same stream) with dist[s] as the per-class height, without a height where it is None;
+        inst, table and ungrown are the flooded ones (flood_table), and each tuple gains a fifth element {"settled", "last_round",
+        "rounds"}.  ValueError naming both numbers if a scene holds more than max_instances seeds."""
         C_, mask, bb, da = check_seed_map(num_classes, classes, bound_below, dist_at_least)
         _, _, ms, r, conn, cap = check_instances(C_, classes, min_seed, radius, connectivity, max_instances)
+        fp = flood_params(flood)
         chosen = [c for c in range(C_) if (mask >> c) & 1]
         maps = self._check_region_maps(_INST, maps)
         heads = []
@@ -2877,6 +3049,11 @@ class ScenePool:
                 if m is not None:
                     marker = host_seed_map(m, heads[0][s], heads[1][s], num_classes=C_, classes=chosen, bound_below=bb, dist_at_least=da)
                     out[s] = host_instances(m, marker, num_classes=C_, classes=chosen, min_seed=ms, radius=r, connectivity=conn, max_instances=cap)
+                    if fp is not None:
+                        inst, settled, last = host_flood(m, heads[1][s], out[s][0], num_classes=C_, classes=chosen, connectivity=conn,
+                                                         rounds_per_level=fp["rounds_per_level"], floor=fp["floor"], drain=fp["drain"])
+                        table, ungrown = flood_table(inst, out[s][1], m, num_classes=C_, classes=chosen)
+                        out[s] = (inst, table, out[s][2], ungrown, {"settled": settled, "last_round": last, "rounds": fp["rounds"]})
         else:
             import torch
             with torch.cuda.device(self.device):
@@ -2891,9 +3068,17 @@ class ScenePool:
                     issued[s] = self._device_instances(dev[0].data_ptr(), None if dev[1] is None else dev[1].data_ptr(),
                                                        None if dev[2] is None else dev[2].data_ptr(), (H, W), C_, mask, bb, da, ms, r, conn,
                                                        min(cap, H * W), st, keep)
-                for s, (inst, table, n) in issued.items():
+                    if fp is not None:
+                        inst, table, n = issued[s]
+                        stats = self._device_flood(dev[0].data_ptr(), None if dev[2] is None else dev[2].data_ptr(), C_, 1, (H, W), C_, mask, conn,
+                                                   fp, inst, table, min(cap, H * W), n, st, keep)
+                        issued[s] += (stats,)
+                for s, (inst, table, n, *stats) in issued.items():
                     N, ungrown = (int(v) for v in n.cpu().numpy())
                     out[s] = (inst.cpu().numpy(), table[:min(N, cap)].cpu().numpy(), N, ungrown)
+                    if stats:
+                        settled, last = (int(v) for v in stats[0].cpu().numpy())
+                        out[s] += ({"settled": settled, "last_round": last, "rounds": fp["rounds"]},)
         for s, res in enumerate(out):
             if res is not None:
                 if res[2] > cap:
